@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--workload ns|c1|c2|c3|c3s|c4s|c4|c1g|hard|cliff|gmm|ea15k] [--no-others]
     python bench.py --openea EMB_DIR KG_DIR [--steps K] [--warmup W]      (real entity-alignment embeddings)
+    python bench.py ... --dump-outputs DIR      (also write what the last timed step computed: DIR/dist.npy, ind.npy, rows.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment LAUNCHES ITSELF: the parent (which never touches a
@@ -511,6 +512,42 @@ def run_workload(name, eng, comm, dist, rank, world, steps, warmup, check=True, 
     return summary, (source_h, target_h), res, source
 
 
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together
+
+
+def _host(x):
+    """numpy copy of an engine tensor (torch, any device) or a kiez_amd DeviceArray."""
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x.numpy())
+
+
+def dump_outputs(out_dir, res, comm=None, shard_rows=None):
+    """`--dump-outputs DIR`: what the timed path returned in its LAST timed step -- kneighbors' (dist, ind), every rank's shard in
+    rank order -- as DIR/dist.npy (float64), DIR/ind.npy (the target ids, float64: exact) and DIR/rows.npy (the source row of each
+    dumped row, float64).  Where the whole result exceeds DUMP_LIMIT_BYTES, a fixed, seeded sample of rows (ascending).
+    A collective when `comm` spans several ranks (every rank calls it; rank 0 writes)."""
+    d, i = res
+    if comm is not None:
+        d = comm.gather_rows_to0(d.contiguous(), shard_rows)
+        i = comm.gather_rows_to0(i.contiguous(), shard_rows)
+        if comm.rank != 0:
+            return None
+    d, i = _host(d), _host(i)
+    if d.dtype != np.float32:
+        d = d.astype(np.float64)
+    n, k = i.shape
+    per_row = k * (d.itemsize + 8) + 8
+    budget = DUMP_LIMIT_BYTES - 3 * 4096      # (the .npy headers)
+    rows = np.arange(n)
+    if n * per_row > budget:
+        rows = np.sort(np.random.RandomState(0).choice(n, budget // per_row, replace=False))
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "dist.npy", np.ascontiguousarray(d[rows]))
+    np.save(out / "ind.npy", i[rows].astype(np.float64))
+    np.save(out / "rows.npy", rows.astype(np.float64))
+    return {"dir": str(out), "rows": int(len(rows)), "of": int(n), "k": int(k)}
+
+
 def pmc_traffic(workload, s):
     """HBM-side bytes per launch of the dominant kernel from the committed rocprofv3 --pmc passes (profiles/pmc_traffic.json,
     tools/pmc_derive.py).  The counters are per KERNEL DISPATCH; a launch here (one kz_knn / kz_knn_dual call) sweeps its query
@@ -629,7 +666,7 @@ def run_openea(args):
             od, oi = O.kiez_pipeline(s64, t64, K, k, metric_c, 2, hub, {})
             chk["index_rows_identical"] = int((ind[rows] == oi[rows]).all(axis=1).sum())
         line["check"] = chk
-    return line
+    return line, res
 
 
 def job_cpu_baseline(args, comm, eng, s, source_dev, source_h, target_h):
@@ -679,6 +716,10 @@ def parse_args(argv=None):
                          "runs no broadcast (ShardedKiez.fit(target_from_rank0=False)) -- the A/B of the 0.8-1.2 GB transfer per step; "
                          "cached = broadcast by the first fit only (ShardedKiez(cache_target=True): the same target tensor in later fits "
                          "reuses every rank's replica -- the serving pattern: one index, many query batches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the main workload's last timed step returned (kneighbors' dist and ind, "
+                         "every rank's rows) to DIR/dist.npy, DIR/ind.npy, DIR/rows.npy; a fixed, seeded row sample above 64 MB. "
+                         "The inputs are seeded: the same arguments give the same inputs on every run")
     ap.add_argument("--launch-check", action="store_true",
                     help="NOT a measurement: run the launch / rendezvous / sharding / collective / reporting path of this script on "
                          "the CPU test engine (tests/cpu_engine.py) over gloo with a tiny shape; `value` is null.  For machines "
@@ -734,8 +775,10 @@ def main():
         comm = Comm(time_collectives=True)
         WORKLOADS["launch-check"] = (2000 if args.scaling == "weak" else 4001, 1500, 16, "euclidean", 5, 5, "CSLS", {},
                                      "launch check (CPU test engine over gloo; NOT a measurement)")
-        s, (src_h, tgt_h), _, src_dev = run_workload("launch-check", eng, comm, dist, rank, world, args.steps, args.warmup,
-                                                     check=not args.no_check, scaling=args.scaling, target_upload=args.target_upload)
+        s, (src_h, tgt_h), res, src_dev = run_workload("launch-check", eng, comm, dist, rank, world, args.steps, args.warmup,
+                                                       check=not args.no_check, scaling=args.scaling, target_upload=args.target_upload)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res, comm, s["shard_rows"])
         cpu = job_cpu_baseline(args, comm, eng, s, src_dev, src_h, tgt_h)
         if rank == 0:
             line = {"metric": METRIC, "recall_at_k": (s["check"] or {}).get("recall_at_k"),
@@ -767,7 +810,9 @@ def main():
     if args.openea is not None:
         if world != 1:
             raise SystemExit("--openea runs on one GPU")
-        line = run_openea(args)
+        line, res = run_openea(args)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
         sys.stdout.flush()
         emit(line, json_fd, args)
         return
@@ -779,9 +824,12 @@ def main():
         name, val = o.split("=")
         eng.ctx.set_option(name, float(val))
 
-    main_s, (source_h, target_h), _, source_dev = run_workload(args.workload, eng, comm, dist, rank, world, args.steps, args.warmup,
-                                                               check=not args.no_check, scaling=args.scaling,
-                                                               target_upload=args.target_upload)
+    main_s, (source_h, target_h), main_res, source_dev = run_workload(args.workload, eng, comm, dist, rank, world, args.steps, args.warmup,
+                                                                      check=not args.no_check, scaling=args.scaling,
+                                                                      target_upload=args.target_upload)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_res, comm, main_s["shard_rows"])      # (collective: every rank calls it)
+    del main_res
     cpu = job_cpu_baseline(args, comm, eng, main_s, source_dev, source_h, target_h)      # (collective: every rank calls it)
     del source_dev
     n_s, n_t, d, metric, K, k, hub, hub_kw, desc = WORKLOADS[args.workload]

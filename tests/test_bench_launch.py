@@ -137,3 +137,55 @@ def test_synthetic_rows_of_every_workload():
     c = np.argmin(((x[:, None, :] - centres[None]) ** 2).sum(-1), axis=1)
     spread = np.array([(x[c == j] - centres[j]).std() for j in range(40) if (c == j).sum() > 50])
     assert spread.max() / spread.min() > 8
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the (dist, ind) the timed path returned, every rank's rows in rank order, as float64 .npy files; the
+    same arguments give the same files (seeded inputs), and they are the oracle pipeline's result on those inputs."""
+    import importlib.util
+    import numpy as np
+    from oracle import kiez_oracle as O
+    outs = []
+    for run, gpus in (("a", 1), ("b", 1), ("c", 2)):
+        r = _run("--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--launch-check", "--no-cpu-baseline",
+                 "--detail", str(tmp_path / f"d_{run}.json"), "--dump-outputs", str(tmp_path / run))
+        assert r.returncode == 0, r.stderr[-4000:]
+        outs.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("dist", "ind", "rows")})
+    for o in outs:
+        assert all(v.dtype == np.float64 for v in o.values())
+    for n in ("dist", "ind", "rows"):
+        np.testing.assert_array_equal(outs[0][n], outs[1][n])
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n_s, n_t, d = 2000, 1500, 16          # (the launch check's shape, bench.main)
+    target = bench.synth_rows("launch-check", 77, n_t, d)
+    shards = [bench.synth_rows("launch-check", 0 if r == 0 else 1000 + r, n_s, d) for r in range(2)]
+    for o, src in ((outs[0], shards[0]), (outs[2], np.concatenate(shards))):
+        od, oi = O.kiez_pipeline(src, target, 5, 5, "euclidean", 2, "CSLS", {})
+        np.testing.assert_array_equal(o["rows"], np.arange(len(src)))
+        np.testing.assert_array_equal(o["ind"], oi)
+        np.testing.assert_allclose(o["dist"], od, rtol=1e-12, atol=0)
+
+
+def test_dump_outputs_samples_a_large_result_within_64_mb(tmp_path):
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, k = 500_000, 10                    # 80 MB as float64 dist + ind
+    dist = torch.arange(n * k, dtype=torch.float64).reshape(n, k)
+    ind = torch.arange(n * k, dtype=torch.int64).reshape(n, k) * 3
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, (dist, ind))
+    total = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert 0.9 * 64e6 < total <= 64e6
+    got = {n_: np.load(tmp_path / "a" / f"{n_}.npy") for n_ in ("dist", "ind", "rows")}
+    for n_, v in got.items():
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / f"{n_}.npy"))     # a fixed sample
+    rows = got["rows"].astype(np.int64)
+    assert (np.diff(rows) > 0).all() and rows[-1] < n
+    np.testing.assert_array_equal(got["dist"], dist.numpy()[rows])
+    np.testing.assert_array_equal(got["ind"], ind.numpy()[rows].astype(np.float64))

@@ -8,11 +8,11 @@ touches: four query chunks of 524288 rows per sweep, event buffers / logs sized 
       array_equal to the oracle's exact float64 search, `r_train` bit-equal, the final (dist, ind) equal to the oracle's CSLS
       transform + `_sort` on the sampled rows;
   (b) ALL rows equal to the concatenation of EIGHT `ShardedKiez` ranks (the north-star partitioning: source row-sharded, target
-      broadcast from rank 0, one all-to-all of the per-shard reverse lists, kz_merge_topk over eight real segments) run as
-      eight processes of the product engine on the one GPU of the box (collectives staged over gloo, tests/staged_comm.py).
+      broadcast from rank 0, one all-to-all of the per-shard reverse lists, kz_merge_topk over eight real segments) run on the
+      product engine on the one GPU of the box: four processes of two ranks each, one thread and one `HipEngine` per rank
+      (collectives staged over gloo, tests/staged_comm.py) -- with this test's own process, five processes hold the GPU.
 """
 import os
-import socket
 import subprocess
 import sys
 import warnings
@@ -80,49 +80,69 @@ def test_c4_full_size_against_the_oracle(c4_single):
     np.testing.assert_array_equal(dist[rows], sd)
 
 
+RANKS_PER_PROCESS = 2
+
 RANK_SCRIPT = r"""
-import os, sys, warnings
+import datetime, os, sys, threading, traceback, warnings
 sys.path.insert(0, %(root)r)
 os.environ["KIEZ_AMD_WITH_TORCH"] = "1"
 import numpy as np
 import torch
 import torch.distributed as dist
-rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-dist.init_process_group("gloo", rank=rank, world_size=world)
+from kiez_amd import _native
 from kiez_amd.distributed import HipEngine, ShardedKiez
 from tests import c4_data as D
 from tests.staged_comm import StagedComm
 warnings.simplefilter("ignore")
-assert world == D.N_SHARDS
-eng = HipEngine(0)
-shard = D.source_shard(rank)
-target = D.target_rows() if rank == 0 else None
-comm = StagedComm()
-sk = ShardedKiez(n_candidates=D.K, algorithm_kwargs={"metric": "euclidean"}, hubness="CSLS", engine=eng, comm=comm)
-sk.fit(shard, target)
-assert sk.shared and eng.last_stats["dual"] == 1 and eng.last_stats_reverse["dual"] == 1, (eng.last_stats, eng.last_stats_reverse)
-dd, ii = sk.kneighbors(D.K)
-np.save(os.path.join(%(out)r, f"dist_{rank}.npy"), dd.cpu().numpy())
-np.save(os.path.join(%(out)r, f"ind_{rank}.npy"), ii.cpu().numpy())
-if rank == 0:
-    np.save(os.path.join(%(out)r, "r_t.npy"), sk.state["r_t"].cpu().numpy())
-dist.barrier()
-dist.destroy_process_group()
-print("C4_RANK_OK", rank)
+first, count = int(sys.argv[1]), int(sys.argv[2])
+_native.load()
+torch.cuda.init()
+
+
+def rank_main(rank):
+    store = dist.FileStore(os.path.join(%(out)r, "store"), D.N_SHARDS)
+    comm = StagedComm(dist.ProcessGroupGloo(store, rank, D.N_SHARDS, datetime.timedelta(minutes=20)))
+    eng = HipEngine(0)
+    shard = D.source_shard(rank)
+    target = D.target_rows() if rank == 0 else None
+    sk = ShardedKiez(n_candidates=D.K, algorithm_kwargs={"metric": "euclidean"}, hubness="CSLS", engine=eng, comm=comm)
+    sk.fit(shard, target)
+    assert sk.shared and eng.last_stats["dual"] == 1 and eng.last_stats_reverse["dual"] == 1, (eng.last_stats, eng.last_stats_reverse)
+    dd, ii = sk.kneighbors(D.K)
+    np.save(os.path.join(%(out)r, f"dist_{rank}.npy"), dd.cpu().numpy())
+    np.save(os.path.join(%(out)r, f"ind_{rank}.npy"), ii.cpu().numpy())
+    if rank == 0:
+        np.save(os.path.join(%(out)r, "r_t.npy"), sk.state["r_t"].cpu().numpy())
+
+
+def guarded(rank):
+    try:
+        rank_main(rank)
+    except BaseException:
+        # (the other ranks wait inside a collective for this one: end the whole process, its peers see the group break)
+        sys.stderr.write(f"rank {rank}:\n{traceback.format_exc()}")
+        sys.stderr.flush()
+        os._exit(1)
+
+
+threads = [threading.Thread(target=guarded, args=(r,)) for r in range(first, first + count)]
+for t in threads:
+    t.start()
+for t in threads:
+    t.join()
+for r in range(first, first + count):
+    print("C4_RANK_OK", r)
 """
 
 
 def test_c4_full_size_equals_eight_sharded_ranks(c4_single, tmp_path):
     from tests import c4_data as D
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
     script = RANK_SCRIPT % {"root": str(ROOT), "out": str(tmp_path)}
     procs = []
-    for r in range(D.N_SHARDS):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(D.N_SHARDS), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", script], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    for first in range(0, D.N_SHARDS, RANKS_PER_PROCESS):
+        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+        procs.append(subprocess.Popen([sys.executable, "-c", script, str(first), str(RANKS_PER_PROCESS)], env=env,
+                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     try:
         for p in procs:
@@ -131,8 +151,9 @@ def test_c4_full_size_equals_eight_sharded_ranks(c4_single, tmp_path):
         for p in procs:
             if p.poll() is None:
                 p.kill()
-    for r, (p, (so_, se_)) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0 and f"C4_RANK_OK {r}" in so_, f"rank {r}:\n{so_[-2000:]}\n{se_[-4000:]}"
+    for i, (p, (so_, se_)) in enumerate(zip(procs, outs)):
+        ranks = range(i * RANKS_PER_PROCESS, (i + 1) * RANKS_PER_PROCESS)
+        assert p.returncode == 0 and all(f"C4_RANK_OK {r}" in so_ for r in ranks), f"ranks {list(ranks)}:\n{so_[-2000:]}\n{se_[-4000:]}"
     res = c4_single
     np.testing.assert_array_equal(np.load(tmp_path / "r_t.npy"), res["r_train"])
     for r in range(D.N_SHARDS):

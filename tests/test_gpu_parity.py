@@ -120,9 +120,11 @@ def _data(n_s, n_t, d, dtype, seed=0, gauss=False):
 @pytest.mark.parametrize("tag", ["none", "csls", "ls", "nicdm", "mp_normal", "mp_empiric", "dsl"])
 def test_oracle_parity(n_s, n_t, d, dtype, metric, K, tag):
     from oracle import kiez_oracle as O
-    if tag == "dsl" and metric == "cosine":
-        pytest.skip("DSL rejects cosine (dis_sim.py:47-61)")
     hname, kw = HUB[tag]
+    if tag == "dsl" and metric == "cosine":
+        with pytest.raises(ValueError, match="DisSimLocal only supports squared Euclidean"):    # as the reference (dis_sim.py:47-61)
+            _kiez(K, metric, 2, hname, kw)
+        return
     s, t = _data(n_s, n_t, d, dtype, seed=n_s + d)
     if metric == "cosine":
         s, t = s.astype(np.float64), t.astype(np.float64)

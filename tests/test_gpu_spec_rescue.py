@@ -28,14 +28,14 @@ def _gmm(rows, d, seed):
     return (x / np.sqrt((x * x).sum(axis=1, keepdims=True))).astype(np.float32)
 
 
-def _few_failures(ctx, qm, ym, k, lo=1, hi=16):
+def _few_failures(ctx, qm, ym, k, lo=1, hi=16, exclude_self=False):
     """An `eps_scale` at which the first pass leaves between lo and hi rows uncertified (speculation off while looking)."""
     from kiez_amd import _native as N
     ctx.set_option("spec_rows", 0)
     scale, lo_s, hi_s = 1.0, None, None
     for _ in range(40):
         ctx.set_option("eps_scale", scale)
-        _, _, st = N.knn(ctx, qm, ym, k)
+        _, _, st = N.knn(ctx, qm, ym, k, exclude_self=exclude_self)
         n = st["n_first_pass_fail"]
         if lo <= n <= hi:
             return scale, n
@@ -100,16 +100,7 @@ def test_self_query_rows_and_row_ranges(ctx):
     from oracle import kiez_oracle as O
     x = _gmm(7000, 200, 5)
     xm = N.DeviceMatrix(ctx, x, "euclidean")
-    ctx.set_option("spec_rows", 0)
-    scale = None
-    for s in (1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0):
-        ctx.set_option("eps_scale", s)
-        _, _, st = N.knn(ctx, xm, xm, 10, exclude_self=True)
-        if 1 <= st["n_first_pass_fail"] <= 16:
-            scale = s
-            break
-    if scale is None:
-        pytest.skip("no handful of uncertified rows on this data")
+    _few_failures(ctx, xm, xm, 10, exclude_self=True)
     ctx.set_option("spec_rows", 64)
     dist, ind, st = N.knn(ctx, xm, xm, 10, exclude_self=True)
     assert st["n_spec_rows"] == st["n_first_pass_fail"] > 0
