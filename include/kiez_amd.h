@@ -42,8 +42,13 @@ enum { KZ_F32 = 0, KZ_F64 = 1 };
  * kernels; 3 .. 5 (the rest of the Minkowski family: manhattan = cityblock = l1, chebyshev, minkowski with any p >= 1 set by
  * kz_matrix_set_minkowski_p) have no inner-product form: a register-tiled VALU kernel computes scikit-learn's generic
  * DistanceMetric expression (sklearn/metrics/_dist_metrics.pyx.tp: |x_j - y_j| in the input dtype, float64 accumulation in
- * feature order, result rounded to the input dtype), the exact float64 selection kernels pick the neighbours */
-enum { KZ_EUCLIDEAN = 0, KZ_SQEUCLIDEAN = 1, KZ_COSINE = 2, KZ_MANHATTAN = 3, KZ_CHEBYSHEV = 4, KZ_MINKOWSKI = 5 };
+ * feature order, result rounded to the input dtype), the exact float64 selection kernels pick the neighbours.
+ * 6 .. 9 take the same VALU route with scikit-learn's expressions of the other per-feature metrics: braycurtis and seuclidean
+ * (DistanceMetric: the difference in the input dtype, float64 sums in feature order, ranking value rounded to the input dtype;
+ * seuclidean needs kz_matrix_set_seuclidean_v and returns sqrt of its ranking value), correlation and hamming (scipy's cdist:
+ * float64 throughout; correlation = 1 - centred cosine, NaN for a constant row, ranked after every finite value). */
+enum { KZ_EUCLIDEAN = 0, KZ_SQEUCLIDEAN = 1, KZ_COSINE = 2, KZ_MANHATTAN = 3, KZ_CHEBYSHEV = 4, KZ_MINKOWSKI = 5,
+       KZ_BRAYCURTIS = 6, KZ_SEUCLIDEAN = 7, KZ_CORRELATION = 8, KZ_HAMMING = 9 };
 
 typedef struct kz_ctx kz_ctx;       /* one GPU + one HIP stream + scratch                                   */
 typedef struct kz_matrix kz_matrix; /* an embedding matrix resident in HBM: raw rows, MFMA-packed tiles, norms */
@@ -124,6 +129,10 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
                      int metric, kz_matrix** out);
 /* metric KZ_MINKOWSKI: the exponent p >= 1 (default 2; both matrices of a search must agree). */
 int kz_matrix_set_minkowski_p(kz_matrix* m, double p);
+/* metric KZ_SEUCLIDEAN: the per-feature variances V[0 .. d) (host memory, copied), every one finite and > 0 -- stricter than
+ * scikit-learn, which divides by whatever V holds.  Refused for any other metric.  A search whose two matrices do not hold
+ * bit-identical V (or no V) fails with KZ_ERR_INVALID. */
+int kz_matrix_set_seuclidean_v(kz_matrix* m, const double* V, int64_t d);
 int kz_matrix_destroy(kz_matrix* m);
 int kz_matrix_shape(const kz_matrix* m, int64_t* n, int64_t* d, int* dtype, int* metric);
 

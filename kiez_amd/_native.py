@@ -25,8 +25,10 @@ _lock = threading.Lock()
 
 KZ_F32, KZ_F64 = 0, 1
 KZ_EUCLIDEAN, KZ_SQEUCLIDEAN, KZ_COSINE, KZ_MANHATTAN, KZ_CHEBYSHEV, KZ_MINKOWSKI = 0, 1, 2, 3, 4, 5
+KZ_BRAYCURTIS, KZ_SEUCLIDEAN, KZ_CORRELATION, KZ_HAMMING = 6, 7, 8, 9
 METRIC_IDS = {"euclidean": KZ_EUCLIDEAN, "sqeuclidean": KZ_SQEUCLIDEAN, "cosine": KZ_COSINE, "manhattan": KZ_MANHATTAN,
-              "chebyshev": KZ_CHEBYSHEV, "minkowski": KZ_MINKOWSKI}
+              "chebyshev": KZ_CHEBYSHEV, "minkowski": KZ_MINKOWSKI, "braycurtis": KZ_BRAYCURTIS, "seuclidean": KZ_SEUCLIDEAN,
+              "correlation": KZ_CORRELATION, "hamming": KZ_HAMMING}
 
 
 def split_metric(metric: str):
@@ -94,6 +96,7 @@ SYMBOLS = [
     ("kz_matrix_create", C.c_int, [_P, _P, C.c_int, _I64, _I64, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_matrix_destroy", C.c_int, [_P]),
     ("kz_matrix_set_minkowski_p", C.c_int, [_P, C.c_double]),
+    ("kz_matrix_set_seuclidean_v", C.c_int, [_P, _P, _I64]),
     ("kz_matrix_shape", C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("kz_knn", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, C.POINTER(KnnStats)]),
     ("kz_knn_dual", C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P, C.POINTER(KnnStats), C.POINTER(KnnStats)]),
@@ -291,10 +294,11 @@ class DeviceMatrix:
     """kz_matrix: an embedding matrix in HBM (exact rows + float64 norms + MFMA operand images: float32 and split-bf16)."""
 
     def __init__(self, ctx: Context, data, metric: str, device_ptr: Optional[int] = None, shape=None, dtype=None,
-                 borrow: bool = False, keepalive=None, rows_only: bool = False):
+                 borrow: bool = False, keepalive=None, rows_only: bool = False, V=None):
         """`device_ptr` + `borrow=True`: zero-copy -- the matrix reads the caller's HBM buffer in place (kz_matrix_create
         rows_on_device = 2); `keepalive` (the tensor / array that owns it) is held until the matrix is destroyed and must
-        not be modified meanwhile (the reference holds its inputs the same way, neighbor_algorithm_base.py:95-96)."""
+        not be modified meanwhile (the reference holds its inputs the same way, neighbor_algorithm_base.py:95-96).
+        `V`: metric 'seuclidean', the per-feature variances (kz_matrix_set_seuclidean_v; both matrices of a search need the same)."""
         self.ctx = ctx
         self.metric = metric
         metric, mink_p = split_metric(metric)
@@ -323,6 +327,9 @@ class DeviceMatrix:
         self.handle = h
         if mink_p is not None:
             _check(ctx.lib.kz_matrix_set_minkowski_p(h, mink_p), "kz_matrix_set_minkowski_p")
+        if V is not None:
+            v = np.ascontiguousarray(V, dtype=np.float64)
+            _check(ctx.lib.kz_matrix_set_seuclidean_v(h, v.ctypes.data_as(_P), v.shape[0]), "kz_matrix_set_seuclidean_v")
 
     def __del__(self):
         h = getattr(self, "handle", None)

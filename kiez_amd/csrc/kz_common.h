@@ -142,6 +142,9 @@ struct kz_matrix {
     int64_t n, d;
     int dtype, metric;
     double mink_p;    // KZ_MINKOWSKI: the exponent (kz_matrix_set_minkowski_p; 2 by default)
+    double* seu_v;    // KZ_SEUCLIDEAN: device [d] per-feature variances (kz_matrix_set_seuclidean_v; NULL until set)
+    double* seu_v_host;  // ... and their host copy (the bit-identical check between the two matrices of a search)
+    double* corr;     // KZ_CORRELATION: device [n][2] float64 row mean and norm of the centred row (kz_pack.hip: kz_corr_rows_kernel)
     int64_t n_tiles;  // ceil(n / 128)
     int kg;           // d_pad / 4 (number of 4-wide k-groups), d_pad = round_up(d, 16)
     int kg_bf;        // same for the split-bf16 image (currently equal to kg)
@@ -280,6 +283,37 @@ __device__ __forceinline__ double kz_wave_dot_normalized(const T* __restrict__ a
     return kz_wave_sum(acc);
 }
 
+// numpy's pairwise summation of a contiguous run converted to float64 (numpy/_core/src/umath/loops_utils.h.src,
+// DOUBLE_pairwise_sum): < 8 elements sequential, <= 128 eight interleaved accumulators, else split.
+template <typename T>
+__device__ double kz_np_pairwise_sum(const T* a, int n) {
+    if (n < 8) {
+        double res = 0.0;
+        for (int i = 0; i < n; ++i) res += (double)a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
+        int i;
+        for (i = 8; i < n - (n % 8); i += 8) {
+            r0 += (double)a[i + 0];
+            r1 += (double)a[i + 1];
+            r2 += (double)a[i + 2];
+            r3 += (double)a[i + 3];
+            r4 += (double)a[i + 4];
+            r5 += (double)a[i + 5];
+            r6 += (double)a[i + 6];
+            r7 += (double)a[i + 7];
+        }
+        double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+        for (; i < n; ++i) res += (double)a[i];
+        return res;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    return kz_np_pairwise_sum(a, n2) + kz_np_pairwise_sum(a + n2, n - n2);
+}
+
 // The exact float64 value the search ranks an index row by (squared euclidean distance / cosine distance): the re-rank of
 // kz_knn_finalize_kernel, the exact fallback and kz_pair_values all evaluate THIS expression on the canonical dot product.
 // Minkowski family beyond p = 2 (KZ_MANHATTAN, KZ_CHEBYSHEV, KZ_MINKOWSKI): scikit-learn's generic DistanceMetric
@@ -309,26 +343,110 @@ __device__ __forceinline__ double kz_family_add(double acc, double term) {
 __host__ __device__ __forceinline__ int kz_family_p_int(int metric, double p, bool f32_inputs) {
     return (metric == KZ_MINKOWSKI && f32_inputs && (p == 3.0 || p == 4.0)) ? (int)p : 0;
 }
-template <typename T, int METRIC>
-__device__ __forceinline__ double kz_family_value_seq_m(const T* __restrict__ a, const T* __restrict__ b, int d, double p, int p_int) {
-    double acc = 0.0;
-    for (int j = 0; j < d; ++j) acc = kz_family_add<METRIC>(acc, kz_family_term<T, METRIC>(a[j], b[j], p, p_int));
-    return sizeof(T) == 4 ? (double)(float)acc : acc;
+
+// The per-feature metrics beyond the Minkowski family (KZ_BRAYCURTIS .. KZ_HAMMING) take the same route and the same tiles.  A
+// pair's state is two float64 accumulators (a, b); kz_family_step adds feature j of a pair, kz_family_finish turns (a, b) into the
+// ranking value.  Every expression is scikit-learn's (tests/metric_restate.py restates them and checks them bit for bit):
+//   Minkowski family  a = kz_family_add(a, kz_family_term(x, y))                                          value a (rounded to T)
+//   braycurtis        a += |x - y| (difference in T), b += |x| + |y| (float64)   (DistanceMetric)       value a / b, 0 if b == 0 (rounded to T)
+//   seuclidean        a += t t / V_j with t = x - y in T (a correctly rounded division; no reciprocal)   value a (rounded to T);
+//                     the distance returned is sqrt(a) (kz_output_distance)
+//   correlation       x, y are the CENTRED float64 values (x - mean(x), one float64 subtraction, scipy's cdist); even features
+//                     into a, odd ones into b: scipy's dot product in two interleaved partial sums, the odd tail term added after
+//                     a + b by the caller (kz_family_finish's `tail`); value 1 - clip(dot / (|u| |v|)), NaN (constant row) ranked as
+//                     +inf -- the selection kernels order (+inf, row) after every finite value, kz_output_distance turns it back
+//   hamming           a += x != y                                                   (scipy's cdist)     value a / d
+// kz_family_step's x / y: the input dtype T, except for correlation (the centred float64 values).
+template <typename T, int METRIC, int CHAIN = -1, typename S>
+__device__ __forceinline__ void kz_family_step(double& a, double& b, S x, S y, double p, int p_int, double v_j, bool odd) {
+    if constexpr (METRIC <= KZ_MINKOWSKI) {
+        a = kz_family_add<METRIC>(a, kz_family_term<T, METRIC, CHAIN>(x, y, p, p_int));
+    } else if constexpr (METRIC == KZ_BRAYCURTIS) {
+        const T df = x - y;
+        a += fabs((double)df);
+        b += fabs((double)x) + fabs((double)y);
+    } else if constexpr (METRIC == KZ_SEUCLIDEAN) {
+        const T df = x - y;
+        const double t = (double)df;
+        a += t * t / v_j;
+    } else if constexpr (METRIC == KZ_CORRELATION) {
+        if (odd)
+            b += x * y;
+        else
+            a += x * y;
+    } else {
+        a += x != y ? 1.0 : 0.0;
+    }
 }
-// (one thread, one pair)
+// (tail: correlation, odd d -- the product of the centred last features; nx, ny: correlation, the norms of the centred rows)
+template <typename T, int METRIC>
+__device__ __forceinline__ double kz_family_finish(double a, double b, int d, double tail, double nx, double ny) {
+    if constexpr (METRIC == KZ_BRAYCURTIS) {
+        const double v = b != 0.0 ? a / b : 0.0;
+        return sizeof(T) == 4 ? (double)(float)v : v;
+    } else if constexpr (METRIC == KZ_CORRELATION) {
+        double s = a + b;
+        if (d & 1) s += tail;
+        double c = s / (nx * ny);
+        if (fabs(c) > 1.0) c = copysign(1.0, c);
+        const double v = 1.0 - c;
+        return v == v ? v : INFINITY;
+    } else if constexpr (METRIC == KZ_HAMMING) {
+        return a / (double)d;
+    } else {
+        return sizeof(T) == 4 ? (double)(float)a : a;
+    }
+}
+// per-search state of the metrics beyond the Minkowski family, for one pair: V (seuclidean), the (mean, centred norm) of both rows
+// (correlation)
+struct kz_family_pair_args {
+    const double* V;
+    const double* xc;
+    const double* yc;
+};
+template <typename T, int METRIC>
+__device__ __forceinline__ double kz_family_value_seq_m(const T* __restrict__ a, const T* __restrict__ b, int d, double p, int p_int,
+                                                        const kz_family_pair_args& ex) {
+    double acc = 0.0, acc2 = 0.0;
+    if constexpr (METRIC == KZ_CORRELATION) {
+        const int de = d & ~1;
+        for (int j = 0; j < de; ++j)
+            kz_family_step<T, METRIC>(acc, acc2, (double)a[j] - ex.xc[0], (double)b[j] - ex.yc[0], p, p_int, 1.0, (j & 1) != 0);
+        const double tail = (d & 1) ? ((double)a[d - 1] - ex.xc[0]) * ((double)b[d - 1] - ex.yc[0]) : 0.0;
+        return kz_family_finish<T, METRIC>(acc, acc2, d, tail, ex.xc[1], ex.yc[1]);
+    } else {
+        for (int j = 0; j < d; ++j)
+            kz_family_step<T, METRIC>(acc, acc2, a[j], b[j], p, p_int, METRIC == KZ_SEUCLIDEAN ? ex.V[j] : 1.0, false);
+        return kz_family_finish<T, METRIC>(acc, acc2, d, 0.0, 0.0, 0.0);
+    }
+}
+// (one thread, one pair; ex: only the metrics beyond the Minkowski family read it)
 template <typename T>
-__device__ __forceinline__ double kz_family_value_seq(const T* __restrict__ a, const T* __restrict__ b, int d, int metric, double p) {
+__device__ __forceinline__ double kz_family_value_seq(const T* __restrict__ a, const T* __restrict__ b, int d, int metric, double p,
+                                                      const kz_family_pair_args& ex = {nullptr, nullptr, nullptr}) {
     const int p_int = kz_family_p_int(metric, p, sizeof(T) == 4);
-    if (metric == KZ_MANHATTAN) return kz_family_value_seq_m<T, KZ_MANHATTAN>(a, b, d, p, p_int);
-    if (metric == KZ_CHEBYSHEV) return kz_family_value_seq_m<T, KZ_CHEBYSHEV>(a, b, d, p, p_int);
-    return kz_family_value_seq_m<T, KZ_MINKOWSKI>(a, b, d, p, p_int);
+    if (metric == KZ_MANHATTAN) return kz_family_value_seq_m<T, KZ_MANHATTAN>(a, b, d, p, p_int, ex);
+    if (metric == KZ_CHEBYSHEV) return kz_family_value_seq_m<T, KZ_CHEBYSHEV>(a, b, d, p, p_int, ex);
+    if (metric == KZ_BRAYCURTIS) return kz_family_value_seq_m<T, KZ_BRAYCURTIS>(a, b, d, p, p_int, ex);
+    if (metric == KZ_SEUCLIDEAN) return kz_family_value_seq_m<T, KZ_SEUCLIDEAN>(a, b, d, p, p_int, ex);
+    if (metric == KZ_CORRELATION) return kz_family_value_seq_m<T, KZ_CORRELATION>(a, b, d, p, p_int, ex);
+    if (metric == KZ_HAMMING) return kz_family_value_seq_m<T, KZ_HAMMING>(a, b, d, p, p_int, ex);
+    return kz_family_value_seq_m<T, KZ_MINKOWSKI>(a, b, d, p, p_int, ex);
+}
+// Search-time agreement of the two matrices beyond the metric id: the Minkowski exponent, seuclidean's V (set on both, bit-identical)
+static inline bool kz_metric_params_match(const kz_matrix* a, const kz_matrix* b) {
+    if (a->metric != b->metric || a->mink_p != b->mink_p) return false;
+    if (a->metric != KZ_SEUCLIDEAN) return true;
+    return a->seu_v_host && b->seu_v_host && a->d == b->d && memcmp(a->seu_v_host, b->seu_v_host, (size_t)a->d * sizeof(double)) == 0;
 }
 
 // The exact float64 value the search ranks an index row by (squared euclidean distance / cosine distance / the Minkowski family's
 // reduced distance): the re-rank of kz_knn_finalize_kernel, the exact fallback and kz_pair_values all evaluate THIS expression.
 template <typename T>
 __device__ __forceinline__ double kz_exact_value(const T* q, const T* y, double qs, double ys, int d, int metric, int lane, double p = 2.0) {
-    if (metric >= KZ_MANHATTAN) return kz_family_value_seq<T>(q, y, d, metric, p);   // (every lane the whole pair: no fused kernel ranks by this metric)
+    // (every lane the whole pair: no fused kernel ranks by this metric.  Metrics 6 .. 9 never come here -- their per-search state
+    //  travels in kz_family_pair_args: the tiled kernel and kz_pair_values call kz_family_value_seq themselves)
+    if (metric >= KZ_MANHATTAN) return kz_family_value_seq<T>(q, y, d, metric, p);
     if (metric == KZ_COSINE) {
         const double sim = kz_wave_dot_normalized(q, qs, y, ys, d, lane);
         double v = 1.0 - sim;  // sklearn cosine_distances: S *= -1; S += 1; clip(0, 2)

@@ -9,35 +9,7 @@
 //   _sort           kiez/hubness_reduction/base.py:72-87
 #include "kz_common.h"
 
-// numpy's pairwise summation of a contiguous float64 run (numpy/_core/src/umath/loops_utils.h.src,
-// DOUBLE_pairwise_sum): < 8 elements sequential, <= 128 eight interleaved accumulators, else split.
-__device__ double kz_np_pairwise_sum(const double* a, int n) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    if (n <= 128) {
-        double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-        int i;
-        for (i = 8; i < n - (n % 8); i += 8) {
-            r0 += a[i + 0];
-            r1 += a[i + 1];
-            r2 += a[i + 2];
-            r3 += a[i + 3];
-            r4 += a[i + 4];
-            r5 += a[i + 5];
-            r6 += a[i + 6];
-            r7 += a[i + 7];
-        }
-        double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return kz_np_pairwise_sum(a, n2) + kz_np_pairwise_sum(a + n2, n - n2);
-}
+// (kz_np_pairwise_sum, numpy's pairwise summation: kz_common.h)
 
 // same summation applied to (a[i] - c)^2 (np.nanstd: subtract mean, square, sum; numpy/lib/_nanfunctions_impl.py)
 __device__ double kz_np_pairwise_sumsq_dev(const double* a, int n, double c) {

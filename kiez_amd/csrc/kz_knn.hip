@@ -13,6 +13,7 @@
 #include <vector>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "kz_common.h"
 #include "kz_floor.h"
@@ -254,6 +255,10 @@ __device__ __forceinline__ double kz_output_distance(double v, int metric, doubl
     // (Minkowski family: the ranking value is the reduced distance; scikit-learn converts at the end,
     //  MinkowskiDistance._rdist_to_dist: rdist ** (1 / p), rounded to the input dtype -- measured on scikit-learn 1.7.2)
     if (metric == KZ_MINKOWSKI) return sizeof(T) == 4 ? (double)(float)pow(v, 1.0 / p) : pow(v, 1.0 / p);
+    // (seuclidean: SEuclideanDistance._rdist_to_dist, sqrt of the ranking value -- already rounded to the input dtype -- rounded
+    //  again; correlation: the constant row's NaN, ranked as +inf (kz_family_finish), is NaN again)
+    if (metric == KZ_SEUCLIDEAN) return sizeof(T) == 4 ? (double)(float)sqrt(v) : sqrt(v);
+    if (metric == KZ_CORRELATION && v == INFINITY) return NAN;
     if (metric == KZ_EUCLIDEAN) {
         // ArgKmin32 converts the surrogate with the float32 metric object: (double)sqrtf((float)d2)
         // (_argkmin.pyx.tp:285-295 with INPUT_DTYPE_t = float32); ArgKmin64 uses sqrt in float64.
@@ -1325,32 +1330,53 @@ static int kz_launch_exact_lanes(kz_ctx* ctx, const int* fl, int b0, int nb, int
 // (the conversion carries the abs modifier), add -- three VALU operations; every thread adds the terms of its pairs in feature
 // order (kz_common.h: kz_family_term / kz_family_add), which is scikit-learn's order.  VALU-bound: 15 k x 15 k x 300 float32,
 // manhattan: see DESIGN section 9.  Output: the same [batch][n_i] float64 value matrix kz_exact_dist_kernel writes.
+// Metrics 6 .. 9 (braycurtis, seuclidean, correlation, hamming: kz_common.h, kz_family_step) run on the same tiles: a pair's
+// state is two float64 accumulators.  Seuclidean reads V_j at a wave-uniform address; correlation stages the CENTRED float64 values
+// (x - row mean, one subtraction per element as the tile is loaded, not per pair), features [0, d & ~1) go through the tiles in
+// even / odd pairs and the odd tail term is added at the end.
 template <typename T, int METRIC, int DK, int CHAIN>
 __global__ __launch_bounds__(256) void kz_family_dist_kernel(const int* __restrict__ fail_list, int batch0, int nb, int64_t q_begin,
                                                              const T* __restrict__ qraw, const T* __restrict__ yraw, int64_t n_i, int d,
-                                                             double p, int p_int, double* __restrict__ vals) {
-    __shared__ __attribute__((aligned(32))) T sQ[DK][64];
-    __shared__ __attribute__((aligned(32))) T sY[DK][64];
+                                                             double p, int p_int, double* __restrict__ vals,
+                                                             const double* __restrict__ V = nullptr, const double* __restrict__ qcorr = nullptr,
+                                                             const double* __restrict__ ycorr = nullptr) {
+    using S = typename std::conditional<METRIC == KZ_CORRELATION, double, T>::type;   // (staged type)
+    __shared__ __attribute__((aligned(32))) S sQ[DK][64];
+    __shared__ __attribute__((aligned(32))) S sY[DK][64];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     const int64_t y0 = (int64_t)blockIdx.x * 64;
     const int b0 = blockIdx.y * 64;
     // staging: thread t copies DK / 4 consecutive features of row (t & 63) of both tiles (rows past the end: the last row again)
     const int lrow = t & 63, lseg = (t >> 6) * (DK / 4);
     const int bq = b0 + lrow < nb ? b0 + lrow : nb - 1;
-    const T* __restrict__ qp = qraw + (q_begin + fail_list[batch0 + bq]) * (int64_t)d;
-    const T* __restrict__ yp = yraw + (y0 + lrow < n_i ? y0 + lrow : n_i - 1) * (int64_t)d;
-    double acc[4][4];
+    const int64_t qrow_l = q_begin + fail_list[batch0 + bq];
+    const int64_t yrow_l = y0 + lrow < n_i ? y0 + lrow : n_i - 1;
+    const T* __restrict__ qp = qraw + qrow_l * (int64_t)d;
+    const T* __restrict__ yp = yraw + yrow_l * (int64_t)d;
+    // correlation: the features the tiles cover (the odd tail is added at the end) and the staged rows' means
+    const int d_tiles = METRIC == KZ_CORRELATION ? (d & ~1) : d;
+    double mq = 0.0, my = 0.0;
+    if constexpr (METRIC == KZ_CORRELATION) {
+        mq = qcorr[2 * qrow_l];
+        my = ycorr[2 * yrow_l];
+    }
+    double acc[4][4], acc2[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc[a][c] = 0.0;
-    for (int k0 = 0; k0 < d; k0 += DK) {
-        T rq[DK / 4], ry[DK / 4];
+        for (int c = 0; c < 4; ++c) acc[a][c] = acc2[a][c] = 0.0;
+    for (int k0 = 0; k0 < d_tiles; k0 += DK) {
+        S rq[DK / 4], ry[DK / 4];
 #pragma unroll
         for (int u = 0; u < DK / 4; ++u) {
             const int k = k0 + lseg + u;
-            rq[u] = k < d ? qp[k] : (T)0;
-            ry[u] = k < d ? yp[k] : (T)0;   // (|0 - 0| = 0 changes no sum and no maximum)
+            if constexpr (METRIC == KZ_CORRELATION) {
+                rq[u] = k < d_tiles ? (double)qp[k] - mq : 0.0;   // (0 x 0 adds +0: changes no sum)
+                ry[u] = k < d_tiles ? (double)yp[k] - my : 0.0;
+            } else {
+                rq[u] = k < d ? qp[k] : (T)0;
+                ry[u] = k < d ? yp[k] : (T)0;   // (|0 - 0| = 0 changes no sum and no maximum; nor 0 != 0, nor 0 0 / 1)
+            }
         }
         __syncthreads();   // (the previous chunk has been read)
 #pragma unroll
@@ -1359,28 +1385,61 @@ __global__ __launch_bounds__(256) void kz_family_dist_kernel(const int* __restri
             sY[lseg + u][lrow] = ry[u];
         }
         __syncthreads();
-#pragma unroll 4
-        for (int j = 0; j < DK; ++j) {
-            T q4[4], y4[4];
+        if constexpr (METRIC == KZ_CORRELATION) {
+            // (fully unrolled: the parity of a feature -- which partial sum it goes to -- is known at compile time)
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                q4[a] = sQ[j][ty * 4 + a];
-                y4[a] = sY[j][tx * 4 + a];
+            for (int j = 0; j < DK; ++j) {
+                S q4[4], y4[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    q4[a] = sQ[j][ty * 4 + a];
+                    y4[a] = sY[j][tx * 4 + a];
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) kz_family_step<T, METRIC, CHAIN>(acc[a][c], acc2[a][c], q4[a], y4[c], p, p_int, 1.0, (j & 1) != 0);
             }
+        } else {
+#pragma unroll 4
+            for (int j = 0; j < DK; ++j) {
+                // (seuclidean: a wave-uniform read of V_j; past the end 1: the padded term is 0 / 1)
+                const double v_j = METRIC == KZ_SEUCLIDEAN ? (k0 + j < d ? V[k0 + j] : 1.0) : 1.0;
+                S q4[4], y4[4];
 #pragma unroll
-            for (int a = 0; a < 4; ++a)
+                for (int a = 0; a < 4; ++a) {
+                    q4[a] = sQ[j][ty * 4 + a];
+                    y4[a] = sY[j][tx * 4 + a];
+                }
 #pragma unroll
-                for (int c = 0; c < 4; ++c) acc[a][c] = kz_family_add<METRIC>(acc[a][c], kz_family_term<T, METRIC, CHAIN>(q4[a], y4[c], p, p_int));
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) kz_family_step<T, METRIC, CHAIN>(acc[a][c], acc2[a][c], q4[a], y4[c], p, p_int, v_j, false);
+            }
         }
     }
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int b = b0 + ty * 4 + a;
         if (b >= nb) continue;
+        double nq = 0.0, tq = 0.0;
+        const T* qrow = nullptr;
+        if constexpr (METRIC == KZ_CORRELATION) {
+            const int64_t qr = q_begin + fail_list[batch0 + b];
+            nq = qcorr[2 * qr + 1];
+            qrow = qraw + qr * (int64_t)d;
+            if (d & 1) tq = (double)qrow[d - 1] - qcorr[2 * qr];
+        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int64_t i = y0 + tx * 4 + c;
-            if (i < n_i) vals[(int64_t)b * n_i + i] = sizeof(T) == 4 ? (double)(float)acc[a][c] : acc[a][c];
+            if (i >= n_i) continue;
+            double ny = 0.0, tail = 0.0;
+            if constexpr (METRIC == KZ_CORRELATION) {
+                ny = ycorr[2 * i + 1];
+                if (d & 1) tail = tq * ((double)yraw[i * (int64_t)d + d - 1] - ycorr[2 * i]);
+            }
+            vals[(int64_t)b * n_i + i] = kz_family_finish<T, METRIC>(acc[a][c], acc2[a][c], d, tail, nq, ny);
         }
     }
 }
@@ -1390,13 +1449,22 @@ static void kz_launch_family_dist(kz_ctx* ctx, const int* fl, int b0, int nb, in
     constexpr int DK = sizeof(T) == 4 ? 32 : 16;
     const dim3 grid((unsigned)((index->n + 63) / 64), (unsigned)((nb + 63) / 64));
     const int p_int = kz_family_p_int(index->metric, index->mink_p, sizeof(T) == 4);
-#define KZ_FAMILY_LAUNCH(M, C)                                                                                                          \
-    hipLaunchKernelGGL((kz_family_dist_kernel<T, M, DK, C>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin, (const T*)query->raw, \
-                       (const T*)index->raw, index->n, (int)index->d, index->mink_p, p_int, vals)
+#define KZ_FAMILY_LAUNCH_DK(M, C, DKM)                                                                                                    \
+    hipLaunchKernelGGL((kz_family_dist_kernel<T, M, DKM, C>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin, (const T*)query->raw, \
+                       (const T*)index->raw, index->n, (int)index->d, index->mink_p, p_int, vals, index->seu_v, query->corr, index->corr)
+#define KZ_FAMILY_LAUNCH(M, C) KZ_FAMILY_LAUNCH_DK(M, C, DK)
     if (index->metric == KZ_MANHATTAN)
         KZ_FAMILY_LAUNCH(KZ_MANHATTAN, -1);
     else if (index->metric == KZ_CHEBYSHEV)
         KZ_FAMILY_LAUNCH(KZ_CHEBYSHEV, -1);
+    else if (index->metric == KZ_BRAYCURTIS)
+        KZ_FAMILY_LAUNCH(KZ_BRAYCURTIS, -1);
+    else if (index->metric == KZ_SEUCLIDEAN)
+        KZ_FAMILY_LAUNCH(KZ_SEUCLIDEAN, -1);
+    else if (index->metric == KZ_CORRELATION)
+        KZ_FAMILY_LAUNCH_DK(KZ_CORRELATION, -1, 16);   // (float64 tiles whatever the input dtype)
+    else if (index->metric == KZ_HAMMING)
+        KZ_FAMILY_LAUNCH(KZ_HAMMING, -1);
     else if (p_int == 3)
         KZ_FAMILY_LAUNCH(KZ_MINKOWSKI, 3);     // (float32 inputs, p = 3 or 4: a product with one rounding, no pow() in the kernel)
     else if (p_int == 4)
@@ -1404,6 +1472,7 @@ static void kz_launch_family_dist(kz_ctx* ctx, const int* fl, int b0, int nb, in
     else
         KZ_FAMILY_LAUNCH(KZ_MINKOWSKI, -1);
 #undef KZ_FAMILY_LAUNCH
+#undef KZ_FAMILY_LAUNCH_DK
 }
 
 // First level of the exact selection on a long row: the k_eff smallest (value, index row) pairs of every CHUNK of KZ_EXACT_CHUNK
@@ -2413,6 +2482,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                (long long)index->d);
     KZ_REQUIRE(query->dtype == index->dtype, "kz_knn: query and index must have the same dtype");
     KZ_REQUIRE(query->metric == index->metric && query->mink_p == index->mink_p, "kz_knn: query and index were packed for different metrics");
+    KZ_REQUIRE(kz_metric_params_match(query, index), "kz_knn: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index");
     KZ_REQUIRE(q_begin >= 0 && q_count >= 0 && q_begin + q_count <= query->n, "kz_knn: query row range out of bounds");
     KZ_REQUIRE(k >= 1, "kz_knn: Expected k > 0. Got %d", k);
     // kp_min >= 1000: lists of kp_min - 1000, and NOT the short-list route (the re-search of rows that route could not certify:

@@ -603,6 +603,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     KZ_REQUIRE(a->d == b->d, "kz_knn_dual: feature dimensions differ (%lld vs %lld)", (long long)a->d, (long long)b->d);
     KZ_REQUIRE(a->dtype == b->dtype, "kz_knn_dual: the matrices must have the same dtype");
     KZ_REQUIRE(a->metric == b->metric, "kz_knn_dual: the matrices were packed for different metrics");
+    KZ_REQUIRE(kz_metric_params_match(a, b), "kz_knn_dual: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on both matrices");
     KZ_REQUIRE(k >= 1, "kz_knn_dual: Expected k > 0. Got %d", k);
     KZ_REQUIRE((int64_t)k <= a->n && (int64_t)k <= b->n,
                "kz_knn_dual: Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld", k,

@@ -15,7 +15,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void kz_pair_values_kernel(const T* __restrict__ qraw, const double* __restrict__ qsqn,
                                                              int64_t q_begin, int64_t q_count, const T* __restrict__ yraw,
                                                              const double* __restrict__ ysqn, int64_t n_i, int d, int metric, double p,
-                                                             const int64_t* __restrict__ ind, int K, double* __restrict__ val) {
+                                                             const int64_t* __restrict__ ind, int K, double* __restrict__ val,
+                                                             const double* __restrict__ V, const double* __restrict__ qcorr,
+                                                             const double* __restrict__ ycorr) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= q_count) return;
@@ -27,7 +29,9 @@ __global__ __launch_bounds__(256) void kz_pair_values_kernel(const T* __restrict
         // tiled distance kernel the search ranked by, so that the values that travel between GPUs ARE the search's values
         for (int c = threadIdx.x & 63; c < K; c += 64) {
             const int64_t yi = ind[r * (int64_t)K + c];
-            val[r * (int64_t)K + c] = (yi >= 0 && yi < n_i) ? kz_family_value_seq<T>(q, yraw + yi * (int64_t)d, d, metric, p) : INFINITY;
+            const bool ok = yi >= 0 && yi < n_i;
+            const kz_family_pair_args ex = {V, qcorr ? qcorr + 2 * qrow : nullptr, ycorr && ok ? ycorr + 2 * yi : nullptr};
+            val[r * (int64_t)K + c] = ok ? kz_family_value_seq<T>(q, yraw + yi * (int64_t)d, d, metric, p, ex) : INFINITY;
         }
         return;
     }
@@ -102,16 +106,19 @@ int kz_pair_values(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t
     KZ_REQUIRE(query && index && !query->raw_only && !index->raw_only, "kz_pair_values: null or rows-only matrix");
     KZ_REQUIRE(query->d == index->d && query->dtype == index->dtype && query->metric == index->metric && query->mink_p == index->mink_p,
                "kz_pair_values: query/index mismatch (d %lld vs %lld)", (long long)query->d, (long long)index->d);
+    KZ_REQUIRE(kz_metric_params_match(query, index), "kz_pair_values: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index");
     KZ_REQUIRE(q_begin >= 0 && q_count >= 0 && q_begin + q_count <= query->n && k >= 1, "kz_pair_values: bad row range");
     KZ_HIP(hipSetDevice(ctx->device));
     if (q_count == 0) return KZ_OK;
     const dim3 grid((unsigned)((q_count + 3) / 4));
     if (query->dtype == KZ_F32)
         hipLaunchKernelGGL(kz_pair_values_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)query->raw, query->sqn, q_begin,
-                           q_count, (const float*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val);
+                           q_count, (const float*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val,
+                           index->seu_v, query->corr, index->corr);
     else
         hipLaunchKernelGGL(kz_pair_values_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double*)query->raw, query->sqn, q_begin,
-                           q_count, (const double*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val);
+                           q_count, (const double*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val,
+                           index->seu_v, query->corr, index->corr);
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }

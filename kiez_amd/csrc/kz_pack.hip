@@ -15,6 +15,9 @@
 //   bf16x2 (second tier, kz_knn_bf16.h) packed_bf[tile][slice][plane][row][8]     8 KiB per slice
 //          planes hi(k 0-7), hi(k 8-15), lo(k 0-7), lo(k 8-15) with hi = bf16(x), lo = bf16(x - hi).
 //   fp32   (third tier, kz_knn.hip)     packed[tile][kgroup][row][4]              8 KiB per slice (4 kgroups)
+#include <cfloat>
+#include <cstdlib>
+
 #include "kz_common.h"
 
 // round-to-nearest-even float32 -> bf16 bits (finite inputs)
@@ -366,6 +369,31 @@ __global__ __launch_bounds__(256) void kz_pack_h_kernel(const T* __restrict__ ra
     }
 }
 
+// KZ_CORRELATION: per row, scipy's centring state (cdist 'correlation': the rows in float64, u = x - x.mean(), then the cosine of
+// the centred rows): [2r] the mean (numpy's pairwise sum / d), [2r + 1] |u| = sqrt(u.u) with u.u in scipy's two interleaved
+// partial sums (kz_common.h: kz_family_step) -- the norms the distance kernel divides by.  One thread per row.
+template <typename T>
+__global__ __launch_bounds__(256) void kz_corr_rows_kernel(const T* __restrict__ raw, int64_t n, int d, double* __restrict__ corr) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const T* x = raw + r * (int64_t)d;
+    const double mean = kz_np_pairwise_sum(x, d) / (double)d;
+    double s0 = 0.0, s1 = 0.0;
+    const int de = d & ~1;
+    for (int j = 0; j < de; j += 2) {
+        const double u0 = (double)x[j] - mean, u1 = (double)x[j + 1] - mean;
+        s0 += u0 * u0;
+        s1 += u1 * u1;
+    }
+    double s = s0 + s1;
+    if (d & 1) {
+        const double u = (double)x[d - 1] - mean;
+        s += u * u;
+    }
+    corr[2 * r] = mean;
+    corr[2 * r + 1] = sqrt(s);
+}
+
 static int kz_pack_blocks(int64_t n_pad) {
     const int64_t b = (n_pad + 3) / 4;
     return (int)(b < 4096 ? b : 4096);   // (32768: no faster -- 100k x 128: norms 46 -> 68 us, pack 62 -> 64 us)
@@ -676,7 +704,7 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
     KZ_REQUIRE(d <= 65536, "kz_matrix_create: d=%lld too large", (long long)d);
     KZ_REQUIRE(n < ((int64_t)1 << 31) - 256, "kz_matrix_create: n=%lld exceeds the int32 row-id range", (long long)n);
     KZ_REQUIRE(dtype == KZ_F32 || dtype == KZ_F64, "kz_matrix_create: dtype must be KZ_F32 or KZ_F64");
-    KZ_REQUIRE(metric >= KZ_EUCLIDEAN && metric <= KZ_MINKOWSKI, "kz_matrix_create: unknown metric %d", metric);
+    KZ_REQUIRE(metric >= KZ_EUCLIDEAN && metric <= KZ_HAMMING, "kz_matrix_create: unknown metric %d", metric);
     KZ_REQUIRE(rows_on_device >= 0 && rows_on_device <= 3, "kz_matrix_create: rows_on_device must be 0, 1, 2 or 3");
     KZ_HIP(hipSetDevice(ctx->device));
     kz_matrix* m = new kz_matrix();
@@ -740,6 +768,22 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
         kz_set_error("kz_matrix_create: norm kernel failed: %s", hipGetErrorString(e));
         return fail(KZ_ERR_HIP);
     }
+    if (metric == KZ_CORRELATION) {
+        if (kz_pool_alloc(ctx, (size_t)n * 16, (void**)&m->corr) != KZ_OK) {
+            kz_set_error("kz_matrix_create: out of device memory (correlation row state)");
+            return fail(KZ_ERR_NOMEM);
+        }
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        if (dtype == KZ_F32)
+            hipLaunchKernelGGL(kz_corr_rows_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, (const float*)m->raw, n, (int)d, m->corr);
+        else
+            hipLaunchKernelGGL(kz_corr_rows_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)m->raw, n, (int)d, m->corr);
+        e = hipGetLastError();
+        if (e != hipSuccess) {
+            kz_set_error("kz_matrix_create: correlation row kernel failed: %s", hipGetErrorString(e));
+            return fail(KZ_ERR_HIP);
+        }
+    }
     // Host rows: the copy above was synchronous anyway, so the finiteness verdict is checked here and the caller gets
     // KZ_ERR_NONFINITE from the call that passed the data (scikit-learn rejects such input in fit, too).  Device rows:
     // NOTHING is waited for -- the matrix is usable at once, the verdict stays in d_stats and is checked by the first kz_knn
@@ -765,7 +809,10 @@ int kz_matrix_destroy(kz_matrix* m) {
         kz_pool_free(m->ctx, m->bias, 0);
         kz_pool_free(m->ctx, m->sqn, 0);
         kz_pool_free(m->ctx, m->d_stats, 0);
+        kz_pool_free(m->ctx, m->corr, 0);
+        kz_pool_free(m->ctx, m->seu_v, 0);
     }
+    free(m->seu_v_host);
     delete m;
     return KZ_OK;
 }
@@ -775,6 +822,40 @@ int kz_matrix_set_minkowski_p(kz_matrix* m, double p) {
     KZ_REQUIRE(m->metric == KZ_MINKOWSKI, "kz_matrix_set_minkowski_p: the matrix was not created for KZ_MINKOWSKI");
     KZ_REQUIRE(p >= 1.0 && p < 1e6, "kz_matrix_set_minkowski_p: p must be >= 1 (got %g)", p);
     m->mink_p = p;
+    return KZ_OK;
+}
+
+int kz_matrix_set_seuclidean_v(kz_matrix* m, const double* V, int64_t d) {
+    KZ_REQUIRE(m != nullptr && V != nullptr, "kz_matrix_set_seuclidean_v: null argument");
+    KZ_REQUIRE(m->metric == KZ_SEUCLIDEAN, "kz_matrix_set_seuclidean_v: the matrix was not created for KZ_SEUCLIDEAN");
+    KZ_REQUIRE(d == m->d, "kz_matrix_set_seuclidean_v: V has %lld entries, the matrix %lld features", (long long)d, (long long)m->d);
+    for (int64_t j = 0; j < d; ++j)
+        KZ_REQUIRE(V[j] > 0.0 && V[j] <= DBL_MAX, "kz_matrix_set_seuclidean_v: V[%lld] = %g (every variance must be finite and > 0)",
+                   (long long)j, V[j]);
+    kz_ctx* ctx = m->ctx;
+    const size_t bytes = (size_t)d * sizeof(double);
+    double* host = (double*)malloc(bytes);
+    if (!host) {
+        kz_set_error("kz_matrix_set_seuclidean_v: out of host memory");
+        return KZ_ERR_NOMEM;
+    }
+    memcpy(host, V, bytes);
+    KZ_HIP(hipSetDevice(ctx->device));
+    if (!m->seu_v && kz_pool_alloc(ctx, bytes, (void**)&m->seu_v) != KZ_OK) {
+        free(host);
+        kz_set_error("kz_matrix_set_seuclidean_v: out of device memory");
+        return KZ_ERR_NOMEM;
+    }
+    // (synchronous: V is the caller's host buffer, and a search already enqueued may still read the previous V)
+    const hipError_t e = hipMemcpyAsync(m->seu_v, host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
+    if (e2 != hipSuccess) {
+        free(host);
+        kz_set_error("kz_matrix_set_seuclidean_v: copy failed: %s", hipGetErrorString(e2));
+        return KZ_ERR_HIP;
+    }
+    free(m->seu_v_host);
+    m->seu_v_host = host;
     return KZ_OK;
 }
 

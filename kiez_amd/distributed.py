@@ -28,7 +28,7 @@ from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 
-from .neighbors import canonical_metric
+from .neighbors import canonical_metric, seuclidean_V
 
 _P = C.c_void_p
 
@@ -80,13 +80,13 @@ class HipEngine:
         return t.cpu().numpy()
 
     # -- compute ----------------------------------------------------------------------------------
-    def matrix(self, rows, metric: str, rows_only: bool = False):
+    def matrix(self, rows, metric: str, rows_only: bool = False, V=None):
         N = self.N
         assert rows.dtype in (self.torch.float32, self.torch.float64)
         dt = np.float32 if rows.dtype == self.torch.float32 else np.float64
         # zero-copy: the matrix reads the tensor's HBM in place and keeps the tensor alive
         return N.DeviceMatrix(self.ctx, None, metric, device_ptr=rows.data_ptr(), shape=tuple(rows.shape), dtype=dt, borrow=True,
-                              keepalive=rows, rows_only=rows_only)
+                              keepalive=rows, rows_only=rows_only, V=None if rows_only else V)
 
     def knn(self, qm, q_begin: int, q_count: int, im, k: int, exclude_self: bool):
         torch, N = self.torch, self.N
@@ -564,6 +564,7 @@ class ShardedKiez:
         akw = dict(algorithm_kwargs or {})
         self.K = int(akw.get("n_candidates", n_candidates))
         self.metric = canonical_metric(akw.get("metric", "minkowski"), akw.get("p", 2))
+        self.V = seuclidean_V(self.metric, akw.get("metric_params"))   # (seuclidean: every rank's matrices carry the same V)
         key = hubness.lower() if isinstance(hubness, str) else hubness
         if key not in _HUB:
             raise KeyError(f"Invalid hubness reduction: {hubness}")
@@ -592,6 +593,18 @@ class ShardedKiez:
         self._tgt_replica = None       # ... and the tensor it landed in (rank 0: the caller's tensor, kept alive)
 
     # -- fit -----------------------------------------------------------------------------------------
+    def _matrix(self, eng, rows):
+        # (V only where there is one: an engine's matrix() need not know the keyword otherwise)
+        return eng.matrix(rows, self.metric) if self.V is None else eng.matrix(rows, self.metric, V=self.V)
+
+    def _merge_key(self, d):
+        """The merge key of returned distances: the distance itself; correlation's NaN (a constant row) as the +inf the search
+        ranked it by (kz_merge_topk orders finite keys only by value)."""
+        return _torch().nan_to_num(d, nan=float("inf")) if self.metric == "correlation" else d
+
+    def _merge_unkey(self, d):
+        return _torch().where(_torch().isinf(d), float("nan"), d) if self.metric == "correlation" else d
+
     def fit(self, source_shard, target=None, single_source: bool = False, target_from_rank0: bool = True):
         eng, comm = self.engine, self.comm
         src = eng.to_engine(source_shard)
@@ -673,12 +686,12 @@ class ShardedKiez:
         S_own = None
         try:
             if not need_full_source:
-                S_own = eng.matrix(src, self.metric)     # (beside the broadcast: touches the shard only)
+                S_own = self._matrix(eng, src)     # (beside the broadcast: touches the shard only)
         finally:
             comm.broadcast_end(bcast)                    # (also on an error: the transfer is always awaited)
-        self.T = eng.matrix(tgt, self.metric)
+        self.T = self._matrix(eng, tgt)
         if need_full_source:
-            self.S = self.T if self.single else eng.matrix(src_full, self.metric)
+            self.S = self.T if self.single else self._matrix(eng, src_full)
             self.q_begin = self.s_begin   # forward queries are a row range of the full source matrix
         else:
             self.S = S_own
@@ -702,8 +715,10 @@ class ShardedKiez:
                     # ranked by (euclidean: sqrt, for float32 inputs through float32) -- the exact ordering values too: merging
                     # by rounded distances would break ties differently from one GPU.  ONE all-to-all either way.
                     gids = (i_rev + self.s_begin).contiguous()
-                    lossless = self.metric in ("sqeuclidean", "cosine", "manhattan", "chebyshev")   # the returned distance IS the ordering value
-                    planes = [d_rev, gids.view(torch.float64)] if lossless else \
+                    # (the returned distance IS the ordering value; correlation's NaN -- a constant row -- is keyed as the +inf it
+                    #  ranks as, _merge_key)
+                    lossless = self.metric in ("sqeuclidean", "cosine", "manhattan", "chebyshev", "braycurtis", "correlation", "hamming")
+                    planes = [self._merge_key(d_rev), gids.view(torch.float64)] if lossless else \
                         [eng.pair_values(self.T, 0, self.n_t, self.S, i_rev), d_rev, gids.view(torch.float64)]
                     parts = comm.all_to_all_rows(torch.stack(planes, dim=1), t_counts)          # [W, t_count, 2 or 3, K]
 
@@ -711,12 +726,14 @@ class ShardedKiez:
                         return parts[:, :, c].permute(1, 0, 2).reshape(t_count, W * K).contiguous()
                     if lossless:
                         d_t2s, i_t2s = eng.merge_topk(seg(0), seg(1).view(torch.int64), None, W, K, K)
+                        d_t2s = self._merge_unkey(d_t2s)
                     else:
                         d_t2s, i_t2s = eng.merge_topk(seg(0), seg(2).view(torch.int64), seg(1), W, K, K)
                 else:
-                    parts = comm.all_to_all_rows(d_rev, t_counts)                               # [W, t_count, K]
+                    parts = comm.all_to_all_rows(self._merge_key(d_rev), t_counts)              # [W, t_count, K]
                     merged = parts.permute(1, 0, 2).reshape(t_count, W * K).contiguous()
                     d_t2s, i_t2s = eng.merge_topk(merged, None, None, W, K, K)                  # (ids unused by these kinds)
+                    d_t2s = self._merge_unkey(d_t2s)
                 if self.hub == "dsl":
                     # the centroids average SOURCE ROWS of all shards (dis_sim.py:96-101): the shards are gathered after all,
                     # but only for this gather kernel -- the second sweep stays saved

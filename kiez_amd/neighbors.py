@@ -157,7 +157,8 @@ def canonical_metric(metric: str, p=2) -> str:
 
     scikit-learn's own aliases (sklearn/metrics/_dist_metrics.pyx.tp, DistanceMetric.get_metric): minkowski with p = 1 / 2 / inf IS
     manhattan / euclidean / chebyshev; `p` is ignored for every other metric name.  Euclidean, squared euclidean and cosine run the
-    fused MFMA kernels; manhattan, chebyshev and minkowski(p) have no inner-product form and run on a register-tiled VALU kernel + the exact selection."""
+    fused MFMA kernels; manhattan, chebyshev and minkowski(p) have no inner-product form and run on a register-tiled VALU kernel + the exact selection,
+    as do braycurtis, seuclidean, correlation and hamming (scikit-learn's brute-force expressions, bit for bit)."""
     if metric == "minkowski":
         if not isinstance(p, (int, float, np.integer, np.floating)) or isinstance(p, bool) or not p >= 1:
             raise ValueError(f"metric='minkowski' needs p >= 1 on the MI355X exact backend (got p={p!r})")
@@ -174,10 +175,30 @@ def canonical_metric(metric: str, p=2) -> str:
         return "euclidean"
     if metric in ("manhattan", "cityblock", "l1"):
         return "manhattan"
-    if metric in ("sqeuclidean", "cosine", "chebyshev"):
+    if metric in ("sqeuclidean", "cosine", "chebyshev", "braycurtis", "seuclidean", "correlation", "hamming"):
         return metric
     raise ValueError(
         f"metric='{metric}' is not implemented by the MI355X exact backend; valid metrics: {SklearnNN.valid_metrics}")
+
+
+def seuclidean_V(metric_c: str, metric_params):
+    """The variances V of metric 'seuclidean' from `metric_params` ({"V": array_like}, scikit-learn's spelling) as a float64 vector;
+    None for every other metric."""
+    if metric_c != "seuclidean":
+        return None
+    if not metric_params:
+        # (scikit-learn raises TypeError at the first search, when it builds SEuclideanDistance without V; here at once)
+        raise TypeError("metric='seuclidean' needs metric_params={'V': array_like of length n_features}")
+    if not isinstance(metric_params, dict) or set(metric_params) != {"V"}:
+        raise NotImplementedError(f"metric_params={metric_params!r} is not implemented by the MI355X exact backend "
+                                  "(only metric='seuclidean' with metric_params={'V': array_like})")
+    V = np.asarray(metric_params["V"], dtype=np.float64)
+    if V.ndim != 1:
+        raise ValueError(f"metric_params['V'] must be one-dimensional, got shape {V.shape}")
+    if not (np.all(np.isfinite(V)) and np.all(V > 0)):
+        # (scikit-learn divides by whatever V holds; here every variance must be finite and > 0)
+        raise ValueError("metric_params['V']: every variance must be finite and > 0 on the MI355X exact backend")
+    return np.ascontiguousarray(V)
 
 
 class SklearnNN(NNAlgorithm):
@@ -189,7 +210,8 @@ class SklearnNN(NNAlgorithm):
     distance + top-k pass on the GPU.
     """
 
-    valid_metrics = ["chebyshev", "cityblock", "cosine", "euclidean", "l1", "l2", "manhattan", "minkowski", "sqeuclidean"]
+    valid_metrics = ["braycurtis", "chebyshev", "cityblock", "correlation", "cosine", "euclidean", "hamming", "l1", "l2", "manhattan",
+                     "minkowski", "seuclidean", "sqeuclidean"]
     # numpy arrays as in the reference; additionally arrays already resident in HBM (zero-copy fit)
     _ALLOWED_INPUT_TYPES = (np.ndarray, N.DeviceArray)
 
@@ -202,8 +224,10 @@ class SklearnNN(NNAlgorithm):
         self.metric_params = metric_params
         self.device = device
         self._metric_c = canonical_metric(metric, p)
-        if metric_params:
-            raise NotImplementedError(f"metric_params={metric_params!r} is not implemented by the MI355X exact backend")
+        if metric_params and self._metric_c != "seuclidean":
+            raise NotImplementedError(f"metric_params={metric_params!r} is not implemented by the MI355X exact backend "
+                                      "(only metric='seuclidean' with metric_params={'V': array_like})")
+        self._V = seuclidean_V(self._metric_c, metric_params)   # seuclidean: the per-feature variances, float64
         if isinstance(n_candidates, (int, np.integer)) and n_candidates > N.MAX_NEIGHBORS - 1:
             raise NotImplementedError(f"n_candidates={n_candidates} exceeds the {N.MAX_NEIGHBORS - 1} neighbours per query the "
                                       "MI355X exact backend supports")
@@ -240,6 +264,10 @@ class SklearnNN(NNAlgorithm):
             value = (value,)
         super()._check_input_types(tuple(None if _is_tensor(x) else x for x in value))
 
+    def _check_V(self, shape):
+        if self._V is not None and self._V.shape[0] != shape[1]:
+            raise ValueError(f"metric_params['V'] has {self._V.shape[0]} entries, the data {shape[1]} features")
+
     def _make_matrix(self, data, dtype=None) -> N.DeviceMatrix:
         if _is_tensor(data):
             torch = _torch_if_loaded()
@@ -255,22 +283,26 @@ class SklearnNN(NNAlgorithm):
             t = t.contiguous()
             if t.device.index != self.ctx.device:
                 raise ValueError(f"tensor lives on cuda:{t.device.index}, the NN backend on device {self.ctx.device}")
+            self._check_V(tuple(t.shape))
             torch.cuda.current_stream(t.device).synchronize()   # the producer stream is not ours
             # zero-copy: the matrix reads the tensor's HBM in place and keeps it alive (the reference, too, only keeps
             # references to its inputs, neighbor_algorithm_base.py:95-96: they must not be modified while fitted)
             return N.DeviceMatrix(self.ctx, None, self._metric_c, device_ptr=t.data_ptr(), shape=tuple(t.shape),
-                                  dtype=np.float32 if t.dtype == torch.float32 else np.float64, borrow=True, keepalive=t)
+                                  dtype=np.float32 if t.dtype == torch.float32 else np.float64, borrow=True, keepalive=t,
+                                  V=self._V)
         if isinstance(data, N.DeviceArray):
             if len(data.shape) != 2 or data.dtype not in (np.float32, np.float64):
                 raise ValueError("device inputs must be 2D float32/float64 arrays")
             if dtype is not None and data.dtype != dtype:
                 raise ValueError(f"device input has dtype {data.dtype}, the index has {dtype}")
+            self._check_V(data.shape)
             return N.DeviceMatrix(self.ctx, None, self._metric_c, device_ptr=data.ptr.value, shape=data.shape,
-                                  dtype=data.dtype, borrow=True, keepalive=data)
+                                  dtype=data.dtype, borrow=True, keepalive=data, V=self._V)
         arr = self._prepare(data)
         if dtype is not None and arr.dtype != dtype:
             arr = arr.astype(dtype)
-        return N.DeviceMatrix(self.ctx, arr, self._metric_c)
+        self._check_V(arr.shape)
+        return N.DeviceMatrix(self.ctx, arr, self._metric_c, V=self._V)
 
     def _fit(self, data, is_source: bool):
         """Replaces SklearnNN._fit (sklearn_nearest_neighbors.py:83-94): upload + norms + MFMA tile packing."""
