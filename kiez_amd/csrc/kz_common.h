@@ -96,8 +96,21 @@ void kz_pool_free(kz_ctx* ctx, void* ptr, size_t bytes);
 // Shift and scale shared by the fp16 images of the matrices that are searched against each other (kz_pack.hip):
 // distances are translation invariant, so both sides are centred with ONE vector mu (the column mean of the first index
 // of the pair) and scaled by ONE power of two S into the fp16 range.  Reference counted: images keep it alive.
+// Slices (16 features) of the fp16 image of a matrix with kg k-groups: d_pad / 16 -- rounded up to a multiple of 8 beyond 32
+// slices (the wide-row builds of the fp16 kernel, kz_knn_h_inst.h, exist for 32, 40, 48, 56 and 64 slices only; the padding
+// slices are zero, and zero products add exactly nothing to the float32 accumulators).
+__host__ __device__ __forceinline__ int kz_h_nsr(int kg) {
+    const int s = kg / 4;
+    return s <= 32 ? s : (s + 7) & ~7;
+}
+// The fp16 tier exists for 2 .. 24 slices (d <= 384) and 32 .. 64 slices (d = 497 .. 1024); 25 .. 31 run on float32 operands.
+__host__ __device__ __forceinline__ bool kz_h_slices_ok(int kg) {
+    const int s = kg / 4;
+    return (s >= 2 && s <= 24) || (s >= 32 && s <= 64);
+}
+
 struct kz_center {
-    float* d_mu;      // [d_pad16] float32 shift (zero padded)
+    float* d_mu;      // [16 kz_h_nsr(kg)] float32 shift (zero padded)
     double* d_scale;  // device {S, 1 / S^2}
     int refs;
 };

@@ -2565,7 +2565,8 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
 
     const int metric = index->metric;
     const int n_ytiles = (dual && dual->n_ytiles > 0) ? dual->n_ytiles : (int)index->n_tiles;
-    const int n_slices = index->kg / 4;
+    // (slices of the fp16 image: kz_h_nsr pads 32 .. 64 to a multiple of 8 -- the other tiers never read n_slices beyond 24)
+    const int n_slices = kz_h_nsr(index->kg);
     // rounding bound factors.  float32 operands: (d_pad + 16) 2^-24 covers the d+1 step fma chain, the float32 rounding of
     // the bias and (float64 inputs) of the operands; 1e-12 covers the float64 re-rank's own rounding.  fp16 operands: the
     // float32 accumulation of d_pad exact products + bias in an unspecified order, (n + 16) u doubled to allow for
@@ -2577,7 +2578,14 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     // ---- tier of this call ------------------------------------------------------------------------------------------
     const int precision = precision_override >= 0 ? precision_override : ctx->precision;
     int tier = KZ_TIER_F32;
-    if (precision != 1 && n_slices >= 2 && n_slices <= 24 && query->kg == index->kg) tier = precision == 2 ? KZ_TIER_BF : KZ_TIER_H;
+    // (d = 497 .. 1024, 32 .. 64 slices: the fp16 tier's wide-row builds -- and no split-bf16 tier: precision = 2 runs on float32
+    //  operands there, and so does every row the fp16 pass leaves that would have gone to the split-bf16 operands: esc_bf)
+    const bool bf_ok = n_slices >= 2 && n_slices <= 24 && query->kg == index->kg;
+    const bool esc_bf = ctx->esc_bf && bf_ok;
+    if (precision != 1 && kz_h_slices_ok(index->kg) && query->kg == index->kg) {
+        if (precision != 2) tier = KZ_TIER_H;
+        else if (bf_ok) tier = KZ_TIER_BF;
+    }
     if (exact_only) tier = KZ_TIER_F32;   // (nothing is packed or launched for it below)
     if (tier == KZ_TIER_H) {
         const int rc = kz_himage_ensure(query, index);
@@ -2702,7 +2710,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         }
         kz_pool_free(ctx, plist_keep, 0);
         if (hard) {
-            tier = KZ_TIER_BF;
+            tier = bf_ok ? KZ_TIER_BF : KZ_TIER_F32;   // (wide rows: no split-bf16 operands, the float32 ones)
             // (data this hard for fp16 is hard for the split-bf16 operands, too, wherever the keys are dense: lists of 64 from the
             //  start -- 300k x 300k x 96, k = 10, clusters of very different spread: rows searched again 135 k -> 51 k, call 170 -> 110 ms)
             if (KSEL == 0 && KP < 64) KP = 64;
@@ -3083,7 +3091,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         // tight clusters: 579 -> 540 ms cluster by cluster, 528 -> 348 ms shuffled; nearly every row of that set needs better operands).
         int tier_next = tier;
         if (!dual && tier != KZ_TIER_F32 && (int64_t)n_fail * 4 > cq_count)
-            tier_next = (tier == KZ_TIER_H && ctx->esc_bf && long_pieces == 0) ? KZ_TIER_BF : KZ_TIER_F32;
+            tier_next = (tier == KZ_TIER_H && esc_bf && long_pieces == 0) ? KZ_TIER_BF : KZ_TIER_F32;
         // A HANDFUL of rows left by the split-bf16 operands skips the float32-operand kernel: that kernel sweeps the whole index for
         // one query tile in at most eight pieces -- 2.2 ms on 300 k rows of d = 64 whatever the row count -- while the exact kernels
         // cost ~35 us a row there (both scale with n d): bench.py "hard", ~20 rows per direction and step: 60.6 -> see r05_notes.
@@ -3122,7 +3130,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             // what the re-search asks for: (operand tier, list length) -- never what this pass just tried
             int next_prec, next_kp;
             if (!widen) {   // fp16 with its longest lists, or fp16 altogether, has failed: better operands, this call's own list length
-                next_prec = (tier == KZ_TIER_H && ctx->esc_bf && (long_pieces == 0 || fp16_hard)) ? 2 : 1;
+                next_prec = (tier == KZ_TIER_H && esc_bf && (long_pieces == 0 || fp16_hard)) ? 2 : 1;
                 // (the float32 operands are the LAST approximate tier and their a-priori bound is the loosest: with this call's own
                 //  list length -- 16 for k = 10 -- the K'-th key lies a handful of keys below the k-th and inside the bound wherever
                 //  the keys are dense; lists of 64 certify such rows instead of handing them to the exact kernels at ~60 us a row:

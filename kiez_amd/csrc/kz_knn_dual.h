@@ -639,7 +639,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     // distances) far fewer rows are searched again (400k x 400k, k = 50, 40 clusters: 42.7k -> 0 rows, call 162 -> 134 ms; uniform 500k x 500k: +0.9 ms; k = 10: 12.4k -> 0 rows, 104 -> 97 ms, and ns 105.9 -> 104.4 ms per step:
     // its ~25 uncertified reverse rows per step are gone)
     const int KPr = ctx->dual_rev_long ? (2 * KP < 128 ? 2 * KP : 128) : KP;
-    const int n_slices = b->kg / 4;
+    const int n_slices = kz_h_nsr(b->kg);   // (slices of the fp16 images: 32 .. 64 padded to a multiple of 8)
     // every stride-th tile of A is in the sample.  Automatic (dual_stride = 1): the sample sweep costs T / stride, the events
     // (log, scatter, select, slower sweep) ~0.10 ns each with |B| k stride of them: stride = sqrt(T / (|B| k 0.07 ns)), T ~ 2 |A| |B| d / 1e15 s
     // (ns: 20, measured flat between 16 and 28; 500k x 500k, k = 50: 6)
@@ -688,7 +688,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     const double t_sweep_ms = 2.0 * (double)a->n * (double)b->n * (double)(a->kg * 4) / 1e12;
     const double t_events_ms = (double)b->n * rank * stride * 0.15e-6;
     const bool pays = ctx->dual_force || 0.7 * t_sweep_ms * (KP > 16 ? 2.0 : 1.0) > 2.0 * t_events_ms + 0.3;
-    const bool eligible = pays && stride >= 2 && ctx->precision == 0 && KP > 0 && a->metric < KZ_MANHATTAN && n_slices >= 2 && n_slices <= 24 && a->kg == b->kg &&
+    const bool eligible = pays && stride >= 2 && ctx->precision == 0 && KP > 0 && a->metric < KZ_MANHATTAN && kz_h_slices_ok(b->kg) && a->kg == b->kg &&
                           s_rows >= (int64_t)8 * KP && b->n >= 1024 && b_tiles < (1 << 20);
     if (!eligible) return kz_knn_dual_separately(ctx, a, b, k, d_dist_ab, d_ind_ab, d_dist_ba, d_ind_ba, stats_ab, stats_ba);
     {

@@ -13,7 +13,8 @@
 // index image streamed global -> LDS by LDS-DMA (one 16-k slice of 128 index rows = 4 KiB: two planes k 0-7 / 8-15 of
 // 128 rows x 16 B, copied linearly because the image already is the conflict-free ds_read_b128 layout) through a ring of
 // R = 2 P slots with one workgroup barrier per P slices; fragments of slice g+1 are read under the MFMAs of slice g.
-// Candidate selection: kz_knn_epi3.h.  Three workgroups per CU (168 VGPRs) up to d = 128, two beyond.
+// Candidate selection: kz_knn_epi3.h.  Three workgroups per CU (168 VGPRs) up to d = 128, two beyond, ONE at 32 .. 64 slices
+// (WPS = 1, d = 497 .. 1024: the query tile in the unified VGPR + AGPR file, kz_knn_h_inst.h "WIDE ROWS").
 #pragma once
 #include <type_traits>
 
@@ -45,19 +46,21 @@ template <int KP, int WPS, int NSR, bool DUAL = false, bool WIDE = false>
 struct KzHCfg {
     static constexpr int TPW = WIDE ? WPS : 1;                         // query tiles (of 128 rows) per workgroup
     static constexpr bool LDS_LIST = KP <= 32;
-    static constexpr bool LISTS_FIT = WPS == 2 || KP == 16;   // K' = 32 lists do not fit beside the ring at 3 per CU
+    static constexpr bool LISTS_FIT = WPS <= 2 || KP == 16;   // K' = 32 lists do not fit beside the ring at 3 per CU
     // where the lists live (KzListRef, kz_knn_epi3.h): 1 = LDS, 2 = keys in LDS + rows in the output arrays, 0 = output arrays.
     // The hybrid needs K' x 512 B: K' = 64 at two per CU (with a 4-slot ring), K' = 32 at three per CU (with a smaller pool).
-    static constexpr int LMODE = (LDS_LIST && LISTS_FIT) ? 1 : (((KP == 64 && WPS == 2) || (KP == 32 && WPS == 3)) ? 2 : 0);
+    // (one per CU -- the wide-row builds, WPS = 1 -- keep the list modes of two per CU)
+    static constexpr int LMODE = (LDS_LIST && LISTS_FIT) ? 1 : (((KP == 64 && WPS <= 2) || (KP == 32 && WPS == 3)) ? 2 : 0);
     static constexpr bool IN_LDS = LMODE == 1;
     // WIDE: eight slots, one barrier per four slices -- a barrier of a wide workgroup stops every wave of the CU (same-box,
     // 250k x 1M x 200, ordinary kernel: 4 slots / 2 slices per barrier 91.8 ms, 8 / 4: 85.0 ms, 12 / 6: 90.0 ms, narrow 88-89.6;
     // the wave groups staggered by a period with a barrier per 2 slices: 106 ms -- profiles/r03_ablation.md)
-    static constexpr int RING = WIDE ? 8 : ((WPS == 3 || KP == 32 || NSR < 4) ? 4 : 8);
+    // (one per CU: eight slots at every list length -- 160 KiB of LDS leave room for them beside the lists of K' = 32)
+    static constexpr int RING = WIDE ? 8 : (WPS == 1 ? 8 : ((WPS == 3 || KP == 32 || NSR < 4) ? 4 : 8));
     static constexpr int PERIOD = RING / 2;                            // slices per barrier: a slot is refilled one period before it is read
     // (three per CU: the workgroup must stay within 42 LDS granules of 1280 B -- 52.5 KiB with the lists of K' = 16 or the
     //  keys of K' = 32; the dual-pass build pays for its 1.5 KiB of thresholds and query offsets with 16 pool entries)
-    static constexpr int CAP = WPS == 3 ? (KP <= 32 ? (DUAL ? 176 : 192) : 256) : (LMODE == 2 && RING == 8 ? (DUAL ? 140 : 156) : 256);     // event-pool entries per wave (24 B each)
+    static constexpr int CAP = WPS == 3 ? (KP <= 32 ? (DUAL ? 176 : 192) : 256) : (WPS == 2 && LMODE == 2 && RING == 8 ? (DUAL ? 140 : 156) : 256);     // event-pool entries per wave (24 B each)
     static constexpr int RING_BYTES = RING * 4096;
     static constexpr int BIAS_OFF = RING_BYTES;                        // 2 x 128 floats
     static constexpr int SYNC_OFF = BIAS_OFF + 1024;                   // 4 merge flags (+ padding)
@@ -76,7 +79,7 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
     constexpr int TPW = Cfg::TPW;
     constexpr int R = Cfg::RING, P = Cfg::PERIOD, CAP = Cfg::CAP;
     static_assert((R & (R - 1)) == 0 && R == 2 * P, "slot arithmetic below: a power-of-two ring of two periods");
-    constexpr bool LATE = KZ_H_DMA_LATE == 2 || (KZ_H_DMA_LATE == 1 && WPS == 2 && !WIDE);
+    constexpr bool LATE = KZ_H_DMA_LATE == 2 || (KZ_H_DMA_LATE == 1 && WPS <= 2 && !WIDE);
     constexpr int IN_LDS = Cfg::LMODE;   // list storage mode (KzListRef)
     // at three waves per SIMD (168 VGPRs) the first fragments of the next tile are NOT fetched across the epilogue: the 16
     // registers they would occupy there are what keeps the stationary query tile out of scratch memory.  Exception: a tile
@@ -220,7 +223,9 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
     f32x16 acc[4];
 
     // one tile whose first slice has global parity P0 (compile time: the parity alternates from tile to tile when NSR is odd)
-    auto run_tile = [&](const int tile, auto start_parity) {
+    // (always inlined: from 48 slices on the inliner kept one out-of-line copy for the two calls below, and its wave-uniform
+    //  captures -- the DMA source, the tile number -- no longer compiled into the scalar registers the LDS-DMA asm needs)
+    auto run_tile = [&](const int tile, auto start_parity) __attribute__((always_inline)) {
         constexpr int P0 = decltype(start_parity)::value;
         {
             int h_now = h;

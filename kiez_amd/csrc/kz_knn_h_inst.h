@@ -14,6 +14,13 @@
 #endif
 #define KZ_H_CAT2(a, b) a##b
 #define KZ_H_CAT(a, b) KZ_H_CAT2(a, b)
+// the wide-row builds (32 .. 64 slices) of the same list length: their own translation units (kz_knn_hw_kp*.hip,
+// kz_knn_hwd_kp*.hip, KZ_H_WIDE_ROWS defined) so that they compile in parallel with the narrow ones
+#ifdef KZ_H_DUAL
+#define KZ_HW_NAME(base) KZ_H_CAT(kz_hwd_##base##_kp, KZ_H_KP)
+#else
+#define KZ_HW_NAME(base) KZ_H_CAT(kz_hw_##base##_kp, KZ_H_KP)
+#endif
 
 // Occupancy class of a slice count: three workgroups per CU (168 VGPRs, 53 KiB of LDS each) while the stationary query
 // tile fits, two (256 VGPRs, 80 KiB) beyond.  wps (tuning knob "h_wps") = 2 forces the two-workgroup build.
@@ -31,7 +38,7 @@ constexpr int KZ_H_WPS3_MAX_KP16 = 13;  // d <= 208: K' = 16 only
 // -> wide: 250k x 1M x 200: 88.0 -> 85.0, x 300: 124.5 -> 119.3; 100k x 100k x 128: 2.86 -> 2.95; 500k x 500k x 200, K' = 64:
 // 103 -> 111: every wave of the CU reaches the tile epilogue at the same time); elsewhere the narrow builds run.
 template <int KP, int NSR>
-static const void* kz_h_kernel(int wps, int wide_opt, int* lds, int* tpw) {
+static const void* kz_h_kernel_narrow(int wps, int wide_opt, int* lds, int* tpw) {
     constexpr bool three = NSR <= KZ_H_WPS3_MAX || (KP == 16 && NSR <= KZ_H_WPS3_MAX_KP16);
     constexpr bool WIDE_OK = false;   // (round 6: the wide builds are no longer instantiated -- KZ_K_H_WIDE; was KP == 16 && NSR > 8)
     const int wide = WIDE_OK ? wide_opt : 0;
@@ -58,6 +65,22 @@ static const void* kz_h_kernel(int wps, int wide_opt, int* lds, int* tpw) {
     *lds = KzHCfg<KP, 2, NSR, KZ_H_DUALV>::LDS_BYTES;
     *tpw = 1;
     return (const void*)kz_knn_cand_h_kernel<KP, NSR, 2, KZ_H_DUALV>;
+}
+
+// WIDE ROWS (d = 497 .. 1024: 32 .. 64 slices, the image zero-padded to a multiple of 8 slices -- kz_h_nsr): ONE workgroup per
+// CU, one wave per SIMD.  The stationary query tile alone takes 4 NSR = 128 .. 256 registers a lane; at one wave per SIMD the
+// wave owns the SIMD's whole 512-entry register file (VGPRs + AGPRs, kz_knn_h16.h) and the workgroup up to 160 KiB of LDS.
+// No co-resident workgroup hides the tile epilogue -- but its cost is fixed while the MFMAs of a tile grow with d (48 slices:
+// 3.7x those of d = 200).  Same kernel, same contract, same epilogue; the list modes of two per CU, an eight-slot ring.
+template <int KP, int NSR>
+static const void* kz_h_kernel(int wps, int wide_opt, int* lds, int* tpw) {
+    if constexpr (NSR > 24) {
+        *lds = KzHCfg<KP, 1, NSR, KZ_H_DUALV>::LDS_BYTES;
+        *tpw = 1;
+        return (const void*)kz_knn_cand_h_kernel<KP, NSR, 1, KZ_H_DUALV>;
+    } else {
+        return kz_h_kernel_narrow<KP, NSR>(wps, wide_opt, lds, tpw);
+    }
 }
 
 // *blocks_per_cu = workgroups of the kernel resident per CU, *tpw = query tiles each of them takes
@@ -111,14 +134,48 @@ static int kz_launch_h(kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wp
         }                                                 \
     } while (0)
 
+// (wide rows: the padded slice counts kz_h_nsr returns)
+#define KZ_DISPATCH_HW_NSR(rc, fn, args, KPV)             \
+    do {                                                  \
+        switch (n_slices) {                               \
+            case 32: rc = fn<KPV, 32> args; break;        \
+            case 40: rc = fn<KPV, 40> args; break;        \
+            case 48: rc = fn<KPV, 48> args; break;        \
+            case 56: rc = fn<KPV, 56> args; break;        \
+            case 64: rc = fn<KPV, 64> args; break;        \
+            default:                                      \
+                kz_set_error("kz_knn: no fp16 kernel for %d slices", n_slices); \
+                rc = KZ_ERR_UNSUPPORTED;                  \
+        }                                                 \
+    } while (0)
+
+#ifdef KZ_H_WIDE_ROWS
+int KZ_HW_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad) {
+    int rc;
+    KZ_DISPATCH_HW_NSR(rc, kz_h_occupancy, (blocks_per_cu, tpw, wps, wide, lds_pad), KZ_H_KP);
+    return rc;
+}
+
+int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide) {
+    int rc;
+    KZ_DISPATCH_HW_NSR(rc, kz_launch_h, (ctx, p, n_blocks, wps, wide), KZ_H_KP);
+    return rc;
+}
+#else
+int KZ_HW_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
+int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
+
 int KZ_H_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad) {
+    if (n_slices > 24) return KZ_HW_NAME(occupancy)(n_slices, blocks_per_cu, tpw, wps, wide, lds_pad);
     int rc;
     KZ_DISPATCH_H_NSR(rc, kz_h_occupancy, (blocks_per_cu, tpw, wps, wide, lds_pad), KZ_H_KP);
     return rc;
 }
 
 int KZ_H_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide) {
+    if (n_slices > 24) return KZ_HW_NAME(launch)(n_slices, ctx, p, n_blocks, wps, wide);
     int rc;
     KZ_DISPATCH_H_NSR(rc, kz_launch_h, (ctx, p, n_blocks, wps, wide), KZ_H_KP);
     return rc;
 }
+#endif

@@ -1,0 +1,4 @@
+// wide-row builds (32 .. 64 slices) of the fp16 fused kernel, list length 128 (kz_knn_h_inst.h)
+#define KZ_H_KP 128
+#define KZ_H_WIDE_ROWS 1
+#include "kz_knn_h_inst.h"

@@ -1,0 +1,5 @@
+// wide-row dual-pass builds (32 .. 64 slices) of the fp16 fused kernel, list length 16 (kz_knn_h_inst.h)
+#define KZ_H_KP 16
+#define KZ_H_DUAL 1
+#define KZ_H_WIDE_ROWS 1
+#include "kz_knn_h_inst.h"

@@ -495,7 +495,7 @@ static int kz_center_create(kz_ctx* ctx, const kz_matrix* from, kz_center** out)
     kz_center* c = new kz_center();
     memset(c, 0, sizeof(*c));
     c->refs = 1;
-    const int d = (int)from->d, d_pad = from->kg * 4;
+    const int d = (int)from->d, d_pad = kz_h_nsr(from->kg) * 16;   // (the fp16 image's width: kz_pack_h_kernel reads mu up to it)
     double* partial = nullptr;
     if (kz_pool_alloc(ctx, (size_t)d_pad * 4, (void**)&c->d_mu) != KZ_OK || kz_pool_alloc(ctx, 16, (void**)&c->d_scale) != KZ_OK ||
         kz_pool_alloc(ctx, (size_t)KZ_COLSUM_BLOCKS * d * 8, (void**)&partial) != KZ_OK) {
@@ -531,7 +531,7 @@ static int kz_himage_build(kz_matrix* m, kz_center* center) {
     im->center = center;
     ++center->refs;
     m->himg = im;
-    const int nsr = m->kg / 4;
+    const int nsr = kz_h_nsr(m->kg);
     const int64_t n_pad = m->n_tiles * KZ_TILE;
     // (+ 32 slices of padding: the kernel's DMA ring runs a few slices past the end of a sweep, kz_knn_h16.h)
     if (kz_pool_alloc(ctx, (size_t)n_pad * (size_t)nsr * 32 + 32 * 4096, (void**)&im->packed) != KZ_OK ||
@@ -567,7 +567,7 @@ int kz_himage_pack_permuted(kz_matrix* m, const int* d_perm, unsigned short* pac
     kz_ctx* ctx = m->ctx;
     KZ_REQUIRE(m->himg, "kz_himage_pack_permuted: the matrix has no fp16 image");
     const kz_center* center = m->himg->center;
-    const int nsr = m->kg / 4;
+    const int nsr = kz_h_nsr(m->kg);
     const int64_t n_pad = m->n_tiles * KZ_TILE;
     if (m->dtype == KZ_F32)
         hipLaunchKernelGGL(kz_pack_h_kernel<float>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const float*)m->raw, m->sqn,
@@ -586,7 +586,7 @@ int kz_himage_pack_rows(kz_matrix* m, const int* d_rows, int64_t n_rows, int64_t
     kz_ctx* ctx = m->ctx;
     KZ_REQUIRE(m->himg && n_pad % KZ_TILE == 0 && n_rows <= n_pad, "kz_himage_pack_rows: no fp16 image / bad row counts");
     const kz_center* center = m->himg->center;
-    const int nsr = m->kg / 4;
+    const int nsr = kz_h_nsr(m->kg);
     if (m->dtype == KZ_F32)
         hipLaunchKernelGGL(kz_pack_h_kernel<float>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const float*)m->raw, m->sqn,
                            n_rows, (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, packed, bias, (double*)nullptr,
@@ -626,7 +626,7 @@ int kz_himage_dealt(kz_matrix* m, int P) {
         }
     // not cached: an empty slot, else the one that was NOT selected last
     int v = !im->slot[0].packed ? 0 : (!im->slot[1].packed ? 1 : 1 - im->slot_cur);
-    const int nsr = m->kg / 4;
+    const int nsr = kz_h_nsr(m->kg);
     const int64_t n_pad = m->n_tiles * KZ_TILE;
     if (!im->slot[v].packed) {
         if (kz_pool_alloc(ctx, (size_t)n_pad * (size_t)nsr * 32 + 32 * 4096, (void**)&im->slot[v].packed) != KZ_OK ||
