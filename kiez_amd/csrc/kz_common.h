@@ -6,8 +6,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 
 #include "../../include/kiez_amd.h"
+#include "kz_pool_buf.h"
 
 #define KZ_TILE 128   // rows per packed tile (= MFMA block tile edge)
 #define KZ_KSLICE 16  // k elements staged per LDS slice (4 k-groups of 4)
@@ -90,8 +92,7 @@ struct kz_ctx {
     size_t live_bytes[KZ_LIVE_MAX];
 };
 
-int kz_pool_alloc(kz_ctx* ctx, size_t bytes, void** out);   // returns KZ_OK / KZ_ERR_NOMEM
-void kz_pool_free(kz_ctx* ctx, void* ptr, size_t bytes);
+// kz_pool_alloc / kz_pool_free are declared in kz_pool_buf.h (with KzPoolBuf, the scoped owner of a transient buffer)
 
 // Shift and scale shared by the fp16 images of the matrices that are searched against each other (kz_pack.hip):
 // distances are translation invariant, so both sides are centred with ONE vector mu (the column mean of the first index
@@ -192,6 +193,12 @@ int kz_matrix_check(kz_matrix* m);
 void kz_himage_free(kz_matrix* m);
 
 void kz_set_error(const char* fmt, ...);
+
+// scoped owner of a scratch matrix (the rows of a re-search, kz_matrix_create with rows borrowed on the device)
+struct KzMatrixDestroy {
+    void operator()(kz_matrix* m) const { kz_matrix_destroy(m); }
+};
+using KzMatrixPtr = std::unique_ptr<kz_matrix, KzMatrixDestroy>;
 
 #define KZ_HIP(call)                                                                             \
     do {                                                                                         \

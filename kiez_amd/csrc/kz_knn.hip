@@ -1245,9 +1245,11 @@ static int kz_launch_exact_lanes(kz_ctx* ctx, const int* fl, int b0, int nb, int
     const int d_pad = d;   // (a multiple of 4: whole leaves)
     const int nb_pad = groups ? nb : (nb + 4 * KZ_XL_Q - 1) / (4 * KZ_XL_Q) * (4 * KZ_XL_Q);   // (whole blocks of 4 waves x KZ_XL_Q rows; groups: the slots are padded per block)
     double* qd = qd_buf;   // (a caller that runs these launches on another stream than the pool's brings the buffer: kz_spec_alloc)
+    KzPoolBuf<double> qd_own;
     if (!qd) {
-        const int rc = kz_pool_alloc(ctx, kz_exact_lanes_qd_bytes(nb, d), (void**)&qd);
+        const int rc = qd_own.alloc(ctx, kz_exact_lanes_qd_bytes(nb, d));
         if (rc != KZ_OK) return rc == KZ_ERR_NOMEM ? KZ_OK : rc;   // (no memory for the operand rows: the cooperative kernel)
+        qd = qd_own.get();
     }
     double* qsq = qd + (size_t)nb_pad * d_pad;
     if (groups)
@@ -1314,7 +1316,7 @@ static int kz_launch_exact_lanes(kz_ctx* ctx, const int* fl, int b0, int nb, int
 #undef KZ_XL_LAUNCH
 #undef KZ_XL_LAUNCH_G
     if (e == hipSuccess) e = hipGetLastError();
-    if (!qd_buf) kz_pool_free(ctx, qd, 0);   // (stream-ordered pool)
+    qd_own.reset();   // (stream-ordered pool)
     if (e != hipSuccess) {
         kz_set_error("kz_knn: exact distance kernel (one pair per lane) failed: %s", hipGetErrorString(e));
         return KZ_ERR_HIP;
@@ -2139,16 +2141,16 @@ static inline double kz_gamma_acc_h(int kg) { return 2.0 * (double)(kg * 4 + 16)
 // row i * stride is probe row i; rowq: the query image's per-row statistics, same row numbering.  Waits for the stream.
 static int kz_floor_model(kz_ctx* ctx, const double* dist, const double* rowq, int n_probe, int64_t stride, int k, int metric, double* model,
                           bool* ok) {
-    double* d_pairs = nullptr;
-    int rc = kz_pool_alloc(ctx, (size_t)n_probe * 16, (void**)&d_pairs);
+    KzPoolBuf<double> d_pairs;
+    int rc = d_pairs.alloc(ctx, (size_t)n_probe * 16);
     if (rc != KZ_OK) return rc;
     std::vector<double> hp((size_t)n_probe * 2);
     hipLaunchKernelGGL(kz_floor_pairs_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, dist, rowq, n_probe, stride, k,
-                       metric, d_pairs);
+                       metric, d_pairs.get());
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), d_pairs, (size_t)n_probe * 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), d_pairs.get(), (size_t)n_probe * 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    kz_pool_free(ctx, d_pairs, 0);
+    d_pairs.reset();
     if (e != hipSuccess) {
         kz_set_error("kz_knn: floor probe failed: %s", hipGetErrorString(e));
         return KZ_ERR_HIP;
@@ -2241,20 +2243,13 @@ static inline int64_t kz_rows_per_chunk(const kz_ctx* ctx, int KP_mem, bool wide
 // 4 .. "spec_rows" (64), as many as "spec_elems" / (n d) allows (a row of a 1 M x 200 index is 0.2 G multiply-adds: R = 8).  The
 // read-back that follows tells the host whether that was all (count <= R: the results are in place -- the exact float64 order, what
 // every route returns) or whether the ordinary re-search has to run (count > R: the speculative launches did nothing).
-struct KzSpec {
+struct KzSpec {   // (the buffers in reverse release order: qd, vals, cand_v, cand_i)
     int R = 0;            // rows the speculative launches cover (0: not launched)
-    double* vals = nullptr;
-    double* cand_v = nullptr;
-    int* cand_i = nullptr;
-    double* qd = nullptr;   // float64 operand rows of the (up to R) query rows: kz_exact_lanes.h
+    KzPoolBuf<int> cand_i;
+    KzPoolBuf<double> cand_v;
+    KzPoolBuf<double> vals;
+    KzPoolBuf<double> qd;   // float64 operand rows of the (up to R) query rows: kz_exact_lanes.h
 };
-static void kz_spec_release(kz_ctx* ctx, KzSpec& sp) {
-    kz_pool_free(ctx, sp.qd, 0);
-    kz_pool_free(ctx, sp.vals, 0);
-    kz_pool_free(ctx, sp.cand_v, 0);
-    kz_pool_free(ctx, sp.cand_i, 0);
-    sp = KzSpec();
-}
 static int kz_spec_rows(const kz_ctx* ctx, const kz_matrix* index, int k_eff) {
     if (ctx->spec_rows <= 0 || index->metric >= KZ_MANHATTAN || k_eff > 64) return 0;
     const double nd = (double)index->n * (double)index->d;
@@ -2274,17 +2269,17 @@ static int kz_spec_alloc(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* index,
     const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
     const int n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
     const bool two_level = n_chunks >= 2 && k_sel <= KZ_EXACT_CHUNK;
-    int rc = kz_pool_alloc(ctx, (size_t)R * (size_t)index->n * 8, (void**)&sp.vals);
-    if (rc == KZ_OK && two_level) rc = kz_pool_alloc(ctx, (size_t)R * n_chunks * k_sel * 8, (void**)&sp.cand_v);
-    if (rc == KZ_OK && two_level) rc = kz_pool_alloc(ctx, (size_t)R * n_chunks * k_sel * 4, (void**)&sp.cand_i);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, kz_exact_lanes_qd_bytes(R, (int)index->d), (void**)&sp.qd);
-    if (rc != KZ_OK) {
-        kz_spec_release(ctx, sp);
-        return rc == KZ_ERR_NOMEM ? KZ_OK : rc;
-    }
+    KzSpec s;   // (all or nothing)
+    int rc = s.vals.alloc(ctx, (size_t)R * (size_t)index->n * 8);
+    if (rc == KZ_OK && two_level) rc = s.cand_v.alloc(ctx, (size_t)R * n_chunks * k_sel * 8);
+    if (rc == KZ_OK && two_level) rc = s.cand_i.alloc(ctx, (size_t)R * n_chunks * k_sel * 4);
+    if (rc == KZ_OK) rc = s.qd.alloc(ctx, kz_exact_lanes_qd_bytes(R, (int)index->d));
+    if (rc != KZ_OK) return rc == KZ_ERR_NOMEM ? KZ_OK : rc;
+    sp = std::move(s);
     return KZ_OK;
 }
-// fail_list / fail_count: the finalize kernel's device-side list and counter (fail_list holds rows relative to q0)
+// fail_list / fail_count: the finalize kernel's device-side list and counter (fail_list holds rows relative to q0).  The caller's
+// sp keeps its buffers whatever happens here: they are released by sp's owner, behind the stream the launches are on.
 static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query, int64_t q0, const int* fail_list, const int* fail_count,
                           const kz_matrix* index, int k, int exclude_self, const int64_t* d_self_ids, double* out_dist, int64_t* out_ind) {
     const int metric = index->metric;
@@ -2295,13 +2290,13 @@ static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query
     // (two selection levels from two chunks on: the single-level kernel passes k_eff times over the whole row with ONE workgroup --
     //  135 us for 15 k values, k = 10; the chunk kernel selects from registers)
     const bool two_level = n_chunks >= 2 && k_sel <= KZ_EXACT_CHUNK;
-    if (!sp.vals) {   // (not allocated ahead by the caller: kz_spec_alloc)
+    if (!sp.vals.get()) {   // (not allocated ahead by the caller: kz_spec_alloc)
         const int rc = kz_spec_alloc(ctx, sp, R, index, k_eff);
-        if (rc != KZ_OK || !sp.vals) return rc;
+        if (rc != KZ_OK || !sp.vals.get()) return rc;
     }
     const int dist_blocks = (int)((index->n + 3) / 4 < 256 ? (index->n + 3) / 4 : 256);   // (grid-stride; dead rows cost their dispatch)
-    const double* sel_v = two_level ? (const double*)sp.cand_v : (const double*)sp.vals;
-    const int* sel_i = two_level ? (const int*)sp.cand_i : (const int*)nullptr;
+    const double* sel_v = two_level ? (const double*)sp.cand_v.get() : (const double*)sp.vals.get();
+    const int* sel_i = two_level ? (const int*)sp.cand_i.get() : (const int*)nullptr;
     const int64_t n_entries = two_level ? (int64_t)n_chunks * k_sel : index->n;
     bool lanes = false;
     // (... from ~4 workgroups of 64 index rows per CU on: on a 15 k-row index its 235 workgroups run one per CU, all latency -- 73 us
@@ -2309,29 +2304,26 @@ static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query
     if (index->dtype == KZ_F32 && index->n >= (int64_t)4 * KZ_XL_ROWS * ctx->n_cus) {
         // (one pair per lane where that kernel applies: a pass over a 500 k x 200 index per FOUR rows made the cooperative kernel 2 ms
         //  for 16 rows -- on the critical path behind the forward finalize; 0.3 ms)
-        const int rcl = kz_launch_exact_lanes(ctx, fail_list, 0, R, q0, query, index, metric, sp.vals, &lanes, fail_count, sp.qd);
-        if (rcl != KZ_OK) {
-            kz_spec_release(ctx, sp);
-            return rcl;
-        }
+        const int rcl = kz_launch_exact_lanes(ctx, fail_list, 0, R, q0, query, index, metric, sp.vals.get(), &lanes, fail_count, sp.qd.get());
+        if (rcl != KZ_OK) return rcl;
     }
     if (lanes) {
     } else if (index->dtype == KZ_F32) {
         // (a handful of rows: short stretches of index rows per wave, so that the launch is wide -- 15 k rows: 235 x R / 4 workgroups)
         int rpw = (int)(index->n / 1024);
         rpw = rpw < 16 ? 16 : (rpw > 256 ? 256 : rpw);
-        if (!(ctx->exact_rows && kz_launch_exact_rows(ctx, fail_list, 0, R, q0, query, index, metric, sp.vals, fail_count, rpw)))
+        if (!(ctx->exact_rows && kz_launch_exact_rows(ctx, fail_list, 0, R, q0, query, index, metric, sp.vals.get(), fail_count, rpw)))
             hipLaunchKernelGGL(kz_exact_dist_kernel<float>, dim3(dist_blocks, R), dim3(256), 0, ctx->stream, fail_list, 0, q0,
                                (const float*)query->raw, (const float*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric,
-                               index->mink_p, sp.vals, fail_count);
+                               index->mink_p, sp.vals.get(), fail_count);
     } else {
         hipLaunchKernelGGL(kz_exact_dist_kernel<double>, dim3(dist_blocks, R), dim3(256), 0, ctx->stream, fail_list, 0, q0,
                            (const double*)query->raw, (const double*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric,
-                           index->mink_p, sp.vals, fail_count);
+                           index->mink_p, sp.vals.get(), fail_count);
     }
     if (two_level)
         hipLaunchKernelGGL(k_sel >= 24 && ctx->exact_rows ? kz_exact_chunk_radix_kernel : kz_exact_chunk_kernel, dim3(n_chunks, R), dim3(256), 0,
-                           ctx->stream, (const double*)sp.vals, index->n, k_sel, n_chunks, sp.cand_v, sp.cand_i, fail_count);
+                           ctx->stream, (const double*)sp.vals.get(), index->n, k_sel, n_chunks, sp.cand_v.get(), sp.cand_i.get(), fail_count);
     if (index->dtype == KZ_F32)
         hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(R), dim3(256), sel_lds, ctx->stream, fail_list, 0, q0, sel_v, sel_i, n_entries,
                            index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p, out_dist, out_ind, fail_count);
@@ -2340,7 +2332,6 @@ static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query
                            index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p, out_dist, out_ind, fail_count);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        kz_spec_release(ctx, sp);
         kz_set_error("kz_knn: speculative exact re-search failed to launch: %s", hipGetErrorString(e));
         return KZ_ERR_HIP;
     }
@@ -2348,55 +2339,61 @@ static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query
     return KZ_OK;
 }
 
+// What a re-search asks of kz_knn_impl (the default asks for nothing: the context's settings).  The caller decides the fields together.
+struct KzResearch {
+    int prec = -1;            // operands: -1 = the context's setting (kz_ctx::precision), else 0 / 1 / 2
+    int min_kp = 0;           // smallest list length, 16 .. 128 (escalated rows of the fp16 tier: longer lists on the same operand images)
+    bool more_lists = false;  // escalated rows of a K' = 16 pass: more lists of 16 instead of longer ones (min_kp 0)
+    int wide_lists = 0;       // > 0: the fp16 tier's WIDE route with this many lists of 16 per query (min_kp 0)
+    bool no_short = false;    // not the short-list route (rows that route could not certify: a re-search differs from the pass that failed)
+};
+static KzResearch kz_research_wide(int lists) {   // (a caller's probe has found that this data needs margin in ranks, not better operands)
+    KzResearch r;
+    r.prec = 0;
+    r.wide_lists = lists;
+    return r;
+}
+
 static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index, int k,
-                       int exclude_self, const int64_t* d_self_ids, int precision_override, int kp_min, double* d_dist,
+                       int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* d_dist,
                        int64_t* d_ind, kz_knn_stats* stats, KzDualPass* dual);
 static int kz_escalate_rows(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, const int* fail_list, int n_fail, kz_matrix* index, int k,
-                            int exclude_self, const int64_t* d_self_ids, int precision_override, int kp_min, double* out_dist,
+                            int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* out_dist,
                             int64_t* out_ind, kz_knn_stats* st2, float* ms_out) {
     KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
     const size_t row_bytes = (size_t)query->d * (query->dtype == KZ_F32 ? 4 : 8);
-    int* fl = nullptr;
-    void* sub_raw = nullptr;
-    int64_t* sub_self = nullptr;
-    double* sub_dist = nullptr;
-    int64_t* sub_ind = nullptr;
-    kz_matrix* qsub = nullptr;
-    auto release = [&]() {
-        if (qsub) kz_matrix_destroy(qsub);
-        kz_pool_free(ctx, fl, 0);
-        kz_pool_free(ctx, sub_raw, 0);
-        kz_pool_free(ctx, sub_self, 0);
-        kz_pool_free(ctx, sub_dist, 0);
-        kz_pool_free(ctx, sub_ind, 0);
-    };
-    int rc = kz_pool_alloc(ctx, (size_t)n_fail * sizeof(int), (void**)&fl);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * row_bytes, &sub_raw);
-    if (rc == KZ_OK && exclude_self) rc = kz_pool_alloc(ctx, (size_t)n_fail * 8, (void**)&sub_self);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * k * 8, (void**)&sub_dist);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * k * 8, (void**)&sub_ind);
-    if (rc != KZ_OK) {
-        release();
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(fl, fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream);
+    // (released when the function returns: qsub, fl, sub_raw, sub_self, sub_dist, sub_ind)
+    KzPoolBuf<int64_t> sub_ind;
+    KzPoolBuf<double> sub_dist;
+    KzPoolBuf<int64_t> sub_self;
+    KzPoolBuf<void> sub_raw;
+    KzPoolBuf<int> fl;
+    KzMatrixPtr qsub;
+    int rc = fl.alloc(ctx, (size_t)n_fail * sizeof(int));
+    if (rc == KZ_OK) rc = sub_raw.alloc(ctx, (size_t)n_fail * row_bytes);
+    if (rc == KZ_OK && exclude_self) rc = sub_self.alloc(ctx, (size_t)n_fail * 8);
+    if (rc == KZ_OK) rc = sub_dist.alloc(ctx, (size_t)n_fail * k * 8);
+    if (rc == KZ_OK) rc = sub_ind.alloc(ctx, (size_t)n_fail * k * 8);
+    if (rc != KZ_OK) return rc;
+    hipError_t e = hipMemcpyAsync(fl.get(), fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_fail), dim3(256), 0, ctx->stream, (const char*)query->raw, fl, cq_begin,
-                           n_fail, (int64_t)row_bytes, (char*)sub_raw, sub_self, d_self_ids);
+        hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_fail), dim3(256), 0, ctx->stream, (const char*)query->raw, fl.get(), cq_begin,
+                           n_fail, (int64_t)row_bytes, (char*)sub_raw.get(), sub_self.get(), d_self_ids);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
-        release();
         kz_set_error("kz_knn: gathering the escalated rows failed: %s", hipGetErrorString(e));
         return KZ_ERR_HIP;
     }
-    rc = kz_matrix_create(ctx, sub_raw, 2, n_fail, query->d, query->dtype, query->metric, &qsub);
+    kz_matrix* qsub_new = nullptr;
+    rc = kz_matrix_create(ctx, sub_raw.get(), 2, n_fail, query->d, query->dtype, query->metric, &qsub_new);
+    qsub.reset(qsub_new);
     memset(st2, 0, sizeof(*st2));
     if (rc == KZ_OK)
-        rc = kz_knn_impl(ctx, qsub, 0, n_fail, index, k, exclude_self, sub_self, precision_override, kp_min, sub_dist, sub_ind, st2, nullptr);
+        rc = kz_knn_impl(ctx, qsub.get(), 0, n_fail, index, k, exclude_self, sub_self.get(), rs, sub_dist.get(), sub_ind.get(), st2, nullptr);
     if (rc == KZ_OK) {
         hipLaunchKernelGGL(kz_scatter_rows_kernel, dim3((unsigned)(((int64_t)n_fail * k + 255) / 256)), dim3(256), 0, ctx->stream,
-                           sub_dist, sub_ind, fl, n_fail, k, out_dist, out_ind);
+                           sub_dist.get(), sub_ind.get(), fl.get(), n_fail, k, out_dist, out_ind);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -2405,67 +2402,56 @@ static int kz_escalate_rows(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, con
             rc = KZ_ERR_HIP;
         }
     }
-    release();
     if (rc != KZ_OK) return rc;
     KZ_HIP(hipEventElapsedTime(ms_out, ctx->ev[3], ctx->ev[4]));
     return KZ_OK;
 }
 
 // d_self_ids (device, optional): index row to strip per query when exclude_self is set and the query matrix is not the
-// index matrix itself (escalated subsets).  precision_override: -1 = the context's setting, 1 = float32 operands only.
-// kp_min: smallest list length to use (escalated subsets of the fp16 tier are first re-done with LONGER lists on the same
-// operand images: the certification compares the K'-th approximate key with the k-th exact one, so more margin in ranks
-// is usually all a failed row needs, and unlike the float32 tier it costs no new image of the index).
+// index matrix itself (escalated subsets).  rs: what a re-search asks for (KzResearch).  Escalated subsets of the fp16 tier are
+// first re-done with LONGER lists on the same operand images (rs.min_kp): the certification compares the K'-th approximate key with
+// the k-th exact one, so more margin in ranks is usually all a failed row needs, and unlike the float32 tier it costs no new image
+// of the index.
 // LADDER AFTER THE FACT (round 5).  A pass that leaves MORE THAN HALF of its rows uncertified without a tier probe having looked at
 // the data first (searches below the probe's size gates; tools/cliff_probe.py: 100k x 101k x 128, tight clusters, 60 - 100 ms
 // against 5.6 on uniform rows) used to hand all of them to the split-bf16 operands, where rows of a tight cluster fail again --
 // what they lack is margin in ranks.  Now a strided sample of the failed rows goes through the fp16 tier's WIDE route first (their
 // results are final either way); at most a quarter of the sample uncertified there: every failed row takes that route, else the
-// caller's choice (prec, kp_min).  Fewer than 4096 failed rows: the caller's choice at once.
+// caller's choice (rs).  Fewer than 4096 failed rows: the caller's choice at once.
 __global__ void kz_strided_pick_kernel(const int* __restrict__ in, int n_out, int64_t stride, int* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_out) out[i] = in[(int64_t)i * stride];
 }
 static int kz_escalate_ladder(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, const int* fail_list, int n_fail, kz_matrix* index, int k,
-                              int exclude_self, const int64_t* d_self_ids, int prec, int kp_min, double* out_dist, int64_t* out_ind,
+                              int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* out_dist, int64_t* out_ind,
                               kz_knn_stats* st, float* ms_out) {
     float ms_probe = 0;
     // (the wide route wants at least 8 index tiles per list: a small index gets fewer lists, down to 8 -- 128 entries per query)
     int P = ctx->wide_lists;
     if ((int64_t)index->n_tiles < (int64_t)8 * P) P = (int)(index->n_tiles / 8);
-    int* keep = nullptr;   // (the caller's list lives in the pass's scratch block, which the probe's own search reuses: a private copy)
+    KzPoolBuf<int> keep;   // (the caller's list lives in the pass's scratch block, which the probe's own search reuses: a private copy)
     if (P >= 8 && ctx->esc_ladder && n_fail >= 4096) {
         const int n_probe = 1024;
-        int* plist = nullptr;
-        int rc = kz_pool_alloc(ctx, (size_t)n_probe * sizeof(int), (void**)&plist);
-        if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * sizeof(int), (void**)&keep);
-        if (rc != KZ_OK) {
-            kz_pool_free(ctx, plist, 0);
-            return rc;
-        }
-        if (hipMemcpyAsync(keep, fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
-            kz_pool_free(ctx, plist, 0);
-            kz_pool_free(ctx, keep, 0);
+        KzPoolBuf<int> plist;
+        int rc = plist.alloc(ctx, (size_t)n_probe * sizeof(int));
+        if (rc == KZ_OK) rc = keep.alloc(ctx, (size_t)n_fail * sizeof(int));
+        if (rc != KZ_OK) return rc;
+        if (hipMemcpyAsync(keep.get(), fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
             kz_set_error("kz_knn: copying the list of uncertified rows failed");
             return KZ_ERR_HIP;
         }
-        hipLaunchKernelGGL(kz_strided_pick_kernel, dim3((n_probe + 255) / 256), dim3(256), 0, ctx->stream, keep, n_probe, (int64_t)(n_fail / n_probe), plist);
+        hipLaunchKernelGGL(kz_strided_pick_kernel, dim3((n_probe + 255) / 256), dim3(256), 0, ctx->stream, keep.get(), n_probe, (int64_t)(n_fail / n_probe),
+                           plist.get());
         kz_knn_stats stw;
         memset(&stw, 0, sizeof(stw));
-        rc = kz_escalate_rows(ctx, query, cq_begin, plist, n_probe, index, k, exclude_self, d_self_ids, 0, -P, out_dist, out_ind, &stw, &ms_probe);
-        kz_pool_free(ctx, plist, 0);
-        if (rc != KZ_OK) {
-            kz_pool_free(ctx, keep, 0);
-            return rc;
-        }
-        if (stw.wide_lists > 0 && (int64_t)stw.n_first_pass_fail * 4 <= n_probe) {
-            prec = 0;
-            kp_min = -P;
-        }
-        fail_list = keep;
+        rc = kz_escalate_rows(ctx, query, cq_begin, plist.get(), n_probe, index, k, exclude_self, d_self_ids, kz_research_wide(P), out_dist, out_ind,
+                              &stw, &ms_probe);
+        plist.reset();
+        if (rc != KZ_OK) return rc;
+        if (stw.wide_lists > 0 && (int64_t)stw.n_first_pass_fail * 4 <= n_probe) rs = kz_research_wide(P);
+        fail_list = keep.get();
     }
-    const int rc = kz_escalate_rows(ctx, query, cq_begin, fail_list, n_fail, index, k, exclude_self, d_self_ids, prec, kp_min, out_dist, out_ind, st, ms_out);
-    kz_pool_free(ctx, keep, 0);
+    const int rc = kz_escalate_rows(ctx, query, cq_begin, fail_list, n_fail, index, k, exclude_self, d_self_ids, rs, out_dist, out_ind, st, ms_out);
     if (ms_out) *ms_out += ms_probe;
     return rc;
 }
@@ -2473,7 +2459,7 @@ static int kz_escalate_ladder(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, c
 #include "kz_range.h"
 
 static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index, int k,
-                       int exclude_self, const int64_t* d_self_ids, int precision_override, int kp_min, double* d_dist,
+                       int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* d_dist,
                        int64_t* d_ind, kz_knn_stats* stats, KzDualPass* dual) {
     KZ_REQUIRE(ctx && query && index && d_dist && d_ind, "kz_knn: null argument");
     KZ_REQUIRE(query->ctx == ctx && index->ctx == ctx, "kz_knn: matrices belong to a different context");
@@ -2485,17 +2471,6 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     KZ_REQUIRE(kz_metric_params_match(query, index), "kz_knn: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index");
     KZ_REQUIRE(q_begin >= 0 && q_count >= 0 && q_begin + q_count <= query->n, "kz_knn: query row range out of bounds");
     KZ_REQUIRE(k >= 1, "kz_knn: Expected k > 0. Got %d", k);
-    // kp_min >= 1000: lists of kp_min - 1000, and NOT the short-list route (the re-search of rows that route could not certify:
-    // every re-search must differ from the pass that failed)
-    const bool no_short = kp_min >= 1000;
-    if (no_short) kp_min -= 1000;
-    // kp_min <= -2: the WIDE fp16 route with -kp_min lists of 16 per query (below, "WIDE ROUTE"): a caller's probe has found that
-    // this data needs more margin in ranks, not better operands
-    int forced_lists = 0;
-    if (kp_min <= -2) {
-        forced_lists = -kp_min;
-        kp_min = 0;
-    }
     const int k_eff = k + (exclude_self ? 1 : 0);
     KZ_REQUIRE((int64_t)k_eff <= index->n, "kz_knn: Expected n_neighbors %s n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld",
                exclude_self ? "<" : "<=", k, (long long)index->n);
@@ -2531,7 +2506,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     // and its merges short; a range that holds 16 or more of a query's nearest rows is seen by the certification (piece_bound).
     // The caller has dealt the index tiles over the ranges (kz_knn_dual.h): near rows of a query sit in ALL ranges alike.
     const int KP_class = KP;
-    if (dual && dual->short_pieces > 0 && KP > dual->short_kp && kp_min <= dual->short_kp) {
+    if (dual && dual->short_pieces > 0 && KP > dual->short_kp && rs.min_kp <= dual->short_kp) {
         KP = dual->short_kp;
         KSEL = dual->short_ksel;
         long_pieces = dual->short_pieces;
@@ -2544,14 +2519,14 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         }
         KP = 128;   // (list geometry of the scratch block only; no list kernel runs)
     }
-    if (KP < kp_min) KP = kp_min < 128 ? kp_min : 128;   // (list lengths are 16 / 32 / 64 / 128)
-    // kp_min = -1 (escalated rows of a K' = 16 pass): MORE LISTS instead of longer ones -- a list of 16 per index range over at
+    if (KP < rs.min_kp) KP = rs.min_kp < 128 ? rs.min_kp : 128;   // (list lengths are 16 / 32 / 64 / 128)
+    // rs.more_lists (escalated rows of a K' = 16 pass): MORE LISTS instead of longer ones -- a list of 16 per index range over at
     // least four ranges, the finalize kernel selecting k + 16 of their entries.  The bound of the certification becomes the
     // largest 16th-best key of a RANGE (a quarter of the index or less) instead of the 16th-best key of the whole index: the
     // margin in ranks a failed row needs, with the K' = 16 kernel and a quarter of the entries to merge (14 rows of a 1M-row
     // index: 0.75 + 0.62 ms with lists of 64 over 64 ranges).
     int min_pieces_call = 0;
-    if (kp_min == -1) {
+    if (rs.more_lists) {
         if (KP == 16 && !exact_only && KSEL == 0 && index->n_tiles >= 16) {
             KSEL = k_eff + 48;   // (<= 60 of the >= 64 entries)
             min_pieces_call = 4;
@@ -2576,7 +2551,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     const double gamma_acc_h = kz_gamma_acc_h(index->kg);
 
     // ---- tier of this call ------------------------------------------------------------------------------------------
-    const int precision = precision_override >= 0 ? precision_override : ctx->precision;
+    const int precision = rs.prec >= 0 ? rs.prec : ctx->precision;
     int tier = KZ_TIER_F32;
     // (d = 497 .. 1024, 32 .. 64 slices: the fp16 tier's wide-row builds -- and no split-bf16 tier: precision = 2 runs on float32
     //  operands there, and so does every row the fp16 pass leaves that would have gone to the split-bf16 operands: esc_bf)
@@ -2602,11 +2577,11 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     float probe_ms = 0;   // (tier probe, below: reported with the fallback time)
     // (the long-k route up to 320 neighbours as well: k / 5 <= 64 lists of 16 instead of 4 .. 14 lists of 128 -- 50k x 500k x 200, main
     //  kernel: k = 128 32.4 -> 12.5 ms, k = 160 35.4 -> 13.3; beyond 32 lists the finalize kernel selects by repeated arg-max)
-    const bool longk_lists = KSEL > 0 && long_pieces > 0 && KP == 128 && kp_min <= 0 && k_eff <= 320;
-    if (!dual && !no_short && tier == KZ_TIER_H && ctx->short_ord && KP > 16 && (KSEL == 0 || longk_lists) && !exact_only) {
+    const bool longk_lists = KSEL > 0 && long_pieces > 0 && KP == 128 && rs.min_kp == 0 && k_eff <= 320;
+    if (!dual && !rs.no_short && tier == KZ_TIER_H && ctx->short_ord && KP > 16 && (KSEL == 0 || longk_lists) && !exact_only) {
         int P = (k_eff + KZ_K_DUAL_SHORT_DIV - 1) / KZ_K_DUAL_SHORT_DIV;
         if (P < KP / 16) P = KP / 16;
-        if (kp_min >= 128) P = 16;   // (a re-search that asks for lists of 128: all the ranges the finalize kernel's fast selection takes)
+        if (rs.min_kp >= 128) P = 16;   // (a re-search that asks for lists of 128: all the ranges the finalize kernel's fast selection takes)
         const int sel = k_eff + (KP >= 128 ? 80 : 48) < P * 16 ? k_eff + (KP >= 128 ? 80 : 48) : P * 16;
         if (P <= (longk_lists ? 64 : 32) && (int64_t)index->n_tiles >= (int64_t)ctx->short_ord_min_tiles * P && sel >= k_eff &&
             4 * kz_fin_wave_bytes(P * 16, sel) <= 160 * 1024) {   // (<= 512 entries: kz_rank_select<8>; up to 1024 -- 33 .. 64 lists of the long-k route -- the radix select)
@@ -2628,7 +2603,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     // in RANKS -- the bound on the rows outside the candidate set must fall 2 eps below the k-th key, i.e. the set must reach down
     // to the ~250th key -- and that costs list events and re-ranked rows, not MFMA products: the fp16 kernel with one product per
     // multiply-add stays, where the split-bf16 tier pays three (bench.py "hard": every row failed the fp16 pass with lists worth
-    // ~100 ranks; with 256 they are certified).  Taken when the tier probe says so (below) or a caller asks for it (forced_lists).
+    // ~100 ranks; with 256 they are certified).  Taken when the tier probe says so (below) or a caller asks for it (rs.wide_lists).
     bool wide_route = false;
     auto wide_geometry = [&](int P, int* sel_out) -> bool {
         int sel = ctx->wide_sel < P * 16 ? ctx->wide_sel : P * 16;
@@ -2649,8 +2624,8 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         long_pieces = P;
         return KZ_OK;
     };
-    if (forced_lists > 0) {
-        const int rc = take_wide(forced_lists);
+    if (rs.wide_lists > 0) {
+        const int rc = take_wide(rs.wide_lists);
         if (rc != KZ_OK && rc != KZ_ERR_UNSUPPORTED && rc != KZ_ERR_NOMEM) return rc;   // (not available: this call's ordinary route)
     }
     // TIER PROBE.  Data that is hard for fp16 as a whole (tight clusters far from the centre: nearly every row fails the first pass'
@@ -2663,24 +2638,23 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     // and >= 16 probe sizes of query rows take it (C1 / C2 do not).  Option "tier_probe" = 0: off.
     float* qfloor_ord = nullptr;   // seeded lists of an ordinary search (the context's buffer: nothing to release)
     bool probed = false;           // the tier probe below has run: its verdict stands (no ladder after the fact)
-    if (tier == KZ_TIER_H && !dual && precision_override < 0 && kp_min == 0 && forced_lists == 0 && !exact_only && ctx->tier_probe > 0 && ctx->esc_bf &&
+    const bool default_request = rs.prec < 0 && rs.min_kp == 0 && !rs.more_lists && rs.wide_lists == 0;   // (a top-level call's)
+    if (tier == KZ_TIER_H && !dual && default_request && !exact_only && ctx->tier_probe > 0 && ctx->esc_bf &&
         q_count >= (int64_t)16 * ctx->tier_probe && ctx->chunk_rows == 0 &&
         ((double)q_count * (double)index->n >= ctx->probe_min_pairs ||
          2.0 * (double)q_count * (double)index->n * (double)(index->kg * 4) / 1e12 >= KZ_K_PROBE_MIN_MS)) {
         const int n_probe = ctx->tier_probe;
-        int* plist = nullptr;
-        int rc = kz_pool_alloc(ctx, (size_t)n_probe * sizeof(int), (void**)&plist);
+        KzPoolBuf<int> plist;
+        int rc = plist.alloc(ctx, (size_t)n_probe * sizeof(int));
         if (rc != KZ_OK) return rc;
-        hipLaunchKernelGGL(kz_strided_rows_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, plist, n_probe,
+        hipLaunchKernelGGL(kz_strided_rows_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, plist.get(), n_probe,
                            q_count / n_probe);
         kz_knn_stats stp;
         float pms = 0;
-        rc = kz_escalate_rows(ctx, query, q_begin, plist, n_probe, index, k, exclude_self, d_self_ids, 0, 0, d_dist, d_ind, &stp, &pms);
-        int* plist_keep = plist;
-        if (rc != KZ_OK) {
-            kz_pool_free(ctx, plist, 0);
-            return rc;
-        }
+        KzResearch probe_rs;
+        probe_rs.prec = 0;
+        rc = kz_escalate_rows(ctx, query, q_begin, plist.get(), n_probe, index, k, exclude_self, d_self_ids, probe_rs, d_dist, d_ind, &stp, &pms);
+        if (rc != KZ_OK) return rc;
         probe_ms = pms;
         probed = true;
         // (the verdict counts the rows that left the probe's FIRST pass uncertified, once each -- not the cumulative count of the
@@ -2696,19 +2670,16 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             if (wide_geometry(ctx->wide_lists, &sel)) {
                 kz_knn_stats stw;
                 float wms = 0;
-                rc = kz_escalate_rows(ctx, query, q_begin, plist_keep, n_probe, index, k, exclude_self, d_self_ids, 0, -ctx->wide_lists, d_dist, d_ind,
-                                      &stw, &wms);
-                if (rc != KZ_OK) {
-                    kz_pool_free(ctx, plist_keep, 0);
-                    return rc;
-                }
+                rc = kz_escalate_rows(ctx, query, q_begin, plist.get(), n_probe, index, k, exclude_self, d_self_ids, kz_research_wide(ctx->wide_lists),
+                                      d_dist, d_ind, &stw, &wms);
+                if (rc != KZ_OK) return rc;
                 probe_ms += wms;
                 if ((int64_t)stw.n_first_pass_fail * 4 <= n_probe && (int64_t)stw.n_first_pass_fail * 2 < stp.n_first_pass_fail &&
                     take_wide(ctx->wide_lists) == KZ_OK)
                     hard = false;
             }
         }
-        kz_pool_free(ctx, plist_keep, 0);
+        plist.reset();
         if (hard) {
             tier = bf_ok ? KZ_TIER_BF : KZ_TIER_F32;   // (wide rows: no split-bf16 operands, the float32 ones)
             // (data this hard for fp16 is hard for the split-bf16 operands, too, wherever the keys are dense: lists of 64 from the
@@ -2798,7 +2769,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             //  number of ranges: this route's own image again; cached, two are kept)
             // (any failure ends the call: launching on whatever image the last sub-search selected would certify against the wrong
             //  range layout; unreachable while a slot exists once the route is chosen)
-            const int rcd = kz_himage_dealt(index, wide_route || forced_lists > 0 ? long_pieces : route_P);
+            const int rcd = kz_himage_dealt(index, wide_route || rs.wide_lists > 0 ? long_pieces : route_P);
             if (rcd != KZ_OK) {
                 if (rcd == KZ_ERR_NOMEM) kz_set_error("kz_knn: out of device memory for the row-dealt image of the index");
                 return rcd;
@@ -2855,8 +2826,8 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         int4* d_work = ps.d_work;
         int* fail_count = ctx->d_counters + 8;
         KZ_HIP(hipMemsetAsync(fail_count, 0, 4 * sizeof(int), ctx->stream));  // fail counter, (unused), error-ratio bits
-        const float* boot_floor = nullptr;   // (this chunk's range-0 floor, if any: the finalize kernel must know it)
-        unsigned long long* stamp_buf = nullptr;   // (diagnostic "abl_stamp")
+        KzPoolBuf<float> boot_floor;   // (this chunk's range-0 floor, if any: the finalize kernel must know it)
+        KzPoolBuf<unsigned long long> stamp_buf;   // (diagnostic "abl_stamp")
         KnnCandParams cp;
         memset(&cp, 0, sizeof(cp));
         if (tier == KZ_TIER_H) {
@@ -2903,25 +2874,23 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             // range 0 of every query tile, the floor off its lists, then the other ranges
             KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W0, KZ_K_H_WPS, KZ_K_H_WIDE));
             if (rc != KZ_OK) return rc;
-            float* bfloor = nullptr;
             const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
-            rc = kz_pool_alloc(ctx, (size_t)n_pad * 4, (void**)&bfloor);   // (a buffer of this chunk: escalated sub-searches boot too)
+            rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);   // (a buffer of this chunk: escalated sub-searches boot too)
             if (rc != KZ_OK) return rc;
             hipLaunchKernelGGL(kz_boot_floor_kernel, dim3((unsigned)((cq_count + 255) / 256)), dim3(256), 0, ctx->stream, out_key, out_idx, lay, KP,
-                               cq_begin - (int64_t)qt0 * KZ_TILE, cq_begin, cq_count, cp.qfloor, bfloor);
+                               cq_begin - (int64_t)qt0 * KZ_TILE, cq_begin, cq_count, cp.qfloor, boot_floor.get());
             KZ_HIP(hipGetLastError());
-            cp.qfloor = bfloor;
+            cp.qfloor = boot_floor.get();
             cp.work = d_work + ps.W0;
             KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W - ps.W0, KZ_K_H_WPS, KZ_K_H_WIDE));
             cp.work = d_work;
-            boot_floor = bfloor;
         } else if (tier == KZ_TIER_H) {
             if ((ctx->abl & 2) && getenv("KZ_STAMP_FILE")) {   // (diagnostic: a -DKZ_ABL_STAMP build of the fp16 units fills it)
-                rc = kz_pool_alloc(ctx, (size_t)W * (16 + 1024), (void**)&stamp_buf);
+                rc = stamp_buf.alloc(ctx, (size_t)W * (16 + 1024));
                 if (rc != KZ_OK) return rc;
-                KZ_HIP(hipMemsetAsync(stamp_buf, 0, (size_t)W * (16 + 1024), ctx->stream));
-                cp.log_meta = stamp_buf;
-                cp.log_keys = stamp_buf + 2 * (size_t)W;
+                KZ_HIP(hipMemsetAsync(stamp_buf.get(), 0, (size_t)W * (16 + 1024), ctx->stream));
+                cp.log_meta = stamp_buf.get();
+                cp.log_keys = stamp_buf.get() + 2 * (size_t)W;
             }
             KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W, KZ_K_H_WPS, KZ_K_H_WIDE));
             cp.log_meta = nullptr;
@@ -2930,19 +2899,17 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 // DIAGNOSTIC ("abl_refloor", profiles/r06_event_ablation.md): the same sweep AGAIN with every list starting at the
                 // threshold it ENDED on (the K'-th best key of the first sweep's list): K' insertions per query instead of
                 // K' (1 + ln(n / K')) -- the time any seeding of the lists could at best reach.  The second sweep is the one timed.
-                float* bfloor = nullptr;
                 const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
-                rc = kz_pool_alloc(ctx, (size_t)n_pad * 4, (void**)&bfloor);
+                rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);
                 if (rc != KZ_OK) return rc;
                 hipLaunchKernelGGL(kz_boot_floor_kernel, dim3((unsigned)((cq_count + 255) / 256)), dim3(256), 0, ctx->stream, out_key, out_idx, lay, KP,
-                                   cq_begin - (int64_t)qt0 * KZ_TILE, cq_begin, cq_count, cp.qfloor, bfloor);
+                                   cq_begin - (int64_t)qt0 * KZ_TILE, cq_begin, cq_count, cp.qfloor, boot_floor.get());
                 // (one ulp below: entries equal to the threshold must get in again)
-                hipLaunchKernelGGL(kz_floor_nudge_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, bfloor, n_pad);
+                hipLaunchKernelGGL(kz_floor_nudge_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, boot_floor.get(), n_pad);
                 KZ_HIP(hipGetLastError());
-                cp.qfloor = bfloor;
+                cp.qfloor = boot_floor.get();
                 KZ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
                 KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W, KZ_K_H_WPS, KZ_K_H_WIDE));
-                boot_floor = bfloor;
             }
         } else if (tier == KZ_TIER_BF)
             KZ_DISPATCH_KP(rc, kz_bf_launch, (n_slices, ctx, cp, W));
@@ -2996,7 +2963,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         fp.out_dist = d_dist + c0 * (int64_t)k;
         fp.out_ind = d_ind + c0 * (int64_t)k;
         if (tier == KZ_TIER_H && short_ord) fp.idx_map = index->himg->dealt_perm;   // the lists hold rows of the dealt index image
-        if (tier == KZ_TIER_H && !dual) fp.list_floor = boot_floor ? boot_floor : qfloor_ord;
+        if (tier == KZ_TIER_H && !dual) fp.list_floor = boot_floor.get() ? boot_floor.get() : qfloor_ord;
         if (tier == KZ_TIER_H && dual) {
             fp.idx_map = dual->perm;      // the lists hold rows of the sorted index image
             fp.row_map = dual->row_map;   // the chunk is a range of IMAGE rows: results and failures go by matrix row
@@ -3018,38 +2985,38 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             rc = kz_launch_finalize(ctx, fp, lay, KP, cq_count, index->dtype);
             if (rc != KZ_OK) return rc;
         }
-        if (boot_floor) kz_pool_free(ctx, const_cast<float*>(boot_floor), 0);   // (stream-ordered: the launches above have it)
+        boot_floor.reset();   // (stream-ordered: the launches above have it)
         KZ_HIP(hipGetLastError());
         KZ_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-        // SPECULATIVE RESCUE (above kz_escalate_rows): the exact kernels for up to R uncertified rows, before the count is known
-        KzSpec spec;
-        if (!exact_only && !(dual && dual->raw_lists) && tier != KZ_TIER_F32) {
-            const int R = kz_spec_rows(ctx, index, k_eff);
-            if (R > 0) {
-                rc = kz_spec_rescue(ctx, spec, R, query, fp.row_map ? 0 : cq_begin, fail_list, fail_count, index, k, exclude_self, d_self_ids,
-                                    fp.out_dist, fp.out_ind);
-                if (rc != KZ_OK) return rc;
-                if (spec.R > 0) KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-            }
-        }
-        KZ_HIP(hipMemcpyAsync(ctx->h_counters + 8, fail_count, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         // matrices created from device rows have not had their finiteness verdict read yet (kz_matrix_create waits for
         // nothing): it rides on this call's read-back
         kz_matrix* unchecked[2] = {query->checked ? nullptr : query, (index->checked || index == query) ? nullptr : index};
-        for (int u = 0; u < 2; ++u)
-            if (unchecked[u])
-                KZ_HIP(hipMemcpyAsync(ctx->h_counters + 44 + 10 * u, unchecked[u]->d_stats, 40, hipMemcpyDeviceToHost, ctx->stream));
+        int spec_R = 0;   // rows the speculative launches below covered
+        hipError_t es;
         {
-            const hipError_t es = hipStreamSynchronize(ctx->stream);
-            const int spec_R = spec.R;
-            kz_spec_release(ctx, spec);   // (stream-ordered pool: the launches that used the buffers are on the stream)
-            spec.R = spec_R;
-            KZ_HIP(es);
+            // SPECULATIVE RESCUE (above kz_escalate_rows): the exact kernels for up to R uncertified rows, before the count is known
+            KzSpec spec;   // (its buffers go right after the read-back -- stream-ordered: the launches that used them are on the stream)
+            if (!exact_only && !(dual && dual->raw_lists) && tier != KZ_TIER_F32) {
+                const int R = kz_spec_rows(ctx, index, k_eff);
+                if (R > 0) {
+                    rc = kz_spec_rescue(ctx, spec, R, query, fp.row_map ? 0 : cq_begin, fail_list, fail_count, index, k, exclude_self, d_self_ids,
+                                        fp.out_dist, fp.out_ind);
+                    if (rc != KZ_OK) return rc;
+                    if (spec.R > 0) KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+                }
+            }
+            KZ_HIP(hipMemcpyAsync(ctx->h_counters + 8, fail_count, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            for (int u = 0; u < 2; ++u)
+                if (unchecked[u])
+                    KZ_HIP(hipMemcpyAsync(ctx->h_counters + 44 + 10 * u, unchecked[u]->d_stats, 40, hipMemcpyDeviceToHost, ctx->stream));
+            es = hipStreamSynchronize(ctx->stream);
+            spec_R = spec.R;
         }
-        if (stamp_buf) {   // (diagnostic: start / end of every workgroup of the sweep, in work-table order, appended to the file)
+        KZ_HIP(es);
+        if (stamp_buf.get()) {   // (diagnostic: start / end of every workgroup of the sweep, in work-table order, appended to the file)
             std::vector<unsigned long long> hs((size_t)W * 130);
-            KZ_HIP(hipMemcpy(hs.data(), stamp_buf, (size_t)W * (16 + 1024), hipMemcpyDeviceToHost));
-            kz_pool_free(ctx, stamp_buf, 0);
+            KZ_HIP(hipMemcpy(hs.data(), stamp_buf.get(), (size_t)W * (16 + 1024), hipMemcpyDeviceToHost));
+            stamp_buf.reset();
             if (FILE* f = fopen(getenv("KZ_STAMP_FILE"), "a")) {
                 fprintf(f, "# launch W=%d n_qtiles=%d n_ytiles=%d slices=%d\n", W, n_qtiles, n_ytiles, n_slices);
                 for (int w = 0; w < W; ++w) {
@@ -3102,7 +3069,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                                   index->n >= 65536 && kz_range_shapes_ok(ctx, query, index);
         const bool exact_direct = (tier == KZ_TIER_BF && !dual && n_fail > 0 && n_fail <= KZ_K_EXACT_DIRECT_ROWS) || range_direct;
         // (the speculative launches behind the finalize kernel have answered them all)
-        const bool rescued = spec.R > 0 && n_fail > 0 && n_fail <= spec.R;
+        const bool rescued = spec_R > 0 && n_fail > 0 && n_fail <= spec_R;
         if (rescued) {
             KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
             fb_ms += ms;
@@ -3128,42 +3095,41 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             //  500k, k = 50: 4.7 -> 1.7 ms per step)
             const bool crowding_only = KP_esc > KP && n_fail <= KZ_ESC_SHORT_MAX_ROWS;
             // what the re-search asks for: (operand tier, list length) -- never what this pass just tried
-            int next_prec, next_kp;
+            KzResearch next;
             if (!widen) {   // fp16 with its longest lists, or fp16 altogether, has failed: better operands, this call's own list length
-                next_prec = (tier == KZ_TIER_H && esc_bf && (long_pieces == 0 || fp16_hard)) ? 2 : 1;
+                next.prec = (tier == KZ_TIER_H && esc_bf && (long_pieces == 0 || fp16_hard)) ? 2 : 1;
                 // (the float32 operands are the LAST approximate tier and their a-priori bound is the loosest: with this call's own
                 //  list length -- 16 for k = 10 -- the K'-th key lies a handful of keys below the k-th and inside the bound wherever
                 //  the keys are dense; lists of 64 certify such rows instead of handing them to the exact kernels at ~60 us a row:
                 //  300k x 300k x 96, clusters of very different spread: 9 968 rows to the exact kernels and 726 ms per call before, none and
                 //  169 ms now; lists of 128 for every call: bench.py "hard", k = 50, 118 -> 225 ms -- its lists of 64 were long enough)
-                next_kp = ((next_prec == 1 || wide_route) && KP_class < 64) ? 64 : 0;
+                next.min_kp = ((next.prec == 1 || wide_route) && KP_class < 64) ? 64 : 0;
             } else if (KP == 16 && KSEL == 0 && KZ_K_ESC_SHORT && n_fail <= KZ_ESC_SHORT_MAX_ROWS) {
-                next_prec = 0;
-                next_kp = -1;   // a handful of rows of a K' = 16 pass: more lists of 16
+                next.prec = 0;
+                next.more_lists = true;   // a handful of rows of a K' = 16 pass: more lists of 16
             } else {
-                const int len = crowding_only ? KP_esc : (KP_esc * 4 < 128 ? KP_esc * 4 : 128);
+                next.prec = 0;
+                next.min_kp = crowding_only ? KP_esc : (KP_esc * 4 < 128 ? KP_esc * 4 : 128);
                 // (after a short-list pass: one LONG list -- unless many rows failed and the callee can still add ranges)
-                const bool long_only = KP_esc > KP && (crowding_only || long_pieces >= 16);
-                next_prec = 0;
-                next_kp = (long_only ? 1000 : 0) + len;
+                next.no_short = KP_esc > KP && (crowding_only || long_pieces >= 16);
             }
             // EARLY RANGE RE-SEARCH (kz_range.h "grouped"): thousands of rows the split-bf16 operands could not certify are, on data
             // with clusters far tighter than its extent, rows the float32 operands cannot certify either -- they used to cost a sweep
             // of the whole index there (85 of 180 ms per direction, 200 k x 200 k x 200) before the exact kernels got them.  The
             // groups are tried HERE: rows that share a representative's range are answered by the exact kernels at once; the others
             // go on to the next tier as before.
-            int* early_left = nullptr;
+            KzPoolBuf<int> early_left;
             const int* esc_list = fail_list;
             // (NOT on what an fp16 pass leaves: rows that only lack margin in ranks -- 40 tight clusters, 100 k x 101 k x 128 -- are
             //  cheaper on the ladder's wide route than as 2.4e8 exact pairs: 26.5 -> 33.7 ms with the groups tried there, removed)
             if (tier == KZ_TIER_BF && !dual && n_fail >= KZ_RG_MIN_ROWS && kz_range_shapes_ok(ctx, query, index)) {
-                int* fl0 = nullptr;
-                double* tau0 = nullptr;
-                rc = kz_pool_alloc(ctx, (size_t)n_fail * sizeof(int), (void**)&fl0);
-                if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * 8, (void**)&tau0);
-                if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * sizeof(int), (void**)&early_left);
-                if (rc == KZ_OK && (hipMemcpyAsync(fl0, fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                                    hipMemcpyAsync(tau0, ps.fail_tau, (size_t)n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)) {
+                KzPoolBuf<int> fl0;
+                KzPoolBuf<double> tau0;
+                rc = fl0.alloc(ctx, (size_t)n_fail * sizeof(int));
+                if (rc == KZ_OK) rc = tau0.alloc(ctx, (size_t)n_fail * 8);
+                if (rc == KZ_OK) rc = early_left.alloc(ctx, (size_t)n_fail * sizeof(int));
+                if (rc == KZ_OK && (hipMemcpyAsync(fl0.get(), fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+                                    hipMemcpyAsync(tau0.get(), ps.fail_tau, (size_t)n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)) {
                     kz_set_error("kz_knn: copying the uncertified rows failed");
                     rc = KZ_ERR_HIP;
                 }
@@ -3172,20 +3138,16 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 const bool no_mem = rc == KZ_ERR_NOMEM;   // (no room for the lists: the next tier as before -- the step is an optimisation)
                 if (rc == KZ_OK) {
                     KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-                    rc = kz_range_rescue(ctx, query, fp.row_map ? 0 : cq_begin, fl0, tau0, n_fail, index, k, exclude_self, d_self_ids, fp.out_dist,
-                                         fp.out_ind, early_left, &n_after, &pairs, &grouped, true, KZ_RANGE_EARLY_PER_ROW);
+                    rc = kz_range_rescue(ctx, query, fp.row_map ? 0 : cq_begin, fl0.get(), tau0.get(), n_fail, index, k, exclude_self, d_self_ids,
+                                         fp.out_dist, fp.out_ind, early_left.get(), &n_after, &pairs, &grouped, true, KZ_RANGE_EARLY_PER_ROW);
                 }
-                kz_pool_free(ctx, fl0, 0);
-                kz_pool_free(ctx, tau0, 0);
+                fl0.reset();
+                tau0.reset();
                 if (no_mem) {
-                    kz_pool_free(ctx, early_left, 0);
-                    early_left = nullptr;
+                    early_left.reset();
                     rc = KZ_OK;
                 } else {
-                    if (rc != KZ_OK) {
-                        kz_pool_free(ctx, early_left, 0);
-                        return rc;
-                    }
+                    if (rc != KZ_OK) return rc;
                     KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
                     KZ_HIP(hipStreamSynchronize(ctx->stream));
                     KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
@@ -3195,23 +3157,22 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                     n_range_pairs += pairs;
                     n_fail_total += n_fail - n_after;   // (answered by the exact kernels)
                     n_fail = n_after;
-                    esc_list = early_left;
+                    esc_list = early_left.get();
                 }
             }
             kz_knn_stats st2;
             memset(&st2, 0, sizeof(st2));
             // (fp16 found hard after the fact, no probe beforehand: the ladder on the failed rows -- top-level calls only)
-            const bool ladder = fp16_hard && !wide_route && next_prec == 2 && !probed && kp_min == 0 && forced_lists == 0 && precision_override < 0 &&
-                                !(dual && dual->probed);
+            const bool ladder = fp16_hard && !wide_route && next.prec == 2 && !probed && default_request && !(dual && dual->probed);
             ms = 0;
             if (n_fail == 0) {
             } else if (ladder)
-                rc = kz_escalate_ladder(ctx, query, fp.row_map ? 0 : cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, next_prec,
-                                        next_kp, fp.out_dist, fp.out_ind, &st2, &ms);
+                rc = kz_escalate_ladder(ctx, query, fp.row_map ? 0 : cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, next,
+                                        fp.out_dist, fp.out_ind, &st2, &ms);
             else
-                rc = kz_escalate_rows(ctx, query, fp.row_map ? 0 : cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, next_prec,
-                                      next_kp, fp.out_dist, fp.out_ind, &st2, &ms);
-            kz_pool_free(ctx, early_left, 0);
+                rc = kz_escalate_rows(ctx, query, fp.row_map ? 0 : cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, next,
+                                      fp.out_dist, fp.out_ind, &st2, &ms);
+            early_left.reset();
             if (rc != KZ_OK) return rc;
             fb_ms += ms;
             n_escalated += n_fail + st2.n_escalated_rows;
@@ -3236,47 +3197,45 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             // exact brute force in batches; the fail list lives at the end of the scratch block, the value matrix
             // goes to a separate allocation so that the list is not overwritten by a scratch regrow.
             KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-            int* fl = nullptr;
-            rc = kz_pool_alloc(ctx, (size_t)n_fail * sizeof(int), (void**)&fl);  // stream-ordered pool: no device sync
+            // (released when this block ends, stream-ordered: fl, cand_v, cand_i)
+            KzPoolBuf<int> cand_i;
+            KzPoolBuf<double> cand_v;
+            KzPoolBuf<int> fl;
+            rc = fl.alloc(ctx, (size_t)n_fail * sizeof(int));  // stream-ordered pool: no device sync
             if (rc != KZ_OK) return rc;
-            KZ_HIP(hipMemcpyAsync(fl, fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+            KZ_HIP(hipMemcpyAsync(fl.get(), fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
             // RANGE RE-SEARCH (kz_range.h): the exact kernels on the pairs that can matter; the rows it hands back -- and every
             // row where it does not apply -- go on against the whole index below
             int n_dense = n_fail;
             if (!exact_only && n_fail >= KZ_RANGE_MIN_ROWS && kz_range_shapes_ok(ctx, query, index)) {
-                double* tau = nullptr;
-                int* left = nullptr;
-                rc = kz_pool_alloc(ctx, (size_t)n_fail * 8, (void**)&tau);
-                if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * sizeof(int), (void**)&left);
-                if (rc == KZ_OK && hipMemcpyAsync(tau, ps.fail_tau, (size_t)n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+                KzPoolBuf<int> left;
+                KzPoolBuf<double> tau;
+                rc = tau.alloc(ctx, (size_t)n_fail * 8);
+                if (rc == KZ_OK) rc = left.alloc(ctx, (size_t)n_fail * sizeof(int));
+                if (rc == KZ_OK && hipMemcpyAsync(tau.get(), ps.fail_tau, (size_t)n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
                     kz_set_error("kz_knn: copying the bounds of the uncertified rows failed");
                     rc = KZ_ERR_HIP;
                 }
                 long long pairs = 0, grouped = 0;
                 const bool no_mem = rc == KZ_ERR_NOMEM;   // (no room for the lists: the whole-index kernels as before)
                 if (rc == KZ_OK)
-                    rc = kz_range_rescue(ctx, query, cq_begin, fl, tau, n_fail, index, k, exclude_self, d_self_ids, fp.out_dist, fp.out_ind, left,
-                                         &n_dense, &pairs, &grouped);
-                kz_pool_free(ctx, tau, 0);
+                    rc = kz_range_rescue(ctx, query, cq_begin, fl.get(), tau.get(), n_fail, index, k, exclude_self, d_self_ids, fp.out_dist,
+                                         fp.out_ind, left.get(), &n_dense, &pairs, &grouped);
+                tau.reset();
                 if (no_mem) {
-                    kz_pool_free(ctx, left, 0);
+                    left.reset();
                     rc = KZ_OK;
                 } else {
-                    if (rc != KZ_OK) {
-                        kz_pool_free(ctx, left, 0);
-                        kz_pool_free(ctx, fl, 0);
-                        return rc;
-                    }
+                    if (rc != KZ_OK) return rc;
                     n_range += n_fail - n_dense;
                     n_range_pairs += pairs;
                     n_range_group += grouped;
-                    kz_pool_free(ctx, fl, 0);   // (the rows handed back take the list's place)
-                    fl = left;
+                    fl = std::move(left);   // (the rows handed back take the list's place)
                 }
             }
             n_fail = n_dense;
             if (n_fail == 0) {
-                kz_pool_free(ctx, fl, 0);
+                fl.reset();
                 KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
                 KZ_HIP(hipStreamSynchronize(ctx->stream));
                 KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
@@ -3294,72 +3253,57 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             if (batch > 65535) batch = 65535;
             void* vals = nullptr;
             rc = kz_scratch(ctx, (size_t)batch * (size_t)index->n * 8, &vals);
-            if (rc != KZ_OK) {
-                kz_pool_free(ctx, fl, 0);
-                return rc;
-            }
+            if (rc != KZ_OK) return rc;
             const int dist_blocks = (int)((index->n + 3) / 4);
             const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
             const size_t sel_lds = (size_t)k_sel * 12 + 16;
             if (sel_lds > 65536) {
-                kz_pool_free(ctx, fl, 0);
                 kz_set_error("kz_knn: k=%d is too large for the exact selection kernel", k_eff);
                 return KZ_ERR_UNSUPPORTED;
             }
             // rows of more than four chunks: the selection in two levels (kz_exact_chunk_kernel)
             const int n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
             const bool two_level = n_chunks > 4 && k_sel <= KZ_EXACT_CHUNK;
-            double* cand_v = nullptr;
-            int* cand_i = nullptr;
             if (two_level) {
-                rc = kz_pool_alloc(ctx, (size_t)batch * n_chunks * k_sel * 8, (void**)&cand_v);
-                if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)batch * n_chunks * k_sel * 4, (void**)&cand_i);
-                if (rc != KZ_OK) {
-                    kz_pool_free(ctx, cand_v, 0);
-                    kz_pool_free(ctx, fl, 0);
-                    return rc;
-                }
+                rc = cand_v.alloc(ctx, (size_t)batch * n_chunks * k_sel * 8);
+                if (rc == KZ_OK) rc = cand_i.alloc(ctx, (size_t)batch * n_chunks * k_sel * 4);
+                if (rc != KZ_OK) return rc;
             }
             for (int b0 = 0; b0 < n_fail; b0 += (int)batch) {
                 const int nb = (n_fail - b0 < batch) ? (n_fail - b0) : (int)batch;
                 if (index->dtype == KZ_F32) {
                     bool lanes = false;
                     if (!no_gemm_form) {
-                        rc = kz_launch_exact_lanes(ctx, fl, b0, nb, cq_begin, query, index, metric, (double*)vals, &lanes);
-                        if (rc != KZ_OK) {
-                            kz_pool_free(ctx, fl, 0);
-                            kz_pool_free(ctx, cand_v, 0);
-                            kz_pool_free(ctx, cand_i, 0);
-                            return rc;
-                        }
+                        rc = kz_launch_exact_lanes(ctx, fl.get(), b0, nb, cq_begin, query, index, metric, (double*)vals, &lanes);
+                        if (rc != KZ_OK) return rc;
                     }
                     if (lanes) {
                     } else if (no_gemm_form)
-                        kz_launch_family_dist<float>(ctx, fl, b0, nb, cq_begin, query, index, (double*)vals);
-                    else if (ctx->exact_rows && kz_launch_exact_rows(ctx, fl, b0, nb, cq_begin, query, index, metric, (double*)vals)) {
+                        kz_launch_family_dist<float>(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
+                    else if (ctx->exact_rows && kz_launch_exact_rows(ctx, fl.get(), b0, nb, cq_begin, query, index, metric, (double*)vals)) {
                     } else
-                        hipLaunchKernelGGL(kz_exact_dist_kernel<float>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl, b0,
+                        hipLaunchKernelGGL(kz_exact_dist_kernel<float>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl.get(), b0,
                                            cq_begin, (const float*)query->raw, (const float*)index->raw, query->sqn, index->sqn,
                                            index->n, (int)index->d, metric, index->mink_p, (double*)vals);
                     if (two_level)
                         hipLaunchKernelGGL(k_sel >= 24 && ctx->exact_rows ? kz_exact_chunk_radix_kernel : kz_exact_chunk_kernel, dim3(n_chunks, nb), dim3(256), 0,
-                                           ctx->stream, (const double*)vals, index->n, k_sel, n_chunks, cand_v, cand_i, (const int*)nullptr);
-                    hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl, b0, cq_begin,
-                                       two_level ? (const double*)cand_v : (const double*)vals, two_level ? (const int*)cand_i : (const int*)nullptr,
+                                           ctx->stream, (const double*)vals, index->n, k_sel, n_chunks, cand_v.get(), cand_i.get(), (const int*)nullptr);
+                    hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl.get(), b0, cq_begin,
+                                       two_level ? (const double*)cand_v.get() : (const double*)vals, two_level ? (const int*)cand_i.get() : (const int*)nullptr,
                                        two_level ? (int64_t)n_chunks * k_sel : index->n, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p,
                                        fp.out_dist, fp.out_ind);
                 } else {
                     if (no_gemm_form)
-                        kz_launch_family_dist<double>(ctx, fl, b0, nb, cq_begin, query, index, (double*)vals);
+                        kz_launch_family_dist<double>(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
                     else
-                        hipLaunchKernelGGL(kz_exact_dist_kernel<double>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl, b0,
+                        hipLaunchKernelGGL(kz_exact_dist_kernel<double>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl.get(), b0,
                                            cq_begin, (const double*)query->raw, (const double*)index->raw, query->sqn, index->sqn,
                                            index->n, (int)index->d, metric, index->mink_p, (double*)vals);
                     if (two_level)
                         hipLaunchKernelGGL(k_sel >= 24 && ctx->exact_rows ? kz_exact_chunk_radix_kernel : kz_exact_chunk_kernel, dim3(n_chunks, nb), dim3(256), 0,
-                                           ctx->stream, (const double*)vals, index->n, k_sel, n_chunks, cand_v, cand_i, (const int*)nullptr);
-                    hipLaunchKernelGGL(kz_exact_select_kernel<double>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl, b0, cq_begin,
-                                       two_level ? (const double*)cand_v : (const double*)vals, two_level ? (const int*)cand_i : (const int*)nullptr,
+                                           ctx->stream, (const double*)vals, index->n, k_sel, n_chunks, cand_v.get(), cand_i.get(), (const int*)nullptr);
+                    hipLaunchKernelGGL(kz_exact_select_kernel<double>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl.get(), b0, cq_begin,
+                                       two_level ? (const double*)cand_v.get() : (const double*)vals, two_level ? (const int*)cand_i.get() : (const int*)nullptr,
                                        two_level ? (int64_t)n_chunks * k_sel : index->n, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p,
                                        fp.out_dist, fp.out_ind);
                 }
@@ -3367,9 +3311,6 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            kz_pool_free(ctx, fl, 0);
-            kz_pool_free(ctx, cand_v, 0);
-            kz_pool_free(ctx, cand_i, 0);
             if (e != hipSuccess) {
                 kz_set_error("kz_knn: exact fallback failed: %s", hipGetErrorString(e));
                 return KZ_ERR_HIP;
@@ -3405,7 +3346,7 @@ extern "C" int kz_knn(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int6
                       int exclude_self, double* d_dist, int64_t* d_ind, kz_knn_stats* stats) {
     // (the matrices are logically const for the caller: kz_knn only attaches lazily built operand images to them)
     return kz_knn_impl(ctx, const_cast<kz_matrix*>(query), q_begin, q_count, const_cast<kz_matrix*>(index), k, exclude_self, nullptr,
-                       -1, 0, d_dist, d_ind, stats, nullptr);
+                       KzResearch(), d_dist, d_ind, stats, nullptr);
 }
 
 #include "kz_knn_dual.h"

@@ -431,11 +431,28 @@ static int kz_knn_dual_separately(kz_ctx* ctx, kz_matrix* a, kz_matrix* b, int k
                                   int precision_override = -1, int wide = 0) {
     // (precision_override = 2: the caller's probe has found the data hard for fp16 -- both searches start at the split-bf16 tier
     //  without probing again, with lists of at least 64 as an ordinary search's own probe would have chosen;
-    //  wide > 0: the probe has found that the fp16 tier's WIDE route certifies this data -- both searches take it, kz_knn_impl kp_min = -wide)
-    const int kp_min = wide > 0 ? -wide : (precision_override == 2 ? 64 : 0);
-    int rc = kz_knn_impl(ctx, a, 0, a->n, b, k, 0, nullptr, precision_override, kp_min, d_dist_ab, d_ind_ab, stats_ab, nullptr);
-    if (rc == KZ_OK) rc = kz_knn_impl(ctx, b, 0, b->n, a, k, 0, nullptr, precision_override, kp_min, d_dist_ba, d_ind_ba, stats_ba, nullptr);
+    //  wide > 0: the probe has found that the fp16 tier's WIDE route certifies this data -- both searches take it)
+    KzResearch rs;
+    rs.prec = precision_override;
+    if (wide > 0)
+        rs.wide_lists = wide;
+    else if (precision_override == 2)
+        rs.min_kp = 64;
+    int rc = kz_knn_impl(ctx, a, 0, a->n, b, k, 0, nullptr, rs, d_dist_ab, d_ind_ab, stats_ab, nullptr);
+    if (rc == KZ_OK) rc = kz_knn_impl(ctx, b, 0, b->n, a, k, 0, nullptr, rs, d_dist_ba, d_ind_ba, stats_ba, nullptr);
     return rc;
+}
+// The re-search of the rows a chain left uncertified (n_fail of n_rows, lists of KPr): more than half -- the split-bf16 operands at
+// once; few -- longer lists on the same operands (K' = 16: more lists instead of longer ones)
+static KzResearch kz_dual_research(const kz_ctx* ctx, int n_fail, int64_t n_rows, int KPr) {
+    KzResearch rs;
+    rs.prec = ((int64_t)n_fail * 2 > n_rows && ctx->esc_bf) ? 2 : -1;
+    if (rs.prec == 2 || (int64_t)n_fail * 8 > n_rows || KPr >= 128) return rs;
+    if (KPr == 16 && KZ_K_ESC_SHORT && n_fail <= KZ_ESC_SHORT_MAX_ROWS)
+        rs.more_lists = true;
+    else
+        rs.min_kp = KPr * 4 < 128 ? KPr * 4 : 128;
+    return rs;
 }
 
 // Rank of the sample key that becomes a row's event threshold (kz_knn_dual "rank").  Model, per candidate rank r: stride s =
@@ -578,7 +595,7 @@ static int kz_dual_enqueue_chain(KzRevChain& r) {
             // (the handful of rows this chain leaves uncertified -- short of events, an overflowing buffer, a near-tie -- answered by the
             //  exact kernels on this chain's stream before the host knows the count; fail_list holds matrix rows)
             const int R = kz_spec_rows(ctx, r.im, r.k);
-            if (R > 0 && r.spec->vals) {   // (the buffers were allocated ahead: kz_knn_dual)
+            if (R > 0 && r.spec->vals.get()) {   // (the buffers were allocated ahead: kz_knn_dual)
                 const int rc3 = kz_spec_rescue(ctx, *r.spec, R, r.qm, 0, r.fail_list, r.fail_count, r.im, r.k, 0, nullptr, r.d_dist, r.d_ind);
                 if (rc3 != KZ_OK) return rc3;
             }
@@ -722,110 +739,75 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     // overflowing log is detected and the direction redone.
     const long long log_cap = (long long)((double)b->n * rank * stride * 1.5) + (1 << 20);
 
-    unsigned short *s_packed = nullptr, *p_packed = nullptr, *q_packed = nullptr;
-    float *s_bias = nullptr, *p_bias = nullptr, *q_bias = nullptr, *q_key = nullptr, *q_key_s = nullptr, *theta = nullptr, *theta_s = nullptr, *theta_min = nullptr, *floor_ = nullptr, *qnb = nullptr, *col_key = nullptr, *qfloor = nullptr;
-    int *ev_cnt = nullptr, *col_idx = nullptr, *fail_list = nullptr, *iota = nullptr, *perm = nullptr, *q_iota = nullptr, *q_sorted = nullptr, *row_map = nullptr;
-    uint2* ev = nullptr;
-    void *log_keys = nullptr, *log_meta = nullptr;
-    unsigned long long* d_cnt = nullptr;   // [0] log counter, [1] events filed, [2] rows with an overflowing buffer, [16 ..] 32 spread pairs of [1], [2]
-    // buffers of the nested stages (released with everything else)
-    unsigned short *s3_packed = nullptr, *ss_packed = nullptr;
-    float *s3_bias = nullptr, *ss_bias = nullptr, *theta3 = nullptr, *theta3_s = nullptr, *theta3_min = nullptr, *floor3 = nullptr, *floor3m = nullptr,
-          *qnb_b = nullptr, *col3_key = nullptr;
-    int *iota3 = nullptr, *perm3 = nullptr, *rm3 = nullptr, *row_map_b = nullptr, *ev3_cnt = nullptr, *col3_idx = nullptr, *fail3 = nullptr, *sev_cnt = nullptr;
-    uint2 *ev3 = nullptr, *sev = nullptr;
-    void *log3_keys = nullptr, *log3_meta = nullptr;
-    unsigned long long* d_cnt3 = nullptr;
-    auto release_nested = [&]() {
-        void* bufs[] = {s3_packed, ss_packed, s3_bias, ss_bias, theta3, theta3_s, theta3_min, floor3, floor3m, qnb_b, col3_key, iota3, perm3, rm3,
-                        row_map_b, ev3_cnt, col3_idx, fail3, sev_cnt, ev3, sev, log3_keys, log3_meta, d_cnt3};
-        for (void* q : bufs) kz_pool_free(ctx, q, 0);
-        s3_packed = ss_packed = nullptr; s3_bias = ss_bias = theta3 = theta3_s = theta3_min = floor3 = floor3m = qnb_b = col3_key = nullptr;
-        iota3 = perm3 = rm3 = row_map_b = ev3_cnt = col3_idx = fail3 = sev_cnt = nullptr; ev3 = sev = nullptr; log3_keys = log3_meta = nullptr; d_cnt3 = nullptr;
-    };
-    KzSpec spec_ba, spec_s3;   // (buffers of the two chains' speculative exact launches: released with everything else, behind the second stream's sync)
-    auto release = [&]() {
-        release_nested();
-        kz_spec_release(ctx, spec_ba);
-        kz_spec_release(ctx, spec_s3);
-        kz_pool_free(ctx, s_packed, 0);
-        kz_pool_free(ctx, s_bias, 0);
-        kz_pool_free(ctx, p_packed, 0);
-        kz_pool_free(ctx, p_bias, 0);
-        kz_pool_free(ctx, q_packed, 0);
-        kz_pool_free(ctx, q_bias, 0);
-        kz_pool_free(ctx, q_key, 0);
-        kz_pool_free(ctx, q_key_s, 0);
-        kz_pool_free(ctx, q_iota, 0);
-        kz_pool_free(ctx, q_sorted, 0);
-        kz_pool_free(ctx, row_map, 0);
-        kz_pool_free(ctx, theta_s, 0);
-        kz_pool_free(ctx, theta_min, 0);
-        kz_pool_free(ctx, iota, 0);
-        kz_pool_free(ctx, perm, 0);
-        kz_pool_free(ctx, theta, 0);
-        kz_pool_free(ctx, floor_, 0);
-        kz_pool_free(ctx, qnb, 0);
-        kz_pool_free(ctx, qfloor, 0);
-        kz_pool_free(ctx, col_key, 0);
-        kz_pool_free(ctx, ev_cnt, 0);
-        kz_pool_free(ctx, col_idx, 0);
-        kz_pool_free(ctx, fail_list, 0);
-        kz_pool_free(ctx, ev, 0);
-        kz_pool_free(ctx, log_keys, 0);
-        kz_pool_free(ctx, log_meta, 0);
-        kz_pool_free(ctx, d_cnt, 0);
-    };
+    // Every buffer of the pass is released when the lambda below returns, in this order: the nested stages' (s3_packed .. d_cnt3), the
+    // speculative launches' (spec_ba, spec_s3), then s_packed .. d_cnt -- behind the second stream: `join` waits for it first.
+    // What the call does once they are released: then = 1 both directions by two ordinary searches (kz_knn_dual_separately with
+    // sep_prec, sep_wide), 2 the reverse direction the ordinary way.
+    int then = 0, sep_prec = -1, sep_wide = 0;
+    kz_knn_stats st_ba;
+    memset(&st_ba, 0, sizeof(st_ba));
+    const int rc_pass = [&]() -> int {
+    KzPoolBuf<unsigned long long> d_cnt;   // [0] log counter, [1] events filed, [2] rows with an overflowing buffer, [16 ..] 32 spread pairs of [1], [2]
+    KzPoolBuf<void> log_meta, log_keys;
+    KzPoolBuf<uint2> ev;
+    KzPoolBuf<int> fail_list, col_idx, ev_cnt;
+    KzPoolBuf<float> col_key, qfloor, qnb, floor_, theta;
+    KzPoolBuf<int> perm, iota;
+    KzPoolBuf<float> theta_min, theta_s;
+    KzPoolBuf<int> row_map, q_sorted, q_iota;
+    KzPoolBuf<float> q_key_s, q_key, q_bias;
+    KzPoolBuf<unsigned short> q_packed;
+    KzPoolBuf<float> p_bias;
+    KzPoolBuf<unsigned short> p_packed;
+    KzPoolBuf<float> s_bias;
+    KzPoolBuf<unsigned short> s_packed;
+    KzSpec spec_s3, spec_ba;   // (buffers of the two chains' speculative exact launches)
+    struct NestedBufs {   // (the nested stages, NESTED below)
+        KzPoolBuf<unsigned long long> d_cnt3;
+        KzPoolBuf<void> log3_meta, log3_keys;
+        KzPoolBuf<uint2> sev, ev3;
+        KzPoolBuf<int> sev_cnt, fail3, col3_idx, ev3_cnt, row_map_b, rm3, perm3, iota3;
+        KzPoolBuf<float> col3_key, qnb_b, floor3m, floor3, theta3_min, theta3_s, theta3, ss_bias, s3_bias;
+        KzPoolBuf<unsigned short> ss_packed, s3_packed;
+    } nst;
+    struct Stream2Join {   // (the reverse chains may still run on the second stream: it is done with the buffers before they go)
+        kz_ctx* ctx;
+        ~Stream2Join() {
+            if (ctx->stream2_busy) (void)hipStreamSynchronize(ctx->stream2);
+            ctx->stream2_busy = 0;
+        }
+    } join{ctx};
     const size_t tile_bytes = (size_t)n_slices * 4096;
-    rc = kz_pool_alloc(ctx, (size_t)s_tiles * tile_bytes + 32 * 4096, (void**)&s_packed);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)s_tiles * KZ_TILE * 4, (void**)&s_bias);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_tiles * tile_bytes + 32 * 4096, (void**)&p_packed);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_tiles * tile_bytes + 32 * 4096, (void**)&q_packed);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&q_bias);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&q_key);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&q_key_s);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&q_iota);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&q_sorted);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&row_map);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4, (void**)&p_bias);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4, (void**)&theta_s);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4, (void**)&theta_min);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4, (void**)&iota);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4, (void**)&perm);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4, (void**)&theta);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4, (void**)&floor_);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&qnb);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b->n * KPr * 4, (void**)&col_key);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b->n * KPr * 4, (void**)&col_idx);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * 4 * KZ_EVC, (void**)&ev_cnt);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b->n * 4, (void**)&fail_list);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)b_pad * ev_cap * 8, (void**)&ev);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)log_cap * 16, &log_keys);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)log_cap * 8, &log_meta);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, KZ_DUAL_CNT_BYTES, (void**)&d_cnt);
-    if (rc != KZ_OK) {
-        release();
-        // (not enough memory for the event buffers: the two ordinary searches need far less)
-        return kz_knn_dual_separately(ctx, a, b, k, d_dist_ab, d_ind_ab, d_dist_ba, d_ind_ba, stats_ab, stats_ba);
+    rc = s_packed.alloc(ctx, (size_t)s_tiles * tile_bytes + 32 * 4096);
+    if (rc == KZ_OK) rc = s_bias.alloc(ctx, (size_t)s_tiles * KZ_TILE * 4);
+    if (rc == KZ_OK) rc = p_packed.alloc(ctx, (size_t)b_tiles * tile_bytes + 32 * 4096);
+    if (rc == KZ_OK) rc = q_packed.alloc(ctx, (size_t)a_tiles * tile_bytes + 32 * 4096);
+    if (rc == KZ_OK) rc = q_bias.alloc(ctx, (size_t)a_pad * 4);
+    if (rc == KZ_OK) rc = q_key.alloc(ctx, (size_t)a_pad * 4);
+    if (rc == KZ_OK) rc = q_key_s.alloc(ctx, (size_t)a_pad * 4);
+    if (rc == KZ_OK) rc = q_iota.alloc(ctx, (size_t)a_pad * 4);
+    if (rc == KZ_OK) rc = q_sorted.alloc(ctx, (size_t)a_pad * 4);
+    if (rc == KZ_OK) rc = row_map.alloc(ctx, (size_t)a_pad * 4);
+    if (rc == KZ_OK) rc = p_bias.alloc(ctx, (size_t)b_pad * 4);
+    if (rc == KZ_OK) rc = theta_s.alloc(ctx, (size_t)b_pad * 4);
+    if (rc == KZ_OK) rc = theta_min.alloc(ctx, (size_t)b_pad * 4);
+    if (rc == KZ_OK) rc = iota.alloc(ctx, (size_t)b_pad * 4);
+    if (rc == KZ_OK) rc = perm.alloc(ctx, (size_t)b_pad * 4);
+    if (rc == KZ_OK) rc = theta.alloc(ctx, (size_t)b_pad * 4);
+    if (rc == KZ_OK) rc = floor_.alloc(ctx, (size_t)b_pad * 4);
+    if (rc == KZ_OK) rc = qnb.alloc(ctx, (size_t)a_pad * 4);
+    if (rc == KZ_OK) rc = col_key.alloc(ctx, (size_t)b->n * KPr * 4);
+    if (rc == KZ_OK) rc = col_idx.alloc(ctx, (size_t)b->n * KPr * 4);
+    if (rc == KZ_OK) rc = ev_cnt.alloc(ctx, (size_t)b_pad * 4 * KZ_EVC);
+    if (rc == KZ_OK) rc = fail_list.alloc(ctx, (size_t)b->n * 4);
+    if (rc == KZ_OK) rc = ev.alloc(ctx, (size_t)b_pad * ev_cap * 8);
+    if (rc == KZ_OK) rc = log_keys.alloc(ctx, (size_t)log_cap * 16);
+    if (rc == KZ_OK) rc = log_meta.alloc(ctx, (size_t)log_cap * 8);
+    if (rc == KZ_OK) rc = d_cnt.alloc(ctx, KZ_DUAL_CNT_BYTES);
+    if (rc != KZ_OK) {   // (not enough memory for the event buffers: the two ordinary searches need far less)
+        then = 1;
+        return KZ_OK;
     }
-#define KZ_DUAL_HIP(call)                                                                              \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            kz_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);   \
-            release();                                                                                 \
-            return KZ_ERR_HIP;                                                                         \
-        }                                                                                              \
-    } while (0)
-#define KZ_DUAL_RC(expr)      \
-    do {                      \
-        rc = (expr);          \
-        if (rc != KZ_OK) {    \
-            release();        \
-            return rc;        \
-        }                     \
-    } while (0)
-
     // ---- POPULATION FLOOR of the forward lists (kz_knn.hip "POPULATION FLOOR"): a strided probe of A's rows -- an escalation-style
     // sub-search, exact float64 results written to their places -- gives the model.  It runs FIRST: it is this call's tier probe as well (below), and a call
     // that is handed to two ordinary searches should not have enqueued a sample sweep.
@@ -847,15 +829,17 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     if (want_floor || want_tier) {
         const int n_probe = want_floor ? KZ_K_FLOOR_PROBE : (ctx->tier_probe < 1024 ? ctx->tier_probe : 1024);
         const int64_t pstride = a->n / n_probe;
-        int* plist = nullptr;
-        rc = kz_pool_alloc(ctx, (size_t)n_probe * sizeof(int), (void**)&plist);
-        if (rc == KZ_OK && want_floor) rc = kz_pool_alloc(ctx, (size_t)a_pad * 4, (void**)&qfloor);
+        KzPoolBuf<int> plist;
+        rc = plist.alloc(ctx, (size_t)n_probe * sizeof(int));
+        if (rc == KZ_OK && want_floor) rc = qfloor.alloc(ctx, (size_t)a_pad * 4);
         kz_knn_stats stp;
         memset(&stp, 0, sizeof(stp));
         float pms = 0;
         if (rc == KZ_OK) {
-            hipLaunchKernelGGL(kz_strided_rows_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, plist, n_probe, pstride);
-            rc = kz_escalate_rows(ctx, a, 0, plist, n_probe, b, k, 0, nullptr, 0, 0, d_dist_ab, d_ind_ab, &stp, &pms);
+            hipLaunchKernelGGL(kz_strided_rows_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, plist.get(), n_probe, pstride);
+            KzResearch probe_rs;
+            probe_rs.prec = 0;
+            rc = kz_escalate_rows(ctx, a, 0, plist.get(), n_probe, b, k, 0, nullptr, probe_rs, d_dist_ab, d_ind_ab, &stp, &pms);
         }
         if (rc == KZ_OK && want_tier) tier_probed = true;
         // (the rows the probe's FIRST pass left uncertified, once each)
@@ -871,28 +855,24 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
                 kz_knn_stats stw;
                 memset(&stw, 0, sizeof(stw));
                 float wms = 0;
-                rc = kz_escalate_rows(ctx, a, 0, plist, n_probe, b, k, 0, nullptr, 0, -ctx->wide_lists, d_dist_ab, d_ind_ab, &stw, &wms);
+                rc = kz_escalate_rows(ctx, a, 0, plist.get(), n_probe, b, k, 0, nullptr, kz_research_wide(ctx->wide_lists), d_dist_ab, d_ind_ab, &stw,
+                                      &wms);
                 if (rc == KZ_OK && stw.wide_lists > 0 && (int64_t)stw.n_first_pass_fail * 4 <= n_probe &&
                     (int64_t)stw.n_first_pass_fail * 2 < stp.n_first_pass_fail)
                     wide = ctx->wide_lists;
             }
-            if (rc != KZ_OK || wide > 0 || (int64_t)stp.n_first_pass_fail * 2 > n_probe) {
-                kz_pool_free(ctx, plist, 0);
-                release();
-                if (rc != KZ_OK) return rc;
-                return kz_knn_dual_separately(ctx, a, b, k, d_dist_ab, d_ind_ab, d_dist_ba, d_ind_ba, stats_ab, stats_ba, wide > 0 ? -1 : 2, wide);
+            if (rc != KZ_OK) return rc;
+            if (wide > 0 || (int64_t)stp.n_first_pass_fail * 2 > n_probe) {
+                then = 1;
+                sep_prec = wide > 0 ? -1 : 2;
+                sep_wide = wide;
+                return KZ_OK;
             }
         }
-        kz_pool_free(ctx, plist, 0);
+        plist.reset();
         if (rc == KZ_OK && want_floor) rc = kz_floor_model(ctx, d_dist_ab, ia->rowq, n_probe, pstride, k, a->metric, floor_model, &have_floor);
-        if (rc != KZ_OK) {
-            release();
-            return rc;
-        }
-        if (!have_floor) {
-            kz_pool_free(ctx, qfloor, 0);
-            qfloor = nullptr;
-        }
+        if (rc != KZ_OK) return rc;
+        if (!have_floor) qfloor.reset();
     }
 
     // ---- sample sweep's lists.  The threshold is the rank-th best sample key, and the rank-th best of ANY set of distinct sample
@@ -918,29 +898,31 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     };
     int KPs = KP, force_s = 0;
     sample_lists(rank, s_tiles, &KPs, &force_s);
-    KZ_DUAL_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-    KZ_DUAL_HIP(hipMemsetAsync(ev_cnt, 0, (size_t)b_pad * 4 * KZ_EVC, ctx->stream));
-    KZ_DUAL_HIP(hipMemsetAsync(d_cnt, 0, KZ_DUAL_CNT_BYTES, ctx->stream));
+    KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
+    KZ_HIP(hipMemsetAsync(ev_cnt.get(), 0, (size_t)b_pad * 4 * KZ_EVC, ctx->stream));
+    KZ_HIP(hipMemsetAsync(d_cnt.get(), 0, KZ_DUAL_CNT_BYTES, ctx->stream));
     // ---- query side: rows dealt into tiles by |q_c|^2 (load balance), its image and its offsets in that order --------------
-    hipLaunchKernelGGL(kz_dual_c2key_kernel, dim3((unsigned)((a->n + 255) / 256)), dim3(256), 0, ctx->stream, ia->rowq, a->n, q_key);
-    hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_iota, (int)a_pad);
-    KZ_DUAL_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kz_dual_c2key_kernel, dim3((unsigned)((a->n + 255) / 256)), dim3(256), 0, ctx->stream, ia->rowq, a->n, q_key.get());
+    hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_iota.get(), (int)a_pad);
+    KZ_HIP(hipGetLastError());
     if (KZ_K_DUAL_DEAL) {
-        KZ_DUAL_RC(kz_sort_pairs_f32_i32(ctx, q_key, q_key_s, q_iota, q_sorted, (int)a->n, 0));
-        hipLaunchKernelGGL(kz_dual_deal_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_sorted, a->n, a_pad, row_map);
+        rc = kz_sort_pairs_f32_i32(ctx, q_key.get(), q_key_s.get(), q_iota.get(), q_sorted.get(), (int)a->n, 0);
+        if (rc != KZ_OK) return rc;
+        hipLaunchKernelGGL(kz_dual_deal_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_sorted.get(), a->n, a_pad, row_map.get());
     } else {   // tuning knob "dual_deal" = 0: the query rows in their natural order
-        hipLaunchKernelGGL(kz_dual_natural_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, a->n, a_pad, row_map);
+        hipLaunchKernelGGL(kz_dual_natural_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, a->n, a_pad, row_map.get());
     }
-    KZ_DUAL_HIP(hipGetLastError());
-    KZ_DUAL_RC(kz_himage_pack_permuted(a, row_map, q_packed, q_bias));
-    hipLaunchKernelGGL(kz_dual_negbias_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_bias, a->n, a_pad, qnb);
+    KZ_HIP(hipGetLastError());
+    rc = kz_himage_pack_permuted(a, row_map.get(), q_packed.get(), q_bias.get());
+    if (rc != KZ_OK) return rc;
+    hipLaunchKernelGGL(kz_dual_negbias_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_bias.get(), a->n, a_pad, qnb.get());
 
     // ---- NESTED sample (round 5).  The sample sweep b x sample(a) used to be work the main sweep repeated: the main sweep swept ALL
     // of a, the sampled rows included.  Now the sample S is the FIRST s_tiles tiles of the DEALT image of a (a dealt tile is a
     // stratified draw of a's rows -- sorted by |q_c|^2 and dealt round-robin -- whatever order the caller stored them in), the main
     // sweep covers the other tiles only, and everything the sampled rows need comes out of the sample sweep, which is a shared
     // sweep itself (b as its query side, S sorted by threshold as its index side):
-    //   * b's lists over S give tau(t) as before -- and ARE the events of t among the sample rows (kz_dual_theta_kernel, sev);
+    //   * b's lists over S give tau(t) as before -- and ARE the events of t among the sample rows (kz_dual_theta_kernel, nst.sev.get());
     //   * the events of the rows of S (thresholds from a third, small sweep S x sample(b)) become their forward lists, certified
     //     and re-ranked by the ordinary finalize kernel with S as the query side (KzRevChain), failures searched again.
     // Saves 1 / stride of the main sweep (ns: stride 20, C3: 11) for a sample sweep that runs the dual build (+5 .. 10 %) and a
@@ -978,35 +960,36 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     const int sev_cap = ((2 * rank + 16 + 15) & ~15) < 256 ? ((2 * rank + 16 + 15) & ~15) : 256;
     if (nested) {
         const int KPr3 = ctx->dual_rev_long ? (2 * KP < 128 ? 2 * KP : 128) : KP;
-        int rcn = kz_pool_alloc(ctx, (size_t)s3_tiles * tile_bytes + 32 * 4096, (void**)&s3_packed);
-        auto al = [&](size_t bytes, void** out) { if (rcn == KZ_OK) rcn = kz_pool_alloc(ctx, bytes, out); };
-        al((size_t)s3_tiles * KZ_TILE * 4, (void**)&s3_bias);
-        al((size_t)s_tiles * tile_bytes + 32 * 4096, (void**)&ss_packed);
-        al((size_t)s_img_rows * 4, (void**)&ss_bias);
-        al((size_t)s_img_rows * 4, (void**)&theta3);
-        al((size_t)s_img_rows * 4, (void**)&theta3_s);
-        al((size_t)s_img_rows * 4, (void**)&theta3_min);
-        al((size_t)s_img_rows * 4, (void**)&floor3);
-        al((size_t)a_pad * 4, (void**)&floor3m);
-        al((size_t)b_pad * 4, (void**)&qnb_b);
-        al((size_t)s_img_rows * KPr3 * 4, (void**)&col3_key);
-        al((size_t)s_img_rows * KPr3 * 4, (void**)&col3_idx);
-        al((size_t)s_img_rows * 4, (void**)&iota3);
-        al((size_t)s_img_rows * 4, (void**)&perm3);
-        al((size_t)s_img_rows * 4, (void**)&rm3);
-        al((size_t)b_pad * 4, (void**)&row_map_b);
-        al((size_t)s_img_rows * 4 * KZ_EVC, (void**)&ev3_cnt);
-        al((size_t)s_img_rows * 4, (void**)&fail3);
-        al((size_t)b_pad * 4, (void**)&sev_cnt);
-        al((size_t)s_img_rows * ev_cap3 * 8, (void**)&ev3);
-        al((size_t)b->n * sev_cap * 8, (void**)&sev);
-        al((size_t)log_cap3 * 16, &log3_keys);
-        al((size_t)log_cap3 * 8, &log3_meta);
-        al(KZ_DUAL_CNT_BYTES, (void**)&d_cnt3);
-        if (rcn != KZ_OK) {   // (no memory for the nested stages: the classic sample sweep)
-            release_nested();
+        NestedBufs n3;   // (all or nothing)
+        int rcn = n3.s3_packed.alloc(ctx, (size_t)s3_tiles * tile_bytes + 32 * 4096);
+        auto al = [&](auto& buf, size_t bytes) { if (rcn == KZ_OK) rcn = buf.alloc(ctx, bytes); };
+        al(n3.s3_bias, (size_t)s3_tiles * KZ_TILE * 4);
+        al(n3.ss_packed, (size_t)s_tiles * tile_bytes + 32 * 4096);
+        al(n3.ss_bias, (size_t)s_img_rows * 4);
+        al(n3.theta3, (size_t)s_img_rows * 4);
+        al(n3.theta3_s, (size_t)s_img_rows * 4);
+        al(n3.theta3_min, (size_t)s_img_rows * 4);
+        al(n3.floor3, (size_t)s_img_rows * 4);
+        al(n3.floor3m, (size_t)a_pad * 4);
+        al(n3.qnb_b, (size_t)b_pad * 4);
+        al(n3.col3_key, (size_t)s_img_rows * KPr3 * 4);
+        al(n3.col3_idx, (size_t)s_img_rows * KPr3 * 4);
+        al(n3.iota3, (size_t)s_img_rows * 4);
+        al(n3.perm3, (size_t)s_img_rows * 4);
+        al(n3.rm3, (size_t)s_img_rows * 4);
+        al(n3.row_map_b, (size_t)b_pad * 4);
+        al(n3.ev3_cnt, (size_t)s_img_rows * 4 * KZ_EVC);
+        al(n3.fail3, (size_t)s_img_rows * 4);
+        al(n3.sev_cnt, (size_t)b_pad * 4);
+        al(n3.ev3, (size_t)s_img_rows * ev_cap3 * 8);
+        al(n3.sev, (size_t)b->n * sev_cap * 8);
+        al(n3.log3_keys, (size_t)log_cap3 * 16);
+        al(n3.log3_meta, (size_t)log_cap3 * 8);
+        al(n3.d_cnt3, KZ_DUAL_CNT_BYTES);
+        if (rcn == KZ_OK)
+            nst = std::move(n3);
+        else   // (no memory for the nested stages: the classic sample sweep)
             nested = false;
-        }
     }
     double nested_sweep_ms = 0;   // the sample sweep b x S: part of the distance matrix the dominant kernel covers (reported with the main sweep)
     KzRevChain rv3;
@@ -1017,7 +1000,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     struct Hook2 {
         kz_ctx* ctx; KzDualPass* dp2; KzRevChain* rv3; int rank; int64_t b_n, b_pad; const kz_himage *ia, *ib;
         float *theta, *floor_; const int* rm3; int sev_cap; int* sev_cnt; uint2* sev; int overlap;
-    } hk2 = {ctx, &dp2, &rv3, rank, b->n, b_pad, ia, ib, theta, floor_, nullptr, sev_cap, nullptr, nullptr, ctx->dual_overlap};
+    } hk2 = {ctx, &dp2, &rv3, rank, b->n, b_pad, ia, ib, theta.get(), floor_.get(), nullptr, sev_cap, nullptr, nullptr, ctx->dual_overlap};
     // (the nested sample is STRATIFIED by |q_c|^2 -- which correlates with the keys at -0.75: rows near the centre are near
     //  neighbours of everybody -- and the count of rows above the r-th best of a stratified sample is not negative binomial
     //  (r, 1 / stride) but lower: sampled systematically along the key order, the r-th best sample row is the (stride (r - 1) + 1)-th
@@ -1032,24 +1015,21 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     if (nested) {
         // ---- third level: S x sample(b) with the ordinary kernel -> the event thresholds of the rows of S ----
         hipLaunchKernelGGL(kz_dual_sample_kernel, dim3((unsigned)s3_tiles), dim3(256), 0, ctx->stream, (const uint4*)ib->packed, ib->bias,
-                           n_slices, stride3, (int)s3_tiles, force_s3 > 0 ? force_s3 : 1, (uint4*)s3_packed, s3_bias);
-        KZ_DUAL_HIP(hipGetLastError());
+                           n_slices, stride3, (int)s3_tiles, force_s3 > 0 ? force_s3 : 1, (uint4*)nst.s3_packed.get(), nst.s3_bias.get());
+        KZ_HIP(hipGetLastError());
         {
             const int KP = KPs3;   // (KZ_DISPATCH_KP switches on `KP`)
             int blocks_per_cu = 1, tpw = 1;
             KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu, &tpw, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
-            if (rc != KZ_OK) {
-                release();
-                return rc;
-            }
+            if (rc != KZ_OK) return rc;
             KzPass ps;
             rc = kz_prepare_pass(ctx, (int)s_tiles, (int)s3_tiles, blocks_per_cu * ctx->n_cus, 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s3);
             if (rc == KZ_OK) {
                 KnnCandParams cp;
                 memset(&cp, 0, sizeof(cp));
-                cp.qpack = (const float*)q_packed;     // S = the first s_tiles tiles of the dealt image of a
-                cp.ypack = (const float*)s3_packed;
-                cp.ybias = s3_bias;
+                cp.qpack = (const float*)q_packed.get();     // S = the first s_tiles tiles of the dealt image of a
+                cp.ypack = (const float*)nst.s3_packed.get();
+                cp.ybias = nst.s3_bias.get();
                 cp.work = ps.d_work;
                 cp.qt0 = 0;
                 cp.n_ytiles = (int)s3_tiles;
@@ -1060,20 +1040,17 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
                 cp.out_idx = ps.out_idx;
                 KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W, KZ_K_H_WPS, KZ_K_H_WIDE));
             }
-            if (rc != KZ_OK) {
-                release();
-                return rc;
-            }
-            // (the rows owning these thresholds are rows of S, position j of the dealt image: bias q_bias[j]; their events come from b)
+            if (rc != KZ_OK) return rc;
+            // (the rows owning these thresholds are rows of S, position j of the dealt image: bias q_bias.get()[j]; their events come from b)
             hipLaunchKernelGGL(kz_dual_theta_kernel, dim3((unsigned)((s_img_rows + 3) / 4)), dim3(256), 0, ctx->stream, ps.out_key, ps.out_idx,
-                               ps.lay, KP, rank3, s_img_rows, s_img_rows, q_bias, ib->d_max, ia->d_max, ia->center->d_scale, theta3, floor3,
+                               ps.lay, KP, rank3, s_img_rows, s_img_rows, q_bias.get(), ib->d_max, ia->d_max, ia->center->d_scale, nst.theta3.get(), nst.floor3.get(),
                                (const int*)nullptr, 0, (int*)nullptr, (uint2*)nullptr);
-            KZ_DUAL_HIP(hipGetLastError());
+            KZ_HIP(hipGetLastError());
         }
-        // S sorted by descending threshold: perm3 (sorted row -> j), its image from the raw rows, per-tile minima
-        hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, iota3, (int)s_img_rows);
-        KZ_DUAL_HIP(hipGetLastError());
-        rc = kz_sort_pairs_f32_i32(ctx, theta3, theta3_s, iota3, perm3, (int)s_img_rows, 1);
+        // S sorted by descending threshold: nst.perm3.get() (sorted row -> j), its image from the raw rows, per-tile minima
+        hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, nst.iota3.get(), (int)s_img_rows);
+        KZ_HIP(hipGetLastError());
+        rc = kz_sort_pairs_f32_i32(ctx, nst.theta3.get(), nst.theta3_s.get(), nst.iota3.get(), nst.perm3.get(), (int)s_img_rows, 1);
         if (rc == KZ_OK && force_s > 1) {
             // b's lists over S are kept per index RANGE of this image (force_s lists of 16), and the ranges must be ALIKE: a range
             // that holds most of a row's near sample rows truncates them, the threshold is read too low and the row's event
@@ -1084,53 +1061,53 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
             // is a stratified draw of a -- sorted by threshold INSIDE the range: a stable sort by range number on top of the sort
             // by threshold.  Tiles stay coherent in threshold (the per-tile test), ranges are fair.
             const int64_t range_rows = ((s_tiles + force_s - 1) / force_s) * KZ_TILE;
-            hipLaunchKernelGGL(kz_dual_rangekey_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, perm3, s_img_rows, range_rows,
-                               theta3, iota3);     // (theta3, iota3: free since the sort above) range number as the key, sorted position as the value
+            hipLaunchKernelGGL(kz_dual_rangekey_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, nst.perm3.get(), s_img_rows, range_rows,
+                               nst.theta3.get(), nst.iota3.get());     // (nst.theta3.get(), nst.iota3.get(): free since the sort above) range number as the key, sorted position as the value
             if (hipGetLastError() != hipSuccess) rc = KZ_ERR_HIP;
-            if (rc == KZ_OK) rc = kz_sort_pairs_f32_i32(ctx, theta3, floor3m, iota3, rm3, (int)s_img_rows, 0);   // (floor3m, rm3: scratch here, written later)
+            if (rc == KZ_OK) rc = kz_sort_pairs_f32_i32(ctx, nst.theta3.get(), nst.floor3m.get(), nst.iota3.get(), nst.rm3.get(), (int)s_img_rows, 0);   // (nst.floor3m.get(), nst.rm3.get(): scratch here, written later)
             if (rc == KZ_OK) {
-                hipLaunchKernelGGL(kz_dual_gather2_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, rm3, perm3, theta3_s,
-                                   s_img_rows, iota3, theta3);
+                hipLaunchKernelGGL(kz_dual_gather2_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, nst.rm3.get(), nst.perm3.get(), nst.theta3_s.get(),
+                                   s_img_rows, nst.iota3.get(), nst.theta3.get());
                 if (hipGetLastError() != hipSuccess) rc = KZ_ERR_HIP;
-                int* ti = perm3; perm3 = iota3; iota3 = ti;
-                float* tf = theta3_s; theta3_s = theta3; theta3 = tf;
+                std::swap(nst.perm3, nst.iota3);
+                std::swap(nst.theta3_s, nst.theta3);
             }
         }
         if (rc == KZ_OK) {
-            hipLaunchKernelGGL(kz_dual_rows_of_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, perm3, row_map, s_img_rows, rm3);
-            hipLaunchKernelGGL(kz_dual_tilemin_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, theta3_s, s_img_rows, s_img_rows, theta3_min);
-            hipLaunchKernelGGL(kz_dual_natural_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, b->n, b_pad, row_map_b);
-            hipLaunchKernelGGL(kz_dual_negbias_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, ib->bias, b->n, b_pad, qnb_b);
-            rc = kz_himage_pack_rows(a, rm3, s_img_rows, s_img_rows, ss_packed, ss_bias);
+            hipLaunchKernelGGL(kz_dual_rows_of_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, nst.perm3.get(), row_map.get(), s_img_rows, nst.rm3.get());
+            hipLaunchKernelGGL(kz_dual_tilemin_kernel, dim3((unsigned)((s_img_rows + 255) / 256)), dim3(256), 0, ctx->stream, nst.theta3_s.get(), s_img_rows, s_img_rows, nst.theta3_min.get());
+            hipLaunchKernelGGL(kz_dual_natural_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, b->n, b_pad, nst.row_map_b.get());
+            hipLaunchKernelGGL(kz_dual_negbias_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, ib->bias, b->n, b_pad, nst.qnb_b.get());
+            rc = kz_himage_pack_rows(a, nst.rm3.get(), s_img_rows, s_img_rows, nst.ss_packed.get(), nst.ss_bias.get());
         }
-        if (rc == KZ_OK && hipMemsetAsync(ev3_cnt, 0, (size_t)s_img_rows * 4 * KZ_EVC, ctx->stream) != hipSuccess) rc = KZ_ERR_HIP;
-        if (rc == KZ_OK && hipMemsetAsync(d_cnt3, 0, KZ_DUAL_CNT_BYTES, ctx->stream) != hipSuccess) rc = KZ_ERR_HIP;
-        if (rc != KZ_OK) {
-            release();
-            return rc;
-        }
-        // ---- second level: b x S with the DUAL build.  Forward lists (raw) -> tau(t), theta(t) and the sample-row events of t;
+        if (rc == KZ_OK && hipMemsetAsync(nst.ev3_cnt.get(), 0, (size_t)s_img_rows * 4 * KZ_EVC, ctx->stream) != hipSuccess) rc = KZ_ERR_HIP;
+        if (rc == KZ_OK && hipMemsetAsync(nst.d_cnt3.get(), 0, KZ_DUAL_CNT_BYTES, ctx->stream) != hipSuccess) rc = KZ_ERR_HIP;
+        if (rc != KZ_OK) return rc;
+        // ---- second level: b x S with the DUAL build.  Forward lists (raw) -> tau(t), theta.get()(t) and the sample-row events of t;
         // event log -> the forward results of the rows of S (chain rv3, second stream) ----
         rv3.ctx = ctx; rv3.qm = a; rv3.im = b; rv3.qi = ia; rv3.ii = ib;
-        rv3.log_keys = log3_keys; rv3.log_meta = log3_meta; rv3.d_cnt = d_cnt3; rv3.log_cap = log_cap3;
-        rv3.theta_s = theta3_s; rv3.qnb = qnb_b; rv3.p_bias = ss_bias; rv3.col_key = col3_key; rv3.floor_sel = floor3; rv3.floor_fin = floor3m;
-        rv3.row_map = row_map_b; rv3.ev_cnt = ev3_cnt; rv3.perm = perm3; rv3.col_idx = col3_idx; rv3.fail_list = fail3;
-        rv3.fail_count = ctx->d_counters + 24; rv3.fin_row_map = row_map;
-        rv3.ev = ev3; rv3.ev_cap = ev_cap3; rv3.KP = ctx->dual_rev_long ? (2 * KP < 128 ? 2 * KP : 128) : KP; rv3.k = k;
+        rv3.log_keys = nst.log3_keys.get(); rv3.log_meta = nst.log3_meta.get(); rv3.d_cnt = nst.d_cnt3.get(); rv3.log_cap = log_cap3;
+        rv3.theta_s = nst.theta3_s.get(); rv3.qnb = nst.qnb_b.get(); rv3.p_bias = nst.ss_bias.get(); rv3.col_key = nst.col3_key.get(); rv3.floor_sel = nst.floor3.get(); rv3.floor_fin = nst.floor3m.get();
+        rv3.row_map = nst.row_map_b.get(); rv3.ev_cnt = nst.ev3_cnt.get(); rv3.perm = nst.perm3.get(); rv3.col_idx = nst.col3_idx.get(); rv3.fail_list = nst.fail3.get();
+        rv3.fail_count = ctx->d_counters + 24; rv3.fin_row_map = row_map.get();
+        rv3.ev = nst.ev3.get(); rv3.ev_cap = ev_cap3; rv3.KP = ctx->dual_rev_long ? (2 * KP < 128 ? 2 * KP : 128) : KP; rv3.k = k;
         rv3.n_rows = s_img_rows; rv3.n_tiles = s_tiles; rv3.d_dist = d_dist_ab; rv3.d_ind = d_ind_ab;
         rv3.timed = 0; rv3.h_fail = 24; rv3.h_cnt = 28; rv3.second_stream = ctx->dual_overlap ? 1 : 0;
-        if (kz_spec_rows(ctx, b, k) > 0) KZ_DUAL_RC(kz_spec_alloc(ctx, spec_s3, kz_spec_rows(ctx, b, k), b, k));   // (ahead of the chain: see kz_spec_alloc)
+        if (kz_spec_rows(ctx, b, k) > 0) {   // (ahead of the chain: see kz_spec_alloc)
+            rc = kz_spec_alloc(ctx, spec_s3, kz_spec_rows(ctx, b, k), b, k);
+            if (rc != KZ_OK) return rc;
+        }
         rv3.spec = &spec_s3;
         dp2.qpack = (const float*)ib->packed;
-        dp2.row_map = row_map_b;
-        dp2.ypack = (const float*)ss_packed;
-        dp2.ybias = ss_bias;
-        dp2.perm = rm3;
-        dp2.theta = theta3_min;
-        dp2.qnbias = qnb_b;
-        dp2.log_keys = log3_keys;
-        dp2.log_meta = log3_meta;
-        dp2.log_cnt = d_cnt3;
+        dp2.row_map = nst.row_map_b.get();
+        dp2.ypack = (const float*)nst.ss_packed.get();
+        dp2.ybias = nst.ss_bias.get();
+        dp2.perm = nst.rm3.get();
+        dp2.theta = nst.theta3_min.get();
+        dp2.qnbias = nst.qnb_b.get();
+        dp2.log_keys = nst.log3_keys.get();
+        dp2.log_meta = nst.log3_meta.get();
+        dp2.log_cnt = nst.d_cnt3.get();
         dp2.log_cap = log_cap3;
         dp2.short_pieces = force_s;       // (lists of KPs over force_s parts of S, as the classic sample sweep keeps them)
         dp2.short_kp = KPs;
@@ -1138,9 +1115,9 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         dp2.n_ytiles = (int)s_tiles;
         dp2.raw_lists = 1;
         dp2.max_entries = 256;
-        hk2.rm3 = rm3;
-        hk2.sev_cnt = sev_cnt;
-        hk2.sev = sev;
+        hk2.rm3 = nst.rm3.get();
+        hk2.sev_cnt = nst.sev_cnt.get();
+        hk2.sev = nst.sev.get();
         dp2.post_user = &hk2;
         dp2.post_sweep = +[](void* user) -> int {
             Hook2& h = *(Hook2*)user;
@@ -1155,41 +1132,32 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         };
         kz_knn_stats st2;
         ctx->stream2_busy = 1;
-        rc = kz_knn_impl(ctx, b, 0, b->n, a, k, 0, nullptr, -1, 0, d_dist_ba, d_ind_ba, &st2, &dp2);
-        if (rc == KZ_OK && (dp2.broken || !dp2.post_called)) {
+        rc = kz_knn_impl(ctx, b, 0, b->n, a, k, 0, nullptr, KzResearch(), d_dist_ba, d_ind_ba, &st2, &dp2);
+        if (rc != KZ_OK) return rc;
+        if (dp2.broken || !dp2.post_called) {
             // the sweep left the fp16 tier (cannot happen for a dual pass today) -- no thresholds: give the call to two ordinary searches
-            (void)hipStreamSynchronize(ctx->stream2);
-            ctx->stream2_busy = 0;
-            release();
-            return kz_knn_dual_separately(ctx, a, b, k, d_dist_ab, d_ind_ab, d_dist_ba, d_ind_ba, stats_ab, stats_ba);
-        }
-        if (rc != KZ_OK) {
-            (void)hipStreamSynchronize(ctx->stream2);
-            ctx->stream2_busy = 0;
-            release();
-            return rc;
+            then = 1;
+            return KZ_OK;
         }
         nested_sweep_ms = st2.main_kernel_ms;
     } else {
         // ---- classic sample image: every stride-th tile of A's fp16 image (tiles are contiguous runs of n_slices x 4 KiB), dealt over the parts
         hipLaunchKernelGGL(kz_dual_sample_kernel, dim3((unsigned)s_tiles), dim3(256), 0, ctx->stream, (const uint4*)ia->packed, ia->bias,
-                           n_slices, stride, (int)s_tiles, force_s > 0 ? force_s : 1, (uint4*)s_packed, s_bias);
-        KZ_DUAL_HIP(hipGetLastError());
+                           n_slices, stride, (int)s_tiles, force_s > 0 ? force_s : 1, (uint4*)s_packed.get(), s_bias.get());
+        KZ_HIP(hipGetLastError());
         // ---- sample sweep: B x sample(A) with the ordinary kernel, lists of at most 256 entries per row -----------------------
         const int KP = KPs;   // (KZ_DISPATCH_KP switches on `KP`)
         int blocks_per_cu = 1, tpw = 1;
         KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu, &tpw, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
-        if (rc != KZ_OK) {
-            release();
-            return rc;
-        }
+        if (rc != KZ_OK) return rc;
         KzPass ps;
-        KZ_DUAL_RC(kz_prepare_pass(ctx, (int)b_tiles, (int)s_tiles, blocks_per_cu * ctx->n_cus, 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s));
+        rc = kz_prepare_pass(ctx, (int)b_tiles, (int)s_tiles, blocks_per_cu * ctx->n_cus, 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s);
+        if (rc != KZ_OK) return rc;
         KnnCandParams cp;
         memset(&cp, 0, sizeof(cp));
         cp.qpack = (const float*)ib->packed;
-        cp.ypack = (const float*)s_packed;
-        cp.ybias = s_bias;
+        cp.ypack = (const float*)s_packed.get();
+        cp.ybias = s_bias.get();
         cp.work = ps.d_work;
         cp.qt0 = 0;
         cp.n_ytiles = (int)s_tiles;
@@ -1199,23 +1167,21 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         cp.out_key = ps.out_key;
         cp.out_idx = ps.out_idx;
         KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W, KZ_K_H_WPS, KZ_K_H_WIDE));
-        if (rc != KZ_OK) {
-            release();
-            return rc;
-        }
+        if (rc != KZ_OK) return rc;
         hipLaunchKernelGGL(kz_dual_theta_kernel, dim3((unsigned)((b_pad + 3) / 4)), dim3(256), 0, ctx->stream, ps.out_key, ps.out_idx,
-                           ps.lay, KP, rank, b->n, b_pad, ib->bias, ia->d_max, ib->d_max, ib->center->d_scale, theta, floor_,
+                           ps.lay, KP, rank, b->n, b_pad, ib->bias, ia->d_max, ib->d_max, ib->center->d_scale, theta.get(), floor_.get(),
                            (const int*)nullptr, 0, (int*)nullptr, (uint2*)nullptr);
-        KZ_DUAL_HIP(hipGetLastError());
+        KZ_HIP(hipGetLastError());
     }
     // ---- B's rows in DESCENDING order of their threshold: permutation, sorted thresholds (+inf behind them), sorted image.
     // Descending = rows with a near K'-th neighbour first: those are the rows that ARE near neighbours of many queries, so the
     // forward lists meet their best candidates early and their thresholds tighten at once (ascending order is the
     // adversarial one: candidates keep improving over the whole sweep -- 4.7 against 2.7 list inserts per wave and tile) ----
-    hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, iota, (int)b_pad);
-    hipLaunchKernelGGL(kz_dual_fill_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, theta_s, b_pad, INFINITY);
-    KZ_DUAL_HIP(hipGetLastError());
-    KZ_DUAL_RC(kz_sort_pairs_f32_i32(ctx, theta, theta_s, iota, perm, (int)b->n, 1));
+    hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, iota.get(), (int)b_pad);
+    hipLaunchKernelGGL(kz_dual_fill_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, theta_s.get(), b_pad, INFINITY);
+    KZ_HIP(hipGetLastError());
+    rc = kz_sort_pairs_f32_i32(ctx, theta.get(), theta_s.get(), iota.get(), perm.get(), (int)b->n, 1);
+    if (rc != KZ_OK) return rc;
     // ---- short-list route of the main sweep (kz_knn_impl): k / 5 lists of 16 per query instead of one of 32 / 64 / 128.  Rows with
     // neighbouring thresholds tend to be neighbours of the same queries, so the sorted tiles are dealt over the index ranges.
     int main_pieces = 0;
@@ -1226,48 +1192,49 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         if (P >= 2 && P * KZ_K_DUAL_SHORT_KP <= 512 && KP > KZ_K_DUAL_SHORT_KP && b_tiles - 1 >= (int64_t)ctx->dual_short_min_tiles * P) main_pieces = P;
     }
     if (main_pieces > 0) {
-        // (iota and theta -- the sort's inputs -- are free now: they take the dealt order)
-        hipLaunchKernelGGL(kz_dual_interleave_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, perm, theta_s, b->n,
-                           b_pad, main_pieces, iota, theta);
-        KZ_DUAL_HIP(hipGetLastError());
-        int* ti = perm; perm = iota; iota = ti;
-        float* tf = theta_s; theta_s = theta; theta = tf;
+        // (iota.get() and theta.get() -- the sort's inputs -- are free now: they take the dealt order)
+        hipLaunchKernelGGL(kz_dual_interleave_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, perm.get(), theta_s.get(), b->n,
+                           b_pad, main_pieces, iota.get(), theta.get());
+        KZ_HIP(hipGetLastError());
+        std::swap(perm, iota);
+        std::swap(theta_s, theta);
     }
-    hipLaunchKernelGGL(kz_dual_tilemin_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, theta_s, b->n, b_pad, theta_min);
-    KZ_DUAL_HIP(hipGetLastError());
-    KZ_DUAL_RC(kz_himage_pack_permuted(b, perm, p_packed, p_bias));
+    hipLaunchKernelGGL(kz_dual_tilemin_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, theta_s.get(), b->n, b_pad, theta_min.get());
+    KZ_HIP(hipGetLastError());
+    rc = kz_himage_pack_permuted(b, perm.get(), p_packed.get(), p_bias.get());
+    if (rc != KZ_OK) return rc;
     if (nested) {
         // the sample-row events of every row of b open its event buffer (the main sweep's scatter kernel appends behind them)
         // (rows [0, b->n) of the sorted image: the permutation is only defined there without the dealt tiles, and they keep the
         //  ragged last tile last)
-        hipLaunchKernelGGL(kz_dual_inject_kernel, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, ctx->stream, perm, b->n, sev_cnt, sev, sev_cap,
-                           ev_cnt, ev, ev_cap);
-        KZ_DUAL_HIP(hipGetLastError());
+        hipLaunchKernelGGL(kz_dual_inject_kernel, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, ctx->stream, perm.get(), b->n, nst.sev_cnt.get(), nst.sev.get(), sev_cap,
+                           ev_cnt.get(), ev.get(), ev_cap);
+        KZ_HIP(hipGetLastError());
     }
-    KZ_DUAL_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
+    KZ_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
     float sample_ms = 0;
-    if (qfloor) {
-        hipLaunchKernelGGL(kz_floor_rows_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, row_map, a->n, a_pad, ia->rowq,
+    if (qfloor.get()) {
+        hipLaunchKernelGGL(kz_floor_rows_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, row_map.get(), a->n, a_pad, ia->rowq,
                            ib->d_max, ib->center->d_scale, floor_model[0], floor_model[1], floor_model[2], ctx->eps_scale,
-                           kz_gamma_acc_h(b->kg), qfloor);
-        KZ_DUAL_HIP(hipGetLastError());
+                           kz_gamma_acc_h(b->kg), qfloor.get());
+        KZ_HIP(hipGetLastError());
     }
 
     // ---- main sweep: A x B, lists of A's rows + event log of B's rows ---------------------------------------------------------
     KzDualPass dp;
     memset(&dp, 0, sizeof(dp));
     dp.probed = tier_probed ? 1 : 0;
-    dp.qpack = (const float*)q_packed;
-    dp.row_map = row_map;
-    dp.ypack = (const float*)p_packed;
-    dp.ybias = p_bias;
-    dp.perm = perm;
-    dp.theta = theta_min;
-    dp.qnbias = qnb;
-    dp.qfloor = qfloor;
-    dp.log_keys = log_keys;
-    dp.log_meta = log_meta;
-    dp.log_cnt = d_cnt;
+    dp.qpack = (const float*)q_packed.get();
+    dp.row_map = row_map.get();
+    dp.ypack = (const float*)p_packed.get();
+    dp.ybias = p_bias.get();
+    dp.perm = perm.get();
+    dp.theta = theta_min.get();
+    dp.qnbias = qnb.get();
+    dp.qfloor = qfloor.get();
+    dp.log_keys = log_keys.get();
+    dp.log_meta = log_meta.get();
+    dp.log_cnt = d_cnt.get();
     dp.log_cap = log_cap;
     dp.short_pieces = main_pieces;
     dp.short_ksel = k + ctx->dual_short_extra < main_pieces * KZ_K_DUAL_SHORT_KP ? k + ctx->dual_short_extra : main_pieces * KZ_K_DUAL_SHORT_KP;
@@ -1279,12 +1246,15 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     KzRevChain rv;
     memset(&rv, 0, sizeof(rv));
     rv.ctx = ctx; rv.qm = b; rv.im = a; rv.qi = ib; rv.ii = ia;
-    rv.log_keys = log_keys; rv.log_meta = log_meta; rv.d_cnt = d_cnt; rv.log_cap = log_cap;
-    rv.theta_s = theta_s; rv.qnb = qnb; rv.p_bias = p_bias; rv.col_key = col_key; rv.floor_sel = floor_; rv.floor_fin = floor_;
-    rv.row_map = row_map; rv.ev_cnt = ev_cnt; rv.perm = perm; rv.col_idx = col_idx; rv.fail_list = fail_list; rv.fail_count = fail_count_b;
-    rv.ev = ev; rv.ev_cap = ev_cap; rv.KP = KPr; rv.k = k; rv.n_rows = b->n; rv.n_tiles = b_tiles; rv.d_dist = d_dist_ba; rv.d_ind = d_ind_ba;
+    rv.log_keys = log_keys.get(); rv.log_meta = log_meta.get(); rv.d_cnt = d_cnt.get(); rv.log_cap = log_cap;
+    rv.theta_s = theta_s.get(); rv.qnb = qnb.get(); rv.p_bias = p_bias.get(); rv.col_key = col_key.get(); rv.floor_sel = floor_.get(); rv.floor_fin = floor_.get();
+    rv.row_map = row_map.get(); rv.ev_cnt = ev_cnt.get(); rv.perm = perm.get(); rv.col_idx = col_idx.get(); rv.fail_list = fail_list.get(); rv.fail_count = fail_count_b;
+    rv.ev = ev.get(); rv.ev_cap = ev_cap; rv.KP = KPr; rv.k = k; rv.n_rows = b->n; rv.n_tiles = b_tiles; rv.d_dist = d_dist_ba; rv.d_ind = d_ind_ba;
     rv.timed = 1; rv.h_fail = 12; rv.h_cnt = 16; rv.second_stream = 1;
-    if (kz_spec_rows(ctx, a, k) > 0) KZ_DUAL_RC(kz_spec_alloc(ctx, spec_ba, kz_spec_rows(ctx, a, k), a, k));   // (ahead of the chain: see kz_spec_alloc)
+    if (kz_spec_rows(ctx, a, k) > 0) {   // (ahead of the chain: see kz_spec_alloc)
+        rc = kz_spec_alloc(ctx, spec_ba, kz_spec_rows(ctx, a, k), a, k);
+        if (rc != KZ_OK) return rc;
+    }
     rv.spec = &spec_ba;
     auto enqueue_reverse = [](void* user) -> int { return kz_dual_enqueue_chain(*(KzRevChain*)user); };
     if (ctx->dual_overlap) {
@@ -1294,7 +1264,8 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     kz_knn_stats st_ab;
     ctx->stream2_busy = 1;   // (from here to the synchronisation below the second stream belongs to the reverse chain)
     // (nested: the main sweep covers the image rows behind the sample -- in the dual pass a query range is a range of IMAGE rows)
-    rc = kz_knn_impl(ctx, a, nested ? s_img_rows : 0, nested ? a->n - s_img_rows : a->n, b, k, 0, nullptr, -1, 0, d_dist_ab, d_ind_ab, &st_ab, &dp);
+    rc = kz_knn_impl(ctx, a, nested ? s_img_rows : 0, nested ? a->n - s_img_rows : a->n, b, k, 0, nullptr, KzResearch(), d_dist_ab, d_ind_ab, &st_ab,
+                     &dp);
     if (rc == KZ_OK && !ctx->dual_overlap && !dp.broken) {   // ("dual_overlap" = 0: the same chain, behind the forward direction)
         dp.post_called = 1;
         rc = enqueue_reverse(&rv);
@@ -1308,12 +1279,9 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
             rc = KZ_ERR_HIP;
         }
     }
-    if (rc != KZ_OK) {
-        release();
-        return rc;
-    }
-    // (kz_knn_impl ends with a stream synchronisation: ev[5] and ev[6] around the sample sweep have completed)
-    KZ_DUAL_HIP(hipEventElapsedTime(&sample_ms, ctx->ev[5], ctx->ev[6]));
+    if (rc != KZ_OK) return rc;
+    // (kz_knn_impl ends with a stream synchronisation: ev.get()[5] and ev.get()[6] around the sample sweep have completed)
+    KZ_HIP(hipEventElapsedTime(&sample_ms, ctx->ev[5], ctx->ev[6]));
     st_ab.dual = 1;
     st_ab.main_kernel_ms += nested_sweep_ms;   // (nested: S x B is swept by the sample sweep, the rest of A x B by the main sweep)
     if (nested) {
@@ -1322,21 +1290,21 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         int n_fail3 = ctx->h_counters[24];
         unsigned long long hc3[4];
         memcpy(hc3, ctx->h_counters + 28, 32);
-        const int* list3 = fail3;
+        const int* list3 = nst.fail3.get();
         if (hc3[0] > (unsigned long long)log_cap3) {
             n_fail3 = (int)s_img_rows;
-            list3 = rm3;   // (the matrix rows of S)
+            list3 = nst.rm3.get();   // (the matrix rows of S)
         }
         const bool rescued3 = hc3[0] <= (unsigned long long)log_cap3 && spec_s3.R > 0 && n_fail3 > 0 && n_fail3 <= spec_s3.R;
         if (rescued3) {   // (the speculative exact launches behind the chain's finalize have answered them)
             st_ab.n_fallback_rows += n_fail3;
             st_ab.n_spec_rows += n_fail3;
         } else if (n_fail3 > 0) {
-            const int kp_min3 = ((int64_t)n_fail3 * 8 > s_img_rows || KPr >= 128) ? 0 : (KPr == 16 && KZ_K_ESC_SHORT && n_fail3 <= KZ_ESC_SHORT_MAX_ROWS ? -1 : (KPr * 4 < 128 ? KPr * 4 : 128));
             kz_knn_stats st3;
             float ms3 = 0;
-            const int prec3 = ((int64_t)n_fail3 * 2 > s_img_rows && ctx->esc_bf) ? 2 : -1;
-            KZ_DUAL_RC(kz_escalate_rows(ctx, a, 0, list3, n_fail3, b, k, 0, nullptr, prec3, prec3 == 2 ? 0 : kp_min3, d_dist_ab, d_ind_ab, &st3, &ms3));
+            rc = kz_escalate_rows(ctx, a, 0, list3, n_fail3, b, k, 0, nullptr, kz_dual_research(ctx, n_fail3, s_img_rows, KPr), d_dist_ab, d_ind_ab, &st3,
+                                  &ms3);
+            if (rc != KZ_OK) return rc;
             st_ab.fallback_ms += ms3;
             st_ab.n_escalated_rows += n_fail3 + st3.n_escalated_rows;
             st_ab.n_fallback_rows += st3.n_fallback_rows;
@@ -1349,8 +1317,6 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     }
     kz_dual_fill_stats(stats_ab, st_ab);
 
-    kz_knn_stats st_ba;
-    memset(&st_ba, 0, sizeof(st_ba));
     if (!dp.broken && !dp.post_called) dp.broken = 1;   // (the sweep never got as far as its last chunk in the fp16 tier)
     if (!dp.broken) {
         const int n_fail = ctx->h_counters[12];
@@ -1358,9 +1324,9 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         memcpy(hc, ctx->h_counters + 16, 32);
         memcpy(&st_ba.max_err_ratio, ctx->h_counters + 14, 8);
         float ms = 0;
-        KZ_DUAL_HIP(hipEventElapsedTime(&ms, ctx->ev[8], ctx->ev[9]));
+        KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[8], ctx->ev[9]));
         st_ba.main_kernel_ms = sample_ms - (float)nested_sweep_ms + ms;   // sample stage (without the part of the matrix it covers for both directions) + scatter + select: what this direction cost besides the shared sweep
-        KZ_DUAL_HIP(hipEventElapsedTime(&ms, ctx->ev[9], ctx->ev[10]));
+        KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[9], ctx->ev[10]));
         st_ba.finalize_ms = ms;
         st_ba.list_len = KPr;
         st_ba.n_splits = 1;
@@ -1376,33 +1342,31 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
             st_ba.n_spec_rows = n_fail;
         } else if (n_fail > 0) {
             // rows of B with an overflowing buffer or an uncertified list: the ordinary search, longer lists when they are few
-            // (K' = 16: more lists instead of longer ones, kz_knn_impl kp_min = -1)
-            const int kp_min = ((int64_t)n_fail * 8 > b->n || KPr >= 128) ? 0 : (KPr == 16 && KZ_K_ESC_SHORT && n_fail <= KZ_ESC_SHORT_MAX_ROWS ? -1 : (KPr * 4 < 128 ? KPr * 4 : 128));
-            kz_knn_stats st2;
             // (more than half of B's rows: fp16 is the wrong tier for this data -- the split-bf16 operands at once)
-            const int prec = ((int64_t)n_fail * 2 > b->n && ctx->esc_bf) ? 2 : -1;
-            if (prec == 2 && !tier_probed)   // (no probe has looked at this data: the ladder on the failed rows, kz_knn.hip "LADDER AFTER THE FACT")
-                KZ_DUAL_RC(kz_escalate_ladder(ctx, b, 0, fail_list, n_fail, a, k, 0, nullptr, prec, 0, d_dist_ba, d_ind_ba, &st2, &ms));
+            kz_knn_stats st2;
+            const KzResearch rs = kz_dual_research(ctx, n_fail, b->n, KPr);
+            if (rs.prec == 2 && !tier_probed)   // (no probe has looked at this data: the ladder on the failed rows, kz_knn.hip "LADDER AFTER THE FACT")
+                rc = kz_escalate_ladder(ctx, b, 0, fail_list.get(), n_fail, a, k, 0, nullptr, rs, d_dist_ba, d_ind_ba, &st2, &ms);
             else
-                KZ_DUAL_RC(kz_escalate_rows(ctx, b, 0, fail_list, n_fail, a, k, 0, nullptr, prec, prec == 2 ? 0 : kp_min, d_dist_ba, d_ind_ba, &st2, &ms));
+                rc = kz_escalate_rows(ctx, b, 0, fail_list.get(), n_fail, a, k, 0, nullptr, rs, d_dist_ba, d_ind_ba, &st2, &ms);
+            if (rc != KZ_OK) return rc;
             st_ba.fallback_ms = ms;
             st_ba.n_escalated_rows = n_fail + st2.n_escalated_rows;
             st_ba.n_fallback_rows = st2.n_fallback_rows;
             if (st2.max_err_ratio > st_ba.max_err_ratio) st_ba.max_err_ratio = st2.max_err_ratio;
         }
     }
-    release();
-    if (dp.broken == 2) {
-        // the forward sweep gave up on a chunk (too many uncertified rows for the fp16 tier): both directions the ordinary way
-        return kz_knn_dual_separately(ctx, a, b, k, d_dist_ab, d_ind_ab, d_dist_ba, d_ind_ba, stats_ab, stats_ba);
-    }
-    if (dp.broken) {
-        // the sweep left the fp16 tier on the way, or the log overflowed: this direction the ordinary way
-        rc = kz_knn_impl(ctx, b, 0, b->n, a, k, 0, nullptr, -1, 0, d_dist_ba, d_ind_ba, &st_ba, nullptr);
+    // dp.broken == 2: the forward sweep gave up on a chunk (too many uncertified rows for the fp16 tier): both directions the ordinary
+    // way; else dp.broken: the sweep left the fp16 tier on the way, or the log overflowed: this direction the ordinary way
+    then = dp.broken == 2 ? 1 : (dp.broken ? 2 : 0);
+    return KZ_OK;
+    }();
+    if (rc_pass != KZ_OK) return rc_pass;
+    if (then == 1) return kz_knn_dual_separately(ctx, a, b, k, d_dist_ab, d_ind_ab, d_dist_ba, d_ind_ba, stats_ab, stats_ba, sep_prec, sep_wide);
+    if (then == 2) {
+        rc = kz_knn_impl(ctx, b, 0, b->n, a, k, 0, nullptr, KzResearch(), d_dist_ba, d_ind_ba, &st_ba, nullptr);
         if (rc != KZ_OK) return rc;
     }
     kz_dual_fill_stats(stats_ba, st_ba);
     return KZ_OK;
-#undef KZ_DUAL_HIP
-#undef KZ_DUAL_RC
 }

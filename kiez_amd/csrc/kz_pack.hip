@@ -496,24 +496,23 @@ static int kz_center_create(kz_ctx* ctx, const kz_matrix* from, kz_center** out)
     memset(c, 0, sizeof(*c));
     c->refs = 1;
     const int d = (int)from->d, d_pad = kz_h_nsr(from->kg) * 16;   // (the fp16 image's width: kz_pack_h_kernel reads mu up to it)
-    double* partial = nullptr;
+    KzPoolBuf<double> partial;
     if (kz_pool_alloc(ctx, (size_t)d_pad * 4, (void**)&c->d_mu) != KZ_OK || kz_pool_alloc(ctx, 16, (void**)&c->d_scale) != KZ_OK ||
-        kz_pool_alloc(ctx, (size_t)KZ_COLSUM_BLOCKS * d * 8, (void**)&partial) != KZ_OK) {
-        kz_pool_free(ctx, partial, 0);
+        partial.alloc(ctx, (size_t)KZ_COLSUM_BLOCKS * d * 8) != KZ_OK) {
         kz_center_release(ctx, c);
         return KZ_ERR_NOMEM;
     }
     const int blocks = (int)(from->n < KZ_COLSUM_BLOCKS ? from->n : KZ_COLSUM_BLOCKS);
     if (from->dtype == KZ_F32)
         hipLaunchKernelGGL(kz_colsum_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, (const float*)from->raw, from->sqn,
-                           from->n, d, from->metric, partial);
+                           from->n, d, from->metric, partial.get());
     else
         hipLaunchKernelGGL(kz_colsum_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)from->raw, from->sqn,
-                           from->n, d, from->metric, partial);
-    hipLaunchKernelGGL(kz_center_finish_kernel, dim3(d_pad), dim3(256), 0, ctx->stream, partial, blocks, from->n, d, from->d_stats,
+                           from->n, d, from->metric, partial.get());
+    hipLaunchKernelGGL(kz_center_finish_kernel, dim3(d_pad), dim3(256), 0, ctx->stream, partial.get(), blocks, from->n, d, from->d_stats,
                        c->d_mu, c->d_scale);
     const hipError_t e = hipGetLastError();
-    kz_pool_free(ctx, partial, 0);   // stream-ordered pool: reuse is ordered behind the kernels above
+    partial.reset();   // stream-ordered pool: reuse is ordered behind the kernels above
     if (e != hipSuccess) {
         kz_center_release(ctx, c);
         kz_set_error("kz_knn: centre kernels failed: %s", hipGetErrorString(e));

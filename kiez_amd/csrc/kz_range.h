@@ -320,11 +320,11 @@ static void kz_launch_exact_pairs(kz_ctx* ctx, const long long* seg_off, int nb,
 }
 
 // The log of a sweep and what the sweep needs around it (allocated once per call of kz_range_rescue)
-struct KzRangeLog {
-    float* theta0 = nullptr;               // [index tiles * 128] zeros: the per-tile part of the kernel's threshold
-    void* keys = nullptr;                  // [cap] groups of four keys
-    void* meta = nullptr;                  // [cap] {lane | 16 tile + group, batch row}
-    unsigned long long* counters = nullptr;   // [0] groups logged, [1] (as int) rows handed back
+struct KzRangeLog {   // (members in reverse release order: theta0, keys, meta, counters)
+    KzPoolBuf<unsigned long long> counters;   // [0] groups logged, [1] (as int) rows handed back
+    KzPoolBuf<void> meta;                     // [cap] {lane | 16 tile + group, batch row}
+    KzPoolBuf<void> keys;                     // [cap] groups of four keys
+    KzPoolBuf<float> theta0;                  // [index tiles * 128] zeros: the per-tile part of the kernel's threshold
     long long cap = 0;
 };
 // The sweep of the rows of `qsub` (nb rows; tau [nb] on the device) against the whole index: thr / inff [n_pad] are filled, the log
@@ -342,7 +342,7 @@ static int kz_range_sweep_rows(kz_ctx* ctx, kz_matrix* qsub, const double* tau, 
     hipLaunchKernelGGL(kz_range_thr_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, tau, (ctx->abl & 8) ? 0 : nb, n_pad,
                        qsub->himg->rowq, qsub->sqn, index->himg->d_max, index->himg->center->d_scale, index->d_stats, index->metric, ctx->eps_scale,
                        kz_gamma_acc_h(index->kg), thr, inff);
-    hipError_t e = hipMemsetAsync(lg.counters, 0, 8, ctx->stream);
+    hipError_t e = hipMemsetAsync(lg.counters.get(), 0, 8, ctx->stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) {
         kz_set_error("kz_knn: range re-search: %s", hipGetErrorString(e));
@@ -354,20 +354,22 @@ static int kz_range_sweep_rows(kz_ctx* ctx, kz_matrix* qsub, const double* tau, 
     dp.qpack = (const float*)qsub->himg->packed;
     dp.ypack = (const float*)index->himg->packed;
     dp.ybias = index->himg->bias;
-    dp.theta = lg.theta0;
+    dp.theta = lg.theta0.get();
     dp.qnbias = thr;
     dp.qfloor = inff;
-    dp.log_keys = lg.keys;
-    dp.log_meta = lg.meta;
-    dp.log_cnt = lg.counters;
+    dp.log_keys = lg.keys.get();
+    dp.log_meta = lg.meta.get();
+    dp.log_cnt = lg.counters.get();
     dp.log_cap = lg.cap;
     dp.raw_lists = 1;
     dp.no_q64 = 1;
     kz_knn_stats st;
     // (k = 1: lists of 16 -- the build with the most workgroups per CU; nothing is finalized, out_dist / out_ind are not written)
-    rc = kz_knn_impl(ctx, qsub, 0, nb, index, 1, 0, nullptr, 0, 0, out_dist, out_ind, &st, &dp);
+    KzResearch fp16_only;
+    fp16_only.prec = 0;
+    rc = kz_knn_impl(ctx, qsub, 0, nb, index, 1, 0, nullptr, fp16_only, out_dist, out_ind, &st, &dp);
     if (rc != KZ_OK) return rc;
-    e = hipMemcpyAsync(n_groups, lg.counters, 8, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(n_groups, lg.counters.get(), 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         kz_set_error("kz_knn: range re-search: reading the log counter failed");
@@ -504,24 +506,15 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
     if (n_rep > KZ_RG_MAX_REPS) n_rep = KZ_RG_MAX_REPS;
     if ((size_t)n_rep * n_fail > ((size_t)1 << 27)) n_rep = (int)(((size_t)1 << 27) / n_fail);   // (representatives x rows: at most 1 GiB of values)
     *pairs = 0;
-    // every buffer of the path (released together, stream-ordered)
-    int *rep_fl = nullptr, *ibuf = nullptr, *pair_idx = nullptr, *mates = nullptr, *slot_grp = nullptr;
-    void *rep_raw = nullptr, *all_raw = nullptr;
-    kz_matrix *rm = nullptr, *fm = nullptr;
-    double *rv = nullptr, *tau_rep = nullptr, *vals = nullptr;
-    float* thr = nullptr;   // [2 n_pad]: thresholds, +inf floors
-    long long *seg_rep = nullptr, *lbuf = nullptr;
-    auto release = [&]() {
-        if (rm) kz_matrix_destroy(rm);
-        if (fm) kz_matrix_destroy(fm);
-        kz_pool_free(ctx, rep_fl, 0); kz_pool_free(ctx, ibuf, 0); kz_pool_free(ctx, pair_idx, 0); kz_pool_free(ctx, mates, 0);
-        kz_pool_free(ctx, rep_raw, 0); kz_pool_free(ctx, all_raw, 0); kz_pool_free(ctx, rv, 0);
-        kz_pool_free(ctx, tau_rep, 0); kz_pool_free(ctx, vals, 0); kz_pool_free(ctx, thr, 0);
-        kz_pool_free(ctx, seg_rep, 0); kz_pool_free(ctx, lbuf, 0);
-    };
+    // every buffer of the path (released together when it returns, stream-ordered: rm, fm, rep_fl, ibuf, pair_idx, ..., lbuf)
+    KzPoolBuf<long long> lbuf, seg_rep;
+    KzPoolBuf<float> thr;   // [2 n_pad]: thresholds, +inf floors
+    KzPoolBuf<double> vals, tau_rep, rv;
+    KzPoolBuf<void> all_raw, rep_raw;
+    KzPoolBuf<int> mates, pair_idx, ibuf, rep_fl;
+    KzMatrixPtr fm, rm;
     // "nothing grouped": every row is the per-row path's
     auto give_up = [&](int rc_in) -> int {
-        release();
         if (rc_in != KZ_OK && rc_in != KZ_ERR_NOMEM) return rc_in;
         hipError_t e0 = hipMemcpyAsync(rest, fl, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream);
         if (e0 == hipSuccess) e0 = hipMemcpyAsync(rest_tau, tau, (size_t)n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream);
@@ -537,68 +530,71 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
     const int64_t stride = n_fail / n_rep;
     const int64_t rep_pad = (int64_t)((n_rep + KZ_TILE - 1) / KZ_TILE) * KZ_TILE;
     // ibuf: grp [n_fail] | rbits | mcount | cnt | cur | acc_of | mate_off | blen | mcur | iota [n_rep each] | rest_cnt [1]
-    int rc = kz_pool_alloc(ctx, (size_t)n_rep * sizeof(int), (void**)&rep_fl);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, ((size_t)n_fail + 9 * (size_t)n_rep + 4) * sizeof(int), (void**)&ibuf);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_rep * row_bytes, &rep_raw);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * row_bytes, &all_raw);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_rep * (size_t)n_fail * 8, (void**)&rv);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_rep * 8, (void**)&tau_rep);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)rep_pad * 2 * sizeof(float), (void**)&thr);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)(n_rep + 1) * sizeof(long long), (void**)&seg_rep);
+    int rc = rep_fl.alloc(ctx, (size_t)n_rep * sizeof(int));
+    if (rc == KZ_OK) rc = ibuf.alloc(ctx, ((size_t)n_fail + 9 * (size_t)n_rep + 4) * sizeof(int));
+    if (rc == KZ_OK) rc = rep_raw.alloc(ctx, (size_t)n_rep * row_bytes);
+    if (rc == KZ_OK) rc = all_raw.alloc(ctx, (size_t)n_fail * row_bytes);
+    if (rc == KZ_OK) rc = rv.alloc(ctx, (size_t)n_rep * (size_t)n_fail * 8);
+    if (rc == KZ_OK) rc = tau_rep.alloc(ctx, (size_t)n_rep * 8);
+    if (rc == KZ_OK) rc = thr.alloc(ctx, (size_t)rep_pad * 2 * sizeof(float));
+    if (rc == KZ_OK) rc = seg_rep.alloc(ctx, (size_t)(n_rep + 1) * sizeof(long long));
     // (slots: a group's rows, padded to whole blocks of 16 operand rows -- at most n_fail + 16 n_rep of them)
     const size_t slots_cap = (size_t)n_fail + 16 * (size_t)n_rep;
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, slots_cap * 3 * sizeof(int), (void**)&mates);   // mates | slot_grp | seg_len
+    if (rc == KZ_OK) rc = mates.alloc(ctx, slots_cap * 3 * sizeof(int));   // mates | slot_grp | seg_len
     // lbuf: ball_off [n_rep] | val_off [n_rep] | seg_off [slots] | idx_off [slots] | group descriptors [n_rep]
     if (rc == KZ_OK)
-        rc = kz_pool_alloc(ctx, (2 * (size_t)n_rep + 2 * slots_cap + 2) * sizeof(long long) + (size_t)n_rep * sizeof(KzXlGroup), (void**)&lbuf);
+        rc = lbuf.alloc(ctx, (2 * (size_t)n_rep + 2 * slots_cap + 2) * sizeof(long long) + (size_t)n_rep * sizeof(KzXlGroup));
     if (rc != KZ_OK) return give_up(rc);
-    int *grp = ibuf, *rbits = ibuf + n_fail, *mcount = rbits + n_rep, *cnt = mcount + n_rep, *cur = cnt + n_rep, *acc_of = cur + n_rep,
+    int *grp = ibuf.get(), *rbits = ibuf.get() + n_fail, *mcount = rbits + n_rep, *cnt = mcount + n_rep, *cur = cnt + n_rep, *acc_of = cur + n_rep,
         *mate_off = acc_of + n_rep, *blen = mate_off + n_rep, *mcur = blen + n_rep, *iota = mcur + n_rep, *rest_cnt = iota + n_rep;
-    long long *ball_off = lbuf, *val_off = lbuf + n_rep, *seg_off = val_off + n_rep, *idx_off = seg_off + slots_cap + 1;
+    long long *ball_off = lbuf.get(), *val_off = lbuf.get() + n_rep, *seg_off = val_off + n_rep, *idx_off = seg_off + slots_cap + 1;
     KzXlGroup* d_groups = (KzXlGroup*)(idx_off + slots_cap + 1);
-    slot_grp = mates + slots_cap;
+    int* slot_grp = mates.get() + slots_cap;
     int* seg_len = slot_grp + slots_cap;
     hipError_t e = hipMemsetAsync(rbits, 0, (9 * (size_t)n_rep + 4) * sizeof(int), ctx->stream);
     if (e != hipSuccess) return give_up(KZ_ERR_NOMEM);
     // ---- representatives; every failed row's nearest one (exact values representatives x failed rows, the dense kernels) --------
-    hipLaunchKernelGGL(kz_strided_pick_kernel, dim3((n_rep + 255) / 256), dim3(256), 0, ctx->stream, fl, n_rep, stride, rep_fl);
+    hipLaunchKernelGGL(kz_strided_pick_kernel, dim3((n_rep + 255) / 256), dim3(256), 0, ctx->stream, fl, n_rep, stride, rep_fl.get());
     hipLaunchKernelGGL(kz_iota_kernel, dim3((n_rep + 255) / 256), dim3(256), 0, ctx->stream, iota, n_rep);
-    hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_rep), dim3(256), 0, ctx->stream, (const char*)query->raw, rep_fl, q0, n_rep, (int64_t)row_bytes,
-                       (char*)rep_raw, (int64_t*)nullptr, (const int64_t*)nullptr);
+    hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_rep), dim3(256), 0, ctx->stream, (const char*)query->raw, rep_fl.get(), q0, n_rep, (int64_t)row_bytes,
+                       (char*)rep_raw.get(), (int64_t*)nullptr, (const int64_t*)nullptr);
     hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_fail), dim3(256), 0, ctx->stream, (const char*)query->raw, fl, q0, n_fail, (int64_t)row_bytes,
-                       (char*)all_raw, (int64_t*)nullptr, (const int64_t*)nullptr);
-    rc = kz_matrix_create(ctx, rep_raw, 2, n_rep, d, query->dtype, query->metric, &rm);
-    if (rc == KZ_OK) rc = kz_matrix_create(ctx, all_raw, 2, n_fail, d, query->dtype, query->metric, &fm);
+                       (char*)all_raw.get(), (int64_t*)nullptr, (const int64_t*)nullptr);
+    kz_matrix *rm_new = nullptr, *fm_new = nullptr;
+    rc = kz_matrix_create(ctx, rep_raw.get(), 2, n_rep, d, query->dtype, query->metric, &rm_new);
+    rm.reset(rm_new);
+    if (rc == KZ_OK) rc = kz_matrix_create(ctx, all_raw.get(), 2, n_fail, d, query->dtype, query->metric, &fm_new);
+    fm.reset(fm_new);
     if (rc != KZ_OK) return give_up(rc);
     {
         bool took = false;
-        rc = kz_launch_exact_lanes(ctx, iota, 0, n_rep, 0, rm, fm, metric, rv, &took);
+        rc = kz_launch_exact_lanes(ctx, iota, 0, n_rep, 0, rm.get(), fm.get(), metric, rv.get(), &took);
         if (rc != KZ_OK) return give_up(rc);
-        if (!took && !kz_launch_exact_rows(ctx, iota, 0, n_rep, 0, rm, fm, metric, rv))
+        if (!took && !kz_launch_exact_rows(ctx, iota, 0, n_rep, 0, rm.get(), fm.get(), metric, rv.get()))
             hipLaunchKernelGGL(kz_exact_dist_kernel<float>, dim3((unsigned)((n_fail + 3) / 4), n_rep), dim3(256), 0, ctx->stream, iota, 0, (int64_t)0,
-                               (const float*)rm->raw, (const float*)fm->raw, rm->sqn, fm->sqn, (int64_t)n_fail, d, metric, index->mink_p, rv,
+                               (const float*)rm->raw, (const float*)fm->raw, rm->sqn, fm->sqn, (int64_t)n_fail, d, metric, index->mink_p, rv.get(),
                                (const int*)nullptr);
     }
-    hipLaunchKernelGGL(kz_rg_assign_kernel, dim3((n_fail + 255) / 256), dim3(256), 0, ctx->stream, tau, rv, n_rep, n_fail, metric, fm->d_stats,
+    hipLaunchKernelGGL(kz_rg_assign_kernel, dim3((n_fail + 255) / 256), dim3(256), 0, ctx->stream, tau, rv.get(), n_rep, n_fail, metric, fm->d_stats,
                        index->d_stats, grp, rbits, mcount);
     hipLaunchKernelGGL(kz_rg_tau_kernel, dim3((n_rep + 255) / 256), dim3(256), 0, ctx->stream, rbits, mcount, n_rep, metric, fm->d_stats, index->d_stats,
-                       tau_rep);
+                       tau_rep.get());
     // ---- the representatives' ranges -----------------------------------------------------------------------------------------
     unsigned long long n_groups = 0;
     bool over = false;
-    rc = kz_range_sweep_rows(ctx, rm, tau_rep, n_rep, index, lg, thr, thr + rep_pad, out_dist, out_ind, &n_groups, &over);
+    rc = kz_range_sweep_rows(ctx, rm.get(), tau_rep.get(), n_rep, index, lg, thr.get(), thr.get() + rep_pad, out_dist, out_ind, &n_groups, &over);
     if (rc != KZ_OK) return give_up(rc);
     if (over) return give_up(KZ_OK);
     const int gb = (int)((n_groups + 255) / 256 < 8192 ? (n_groups + 255) / 256 : 8192);
     if (n_groups > 0)
-        hipLaunchKernelGGL(kz_range_count_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys, (const i32x2e*)lg.meta, (long long)n_groups,
-                           thr, index->n, cnt);
-    hipLaunchKernelGGL(kz_range_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt, n_rep, seg_rep);
+        hipLaunchKernelGGL(kz_range_count_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys.get(), (const i32x2e*)lg.meta.get(), (long long)n_groups,
+                           thr.get(), index->n, cnt);
+    hipLaunchKernelGGL(kz_range_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt, n_rep, seg_rep.get());
     std::vector<int> h_cnt(n_rep), h_m(n_rep);
     long long rep_total = 0;
     e = hipMemcpyAsync(h_cnt.data(), cnt, (size_t)n_rep * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h_m.data(), mcount, (size_t)n_rep * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&rep_total, seg_rep + n_rep, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&rep_total, seg_rep.get() + n_rep, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return give_up(KZ_ERR_NOMEM);
     size_t mem_free = 0, mem_total = 0;
@@ -641,8 +637,8 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
     }
     const int n_acc = (int)h_moff.size();
     if (n_acc == 0) return give_up(KZ_OK);
-    rc = kz_pool_alloc(ctx, (size_t)rep_total * 4 + 4, (void**)&pair_idx);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)tot_pairs * 8 + 8, (void**)&vals);
+    rc = pair_idx.alloc(ctx, (size_t)rep_total * 4 + 4);
+    if (rc == KZ_OK) rc = vals.alloc(ctx, (size_t)tot_pairs * 8 + 8);
     if (rc != KZ_OK) return give_up(rc);
     // (pageable host arrays: waited for below, before the vectors go out of scope)
     e = hipMemcpyAsync(acc_of, h_acc.data(), (size_t)n_rep * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
@@ -651,21 +647,21 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
     if (e == hipSuccess) e = hipMemcpyAsync(ball_off, h_boff.data(), (size_t)n_acc * sizeof(long long), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(val_off, h_voff.data(), (size_t)n_acc * sizeof(long long), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_groups, h_groups.data(), (size_t)n_acc * sizeof(KzXlGroup), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(mates, 0xff, (size_t)n_slots * sizeof(int), ctx->stream);      // (-1: padding rows)
+    if (e == hipSuccess) e = hipMemsetAsync(mates.get(), 0xff, (size_t)n_slots * sizeof(int), ctx->stream);      // (-1: padding rows)
     if (e == hipSuccess) e = hipMemsetAsync(slot_grp, 0xff, (size_t)n_slots * sizeof(int), ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return give_up(KZ_ERR_NOMEM);
     if (n_groups > 0)
-        hipLaunchKernelGGL(kz_range_fill_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys, (const i32x2e*)lg.meta, (long long)n_groups,
-                           thr, index->n, seg_rep, cur, pair_idx);
-    hipLaunchKernelGGL(kz_rg_mates_kernel, dim3((n_fail + 255) / 256), dim3(256), 0, ctx->stream, grp, acc_of, mate_off, n_fail, fl, tau, mcur, mates, slot_grp,
+        hipLaunchKernelGGL(kz_range_fill_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys.get(), (const i32x2e*)lg.meta.get(), (long long)n_groups,
+                           thr.get(), index->n, seg_rep.get(), cur, pair_idx.get());
+    hipLaunchKernelGGL(kz_rg_mates_kernel, dim3((n_fail + 255) / 256), dim3(256), 0, ctx->stream, grp, acc_of, mate_off, n_fail, fl, tau, mcur, mates.get(), slot_grp,
                        rest, rest_tau, rest_cnt);
     hipLaunchKernelGGL(kz_rg_slots_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, slot_grp, mate_off, blen, ball_off, val_off, n_slots,
                        seg_off, seg_len, idx_off);
     // the groups = dense blocks, ONE launch: their rows against the rows of their ranges, one pair per lane (kz_exact_lanes.h, GATHER)
     {
         bool took = false;
-        rc = kz_launch_exact_lanes(ctx, mates, 0, n_slots, q0, query, index, metric, vals, &took, nullptr, nullptr, pair_idx, d_groups, n_acc, rows_max,
+        rc = kz_launch_exact_lanes(ctx, mates.get(), 0, n_slots, q0, query, index, metric, vals.get(), &took, nullptr, nullptr, pair_idx.get(), d_groups, n_acc, rows_max,
                                    q_max);
         if (rc == KZ_OK && !took) {
             kz_set_error("kz_knn: internal: the dense kernel refused the groups of the range re-search");
@@ -673,18 +669,16 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
         }
         if (rc != KZ_OK) {
             (void)hipStreamSynchronize(ctx->stream);
-            release();
             return rc;
         }
     }
-    hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(n_slots), dim3(256), sel_lds, ctx->stream, mates, 0, q0, (const double*)vals, (const int*)pair_idx,
+    hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(n_slots), dim3(256), sel_lds, ctx->stream, mates.get(), 0, q0, (const double*)vals.get(), (const int*)pair_idx.get(),
                        (int64_t)0, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p, out_dist, out_ind, (const int*)nullptr,
                        (const long long*)seg_off, left, left_cnt, (const long long*)idx_off, (const int*)seg_len);
     int h_rest = 0;
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&h_rest, rest_cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    release();
     if (e != hipSuccess) {
         kz_set_error("kz_knn: grouped range re-search failed: %s", hipGetErrorString(e));
         return KZ_ERR_HIP;
@@ -725,9 +719,10 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
         const int rc = kz_matrix_norm64(index);    //  them; for a few hundred rows the image -- 800 MB for 500 k x 200 -- costs more than
         if (rc != KZ_OK) return rc;                //  the divisions it saves: the kernels divide the raw rows, the same values)
     }
+    // (every buffer below is released when the search returns, the log's first: theta0, keys, meta, counters, rest, rest_tau)
+    KzPoolBuf<double> rest_tau;
+    KzPoolBuf<int> rest;        // the rows the grouped path leaves to the per-row path, their bounds
     KzRangeLog lg;
-    int* rest = nullptr;        // the rows the grouped path leaves to the per-row path, their bounds
-    double* rest_tau = nullptr;
     // The log is sized for what is about to be swept -- 65 536 groups per representative (a range beyond that is not taken anyway),
     // 4 096 per row of a per-row batch -- and grown when the next sweep needs more: a 6 GiB log for every call (the limit above)
     // kept the context's buffer cache turning over gigabytes.
@@ -735,45 +730,34 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
         if (want > log_cap) want = log_cap;
         if (want < (1ll << 16) && !(ctx->abl & 4)) want = 1ll << 16;
         if (lg.cap >= want) return KZ_OK;
-        kz_pool_free(ctx, lg.keys, 0);
-        kz_pool_free(ctx, lg.meta, 0);
-        lg.keys = lg.meta = nullptr;
+        lg.keys.reset();
+        lg.meta.reset();
         lg.cap = 0;
-        int rc2 = kz_pool_alloc(ctx, (size_t)want * 16, &lg.keys);
-        if (rc2 == KZ_OK) rc2 = kz_pool_alloc(ctx, (size_t)want * 8, &lg.meta);
+        int rc2 = lg.keys.alloc(ctx, (size_t)want * 16);
+        if (rc2 == KZ_OK) rc2 = lg.meta.alloc(ctx, (size_t)want * 8);
         if (rc2 == KZ_OK) lg.cap = want;
         return rc2;
     };
     const bool try_groups = n_fail >= KZ_RG_MIN_ROWS && !(ctx->abl & 16);
-    int rc = kz_pool_alloc(ctx, (size_t)y_pad * 4, (void**)&lg.theta0);
+    int rc = lg.theta0.alloc(ctx, (size_t)y_pad * 4);
     if (rc == KZ_OK)
         rc = ensure_log(try_groups ? (long long)(n_fail / KZ_RG_STRIDE + 1 < KZ_RG_MAX_REPS ? n_fail / KZ_RG_STRIDE + 1 : KZ_RG_MAX_REPS) * 65536
                                    : (long long)(n_fail < KZ_RANGE_BATCH ? n_fail : KZ_RANGE_BATCH) * 4096);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, 64, (void**)&lg.counters);
-    auto release_all = [&]() {
-        kz_pool_free(ctx, lg.theta0, 0);
-        kz_pool_free(ctx, lg.keys, 0);
-        kz_pool_free(ctx, lg.meta, 0);
-        kz_pool_free(ctx, lg.counters, 0);
-        kz_pool_free(ctx, rest, 0);
-        kz_pool_free(ctx, rest_tau, 0);
-    };
+    if (rc == KZ_OK) rc = lg.counters.alloc(ctx, 64);
     if (rc != KZ_OK) {
-        release_all();
         if (rc != KZ_ERR_NOMEM) return rc;
         KZ_HIP(hipMemcpyAsync(left, fl, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
         KZ_HIP(hipStreamSynchronize(ctx->stream));
         *n_left = n_fail;
         return KZ_OK;
     }
-    hipError_t e = hipMemsetAsync(lg.theta0, 0, (size_t)y_pad * 4, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(lg.counters, 0, 64, ctx->stream);
+    hipError_t e = hipMemsetAsync(lg.theta0.get(), 0, (size_t)y_pad * 4, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(lg.counters.get(), 0, 64, ctx->stream);
     if (e != hipSuccess) {
-        release_all();
         kz_set_error("kz_knn: range re-search: %s", hipGetErrorString(e));
         return KZ_ERR_HIP;
     }
-    int* left_cnt = (int*)(lg.counters + 1);
+    int* left_cnt = (int*)(lg.counters.get() + 1);
     long long pairs_total = 0;
     auto read_back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {   // (behind everything queued on the context's stream)
         const hipError_t e1 = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -783,33 +767,28 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
     // (grouped_only -- the EARLY call, rows that have tiers left to try: groups only, and only while their blocks hold at most an eighth
     //  of the pairs the whole index would; the rows that are not grouped come back in `left` for the next tier)
     if (try_groups) {
-        rc = kz_pool_alloc(ctx, (size_t)n_fail * sizeof(int), (void**)&rest);
-        if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_fail * 8, (void**)&rest_tau);
+        rc = rest.alloc(ctx, (size_t)n_fail * sizeof(int));
+        if (rc == KZ_OK) rc = rest_tau.alloc(ctx, (size_t)n_fail * 8);
         if (rc == KZ_OK) {
             int n_rest = 0;
             long long gp = 0;
-            rc = kz_range_grouped(ctx, query, q0, fl, tau, n_fail, index, k, exclude_self, d_self_ids, out_dist, out_ind, lg, rest, rest_tau, &n_rest,
+            rc = kz_range_grouped(ctx, query, q0, fl, tau, n_fail, index, k, exclude_self, d_self_ids, out_dist, out_ind, lg, rest.get(), rest_tau.get(), &n_rest,
                                   left, left_cnt, &gp, grouped_only ? (long long)((double)n_fail * (double)index->n / 8.0) : -1);
-            if (rc != KZ_OK) {
-                release_all();
-                return rc;
-            }
+            if (rc != KZ_OK) return rc;
             pairs_total += gp;
             if (n_grouped_out) *n_grouped_out = n_fail - n_rest;
-            fl = rest;
-            tau = rest_tau;
+            fl = rest.get();
+            tau = rest_tau.get();
             n_fail = n_rest;
         } else if (rc != KZ_ERR_NOMEM) {
-            release_all();
             return rc;
         }
     }
     // (... unless only a few are left: the next tier would sweep the whole index for them -- 3.3 ms per launch of the float32-operand
     //  kernel on 200 k rows whatever the row count -- where their own ranges cost a fraction of that)
-    if (grouped_only && fl == rest && n_fail <= per_row_max) grouped_only = false;
+    if (grouped_only && fl == rest.get() && n_fail <= per_row_max) grouped_only = false;
     if (grouped_only) {   // (what the groups did not take: handed back behind the rows their selection handed back)
-        if (fl != rest) {   // (no group was tried: nothing was answered)
-            release_all();
+        if (fl != rest.get()) {   // (no group was tried: nothing was answered)
             KZ_HIP(hipMemcpyAsync(left, fl, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
             KZ_HIP(hipStreamSynchronize(ctx->stream));
             *n_left = n_fail;
@@ -819,7 +798,6 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
         hipError_t e2 = read_back(&have, left_cnt, sizeof(int));
         if (e2 == hipSuccess && n_fail > 0) e2 = hipMemcpyAsync(left + have, fl, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream);
         if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-        release_all();
         if (e2 != hipSuccess) {
             kz_set_error("kz_knn: range re-search: %s", hipGetErrorString(e2));
             return KZ_ERR_HIP;
@@ -837,7 +815,6 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
             hipError_t e2 = rc == KZ_ERR_NOMEM ? read_back(&have, left_cnt, sizeof(int)) : hipErrorUnknown;
             if (e2 == hipSuccess) e2 = hipMemcpyAsync(left + have, fl, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream);
             if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-            release_all();
             if (e2 != hipSuccess) return rc == KZ_ERR_NOMEM ? KZ_ERR_HIP : rc;
             *n_left = have + n_fail;
             if (n_pairs_out) *n_pairs_out = pairs_total;
@@ -847,59 +824,47 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
     for (int b0 = 0; b0 < n_fail;) {
         const int nb = n_fail - b0 < batch ? n_fail - b0 : batch;
         // ---- the batch's rows as a matrix of their own, their thresholds, the sweep ------------------------------------
-        void* sub_raw = nullptr;
-        kz_matrix* qsub = nullptr;
-        float *thr = nullptr, *inff = nullptr;
-        int* cnt = nullptr;   // [nb] pairs per row, then [nb] fill cursors
-        long long* seg_off = nullptr;
-        int* pair_idx = nullptr;
-        double* pair_val = nullptr;
-        auto release = [&]() {
-            if (qsub) kz_matrix_destroy(qsub);
-            kz_pool_free(ctx, sub_raw, 0);
-            kz_pool_free(ctx, thr, 0);
-            kz_pool_free(ctx, inff, 0);
-            kz_pool_free(ctx, cnt, 0);
-            kz_pool_free(ctx, seg_off, 0);
-            kz_pool_free(ctx, pair_idx, 0);
-            kz_pool_free(ctx, pair_val, 0);
-        };
-        auto fail = [&](int code) {
-            release();
-            release_all();
-            return code;
-        };
+        // (the batch's buffers: released at the end of each pass of the loop -- qsub, sub_raw, thr, inff, cnt, seg_off, pair_idx, pair_val)
+        KzPoolBuf<double> pair_val;
+        KzPoolBuf<int> pair_idx;
+        KzPoolBuf<long long> seg_off;
+        KzPoolBuf<int> cnt;   // [nb] pairs per row, then [nb] fill cursors
+        KzPoolBuf<float> inff, thr;
+        KzPoolBuf<void> sub_raw;
+        KzMatrixPtr qsub;
         const int64_t n_pad = (int64_t)((nb + KZ_TILE - 1) / KZ_TILE) * KZ_TILE;
-        rc = kz_pool_alloc(ctx, (size_t)nb * row_bytes, &sub_raw);
-        if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_pad * 4, (void**)&thr);
-        if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n_pad * 4, (void**)&inff);
-        if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)nb * 2 * sizeof(int), (void**)&cnt);
-        if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)(nb + 1) * sizeof(long long), (void**)&seg_off);
-        if (rc != KZ_OK) return fail(rc);
+        rc = sub_raw.alloc(ctx, (size_t)nb * row_bytes);
+        if (rc == KZ_OK) rc = thr.alloc(ctx, (size_t)n_pad * 4);
+        if (rc == KZ_OK) rc = inff.alloc(ctx, (size_t)n_pad * 4);
+        if (rc == KZ_OK) rc = cnt.alloc(ctx, (size_t)nb * 2 * sizeof(int));
+        if (rc == KZ_OK) rc = seg_off.alloc(ctx, (size_t)(nb + 1) * sizeof(long long));
+        if (rc != KZ_OK) return rc;
         hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const char*)query->raw, fl + b0, q0, nb, (int64_t)row_bytes,
-                           (char*)sub_raw, (int64_t*)nullptr, (const int64_t*)nullptr);
-        rc = kz_matrix_create(ctx, sub_raw, 2, nb, query->d, query->dtype, query->metric, &qsub);
-        if (rc != KZ_OK) return fail(rc);
-        e = hipMemsetAsync(cnt, 0, (size_t)nb * 2 * sizeof(int), ctx->stream);
+                           (char*)sub_raw.get(), (int64_t*)nullptr, (const int64_t*)nullptr);
+        kz_matrix* qsub_new = nullptr;
+        rc = kz_matrix_create(ctx, sub_raw.get(), 2, nb, query->d, query->dtype, query->metric, &qsub_new);
+        qsub.reset(qsub_new);
+        if (rc != KZ_OK) return rc;
+        e = hipMemsetAsync(cnt.get(), 0, (size_t)nb * 2 * sizeof(int), ctx->stream);
         if (e != hipSuccess) {
             kz_set_error("kz_knn: range re-search: %s", hipGetErrorString(e));
-            return fail(KZ_ERR_HIP);
+            return KZ_ERR_HIP;
         }
         unsigned long long n_groups = 0;
         bool over = false;
-        rc = kz_range_sweep_rows(ctx, qsub, tau + b0, nb, index, lg, thr, inff, out_dist, out_ind, &n_groups, &over);
-        if (rc != KZ_OK) return fail(rc);
+        rc = kz_range_sweep_rows(ctx, qsub.get(), tau + b0, nb, index, lg, thr.get(), inff.get(), out_dist, out_ind, &n_groups, &over);
+        if (rc != KZ_OK) return rc;
         long long total = 0;
         if (!over && n_groups > 0) {
             const int gb = (int)((n_groups + 255) / 256 < 8192 ? (n_groups + 255) / 256 : 8192);
-            hipLaunchKernelGGL(kz_range_count_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys, (const i32x2e*)lg.meta,
-                               (long long)n_groups, thr, index->n, cnt);
+            hipLaunchKernelGGL(kz_range_count_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys.get(), (const i32x2e*)lg.meta.get(),
+                               (long long)n_groups, thr.get(), index->n, cnt.get());
         }
         if (!over) {
-            hipLaunchKernelGGL(kz_range_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt, nb, seg_off);
-            if (hipGetLastError() != hipSuccess || read_back(&total, seg_off + nb, 8) != hipSuccess) {
+            hipLaunchKernelGGL(kz_range_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt.get(), nb, seg_off.get());
+            if (hipGetLastError() != hipSuccess || read_back(&total, seg_off.get() + nb, 8) != hipSuccess) {
                 kz_set_error("kz_knn: range re-search: counting the pairs failed");
-                return fail(KZ_ERR_HIP);
+                return KZ_ERR_HIP;
             }
             // (idx + value: 12 bytes a pair, at most a quarter of what is free now)
             size_t f2 = 0, t2 = 0;
@@ -907,7 +872,6 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
             if ((size_t)total * 12 > f2 / 4) over = true;
         }
         if (over) {
-            release();
             if (batch > KZ_RANGE_MIN_BATCH && nb > KZ_RANGE_MIN_BATCH) {   // the same rows again, fewer per sweep
                 batch = batch / 4 > KZ_RANGE_MIN_BATCH ? batch / 4 : KZ_RANGE_MIN_BATCH;
                 continue;
@@ -920,7 +884,6 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
             if (e2 == hipSuccess) e2 = hipMemcpyAsync(left_cnt, &have, sizeof(int), hipMemcpyHostToDevice, ctx->stream);
             if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
             if (e2 != hipSuccess) {
-                release_all();
                 kz_set_error("kz_knn: range re-search: %s", hipGetErrorString(e2));
                 return KZ_ERR_HIP;
             }
@@ -928,29 +891,28 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
             continue;
         }
         if (total > 0) {
-            rc = kz_pool_alloc(ctx, (size_t)total * 4, (void**)&pair_idx);
-            if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)total * 8, (void**)&pair_val);
-            if (rc != KZ_OK) return fail(rc);
+            rc = pair_idx.alloc(ctx, (size_t)total * 4);
+            if (rc == KZ_OK) rc = pair_val.alloc(ctx, (size_t)total * 8);
+            if (rc != KZ_OK) return rc;
             const int gb = (int)((n_groups + 255) / 256 < 8192 ? (n_groups + 255) / 256 : 8192);
-            hipLaunchKernelGGL(kz_range_fill_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys, (const i32x2e*)lg.meta,
-                               (long long)n_groups, thr, index->n, seg_off, cnt + nb, pair_idx);
-            kz_launch_exact_pairs(ctx, seg_off, nb, fl, b0, q0, query, index, total, pair_idx, pair_val);
+            hipLaunchKernelGGL(kz_range_fill_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const f32x4e*)lg.keys.get(), (const i32x2e*)lg.meta.get(),
+                               (long long)n_groups, thr.get(), index->n, seg_off.get(), cnt.get() + nb, pair_idx.get());
+            kz_launch_exact_pairs(ctx, seg_off.get(), nb, fl, b0, q0, query, index, total, pair_idx.get(), pair_val.get());
         }
-        hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl, b0, q0, (const double*)pair_val,
-                           (const int*)pair_idx, (int64_t)0, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p, out_dist, out_ind,
-                           (const int*)nullptr, (const long long*)seg_off, left, left_cnt);
+        hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl, b0, q0, (const double*)pair_val.get(),
+                           (const int*)pair_idx.get(), (int64_t)0, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p, out_dist, out_ind,
+                           (const int*)nullptr, (const long long*)seg_off.get(), left, left_cnt);
         e = hipGetLastError();
         if (e != hipSuccess) {
             kz_set_error("kz_knn: range re-search: %s", hipGetErrorString(e));
-            return fail(KZ_ERR_HIP);
+            return KZ_ERR_HIP;
         }
         pairs_total += total;
-        release();   // (stream-ordered pool: the launches above have the buffers)
+        // (the batch's buffers go here, stream-ordered: the launches above have them)
         b0 += nb;
     }
     int have = 0;
     e = read_back(&have, left_cnt, sizeof(int));
-    release_all();
     if (e != hipSuccess) {
         kz_set_error("kz_knn: range re-search failed: %s", hipGetErrorString(e));
         return KZ_ERR_HIP;

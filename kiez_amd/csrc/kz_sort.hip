@@ -149,12 +149,15 @@ int kz_sort_pairs_f32_i32(kz_ctx* ctx, const float* keys_in, float* keys_out, co
     if (n == 0) return KZ_OK;
     const int n_tiles = (n + SORT_TILE - 1) / SORT_TILE;
     // ping-pong: pass 0  in -> tmp, pass 1  tmp -> out, pass 2  out -> tmp, pass 3  tmp -> out
-    unsigned* tmp_k = nullptr;
-    int *tmp_v = nullptr, *hist = nullptr;
-    int rc = kz_pool_alloc(ctx, (size_t)n * 4, (void**)&tmp_k);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, (size_t)n * 4, (void**)&tmp_v);
-    if (rc == KZ_OK) rc = kz_pool_alloc(ctx, ((size_t)256 * n_tiles + 256) * 4, (void**)&hist);   // counters [digit][tile] + 256 digit totals
+    // (stream-ordered pool: reuse is ordered behind the sort; released hist, tmp_v, tmp_k)
+    KzPoolBuf<unsigned> tmp_kb;
+    KzPoolBuf<int> tmp_vb, histb;
+    int rc = tmp_kb.alloc(ctx, (size_t)n * 4);
+    if (rc == KZ_OK) rc = tmp_vb.alloc(ctx, (size_t)n * 4);
+    if (rc == KZ_OK) rc = histb.alloc(ctx, ((size_t)256 * n_tiles + 256) * 4);   // counters [digit][tile] + 256 digit totals
     if (rc == KZ_OK) {
+        unsigned* tmp_k = tmp_kb.get();
+        int *tmp_v = tmp_vb.get(), *hist = histb.get();
         const dim3 grid((unsigned)n_tiles), block(SORT_THREADS);
         int* totals = hist + (size_t)256 * n_tiles;
         const int desc = descending ? 1 : 0;
@@ -181,8 +184,5 @@ int kz_sort_pairs_f32_i32(kz_ctx* ctx, const float* keys_in, float* keys_out, co
             rc = KZ_ERR_HIP;
         }
     }
-    kz_pool_free(ctx, hist, 0);   // stream-ordered pool: reuse is ordered behind the sort
-    kz_pool_free(ctx, tmp_v, 0);
-    kz_pool_free(ctx, tmp_k, 0);
     return rc;
 }

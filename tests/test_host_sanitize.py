@@ -1,7 +1,9 @@
 """the host-side scheduling code of the native library under AddressSanitizer + UBSan -- on the CPU build
 only (GPU sanitizers are not available on the pool).  kiez_amd/csrc/kz_plan.h has no HIP dependency; tests/host/plan_sanitize.cpp
 plans ~3000 random and all BASELINE shapes (narrow and wide workgroups) and checks coverage / layout invariants;
-kiez_amd/csrc/kz_floor.h (the model behind the seeded candidate lists) is fitted to synthetic probes by tests/host/floor_sanitize.cpp."""
+kiez_amd/csrc/kz_floor.h (the model behind the seeded candidate lists) is fitted to synthetic probes by tests/host/floor_sanitize.cpp;
+kiez_amd/csrc/kz_pool_buf.h (the scoped owner of the context pool's transient buffers) runs against a fake pool in
+tests/host/pool_buf_sanitize.cpp: every buffer released exactly once on every return path, none left live."""
 import shutil
 import subprocess
 from pathlib import Path
@@ -12,7 +14,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-@pytest.mark.parametrize("name", ["plan_sanitize", "floor_sanitize"])
+@pytest.mark.parametrize("name", ["plan_sanitize", "floor_sanitize", "pool_buf_sanitize"])
 def test_host_code_is_clean_under_asan_and_ubsan(tmp_path, name):
     exe = tmp_path / name
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
