@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: source queries/s over fit + kneighbors (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--workload ns|c1|c2|c3|c3s|c4s|c4|c1g|hard|cliff|gmm|ea15k] [--no-others]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--workload ns|c1|c2|c3|c3s|c4s|c4|c1g|hard|cliff|gmm|ea15k]
+    python bench.py ... --full [--no-check] [--no-cpu-baseline] [--no-others]      (also the checks and the other measurements)
     python bench.py --openea EMB_DIR KG_DIR [--steps K] [--warmup W]      (real entity-alignment embeddings)
     python bench.py ... --dump-outputs DIR      (also write what the last timed step computed: DIR/dist.npy, ind.npy, rows.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -17,9 +18,14 @@ A "step" is one full `fit(source, target)` + `kneighbors(k)` over synthetic embe
 HBM (the reference's `rng.rand` data, float32).  Default workload = the shape BASELINE.json quotes its target on, one
 GPU's share of it: 250k source rows x 1M targets, d=200, k=10, CSLS ("ns"); with N > 1 every rank owns a 250k-row source
 shard (weak scaling, 8 GPUs = 2M x 1M); the target lives on rank 0 and is RCCL-broadcast inside `fit`.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects; at N = 1 the
-other BASELINE configurations (C1, C2, C3 full size, C4's per-GPU share) are run briefly too and reported under
-`other_workloads` (each with step time, main-kernel time, roofline fraction, fallback counts and a result check).
+Prints ONE JSON line on rank 0 with the headline figure and a `roofline` object taken from the timed steps.
+
+A plain run does only what that line's headline figure needs: it generates and uploads the inputs, runs the warm-up and timed
+steps, writes `--dump-outputs` and prints the line.  `--full` adds, after the timed region, everything else the benchmark measures
+or checks: the oracle sample check (`check`, `recall_at_k`), the CPU baseline (`cpu_baseline`), the PCIe-inclusive rate of the
+drop-in API (`host_api`) and, at N = 1, the other BASELINE configurations and data kinds, each run briefly and reported under
+`other_workloads` (step time, main-kernel time, roofline fraction, fallback counts and a result check) and `summary`, plus the
+float64 order and cosine float32 probes.  `--no-check`, `--no-cpu-baseline` and `--no-others` leave parts of a `--full` run out.
 """
 import argparse
 import json
@@ -672,8 +678,8 @@ def run_openea(args):
 def job_cpu_baseline(args, comm, eng, s, source_dev, source_h, target_h):
     """`cpu_baseline` of the line at ANY world size: rank 0 times the reference's CPU path on a bounded sample of the WHOLE
     job's workload after the timed region.  A collective when the workload has a reverse pass on more than one rank (its index is the
-    whole source: the shards are gathered to rank 0's host); returns the record on rank 0, None elsewhere."""
-    if args.no_cpu_baseline:
+    whole source: the shards are gathered to rank 0's host); returns the record on rank 0, None elsewhere.  `--full` runs only."""
+    if not args.full or args.no_cpu_baseline:
         return None
     n_s, n_t, d, metric, K, k, hub, hub_kw, _ = WORKLOADS[s["name"]]
     held = source_h
@@ -698,10 +704,13 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="weak: every rank owns the workload's source rows (default); strong: the workload's source rows are split "
                          "over the ranks (default workload: BASELINE.json configuration 4 at its stated size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline figure does not need: the oracle sample check, the CPU "
+                         "baseline, the drop-in API rate and, at N = 1, the other workloads and the probes (off: a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--detail", default="bench_detail.json", help="file name of the full record (written next to bench.py and into gpurun_out/; an absolute path: only there)")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle sample check")
-    ap.add_argument("--no-others", action="store_true", help="do not run the other BASELINE configurations after the main workload")
+    ap.add_argument("--no-check", action="store_true", help="skip the oracle sample check (of --full and of --openea)")
+    ap.add_argument("--no-others", action="store_true", help="--full without the other BASELINE configurations after the main workload")
     ap.add_argument("--opt", action="append", default=[], help="context option name=value (tuning experiments)")
     ap.add_argument("--other-steps", type=int, default=10, help="timed steps of each secondary workload (other_workloads)")
     ap.add_argument("--other-warmup", type=int, default=2)
@@ -762,6 +771,7 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
     import torch.distributed as dist
+    check = args.full and not args.no_check
     if args.launch_check:
         # launch-path check on the CPU test engine (no GPU in this process): gloo, tiny shape, no measurement
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -776,7 +786,7 @@ def main():
         WORKLOADS["launch-check"] = (2000 if args.scaling == "weak" else 4001, 1500, 16, "euclidean", 5, 5, "CSLS", {},
                                      "launch check (CPU test engine over gloo; NOT a measurement)")
         s, (src_h, tgt_h), res, src_dev = run_workload("launch-check", eng, comm, dist, rank, world, args.steps, args.warmup,
-                                                       check=not args.no_check, scaling=args.scaling, target_upload=args.target_upload)
+                                                       check=check, scaling=args.scaling, target_upload=args.target_upload)
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, res, comm, s["shard_rows"])
         cpu = job_cpu_baseline(args, comm, eng, s, src_dev, src_h, tgt_h)
@@ -825,7 +835,7 @@ def main():
         eng.ctx.set_option(name, float(val))
 
     main_s, (source_h, target_h), main_res, source_dev = run_workload(args.workload, eng, comm, dist, rank, world, args.steps, args.warmup,
-                                                                      check=not args.no_check, scaling=args.scaling,
+                                                                      check=check, scaling=args.scaling,
                                                                       target_upload=args.target_upload)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, main_res, comm, main_s["shard_rows"])      # (collective: every rank calls it)
@@ -891,7 +901,7 @@ def main():
         }
         if s["check"] is not None:
             line["check"] = s["check"]
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         # PCIe-inclusive rate of the drop-in API (numpy in -> numpy out); reported beside `value`, never as `value`
         import warnings
         from kiez_amd import Kiez
@@ -909,7 +919,7 @@ def main():
     if rank == 0 and cpu is not None:
         line["cpu_baseline"] = cpu
     del source_h, target_h
-    if world == 1 and not args.no_others:
+    if args.full and world == 1 and not args.no_others:
         others = {}
         # c4 = configuration 4 at its stated size on this one GPU (the N = 1 anchor of `--scaling strong`; ~1.3 s per step: fewer
         # steps); c1g / hard = the same kernels on gaussian and on clustered data (how often the tier chain runs is data dependent)
@@ -921,7 +931,7 @@ def main():
                 #  only turns this one's first releases into hipFree calls)
                 eng.ctx.trim()
                 o_steps, o_warm = (min(args.other_steps, 3), min(args.other_warmup, 1)) if name == "c4" else (args.other_steps, args.other_warmup)
-                osum, _, _, _ = run_workload(name, eng, comm, dist, rank, world, o_steps, o_warm, check=not args.no_check)
+                osum, _, _, _ = run_workload(name, eng, comm, dist, rank, world, o_steps, o_warm, check=check)
                 others[name] = short(osum)
             except Exception as e:  # pragma: no cover  (a secondary workload must never cost the main line)
                 others[name] = {"error": f"{type(e).__name__}: {e}"}

@@ -30,7 +30,7 @@ def _lines(r, detail):
 
 @pytest.mark.parametrize("gpus,scaling", [(2, "weak"), (3, "strong")])
 def test_bench_launches_its_own_ranks(gpus, scaling, tmp_path):
-    r = _run("--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--scaling", scaling, "--launch-check", "--detail", str(tmp_path / "d.json"))
+    r = _run("--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--scaling", scaling, "--launch-check", "--full", "--detail", str(tmp_path / "d.json"))
     assert r.returncode == 0, r.stderr[-4000:]
     line, full = _lines(r, tmp_path / "d.json")
     assert line["n_gpus"] == gpus and line["scaling"] == scaling and line["steps"] == 1 and line["warmup"] == 1
@@ -44,8 +44,8 @@ def test_bench_launches_its_own_ranks(gpus, scaling, tmp_path):
     traffic = full["collective_traffic_per_step"]
     assert traffic["broadcast"]["calls"] == 1 and traffic["all_to_all"]["calls"] == 1 and traffic["all_gather"]["calls"] == 1
     assert set(line["collective_ms_per_step"]) == {"broadcast", "broadcast_exposed", "all_to_all", "all_gather"}
-    # the line of an N > 1 run carries the evidence a measurement needs: an oracle check that covers the fit state and rows of
-    # EVERY rank's shard, recall@k, and the CPU baseline of the whole job (rank 0, after the timed region)
+    # the line of an N > 1 `--full` run carries the evidence a measurement needs: an oracle check that covers the fit state and
+    # rows of EVERY rank's shard, recall@k, and the CPU baseline of the whole job (rank 0, after the timed region)
     assert line["check"]["index_rows_identical"] == line["check"]["rows"] and line["check"]["ranks"] == gpus
     chk = full["check"]
     assert chk["ranks"] == gpus and len(chk["index_rows_identical_per_rank"]) == gpus
@@ -57,9 +57,24 @@ def test_bench_launches_its_own_ranks(gpus, scaling, tmp_path):
     assert full["cpu_baseline"]["workload_rows"]["n_source_total"] == cfg["n_source_total"]
 
 
+def test_a_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    """Without `--full` the ranks run the warm-up and timed steps, dump and report: no oracle check, no CPU baseline."""
+    r = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--launch-check", "--detail", str(tmp_path / "d.json"),
+             "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-4000:]
+    line, full = _lines(r, tmp_path / "d.json")
+    assert line["n_gpus"] == 2 and line["steps"] == 2 and line["warmup"] == 1 and line["value"] is None and line["ms_per_step"] > 0
+    traffic = full["collective_traffic_per_step"]
+    assert traffic["broadcast"]["calls"] == 1 and traffic["all_to_all"]["calls"] == 1 and traffic["all_gather"]["calls"] == 1
+    for key in ("check", "cpu_baseline", "host_api", "other_workloads", "summary"):
+        assert key not in full and key not in line, key
+    assert line["recall_at_k"] is None
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["dist.npy", "ind.npy", "rows.npy"]
+
+
 def test_every_rank_can_upload_the_target_itself(tmp_path):
     """`--target-upload local`: ShardedKiez.fit(target_from_rank0=False) -- no broadcast in the step, same results."""
-    r = _run("--gpus", "2", "--steps", "1", "--warmup", "0", "--launch-check", "--target-upload", "local", "--detail", str(tmp_path / "d.json"))
+    r = _run("--gpus", "2", "--steps", "1", "--warmup", "0", "--launch-check", "--full", "--target-upload", "local", "--detail", str(tmp_path / "d.json"))
     assert r.returncode == 0, r.stderr[-4000:]
     line, full = _lines(r, tmp_path / "d.json")
     assert line["config"]["target_upload"] == "local"
@@ -69,7 +84,7 @@ def test_every_rank_can_upload_the_target_itself(tmp_path):
 
 def test_target_broadcast_once_then_cached(tmp_path):
     """`--target-upload cached`: the broadcast runs in the first fit only (1 warm-up + 2 timed steps: none inside the timed region)."""
-    r = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--launch-check", "--target-upload", "cached", "--detail", str(tmp_path / "d.json"))
+    r = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--launch-check", "--full", "--target-upload", "cached", "--detail", str(tmp_path / "d.json"))
     assert r.returncode == 0, r.stderr[-4000:]
     line, full = _lines(r, tmp_path / "d.json")
     assert line["config"]["target_upload"] == "cached" and "broadcast" not in full["collective_traffic_per_step"]

@@ -82,7 +82,7 @@ def test_sharded_kiez_hip_engine_over_rccl_single_rank():
 
 
 def test_bench_line_of_a_launched_run_carries_check_and_cpu_baseline(tmp_path):
-    """`bench.py` as torch.distributed.run starts it (RANK / WORLD_SIZE / MASTER_* in the environment, RCCL process group), one
+    """`bench.py --full` as torch.distributed.run starts it (RANK / WORLD_SIZE / MASTER_* in the environment, RCCL process group), one
     rank, every collective forced: the line of a launched run -- the code path of `--gpus 8` -- carries the oracle check
     (fit state + rows of every rank's shard), recall@k and the CPU baseline, for both ways of getting the target onto the ranks."""
     import json
@@ -91,7 +91,7 @@ def test_bench_line_of_a_launched_run_carries_check_and_cpu_baseline(tmp_path):
         env = {**os.environ, "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": port,
                "KIEZ_AMD_FORCE_COLLECTIVES": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
         r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "2", "--warmup", "1",
-                            "--no-others", "--target-upload", upload, "--detail", str(tmp_path / "detail.json")],
+                            "--full", "--no-others", "--target-upload", upload, "--detail", str(tmp_path / "detail.json")],
                            capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
         assert r.returncode == 0, r.stderr[-6000:]
         short = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1]

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export O=gpurun_out/all; mkdir -p $O
 timeout 2400 python3 -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; tail -5 $O/pytest.log
-timeout 900 python3 bench.py --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err; python3 tools/show.py $O/bench.json | cut -c1-200
+timeout 900 python3 bench.py --full --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err; python3 tools/show.py $O/bench.json | cut -c1-200
 python3 - <<'PY'
 import json,sys,os
 j=json.load(open(os.environ["O"]+"/bench.json"))
