@@ -99,15 +99,23 @@ struct kz_ctx {
 // of the pair) and scaled by ONE power of two S into the fp16 range.  Reference counted: images keep it alive.
 // Slices (16 features) of the fp16 image of a matrix with kg k-groups: d_pad / 16 -- rounded up to a multiple of 8 beyond 32
 // slices (the wide-row builds of the fp16 kernel, kz_knn_h_inst.h, exist for 32, 40, 48, 56 and 64 slices only; the padding
-// slices are zero, and zero products add exactly nothing to the float32 accumulators).
+// slices are zero, and zero products add exactly nothing to the float32 accumulators) and to a multiple of 16 beyond 64 (the
+// parity-split builds, kz_knn_hx16.h: 80, 96, 112 and 128 slices -- each wave pair splits them into two of the counts above).
 __host__ __device__ __forceinline__ int kz_h_nsr(int kg) {
     const int s = kg / 4;
-    return s <= 32 ? s : (s + 7) & ~7;
+    return s <= 32 ? s : (s <= 64 ? (s + 7) & ~7 : (s + 15) & ~15);
 }
-// The fp16 tier exists for 2 .. 24 slices (d <= 384) and 32 .. 64 slices (d = 497 .. 1024); 25 .. 31 run on float32 operands.
+// The fp16 tier exists for 2 .. 24 slices (d <= 384) and 32 .. 128 slices (d = 497 .. 2048: the wide-row builds up to 64 slices,
+// the parity-split builds beyond); 25 .. 31 slices and more than 128 run on float32 operands.
 __host__ __device__ __forceinline__ bool kz_h_slices_ok(int kg) {
     const int s = kg / 4;
-    return (s >= 2 && s <= 24) || (s >= 32 && s <= 64);
+    return (s >= 2 && s <= 24) || (s >= 32 && s <= 128);
+}
+// Work items the planner may put into one round of an fp16 launch: the resident workgroups -- half of them where two workgroups
+// sweep one item (n_slices = kz_h_nsr(kg) > 64: the parity-split builds own 64 queries each).
+__host__ __forceinline__ int kz_h_slots(int n_slices, int blocks_per_cu, int n_cus) {
+    const int resident = blocks_per_cu * n_cus;
+    return n_slices > 64 ? (resident + 1) / 2 : resident;
 }
 
 struct kz_center {

@@ -2540,7 +2540,8 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
 
     const int metric = index->metric;
     const int n_ytiles = (dual && dual->n_ytiles > 0) ? dual->n_ytiles : (int)index->n_tiles;
-    // (slices of the fp16 image: kz_h_nsr pads 32 .. 64 to a multiple of 8 -- the other tiers never read n_slices beyond 24)
+    // (slices of the fp16 image: kz_h_nsr pads 32 .. 64 to a multiple of 8 and 65 .. 128 to a multiple of 16 -- the other tiers never
+    //  read n_slices beyond 24)
     const int n_slices = kz_h_nsr(index->kg);
     // rounding bound factors.  float32 operands: (d_pad + 16) 2^-24 covers the d+1 step fma chain, the float32 rounding of
     // the bias and (float64 inputs) of the operands; 1e-12 covers the float64 re-rank's own rounding.  fp16 operands: the
@@ -2553,7 +2554,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     // ---- tier of this call ------------------------------------------------------------------------------------------
     const int precision = rs.prec >= 0 ? rs.prec : ctx->precision;
     int tier = KZ_TIER_F32;
-    // (d = 497 .. 1024, 32 .. 64 slices: the fp16 tier's wide-row builds -- and no split-bf16 tier: precision = 2 runs on float32
+    // (d = 497 .. 2048, 32 .. 128 slices: the fp16 tier's wide-row and parity-split builds -- and no split-bf16 tier: precision = 2 runs on float32
     //  operands there, and so does every row the fp16 pass leaves that would have gone to the split-bf16 operands: esc_bf)
     const bool bf_ok = n_slices >= 2 && n_slices <= 24 && query->kg == index->kg;
     const bool esc_bf = ctx->esc_bf && bf_ok;
@@ -2735,7 +2736,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             else
                 KZ_DISPATCH_CAND(rc0, kz_cand_occupancy, (&blocks_per_cu));
             if (rc0 != KZ_OK) return rc0;
-            slots_cache[t] = blocks_per_cu * ctx->n_cus;
+            slots_cache[t] = t == KZ_TIER_H ? kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus) : blocks_per_cu * ctx->n_cus;
         }
         *out = slots_cache[t];
         return KZ_OK;

@@ -656,7 +656,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     // distances) far fewer rows are searched again (400k x 400k, k = 50, 40 clusters: 42.7k -> 0 rows, call 162 -> 134 ms; uniform 500k x 500k: +0.9 ms; k = 10: 12.4k -> 0 rows, 104 -> 97 ms, and ns 105.9 -> 104.4 ms per step:
     // its ~25 uncertified reverse rows per step are gone)
     const int KPr = ctx->dual_rev_long ? (2 * KP < 128 ? 2 * KP : 128) : KP;
-    const int n_slices = kz_h_nsr(b->kg);   // (slices of the fp16 images: 32 .. 64 padded to a multiple of 8)
+    const int n_slices = kz_h_nsr(b->kg);   // (slices of the fp16 images: 32 .. 64 padded to a multiple of 8, 65 .. 128 to a multiple of 16)
     // every stride-th tile of A is in the sample.  Automatic (dual_stride = 1): the sample sweep costs T / stride, the events
     // (log, scatter, select, slower sweep) ~0.10 ns each with |B| k stride of them: stride = sqrt(T / (|B| k 0.07 ns)), T ~ 2 |A| |B| d / 1e15 s
     // (ns: 20, measured flat between 16 and 28; 500k x 500k, k = 50: 6)
@@ -1023,7 +1023,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
             KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu, &tpw, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
             if (rc != KZ_OK) return rc;
             KzPass ps;
-            rc = kz_prepare_pass(ctx, (int)s_tiles, (int)s3_tiles, blocks_per_cu * ctx->n_cus, 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s3);
+            rc = kz_prepare_pass(ctx, (int)s_tiles, (int)s3_tiles, kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus), 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s3);
             if (rc == KZ_OK) {
                 KnnCandParams cp;
                 memset(&cp, 0, sizeof(cp));
@@ -1151,7 +1151,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu, &tpw, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
         if (rc != KZ_OK) return rc;
         KzPass ps;
-        rc = kz_prepare_pass(ctx, (int)b_tiles, (int)s_tiles, blocks_per_cu * ctx->n_cus, 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s);
+        rc = kz_prepare_pass(ctx, (int)b_tiles, (int)s_tiles, kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus), 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s);
         if (rc != KZ_OK) return rc;
         KnnCandParams cp;
         memset(&cp, 0, sizeof(cp));

@@ -14,7 +14,8 @@
 // 128 rows x 16 B, copied linearly because the image already is the conflict-free ds_read_b128 layout) through a ring of
 // R = 2 P slots with one workgroup barrier per P slices; fragments of slice g+1 are read under the MFMAs of slice g.
 // Candidate selection: kz_knn_epi3.h.  Three workgroups per CU (168 VGPRs) up to d = 128, two beyond, ONE at 32 .. 64 slices
-// (WPS = 1, d = 497 .. 1024: the query tile in the unified VGPR + AGPR file, kz_knn_h_inst.h "WIDE ROWS").
+// (WPS = 1, d = 497 .. 1024: the query tile in the unified VGPR + AGPR file, kz_knn_h_inst.h "WIDE ROWS").  65 .. 128 slices
+// (d = 1025 .. 2048) run on kz_knn_cand_hx_kernel (kz_knn_hx16.h): this kernel with the slices split between wave pairs.
 #pragma once
 #include <type_traits>
 

@@ -165,14 +165,30 @@ int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_
 int KZ_HW_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
 int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
 
+// (65 .. 128 slices, d = 1025 .. 2048: the parity-split builds, kz_knn_hx_inst.h -- units of their own as well; two workgroups per
+//  work item, one query tile per item)
+#ifdef KZ_H_DUAL
+#define KZ_HX_FWD(base) KZ_H_CAT(kz_hxd_##base##_kp, KZ_H_KP)
+#else
+#define KZ_HX_FWD(base) KZ_H_CAT(kz_hx_##base##_kp, KZ_H_KP)
+#endif
+int KZ_HX_FWD(occupancy)(int n_slices, int* blocks_per_cu, int lds_pad);
+int KZ_HX_FWD(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_items);
+
 int KZ_H_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad) {
+    if (n_slices > 64) {
+        *tpw = 1;
+        return KZ_HX_FWD(occupancy)(n_slices, blocks_per_cu, lds_pad);
+    }
     if (n_slices > 24) return KZ_HW_NAME(occupancy)(n_slices, blocks_per_cu, tpw, wps, wide, lds_pad);
     int rc;
     KZ_DISPATCH_H_NSR(rc, kz_h_occupancy, (blocks_per_cu, tpw, wps, wide, lds_pad), KZ_H_KP);
     return rc;
 }
 
+// n_blocks = work items of the plan: one workgroup each, two beyond 64 slices (kz_launch_hx starts 2 n_blocks workgroups)
 int KZ_H_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide) {
+    if (n_slices > 64) return KZ_HX_FWD(launch)(n_slices, ctx, p, n_blocks);
     if (n_slices > 24) return KZ_HW_NAME(launch)(n_slices, ctx, p, n_blocks, wps, wide);
     int rc;
     KZ_DISPATCH_H_NSR(rc, kz_launch_h, (ctx, p, n_blocks, wps, wide), KZ_H_KP);

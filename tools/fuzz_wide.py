@@ -1,6 +1,7 @@
-"""GPU box: randomised shapes at 32 .. 64 slices (d = 497 .. 1024) -- the fp16 kernel's wide-row builds.  Per case: the shared
-sweep (kz_knn_dual, forced) against two kz_knn calls, bit for bit, and a row sample of both directions against the oracle.
-   python3 tools/fuzz_wide.py [n_cases] [seed] [max_rows]
+"""GPU box: randomised shapes at 32 .. 64 slices (d = 497 .. 1024) -- the fp16 kernel's wide-row builds -- or, with a width range,
+at 65 .. 128 slices (d = 1025 .. 2048: the parity-split builds).  Per case: the shared sweep (kz_knn_dual, forced) against two
+kz_knn calls, bit for bit, and a row sample of both directions against the oracle.
+   python3 tools/fuzz_wide.py [n_cases] [seed] [max_rows] [d_lo d_hi [k_max]]
 A case is bad when the bits differ, the oracle disagrees or the first pass was not the fp16 one.  The shared sweep may still
 decline a forced case for reasons other than the width (too few sample rows for lists of 128: k > 54 on small inputs); those
 cases compare two pairs of ordinary searches, and the count of cases that did share the sweep is printed.
@@ -14,11 +15,14 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
-def _case(rng, max_rows):
+def _case(rng, max_rows, d_lo=497, d_hi=1024, k_max=64, d_force=None):
+    """(the draws are the same whatever the width range: d_force swaps the width of a case and keeps its rows, k and metric)"""
     na = int(rng.integers(1100, max_rows + 1))
     nb = int(rng.integers(1100, max_rows + 1))
-    d = int(rng.integers(497, 1025))
-    k = int(rng.choice([1, 2, 5, 10, 13, 27, 50, 64]))
+    d = int(rng.integers(d_lo, d_hi + 1))
+    if d_force:
+        d = d_force
+    k = int(rng.choice([k for k in (1, 2, 5, 10, 13, 27, 50, 64) if k <= k_max]))
     metric = str(rng.choice(["euclidean", "sqeuclidean", "cosine"]))
     dtype = np.float32 if rng.random() < 0.7 else np.float64
     kind = str(rng.choice(["uniform", "normal", "clustered", "dups"]))
@@ -47,7 +51,7 @@ def _oracle_rows_ok(q, y, dd, ii, k, metric, rows):
     return bool(np.allclose(dd[rows], od, rtol=1e-12, atol=0))
 
 
-def run(seed=1, n_cases=20, max_rows=6000, verbose=False):
+def run(seed=1, n_cases=20, max_rows=6000, verbose=False, d_lo=497, d_hi=1024, k_max=64, d_force=None):
     """Returns (the list of bad cases -- empty: all good --, the number of cases that ran the shared sweep)."""
     from kiez_amd import _native as N
     ctx = N.Context.get()
@@ -55,7 +59,7 @@ def run(seed=1, n_cases=20, max_rows=6000, verbose=False):
     bad = []
     n_dual = 0
     for case in range(n_cases):
-        a, b, d, k, metric, kind = _case(rng, max_rows)
+        a, b, d, k, metric, kind = _case(rng, max_rows, d_lo, d_hi, k_max, d_force)
         am, bm = N.DeviceMatrix(ctx, a, metric), N.DeviceMatrix(ctx, b, metric)
         try:
             ctx.set_option("dual_force", 0)
@@ -86,6 +90,8 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     max_rows = int(sys.argv[3]) if len(sys.argv) > 3 else 6000
-    bad, n_dual = run(seed, n, max_rows, verbose=True)
+    d_lo, d_hi = (int(sys.argv[4]), int(sys.argv[5])) if len(sys.argv) > 5 else (497, 1024)
+    k_max = int(sys.argv[6]) if len(sys.argv) > 6 else 64
+    bad, n_dual = run(seed, n, max_rows, verbose=True, d_lo=d_lo, d_hi=d_hi, k_max=k_max)
     print(f"fuzz_wide: {n} cases, {n_dual} through the shared sweep, {len(bad)} bad")
     sys.exit(1 if bad else 0)

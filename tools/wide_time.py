@@ -1,5 +1,6 @@
-"""GPU box: wide rows (d = 512 .. 1024) on the fp16 first pass against float32 operands, same process, alternated.
-   python3 tools/wide_time.py [--reps R] [--big]
+"""GPU box: wide rows (d = 512 .. 1024; --widths 1024,1536,2048 for the parity-split builds) on the fp16 first pass against
+float32 operands, same process, alternated.
+   python3 tools/wide_time.py [--reps R] [--widths D,D,...] [--data uniform|gmm] [--big | --only-big] [--big-d D]
 Per shape and precision (0 = fp16 pass, 1 = float32 operands): the step time (median of R), the main kernel's time
 (main_kernel_ms, summed over both directions of a fit), its fraction of the dense fp16 peak (2 n_q n_i d / time / 2.5 PF) and
 n_first_pass_fail; every step's result is checked against the oracle on a seeded row sample, and the two precisions against each
@@ -18,8 +19,19 @@ sys.path.insert(0, str(ROOT))
 PEAK_FP16 = 2.5e15
 
 
+DATA = "uniform"
+
+
 def _data(n, d, seed):
-    return np.random.default_rng(seed).random((n, d), dtype=np.float32)
+    rng = np.random.default_rng(seed)
+    if DATA == "uniform":
+        return rng.random((n, d), dtype=np.float32)
+    # L2-normalised mixture of 64 clusters (the `_gmm` rows of tests/test_gpu_wide_dims.py)
+    centres = np.random.default_rng(6).standard_normal((64, d), dtype=np.float32)
+    x = centres[rng.integers(0, 64, n)]
+    x += np.float32(0.35) * rng.standard_normal((n, d), dtype=np.float32)
+    x /= np.sqrt((x * x).sum(axis=1, keepdims=True))
+    return x
 
 
 def _oracle_check(q, y, ind, k, rows):
@@ -77,7 +89,7 @@ def csls(ctx, n_s, n_t, d, reps, k=10):
 
 
 def _report(kind, n_q, n_i, d, k, res, same, oracle_ok, directions):
-    line = {"kind": kind, "n_q": n_q, "n_i": n_i, "d": d, "k": k, "same_bits": same, "oracle_sample_ok": oracle_ok}
+    line = {"kind": kind, "data": DATA, "n_q": n_q, "n_i": n_i, "d": d, "k": k, "same_bits": same, "oracle_sample_ok": oracle_ok}
     for prec, name in ((0, "fp16"), (1, "f32")):
         runs = res[prec][1:]
         # (the shared sweep computes each distance once for both directions)
@@ -86,7 +98,9 @@ def _report(kind, n_q, n_i, d, k, res, same, oracle_ok, directions):
         main = float(np.median([r[1].get("main_kernel_ms", 0.0) for r in runs]))
         line[name] = {"step_ms": round(step, 2), "main_kernel_ms": round(main, 2),
                       "fp16_peak_fraction": round(flops / (main * 1e-3) / PEAK_FP16, 3) if main > 0 else None,
-                      "n_first_pass_fail": int(runs[-1][1].get("n_first_pass_fail", 0)), "first_pass": int(runs[-1][1].get("first_pass", -1)),
+                      "n_first_pass_fail": int(runs[-1][1].get("n_first_pass_fail", 0)),
+                      "n_escalated_rows": int(runs[-1][1].get("n_escalated_rows", 0)),
+                      "n_fallback_rows": int(runs[-1][1].get("n_fallback_rows", 0)), "first_pass": int(runs[-1][1].get("first_pass", -1)),
                       "dual": int(runs[-1][1].get("dual", 0))}
     line["speedup_step"] = round(line["f32"]["step_ms"] / line["fp16"]["step_ms"], 2)
     print(json.dumps(line), flush=True)
@@ -96,19 +110,25 @@ def _report(kind, n_q, n_i, d, k, res, same, oracle_ok, directions):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--big", action="store_true", help="also 250k x 1M x 768 CSLS")
+    ap.add_argument("--widths", default="512,768,1024", help="feature counts of the 100k x 100k shapes")
+    ap.add_argument("--data", default="uniform", choices=["uniform", "gmm"])
+    ap.add_argument("--big", action="store_true", help="also 250k x 1M CSLS at --big-d")
     ap.add_argument("--only-big", action="store_true")
+    ap.add_argument("--big-d", type=int, default=768)
     args = ap.parse_args()
+    global DATA
+    DATA = args.data
+    widths = [int(w) for w in args.widths.split(",")]
     warnings.simplefilter("ignore")
     from kiez_amd import _native as N
     ctx = N.Context.get()
     if not args.only_big:
-        for d in (512, 768, 1024):
+        for d in widths:
             ordinary(ctx, 100_000, 100_000, d, args.reps)
-        for d in (512, 768, 1024):
+        for d in widths:
             csls(ctx, 100_000, 100_000, d, args.reps)
     if args.big or args.only_big:
-        csls(ctx, 250_000, 1_000_000, 768, 1)
+        csls(ctx, 250_000, 1_000_000, args.big_d, 1)
 
 
 if __name__ == "__main__":
