@@ -123,7 +123,9 @@ int kz_memcpy_d2d(kz_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);
  * (read in place; the caller keeps the buffer alive and unchanged until kz_matrix_destroy), 3 device memory borrowed as a ROW
  * SOURCE only (no norms, no operand images: accepted by kz_dsl_fit as `source`, refused by every search entry point).  Computes the float64 row
  * norms; the MFMA operand images (fp16 / split-bf16 / float32 tiles) are built by the first kz_knn that needs them.
- * NaN/inf input is an error (KZ_ERR_NONFINITE; scikit-learn rejects those inputs too): reported here for host rows, by
+ * NaN/inf input is an error (KZ_ERR_NONFINITE; scikit-learn rejects those inputs too), and so is a row whose squared norm
+ * |x|^2 exceeds 1e30 (|x| <= 1e15: the input limit of the float32 operand images and of the rounding bounds built on the row
+ * norms; scikit-learn accepts such rows -- same error code, the message names the limit): reported here for host rows, by
  * the first kz_knn / kz_knn_dual that searches the matrix for device rows (this call then waits for nothing). */
 int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t n, int64_t d, int dtype,
                      int metric, kz_matrix** out);

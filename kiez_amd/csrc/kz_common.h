@@ -225,6 +225,9 @@ using KzMatrixPtr = std::unique_ptr<kz_matrix, KzMatrixDestroy>;
         }                              \
     } while (0)
 
+// what kz_norms_kernel's flag means (KZ_ERR_NONFINITE): a NaN, an infinity, or a row whose squared norm exceeds the input limit
+#define KZ_MSG_NONFINITE "kz_matrix_create: input contains NaN, infinity or a row with |x|^2 > 1e30 (the input limit: squared row norms up to 1e30)"
+
 int kz_scratch(kz_ctx* ctx, size_t bytes, void** out);
 int kz_floor_buf(kz_ctx* ctx, size_t bytes, float** out);
 

@@ -3032,7 +3032,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         for (int u = 0; u < 2; ++u) {
             if (!unchecked[u]) continue;
             if (ctx->h_counters[44 + 10 * u + 8] != 0) {
-                kz_set_error("kz_matrix_create: input contains NaN, infinity or a value too large for float32");
+                kz_set_error(KZ_MSG_NONFINITE);
                 return KZ_ERR_NONFINITE;
             }
             memcpy(&unchecked[u]->max_norm, ctx->h_counters + 44 + 10 * u, 8);

@@ -684,7 +684,7 @@ int kz_matrix_check(kz_matrix* m) {
     KZ_HIP(hipMemcpyAsync(ctx->h_counters, m->d_stats, 40, hipMemcpyDeviceToHost, ctx->stream));
     KZ_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->h_counters[8] != 0) {
-        kz_set_error("kz_matrix_create: input contains NaN, infinity or a value too large for float32");
+        kz_set_error(KZ_MSG_NONFINITE);
         return KZ_ERR_NONFINITE;
     }
     memcpy(&m->max_norm, ctx->h_counters, 8);
