@@ -46,9 +46,14 @@ enum { KZ_F32 = 0, KZ_F64 = 1 };
  * 6 .. 9 take the same VALU route with scikit-learn's expressions of the other per-feature metrics: braycurtis and seuclidean
  * (DistanceMetric: the difference in the input dtype, float64 sums in feature order, ranking value rounded to the input dtype;
  * seuclidean needs kz_matrix_set_seuclidean_v and returns sqrt of its ranking value), correlation and hamming (scipy's cdist:
- * float64 throughout; correlation = 1 - centred cosine, NaN for a constant row, ranked after every finite value). */
+ * float64 throughout; correlation = 1 - centred cosine, NaN for a constant row, ranked after every finite value).
+ * 10 .. 16 are scipy's boolean metrics (scikit-learn casts the rows to bool, x != 0, and calls cdist): the matrix keeps a
+ * bit-packed image of the rows, a popcount kernel counts popcount(x & y) per pair and one float64 division gives scipy's value;
+ * dice and sokalsneath are NaN between two all-false rows, ranked after every finite value and returned as NaN. */
 enum { KZ_EUCLIDEAN = 0, KZ_SQEUCLIDEAN = 1, KZ_COSINE = 2, KZ_MANHATTAN = 3, KZ_CHEBYSHEV = 4, KZ_MINKOWSKI = 5,
-       KZ_BRAYCURTIS = 6, KZ_SEUCLIDEAN = 7, KZ_CORRELATION = 8, KZ_HAMMING = 9 };
+       KZ_BRAYCURTIS = 6, KZ_SEUCLIDEAN = 7, KZ_CORRELATION = 8, KZ_HAMMING = 9,
+       KZ_JACCARD = 10, KZ_DICE = 11, KZ_ROGERSTANIMOTO = 12, KZ_RUSSELLRAO = 13, KZ_SOKALMICHENER = 14, KZ_SOKALSNEATH = 15,
+       KZ_YULE = 16 };
 
 typedef struct kz_ctx kz_ctx;       /* one GPU + one HIP stream + scratch                                   */
 typedef struct kz_matrix kz_matrix; /* an embedding matrix resident in HBM: raw rows, MFMA-packed tiles, norms */

@@ -26,9 +26,14 @@ _lock = threading.Lock()
 KZ_F32, KZ_F64 = 0, 1
 KZ_EUCLIDEAN, KZ_SQEUCLIDEAN, KZ_COSINE, KZ_MANHATTAN, KZ_CHEBYSHEV, KZ_MINKOWSKI = 0, 1, 2, 3, 4, 5
 KZ_BRAYCURTIS, KZ_SEUCLIDEAN, KZ_CORRELATION, KZ_HAMMING = 6, 7, 8, 9
+KZ_JACCARD, KZ_DICE, KZ_ROGERSTANIMOTO, KZ_RUSSELLRAO, KZ_SOKALMICHENER, KZ_SOKALSNEATH, KZ_YULE = 10, 11, 12, 13, 14, 15, 16
+# scipy's boolean metrics: searched on a bit-packed image of the rows (x != 0), kz_bool.hip
+BOOLEAN_METRICS = ("jaccard", "dice", "rogerstanimoto", "russellrao", "sokalmichener", "sokalsneath", "yule")
 METRIC_IDS = {"euclidean": KZ_EUCLIDEAN, "sqeuclidean": KZ_SQEUCLIDEAN, "cosine": KZ_COSINE, "manhattan": KZ_MANHATTAN,
               "chebyshev": KZ_CHEBYSHEV, "minkowski": KZ_MINKOWSKI, "braycurtis": KZ_BRAYCURTIS, "seuclidean": KZ_SEUCLIDEAN,
-              "correlation": KZ_CORRELATION, "hamming": KZ_HAMMING}
+              "correlation": KZ_CORRELATION, "hamming": KZ_HAMMING, "jaccard": KZ_JACCARD, "dice": KZ_DICE,
+              "rogerstanimoto": KZ_ROGERSTANIMOTO, "russellrao": KZ_RUSSELLRAO, "sokalmichener": KZ_SOKALMICHENER,
+              "sokalsneath": KZ_SOKALSNEATH, "yule": KZ_YULE}
 
 
 def split_metric(metric: str):

@@ -167,8 +167,12 @@ struct kz_matrix {
     double* seu_v;    // KZ_SEUCLIDEAN: device [d] per-feature variances (kz_matrix_set_seuclidean_v; NULL until set)
     double* seu_v_host;  // ... and their host copy (the bit-identical check between the two matrices of a search)
     double* corr;     // KZ_CORRELATION: device [n][2] float64 row mean and norm of the centred row (kz_pack.hip: kz_corr_rows_kernel)
+    uint32_t* bits;   // the boolean metrics (KZ_JACCARD .. KZ_YULE): device [n][bits_words] uint32, bit j of word w = x[32 w + j] != 0, rows
+                      // zero-padded to a multiple of four words (kz_bool.hip: kz_bool_pack_kernel)
+    int32_t* bits_cnt;   // ... and device [n] int32: the row's number of true features
+    int bits_words;      // ... words per image row (a multiple of 4)
     int64_t n_tiles;  // ceil(n / 128)
-    int kg;           // d_pad / 4 (number of 4-wide k-groups), d_pad = round_up(d, 16)
+    int kg;       // d_pad / 4 (number of 4-wide k-groups), d_pad = round_up(d, 16)
     int kg_bf;        // same for the split-bf16 image (currently equal to kg)
     void* raw;        // [n, d] dtype, row-major (exact data, used by the float64 re-rank)
     bool raw_borrowed;  // raw is the caller's buffer (kz_matrix_create rows_on_device = 2 / 3), not ours to free

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "kz_common.h"
+#include "kz_bool.h"
 #include "kz_floor.h"
 
 #include "kz_knn_device.h"
@@ -258,7 +259,7 @@ __device__ __forceinline__ double kz_output_distance(double v, int metric, doubl
     // (seuclidean: SEuclideanDistance._rdist_to_dist, sqrt of the ranking value -- already rounded to the input dtype -- rounded
     //  again; correlation: the constant row's NaN, ranked as +inf (kz_family_finish), is NaN again)
     if (metric == KZ_SEUCLIDEAN) return sizeof(T) == 4 ? (double)(float)sqrt(v) : sqrt(v);
-    if (metric == KZ_CORRELATION && v == INFINITY) return NAN;
+    if ((metric == KZ_CORRELATION || metric == KZ_DICE || metric == KZ_SOKALSNEATH) && v == INFINITY) return NAN;   // (dice, sokalsneath: kz_bool.h)
     if (metric == KZ_EUCLIDEAN) {
         // ArgKmin32 converts the surrogate with the float32 metric object: (double)sqrtf((float)d2)
         // (_argkmin.pyx.tp:285-295 with INPUT_DTYPE_t = float32); ArgKmin64 uses sqrt in float64.
@@ -3279,7 +3280,9 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                         if (rc != KZ_OK) return rc;
                     }
                     if (lanes) {
-                    } else if (no_gemm_form)
+                    } else if (kz_is_bool_metric(index->metric))
+                        kz_bool_launch_dist(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
+                    else if (no_gemm_form)
                         kz_launch_family_dist<float>(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
                     else if (ctx->exact_rows && kz_launch_exact_rows(ctx, fl.get(), b0, nb, cq_begin, query, index, metric, (double*)vals)) {
                     } else
@@ -3294,7 +3297,9 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                                        two_level ? (int64_t)n_chunks * k_sel : index->n, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p,
                                        fp.out_dist, fp.out_ind);
                 } else {
-                    if (no_gemm_form)
+                    if (kz_is_bool_metric(index->metric))
+                        kz_bool_launch_dist(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
+                    else if (no_gemm_form)
                         kz_launch_family_dist<double>(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
                     else
                         hipLaunchKernelGGL(kz_exact_dist_kernel<double>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl.get(), b0,

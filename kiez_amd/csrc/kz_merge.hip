@@ -9,6 +9,7 @@
 // MutualProximity 'empiric' (mutual_proximity.py:185-212) and DisSimLocal (dis_sim.py:96-107) need the reverse INDICES in
 // exactly the single-GPU order; CSLS / LocalScaling / MP 'normal' only the distances (merged by the distances themselves).
 #include "kz_common.h"
+#include "kz_bool.h"
 
 // one wave per query row; the row's K pairs one after the other through the canonical dot product
 template <typename T>
@@ -111,7 +112,9 @@ int kz_pair_values(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t
     KZ_HIP(hipSetDevice(ctx->device));
     if (q_count == 0) return KZ_OK;
     const dim3 grid((unsigned)((q_count + 3) / 4));
-    if (query->dtype == KZ_F32)
+    if (kz_is_bool_metric(query->metric))
+        kz_bool_launch_pair_values(ctx, query, q_begin, q_count, index, d_ind, k, d_val);
+    else if (query->dtype == KZ_F32)
         hipLaunchKernelGGL(kz_pair_values_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)query->raw, query->sqn, q_begin,
                            q_count, (const float*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val,
                            index->seu_v, query->corr, index->corr);

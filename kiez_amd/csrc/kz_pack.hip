@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "kz_common.h"
+#include "kz_bool.h"
 
 // round-to-nearest-even float32 -> bf16 bits (finite inputs)
 __device__ __forceinline__ unsigned short kz_bf16_rn(float f) {
@@ -703,7 +704,7 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
     KZ_REQUIRE(d <= 65536, "kz_matrix_create: d=%lld too large", (long long)d);
     KZ_REQUIRE(n < ((int64_t)1 << 31) - 256, "kz_matrix_create: n=%lld exceeds the int32 row-id range", (long long)n);
     KZ_REQUIRE(dtype == KZ_F32 || dtype == KZ_F64, "kz_matrix_create: dtype must be KZ_F32 or KZ_F64");
-    KZ_REQUIRE(metric >= KZ_EUCLIDEAN && metric <= KZ_HAMMING, "kz_matrix_create: unknown metric %d", metric);
+    KZ_REQUIRE(metric >= KZ_EUCLIDEAN && metric <= KZ_YULE, "kz_matrix_create: unknown metric %d", metric);
     KZ_REQUIRE(rows_on_device >= 0 && rows_on_device <= 3, "kz_matrix_create: rows_on_device must be 0, 1, 2 or 3");
     KZ_HIP(hipSetDevice(ctx->device));
     kz_matrix* m = new kz_matrix();
@@ -783,6 +784,10 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
             return fail(KZ_ERR_HIP);
         }
     }
+    if (kz_is_bool_metric(metric)) {   // (the boolean metrics search the bit image; the float rows stay: finiteness check, borrowed rows)
+        const int rc = kz_bool_image(m);
+        if (rc != KZ_OK) return fail(rc);
+    }
     // Host rows: the copy above was synchronous anyway, so the finiteness verdict is checked here and the caller gets
     // KZ_ERR_NONFINITE from the call that passed the data (scikit-learn rejects such input in fit, too).  Device rows:
     // NOTHING is waited for -- the matrix is usable at once, the verdict stays in d_stats and is checked by the first kz_knn
@@ -809,6 +814,7 @@ int kz_matrix_destroy(kz_matrix* m) {
         kz_pool_free(m->ctx, m->sqn, 0);
         kz_pool_free(m->ctx, m->d_stats, 0);
         kz_pool_free(m->ctx, m->corr, 0);
+        kz_bool_image_free(m);
         kz_pool_free(m->ctx, m->seu_v, 0);
     }
     free(m->seu_v_host);

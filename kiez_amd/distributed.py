@@ -540,6 +540,7 @@ def row_slice(n: int, rank: int, world: int) -> Tuple[int, int]:
 # ---------------------------------------------------------------------------------------------------
 # the sharded pipeline
 # ---------------------------------------------------------------------------------------------------
+_NAN_METRICS = ("correlation", "dice", "sokalsneath")   # a returned distance can be NaN, ranked as +inf
 _HUB = {None: "none", "no": "none", "nohubnessreduction": "none", "csls": "csls", "localscaling": "ls", "ls": "ls",
         "mutualproximity": "mp", "mp": "mp", "dissimlocal": "dsl", "dsl": "dsl"}
 
@@ -598,12 +599,12 @@ class ShardedKiez:
         return eng.matrix(rows, self.metric) if self.V is None else eng.matrix(rows, self.metric, V=self.V)
 
     def _merge_key(self, d):
-        """The merge key of returned distances: the distance itself; correlation's NaN (a constant row) as the +inf the search
-        ranked it by (kz_merge_topk orders finite keys only by value)."""
-        return _torch().nan_to_num(d, nan=float("inf")) if self.metric == "correlation" else d
+        """The merge key of returned distances: the distance itself; correlation's NaN (a constant row; dice and sokalsneath: two
+        all-false rows) as the +inf the search ranked it by (kz_merge_topk orders finite keys only by value)."""
+        return _torch().nan_to_num(d, nan=float("inf")) if self.metric in _NAN_METRICS else d
 
     def _merge_unkey(self, d):
-        return _torch().where(_torch().isinf(d), float("nan"), d) if self.metric == "correlation" else d
+        return _torch().where(_torch().isinf(d), float("nan"), d) if self.metric in _NAN_METRICS else d
 
     def fit(self, source_shard, target=None, single_source: bool = False, target_from_rank0: bool = True):
         eng, comm = self.engine, self.comm

@@ -158,7 +158,9 @@ def canonical_metric(metric: str, p=2) -> str:
     scikit-learn's own aliases (sklearn/metrics/_dist_metrics.pyx.tp, DistanceMetric.get_metric): minkowski with p = 1 / 2 / inf IS
     manhattan / euclidean / chebyshev; `p` is ignored for every other metric name.  Euclidean, squared euclidean and cosine run the
     fused MFMA kernels; manhattan, chebyshev and minkowski(p) have no inner-product form and run on a register-tiled VALU kernel + the exact selection,
-    as do braycurtis, seuclidean, correlation and hamming (scikit-learn's brute-force expressions, bit for bit)."""
+    as do braycurtis, seuclidean, correlation and hamming (scikit-learn's brute-force expressions, bit for bit).  The seven boolean
+    metrics (jaccard, dice, rogerstanimoto, russellrao, sokalmichener, sokalsneath, yule: scipy's cdist on x != 0) run a popcount
+    kernel on bit-packed rows + the exact selection."""
     if metric == "minkowski":
         if not isinstance(p, (int, float, np.integer, np.floating)) or isinstance(p, bool) or not p >= 1:
             raise ValueError(f"metric='minkowski' needs p >= 1 on the MI355X exact backend (got p={p!r})")
@@ -175,7 +177,7 @@ def canonical_metric(metric: str, p=2) -> str:
         return "euclidean"
     if metric in ("manhattan", "cityblock", "l1"):
         return "manhattan"
-    if metric in ("sqeuclidean", "cosine", "chebyshev", "braycurtis", "seuclidean", "correlation", "hamming"):
+    if metric in ("sqeuclidean", "cosine", "chebyshev", "braycurtis", "seuclidean", "correlation", "hamming") or metric in N.BOOLEAN_METRICS:
         return metric
     raise ValueError(
         f"metric='{metric}' is not implemented by the MI355X exact backend; valid metrics: {SklearnNN.valid_metrics}")
@@ -210,8 +212,9 @@ class SklearnNN(NNAlgorithm):
     distance + top-k pass on the GPU.
     """
 
-    valid_metrics = ["braycurtis", "chebyshev", "cityblock", "correlation", "cosine", "euclidean", "hamming", "l1", "l2", "manhattan",
-                     "minkowski", "seuclidean", "sqeuclidean"]
+    valid_metrics = ["braycurtis", "chebyshev", "cityblock", "correlation", "cosine", "dice", "euclidean", "hamming", "jaccard", "l1",
+                     "l2", "manhattan", "minkowski", "rogerstanimoto", "russellrao", "seuclidean", "sokalmichener", "sokalsneath",
+                     "sqeuclidean", "yule"]
     # numpy arrays as in the reference; additionally arrays already resident in HBM (zero-copy fit)
     _ALLOWED_INPUT_TYPES = (np.ndarray, N.DeviceArray)
 
@@ -248,13 +251,13 @@ class SklearnNN(NNAlgorithm):
             self._ctx = N.Context.get(self.device)
         return self._ctx
 
-    @staticmethod
-    def _prepare(data) -> np.ndarray:
+    def _prepare(self, data) -> np.ndarray:
         arr = np.asarray(data)
         if arr.ndim != 2:
             raise ValueError(f"Expected 2D array, got {arr.ndim}D array instead")
         if arr.dtype not in (np.float32, np.float64):
-            arr = arr.astype(np.float64)
+            # (the boolean metrics read x != 0 only: bool, integer and float16 rows go up as float32 -- half the bytes; a nonzero value stays nonzero)
+            arr = arr.astype(np.float32 if self._metric_c in N.BOOLEAN_METRICS else np.float64)
         return np.ascontiguousarray(arr)
 
     def _check_input_types(self, value):
@@ -275,7 +278,7 @@ class SklearnNN(NNAlgorithm):
             if t.dim() != 2:
                 raise ValueError(f"Expected 2D array, got {t.dim()}D array instead")
             if t.dtype not in (torch.float32, torch.float64):
-                t = t.to(torch.float64)
+                t = t.to(torch.float32 if self._metric_c in N.BOOLEAN_METRICS else torch.float64)
             if dtype is not None and np.dtype(str(t.dtype).replace("torch.", "")) != dtype:
                 t = t.to(torch.float32 if dtype == np.float32 else torch.float64)
             if not t.is_cuda:
