@@ -14,8 +14,10 @@ __device__ __forceinline__ void kz_glds16(const float* gsrc, float* lds_wave_bas
 // The same with the address split the way the instruction takes it -- scalar 64-bit base + 32-bit per-lane byte offset
 // (saddr form) -- and the LDS base placed in M0 by hand.  hipcc otherwise materialises base + offset as a 64-bit VGPR pair
 // per lane and keeps it alive (and, at 168 VGPRs, spills and reloads it at every barrier).  Inline asm is invisible to
-// hipcc's waitcnt pass: it only ever under-counts the wave's outstanding operations, which makes its own vmcnt waits
-// stricter, never looser; completion of these copies is awaited explicitly (vmcnt(0) in front of the slice barrier).
+// hipcc's waitcnt pass: it under-counts the wave's outstanding operations, so a vmcnt(N) it inserts for a load of its own waits
+// for that load AND for every copy issued behind it.  Correct -- and expensive: between a tile's MFMAs such a wait is a wait for
+// the DMA ring.  So the pass must have nothing to wait for there ("waitcnt pass" below, tools/check_waits.py); completion of
+// the copies themselves is awaited explicitly (vmcnt(0) in front of the slice barrier).
 __device__ __forceinline__ void kz_glds16_s(const void* sbase_uniform, unsigned lane_byte_off, float* lds_wave_base) {
     const unsigned lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base;
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
@@ -30,6 +32,21 @@ __device__ __forceinline__ void kz_glds4_s(const void* sbase_uniform, unsigned l
                  :
                  : "s"(lds), "v"(lane_byte_off), "s"(sbase_uniform)
                  : "memory", "m0");
+}
+// WAITCNT PASS.  What hipcc's waitcnt pass believes at the entry of a sweep kernel's tile loop decides what it inserts INSIDE it:
+//   * a load of the prologue that it still counts as in flight (the stationary query fragments: 13 .. 64 global loads) is awaited
+//     at its first use in the loop, in every iteration -- a descending chain vmcnt(23) .. vmcnt(0) down the slices and a
+//     vmcnt(0) in front of a tile's first MFMA.  A hand-written `s_waitcnt` in inline asm does not tell it otherwise;
+//   * a FLAT operation it counts as pending (it may return out of order, in both counters) makes every later wait for an LDS read
+//     a wait for ZERO -- the fragment prefetch under the MFMAs is gone -- until a vmcnt wait clears it, which the loop never has.
+// Hence: the prologue's wait for its loads is the BUILTIN below (a wait the pass sees takes those loads off its books: nothing of
+// its own is pending at loop entry), and the log flush of the dual pass uses global-address-space pointers (kz_knn_epi3.h).
+// s_waitcnt vmcnt(0), gfx9 encoding: vmcnt = 0; expcnt = 7 and lgkmcnt = 15 are left alone.  The empty asm statements keep the
+// hand-issued copies in front of it and the workgroup barrier behind it.
+__device__ __forceinline__ void kz_wait_vm0_seen() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+    asm volatile("" ::: "memory");
 }
 typedef float f32x4e __attribute__((ext_vector_type(4)));
 typedef int i32x2e __attribute__((ext_vector_type(2)));

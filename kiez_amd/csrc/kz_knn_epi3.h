@@ -100,6 +100,12 @@ struct KzDualRef {
     //  carried in scalar registers for the whole sweep they pushed the kernel into spilling SGPRs to a VGPR)
 };
 constexpr int KZ_COL_FLAG = (int)0x80000000;
+// The log lives in global memory and the flush says so: a pointer made from a kernel-argument word is a GENERIC one to the compiler,
+// whose atomics and stores are FLAT instructions -- counted in vmcnt AND lgkmcnt, possibly returning out of order, so that with one
+// of them pending hipcc's waitcnt pass waits for ZERO at every later LDS read of the sweep (kz_knn_device.h, "waitcnt pass").
+typedef __attribute__((address_space(1))) f32x4e kz_glb_f32x4;
+typedef __attribute__((address_space(1))) i32x2e kz_glb_i32x2;
+typedef __attribute__((address_space(1))) unsigned long long kz_glb_u64;
 
 __device__ __forceinline__ void kz_flush_col3(const KzWavePool& pool, const KzDualRef& du) {
     const int lane = threadIdx.x & 63;
@@ -113,9 +119,9 @@ __device__ __forceinline__ void kz_flush_col3(const KzWavePool& pool, const KzDu
     if (n_col == 0) return;
     typedef __attribute__((address_space(4))) const volatile unsigned long long kz_karg_u64;
     const __attribute__((address_space(4))) char* ka = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-    f32x4e* log_keys = (f32x4e*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_keys));
-    i32x2e* log_meta = (i32x2e*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_meta));
-    unsigned long long* log_cnt = (unsigned long long*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_cnt));
+    kz_glb_f32x4* log_keys = (kz_glb_f32x4*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_keys));
+    kz_glb_i32x2* log_meta = (kz_glb_i32x2*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_meta));
+    kz_glb_u64* log_cnt = (kz_glb_u64*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_cnt));
     const long long log_cap = (long long)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_cap));
     unsigned long long base = 0;
     if (lane == 0) base = __hip_atomic_fetch_add(log_cnt, (unsigned long long)n_col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

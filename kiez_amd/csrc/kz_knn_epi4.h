@@ -36,9 +36,9 @@ __device__ __forceinline__ void kz_flush_col4(const KzWavePool& pool, const KzDu
     if (n_col == 0) return;
     typedef __attribute__((address_space(4))) const volatile unsigned long long kz_karg_u64;
     const __attribute__((address_space(4))) char* ka = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-    f32x4e* log_keys = (f32x4e*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_keys));
-    i32x2e* log_meta = (i32x2e*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_meta));
-    unsigned long long* log_cnt = (unsigned long long*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_cnt));
+    kz_glb_f32x4* log_keys = (kz_glb_f32x4*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_keys));
+    kz_glb_i32x2* log_meta = (kz_glb_i32x2*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_meta));
+    kz_glb_u64* log_cnt = (kz_glb_u64*)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_cnt));
     const long long log_cap = (long long)*(kz_karg_u64*)(ka + offsetof(KnnCandParams, log_cap));
     unsigned long long base = 0;
     if (lane == 0) base = __hip_atomic_fetch_add(log_cnt, (unsigned long long)n_col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

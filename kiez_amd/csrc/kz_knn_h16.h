@@ -206,7 +206,9 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
     for (int u = 0; u < NSR; ++u) qf[u] = *reinterpret_cast<const kz_f16x8*>(qbase + u * 1024);
     // the whole prologue ring must have landed before anyone reads it: said explicitly (the copies are inline asm, invisible to the
     // compiler's barrier; every wave's bias-row store above happens to wait for them too -- kz_knn_h64.h shows what happens without)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // -- and said so that the waitcnt pass sees it: the query fragments above are complete HERE, not at their first use in every
+    // tile (kz_knn_device.h "WAITCNT PASS")
+    kz_wait_vm0_seen();
     __syncthreads();
 
     const float* fbase = ybuf + (h * KZ_TILE + j) * 4;  // this lane's fragment inside a slot: plane h, row j (+ 32 mt)

@@ -23,6 +23,7 @@
 // Order of a sweep: tile t: half 0 slices 0 .. NSR-1, half 1 slices 0 .. NSR-1, tile t + 1 ...  Ring of 8 slots (16 KiB), one
 // workgroup barrier per 4 half slices, fragments of half slice g + 1 fetched under the MFMAs of half slice g (two static sets) --
 // the protocol of kz_knn_h16.h at two workgroups per CU.  Requires 4 <= NSR (every half tile contains a barrier) and NSR <= 13.
+// Which slices carry a barrier, and what a wave copies there, is fixed at compile time per tile body (see "LDS-DMA of half slices").
 // Candidate selection: kz_knn_epi4.h (the scan of kz_knn_epi3.h for a lane that owns two queries).  Lists in LDS, flushed to the
 // output arrays in the layout kz_knn_finalize_kernel reads; entry codes, dual-pass log and results are those of kz_knn_h16.h.
 #pragma once
@@ -49,6 +50,13 @@ struct KzH64Cfg {
     static_assert(LDS_BYTES <= 64 * 1280, "two workgroups per CU: 64 LDS granules of 1280 B each");
     static_assert(NSR >= PERIOD && NSR <= 13, "every half tile must contain a slice barrier; 13 stationary slices = 104 VGPRs");
 };
+
+// Byte offset of half slice L of a sweep (L counted from half 0, slice 0 of some tile: L = 2 NSR tiles + NSR half + slice) inside the
+// image, relative to that tile's first slice and without the plane: the order of a sweep is the order of L.
+template <int NSR>
+__host__ __device__ constexpr unsigned kz_h64_half_slice_off(const int L) {
+    return (unsigned)((L / (2 * NSR)) * NSR + (L % (2 * NSR)) % NSR) * 4096u + (unsigned)((L % (2 * NSR)) / NSR) * 1024u;
+}
 
 template <int NSR, bool DUAL>
 __global__ __launch_bounds__(256, 2) void kz_knn_cand_h64_kernel(KnnCandParams p) {
@@ -116,26 +124,27 @@ __global__ __launch_bounds__(256, 2) void kz_knn_cand_h64_kernel(KnnCandParams p
     pool.next_merge = 1;
 
     // LDS-DMA of half slices: the waves of pair (wave >> 1) copy the half slices G of the sweep with G % 2 == pair, wave (wave & 1)
-    // of the pair the rows' plane (wave & 1) -- 64 rows x 16 B = 1 KiB per instruction.  (d_tile, d_hf, d_u) = the next half slice
-    // of this wave, d_slot its ring slot; the sequence runs past the end of the sweep into the next tiles of the image or the
-    // padding behind it (kz_himage_build), those slots are never read.
-    int d_tile = t_begin, d_hf = 0, d_u = tb, d_slot = tb;   // (NSR >= 4: half slices 0 and 1 are slices 0 and 1 of half 0)
-    const char* ybase = reinterpret_cast<const char*>(p.ypack) + (wave & 1) * 2048;
-    auto dma_next = [&]() {
-        const char* src = ybase + ((int64_t)d_tile * NSR + d_u) * 4096 + d_hf * 1024;   // uniform
+    // of the pair the rows' plane (wave & 1) -- 64 rows x 16 B = 1 KiB per instruction.  The sequence runs past the end of the sweep
+    // into the next tiles of the image or the padding behind it (kz_himage_build), those slots are never read.
+    // The tile loop is unrolled over the slices with the barrier phase as a template argument: the copy a wave issues at a given
+    // barrier is the half slice a FIXED lead ahead, so its source offset from the current tile's first slice is a compile-time
+    // constant per barrier position (two of them: one per pair) and its slot differs from a constant by one bit that flips at
+    // every barrier.  tile_src advances once per tile; a copy costs a scalar select and a 64-bit add (a running (tile, half, slice,
+    // slot) with its wraps and a 64-bit multiply by NSR was ~20 scalar instructions and two branches per copy).
+    const char* tile_src = reinterpret_cast<const char*>(p.ypack) + (wave & 1) * 2048 + ((int64_t)t_begin * NSR) * 4096;   // uniform
+    float* const ring_wave = ybuf + tb * Cfg::SLOT_FLOATS + (wave & 1) * 256;   // slot `pair` of the ring, this wave's plane
+    int ring_hi = 0;   // 0 or 4: the slots a barrier hands out alternate between the ring's halves (uniform)
+    // half slice L0 + pair (L0 even, counted from the current tile's first half slice) into slot slot0 + pair.  Always inlined: L0
+    // is a constant only inside the unrolled slice loop of its caller (in the built 13-slice dual kernel a copy is s_add_u32 /
+    // s_addc_u32 twice -- the pair's offsets sit in two scalar registers -- and one s_add_i32 for M0; profiles/sweep_waits.md)
+    auto dma_at = [&](const int L0, const int slot0) __attribute__((always_inline)) {
+        const unsigned off = tb ? kz_h64_half_slice_off<NSR>(L0 + 1) : kz_h64_half_slice_off<NSR>(L0);   // uniform
         unsigned lane16;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshlrev_b32 %0, 4, %0" : "=v"(lane16));
-        kz_glds16_s(src, lane16, ybuf + d_slot * Cfg::SLOT_FLOATS + (wave & 1) * 256);
-        d_u += 2;
-        if (d_u >= NSR) {
-            d_u -= NSR;
-            d_hf ^= 1;
-            if (d_hf == 0) ++d_tile;
-        }
-        d_slot = (d_slot + 2) & (R - 1);
+        kz_glds16_s(tile_src + off, lane16, ring_wave + slot0 * Cfg::SLOT_FLOATS);
     };
 #pragma unroll
-    for (int i = 0; i < R / 2; ++i) dma_next();
+    for (int i = 0; i < R / 2; ++i) dma_at(2 * i, 2 * i);   // (NSR >= 4: half slices 0 .. 7 lie in the first tile or the one behind it)
     if (tid < 64) bbuf[tid] = p.ybias[(int64_t)t_begin * KZ_TILE + tid];
     KzDualRef4 du;
     du.qrow0 = (p.qt0 + qt) * KZ_TILE + r0;
@@ -160,7 +169,9 @@ __global__ __launch_bounds__(256, 2) void kz_knn_cand_h64_kernel(KnnCandParams p
     // know them, and only waves with a load-dependent LDS store of their own in front of it (wave 0's bias rows; every wave in the
     // dual build) would wait for them by accident -- at 4 slices (8 query-fragment loads) waves 1 .. 3 of the ordinary build did
     // reach the barrier with copies in flight: 1 - 4 wrong rows in ~1 % of randomised runs (tools/fuzz_dual.py, round 4).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // A wait the waitcnt pass sees: the query fragments are complete here, not at their first use in every tile (kz_knn_device.h
+    // "WAITCNT PASS").
+    kz_wait_vm0_seen();
     __syncthreads();
 
     const float* fbase = ybuf + (h * 64 + j) * 4;   // this lane's fragment inside a slot: plane h, row j (+ 32 rb)
@@ -176,9 +187,10 @@ __global__ __launch_bounds__(256, 2) void kz_knn_cand_h64_kernel(KnnCandParams p
     int th_cur = 0;   // dual pass: threshold buffer of the current half tile (uniform)
     f32x16 acc[2][2];
 
-    // one half tile (64 index rows) whose first half slice has global parity P0
-    auto run_half = [&](const int tile, const int hf, auto start_parity) {
-        constexpr int P0 = decltype(start_parity)::value;
+    // one half tile (64 index rows), half HF of its tile, whose first half slice has the global number Q0 modulo the barrier period
+    auto run_half = [&](const int tile, auto half, auto start_phase) __attribute__((always_inline)) {
+        constexpr int HF = decltype(half)::value, Q0 = decltype(start_phase)::value, P0 = Q0 & 1;
+        const int hf = HF;
         f32x16 binit[2];
         {
             const float* bp = bbuf + (seq & 1) * 64 + 4 * h;
@@ -236,10 +248,12 @@ __global__ __launch_bounds__(256, 2) void kz_knn_cand_h64_kernel(KnnCandParams p
             // fragments of all half slices <= g + 1 in registers, so the slots of g-P+2 .. g+1 take g+P+2 .. g+2P+1 (this wave's
             // share: the two of its parity).  The next period prefetches g+2 .. g+P+1: issued at the PREVIOUS barrier, hence
             // vmcnt(0).
-            if (((g + 2) & (P - 1)) == 0) {
+            // (g = Q0 + u modulo P: a compile-time phase.  This wave's share of the slots: half slices g + 6 + pair, g + 8 + pair.)
+            if (((Q0 + u + 2) & (P - 1)) == 0) {
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-                for (int i = 0; i < P / 2; ++i) dma_next();   // (issued one half slice later, behind the next MFMAs: +3 ... +4 % -- measured, not kept)
+                dma_at(HF * NSR + u + 6, ring_hi);       // (issued one half slice later, behind the next MFMAs: +3 ... +4 % -- measured, not kept)
+                dma_at(HF * NSR + u + 8, ring_hi + 2);
+                ring_hi ^= 4;
             }
             ++g;
         }
@@ -255,11 +269,21 @@ __global__ __launch_bounds__(256, 2) void kz_knn_cand_h64_kernel(KnnCandParams p
         ++seq;
     };
 
+    // a tile is 2 NSR half slices: with NSR odd the barrier phase of a tile's first half slice alternates between 0 and 2
+    using H0 = std::integral_constant<int, 0>;
+    using H1 = std::integral_constant<int, 1>;
     int tile = t_begin;
     for (;;) {
-        run_half(tile, 0, std::integral_constant<int, 0>{});
-        run_half(tile, 1, std::integral_constant<int, (NSR & 1)>{});
+        run_half(tile, H0{}, std::integral_constant<int, 0>{});
+        run_half(tile, H1{}, std::integral_constant<int, NSR % P>{});
+        tile_src += NSR * 4096;
         if (++tile >= t_end) break;
+        if constexpr ((NSR & 1) != 0) {
+            run_half(tile, H0{}, std::integral_constant<int, 2>{});
+            run_half(tile, H1{}, std::integral_constant<int, (2 + NSR) % P>{});
+            tile_src += NSR * 4096;
+            if (++tile >= t_end) break;
+        }
     }
     // the sweep is over: the lists go to the output arrays in the layout kz_knn_finalize_kernel reads
     int lane_now;

@@ -180,8 +180,9 @@ __global__ __launch_bounds__(256, 1) void kz_knn_cand_hx_kernel(KnnCandParams p)
     kz_f16x8 qf[NSH];
 #pragma unroll
     for (int u = 0; u < NSH; ++u) qf[u] = *reinterpret_cast<const kz_f16x8*>(qbase + u * 2048);
-    // the whole prologue ring must have landed before anyone reads it (the copies are inline asm, invisible to the compiler's barrier)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the whole prologue ring must have landed before anyone reads it (the copies are inline asm, invisible to the compiler's barrier);
+    // a wait the waitcnt pass sees: the 40 .. 64 query-fragment loads above are complete here (kz_knn_device.h "WAITCNT PASS")
+    kz_wait_vm0_seen();
     __syncthreads();
 
     const float* fbase = ybuf + (h * KZ_TILE + j) * 4;  // this lane's fragment inside a slot: plane h, row j (+ 32 mt)
