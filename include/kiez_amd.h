@@ -175,10 +175,15 @@ int kz_knn_plan(int64_t n_query_rows, int64_t n_index_rows, int k_eff, int slots
                 int* n_rounds, int* round_qtiles, int* round_pieces, int* round_piece_tiles);
 
 /* ---- per-row statistics of a [n, K] distance array (numpy summation order) ----------------------------- */
-/* mean: ndarray.mean(axis=1); std: np.nanstd(axis=1) (ddof=0); last: column K-1.  Any output may be NULL.
- * Used for the fit state of CSLS (csls.py:90), NICDM (local_scaling.py:143), LS (:136), MP normal
- * (mutual_proximity.py:102-103). */
+/* mean: ndarray.mean(axis=1) (a NaN in the row gives NaN, as CSLS and NICDM have it); std: np.nanstd(axis=1) (ddof=0: NaN
+ * entries are skipped, a row of NaN only gives NaN); last: column K-1.  Any output may be NULL.
+ * Used for the fit state of CSLS (csls.py:90), NICDM (local_scaling.py:143), LS (:136). */
 int kz_row_stats(kz_ctx* ctx, const double* d_dist, int64_t n, int K, double* d_mean, double* d_std, double* d_last);
+/* mean: np.nanmean(axis=1); std: np.nanstd(axis=1) (ddof=0).  NaN entries (correlation against a constant row, dice /
+ * sokalsneath between all-false rows) count as 0 in numpy's summation tree over the whole row and the sums are divided by the
+ * number of entries that are not NaN; a row of NaN only gives NaN.  Either output may be NULL.  The fit state of MP normal
+ * (mutual_proximity.py:102-103); kz_mp_normal computes the query side (:177-178) the same way. */
+int kz_row_nanstats(kz_ctx* ctx, const double* d_dist, int64_t n, int K, double* d_mean, double* d_std);
 
 /* ---- hubness rescaling: replace HubnessReduction.transform of each method ------------------------------ */
 /* All take the forward candidates d_dist/d_ind [n, K] and write the UNSORTED rescaled distances d_out [n, K]. */

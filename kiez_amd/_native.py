@@ -112,6 +112,7 @@ SYMBOLS = [
                               C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("kz_selftest_div", C.c_int, [_P, _I64, C.c_uint64, C.c_int, C.POINTER(_I64)]),
     ("kz_row_stats", C.c_int, [_P, _P, _I64, C.c_int, _P, _P, _P]),
+    ("kz_row_nanstats", C.c_int, [_P, _P, _I64, C.c_int, _P, _P]),
     ("kz_csls", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, _P]),
     ("kz_local_scaling", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, C.c_int, _P]),
     ("kz_mp_normal", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, _P, _P]),
@@ -390,6 +391,14 @@ def row_stats(ctx: Context, dist: DeviceArray, mean=False, std=False, last=False
     _check(ctx.lib.kz_row_stats(ctx.handle, dist.ptr, n, K, m.ptr if m else None, s.ptr if s else None,
                                 l_.ptr if l_ else None), "kz_row_stats")
     return m, s, l_
+
+
+def row_nanstats(ctx: Context, dist: DeviceArray):
+    """kz_row_nanstats -> (np.nanmean, np.nanstd) of every row, each [n]."""
+    n, K = dist.shape
+    m, s = ctx.empty((n,), np.float64), ctx.empty((n,), np.float64)
+    _check(ctx.lib.kz_row_nanstats(ctx.handle, dist.ptr, n, K, m.ptr, s.ptr), "kz_row_nanstats")
+    return m, s
 
 
 def select_topk(ctx: Context, dist: DeviceArray, ind: DeviceArray, k: int):

@@ -11,52 +11,69 @@
 
 // (kz_np_pairwise_sum, numpy's pairwise summation: kz_common.h)
 
-// same summation applied to (a[i] - c)^2 (np.nanstd: subtract mean, square, sum; numpy/lib/_nanfunctions_impl.py)
-__device__ double kz_np_pairwise_sumsq_dev(const double* a, int n, double c) {
+// numpy's pairwise summation tree (kz_np_pairwise_sum, kz_common.h) over n terms term(lo) .. term(lo + n - 1)
+template <typename F>
+__device__ double kz_np_pairwise_terms(int lo, int n, const F& term) {
     if (n < 8) {
         double res = 0.0;
-        for (int i = 0; i < n; ++i) {
-            const double t = a[i] - c;
-            res += t * t;
-        }
+        for (int i = 0; i < n; ++i) res += term(lo + i);
         return res;
     }
     if (n <= 128) {
         double r[8];
-        for (int u = 0; u < 8; ++u) {
-            const double t = a[u] - c;
-            r[u] = t * t;
-        }
+        for (int u = 0; u < 8; ++u) r[u] = term(lo + u);
         int i;
         for (i = 8; i < n - (n % 8); i += 8) {
-            for (int u = 0; u < 8; ++u) {
-                const double t = a[i + u] - c;
-                r[u] += t * t;
-            }
+            for (int u = 0; u < 8; ++u) r[u] += term(lo + i + u);
         }
         double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) {
-            const double t = a[i] - c;
-            res += t * t;
-        }
+        for (; i < n; ++i) res += term(lo + i);
         return res;
     }
     int n2 = n / 2;
     n2 -= n2 % 8;
-    return kz_np_pairwise_sumsq_dev(a, n2, c) + kz_np_pairwise_sumsq_dev(a + n2, n - n2, c);
+    return kz_np_pairwise_terms(lo, n2, term) + kz_np_pairwise_terms(lo + n2, n - n2, term);
 }
 
+// np.nanmean / np.nanstd of one row (numpy/lib/_nanfunctions_impl.py: nanmean, _nanvar with ddof = 0): NaN entries are replaced
+// by 0 and summed in the SAME full-length tree, the sum is divided by the number of entries that are not NaN; for the variance
+// the mean is subtracted first, then the NaN positions are set to 0, then the squares are summed in that tree and divided by the
+// same count.  A row of NaN only gives 0 / 0 = NaN for both.  Without a NaN this is ndarray.mean / ndarray.std bit for bit.
+__device__ void kz_np_nanmean_nanstd(const double* a, int K, double* mean, double* sd) {
+    int cnt = 0;
+    for (int c = 0; c < K; ++c) cnt += a[c] == a[c] ? 1 : 0;
+    const double m = kz_np_pairwise_terms(0, K, [a](int i) { const double x = a[i]; return x == x ? x : 0.0; }) / (double)cnt;
+    *mean = m;
+    if (sd)
+        *sd = sqrt(kz_np_pairwise_terms(0, K, [a, m](int i) {
+                  const double x = a[i];
+                  const double t = x == x ? x - m : 0.0;
+                  return t * t;
+              }) / (double)cnt);
+}
+
+// mean: ndarray.mean (a NaN propagates: CSLS csls.py:90-91 and NICDM local_scaling.py:143-144 call .mean()); sd: np.nanstd
 __global__ void kz_row_stats_kernel(const double* __restrict__ dist, int64_t n, int K, double* __restrict__ mean,
                                     double* __restrict__ sd, double* __restrict__ last) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const double* a = dist + r * (int64_t)K;
     if (last) last[r] = a[K - 1];
-    if (mean || sd) {
-        const double m = kz_np_pairwise_sum(a, K) / (double)K;
-        if (mean) mean[r] = m;
-        if (sd) sd[r] = sqrt(kz_np_pairwise_sumsq_dev(a, K, m) / (double)K);
+    if (mean) mean[r] = kz_np_pairwise_sum(a, K) / (double)K;
+    if (sd) {
+        double m;
+        kz_np_nanmean_nanstd(a, K, &m, &sd[r]);
     }
+}
+
+// np.nanmean / np.nanstd: the fit state of MutualProximity 'normal' (mutual_proximity.py:102-103)
+__global__ void kz_row_nanstats_kernel(const double* __restrict__ dist, int64_t n, int K, double* __restrict__ mean,
+                                       double* __restrict__ sd) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    double m;
+    kz_np_nanmean_nanstd(dist + r * (int64_t)K, K, &m, sd ? &sd[r] : nullptr);
+    if (mean) mean[r] = m;
 }
 
 // CSLS: out = 2*d - mean_K(d[i,:]) - r_train[ind]      (csls.py:90-93)
@@ -114,8 +131,8 @@ __global__ void kz_mp_normal_kernel(const double* __restrict__ dist, const int64
     if (r >= n) return;
     const double* a = dist + r * (int64_t)K;
     const int64_t* id = ind + r * (int64_t)K;
-    const double mu = kz_np_pairwise_sum(a, K) / (double)K;
-    const double sd = sqrt(kz_np_pairwise_sumsq_dev(a, K, mu) / (double)K);
+    double mu, sd;   // np.nanmean / np.nanstd (mutual_proximity.py:177-178): a list that ends in NaN keeps its finite entries
+    kz_np_nanmean_nanstd(a, K, &mu, &sd);
     for (int c = 0; c < K; ++c) {
         const double d = a[c];
         const double p1 = kz_ndtr(-((d - mu) / sd));
@@ -538,6 +555,14 @@ int kz_row_stats(kz_ctx* ctx, const double* d_dist, int64_t n, int K, double* d_
     KZ_CHECK_NK("kz_row_stats");
     KZ_REQUIRE(d_dist != nullptr, "kz_row_stats: null input");
     hipLaunchKernelGGL(kz_row_stats_kernel, kz_grid1d(n, 256), dim3(256), 0, ctx->stream, d_dist, n, K, d_mean, d_std, d_last);
+    KZ_HIP(hipGetLastError());
+    return KZ_OK;
+}
+
+int kz_row_nanstats(kz_ctx* ctx, const double* d_dist, int64_t n, int K, double* d_mean, double* d_std) {
+    KZ_CHECK_NK("kz_row_nanstats");
+    KZ_REQUIRE(d_dist != nullptr, "kz_row_nanstats: null input");
+    hipLaunchKernelGGL(kz_row_nanstats_kernel, kz_grid1d(n, 256), dim3(256), 0, ctx->stream, d_dist, n, K, d_mean, d_std);
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }

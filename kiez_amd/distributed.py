@@ -121,6 +121,12 @@ class HipEngine:
                                             self._ptr(s) if std else None, self._ptr(l_) if last else None), "kz_row_stats")
         return m, s, l_
 
+    def row_nanstats(self, dist):
+        n, K = dist.shape
+        m, s = self.empty((n,), self.torch.float64), self.empty((n,), self.torch.float64)
+        self.N._check(self.lib.kz_row_nanstats(self.ctx.handle, self._ptr(dist), n, K, self._ptr(m), self._ptr(s)), "kz_row_nanstats")
+        return m, s
+
     def csls(self, dist, ind, r_train):
         out = self.empty(tuple(dist.shape), self.torch.float64)
         self.N._check(self.lib.kz_csls(self.ctx.handle, self._ptr(dist), self._ptr(ind), dist.shape[0], dist.shape[1],
@@ -756,7 +762,12 @@ class ShardedKiez:
             _, _, last = eng.row_stats(d_t2s, last=True)
             st["r_t"] = comm.all_gather_rows(last, t_counts)
         elif self.hub == "mp" and self.method == "normal":
-            m, s, _ = eng.row_stats(d_t2s, mean=True, std=True)
+            # np.nanmean / np.nanstd (mutual_proximity.py:102-103).  row_nanstats joined the engine interface after row_stats:
+            # an engine without it states the same through row_stats, which agrees on every list without a NaN
+            if hasattr(eng, "row_nanstats"):
+                m, s = eng.row_nanstats(d_t2s)
+            else:
+                m, s, _ = eng.row_stats(d_t2s, mean=True, std=True)
             st["mu_t"] = comm.all_gather_rows(m, t_counts)
             st["sd_t"] = comm.all_gather_rows(s, t_counts)
         elif self.hub == "mp":

@@ -284,7 +284,7 @@ class MutualProximity(HubnessReduction):
             self._dist_t2s_dev = d
             self._ind_t2s_dev = self.ctx.as_device(neigh_ind, np.int64)
         else:
-            mu, sd, _ = N.row_stats(self.ctx, d, mean=True, std=True)      # :102-103
+            mu, sd = N.row_nanstats(self.ctx, d)       # :102-103 (np.nanmean / np.nanstd)
             self._mu_dev, self._sd_dev = mu, sd
             self.mu_t_to_s_ = mu
             self.sd_t_to_s_ = sd

@@ -62,6 +62,10 @@ class OracleEngine:
         l_ = torch.from_numpy(a[:, -1].copy()) if last else None
         return m, s, l_
 
+    def row_nanstats(self, dist):
+        a = dist.numpy()
+        return torch.from_numpy(np.nanmean(a, axis=1)), torch.from_numpy(np.nanstd(a, axis=1))
+
     def csls(self, dist, ind, r_train):
         d, i = dist.numpy(), ind.numpy()
         return torch.from_numpy(2 * d - d.mean(axis=1).reshape(-1, 1) - r_train.numpy()[i])

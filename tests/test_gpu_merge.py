@@ -98,7 +98,8 @@ def test_merge_topk_rejects_bad_shapes(ctx):
         N._check(ctx.lib.kz_merge_topk(ctx.handle, a.ptr, None, None, 4, 100, 100, 5, od.ptr, oi.ptr), "kz_merge_topk")
 
 
-@pytest.mark.parametrize("n,K,k", [(1000, 129, 129), (777, 200, 50), (300, 1000, 1000), (65, 1500, 3), (40, 4096, 100), (500, 256, 1)])
+@pytest.mark.parametrize("n,K,k", [(1000, 129, 129), (777, 200, 50), (300, 1000, 1000), (65, 1500, 3), (40, 4096, 100), (500, 256, 1),
+                                   (9, 1024, 7), (9, 1025, 7)])
 def test_wide_select_topk_is_the_reference_selection_sort(ctx, n, K, k):
     """HubnessReduction._sort (base.py:72-87) for more than 128 candidates: tie-heavy rows, NaN last."""
     from kiez_amd import _native as N
