@@ -13,6 +13,7 @@
 #include <vector>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "kz_common.h"
@@ -1804,6 +1805,35 @@ __global__ __launch_bounds__(256) void kz_exact_select_kernel(const int* __restr
                           out_dist + (int64_t)q * k, out_ind + (int64_t)q * k, lane, p);
 }
 
+// The dynamic LDS of a kz_exact_select_kernel<T> launch that selects k_sel neighbours per row -- the ONE rule of every launch site
+// (the whole-index fallback and kz_spec_rescue below, the grouped and per-row ranges of kz_range.h): k_sel doubles + k_sel ints.
+// The kernel's STATIC LDS (the lists of the long-segment pre-selection) comes on top of it: the runtime is asked for that size,
+// once per instantiation -- no constant here to keep in step with the kernel -- and a workgroup that needs more than 64 KiB in
+// all (k_sel >= 3749 of the 4096 the exact-only route admits) opts in, as every other launcher of this library does.  Beyond the
+// 160 KiB of a CU's LDS no launch can be made: KZ_ERR_UNSUPPORTED (unreachable while KZ_EXACT_MAX_K = 4096: 68.2 KiB).
+template <typename T>
+static int kz_exact_select_lds(int k_sel, size_t* dyn_bytes) {
+    static std::atomic<long long> static_cache{-1};
+    long long static_bytes = static_cache.load(std::memory_order_relaxed);
+    if (static_bytes < 0) {
+        hipFuncAttributes fa;
+        KZ_HIP(hipFuncGetAttributes(&fa, (const void*)kz_exact_select_kernel<T>));
+        static_bytes = (long long)fa.sharedSizeBytes;
+        static_cache.store(static_bytes, std::memory_order_relaxed);
+    }
+    const size_t dyn = (size_t)k_sel * 12 + 16;
+    const size_t total = (size_t)static_bytes + dyn;
+    if (total > (size_t)160 * 1024) {
+        kz_set_error("kz_knn: %d neighbours per query need %zu bytes of LDS in the exact selection kernel (%lld static), more than the 163840 of a CU",
+                     k_sel, total, static_bytes);
+        return KZ_ERR_UNSUPPORTED;
+    }
+    if (total > 65536)   // (per device: set whenever it is needed, the call is host bookkeeping)
+        KZ_HIP(hipFuncSetAttribute((const void*)kz_exact_select_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    *dyn_bytes = dyn;
+    return KZ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------------------
@@ -1937,7 +1967,10 @@ __global__ __launch_bounds__(256) void kz_scatter_rows_kernel(const double* __re
 // candidate set cannot be certified under that tier's bound go down: fp16 / split-bf16 -> float32 operands (gathered into
 // a dense query block) -> exact float64 brute force.  The result is the float64 neighbour order at every tier.
 enum { KZ_TIER_F32 = 0, KZ_TIER_BF = 1, KZ_TIER_H = 2 };
-constexpr int KZ_EXACT_MAX_K = 4096;   // neighbours per query on the exact-only route (selection state: 48 KiB of LDS)
+// neighbours per query on the exact-only route.  Selection state: 12 bytes per neighbour, 48 KiB of dynamic LDS at 4096 -- on top
+// of kz_exact_select_kernel's ~20 KiB of static LDS: more than 64 KiB in all from 3749 neighbours on, hence the opt-in of
+// kz_exact_select_lds (68.2 KiB of a CU's 160 at 4096)
+constexpr int KZ_EXACT_MAX_K = 4096;
 
 // The finalize launches of one pass: one per list region (the dynamic LDS follows the region's entry count: occupancy of
 // the gather).  fp.q_first / q_last / max_m are filled here.
@@ -2286,7 +2319,11 @@ static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query
     const int metric = index->metric;
     const int k_eff = k + (exclude_self ? 1 : 0);
     const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-    const size_t sel_lds = (size_t)k_sel * 12 + 16;
+    size_t sel_lds = 0;
+    {
+        const int rcs = index->dtype == KZ_F32 ? kz_exact_select_lds<float>(k_sel, &sel_lds) : kz_exact_select_lds<double>(k_sel, &sel_lds);
+        if (rcs != KZ_OK) return rcs;
+    }
     const int n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
     // (two selection levels from two chunks on: the single-level kernel passes k_eff times over the whole row with ONE workgroup --
     //  135 us for 15 k values, k = 10; the chunk kernel selects from registers)
@@ -3258,11 +3295,9 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             if (rc != KZ_OK) return rc;
             const int dist_blocks = (int)((index->n + 3) / 4);
             const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-            const size_t sel_lds = (size_t)k_sel * 12 + 16;
-            if (sel_lds > 65536) {
-                kz_set_error("kz_knn: k=%d is too large for the exact selection kernel", k_eff);
-                return KZ_ERR_UNSUPPORTED;
-            }
+            size_t sel_lds = 0;
+            rc = index->dtype == KZ_F32 ? kz_exact_select_lds<float>(k_sel, &sel_lds) : kz_exact_select_lds<double>(k_sel, &sel_lds);
+            if (rc != KZ_OK) return rc;
             // rows of more than four chunks: the selection in two levels (kz_exact_chunk_kernel)
             const int n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
             const bool two_level = n_chunks > 4 && k_sel <= KZ_EXACT_CHUNK;

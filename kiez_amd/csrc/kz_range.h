@@ -500,7 +500,11 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
     const int metric = index->metric, d = (int)index->d;
     const int k_eff = k + (exclude_self ? 1 : 0);
     const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-    const size_t sel_lds = (size_t)k_sel * 12 + 16;
+    size_t sel_lds = 0;   // (kz_exact_select_lds, kz_knn.hip: the one rule of every launch of the selection kernel)
+    {
+        const int rcs = kz_exact_select_lds<float>(k_sel, &sel_lds);
+        if (rcs != KZ_OK) return rcs;
+    }
     const size_t row_bytes = (size_t)d * 4;
     int n_rep = (n_fail + KZ_RG_STRIDE - 1) / KZ_RG_STRIDE;
     if (n_rep > KZ_RG_MAX_REPS) n_rep = KZ_RG_MAX_REPS;
@@ -700,7 +704,11 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
     const int metric = index->metric;
     const int k_eff = k + (exclude_self ? 1 : 0);
     const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-    const size_t sel_lds = (size_t)k_sel * 12 + 16;
+    size_t sel_lds = 0;   // (kz_exact_select_lds, kz_knn.hip: the one rule of every launch of the selection kernel)
+    {
+        const int rcs = kz_exact_select_lds<float>(k_sel, &sel_lds);
+        if (rcs != KZ_OK) return rcs;
+    }
     const size_t row_bytes = (size_t)query->d * 4;
     const int64_t y_pad = index->n_tiles * KZ_TILE;
     // the log: 24 bytes per group of four keys -- at most a quarter of the free memory, at most 2^28 groups (6 GiB)
