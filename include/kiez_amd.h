@@ -287,6 +287,22 @@ int kz_kocc_select(kz_ctx* ctx, const int64_t* d_kocc, int64_t n, int mode, doub
  * rows whose gold id is absent.  hits@k = sum(d_hist[:k]) / len(gold). */
 int kz_hit_positions(kz_ctx* ctx, const int64_t* d_ind, const int64_t* d_gold, int64_t n, int cols, int64_t* d_hist);
 
+/* Exact ranks of gold targets against the WHOLE index: mean rank, mean reciprocal rank and hits@k beyond any neighbour list (a list
+ * ends at 4096 neighbours).  d_gold[r] = the index row that is the gold answer of query row q_begin + r, INT64_MIN = no gold row
+ * (kz_hit_positions' convention); d_gold and d_rank: [q_count] on the device.
+ * d_rank[r] = the number of index rows kz_knn orders BEFORE the gold row -- by the exact float64 ranking value ascending, ties by
+ * smaller index row, NaN values (correlation against a constant row, dice / sokalsneath between all-false rows) ranked as +inf by
+ * row, as the selection kernels have it -- i.e. the 0-based position of the gold row in kz_knn(query, index, k = index.n,
+ * exclude_self = 0), for any index.n; d_rank[r] = -1 where d_gold[r] is INT64_MIN or outside [0, index.n).
+ * The matrices must agree as for a search (dtype, metric, exponent, seuclidean V: KZ_ERR_INVALID otherwise).  No self-exclusion:
+ * the call is for two-sided data.  Runs the exact float64 value kernels of kz_knn for the rows that have a gold id (every metric)
+ * and a counting kernel in place of the selection; rows without gold cost no distance work.  Synchronises the context's stream. */
+int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                  const int64_t* d_gold, int64_t* d_rank);
+/* Reductions of a rank vector d_rank [n] (entries < 0: no rank).  h_hits[j] (host, j < n_k <= 64) = #(0 <= rank < h_ks[j]);
+ * h_out[3] (host) = #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1) -- the float64 sum in a fixed order. */
+int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* h_ks, int n_k, int64_t* h_hits, double* h_out);
+
 /* float64 -> float32 cast of an [count] array (cosine + float32 inputs keep the reference's output dtype). */
 int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count);
 

@@ -128,6 +128,8 @@ SYMBOLS = [
     ("kz_kocc_stats", C.c_int, [_P, _P, _I64, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     ("kz_kocc_select", C.c_int, [_P, _P, _I64, C.c_int, C.c_double, _P, C.POINTER(_I64)]),
     ("kz_hit_positions", C.c_int, [_P, _P, _P, _I64, C.c_int, _P]),
+    ("kz_gold_ranks", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
+    ("kz_rank_stats", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.c_int, C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_comm_destroy", C.c_int, [_P]),
@@ -371,6 +373,29 @@ def knn_dual(ctx: Context, a: DeviceMatrix, b: DeviceMatrix, k: int):
     _check(ctx.lib.kz_knn_dual(ctx.handle, a.handle, b.handle, int(k), d_ab.ptr, i_ab.ptr, d_ba.ptr, i_ba.ptr,
                                C.byref(s_ab), C.byref(s_ba)), "kz_knn_dual")
     return (d_ab, i_ab, s_ab.as_dict()), (d_ba, i_ba, s_ba.as_dict())
+
+
+def gold_ranks(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev: DeviceArray, q_begin: int = 0,
+               q_count: Optional[int] = None) -> DeviceArray:
+    """kz_gold_ranks -> int64 [q_count] on the device: the 0-based rank of index row gold_dev[r] for query row q_begin + r against
+    the whole index (the position it holds in kz_knn with k = index.n), -1 where gold_dev[r] is INT64_MIN or no index row."""
+    if q_count is None:
+        q_count = query.shape[0] - q_begin
+    if gold_dev.dtype != np.int64 or gold_dev.shape != (q_count,):
+        raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
+    rank = ctx.empty((q_count,), np.int64)
+    _check(ctx.lib.kz_gold_ranks(ctx.handle, query.handle, q_begin, q_count, index.handle, gold_dev.ptr, rank.ptr), "kz_gold_ranks")
+    return rank
+
+
+def rank_stats(ctx: Context, rank: DeviceArray, ks):
+    """kz_rank_stats -> ([#(0 <= rank < k) for k in ks], #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1)) of an int64 rank vector."""
+    n_k = len(ks)
+    h_ks = (_I64 * max(n_k, 1))(*[int(k) for k in ks])
+    h_hits = (_I64 * max(n_k, 1))()
+    h_out = (C.c_double * 3)()
+    _check(ctx.lib.kz_rank_stats(ctx.handle, rank.ptr, rank.shape[0], h_ks, n_k, h_hits, h_out), "kz_rank_stats")
+    return [int(h_hits[j]) for j in range(n_k)], int(h_out[0]), float(h_out[1]), float(h_out[2])
 
 
 def split_self(ctx: Context, dist: DeviceArray, ind: DeviceArray, row0: int = 0):

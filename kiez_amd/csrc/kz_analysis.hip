@@ -177,6 +177,49 @@ __global__ void kz_hit_positions_kernel(const int64_t* __restrict__ ind, const i
     atomicAdd(hist + pos, 1ull);
 }
 
+// Reductions of a rank vector (kz_gold_ranks; kiez_amd/evaluate.py: rank_metrics), entries < 0 = no rank.  Workgroup j < n_k:
+// out[j] = #(0 <= rank < ks[j]); workgroup n_k: out[n_k] = #(rank >= 0), out[n_k + 1] = sum(rank + 1) (both integers),
+// out[n_k + 2] = the bits of the float64 sum of 1 / (rank + 1).  One workgroup per quantity, every thread a strided partial sum, then
+// a tree of fixed shape: the float64 sum is the same from run to run.
+__global__ __launch_bounds__(256) void kz_rank_stats_kernel(const long long* __restrict__ rank, int64_t n, const long long* __restrict__ ks,
+                                                            int n_k, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_c[256], s_s[256];
+    __shared__ double s_r[256];
+    const int tid = threadIdx.x, j = blockIdx.x;
+    const bool sums = j == n_k;
+    const long long kk = sums ? 0x7fffffffffffffffLL : ks[j];
+    unsigned long long c = 0, s = 0;
+    double r = 0.0;
+    for (int64_t i = tid; i < n; i += 256) {
+        const long long x = rank[i];
+        if (x < 0 || x >= kk) continue;
+        c += 1ull;
+        if (sums) {
+            s += (unsigned long long)x + 1ull;
+            r += 1.0 / (double)(x + 1);
+        }
+    }
+    s_c[tid] = c;
+    s_s[tid] = s;
+    s_r[tid] = r;
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+        if (tid < off) {
+            s_c[tid] += s_c[tid + off];
+            s_s[tid] += s_s[tid + off];
+            s_r[tid] += s_r[tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out[j] = s_c[0];
+        if (sums) {
+            out[n_k + 1] = s_s[0];
+            out[n_k + 2] = (unsigned long long)__double_as_longlong(s_r[0]);
+        }
+    }
+}
+
 // ---- self-test of kz_div_shared (kz_common.h): pseudo-random pairs, the bits of the shared-reciprocal quotient against a / b ----
 __device__ __forceinline__ unsigned long long kz_mix64(unsigned long long z) {   // (splitmix64 finaliser)
     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -216,6 +259,27 @@ int kz_hit_positions(kz_ctx* ctx, const int64_t* d_ind, const int64_t* d_gold, i
     hipLaunchKernelGGL(kz_hit_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_ind, d_gold, n, cols,
                        (unsigned long long*)d_hist);
     KZ_HIP(hipGetLastError());
+    return KZ_OK;
+}
+
+int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* h_ks, int n_k, int64_t* h_hits, double* h_out) {
+    KZ_REQUIRE(ctx && d_rank && h_out && n > 0 && n_k >= 0 && n_k <= 64 && (n_k == 0 || (h_ks && h_hits)), "kz_rank_stats: bad argument");
+    KZ_HIP(hipSetDevice(ctx->device));
+    void* scratch = nullptr;
+    int rc = kz_scratch(ctx, 2048, &scratch);
+    if (rc != KZ_OK) return rc;
+    long long* d_ks = (long long*)scratch;                          // [64]
+    unsigned long long* d_out = (unsigned long long*)scratch + 64;  // [n_k + 3]
+    if (n_k) KZ_HIP(hipMemcpyAsync(d_ks, h_ks, (size_t)n_k * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(kz_rank_stats_kernel, dim3(n_k + 1), dim3(256), 0, ctx->stream, (const long long*)d_rank, n, d_ks, n_k, d_out);
+    KZ_HIP(hipGetLastError());
+    unsigned long long h[67];
+    KZ_HIP(hipMemcpyAsync(h, d_out, (size_t)(n_k + 3) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    for (int j = 0; j < n_k; ++j) h_hits[j] = (int64_t)h[j];
+    h_out[0] = (double)h[n_k];       // # ranked
+    h_out[1] = (double)h[n_k + 1];   // sum (rank + 1)
+    memcpy(&h_out[2], &h[n_k + 2], 8);   // sum 1 / (rank + 1)
     return KZ_OK;
 }
 

@@ -3390,4 +3390,5 @@ extern "C" int kz_knn(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int6
                        KzResearch(), d_dist, d_ind, stats, nullptr);
 }
 
+#include "kz_gold_ranks.h"
 #include "kz_knn_dual.h"

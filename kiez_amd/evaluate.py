@@ -45,6 +45,47 @@ def _gold_vector(gold: Dict[Any, Any], n_rows: int) -> np.ndarray:
     return out
 
 
+def _rank_stats(ranks, ks: List[int], ctx: Optional[N.Context]):
+    """([#(0 <= rank < k) for k in ks], #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1)) of a rank vector, reduced on the device."""
+    if isinstance(ranks, N.DeviceArray):
+        if ranks.dtype != np.int64 or len(ranks.shape) != 1:
+            raise ValueError("ranks must be a one-dimensional int64 vector")
+        ctx, rank_dev = ranks.ctx, ranks
+    else:
+        arr = np.asarray(ranks)
+        if arr.ndim != 1 or not (np.issubdtype(arr.dtype, np.integer) or arr.size == 0):
+            raise ValueError("ranks must be a one-dimensional integer vector")
+        if arr.size == 0:
+            return [0] * len(ks), 0, 0.0, 0.0
+        ctx = ctx or N.Context.get()
+        rank_dev = ctx.to_device(arr.astype(np.int64))
+    if rank_dev.shape[0] == 0:
+        return [0] * len(ks), 0, 0.0, 0.0
+    return N.rank_stats(ctx, rank_dev, ks)
+
+
+def rank_metrics(ranks: Union[np.ndarray, list, "N.DeviceArray"], gold, k=None, ctx: Optional[N.Context] = None) -> Dict[str, Any]:
+    """hits@k, mean rank and mean reciprocal rank from the exact ranks of the gold targets (`Kiez.gold_ranks`,
+    `SklearnNN.gold_ranks_device`: 0-based, -1 = the row has no rank), for every k in `k` (default [1, 5, 10]) -- any k, also
+    beyond the longest neighbour list a search returns.
+
+    `gold` is what `gold_ranks` was given: the dict of `hits` (every pair counts, also one whose key is no query row) or the array
+    with -1 for rows without gold.  Returns {"hits": {k: #(0 <= rank < k) / n_gold}, "mr": mean(rank + 1), "mrr": mean(1 / (rank + 1)),
+    "n_ranked": ..., "n_gold": ...}: `hits` has the denominator of `evaluate.hits`, len(gold), so the two agree wherever a list is
+    long enough to hold the answer; `mr` and `mrr` average over the n_ranked pairs that have a rank (nan when there is none).
+    The rank vector is reduced on the device (kz_rank_stats); only the scalars come to the host."""
+    if k is None:
+        k = [1, 5, 10]
+    k = sorted(k)
+    n_gold = len(gold) if isinstance(gold, dict) else int(np.count_nonzero(np.asarray(gold) >= 0))
+    int64_max = int(np.iinfo(np.int64).max)
+    counts, n_ranked, sum_pos, sum_rec = _rank_stats(ranks, [min(max(int(kk), 0), int64_max) for kk in k], ctx)
+    return {"hits": {kk: (c / n_gold if n_gold else 0.0) for kk, c in zip(k, counts)},
+            "mr": sum_pos / n_ranked if n_ranked else float("nan"),
+            "mrr": sum_rec / n_ranked if n_ranked else float("nan"),
+            "n_ranked": n_ranked, "n_gold": n_gold}
+
+
 def hits(nn_ind: Union[np.ndarray, list, Dict[Any, List], "N.DeviceArray"], gold: Dict[Any, Any], k=None,
          ctx: Optional[N.Context] = None) -> Dict[int, float]:
     """Relative hits@k for every k in `k` (default [1, 5, 10]); same semantics as the reference."""

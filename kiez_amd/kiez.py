@@ -100,3 +100,9 @@ class Kiez:
     def kneighbors(self, k: Optional[int] = None, return_distance: bool = True):
         dist, ind = self.hubness.kneighbors(k)
         return (dist, ind) if return_distance else ind
+
+    def gold_ranks(self, gold, s_to_t: bool = True):
+        """Exact 0-based rank of every source row's gold target against the whole target index, under the SEARCH METRIC -- not
+        under the hubness-reduced distances, which exist for the `n_candidates` nearest rows only (`SklearnNN.gold_ranks`;
+        `evaluate.rank_metrics` turns the ranks into hits@k, mean rank and mean reciprocal rank)."""
+        return self.algorithm.gold_ranks(gold, s_to_t=s_to_t)

@@ -1,0 +1,232 @@
+"""Exact gold ranks on the device (kz_gold_ranks, kz_rank_stats, SklearnNN / Kiez.gold_ranks, evaluate.rank_metrics): the rank is
+the position the gold row holds in the full-length search, for every class of metric, at the value launchers' tile edges, beyond
+the longest list a search returns, over more rows than one batch of values holds, with ties and NaN values -- and it is what the
+reference's full-length lists say (tests/golden/full_ranks.npz).  The reference has no such call: it reaches a rank through
+SklearnNN(n_candidates = n_target) and kiez.evaluate.hits (eval_metrics.py:23-61).  `pytest -m gpu`."""
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from tests import rank_restate as RR
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = Path(__file__).resolve().parent / "golden" / "full_ranks.npz"
+NO_GOLD = RR.NO_GOLD
+
+
+@pytest.fixture()
+def ctx():
+    from kiez_amd import _native as N
+    return N.Context.get()
+
+
+def _ranks(ctx, qm, ym, gold, q_begin=0, q_count=None):
+    from kiez_amd import _native as N
+    return N.gold_ranks(ctx, qm, ym, ctx.to_device(np.asarray(gold, dtype=np.int64)), q_begin, q_count).numpy()
+
+
+def _all_pair_values(ctx, qm, ym):
+    """[n_q, n_i] float64: kz_pair_values of every pair -- the values the search ranks by."""
+    from kiez_amd import _native as N
+    n_q, n_i = qm.shape[0], ym.shape[0]
+    ind = ctx.to_device(np.tile(np.arange(n_i, dtype=np.int64), (n_q, 1)))
+    val = ctx.empty((n_q, n_i), np.float64)
+    N._check(ctx.lib.kz_pair_values(ctx.handle, qm.handle, 0, n_q, ym.handle, ind.ptr, n_i, val.ptr), "kz_pair_values")
+    return val.numpy()
+
+
+def _continuous(rng, n, d, dtype):
+    return rng.standard_normal((n, d)).astype(dtype)
+
+
+def _small_ints(rng, n, d, dtype):
+    return rng.integers(0, 3, (n, d)).astype(dtype)
+
+
+def _booleans(rng, n, d, dtype):
+    return (rng.random((n, d)) < 0.4).astype(dtype)
+
+
+# (name, metric, dtype, data, special rows)
+CLASSES = [
+    ("euclidean_f32", "euclidean", np.float32, _continuous, None),
+    ("euclidean_f64", "euclidean", np.float64, _continuous, None),
+    ("cosine_f32", "cosine", np.float32, _continuous, None),
+    ("cosine_f64", "cosine", np.float64, _continuous, None),
+    ("sqeuclidean", "sqeuclidean", np.float32, _continuous, None),
+    ("manhattan", "manhattan", np.float32, _continuous, None),
+    ("minkowski3_f32", "minkowski[3.0]", np.float32, _continuous, None),
+    ("correlation_constant_row", "correlation", np.float64, _continuous, "constant"),
+    ("hamming_small_ints", "hamming", np.float32, _small_ints, None),
+    ("jaccard", "jaccard", np.float32, _booleans, None),
+    ("dice_all_false_rows", "dice", np.float32, _booleans, "all_false"),
+]
+
+
+@pytest.mark.parametrize("name,metric,dtype,data,special", CLASSES, ids=[c[0] for c in CLASSES])
+def test_rank_is_the_position_in_the_full_length_search(ctx, name, metric, dtype, data, special):
+    """n_index at the launchers' tile edges and at the largest k a search returns: rank == position of the gold id in
+    kz_knn(k = n_index), and == the restatement's count over kz_pair_values of all pairs (ties and NaN included: the restatement
+    orders by (value, row) as the kernels do)."""
+    from kiez_amd import _native as N
+    n_q = 37
+    for d in (3, 64, 300):
+        for n_i in (1, 63, 64, 65, 257, 4096):
+            rng = np.random.default_rng(1000 * d + n_i)
+            q, y = data(rng, n_q, d, dtype), data(rng, n_i, d, dtype)
+            gold = rng.integers(0, n_i, n_q).astype(np.int64)
+            if special == "constant":          # a constant index row: correlation against it is NaN, ranked as +inf by row
+                y[n_i // 2] = 1.5
+                gold[:3] = n_i // 2
+            if special == "all_false":         # 0 / 0 between all-false rows
+                y[n_i // 2] = 0.0
+                y[n_i - 1] = 0.0
+                q[0] = 0.0
+                q[1] = 0.0
+                gold[0], gold[1] = n_i - 1, n_i // 2
+            qm, ym = N.DeviceMatrix(ctx, q, metric), N.DeviceMatrix(ctx, y, metric)
+            rank = _ranks(ctx, qm, ym, gold)
+            _, ind, _ = N.knn(ctx, qm, ym, n_i)
+            where = f"{name} d={d} n_index={n_i}"
+            np.testing.assert_array_equal(rank, RR.positions(ind.numpy(), gold), err_msg=where)
+            np.testing.assert_array_equal(rank, RR.gold_ranks(_all_pair_values(ctx, qm, ym), gold), err_msg=where)
+
+
+@pytest.mark.parametrize("n_i", [4097, 9000])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_beyond_a_lists_reach_and_beyond_one_chunk(ctx, n_i, dtype):
+    from kiez_amd import _native as N
+    rng = np.random.default_rng(n_i)
+    q, y = _continuous(rng, 37, 8, dtype), _continuous(rng, n_i, 8, dtype)
+    gold = rng.integers(0, n_i, 37).astype(np.int64)
+    gold[0], gold[1] = 0, n_i - 1              # the first and the last value of a row
+    # rows 2 and 3: the farthest and the second farthest index row (float64 numpy; the gaps at the far end are many orders above
+    # the rounding of either side), ranks n_i - 1 and n_i - 2 -- with 4 097 index rows the only two ranks no list reaches or just reaches
+    far = np.argsort(((q[2:4].astype(np.float64)[:, None, :] - y.astype(np.float64)[None, :, :]) ** 2).sum(axis=2), axis=1)
+    gold[2], gold[3] = far[0, -1], far[1, -2]
+    qm, ym = N.DeviceMatrix(ctx, q, "euclidean"), N.DeviceMatrix(ctx, y, "euclidean")
+    rank = _ranks(ctx, qm, ym, gold)
+    np.testing.assert_array_equal(rank, RR.gold_ranks(_all_pair_values(ctx, qm, ym), gold))
+    assert rank[2] == n_i - 1 and rank[3] == n_i - 2
+    assert rank.max() >= 4096                  # some gold row lies beyond any list
+    _, ind, _ = N.knn(ctx, qm, ym, 4096)
+    pos = RR.positions(ind.numpy(), gold)
+    np.testing.assert_array_equal(pos, np.where(rank < 4096, rank, -1))
+
+
+def test_more_rows_than_one_batch(ctx):
+    """70 000 index rows: 479 rows of values per batch, 1 000 query rows, a third of them without gold."""
+    from kiez_amd import _native as N
+    rng = np.random.default_rng(7)
+    n_q, n_i, d = 1000, 70_000, 8
+    q, y = _continuous(rng, n_q, d, np.float32), _continuous(rng, n_i, d, np.float32)
+    gold = rng.integers(0, n_i, n_q).astype(np.int64)
+    gold[::3] = NO_GOLD
+    gold[1], gold[4], gold[998] = n_i, -7, n_i + 12345          # out of range
+    missing = (gold < 0) | (gold >= n_i)
+    assert (~missing).sum() > 479
+    qm, ym = N.DeviceMatrix(ctx, q, "euclidean"), N.DeviceMatrix(ctx, y, "euclidean")
+    rank = _ranks(ctx, qm, ym, gold)
+    np.testing.assert_array_equal(rank == -1, missing)
+    assert (rank[~missing] >= 0).all() and (rank < n_i).all()
+    halves = np.concatenate([_ranks(ctx, qm, ym, gold[:500], 0, 500), _ranks(ctx, qm, ym, gold[500:], 500, 500)])
+    np.testing.assert_array_equal(halves, rank)
+    np.testing.assert_array_equal(_ranks(ctx, qm, ym, gold), rank)          # (and the same from call to call)
+    rows = np.flatnonzero(~missing)[[0, 1, 2, 300, 478, 479, 480, 600, -2, -1]]      # both batches, and their edge
+    vals = ((q[rows].astype(np.float64)[:, None, :] - y.astype(np.float64)[None, :, :]) ** 2).sum(axis=2)
+    np.testing.assert_array_equal(rank[rows], RR.gold_ranks(vals, gold[rows]))
+
+
+@pytest.mark.parametrize("metric,dtype", [("euclidean", np.float32), ("cosine", np.float64), ("manhattan", np.float32)])
+def test_duplicated_index_rows(ctx, metric, dtype):
+    """The gold is the later copy of a duplicated index row: the earlier copy counts before it, and nothing else does."""
+    from kiez_amd import _native as N
+    rng = np.random.default_rng(3)
+    y = _continuous(rng, 500, 12, dtype)
+    y[400] = y[10]
+    y[450] = y[10]
+    q = np.repeat(y[10][None, :], 3, axis=0) + (1e-3 * rng.standard_normal((3, 12))).astype(dtype)
+    qm, ym = N.DeviceMatrix(ctx, q, metric), N.DeviceMatrix(ctx, y, metric)
+    np.testing.assert_array_equal(_ranks(ctx, qm, ym, [10, 400, 450]), [0, 1, 2])
+
+
+def test_mismatched_matrices_and_empty_calls(ctx):
+    from kiez_amd import _native as N
+    rng = np.random.default_rng(5)
+    q, y = _continuous(rng, 10, 4, np.float32), _continuous(rng, 20, 4, np.float32)
+    qm, ym = N.DeviceMatrix(ctx, q, "euclidean"), N.DeviceMatrix(ctx, y, "euclidean")
+    with pytest.raises(ValueError, match="different metrics"):
+        _ranks(ctx, N.DeviceMatrix(ctx, q, "cosine"), ym, np.zeros(10))
+    with pytest.raises(ValueError, match="same dtype"):
+        _ranks(ctx, N.DeviceMatrix(ctx, q.astype(np.float64), "euclidean"), ym, np.zeros(10))
+    with pytest.raises(ValueError, match="out of bounds"):
+        _ranks(ctx, qm, ym, np.zeros(10), 5, 10)
+    np.testing.assert_array_equal(_ranks(ctx, qm, ym, np.full(10, NO_GOLD)), np.full(10, -1))
+    assert _ranks(ctx, qm, ym, np.zeros(0), 3, 0).shape == (0,)
+
+
+def test_rank_stats_on_the_device(ctx):
+    from kiez_amd import _native as N
+    rng = np.random.default_rng(11)
+    ranks = rng.integers(0, 100_000, 5000).astype(np.int64)
+    ranks[rng.random(5000) < 0.3] = -1
+    ks = [0, 1, 10, 4096, 50_000, 2 ** 62]
+    dev = ctx.to_device(ranks)
+    got = N.rank_stats(ctx, dev, ks)
+    want = RR.rank_stats(ranks, ks)
+    assert got[0] == want[0] and got[1] == want[1] and got[2] == want[2]
+    assert got[3] == pytest.approx(want[3], rel=1e-13)          # (5 000 float64 terms in another order)
+    assert N.rank_stats(ctx, dev, ks) == got                     # fixed order: the same bits every time
+    assert N.rank_stats(ctx, ctx.to_device(np.array([-1], dtype=np.int64)), []) == ([], 0, 0.0, 0.0)
+
+
+@pytest.mark.parametrize("hubness", [None, "CSLS"])
+def test_golden_from_the_reference(hubness):
+    """Kiez.fit(source, target).gold_ranks(gold) = the positions in the reference's full-length lists, whatever the hubness
+    reduction (ranks are under the search metric); rank_metrics = the reference's hits on those lists."""
+    from kiez_amd import Kiez, evaluate
+    g = np.load(GOLDEN)
+    source, target = g["source"], g["target"]
+    gold = {int(a): int(b) for a, b in zip(g["gold_keys"], g["gold_vals"])}
+    gold_vec = evaluate._gold_vector(gold, source.shape[0])
+    ks = [int(k) for k in g["ks"]]
+    for metric in g["metrics"]:
+        kz = Kiez(n_candidates=10, algorithm="SklearnNN", algorithm_kwargs={"metric": str(metric)}, hubness=hubness)
+        ranks = kz.fit(source, target).gold_ranks(gold)
+        pos = RR.positions(g[f"{metric}__ind"].astype(np.int64), gold_vec)
+        assert ranks.dtype == np.int64
+        np.testing.assert_array_equal(ranks, pos)
+        np.testing.assert_array_equal(kz.gold_ranks(np.where(gold_vec == NO_GOLD, -1, gold_vec)), pos)      # array form, -1 = none
+        m = evaluate.rank_metrics(ranks, gold, k=ks)
+        np.testing.assert_array_equal([m["hits"][k] for k in ks], g[f"{metric}__hits"])
+        have = pos[pos >= 0]
+        assert m["n_ranked"] == have.size and m["n_gold"] == len(gold)
+        assert m["mr"] == pytest.approx((have + 1).mean(), rel=1e-15) and m["mrr"] == pytest.approx((1.0 / (have + 1)).mean(), rel=1e-14)
+        # the device vector, reduced where it lies
+        md = evaluate.rank_metrics(kz.algorithm.gold_ranks_device(gold), gold, k=ks)
+        assert md == m
+    # the other direction: target rows against the indexed source (a hubness reduction indexes both sides)
+    if hubness is not None:
+        back = {b: a for a, b in gold.items() if a < source.shape[0]}
+        rb = kz.gold_ranks(back, s_to_t=False)
+        vals = 1.0 - (target / np.linalg.norm(target, axis=1)[:, None]) @ (source / np.linalg.norm(source, axis=1)[:, None]).T
+        np.testing.assert_array_equal(rb, RR.gold_ranks(vals, evaluate._gold_vector(back, target.shape[0])))
+
+
+def test_agreement_with_hits():
+    """Where a list is long enough to hold the answer, hits from ranks = hits from the list."""
+    from kiez_amd import Kiez, evaluate
+    rng = np.random.default_rng(21)
+    source = rng.standard_normal((300, 16)).astype(np.float32)
+    target = np.concatenate([source + 0.6 * rng.standard_normal((300, 16)).astype(np.float32),
+                             rng.standard_normal((100, 16)).astype(np.float32)])
+    gold = {i: i for i in range(0, 300, 2)}
+    gold[1000] = 3                                      # no such source row: denominator only
+    kz = Kiez(n_candidates=10, algorithm="SklearnNN", algorithm_kwargs={"metric": "euclidean"}, hubness=None).fit(source, target)
+    _, ind = kz.kneighbors(10)
+    from_list = evaluate.hits(ind, gold, k=[1, 5, 10])
+    from_rank = evaluate.rank_metrics(kz.gold_ranks(gold), gold, k=[1, 5, 10])
+    assert from_rank["hits"] == from_list
+    assert 0.0 < from_list[1] < from_list[10] < 1.0     # (the data decides something)
