@@ -55,7 +55,7 @@ static inline bool kz_bool_self_zero(const kz_matrix* query, const kz_matrix* in
 // kz_matrix_create: the bit image and the row counts of a matrix created for a boolean metric (enqueued on the context's stream)
 int kz_bool_image(kz_matrix* m);
 void kz_bool_image_free(kz_matrix* m);
-// the exact route's distance step: the [nb][n_i] float64 value matrix of the queries fail_list[b0 .. b0 + nb) (kz_knn.hip)
+// the exact route's distance step: the [nb][n_i] float64 value matrix of the queries fail_list[b0 .. b0 + nb) (kz_exact.h: kz_exact_distances)
 void kz_bool_launch_dist(kz_ctx* ctx, const int* fail_list, int b0, int nb, int64_t q_begin, const kz_matrix* query, const kz_matrix* index,
                          double* vals);
 // kz_pair_values of the boolean metrics: one lane per pair over the packed rows

@@ -6,12 +6,12 @@
 //     rank = #{ j : v_j < v_g  or  (v_j == v_g and j < g) }
 // = the 0-based position of g in kz_knn(query, index, k = index.n, exclude_self = 0): the order of kz_exact_select_kernel, ties by
 // smaller index row, NaN (correlation against a constant row, dice / sokalsneath between all-false rows) ranked as +inf by row.
-// No list, no limit on k, no n x n output.  This header is a second caller of the value launchers of the exact route (they are
-// static in kz_knn.hip, hence an include like kz_range.h); the route itself is not touched.
+// No list, no limit on k, no n x n output.  This header calls the distance function of the exact stage (kz_exact.h: static in
+// kz_knn.hip's translation unit, hence an include like kz_range.h).
 //   1. kz_rank_compact_kernel: the rows with a gold id inside [0, index.n), in row order, as a row list of the fail_list kind (int
 //      rows relative to q_begin); d_rank = 0 for them, -1 for every other row.  One count comes back to the host.  Rows without gold
 //      cost no distance work.
-//   2. per batch of listed rows (256 MiB of values, kz_scratch): the launchers the exact route calls for this metric and dtype;
+//   2. per batch of listed rows (kz_exact_batch_rows): kz_exact_distances -- the kernel the exact stage runs for this metric and dtype;
 //   3. kz_rank_count_kernel: one workgroup per (chunk of the index row range, listed row) counts its chunk and adds ONE integer to
 //      the row's d_rank entry -- integer counting: the result does not depend on the order the workgroups run in.
 // Reference: the n_s x n_t neighbour matrix of SklearnNN(n_candidates = n_target) followed by kiez.evaluate.hits
@@ -108,14 +108,10 @@ extern "C" int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_be
     // (the matrices are logically const for the caller: cosine attaches the lazily built normalised rows to the index, as kz_knn does)
     kz_matrix* query = const_cast<kz_matrix*>(query_c);
     kz_matrix* index = const_cast<kz_matrix*>(index_c);
-    KZ_REQUIRE(ctx && query && index && d_gold && d_rank, "kz_gold_ranks: null argument");
-    KZ_REQUIRE(query->ctx == ctx && index->ctx == ctx, "kz_gold_ranks: matrices belong to a different context");
-    KZ_REQUIRE(!query->raw_only && !index->raw_only, "kz_gold_ranks: a rows-only matrix (kz_matrix_create rows_on_device = 3) cannot be searched");
-    KZ_REQUIRE(query->d == index->d, "kz_gold_ranks: feature dimensions differ (%lld vs %lld)", (long long)query->d, (long long)index->d);
-    KZ_REQUIRE(query->dtype == index->dtype, "kz_gold_ranks: query and index must have the same dtype");
-    KZ_REQUIRE(query->metric == index->metric && query->mink_p == index->mink_p, "kz_gold_ranks: query and index were packed for different metrics");
-    KZ_REQUIRE(kz_metric_params_match(query, index), "kz_gold_ranks: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index");
-    KZ_REQUIRE(q_begin >= 0 && q_count >= 0 && q_begin + q_count <= query->n, "kz_gold_ranks: query row range out of bounds");
+    {
+        const int rcp = kz_require_pair("kz_gold_ranks", ctx, query, q_begin, q_count, index, d_gold, d_rank);
+        if (rcp != KZ_OK) return rcp;
+    }
     KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "kz_gold_ranks: more than 2^31 - 1 rows");
     if (q_count == 0) return KZ_OK;
     KZ_HIP(hipSetDevice(ctx->device));
@@ -130,50 +126,18 @@ extern "C" int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_be
     KZ_HIP(hipStreamSynchronize(ctx->stream));
     if (n_list == 0) return KZ_OK;
 
-    // from here on: the exact route of kz_knn_impl ("exact brute force in batches"), the count in place of the selection
-    const int metric = index->metric;
-    const bool no_gemm_form = index->metric >= KZ_MANHATTAN;
-    if (metric == KZ_COSINE && n_list >= 64 && ctx->exact_rows) {   // (many rows: the normalised float64 index rows, once)
-        rc = kz_matrix_norm64(index);
-        if (rc != KZ_OK) return rc;
-    }
-    int64_t batch = ((int64_t)256 << 20) / (index->n * 8);
-    if (batch < 1) batch = 1;
-    if (batch > n_list) batch = n_list;
-    if (batch > 65535) batch = 65535;
-    void* vals = nullptr;
-    rc = kz_scratch(ctx, (size_t)batch * (size_t)index->n * 8, &vals);
+    // the value matrix of the exact stage (kz_exact.h), batch by batch; the count in place of its selection
+    rc = kz_exact_prepare_index(ctx, index, n_list);
     if (rc != KZ_OK) return rc;
-    const int dist_blocks = (int)((index->n + 3) / 4);
+    int batch = 0;
+    double* vals = nullptr;
+    rc = kz_exact_batch_rows(ctx, index, n_list, &batch, &vals);
+    if (rc != KZ_OK) return rc;
     const int n_chunks = (int)((index->n + KZ_RANK_CHUNK - 1) / KZ_RANK_CHUNK);
-    for (int b0 = 0; b0 < n_list; b0 += (int)batch) {
-        const int nb = (n_list - b0 < batch) ? (n_list - b0) : (int)batch;
-        if (index->dtype == KZ_F32) {
-            bool lanes = false;
-            if (!no_gemm_form) {
-                rc = kz_launch_exact_lanes(ctx, fl.get(), b0, nb, q_begin, query, index, metric, (double*)vals, &lanes);
-                if (rc != KZ_OK) return rc;
-            }
-            if (lanes) {
-            } else if (kz_is_bool_metric(index->metric))
-                kz_bool_launch_dist(ctx, fl.get(), b0, nb, q_begin, query, index, (double*)vals);
-            else if (no_gemm_form)
-                kz_launch_family_dist<float>(ctx, fl.get(), b0, nb, q_begin, query, index, (double*)vals);
-            else if (ctx->exact_rows && kz_launch_exact_rows(ctx, fl.get(), b0, nb, q_begin, query, index, metric, (double*)vals)) {
-            } else
-                hipLaunchKernelGGL(kz_exact_dist_kernel<float>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl.get(), b0, q_begin,
-                                   (const float*)query->raw, (const float*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric,
-                                   index->mink_p, (double*)vals);
-        } else {
-            if (kz_is_bool_metric(index->metric))
-                kz_bool_launch_dist(ctx, fl.get(), b0, nb, q_begin, query, index, (double*)vals);
-            else if (no_gemm_form)
-                kz_launch_family_dist<double>(ctx, fl.get(), b0, nb, q_begin, query, index, (double*)vals);
-            else
-                hipLaunchKernelGGL(kz_exact_dist_kernel<double>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl.get(), b0, q_begin,
-                                   (const double*)query->raw, (const double*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric,
-                                   index->mink_p, (double*)vals);
-        }
+    for (int b0 = 0; b0 < n_list; b0 += batch) {
+        const int nb = n_list - b0 < batch ? n_list - b0 : batch;
+        rc = kz_exact_distances(ctx, fl.get(), b0, nb, q_begin, query, index, vals);
+        if (rc != KZ_OK) return rc;
         hipLaunchKernelGGL(kz_rank_count_kernel, dim3(n_chunks, nb), dim3(256), 0, ctx->stream, (const double*)vals, index->n, fl.get(), b0,
                            d_gold, d_rank);
     }

@@ -5,10 +5,11 @@
 // Three stages (DESIGN.md "Kernels"):
 //   1. kz_knn_cand_kernel   fused  X.Y^T (float32 MFMA 32x32x2)  +  per-query top-K' candidate lists.
 //                           The n_q x n_i similarity matrix never leaves registers.
-//   2. kz_knn_finalize      merge the lists, CERTIFY that the true top-k is inside the candidate set using a
+//   2. kz_knn_finalize      (kz_knn_finalize.h) merge the lists, CERTIFY that the true top-k is inside the candidate set using a
 //                           rigorous float32 rounding bound, re-rank the K' candidates with exact float64
 //                           distances, sort, strip the query itself (single-source mode), write [q, k].
-//   3. kz_exact_*           exact float64 brute force for the (rare) rows that could not be certified.
+//   3. kz_exact_*           (kz_exact.h) exact float64 brute force for the (rare) rows that could not be certified.
+// This file: the float32-operand kernel, launch plumbing, the escalation helpers and the host ladder kz_knn_impl.
 // Result: neighbour order == order of the float64 distances the reference computes; no approximation.
 #include <vector>
 
@@ -195,128 +196,8 @@ __global__ __launch_bounds__(256, 3) void kz_knn_cand_kernel(KnnCandParams p) {
 
 #include "kz_knn_bf16.h"
 
-// ---------------------------------------------------------------------------------------------------
-// Stage 2: merge + certify + float64 re-rank
-// ---------------------------------------------------------------------------------------------------
+#include "kz_knn_finalize.h"
 
-struct KnnFinParams {
-    const float* in_key;  // [rows][M]
-    const int* in_idx;
-    KzListLayout lay;     // list layout (kz_list_base)
-    int max_m;            // largest entry count of a query in this launch (sizes the dynamic LDS)
-    int fast_div;         // cosine re-rank: y_k / |y| as kz_div_shared (one reciprocal per candidate row; same bits as the division)
-    int64_t q_first, q_last;  // local query range [q_first, q_last) handled by this launch
-    int KP;               // entries per list (per query and index range)
-    int KSEL;             // candidates the finalize kernel selects from a query's lists and re-ranks (0: = KP).  Larger than KP on the
-                          // long-k route (more than 110 neighbours: lists of 128 over many index ranges, kz_knn_impl)
-    int64_t list_row0;    // list row of local query 0  (= q_begin - qt0*128)
-    int64_t q_begin;      // global query row of local query 0
-    int64_t q_count;
-    const void* qraw;     // raw query rows (global row indexing)
-    const void* yraw;     // raw index rows
-    const double* ynorm64; // cosine, float32 rows: the index rows normalised in float64 (kz_matrix_norm64), or NULL
-    const double* qsqn;
-    const double* ysqn;
-    int64_t n_i;
-    int d;
-    int metric;
-    int k;                // neighbours to return
-    int exclude_self;
-    const int64_t* self_ids;  // optional: index row to strip per local query (escalated subsets); NULL = q_begin + q
-    double gamma;         // rounding-bound factor (already multiplied by eps_scale)
-    const double* ystats; // index matrix: [0] max row norm (device)
-    // fp16 first pass (kz_knn_h16.h): keys are in centred, scaled units; the bound uses the measured operand residuals
-    int tier_h;
-    double eps_mult;      // eps_scale (test knob)
-    double gamma_acc;     // float32 accumulation part of the bound
-    const double* q_rowq; // query image: [n][3] = |x_c|^2, |x_h|, |x_c - x_h|
-    const double* y_hmax; // index image: max |y_h|, max |y_c - y_h|, max |y_c|^2
-    const double* hscale; // {S, 1 / S^2}
-    // dual pass, reverse direction (kz_knn_dual.h): the list holds the K' best EVENTS of the row; rows outside the events
-    // have an approximate key below excl_floor[q] (+inf: the row's events are incomplete, it must fail)
-    const float* excl_floor;
-    // seeded lists (KnnCandParams::qfloor): [q_begin + q] the key the query's lists started from -- rows that never entered a list
-    // have an approximate key at or below it
-    const float* list_floor;
-    int dual_col;
-    const int* idx_map;   // dual pass, forward direction: list entry r stands for index row idx_map[r] (NULL: identity)
-    const int* row_map;   // dual pass, forward direction: the query image is permuted too -- image row r is matrix row row_map[r];
-                          // raw row, norms, residuals, the output position and the fail-list entry all go by the MATRIX row
-    double* out_dist;     // [q_count][k]
-    int64_t* out_ind;
-    int* fail_count;
-    int* fail_list;
-    double* fail_tau;     // optional, beside fail_list: the exact value of the row's k-th best CANDIDATE (+inf: fewer than k candidates) -- an
-                          // upper bound of its k-th neighbour's value whatever the tier: what the range re-search starts from (kz_range.h)
-    unsigned long long* err_ratio_bits;  // max over certified candidates of |key~ - key| / eps (bits of a non-negative double)
-};
-
-// (kz_exact_value: kz_common.h -- shared with kz_pair_values, which must reproduce the re-rank's values bit for bit)
-template <typename T>
-__device__ __forceinline__ double kz_output_distance(double v, int metric, double p = 2.0) {
-    // (Minkowski family: the ranking value is the reduced distance; scikit-learn converts at the end,
-    //  MinkowskiDistance._rdist_to_dist: rdist ** (1 / p), rounded to the input dtype -- measured on scikit-learn 1.7.2)
-    if (metric == KZ_MINKOWSKI) return sizeof(T) == 4 ? (double)(float)pow(v, 1.0 / p) : pow(v, 1.0 / p);
-    // (seuclidean: SEuclideanDistance._rdist_to_dist, sqrt of the ranking value -- already rounded to the input dtype -- rounded
-    //  again; correlation: the constant row's NaN, ranked as +inf (kz_family_finish), is NaN again)
-    if (metric == KZ_SEUCLIDEAN) return sizeof(T) == 4 ? (double)(float)sqrt(v) : sqrt(v);
-    if ((metric == KZ_CORRELATION || metric == KZ_DICE || metric == KZ_SOKALSNEATH) && v == INFINITY) return NAN;   // (dice, sokalsneath: kz_bool.h)
-    if (metric == KZ_EUCLIDEAN) {
-        // ArgKmin32 converts the surrogate with the float32 metric object: (double)sqrtf((float)d2)
-        // (_argkmin.pyx.tp:285-295 with INPUT_DTYPE_t = float32); ArgKmin64 uses sqrt in float64.
-        // exactly what sklearn executes: float32 argument, double sqrt, result rounded back to float32
-        if (sizeof(T) == 4) return (double)(float)sqrt((double)(float)v);
-        return sqrt(v);
-    }
-    return v;
-}
-
-// Writes the final k entries of one query from its (value, idx)-sorted prefix.  sorted arrays live in LDS.
-// sklearn self removal (neighbors/_base.py:947-965): among the first k+1, drop the entry whose index is the
-// query row; if it is absent drop the first one.
-template <typename T>
-__device__ __forceinline__ void kz_emit_sorted(const double* sval, const int* sidx, int n_sorted, int k, int exclude_self,
-                                               int64_t self_row, int metric, double* od, int64_t* oi, int lane, double p = 2.0) {
-    int self_rank = -1;
-    if (exclude_self) {
-        self_rank = 0;
-        const int lim = min(n_sorted, k + 1);
-        for (int c = 0; c < lim; ++c)
-            if ((int64_t)sidx[c] == self_row) {
-                self_rank = c;
-                break;
-            }
-    }
-    for (int c = lane; c < n_sorted; c += 64) {
-        if (c == self_rank) continue;
-        const int o = (self_rank >= 0 && c > self_rank) ? c - 1 : c;
-        if (o < k) {
-            od[o] = kz_output_distance<T>(sval[c], metric, p);
-            oi[o] = (int64_t)sidx[c];
-        }
-    }
-}
-
-// Gather parallelism of the finalize kernel: candidate rows per group (KZ_FIN_ROWS), groups in flight per wave (KZ_FIN_DEPTH:
-// 2 = one group ahead, 3 = two) and the occupancy the kernel is compiled for (KZ_FIN_WAVES).  Round 3, same box, average
-// launch on ns / C3 (tools/job_fin.sh): rows 4 depth 2 at 4 waves per SIMD (round 2's build, 112 VGPRs) 4.06 / 8.47 ms; rows 2
-// depth 3 at 5 waves (4 spilled) 3.57 / 7.60; rows 1 depth 2 at 7 waves (70 VGPRs, no spill) 3.03 / 7.37; rows 1 depth 3 at 7
-// (6 spilled) 3.14 / 7.25; rows 4 depth 3 at 3 waves 4.96 / 9.59.  Waves in flight beat rows in flight per wave: the phases
-// around the gather loop (list load, rank select, rank sort) of one query hide under the gathers of the other waves' queries.
-// Round 4 (the loads of the loop issued without branches, so that the prefetch overlaps at all; the per-query values in scalar
-// registers: 71 -> 59 VGPRs), finalize time over 4 steps of C3 + 4 of ns, reverse chain not overlapped: rows 1 depth 2 at 8 waves
-// 69.2 ms; rows 2 depth 2 at 7 (70 VGPRs) 69.1; rows 1 depth 3 at 7 69.5; **rows 1 depth 3 at 8 (64 VGPRs, no spill) 67.4**; rows 2
-// depth 3 at 6 72.9.  Round 5: the selection paths added since (unsorted path, radix selections) brought the 8-wave build to 8
-// spilled VGPRs; 7 waves (72 VGPRs, none spilled), same box, two runs each: ns 98.14 / 98.04 -> 97.56 / 97.16 ms per step, C3
-// 122.43 / 122.34 -> 122.19 / 121.87.
-#ifndef KZ_FIN_ROWS_N
-#define KZ_FIN_ROWS_N 1
-#endif
-#ifndef KZ_FIN_DEPTH
-#define KZ_FIN_DEPTH 3
-#endif
-constexpr int KZ_FIN_ROWS = KZ_FIN_ROWS_N;
-constexpr int KZ_FIN_MAXM = 4096;  // list entries per query: 4 waves x (4096*8 + 128*28) B = 142 KiB of LDS at most
 // Rows a K' = 16 pass could not certify: few (the usual handful) -> more lists of 16, it is all latency; many (hard data) -> lists
 // of 64, which certify more of them in one go (400k x 400k, k = 10, clusters of very different density: 140 against 112 ms)
 constexpr int KZ_ESC_SHORT_MAX_ROWS = 2048;
@@ -327,1512 +208,7 @@ static int kz_max_pieces(int KP, int halves) {
     return m < KZ_MAX_PIECES ? m : KZ_MAX_PIECES;
 }
 
-// Per-wave LDS of the finalize kernel for a launch whose queries hold at most max_m list entries.
-__host__ __device__ __forceinline__ int kz_fin_wave_bytes(int max_m, int KP) {
-    return ((max_m * 8 + KP * 28) + 15) & ~15;
-}
-// (the finalize kernel for many candidates shares bytes between arrays that are never live together: kz_knn_fin_wide.h)
-__host__ __device__ __forceinline__ int kz_fin_wide_wave_bytes(int max_m, int KS) {
-    return ((max_m * 8 + KS * 20) + 15) & ~15;
-}
-
-// k-th largest (rank = 1: the largest) of n float keys held as SORTABLE unsigned patterns in LDS; returns the pattern.
-// Wave-cooperative: 32 counting passes at most, fewer below the common prefix of the patterns.  The entries are read ONCE into
-// registers (E per lane, n <= 64 E): a counting pass is then E compares and E ballots, no LDS round trip in the dependent chain
-// bit -> count -> next bit (round 5: the finalize kernel for many candidates runs three such selections per query at three waves
-// per SIMD -- the chains, not the instruction count, were what it waited for).
-// Largest "smallest key of a FULL list" over a query's lists of KP = 16 or 32 entries, the entries held E per lane (entry e = lane +
-// 64 i): a list's entries sit in KP consecutive lanes of one i, so every list is reduced inside its lane group -- all lists of an
-// i at once, no loop over the lists (32 lists: 8 x 4 shuffle steps instead of 32 dependent rounds of 5).  -inf: no full list.
-template <int E>
-__device__ __forceinline__ float kz_full_lists_bound(const float (&key)[E], const bool (&ok)[E], int M, int KP, int lane) {
-    float bound = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-        if (64 * i >= M) break;   // (uniform)
-        int c = ok[i] ? 1 : 0;
-        float mn = ok[i] ? key[i] : INFINITY;
-        for (int off = KP >> 1; off >= 1; off >>= 1) {   // (uniform trip count: 4 or 5)
-            c += __shfl_xor(c, off, 64);
-            mn = fminf(mn, __shfl_xor(mn, off, 64));
-        }
-        if (c == KP && lane + 64 * i < M) bound = fmaxf(bound, mn);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) bound = fmaxf(bound, __shfl_xor(bound, off, 64));
-    return bound;
-}
-
-// (core: the lane's E patterns in registers; pattern 0 = no entry)
-template <int E>
-__device__ __forceinline__ unsigned kz_radix_kth_u32_regs(const unsigned (&x)[E], unsigned all_or, unsigned all_and, int rank) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        all_or |= __shfl_xor(all_or, off, 64);
-        all_and &= __shfl_xor(all_and, off, 64);
-    }
-    const unsigned differ = all_or ^ all_and;
-    const int top = differ ? 31 - __clz(differ) : -1;
-    unsigned thr = top >= 31 ? 0u : (top < 0 ? all_and : (all_and & ~((2u << top) - 1u)));
-    for (int bit = top; bit >= 0; --bit) {
-        const unsigned cand = thr | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int i = 0; i < E; ++i) c += (int)__popcll(__ballot(x[i] >= cand));
-        if (c >= rank) thr = cand;
-    }
-    return thr;
-}
-template <int E>
-__device__ __forceinline__ unsigned kz_radix_kth_u32_e(const unsigned* u, int n, int rank, int lane) {
-    unsigned x[E];
-    unsigned all_or = 0u, all_and = 0xffffffffu;
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-        const int e = lane + 64 * i;
-        const bool in = e < n;
-        x[i] = in ? u[e] : 0u;   // (pattern 0 is below every candidate threshold, which has at least one bit set)
-        all_or |= x[i];
-        all_and &= in ? x[i] : 0xffffffffu;
-    }
-    return kz_radix_kth_u32_regs<E>(x, all_or, all_and, rank);
-}
-// (the generic finalize kernel is compiled for 64 VGPRs: it keeps the LDS loops)
-template <bool REGS = false>
-__device__ __forceinline__ unsigned kz_radix_kth_u32(const unsigned* u, int n, int rank, int lane) {
-    if (REGS && n <= 256) return kz_radix_kth_u32_e<4>(u, n, rank, lane);
-    if (REGS && n <= 512) return kz_radix_kth_u32_e<8>(u, n, rank, lane);
-    unsigned all_or = 0u, all_and = 0xffffffffu;
-    for (int e = lane; e < n; e += 64) {
-        all_or |= u[e];
-        all_and &= u[e];
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        all_or |= __shfl_xor(all_or, off, 64);
-        all_and &= __shfl_xor(all_and, off, 64);
-    }
-    const unsigned differ = all_or ^ all_and;
-    const int top = differ ? 31 - __clz(differ) : -1;
-    unsigned thr = top >= 31 ? 0u : (top < 0 ? all_and : (all_and & ~((2u << top) - 1u)));
-    for (int bit = top; bit >= 0; --bit) {
-        const unsigned cand = thr | (1u << bit);
-        int c = 0;
-        for (int e0 = 0; e0 < n; e0 += 64) c += (int)__popcll(__ballot(e0 + lane < n && u[e0 + lane] >= cand));
-        if (c >= rank) thr = cand;
-    }
-    return thr;
-}
-// rank-th SMALLEST (rank = 1: the smallest) of n non-negative doubles in LDS (their bit patterns order like the values).
-template <int E>
-__device__ __forceinline__ unsigned long long kz_radix_kth_small_f64_e(const double* v, int n, int rank, int lane) {
-    unsigned long long x[E];
-    unsigned long long all_or = 0ull, all_and = ~0ull;
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-        const int e = lane + 64 * i;
-        const bool in = e < n;
-        x[i] = in ? (unsigned long long)__double_as_longlong(v[e]) : ~0ull;   // (the largest pattern: never BELOW a candidate)
-        all_or |= in ? x[i] : 0ull;
-        all_and &= x[i];
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        all_or |= __shfl_xor(all_or, off, 64);
-        all_and &= __shfl_xor(all_and, off, 64);
-    }
-    const unsigned long long differ = all_or ^ all_and;
-    const int top = differ ? 63 - __clzll(differ) : -1;
-    unsigned long long thr = top >= 63 ? 0ull : (top < 0 ? all_and : (all_and & ~((2ull << top) - 1ull)));
-    for (int bit = top; bit >= 0; --bit) {
-        const unsigned long long cand = thr | (1ull << bit);
-        int c = 0;   // entries below cand
-#pragma unroll
-        for (int i = 0; i < E; ++i) c += (int)__popcll(__ballot(x[i] < cand));
-        if (c < rank) thr = cand;
-    }
-    return thr;
-}
-template <bool REGS = false>
-__device__ __forceinline__ unsigned long long kz_radix_kth_small_f64(const double* v, int n, int rank, int lane) {
-    if (REGS && n <= 256) return kz_radix_kth_small_f64_e<4>(v, n, rank, lane);
-    unsigned long long all_or = 0ull, all_and = ~0ull;
-    for (int e = lane; e < n; e += 64) {
-        const unsigned long long b = (unsigned long long)__double_as_longlong(v[e]);
-        all_or |= b;
-        all_and &= b;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        all_or |= __shfl_xor(all_or, off, 64);
-        all_and &= __shfl_xor(all_and, off, 64);
-    }
-    const unsigned long long differ = all_or ^ all_and;
-    const int top = differ ? 63 - __clzll(differ) : -1;
-    // thr = the smallest value with at least `rank` entries <= it: build the largest prefix p such that fewer than `rank` entries are
-    // BELOW p, bit by bit from the top
-    unsigned long long thr = top >= 63 ? 0ull : (top < 0 ? all_and : (all_and & ~((2ull << top) - 1ull)));
-    for (int bit = top; bit >= 0; --bit) {
-        const unsigned long long cand = thr | (1ull << bit);
-        int c = 0;   // entries below cand
-        for (int e0 = 0; e0 < n; e0 += 64)
-            c += (int)__popcll(__ballot(e0 + lane < n && (unsigned long long)__double_as_longlong(v[e0 + lane]) < cand));
-        if (c < rank) thr = cand;
-    }
-    return thr;
-}
-
-// Rank-based selection of the KP best of M <= 64*E list entries (key descending, row ascending; entries with row < 0 are
-// empty).  Lane l holds entries l, l+64, ...; returns the number of entries written to ck/ci (ordered by rank).
-template <int E>
-__device__ __forceinline__ int kz_rank_select(const float* ekey, const int* eidx, int M, int KP, float* ck, int* ci, int lane) {
-    float x[E];
-    int xi[E], rank[E];
-#pragma unroll
-    for (int u = 0; u < E; ++u) {
-        const int e = lane + 64 * u;
-        x[u] = e < M ? ekey[e] : -INFINITY;
-        xi[u] = e < M ? eidx[e] : -1;
-        rank[u] = 0;
-    }
-    int n_valid = 0;
-#pragma unroll
-    for (int v = 0; v < E; ++v) {
-        n_valid += __popcll(__ballot(xi[v] >= 0));
-        const int lim = min(64, M - 64 * v);
-        for (int jj = 0; jj < lim; ++jj) {  // jj is wave-uniform: the broadcasts are v_readlane (spelled out: __shfl compiled to ds_bpermute)
-            const int oi = __builtin_amdgcn_readlane(xi[v], jj);
-            if (oi < 0) continue;   // (uniform)
-            const float ox = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(x[v]), jj));
-#pragma unroll
-            for (int u = 0; u < E; ++u)
-                if (64 * u < M) rank[u] += (ox > x[u] || (ox == x[u] && oi < xi[u])) ? 1 : 0;
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < E; ++u) {
-        if (xi[u] >= 0 && rank[u] < KP) {
-            ck[rank[u]] = x[u];
-            ci[rank[u]] = xi[u];
-        }
-    }
-    return n_valid < KP ? n_valid : KP;
-}
-
-// One query, one wave (only wave-level synchronisation inside).
-// NV (round 6): 16-byte loads per lane and candidate row in the pipelined re-rank -- 1: float32 rows of up to 256 elements, 2: up to
-// 512 (the second 256-element chunk's four fma continue the first chunk's chain: kz_wave_dot's order).  d = 300 -- the dimension
-// of the entity-alignment embeddings kiez is used on, and of BASELINE configuration 4 -- used to take the generic loop below: no
-// load in flight under the sums, the query row re-read per candidate (250 k x 1 M x 300: 7.3 ms per launch against 4.3 at d = 200).
-template <typename T, int FROWS, int NV = 1>
-__device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const int64_t q, const int lane, char* wbase) {
-    const int KS = p.KSEL > 0 ? p.KSEL : p.KP;   // candidates selected and re-ranked
-    double* cv = reinterpret_cast<double*>(wbase);
-    double* sv = cv + KS;
-    float* ekey = reinterpret_cast<float*>(sv + KS);
-    int* eidx = reinterpret_cast<int*>(ekey + p.max_m);
-    float* ck = reinterpret_cast<float*>(eidx + p.max_m);
-    int* ci = reinterpret_cast<int*>(ck + KS);
-    int* si = ci + KS;
-    const int KP = p.KP;
-    const int k_eff = p.k + (p.exclude_self ? 1 : 0);
-    // the query's own row and norm first: their latency passes under the list phase
-    const int64_t qrow = p.row_map ? (int64_t)p.row_map[p.q_begin + q] : p.q_begin + q;
-    const int64_t qout = p.row_map ? qrow : q;   // output row (row_map: out_dist / out_ind / fail_list are indexed by matrix rows)
-    const T* qptr = reinterpret_cast<const T*>(p.qraw) + qrow * (int64_t)p.d;
-    const double qs = p.qsqn[qrow];
-
-    const int64_t lrow = p.list_row0 + q;
-    const int n_pieces = p.lay.pieces[kz_list_region(lrow, p.lay)];
-    const int halves = p.lay.halves;
-    const int M = n_pieces * halves * KP;
-    // entry e of this query: piece e / (halves KP), lane-half (e / KP) % halves, list entry e % KP  (kz_list_wave_base)
-    if (p.lay.contig) {
-        // fp16 kernel: the query's pieces x K' entries are one contiguous run
-        const int64_t l0 = kz_list_contig_off(lrow, p.lay, KP, 0);
-        for (int e = lane; e < M; e += 64) {
-            ekey[e] = p.in_key[l0 + e];
-            int r = p.in_idx[l0 + e];
-            if (p.idx_map && r >= 0) r = p.idx_map[r];
-            eidx[e] = r;
-        }
-    } else {
-        const int64_t lwave = kz_list_wave_base(lrow, p.lay, KP, 0) + (lrow & 31);
-        for (int e = lane; e < M; e += 64) {
-            const int piece = e / (halves * KP);
-            const int rem = e - piece * halves * KP;
-            const int hh = rem / KP;
-            const int ee = rem - hh * KP;
-            const int64_t off = lwave + ((int64_t)piece * KP + ee) * KZ_LSTRIDE + hh * 32;
-            ekey[e] = p.in_key[off];
-            eidx[e] = p.in_idx[off];
-        }
-    }
-    kz_wave_sync();
-
-    // Long-k route (KS > KP): the union of the per-range lists holds the KS best approximate keys only if no range
-    // contributes more than its list can hold.  A FULL list may have evicted rows: everything outside it has a key <= its
-    // smallest entry -- the largest such value over the full lists joins the certification bound below.
-    float piece_bound = p.list_floor ? p.list_floor[p.q_begin + q] : -INFINITY;
-    if (KS > KP) {
-        for (int l0 = 0; l0 < M; l0 += KP) {   // (uniform; KP is a multiple of 16, lists are at most 128 entries)
-            float mn = INFINITY;
-            int cnt = 0;
-            for (int e = lane; e < KP; e += 64) {
-                const bool ok = eidx[l0 + e] >= 0;
-                cnt += ok ? 1 : 0;
-                mn = ok ? fminf(mn, ekey[l0 + e]) : mn;
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                cnt += __shfl_xor(cnt, off, 64);
-                mn = fminf(mn, __shfl_xor(mn, off, 64));
-            }
-            if (cnt == KP) piece_bound = fmaxf(piece_bound, mn);
-        }
-    }
-    // top-KS of the M entries by (key desc, idx asc).  Up to 64 entries: rank counting (ck / ci come out ordered).  More (round
-    // 5): rank counting is O(M^2 / 64) per lane -- 160 entries (ten lists of 16): ~3 500 of a query's ~8 000 instructions -- and
-    // NOTHING below needs the selected keys in order: the KS best by a radix select + compaction (unordered), further down the
-    // k-th best of them by a second radix select and the candidates within 2 eps of it by compaction.
-    int V = 0;
-    bool unsorted = false;
-    float sel_min = INFINITY, left_max = -INFINITY;   // unsorted path: smallest selected key; largest selected key NOT re-ranked
-    if (M <= 64) {
-        V = kz_rank_select<1>(ekey, eidx, M, KS, ck, ci, lane);
-    } else {
-        unsorted = true;
-        unsigned* uk = reinterpret_cast<unsigned*>(ekey);   // (the keys are not needed as floats any more)
-        auto key_of = [](unsigned u) { return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu)); };
-        int nv = 0;
-        for (int e = lane; e < M; e += 64) {
-            unsigned bts = __float_as_uint(ekey[e]);
-            if (bts == 0x80000000u) bts = 0u;   // (-0 = +0)
-            const bool valid = eidx[e] >= 0;
-            uk[e] = valid ? (bts ^ ((bts >> 31) ? 0xffffffffu : 0x80000000u)) : 0u;
-            nv += valid ? 1 : 0;
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) nv += __shfl_xor(nv, off, 64);
-        kz_wave_sync();
-        const bool all = nv <= KS;
-        unsigned thr = 0u;
-        if (!all) thr = kz_radix_kth_u32(uk, M, KS, lane);   // (invalid entries carry the smallest pattern: they never reach rank KS)
-        for (int e0 = 0; e0 < M; e0 += 64) {   // entries above the threshold (all valid entries when there are at most KS)
-            const int e = e0 + lane;
-            const bool sel = e < M && eidx[e] >= 0 && (all || uk[e] > thr);
-            const unsigned long long mask = __ballot(sel);
-            if (sel) {
-                const int pos = V + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                const float kf = key_of(uk[e]);
-                ck[pos] = kf;
-                ci[pos] = eidx[e];
-                sel_min = fminf(sel_min, kf);
-            }
-            V += (int)__popcll(mask);
-        }
-        if (!all) {   // the remaining places go to the entries AT the threshold with the smallest rows
-            int last = -1;
-            while (V < KS) {
-                int best = 0x7fffffff;
-                for (int e = lane; e < M; e += 64) {
-                    const int xi = eidx[e];
-                    if (xi >= 0 && uk[e] == thr && xi > last && xi < best) best = xi;
-                }
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) best = min(best, __shfl_xor(best, off, 64));
-                if (best == 0x7fffffff) break;   // (cannot happen: at least KS entries are >= thr)
-                if (lane == 0) {
-                    ck[V] = key_of(thr);
-                    ci[V] = best;
-                }
-                last = best;
-                ++V;
-                sel_min = fminf(sel_min, key_of(thr));
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sel_min = fminf(sel_min, __shfl_xor(sel_min, off, 64));
-    }
-    kz_wave_sync();
-
-    // Rounding bound of this query's approximate keys and the exact key of a candidate from its exact value.
-    //   float32 / split-bf16 operands: |key~ - key| <= gamma (|y|max^2 / 2 + |q| |y|max), key = (|q|^2 - d^2) / 2 (euclidean
-    //   family) or 1 - dist (cosine);
-    //   fp16 operands (centred vectors x_c = float32(x - mu), operands x_h, residuals r = x_c - x_h measured at pack time):
-    //   q_h.y_h - q_c.y_c = -(r_q.y_h + q_h.r_y + r_q.r_y), so by Cauchy-Schwarz on the ACTUAL residual norms
-    //     |key~ - key_c| <= |r_q| Yh + |q_h| Ry + |r_q| Ry              (operand rounding; Yh = max |y_h|, Ry = max |r_y|)
-    //                      + gamma_acc (Yc2 / 2 + |q_h| Yh)               (float32 accumulation of exact products + bias)
-    //                      + 2^-23 (|q_c| + sqrt(Yc2))^2 + 1e-12 (...) + 1e-14 (|q|^2 + |y|max^2)
-    //                                                                     (float32 centring round-off, float64 re-rank)
-    //   with key_c = (|q_c|^2 - d^2) / 2 and d^2 = the exact squared distance (cosine: 2 dist, rows are unit vectors).
-    double eps_q, key_scale = 1.0, qref = qs;
-    const bool cosine_plain = p.metric == KZ_COSINE && !p.tier_h;
-    if (p.tier_h) {
-        const double qc2 = p.q_rowq[qrow * 3 + 0], qh = p.q_rowq[qrow * 3 + 1], qr = p.q_rowq[qrow * 3 + 2];
-        const double Yh = p.y_hmax[0], Ry = p.y_hmax[1], Yc2 = p.y_hmax[2];
-        const double qc = sqrt(qc2), yc = sqrt(Yc2);
-        // (the float64 re-rank evaluates |q|^2 + |y|^2 - 2 q.y on the UNCENTRED rows: its own round-off scales with those)
-        const double ymax = p.ystats[0];
-        const double raw2 = p.metric == KZ_COSINE ? 2.0 : qs + ymax * ymax;
-        eps_q = p.eps_mult * (qr * Yh + qh * Ry + qr * Ry + p.gamma_acc * (0.5 * Yc2 + qh * Yh) +
-                              1.1920928955078125e-07 * (qc + yc) * (qc + yc) + 1e-12 * (0.5 * Yc2 + qc2) + 1e-14 * raw2);
-        // reverse direction of a dual pass: the key was accumulated on top of THIS row's bias (|q_c|^2 / 2 joins the
-        // accumulation term) and went through one more float32 rounding when it was filed as key' = acc - bias(t) + bias(q)
-        if (p.dual_col) eps_q += p.eps_mult * (p.gamma_acc * 0.5 * qc2 + 1.1920928955078125e-07 * (0.5 * Yc2 + 0.5 * qc2 + qh * Yh));
-        key_scale = p.hscale[1];
-        qref = qc2;
-    } else if (p.metric == KZ_COSINE) {
-        eps_q = p.gamma * 1.001;
-    } else {
-        const double ymax = p.ystats[0];
-        const double scale = 0.5 * ymax * ymax + sqrt(qs) * ymax;
-        eps_q = p.gamma * scale;
-        // the relative bound assumes the products stay in the normal float32 range (data at the 1e-19 scale and below
-        // underflows in the matrix pipe): such rows are left to the exact float64 kernels
-        if (scale < 1e-30) eps_q = INFINITY;
-    }
-    auto exact_key = [&](double v) {
-        if (cosine_plain) return 1.0 - v;
-        return 0.5 * (qref - (p.metric == KZ_COSINE ? 2.0 * v : v));
-    };
-
-    // Which candidates need an exact distance?  Those that can still be among the exact top-k: a candidate c with
-    // key~_c < key~_(k) - 2 eps has key_c <= key~_c + eps < key~_(k) - eps <= (k-th best exact key of the re-ranked ones),
-    // so it is out.  The list is ordered by approximate key: the re-rank covers a prefix of Vr >= k_eff candidates (K' = 64,
-    // k = 50: ~52 gathered rows instead of 64).  The certification below re-checks the first pruned candidate.
-    int Vr = V;
-    if (unsorted) {
-        if (V > k_eff && eps_q < INFINITY) {
-            // the k-th best selected key (radix select over the sortable patterns, scratch: sv is written after the re-rank), then
-            // the candidates within 2 eps of it to the front of ekey / eidx (the list copy is spent): the re-rank's set, unordered
-            unsigned* su = reinterpret_cast<unsigned*>(sv);
-            for (int c = lane; c < V; c += 64) {
-                unsigned b = __float_as_uint(ck[c]);
-                if (b == 0x80000000u) b = 0u;
-                su[c] = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-            }
-            kz_wave_sync();
-            const unsigned uk_k = kz_radix_kth_u32(su, V, k_eff, lane);
-            const float key_k = __uint_as_float(uk_k ^ ((uk_k >> 31) ? 0x80000000u : 0xffffffffu));
-            const double thr = (double)key_k * key_scale - 2.0 * eps_q;
-            int cnt = 0;
-            for (int c0 = 0; c0 < V; c0 += 64) {
-                const int c = c0 + lane;
-                const bool in = c < V && (double)ck[c] * key_scale >= thr;
-                const unsigned long long mask = __ballot(in);
-                if (in) {
-                    const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                    ekey[pos] = ck[c];
-                    eidx[pos] = ci[c];
-                } else if (c < V) {
-                    left_max = fmaxf(left_max, ck[c]);
-                }
-                cnt += (int)__popcll(mask);
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) left_max = fmaxf(left_max, __shfl_xor(left_max, off, 64));
-            Vr = cnt;       // (>= k_eff: the k_eff best keys are all >= key_k)
-            ck = ekey;
-            ci = eidx;
-            kz_wave_sync();
-        }
-    } else if (V > k_eff && eps_q < INFINITY) {
-        const double thr = (double)ck[k_eff - 1] * key_scale - 2.0 * eps_q;
-        int cnt = 0;
-        for (int c = lane; c < V; c += 64) cnt += ((double)ck[c] * key_scale >= thr) ? 1 : 0;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-        Vr = cnt < k_eff ? k_eff : cnt;
-    }
-
-    // exact float64 re-rank of the Vr candidates, FROWS rows in flight per pass (independent gathers and butterfly sums
-    // overlap); the per-candidate arithmetic is exactly kz_wave_dot / kz_wave_dot_normalized (kz_common.h)
-    const T* yraw = reinterpret_cast<const T*>(p.yraw);
-    const bool vec = kz_row_vec_ok(qptr, p.d) && kz_row_vec_ok(yraw, p.d);
-#ifdef KZ_NO_FIN_PIPE
-    if (false) {
-#else
-    if (sizeof(T) == 4 && vec && p.d <= 256 * NV && Vr > 0) {
-#endif   // (Vr == 0: a reverse-direction row without a single event)
-        // float32 rows of up to 256 NV elements (NV 16-byte loads per lane and row): the loads of the NEXT group of FROWS
-        // candidates are issued before the current group's fma chains and butterfly sums -- same arithmetic in the same order
-        // as the generic loop below (and as kz_wave_dot), only the memory latency of group g+1 hides under the sums of group g
-        const int k0 = 4 * lane;
-        bool act[NV];
-        int k0r[NV];
-        double qk[4 * NV];
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-            act[c] = k0 + 256 * c < p.d;
-            k0r[c] = act[c] ? k0 + 256 * c : 0;
-            double t[4] = {0.0, 0.0, 0.0, 0.0};
-            if (act[c]) {
-                kz_row4(qptr, k0r[c], p.d, true, t);
-                if (p.metric == KZ_COSINE) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] = t[e] / qs;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qk[4 * c + e] = t[e];
-        }
-        auto issue = [&](int c0, float4 (&buf)[FROWS][NV], double (&ysb)[FROWS]) {
-#pragma unroll
-            for (int u = 0; u < FROWS; ++u) {
-                // (no branch around a load, and no load under a condition: with loads on some paths only the compiler waits for
-                //  ALL outstanding loads -- s_waitcnt vmcnt(0), the group just issued included -- before the first use of the
-                //  current group, and the prefetch hides nothing (the loop ran at latency + arithmetic per candidate).  Lanes
-                //  past the end of the row read its first elements and never use them; the group past the last one is the last
-                //  candidate again.)
-                const int yi = ci[min(c0 + u, Vr - 1)];
-                ysb[u] = p.ysqn[yi];
-#pragma unroll
-                for (int c = 0; c < NV; ++c)
-                    buf[u][c] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(yraw) + (int64_t)yi * p.d + k0r[c]);
-            }
-        };
-        auto reduce = [&](int c0, const float4 (&buf)[FROWS][NV], const double (&ysb)[FROWS]) {
-#pragma unroll
-            for (int u = 0; u < FROWS; ++u) {
-                double a = 0.0;
-                bool done = false;
-                if (p.metric == KZ_COSINE && p.fast_div) {
-                    const double rcp = 1.0 / ysb[u];   // (wave-uniform: every lane holds the same row norm)
-                    const int rcp_hi = __builtin_amdgcn_readfirstlane((int)((unsigned long long)__double_as_longlong(rcp) >> 32));
-                    if ((rcp_hi & 0x7ff00000) != 0x7ff00000) {
-#pragma unroll
-                        for (int c = 0; c < NV; ++c) {
-                            const double yk[4] = {(double)buf[u][c].x, (double)buf[u][c].y, (double)buf[u][c].z, (double)buf[u][c].w};
-                            if (act[c]) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) a = fma(qk[4 * c + e], kz_div_shared(yk[e], ysb[u], rcp), a);
-                            }
-                        }
-                        done = true;
-                    }
-                }
-                if (!done) {
-#pragma unroll
-                    for (int c = 0; c < NV; ++c) {
-                        const double yk[4] = {(double)buf[u][c].x, (double)buf[u][c].y, (double)buf[u][c].z, (double)buf[u][c].w};
-                        if (act[c]) {
-                            if (p.metric == KZ_COSINE) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) a = fma(qk[4 * c + e], yk[e] / ysb[u], a);
-                            } else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) a = fma(qk[4 * c + e], yk[e], a);
-                            }
-                        }
-                    }
-                }
-                const double dot = kz_wave_sum(a);
-                double v;
-                if (p.metric == KZ_COSINE) {
-                    v = fmin(fmax(1.0 - dot, 0.0), 2.0);
-                } else {
-                    v = fmax((qs + ysb[u]) - 2.0 * dot, 0.0);
-                }
-                if (lane == 0 && c0 + u < Vr) cv[c0 + u] = v;
-            }
-        };
-#if KZ_FIN_DEPTH == 3
-        // three groups in flight (a rotating set of three register buffers, the loop unrolled by three: no copies): the gathers
-        // of groups g + 1 and g + 2 are under way while group g is reduced
-        constexpr int R = FROWS;
-        float4 b0[R][NV], b1[R][NV], b2[R][NV];
-        double y0[R], y1[R], y2[R];
-        issue(0, b0, y0);
-        issue(R, b1, y1);
-        for (int c0 = 0;;) {   // (all conditions wave-uniform)
-            issue(c0 + 2 * R, b2, y2);
-            reduce(c0, b0, y0);
-            if ((c0 += R) >= Vr) break;
-            issue(c0 + 2 * R, b0, y0);
-            reduce(c0, b1, y1);
-            if ((c0 += R) >= Vr) break;
-            issue(c0 + 2 * R, b1, y1);
-            reduce(c0, b2, y2);
-            if ((c0 += R) >= Vr) break;
-        }
-#else
-        float4 cur[FROWS][NV], nxt[FROWS][NV];
-        double ys_c[FROWS], ys_n[FROWS];
-        issue(0, cur, ys_c);
-        for (int c0 = 0; c0 < Vr; c0 += 2 * FROWS) {   // (unrolled by two: the buffers swap roles, no copies)
-            issue(c0 + FROWS, nxt, ys_n);
-            reduce(c0, cur, ys_c);
-            if (c0 + FROWS >= Vr) break;
-            issue(c0 + 2 * FROWS, cur, ys_c);
-            reduce(c0 + FROWS, nxt, ys_n);
-        }
-#endif
-    } else
-    for (int c0 = 0; c0 < Vr; c0 += FROWS) {
-        const T* yp[FROWS];
-        double ys[FROWS], acc[FROWS];
-#pragma unroll
-        for (int u = 0; u < FROWS; ++u) {
-            const int yi = ci[min(c0 + u, Vr - 1)];
-            yp[u] = yraw + (int64_t)yi * p.d;
-            ys[u] = p.ysqn[yi];
-            acc[u] = 0.0;
-        }
-        for (int k0 = 4 * lane; k0 < p.d; k0 += 256) {
-            double qk[4];
-            kz_row4(qptr, k0, p.d, vec, qk);
-            if (p.metric == KZ_COSINE) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) qk[e] = qk[e] / qs;
-            }
-#pragma unroll
-            for (int u = 0; u < FROWS; ++u) {
-                double yk[4];
-                kz_row4(yp[u], k0, p.d, vec, yk);
-                if (p.metric == KZ_COSINE) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[u] = fma(qk[e], yk[e] / ys[u], acc[u]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[u] = fma(qk[e], yk[e], acc[u]);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < FROWS; ++u) {
-            const double dot = kz_wave_sum(acc[u]);
-            double v;
-            if (p.metric == KZ_COSINE) {
-                v = fmin(fmax(1.0 - dot, 0.0), 2.0);  // sklearn cosine_distances: S *= -1; S += 1; clip(0, 2)
-            } else {
-                v = fmax((qs + ys[u]) - 2.0 * dot, 0.0);  // |x|^2 - 2 x.y + |y|^2, clamped (_argkmin.pyx.tp:494-502)
-            }
-            if (lane == 0 && c0 + u < Vr) cv[c0 + u] = v;
-        }
-    }
-    kz_wave_sync();
-    // rank by (value asc, idx asc) and scatter into sorted order
-    for (int c = lane; c < Vr; c += 64) {
-        const double v = cv[c];
-        const int id = ci[c];
-        int rank = 0;
-        for (int o = 0; o < Vr; ++o) {
-            const double ov = cv[o];
-            const int oid = ci[o];
-            rank += (ov < v || (ov == v && oid < id)) ? 1 : 0;
-        }
-        sv[rank] = v;
-        si[rank] = id;
-    }
-    kz_wave_sync();
-
-    // Self-check of the bound the certification rests on: for every candidate both the approximate key (ck, from the
-    // fused kernel) and the exact key (from the float64 re-rank) are known here.
-    bool bound_violated = false;
-    if (eps_q > 0.0 && eps_q < INFINITY && p.err_ratio_bits) {
-        double worst = 0.0;
-        for (int c = lane; c < Vr; c += 64) {
-            const double v = cv[c];
-            if (v > 0.0)  // (a distance clamped at 0 no longer carries the exact key)
-                worst = fmax(worst, fabs((double)ck[c] * key_scale - exact_key(v)) / eps_q);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off, 64));
-        bound_violated = worst > 1.0;   // (wave-uniform after the butterfly) never expected: see the certification below
-        if (lane == 0 && worst > 0.0) {
-            // a million waves hit ONE address: read first -- an ordinary load (served by this XCD's L2; a stale value only costs
-            // a redundant atomicMax), not an agent-scope atomic load that goes to the memory side every time -- and only the
-            // (rare) new maxima pay for the atomic
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(worst);
-            if (bits > *(const volatile unsigned long long*)p.err_ratio_bits) atomicMax(p.err_ratio_bits, bits);
-        }
-    }
-
-    // Certification (DESIGN.md "Certified candidate sets").  |key~ - key| <= eps for every index row.  A row outside
-    // the candidate set has key~ <= ck[KP-1] (the K'-th best approximate key), hence an exact key <= ck[KP-1] + eps.
-    // The exact key of the k-th re-ranked candidate is known.  If it is strictly larger, no outside row can enter -- or
-    // tie with -- the exact top-k.  V < KP means no list ever evicted anything: the set is complete.
-    bool certified;
-    if (p.excl_floor) {
-        // dual pass: outside the list are events that lost the selection (key~ <= ck[KP-1], full lists only) and the rows
-        // that never were events (key~ < floor)
-        double bound = (double)p.excl_floor[qrow];
-        if (V == KP) bound = fmax(bound, (double)(unsorted ? sel_min : ck[KP - 1]));
-        certified = V >= k_eff && bound * key_scale + eps_q < exact_key(sv[k_eff - 1]);
-    } else {
-        // rows outside the selected set: behind the KS-th selected key (when the selection is full), or evicted from a full
-        // list (long-k route: piece_bound; with KS = KP a full list implies a full selection whose KS-th key is at least as
-        // large, so the first term alone is the round-1 rule).  Neither: no list ever evicted anything, the set is complete.
-        float bound = piece_bound;
-        if (V == KS) bound = fmaxf(bound, unsorted ? sel_min : ck[KS - 1]);
-        if (bound == -INFINITY)
-            certified = (V >= min((int64_t)k_eff, p.n_i));
-        else
-            certified = V >= k_eff && (double)bound * key_scale + eps_q < exact_key(sv[k_eff - 1]);
-    }
-    // ... and the candidates that were not re-ranked are out by the same argument (implied by how Vr was chosen; re-checked)
-    if (Vr < V && !((double)(unsorted ? left_max : ck[Vr]) * key_scale + eps_q < exact_key(sv[k_eff - 1]))) certified = false;
-    // An approximate key further than eps from its exact value contradicts the bound everything above rests on (a kernel
-    // or hardware fault, not a property of the data): do not trust this row's candidate set, send it down a tier.
-    if (bound_violated) certified = false;
-    if (!certified) {
-        if (lane == 0) {
-            const int pos = atomicAdd(p.fail_count, 1);
-            p.fail_list[pos] = (int)qout;
-            if (p.fail_tau) p.fail_tau[pos] = Vr >= k_eff ? sv[k_eff - 1] : (double)INFINITY;
-        }
-        return;
-    }
-    kz_emit_sorted<T>(sv, si, Vr, p.k, p.exclude_self, p.self_ids ? p.self_ids[q] : qrow, p.metric,
-                      p.out_dist + qout * (int64_t)p.k, p.out_ind + qout * (int64_t)p.k, lane);
-}
-
-// A workgroup finalizes KZ_FIN_QPB consecutive queries (wave w takes queries w, w+4, ...).  32 per workgroup (sharing the list
-// cache lines of one wave-interleaved block) measured 2x SLOWER than 4: finalize is latency-bound and wants many workgroups.
-constexpr int KZ_FIN_QPB = 4;
-#ifndef KZ_FIN_WAVES_2
-#define KZ_FIN_WAVES_2 5  // ... of the two-loads-per-row build (NV = 2: 24 more registers of gather buffers and query elements)
-#endif
-#ifndef KZ_FIN_WAVES
-#define KZ_FIN_WAVES 7  // minimum waves per SIMD the finalize kernel is compiled for (see KZ_FIN_ROWS_N above)
-#endif
-// FROWS / MINW: candidate rows gathered per group and the occupancy compiled for.  <1, KZ_FIN_WAVES> is the kernel of every
-// ordinary pass (a dozen to ~50 gathered rows per query: waves in flight beat rows in flight per wave); <8, 2> serves the long-k
-// route (hundreds of gathered rows per query, one workgroup per CU for its LDS anyway: the gathers of a query were a chain of
-// ~k / 2 round trips).
-template <typename T, int FROWS, int MINW, int NV = 1>
-__global__ __launch_bounds__(256, MINW) void kz_knn_finalize_kernel(KnnFinParams p) {
-    extern __shared__ __attribute__((aligned(16))) char fsm[];
-    const int lane = threadIdx.x & 63;
-    // (wave number in a scalar register: the query number, its matrix row and everything loaded per query -- norm, image statistics
-    //  -- are then scalar loads issued at the top of the query, not vector loads of one address by 64 lanes)
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    char* wbase = fsm + (size_t)wave * kz_fin_wave_bytes(p.max_m, p.KSEL > 0 ? p.KSEL : p.KP);
-    for (int rep = 0; rep < KZ_FIN_QPB / 4; ++rep) {
-        const int64_t q = p.q_first + (int64_t)blockIdx.x * KZ_FIN_QPB + rep * 4 + wave;
-        if (q >= p.q_last) break;  // whole wave leaves; only wave-level sync inside
-        kz_finalize_query<T, FROWS, NV>(p, q, lane, wbase);
-        kz_wave_sync();
-    }
-}
-
-#include "kz_knn_fin_wide.h"
-
-// ---------------------------------------------------------------------------------------------------
-// Stage 3: exact float64 brute force for uncertified rows (rare; correctness backstop)
-// ---------------------------------------------------------------------------------------------------
-// SPECULATIVE launches of the exact kernels (kz_spec_rescue below): the grid is sized for `cap` rows BEFORE the host knows how
-// many rows the finalize kernel left uncertified; the count is read from device memory, row b of the grid lives when
-// b < count <= cap (count > cap: nothing runs here, the host takes the ordinary re-search).
-__device__ __forceinline__ bool kz_spec_row_live(const int* __restrict__ dyn_n, int b, int cap) {
-    const int n = *dyn_n;
-    return n <= cap && b < n;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void kz_exact_dist_kernel(const int* __restrict__ fail_list, int batch0, int64_t q_begin,
-                                                            const T* __restrict__ qraw, const T* __restrict__ yraw,
-                                                            const double* __restrict__ qsqn, const double* __restrict__ ysqn,
-                                                            int64_t n_i, int d, int metric, double p, double* __restrict__ vals,
-                                                            const int* __restrict__ dyn_n = nullptr) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int b = blockIdx.y;
-    if (dyn_n && !kz_spec_row_live(dyn_n, b, (int)gridDim.y)) return;
-    const int64_t qrow = q_begin + fail_list[batch0 + b];
-    // (grid-stride over the index rows: the ordinary callers launch one wave per pair, a speculative launch a bounded grid --
-    //  workgroups of a dead row cost their dispatch, and n_i / 4 x R of them would be milliseconds on a 1 M-row index)
-    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_i; i += (int64_t)gridDim.x * 4) {
-        const double v = kz_exact_value<T>(qraw + qrow * (int64_t)d, yraw + i * (int64_t)d, qsqn[qrow], ysqn[i], d, metric, lane, p);
-        if (lane == 0) vals[(int64_t)b * n_i + i] = v;
-    }
-}
-
-// The same values for float32 rows of d <= 256 (d a multiple of 4), many pairs per wave step (round 5).  kz_exact_dist_kernel spends
-// a wave on ONE pair -- at d = 64 a quarter of its lanes, re-reading the query row and, for cosine, dividing every element twice:
-// 2.9 G pairs/s, 125 us per query row against 301 k index rows; on data with clusters three orders of magnitude tighter than the
-// data's extent a tenth of the rows end there, and a 300 k x 300 k call took 8 s (tools/cliff_probe.py).  Here a wave keeps Q = 4
-// query rows in registers and walks CONSECUTIVE index rows, G = 64 / LPR of them per step (a row needs LPR = d / 4 lanes rounded up
-// to a power of two): one coalesced load serves G x Q pairs.  The arithmetic of a pair is kz_wave_dot's, operation for operation
-// -- the lane's four fma in element order, then the butterfly inside the lane group (the steps of the full-wave butterfly that it
-// skips add the exact zeros of lanes past the row) -- as in the finalize kernel for many candidates (kz_knn_fin_wide.h), so the
-// values are bit for bit those of kz_exact_value, kz_pair_values and the re-rank.  Cosine: the index rows normalised once in
-// float64 (kz_matrix_norm64) where that image exists, else the shared-reciprocal division.
-template <int LPR, bool NORM, int NV = 1>
-__global__ __launch_bounds__(256) void kz_exact_dist_rows_kernel(const int* __restrict__ fail_list, int batch0, int nb, int64_t q_begin,
-                                                                 const float* __restrict__ qraw, const float* __restrict__ yraw,
-                                                                 const double* __restrict__ ynorm64, const double* __restrict__ qsqn,
-                                                                 const double* __restrict__ ysqn, int64_t n_i, int d, int metric,
-                                                                 int rows_per_wave, double* __restrict__ vals,
-                                                                 const int* __restrict__ dyn_n = nullptr) {
-    // NV = 2 (round 6): rows of 260 .. 512 elements -- a lane owns elements 4 sl .. 4 sl + 3 of BOTH 256-element chunks of the row
-    // (LPR = 64, one index row per wave step), the second chunk's four fma continue the first's chain: kz_wave_dot's order for d > 256.
-    static_assert(NV == 1 || LPR == 64, "two chunks per lane: the whole wave owns one row");
-    constexpr int G = 64 / LPR, Q = 4;
-    if (dyn_n) {   // (speculative launch: nb was the grid's capacity)
-        if (!kz_spec_row_live(dyn_n, blockIdx.y * Q, nb)) return;
-        nb = *dyn_n;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int grp = lane / LPR, sl = lane & (LPR - 1);
-    const int k0 = 4 * sl;
-    bool act[NV];
-    int k0r[NV];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-        act[c] = k0 + 256 * c < d;
-        k0r[c] = act[c] ? k0 + 256 * c : 0;
-    }
-    const int b0 = blockIdx.y * Q;
-    double qk[Q][4 * NV], qs[Q];
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-        const int bq = b0 + j < nb ? b0 + j : nb - 1;
-        const int64_t qrow = q_begin + fail_list[batch0 + bq];
-        qs[j] = qsqn[qrow];
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-            double t[4] = {0.0, 0.0, 0.0, 0.0};
-            if (act[c]) {
-                kz_row4(qraw + qrow * (int64_t)d, k0r[c], d, true, t);
-                if (metric == KZ_COSINE) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] = t[e] / qs[j];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qk[j][4 * c + e] = t[e];
-        }
-    }
-    const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * rows_per_wave;
-    const int64_t i1 = i0 + rows_per_wave < n_i ? i0 + rows_per_wave : n_i;
-    if (i0 >= i1) return;
-    struct Buf {
-        float4 f[NV];
-        double ys;
-        double2 n0[NV], n1[NV];
-    };
-    auto issue = [&](int64_t i, Buf& b) {   // (rows past the end: the last row again, nothing is written for them)
-        const int64_t yi = i + grp < i1 ? i + grp : i1 - 1;
-        if (NORM) {
-#pragma unroll
-            for (int c = 0; c < NV; ++c) {
-                const double* row = ynorm64 + yi * (int64_t)d + k0r[c];
-                b.n0[c] = *reinterpret_cast<const double2*>(row);
-                b.n1[c] = *reinterpret_cast<const double2*>(row + 2);
-            }
-        } else {
-            b.ys = ysqn[yi];
-#pragma unroll
-            for (int c = 0; c < NV; ++c) b.f[c] = *reinterpret_cast<const float4*>(yraw + yi * (int64_t)d + k0r[c]);
-        }
-    };
-    auto reduce = [&](int64_t i, const Buf& b) {
-        double yv[4 * NV];
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) yv[4 * c + e] = 0.0;
-            if (act[c]) {
-                if (NORM) {
-                    yv[4 * c] = b.n0[c].x, yv[4 * c + 1] = b.n0[c].y, yv[4 * c + 2] = b.n1[c].x, yv[4 * c + 3] = b.n1[c].y;
-                } else {
-                    const double yk[4] = {(double)b.f[c].x, (double)b.f[c].y, (double)b.f[c].z, (double)b.f[c].w};
-                    if (metric == KZ_COSINE) {
-                        const double rcp = 1.0 / b.ys;
-                        const bool fin = (((unsigned long long)__double_as_longlong(rcp) >> 52) & 0x7ff) != 0x7ff;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) yv[4 * c + e] = fin ? kz_div_shared(yk[e], b.ys, rcp) : yk[e] / b.ys;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) yv[4 * c + e] = yk[e];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            double a = 0.0;
-#pragma unroll
-            for (int c = 0; c < NV; ++c) {
-                if (act[c]) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a = fma(qk[j][4 * c + e], yv[4 * c + e], a);
-                }
-            }
-#pragma unroll
-            for (int off = LPR >> 1; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
-            double v;
-            if (metric == KZ_COSINE)
-                v = fmin(fmax(1.0 - a, 0.0), 2.0);
-            else
-                v = fmax((qs[j] + b.ys) - 2.0 * a, 0.0);
-            if (sl == 0 && i + grp < i1 && b0 + j < nb) vals[(int64_t)(b0 + j) * n_i + i + grp] = v;
-        }
-    };
-    Buf ba, bb;
-    issue(i0, ba);
-    for (int64_t i = i0; i < i1;) {   // (two steps in flight; the conditions are wave-uniform)
-        issue(i + G, bb);
-        reduce(i, ba);
-        i += G;
-        if (i >= i1) break;
-        issue(i + G, ba);
-        reduce(i, bb);
-        i += G;
-    }
-}
-// -> true when the kernel above took the batch
-static bool kz_launch_exact_rows(kz_ctx* ctx, const int* fl, int b0, int nb, int64_t cq_begin, const kz_matrix* query, const kz_matrix* index,
-                                 int metric, double* vals, const int* dyn_n = nullptr, int rows_per_wave = 256) {
-    const int d = (int)index->d;
-    if (index->dtype != KZ_F32 || (d & 3) != 0 || d > 512 || metric > KZ_COSINE || (((uintptr_t)query->raw | (uintptr_t)index->raw) & 15u) != 0) return false;
-    const bool norm = metric == KZ_COSINE && index->norm64 != nullptr;
-    const dim3 grid((unsigned)((index->n + 4 * rows_per_wave - 1) / (4 * rows_per_wave)), (unsigned)((nb + 3) / 4));
-    const int lanes = (d + 3) >> 2;
-#define KZ_EXACT_ROWS(L)                                                                                                                \
-    do {                                                                                                                                \
-        if (norm)                                                                                                                       \
-            hipLaunchKernelGGL((kz_exact_dist_rows_kernel<L, true>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin,          \
-                               (const float*)query->raw, (const float*)index->raw, index->norm64, query->sqn, index->sqn, index->n, d, \
-                               metric, rows_per_wave, vals, dyn_n);                                                                     \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((kz_exact_dist_rows_kernel<L, false>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin,         \
-                               (const float*)query->raw, (const float*)index->raw, (const double*)nullptr, query->sqn, index->sqn,      \
-                               index->n, d, metric, rows_per_wave, vals, dyn_n);                                                        \
-    } while (0)
-    if (lanes <= 8)
-        KZ_EXACT_ROWS(8);
-    else if (lanes <= 16)
-        KZ_EXACT_ROWS(16);
-    else if (lanes <= 32)
-        KZ_EXACT_ROWS(32);
-    else if (lanes <= 64)
-        KZ_EXACT_ROWS(64);
-    else if (norm)   // (260 .. 512 elements: two chunks per lane)
-        hipLaunchKernelGGL((kz_exact_dist_rows_kernel<64, true, 2>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin, (const float*)query->raw,
-                           (const float*)index->raw, index->norm64, query->sqn, index->sqn, index->n, d, metric, rows_per_wave, vals, dyn_n);
-    else
-        hipLaunchKernelGGL((kz_exact_dist_rows_kernel<64, false, 2>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin, (const float*)query->raw,
-                           (const float*)index->raw, (const double*)nullptr, query->sqn, index->sqn, index->n, d, metric, rows_per_wave, vals, dyn_n);
-#undef KZ_EXACT_ROWS
-    return true;
-}
-
-#include "kz_exact_lanes.h"
-// -> true when the one-pair-per-lane kernel (kz_exact_lanes.h) took the batch: float32 rows of up to 512 elements (a multiple of 4,
-// 16-byte aligned), the euclidean family on the raw rows, cosine on the normalised float64 rows where that image exists, and a
-// batch of at least KZ_XL_MIN_ROWS query rows (a handful is the cooperative kernel's: it needs no staging and no pre-pass).
-constexpr int KZ_XL_MIN_ROWS = 32;
-static inline size_t kz_exact_lanes_qd_bytes(int nb, int d) {   // float64 operand rows + squared norms of whole blocks of query rows
-    const size_t nb_pad = (size_t)(nb + 4 * KZ_XL_Q - 1) / (4 * KZ_XL_Q) * (4 * KZ_XL_Q);
-    return (nb_pad * (size_t)d + nb_pad) * 8;
-}
-// dyn_n (speculative launch): nb is the capacity of the launch, the row count is read on the device
-// groups != nullptr (kz_range.h, grouped ranges): ONE launch for n_groups dense blocks (KzXlGroup) -- fl [n_slots] then holds the
-// query row of every operand row of every block (-1: padding), gather the blocks' lists of index rows; nb = n_slots, rows_max /
-// q_max = the largest block's index rows / query rows; vals as the blocks' val_off say.
-static int kz_launch_exact_lanes(kz_ctx* ctx, const int* fl, int b0, int nb, int64_t cq_begin, const kz_matrix* query, const kz_matrix* index,
-                                 int metric, double* vals, bool* took, const int* dyn_n = nullptr, double* qd_buf = nullptr,
-                                 const int* gather = nullptr, const KzXlGroup* groups = nullptr, int n_groups = 0, int rows_max = 0,
-                                 int q_max = 0) {
-    *took = false;
-    const int d = (int)index->d;
-    if (ctx->exact_rows < 2 || (nb < KZ_XL_MIN_ROWS && !dyn_n) || index->dtype != KZ_F32 || (d & 3) != 0 || d > 512 || metric > KZ_COSINE ||
-        (((uintptr_t)query->raw | (uintptr_t)index->raw) & 15u) != 0)
-        return KZ_OK;
-    const bool cosine = metric == KZ_COSINE && index->norm64 != nullptr && d <= 256;   // (the normalised float64 rows, staged as they are)
-    const bool cos_raw = metric == KZ_COSINE && !cosine;                               // (the raw rows, divided by the lane)
-    const int d_pad = d;   // (a multiple of 4: whole leaves)
-    const int nb_pad = groups ? nb : (nb + 4 * KZ_XL_Q - 1) / (4 * KZ_XL_Q) * (4 * KZ_XL_Q);   // (whole blocks of 4 waves x KZ_XL_Q rows; groups: the slots are padded per block)
-    double* qd = qd_buf;   // (a caller that runs these launches on another stream than the pool's brings the buffer: kz_spec_alloc)
-    KzPoolBuf<double> qd_own;
-    if (!qd) {
-        const int rc = qd_own.alloc(ctx, kz_exact_lanes_qd_bytes(nb, d));
-        if (rc != KZ_OK) return rc == KZ_ERR_NOMEM ? KZ_OK : rc;   // (no memory for the operand rows: the cooperative kernel)
-        qd = qd_own.get();
-    }
-    double* qsq = qd + (size_t)nb_pad * d_pad;
-    if (groups)
-        hipLaunchKernelGGL(kz_exact_qprep_slots_kernel, dim3(nb_pad), dim3(256), 0, ctx->stream, fl, cq_begin, (const float*)query->raw, query->sqn, d,
-                           d_pad, metric, qd, qsq);
-    else
-        hipLaunchKernelGGL(kz_exact_qprep_kernel, dim3(nb_pad), dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin, (const float*)query->raw, query->sqn, d,
-                           d_pad, metric, qd, qsq, dyn_n);
-    const int64_t n_rows = groups ? rows_max : index->n;
-    // (groups: a workgroup takes q_chunk = 64 query rows of its block -- four rounds of its 16 -- for one tile of 64 index rows)
-    const int q_chunk = 16 * KZ_XL_Q;
-    const dim3 grid((unsigned)((n_rows + KZ_XL_ROWS - 1) / KZ_XL_ROWS), groups ? (unsigned)((q_max + q_chunk - 1) / q_chunk) : 1u,
-                    groups ? (unsigned)n_groups : 1u);
-    const size_t lds = (size_t)(d_pad / 4) * (KZ_XL_ROWS + 1) * (cosine ? 32 : 16);   // (<= 133 KiB: 512 float32 / 256 float64 elements)
-    hipError_t e = hipSuccess;
-#define KZ_XL_LAUNCH_G(NL, NVV, ELT, CR, GA, rows)                                                                                             \
-    do {                                                                                                                                        \
-        if (lds > 65536) e = hipFuncSetAttribute((const void*)kz_exact_dist_lanes_kernel<NL, NVV, ELT, CR, GA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess)                                                                                                                     \
-            hipLaunchKernelGGL((kz_exact_dist_lanes_kernel<NL, NVV, ELT, CR, GA>), grid, dim3(256), lds, ctx->stream, nb, (const double*)qd, (const double*)qsq, \
-                               (const ELT*)(rows), index->sqn, n_rows, d, d_pad, metric, vals, dyn_n, gather, groups, q_chunk);                 \
-    } while (0)
-#define KZ_XL_LAUNCH(NL, NVV, ELT, rows)                          \
-    do {                                                           \
-        if (groups)                                                \
-            KZ_XL_LAUNCH_G(NL, NVV, ELT, false, true, rows);       \
-        else                                                       \
-            KZ_XL_LAUNCH_G(NL, NVV, ELT, false, false, rows);      \
-    } while (0)
-    if (cos_raw) {
-#define KZ_XL_LAUNCH_COS(NL, NVV)                                        \
-    do {                                                                  \
-        if (groups)                                                       \
-            KZ_XL_LAUNCH_G(NL, NVV, float, true, true, index->raw);       \
-        else                                                              \
-            KZ_XL_LAUNCH_G(NL, NVV, float, true, false, index->raw);      \
-    } while (0)
-        if (d <= 64)
-            KZ_XL_LAUNCH_COS(16, 1);
-        else if (d <= 128)
-            KZ_XL_LAUNCH_COS(32, 1);
-        else if (d <= 256)
-            KZ_XL_LAUNCH_COS(64, 1);
-        else
-            KZ_XL_LAUNCH_COS(64, 2);
-#undef KZ_XL_LAUNCH_COS
-    } else if (cosine) {
-        if (d <= 64)
-            KZ_XL_LAUNCH(16, 1, double, index->norm64);
-        else if (d <= 128)
-            KZ_XL_LAUNCH(32, 1, double, index->norm64);
-        else
-            KZ_XL_LAUNCH(64, 1, double, index->norm64);
-    } else {
-        if (d <= 64)
-            KZ_XL_LAUNCH(16, 1, float, index->raw);
-        else if (d <= 128)
-            KZ_XL_LAUNCH(32, 1, float, index->raw);
-        else if (d <= 256)
-            KZ_XL_LAUNCH(64, 1, float, index->raw);
-        else
-            KZ_XL_LAUNCH(64, 2, float, index->raw);
-    }
-#undef KZ_XL_LAUNCH
-#undef KZ_XL_LAUNCH_G
-    if (e == hipSuccess) e = hipGetLastError();
-    qd_own.reset();   // (stream-ordered pool)
-    if (e != hipSuccess) {
-        kz_set_error("kz_knn: exact distance kernel (one pair per lane) failed: %s", hipGetErrorString(e));
-        return KZ_ERR_HIP;
-    }
-    *took = true;
-    return KZ_OK;
-}
-
-// The Minkowski family beyond p = 2 (KZ_MANHATTAN, KZ_CHEBYSHEV, KZ_MINKOWSKI): no inner-product form, hence no MFMA -- a
-// register-tiled VALU kernel.  A workgroup of 256 threads owns 64 queries x 64 index rows, a thread 4 x 4 pairs; the rows are
-// staged through LDS DK features at a time, transposed ([feature][row]: a thread reads its four query values and its four index
-// values of a feature as one 16- / 32-byte LDS read each).  Per pair and feature: subtract in the input dtype, |.| into float64
-// (the conversion carries the abs modifier), add -- three VALU operations; every thread adds the terms of its pairs in feature
-// order (kz_common.h: kz_family_term / kz_family_add), which is scikit-learn's order.  VALU-bound: 15 k x 15 k x 300 float32,
-// manhattan: see DESIGN section 9.  Output: the same [batch][n_i] float64 value matrix kz_exact_dist_kernel writes.
-// Metrics 6 .. 9 (braycurtis, seuclidean, correlation, hamming: kz_common.h, kz_family_step) run on the same tiles: a pair's
-// state is two float64 accumulators.  Seuclidean reads V_j at a wave-uniform address; correlation stages the CENTRED float64 values
-// (x - row mean, one subtraction per element as the tile is loaded, not per pair), features [0, d & ~1) go through the tiles in
-// even / odd pairs and the odd tail term is added at the end.
-template <typename T, int METRIC, int DK, int CHAIN>
-__global__ __launch_bounds__(256) void kz_family_dist_kernel(const int* __restrict__ fail_list, int batch0, int nb, int64_t q_begin,
-                                                             const T* __restrict__ qraw, const T* __restrict__ yraw, int64_t n_i, int d,
-                                                             double p, int p_int, double* __restrict__ vals,
-                                                             const double* __restrict__ V = nullptr, const double* __restrict__ qcorr = nullptr,
-                                                             const double* __restrict__ ycorr = nullptr) {
-    using S = typename std::conditional<METRIC == KZ_CORRELATION, double, T>::type;   // (staged type)
-    __shared__ __attribute__((aligned(32))) S sQ[DK][64];
-    __shared__ __attribute__((aligned(32))) S sY[DK][64];
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const int64_t y0 = (int64_t)blockIdx.x * 64;
-    const int b0 = blockIdx.y * 64;
-    // staging: thread t copies DK / 4 consecutive features of row (t & 63) of both tiles (rows past the end: the last row again)
-    const int lrow = t & 63, lseg = (t >> 6) * (DK / 4);
-    const int bq = b0 + lrow < nb ? b0 + lrow : nb - 1;
-    const int64_t qrow_l = q_begin + fail_list[batch0 + bq];
-    const int64_t yrow_l = y0 + lrow < n_i ? y0 + lrow : n_i - 1;
-    const T* __restrict__ qp = qraw + qrow_l * (int64_t)d;
-    const T* __restrict__ yp = yraw + yrow_l * (int64_t)d;
-    // correlation: the features the tiles cover (the odd tail is added at the end) and the staged rows' means
-    const int d_tiles = METRIC == KZ_CORRELATION ? (d & ~1) : d;
-    double mq = 0.0, my = 0.0;
-    if constexpr (METRIC == KZ_CORRELATION) {
-        mq = qcorr[2 * qrow_l];
-        my = ycorr[2 * yrow_l];
-    }
-    double acc[4][4], acc2[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[a][c] = acc2[a][c] = 0.0;
-    for (int k0 = 0; k0 < d_tiles; k0 += DK) {
-        S rq[DK / 4], ry[DK / 4];
-#pragma unroll
-        for (int u = 0; u < DK / 4; ++u) {
-            const int k = k0 + lseg + u;
-            if constexpr (METRIC == KZ_CORRELATION) {
-                rq[u] = k < d_tiles ? (double)qp[k] - mq : 0.0;   // (0 x 0 adds +0: changes no sum)
-                ry[u] = k < d_tiles ? (double)yp[k] - my : 0.0;
-            } else {
-                rq[u] = k < d ? qp[k] : (T)0;
-                ry[u] = k < d ? yp[k] : (T)0;   // (|0 - 0| = 0 changes no sum and no maximum; nor 0 != 0, nor 0 0 / 1)
-            }
-        }
-        __syncthreads();   // (the previous chunk has been read)
-#pragma unroll
-        for (int u = 0; u < DK / 4; ++u) {
-            sQ[lseg + u][lrow] = rq[u];
-            sY[lseg + u][lrow] = ry[u];
-        }
-        __syncthreads();
-        if constexpr (METRIC == KZ_CORRELATION) {
-            // (fully unrolled: the parity of a feature -- which partial sum it goes to -- is known at compile time)
-#pragma unroll
-            for (int j = 0; j < DK; ++j) {
-                S q4[4], y4[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    q4[a] = sQ[j][ty * 4 + a];
-                    y4[a] = sY[j][tx * 4 + a];
-                }
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) kz_family_step<T, METRIC, CHAIN>(acc[a][c], acc2[a][c], q4[a], y4[c], p, p_int, 1.0, (j & 1) != 0);
-            }
-        } else {
-#pragma unroll 4
-            for (int j = 0; j < DK; ++j) {
-                // (seuclidean: a wave-uniform read of V_j; past the end 1: the padded term is 0 / 1)
-                const double v_j = METRIC == KZ_SEUCLIDEAN ? (k0 + j < d ? V[k0 + j] : 1.0) : 1.0;
-                S q4[4], y4[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    q4[a] = sQ[j][ty * 4 + a];
-                    y4[a] = sY[j][tx * 4 + a];
-                }
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) kz_family_step<T, METRIC, CHAIN>(acc[a][c], acc2[a][c], q4[a], y4[c], p, p_int, v_j, false);
-            }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int b = b0 + ty * 4 + a;
-        if (b >= nb) continue;
-        double nq = 0.0, tq = 0.0;
-        const T* qrow = nullptr;
-        if constexpr (METRIC == KZ_CORRELATION) {
-            const int64_t qr = q_begin + fail_list[batch0 + b];
-            nq = qcorr[2 * qr + 1];
-            qrow = qraw + qr * (int64_t)d;
-            if (d & 1) tq = (double)qrow[d - 1] - qcorr[2 * qr];
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int64_t i = y0 + tx * 4 + c;
-            if (i >= n_i) continue;
-            double ny = 0.0, tail = 0.0;
-            if constexpr (METRIC == KZ_CORRELATION) {
-                ny = ycorr[2 * i + 1];
-                if (d & 1) tail = tq * ((double)yraw[i * (int64_t)d + d - 1] - ycorr[2 * i]);
-            }
-            vals[(int64_t)b * n_i + i] = kz_family_finish<T, METRIC>(acc[a][c], acc2[a][c], d, tail, nq, ny);
-        }
-    }
-}
-template <typename T>
-static void kz_launch_family_dist(kz_ctx* ctx, const int* fl, int b0, int nb, int64_t cq_begin, const kz_matrix* query, const kz_matrix* index,
-                                  double* vals) {
-    constexpr int DK = sizeof(T) == 4 ? 32 : 16;
-    const dim3 grid((unsigned)((index->n + 63) / 64), (unsigned)((nb + 63) / 64));
-    const int p_int = kz_family_p_int(index->metric, index->mink_p, sizeof(T) == 4);
-#define KZ_FAMILY_LAUNCH_DK(M, C, DKM)                                                                                                    \
-    hipLaunchKernelGGL((kz_family_dist_kernel<T, M, DKM, C>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin, (const T*)query->raw, \
-                       (const T*)index->raw, index->n, (int)index->d, index->mink_p, p_int, vals, index->seu_v, query->corr, index->corr)
-#define KZ_FAMILY_LAUNCH(M, C) KZ_FAMILY_LAUNCH_DK(M, C, DK)
-    if (index->metric == KZ_MANHATTAN)
-        KZ_FAMILY_LAUNCH(KZ_MANHATTAN, -1);
-    else if (index->metric == KZ_CHEBYSHEV)
-        KZ_FAMILY_LAUNCH(KZ_CHEBYSHEV, -1);
-    else if (index->metric == KZ_BRAYCURTIS)
-        KZ_FAMILY_LAUNCH(KZ_BRAYCURTIS, -1);
-    else if (index->metric == KZ_SEUCLIDEAN)
-        KZ_FAMILY_LAUNCH(KZ_SEUCLIDEAN, -1);
-    else if (index->metric == KZ_CORRELATION)
-        KZ_FAMILY_LAUNCH_DK(KZ_CORRELATION, -1, 16);   // (float64 tiles whatever the input dtype)
-    else if (index->metric == KZ_HAMMING)
-        KZ_FAMILY_LAUNCH(KZ_HAMMING, -1);
-    else if (p_int == 3)
-        KZ_FAMILY_LAUNCH(KZ_MINKOWSKI, 3);     // (float32 inputs, p = 3 or 4: a product with one rounding, no pow() in the kernel)
-    else if (p_int == 4)
-        KZ_FAMILY_LAUNCH(KZ_MINKOWSKI, 4);
-    else
-        KZ_FAMILY_LAUNCH(KZ_MINKOWSKI, -1);
-#undef KZ_FAMILY_LAUNCH
-#undef KZ_FAMILY_LAUNCH_DK
-}
-
-// First level of the exact selection on a long row: the k_eff smallest (value, index row) pairs of every CHUNK of KZ_EXACT_CHUNK
-// values (the smallest k_eff of the row are among the smallest k_eff of their chunks); kz_exact_select_kernel then picks from
-// n_chunks x k_eff survivors instead of passing k_eff times over the whole row with one workgroup (1 M index rows, k = 10: 2 ms
-// per query row before, the distance kernel's time now).  One workgroup per (chunk, query row); a thread holds 16 values.
-constexpr int KZ_EXACT_CHUNK = 4096;
-__global__ __launch_bounds__(256) void kz_exact_chunk_kernel(const double* __restrict__ vals, int64_t n_i, int k_eff, int n_chunks,
-                                                             double* __restrict__ cand_v, int* __restrict__ cand_i,
-                                                             const int* __restrict__ dyn_n = nullptr) {
-    __shared__ double s_v[4];
-    __shared__ int s_i[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = blockIdx.x, b = blockIdx.y;
-    if (dyn_n && !kz_spec_row_live(dyn_n, b, (int)gridDim.y)) return;
-    const double* v = vals + (int64_t)b * n_i;
-    const int64_t i0 = (int64_t)c * KZ_EXACT_CHUNK;
-    constexpr int PER = KZ_EXACT_CHUNK / 256;
-    double x[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const int64_t i = i0 + tid + 256 * u;
-        x[u] = i < n_i ? v[i] : INFINITY;
-    }
-    double* ov = cand_v + ((int64_t)b * n_chunks + c) * k_eff;
-    int* oi = cand_i + ((int64_t)b * n_chunks + c) * k_eff;
-    double pv = -1.0;  // values are >= 0
-    int pi = -1;
-    for (int r = 0; r < k_eff; ++r) {
-        double bv = INFINITY;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int64_t i = i0 + tid + 256 * u;
-            const int id = i < n_i ? (int)i : 0x7fffffff;   // (places past the end of the row: (+inf, INT_MAX), after every real entry)
-            const bool after = (x[u] > pv) || (x[u] == pv && id > pi);
-            if (after && (x[u] < bv || (x[u] == bv && id < bi))) {
-                bv = x[u];
-                bi = id;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double o_v = __shfl_xor(bv, off, 64);
-            const int o_i = __shfl_xor(bi, off, 64);
-            if (o_v < bv || (o_v == bv && o_i < bi)) {
-                bv = o_v;
-                bi = o_i;
-            }
-        }
-        if (lane == 0) {
-            s_v[wave] = bv;
-            s_i[wave] = bi;
-        }
-        __syncthreads();
-        bv = s_v[0];
-        bi = s_i[0];
-        for (int ww = 1; ww < 4; ++ww) {
-            if (s_v[ww] < bv || (s_v[ww] == bv && s_i[ww] < bi)) {
-                bv = s_v[ww];
-                bi = s_i[ww];
-            }
-        }
-        if (tid == 0) {
-            ov[r] = bv;
-            oi[r] = bi;
-        }
-        pv = bv;
-        pi = bi;
-        __syncthreads();
-    }
-}
-
-// The same first level for MANY neighbours (k_eff >= 24): the k_eff-th smallest value of the chunk by a workgroup-wide radix
-// selection on the float64 bit patterns (non-negative doubles order like their patterns; a thread holds 16 of them, a counting pass
-// is 16 compares, a wave sum and one exchange through LDS -- ~55 passes below the common prefix whatever k is, against k_eff rounds
-// of a workgroup-wide arg-min: k = 50: 0.96 -> see r05_notes), then everything below it and, of the entries equal to it, those with
-// the smallest index rows.  The survivors come out in no particular order: kz_exact_select_kernel orders by (value, index row).
-__global__ __launch_bounds__(256) void kz_exact_chunk_radix_kernel(const double* __restrict__ vals, int64_t n_i, int k_eff, int n_chunks,
-                                                                   double* __restrict__ cand_v, int* __restrict__ cand_i,
-                                                                   const int* __restrict__ dyn_n = nullptr) {
-    __shared__ unsigned long long s_or[4], s_and[4];
-    __shared__ int s_cnt[4];
-    __shared__ int s_pos;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = blockIdx.x, b = blockIdx.y;
-    if (dyn_n && !kz_spec_row_live(dyn_n, b, (int)gridDim.y)) return;
-    const double* v = vals + (int64_t)b * n_i;
-    const int64_t i0 = (int64_t)c * KZ_EXACT_CHUNK;
-    constexpr int PER = KZ_EXACT_CHUNK / 256;
-    const int nvalid = (int)(n_i - i0 < KZ_EXACT_CHUNK ? n_i - i0 : KZ_EXACT_CHUNK);
-    double* ov = cand_v + ((int64_t)b * n_chunks + c) * k_eff;
-    int* oi = cand_i + ((int64_t)b * n_chunks + c) * k_eff;
-    unsigned long long x[PER];
-    unsigned long long all_or = 0ull, all_and = ~0ull;
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const int e = tid + 256 * u;
-        const bool in = e < nvalid;
-        x[u] = in ? (unsigned long long)__double_as_longlong(v[i0 + e]) : ~0ull;   // (places past the end: above every value)
-        all_or |= in ? x[u] : 0ull;
-        all_and &= x[u];
-    }
-    if (nvalid <= k_eff) {   // (a short last chunk: every entry survives; the unused places hold (+inf, INT_MAX))
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + 256 * u;
-            if (e < nvalid) {
-                ov[e] = __longlong_as_double((long long)x[u]);
-                oi[e] = (int)(i0 + e);
-            }
-        }
-        for (int e = nvalid + tid; e < k_eff; e += 256) {
-            ov[e] = INFINITY;
-            oi[e] = 0x7fffffff;
-        }
-        return;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        all_or |= __shfl_xor(all_or, off, 64);
-        all_and &= __shfl_xor(all_and, off, 64);
-    }
-    if (lane == 0) {
-        s_or[wave] = all_or;
-        s_and[wave] = all_and;
-    }
-    if (tid == 0) s_pos = 0;
-    __syncthreads();
-    all_or = s_or[0] | s_or[1] | s_or[2] | s_or[3];
-    all_and = s_and[0] & s_and[1] & s_and[2] & s_and[3];
-    auto block_sum = [&](int cnt) {   // (every thread gets the workgroup's total)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-        __syncthreads();   // (the previous round's readers are done with s_cnt)
-        if (lane == 0) s_cnt[wave] = cnt;
-        __syncthreads();
-        return s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    };
-    const unsigned long long differ = all_or ^ all_and;
-    const int top = differ ? 63 - __clzll(differ) : -1;
-    // thr = the k_eff-th smallest pattern: the largest prefix with fewer than k_eff entries below it, bit by bit
-    unsigned long long thr = top >= 63 ? 0ull : (top < 0 ? all_and : (all_and & ~((2ull << top) - 1ull)));
-    for (int bit = top; bit >= 0; --bit) {
-        const unsigned long long cand = thr | (1ull << bit);
-        int cnt = 0;
-#pragma unroll
-        for (int u = 0; u < PER; ++u) cnt += x[u] < cand ? 1 : 0;
-        if (block_sum(cnt) < k_eff) thr = cand;
-    }
-    // everything below thr
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        if (x[u] < thr) {
-            const int pos = atomicAdd(&s_pos, 1);
-            ov[pos] = __longlong_as_double((long long)x[u]);
-            oi[pos] = (int)(i0 + tid + 256 * u);
-        }
-    }
-    int ties = 0;
-#pragma unroll
-    for (int u = 0; u < PER; ++u) ties += x[u] == thr ? 1 : 0;
-    const int T = block_sum(ties);   // (its barriers also publish s_pos)
-    const int L = s_pos;
-    const int m = k_eff - L;         // places left for entries equal to thr: 1 <= m <= T
-    if (T == m) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            if (x[u] == thr) {
-                const int pos = atomicAdd(&s_pos, 1);
-                ov[pos] = __longlong_as_double((long long)thr);
-                oi[pos] = (int)(i0 + tid + 256 * u);
-            }
-        }
-        return;
-    }
-    // more ties at the k_eff-th place than places: those with the smallest index rows, one per round
-    int last = -1;
-    for (int r = 0; r < m; ++r) {
-        int best = 0x7fffffff;
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int id = (int)(i0 + tid + 256 * u);
-            if (x[u] == thr && id > last && id < best) best = id;
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) best = min(best, __shfl_xor(best, off, 64));
-        __syncthreads();
-        if (lane == 0) s_cnt[wave] = best;
-        __syncthreads();
-        best = min(min(s_cnt[0], s_cnt[1]), min(s_cnt[2], s_cnt[3]));
-        if (tid == 0) {
-            ov[L + r] = __longlong_as_double((long long)thr);
-            oi[L + r] = best;
-        }
-        last = best;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void kz_exact_select_kernel(const int* __restrict__ fail_list, int batch0, int64_t q_begin,
-                                                              const double* __restrict__ vals, const int* __restrict__ cand_idx,
-                                                              int64_t n_entries, int64_t n_i, int k,
-                                                              int exclude_self, const int64_t* __restrict__ self_ids,
-                                                              int metric, double p, double* __restrict__ out_dist,
-                                                              int64_t* __restrict__ out_ind, const int* __restrict__ dyn_n = nullptr,
-                                                              const long long* __restrict__ seg_off = nullptr, int* __restrict__ left = nullptr,
-                                                              int* __restrict__ left_cnt = nullptr, const long long* __restrict__ idx_off = nullptr,
-                                                              const int* __restrict__ seg_len = nullptr) {
-    __shared__ double s_v[4];
-    __shared__ int s_i[4];
-    extern __shared__ __attribute__((aligned(16))) char sel_sm[];   // k_eff doubles + k_eff ints (any k the host admits)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x;
-    if (dyn_n && !kz_spec_row_live(dyn_n, b, (int)gridDim.x)) return;
-    const int q = fail_list[batch0 + b];
-    if (q < 0) return;   // (grouped ranges, kz_range.h: a padding slot of a block)
-    // the row's values: all n_i of them (cand_idx == nullptr: entry i is index row i), or the survivors of kz_exact_chunk_kernel
-    // (n_entries (value, index row) pairs; unused places hold (+inf, INT_MAX) and are never reached: k_eff <= n_i real entries exist)
-    const double* v = vals + (int64_t)b * n_entries;
-    const int* vid = cand_idx ? cand_idx + (int64_t)b * n_entries : nullptr;
-    const int k_eff = (int)min((int64_t)(k + (exclude_self ? 1 : 0)), n_i);
-    if (seg_off) {
-        // range re-search (kz_range.h): row b's entries are the segment [seg_off[b], seg_off[b + 1]) of vals / cand_idx; a segment
-        // with fewer than k entries cannot answer its row -- the row is handed back (left)
-        const long long s0 = seg_off[b];
-        n_entries = seg_len ? (int64_t)seg_len[b] : seg_off[b + 1] - s0;   // (seg_len: the segments are not adjacent)
-        if (n_entries < k_eff) {
-            if (tid == 0) left[atomicAdd(left_cnt, 1)] = q;
-            return;
-        }
-        v = vals + s0;
-        vid = cand_idx + (idx_off ? idx_off[b] : s0);   // (idx_off: the rows of a group share one list of index rows)
-    }
-    // LONG SEGMENTS (a group's range: thousands of values per row, kz_range.h): k passes over all of them -- 82 k rows x 10 x 5 000
-    // loads, 4 ms of a 79 ms search -- become two.  Pass 1: every thread's smallest value; the k-th smallest T of those 256 minima is
-    // at or above the k-th smallest value of the segment.  Pass 2: the entries <= T (all ties included) go to a list in LDS; the k
-    // rounds below then run over that list.  The k smallest by (value, row) all lie at or below T: the same selection.  A list
-    // that would not fit (values dense at the bottom, duplicates) leaves the segment where it is.
-    constexpr int SEL_CAP = 1536;
-    __shared__ double c_v[SEL_CAP];
-    __shared__ int c_i[SEL_CAP];
-    __shared__ double s_min[256];
-    __shared__ double s_T;
-    __shared__ int s_cnt;
-    if (seg_off && n_entries >= 2048 && k_eff <= 256) {   // (uniform; every thread then owns >= 8 entries)
-        double m = INFINITY;
-        for (int64_t i = tid; i < n_entries; i += 256) m = fmin(m, v[i]);
-        s_min[tid] = m;
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        int rank = 0;
-        for (int o = 0; o < 256; ++o) {
-            const double om = s_min[o];
-            rank += (om < m || (om == m && o < tid)) ? 1 : 0;
-        }
-        if (rank == k_eff - 1) s_T = m;
-        __syncthreads();
-        const double Tv = s_T;
-        for (int64_t i = tid; i < n_entries; i += 256) {
-            const double x = v[i];
-            if (x <= Tv) {
-                const int pos = atomicAdd(&s_cnt, 1);
-                if (pos < SEL_CAP) {
-                    c_v[pos] = x;
-                    c_i[pos] = vid ? vid[i] : (int)i;
-                }
-            }
-        }
-        __syncthreads();
-        if (s_cnt <= SEL_CAP) {   // (uniform)
-            v = c_v;
-            vid = c_i;
-            n_entries = s_cnt;
-        }
-    }
-    double* s_sv = reinterpret_cast<double*>(sel_sm);
-    int* s_si = reinterpret_cast<int*>(s_sv + k_eff);
-    double pv = -1.0;  // values are >= 0
-    int pi = -1;
-    for (int r = 0; r < k_eff; ++r) {
-        double bv = INFINITY;
-        int bi = 0x7fffffff;
-        for (int64_t i = tid; i < n_entries; i += 256) {
-            const double x = v[i];
-            const int id = vid ? vid[i] : (int)i;
-            const bool after = (x > pv) || (x == pv && id > pi);
-            if (after && (x < bv || (x == bv && id < bi))) {
-                bv = x;
-                bi = id;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double ov = __shfl_xor(bv, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (ov < bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            s_v[wave] = bv;
-            s_i[wave] = bi;
-        }
-        __syncthreads();
-        bv = s_v[0];
-        bi = s_i[0];
-        for (int ww = 1; ww < 4; ++ww) {
-            if (s_v[ww] < bv || (s_v[ww] == bv && s_i[ww] < bi)) {
-                bv = s_v[ww];
-                bi = s_i[ww];
-            }
-        }
-        if (tid == 0) {
-            s_sv[r] = bv;
-            s_si[r] = bi;
-        }
-        pv = bv;
-        pi = bi;
-        __syncthreads();
-    }
-    if (wave == 0)
-        kz_emit_sorted<T>(s_sv, s_si, k_eff, k, exclude_self, self_ids ? self_ids[q] : q_begin + q, metric,
-                          out_dist + (int64_t)q * k, out_ind + (int64_t)q * k, lane, p);
-}
-
-// The dynamic LDS of a kz_exact_select_kernel<T> launch that selects k_sel neighbours per row -- the ONE rule of every launch site
-// (the whole-index fallback and kz_spec_rescue below, the grouped and per-row ranges of kz_range.h): k_sel doubles + k_sel ints.
-// The kernel's STATIC LDS (the lists of the long-segment pre-selection) comes on top of it: the runtime is asked for that size,
-// once per instantiation -- no constant here to keep in step with the kernel -- and a workgroup that needs more than 64 KiB in
-// all (k_sel >= 3749 of the 4096 the exact-only route admits) opts in, as every other launcher of this library does.  Beyond the
-// 160 KiB of a CU's LDS no launch can be made: KZ_ERR_UNSUPPORTED (unreachable while KZ_EXACT_MAX_K = 4096: 68.2 KiB).
-template <typename T>
-static int kz_exact_select_lds(int k_sel, size_t* dyn_bytes) {
-    static std::atomic<long long> static_cache{-1};
-    long long static_bytes = static_cache.load(std::memory_order_relaxed);
-    if (static_bytes < 0) {
-        hipFuncAttributes fa;
-        KZ_HIP(hipFuncGetAttributes(&fa, (const void*)kz_exact_select_kernel<T>));
-        static_bytes = (long long)fa.sharedSizeBytes;
-        static_cache.store(static_bytes, std::memory_order_relaxed);
-    }
-    const size_t dyn = (size_t)k_sel * 12 + 16;
-    const size_t total = (size_t)static_bytes + dyn;
-    if (total > (size_t)160 * 1024) {
-        kz_set_error("kz_knn: %d neighbours per query need %zu bytes of LDS in the exact selection kernel (%lld static), more than the 163840 of a CU",
-                     k_sel, total, static_bytes);
-        return KZ_ERR_UNSUPPORTED;
-    }
-    if (total > 65536)   // (per device: set whenever it is needed, the call is host bookkeeping)
-        KZ_HIP(hipFuncSetAttribute((const void*)kz_exact_select_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    *dyn_bytes = dyn;
-    return KZ_OK;
-}
+#include "kz_exact.h"
 
 // ---------------------------------------------------------------------------------------------------
 // host driver
@@ -1872,29 +248,29 @@ static int kz_launch_cand(kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
     } while (0)
 
 // fp16 and split-bf16 kernels: instantiated per list length in kz_knn_h_kp*.hip / kz_knn_bf_kp*.hip (parallel compilation)
-int kz_h_occupancy_kp16(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_h_occupancy_kp32(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_h_occupancy_kp64(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_h_occupancy_kp128(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_h_launch_kp16(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
-int kz_h_launch_kp32(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
-int kz_h_launch_kp64(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
-int kz_h_launch_kp128(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
-int kz_hd_occupancy_kp16(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_hd_occupancy_kp32(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_hd_occupancy_kp64(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_hd_occupancy_kp128(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int kz_hd_launch_kp16(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
-int kz_hd_launch_kp32(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
-int kz_hd_launch_kp64(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
-int kz_hd_launch_kp128(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
+int kz_h_occupancy_kp16(int n_slices, int* blocks_per_cu);
+int kz_h_occupancy_kp32(int n_slices, int* blocks_per_cu);
+int kz_h_occupancy_kp64(int n_slices, int* blocks_per_cu);
+int kz_h_occupancy_kp128(int n_slices, int* blocks_per_cu);
+int kz_h_launch_kp16(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
+int kz_h_launch_kp32(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
+int kz_h_launch_kp64(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
+int kz_h_launch_kp128(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
+int kz_hd_occupancy_kp16(int n_slices, int* blocks_per_cu);
+int kz_hd_occupancy_kp32(int n_slices, int* blocks_per_cu);
+int kz_hd_occupancy_kp64(int n_slices, int* blocks_per_cu);
+int kz_hd_occupancy_kp128(int n_slices, int* blocks_per_cu);
+int kz_hd_launch_kp16(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
+int kz_hd_launch_kp32(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
+int kz_hd_launch_kp64(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
+int kz_hd_launch_kp128(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
 bool kz_h64_supports(int n_slices);   // kz_knn_h64.hip: 64 queries per wave, K' = 16, ordinary (dual = 0) and dual-pass builds
-int kz_h64_occupancy(int n_slices, int dual, int* blocks_per_cu, int lds_pad);
+int kz_h64_occupancy(int n_slices, int dual, int* blocks_per_cu);
 int kz_h64_launch(int n_slices, int dual, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_bf_occupancy_kp16(int n_slices_bf, int* blocks_per_cu, int lds_pad);
-int kz_bf_occupancy_kp32(int n_slices_bf, int* blocks_per_cu, int lds_pad);
-int kz_bf_occupancy_kp64(int n_slices_bf, int* blocks_per_cu, int lds_pad);
-int kz_bf_occupancy_kp128(int n_slices_bf, int* blocks_per_cu, int lds_pad);
+int kz_bf_occupancy_kp16(int n_slices_bf, int* blocks_per_cu);
+int kz_bf_occupancy_kp32(int n_slices_bf, int* blocks_per_cu);
+int kz_bf_occupancy_kp64(int n_slices_bf, int* blocks_per_cu);
+int kz_bf_occupancy_kp128(int n_slices_bf, int* blocks_per_cu);
 int kz_bf_launch_kp16(int n_slices_bf, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
 int kz_bf_launch_kp32(int n_slices_bf, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
 int kz_bf_launch_kp64(int n_slices_bf, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
@@ -1967,82 +343,6 @@ __global__ __launch_bounds__(256) void kz_scatter_rows_kernel(const double* __re
 // candidate set cannot be certified under that tier's bound go down: fp16 / split-bf16 -> float32 operands (gathered into
 // a dense query block) -> exact float64 brute force.  The result is the float64 neighbour order at every tier.
 enum { KZ_TIER_F32 = 0, KZ_TIER_BF = 1, KZ_TIER_H = 2 };
-// neighbours per query on the exact-only route.  Selection state: 12 bytes per neighbour, 48 KiB of dynamic LDS at 4096 -- on top
-// of kz_exact_select_kernel's ~20 KiB of static LDS: more than 64 KiB in all from 3749 neighbours on, hence the opt-in of
-// kz_exact_select_lds (68.2 KiB of a CU's 160 at 4096)
-constexpr int KZ_EXACT_MAX_K = 4096;
-
-// The finalize launches of one pass: one per list region (the dynamic LDS follows the region's entry count: occupancy of
-// the gather).  fp.q_first / q_last / max_m are filled here.
-static int kz_launch_finalize(kz_ctx* ctx, KnnFinParams& fp, const KzListLayout& lay, int KP, int64_t q_count, int dtype) {
-    // the launches of this pass: [first query, last query), entries per query
-    struct Group { int64_t lo, hi; int max_m; } groups[KZ_MAX_REGIONS];
-    int n_groups = 0;
-    for (int rg = 0; rg < lay.n_regions; ++rg) {
-        const int64_t lo = (int64_t)(rg > 0 ? lay.qt_end[rg - 1] : 0) * KZ_TILE - fp.list_row0;
-        // (neighbouring regions with the same number of ranges -- forced ranges: all of them -- go out as ONE launch)
-        while (rg + 1 < lay.n_regions && lay.pieces[rg + 1] == lay.pieces[rg]) ++rg;
-        const int64_t hi = (int64_t)lay.qt_end[rg] * KZ_TILE - fp.list_row0;
-        Group g = {lo < 0 ? 0 : lo, hi > q_count ? q_count : hi, lay.pieces[rg] * lay.halves * KP};
-        if (g.hi > g.lo) groups[n_groups++] = g;
-    }
-    // The SMALL launches -- the last query tiles of a pass, swept in many short ranges so that they fill the chip: a few hundred
-    // queries with hundreds of list entries each, all latency (100k x 100k: 117 us after the 284 us of the main launch) -- go to
-    // the context's second stream and run BESIDE the large one (fork / join by events), unless that stream is busy with the
-    // reverse chain of a shared sweep or is the stream this call runs on.
-    const hipStream_t main_stream = ctx->stream;
-    const bool fork = n_groups >= 2 && ctx->stream2 && ctx->stream2 != main_stream && !ctx->stream2_busy;
-    int big = 0;
-    for (int g = 1; g < n_groups; ++g)
-        if (groups[g].hi - groups[g].lo > groups[big].hi - groups[big].lo) big = g;
-    if (fork) {
-        KZ_HIP(hipEventRecord(ctx->ev[7], main_stream));
-        KZ_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev[7], 0));
-    }
-    for (int pass = 0; pass < 2; ++pass) {   // (fork: the small launches first, on the second stream; then the large one)
-        for (int g = 0; g < n_groups; ++g) {
-            const bool side = fork && g != big;
-            if (fork ? (side != (pass == 0)) : pass == 1) continue;
-            const hipStream_t st = side ? ctx->stream2 : main_stream;
-            fp.q_first = groups[g].lo;
-            fp.q_last = groups[g].hi;
-            fp.max_m = groups[g].max_m;
-            fp.fast_div = ctx->fin_fast_div;
-            const int fin_blocks = (int)((fp.q_last - fp.q_first + KZ_FIN_QPB - 1) / KZ_FIN_QPB);
-            size_t fin_lds = (size_t)4 * kz_fin_wave_bytes(fp.max_m, fp.KSEL > 0 ? fp.KSEL : KP);
-            const bool wide = (fp.KSEL > 0 ? fp.KSEL : KP) > 160;   // the long-k route
-            // (many selected candidates + float32 rows on the fp16 tier, ordinary direction: kz_knn_fin_wide.h -- option "fin_wide")
-            // ("fin_wide" = 2: every launch that selects from several lists, KSEL > 0 -- the short-list routes -- takes it too)
-            const bool rows_vec = fp.d <= 256 && (fp.d & 3) == 0 && (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & 15u) == 0;
-            const bool wide2 = (wide || (KZ_K_FIN_WIDE >= 2 && fp.KSEL > 0)) && dtype == KZ_F32 && fp.tier_h && !fp.excl_floor && KZ_K_FIN_WIDE && rows_vec;
-            // (float32 rows of 260 .. 512 elements, 16-byte aligned: the build whose pipelined re-rank takes two loads per lane and row)
-            const bool two_chunks = !wide && !wide2 && dtype == KZ_F32 && fp.d > 256 && fp.d <= 512 && (fp.d & 3) == 0 &&
-                                    (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & 15u) == 0;
-            const void* fk = two_chunks ? (const void*)kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES_2, 2> : dtype == KZ_F32 ? (wide2 ? (const void*)kz_knn_finalize_wide_kernel<float, 4> : (wide ? (const void*)kz_knn_finalize_kernel<float, 8, 2> : (const void*)kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES>))
-                                             : (wide ? (const void*)kz_knn_finalize_kernel<double, 4, 2> : (const void*)kz_knn_finalize_kernel<double, KZ_FIN_ROWS, KZ_FIN_WAVES>);
-            if (wide2) fin_lds = (size_t)4 * kz_fin_wide_wave_bytes(fp.max_m, fp.KSEL);
-            if (fin_lds > 65536) KZ_HIP(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds));
-            if (wide2)
-                hipLaunchKernelGGL((kz_knn_finalize_wide_kernel<float, 4>), dim3(fin_blocks), dim3(256), fin_lds, st, fp);
-            else if (dtype == KZ_F32 && wide)
-                hipLaunchKernelGGL((kz_knn_finalize_kernel<float, 8, 2>), dim3(fin_blocks), dim3(256), fin_lds, st, fp);
-            else if (dtype == KZ_F32 && two_chunks)
-                hipLaunchKernelGGL((kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES_2, 2>), dim3(fin_blocks), dim3(256), fin_lds, st, fp);
-            else if (dtype == KZ_F32)
-                hipLaunchKernelGGL((kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES>), dim3(fin_blocks), dim3(256), fin_lds, st, fp);
-            else if (wide)
-                hipLaunchKernelGGL((kz_knn_finalize_kernel<double, 4, 2>), dim3(fin_blocks), dim3(256), fin_lds, st, fp);
-            else
-                hipLaunchKernelGGL((kz_knn_finalize_kernel<double, KZ_FIN_ROWS, KZ_FIN_WAVES>), dim3(fin_blocks), dim3(256), fin_lds, st, fp);
-        }
-    }
-    KZ_HIP(hipGetLastError());
-    if (fork) {
-        KZ_HIP(hipEventRecord(ctx->ev[11], ctx->stream2));
-        KZ_HIP(hipStreamWaitEvent(main_stream, ctx->ev[11], 0));
-    }
-    return KZ_OK;
-}
 
 // One launch of a fused kernel: list layout, scratch carve-up and the uploaded work table.
 struct KzPass {
@@ -2056,16 +356,18 @@ struct KzPass {
     int4* d_work;     // [W] (scratch)
 };
 
-// Plans the rounds (kz_plan_rounds), carves the context's scratch block and uploads the work table.  tier decides the
-// list layout (fp16: K' contiguous entries per list; float32 kernels: two lane-half lists per query and range).
-// tpw = query tiles per workgroup (wide fp16 builds: 2 or 3, kz_knn_h16.h "WIDE"): the plan is made for UNITS of tpw consecutive
-// query tiles -- one work item = one unit x one index range, w4.x = its first tile -- and converted back to tiles for the list
-// layout (a region ends on a unit boundary, the last one at the last tile).
-static int kz_prepare_pass(kz_ctx* ctx, int n_qtiles, int n_ytiles, int slots, int max_pieces, int KP, int tier, int64_t fail_rows,
-                           KzPass* out, int tpw = 1, int force_pieces = 0, int min_pieces = 0, bool boot_first = false) {
-    KzPlan pl;
-    kz_plan_pass(n_qtiles, n_ytiles, slots, max_pieces, (tier == KZ_TIER_H ? 1 : 2) * KP, tier == KZ_TIER_F32 ? 2 : 1,
-                 tier == KZ_TIER_H ? 1 : 0, tpw, force_pieces > 0 ? force_pieces : ctx->force_splits, min_pieces > KZ_K_MIN_SPLITS ? min_pieces : KZ_K_MIN_SPLITS, &pl);
+// The plan of one launch of a tier's fused kernel (kz_plan_pass): tier decides the list layout (fp16: K' contiguous entries per
+// list; float32 kernels: two lane-half lists per query and range).  tpw = query tiles per workgroup (2: the 64-query kernel,
+// kz_knn_h64.h): the plan is made for UNITS of tpw consecutive query tiles -- one work item = one unit x one index range, w4.x =
+// its first tile -- and converted back to tiles for the list layout (a region ends on a unit boundary, the last one at the last tile).
+static void kz_plan_tier_pass(const kz_ctx* ctx, int n_qtiles, int n_ytiles, int slots, int max_pieces, int KP, int tier, int tpw, int force_pieces,
+                              int min_pieces, KzPlan* pl) {
+    kz_plan_pass(n_qtiles, n_ytiles, slots, max_pieces, (tier == KZ_TIER_H ? 1 : 2) * KP, tier == KZ_TIER_F32 ? 2 : 1, tier == KZ_TIER_H ? 1 : 0, tpw,
+                 force_pieces > 0 ? force_pieces : ctx->force_splits, min_pieces > 1 ? min_pieces : 1, pl);
+}
+// Carves the context's scratch block for a planned pass and uploads its work table (n_ytiles, slots, tier, tpw: what the plan was made with).
+static int kz_prepare_pass(kz_ctx* ctx, const KzPlan& pl, int n_ytiles, int slots, int tier, int64_t fail_rows, KzPass* out, int tpw = 1,
+                           bool boot_first = false) {
     const KzListLayout& lay = pl.lay;
     const int W = pl.W;
     const size_t list_elems = pl.list_elems;
@@ -2107,7 +409,7 @@ static int kz_prepare_pass(kz_ctx* ctx, int n_qtiles, int n_ytiles, int slots, i
         // (fp16 kernel: query groups of four times what an XCD holds, see kz_plan_fill_work; "qgroup" overrides.  500k x 500k,
         //  ten ranges per query tile, main kernel: 24: 109.3 ms, 96: 107.6, 384: 102.5, 768 .. 4096: 101.9 .. 103.2)
         const int per_xcd = (slots + 7) / 8;
-        const int qgroup = KZ_K_QGROUP > 0 ? KZ_K_QGROUP : (tier == KZ_TIER_H && 4 * per_xcd > KZ_QGROUP ? 4 * per_xcd : KZ_QGROUP);
+        const int qgroup = tier == KZ_TIER_H && 4 * per_xcd > KZ_QGROUP ? 4 * per_xcd : KZ_QGROUP;
         kz_plan_fill_work(pl, n_ytiles, tpw, (KzWorkItem*)hw, qgroup);
         out->W0 = 0;
         if (boot_first) {
@@ -2277,6 +579,8 @@ static inline int64_t kz_rows_per_chunk(const kz_ctx* ctx, int KP_mem, bool wide
 // 4 .. "spec_rows" (64), as many as "spec_elems" / (n d) allows (a row of a 1 M x 200 index is 0.2 G multiply-adds: R = 8).  The
 // read-back that follows tells the host whether that was all (count <= R: the results are in place -- the exact float64 order, what
 // every route returns) or whether the ordinary re-search has to run (count > R: the speculative launches did nothing).
+// (two selection levels from two chunks on: a handful of rows, nothing else hides the single-level kernel's passes over the row)
+constexpr int KZ_SPEC_TWO_LEVEL_FROM = 2;
 struct KzSpec {   // (the buffers in reverse release order: qd, vals, cand_v, cand_i)
     int R = 0;            // rows the speculative launches cover (0: not launched)
     KzPoolBuf<int> cand_i;
@@ -2300,13 +604,13 @@ static int kz_spec_rows(const kz_ctx* ctx, const kz_matrix* index, int k_eff) {
 // chains of kz_knn_dual -- a buffer handed out here may have been released by work that is still in flight on the context's stream).
 // No memory: sp stays empty and nothing is speculated (the ordinary re-search will do).
 static int kz_spec_alloc(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* index, int k_eff) {
-    const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-    const int n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
-    const bool two_level = n_chunks >= 2 && k_sel <= KZ_EXACT_CHUNK;
+    KzExactSelection sel;
+    int rc = kz_exact_selection(index, k_eff, KZ_SPEC_TWO_LEVEL_FROM, &sel);
+    if (rc != KZ_OK) return rc;
     KzSpec s;   // (all or nothing)
-    int rc = s.vals.alloc(ctx, (size_t)R * (size_t)index->n * 8);
-    if (rc == KZ_OK && two_level) rc = s.cand_v.alloc(ctx, (size_t)R * n_chunks * k_sel * 8);
-    if (rc == KZ_OK && two_level) rc = s.cand_i.alloc(ctx, (size_t)R * n_chunks * k_sel * 4);
+    rc = s.vals.alloc(ctx, (size_t)R * (size_t)index->n * 8);
+    if (rc == KZ_OK && sel.two_level) rc = s.cand_v.alloc(ctx, sel.cand_entries(R) * 8);
+    if (rc == KZ_OK && sel.two_level) rc = s.cand_i.alloc(ctx, sel.cand_entries(R) * 4);
     if (rc == KZ_OK) rc = s.qd.alloc(ctx, kz_exact_lanes_qd_bytes(R, (int)index->d));
     if (rc != KZ_OK) return rc == KZ_ERR_NOMEM ? KZ_OK : rc;
     sp = std::move(s);
@@ -2316,58 +620,30 @@ static int kz_spec_alloc(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* index,
 // sp keeps its buffers whatever happens here: they are released by sp's owner, behind the stream the launches are on.
 static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query, int64_t q0, const int* fail_list, const int* fail_count,
                           const kz_matrix* index, int k, int exclude_self, const int64_t* d_self_ids, double* out_dist, int64_t* out_ind) {
-    const int metric = index->metric;
     const int k_eff = k + (exclude_self ? 1 : 0);
-    const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-    size_t sel_lds = 0;
-    {
-        const int rcs = index->dtype == KZ_F32 ? kz_exact_select_lds<float>(k_sel, &sel_lds) : kz_exact_select_lds<double>(k_sel, &sel_lds);
-        if (rcs != KZ_OK) return rcs;
-    }
-    const int n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
-    // (two selection levels from two chunks on: the single-level kernel passes k_eff times over the whole row with ONE workgroup --
-    //  135 us for 15 k values, k = 10; the chunk kernel selects from registers)
-    const bool two_level = n_chunks >= 2 && k_sel <= KZ_EXACT_CHUNK;
+    KzExactSelection sel;
+    int rc = kz_exact_selection(index, k_eff, KZ_SPEC_TWO_LEVEL_FROM, &sel);
+    if (rc != KZ_OK) return rc;
     if (!sp.vals.get()) {   // (not allocated ahead by the caller: kz_spec_alloc)
-        const int rc = kz_spec_alloc(ctx, sp, R, index, k_eff);
+        rc = kz_spec_alloc(ctx, sp, R, index, k_eff);
         if (rc != KZ_OK || !sp.vals.get()) return rc;
     }
-    const int dist_blocks = (int)((index->n + 3) / 4 < 256 ? (index->n + 3) / 4 : 256);   // (grid-stride; dead rows cost their dispatch)
-    const double* sel_v = two_level ? (const double*)sp.cand_v.get() : (const double*)sp.vals.get();
-    const int* sel_i = two_level ? (const int*)sp.cand_i.get() : (const int*)nullptr;
-    const int64_t n_entries = two_level ? (int64_t)n_chunks * k_sel : index->n;
-    bool lanes = false;
-    // (... from ~4 workgroups of 64 index rows per CU on: on a 15 k-row index its 235 workgroups run one per CU, all latency -- 73 us
-    //  against the cooperative kernel's 60)
-    if (index->dtype == KZ_F32 && index->n >= (int64_t)4 * KZ_XL_ROWS * ctx->n_cus) {
-        // (one pair per lane where that kernel applies: a pass over a 500 k x 200 index per FOUR rows made the cooperative kernel 2 ms
-        //  for 16 rows -- on the critical path behind the forward finalize; 0.3 ms)
-        const int rcl = kz_launch_exact_lanes(ctx, fail_list, 0, R, q0, query, index, metric, sp.vals.get(), &lanes, fail_count, sp.qd.get());
-        if (rcl != KZ_OK) return rcl;
-    }
-    if (lanes) {
-    } else if (index->dtype == KZ_F32) {
-        // (a handful of rows: short stretches of index rows per wave, so that the launch is wide -- 15 k rows: 235 x R / 4 workgroups)
-        int rpw = (int)(index->n / 1024);
-        rpw = rpw < 16 ? 16 : (rpw > 256 ? 256 : rpw);
-        if (!(ctx->exact_rows && kz_launch_exact_rows(ctx, fail_list, 0, R, q0, query, index, metric, sp.vals.get(), fail_count, rpw)))
-            hipLaunchKernelGGL(kz_exact_dist_kernel<float>, dim3(dist_blocks, R), dim3(256), 0, ctx->stream, fail_list, 0, q0,
-                               (const float*)query->raw, (const float*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric,
-                               index->mink_p, sp.vals.get(), fail_count);
-    } else {
-        hipLaunchKernelGGL(kz_exact_dist_kernel<double>, dim3(dist_blocks, R), dim3(256), 0, ctx->stream, fail_list, 0, q0,
-                           (const double*)query->raw, (const double*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric,
-                           index->mink_p, sp.vals.get(), fail_count);
-    }
-    if (two_level)
-        hipLaunchKernelGGL(k_sel >= 24 && ctx->exact_rows ? kz_exact_chunk_radix_kernel : kz_exact_chunk_kernel, dim3(n_chunks, R), dim3(256), 0,
-                           ctx->stream, (const double*)sp.vals.get(), index->n, k_sel, n_chunks, sp.cand_v.get(), sp.cand_i.get(), fail_count);
-    if (index->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(R), dim3(256), sel_lds, ctx->stream, fail_list, 0, q0, sel_v, sel_i, n_entries,
-                           index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p, out_dist, out_ind, fail_count);
-    else
-        hipLaunchKernelGGL(kz_exact_select_kernel<double>, dim3(R), dim3(256), sel_lds, ctx->stream, fail_list, 0, q0, sel_v, sel_i, n_entries,
-                           index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p, out_dist, out_ind, fail_count);
+    KzExactLaunch ln;
+    ln.dyn_n = fail_count;
+    // (one pair per lane from ~4 workgroups of 64 index rows per CU on: on a 15 k-row index its 235 workgroups run one per CU, all
+    //  latency -- 73 us against the cooperative kernel's 60.  Where it applies: a pass over a 500 k x 200 index per FOUR rows made the
+    //  cooperative kernel 2 ms for 16 rows -- on the critical path behind the forward finalize; 0.3 ms)
+    ln.try_lanes = index->dtype == KZ_F32 && index->n >= (int64_t)4 * KZ_XL_ROWS * ctx->n_cus;
+    ln.lanes_qd = sp.qd.get();
+    // (a handful of rows: short stretches of index rows per wave, so that the launch is wide -- 15 k rows: 235 x R / 4 workgroups)
+    const int rpw = (int)(index->n / 1024);
+    ln.rows_per_wave = rpw < 16 ? 16 : (rpw > 256 ? 256 : rpw);
+    ln.pair_blocks_max = 256;   // (grid-stride; dead rows cost their dispatch)
+    ln.two_level_from = KZ_SPEC_TWO_LEVEL_FROM;
+    rc = kz_exact_distances(ctx, fail_list, 0, R, q0, query, index, sp.vals.get(), ln);
+    if (rc != KZ_OK) return rc;
+    kz_exact_select(ctx, sel, fail_list, 0, R, q0, index, k, exclude_self, d_self_ids, sp.vals.get(), sp.cand_v.get(), sp.cand_i.get(), out_dist,
+                    out_ind, fail_count);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         kz_set_error("kz_knn: speculative exact re-search failed to launch: %s", hipGetErrorString(e));
@@ -2390,6 +666,20 @@ static KzResearch kz_research_wide(int lists) {   // (a caller's probe has found
     r.prec = 0;
     r.wide_lists = lists;
     return r;
+}
+
+// What every entry point asks of a query / index pair and its two output arrays (`who`: the entry point, as its messages name it)
+static int kz_require_pair(const char* who, const kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                           const void* out0, const void* out1) {
+    KZ_REQUIRE(ctx && query && index && out0 && out1, "%s: null argument", who);
+    KZ_REQUIRE(query->ctx == ctx && index->ctx == ctx, "%s: matrices belong to a different context", who);
+    KZ_REQUIRE(!query->raw_only && !index->raw_only, "%s: a rows-only matrix (kz_matrix_create rows_on_device = 3) cannot be searched", who);
+    KZ_REQUIRE(query->d == index->d, "%s: feature dimensions differ (%lld vs %lld)", who, (long long)query->d, (long long)index->d);
+    KZ_REQUIRE(query->dtype == index->dtype, "%s: query and index must have the same dtype", who);
+    KZ_REQUIRE(query->metric == index->metric && query->mink_p == index->mink_p, "%s: query and index were packed for different metrics", who);
+    KZ_REQUIRE(kz_metric_params_match(query, index), "%s: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index", who);
+    KZ_REQUIRE(q_begin >= 0 && q_count >= 0 && q_begin + q_count <= query->n, "%s: query row range out of bounds", who);
+    return KZ_OK;
 }
 
 static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index, int k,
@@ -2499,15 +789,10 @@ static int kz_escalate_ladder(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, c
 static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index, int k,
                        int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* d_dist,
                        int64_t* d_ind, kz_knn_stats* stats, KzDualPass* dual) {
-    KZ_REQUIRE(ctx && query && index && d_dist && d_ind, "kz_knn: null argument");
-    KZ_REQUIRE(query->ctx == ctx && index->ctx == ctx, "kz_knn: matrices belong to a different context");
-    KZ_REQUIRE(!query->raw_only && !index->raw_only, "kz_knn: a rows-only matrix (kz_matrix_create rows_on_device = 3) cannot be searched");
-    KZ_REQUIRE(query->d == index->d, "kz_knn: feature dimensions differ (%lld vs %lld)", (long long)query->d,
-               (long long)index->d);
-    KZ_REQUIRE(query->dtype == index->dtype, "kz_knn: query and index must have the same dtype");
-    KZ_REQUIRE(query->metric == index->metric && query->mink_p == index->mink_p, "kz_knn: query and index were packed for different metrics");
-    KZ_REQUIRE(kz_metric_params_match(query, index), "kz_knn: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index");
-    KZ_REQUIRE(q_begin >= 0 && q_count >= 0 && q_begin + q_count <= query->n, "kz_knn: query row range out of bounds");
+    {
+        const int rcp = kz_require_pair("kz_knn", ctx, query, q_begin, q_count, index, d_dist, d_ind);
+        if (rcp != KZ_OK) return rcp;
+    }
     KZ_REQUIRE(k >= 1, "kz_knn: Expected k > 0. Got %d", k);
     const int k_eff = k + (exclude_self ? 1 : 0);
     KZ_REQUIRE((int64_t)k_eff <= index->n, "kz_knn: Expected n_neighbors %s n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld",
@@ -2527,7 +812,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     const bool no_gemm_form = index->metric >= KZ_MANHATTAN;
     int KP = no_gemm_form ? 0 : kz_pick_list_len(k_eff);
     int KSEL = 0, long_pieces = 0;
-    if (KP == 0 && !dual && KZ_K_LONG_K && !no_gemm_form) {
+    if (KP == 0 && !dual && !no_gemm_form) {
         const int S = k_eff / 24 + 1 > 4 ? k_eff / 24 + 1 : 4;
         const int sel = k_eff + (k_eff / 8 > 16 ? k_eff / 8 : 16);
         // (finalize: 4 waves x (S 128 entries x 8 B + KSEL x 28 B) of LDS per workgroup)
@@ -2757,20 +1042,19 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     const bool q64 = q64_ok && !(dual && dual->no_q64) && (ctx->h_q64 == 1 || (ctx->h_q64 == 2 && dual && n_slices >= 9 &&
                                                      (q_count + 2 * KZ_TILE - 1) / (2 * KZ_TILE) >= (int64_t)4 * 2 * ctx->n_cus));
     int slots_cache[3] = {0, 0, 0};
-    int tpw_h = 1;   // query tiles per workgroup of the fp16 kernel this call runs (wide builds: 2 or 3)
+    const int tpw_h = q64 ? 2 : 1;   // query tiles per workgroup of the fp16 kernel this call runs
     auto slots_for = [&](int t, int* out) -> int {
         if (slots_cache[t] == 0) {
             int blocks_per_cu = 1;
             int rc0;
-            if (t == KZ_TIER_H && q64) {
-                rc0 = kz_h64_occupancy(n_slices, dual ? 1 : 0, &blocks_per_cu, KZ_K_LDS_PAD);
-                tpw_h = 2;
-            } else if (t == KZ_TIER_H && dual)
-                KZ_DISPATCH_KP(rc0, kz_hd_occupancy, (n_slices, &blocks_per_cu, &tpw_h, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
+            if (t == KZ_TIER_H && q64)
+                rc0 = kz_h64_occupancy(n_slices, dual ? 1 : 0, &blocks_per_cu);
+            else if (t == KZ_TIER_H && dual)
+                KZ_DISPATCH_KP(rc0, kz_hd_occupancy, (n_slices, &blocks_per_cu));
             else if (t == KZ_TIER_H)
-                KZ_DISPATCH_KP(rc0, kz_h_occupancy, (n_slices, &blocks_per_cu, &tpw_h, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
+                KZ_DISPATCH_KP(rc0, kz_h_occupancy, (n_slices, &blocks_per_cu));
             else if (t == KZ_TIER_BF)
-                KZ_DISPATCH_KP(rc0, kz_bf_occupancy, (n_slices, &blocks_per_cu, KZ_K_LDS_PAD));
+                KZ_DISPATCH_KP(rc0, kz_bf_occupancy, (n_slices, &blocks_per_cu));
             else
                 KZ_DISPATCH_CAND(rc0, kz_cand_occupancy, (&blocks_per_cu));
             if (rc0 != KZ_OK) return rc0;
@@ -2823,6 +1107,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         const int qt0 = (int)(cq_begin / KZ_TILE);
         int64_t cq_count = 0;
         int n_qtiles = 0, force_pieces = 0, max_pieces = 0;
+        KzPlan pl;
         // ---- schedule: which workgroup sweeps which (query tile, index-tile range): kz_prepare_pass above --------------
         for (;;) {
             cq_count = (q_count - c0 < max_rows_per_chunk) ? (q_count - c0) : max_rows_per_chunk;
@@ -2843,19 +1128,15 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             max_pieces = kz_max_pieces(KP, tier == KZ_TIER_F32 ? 2 : 1);
             if (dual && dual->max_entries > 0 && max_pieces > dual->max_entries / KP) max_pieces = dual->max_entries / KP;
             // The kernels address a launch's lists with 32-bit element offsets: a chunk whose plan would pass 2^32 entries (K' = 16,
-            // 2 M rows over 128 ranges) is halved -- the plan is host arithmetic, made here once more than kz_prepare_pass makes it.
-            KzPlan pl;
-            kz_plan_pass(n_qtiles, n_ytiles, slots, max_pieces, (tier == KZ_TIER_H ? 1 : 2) * KP, tier == KZ_TIER_F32 ? 2 : 1, tier == KZ_TIER_H ? 1 : 0,
-                         tier == KZ_TIER_H ? tpw_h : 1, force_pieces > 0 ? force_pieces : ctx->force_splits,
-                         min_pieces_call > KZ_K_MIN_SPLITS ? min_pieces_call : KZ_K_MIN_SPLITS, &pl);
+            // 2 M rows over 128 ranges) is halved.
+            kz_plan_tier_pass(ctx, n_qtiles, n_ytiles, slots, max_pieces, KP, tier, tier == KZ_TIER_H ? tpw_h : 1, force_pieces, min_pieces_call, &pl);
             if (pl.list_elems < ((size_t)1 << 32) || cq_count <= 8 * KZ_TILE || (dual && dual->raw_lists)) break;
             max_rows_per_chunk = ((cq_count / 2 + KZ_TILE - 1) / KZ_TILE) * KZ_TILE;
         }
         KzPass ps;
         // (range-0 bootstrap: the short-list routes of the ordinary 32-query kernel, from four ranges on)
-        const bool boot = tier == KZ_TIER_H && short_ord && !dual && !q64 && KZ_K_RANGE_BOOT && force_pieces >= 4;
-        int rc = kz_prepare_pass(ctx, n_qtiles, n_ytiles, slots, max_pieces, KP, tier, cq_count, &ps,
-                                 tier == KZ_TIER_H ? tpw_h : 1, force_pieces, min_pieces_call, boot);
+        const bool boot = tier == KZ_TIER_H && short_ord && !dual && !q64 && force_pieces >= 4;
+        int rc = kz_prepare_pass(ctx, pl, n_ytiles, slots, tier, cq_count, &ps, tier == KZ_TIER_H ? tpw_h : 1, boot);
         if (rc != KZ_OK) return rc;
         const KzListLayout& lay = ps.lay;
         const int W = ps.W;
@@ -2906,12 +1187,12 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             if (q64)
                 rc = kz_h64_launch(n_slices, 1, ctx, cp, W);
             else
-                KZ_DISPATCH_KP(rc, kz_hd_launch, (n_slices, ctx, cp, W, KZ_K_H_WPS, KZ_K_H_WIDE));
+                KZ_DISPATCH_KP(rc, kz_hd_launch, (n_slices, ctx, cp, W));
         } else if (tier == KZ_TIER_H && q64)
             rc = kz_h64_launch(n_slices, 0, ctx, cp, W);
         else if (tier == KZ_TIER_H && boot && ps.W0 > 0 && ps.W0 < W) {
             // range 0 of every query tile, the floor off its lists, then the other ranges
-            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W0, KZ_K_H_WPS, KZ_K_H_WIDE));
+            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W0));
             if (rc != KZ_OK) return rc;
             const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
             rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);   // (a buffer of this chunk: escalated sub-searches boot too)
@@ -2921,7 +1202,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             KZ_HIP(hipGetLastError());
             cp.qfloor = boot_floor.get();
             cp.work = d_work + ps.W0;
-            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W - ps.W0, KZ_K_H_WPS, KZ_K_H_WIDE));
+            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W - ps.W0));
             cp.work = d_work;
         } else if (tier == KZ_TIER_H) {
             if ((ctx->abl & 2) && getenv("KZ_STAMP_FILE")) {   // (diagnostic: a -DKZ_ABL_STAMP build of the fp16 units fills it)
@@ -2931,7 +1212,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 cp.log_meta = stamp_buf.get();
                 cp.log_keys = stamp_buf.get() + 2 * (size_t)W;
             }
-            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W, KZ_K_H_WPS, KZ_K_H_WIDE));
+            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W));
             cp.log_meta = nullptr;
             cp.log_keys = nullptr;
             if (rc == KZ_OK && (ctx->abl & 1) && !short_ord && ps.lay.n_regions == 1 && ps.lay.pieces[0] == 1) {
@@ -2948,7 +1229,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 KZ_HIP(hipGetLastError());
                 cp.qfloor = boot_floor.get();
                 KZ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-                KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W, KZ_K_H_WPS, KZ_K_H_WIDE));
+                KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W));
             }
         } else if (tier == KZ_TIER_BF)
             KZ_DISPATCH_KP(rc, kz_bf_launch, (n_slices, ctx, cp, W));
@@ -3014,7 +1295,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         fp.fail_list = fail_list;
         fp.fail_tau = ps.fail_tau;
         fp.err_ratio_bits = (unsigned long long*)(ctx->d_counters + 10);
-        if (fp.tier_h && metric == KZ_COSINE && (fp.KSEL > 0 ? fp.KSEL : KP) > 160 && KZ_K_FIN_WIDE && !(dual && dual->raw_lists)) {
+        if (fp.tier_h && metric == KZ_COSINE && (fp.KSEL > 0 ? fp.KSEL : KP) > 160 && !(dual && dual->raw_lists)) {
             // (hundreds of re-ranked candidates per query: the normalised float64 rows of the index, built once -- kz_pack.hip)
             rc = kz_matrix_norm64(index);
             if (rc != KZ_OK) return rc;
@@ -3143,7 +1424,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 //  300k x 300k x 96, clusters of very different spread: 9 968 rows to the exact kernels and 726 ms per call before, none and
                 //  169 ms now; lists of 128 for every call: bench.py "hard", k = 50, 118 -> 225 ms -- its lists of 64 were long enough)
                 next.min_kp = ((next.prec == 1 || wide_route) && KP_class < 64) ? 64 : 0;
-            } else if (KP == 16 && KSEL == 0 && KZ_K_ESC_SHORT && n_fail <= KZ_ESC_SHORT_MAX_ROWS) {
+            } else if (KP == 16 && KSEL == 0 && n_fail <= KZ_ESC_SHORT_MAX_ROWS) {
                 next.prec = 0;
                 next.more_lists = true;   // a handful of rows of a K' = 16 pass: more lists of 16
             } else {
@@ -3233,131 +1514,16 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
         n_fail_total += n_fail;
 
         if (n_fail > 0 && !rescued) {
-            // exact brute force in batches; the fail list lives at the end of the scratch block, the value matrix
-            // goes to a separate allocation so that the list is not overwritten by a scratch regrow.
-            KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-            // (released when this block ends, stream-ordered: fl, cand_v, cand_i)
-            KzPoolBuf<int> cand_i;
-            KzPoolBuf<double> cand_v;
-            KzPoolBuf<int> fl;
-            rc = fl.alloc(ctx, (size_t)n_fail * sizeof(int));  // stream-ordered pool: no device sync
+            // exact brute force against the whole index (kz_exact.h), behind the range re-search where that applies
+            KzExactTaken taken;
+            rc = kz_exact_whole_index(ctx, query, cq_begin, fail_list, ps.fail_tau, n_fail,
+                                      !exact_only && n_fail >= KZ_RANGE_MIN_ROWS && kz_range_shapes_ok(ctx, query, index), index, k, exclude_self,
+                                      d_self_ids, fp.out_dist, fp.out_ind, &taken);
             if (rc != KZ_OK) return rc;
-            KZ_HIP(hipMemcpyAsync(fl.get(), fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
-            // RANGE RE-SEARCH (kz_range.h): the exact kernels on the pairs that can matter; the rows it hands back -- and every
-            // row where it does not apply -- go on against the whole index below
-            int n_dense = n_fail;
-            if (!exact_only && n_fail >= KZ_RANGE_MIN_ROWS && kz_range_shapes_ok(ctx, query, index)) {
-                KzPoolBuf<int> left;
-                KzPoolBuf<double> tau;
-                rc = tau.alloc(ctx, (size_t)n_fail * 8);
-                if (rc == KZ_OK) rc = left.alloc(ctx, (size_t)n_fail * sizeof(int));
-                if (rc == KZ_OK && hipMemcpyAsync(tau.get(), ps.fail_tau, (size_t)n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
-                    kz_set_error("kz_knn: copying the bounds of the uncertified rows failed");
-                    rc = KZ_ERR_HIP;
-                }
-                long long pairs = 0, grouped = 0;
-                const bool no_mem = rc == KZ_ERR_NOMEM;   // (no room for the lists: the whole-index kernels as before)
-                if (rc == KZ_OK)
-                    rc = kz_range_rescue(ctx, query, cq_begin, fl.get(), tau.get(), n_fail, index, k, exclude_self, d_self_ids, fp.out_dist,
-                                         fp.out_ind, left.get(), &n_dense, &pairs, &grouped);
-                tau.reset();
-                if (no_mem) {
-                    left.reset();
-                    rc = KZ_OK;
-                } else {
-                    if (rc != KZ_OK) return rc;
-                    n_range += n_fail - n_dense;
-                    n_range_pairs += pairs;
-                    n_range_group += grouped;
-                    fl = std::move(left);   // (the rows handed back take the list's place)
-                }
-            }
-            n_fail = n_dense;
-            if (n_fail == 0) {
-                fl.reset();
-                KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-                KZ_HIP(hipStreamSynchronize(ctx->stream));
-                KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-                fb_ms += ms;
-                c0 += max_rows_per_chunk;
-                continue;
-            }
-            if (metric == KZ_COSINE && n_fail >= 64 && ctx->exact_rows) {   // (many rows: the normalised float64 index rows, once)
-                rc = kz_matrix_norm64(index);
-                if (rc != KZ_OK) return rc;
-            }
-            int64_t batch = ((int64_t)256 << 20) / (index->n * 8);
-            if (batch < 1) batch = 1;
-            if (batch > n_fail) batch = n_fail;
-            if (batch > 65535) batch = 65535;
-            void* vals = nullptr;
-            rc = kz_scratch(ctx, (size_t)batch * (size_t)index->n * 8, &vals);
-            if (rc != KZ_OK) return rc;
-            const int dist_blocks = (int)((index->n + 3) / 4);
-            const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-            size_t sel_lds = 0;
-            rc = index->dtype == KZ_F32 ? kz_exact_select_lds<float>(k_sel, &sel_lds) : kz_exact_select_lds<double>(k_sel, &sel_lds);
-            if (rc != KZ_OK) return rc;
-            // rows of more than four chunks: the selection in two levels (kz_exact_chunk_kernel)
-            const int n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
-            const bool two_level = n_chunks > 4 && k_sel <= KZ_EXACT_CHUNK;
-            if (two_level) {
-                rc = cand_v.alloc(ctx, (size_t)batch * n_chunks * k_sel * 8);
-                if (rc == KZ_OK) rc = cand_i.alloc(ctx, (size_t)batch * n_chunks * k_sel * 4);
-                if (rc != KZ_OK) return rc;
-            }
-            for (int b0 = 0; b0 < n_fail; b0 += (int)batch) {
-                const int nb = (n_fail - b0 < batch) ? (n_fail - b0) : (int)batch;
-                if (index->dtype == KZ_F32) {
-                    bool lanes = false;
-                    if (!no_gemm_form) {
-                        rc = kz_launch_exact_lanes(ctx, fl.get(), b0, nb, cq_begin, query, index, metric, (double*)vals, &lanes);
-                        if (rc != KZ_OK) return rc;
-                    }
-                    if (lanes) {
-                    } else if (kz_is_bool_metric(index->metric))
-                        kz_bool_launch_dist(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
-                    else if (no_gemm_form)
-                        kz_launch_family_dist<float>(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
-                    else if (ctx->exact_rows && kz_launch_exact_rows(ctx, fl.get(), b0, nb, cq_begin, query, index, metric, (double*)vals)) {
-                    } else
-                        hipLaunchKernelGGL(kz_exact_dist_kernel<float>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl.get(), b0,
-                                           cq_begin, (const float*)query->raw, (const float*)index->raw, query->sqn, index->sqn,
-                                           index->n, (int)index->d, metric, index->mink_p, (double*)vals);
-                    if (two_level)
-                        hipLaunchKernelGGL(k_sel >= 24 && ctx->exact_rows ? kz_exact_chunk_radix_kernel : kz_exact_chunk_kernel, dim3(n_chunks, nb), dim3(256), 0,
-                                           ctx->stream, (const double*)vals, index->n, k_sel, n_chunks, cand_v.get(), cand_i.get(), (const int*)nullptr);
-                    hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl.get(), b0, cq_begin,
-                                       two_level ? (const double*)cand_v.get() : (const double*)vals, two_level ? (const int*)cand_i.get() : (const int*)nullptr,
-                                       two_level ? (int64_t)n_chunks * k_sel : index->n, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p,
-                                       fp.out_dist, fp.out_ind);
-                } else {
-                    if (kz_is_bool_metric(index->metric))
-                        kz_bool_launch_dist(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
-                    else if (no_gemm_form)
-                        kz_launch_family_dist<double>(ctx, fl.get(), b0, nb, cq_begin, query, index, (double*)vals);
-                    else
-                        hipLaunchKernelGGL(kz_exact_dist_kernel<double>, dim3(dist_blocks, nb), dim3(256), 0, ctx->stream, fl.get(), b0,
-                                           cq_begin, (const double*)query->raw, (const double*)index->raw, query->sqn, index->sqn,
-                                           index->n, (int)index->d, metric, index->mink_p, (double*)vals);
-                    if (two_level)
-                        hipLaunchKernelGGL(k_sel >= 24 && ctx->exact_rows ? kz_exact_chunk_radix_kernel : kz_exact_chunk_kernel, dim3(n_chunks, nb), dim3(256), 0,
-                                           ctx->stream, (const double*)vals, index->n, k_sel, n_chunks, cand_v.get(), cand_i.get(), (const int*)nullptr);
-                    hipLaunchKernelGGL(kz_exact_select_kernel<double>, dim3(nb), dim3(256), sel_lds, ctx->stream, fl.get(), b0, cq_begin,
-                                       two_level ? (const double*)cand_v.get() : (const double*)vals, two_level ? (const int*)cand_i.get() : (const int*)nullptr,
-                                       two_level ? (int64_t)n_chunks * k_sel : index->n, index->n, k, exclude_self ? 1 : 0, d_self_ids, metric, index->mink_p,
-                                       fp.out_dist, fp.out_ind);
-                }
-            }
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) {
-                kz_set_error("kz_knn: exact fallback failed: %s", hipGetErrorString(e));
-                return KZ_ERR_HIP;
-            }
-            KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-            fb_ms += ms;
+            n_range += taken.range_rows;
+            n_range_pairs += taken.range_pairs;
+            n_range_group += taken.range_group_rows;
+            fb_ms += taken.ms;
         }
         c0 += max_rows_per_chunk;
     }

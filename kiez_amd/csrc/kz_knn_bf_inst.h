@@ -14,10 +14,10 @@ constexpr int KZ_TWM = KZ_BF_TWO_WAVE_MAX;
 #define KZ_BF_CAT(a, b) KZ_BF_CAT2(a, b)
 
 template <int KP, int NSR>
-static int kz_bf_occupancy(int* blocks_per_cu, int lds_pad) {
+static int kz_bf_occupancy(int* blocks_per_cu) {
     const void* kern = NSR <= KZ_TWM ? (const void*)kz_knn_cand_bf_kernel<KP, (NSR <= KZ_TWM ? NSR : KZ_TWM), 2>
                                      : (const void*)kz_knn_cand_bf_ov_kernel<KP, (NSR > KZ_TWM ? NSR : KZ_TWM + 1)>;
-    const int lds = (NSR <= KZ_TWM ? KZ_BF_LDS : KZ_OV_LDS) + lds_pad;
+    const int lds = (NSR <= KZ_TWM ? KZ_BF_LDS : KZ_OV_LDS);
     KZ_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int nb = 0;
     KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds));
@@ -28,10 +28,10 @@ static int kz_bf_occupancy(int* blocks_per_cu, int lds_pad) {
 template <int KP, int NSR>
 static int kz_launch_bf(kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
     if (NSR <= KZ_TWM)
-        hipLaunchKernelGGL((kz_knn_cand_bf_kernel<KP, (NSR <= KZ_TWM ? NSR : KZ_TWM), 2>), dim3(n_blocks), dim3(256), KZ_BF_LDS + KZ_K_LDS_PAD,
+        hipLaunchKernelGGL((kz_knn_cand_bf_kernel<KP, (NSR <= KZ_TWM ? NSR : KZ_TWM), 2>), dim3(n_blocks), dim3(256), KZ_BF_LDS,
                            ctx->stream, p);
     else
-        hipLaunchKernelGGL((kz_knn_cand_bf_ov_kernel<KP, (NSR > KZ_TWM ? NSR : KZ_TWM + 1)>), dim3(n_blocks), dim3(256), KZ_OV_LDS + KZ_K_LDS_PAD,
+        hipLaunchKernelGGL((kz_knn_cand_bf_ov_kernel<KP, (NSR > KZ_TWM ? NSR : KZ_TWM + 1)>), dim3(n_blocks), dim3(256), KZ_OV_LDS,
                            ctx->stream, p);
     KZ_HIP(hipGetLastError());
     return KZ_OK;
@@ -66,9 +66,9 @@ static int kz_launch_bf(kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
         }                                                 \
     } while (0)
 
-int KZ_BF_CAT(kz_bf_occupancy_kp, KZ_BF_KP)(int n_slices_bf, int* blocks_per_cu, int lds_pad) {
+int KZ_BF_CAT(kz_bf_occupancy_kp, KZ_BF_KP)(int n_slices_bf, int* blocks_per_cu) {
     int rc;
-    KZ_DISPATCH_BF_NSR(rc, kz_bf_occupancy, (blocks_per_cu, lds_pad), KZ_BF_KP);
+    KZ_DISPATCH_BF_NSR(rc, kz_bf_occupancy, (blocks_per_cu), KZ_BF_KP);
     return rc;
 }
 

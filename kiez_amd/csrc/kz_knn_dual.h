@@ -448,7 +448,7 @@ static KzResearch kz_dual_research(const kz_ctx* ctx, int n_fail, int64_t n_rows
     KzResearch rs;
     rs.prec = ((int64_t)n_fail * 2 > n_rows && ctx->esc_bf) ? 2 : -1;
     if (rs.prec == 2 || (int64_t)n_fail * 8 > n_rows || KPr >= 128) return rs;
-    if (KPr == 16 && KZ_K_ESC_SHORT && n_fail <= KZ_ESC_SHORT_MAX_ROWS)
+    if (KPr == 16 && n_fail <= KZ_ESC_SHORT_MAX_ROWS)
         rs.more_lists = true;
     else
         rs.min_kp = KPr * 4 < 128 ? KPr * 4 : 128;
@@ -905,13 +905,9 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     hipLaunchKernelGGL(kz_dual_c2key_kernel, dim3((unsigned)((a->n + 255) / 256)), dim3(256), 0, ctx->stream, ia->rowq, a->n, q_key.get());
     hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_iota.get(), (int)a_pad);
     KZ_HIP(hipGetLastError());
-    if (KZ_K_DUAL_DEAL) {
-        rc = kz_sort_pairs_f32_i32(ctx, q_key.get(), q_key_s.get(), q_iota.get(), q_sorted.get(), (int)a->n, 0);
-        if (rc != KZ_OK) return rc;
-        hipLaunchKernelGGL(kz_dual_deal_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_sorted.get(), a->n, a_pad, row_map.get());
-    } else {   // tuning knob "dual_deal" = 0: the query rows in their natural order
-        hipLaunchKernelGGL(kz_dual_natural_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, a->n, a_pad, row_map.get());
-    }
+    rc = kz_sort_pairs_f32_i32(ctx, q_key.get(), q_key_s.get(), q_iota.get(), q_sorted.get(), (int)a->n, 0);
+    if (rc != KZ_OK) return rc;
+    hipLaunchKernelGGL(kz_dual_deal_kernel, dim3((unsigned)((a_pad + 255) / 256)), dim3(256), 0, ctx->stream, q_sorted.get(), a->n, a_pad, row_map.get());
     KZ_HIP(hipGetLastError());
     rc = kz_himage_pack_permuted(a, row_map.get(), q_packed.get(), q_bias.get());
     if (rc != KZ_OK) return rc;
@@ -1019,11 +1015,14 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         KZ_HIP(hipGetLastError());
         {
             const int KP = KPs3;   // (KZ_DISPATCH_KP switches on `KP`)
-            int blocks_per_cu = 1, tpw = 1;
-            KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu, &tpw, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
+            int blocks_per_cu = 1;
+            KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu));
             if (rc != KZ_OK) return rc;
             KzPass ps;
-            rc = kz_prepare_pass(ctx, (int)s_tiles, (int)s3_tiles, kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus), 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s3);
+            const int slots = kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus);
+            KzPlan pl;
+            kz_plan_tier_pass(ctx, (int)s_tiles, (int)s3_tiles, slots, 256 / KP, KP, KZ_TIER_H, 1, force_s3, 0, &pl);
+            rc = kz_prepare_pass(ctx, pl, (int)s3_tiles, slots, KZ_TIER_H, 0, &ps);
             if (rc == KZ_OK) {
                 KnnCandParams cp;
                 memset(&cp, 0, sizeof(cp));
@@ -1038,7 +1037,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
                 cp.kg = b->kg;
                 cp.out_key = ps.out_key;
                 cp.out_idx = ps.out_idx;
-                KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W, KZ_K_H_WPS, KZ_K_H_WIDE));
+                KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W));
             }
             if (rc != KZ_OK) return rc;
             // (the rows owning these thresholds are rows of S, position j of the dealt image: bias q_bias.get()[j]; their events come from b)
@@ -1147,11 +1146,14 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         KZ_HIP(hipGetLastError());
         // ---- sample sweep: B x sample(A) with the ordinary kernel, lists of at most 256 entries per row -----------------------
         const int KP = KPs;   // (KZ_DISPATCH_KP switches on `KP`)
-        int blocks_per_cu = 1, tpw = 1;
-        KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu, &tpw, KZ_K_H_WPS, KZ_K_H_WIDE, KZ_K_LDS_PAD));
+        int blocks_per_cu = 1;
+        KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu));
         if (rc != KZ_OK) return rc;
         KzPass ps;
-        rc = kz_prepare_pass(ctx, (int)b_tiles, (int)s_tiles, kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus), 256 / KP, KP, KZ_TIER_H, 0, &ps, tpw, force_s);
+        const int slots = kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus);
+        KzPlan pl;
+        kz_plan_tier_pass(ctx, (int)b_tiles, (int)s_tiles, slots, 256 / KP, KP, KZ_TIER_H, 1, force_s, 0, &pl);
+        rc = kz_prepare_pass(ctx, pl, (int)s_tiles, slots, KZ_TIER_H, 0, &ps);
         if (rc != KZ_OK) return rc;
         KnnCandParams cp;
         memset(&cp, 0, sizeof(cp));
@@ -1166,7 +1168,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         cp.kg = b->kg;
         cp.out_key = ps.out_key;
         cp.out_idx = ps.out_idx;
-        KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W, KZ_K_H_WPS, KZ_K_H_WIDE));
+        KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W));
         if (rc != KZ_OK) return rc;
         hipLaunchKernelGGL(kz_dual_theta_kernel, dim3((unsigned)((b_pad + 3) / 4)), dim3(256), 0, ctx->stream, ps.out_key, ps.out_idx,
                            ps.lay, KP, rank, b->n, b_pad, ib->bias, ia->d_max, ib->d_max, ib->center->d_scale, theta.get(), floor_.get(),

@@ -1,5 +1,5 @@
 // Finalize of a query with MANY selected candidates (KSEL > 160: the fp16 tier's wide route -- 32 lists of 16, 256 selected -- and
-// the long-k route).  Same contract and same certification as kz_finalize_query (kz_knn.hip), which it falls back to for rows it
+// the long-k route).  Same contract and same certification as kz_finalize_query (kz_knn_finalize.h), which it falls back to for rows it
 // is not built for; what differs is the cost per candidate.  Round 5: on bench.py "hard" (300k queries, 512 list entries each, ~250
 // candidates within 2 eps of the k-th key) the generic path took 47 ms per launch, three quarters of it in three O(n^2) rank sorts
 // and in a re-rank that used 16 of 64 lanes.  Here:

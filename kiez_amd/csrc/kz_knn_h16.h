@@ -35,17 +35,11 @@ typedef _Float16 kz_f16x8 __attribute__((ext_vector_type(8)));
 #ifndef KZ_H_DMA_LATE
 #define KZ_H_DMA_LATE 1
 #endif
-// WIDE: ONE workgroup of 4 x WPS waves per CU instead of WPS workgroups of 4 waves: its WPS query tiles share one ring, so
-// every index slice is copied into the CU's LDS once instead of WPS times.  Measured on the scan-less diagnostic kernel of round 3 (profiles/r03_ablation.md section 2; builds
-// 1 5 6 7; 250k x 1M x 200, same box): bare loop 71.2 ms, + slice barriers 71.2 -> 72.9, + the LDS-DMA traffic 83.4 -- and
-// with a third of the DMA volume 75.3: the copies, not the barriers, are what the ring costs, in proportion to their volume.
-// What the wide build gives back: all waves of the CU now run in lockstep -- they reach every barrier and every tile epilogue
-// together, so nothing covers them (narrow: the three workgroups of a CU are in different phases).  Net, same-box: ordinary
-// kernel 250k x 1M x 200 -3 % ... +0.5 %, x 300 -1 % ... -4 %, shared sweep +1 % ... +10 %; 100k x 100k x 128 +3 %; K' = 64 +8 %.
-// Off by default (context option "h_wide" = 1 turns it on for K' = 16 with more than 8 slices); parity-tested both ways.
-template <int KP, int WPS, int NSR, bool DUAL = false, bool WIDE = false>
+// (A build with ONE workgroup of 4 x WPS waves per CU, its WPS query tiles on one ring, was measured in rounds 3 .. 6 and removed:
+//  the copies, not the barriers, are what the ring costs, but waves in lockstep leave nothing to cover barriers and epilogues --
+//  slower on every shared sweep, 250 k x 1 M x 300: 149.2 -> 151.4 ms.  profiles/r03_ablation.md section 2.)
+template <int KP, int WPS, int NSR, bool DUAL = false>
 struct KzHCfg {
-    static constexpr int TPW = WIDE ? WPS : 1;                         // query tiles (of 128 rows) per workgroup
     static constexpr bool LDS_LIST = KP <= 32;
     static constexpr bool LISTS_FIT = WPS <= 2 || KP == 16;   // K' = 32 lists do not fit beside the ring at 3 per CU
     // where the lists live (KzListRef, kz_knn_epi3.h): 1 = LDS, 2 = keys in LDS + rows in the output arrays, 0 = output arrays.
@@ -53,11 +47,8 @@ struct KzHCfg {
     // (one per CU -- the wide-row builds, WPS = 1 -- keep the list modes of two per CU)
     static constexpr int LMODE = (LDS_LIST && LISTS_FIT) ? 1 : (((KP == 64 && WPS <= 2) || (KP == 32 && WPS == 3)) ? 2 : 0);
     static constexpr bool IN_LDS = LMODE == 1;
-    // WIDE: eight slots, one barrier per four slices -- a barrier of a wide workgroup stops every wave of the CU (same-box,
-    // 250k x 1M x 200, ordinary kernel: 4 slots / 2 slices per barrier 91.8 ms, 8 / 4: 85.0 ms, 12 / 6: 90.0 ms, narrow 88-89.6;
-    // the wave groups staggered by a period with a barrier per 2 slices: 106 ms -- profiles/r03_ablation.md)
     // (one per CU: eight slots at every list length -- 160 KiB of LDS leave room for them beside the lists of K' = 32)
-    static constexpr int RING = WIDE ? 8 : (WPS == 1 ? 8 : ((WPS == 3 || KP == 32 || NSR < 4) ? 4 : 8));
+    static constexpr int RING = WPS == 1 ? 8 : ((WPS == 3 || KP == 32 || NSR < 4) ? 4 : 8);
     static constexpr int PERIOD = RING / 2;                            // slices per barrier: a slot is refilled one period before it is read
     // (three per CU: the workgroup must stay within 42 LDS granules of 1280 B -- 52.5 KiB with the lists of K' = 16 or the
     //  keys of K' = 32; the dual-pass build pays for its 1.5 KiB of thresholds and query offsets with 16 pool entries)
@@ -66,21 +57,20 @@ struct KzHCfg {
     static constexpr int BIAS_OFF = RING_BYTES;                        // 2 x 128 floats
     static constexpr int SYNC_OFF = BIAS_OFF + 1024;                   // 4 merge flags (+ padding)
     static constexpr int THETA_OFF = SYNC_OFF + 256;                   // dual pass: 3 x 64 threshold floats + 128 query offsets per tile
-    static constexpr int POOLK_OFF = THETA_OFF + (DUAL ? 768 + 768 * TPW : 0);    // [4 TPW waves][CAP] x 4 floats
-    static constexpr int POOLM_OFF = POOLK_OFF + 4 * TPW * CAP * 16;   // [4 TPW waves][CAP] x {code, next}
-    static constexpr int LIST_OFF = POOLM_OFF + 4 * TPW * CAP * 8;     // per tile: keys [KP][128], then rows [KP][128]
+    static constexpr int POOLK_OFF = THETA_OFF + (DUAL ? 768 + 768 : 0);    // [4 waves][CAP] x 4 floats
+    static constexpr int POOLM_OFF = POOLK_OFF + 4 * CAP * 16;   // [4 waves][CAP] x {code, next}
+    static constexpr int LIST_OFF = POOLM_OFF + 4 * CAP * 8;     // keys [KP][128], then rows [KP][128]
     static constexpr int LIST_BLOCK = LMODE == 1 ? KP * 128 * 8 : (LMODE == 2 ? KP * 128 * 4 : 0);
-    static constexpr int LDS_BYTES = LIST_OFF + TPW * LIST_BLOCK;
+    static constexpr int LDS_BYTES = LIST_OFF + LIST_BLOCK;
     static_assert(LDS_BYTES <= 160 * 1024, "workgroup exceeds the CU's LDS");
 };
 
-template <int KP, int NSR, int WPS, bool DUAL = false, bool WIDE = false>
-__global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn_cand_h_kernel(KnnCandParams p) {
-    using Cfg = KzHCfg<KP, WPS, NSR, DUAL, WIDE>;
-    constexpr int TPW = Cfg::TPW;
+template <int KP, int NSR, int WPS, bool DUAL = false>
+__global__ __launch_bounds__(256, WPS) void kz_knn_cand_h_kernel(KnnCandParams p) {
+    using Cfg = KzHCfg<KP, WPS, NSR, DUAL>;
     constexpr int R = Cfg::RING, P = Cfg::PERIOD, CAP = Cfg::CAP;
     static_assert((R & (R - 1)) == 0 && R == 2 * P, "slot arithmetic below: a power-of-two ring of two periods");
-    constexpr bool LATE = KZ_H_DMA_LATE == 2 || (KZ_H_DMA_LATE == 1 && WPS <= 2 && !WIDE);
+    constexpr bool LATE = KZ_H_DMA_LATE == 2 || (KZ_H_DMA_LATE == 1 && WPS <= 2);
     constexpr int IN_LDS = Cfg::LMODE;   // list storage mode (KzListRef)
     // at three waves per SIMD (168 VGPRs) the first fragments of the next tile are NOT fetched across the epilogue: the 16
     // registers they would occupy there are what keeps the stationary query tile out of scratch memory.  Exception: a tile
@@ -108,27 +98,20 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
 #endif
     const int t_begin = wd.y, t_end = wd.z, s = wd.w;
     const int total = (t_end - t_begin) * NSR;
-    // WIDE: waves 4 b .. 4 b + 3 take query tile wd.x + b; a workgroup at the end of the launch may reach past its last
-    // tile: those waves sweep along (barriers, and nothing else, need them) on the last valid tile's rows with every
-    // threshold at +inf -- no event, no list traffic, no output
-    const int wq = WIDE ? (wave & 3) : wave;            // wave within its query tile (uniform)
-    const int wq_v = WIDE ? ((tid >> 6) & 3) : (tid >> 6);
-    const int tb = WIDE ? (wave >> 2) : 0;              // tile within the workgroup (uniform)
-    const bool valid = !WIDE || wd.x + tb < p.n_qtiles;
-    const int qt = WIDE ? (valid ? wd.x + tb : p.n_qtiles - 1) : wd.x;
-
+    const int wave_v = tid >> 6;   // (the wave number per lane: vector address arithmetic without a copy out of the scalar register)
+    const int qt = wd.x;
     // this query's list in the output arrays (ONE list per query and index range, K' contiguous entries)
-    auto out_list_offset = [&]() { return kz_list_contig_off((int64_t)qt * KZ_TILE + 32 * wq_v + j, p.lay, KP, s); };
+    auto out_list_offset = [&]() { return kz_list_contig_off((int64_t)qt * KZ_TILE + 32 * wave_v + j, p.lay, KP, s); };
     KzCandState3<IN_LDS> st;
     if constexpr (IN_LDS == 1) {
-        st.list.k = (kz_lds_f32*)(smem + Cfg::LIST_OFF + tb * Cfg::LIST_BLOCK) + 32 * wq_v + j;
+        st.list.k = (kz_lds_f32*)(smem + Cfg::LIST_OFF) + 32 * wave_v + j;
         st.list.i_off = KP * 128;
     } else if constexpr (IN_LDS == 2) {
-        st.list.k = (kz_lds_f32*)(smem + Cfg::LIST_OFF + tb * Cfg::LIST_BLOCK) + 32 * wq_v + j;
+        st.list.k = (kz_lds_f32*)(smem + Cfg::LIST_OFF) + 32 * wave_v + j;
         st.list.ib = p.out_idx;
         {
             // (uniform: the offsets of this wave's query 0 and of its query 1 -- lists of consecutive queries are equally spaced)
-            const int64_t row0 = (int64_t)qt * KZ_TILE + 32 * wq;
+            const int64_t row0 = (int64_t)qt * KZ_TILE + 32 * wave;
             const int64_t o0 = kz_list_contig_off(row0, p.lay, KP, s);
             st.list.off_u = (unsigned)o0;
             st.list.stride = (unsigned)(kz_list_contig_off(row0 + 1, p.lay, KP, s) - o0);
@@ -144,8 +127,8 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
     pool.keys = (__attribute__((address_space(3))) f32x4e*)(smem + Cfg::POOLK_OFF) + wave * CAP;
     pool.meta = (__attribute__((address_space(3))) i32x2e*)(smem + Cfg::POOLM_OFF) + wave * CAP;
     // (seeded lists: KnnCandParams::qfloor)
-    const float fl = p.qfloor ? p.qfloor[(int64_t)(p.qt0 + qt) * KZ_TILE + 32 * wq_v + j] : -INFINITY;
-    if (h == 0 && valid) {  // the list belongs to the query: lane-half 0 owns it (kz_merge_logs3)
+    const float fl = p.qfloor ? p.qfloor[(int64_t)(p.qt0 + qt) * KZ_TILE + 32 * wave_v + j] : -INFINITY;
+    if (h == 0) {  // the list belongs to the query: lane-half 0 owns it (kz_merge_logs3)
 #pragma unroll 4
         for (int e = 0; e < KP; ++e) {
             st.list.kp()[e * KzListRef<IN_LDS>::KSTRIDE] = fl;
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
     if (total <= 0) {
         if constexpr (IN_LDS != 0) {
             const int64_t listoff = out_list_offset();
-            if (h == 0 && valid)
+            if (h == 0)
                 for (int e = 0; e < KP; ++e) {
                     p.out_key[listoff + e] = -INFINITY;
                     if constexpr (IN_LDS == 1) p.out_idx[listoff + e] = -1;   // (hybrid: the rows were initialised in place above)
@@ -163,7 +146,7 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
         }
         return;
     }
-    st.tau = valid ? fl : INFINITY;
+    st.tau = fl;
     KzBlockMin3<KP> bmin;
     bmin.init(fl);
     st.head = -1;
@@ -178,12 +161,10 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
     // the padding kz_himage_build allocates behind it (those slots are never read).
     const char* dma_src = reinterpret_cast<const char*>(p.ypack) + ((int64_t)t_begin * NSR) * 4096;   // uniform
     int dma_slot = 0;   // uniform: slot of the next slice to issue
-    int dma_turn = 0;   // WIDE: the group of four waves that copies the next slice (the groups take turns)
-    const int lane_off = (WIDE ? (tid & 255) : tid) * 16;
+    const int lane_off = tid * 16;
     auto dma_next = [&]() {
-        float* dst = ybuf + dma_slot * 1024 + wq * 256;  // wave-uniform LDS base (floats)
-        if (!WIDE || tb == dma_turn) kz_glds16_s(dma_src, (unsigned)lane_off, dst);
-        if constexpr (WIDE) dma_turn = dma_turn + 1 == TPW ? 0 : dma_turn + 1;
+        float* dst = ybuf + dma_slot * 1024 + wave * 256;  // wave-uniform LDS base (floats)
+        kz_glds16_s(dma_src, (unsigned)lane_off, dst);
         dma_src += 4096;
         dma_slot = (dma_slot + 1) & (R - 1);
     };
@@ -193,14 +174,14 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
     KzDualRef du;
     if constexpr (DUAL) {
         if (tid < 64) tbuf[tid] = p.theta[(int64_t)t_begin * KZ_TILE + tid];
-        du.qrow0 = (p.qt0 + qt) * KZ_TILE + 32 * wq;
+        du.qrow0 = (p.qt0 + qt) * KZ_TILE + 32 * wave;
         // this query's own offset: read back from LDS in every epilogue (a register held for the whole sweep was spilled at
         // three workgroups per CU, and reloaded behind a wait for the DMA ring)
-        if (h == 0) tbuf[192 + 32 * (tid >> 6) + j] = valid ? p.qnbias[du.qrow0 + j] : INFINITY;
+        if (h == 0) tbuf[192 + 32 * (tid >> 6) + j] = p.qnbias[du.qrow0 + j];
     }
     if (tid < 4) msync[tid] = 0;
     // stationary query fragments: lane (j, h) holds k = 16 u + 8 h + 0..7 of query row 32 wave + j
-    const float* qbase = p.qpack + ((int64_t)(p.qt0 + qt) * NSR) * 1024 + (h * KZ_TILE + 32 * wq_v + j) * 4;
+    const float* qbase = p.qpack + ((int64_t)(p.qt0 + qt) * NSR) * 1024 + (h * KZ_TILE + 32 * wave_v + j) * 4;
     kz_f16x8 qf[NSR];
 #pragma unroll
     for (int u = 0; u < NSR; ++u) qf[u] = *reinterpret_cast<const kz_f16x8*>(qbase + u * 1024);
@@ -360,7 +341,7 @@ __global__ __launch_bounds__(WIDE ? 256 * WPS : 256, WIDE ? 1 : WPS) void kz_knn
         // (lane number re-made here: the `h == 0` mask of the prologue, kept for this one use, cost a VGPR as SGPR spill space)
         int lane_now;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_now));
-        if (lane_now < 32 && valid) {
+        if (lane_now < 32) {
 #pragma unroll 4
             for (int e = 0; e < KP; ++e) {
                 p.out_key[listoff + e] = st.list.kp()[e * 128];

@@ -4,9 +4,9 @@
 #include "kz_knn_h64.h"
 
 template <int NSR, bool DUAL>
-static int kz_h64_occ(int* blocks_per_cu, int lds_pad) {
+static int kz_h64_occ(int* blocks_per_cu) {
     const void* kern = (const void*)kz_knn_cand_h64_kernel<NSR, DUAL>;
-    const int lds = KzH64Cfg<NSR, DUAL>::LDS_BYTES + lds_pad;
+    const int lds = KzH64Cfg<NSR, DUAL>::LDS_BYTES;
     KZ_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int nb = 0;
     KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds));
@@ -19,7 +19,7 @@ static int kz_h64_run(kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
     KnnCandParams pc = p;
     void* args[] = {&pc};
     KZ_HIP(hipLaunchKernel((const void*)kz_knn_cand_h64_kernel<NSR, DUAL>, dim3(n_blocks), dim3(256), args,
-                           (size_t)(KzH64Cfg<NSR, DUAL>::LDS_BYTES + KZ_K_LDS_PAD), ctx->stream));
+                           (size_t)KzH64Cfg<NSR, DUAL>::LDS_BYTES, ctx->stream));
     return KZ_OK;
 }
 
@@ -43,12 +43,12 @@ static int kz_h64_run(kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
 // slice counts this kernel is built for (kz_knn.hip asks before it plans a pass)
 bool kz_h64_supports(int n_slices) { return n_slices >= 4 && n_slices <= 13; }
 
-int kz_h64_occupancy(int n_slices, int dual, int* blocks_per_cu, int lds_pad) {
+int kz_h64_occupancy(int n_slices, int dual, int* blocks_per_cu) {
     int rc;
     if (dual)
-        KZ_DISPATCH_H64(rc, kz_h64_occ, (blocks_per_cu, lds_pad), true);
+        KZ_DISPATCH_H64(rc, kz_h64_occ, (blocks_per_cu), true);
     else
-        KZ_DISPATCH_H64(rc, kz_h64_occ, (blocks_per_cu, lds_pad), false);
+        KZ_DISPATCH_H64(rc, kz_h64_occ, (blocks_per_cu), false);
     return rc;
 }
 

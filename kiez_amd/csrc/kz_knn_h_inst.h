@@ -23,7 +23,7 @@
 #endif
 
 // Occupancy class of a slice count: three workgroups per CU (168 VGPRs, 53 KiB of LDS each) while the stationary query
-// tile fits, two (256 VGPRs, 80 KiB) beyond.  wps (tuning knob "h_wps") = 2 forces the two-workgroup build.
+// tile fits, two (256 VGPRs, 80 KiB) beyond.
 // Measured (MI355X, rocprof): d = 128, K' = 16: 2.93 ms at three per CU against 3.51 ms at two; d = 200, K' = 16 (single
 // fragment set, kz_knn_h16.h: ONE_SET): 96.8 against 102.2 ms; d = 200, K' = 64 (lists in the output arrays, 13 spilled
 // VGPRs at three per CU): 132 against 127 ms -- so beyond 8 slices only the K' = 16 build runs three per CU.
@@ -32,38 +32,16 @@
 constexpr int KZ_H_WPS3_MAX = 8;        // d <= 128: every list length
 constexpr int KZ_H_WPS3_MAX_KP16 = 13;  // d <= 208: K' = 16 only
 
-// wide != 0: the wide build (kz_knn_h16.h "WIDE": one workgroup of 4 x WPS waves per CU, WPS query tiles on one ring);
-// *tpw = query tiles per workgroup of the kernel returned.
-// The wide builds pay where the sweep is long and the epilogue light (K' = 16, more than 8 slices; measured same-box, ms narrow
-// -> wide: 250k x 1M x 200: 88.0 -> 85.0, x 300: 124.5 -> 119.3; 100k x 100k x 128: 2.86 -> 2.95; 500k x 500k x 200, K' = 64:
-// 103 -> 111: every wave of the CU reaches the tile epilogue at the same time); elsewhere the narrow builds run.
+// (an ordinary `if`: both builds of every slice count are instantiated, as they were while a tuning knob could force two per CU)
 template <int KP, int NSR>
-static const void* kz_h_kernel_narrow(int wps, int wide_opt, int* lds, int* tpw) {
+static const void* kz_h_kernel_narrow(int* lds) {
     constexpr bool three = NSR <= KZ_H_WPS3_MAX || (KP == 16 && NSR <= KZ_H_WPS3_MAX_KP16);
-    constexpr bool WIDE_OK = false;   // (round 6: the wide builds are no longer instantiated -- KZ_K_H_WIDE; was KP == 16 && NSR > 8)
-    const int wide = WIDE_OK ? wide_opt : 0;
-    if (three && wps != 2) {
+    if (three) {
         constexpr int N3 = three ? NSR : 2;
-        if constexpr (WIDE_OK) {
-            if (wide) {
-                *lds = KzHCfg<KP, 3, N3, KZ_H_DUALV, true>::LDS_BYTES;
-                *tpw = 3;
-                return (const void*)kz_knn_cand_h_kernel<KP, N3, 3, KZ_H_DUALV, true>;
-            }
-        }
         *lds = KzHCfg<KP, 3, NSR, KZ_H_DUALV>::LDS_BYTES;
-        *tpw = 1;
         return (const void*)kz_knn_cand_h_kernel<KP, N3, 3, KZ_H_DUALV>;
     }
-    if constexpr (WIDE_OK) {
-        if (wide) {
-            *lds = KzHCfg<KP, 2, NSR, KZ_H_DUALV, true>::LDS_BYTES;
-            *tpw = 2;
-            return (const void*)kz_knn_cand_h_kernel<KP, NSR, 2, KZ_H_DUALV, true>;
-        }
-    }
     *lds = KzHCfg<KP, 2, NSR, KZ_H_DUALV>::LDS_BYTES;
-    *tpw = 1;
     return (const void*)kz_knn_cand_h_kernel<KP, NSR, 2, KZ_H_DUALV>;
 }
 
@@ -73,35 +51,34 @@ static const void* kz_h_kernel_narrow(int wps, int wide_opt, int* lds, int* tpw)
 // No co-resident workgroup hides the tile epilogue -- but its cost is fixed while the MFMAs of a tile grow with d (48 slices:
 // 3.7x those of d = 200).  Same kernel, same contract, same epilogue; the list modes of two per CU, an eight-slot ring.
 template <int KP, int NSR>
-static const void* kz_h_kernel(int wps, int wide_opt, int* lds, int* tpw) {
+static const void* kz_h_kernel(int* lds) {
     if constexpr (NSR > 24) {
         *lds = KzHCfg<KP, 1, NSR, KZ_H_DUALV>::LDS_BYTES;
-        *tpw = 1;
         return (const void*)kz_knn_cand_h_kernel<KP, NSR, 1, KZ_H_DUALV>;
     } else {
-        return kz_h_kernel_narrow<KP, NSR>(wps, wide_opt, lds, tpw);
+        return kz_h_kernel_narrow<KP, NSR>(lds);
     }
 }
 
-// *blocks_per_cu = workgroups of the kernel resident per CU, *tpw = query tiles each of them takes
+// *blocks_per_cu = workgroups of the kernel resident per CU (each takes one query tile)
 template <int KP, int NSR>
-static int kz_h_occupancy(int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad) {
+static int kz_h_occupancy(int* blocks_per_cu) {
     int lds = 0;
-    const void* kern = kz_h_kernel<KP, NSR>(wps, wide, &lds, tpw);
-    KZ_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds + lds_pad));
+    const void* kern = kz_h_kernel<KP, NSR>(&lds);
+    KZ_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int nb = 0;
-    KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256 * *tpw, lds + lds_pad));
+    KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds));
     *blocks_per_cu = nb < 1 ? 1 : nb;
     return KZ_OK;
 }
 
 template <int KP, int NSR>
-static int kz_launch_h(kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide) {
-    int lds = 0, tpw = 1;
-    const void* kern = kz_h_kernel<KP, NSR>(wps, wide, &lds, &tpw);
+static int kz_launch_h(kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
+    int lds = 0;
+    const void* kern = kz_h_kernel<KP, NSR>(&lds);
     KnnCandParams pc = p;
     void* args[] = {&pc};
-    KZ_HIP(hipLaunchKernel(kern, dim3(n_blocks), dim3(256 * tpw), args, (size_t)(lds + KZ_K_LDS_PAD), ctx->stream));
+    KZ_HIP(hipLaunchKernel(kern, dim3(n_blocks), dim3(256), args, (size_t)lds, ctx->stream));
     return KZ_OK;
 }
 
@@ -150,20 +127,20 @@ static int kz_launch_h(kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wp
     } while (0)
 
 #ifdef KZ_H_WIDE_ROWS
-int KZ_HW_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad) {
+int KZ_HW_NAME(occupancy)(int n_slices, int* blocks_per_cu) {
     int rc;
-    KZ_DISPATCH_HW_NSR(rc, kz_h_occupancy, (blocks_per_cu, tpw, wps, wide, lds_pad), KZ_H_KP);
+    KZ_DISPATCH_HW_NSR(rc, kz_h_occupancy, (blocks_per_cu), KZ_H_KP);
     return rc;
 }
 
-int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide) {
+int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
     int rc;
-    KZ_DISPATCH_HW_NSR(rc, kz_launch_h, (ctx, p, n_blocks, wps, wide), KZ_H_KP);
+    KZ_DISPATCH_HW_NSR(rc, kz_launch_h, (ctx, p, n_blocks), KZ_H_KP);
     return rc;
 }
 #else
-int KZ_HW_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad);
-int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide);
+int KZ_HW_NAME(occupancy)(int n_slices, int* blocks_per_cu);
+int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
 
 // (65 .. 128 slices, d = 1025 .. 2048: the parity-split builds, kz_knn_hx_inst.h -- units of their own as well; two workgroups per
 //  work item, one query tile per item)
@@ -172,26 +149,23 @@ int KZ_HW_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_
 #else
 #define KZ_HX_FWD(base) KZ_H_CAT(kz_hx_##base##_kp, KZ_H_KP)
 #endif
-int KZ_HX_FWD(occupancy)(int n_slices, int* blocks_per_cu, int lds_pad);
+int KZ_HX_FWD(occupancy)(int n_slices, int* blocks_per_cu);
 int KZ_HX_FWD(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_items);
 
-int KZ_H_NAME(occupancy)(int n_slices, int* blocks_per_cu, int* tpw, int wps, int wide, int lds_pad) {
-    if (n_slices > 64) {
-        *tpw = 1;
-        return KZ_HX_FWD(occupancy)(n_slices, blocks_per_cu, lds_pad);
-    }
-    if (n_slices > 24) return KZ_HW_NAME(occupancy)(n_slices, blocks_per_cu, tpw, wps, wide, lds_pad);
+int KZ_H_NAME(occupancy)(int n_slices, int* blocks_per_cu) {
+    if (n_slices > 64) return KZ_HX_FWD(occupancy)(n_slices, blocks_per_cu);
+    if (n_slices > 24) return KZ_HW_NAME(occupancy)(n_slices, blocks_per_cu);
     int rc;
-    KZ_DISPATCH_H_NSR(rc, kz_h_occupancy, (blocks_per_cu, tpw, wps, wide, lds_pad), KZ_H_KP);
+    KZ_DISPATCH_H_NSR(rc, kz_h_occupancy, (blocks_per_cu), KZ_H_KP);
     return rc;
 }
 
 // n_blocks = work items of the plan: one workgroup each, two beyond 64 slices (kz_launch_hx starts 2 n_blocks workgroups)
-int KZ_H_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks, int wps, int wide) {
+int KZ_H_NAME(launch)(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
     if (n_slices > 64) return KZ_HX_FWD(launch)(n_slices, ctx, p, n_blocks);
-    if (n_slices > 24) return KZ_HW_NAME(launch)(n_slices, ctx, p, n_blocks, wps, wide);
+    if (n_slices > 24) return KZ_HW_NAME(launch)(n_slices, ctx, p, n_blocks);
     int rc;
-    KZ_DISPATCH_H_NSR(rc, kz_launch_h, (ctx, p, n_blocks, wps, wide), KZ_H_KP);
+    KZ_DISPATCH_H_NSR(rc, kz_launch_h, (ctx, p, n_blocks), KZ_H_KP);
     return rc;
 }
 #endif

@@ -19,12 +19,12 @@
 // *blocks_per_cu = workgroups of the kernel resident per CU (one); the planner's slots are HALF the resident workgroups, because
 // a work item is swept by two of them (kz_h_slots, kz_common.h)
 template <int KP, int NS>
-static int kz_hx_occupancy(int* blocks_per_cu, int lds_pad) {
+static int kz_hx_occupancy(int* blocks_per_cu) {
     const void* kern = (const void*)kz_knn_cand_hx_kernel<KP, NS, KZ_HX_DUALV>;
     const int lds = KzHxCfg<KP, KZ_HX_DUALV>::LDS_BYTES;
-    KZ_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds + lds_pad));
+    KZ_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int nb = 0;
-    KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds + lds_pad));
+    KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds));
     *blocks_per_cu = nb < 1 ? 1 : nb;
     return KZ_OK;
 }
@@ -35,7 +35,7 @@ static int kz_launch_hx(kz_ctx* ctx, const KnnCandParams& p, int n_items) {
     KnnCandParams pc = p;
     void* args[] = {&pc};
     KZ_HIP(hipLaunchKernel((const void*)kz_knn_cand_hx_kernel<KP, NS, KZ_HX_DUALV>, dim3(2 * n_items), dim3(256), args,
-                           (size_t)(KzHxCfg<KP, KZ_HX_DUALV>::LDS_BYTES + KZ_K_LDS_PAD), ctx->stream));
+                           (size_t)KzHxCfg<KP, KZ_HX_DUALV>::LDS_BYTES, ctx->stream));
     return KZ_OK;
 }
 
@@ -53,9 +53,9 @@ static int kz_launch_hx(kz_ctx* ctx, const KnnCandParams& p, int n_items) {
         }                                                 \
     } while (0)
 
-int KZ_HX_NAME(occupancy)(int n_slices, int* blocks_per_cu, int lds_pad) {
+int KZ_HX_NAME(occupancy)(int n_slices, int* blocks_per_cu) {
     int rc;
-    KZ_DISPATCH_HX_NSR(rc, kz_hx_occupancy, (blocks_per_cu, lds_pad), KZ_H_KP);
+    KZ_DISPATCH_HX_NSR(rc, kz_hx_occupancy, (blocks_per_cu), KZ_H_KP);
     return rc;
 }
 

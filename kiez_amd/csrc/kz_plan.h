@@ -102,7 +102,7 @@ static inline void kz_plan_rounds(int n_qtiles, int n_ytiles, int slots, int max
     *n_rounds = n;
 }
 
-// The plan of one pass.  tpw = query tiles per workgroup (wide fp16 builds: 2 or 3, kz_knn_h16.h "WIDE"): rounds are planned for
+// The plan of one pass.  tpw = query tiles per workgroup (2: the 64-query kernel, kz_knn_h64.h; else 1): rounds are planned for
 // UNITS of tpw consecutive query tiles -- one work item = one unit x one index range, x = its first tile -- and converted back
 // to tiles for the list layout (a region ends on a unit boundary, the last one at the last tile).  entries_per_list = K' in
 // the contiguous layout, 2 K' in the interleaved one.

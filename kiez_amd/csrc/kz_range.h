@@ -500,7 +500,7 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
     const int metric = index->metric, d = (int)index->d;
     const int k_eff = k + (exclude_self ? 1 : 0);
     const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-    size_t sel_lds = 0;   // (kz_exact_select_lds, kz_knn.hip: the one rule of every launch of the selection kernel)
+    size_t sel_lds = 0;   // (kz_exact_select_lds, kz_exact.h: the one rule of every launch of the selection kernel)
     {
         const int rcs = kz_exact_select_lds<float>(k_sel, &sel_lds);
         if (rcs != KZ_OK) return rcs;
@@ -571,6 +571,8 @@ static int kz_range_grouped(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int
     fm.reset(fm_new);
     if (rc != KZ_OK) return give_up(rc);
     {
+        // (not kz_exact_distances: the representatives take the rows kernel whatever "exact_rows" says, and the "index" of these
+        //  launches is the gathered block of failed rows -- a rule of this header's own)
         bool took = false;
         rc = kz_launch_exact_lanes(ctx, iota, 0, n_rep, 0, rm.get(), fm.get(), metric, rv.get(), &took);
         if (rc != KZ_OK) return give_up(rc);
@@ -704,7 +706,7 @@ static int kz_range_rescue(kz_ctx* ctx, kz_matrix* query, int64_t q0, const int*
     const int metric = index->metric;
     const int k_eff = k + (exclude_self ? 1 : 0);
     const int k_sel = (int)(k_eff < index->n ? k_eff : index->n);
-    size_t sel_lds = 0;   // (kz_exact_select_lds, kz_knn.hip: the one rule of every launch of the selection kernel)
+    size_t sel_lds = 0;   // (kz_exact_select_lds, kz_exact.h: the one rule of every launch of the selection kernel)
     {
         const int rcs = kz_exact_select_lds<float>(k_sel, &sel_lds);
         if (rcs != KZ_OK) return rcs;

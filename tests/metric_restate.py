@@ -1,7 +1,7 @@
 """numpy restatements of the four metrics the Minkowski-family VALU path computes beyond the Minkowski family itself:
 braycurtis, seuclidean, correlation and hamming.
 
-They are the specification the device follows (kz_common.h: kz_family_term / kz_family_add, kz_knn.hip: kz_family_dist_kernel):
+They are the specification the device follows (kz_common.h: kz_family_term / kz_family_add, kz_exact.h: kz_family_dist_kernel):
 each function evaluates ONE expression per pair, vectorised over all pairs of a query block and an index block, with the loop over
 features written out so that the order of the additions is the order the kernels use.  tests/test_metrics_extra.py checks them
 against scikit-learn bit for bit; the GPU tests check the device against scikit-learn through them.

@@ -1,5 +1,5 @@
 """kz_knn from 541 to 4096 neighbours per query: the range where no fused kernel runs and every row is answered by the exact float64
-kernels (kz_knn.hip: kz_exact_dist_* and the family / boolean distance kernels, kz_exact_chunk_kernel / kz_exact_chunk_radix_kernel,
+kernels (kz_exact.h: kz_exact_dist_* and the family / boolean distance kernels, kz_exact_chunk_kernel / kz_exact_chunk_radix_kernel,
 kz_exact_select_kernel, kz_emit_sorted).  The reference's SklearnNN takes any k <= n (sklearn_nearest_neighbors.py:51-65, 96-101);
 include/kiez_amd.h promises up to 4096.  Against the oracle (scikit-learn's brute force restated: float64 values, (value, smaller
 index) order, also at k = n):

@@ -1,6 +1,6 @@
 """The rest of SklearnNN.valid_metrics' Minkowski family (kiez/neighbors/exact/sklearn_nearest_neighbors.py:49 -> scikit-learn's
 VALID_METRICS): manhattan = cityblock = l1, chebyshev, minkowski with any p >= 1.  No inner-product form, so the call runs on a
-register-tiled VALU kernel and the exact float64 selection (kz_knn.hip: kz_family_dist_kernel / kz_exact_select_kernel) -- against the oracle's restatement of
+register-tiled VALU kernel and the exact float64 selection (kz_exact.h: kz_family_dist_kernel / kz_exact_select_kernel) -- against the oracle's restatement of
 scikit-learn's DistanceMetric32 / 64 (pinned by tests/golden/f64_manhattan.npz ... f32_cityblock.npz, generated from the real
 reference): indices bit-exact, distances to rounding.  `pytest -m gpu`."""
 import warnings

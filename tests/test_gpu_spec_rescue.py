@@ -28,8 +28,9 @@ def _gmm(rows, d, seed):
     return (x / np.sqrt((x * x).sum(axis=1, keepdims=True))).astype(np.float32)
 
 
-def _few_failures(ctx, qm, ym, k, lo=1, hi=16, exclude_self=False):
-    """An `eps_scale` at which the first pass leaves between lo and hi rows uncertified (speculation off while looking)."""
+def _few_failures(ctx, qm, ym, k, lo=1, hi=16, exclude_self=False, must=False):
+    """An `eps_scale` at which the first pass leaves between lo and hi rows uncertified (speculation off while looking).
+    must: finding none fails the test instead of skipping it."""
     from kiez_amd import _native as N
     ctx.set_option("spec_rows", 0)
     scale, lo_s, hi_s = 1.0, None, None
@@ -45,6 +46,8 @@ def _few_failures(ctx, qm, ym, k, lo=1, hi=16, exclude_self=False):
         else:
             hi_s = scale
             scale = scale / 2 if lo_s is None else 0.5 * (scale + lo_s)
+    if must:
+        pytest.fail("no eps_scale leaves a handful of rows uncertified on this data")
     pytest.skip("no eps_scale leaves a handful of rows uncertified on this data")
 
 
@@ -71,6 +74,22 @@ def test_a_handful_of_uncertified_rows_is_answered_in_place(ctx, metric, d, k, d
         np.testing.assert_allclose(d_on.numpy(), od, rtol=1e-5, atol=1e-7)
     else:
         np.testing.assert_allclose(d_on.numpy(), od, rtol=1e-12, atol=0)
+
+
+def test_a_large_index_takes_the_one_pair_per_lane_launch(ctx):
+    """70 001 index rows are at least 4 x 64 per CU of a 256-CU device: kz_spec_rescue then tries the one-pair-per-lane kernel
+    (kz_exact_lanes.h), here with the row count read on the device -- the other tests of this file, on 7 .. 9 k rows, never reach it."""
+    from kiez_amd import _native as N
+    from oracle import kiez_oracle as O
+    q, y = _gmm(3000, 32, 9), _gmm(70001, 32, 10)
+    qm, ym = N.DeviceMatrix(ctx, q, "euclidean"), N.DeviceMatrix(ctx, y, "euclidean")
+    _few_failures(ctx, qm, ym, 10, must=True)
+    ctx.set_option("spec_rows", 64)
+    dist, ind, st = N.knn(ctx, qm, ym, 10)
+    assert st["n_spec_rows"] == st["n_first_pass_fail"] > 0, st
+    od, oi = O.knn_exact(q, y, 10, "euclidean")
+    np.testing.assert_array_equal(ind.numpy(), oi)
+    np.testing.assert_allclose(dist.numpy(), od, rtol=1e-12, atol=0)
 
 
 def test_more_uncertified_rows_than_the_speculation_covers(ctx):

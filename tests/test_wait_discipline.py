@@ -99,8 +99,8 @@ def test_checker_sees_a_flat_instruction():
 
 def test_starved_builds_are_excused_by_name_and_only_when_they_spill():
     zero = ["ds_read_b128 v[64:67], v1 offset:8192", "s_waitcnt lgkmcnt(0)", MFMA, MFMA]
-    long_list = "_Z20kz_knn_cand_h_kernelILi128ELi7ELi3ELb0ELb0EEv13KnnCandParams"
-    short_list = "_Z20kz_knn_cand_h_kernelILi16ELi13ELi3ELb1ELb0EEv13KnnCandParams"
+    long_list = "_Z20kz_knn_cand_h_kernelILi128ELi7ELi3ELb0EEv13KnnCandParams"
+    short_list = "_Z20kz_knn_cand_h_kernelILi16ELi13ELi3ELb1EEv13KnnCandParams"
     for name, spills, want in ((long_list, True, []), (long_list, False, ["lgkm0"]), (short_list, True, ["lgkm0"])):
         text = kernel(zero, FLUSH, name=name)
         assert [f[1] for f in findings(text, {name} if spills else ())] == want

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B library with extra flags for kz_knn.hip (finalize / exact kernels, host driver): tools/ab_build_knn.sh <name> <-D flags...>
+# A/B library with extra flags for the kz_knn.hip unit (kz_knn_finalize.h, kz_exact.h, host driver): tools/ab_build_knn.sh <name> <-D flags...>
 # -> build/abl/libkiez_amd_<name>.so (every other object taken from the current build)
 set -e
 cd "$(dirname "$0")/.."
