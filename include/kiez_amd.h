@@ -299,6 +299,27 @@ int kz_hit_positions(kz_ctx* ctx, const int64_t* d_ind, const int64_t* d_gold, i
  * and a counting kernel in place of the selection; rows without gold cost no distance work.  Synchronises the context's stream. */
 int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                   const int64_t* d_gold, int64_t* d_rank);
+/* The same ranks under a POINTWISE hubness reduction -- ABI v7, additive: CSLS, LocalScaling 'standard', NICDM and MutualProximity
+ * 'normal' rescale a pair's distance d with one state of the query row and one of the index row (two each for MP), so the reduced
+ * distance w exists for EVERY index row, not for the K candidates alone.  d_rank[r] = #{ j : w_j < w_g or (w_j == w_g and j < g) }
+ * with g = d_gold[r], d = the distance kz_knn returns for the pair (the exact ranking value converted as kz_knn converts it) and
+ *   KZ_RANK_CSLS       w = 2 d - q_a[r] - t_a[j]                              (the means of the K forward / reverse distances)
+ *   KZ_RANK_LS         w = 1 - exp(-d^2 / (q_a[r] t_a[j]))                    (the K-th forward / reverse distance)
+ *   KZ_RANK_NICDM      w = d / sqrt(q_a[r] t_a[j])                            (the means)
+ *   KZ_RANK_MP_NORMAL  w = 1 - sf(d; q_a[r], q_b[r]) sf(d; t_a[j], t_b[j])    (nanmean and nanstd; sf: the normal survival function)
+ * in float64, the expressions of kz_csls / kz_local_scaling / kz_mp_normal: w of a pair is bit for bit what those write for it, so
+ * with lists over the whole index (K = index.n) the rank is the count over the transform's output row by (value, index row).  A NaN w
+ * ranks as +inf by row.  MP normal is exactly 1.0 for pairs far beyond both lists: they tie and go by row.
+ * d_q_a / d_q_b: [q_count] on the device, entry r for query row q_begin + r (kz_row_stats / kz_row_nanstats of the forward lists);
+ * d_t_a / d_t_b: [index.n] (the same of the reverse lists: the fit state).  d_q_b and d_t_b are for KZ_RANK_MP_NORMAL and must be
+ * NULL otherwise; an unknown kind, a missing or a surplus vector: KZ_ERR_INVALID.  Everything else as kz_gold_ranks. */
+#define KZ_RANK_CSLS 1
+#define KZ_RANK_LS 2
+#define KZ_RANK_NICDM 3
+#define KZ_RANK_MP_NORMAL 4
+int kz_gold_ranks_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                          const int64_t* d_gold, int kind, const double* d_q_a, const double* d_q_b,
+                          const double* d_t_a, const double* d_t_b, int64_t* d_rank);
 /* Reductions of a rank vector d_rank [n] (entries < 0: no rank).  h_hits[j] (host, j < n_k <= 64) = #(0 <= rank < h_ks[j]);
  * h_out[3] (host) = #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1) -- the float64 sum in a fixed order. */
 int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* h_ks, int n_k, int64_t* h_hits, double* h_out);

@@ -129,6 +129,7 @@ SYMBOLS = [
     ("kz_kocc_select", C.c_int, [_P, _P, _I64, C.c_int, C.c_double, _P, C.POINTER(_I64)]),
     ("kz_hit_positions", C.c_int, [_P, _P, _P, _I64, C.c_int, _P]),
     ("kz_gold_ranks", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
+    ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_rank_stats", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.c_int, C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -385,6 +386,36 @@ def gold_ranks(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev:
         raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
     rank = ctx.empty((q_count,), np.int64)
     _check(ctx.lib.kz_gold_ranks(ctx.handle, query.handle, q_begin, q_count, index.handle, gold_dev.ptr, rank.ptr), "kz_gold_ranks")
+    return rank
+
+
+# kz_gold_ranks_reduced's kinds (include/kiez_amd.h: KZ_RANK_*)
+RANK_CSLS, RANK_LS, RANK_NICDM, RANK_MP_NORMAL = 1, 2, 3, 4
+
+
+def gold_ranks_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev: DeviceArray, kind: int, q_state, t_state,
+                       q_begin: int = 0, q_count: Optional[int] = None) -> DeviceArray:
+    """kz_gold_ranks_reduced -> int64 [q_count] on the device: the rank of index row gold_dev[r] for query row q_begin + r against the
+    whole index under a pointwise hubness reduction (`kind`: RANK_CSLS, RANK_LS, RANK_NICDM, RANK_MP_NORMAL).  `q_state`: the
+    float64 DeviceArrays [q_count] of the query side, entry r for query row q_begin + r -- one (mean / last) or, for MP normal, two
+    (nanmean, nanstd); `t_state`: the same of the index side, [index rows].  A single DeviceArray stands for a 1-tuple."""
+    if q_count is None:
+        q_count = query.shape[0] - q_begin
+    if gold_dev.dtype != np.int64 or gold_dev.shape != (q_count,):
+        raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
+    q_state = (q_state,) if isinstance(q_state, DeviceArray) else tuple(q_state)
+    t_state = (t_state,) if isinstance(t_state, DeviceArray) else tuple(t_state)
+    for what, state, n in (("q_state", q_state, q_count), ("t_state", t_state, index.shape[0])):
+        if not 1 <= len(state) <= 2:
+            raise ValueError(f"{what}: one or two device vectors, got {len(state)}")
+        for v in state:
+            if not isinstance(v, DeviceArray) or v.dtype != np.float64 or v.shape != (n,):
+                raise ValueError(f"{what} must hold float64 device vectors of shape ({n},)")
+    qp = [v.ptr for v in q_state] + [None]
+    tp = [v.ptr for v in t_state] + [None]
+    rank = ctx.empty((q_count,), np.int64)
+    _check(ctx.lib.kz_gold_ranks_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, gold_dev.ptr, int(kind), qp[0], qp[1],
+                                         tp[0], tp[1], rank.ptr), "kz_gold_ranks_reduced")
     return rank
 
 

@@ -8,6 +8,7 @@
 //   DisSimLocal     kiez/hubness_reduction/dis_sim.py:96-107, 139-181
 //   _sort           kiez/hubness_reduction/base.py:72-87
 #include "kz_common.h"
+#include "kz_reduce.h"   // the pointwise formulas, shared with the rank count over the whole index (kz_gold_ranks.h)
 
 // (kz_np_pairwise_sum, numpy's pairwise summation: kz_common.h)
 
@@ -84,12 +85,7 @@ __global__ void kz_csls_kernel(const double* __restrict__ dist, const int64_t* _
     const double* a = dist + r * (int64_t)K;
     const int64_t* id = ind + r * (int64_t)K;
     const double r_test = kz_np_pairwise_sum(a, K) / (double)K;
-    for (int c = 0; c < K; ++c) {
-        double v = 2.0 * a[c];
-        v = v - r_test;
-        v = v - r_train[id[c]];
-        out[r * (int64_t)K + c] = v;
-    }
+    for (int c = 0; c < K; ++c) out[r * (int64_t)K + c] = kz_reduce_csls(a[c], r_test, r_train[id[c]]);
 }
 
 // LocalScaling (local_scaling.py:135-147)
@@ -101,29 +97,14 @@ __global__ void kz_ls_kernel(const double* __restrict__ dist, const int64_t* __r
     const int64_t* id = ind + r * (int64_t)K;
     if (nicdm) {
         const double r_s = kz_np_pairwise_sum(a, K) / (double)K;
-        for (int c = 0; c < K; ++c) out[r * (int64_t)K + c] = a[c] / sqrt(r_s * r_t[id[c]]);
+        for (int c = 0; c < K; ++c) out[r * (int64_t)K + c] = kz_reduce_nicdm(a[c], r_s, r_t[id[c]]);
     } else {
         const double r_s = a[K - 1];
-        for (int c = 0; c < K; ++c) {
-            const double d = a[c];
-            const double inner = (-1.0 * (d * d)) / (r_s * r_t[id[c]]);
-            out[r * (int64_t)K + c] = 1.0 - exp(inner);
-        }
+        for (int c = 0; c < K; ++c) out[r * (int64_t)K + c] = kz_reduce_ls(a[c], r_s, r_t[id[c]]);
     }
 }
 
-// scipy.stats.norm.sf(x, loc, scale) = ndtr(-(x-loc)/scale), cephes ndtr (scipy/special/xsf/cephes/ndtr.h)
-__device__ __forceinline__ double kz_ndtr(double a) {
-    const double SQRT1_2 = 0.70710678118654752440;
-    if (isnan(a)) return a;
-    const double x = a * SQRT1_2;
-    const double z = fabs(x);
-    if (z < SQRT1_2) return 0.5 + 0.5 * erf(x);
-    double y = 0.5 * erfc(z);
-    if (x > 0) y = 1.0 - y;
-    return y;
-}
-
+// (kz_ndtr, scipy.stats.norm.sf: kz_reduce.h)
 __global__ void kz_mp_normal_kernel(const double* __restrict__ dist, const int64_t* __restrict__ ind, int64_t n, int K,
                                     const double* __restrict__ mu_t, const double* __restrict__ sd_t,
                                     double* __restrict__ out) {
@@ -134,11 +115,8 @@ __global__ void kz_mp_normal_kernel(const double* __restrict__ dist, const int64
     double mu, sd;   // np.nanmean / np.nanstd (mutual_proximity.py:177-178): a list that ends in NaN keeps its finite entries
     kz_np_nanmean_nanstd(a, K, &mu, &sd);
     for (int c = 0; c < K; ++c) {
-        const double d = a[c];
-        const double p1 = kz_ndtr(-((d - mu) / sd));
         const int64_t t = id[c];
-        const double p2 = kz_ndtr(-((d - mu_t[t]) / sd_t[t]));
-        out[r * (int64_t)K + c] = 1.0 - p1 * p2;
+        out[r * (int64_t)K + c] = kz_reduce_mp_normal(a[c], mu, sd, mu_t[t], sd_t[t]);
     }
 }
 

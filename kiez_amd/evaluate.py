@@ -45,6 +45,19 @@ def _gold_vector(gold: Dict[Any, Any], n_rows: int) -> np.ndarray:
     return out
 
 
+def _gold_rows(gold, n_rows: int) -> np.ndarray:
+    """What every `gold_ranks` takes -- the dict of `hits`, or an integer array with one gold id per query row and -1 for none --
+    as the int64 vector the native calls read: _NO_GOLD where a row has no gold id."""
+    if isinstance(gold, dict):
+        return _gold_vector(gold, n_rows)
+    gold_arr = np.asarray(gold)
+    if gold_arr.shape != (n_rows,) or not np.issubdtype(gold_arr.dtype, np.integer):
+        raise ValueError(f"gold must be a dict or an integer array with one gold id per query row ({n_rows},), -1 for none")
+    gold_arr = gold_arr.astype(np.int64)
+    gold_arr[gold_arr < 0] = _NO_GOLD
+    return gold_arr
+
+
 def _rank_stats(ranks, ks: List[int], ctx: Optional[N.Context]):
     """([#(0 <= rank < k) for k in ks], #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1)) of a rank vector, reduced on the device."""
     if isinstance(ranks, N.DeviceArray):

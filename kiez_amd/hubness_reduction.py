@@ -154,6 +154,51 @@ class HubnessReduction(ABC):
         hub_dist, query_ind = self.transform(query_dist, query_ind, self.nn_algo.source_)
         return HubnessReduction._sort(hub_dist, query_ind, n_neighbors, ctx=self.ctx)
 
+    # ---- ranks of gold targets under the reduced distances -------------------------------------------
+    # why gold_ranks cannot rank under this reduction (None: it can, and `_rank_state` says how)
+    _no_rank_reason: Optional[str] = ("this reduction has no rank over the whole index: gold_ranks needs a reduction that is a function "
+                                      "of a pair's distance and one state per side (CSLS, LocalScaling, MutualProximity 'normal')")
+
+    def _rank_state(self, query_dist):
+        """(kind, query-side state vectors of the forward lists `query_dist`, index-side fit state) for kz_gold_ranks_reduced."""
+        raise NotImplementedError(self._no_rank_reason)
+
+    def gold_ranks_device(self, gold) -> N.DeviceArray:
+        """`gold_ranks` that leaves the int64 rank vector in HBM (evaluate.rank_metrics reduces it there)."""
+        if not self._gpu_nn:
+            raise NotImplementedError("gold_ranks under a hubness reduction needs one of the device-native reductions on the "
+                                      "MI355X SklearnNN backend")
+        nn = self.nn_algo
+        query, index, gold_dev = nn._gold_rank_operands(gold)   # (NotFittedError, single-source fit: as the plain call)
+        if self._no_rank_reason:
+            raise NotImplementedError(f"{type(self).__name__}: {self._no_rank_reason}")
+        # the forward lists of kneighbors(); when they are the shared sweep's cached result, the cache is left as it was found, so
+        # the kneighbors() that follows is served as it would have been
+        cached = nn._forward
+        query_dist, _ = nn.kneighbors_device(query=None, k=nn.n_candidates)
+        if cached is not None and cached[1] is query_dist:
+            nn._forward = cached
+        kind, q_state, t_state = self._rank_state(query_dist)
+        return N.gold_ranks_reduced(self.ctx, query, index, gold_dev, kind, q_state, t_state)
+
+    def gold_ranks(self, gold) -> np.ndarray:
+        """Exact 0-based rank of every source row's gold target against the WHOLE target index under the HUBNESS-REDUCED distances
+        (`SklearnNN.gold_ranks`: under the search metric; same `gold`, same result vector, -1 = no gold id).
+
+        CSLS, LocalScaling ('standard', 'nicdm') and MutualProximity 'normal' rescale a pair's distance d with one state of the
+        source row and one of the target row: w = f(d, a_i, b_j) is defined for every target row, as CSLS was defined.  The state
+        is what `fit` / `kneighbors` use -- statistics of the K = n_candidates forward and reverse neighbours -- d is the distance the
+        search returns for the pair, and rank_i = #{j : w_ij < w_ig or (w_ij == w_ig and j < g)}, NaN ranked as +inf by row.
+        * With lists over the whole index (n_candidates = n_target) this is the position of g in `transform`'s output row ordered
+          by (value, target row), bit for bit.
+        * With K < n_target, a gold row inside the candidate list need not have rank == its position in `kneighbors(k)`: a row
+          outside the list can have a smaller reduced distance.  Ranking all targets is the point.
+        * MutualProximity 'normal' is exactly 1.0 for pairs far beyond both lists (the product of two survival functions falls
+          below 2^-53): with small K most pairs tie there and are ordered by target row.
+        MutualProximity 'empiric' (its value depends on list membership) and DisSimLocal (its values come from its own gather of
+        the embeddings, not from the search's distances) raise NotImplementedError, as does a user-written reduction."""
+        return self.gold_ranks_device(gold).numpy()
+
     # ---- shared plumbing for the transform kernels -------------------------------------------------
     def _device_inputs(self, neigh_dist, neigh_ind):
         ctx = self.ctx
@@ -196,6 +241,9 @@ class NoHubnessReduction(HubnessReduction):
         n_neighbors = self._set_k_if_needed(k)
         return self.nn_algo.kneighbors(query=None, k=n_neighbors, return_distance=True)
 
+    def gold_ranks_device(self, gold) -> N.DeviceArray:
+        return self.nn_algo.gold_ranks_device(gold)   # (nothing is rescaled: the ranks under the search metric)
+
     def __repr__(self):
         return f"{self.__class__.__name__}()"
 
@@ -214,6 +262,13 @@ class CSLS(HubnessReduction):
         d = self.ctx.as_device(neigh_dist, np.float64)
         self._r_train_dev, _, _ = N.row_stats(self.ctx, d, mean=True)   # csls.py:90, hoisted into fit
         return self
+
+    _no_rank_reason = None
+
+    def _rank_state(self, query_dist):
+        check_is_fitted(self, "r_dist_train_")
+        r_test, _, _ = N.row_stats(self.ctx, query_dist, mean=True)
+        return N.RANK_CSLS, r_test, self._r_train_dev
 
     def transform(self, neigh_dist, neigh_ind, query):
         check_is_fitted(self, "r_dist_train_")
@@ -247,6 +302,14 @@ class LocalScaling(HubnessReduction):
         else:
             _, _, self._r_t_dev = N.row_stats(self.ctx, d, last=True)       # :136
         return self
+
+    _no_rank_reason = None
+
+    def _rank_state(self, query_dist):
+        check_is_fitted(self, "r_dist_t_to_s_")
+        nicdm = self.method == "nicdm"
+        r_s, _, last = N.row_stats(self.ctx, query_dist, mean=nicdm, last=not nicdm)
+        return (N.RANK_NICDM, r_s, self._r_t_dev) if nicdm else (N.RANK_LS, last, self._r_t_dev)
 
     def transform(self, neigh_dist, neigh_ind, query=None):
         check_is_fitted(self, "r_dist_t_to_s_")
@@ -289,6 +352,17 @@ class MutualProximity(HubnessReduction):
             self.mu_t_to_s_ = mu
             self.sd_t_to_s_ = sd
         return self
+
+    @property
+    def _no_rank_reason(self):
+        if self.method == "empiric":
+            return ("MutualProximity 'empiric' counts over the members of the two candidate lists: a target row outside the list "
+                    "has no value, so there is no rank over the whole index (use method='normal')")
+        return None
+
+    def _rank_state(self, query_dist):
+        check_is_fitted(self, ["mu_t_to_s_", "sd_t_to_s_"])
+        return N.RANK_MP_NORMAL, N.row_nanstats(self.ctx, query_dist), (self._mu_dev, self._sd_dev)
 
     def transform(self, neigh_dist, neigh_ind, query):
         check_is_fitted(self, ["mu_t_to_s_", "sd_t_to_s_", "neigh_dist_t_to_s_", "neigh_ind_t_to_s_"], all_or_any=any)
@@ -375,6 +449,9 @@ class DisSimLocal(HubnessReduction):
         mn = float(self._reduce_min(gmin.numpy()[0]))
         N._check(ctx.lib.kz_dsl_finalize(ctx.handle, out.ptr, n * K, mn, 1 if self.squared else 0), "kz_dsl_finalize")
         return self._finish(out, neigh_dist, neigh_ind)
+
+    _no_rank_reason = ("DisSimLocal's values come from its own gather of the embeddings around the candidate list's centroid, not from "
+                       "the search's distances: a target row outside the list has no value, so there is no rank over the whole index")
 
     def _reduce_min(self, local_min: float) -> float:
         """Hook for the multi-GPU path: the shift uses the GLOBAL minimum (dis_sim.py:171-173)."""

@@ -101,8 +101,19 @@ class Kiez:
         dist, ind = self.hubness.kneighbors(k)
         return (dist, ind) if return_distance else ind
 
-    def gold_ranks(self, gold, s_to_t: bool = True):
-        """Exact 0-based rank of every source row's gold target against the whole target index, under the SEARCH METRIC -- not
-        under the hubness-reduced distances, which exist for the `n_candidates` nearest rows only (`SklearnNN.gold_ranks`;
-        `evaluate.rank_metrics` turns the ranks into hits@k, mean rank and mean reciprocal rank)."""
-        return self.algorithm.gold_ranks(gold, s_to_t=s_to_t)
+    def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
+        """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
+        ranks into hits@k, mean rank and mean reciprocal rank).
+
+        `reduced=False`: under the SEARCH METRIC, whatever the hubness setting (`SklearnNN.gold_ranks`).  `reduced=True`: under the
+        hubness-reduced distances of the fitted reduction (`HubnessReduction.gold_ranks`: CSLS, LocalScaling 'standard' / 'nicdm',
+        MutualProximity 'normal'; none: the plain ranks) -- every target row is ranked by its reduced distance, with the state taken
+        from the `n_candidates` neighbours as `fit` / `kneighbors` use them, so a gold row outside the candidate list has a rank too.
+        MutualProximity 'empiric' and DisSimLocal raise NotImplementedError.  The fit state exists for the source -> target
+        direction: `reduced=True` with `s_to_t=False` raises ValueError."""
+        if not reduced:
+            return self.algorithm.gold_ranks(gold, s_to_t=s_to_t)
+        if not s_to_t:
+            raise ValueError("gold_ranks(reduced=True) ranks source rows against the target index only (s_to_t=True): the hubness "
+                             "reduction is fitted for that direction")
+        return self.hubness.gold_ranks(gold)

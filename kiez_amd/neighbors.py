@@ -361,9 +361,9 @@ class SklearnNN(NNAlgorithm):
         self.last_stats = stats
         return dist, ind
 
-    def gold_ranks_device(self, gold, s_to_t=True) -> N.DeviceArray:
-        """`gold_ranks` that leaves the int64 rank vector in HBM (evaluate.rank_metrics reduces it there)."""
-        from .evaluate import _NO_GOLD, _gold_vector
+    def _gold_rank_operands(self, gold, s_to_t=True):
+        """(query matrix, index matrix, gold ids int64 on the device) of a `gold_ranks` call, after its checks."""
+        from .evaluate import _gold_rows
 
         check_is_fitted(self, ["source_index", "target_index"], all_or_any=any)
         if self.source_equals_target:
@@ -373,16 +373,12 @@ class SklearnNN(NNAlgorithm):
         if index is None:   # e.g. target -> source after fit(..., only_fit_target=True)
             raise NotFittedError(f"'{type(self).__name__}' object has no attribute "
                                  f"'{'target_index' if s_to_t else 'source_index'}'")
-        n_rows = query.shape[0]
-        if isinstance(gold, dict):
-            gold_arr = _gold_vector(gold, n_rows)
-        else:
-            gold_arr = np.asarray(gold)
-            if gold_arr.shape != (n_rows,) or not np.issubdtype(gold_arr.dtype, np.integer):
-                raise ValueError(f"gold must be a dict or an integer array with one gold id per query row ({n_rows},), -1 for none")
-            gold_arr = gold_arr.astype(np.int64)
-            gold_arr[gold_arr < 0] = _NO_GOLD
-        return N.gold_ranks(self.ctx, self._matrix_for(query), index, self.ctx.to_device(gold_arr))
+        return self._matrix_for(query), index, self.ctx.to_device(_gold_rows(gold, query.shape[0]))
+
+    def gold_ranks_device(self, gold, s_to_t=True) -> N.DeviceArray:
+        """`gold_ranks` that leaves the int64 rank vector in HBM (evaluate.rank_metrics reduces it there)."""
+        query, index, gold_dev = self._gold_rank_operands(gold, s_to_t)
+        return N.gold_ranks(self.ctx, query, index, gold_dev)
 
     def gold_ranks(self, gold, s_to_t=True) -> np.ndarray:
         """Exact 0-based rank of every query row's gold answer against the WHOLE index: the position the gold row would hold in
@@ -393,10 +389,12 @@ class SklearnNN(NNAlgorithm):
         `gold`: the dict `evaluate.hits` takes ({query row: index row}), or an int64 array with one gold id per query row, -1 for
         none.  Returns a numpy int64 vector: -1 where a row has no gold id (or one that is no index row), else the rank.
 
-        These are ranks under the SEARCH METRIC, not under hubness-reduced distances: a hubness reduction rescales the
-        `n_candidates` nearest rows only, so a row outside the candidate list has no reduced distance to rank by (in the reference's
-        model either).  Raises NotFittedError before `fit` and NotImplementedError after a single-source fit (`fit(source)`):
-        sklearn's self-removal rule has no meaning for a rank.  `evaluate.rank_metrics` turns the ranks into hits@k, MR and MRR."""
+        These are ranks under the SEARCH METRIC.  The ranks under the hubness-reduced distances -- what MRR / hits@k after CSLS,
+        LocalScaling, NICDM or MutualProximity 'normal' are computed from -- come from `Kiez.gold_ranks(gold, reduced=True)`
+        (`HubnessReduction.gold_ranks`): those reductions are functions of a pair's distance and one state per side, defined for
+        every index row and not for the candidate list alone.  Raises NotFittedError before `fit` and NotImplementedError after a
+        single-source fit (`fit(source)`): sklearn's self-removal rule has no meaning for a rank.  `evaluate.rank_metrics` turns the
+        ranks into hits@k, MR and MRR."""
         return self.gold_ranks_device(gold, s_to_t).numpy()
 
     def kneighbors_device_both(self, k=None):
