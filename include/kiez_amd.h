@@ -320,6 +320,22 @@ int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t 
 int kz_gold_ranks_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                           const int64_t* d_gold, int kind, const double* d_q_a, const double* d_q_b,
                           const double* d_t_a, const double* d_t_b, int64_t* d_rank);
+/* The list those ranks are positions in -- ABI v7, additive: the k nearest index rows of every query row by the REDUCED distance w
+ * over the WHOLE index, not over a candidate list (kz_csls / kz_local_scaling / kz_mp_normal rescale K candidates; an index row
+ * outside them can have a smaller w).  Row r of d_w / d_ind ([q_count, k] on the device) holds the k index rows with the smallest w
+ * to query row q_begin + r and their w, ascending by (w, index row).  kind, the four state vectors, d and the expression for w are
+ * kz_gold_ranks_reduced's: w of a pair has the bits kz_csls / kz_local_scaling / kz_mp_normal write for it.  The order is that
+ * call's: a NaN w ranks as +inf and ties with it by index row (and is RETURNED as NaN), -inf is an ordinary smallest value, -0.0
+ * equals +0.0.  So for every r and c < k, kz_gold_ranks_reduced with d_gold[r] = d_ind[r, c] and the same inputs gives rank c.
+ * k < 1 or k > index.n: KZ_ERR_INVALID; k > KZ_KNN_REDUCED_MAX_K: KZ_ERR_UNSUPPORTED -- beyond it kz_gold_ranks_reduced is the
+ * tool: it ranks any row against the whole index without a list.  An unknown kind, a missing or a surplus vector, matrices that
+ * disagree (dtype, metric, exponent, seuclidean V): KZ_ERR_INVALID, as kz_gold_ranks_reduced.  No self-exclusion: the call is for
+ * two-sided data.  Runs the exact float64 value kernels of kz_knn for every query row and a two-level selection on integer keys;
+ * the result does not depend on the order anything runs in.  Synchronises the context's stream. */
+#define KZ_KNN_REDUCED_MAX_K 512
+int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                   int k, int kind, const double* d_q_a, const double* d_q_b, const double* d_t_a, const double* d_t_b,
+                   double* d_w, int64_t* d_ind);
 /* Reductions of a rank vector d_rank [n] (entries < 0: no rank).  h_hits[j] (host, j < n_k <= 64) = #(0 <= rank < h_ks[j]);
  * h_out[3] (host) = #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1) -- the float64 sum in a fixed order. */
 int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* h_ks, int n_k, int64_t* h_hits, double* h_out);

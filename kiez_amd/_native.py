@@ -130,6 +130,7 @@ SYMBOLS = [
     ("kz_hit_positions", C.c_int, [_P, _P, _P, _I64, C.c_int, _P]),
     ("kz_gold_ranks", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_rank_stats", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.c_int, C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -403,9 +404,18 @@ def gold_ranks_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, g
         q_count = query.shape[0] - q_begin
     if gold_dev.dtype != np.int64 or gold_dev.shape != (q_count,):
         raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
+    state = _reduction_state(q_state, t_state, q_count, index.shape[0])
+    rank = ctx.empty((q_count,), np.int64)
+    _check(ctx.lib.kz_gold_ranks_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, gold_dev.ptr, int(kind), *state,
+                                         rank.ptr), "kz_gold_ranks_reduced")
+    return rank
+
+
+def _reduction_state(q_state, t_state, q_count: int, n_index: int):
+    """The four state pointers (q_a, q_b, t_a, t_b; None where a side has one vector) of kz_gold_ranks_reduced / kz_knn_reduced."""
     q_state = (q_state,) if isinstance(q_state, DeviceArray) else tuple(q_state)
     t_state = (t_state,) if isinstance(t_state, DeviceArray) else tuple(t_state)
-    for what, state, n in (("q_state", q_state, q_count), ("t_state", t_state, index.shape[0])):
+    for what, state, n in (("q_state", q_state, q_count), ("t_state", t_state, n_index)):
         if not 1 <= len(state) <= 2:
             raise ValueError(f"{what}: one or two device vectors, got {len(state)}")
         for v in state:
@@ -413,10 +423,29 @@ def gold_ranks_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, g
                 raise ValueError(f"{what} must hold float64 device vectors of shape ({n},)")
     qp = [v.ptr for v in q_state] + [None]
     tp = [v.ptr for v in t_state] + [None]
-    rank = ctx.empty((q_count,), np.int64)
-    _check(ctx.lib.kz_gold_ranks_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, gold_dev.ptr, int(kind), qp[0], qp[1],
-                                         tp[0], tp[1], rank.ptr), "kz_gold_ranks_reduced")
-    return rank
+    return qp[0], qp[1], tp[0], tp[1]
+
+
+# neighbours per query of kz_knn_reduced (include/kiez_amd.h: KZ_KNN_REDUCED_MAX_K)
+KNN_REDUCED_MAX_K = 512
+
+
+def knn_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, kind: int, q_state, t_state, q_begin: int = 0,
+                q_count: Optional[int] = None) -> Tuple[DeviceArray, DeviceArray]:
+    """kz_knn_reduced -> (w float64 [q_count, k], ind int64 [q_count, k]) on the device: the k index rows with the smallest
+    hubness-reduced distance to query row q_begin + r over the WHOLE index, ascending by (w, index row) -- the list the ranks of
+    `gold_ranks_reduced` are positions in.  `kind`, `q_state` and `t_state` as there."""
+    if q_count is None:
+        q_count = query.shape[0] - q_begin
+    state = _reduction_state(q_state, t_state, q_count, index.shape[0])
+    k = int(k)
+    # (a k the call refuses -- it says why, before it writes anything -- gets no [q_count, k] arrays)
+    shape = (q_count, k) if 1 <= k <= min(index.shape[0], KNN_REDUCED_MAX_K) else (0, 0)
+    w = ctx.empty(shape, np.float64)
+    ind = ctx.empty(shape, np.int64)
+    _check(ctx.lib.kz_knn_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, k, int(kind), *state, w.ptr, ind.ptr),
+           "kz_knn_reduced")
+    return w, ind
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):

@@ -15,6 +15,7 @@
 //   3. kz_rank_count_kernel: one workgroup per (chunk of the index row range, listed row) counts its chunk and adds ONE integer to
 //      the row's d_rank entry -- integer counting: the result does not depend on the order the workgroups run in.
 // kz_gold_ranks_reduced is the same with step 3 counting the values' hubness-reduced distances (kz_rank_count_reduced_kernel below).
+// The list those ranks are positions in -- a selection in place of the count: kz_knn_reduced.h.
 // Reference: the n_s x n_t neighbour matrix of SklearnNN(n_candidates = n_target) followed by kiez.evaluate.hits
 // (kiez/evaluate/eval_metrics.py:23-61) is the only way the reference reaches a rank.
 #pragma once

@@ -139,16 +139,7 @@ class HubnessReduction(ABC):
         """base.py:89-105: forward candidates, rescale, final top-k."""
         if self._gpu_nn:
             od, oi = self.kneighbors_device(k)
-            src = self.nn_algo.source_
-            from .neighbors import _is_tensor, _torch_if_loaded
-            if _is_tensor(src):   # tensors in -> tensors out, on the source's device
-                torch = _torch_if_loaded()
-                self.ctx.sync()
-                out = (torch.as_tensor(od, device="cuda").clone().to(src.device),
-                       torch.as_tensor(oi, device="cuda").clone().to(src.device))
-                torch.cuda.current_stream().synchronize()   # before od / oi go back to our stream-ordered pool
-                return out
-            return od.numpy(), oi.numpy()
+            return self._to_host(od, oi)
         n_neighbors = self._set_k_if_needed(k)
         query_dist, query_ind = self.nn_algo.kneighbors(query=None, k=self.nn_algo.n_candidates, return_distance=True)
         hub_dist, query_ind = self.transform(query_dist, query_ind, self.nn_algo.source_)
@@ -199,6 +190,68 @@ class HubnessReduction(ABC):
         the embeddings, not from the search's distances) raise NotImplementedError, as does a user-written reduction."""
         return self.gold_ranks_device(gold).numpy()
 
+    # ---- neighbour lists by the reduced distance over the whole index ----------------------------------
+    def _whole_index_k(self, k) -> int:
+        """The k of `kneighbors_whole_index`: a positive int; never clamped to n_candidates (the list is not cut from the candidates)."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"kneighbors_whole_index needs a positive integer k, got {k!r}")
+        return int(k)
+
+    def kneighbors_whole_index_device(self, k: int):
+        """`kneighbors_whole_index` with the result left in HBM: (dist, ind) DeviceArrays."""
+        k = self._whole_index_k(k)
+        if not self._gpu_nn:
+            raise NotImplementedError("kneighbors_whole_index needs one of the device-native reductions on the MI355X SklearnNN backend")
+        nn = self.nn_algo
+        query, index = nn._two_sided_operands("kneighbors_whole_index")   # (NotFittedError, single-source fit: as gold_ranks)
+        if self._no_rank_reason:
+            raise NotImplementedError(f"{type(self).__name__}: {self._no_rank_reason}")
+        if k > index.shape[0]:
+            raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {k}, n_samples_fit = {index.shape[0]}")
+        if k > N.KNN_REDUCED_MAX_K:
+            raise NotImplementedError(f"kneighbors_whole_index returns up to {N.KNN_REDUCED_MAX_K} neighbours per query, got k = {k}: "
+                                      "beyond that, gold_ranks ranks any target row against the whole index")
+        # the state of gold_ranks_device, obtained the same way: a cached shared-sweep result is left as it was found
+        cached = nn._forward
+        query_dist, _ = nn.kneighbors_device(query=None, k=nn.n_candidates)
+        if cached is not None and cached[1] is query_dist:
+            nn._forward = cached
+        kind, q_state, t_state = self._rank_state(query_dist)
+        od, oi = N.knn_reduced(self.ctx, query, index, k, kind, q_state, t_state)
+        if nn._out_dtype(nn.target_index) == np.float32:
+            od = N.cast_f32(self.ctx, od)
+        return od, oi
+
+    def kneighbors_whole_index(self, k: int):
+        """The k nearest target rows of every source row by the HUBNESS-REDUCED distance over the WHOLE target index: the exact
+        CSLS / LocalScaling / NICDM / MutualProximity-'normal' neighbour list, as CSLS was defined over the full similarity matrix.
+
+        `kneighbors(k)` rescales the `n_candidates` nearest targets by raw distance and returns the k best of THOSE; a target
+        outside the candidates can have a smaller reduced distance.  Here every target row is a candidate: w = f(d, a_i, b_j)
+        with the state `fit` / `kneighbors` use (statistics of the `n_candidates` forward and reverse neighbours) is evaluated for
+        every pair, and row i of the result holds the k targets with the smallest w, ascending by (w, target row), NaN last (as
+        +inf, by row).  These are the lists `gold_ranks` ranks in: `gold_ranks(gold)[i] == c` exactly when `ind[i, c] == gold[i]`,
+        so hits@k from either agree.  `k` is required, at most min(n_target, 512), and is NOT clamped to `n_candidates`.
+
+        Returns (dist, ind) like `kneighbors`: numpy arrays, or tensors when fitted on tensors; dist in the dtype `kneighbors`
+        returns.  NoHubnessReduction returns the plain `kneighbors(k)`.  MutualProximity 'empiric', DisSimLocal and user-written
+        reductions raise NotImplementedError (no value outside the list), a single-source fit too (two-sided data only)."""
+        od, oi = self.kneighbors_whole_index_device(k)
+        return self._to_host(od, oi)
+
+    def _to_host(self, od: N.DeviceArray, oi: N.DeviceArray):
+        """A device result as `kneighbors` hands it out: tensors in -> tensors out on the source's device, else numpy."""
+        src = self.nn_algo.source_
+        from .neighbors import _is_tensor, _torch_if_loaded
+        if _is_tensor(src):
+            torch = _torch_if_loaded()
+            self.ctx.sync()
+            out = (torch.as_tensor(od, device="cuda").clone().to(src.device),
+                   torch.as_tensor(oi, device="cuda").clone().to(src.device))
+            torch.cuda.current_stream().synchronize()   # before od / oi go back to our stream-ordered pool
+            return out
+        return od.numpy(), oi.numpy()
+
     # ---- shared plumbing for the transform kernels -------------------------------------------------
     def _device_inputs(self, neigh_dist, neigh_ind):
         ctx = self.ctx
@@ -243,6 +296,13 @@ class NoHubnessReduction(HubnessReduction):
 
     def gold_ranks_device(self, gold) -> N.DeviceArray:
         return self.nn_algo.gold_ranks_device(gold)   # (nothing is rescaled: the ranks under the search metric)
+
+    # (nothing is rescaled: the search's own lists ARE over the whole index)
+    def kneighbors_whole_index_device(self, k: int):
+        return self.kneighbors_device(self._whole_index_k(k))
+
+    def kneighbors_whole_index(self, k: int):
+        return self.kneighbors(self._whole_index_k(k))
 
     def __repr__(self):
         return f"{self.__class__.__name__}()"

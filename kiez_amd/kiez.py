@@ -101,6 +101,19 @@ class Kiez:
         dist, ind = self.hubness.kneighbors(k)
         return (dist, ind) if return_distance else ind
 
+    def kneighbors_whole_index_device(self, k: int):
+        """Like `kneighbors_whole_index` but the (dist, ind) result stays in HBM as DeviceArrays."""
+        return self.hubness.kneighbors_whole_index_device(k)
+
+    def kneighbors_whole_index(self, k: int, return_distance: bool = True):
+        """The k nearest targets of every source row by the hubness-reduced distance over the WHOLE target index
+        (`HubnessReduction.kneighbors_whole_index`: CSLS, LocalScaling 'standard' / 'nicdm', MutualProximity 'normal'; none: the plain
+        `kneighbors(k)`), where `kneighbors(k)` rescales the `n_candidates` nearest targets only.  The lists `gold_ranks(gold,
+        reduced=True)` ranks in: hits@k of the two agree.  `k` is required, at most min(n_target, 512), and not clamped to
+        `n_candidates`.  MutualProximity 'empiric' and DisSimLocal raise NotImplementedError."""
+        dist, ind = self.hubness.kneighbors_whole_index(k)
+        return (dist, ind) if return_distance else ind
+
     def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
         """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
         ranks into hits@k, mean rank and mean reciprocal rank).

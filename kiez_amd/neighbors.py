@@ -361,19 +361,25 @@ class SklearnNN(NNAlgorithm):
         self.last_stats = stats
         return dist, ind
 
-    def _gold_rank_operands(self, gold, s_to_t=True):
-        """(query matrix, index matrix, gold ids int64 on the device) of a `gold_ranks` call, after its checks."""
-        from .evaluate import _gold_rows
-
+    def _two_sided_operands(self, what, s_to_t=True):
+        """(query matrix, index matrix) of a call that ranks every index row for every query row (`what`: `gold_ranks`,
+        `kneighbors_whole_index`), after the checks they share."""
         check_is_fitted(self, ["source_index", "target_index"], all_or_any=any)
         if self.source_equals_target:
-            raise NotImplementedError("gold_ranks needs a two-sided fit (fit(source, target)): sklearn's self-removal rule of a "
+            raise NotImplementedError(f"{what} needs a two-sided fit (fit(source, target)): sklearn's self-removal rule of a "
                                       "single-source search has no meaning for a rank")
         query, index, _ = self._direction(s_to_t)
         if index is None:   # e.g. target -> source after fit(..., only_fit_target=True)
             raise NotFittedError(f"'{type(self).__name__}' object has no attribute "
                                  f"'{'target_index' if s_to_t else 'source_index'}'")
-        return self._matrix_for(query), index, self.ctx.to_device(_gold_rows(gold, query.shape[0]))
+        return self._matrix_for(query), index
+
+    def _gold_rank_operands(self, gold, s_to_t=True):
+        """(query matrix, index matrix, gold ids int64 on the device) of a `gold_ranks` call, after its checks."""
+        from .evaluate import _gold_rows
+
+        query, index = self._two_sided_operands("gold_ranks", s_to_t)
+        return query, index, self.ctx.to_device(_gold_rows(gold, query.shape[0]))
 
     def gold_ranks_device(self, gold, s_to_t=True) -> N.DeviceArray:
         """`gold_ranks` that leaves the int64 rank vector in HBM (evaluate.rank_metrics reduces it there)."""
