@@ -1,6 +1,7 @@
 // Stage 3 of kz_knn (kz_knn.hip): the EXACT FLOAT64 STAGE -- the distance kernels that answer a batch of query rows against the whole
 // index, the selection kernels, and the one host path through them.  Three callers: the fallback of kz_knn_impl
-// (kz_exact_whole_index), the speculative rescue (kz_spec_rescue) and kz_gold_ranks (kz_exact_distances, then its own count kernel).
+// (kz_exact_whole_index), the speculative rescue (kz_spec_rescue) and the whole-index entry points kz_gold_ranks / kz_knn_reduced
+// (kz_exact_walk: kz_exact_distances per batch, then their own count or selection).
 // They run the same rule with different launch geometry: what differs is spelled out in KzExactLaunch, nowhere else.
 // (kz_range.h launches some of these kernels on gathered segments and representative rows by rules of its own.)
 #pragma once
@@ -908,8 +909,14 @@ static void kz_exact_select(kz_ctx* ctx, const KzExactSelection& sel, const int*
                            index->n, k, exclude_self ? 1 : 0, d_self_ids, index->metric, index->mink_p, out_dist, out_ind, dyn_n);
 }
 
-// Query rows per batch of a walk over listed rows: 256 MiB of values, at most a grid's y extent.  vals: the context's scratch block.
-static int kz_exact_batch_rows(kz_ctx* ctx, const kz_matrix* index, int n_rows, int* batch_out, double** vals) {
+// The begin of a walk over n_rows listed rows against the whole index.  Many rows of a cosine search: the normalised float64 index rows,
+// once -- what the float32 kernels then read.  -> query rows per batch: 256 MiB of values, at most a grid's y extent; vals: the
+// context's scratch block.
+static int kz_exact_begin(kz_ctx* ctx, kz_matrix* index, int n_rows, int* batch_out, double** vals) {
+    if (index->metric == KZ_COSINE && n_rows >= 64 && ctx->exact_rows) {
+        const int rc = kz_matrix_norm64(index);
+        if (rc != KZ_OK) return rc;
+    }
     int64_t batch = ((int64_t)256 << 20) / (index->n * 8);
     if (batch < 1) batch = 1;
     if (batch > n_rows) batch = n_rows;
@@ -920,9 +927,25 @@ static int kz_exact_batch_rows(kz_ctx* ctx, const kz_matrix* index, int n_rows, 
     *vals = (double*)v;
     return rc;
 }
-// (many rows of a cosine search: the normalised float64 index rows, once -- what the float32 kernels then read)
-static int kz_exact_prepare_index(kz_ctx* ctx, kz_matrix* index, int n_rows) {
-    return index->metric == KZ_COSINE && n_rows >= 64 && ctx->exact_rows ? kz_matrix_norm64(index) : KZ_OK;
+// The walk of the whole-index entry points (kz_gold_ranks.h, kz_knn_reduced.h) behind kz_exact_begin: per batch of rows
+// q_begin + fl[b0 .. b0 + nb) the value matrix (kz_exact_distances), then per_batch(b0, nb) -- the caller's launches on it.  Ends
+// synchronised with the stream.
+template <typename F>
+static int kz_exact_walk(const char* who, kz_ctx* ctx, const int* fl, int n_rows, int batch, double* vals, int64_t q_begin, const kz_matrix* query,
+                         const kz_matrix* index, F per_batch) {
+    for (int b0 = 0; b0 < n_rows; b0 += batch) {
+        const int nb = n_rows - b0 < batch ? n_rows - b0 : batch;
+        const int rc = kz_exact_distances(ctx, fl, b0, nb, q_begin, query, index, vals);
+        if (rc != KZ_OK) return rc;
+        per_batch(b0, nb);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        kz_set_error("%s: exact kernels failed: %s", who, hipGetErrorString(e));
+        return KZ_ERR_HIP;
+    }
+    return KZ_OK;
 }
 
 // (kz_range.h needs kz_knn_impl and therefore comes later in the translation unit)
@@ -977,11 +1000,9 @@ static int kz_exact_whole_index(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, 
         }
     }
     if (n_fail > 0) {
-        rc = kz_exact_prepare_index(ctx, index, n_fail);
-        if (rc != KZ_OK) return rc;
         int batch = 0;
         double* vals = nullptr;
-        rc = kz_exact_batch_rows(ctx, index, n_fail, &batch, &vals);
+        rc = kz_exact_begin(ctx, index, n_fail, &batch, &vals);
         if (rc != KZ_OK) return rc;
         KzExactSelection sel;
         rc = kz_exact_selection(index, k + (exclude_self ? 1 : 0), KzExactLaunch().two_level_from, &sel);

@@ -5,7 +5,7 @@
 // reduced distance, so the k best of the rescaled candidates and the k best of all rows are two different lists.
 //
 // The host loop is kz_gold_ranks_impl's over all query rows: the float64 value matrix of the exact stage batch by batch
-// (kz_exact_distances), w of every pair by that header's kz_rank_reduce -- the bits the transform kernels write -- and a SELECTION
+// (kz_exact_walk), w of every pair by that header's kz_rank_reduce -- the bits the transform kernels write -- and a SELECTION
 // where it has a count, in two levels whatever the index size:
 //   1. kz_knn_reduced_chunk_kernel: one workgroup per (chunk of KZ_KNNR_CHUNK index rows, row of the batch) computes the chunk's w in
 //      registers and writes the min(k, chunk length) smallest (w, row) pairs;
@@ -42,17 +42,62 @@ __device__ __forceinline__ const int* kz_knnr_exchange(int (*s_cnt)[4], int& pas
     return s;
 }
 
+// The OR and the AND of the workgroup's keys, to every thread: the bits all keys share are those of all_and outside all_or ^ all_and
+// (one barrier; it also publishes what the caller wrote to LDS before the call).
+__device__ __forceinline__ void kz_knnr_or_and(unsigned long long& all_or, unsigned long long& all_and, unsigned long long* s_or,
+                                               unsigned long long* s_and, int lane, int wave) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        all_or |= __shfl_xor(all_or, o, 64);
+        all_and &= __shfl_xor(all_and, o, 64);
+    }
+    if (lane == 0) {
+        s_or[wave] = all_or;
+        s_and[wave] = all_and;
+    }
+    __syncthreads();
+    all_or = s_or[0] | s_or[1] | s_or[2] | s_or[3];
+    all_and = s_and[0] & s_and[1] & s_and[2] & s_and[3];
+}
+
+// THE THRESHOLD SEARCH of both levels, the approach of kz_exact_chunk_radix_kernel on the keys.  count(pred): the number of the
+// workgroup's entries (key, row) that pred holds for, to every thread (kz_knnr_exchange: one barrier per call).  -> thr = the k-th
+// smallest key, bit by bit below the keys' common prefix (the largest pattern with fewer than k keys below it): everything below
+// thr survives, and of the entries equal to it the m that are still missing, by smallest row -- r_thr = the m-th smallest row among
+// them by the same bit-by-bit count over ROW_BITS bits where there are more ties than places, else every row.
+template <int ROW_BITS, typename Count>
+__device__ __forceinline__ void kz_knnr_thresholds(unsigned long long all_or, unsigned long long all_and, int k, Count count,
+                                                   unsigned long long& thr, int& r_thr) {
+    const unsigned long long differ = all_or ^ all_and;
+    const int top = differ ? 63 - __clzll(differ) : -1;
+    thr = top < 0 ? all_and : (all_and & ~((2ull << top) - 1ull));
+    for (int bit = top; bit >= 0; --bit) {   // (uniform)
+        const unsigned long long cand = thr | (1ull << bit);
+        if (count([&](unsigned long long key, int) { return key < cand; }) < k) thr = cand;
+    }
+    const unsigned long long t = thr;
+    const int below = count([&](unsigned long long key, int) { return key < t; });
+    const int ties = count([&](unsigned long long key, int) { return key == t; });
+    const int m = k - below;   // places left for the entries equal to thr: 1 <= m <= ties
+    r_thr = (int)((1u << ROW_BITS) - 1u);
+    if (ties > m) {            // (uniform)
+        r_thr = 0;
+#pragma unroll 1   // (a rare path: ROW_BITS counting passes, not ROW_BITS copies of one)
+        for (int bit = ROW_BITS - 1; bit >= 0; --bit) {
+            const int cand = r_thr | (1 << bit);
+            if (count([&](unsigned long long key, int r) { return key == t && r < cand; }) < m) r_thr = cand;
+        }
+    }
+}
+
 // Level 1.  vals [nb][n_i]: the value matrix of rows list[batch0 .. batch0 + nb).  Workgroup (c, b) owns the values [c KZ_KNNR_CHUNK,
 // (c + 1) KZ_KNNR_CHUNK) of row b and writes the k_c = min(k, chunk length) smallest (w, index row) of them to places [0, k_c) of
 // cand_w / cand_i [(b n_chunks + c) k ..], in no particular order; places [k_c, k) hold (+inf, INT_MAX).
-// Loads as kz_rank_count_reduced_kernel has them: the chunk is one scalar element up to the next even element of the matrix, pairs
-// (16-byte loads, all eight of a thread in flight), and one scalar element behind them; t_a / t_b by 8-byte gathers; the query
-// side uniform.  The two scalar ends live in the pair slot that a chunk with a scalar end never fills (the last one, thread 255's
-// eighth: an end leaves at most 4095 values to the pairs), so every thread holds eight slots = 16 keys and nothing else.
-// Selection, the approach of kz_exact_chunk_radix_kernel on the keys: thr = the k_c-th smallest key, bit by bit below the keys'
-// common prefix (the largest pattern with fewer than k_c keys below it); everything below thr survives, and of the keys equal to it
-// the m that are still missing, by smallest row -- the m-th smallest chunk-local row among them by the same bit-by-bit count, 12
-// bits, where there are more ties than places.  A counting pass is 16 compares and ballots per thread and one barrier.
+// Loads as kz_rank_count_kernel has them (KzRankChunk): pairs (16-byte loads, all eight of a thread in flight) between the scalar
+// ends; t_a / t_b by 8-byte gathers; the query side uniform.  The two scalar ends live in the pair slot that a chunk with a scalar
+// end never fills (the last one, thread 255's eighth: an end leaves at most 4095 values to the pairs), so every thread holds eight
+// slots = 16 keys and nothing else.  Selection: kz_knnr_thresholds on the chunk-local rows, 12 bits; a counting pass is 16 compares
+// and ballots per thread and one barrier.
 template <typename T, int KIND, int METRIC>
 __global__ __launch_bounds__(256) void kz_knn_reduced_chunk_kernel(const double* __restrict__ vals, int64_t n_i, const int* __restrict__ list,
                                                                    int batch0, int k, int n_chunks, double mp,
@@ -67,17 +112,13 @@ __global__ __launch_bounds__(256) void kz_knn_reduced_chunk_kernel(const double*
     const int c = blockIdx.x, b = blockIdx.y;
     const int row = list[batch0 + b];
     const double qa = q_a[row], qb = TWO ? q_b[row] : 0.0;
-    const int64_t e0 = (int64_t)b * n_i;   // first element of the row in vals
-    const int64_t j0 = (int64_t)c * KZ_KNNR_CHUNK;
-    const int64_t j1 = j0 + KZ_KNNR_CHUNK < n_i ? j0 + KZ_KNNR_CHUNK : n_i;
-    const int nvalid = (int)(j1 - j0);               // (>= 1: the chunk is not empty)
-    const int64_t a = (e0 + j0 + 1) & ~(int64_t)1;   // first even element at or behind the chunk's start
-    const int64_t rem = e0 + j1 - a;
-    const int n_pairs = (int)(rem >> 1);
-    const int off = (int)(a - e0 - j0);              // chunk-local row of the first paired element: 0 or 1
-    const bool has_first = off == 1, has_last = (rem & 1) != 0;
+    const KzRankChunk ch(b, c, KZ_KNNR_CHUNK, n_i);
+    const int64_t e0 = ch.e0, j0 = ch.j0, j1 = ch.j1;
+    const int nvalid = (int)(j1 - j0);   // (>= 1: the chunk is not empty)
+    const int n_pairs = ch.n_pairs, off = ch.off;
+    const bool has_first = off == 1, has_last = (ch.rem & 1) != 0;
     const bool end_slot = tid == 255 && 256 * (U - 1) + 255 >= n_pairs;   // this thread's last slot holds the ends, not a pair
-    const double2* __restrict__ pairs = reinterpret_cast<const double2*>(vals + a);
+    const double2* __restrict__ pairs = reinterpret_cast<const double2*>(vals + ch.a);
     auto local_row = [&](int u, int h) -> int {
         if (u == U - 1 && end_slot) return h ? nvalid - 1 : 0;
         return off + 2 * (256 * u + tid) + h;
@@ -126,8 +167,8 @@ __global__ __launch_bounds__(256) void kz_knn_reduced_chunk_kernel(const double*
         }
         return kz_knnr_exchange(s_cnt, pass, cnt, lane, wave);
     };
-    auto count = [&](auto pred) -> int {
-        const int* s = wave_counts(pred);
+    auto count = [&](auto pred) -> int {   // pred(key, chunk-local row)
+        const int* s = wave_counts([&](int u, int h) { return pred(key[2 * u + h], local_row(u, h)); });
         return s[0] + s[1] + s[2] + s[3];
     };
 
@@ -138,39 +179,12 @@ __global__ __launch_bounds__(256) void kz_knn_reduced_chunk_kernel(const double*
         all_or |= key[e] == KZ_KNNR_PAD ? 0ull : key[e];
         all_and &= key[e];
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        all_or |= __shfl_xor(all_or, o, 64);
-        all_and &= __shfl_xor(all_and, o, 64);
-    }
-    if (lane == 0) {
-        s_or[wave] = all_or;
-        s_and[wave] = all_and;
-    }
-    __syncthreads();
-    all_or = s_or[0] | s_or[1] | s_or[2] | s_or[3];
-    all_and = s_and[0] & s_and[1] & s_and[2] & s_and[3];
-    const unsigned long long differ = all_or ^ all_and;
-    const int top = differ ? 63 - __clzll(differ) : -1;
-
+    kz_knnr_or_and(all_or, all_and, s_or, s_and, lane, wave);
     const int k_c = k < nvalid ? k : nvalid;
-    unsigned long long thr = top < 0 ? all_and : (all_and & ~((2ull << top) - 1ull));
-    for (int bit = top; bit >= 0; --bit) {   // (uniform)
-        const unsigned long long cand = thr | (1ull << bit);
-        if (count([&](int u, int h) { return key[2 * u + h] < cand; }) < k_c) thr = cand;
-    }
-    const int below = count([&](int u, int h) { return key[2 * u + h] < thr; });
-    const int ties = count([&](int u, int h) { return key[2 * u + h] == thr; });
-    const int m = k_c - below;   // places left for the keys equal to thr: 1 <= m <= ties
-    int r_thr = KZ_KNNR_CHUNK - 1;
-    if (ties > m) {              // (uniform) the m-th smallest chunk-local row among them
-        r_thr = 0;
-        for (int bit = 11; bit >= 0; --bit) {
-            const int cand = r_thr | (1 << bit);
-            if (count([&](int u, int h) { return key[2 * u + h] == thr && local_row(u, h) < cand; }) < m) r_thr = cand;
-        }
-    }
-    static_assert(KZ_KNNR_CHUNK == 1 << 12, "the row threshold above walks 12 bits");
+    unsigned long long thr;
+    int r_thr;
+    static_assert(KZ_KNNR_CHUNK == 1 << 12, "the row threshold walks the 12 bits of a chunk-local row");
+    kz_knnr_thresholds<12>(all_or, all_and, k_c, count, thr, r_thr);
 
     // the survivors, each wave behind the waves before it, a lane behind the lanes before it: exactly k_c places
     auto survives = [&](int u, int h) { return key[2 * u + h] < thr || (key[2 * u + h] == thr && local_row(u, h) <= r_thr); };
@@ -202,9 +216,8 @@ __global__ __launch_bounds__(256) void kz_knn_reduced_chunk_kernel(const double*
 
 // Level 2.  Row b's n_e = n_chunks x k survivors (cand_w / cand_i [b n_e ..]; unused places (+inf, INT_MAX), behind every entry of
 // an index row: at least k entries are real) -> the k smallest by (key, index row), sorted, to row list[batch0 + b] of d_w / d_ind.
-// The same two thresholds, with the entries streamed from L2 in every counting pass: the k-th smallest key, then -- where more
-// entries equal it than places are left -- the m-th smallest index row among those (31 bits).  The k entries that pass go to LDS
-// (12 bytes each); an entry's place in the output is the number of those that come before it.
+// The same two thresholds (kz_knnr_thresholds on the index rows, 31 bits), with the entries streamed from L2 in every counting pass.
+// The k entries that pass go to LDS (12 bytes each); an entry's place in the output is the number of those that come before it.
 __global__ __launch_bounds__(256) void kz_knn_reduced_merge_kernel(const double* __restrict__ cand_w, const int* __restrict__ cand_i, int n_e,
                                                                    int k, const int* __restrict__ list, int batch0,
                                                                    double* __restrict__ d_w, int64_t* __restrict__ d_ind) {
@@ -237,37 +250,11 @@ __global__ __launch_bounds__(256) void kz_knn_reduced_merge_kernel(const double*
         all_or |= key;
         all_and &= key;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        all_or |= __shfl_xor(all_or, o, 64);
-        all_and &= __shfl_xor(all_and, o, 64);
-    }
-    if (lane == 0) {
-        s_or[wave] = all_or;
-        s_and[wave] = all_and;
-    }
     if (tid == 0) s_n = 0;
-    __syncthreads();
-    all_or = s_or[0] | s_or[1] | s_or[2] | s_or[3];
-    all_and = s_and[0] & s_and[1] & s_and[2] & s_and[3];
-    const unsigned long long differ = all_or ^ all_and;
-    const int top = differ ? 63 - __clzll(differ) : -1;
-    unsigned long long thr = top < 0 ? all_and : (all_and & ~((2ull << top) - 1ull));
-    for (int bit = top; bit >= 0; --bit) {   // (uniform)
-        const unsigned long long cand = thr | (1ull << bit);
-        if (count([&](unsigned long long key, int) { return key < cand; }) < k) thr = cand;
-    }
-    const int below = count([&](unsigned long long key, int) { return key < thr; });
-    const int ties = count([&](unsigned long long key, int) { return key == thr; });
-    const int m = k - below;   // places left for the entries equal to thr: 1 <= m <= ties
-    int r_thr = 0x7fffffff;
-    if (ties > m) {            // (uniform) the m-th smallest index row among them: a real row, the unused places come last
-        r_thr = 0;
-        for (int bit = 30; bit >= 0; --bit) {
-            const int cand = r_thr | (1 << bit);
-            if (count([&](unsigned long long key, int r) { return key == thr && r < cand; }) < m) r_thr = cand;
-        }
-    }
+    kz_knnr_or_and(all_or, all_and, s_or, s_and, lane, wave);
+    unsigned long long thr;
+    int r_thr;   // (an index row: a real one, the unused places come last)
+    kz_knnr_thresholds<31>(all_or, all_and, k, count, thr, r_thr);
     for (int i = tid; i < n_e; i += 256) {
         const double w = cw[i];
         const unsigned long long key = kz_knnr_key(w);
@@ -296,36 +283,6 @@ __global__ __launch_bounds__(256) void kz_knn_reduced_merge_kernel(const double*
     }
 }
 
-template <typename T, int METRIC>
-static void kz_knn_reduced_chunk_launch(kz_ctx* ctx, const KzRankReduction& red, dim3 grid, const double* vals, const kz_matrix* index,
-                                        const int* list, int batch0, int k, double* cand_w, int* cand_i) {
-#define KZ_KNNR_LAUNCH(KIND)                                                                                                               \
-    hipLaunchKernelGGL((kz_knn_reduced_chunk_kernel<T, KIND, METRIC>), grid, dim3(256), 0, ctx->stream, vals, index->n, list, batch0, k,    \
-                       (int)grid.x, index->mink_p, red.q_a, red.q_b, red.t_a, red.t_b, cand_w, cand_i)
-    switch (red.kind) {
-        case KZ_RANK_CSLS: KZ_KNNR_LAUNCH(KZ_RANK_CSLS); break;
-        case KZ_RANK_LS: KZ_KNNR_LAUNCH(KZ_RANK_LS); break;
-        case KZ_RANK_NICDM: KZ_KNNR_LAUNCH(KZ_RANK_NICDM); break;
-        default: KZ_KNNR_LAUNCH(KZ_RANK_MP_NORMAL); break;
-    }
-#undef KZ_KNNR_LAUNCH
-}
-
-// (the instantiations of kz_rank_count_reduced: the input dtype decides the rounding of the three converted metrics only)
-static void kz_knn_reduced_chunks(kz_ctx* ctx, const KzRankReduction& red, dim3 grid, const double* vals, const kz_matrix* index,
-                                  const int* list, int batch0, int k, double* cand_w, int* cand_i) {
-#define KZ_KNNR_METRIC(T, METRIC) kz_knn_reduced_chunk_launch<T, METRIC>(ctx, red, grid, vals, index, list, batch0, k, cand_w, cand_i)
-    const bool f32 = index->dtype == KZ_F32;
-    switch (kz_rank_out_metric(index->metric)) {
-        case KZ_EUCLIDEAN: if (f32) KZ_KNNR_METRIC(float, KZ_EUCLIDEAN); else KZ_KNNR_METRIC(double, KZ_EUCLIDEAN); break;
-        case KZ_SEUCLIDEAN: if (f32) KZ_KNNR_METRIC(float, KZ_SEUCLIDEAN); else KZ_KNNR_METRIC(double, KZ_SEUCLIDEAN); break;
-        case KZ_MINKOWSKI: if (f32) KZ_KNNR_METRIC(float, KZ_MINKOWSKI); else KZ_KNNR_METRIC(double, KZ_MINKOWSKI); break;
-        case KZ_CORRELATION: KZ_KNNR_METRIC(double, KZ_CORRELATION); break;
-        default: KZ_KNNR_METRIC(double, KZ_COSINE); break;
-    }
-#undef KZ_KNNR_METRIC
-}
-
 extern "C" int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_begin, int64_t q_count, const kz_matrix* index_c, int k,
                               int kind, const double* d_q_a, const double* d_q_b, const double* d_t_a, const double* d_t_b, double* d_w,
                               int64_t* d_ind) {
@@ -341,17 +298,11 @@ extern "C" int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_b
                      KZ_KNN_REDUCED_MAX_K);
         return KZ_ERR_UNSUPPORTED;
     }
-    KZ_REQUIRE(kind >= KZ_RANK_CSLS && kind <= KZ_RANK_MP_NORMAL, "kz_knn_reduced: unknown kind %d (KZ_RANK_CSLS .. KZ_RANK_MP_NORMAL)", kind);
-    KZ_REQUIRE(d_q_a && d_t_a, "kz_knn_reduced: the query-side and index-side state vectors d_q_a / d_t_a are required");
-    if (kind == KZ_RANK_MP_NORMAL)
-        KZ_REQUIRE(d_q_b && d_t_b, "kz_knn_reduced: KZ_RANK_MP_NORMAL needs the deviations d_q_b / d_t_b");
-    else
-        KZ_REQUIRE(!d_q_b && !d_t_b, "kz_knn_reduced: d_q_b / d_t_b belong to KZ_RANK_MP_NORMAL only and must be NULL for kind %d", kind);
+    const int rcr = kz_rank_require_reduction("kz_knn_reduced", kind, d_q_a, d_q_b, d_t_a, d_t_b);
+    if (rcr != KZ_OK) return rcr;
     KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "kz_knn_reduced: more than 2^31 - 1 rows");
     if (q_count == 0) return KZ_OK;
     KZ_HIP(hipSetDevice(ctx->device));
-    const KzRankReduction red{kind, d_q_a, d_q_b, d_t_a, d_t_b};
-
     // (released when the function returns, stream-ordered: cand_i, cand_w, fl)
     KzPoolBuf<int> fl;   // every row of the range, as the row list the exact stage takes
     KzPoolBuf<double> cand_w;
@@ -359,30 +310,27 @@ extern "C" int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_b
     int rc = fl.alloc(ctx, (size_t)q_count * sizeof(int));
     if (rc != KZ_OK) return rc;
     hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((q_count + 255) / 256)), dim3(256), 0, ctx->stream, fl.get(), (int)q_count);
-    rc = kz_exact_prepare_index(ctx, index, (int)q_count);
-    if (rc != KZ_OK) return rc;
     int batch = 0;
     double* vals = nullptr;
-    rc = kz_exact_batch_rows(ctx, index, (int)q_count, &batch, &vals);
+    rc = kz_exact_begin(ctx, index, (int)q_count, &batch, &vals);
     if (rc != KZ_OK) return rc;
     const int n_chunks = (int)((index->n + KZ_KNNR_CHUNK - 1) / KZ_KNNR_CHUNK);
     const size_t n_cand = (size_t)batch * n_chunks * k;
     rc = cand_w.alloc(ctx, n_cand * 8);
     if (rc == KZ_OK) rc = cand_i.alloc(ctx, n_cand * 4);
     if (rc != KZ_OK) return rc;
-    for (int b0 = 0; b0 < (int)q_count; b0 += batch) {
-        const int nb = (int)q_count - b0 < batch ? (int)q_count - b0 : batch;
-        rc = kz_exact_distances(ctx, fl.get(), b0, nb, q_begin, query, index, vals);
-        if (rc != KZ_OK) return rc;
-        kz_knn_reduced_chunks(ctx, red, dim3(n_chunks, nb), vals, index, fl.get(), b0, k, cand_w.get(), cand_i.get());
-        hipLaunchKernelGGL(kz_knn_reduced_merge_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const double*)cand_w.get(), (const int*)cand_i.get(),
-                           n_chunks * k, k, (const int*)fl.get(), b0, d_w, d_ind);
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (the buffers go back to the pool; the caller reads d_w / d_ind next)
-    if (e != hipSuccess) {
-        kz_set_error("kz_knn_reduced: exact kernels failed: %s", hipGetErrorString(e));
-        return KZ_ERR_HIP;
-    }
-    return KZ_OK;
+    const int* list = fl.get();
+    double* cw = cand_w.get();
+    int* ci = cand_i.get();
+    // (the buffers go back to the pool behind the walk's synchronise; the caller reads d_w / d_ind next)
+    return kz_exact_walk("kz_knn_reduced", ctx, list, (int)q_count, batch, vals, q_begin, query, index, [&](int b0, int nb) {
+        // (kz_rank_dispatch: the instantiations of the count)
+        kz_rank_dispatch(kind, index, [&](auto t, auto kd, auto metric) {
+            hipLaunchKernelGGL((kz_knn_reduced_chunk_kernel<typename decltype(t)::type, decltype(kd)::value, decltype(metric)::value>),
+                               dim3(n_chunks, nb), dim3(256), 0, ctx->stream, (const double*)vals, index->n, list, b0, k, n_chunks, index->mink_p,
+                               d_q_a, d_q_b, d_t_a, d_t_b, cw, ci);
+        });
+        hipLaunchKernelGGL(kz_knn_reduced_merge_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const double*)cw, (const int*)ci, n_chunks * k, k, list,
+                           b0, d_w, d_ind);
+    });
 }

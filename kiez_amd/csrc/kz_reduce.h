@@ -2,7 +2,7 @@
 // the reference evaluates them with separate numpy operations (the library is compiled with -ffp-contract=off: no fused
 // multiply-add is formed, so one expression gives one result wherever it is inlined).  Two callers, which must not drift:
 //   the transform kernels over the [n, K] candidate arrays        (kz_hubness.hip: kz_csls_kernel, kz_ls_kernel, kz_mp_normal_kernel)
-//   the count kernel over the whole index row of the value matrix (kz_gold_ranks.h: kz_rank_count_reduced_kernel)
+//   the count kernel over the whole index row of the value matrix (kz_gold_ranks.h: kz_rank_count_kernel)
 //
 //   CSLS            kiez/hubness_reduction/csls.py:90-93
 //   LocalScaling    kiez/hubness_reduction/local_scaling.py:135-147

@@ -154,6 +154,16 @@ class HubnessReduction(ABC):
         """(kind, query-side state vectors of the forward lists `query_dist`, index-side fit state) for kz_gold_ranks_reduced."""
         raise NotImplementedError(self._no_rank_reason)
 
+    def _forward_rank_state(self):
+        """`_rank_state` of the forward lists of kneighbors().  When they are the shared sweep's cached result, the cache is left as it
+        was found, so the kneighbors() that follows is served as it would have been."""
+        nn = self.nn_algo
+        cached = nn._forward
+        query_dist, _ = nn.kneighbors_device(query=None, k=nn.n_candidates)
+        if cached is not None and cached[1] is query_dist:
+            nn._forward = cached
+        return self._rank_state(query_dist)
+
     def gold_ranks_device(self, gold) -> N.DeviceArray:
         """`gold_ranks` that leaves the int64 rank vector in HBM (evaluate.rank_metrics reduces it there)."""
         if not self._gpu_nn:
@@ -163,13 +173,7 @@ class HubnessReduction(ABC):
         query, index, gold_dev = nn._gold_rank_operands(gold)   # (NotFittedError, single-source fit: as the plain call)
         if self._no_rank_reason:
             raise NotImplementedError(f"{type(self).__name__}: {self._no_rank_reason}")
-        # the forward lists of kneighbors(); when they are the shared sweep's cached result, the cache is left as it was found, so
-        # the kneighbors() that follows is served as it would have been
-        cached = nn._forward
-        query_dist, _ = nn.kneighbors_device(query=None, k=nn.n_candidates)
-        if cached is not None and cached[1] is query_dist:
-            nn._forward = cached
-        kind, q_state, t_state = self._rank_state(query_dist)
+        kind, q_state, t_state = self._forward_rank_state()
         return N.gold_ranks_reduced(self.ctx, query, index, gold_dev, kind, q_state, t_state)
 
     def gold_ranks(self, gold) -> np.ndarray:
@@ -211,12 +215,7 @@ class HubnessReduction(ABC):
         if k > N.KNN_REDUCED_MAX_K:
             raise NotImplementedError(f"kneighbors_whole_index returns up to {N.KNN_REDUCED_MAX_K} neighbours per query, got k = {k}: "
                                       "beyond that, gold_ranks ranks any target row against the whole index")
-        # the state of gold_ranks_device, obtained the same way: a cached shared-sweep result is left as it was found
-        cached = nn._forward
-        query_dist, _ = nn.kneighbors_device(query=None, k=nn.n_candidates)
-        if cached is not None and cached[1] is query_dist:
-            nn._forward = cached
-        kind, q_state, t_state = self._rank_state(query_dist)
+        kind, q_state, t_state = self._forward_rank_state()
         od, oi = N.knn_reduced(self.ctx, query, index, k, kind, q_state, t_state)
         if nn._out_dtype(nn.target_index) == np.float32:
             od = N.cast_f32(self.ctx, od)

@@ -94,7 +94,7 @@ def test_rank_is_the_position_in_the_full_length_search(ctx, name, metric, dtype
             np.testing.assert_array_equal(rank, RR.gold_ranks(_all_pair_values(ctx, qm, ym), gold), err_msg=where)
 
 
-@pytest.mark.parametrize("n_i", [4097, 9000])
+@pytest.mark.parametrize("n_i", [4097, 8191, 8192, 8193, 9000])   # (8192: the count kernel's chunk; odd: value rows start at both parities)
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_beyond_a_lists_reach_and_beyond_one_chunk(ctx, n_i, dtype):
     from kiez_amd import _native as N
@@ -106,6 +106,7 @@ def test_beyond_a_lists_reach_and_beyond_one_chunk(ctx, n_i, dtype):
     # the rounding of either side), ranks n_i - 1 and n_i - 2 -- with 4 097 index rows the only two ranks no list reaches or just reaches
     far = np.argsort(((q[2:4].astype(np.float64)[:, None, :] - y.astype(np.float64)[None, :, :]) ** 2).sum(axis=2), axis=1)
     gold[2], gold[3] = far[0, -1], far[1, -2]
+    gold[4], gold[5] = min(8191, n_i - 1), min(8192, n_i - 1)   # the two sides of the count chunk's edge
     qm, ym = N.DeviceMatrix(ctx, q, "euclidean"), N.DeviceMatrix(ctx, y, "euclidean")
     rank = _ranks(ctx, qm, ym, gold)
     np.testing.assert_array_equal(rank, RR.gold_ranks(_all_pair_values(ctx, qm, ym), gold))

@@ -158,13 +158,16 @@ def test_short_lists_inside_numpys_bracket(short_lists, kind, K, cap):
     assert wide.sum() <= cap * gold.size
 
 
-def test_csls_beyond_one_chunk_and_beyond_any_list(ctx):
-    """9 000 index rows: two chunks of values per row, ranks past the 4 096 neighbours a list can hold."""
-    rng = np.random.default_rng(9000)
-    n_s, n_t, d = 64, 9000, 8
+@pytest.mark.parametrize("n_t", [8191, 8192, 8193, 9000])
+def test_csls_beyond_one_chunk_and_beyond_any_list(ctx, n_t):
+    """Index rows around the 8 192 values of a count chunk and two chunks of values per row (an odd count: value rows start at both
+    parities), ranks past the 4 096 neighbours a list can hold."""
+    rng = np.random.default_rng(n_t)
+    n_s, d = 64, 8
     source, target = rng.standard_normal((n_s, d)), rng.standard_normal((n_t, d))
     gold = rng.integers(0, n_t, n_s).astype(np.int64)
     gold[0], gold[1] = 0, n_t - 1
+    gold[4], gold[5] = min(8191, n_t - 1), min(8192, n_t - 1)   # the two sides of the count chunk's edge
     hub = _reduction("csls", 10, "euclidean")
     hub.fit(source, target)
     got = hub.gold_ranks(gold)
