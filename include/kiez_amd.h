@@ -91,6 +91,12 @@ typedef struct kz_knn_stats {
     int64_t n_range_pairs;   /* (query row, index row) pairs the range re-search evaluated in float64                            */
     int64_t n_range_group_rows; /* of n_range_rows: rows answered as part of a GROUP -- rows of one tight cluster share the range of a
                                 representative row: a dense block of pairs instead of one range per row                        */
+    int32_t thresh_source;   /* kz_knn_dual: where the shared sweep's event thresholds came from -- 0 no shared sweep, 1 sample sweep,
+                                2 nested sample sweep, 3 probe model (no sample sweep)                                           */
+    int32_t model_max_events; /* ... probe model: the largest event count the model gives a probe row (0: the reverse probe did not run) */
+    double model_mean_events; /* ... probe model: the mean of those counts                                                         */
+    double floor_r2;         /* kz_knn_dual: share of the variance of the forward probe's k-th keys the floor's fit explains
+                                (0: no floor probe); the model thresholds' pre-gate                                               */
 } kz_knn_stats;
 
 /* ---- library / context -------------------------------------------------------------------------------- */

@@ -75,6 +75,10 @@ class KnnStats(C.Structure):
         ("n_range_rows", C.c_int64),
         ("n_range_pairs", C.c_int64),
         ("n_range_group_rows", C.c_int64),
+        ("thresh_source", C.c_int32),
+        ("model_max_events", C.c_int32),
+        ("model_mean_events", C.c_double),
+        ("floor_r2", C.c_double),
     ]
 
     def as_dict(self):

@@ -25,6 +25,7 @@ constexpr double KZ_K_PROBE_MIN_MS = 12.0;   // searches below "probe_min_pairs"
 constexpr int KZ_K_EXACT_DIRECT_ROWS = 32;   // at most this many rows left by the split-bf16 tier skip the float32-operand kernel and go to the exact kernels
 constexpr double KZ_K_SPEC_ELEMS = 1.6e9;   // speculative rescue: at most this / (index rows x d) rows (and at most "spec_rows")
 constexpr int KZ_K_FLOOR_PROBE = 1024;   // seeded lists: rows of the probe in kz_knn_dual
+constexpr double KZ_K_MODEL_MIN_R2 = 0.45;  // model thresholds of the shared sweep: the forward floor fit must explain at least this share of the k-th key's variance, or the reverse probe is not run (kz_knn_dual.h "MODEL THRESHOLDS")
 
 struct kz_ctx {
     int device;
@@ -63,6 +64,8 @@ struct kz_ctx {
     int spec_rows;    // exact kernels launched speculatively behind every finalize kernel for up to this many uncertified rows (default 64; kz_knn.hip "SPECULATIVE RESCUE")
     int wide_lists;   // fp16 tier's WIDE route (kz_knn_impl): lists of 16 per query when the tier probe finds the keys dense around the k-th neighbour (default 32; 0 = off)
     int wide_sel;     // ... entries of those lists the finalize kernel selects (default 256)
+    int dual_model;   // kz_knn_dual: event thresholds from a probe model instead of a sample sweep -- 0 never, 1 (default) where the gate allows, 2 forced (tests; kz_knn_dual.h "MODEL THRESHOLDS")
+    double dual_model_shift;   // ... added to the model's thresholds, in the fit's key units (default 0; test knob: a huge value leaves no events at all)
     // scratch (grown on demand, reused across calls)
     void* scratch;
     size_t scratch_bytes;

@@ -11,6 +11,7 @@
 //   3. kz_exact_*           (kz_exact.h) exact float64 brute force for the (rare) rows that could not be certified.
 // This file: the float32-operand kernel, launch plumbing, the escalation helpers and the host ladder kz_knn_impl.
 // Result: neighbour order == order of the float64 distances the reference computes; no approximation.
+#include <chrono>
 #include <vector>
 
 #include <algorithm>
@@ -476,7 +477,7 @@ static inline double kz_gamma_acc_h(int kg) { return 2.0 * (double)(kg * 4 + 16)
 // model = {alpha, beta, margin}; *ok = false when the probe's values are not finite (no floor then).  `dist`: [.., k] results whose
 // row i * stride is probe row i; rowq: the query image's per-row statistics, same row numbering.  Waits for the stream.
 static int kz_floor_model(kz_ctx* ctx, const double* dist, const double* rowq, int n_probe, int64_t stride, int k, int metric, double* model,
-                          bool* ok) {
+                          bool* ok, double* r2 = nullptr) {   // (r2: the share of the keys' variance the fit explains, kz_floor_r2)
     KzPoolBuf<double> d_pairs;
     int rc = d_pairs.alloc(ctx, (size_t)n_probe * 16);
     if (rc != KZ_OK) return rc;
@@ -492,6 +493,7 @@ static int kz_floor_model(kz_ctx* ctx, const double* dist, const double* rowq, i
         return KZ_ERR_HIP;
     }
     *ok = kz_floor_fit(hp.data(), n_probe, ctx->floor_margin, model);
+    if (r2) *r2 = *ok ? kz_floor_r2(hp.data(), n_probe) : 0.0;
     return KZ_OK;
 }
 
@@ -687,7 +689,8 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                        int64_t* d_ind, kz_knn_stats* stats, KzDualPass* dual);
 static int kz_escalate_rows(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, const int* fail_list, int n_fail, kz_matrix* index, int k,
                             int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* out_dist,
-                            int64_t* out_ind, kz_knn_stats* st2, float* ms_out) {
+                            int64_t* out_ind, kz_knn_stats* st2, float* ms_out, const int* out_rows = nullptr) {
+    // (out_rows: where the results of row i of the list go -- row out_rows[i] of out_dist / out_ind instead of the row's own place)
     KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
     const size_t row_bytes = (size_t)query->d * (query->dtype == KZ_F32 ? 4 : 8);
     // (released when the function returns: qsub, fl, sub_raw, sub_self, sub_dist, sub_ind)
@@ -721,7 +724,7 @@ static int kz_escalate_rows(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, con
         rc = kz_knn_impl(ctx, qsub.get(), 0, n_fail, index, k, exclude_self, sub_self.get(), rs, sub_dist.get(), sub_ind.get(), st2, nullptr);
     if (rc == KZ_OK) {
         hipLaunchKernelGGL(kz_scatter_rows_kernel, dim3((unsigned)(((int64_t)n_fail * k + 255) / 256)), dim3(256), 0, ctx->stream,
-                           sub_dist.get(), sub_ind.get(), fl.get(), n_fail, k, out_dist, out_ind);
+                           sub_dist.get(), sub_ind.get(), out_rows ? out_rows : fl.get(), n_fail, k, out_dist, out_ind);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

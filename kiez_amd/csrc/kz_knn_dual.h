@@ -15,7 +15,8 @@
 // copied into a small image and swept by the ordinary kernel with B as the query side: 1/s of a full sweep).  By
 // construction about k s rows of A pass tau(t), whatever the data looks like (the count of population members above
 // the k-th order statistic of a sample is negative binomial: mean k (s - 1), deviation sqrt(k) s), so the event
-// buffers are small and of predictable size.
+// buffers are small and of predictable size.  (Where a probe shows that the k-th key of a row follows its distance to the data
+// centre, tau(t) comes from that model instead and no sample is swept at all: "MODEL THRESHOLDS" below.)
 //
 // After the sweep: kz_dual_scatter_kernel files the logged groups per index row (per-key test, atomic slot),
 // kz_dual_select_kernel keeps the K' best events of every row as an ordinary candidate list, and the ordinary finalize
@@ -138,6 +139,64 @@ __global__ __launch_bounds__(256) void kz_dual_theta_kernel(const float* __restr
         theta[t] = tf;
         floor_[t] = tau_bound;
     }
+}
+
+// ---- MODEL THRESHOLDS: thresholds from a probe model, no sample sweep ------------------------------------------------
+// A row's k-th neighbour distance is mostly a function of its distance to the data centre (that is what hubness is), and the
+// population floor of the forward lists (kz_knn.hip "POPULATION FLOOR") already fits it.  The same fit for the rows of b against
+// ALL of a -- from a strided probe of b's rows that keeps k_p >> k neighbours, so that the events a probe row would get are
+// counted, not extrapolated (kz_floor.h: kz_theta_fit) -- gives tau(t) = alpha + beta |t_c|^2 - margin for every row of b without
+// any sample sweep.  The contract above kz_dual_theta_kernel holds for ANY tau: the threshold decides which pairs are filed as
+// events, never an answer.  A row whose tau is too high gets fewer than k events and is searched again; one whose tau is too low
+// overflows its buffer and is searched again; a log that overflows sends the whole direction to the ordinary search.
+// Fit rows of the probe: probe row i = matrix row i * stride of b, its results at row i of `dist` ([n_probe, k_p], ascending
+// distance).  out[i (k_p + 1)] = |t_c|^2, then the k_p keys (|t_c|^2 - d^2) / 2 (kz_floor_pairs_kernel's convention).
+__global__ void kz_dual_model_rows_kernel(const double* __restrict__ dist, const double* __restrict__ rowq, int n_probe, int64_t stride, int k_p,
+                                          int metric, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)n_probe * (k_p + 1)) return;
+    const int i = (int)(e / (k_p + 1)), j = (int)(e - (int64_t)i * (k_p + 1));
+    const double x = rowq[(int64_t)i * stride * 3];
+    if (j == 0) {
+        out[e] = x;
+        return;
+    }
+    const double v = dist[(int64_t)i * k_p + j - 1];
+    const double d2 = metric == KZ_EUCLIDEAN ? v * v : (metric == KZ_COSINE ? 2.0 * v : v);
+    out[e] = 0.5 * (x - d2);
+}
+// One thread per row t of b: floor_[t] = tau = the model's key in the sweep's key units, minus the rounding bound of this row's
+// approximate keys, rounded down (as kz_floor_rows_kernel does for the forward lists, with the roles of the two sides exchanged);
+// theta[t] = tau + bias(t) - 2^-21 Mx, rounded down (the contract above kz_dual_theta_kernel).  A tau that is not a number or
+// +inf: no events, the row must fail its certification (+inf in both).  Pad rows: +inf.
+__global__ void kz_dual_model_theta_kernel(int64_t n_b, int64_t n_b_pad, const double* __restrict__ rowq_b, const float* __restrict__ bias_b,
+                                           const double* __restrict__ a_hmax, const double* __restrict__ b_hmax,
+                                           const double* __restrict__ hscale, double alpha, double beta, double margin, double eps_mult,
+                                           double gamma_acc, float* __restrict__ theta, float* __restrict__ floor_) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_b_pad) return;
+    if (t >= n_b) {
+        theta[t] = INFINITY;
+        floor_[t] = INFINITY;
+        return;
+    }
+    const double tc2 = rowq_b[t * 3 + 0], th = rowq_b[t * 3 + 1], tr = rowq_b[t * 3 + 2];
+    const double Ah = a_hmax[0], Ra = a_hmax[1], Ac2 = a_hmax[2];
+    const double tc = sqrt(tc2), ac = sqrt(Ac2);
+    const double eps = eps_mult * (tr * Ah + th * Ra + tr * Ra + gamma_acc * (0.5 * Ac2 + th * Ah) +
+                                   1.1920928955078125e-07 * (tc + ac) * (tc + ac) + 1e-12 * (0.5 * Ac2 + tc2));
+    const double f = (alpha + beta * tc2 - margin - eps) / hscale[1];
+    float tau = (float)f;
+    if ((double)tau > f) tau = nextafterf(tau, -INFINITY);
+    if (!(f < (double)INFINITY)) tau = INFINITY;   // (NaN or +inf)
+    const double S2 = hscale[0] * hscale[0];
+    const double m2 = 4.76837158203125e-07 * S2 * (Ah * b_hmax[0] + Ac2 + b_hmax[2]);   // 2^-21 Mx
+    const double thd = (double)tau + (double)bias_b[t] - m2;
+    float tf = (float)thd;
+    if ((double)tf > thd) tf = nextafterf(tf, -INFINITY);
+    if (tau == INFINITY) tf = INFINITY;
+    theta[t] = tf;
+    floor_[t] = tau;
 }
 
 // Sample image: the rows of every stride-th tile of A's image, dealt over P parts ROW BY ROW (data stored cluster by cluster has
@@ -732,18 +791,20 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
 
     // expected events per row of B: k (stride - 1) + k, deviation sqrt(k) stride; the buffer takes mean + ~7 deviations (a row
     // that overflows is searched again on its own: ~1.5 ms for a single row against a million index rows)
-    const int ev_cap = (int)(((int64_t)rank * stride + (int64_t)(7.0 * sqrt((double)rank) * stride) + 63) & ~(int64_t)63);
+    // (MODEL THRESHOLDS, below, size both from the probe's counts instead)
+    int ev_cap = (int)(((int64_t)rank * stride + (int64_t)(7.0 * sqrt((double)rank) * stride) + 63) & ~(int64_t)63);
     // logged groups: about one per event (rarely two events share a group) plus the groups that pass the tile's smallest
     // threshold but not their own rows' (few: the rows of a tile are neighbours in threshold order); the TOTAL over all rows
     // is sharply concentrated around |B| k stride -- 1.5 times that, plus slack for small inputs (24 B per entry).  An
     // overflowing log is detected and the direction redone.
-    const long long log_cap = (long long)((double)b->n * rank * stride * 1.5) + (1 << 20);
+    long long log_cap = (long long)((double)b->n * rank * stride * 1.5) + (1 << 20);
 
     // Every buffer of the pass is released when the lambda below returns, in this order: the nested stages' (s3_packed .. d_cnt3), the
     // speculative launches' (spec_ba, spec_s3), then s_packed .. d_cnt -- behind the second stream: `join` waits for it first.
     // What the call does once they are released: then = 1 both directions by two ordinary searches (kz_knn_dual_separately with
     // sep_prec, sep_wide), 2 the reverse direction the ordinary way.
     int then = 0, sep_prec = -1, sep_wide = 0;
+    int thresh_source = 0;   // kz_knn_stats::thresh_source of this call
     kz_knn_stats st_ba;
     memset(&st_ba, 0, sizeof(st_ba));
     const int rc_pass = [&]() -> int {
@@ -800,18 +861,17 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     if (rc == KZ_OK) rc = col_idx.alloc(ctx, (size_t)b->n * KPr * 4);
     if (rc == KZ_OK) rc = ev_cnt.alloc(ctx, (size_t)b_pad * 4 * KZ_EVC);
     if (rc == KZ_OK) rc = fail_list.alloc(ctx, (size_t)b->n * 4);
-    if (rc == KZ_OK) rc = ev.alloc(ctx, (size_t)b_pad * ev_cap * 8);
-    if (rc == KZ_OK) rc = log_keys.alloc(ctx, (size_t)log_cap * 16);
-    if (rc == KZ_OK) rc = log_meta.alloc(ctx, (size_t)log_cap * 8);
     if (rc == KZ_OK) rc = d_cnt.alloc(ctx, KZ_DUAL_CNT_BYTES);
-    if (rc != KZ_OK) {   // (not enough memory for the event buffers: the two ordinary searches need far less)
+    if (rc != KZ_OK) {   // (not enough memory: the two ordinary searches need far less)
         then = 1;
         return KZ_OK;
     }
+    // (the event buffers and the log are sized by the route that sets the thresholds: allocated once that is known, below)
     // ---- POPULATION FLOOR of the forward lists (kz_knn.hip "POPULATION FLOOR"): a strided probe of A's rows -- an escalation-style
     // sub-search, exact float64 results written to their places -- gives the model.  It runs FIRST: it is this call's tier probe as well (below), and a call
     // that is handed to two ordinary searches should not have enqueued a sample sweep.
     double floor_model[3] = {0, 0, 0};
+    double floor_r2 = 0;   // share of the variance of the probe's k-th keys the floor's fit explains (kz_floor_r2)
     bool have_floor = false;
     bool tier_probed = false;   // the tier probe below has looked at the data
     // (the floor takes ~2 % off a sweep with one list of 16 per query, ~4.5 % with ten; its probe costs 0.4 - 1 ms: sweeps from
@@ -870,9 +930,104 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
             }
         }
         plist.reset();
-        if (rc == KZ_OK && want_floor) rc = kz_floor_model(ctx, d_dist_ab, ia->rowq, n_probe, pstride, k, a->metric, floor_model, &have_floor);
+        if (rc == KZ_OK && want_floor)
+            rc = kz_floor_model(ctx, d_dist_ab, ia->rowq, n_probe, pstride, k, a->metric, floor_model, &have_floor, &floor_r2);
         if (rc != KZ_OK) return rc;
         if (!have_floor) qfloor.reset();
+    }
+
+    // ---- MODEL THRESHOLDS (above kz_dual_model_rows_kernel): the reverse probe, the fit and the gate.  Option "dual_model": 0 never,
+    // 1 where every condition below holds, 2 forced (tests: whatever the probe says, as long as the fit is finite).  Automatic:
+    //   * the nested sample would have been taken (the sizes at which a sample phase is worth removing), and the call is not under
+    //     "dual_force" (the tests' shapes keep the sample routes they were written for);
+    //   * PRE-GATE: the forward fit that ran anyway explains at least KZ_K_MODEL_MIN_R2 of the variance of the k-th key -- clustered
+    //     data, where |q_c|^2 says nothing about the k-th neighbour, does not pay for a probe that would refuse;
+    //   * the probe can keep max(64, 6 k) neighbours per row (k <= 18), and b has at least 16 probes' worth of rows;
+    //   * no probe row SATURATED (as many events as the probe kept neighbours: the count is then a lower bound only) and none short
+    //     of k events;
+    //   * fewer events per row on average than the rank x stride of the sample route.  (Equal events already win by the whole
+    //     sample phase; more mean that the data is not of the kind the model describes.)
+    // The buffers follow from the counts: the rows of b are exchangeable with the probe rows, so a row exceeds the LARGEST of n_probe
+    // counts with probability 1 / (n_probe + 1) -- a buffer of twice that overflows for far fewer rows than the ~|b| / 1 000 whose
+    // count the sample route's 7-deviation buffer accepts to lose, each of which is searched again on its own -- and the total over
+    // all rows is concentrated around |b| x the mean count: the log takes twice that plus the slack for small inputs.
+    const bool nested_sizes = ctx->dual_nested && s_tiles >= 8 && s_tiles < a->n / KZ_TILE && s_tiles * KZ_TILE >= (int64_t)8 * KP &&
+                              b->n <= kz_rows_per_chunk(ctx, KP, false) && (ctx->dual_force || t_sweep_ms / stride >= KZ_K_NESTED_MIN_MS);
+    bool model = false;
+    KzThetaFit mfit;
+    memset(&mfit, 0, sizeof(mfit));
+    float rev_probe_ms = 0;
+    {
+        const bool forced = ctx->dual_model == 2;
+        // neighbours the probe keeps: enough that a row's event count is observed (the model lets through ~2.5 - 3.5 k per row on
+        // the data it describes) -- at most what one fused list answers.  Where that cap binds (k > 18) the counts would saturate:
+        // the automatic gate does not run a probe that can only refuse (500k x 500k, k = 50: 1.5 ms per step for nothing)
+        const int k_cap = 110;
+        int k_p = 6 * k > 64 ? 6 * k : 64;
+        const bool automatic = ctx->dual_model == 1 && !ctx->dual_force && nested_sizes && have_floor && floor_r2 >= KZ_K_MODEL_MIN_R2 &&
+                               b->n >= (int64_t)16 * KZ_K_FLOOR_PROBE && k_p <= k_cap;
+        if (k_p > k_cap) k_p = k_cap;
+        if ((int64_t)k_p > a->n) k_p = (int)a->n;
+        if ((forced || automatic) && KZ_K_FLOOR_PROBE > 0 && k_p >= k) {
+            const int n_probe = b->n < KZ_K_FLOOR_PROBE ? (int)b->n : KZ_K_FLOOR_PROBE;
+            const int64_t pstride = b->n / n_probe;
+            const size_t w = (size_t)k_p + 1;
+            KzPoolBuf<double> fit_rows, pdist;
+            KzPoolBuf<int64_t> pind;
+            KzPoolBuf<int> plist, pout;
+            rc = plist.alloc(ctx, (size_t)n_probe * sizeof(int));
+            if (rc == KZ_OK) rc = pout.alloc(ctx, (size_t)n_probe * sizeof(int));
+            if (rc == KZ_OK) rc = pdist.alloc(ctx, (size_t)n_probe * k_p * 8);
+            if (rc == KZ_OK) rc = pind.alloc(ctx, (size_t)n_probe * k_p * 8);
+            if (rc == KZ_OK) rc = fit_rows.alloc(ctx, (size_t)n_probe * w * 8);
+            if (rc == KZ_ERR_NOMEM) rc = KZ_OK;   // (no memory for the probe: the sample route)
+            else if (rc == KZ_OK) {
+                hipLaunchKernelGGL(kz_strided_rows_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, plist.get(), n_probe, pstride);
+                hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, pout.get(), n_probe);
+                KZ_HIP(hipGetLastError());
+                kz_knn_stats stp;
+                memset(&stp, 0, sizeof(stp));
+                KzResearch probe_rs;
+                probe_rs.prec = 0;
+                // (timed on the host, from here to the fit: the stream is idle -- kz_floor_model has waited for it -- and the fit's
+                //  read-back waits for it again; the sub-search's own event pair is re-recorded inside kz_knn_impl)
+                float esc_ms = 0;
+                const auto t_probe0 = std::chrono::steady_clock::now();
+                // (the results go to the probe's own [n_probe, k_p] block, row i for probe row i)
+                rc = kz_escalate_rows(ctx, b, 0, plist.get(), n_probe, a, k_p, 0, nullptr, probe_rs, pdist.get(), pind.get(), &stp, &esc_ms, pout.get());
+                if (rc != KZ_OK) return rc;
+                std::vector<double> hrows((size_t)n_probe * w);
+                hipLaunchKernelGGL(kz_dual_model_rows_kernel, dim3((unsigned)(((size_t)n_probe * w + 255) / 256)), dim3(256), 0, ctx->stream, pdist.get(),
+                                   ib->rowq, n_probe, pstride, k_p, b->metric, fit_rows.get());
+                KZ_HIP(hipGetLastError());
+                KZ_HIP(hipMemcpyAsync(hrows.data(), fit_rows.get(), hrows.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+                KZ_HIP(hipStreamSynchronize(ctx->stream));
+                const bool fit_ok = kz_theta_fit(hrows.data(), n_probe, k_p, k, ctx->floor_margin, &mfit);
+                rev_probe_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_probe0).count();
+                model = fit_ok && (forced || (mfit.n_saturated == 0 && mfit.n_short == 0 && mfit.mean_count < (double)rank * stride));
+            } else {
+                return rc;
+            }
+        }
+    }
+    if (model) {
+        int64_t cap = ((int64_t)2 * mfit.max_count + 63) & ~(int64_t)63;
+        ev_cap = (int)(cap < 64 ? 64 : (cap > 4096 ? 4096 : cap));
+        log_cap = (long long)(2.0 * (double)b->n * mfit.mean_count) + (1 << 20);
+    }
+    if (model) {   // (the footprint gate above priced the sample route's buffers: a forced model with huge counts stays within the same budget)
+        const double budget = ctx->dual_max_gb > 0 ? ctx->dual_max_gb * (double)(1ull << 30) : KZ_DUAL_MAX_BYTES;
+        if ((double)b_pad * ev_cap * 8.0 + (double)log_cap * 24.0 > budget) {
+            then = 1;
+            return KZ_OK;
+        }
+    }
+    rc = ev.alloc(ctx, (size_t)b_pad * ev_cap * 8);
+    if (rc == KZ_OK) rc = log_keys.alloc(ctx, (size_t)log_cap * 16);
+    if (rc == KZ_OK) rc = log_meta.alloc(ctx, (size_t)log_cap * 8);
+    if (rc != KZ_OK) {   // (not enough memory for the event buffers: the two ordinary searches need far less)
+        then = 1;
+        return KZ_OK;
     }
 
     // ---- sample sweep's lists.  The threshold is the rank-th best sample key, and the rank-th best of ANY set of distinct sample
@@ -929,8 +1084,7 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     const int64_t s_img_rows = s_tiles * KZ_TILE;   // rows of S: image rows [0, s_img_rows) of the dealt image
     // (it saves t_sweep / stride and costs ~1 ms of extra launches, sorts and a host synchronisation: C2's shared sweep, 2.6 model-ms at
     //  stride 4, went from 5.7 to 6.7 ms per step with it -- taken from 2 model-ms of saving on; "dual_force" keeps it for the tests)
-    bool nested = ctx->dual_nested && s_tiles >= 8 && s_tiles < a->n / KZ_TILE && s_img_rows >= (int64_t)8 * KP &&
-                  b->n <= kz_rows_per_chunk(ctx, KP, false) && (ctx->dual_force || t_sweep_ms / stride >= KZ_K_NESTED_MIN_MS);
+    bool nested = nested_sizes && !model;   // (MODEL THRESHOLDS: no sample of any kind)
     if (nested) {
         const double t2_ms = 2.0 * (double)b->n * (double)s_img_rows * (double)(a->kg * 4) / 1e12;
         const int rank3_safe = k + 1 < KP ? k + 1 : KP;
@@ -1139,6 +1293,11 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
             return KZ_OK;
         }
         nested_sweep_ms = st2.main_kernel_ms;
+    } else if (model) {
+        hipLaunchKernelGGL(kz_dual_model_theta_kernel, dim3((unsigned)((b_pad + 255) / 256)), dim3(256), 0, ctx->stream, b->n, b_pad, ib->rowq, ib->bias,
+                           ia->d_max, ib->d_max, ib->center->d_scale, mfit.alpha + ctx->dual_model_shift, mfit.beta, mfit.margin, ctx->eps_scale,
+                           kz_gamma_acc_h(a->kg), theta.get(), floor_.get());
+        KZ_HIP(hipGetLastError());
     } else {
         // ---- classic sample image: every stride-th tile of A's fp16 image (tiles are contiguous runs of n_slices x 4 KiB), dealt over the parts
         hipLaunchKernelGGL(kz_dual_sample_kernel, dim3((unsigned)s_tiles), dim3(256), 0, ctx->stream, (const uint4*)ia->packed, ia->bias,
@@ -1285,6 +1444,11 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     // (kz_knn_impl ends with a stream synchronisation: ev.get()[5] and ev.get()[6] around the sample sweep have completed)
     KZ_HIP(hipEventElapsedTime(&sample_ms, ctx->ev[5], ctx->ev[6]));
     st_ab.dual = 1;
+    thresh_source = model ? 3 : (nested ? 2 : 1);
+    st_ab.thresh_source = thresh_source;
+    st_ab.floor_r2 = floor_r2;
+    st_ab.model_max_events = mfit.max_count;
+    st_ab.model_mean_events = mfit.mean_count;
     st_ab.main_kernel_ms += nested_sweep_ms;   // (nested: S x B is swept by the sample sweep, the rest of A x B by the main sweep)
     if (nested) {
         // the sample rows' own chain (second stream, synchronised above): rows it could not certify -- or all of them when its
@@ -1327,7 +1491,11 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         memcpy(&st_ba.max_err_ratio, ctx->h_counters + 14, 8);
         float ms = 0;
         KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[8], ctx->ev[9]));
-        st_ba.main_kernel_ms = sample_ms - (float)nested_sweep_ms + ms;   // sample stage (without the part of the matrix it covers for both directions) + scatter + select: what this direction cost besides the shared sweep
+        st_ba.probe_ms = rev_probe_ms;   // (MODEL THRESHOLDS: the reverse probe; 0 on the sample routes)
+        st_ba.thresh_source = thresh_source;
+        st_ba.model_max_events = mfit.max_count;
+        st_ba.model_mean_events = mfit.mean_count;
+        st_ba.main_kernel_ms = rev_probe_ms + sample_ms - (float)nested_sweep_ms + ms;   // reverse probe + sample stage (without the part of the matrix it covers for both directions) + scatter + select: what this direction cost besides the shared sweep
         KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[9], ctx->ev[10]));
         st_ba.finalize_ms = ms;
         st_ba.list_len = KPr;

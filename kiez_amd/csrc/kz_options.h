@@ -64,6 +64,8 @@ static const KzOption KZ_OPTIONS[] = {
     {"dual_short_main", KZ_OPT_BOOL, KZ_O(dual_short_main), 0, 1, 1, 0, {}, 0, "main sweep keeps k / dual_short_div lists of 16 (13 .. 110 neighbours)"},
     {"dual_short_extra", KZ_OPT_INT, KZ_O(dual_short_extra), 1, 200, 48, 0, {}, 0, "entries selected beyond k on that route"},
     {"dual_short_min_tiles", KZ_OPT_INT, KZ_O(dual_short_min_tiles), 1, 1e9, 128, 0, {}, 0, "... taken when an index range has at least this many tiles"},
+    {"dual_model", KZ_OPT_INT, KZ_O(dual_model), 0, 2, 1, 0, {}, 0, "event thresholds from a probe model instead of a sample sweep: 0 never, 1 where the gate allows, 2 forced (tests)"},
+    {"dual_model_shift", KZ_OPT_F64, KZ_O(dual_model_shift), -1e300, 1e300, 0, 0, {}, 0, "... added to the model's thresholds (test knob: a huge value leaves no events, every row is searched again)"},
 };
 #undef KZ_O
 static const int KZ_N_OPTIONS = (int)(sizeof(KZ_OPTIONS) / sizeof(KZ_OPTIONS[0]));
