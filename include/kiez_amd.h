@@ -346,6 +346,27 @@ int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t
  * h_out[3] (host) = #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1) -- the float64 sum in a fixed order. */
 int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* h_ks, int n_k, int64_t* h_hits, double* h_out);
 
+/* ---- one-to-one alignment: stable matching over neighbour lists (kz_match.hip) -- additive, ABI v7 --------------------------- */
+/* d_dist [n_q, k] (dist_dtype: KZ_F32 or KZ_F64) and d_ind [n_q, k] on the device: the lists kz_knn, kz_select_topk or kz_knn_reduced
+ * return.  Entry (i, c) with 0 <= d_ind[i, c] < n_index is a PAIR of source row i and target row d_ind[i, c] with value
+ * w = d_dist[i, c]; any other entry (kz_knn_reduced's INT_MAX padding, a -1) is no pair.  Writes the source-proposing
+ * deferred-acceptance (Gale-Shapley) matching: a source row prefers its pairs by column, smaller first; a target row prefers the
+ * sources that list it by (key(w), source row), smaller first, key = kz_knn_reduced's order of w widened to double -- NaN counts as
+ * +inf, -0.0 equals +0.0, -inf is an ordinary smallest value.  The source-optimal stable matching is unique for fixed preferences,
+ * so the result is that of a sequential Gale-Shapley in any order, bit for bit and from run to run; where every row is
+ * non-decreasing in key order it equals the greedy assignment over all pairs sorted by (key, source row, column), taking a pair
+ * when both ends are free.  A row may list a target twice: each entry is a proposal of its own.
+ * d_match[i] = the target row of source row i or -1, d_col[i] = the column of that pair or -1 (both [n_q] on the device).
+ * *h_rounds (host, may be NULL) = the number of proposal rounds that had a proposer (at most n_q k + n_index).
+ * 1 <= k <= KZ_MAX_CANDIDATES, 1 <= n_index <= 2^31 - 2, n_q <= 2^31 - 2, a known dist_dtype: KZ_ERR_INVALID otherwise, before
+ * anything is written; n_q == 0 returns at once.  Rounds are separate launches on the context's stream (integer atomics only, no
+ * launch waits for another workgroup); synchronises the stream. */
+int kz_match_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index,
+                   int64_t* d_match, int64_t* d_col, int64_t* h_rounds);
+/* The values of the matched pairs: d_out[i] = d_dist[i, d_col[i]] in d_dist's dtype, NaN where d_col[i] < 0 (d_out: [n_q] on the
+ * device).  Enqueued on the context's stream; n_q and k as above. */
+int kz_match_values(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q, int k, void* d_out);
+
 /* float64 -> float32 cast of an [count] array (cosine + float32 inputs keep the reference's output dtype). */
 int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count);
 

@@ -7,6 +7,7 @@ from .hubness_reduction import (CSLS, DisSimLocal, HubnessReduction, LocalScalin
 from .kiez import Kiez, hubness_reduction_resolver, nn_algorithm_resolver
 from .neighbors import NNAlgorithm, NotFittedError, SklearnNN
 from . import analysis, evaluate, io  # noqa: F401  (hubness_score, hits, from_openea: "next" rows of SURVEY.md §8 f)
+from . import matching  # noqa: F401  (one_to_one: the stable matching over neighbour lists)
 
 __version__ = "0.1.0"
 __all__ = ["Kiez", "NNAlgorithm", "SklearnNN", "HubnessReduction", "NoHubnessReduction", "CSLS", "LocalScaling",

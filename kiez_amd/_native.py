@@ -136,6 +136,8 @@ SYMBOLS = [
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_rank_stats", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.c_int, C.POINTER(_I64), C.POINTER(C.c_double)]),
+    ("kz_match_lists", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, _P, _P, C.POINTER(_I64)]),
+    ("kz_match_values", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _P]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_comm_destroy", C.c_int, [_P]),
@@ -450,6 +452,42 @@ def knn_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, 
     _check(ctx.lib.kz_knn_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, k, int(kind), *state, w.ptr, ind.ptr),
            "kz_knn_reduced")
     return w, ind
+
+
+def _list_pair(dist: DeviceArray, ind: DeviceArray):
+    """(n_q, k, dtype code) of a pair of neighbour lists on the device, as kz_match_lists / kz_match_values take them."""
+    if not isinstance(dist, DeviceArray) or not isinstance(ind, DeviceArray):
+        raise ValueError("dist and ind must be DeviceArrays")
+    if len(dist.shape) != 2 or dist.shape != ind.shape:
+        raise ValueError(f"dist and ind must be 2-D and of one shape, got {dist.shape} and {ind.shape}")
+    if dist.dtype not in (np.float32, np.float64) or ind.dtype != np.int64:
+        raise ValueError(f"dist must be float32 or float64 and ind int64, got {dist.dtype} and {ind.dtype}")
+    return dist.shape[0], dist.shape[1], KZ_F32 if dist.dtype == np.float32 else KZ_F64
+
+
+def match_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int) -> Tuple[DeviceArray, DeviceArray, int]:
+    """kz_match_lists -> (match int64 [n_q], col int64 [n_q], rounds): the source-proposing stable matching over the neighbour lists
+    dist / ind [n_q, k] (float32 or float64 / int64, on the device) against n_index target rows.  match[i] is the target row of
+    source row i and col[i] the column of that pair, -1 both where the row stays unmatched; rounds counts the proposal rounds."""
+    n_q, k, dtype = _list_pair(dist, ind)
+    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
+    rounds = _I64(0)
+    _check(ctx.lib.kz_match_lists(ctx.handle, dist.ptr, dtype, ind.ptr, n_q, k, int(n_index), match.ptr, col.ptr, C.byref(rounds)),
+           "kz_match_lists")
+    return match, col, int(rounds.value)
+
+
+def match_values(ctx: Context, dist: DeviceArray, col: DeviceArray) -> DeviceArray:
+    """kz_match_values -> dist[i, col[i]] in dist's dtype, NaN where col[i] < 0: [n_q] on the device."""
+    if len(dist.shape) != 2 or dist.dtype not in (np.float32, np.float64):
+        raise ValueError(f"dist must be a 2-D float32 or float64 device array, got {dist.dtype} {dist.shape}")
+    n_q, k = dist.shape
+    if col.dtype != np.int64 or col.shape != (n_q,):
+        raise ValueError(f"col must be int64 of shape ({n_q},), got {col.dtype} {col.shape}")
+    out = ctx.empty((n_q,), dist.dtype)
+    _check(ctx.lib.kz_match_values(ctx.handle, dist.ptr, KZ_F32 if dist.dtype == np.float32 else KZ_F64, col.ptr, n_q, k, out.ptr),
+           "kz_match_values")
+    return out
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):

@@ -20,16 +20,9 @@
 // The w that is WRITTEN is the expression's own result: a NaN comes back as NaN.  Integer compares and counts only: nothing depends
 // on the order the workgroups, or the waves of one, run in.
 #pragma once
+#include "kz_order_key.h"   // kz_knnr_key, KZ_KNNR_PAD
 
 constexpr int KZ_KNNR_CHUNK = 4096;   // index rows per workgroup of the first level: 8 loads of 16 bytes, 16 keys per thread
-
-__device__ __forceinline__ unsigned long long kz_knnr_key(double w) {
-    unsigned long long b = (unsigned long long)__double_as_longlong(w);
-    if (w != w) b = 0x7ff0000000000000ull;   // NaN ranks as +inf
-    if (w == 0.0) b = 0ull;                  // -0.0 == +0.0
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-constexpr unsigned long long KZ_KNNR_PAD = ~0ull;   // a place without an entry: above +inf's key (0xfff0...), the largest a w has
 
 // The workgroup's total of a wave-uniform count, to every thread: one exchange through LDS and ONE barrier -- the calls alternate
 // between two sets of four counters (`pass`), so the writes of call n + 2 come after the barrier of call n + 1, which every thread

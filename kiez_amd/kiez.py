@@ -13,6 +13,7 @@ from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
 
+from . import _native as N
 from .hubness_reduction import (CSLS, DisSimLocal, HubnessReduction, LocalScaling, MutualProximity,
                                 NoHubnessReduction)
 from .neighbors import NNAlgorithm, SklearnNN, available_nn_algorithms
@@ -113,6 +114,31 @@ class Kiez:
         `n_candidates`.  MutualProximity 'empiric' and DisSimLocal raise NotImplementedError."""
         dist, ind = self.hubness.kneighbors_whole_index(k)
         return (dist, ind) if return_distance else ind
+
+    def match_device(self, k: Optional[int] = None, whole_index: bool = False):
+        """Like `match` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+        nn = self.algorithm
+        cached = getattr(nn, "_forward", None)
+        dist, ind = self.kneighbors_whole_index_device(k) if whole_index else self.kneighbors_device(k)
+        if cached is not None and nn._forward is None:
+            nn._forward = cached   # (the shared sweep's forward lists stay cached for the kneighbors() that follows, as after gold_ranks)
+        ctx = dist.ctx
+        match, col, _ = N.match_lists(ctx, dist, ind, nn.target_.shape[0])
+        return N.match_values(ctx, dist, col), match
+
+    def match(self, k: Optional[int] = None, whole_index: bool = False, return_distance: bool = True):
+        """One-to-one alignment of the fitted source and target rows: the source-proposing stable matching (`matching.one_to_one`)
+        over the neighbour lists of `kneighbors(k)` or, with `whole_index=True`, of `kneighbors_whole_index(k)`.  Both kinds of
+        list are sorted by value, so the matching is the greedy assignment over all listed pairs in the order (value, source row,
+        column).  `k`, its warnings and every error are those of the list call.  The lists never leave HBM; the matching runs on the
+        device (kz_match_lists).
+
+        Returns `(match_dist, match_ind)` or, with `return_distance=False`, `match_ind`: per source row the matched target row
+        (-1: none) and the value of that pair in the lists' dtype (NaN: none).  No target row appears twice.  The result is numpy
+        arrays also after a fit on tensors: tensor output is out of scope.  `evaluate.hits(match_ind[:, None], gold, k=[1])` is the
+        precision of the matching."""
+        match_dist, match_ind = self.match_device(k, whole_index)
+        return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
 
     def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
         """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
