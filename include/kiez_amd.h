@@ -196,6 +196,12 @@ int kz_row_nanstats(kz_ctx* ctx, const double* d_dist, int64_t n, int K, double*
 /* CSLS.transform, csls.py:85-96.  r_train[j] = mean_K dist_t2s[j,:] (length n_t). */
 int kz_csls(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, const double* d_r_train,
             double* d_out);
+/* Sinkhorn / inverted softmax (no counterpart in the reference) -- ABI v7, additive: d_out[i, c] = (d_dist[i, c] - d_f[i]) -
+ * d_g[d_ind[i, c]], two float64 subtractions in that order: the candidate-list form of KZ_RANK_DUAL below, bit for bit what
+ * kz_gold_ranks_reduced / kz_knn_reduced compute for the pair.  d_f: [n], d_g: [n_t], the potentials (kz_softmin_rows).  d_ind is
+ * trusted as in kz_csls: every entry must be a row of d_g. */
+int kz_dual_shift(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, const double* d_f,
+                  const double* d_g, double* d_out);
 /* LocalScaling.transform, local_scaling.py:129-151.  nicdm == 0: r_t = K-th reverse distance (:135-140);
  * nicdm != 0: r_t = mean reverse distance (:142-147). */
 int kz_local_scaling(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, const double* d_r_t,
@@ -313,16 +319,19 @@ int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t 
  *   KZ_RANK_LS         w = 1 - exp(-d^2 / (q_a[r] t_a[j]))                    (the K-th forward / reverse distance)
  *   KZ_RANK_NICDM      w = d / sqrt(q_a[r] t_a[j])                            (the means)
  *   KZ_RANK_MP_NORMAL  w = 1 - sf(d; q_a[r], q_b[r]) sf(d; t_a[j], t_b[j])    (nanmean and nanstd; sf: the normal survival function)
+ *   KZ_RANK_DUAL       w = (d - q_a[r]) - t_a[j]                              (the dual potentials f, g of Sinkhorn / the inverted
+ *                                                                              softmax: kz_softmin_rows; kz_dual_shift's expression)
  * in float64, the expressions of kz_csls / kz_local_scaling / kz_mp_normal: w of a pair is bit for bit what those write for it, so
  * with lists over the whole index (K = index.n) the rank is the count over the transform's output row by (value, index row).  A NaN w
  * ranks as +inf by row.  MP normal is exactly 1.0 for pairs far beyond both lists: they tie and go by row.
  * d_q_a / d_q_b: [q_count] on the device, entry r for query row q_begin + r (kz_row_stats / kz_row_nanstats of the forward lists);
  * d_t_a / d_t_b: [index.n] (the same of the reverse lists: the fit state).  d_q_b and d_t_b are for KZ_RANK_MP_NORMAL and must be
- * NULL otherwise; an unknown kind, a missing or a surplus vector: KZ_ERR_INVALID.  Everything else as kz_gold_ranks. */
+ * NULL otherwise (KZ_RANK_DUAL too: one potential per side); an unknown kind, a missing or a surplus vector: KZ_ERR_INVALID.  Everything else as kz_gold_ranks. */
 #define KZ_RANK_CSLS 1
 #define KZ_RANK_LS 2
 #define KZ_RANK_NICDM 3
 #define KZ_RANK_MP_NORMAL 4
+#define KZ_RANK_DUAL 8 /* (not 5: 5 .. 7 and 0 stay unknown kinds) */
 int kz_gold_ranks_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                           const int64_t* d_gold, int kind, const double* d_q_a, const double* d_q_b,
                           const double* d_t_a, const double* d_t_b, int64_t* d_rank);
@@ -342,6 +351,26 @@ int kz_gold_ranks_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, 
 int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                    int k, int kind, const double* d_q_a, const double* d_q_b, const double* d_t_a, const double* d_t_b,
                    double* d_w, int64_t* d_ind);
+/* Row-wise SOFT-MIN over the whole index -- ABI v7, additive: the primitive of the Sinkhorn potentials and the inverted softmax.
+ *   d_out[r] = softmin_eps over every index row j of (d_rj - d_off[j])  +  shift,   softmin_eps(x) = m - eps log sum exp(-(x - m) / eps),
+ * m = min x, in float64; d_rj = the distance kz_knn returns for query row q_begin + r and index row j (the exact ranking value
+ * converted as kz_knn converts it: what KZ_RANK_* reduce).  d_off: [index.n] on the device or NULL (no offset); d_out: [q_count] on
+ * the device.  eps > 0 is the temperature, in the units of d.  A Sinkhorn row step is this call with d_off = g; the column step is
+ * the same call with target as query, source as index, d_off = f and shift = eps log(n_s / n_t).
+ * A NaN entry (a NaN distance, a NaN offset) counts as +inf and contributes nothing; a row with no entry below +inf gives +inf + shift,
+ * a row whose minimum is -inf gives -inf.  The minimum is taken out before the sum: no term overflows, and the sum is >= 1 however
+ * small eps is.  The order in which a row's terms are added is a function of j, index.n and KZ_SOFTMIN_CHUNK_ROWS only (no atomics,
+ * fixed trees): a row's result has the same bits wherever it stands in the call, however the call is split into row ranges, and
+ * from run to run.  eps not finite or <= 0, a shift that is not finite, matrices that disagree (dtype, metric, exponent, seuclidean V): KZ_ERR_INVALID;
+ * q_count == 0: KZ_OK.  No self-exclusion.  Runs the exact float64 value kernels of kz_knn for every query row and a two-level
+ * reduction; synchronises the context's stream. */
+#define KZ_SOFTMIN_CHUNK_ROWS 4096 /* index rows per first-level workgroup: part of the summation order */
+int kz_softmin_rows(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index, double eps,
+                    const double* d_off, double shift, double* d_out);
+/* *h_out (host) = max over i < n of |d_a[i] - d_b[i]| (float64 vectors on the device), entries whose difference is NaN ignored (0 when
+ * none is left, n == 0 included): a maximum, so the result does not depend on the order anything runs in.  The convergence read-out
+ * of the Sinkhorn iteration.  Synchronises the context's stream. */
+int kz_max_abs_diff(kz_ctx* ctx, const double* d_a, const double* d_b, int64_t n, double* h_out);
 /* Reductions of a rank vector d_rank [n] (entries < 0: no rank).  h_hits[j] (host, j < n_k <= 64) = #(0 <= rank < h_ks[j]);
  * h_out[3] (host) = #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1) -- the float64 sum in a fixed order. */
 int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* h_ks, int n_k, int64_t* h_hits, double* h_out);

@@ -118,6 +118,7 @@ SYMBOLS = [
     ("kz_row_stats", C.c_int, [_P, _P, _I64, C.c_int, _P, _P, _P]),
     ("kz_row_nanstats", C.c_int, [_P, _P, _I64, C.c_int, _P, _P]),
     ("kz_csls", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, _P]),
+    ("kz_dual_shift", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, _P, _P]),
     ("kz_local_scaling", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, C.c_int, _P]),
     ("kz_mp_normal", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, _P, _P]),
     ("kz_mp_empiric", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, _P, _I64, C.c_int, _P]),
@@ -135,6 +136,8 @@ SYMBOLS = [
     ("kz_gold_ranks", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    ("kz_softmin_rows", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, _P, C.c_double, _P]),
+    ("kz_max_abs_diff", C.c_int, [_P, _P, _P, _I64, C.POINTER(C.c_double)]),
     ("kz_rank_stats", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.c_int, C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("kz_match_lists", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, _P, _P, C.POINTER(_I64)]),
     ("kz_match_values", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _P]),
@@ -398,6 +401,7 @@ def gold_ranks(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev:
 
 # kz_gold_ranks_reduced's kinds (include/kiez_amd.h: KZ_RANK_*)
 RANK_CSLS, RANK_LS, RANK_NICDM, RANK_MP_NORMAL = 1, 2, 3, 4
+RANK_DUAL = 8   # w = (d - f_i) - g_j, the dual potentials of Sinkhorn / the inverted softmax (5 .. 7 stay unknown kinds)
 
 
 def gold_ranks_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev: DeviceArray, kind: int, q_state, t_state,
@@ -452,6 +456,61 @@ def knn_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, 
     _check(ctx.lib.kz_knn_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, k, int(kind), *state, w.ptr, ind.ptr),
            "kz_knn_reduced")
     return w, ind
+
+
+# index rows per first-level workgroup of kz_softmin_rows (include/kiez_amd.h: KZ_SOFTMIN_CHUNK_ROWS): part of its summation order
+SOFTMIN_CHUNK = 4096
+
+
+def _f64_vector(what: str, v, n: Optional[int] = None) -> DeviceArray:
+    """`v` if it is a 1-D float64 device vector (of length `n`, where one is given)."""
+    if not isinstance(v, DeviceArray) or v.dtype != np.float64 or len(v.shape) != 1 or (n is not None and v.shape[0] != n):
+        raise ValueError(f"{what} must be a float64 device vector" + ("" if n is None else f" of shape ({n},)"))
+    return v
+
+
+def softmin_rows(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, eps: float, off: Optional[DeviceArray] = None,
+                 shift: float = 0.0, q_begin: int = 0, q_count: Optional[int] = None) -> DeviceArray:
+    """kz_softmin_rows -> float64 [q_count] on the device: per query row q_begin + r the soft-min at temperature `eps` over EVERY
+    index row j of (d_rj - off[j]), plus `shift`; d is the distance kz_knn returns for the pair.  `off`: a float64 DeviceArray
+    [index rows] or None.  NaN entries count as +inf; the bits of a row do not depend on how the rows are split into calls."""
+    if q_count is None:
+        q_count = query.shape[0] - q_begin
+    if off is not None:
+        _f64_vector("off", off, index.shape[0])
+    out = ctx.empty((max(q_count, 0),), np.float64)
+    _check(ctx.lib.kz_softmin_rows(ctx.handle, query.handle, q_begin, q_count, index.handle, float(eps), off.ptr if off is not None else None,
+                                   float(shift), out.ptr), "kz_softmin_rows")
+    return out
+
+
+def dual_shift(ctx: Context, dist: DeviceArray, ind: DeviceArray, f: DeviceArray, g: DeviceArray) -> DeviceArray:
+    """kz_dual_shift -> float64 [n, K] on the device: (dist[i, c] - f[i]) - g[ind[i, c]], the candidate-list form of RANK_DUAL.
+    Every entry of `ind` must be a row of `g` (the native call trusts it, as kz_csls does: `index_range` reads the range back)."""
+    if len(dist.shape) != 2 or dist.shape != ind.shape or dist.dtype != np.float64 or ind.dtype != np.int64:
+        raise ValueError(f"dist (float64) and ind (int64) must be 2-D device arrays of one shape, got {dist.dtype} {dist.shape} and "
+                         f"{ind.dtype} {ind.shape}")
+    n, K = dist.shape
+    _f64_vector("f", f, n)
+    _f64_vector("g", g)
+    out = ctx.empty((n, K), np.float64)
+    _check(ctx.lib.kz_dual_shift(ctx.handle, dist.ptr, ind.ptr, n, K, f.ptr, g.ptr, out.ptr), "kz_dual_shift")
+    return out
+
+
+def index_range(ctx: Context, ind: DeviceArray) -> Tuple[int, int]:
+    """kz_minmax_i64 -> (smallest, largest) entry of a non-empty int64 device array."""
+    lo, hi = _I64(0), _I64(0)
+    _check(ctx.lib.kz_minmax_i64(ctx.handle, ind.ptr, int(np.prod(ind.shape, dtype=np.int64)), C.byref(lo), C.byref(hi)), "kz_minmax_i64")
+    return int(lo.value), int(hi.value)
+
+
+def max_abs_diff(ctx: Context, a: DeviceArray, b: DeviceArray) -> float:
+    """kz_max_abs_diff -> max |a - b| of two float64 device vectors of one shape, NaN differences ignored (0.0 when none is left)."""
+    _f64_vector("b", b, _f64_vector("a", a).shape[0])
+    h = C.c_double(0.0)
+    _check(ctx.lib.kz_max_abs_diff(ctx.handle, a.ptr, b.ptr, a.shape[0], C.byref(h)), "kz_max_abs_diff")
+    return float(h.value)
 
 
 def _list_pair(dist: DeviceArray, ind: DeviceArray):

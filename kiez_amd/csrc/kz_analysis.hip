@@ -220,6 +220,27 @@ __global__ __launch_bounds__(256) void kz_rank_stats_kernel(const long long* __r
     }
 }
 
+// out[0] = max |a[i] - b[i]| over the entries whose difference is not NaN (0.0 when none is left): the convergence read-out of the
+// Sinkhorn iteration (kz_max_abs_diff).  One workgroup -- the vectors are one potential per row of a side -- every thread a strided
+// maximum, then a tree; a maximum does not depend on the order it is taken in.
+__global__ __launch_bounds__(256) void kz_max_abs_diff_kernel(const double* __restrict__ a, const double* __restrict__ b, int64_t n,
+                                                              double* __restrict__ out) {
+    __shared__ double s_m[256];
+    const int tid = threadIdx.x;
+    double m = 0.0;
+    for (int64_t i = tid; i < n; i += 256) {
+        const double d = fabs(a[i] - b[i]);
+        m = d > m ? d : m;   // (a NaN difference compares false: ignored)
+    }
+    s_m[tid] = m;
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+        if (tid < off) s_m[tid] = s_m[tid + off] > s_m[tid] ? s_m[tid + off] : s_m[tid];
+        __syncthreads();
+    }
+    if (tid == 0) out[0] = s_m[0];
+}
+
 // ---- self-test of kz_div_shared (kz_common.h): pseudo-random pairs, the bits of the shared-reciprocal quotient against a / b ----
 __device__ __forceinline__ unsigned long long kz_mix64(unsigned long long z) {   // (splitmix64 finaliser)
     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -280,6 +301,21 @@ int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* 
     h_out[0] = (double)h[n_k];       // # ranked
     h_out[1] = (double)h[n_k + 1];   // sum (rank + 1)
     memcpy(&h_out[2], &h[n_k + 2], 8);   // sum 1 / (rank + 1)
+    return KZ_OK;
+}
+
+int kz_max_abs_diff(kz_ctx* ctx, const double* d_a, const double* d_b, int64_t n, double* h_out) {
+    KZ_REQUIRE(ctx && h_out && n >= 0 && (n == 0 || (d_a && d_b)), "kz_max_abs_diff: bad argument");
+    *h_out = 0.0;
+    if (n == 0) return KZ_OK;
+    KZ_HIP(hipSetDevice(ctx->device));
+    void* scratch = nullptr;
+    const int rc = kz_scratch(ctx, 256, &scratch);
+    if (rc != KZ_OK) return rc;
+    hipLaunchKernelGGL(kz_max_abs_diff_kernel, dim3(1), dim3(256), 0, ctx->stream, d_a, d_b, n, (double*)scratch);
+    KZ_HIP(hipGetLastError());
+    KZ_HIP(hipMemcpyAsync(h_out, scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
     return KZ_OK;
 }
 

@@ -78,7 +78,8 @@ __device__ __forceinline__ bool kz_rank_before(double v, int64_t j, double vg, i
 }
 
 // ---- ranks under a pointwise hubness reduction (kz_gold_ranks_reduced) ---------------------------------------------------------
-// CSLS, LocalScaling 'standard', NICDM and MutualProximity 'normal' are functions w = f(d, state of the query row, state of the
+// CSLS, LocalScaling 'standard', NICDM, MutualProximity 'normal' and the dual potentials of Sinkhorn / the inverted softmax
+// (KZ_RANK_DUAL: w = (d - f_i) - g_j) are functions w = f(d, state of the query row, state of the
 // index row) of the pair's distance (kz_reduce.h), defined for EVERY index row and not for the K candidates alone: the count
 // with the value converted to the distance the search returns (kz_output_distance<T>: what the transform kernels are fed) and
 // reduced before it is compared.  The expressions are the transform kernels' own, so w of a candidate is the bits kz_csls /
@@ -87,8 +88,9 @@ __device__ __forceinline__ bool kz_rank_before(double v, int64_t j, double vg, i
 // and go by row.
 constexpr int KZ_RANK_NONE = 0;   // (internal, beside the public KZ_RANK_*: no reduction, the ranking value itself -- kz_gold_ranks)
 struct KzRankReduction {
-    int kind;            // KZ_RANK_CSLS .. KZ_RANK_MP_NORMAL
-    const double* q_a;   // [q_count], entry r for query row q_begin + r: mean (CSLS, NICDM), last (LS), nanmean (MP) of its forward list
+    int kind;            // KZ_RANK_CSLS .. KZ_RANK_MP_NORMAL, KZ_RANK_DUAL
+    const double* q_a;   // [q_count], entry r for query row q_begin + r: mean (CSLS, NICDM), last (LS), nanmean (MP) of its forward list;
+                         // DUAL: the potentials f (here) and g (t_a)
     const double* q_b;   // MP: nanstd; else null
     const double* t_a;   // [index.n]: the fit state of the index side, same statistic of the reverse lists
     const double* t_b;   // MP: nanstd; else null
@@ -103,6 +105,7 @@ __device__ __forceinline__ double kz_rank_reduce(double v, double p, double qa, 
     if (KIND == KZ_RANK_CSLS) return kz_reduce_csls(d, qa, ta);
     if (KIND == KZ_RANK_LS) return kz_reduce_ls(d, qa, ta);
     if (KIND == KZ_RANK_NICDM) return kz_reduce_nicdm(d, qa, ta);
+    if (KIND == KZ_RANK_DUAL) return kz_reduce_dual(d, qa, ta);
     return kz_reduce_mp_normal(d, qa, qb, ta, tb);
 }
 
@@ -186,6 +189,8 @@ static int kz_rank_out_metric(int metric) {
 // THE kind x metric x dtype dispatch of the kernels that reduce a value (the count above, the first level of kz_knn_reduced.h):
 // launch(KzRankT<T>, KzRankC<KIND>, KzRankC<METRIC>) is called with the one combination the reduction and the index ask for.
 // (The input dtype decides the rounding of the three converted metrics only: the others have one instantiation.)
+// kz_rank_dispatch_distance is its metric x dtype half, by_kind(KzRankT<T>, KzRankC<METRIC>): what a kernel needs that converts a
+// value to the distance and does something else with it (the soft-min, kz_softmin.h).
 template <typename T>
 struct KzRankT {
     using type = T;
@@ -193,15 +198,7 @@ struct KzRankT {
 template <int V>
 using KzRankC = std::integral_constant<int, V>;
 template <typename F>
-static void kz_rank_dispatch(int kind, const kz_matrix* index, F launch) {
-    auto by_kind = [&](auto t, auto metric) {
-        switch (kind) {
-            case KZ_RANK_CSLS: launch(t, KzRankC<KZ_RANK_CSLS>(), metric); break;
-            case KZ_RANK_LS: launch(t, KzRankC<KZ_RANK_LS>(), metric); break;
-            case KZ_RANK_NICDM: launch(t, KzRankC<KZ_RANK_NICDM>(), metric); break;
-            default: launch(t, KzRankC<KZ_RANK_MP_NORMAL>(), metric); break;
-        }
-    };
+static void kz_rank_dispatch_distance(const kz_matrix* index, F by_kind) {
     auto by_dtype = [&](auto metric) {
         if (index->dtype == KZ_F32)
             by_kind(KzRankT<float>(), metric);
@@ -216,9 +213,22 @@ static void kz_rank_dispatch(int kind, const kz_matrix* index, F launch) {
         default: by_kind(KzRankT<double>(), KzRankC<KZ_COSINE>()); break;
     }
 }
+template <typename F>
+static void kz_rank_dispatch(int kind, const kz_matrix* index, F launch) {
+    kz_rank_dispatch_distance(index, [&](auto t, auto metric) {
+        switch (kind) {
+            case KZ_RANK_CSLS: launch(t, KzRankC<KZ_RANK_CSLS>(), metric); break;
+            case KZ_RANK_LS: launch(t, KzRankC<KZ_RANK_LS>(), metric); break;
+            case KZ_RANK_NICDM: launch(t, KzRankC<KZ_RANK_NICDM>(), metric); break;
+            case KZ_RANK_DUAL: launch(t, KzRankC<KZ_RANK_DUAL>(), metric); break;
+            default: launch(t, KzRankC<KZ_RANK_MP_NORMAL>(), metric); break;
+        }
+    });
+}
 
 static int kz_rank_require_reduction(const char* who, int kind, const double* q_a, const double* q_b, const double* t_a, const double* t_b) {
-    KZ_REQUIRE(kind >= KZ_RANK_CSLS && kind <= KZ_RANK_MP_NORMAL, "%s: unknown kind %d (KZ_RANK_CSLS .. KZ_RANK_MP_NORMAL)", who, kind);
+    KZ_REQUIRE((kind >= KZ_RANK_CSLS && kind <= KZ_RANK_MP_NORMAL) || kind == KZ_RANK_DUAL,
+               "%s: unknown kind %d (KZ_RANK_CSLS .. KZ_RANK_MP_NORMAL, KZ_RANK_DUAL)", who, kind);
     KZ_REQUIRE(q_a && t_a, "%s: the query-side and index-side state vectors d_q_a / d_t_a are required", who);
     if (kind == KZ_RANK_MP_NORMAL)
         KZ_REQUIRE(q_b && t_b, "%s: KZ_RANK_MP_NORMAL needs the deviations d_q_b / d_t_b", who);

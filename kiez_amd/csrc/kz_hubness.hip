@@ -88,6 +88,15 @@ __global__ void kz_csls_kernel(const double* __restrict__ dist, const int64_t* _
     for (int c = 0; c < K; ++c) out[r * (int64_t)K + c] = kz_reduce_csls(a[c], r_test, r_train[id[c]]);
 }
 
+// Dual potentials (Sinkhorn, inverted softmax): out = (d - f[i]) - g[ind]: the candidate-list form of the whole-index kind
+// KZ_RANK_DUAL (kz_gold_ranks.h), same expression, same bits.  One thread per entry: no row statistic is needed.
+__global__ void kz_dual_shift_kernel(const double* __restrict__ dist, const int64_t* __restrict__ ind, int64_t n, int K,
+                                     const double* __restrict__ f, const double* __restrict__ g, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * (int64_t)K) return;
+    out[e] = kz_reduce_dual(dist[e], f[e / K], g[ind[e]]);
+}
+
 // LocalScaling (local_scaling.py:135-147)
 __global__ void kz_ls_kernel(const double* __restrict__ dist, const int64_t* __restrict__ ind, int64_t n, int K,
                              const double* __restrict__ r_t, int nicdm, double* __restrict__ out) {
@@ -549,6 +558,15 @@ int kz_csls(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, 
     KZ_CHECK_NK("kz_csls");
     KZ_REQUIRE(d_dist && d_ind && d_r_train && d_out, "kz_csls: null argument");
     hipLaunchKernelGGL(kz_csls_kernel, kz_grid1d(n, 256), dim3(256), 0, ctx->stream, d_dist, d_ind, n, K, d_r_train, d_out);
+    KZ_HIP(hipGetLastError());
+    return KZ_OK;
+}
+
+int kz_dual_shift(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, const double* d_f, const double* d_g,
+                  double* d_out) {
+    KZ_CHECK_NK("kz_dual_shift");
+    KZ_REQUIRE(d_dist && d_ind && d_f && d_g && d_out, "kz_dual_shift: null argument");
+    hipLaunchKernelGGL(kz_dual_shift_kernel, kz_grid1d(n * (int64_t)K, 256), dim3(256), 0, ctx->stream, d_dist, d_ind, n, K, d_f, d_g, d_out);
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }

@@ -438,6 +438,130 @@ class MutualProximity(HubnessReduction):
         return self._finish(out, neigh_dist, neigh_ind)
 
 
+class _DualPotentials(HubnessReduction):
+    """What Sinkhorn and InvertedSoftmax share: the reduced distance w_ij = (d_ij - f_i) - g_j with one soft-min potential per source
+    row (f) and per target row (g) -- CSLS's 2 d - r_i - r_j with soft-min potentials over the WHOLE index in place of k-NN means.
+    The state does not come from neighbour lists, so `fit` runs no reverse search: it iterates `_native.softmin_rows`
+    (kz_softmin_rows) between the two fitted sides.  Everything that ranks -- `kneighbors`, `kneighbors_whole_index`,
+    `gold_ranks(reduced=True)`, `Kiez.match` and their device variants -- is the base class's, fed by `transform` (kz_dual_shift) and
+    the whole-index kind RANK_DUAL."""
+
+    _device_native = True
+    _no_rank_reason = None
+
+    def __init__(self, temperature: float = 0.05, **kwargs):
+        if (isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.integer, np.floating))
+                or not np.isfinite(temperature) or temperature <= 0):
+            raise ValueError(f"temperature must be a finite number > 0 (in the units of the search's distance), got {temperature!r}")
+        super().__init__(**kwargs)
+        self.temperature = float(temperature)
+
+    def _fit(self, neigh_dist, neigh_ind, source, target):
+        raise NotImplementedError(f"{type(self).__name__} has no fit state in neighbour lists: `fit` iterates over the whole index")
+
+    @abstractmethod
+    def _potentials(self, source_m, target_m):
+        """(f [n_s], g [n_t]) as float64 DeviceArrays from the two fitted device matrices; sets n_iter_ / potential_change_."""
+
+    def fit(self, source, target=None):
+        if target is None:
+            raise ValueError(f"{type(self).__name__} normalises between two sides: two-sided data only (fit(source, target))")
+        if not self._gpu_nn:
+            raise NotImplementedError(f"{type(self).__name__} needs the MI355X SklearnNN backend (the soft-min runs over the whole index)")
+        nn = self.nn_algo
+        nn.fit(source, target)
+        source_m, target_m = nn._two_sided_operands(type(self).__name__)
+        for attr in ("_f_dev", "_g_dev"):
+            self.__dict__.pop(attr, None)
+        self._f_dev, self._g_dev = self._potentials(source_m, target_m)
+
+    @property
+    def source_potential_(self) -> np.ndarray:
+        check_is_fitted(self, "_f_dev")
+        return self._f_dev.numpy()
+
+    @property
+    def target_potential_(self) -> np.ndarray:
+        check_is_fitted(self, "_g_dev")
+        return self._g_dev.numpy()
+
+    def _forward_rank_state(self):
+        """The potentials ARE the state of both sides: no forward search."""
+        check_is_fitted(self, ["_f_dev", "_g_dev"])
+        return N.RANK_DUAL, self._f_dev, self._g_dev
+
+    def transform(self, neigh_dist, neigh_ind, query=None):
+        check_is_fitted(self, ["_f_dev", "_g_dev"])
+        d, i = self._device_inputs(neigh_dist, neigh_ind)
+        if len(d.shape) != 2 or d.shape[0] != self._f_dev.shape[0]:
+            raise ValueError(f"{type(self).__name__}.transform takes the candidate lists of the fitted source rows "
+                             f"({self._f_dev.shape[0]} rows), got shape {d.shape}: a potential belongs to a fitted row")
+        if d.shape[0] and d.shape[1]:
+            # (the native call trusts the ids, and this method takes any caller's lists: an id that is no target row would read past g)
+            lo, hi = N.index_range(self.ctx, i)
+            if lo < 0 or hi >= self._g_dev.shape[0]:
+                raise ValueError(f"{type(self).__name__}.transform: neigh_ind holds ids in [{lo}, {hi}], the fitted target has "
+                                 f"{self._g_dev.shape[0]} rows")
+        return self._finish(N.dual_shift(self.ctx, d, i, self._f_dev, self._g_dev), neigh_dist, neigh_ind)
+
+
+class Sinkhorn(_DualPotentials):
+    """Entropic optimal transport between source and target rows (Sinkhorn iterations in the log domain), the soft form of the
+    one-to-one step `Kiez.match` takes greedily.  From f = 0, `n_iter` times:
+        column step  g_j = softmin_eps over i of (d_ij - f_i) + eps log(n_s / n_t)
+        row step     f_i = softmin_eps over j of (d_ij - g_j)
+    with softmin_eps(x) = m - eps log sum exp(-(x - m) / eps), m = min x, in float64 over the whole index.  With P_ij =
+    exp(-w_ij / eps), w_ij = (d_ij - f_i) - g_j, every row of P sums to 1 after a row step and the columns approach n_s / n_t.
+
+    `temperature`: eps > 0, in the units of the distance the search returns.  `tol`: stop after the column step whose largest change
+    of g is <= tol (the row step that follows is still taken); None runs exactly `n_iter` iterations.  After `fit`:
+    `source_potential_` / `target_potential_` (numpy), `n_iter_`, `potential_change_` (the last measured change of g: None after a
+    single iteration).  Not a name of the resolver: pass the class or an instance, `Kiez(hubness=Sinkhorn, hubness_kwargs={...})`."""
+
+    def __init__(self, temperature: float = 0.05, n_iter: int = 10, tol: Optional[float] = None, **kwargs):
+        if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+            raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
+        if tol is not None and (isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0):
+            raise ValueError(f"tol must be None or a number >= 0, got {tol!r}")
+        super().__init__(temperature=temperature, **kwargs)
+        self.n_iter = int(n_iter)
+        self.tol = None if tol is None else float(tol)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(temperature = {self.temperature}, n_iter = {self.n_iter}, tol = {self.tol})"
+
+    def _potentials(self, source_m, target_m):
+        ctx, eps = self.ctx, self.temperature
+        shift = eps * float(np.log(source_m.shape[0] / target_m.shape[0]))
+        f = g = None
+        self.potential_change_ = None
+        for it in range(1, self.n_iter + 1):
+            # column step: the same call with target as query and source as index (f = 0 at first: no offset)
+            g_new = N.softmin_rows(ctx, target_m, source_m, eps, off=f, shift=shift)
+            if g is not None:
+                self.potential_change_ = N.max_abs_diff(ctx, g_new, g)
+            g = g_new
+            f = N.softmin_rows(ctx, source_m, target_m, eps, off=g)
+            self.n_iter_ = it
+            if self.tol is not None and self.potential_change_ is not None and self.potential_change_ <= self.tol:
+                break
+        return f, g
+
+
+class InvertedSoftmax(_DualPotentials):
+    """The inverted softmax (Smith et al. 2017): the target-side state is a log-sum-exp over ALL source rows -- one Sinkhorn column
+    step from f = 0 with the constant left out, g_j = softmin_eps over i of d_ij, and f stays 0: the lists are ranked by d_ij - g_j.
+    `temperature`: eps > 0, in the units of the distance the search returns.  Not a name of the resolver: pass the class or an instance."""
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(temperature = {self.temperature})"
+
+    def _potentials(self, source_m, target_m):
+        self.n_iter_, self.potential_change_ = 1, None
+        g = N.softmin_rows(self.ctx, target_m, source_m, self.temperature)
+        return self.ctx.to_device(np.zeros(source_m.shape[0], dtype=np.float64)), g
+
+
 _DESIRED_P_VALUE = 2
 
 
