@@ -92,8 +92,14 @@ __global__ void kz_kocc_int_stats_kernel(const long long* __restrict__ kocc, int
     }
 }
 
-// pass 2 (float reductions around the mean): sum|x-m|, sum(x-m)^2, sum(x-m)^3, sum sqrt(x)
-__global__ void kz_kocc_float_stats_kernel(const long long* __restrict__ kocc, int64_t n, double mean, double* __restrict__ out) {
+// pass 2 (float reductions around the mean): sum|x-m|, sum(x-m)^2, sum(x-m)^3, sum sqrt(x).  No floating-point atomic: workgroup b
+// leaves its four sums in part[4 b .. 4 b + 3] and kz_kocc_float_fold_kernel adds the slots up.  Every step has a fixed shape --
+// a thread's strided chain, the wave butterfly, waves 0..3 in turn, then the fold's chain and tree -- and the grid is a function
+// of n, so the bits of the four sums depend on the histogram alone, not on the order the workgroups run in.
+#define KZ_KOCC_MAX_BLOCKS 1024   // grid cap of the histogram reductions: one slot of four doubles per workgroup, 32 KB of scratch
+__global__ __launch_bounds__(256) void kz_kocc_float_stats_kernel(const long long* __restrict__ kocc, int64_t n, double mean,
+                                                                  double* __restrict__ part) {
+    __shared__ double s_w[4][4];
     double a1 = 0, a2 = 0, a3 = 0, sq = 0;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
         const double x = (double)kocc[e];
@@ -108,11 +114,35 @@ __global__ void kz_kocc_float_stats_kernel(const long long* __restrict__ kocc, i
     a3 = kz_wave_sum(a3);
     sq = kz_wave_sum(sq);
     if ((threadIdx.x & 63) == 0) {
-        atomicAdd(out + 0, a1);
-        atomicAdd(out + 1, a2);
-        atomicAdd(out + 2, a3);
-        atomicAdd(out + 3, sq);
+        const int w = threadIdx.x >> 6;
+        s_w[w][0] = a1;
+        s_w[w][1] = a2;
+        s_w[w][2] = a3;
+        s_w[w][3] = sq;
     }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int q = threadIdx.x;
+        part[(size_t)blockIdx.x * 4 + q] = ((s_w[0][q] + s_w[1][q]) + s_w[2][q]) + s_w[3][q];
+    }
+}
+
+// one workgroup: thread t adds the slots of workgroups t, t + 256, ... in that order, then a tree of fixed shape per quantity
+// (as kz_rank_stats_kernel); launched after kz_kocc_float_stats_kernel on the same stream, no workgroup waits for another
+__global__ __launch_bounds__(256) void kz_kocc_float_fold_kernel(const double* __restrict__ part, int n_blocks, double* __restrict__ out) {
+    __shared__ double s_p[4][256];
+    const int tid = threadIdx.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = tid; b < n_blocks; b += 256)
+        for (int q = 0; q < 4; ++q) acc[q] += part[(size_t)b * 4 + q];
+    for (int q = 0; q < 4; ++q) s_p[q][tid] = acc[q];
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+        if (tid < off)
+            for (int q = 0; q < 4; ++q) s_p[q][tid] += s_p[q][tid + off];
+        __syncthreads();
+    }
+    if (tid < 4) out[tid] = s_p[tid][0];
 }
 
 // Gini numerator sum_i sum_j |x_i - x_j| (estimation.py:83-97), exact in integers
@@ -375,19 +405,21 @@ int kz_kocc_stats(kz_ctx* ctx, const int64_t* d_kocc, int64_t n, double hub_thre
     KZ_REQUIRE(ctx && d_kocc && h_out && n > 0, "kz_kocc_stats: bad argument");
     KZ_HIP(hipSetDevice(ctx->device));
     void* scratch = nullptr;
-    int rc = kz_scratch(ctx, 256, &scratch);
+    int rc = kz_scratch(ctx, 256 + (size_t)KZ_KOCC_MAX_BLOCKS * 4 * sizeof(double), &scratch);
     if (rc != KZ_OK) return rc;
     unsigned long long* di = (unsigned long long*)scratch;  // [0..4] int stats, [5] gini
     double* df = (double*)scratch + 8;                      // [8..11] float stats
+    double* dpart = (double*)scratch + 32;                  // [blocks][4] float partials, one slot per workgroup (each one written)
     KZ_HIP(hipMemsetAsync(scratch, 0, 128, ctx->stream));
-    const int blocks = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    const int blocks = (int)((n + 255) / 256 < KZ_KOCC_MAX_BLOCKS ? (n + 255) / 256 : KZ_KOCC_MAX_BLOCKS);
     hipLaunchKernelGGL(kz_kocc_int_stats_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const long long*)d_kocc, n, hub_threshold, di);
     KZ_HIP(hipGetLastError());
     unsigned long long hi[8];
     KZ_HIP(hipMemcpyAsync(hi, di, sizeof(hi), hipMemcpyDeviceToHost, ctx->stream));
     KZ_HIP(hipStreamSynchronize(ctx->stream));
     const double mean = (double)hi[0] / (double)n;
-    hipLaunchKernelGGL(kz_kocc_float_stats_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const long long*)d_kocc, n, mean, df);
+    hipLaunchKernelGGL(kz_kocc_float_stats_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const long long*)d_kocc, n, mean, dpart);
+    hipLaunchKernelGGL(kz_kocc_float_fold_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)dpart, blocks, df);
     if (with_gini)
         hipLaunchKernelGGL(kz_gini_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const long long*)d_kocc, n, di + 5);
     KZ_HIP(hipGetLastError());

@@ -136,6 +136,7 @@ def hits(nn_ind: Union[np.ndarray, list, Dict[Any, List], "N.DeviceArray"], gold
         ind_dev = ctx.to_device(ind_host)
     n, cols = ind_dev.shape
     hist = ctx.empty((cols + 1,), np.int64)
-    N._check(ctx.lib.kz_hit_positions(ctx.handle, ind_dev.ptr, ctx.to_device(gold_arr).ptr, n, cols, hist.ptr), "kz_hit_positions")
+    gold_dev = ctx.to_device(gold_arr)   # (held until the call returns: a device array is released with its Python object)
+    N._check(ctx.lib.kz_hit_positions(ctx.handle, ind_dev.ptr, gold_dev.ptr, n, cols, hist.ptr), "kz_hit_positions")
     cum = np.cumsum(hist.numpy()[:cols])
     return {kk: (float(cum[min(kk, cols) - 1]) / len(gold) if kk >= 1 else 0.0) for kk in k}
