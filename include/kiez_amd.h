@@ -49,11 +49,14 @@ enum { KZ_F32 = 0, KZ_F64 = 1 };
  * float64 throughout; correlation = 1 - centred cosine, NaN for a constant row, ranked after every finite value).
  * 10 .. 16 are scipy's boolean metrics (scikit-learn casts the rows to bool, x != 0, and calls cdist): the matrix keeps a
  * bit-packed image of the rows, a popcount kernel counts popcount(x & y) per pair and one float64 division gives scipy's value;
- * dice and sokalsneath are NaN between two all-false rows, ranked after every finite value and returned as NaN. */
+ * dice and sokalsneath are NaN between two all-false rows, ranked after every finite value and returned as NaN.
+ * 17 is scikit-learn's metric="precomputed": the caller's distance matrix IS the value matrix -- no distance arithmetic at all, the
+ * exact float64 selection kernels pick the neighbours.  Such handles come from kz_matrix_create_precomputed only (kz_matrix_create
+ * keeps refusing the id). */
 enum { KZ_EUCLIDEAN = 0, KZ_SQEUCLIDEAN = 1, KZ_COSINE = 2, KZ_MANHATTAN = 3, KZ_CHEBYSHEV = 4, KZ_MINKOWSKI = 5,
        KZ_BRAYCURTIS = 6, KZ_SEUCLIDEAN = 7, KZ_CORRELATION = 8, KZ_HAMMING = 9,
        KZ_JACCARD = 10, KZ_DICE = 11, KZ_ROGERSTANIMOTO = 12, KZ_RUSSELLRAO = 13, KZ_SOKALMICHENER = 14, KZ_SOKALSNEATH = 15,
-       KZ_YULE = 16 };
+       KZ_YULE = 16, KZ_PRECOMPUTED = 17 };
 
 typedef struct kz_ctx kz_ctx;       /* one GPU + one HIP stream + scratch                                   */
 typedef struct kz_matrix kz_matrix; /* an embedding matrix resident in HBM: raw rows, MFMA-packed tiles, norms */
@@ -148,6 +151,30 @@ int kz_matrix_set_minkowski_p(kz_matrix* m, double p);
 int kz_matrix_set_seuclidean_v(kz_matrix* m, const double* V, int64_t d);
 int kz_matrix_destroy(kz_matrix* m);
 int kz_matrix_shape(const kz_matrix* m, int64_t* n, int64_t* d, int* dtype, int* metric);
+
+/* ---- a precomputed distance matrix (scikit-learn's metric="precomputed") -- ABI v7, additive ---------------------------------- */
+/* values: row-major [n_rows, n_cols], dtype KZ_F32 or KZ_F64: values[i, j] = the distance from "source" row i to "target" row j
+ * (a fused similarity of several views turned into a distance, the scores of a matching network, a cdist already in HBM).
+ * values_on_device: 0 host memory (copied into HBM), 1 device memory (copied), 2 device memory BORROWED (read in place; the caller
+ * keeps the buffer alive and unchanged until BOTH handles are destroyed).  Returns two handles over ONE storage: *rows_view has
+ * n = n_rows (its "features" are the n_cols distances of a row), *cols_view has n = n_cols and is the transposed view.  The storage
+ * is shared and reference counted: kz_matrix_destroy takes the handles in either order.  Nothing else is allocated or computed:
+ * no operand image, no norms, no per-row state.  kz_matrix_shape reports (n, the other extent, dtype, KZ_PRECOMPUTED).
+ * Both extents must be >= 1 and below 2^31 - 256 (element offsets are 64-bit: n_rows x n_cols may exceed 2^32).
+ * A precomputed handle pairs ONLY with the other view of the same storage: kz_knn / kz_gold_ranks / kz_gold_ranks_reduced /
+ * kz_knn_reduced / kz_softmin_rows with query = one view and index = the other answer "rows of D against its columns" or the reverse;
+ * the same view on both sides, views of two different matrices, a precomputed handle beside an embedding matrix, and
+ * exclude_self != 0 (the data is two-sided: a caller masks a diagonal themselves) are KZ_ERR_INVALID.  The value of a pair IS its
+ * matrix entry, widened to float64: kz_knn orders by (value, index row) and returns the values as they are (the exact float64
+ * selection kernels, any k <= min(index.n, 4096)); the whole-index calls reduce them as they reduce any distance.
+ * Every value must be finite and >= 0 (-0.0 is fine): NaN or an infinity is KZ_ERR_NONFINITE, a negative value KZ_ERR_INVALID
+ * ("Negative values in data passed to precomputed distance matrix", scikit-learn's words) -- scikit-learn raises ValueError for
+ * both, and the selection kernels assume it.  Host values: the verdict comes from this call; device values: from the first of the
+ * calls above on the pair (this call then waits for nothing).
+ * kz_knn_dual, kz_pair_values, kz_dsl_fit, kz_dsl_transform, kz_matrix_set_minkowski_p and kz_matrix_set_seuclidean_v refuse a
+ * precomputed handle with KZ_ERR_INVALID before anything is launched. */
+int kz_matrix_create_precomputed(kz_ctx* ctx, const void* values, int values_on_device, int64_t n_rows, int64_t n_cols, int dtype,
+                                 kz_matrix** rows_view, kz_matrix** cols_view);
 
 /* ---- exact kNN: replaces SklearnNN._kneighbors (sklearn_nearest_neighbors.py:96-101) -------------------- */
 /* For query rows [q_begin, q_begin+q_count) of `query` find the k nearest rows of `index`, ascending.

@@ -34,6 +34,7 @@ METRIC_IDS = {"euclidean": KZ_EUCLIDEAN, "sqeuclidean": KZ_SQEUCLIDEAN, "cosine"
               "correlation": KZ_CORRELATION, "hamming": KZ_HAMMING, "jaccard": KZ_JACCARD, "dice": KZ_DICE,
               "rogerstanimoto": KZ_ROGERSTANIMOTO, "russellrao": KZ_RUSSELLRAO, "sokalmichener": KZ_SOKALMICHENER,
               "sokalsneath": KZ_SOKALSNEATH, "yule": KZ_YULE}
+KZ_PRECOMPUTED = 17   # scikit-learn's metric="precomputed": not in METRIC_IDS -- kz_matrix_create refuses it, PrecomputedMatrix makes the handles
 
 
 def split_metric(metric: str):
@@ -103,6 +104,7 @@ SYMBOLS = [
     ("kz_memcpy_d2h", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("kz_memcpy_d2d", C.c_int, [_P, _P, _P, C.c_size_t]),
     ("kz_matrix_create", C.c_int, [_P, _P, C.c_int, _I64, _I64, C.c_int, C.c_int, C.POINTER(_P)]),
+    ("kz_matrix_create_precomputed", C.c_int, [_P, _P, C.c_int, _I64, _I64, C.c_int, C.POINTER(_P), C.POINTER(_P)]),
     ("kz_matrix_destroy", C.c_int, [_P]),
     ("kz_matrix_set_minkowski_p", C.c_int, [_P, C.c_double]),
     ("kz_matrix_set_seuclidean_v", C.c_int, [_P, _P, _I64]),
@@ -349,6 +351,41 @@ class DeviceMatrix:
         if V is not None:
             v = np.ascontiguousarray(V, dtype=np.float64)
             _check(ctx.lib.kz_matrix_set_seuclidean_v(h, v.ctypes.data_as(_P), v.shape[0]), "kz_matrix_set_seuclidean_v")
+
+    view = None   # a view of a precomputed distance matrix: "rows" or "columns" (DeviceMatrix.precomputed); None: an embedding matrix
+
+    @classmethod
+    def precomputed(cls, ctx: Context, data, device_ptr: Optional[int] = None, shape=None, dtype=None, borrow: bool = False,
+                    keepalive=None) -> Tuple["DeviceMatrix", "DeviceMatrix"]:
+        """kz_matrix_create_precomputed: the two views (rows, columns) of ONE distance matrix [n_source, n_target], float32 or float64
+        -- `rows` has one row per source row, `columns` one per target row; a search pairs one view as query with the other as
+        index.  `data`: a 2-D numpy array (copied into HBM; NaN, an infinity or a negative value raise ValueError here), or
+        `device_ptr` + `shape` + `dtype` as in the constructor (`borrow=True`: read in place, `keepalive` held until both views are
+        gone; the verdict on the values then comes from the first search).  The storage is shared and reference counted in the
+        library: the views may be dropped in either order."""
+        rows_h, cols_h = _P(), _P()
+        if device_ptr is None:
+            arr = np.ascontiguousarray(data)
+            if arr.ndim != 2:
+                raise ValueError(f"Expected 2D array, got {arr.ndim}D array instead")
+            if arr.dtype not in (np.float32, np.float64):
+                arr = arr.astype(np.float64)
+            shape, dtype = arr.shape, arr.dtype
+            ptr, where = arr.ctypes.data_as(_P), 0
+        else:
+            shape, dtype = tuple(int(s) for s in shape), np.dtype(dtype)
+            if len(shape) != 2 or dtype not in (np.float32, np.float64):
+                raise ValueError("a precomputed device matrix must be a 2D float32/float64 array")
+            ptr, where = _P(device_ptr), 2 if borrow else 1
+        _check(ctx.lib.kz_matrix_create_precomputed(ctx.handle, ptr, where, shape[0], shape[1], KZ_F32 if dtype == np.float32 else KZ_F64,
+                                                    C.byref(rows_h), C.byref(cols_h)), "kz_matrix_create_precomputed")
+        views = []
+        for handle, view, shp in ((rows_h, "rows", (shape[0], shape[1])), (cols_h, "columns", (shape[1], shape[0]))):
+            m = cls.__new__(cls)
+            m.ctx, m.metric, m.shape, m.dtype, m.handle, m.view = ctx, "precomputed", shp, np.dtype(dtype), handle, view
+            m._keepalive = keepalive if (device_ptr is not None and borrow) else None
+            views.append(m)
+        return views[0], views[1]
 
     def __del__(self):
         h = getattr(self, "handle", None)

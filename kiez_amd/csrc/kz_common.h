@@ -183,6 +183,9 @@ struct kz_matrix {
     double* norm64;   // cosine, float32 rows: [n][d] float64 rows x / |x| -- the values the re-rank's per-element divisions produce
                       // (NULL until kz_matrix_norm64: built for finalize launches with many candidates per query, kz_knn_fin_wide.h)
     size_t raw_bytes, packed_bytes, bias_bytes, sqn_bytes;
+    struct kz_precomputed* pre;   // KZ_PRECOMPUTED: the storage the two views share (kz_precomputed.h); NULL for every embedding matrix.  Such a
+                                  // handle owns nothing else: raw points at the shared values (never freed through the handle), no sqn / bias / images
+    bool pre_cols;                // ... this handle is the COLUMNS view (n = n_cols, d = n_rows)
 };
 
 // operand images are built on first use (kz_pack.hip); all enqueue on the context's stream

@@ -839,11 +839,16 @@ struct KzExactLaunch {
 };
 
 // vals [nb][index->n]: the float64 ranking values of rows q_begin + fl[b0 .. b0 + nb) of `query` against every index row.  THE dtype /
-// metric dispatch of the stage, first match: one pair per lane, boolean, Minkowski family, four rows in registers, one pair per
+// metric dispatch of the stage, first match: a precomputed matrix (no arithmetic: kz_precomputed.hip gathers the listed rows or
+// columns), one pair per lane, boolean, Minkowski family, four rows in registers, one pair per
 // wave.  (The float32-only kernels decline float64 rows themselves.)  Launch errors are the caller's hipGetLastError.
 static int kz_exact_distances(kz_ctx* ctx, const int* fl, int b0, int nb, int64_t q_begin, const kz_matrix* query, const kz_matrix* index,
                               double* vals, const KzExactLaunch& ln = KzExactLaunch()) {
     const int metric = index->metric;
+    if (metric == KZ_PRECOMPUTED) {
+        kz_precomputed_launch_values(ctx, fl, b0, nb, q_begin, query, index, vals);
+        return KZ_OK;
+    }
     const bool no_gemm_form = metric >= KZ_MANHATTAN;
     const bool f32 = index->dtype == KZ_F32;
     bool lanes = false;

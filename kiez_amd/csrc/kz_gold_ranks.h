@@ -180,7 +180,8 @@ __global__ __launch_bounds__(256) void kz_rank_count_kernel(const double* __rest
 }
 
 // The constant a launch passes for METRIC: the three metrics kz_output_distance converts stand for themselves, KZ_CORRELATION for
-// those whose +inf ranking value is a NaN distance, KZ_COSINE for every metric whose ranking value IS the distance returned.
+// those whose +inf ranking value is a NaN distance, KZ_COSINE for every metric whose ranking value IS the distance returned
+// (KZ_PRECOMPUTED among them: the matrix entry as it is).
 static int kz_rank_out_metric(int metric) {
     if (metric == KZ_EUCLIDEAN || metric == KZ_SEUCLIDEAN || metric == KZ_MINKOWSKI) return metric;
     return metric == KZ_CORRELATION || metric == KZ_DICE || metric == KZ_SOKALSNEATH ? KZ_CORRELATION : KZ_COSINE;

@@ -8,6 +8,7 @@
 //   DisSimLocal     kiez/hubness_reduction/dis_sim.py:96-107, 139-181
 //   _sort           kiez/hubness_reduction/base.py:72-87
 #include "kz_common.h"
+#include "kz_precomputed.h"
 #include "kz_reduce.h"   // the pointwise formulas, shared with the rank count over the whole index (kz_gold_ranks.h)
 
 // (kz_np_pairwise_sum, numpy's pairwise summation: kz_common.h)
@@ -613,6 +614,8 @@ int kz_mp_empiric(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64
 int kz_dsl_fit(kz_ctx* ctx, const int64_t* d_ind_t2s, int64_t n_rows, int Kt, const kz_matrix* source, const kz_matrix* target,
                int64_t t_begin, double* d_t2c) {
     KZ_REQUIRE(ctx && d_ind_t2s && source && target && d_t2c, "kz_dsl_fit: null argument");
+    KZ_REFUSE_PRECOMPUTED("kz_dsl_fit", source);   // (DisSimLocal gathers embeddings)
+    KZ_REFUSE_PRECOMPUTED("kz_dsl_fit", target);
     KZ_REQUIRE(source->d == target->d && source->dtype == target->dtype, "kz_dsl_fit: source/target mismatch");
     KZ_REQUIRE(n_rows >= 0 && t_begin >= 0 && t_begin + n_rows <= target->n && Kt >= 1, "kz_dsl_fit: bad row range");
     KZ_HIP(hipSetDevice(ctx->device));
@@ -631,6 +634,8 @@ int kz_dsl_transform(kz_ctx* ctx, const int64_t* d_ind, int64_t n, int K, const 
                      const kz_matrix* target, const double* d_t2c, double* d_out, double* d_min) {
     KZ_CHECK_NK("kz_dsl_transform");
     KZ_REQUIRE(d_ind && query && target && d_t2c && d_out && d_min, "kz_dsl_transform: null argument");
+    KZ_REFUSE_PRECOMPUTED("kz_dsl_transform", query);
+    KZ_REFUSE_PRECOMPUTED("kz_dsl_transform", target);
     KZ_REQUIRE(query->d == target->d && query->dtype == target->dtype, "kz_dsl_transform: query/target mismatch");
     KZ_REQUIRE(q_begin >= 0 && q_begin + n <= query->n, "kz_dsl_transform: bad row range");
     if (query->dtype == KZ_F32)

@@ -20,6 +20,7 @@
 
 #include "kz_common.h"
 #include "kz_bool.h"
+#include "kz_precomputed.h"
 #include "kz_floor.h"
 
 #include "kz_knn_device.h"
@@ -676,11 +677,79 @@ static int kz_require_pair(const char* who, const kz_ctx* ctx, const kz_matrix* 
     KZ_REQUIRE(ctx && query && index && out0 && out1, "%s: null argument", who);
     KZ_REQUIRE(query->ctx == ctx && index->ctx == ctx, "%s: matrices belong to a different context", who);
     KZ_REQUIRE(!query->raw_only && !index->raw_only, "%s: a rows-only matrix (kz_matrix_create rows_on_device = 3) cannot be searched", who);
-    KZ_REQUIRE(query->d == index->d, "%s: feature dimensions differ (%lld vs %lld)", who, (long long)query->d, (long long)index->d);
+    {   // (a precomputed distance matrix: the two views of one storage, whose extents differ -- the feature test is not theirs)
+        const int rcv = kz_precomputed_require_pair(who, query, index);
+        if (rcv != KZ_OK) return rcv;
+    }
+    KZ_REQUIRE(query->pre || query->d == index->d, "%s: feature dimensions differ (%lld vs %lld)", who, (long long)query->d, (long long)index->d);
     KZ_REQUIRE(query->dtype == index->dtype, "%s: query and index must have the same dtype", who);
     KZ_REQUIRE(query->metric == index->metric && query->mink_p == index->mink_p, "%s: query and index were packed for different metrics", who);
     KZ_REQUIRE(kz_metric_params_match(query, index), "%s: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index", who);
     KZ_REQUIRE(q_begin >= 0 && q_count >= 0 && q_begin + q_count <= query->n, "%s: query row range out of bounds", who);
+    // (device values of a precomputed matrix: the validation kernel's verdict, read by the first call on the pair -- every entry point
+    //  comes through here, and the kernels behind all of them assume finite values >= 0)
+    if (query->pre) return kz_precomputed_check(query->ctx, query->pre);
+    return KZ_OK;
+}
+
+// KZ_PRECOMPUTED: the exact stage ALONE, entered before kz_knn_impl derives any list geometry or scratch size (a view has no tiles,
+// no k-groups and no operand image to derive them from): the value batch (kz_exact_distances -> kz_precomputed.hip), the one- or
+// two-level selection, kz_emit_sorted -- the values come back as they are (kz_output_distance), ordered by (value, index row).
+// Any k <= min(index.n, KZ_EXACT_MAX_K).  Ends synchronised with the stream.
+static int kz_knn_precomputed(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index, int k, double* d_dist,
+                              int64_t* d_ind, kz_knn_stats* stats) {
+    if (k > KZ_EXACT_MAX_K) {
+        kz_set_error("kz_knn: k=%d exceeds the supported maximum of %d neighbours per query", k, KZ_EXACT_MAX_K);
+        return KZ_ERR_UNSUPPORTED;
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (q_count == 0) return KZ_OK;
+    KZ_HIP(hipSetDevice(ctx->device));
+    KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    // (released when this function ends, stream-ordered: fl, cand_v, cand_i)
+    KzPoolBuf<int> cand_i;
+    KzPoolBuf<double> cand_v;
+    KzPoolBuf<int> fl;   // every row of the range, as the row list the exact stage takes
+    int rc = fl.alloc(ctx, (size_t)q_count * sizeof(int));
+    if (rc != KZ_OK) return rc;
+    hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((q_count + 255) / 256)), dim3(256), 0, ctx->stream, fl.get(), (int)q_count);
+    KZ_HIP(hipGetLastError());
+    int batch = 0;
+    double* vals = nullptr;
+    rc = kz_exact_begin(ctx, index, (int)q_count, &batch, &vals);
+    if (rc != KZ_OK) return rc;
+    // (two levels from TWO chunks on: here EVERY row of the call is selected from its whole value row -- the fallback's default of
+    //  five is sized for a handful of rows, where a second launch costs more than one workgroup's k passes over a short row;
+    //  15 k x 15 k, k = 10: the one-level kernel was 3.6 of the call's 4.3 ms.  Not for long lists: k survivors per chunk of 4 096
+    //  thin nothing out once k is a large share of the chunk)
+    KzExactSelection sel;
+    rc = kz_exact_selection(index, k, k <= KZ_EXACT_CHUNK / 8 ? 2 : KzExactLaunch().two_level_from, &sel);
+    if (rc != KZ_OK) return rc;
+    if (sel.two_level) {
+        rc = cand_v.alloc(ctx, sel.cand_entries(batch) * 8);
+        if (rc == KZ_OK) rc = cand_i.alloc(ctx, sel.cand_entries(batch) * 4);
+        if (rc != KZ_OK) return rc;
+    }
+    for (int b0 = 0; b0 < (int)q_count; b0 += batch) {
+        const int nb = (int)q_count - b0 < batch ? (int)q_count - b0 : batch;
+        rc = kz_exact_distances(ctx, fl.get(), b0, nb, q_begin, query, index, vals);
+        if (rc != KZ_OK) return rc;
+        kz_exact_select(ctx, sel, fl.get(), b0, nb, q_begin, index, k, 0, nullptr, vals, cand_v.get(), cand_i.get(), d_dist, d_ind);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev[4], ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        kz_set_error("kz_knn: exact kernels on a precomputed matrix failed: %s", hipGetErrorString(e));
+        return KZ_ERR_HIP;
+    }
+    if (stats) {
+        float ms = 0;
+        KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
+        stats->fallback_ms = ms;
+        stats->n_fallback_rows = q_count;
+        stats->first_pass = 0;
+    }
     return KZ_OK;
 }
 
@@ -792,6 +861,9 @@ static int kz_escalate_ladder(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, c
 static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index, int k,
                        int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* d_dist,
                        int64_t* d_ind, kz_knn_stats* stats, KzDualPass* dual) {
+    // (before kz_require_pair reads a precomputed matrix' deferred verdict: a refusal waits for nothing)
+    KZ_REQUIRE(!(exclude_self && query && query->pre),
+               "kz_knn: exclude_self has no meaning for a precomputed distance matrix (two-sided data: mask the diagonal in the matrix)");
     {
         const int rcp = kz_require_pair("kz_knn", ctx, query, q_begin, q_count, index, d_dist, d_ind);
         if (rcp != KZ_OK) return rcp;
@@ -800,6 +872,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     const int k_eff = k + (exclude_self ? 1 : 0);
     KZ_REQUIRE((int64_t)k_eff <= index->n, "kz_knn: Expected n_neighbors %s n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld",
                exclude_self ? "<" : "<=", k, (long long)index->n);
+    if (index->metric == KZ_PRECOMPUTED) return kz_knn_precomputed(ctx, query, q_begin, q_count, index, k, d_dist, d_ind, stats);
     if (exclude_self && !d_self_ids)
         KZ_REQUIRE(query->n == index->n, "kz_knn: exclude_self needs query and index of equal length");
     // More than 110 neighbours per query: no fused kernel keeps a list that long -- but the kernels keep ONE list per query and

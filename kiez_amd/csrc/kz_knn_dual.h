@@ -673,6 +673,8 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
     kz_matrix* a = const_cast<kz_matrix*>(a_c);
     kz_matrix* b = const_cast<kz_matrix*>(b_c);
     KZ_REQUIRE(ctx && a && b && d_dist_ab && d_ind_ab && d_dist_ba && d_ind_ba, "kz_knn_dual: null argument");
+    KZ_REFUSE_PRECOMPUTED("kz_knn_dual", a);   // (no shared sweep without embeddings: two kz_knn calls, one per view)
+    KZ_REFUSE_PRECOMPUTED("kz_knn_dual", b);
     KZ_REQUIRE(a != b, "kz_knn_dual: the two matrices must be different objects (a single matrix is searched with kz_knn)");
     KZ_REQUIRE(a->ctx == ctx && b->ctx == ctx, "kz_knn_dual: matrices belong to a different context");
     KZ_REQUIRE(!a->raw_only && !b->raw_only, "kz_knn_dual: a rows-only matrix (kz_matrix_create rows_on_device = 3) cannot be searched");

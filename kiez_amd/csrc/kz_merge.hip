@@ -9,6 +9,7 @@
 // MutualProximity 'empiric' (mutual_proximity.py:185-212) and DisSimLocal (dis_sim.py:96-107) need the reverse INDICES in
 // exactly the single-GPU order; CSLS / LocalScaling / MP 'normal' only the distances (merged by the distances themselves).
 #include "kz_common.h"
+#include "kz_precomputed.h"
 #include "kz_bool.h"
 
 // one wave per query row; the row's K pairs one after the other through the canonical dot product
@@ -105,6 +106,8 @@ int kz_pair_values(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t
                    const int64_t* d_ind, int k, double* d_val) {
     KZ_REQUIRE(ctx && query && index && d_ind && d_val, "kz_pair_values: null argument");
     KZ_REQUIRE(query && index && !query->raw_only && !index->raw_only, "kz_pair_values: null or rows-only matrix");
+    KZ_REFUSE_PRECOMPUTED("kz_pair_values", query);   // (the value of a pair is the caller's own matrix entry)
+    KZ_REFUSE_PRECOMPUTED("kz_pair_values", index);
     KZ_REQUIRE(query->d == index->d && query->dtype == index->dtype && query->metric == index->metric && query->mink_p == index->mink_p,
                "kz_pair_values: query/index mismatch (d %lld vs %lld)", (long long)query->d, (long long)index->d);
     KZ_REQUIRE(kz_metric_params_match(query, index), "kz_pair_values: seuclidean needs the same V (kz_matrix_set_seuclidean_v) on query and index");

@@ -20,6 +20,7 @@
 
 #include "kz_common.h"
 #include "kz_bool.h"
+#include "kz_precomputed.h"
 
 // round-to-nearest-even float32 -> bf16 bits (finite inputs)
 __device__ __forceinline__ unsigned short kz_bf16_rn(float f) {
@@ -805,6 +806,7 @@ int kz_matrix_destroy(kz_matrix* m) {
     if (!m) return KZ_OK;
     if (m->ctx) {
         (void)hipSetDevice(m->ctx->device);
+        kz_precomputed_release(m);   // (a view of a precomputed matrix: its reference to the shared storage; the handle owns nothing else)
         kz_himage_free(m);
         if (!m->raw_borrowed) kz_pool_free(m->ctx, m->raw, 0);
         kz_pool_free(m->ctx, m->packed, 0);
@@ -824,6 +826,7 @@ int kz_matrix_destroy(kz_matrix* m) {
 
 int kz_matrix_set_minkowski_p(kz_matrix* m, double p) {
     KZ_REQUIRE(m != nullptr, "kz_matrix_set_minkowski_p: null matrix");
+    KZ_REFUSE_PRECOMPUTED("kz_matrix_set_minkowski_p", m);
     KZ_REQUIRE(m->metric == KZ_MINKOWSKI, "kz_matrix_set_minkowski_p: the matrix was not created for KZ_MINKOWSKI");
     KZ_REQUIRE(p >= 1.0 && p < 1e6, "kz_matrix_set_minkowski_p: p must be >= 1 (got %g)", p);
     m->mink_p = p;
@@ -832,6 +835,7 @@ int kz_matrix_set_minkowski_p(kz_matrix* m, double p) {
 
 int kz_matrix_set_seuclidean_v(kz_matrix* m, const double* V, int64_t d) {
     KZ_REQUIRE(m != nullptr && V != nullptr, "kz_matrix_set_seuclidean_v: null argument");
+    KZ_REFUSE_PRECOMPUTED("kz_matrix_set_seuclidean_v", m);
     KZ_REQUIRE(m->metric == KZ_SEUCLIDEAN, "kz_matrix_set_seuclidean_v: the matrix was not created for KZ_SEUCLIDEAN");
     KZ_REQUIRE(d == m->d, "kz_matrix_set_seuclidean_v: V has %lld entries, the matrix %lld features", (long long)d, (long long)m->d);
     for (int64_t j = 0; j < d; ++j)

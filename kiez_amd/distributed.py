@@ -571,6 +571,9 @@ class ShardedKiez:
         akw = dict(algorithm_kwargs or {})
         self.K = int(akw.get("n_candidates", n_candidates))
         self.metric = canonical_metric(akw.get("metric", "minkowski"), akw.get("p", 2))
+        if self.metric == "precomputed":
+            # (a distance matrix is one array in one GPU's HBM: there are no rows to shard and nothing to search per shard)
+            raise ValueError("metric='precomputed' runs on one GPU: ShardedKiez shards embedding rows (use Kiez(...).fit(D))")
         self.V = seuclidean_V(self.metric, akw.get("metric_params"))   # (seuclidean: every rank's matrices carry the same V)
         key = hubness.lower() if isinstance(hubness, str) else hubness
         if key not in _HUB:

@@ -25,6 +25,11 @@ def _is_dev(x):
     return isinstance(x, N.DeviceArray)
 
 
+def _is_precomputed(nn_algo) -> bool:
+    """The MI355X backend fitted on a distance matrix (metric='precomputed'): `fit(D)` alone is a two-sided fit."""
+    return isinstance(nn_algo, SklearnNN) and nn_algo._metric_c == "precomputed"
+
+
 class HubnessReduction(ABC):
     """Base class for hubness reduction (kiez/hubness_reduction/base.py:17-105)."""
 
@@ -76,7 +81,9 @@ class HubnessReduction(ABC):
         """base.py:33-50: index both sides, run the reverse (target -> source) kNN, hand it to `_fit`."""
         self.nn_algo.fit(source, target)
         if target is None:
-            target = source
+            # (a precomputed distance matrix is two-sided by itself: its target side is the backend's `target_`, a distinct object
+            #  that the backend resolves to the matrix' COLUMNS view -- `source` again would resolve to the rows view)
+            target = self.nn_algo.target_ if _is_precomputed(self.nn_algo) else source
         if self._gpu_nn:
             # one sweep of the distance matrix serves this reverse search AND the forward search of kneighbors()
             # (kz_knn_dual); where that does not apply, the reverse search alone
@@ -464,7 +471,7 @@ class _DualPotentials(HubnessReduction):
         """(f [n_s], g [n_t]) as float64 DeviceArrays from the two fitted device matrices; sets n_iter_ / potential_change_."""
 
     def fit(self, source, target=None):
-        if target is None:
+        if target is None and not _is_precomputed(self.nn_algo):   # (a precomputed distance matrix IS two-sided)
             raise ValueError(f"{type(self).__name__} normalises between two sides: two-sided data only (fit(source, target))")
         if not self._gpu_nn:
             raise NotImplementedError(f"{type(self).__name__} needs the MI355X SklearnNN backend (the soft-min runs over the whole index)")

@@ -160,7 +160,8 @@ def canonical_metric(metric: str, p=2) -> str:
     fused MFMA kernels; manhattan, chebyshev and minkowski(p) have no inner-product form and run on a register-tiled VALU kernel + the exact selection,
     as do braycurtis, seuclidean, correlation and hamming (scikit-learn's brute-force expressions, bit for bit).  The seven boolean
     metrics (jaccard, dice, rogerstanimoto, russellrao, sokalmichener, sokalsneath, yule: scipy's cdist on x != 0) run a popcount
-    kernel on bit-packed rows + the exact selection."""
+    kernel on bit-packed rows + the exact selection.  'precomputed' (scikit-learn's spelling) takes a distance matrix in place of
+    embeddings: no distance arithmetic at all, the exact selection on the matrix' own values."""
     if metric == "minkowski":
         if not isinstance(p, (int, float, np.integer, np.floating)) or isinstance(p, bool) or not p >= 1:
             raise ValueError(f"metric='minkowski' needs p >= 1 on the MI355X exact backend (got p={p!r})")
@@ -177,10 +178,20 @@ def canonical_metric(metric: str, p=2) -> str:
         return "euclidean"
     if metric in ("manhattan", "cityblock", "l1"):
         return "manhattan"
-    if metric in ("sqeuclidean", "cosine", "chebyshev", "braycurtis", "seuclidean", "correlation", "hamming") or metric in N.BOOLEAN_METRICS:
+    if metric in ("sqeuclidean", "cosine", "chebyshev", "braycurtis", "seuclidean", "correlation", "hamming", "precomputed") or metric in N.BOOLEAN_METRICS:
         return metric
     raise ValueError(
         f"metric='{metric}' is not implemented by the MI355X exact backend; valid metrics: {SklearnNN.valid_metrics}")
+
+
+class _ColumnsSide:
+    """The target side of a fitted precomputed DeviceArray D [n_source, n_target]: `target_` of the backend, a distinct object so that
+    `query=target_` resolves to the matrix' columns view (numpy arrays and tensors use their own transposed view, `D.T`)."""
+
+    def __init__(self, matrix):
+        self.matrix = matrix
+        self.shape = (matrix.shape[1], matrix.shape[0])
+        self.dtype = matrix.dtype
 
 
 def seuclidean_V(metric_c: str, metric_params):
@@ -213,8 +224,8 @@ class SklearnNN(NNAlgorithm):
     """
 
     valid_metrics = ["braycurtis", "chebyshev", "cityblock", "correlation", "cosine", "dice", "euclidean", "hamming", "jaccard", "l1",
-                     "l2", "manhattan", "minkowski", "rogerstanimoto", "russellrao", "seuclidean", "sokalmichener", "sokalsneath",
-                     "sqeuclidean", "yule"]
+                     "l2", "manhattan", "minkowski", "precomputed", "rogerstanimoto", "russellrao", "seuclidean", "sokalmichener",
+                     "sokalsneath", "sqeuclidean", "yule"]
     # numpy arrays as in the reference; additionally arrays already resident in HBM (zero-copy fit)
     _ALLOWED_INPUT_TYPES = (np.ndarray, N.DeviceArray)
 
@@ -314,7 +325,56 @@ class SklearnNN(NNAlgorithm):
         self.last_stats_reverse = None
         return self._make_matrix(data)
 
+    def _make_precomputed(self, data):
+        """The two views (rows, columns) of a distance matrix [n_source, n_target]: numpy arrays are copied into HBM, DeviceArrays and
+        CUDA tensors are read in place (a non-contiguous tensor through a contiguous copy).  float32 / float64 pass through, any other
+        dtype is cast to float64, as `_prepare` does for embeddings."""
+        if _is_tensor(data):
+            torch = _torch_if_loaded()
+            t = data.detach()
+            if t.dim() != 2:
+                raise ValueError(f"Expected 2D array, got {t.dim()}D array instead")
+            if t.dtype not in (torch.float32, torch.float64):
+                t = t.to(torch.float64)
+            if not t.is_cuda:
+                return self._make_precomputed(t.contiguous().numpy())
+            t = t.contiguous()
+            if t.device.index != self.ctx.device:
+                raise ValueError(f"tensor lives on cuda:{t.device.index}, the NN backend on device {self.ctx.device}")
+            torch.cuda.current_stream(t.device).synchronize()   # the producer stream is not ours
+            return N.DeviceMatrix.precomputed(self.ctx, None, device_ptr=t.data_ptr(), shape=tuple(t.shape),
+                                              dtype=np.float32 if t.dtype == torch.float32 else np.float64, borrow=True, keepalive=t)
+        if isinstance(data, N.DeviceArray):
+            if len(data.shape) != 2 or data.dtype not in (np.float32, np.float64):
+                raise ValueError("device inputs must be 2D float32/float64 arrays")
+            return N.DeviceMatrix.precomputed(self.ctx, None, device_ptr=data.ptr.value, shape=data.shape, dtype=data.dtype,
+                                              borrow=True, keepalive=data)
+        return N.DeviceMatrix.precomputed(self.ctx, self._prepare(data))
+
+    def _fit_precomputed(self, matrix, target):
+        """metric='precomputed': ONE matrix D [n_source, n_target], D[i, j] = the distance from source row i to target row j.
+        `source_index` / `target_index` are its rows view and its columns view; `target_` is a distinct object (the transposed view,
+        never materialised) so that a search with `query=target_` resolves to the columns view, not to `source_index`."""
+        if target is not None:
+            raise ValueError("metric='precomputed' takes ONE distance matrix [n_source, n_target]: fit(D), not fit(source, target)")
+        self._check_input_types((matrix,))
+        for stale in ("source_index", "target_index"):
+            if hasattr(self, stale):
+                delattr(self, stale)
+        self._aux = None
+        self._forward = None
+        self.last_stats_reverse = None
+        self.source_index, self.target_index = self._make_precomputed(matrix)
+        self.source_equals_target = False
+        if isinstance(matrix, N.DeviceArray):
+            columns = _ColumnsSide(matrix)
+        else:
+            columns = matrix.t() if _is_tensor(matrix) else np.asarray(matrix).T
+        self.source_, self.target_ = matrix, columns
+
     def fit(self, source, target=None, only_fit_target: bool = False):
+        if self._metric_c == "precomputed":
+            return self._fit_precomputed(source, target)
         self._check_input_types((source, target))
         if (isinstance(source, np.ndarray) and isinstance(target, np.ndarray) and source.ndim == 2 and target.ndim == 2
                 and source.shape[1] == target.shape[1] and source.dtype != target.dtype):
@@ -332,6 +392,10 @@ class SklearnNN(NNAlgorithm):
             return self.source_index
         if hasattr(self, "target_index") and array is self.target_:
             return self.target_index
+        if self._metric_c == "precomputed":
+            # (a distance matrix answers for its own rows and columns only: there are no embeddings to measure a new row against)
+            raise NotImplementedError("metric='precomputed': `query` must be a fitted side (the fitted matrix: its rows; `target_`: its "
+                                      "columns) -- distances from new rows are not in the matrix; fit the extended matrix instead")
         if self._aux is not None and self._aux[0] is array:
             return self._aux[1]
         self._check_input_types(array)
@@ -341,8 +405,8 @@ class SklearnNN(NNAlgorithm):
         return m
 
     def _out_dtype(self, index: N.DeviceMatrix):
-        # sklearn: euclidean family -> float64 always (ArgKmin); cosine -> dtype of the input
-        return np.float32 if (self._metric_c == "cosine" and index.dtype == np.float32) else np.float64
+        # sklearn: euclidean family -> float64 always (ArgKmin); cosine -> dtype of the input; precomputed -> dtype of the matrix
+        return np.float32 if (self._metric_c in ("cosine", "precomputed") and index.dtype == np.float32) else np.float64
 
     def kneighbors_device(self, k=None, query=None, s_to_t=True, q_begin=0, q_count=None):
         """`kneighbors` that leaves (dist float64, ind int64) in HBM; used by the GPU hubness reductions."""
@@ -410,6 +474,8 @@ class SklearnNN(NNAlgorithm):
         searches.  None when sharing does not apply (sides clamped to different k, more neighbours than the fused kernels keep)."""
         check_is_fitted(self, ["source_index", "target_index"], all_or_any=all)
         k = self.n_candidates if k is None else k
+        if self._metric_c == "precomputed":
+            return None   # (no sweep to share: both directions read the caller's matrix -- two searches)
         if self.source_equals_target:
             # single source: the reverse search (explicit query: every row keeps itself) and the forward search (the row
             # itself stripped) are two views of ONE search for k + 1 neighbours (kz_split_self)
