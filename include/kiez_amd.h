@@ -423,6 +423,30 @@ int kz_match_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_
  * device).  Enqueued on the context's stream; n_q and k as above. */
 int kz_match_values(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q, int k, void* d_out);
 
+/* ---- one-to-one alignment: minimum-cost assignment over neighbour lists (kz_assign.hip) -- additive, ABI v7 ------------------ */
+/* The lists of kz_match_lists.  Entry (i, c) is a PAIR when 0 <= d_ind[i, c] < n_index, w = d_dist[i, c] widened to double is finite
+ * and w <= unmatched_cost; any other entry (padding, -1, NaN, +-inf) is no pair.  A matching uses every source and every target row
+ * at most once; its cost is the sum of w over the matched pairs plus unmatched_cost per unmatched source row.  Writes a matching
+ * with cost <= optimum + n_q eps, found by the forward auction in Jacobi form: prices start at 0.0 and all rows FREE; in a round
+ * every FREE row computes v_c = (-w_c) - price[t_c] over its pair columns, best = the first column with the largest v (v1), v2 = the
+ * largest v of its other pair columns taken together with -unmatched_cost; not v1 > -unmatched_cost: the row is unmatched for good;
+ * otherwise it bids (price[t] + (v1 - v2)) + eps on its best target.  A target takes the largest bid, among equal bids the smallest
+ * row; the bid becomes the price, the winner the owner, the previous owner FREE.  The rule is synchronous per round and float64
+ * add / subtract / compare only: the same arrays from every run, whatever the split into launches.
+ * d_match[i] = the target row of source row i or -1, d_col[i] = the column of that pair or -1 (rows still FREE at max_rounds: -1);
+ * d_price (device, [n_index], may be NULL) = the final prices; *h_rounds (host, may be NULL) = the rounds that began with a FREE
+ * row; *h_converged (host, may be NULL) = 1 when no row is FREE, 0 when max_rounds ended the run -- still KZ_OK and a valid matching.
+ * tail_rows: rounds with at most that many FREE rows run inside one single-workgroup launch (0: the default 1024; 1 .. 1024;
+ * negative: never), the others as three grid-wide launches each; the result does not depend on it.
+ * Limits as kz_match_lists; unmatched_cost finite, eps > 0 finite, max_rounds >= 0: KZ_ERR_INVALID otherwise.  Synchronises. */
+int kz_assign_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index,
+                    double unmatched_cost, double eps, int64_t max_rounds, int tail_rows, int64_t* d_match, int64_t* d_col,
+                    double* d_price, int64_t* h_rounds, int* h_converged);
+/* The smallest and the largest value, widened to double, over the entries with 0 <= d_ind < n_index and a finite value (what the
+ * defaults of unmatched_cost and eps are made of): *h_min, *h_max (host); *h_any = 0 and both 0.0 when there is no such entry. */
+int kz_assign_range(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index,
+                    double* h_min, double* h_max, int* h_any);
+
 /* float64 -> float32 cast of an [count] array (cosine + float32 inputs keep the reference's output dtype). */
 int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count);
 

@@ -143,6 +143,10 @@ SYMBOLS = [
     ("kz_rank_stats", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.c_int, C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("kz_match_lists", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, _P, _P, C.POINTER(_I64)]),
     ("kz_match_values", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _P]),
+    ("kz_assign_lists", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, C.c_double, C.c_double, _I64, C.c_int, _P, _P, _P,
+                                  C.POINTER(_I64), C.POINTER(C.c_int)]),
+    ("kz_assign_range", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_int)]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_comm_destroy", C.c_int, [_P]),
@@ -584,6 +588,33 @@ def match_values(ctx: Context, dist: DeviceArray, col: DeviceArray) -> DeviceArr
     _check(ctx.lib.kz_match_values(ctx.handle, dist.ptr, KZ_F32 if dist.dtype == np.float32 else KZ_F64, col.ptr, n_q, k, out.ptr),
            "kz_match_values")
     return out
+
+
+def assign_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, unmatched_cost: float, eps: float, max_rounds: int,
+                 tail_rows: int = 0, want_prices: bool = False):
+    """kz_assign_lists -> (match int64 [n_q], col int64 [n_q], prices float64 [n_index] | None, rounds, converged): the forward
+    auction over the neighbour lists dist / ind [n_q, k] against n_index target rows -- a one-to-one matching whose cost (the
+    values of the matched pairs plus unmatched_cost per unmatched row) is within n_q * eps of the minimum.  match / col as
+    `match_lists` returns them.  tail_rows: 0 the default switch to the single-workgroup kernel, 1 .. 1024 that many FREE rows,
+    negative never; the arrays do not depend on it.  converged False: max_rounds ended the run, the matching is valid but not
+    optimal."""
+    n_q, k, dtype = _list_pair(dist, ind)
+    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
+    prices = ctx.empty((int(n_index),), np.float64) if want_prices and 1 <= int(n_index) < 2 ** 31 - 1 else None
+    rounds, converged = _I64(0), C.c_int(0)
+    _check(ctx.lib.kz_assign_lists(ctx.handle, dist.ptr, dtype, ind.ptr, n_q, k, int(n_index), float(unmatched_cost), float(eps),
+                                   int(max_rounds), int(tail_rows), match.ptr, col.ptr, prices.ptr if prices is not None else None,
+                                   C.byref(rounds), C.byref(converged)), "kz_assign_lists")
+    return match, col, prices, int(rounds.value), bool(converged.value)
+
+
+def assign_range(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int):
+    """kz_assign_range -> (smallest, largest) finite value listed with 0 <= ind < n_index, as float64; None when there is none."""
+    n_q, k, dtype = _list_pair(dist, ind)
+    lo, hi, some = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    _check(ctx.lib.kz_assign_range(ctx.handle, dist.ptr, dtype, ind.ptr, n_q, k, int(n_index), C.byref(lo), C.byref(hi), C.byref(some)),
+           "kz_assign_range")
+    return (float(lo.value), float(hi.value)) if some.value else None
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):

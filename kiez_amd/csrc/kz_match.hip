@@ -193,7 +193,8 @@ static int kz_match_lists_impl(kz_ctx* ctx, const T* d_dist, const int64_t* d_in
     return KZ_OK;
 }
 
-static int kz_match_require(const char* who, kz_ctx* ctx, const void* d_dist, int dist_dtype, int64_t n_q, int k) {
+// (shared with kz_assign.hip)
+int kz_match_require(const char* who, kz_ctx* ctx, const void* d_dist, int dist_dtype, int64_t n_q, int k) {
     KZ_REQUIRE(ctx != nullptr, "%s: null context", who);
     KZ_REQUIRE(dist_dtype == KZ_F32 || dist_dtype == KZ_F64, "%s: dist_dtype must be KZ_F32 or KZ_F64, got %d", who, dist_dtype);
     KZ_REQUIRE(k >= 1 && k <= KZ_MAX_CANDIDATES, "%s: lists of 1 .. %d columns, got k = %d", who, KZ_MAX_CANDIDATES, k);

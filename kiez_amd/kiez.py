@@ -115,15 +115,20 @@ class Kiez:
         dist, ind = self.hubness.kneighbors_whole_index(k)
         return (dist, ind) if return_distance else ind
 
-    def match_device(self, k: Optional[int] = None, whole_index: bool = False):
-        """Like `match` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+    def _lists_for_matching(self, k, whole_index):
+        """The device lists a one-to-one step runs on -> (dist, ind, n_target)."""
         nn = self.algorithm
         cached = getattr(nn, "_forward", None)
         dist, ind = self.kneighbors_whole_index_device(k) if whole_index else self.kneighbors_device(k)
         if cached is not None and nn._forward is None:
             nn._forward = cached   # (the shared sweep's forward lists stay cached for the kneighbors() that follows, as after gold_ranks)
+        return dist, ind, nn.target_.shape[0]
+
+    def match_device(self, k: Optional[int] = None, whole_index: bool = False):
+        """Like `match` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+        dist, ind, n_target = self._lists_for_matching(k, whole_index)
         ctx = dist.ctx
-        match, col, _ = N.match_lists(ctx, dist, ind, nn.target_.shape[0])
+        match, col, _ = N.match_lists(ctx, dist, ind, n_target)
         return N.match_values(ctx, dist, col), match
 
     def match(self, k: Optional[int] = None, whole_index: bool = False, return_distance: bool = True):
@@ -138,6 +143,25 @@ class Kiez:
         arrays also after a fit on tensors: tensor output is out of scope.  `evaluate.hits(match_ind[:, None], gold, k=[1])` is the
         precision of the matching."""
         match_dist, match_ind = self.match_device(k, whole_index)
+        return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
+
+    def assign_device(self, k: Optional[int] = None, whole_index: bool = False, unmatched_cost: Optional[float] = None,
+                      eps: Optional[float] = None):
+        """Like `assign` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+        from . import matching
+        unmatched_cost, eps, _ = matching._assignment_options(unmatched_cost, eps, 1)
+        dist, ind, n_target = self._lists_for_matching(k, whole_index)
+        return matching.assignment(dist, ind, n_target, unmatched_cost=unmatched_cost, eps=eps)
+
+    def assign(self, k: Optional[int] = None, whole_index: bool = False, return_distance: bool = True,
+               unmatched_cost: Optional[float] = None, eps: Optional[float] = None):
+        """One-to-one alignment of the fitted source and target rows by the minimum-cost assignment (`matching.assignment`) over
+        the lists `match` runs on: the total value of the matched pairs plus `unmatched_cost` per unmatched source row is within
+        `n_q * eps` of the smallest any one-to-one matching over these lists reaches, where `match` takes pairs greedily.
+        `unmatched_cost` (default: the largest listed value) is also the threshold above which a pair is never taken; `eps`
+        defaults to a thousandth of the lists' value spread divided by the number of source rows.  The lists never leave HBM; the
+        auction runs on the device (kz_assign_lists).  Returns what `match` returns."""
+        match_dist, match_ind = self.assign_device(k, whole_index, unmatched_cost, eps)
         return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
 
     def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):

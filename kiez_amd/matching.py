@@ -1,8 +1,10 @@
-"""One-to-one alignment: the source-proposing stable matching over neighbour lists, on the device (`kz_match_lists`).
+"""One-to-one alignment over neighbour lists, on the device: the source-proposing stable matching (`kz_match_lists`) and the
+minimum-cost assignment (`kz_assign_lists`).
 
 Every neighbour list lets many source rows claim one target row.  Entity alignment is a matching task -- a target entity belongs
 to at most one source entity -- and the CSLS-style pipelines end with a one-to-one step.  `one_to_one` is that step for any lists
-this library (or anything else) produced; `Kiez.match` runs it on the lists of a fitted instance without taking them out of HBM."""
+this library (or anything else) produced, `assignment` the same step with the total value of the pairs minimised instead of pairs
+taken greedily; `Kiez.match` runs either on the lists of a fitted instance without taking them out of HBM."""
 from __future__ import annotations
 
 from typing import Optional
@@ -64,3 +66,86 @@ def one_to_one(dist, ind, n_target: int, *, return_distance: bool = True, ctx: O
         return match if on_device else match.numpy()
     match_dist = N.match_values(ctx, dist_dev, col)
     return (match_dist, match) if on_device else (match_dist.numpy(), match.numpy())
+
+
+def _assignment_options(unmatched_cost, eps, max_rounds):
+    """The checks of `assignment`'s options that need no data -> (unmatched_cost | None, eps | None, max_rounds)."""
+    def real(name, x):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a real number, got {x!r}")
+        return float(x)
+    if unmatched_cost is not None:
+        unmatched_cost = real("unmatched_cost", unmatched_cost)
+        if not np.isfinite(unmatched_cost):
+            raise ValueError(f"unmatched_cost must be finite, got {unmatched_cost!r}")
+    if eps is not None:
+        eps = real("eps", eps)
+        if not (np.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"eps must be positive and finite, got {eps!r}")
+    if isinstance(max_rounds, (bool, np.bool_)) or not isinstance(max_rounds, (int, np.integer)) or max_rounds < 1:
+        raise ValueError(f"max_rounds must be a positive integer, got {max_rounds!r}")
+    return unmatched_cost, eps, int(max_rounds)
+
+
+def _host_value_range(dist, ind, n_target):
+    """What kz_assign_range returns, for lists on the host: (smallest, largest) finite value listed with 0 <= ind < n_target, as
+    float64, or None."""
+    w = dist.astype(np.float64)[(ind >= 0) & (ind < n_target)]
+    w = w[np.isfinite(w)]
+    return (float(w.min()), float(w.max())) if w.size else None
+
+
+def _assignment_defaults(value_range, n_q, unmatched_cost, eps):
+    """`unmatched_cost` and `eps` with their defaults filled in from the range of the listed values; the lower bound of eps."""
+    lo, hi = value_range if value_range is not None else (0.0, 0.0)
+    scale = hi - lo if hi > lo and np.isfinite(hi - lo) else 1.0
+    if unmatched_cost is None:
+        unmatched_cost = hi
+    if eps is None:
+        eps = scale / (1000.0 * max(n_q, 1))
+    if eps < scale * 2.0 ** -40:
+        raise ValueError(f"eps = {eps!r} is below 2**-40 of the lists' value spread {scale!r}: a bid may fail to raise a price")
+    return unmatched_cost, eps
+
+
+def _assign(ctx, dist_dev, ind_dev, n_target, unmatched_cost, eps, max_rounds, want_prices):
+    match, col, prices, rounds, converged = N.assign_lists(ctx, dist_dev, ind_dev, n_target, unmatched_cost, eps, max_rounds,
+                                                           want_prices=want_prices)
+    if not converged:
+        raise RuntimeError(f"assignment: rows are still free after {rounds} rounds (max_rounds) with eps = {eps!r} and "
+                           f"unmatched_cost = {unmatched_cost!r}; a larger eps or a smaller unmatched_cost shortens the run")
+    return match, col, prices
+
+
+def assignment(dist, ind, n_target: int, *, unmatched_cost: Optional[float] = None, eps: Optional[float] = None,
+               max_rounds: int = 1_000_000, return_distance: bool = True, return_prices: bool = False, ctx: Optional[N.Context] = None):
+    """The minimum-cost one-to-one assignment of source rows to target rows from neighbour lists, on the device (`kz_assign_lists`):
+    the hard form of what `Sinkhorn` computes softly, where `one_to_one` takes pairs greedily.
+
+    `dist`, `ind`, `n_target` as `one_to_one` takes them.  An entry is a pair when `ind` is in [0, n_target), the value widened
+    to float64 is finite, and it is at most `unmatched_cost`.  A matching uses each source and each target row at most once; its
+    cost is the sum of the matched pairs' values plus `unmatched_cost` for every unmatched source row, so a row is matched only
+    where that is strictly better than staying out.  `unmatched_cost` defaults to the largest finite listed value.  The result
+    costs at most `n_q * eps` more than the optimum; `eps` defaults to a thousandth of the lists' value spread divided by n_q,
+    and for integer values `eps < 1 / (n_q + 1)` gives the exact optimum.  Values may be negative; all arithmetic is float64.
+    The solver is a forward auction with synchronous rounds: every run returns the same arrays.
+
+    Returns `(match_dist, match_ind)`, or `match_ind` alone with `return_distance=False`, as `one_to_one` does, with the float64
+    target prices [n_target] appended when `return_prices=True`.  More than `max_rounds` rounds raise RuntimeError."""
+    dist, ind = _checked_lists(dist, ind, n_target)
+    unmatched_cost, eps, max_rounds = _assignment_options(unmatched_cost, eps, max_rounds)
+    on_device = isinstance(dist, N.DeviceArray)
+    if not on_device and not isinstance(ind, N.DeviceArray):   # (host lists: the eps check comes before the device is touched)
+        unmatched_cost, eps = _assignment_defaults(_host_value_range(dist, ind, n_target), dist.shape[0], unmatched_cost, eps)
+    if ctx is None:
+        ctx = dist.ctx if on_device else ind.ctx if isinstance(ind, N.DeviceArray) else N.Context.get()
+    dist_dev, ind_dev = ctx.as_device(dist), ctx.as_device(ind)
+    if on_device or isinstance(ind, N.DeviceArray):
+        unmatched_cost, eps = _assignment_defaults(N.assign_range(ctx, dist_dev, ind_dev, int(n_target)), dist.shape[0], unmatched_cost, eps)
+    match, col, prices = _assign(ctx, dist_dev, ind_dev, int(n_target), unmatched_cost, eps, max_rounds, return_prices)
+    out = (N.match_values(ctx, dist_dev, col), match) if return_distance else (match,)
+    if return_prices:
+        out = out + (prices,)
+    if not on_device:
+        out = tuple(x.numpy() for x in out)
+    return out if len(out) > 1 else out[0]
