@@ -455,6 +455,37 @@ int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count
  * 1: numerators and divisors with all-ones / single-bit significands mixed in); *h_mismatch = pairs whose bits differ. */
 int kz_selftest_div(kz_ctx* ctx, int64_t count, uint64_t seed, int mode, int64_t* h_mismatch);
 
+/* Self-test hook (tests/test_gpu_images.py): the raw device bytes of one of the per-matrix buffers every MFMA search starts from
+ * -- norms, bias, maxima, the float32 / split-bf16 / fp16 operand images, the fp16 centre and row statistics -- built (where it
+ * is lazy) by the functions kz_knn calls, copied to h_dst as they lie in HBM: no un-layouting, no arithmetic.  *h_bytes = the
+ * buffer's size; capacity 0 asks for the size only, a smaller capacity than the size is KZ_ERR_INVALID.  `partner` (may be NULL):
+ * the matrix the fp16 image shares its centre with (the index of a search whose query is m).  `arg`: the number of index ranges
+ * (KZ_IMG_DEALT_*) or of rows in the host list h_rows (KZ_IMG_ROWS_*: packed into the next multiple of 128 image rows).
+ * KZ_ERR_NONFINITE for a matrix whose rows were flagged; KZ_ERR_INVALID for rows-only, precomputed and boolean matrices and, for
+ * the fp16 buffers, widths without an fp16 tier.  Synchronises. */
+enum {
+    KZ_IMG_SQN = 0,      /* double [n] */
+    KZ_IMG_BIAS,         /* float [n_pad] */
+    KZ_IMG_STATS,        /* 40 bytes: double max norm, double max |operand|, 16 bytes unused, int non-finite flag, int unused */
+    KZ_IMG_F32,          /* float [n_tiles][d_pad / 4][128][4] */
+    KZ_IMG_BF,           /* uint16 [n_tiles][d_pad / 16][hi0, hi1, lo0, lo1][128][8] */
+    KZ_IMG_NORM64,       /* double [n][d], 0 bytes when the matrix gets none */
+    KZ_IMG_CORR,         /* double [n][2], 0 bytes unless the metric is KZ_CORRELATION */
+    KZ_IMG_MU,           /* float [16 nsr] */
+    KZ_IMG_SCALE,        /* double {S, 1 / S^2} */
+    KZ_IMG_H,            /* fp16 [n_tiles][nsr][2][128][8] (without the padding behind the image) */
+    KZ_IMG_H_BIAS,       /* float [n_pad] */
+    KZ_IMG_ROWQ,         /* double [n][3] */
+    KZ_IMG_DMAX,         /* double [3] */
+    KZ_IMG_DEALT_PERM,   /* int [n_pad] */
+    KZ_IMG_DEALT_H,
+    KZ_IMG_DEALT_BIAS,
+    KZ_IMG_ROWS_H,
+    KZ_IMG_ROWS_BIAS
+};
+int kz_selftest_image(kz_ctx* ctx, kz_matrix* m, kz_matrix* partner, int what, int64_t arg, const int* h_rows, void* h_dst,
+                      size_t capacity, size_t* h_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -868,6 +868,101 @@ int kz_matrix_set_seuclidean_v(kz_matrix* m, const double* V, int64_t d) {
     return KZ_OK;
 }
 
+// Test hook (tests/test_gpu_images.py): the raw bytes of one buffer this file builds.  The buffer is made by the functions the
+// searches call; nothing is un-layouted or recomputed here -- the test restates layout and arithmetic on its own.
+int kz_selftest_image(kz_ctx* ctx, kz_matrix* m, kz_matrix* partner, int what, int64_t arg, const int* h_rows, void* h_dst, size_t capacity,
+                      size_t* h_bytes) {
+    KZ_REQUIRE(ctx && m && h_bytes && m->ctx == ctx, "kz_selftest_image: null argument / foreign matrix");
+    KZ_REQUIRE(what >= KZ_IMG_SQN && what <= KZ_IMG_ROWS_BIAS, "kz_selftest_image: unknown buffer %d", what);
+    KZ_REQUIRE(capacity == 0 || h_dst, "kz_selftest_image: null destination");
+    for (const kz_matrix* x : {(const kz_matrix*)m, (const kz_matrix*)partner}) {
+        if (!x) continue;
+        KZ_REFUSE_PRECOMPUTED("kz_selftest_image", x);
+        KZ_REQUIRE(!x->raw_only && !kz_is_bool_metric(x->metric), "kz_selftest_image: a rows-only or boolean matrix has none of these buffers");
+    }
+    KZ_REQUIRE(!partner || (partner->ctx == ctx && partner->d == m->d && partner->metric == m->metric),
+               "kz_selftest_image: the partner must share context, width and metric");
+    KZ_HIP(hipSetDevice(ctx->device));
+    int rc = kz_matrix_check(m);
+    if (rc == KZ_OK && partner) rc = kz_matrix_check(partner);
+    if (rc != KZ_OK) return rc;
+    const bool mfma = m->metric <= KZ_COSINE;
+    const bool himage = what >= KZ_IMG_MU;
+    KZ_REQUIRE(mfma || what <= KZ_IMG_STATS || what == KZ_IMG_CORR, "kz_selftest_image: operand images exist for the MFMA metrics only");
+    KZ_REQUIRE(!himage || kz_h_slices_ok(m->kg), "kz_selftest_image: no fp16 image at d=%lld", (long long)m->d);
+    const int64_t n_pad = m->n_tiles * KZ_TILE;
+    const size_t nsr = (size_t)kz_h_nsr(m->kg);
+    if (himage) {
+        rc = kz_himage_ensure(m, partner ? partner : m);
+        if (rc != KZ_OK) return rc;
+    }
+    const void* src = nullptr;
+    size_t bytes = 0;
+    KzPoolBuf<unsigned short> t_packed;
+    KzPoolBuf<float> t_bias;
+    KzPoolBuf<int> t_rows;
+    switch (what) {
+    case KZ_IMG_SQN: src = m->sqn; bytes = (size_t)m->n * 8; break;
+    case KZ_IMG_BIAS: src = m->bias; bytes = (size_t)n_pad * 4; break;
+    case KZ_IMG_STATS: src = m->d_stats; bytes = 40; break;
+    case KZ_IMG_F32:
+        rc = kz_matrix_image_f32(m);
+        src = m->packed; bytes = (size_t)n_pad * (size_t)m->kg * 16;
+        break;
+    case KZ_IMG_BF:
+        rc = kz_matrix_image_bf(m);
+        src = m->packed_bf; bytes = (size_t)n_pad * (size_t)m->kg_bf * 16;
+        break;
+    case KZ_IMG_NORM64:
+        rc = kz_matrix_norm64(m);
+        src = m->norm64; bytes = m->norm64 ? (size_t)m->n * (size_t)m->d * 8 : 0;
+        break;
+    case KZ_IMG_CORR: src = m->corr; bytes = m->corr ? (size_t)m->n * 16 : 0; break;
+    case KZ_IMG_MU: src = m->himg->center->d_mu; bytes = nsr * 16 * 4; break;
+    case KZ_IMG_SCALE: src = m->himg->center->d_scale; bytes = 16; break;
+    case KZ_IMG_H: src = m->himg->packed; bytes = (size_t)n_pad * nsr * 32; break;
+    case KZ_IMG_H_BIAS: src = m->himg->bias; bytes = (size_t)n_pad * 4; break;
+    case KZ_IMG_ROWQ: src = m->himg->rowq; bytes = (size_t)m->n * 24; break;
+    case KZ_IMG_DMAX: src = m->himg->d_max; bytes = 24; break;
+    case KZ_IMG_DEALT_PERM:
+    case KZ_IMG_DEALT_H:
+    case KZ_IMG_DEALT_BIAS:
+        KZ_REQUIRE(arg >= 2 && arg <= m->n, "kz_selftest_image: dealt ranges P=%lld", (long long)arg);
+        rc = kz_himage_dealt(m, (int)arg);
+        if (rc != KZ_OK) return rc;
+        KZ_REQUIRE(m->himg->dealt_P == (int)arg, "kz_selftest_image: kz_himage_dealt selected P=%d", m->himg->dealt_P);
+        if (what == KZ_IMG_DEALT_PERM) { src = m->himg->dealt_perm; bytes = (size_t)n_pad * 4; }
+        else if (what == KZ_IMG_DEALT_H) { src = m->himg->dealt_packed; bytes = (size_t)n_pad * nsr * 32; }
+        else { src = m->himg->dealt_bias; bytes = (size_t)n_pad * 4; }
+        break;
+    default: {   // KZ_IMG_ROWS_H / KZ_IMG_ROWS_BIAS: arg rows of the HOST list h_rows, packed into the next multiple of 128 image rows
+        KZ_REQUIRE(h_rows && arg >= 1 && arg <= ((int64_t)1 << 20), "kz_selftest_image: row list of %lld rows", (long long)arg);
+        for (int64_t i = 0; i < arg; ++i)
+            KZ_REQUIRE(h_rows[i] >= 0 && h_rows[i] < m->n, "kz_selftest_image: row %d of the list is no matrix row", h_rows[i]);
+        const int64_t l_pad = (arg + KZ_TILE - 1) / KZ_TILE * KZ_TILE;
+        bytes = what == KZ_IMG_ROWS_H ? (size_t)l_pad * nsr * 32 : (size_t)l_pad * 4;
+        if (capacity == 0) break;
+        if (t_packed.alloc(ctx, (size_t)l_pad * nsr * 32 + 32 * 4096) != KZ_OK || t_bias.alloc(ctx, (size_t)l_pad * 4) != KZ_OK ||
+            t_rows.alloc(ctx, (size_t)arg * 4) != KZ_OK) {
+            kz_set_error("kz_selftest_image: out of device memory");
+            return KZ_ERR_NOMEM;
+        }
+        KZ_HIP(hipMemcpyAsync(t_rows.get(), h_rows, (size_t)arg * 4, hipMemcpyHostToDevice, ctx->stream));
+        KZ_HIP(hipStreamSynchronize(ctx->stream));   // (h_rows is the caller's pageable buffer)
+        rc = kz_himage_pack_rows(m, t_rows.get(), arg, l_pad, t_packed.get(), t_bias.get());
+        src = what == KZ_IMG_ROWS_H ? (const void*)t_packed.get() : (const void*)t_bias.get();
+        break;
+    }
+    }
+    if (rc != KZ_OK) return rc;
+    *h_bytes = bytes;
+    if (capacity == 0) return KZ_OK;
+    KZ_REQUIRE(capacity >= bytes, "kz_selftest_image: the buffer holds %zu bytes, the destination %zu", bytes, capacity);
+    if (bytes) KZ_HIP(hipMemcpyAsync(h_dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    return KZ_OK;
+}
+
 int kz_matrix_shape(const kz_matrix* m, int64_t* n, int64_t* d, int* dtype, int* metric) {
     KZ_REQUIRE(m != nullptr, "kz_matrix_shape: null matrix");
     if (n) *n = m->n;
