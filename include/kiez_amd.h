@@ -398,6 +398,50 @@ int kz_softmin_rows(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_
  * none is left, n == 0 included): a maximum, so the result does not depend on the order anything runs in.  The convergence read-out
  * of the Sinkhorn iteration.  Synchronises the context's stream. */
 int kz_max_abs_diff(kz_ctx* ctx, const double* d_a, const double* d_b, int64_t n, double* h_out);
+/* ---- the same potentials on the CANDIDATE LISTS (kz_softmin_lists.hip) -- additive, ABI v7 ------------------------------------- */
+/* kz_softmin_rows evaluates every pair of the two sides in every step.  These four calls restrict the transport plan to the pairs of
+ * neighbour lists d_dist / d_ind [n_q, k] (float64 / int64, on the device): entry (i, c) is a PAIR of source row i and target row
+ * d_ind[i, c] when 0 <= d_ind[i, c] < n_index, kz_match_lists' rule; any other id (-1, kz_knn_reduced's INT_MAX padding, an id >=
+ * n_index) is no pair.  A pair outside a row's list would carry exp(-(d - m) / eps) of mass; it is DROPPED, so the potentials depend
+ * on k.  1 <= k <= KZ_MAX_CANDIDATES, 1 <= n_index <= 2^31 - 2, n_q k <= 2^31 - 2, eps finite and > 0, shift finite, no null
+ * pointer: KZ_ERR_INVALID otherwise.  A NaN value (a NaN distance, a NaN offset) counts as +inf; a set with no entry below +inf
+ * gives +inf + shift, one with a -inf gives -inf, all as kz_softmin_rows.  New: a row or a column with NO PAIR AT ALL gives NaN,
+ * "no value" -- a target row nobody lists has no potential, and under KZ_RANK_DUAL its w is NaN and ranks last, by row.
+ *
+ * kz_lists_transpose: the column-major view of the pairs.  d_colptr [n_index + 1] (int64), d_col_row [n_q k] (int32: the source row)
+ * and d_col_val [n_q k] (float64: the pair's d_dist); the entries of column j are the places d_colptr[j] .. d_colptr[j + 1] - 1, in
+ * ascending flat position i k + c (ascending source row); d_colptr[n_index] = nnz, the places behind it are not written.  *h_nnz
+ * (host, may be NULL: then nothing is read back and the call does not synchronise) = nnz.  A stable sort places the entries, no
+ * atomic does: the arrays are the same in every run.  n_q == 0: all of d_colptr is 0. */
+int kz_lists_transpose(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index,
+                       int64_t* d_colptr, int32_t* d_col_row, double* d_col_val, int64_t* h_nnz);
+/* d_out[i] = softmin_eps over the pairs c of row i of (d_dist[i, c] - d_off[d_ind[i, c]])  +  shift; d_off: [n_index] or NULL,
+ * d_out: [n_q].  The order a row's terms are added in is a fixed tree that depends on k only (k <= 64: the next power of two >= k
+ * lanes hold a row; k > 64: one wave per row): the same bits whichever other rows are in the call, and from run to run.
+ * n_q == 0: KZ_OK.  Synchronises the context's stream. */
+int kz_softmin_list_rows(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index, double eps,
+                         const double* d_off, double shift, double* d_out);
+/* d_out[j] = softmin_eps over the entries p of column j of (d_col_val[p] - d_off[d_col_row[p]])  +  shift, on the view
+ * kz_lists_transpose wrote; nnz: what it returned (or the capacity n_q k of the arrays); d_off: [n_q] or NULL, d_out: [n_index].
+ * A column is cut into chunks of KZ_SOFTMIN_LIST_CHUNK entries counted from its own first entry; one wave reduces a chunk to
+ * (minimum, sum), the parts of a column of more than one chunk are folded by one wave, lane l taking the chunks l, l + 64, ...
+ * in ascending order.  The tree is a function of the column's entry count and KZ_SOFTMIN_LIST_CHUNK only (no float atomics): the
+ * same bits wherever the column lies in the view, whatever other columns and rows are in the call, and from run to run.
+ * Synchronises the context's stream. */
+#define KZ_SOFTMIN_LIST_CHUNK 512 /* entries of a column per first-level wave: part of the summation order */
+int kz_softmin_list_cols(kz_ctx* ctx, const int64_t* d_colptr, const int32_t* d_col_row, const double* d_col_val, int64_t n_index,
+                         int64_t nnz, double eps, const double* d_off, double shift, double* d_out);
+/* The Sinkhorn iteration over the lists: from f = 0, n_iter >= 1 times the column step g = kz_softmin_list_cols(d_off = f, shift =
+ * eps log(n_q / n_index)) (the first one without offset) and the row step f = kz_softmin_list_rows(d_off = g), bit for bit what the
+ * two calls return.  tol >= 0: the loop stops after the column step that moves g by at most tol -- the largest |g_new - g_old|, NaN
+ * differences ignored as kz_max_abs_diff ignores them; the row step behind that column step is still taken.  tol < 0: no
+ * tolerance.  Writes d_f [n_q] and d_g [n_index] (device), *h_n_iter = the iterations done, *h_change = the last measured change
+ * of g and *h_measured = 1 -- or 0, with *h_change = 0, when none was measured (a single iteration); the three host pointers may
+ * be NULL.  The transposition and every step are queued at once and the stopping rule is decided on the device (the steps behind
+ * the stop return at once); the host reads once, at the end.  n_iter < 1, a NaN tol: KZ_ERR_INVALID; n_q == 0: KZ_OK, nothing is
+ * written (*h_n_iter = 0).  Synchronises the context's stream. */
+int kz_sinkhorn_lists(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index, double eps,
+                      int n_iter, double tol, double* d_f, double* d_g, int* h_n_iter, double* h_change, int* h_measured);
 /* Reductions of a rank vector d_rank [n] (entries < 0: no rank).  h_hits[j] (host, j < n_k <= 64) = #(0 <= rank < h_ks[j]);
  * h_out[3] (host) = #(rank >= 0), sum(rank + 1), sum 1 / (rank + 1) -- the float64 sum in a fixed order. */
 int kz_rank_stats(kz_ctx* ctx, const int64_t* d_rank, int64_t n, const int64_t* h_ks, int n_k, int64_t* h_hits, double* h_out);

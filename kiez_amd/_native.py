@@ -141,6 +141,11 @@ SYMBOLS = [
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_softmin_rows", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, _P, C.c_double, _P]),
     ("kz_max_abs_diff", C.c_int, [_P, _P, _P, _I64, C.POINTER(C.c_double)]),
+    ("kz_lists_transpose", C.c_int, [_P, _P, _P, _I64, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_softmin_list_rows", C.c_int, [_P, _P, _P, _I64, C.c_int, _I64, C.c_double, _P, C.c_double, _P]),
+    ("kz_softmin_list_cols", C.c_int, [_P, _P, _P, _P, _I64, _I64, C.c_double, _P, C.c_double, _P]),
+    ("kz_sinkhorn_lists", C.c_int, [_P, _P, _P, _I64, C.c_int, _I64, C.c_double, C.c_int, C.c_double, _P, _P, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("kz_rank_stats", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.c_int, C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("kz_match_lists", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, _P, _P, C.POINTER(_I64)]),
     ("kz_match_values", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _P]),
@@ -564,6 +569,78 @@ def _list_pair(dist: DeviceArray, ind: DeviceArray):
     if dist.dtype not in (np.float32, np.float64) or ind.dtype != np.int64:
         raise ValueError(f"dist must be float32 or float64 and ind int64, got {dist.dtype} and {ind.dtype}")
     return dist.shape[0], dist.shape[1], KZ_F32 if dist.dtype == np.float32 else KZ_F64
+
+
+# entries of a column per first-level wave of kz_softmin_list_cols (include/kiez_amd.h: KZ_SOFTMIN_LIST_CHUNK): part of its summation order
+SOFTMIN_LIST_CHUNK = 512
+
+
+def _f64_lists(dist: DeviceArray, ind: DeviceArray):
+    """(n_q, k) of float64 / int64 neighbour lists on the device, as the soft-min calls over the lists take them."""
+    n_q, k, dtype = _list_pair(dist, ind)
+    if dtype != KZ_F64:
+        raise ValueError(f"the soft-min over neighbour lists takes float64 values, got {dist.dtype}")
+    return n_q, k
+
+
+class ListsTransposed:
+    """The column-major view of the pairs of neighbour lists (kz_lists_transpose): `colptr` int64 [n_index + 1], `col_row` int32 and
+    `col_val` float64 with `nnz` entries used (the arrays hold n_q k); column j is colptr[j] .. colptr[j + 1] - 1, ascending source row."""
+
+    def __init__(self, colptr, col_row, col_val, nnz, n_q, n_index):
+        self.colptr, self.col_row, self.col_val, self.nnz, self.n_q, self.n_index = colptr, col_row, col_val, nnz, n_q, n_index
+
+
+def lists_transpose(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int) -> ListsTransposed:
+    """kz_lists_transpose -> the column-major view of the pairs of dist / ind [n_q, k] (float64 / int64, on the device): entry (i, c)
+    with 0 <= ind[i, c] < n_index is a pair, any other id is none.  The same arrays from every run."""
+    n_q, k = _f64_lists(dist, ind)
+    colptr = ctx.empty((int(n_index) + 1,), np.int64)
+    col_row, col_val = ctx.empty((n_q * k,), np.int32), ctx.empty((n_q * k,), np.float64)
+    nnz = _I64(0)
+    _check(ctx.lib.kz_lists_transpose(ctx.handle, dist.ptr, ind.ptr, n_q, k, int(n_index), colptr.ptr, col_row.ptr, col_val.ptr, C.byref(nnz)),
+           "kz_lists_transpose")
+    return ListsTransposed(colptr, col_row, col_val, int(nnz.value), n_q, int(n_index))
+
+
+def softmin_list_rows(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, eps: float, off: Optional[DeviceArray] = None,
+                      shift: float = 0.0) -> DeviceArray:
+    """kz_softmin_list_rows -> float64 [n_q] on the device: per row the soft-min at temperature `eps` over the row's PAIRS of
+    (dist[i, c] - off[ind[i, c]]), plus `shift`.  `off`: a float64 DeviceArray [n_index] or None.  A row without a pair gives NaN; the
+    bits of a row do not depend on the other rows of the call."""
+    n_q, k = _f64_lists(dist, ind)
+    if off is not None:
+        _f64_vector("off", off, int(n_index))
+    out = ctx.empty((n_q,), np.float64)
+    _check(ctx.lib.kz_softmin_list_rows(ctx.handle, dist.ptr, ind.ptr, n_q, k, int(n_index), float(eps), off.ptr if off is not None else None,
+                                        float(shift), out.ptr), "kz_softmin_list_rows")
+    return out
+
+
+def softmin_list_cols(ctx: Context, view: ListsTransposed, eps: float, off: Optional[DeviceArray] = None, shift: float = 0.0) -> DeviceArray:
+    """kz_softmin_list_cols -> float64 [n_index] on the device: per column of the view `lists_transpose` returned the soft-min over
+    its entries of (col_val[p] - off[col_row[p]]), plus `shift`.  `off`: a float64 DeviceArray [n_q] or None.  A column without an
+    entry gives NaN; the bits of a column depend on its entry count and SOFTMIN_LIST_CHUNK only."""
+    if off is not None:
+        _f64_vector("off", off, view.n_q)
+    out = ctx.empty((view.n_index,), np.float64)
+    _check(ctx.lib.kz_softmin_list_cols(ctx.handle, view.colptr.ptr, view.col_row.ptr, view.col_val.ptr, view.n_index, view.nnz, float(eps),
+                                        off.ptr if off is not None else None, float(shift), out.ptr), "kz_softmin_list_cols")
+    return out
+
+
+def sinkhorn_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, eps: float, n_iter: int,
+                   tol: Optional[float] = None) -> Tuple[DeviceArray, DeviceArray, int, Optional[float]]:
+    """kz_sinkhorn_lists -> (f float64 [n_q], g float64 [n_index], iterations done, last measured change of g or None): the Sinkhorn
+    iteration of `softmin_list_cols` / `softmin_list_rows` from f = 0, queued at once, the stopping rule (`tol`; None: none) decided
+    on the device."""
+    n_q, k = _f64_lists(dist, ind)
+    f, g = ctx.empty((n_q,), np.float64), ctx.empty((int(n_index),), np.float64)
+    done, change, measured = C.c_int(0), C.c_double(0.0), C.c_int(0)
+    _check(ctx.lib.kz_sinkhorn_lists(ctx.handle, dist.ptr, ind.ptr, n_q, k, int(n_index), float(eps), int(n_iter),
+                                     -1.0 if tol is None else float(tol), f.ptr, g.ptr, C.byref(done), C.byref(change), C.byref(measured)),
+           "kz_sinkhorn_lists")
+    return f, g, int(done.value), float(change.value) if measured.value else None
 
 
 def match_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int) -> Tuple[DeviceArray, DeviceArray, int]:

@@ -4,7 +4,8 @@ minimum-cost assignment (`kz_assign_lists`).
 Every neighbour list lets many source rows claim one target row.  Entity alignment is a matching task -- a target entity belongs
 to at most one source entity -- and the CSLS-style pipelines end with a one-to-one step.  `one_to_one` is that step for any lists
 this library (or anything else) produced, `assignment` the same step with the total value of the pairs minimised instead of pairs
-taken greedily; `Kiez.match` runs either on the lists of a fitted instance without taking them out of HBM."""
+taken greedily; `Kiez.match` runs either on the lists of a fitted instance without taking them out of HBM.  `sinkhorn_lists` is the soft form over the
+same lists: the Sinkhorn potentials with the transport plan restricted to the listed pairs (`kz_sinkhorn_lists`)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -149,3 +150,40 @@ def assignment(dist, ind, n_target: int, *, unmatched_cost: Optional[float] = No
     if not on_device:
         out = tuple(x.numpy() for x in out)
     return out if len(out) > 1 else out[0]
+
+
+def sinkhorn_lists(dist, ind, n_target: int, *, temperature: float = 0.05, n_iter: int = 10, tol: Optional[float] = None,
+                   ctx: Optional[N.Context] = None, return_info: bool = False):
+    """The Sinkhorn potentials of neighbour lists, on the device (`kz_sinkhorn_lists`): entropic optimal transport between the source
+    rows and `n_target` target rows with the plan restricted to the LISTED pairs -- what `Sinkhorn(support="candidates")` fits, for
+    any caller's lists.
+
+    `dist`, `ind`, `n_target` as `one_to_one` takes them (numpy arrays or `DeviceArray`s; an entry with `ind` outside [0, n_target)
+    is no pair, so the padded lists of `kneighbors_whole_index` are fine); values are taken as float64.  From f = 0, `n_iter` times:
+    g_j = softmin_eps over the rows i that list j of (d_ij - f_i) + eps log(n_q / n_target), then f_i = softmin_eps over the pairs of
+    row i of (d_ij - g_j), softmin_eps(x) = m - eps log sum exp(-(x - m) / eps), m = min x; `temperature` is eps, in the units of
+    `dist`.  `tol`: stop after the column step that moves g by at most tol (None: exactly `n_iter` iterations).  The pairs outside
+    the lists are dropped, so the potentials depend on how long the lists are.  A target row that no row lists, and a row without a
+    pair, get NaN.  Every run returns the same bits.
+
+    Returns `(f, g)`, float64 [n_q] and [n_target] -- numpy arrays for numpy lists, `DeviceArray`s if `dist` is one -- and with
+    `return_info=True` a third item, the dict {"n_iter": iterations done, "potential_change": the last measured change of g or None}.
+    `(dist - f[:, None]) - g[ind]` is the reduced distance of the listed pairs (`Sinkhorn.transform`)."""
+    dist, ind = _checked_lists(dist, ind, n_target)
+    if (isinstance(temperature, (bool, np.bool_)) or not isinstance(temperature, (int, float, np.integer, np.floating))
+            or not np.isfinite(temperature) or temperature <= 0):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    if isinstance(n_iter, (bool, np.bool_)) or not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
+    if tol is not None and (isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0):
+        raise ValueError(f"tol must be None or a number >= 0, got {tol!r}")
+    on_device = isinstance(dist, N.DeviceArray)
+    if on_device and dist.dtype != np.float64:
+        raise ValueError(f"a device dist must be float64 here, got {dist.dtype}")
+    if not on_device:
+        dist = dist.astype(np.float64, copy=False)
+    if ctx is None:
+        ctx = dist.ctx if on_device else ind.ctx if isinstance(ind, N.DeviceArray) else N.Context.get()
+    f, g, done, change = N.sinkhorn_lists(ctx, ctx.as_device(dist), ctx.as_device(ind), int(n_target), float(temperature), int(n_iter), tol)
+    out = (f, g) if on_device else (f.numpy(), g.numpy())
+    return out + ({"n_iter": done, "potential_change": change},) if return_info else out
