@@ -77,6 +77,8 @@ struct kz_ctx {
     void* h_stage;    // pinned host staging for the per-call work table
     size_t h_stage_bytes;
     int h_stage_flip; // which half of h_stage the last pass used (kz_prepare_pass)
+    const void* lds_raised[16];   // sweep kernels whose dynamic-LDS limit this context has raised on its device (kz_knn_kernels.h)
+    unsigned lds_raised_next;
     // stream-ordered free list: buffers released by kz_free / kz_matrix_destroy are reused by later allocations of a
     // similar size instead of going through hipFree (device-wide sync) + hipMalloc on every fit()
     struct { void* ptr; size_t bytes; } pool[KZ_POOL_SLOTS];
@@ -106,10 +108,10 @@ __host__ __device__ __forceinline__ bool kz_h_slices_ok(int kg) {
     return (s >= 2 && s <= 24) || (s >= 32 && s <= 128);
 }
 // Work items the planner may put into one round of an fp16 launch: the resident workgroups -- half of them where two workgroups
-// sweep one item (n_slices = kz_h_nsr(kg) > 64: the parity-split builds own 64 queries each).
-__host__ __forceinline__ int kz_h_slots(int n_slices, int blocks_per_cu, int n_cus) {
+// sweep one item (wg_per_item of the kernel's descriptor, kz_knn_kernels.h: the parity-split builds own 64 queries each).
+__host__ __forceinline__ int kz_h_slots(int wg_per_item, int blocks_per_cu, int n_cus) {
     const int resident = blocks_per_cu * n_cus;
-    return n_slices > 64 ? (resident + 1) / 2 : resident;
+    return wg_per_item > 1 ? (resident + 1) / 2 : resident;
 }
 
 struct kz_center {

@@ -24,6 +24,7 @@
 #include "kz_floor.h"
 
 #include "kz_knn_device.h"
+#include "kz_knn_kernels.h"
 
 // The shipped fused kernel (kernel_variant 0).
 // NRES = number of leading 16-k slices whose QUERY fragments stay resident in registers for the whole sweep
@@ -223,69 +224,20 @@ static int kz_pick_list_len(int k_eff) {
     return 0;
 }
 
-template <int KP>
-static int kz_cand_occupancy(int* blocks_per_cu) {
-    auto kern = kz_knn_cand_kernel<KP, 0>;
-    int nb = 0;
-    KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 256, KZ_CAND_LDS));
-    *blocks_per_cu = nb < 1 ? 1 : nb;
-    return KZ_OK;
+// The float32-operand kernel's entries of the kernel table (kz_knn_kernels.h): one build per list length, any slice count
+template <int... KPS>
+static KzSweepKernel kz_sweep_f32_table(int KP, int n_slices, std::integer_sequence<int, KPS...>) {
+    static const KzSweepKernel table[] = {{(const void*)kz_knn_cand_kernel<KPS, 0>, KZ_CAND_LDS, 1, 1, KPS, 0}...};
+    for (KzSweepKernel k : table)
+        if (k.KP == KP) {
+            k.n_slices = n_slices;
+            return k;
+        }
+    return KzSweepKernel{};
 }
-
-template <int KP>
-static int kz_launch_cand(kz_ctx* ctx, const KnnCandParams& p, int n_blocks) {
-    hipLaunchKernelGGL((kz_knn_cand_kernel<KP, 0>), dim3(n_blocks), dim3(256), KZ_CAND_LDS, ctx->stream, p);
-    KZ_HIP(hipGetLastError());
-    return KZ_OK;
+KzSweepKernel kz_sweep_f32_kernel(int KP, int n_slices) {
+    return kz_sweep_f32_table(KP, n_slices, std::integer_sequence<int, 16, 32, 64, 128>{});
 }
-
-#define KZ_DISPATCH_CAND(rc, fn, args)          \
-    do {                                        \
-        switch (KP) {                           \
-            case 16: rc = fn<16> args; break;   \
-            case 32: rc = fn<32> args; break;   \
-            case 64: rc = fn<64> args; break;   \
-            default: rc = fn<128> args; break;  \
-        }                                       \
-    } while (0)
-
-// fp16 and split-bf16 kernels: instantiated per list length in kz_knn_h_kp*.hip / kz_knn_bf_kp*.hip (parallel compilation)
-int kz_h_occupancy_kp16(int n_slices, int* blocks_per_cu);
-int kz_h_occupancy_kp32(int n_slices, int* blocks_per_cu);
-int kz_h_occupancy_kp64(int n_slices, int* blocks_per_cu);
-int kz_h_occupancy_kp128(int n_slices, int* blocks_per_cu);
-int kz_h_launch_kp16(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_h_launch_kp32(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_h_launch_kp64(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_h_launch_kp128(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_hd_occupancy_kp16(int n_slices, int* blocks_per_cu);
-int kz_hd_occupancy_kp32(int n_slices, int* blocks_per_cu);
-int kz_hd_occupancy_kp64(int n_slices, int* blocks_per_cu);
-int kz_hd_occupancy_kp128(int n_slices, int* blocks_per_cu);
-int kz_hd_launch_kp16(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_hd_launch_kp32(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_hd_launch_kp64(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_hd_launch_kp128(int n_slices, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-bool kz_h64_supports(int n_slices);   // kz_knn_h64.hip: 64 queries per wave, K' = 16, ordinary (dual = 0) and dual-pass builds
-int kz_h64_occupancy(int n_slices, int dual, int* blocks_per_cu);
-int kz_h64_launch(int n_slices, int dual, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_bf_occupancy_kp16(int n_slices_bf, int* blocks_per_cu);
-int kz_bf_occupancy_kp32(int n_slices_bf, int* blocks_per_cu);
-int kz_bf_occupancy_kp64(int n_slices_bf, int* blocks_per_cu);
-int kz_bf_occupancy_kp128(int n_slices_bf, int* blocks_per_cu);
-int kz_bf_launch_kp16(int n_slices_bf, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_bf_launch_kp32(int n_slices_bf, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_bf_launch_kp64(int n_slices_bf, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-int kz_bf_launch_kp128(int n_slices_bf, kz_ctx* ctx, const KnnCandParams& p, int n_blocks);
-#define KZ_DISPATCH_KP(rc, fn, args)                 \
-    do {                                             \
-        switch (KP) {                                \
-            case 16: rc = fn##_kp16 args; break;     \
-            case 32: rc = fn##_kp32 args; break;     \
-            case 64: rc = fn##_kp64 args; break;     \
-            default: rc = fn##_kp128 args; break;    \
-        }                                            \
-    } while (0)
 
 // (kz_plan_rounds, kz_plan_pass, kz_plan_fill_work: kz_plan.h)
 extern "C" int kz_knn_plan(int64_t n_query_rows, int64_t n_index_rows, int k_eff, int slots, int force_splits, int min_splits,
@@ -341,11 +293,7 @@ __global__ __launch_bounds__(256) void kz_scatter_rows_kernel(const double* __re
     oi[(int64_t)rows[r] * k + c] = si[t];
 }
 
-// Operand precision of the fused kernel ("tier").  kz_knn starts at the highest tier the shapes allow; rows whose
-// candidate set cannot be certified under that tier's bound go down: fp16 / split-bf16 -> float32 operands (gathered into
-// a dense query block) -> exact float64 brute force.  The result is the float64 neighbour order at every tier.
-enum { KZ_TIER_F32 = 0, KZ_TIER_BF = 1, KZ_TIER_H = 2 };
-
+// (KZ_TIER_F32 / KZ_TIER_BF / KZ_TIER_H, the operand precision of the fused kernel: kz_knn_kernels.h)
 // One launch of a fused kernel: list layout, scratch carve-up and the uploaded work table.
 struct KzPass {
     KzListLayout lay;
@@ -1114,29 +1062,29 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     // 89.2 ms), the ordinary kernel +0.8 % there, +8 % at 8 slices, and a launch of fewer than ~4 rounds of units does not fill the
     // chip (100k x 100k: +30 %).  Option "h_q64": 2 (default) = the shared sweep from 9 slices on over >= 4 rounds of units,
     // 1 = wherever the kernel is built for (tests), 0 = never.
-    const bool q64_ok = tier == KZ_TIER_H && KP == 16 && kz_h64_supports(n_slices) && !exact_only;
+    bool q64_ok = false;
+    if (tier == KZ_TIER_H && KP == 16 && !exact_only) {   // (is there a 64-query build for these rows?  The resolver may come back empty)
+        KzSweepKernel k64;
+        const int rc = kz_sweep_kernel(KZ_TIER_H, dual != nullptr, true, KP, n_slices, &k64, true);
+        if (rc != KZ_OK) return rc;
+        q64_ok = k64.fn != nullptr;
+    }
     const bool q64 = q64_ok && !(dual && dual->no_q64) && (ctx->h_q64 == 1 || (ctx->h_q64 == 2 && dual && n_slices >= 9 &&
                                                      (q_count + 2 * KZ_TILE - 1) / (2 * KZ_TILE) >= (int64_t)4 * 2 * ctx->n_cus));
-    int slots_cache[3] = {0, 0, 0};
     const int tpw_h = q64 ? 2 : 1;   // query tiles per workgroup of the fp16 kernel this call runs
-    auto slots_for = [&](int t, int* out) -> int {
-        if (slots_cache[t] == 0) {
-            int blocks_per_cu = 1;
-            int rc0;
-            if (t == KZ_TIER_H && q64)
-                rc0 = kz_h64_occupancy(n_slices, dual ? 1 : 0, &blocks_per_cu);
-            else if (t == KZ_TIER_H && dual)
-                KZ_DISPATCH_KP(rc0, kz_hd_occupancy, (n_slices, &blocks_per_cu));
-            else if (t == KZ_TIER_H)
-                KZ_DISPATCH_KP(rc0, kz_h_occupancy, (n_slices, &blocks_per_cu));
-            else if (t == KZ_TIER_BF)
-                KZ_DISPATCH_KP(rc0, kz_bf_occupancy, (n_slices, &blocks_per_cu));
-            else
-                KZ_DISPATCH_CAND(rc0, kz_cand_occupancy, (&blocks_per_cu));
-            if (rc0 != KZ_OK) return rc0;
-            slots_cache[t] = t == KZ_TIER_H ? kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus) : blocks_per_cu * ctx->n_cus;
-        }
-        *out = slots_cache[t];
+    // The sweep kernel of the call's tier and the work items a round of it may hold: resolved (and its occupancy queried) once, and
+    // again only when the call goes down a tier.  The one choice of kernel: every launch below starts `kern`.
+    KzSweepKernel kern;
+    int kern_tier = -1, kern_slots = 0;
+    auto kernel_for = [&](int t) -> int {
+        if (kern_tier == t && kern.KP == KP) return KZ_OK;
+        int rc0 = kz_sweep_kernel(t, dual != nullptr, q64, KP, n_slices, &kern);
+        if (rc0 != KZ_OK) return rc0;
+        int blocks_per_cu = 1;
+        rc0 = kz_sweep_occupancy(ctx, kern, &blocks_per_cu);
+        if (rc0 != KZ_OK) return rc0;
+        kern_slots = kz_h_slots(kern.wg_per_item, blocks_per_cu, ctx->n_cus);
+        kern_tier = t;
         return KZ_OK;
     };
     // query rows are processed in chunks so that the candidate lists stay below ~1 GiB: 524288 rows for K' >= 64, up to four
@@ -1174,11 +1122,11 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 return rcd;
             }
         }
-        int slots = 0;
         {
-            const int rcs = slots_for(tier, &slots);
-            if (rcs != KZ_OK) return rcs;
+            const int rck = kernel_for(tier);
+            if (rck != KZ_OK) return rck;
         }
+        const int slots = kern_slots;
         const int64_t cq_begin = q_begin + c0;
         const int qt0 = (int)(cq_begin / KZ_TILE);
         int64_t cq_count = 0;
@@ -1260,15 +1208,10 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             cp.log_meta = dual->log_meta;
             cp.log_cnt = dual->log_cnt;
             cp.log_cap = dual->log_cap;
-            if (q64)
-                rc = kz_h64_launch(n_slices, 1, ctx, cp, W);
-            else
-                KZ_DISPATCH_KP(rc, kz_hd_launch, (n_slices, ctx, cp, W));
-        } else if (tier == KZ_TIER_H && q64)
-            rc = kz_h64_launch(n_slices, 0, ctx, cp, W);
-        else if (tier == KZ_TIER_H && boot && ps.W0 > 0 && ps.W0 < W) {
+            rc = kz_sweep_launch(ctx, kern, cp, W);
+        } else if (tier == KZ_TIER_H && boot && ps.W0 > 0 && ps.W0 < W) {
             // range 0 of every query tile, the floor off its lists, then the other ranges
-            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W0));
+            rc = kz_sweep_launch(ctx, kern, cp, ps.W0);
             if (rc != KZ_OK) return rc;
             const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
             rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);   // (a buffer of this chunk: escalated sub-searches boot too)
@@ -1278,9 +1221,9 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
             KZ_HIP(hipGetLastError());
             cp.qfloor = boot_floor.get();
             cp.work = d_work + ps.W0;
-            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W - ps.W0));
+            rc = kz_sweep_launch(ctx, kern, cp, W - ps.W0);
             cp.work = d_work;
-        } else if (tier == KZ_TIER_H) {
+        } else if (tier == KZ_TIER_H && !q64) {
             if ((ctx->abl & 2) && getenv("KZ_STAMP_FILE")) {   // (diagnostic: a -DKZ_ABL_STAMP build of the fp16 units fills it)
                 rc = stamp_buf.alloc(ctx, (size_t)W * (16 + 1024));
                 if (rc != KZ_OK) return rc;
@@ -1288,7 +1231,7 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 cp.log_meta = stamp_buf.get();
                 cp.log_keys = stamp_buf.get() + 2 * (size_t)W;
             }
-            KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W));
+            rc = kz_sweep_launch(ctx, kern, cp, W);
             cp.log_meta = nullptr;
             cp.log_keys = nullptr;
             if (rc == KZ_OK && (ctx->abl & 1) && !short_ord && ps.lay.n_regions == 1 && ps.lay.pieces[0] == 1) {
@@ -1305,12 +1248,10 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
                 KZ_HIP(hipGetLastError());
                 cp.qfloor = boot_floor.get();
                 KZ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-                KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, W));
+                rc = kz_sweep_launch(ctx, kern, cp, W);
             }
-        } else if (tier == KZ_TIER_BF)
-            KZ_DISPATCH_KP(rc, kz_bf_launch, (n_slices, ctx, cp, W));
-        else
-            KZ_DISPATCH_CAND(rc, kz_launch_cand, (ctx, cp, W));
+        } else   // (the 64-query kernel, the split-bf16 and the float32 operands: one plain launch)
+            rc = kz_sweep_launch(ctx, kern, cp, W);
         if (rc != KZ_OK) return rc;
         if (dual && tier != KZ_TIER_H) dual->broken = 1;   // this chunk's pairs were not scanned for events
         KZ_HIP(hipEventRecord(ctx->ev[1], ctx->stream));

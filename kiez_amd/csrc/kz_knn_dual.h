@@ -1170,14 +1170,15 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
                            n_slices, stride3, (int)s3_tiles, force_s3 > 0 ? force_s3 : 1, (uint4*)nst.s3_packed.get(), nst.s3_bias.get());
         KZ_HIP(hipGetLastError());
         {
-            const int KP = KPs3;   // (KZ_DISPATCH_KP switches on `KP`)
+            KzSweepKernel kern;
             int blocks_per_cu = 1;
-            KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu));
+            rc = kz_sweep_kernel(KZ_TIER_H, false, false, KPs3, n_slices, &kern);
+            if (rc == KZ_OK) rc = kz_sweep_occupancy(ctx, kern, &blocks_per_cu);
             if (rc != KZ_OK) return rc;
             KzPass ps;
-            const int slots = kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus);
+            const int slots = kz_h_slots(kern.wg_per_item, blocks_per_cu, ctx->n_cus);
             KzPlan pl;
-            kz_plan_tier_pass(ctx, (int)s_tiles, (int)s3_tiles, slots, 256 / KP, KP, KZ_TIER_H, 1, force_s3, 0, &pl);
+            kz_plan_tier_pass(ctx, (int)s_tiles, (int)s3_tiles, slots, 256 / KPs3, KPs3, KZ_TIER_H, 1, force_s3, 0, &pl);
             rc = kz_prepare_pass(ctx, pl, (int)s3_tiles, slots, KZ_TIER_H, 0, &ps);
             if (rc == KZ_OK) {
                 KnnCandParams cp;
@@ -1193,12 +1194,12 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
                 cp.kg = b->kg;
                 cp.out_key = ps.out_key;
                 cp.out_idx = ps.out_idx;
-                KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W));
+                rc = kz_sweep_launch(ctx, kern, cp, ps.W);
             }
             if (rc != KZ_OK) return rc;
             // (the rows owning these thresholds are rows of S, position j of the dealt image: bias q_bias.get()[j]; their events come from b)
             hipLaunchKernelGGL(kz_dual_theta_kernel, dim3((unsigned)((s_img_rows + 3) / 4)), dim3(256), 0, ctx->stream, ps.out_key, ps.out_idx,
-                               ps.lay, KP, rank3, s_img_rows, s_img_rows, q_bias.get(), ib->d_max, ia->d_max, ia->center->d_scale, nst.theta3.get(), nst.floor3.get(),
+                               ps.lay, KPs3, rank3, s_img_rows, s_img_rows, q_bias.get(), ib->d_max, ia->d_max, ia->center->d_scale, nst.theta3.get(), nst.floor3.get(),
                                (const int*)nullptr, 0, (int*)nullptr, (uint2*)nullptr);
             KZ_HIP(hipGetLastError());
         }
@@ -1306,14 +1307,15 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
                            n_slices, stride, (int)s_tiles, force_s > 0 ? force_s : 1, (uint4*)s_packed.get(), s_bias.get());
         KZ_HIP(hipGetLastError());
         // ---- sample sweep: B x sample(A) with the ordinary kernel, lists of at most 256 entries per row -----------------------
-        const int KP = KPs;   // (KZ_DISPATCH_KP switches on `KP`)
+        KzSweepKernel kern;
         int blocks_per_cu = 1;
-        KZ_DISPATCH_KP(rc, kz_h_occupancy, (n_slices, &blocks_per_cu));
+        rc = kz_sweep_kernel(KZ_TIER_H, false, false, KPs, n_slices, &kern);
+        if (rc == KZ_OK) rc = kz_sweep_occupancy(ctx, kern, &blocks_per_cu);
         if (rc != KZ_OK) return rc;
         KzPass ps;
-        const int slots = kz_h_slots(n_slices, blocks_per_cu, ctx->n_cus);
+        const int slots = kz_h_slots(kern.wg_per_item, blocks_per_cu, ctx->n_cus);
         KzPlan pl;
-        kz_plan_tier_pass(ctx, (int)b_tiles, (int)s_tiles, slots, 256 / KP, KP, KZ_TIER_H, 1, force_s, 0, &pl);
+        kz_plan_tier_pass(ctx, (int)b_tiles, (int)s_tiles, slots, 256 / KPs, KPs, KZ_TIER_H, 1, force_s, 0, &pl);
         rc = kz_prepare_pass(ctx, pl, (int)s_tiles, slots, KZ_TIER_H, 0, &ps);
         if (rc != KZ_OK) return rc;
         KnnCandParams cp;
@@ -1329,10 +1331,10 @@ extern "C" int kz_knn_dual(kz_ctx* ctx, const kz_matrix* a_c, const kz_matrix* b
         cp.kg = b->kg;
         cp.out_key = ps.out_key;
         cp.out_idx = ps.out_idx;
-        KZ_DISPATCH_KP(rc, kz_h_launch, (n_slices, ctx, cp, ps.W));
+        rc = kz_sweep_launch(ctx, kern, cp, ps.W);
         if (rc != KZ_OK) return rc;
         hipLaunchKernelGGL(kz_dual_theta_kernel, dim3((unsigned)((b_pad + 3) / 4)), dim3(256), 0, ctx->stream, ps.out_key, ps.out_idx,
-                           ps.lay, KP, rank, b->n, b_pad, ib->bias, ia->d_max, ib->d_max, ib->center->d_scale, theta.get(), floor_.get(),
+                           ps.lay, KPs, rank, b->n, b_pad, ib->bias, ia->d_max, ib->d_max, ib->center->d_scale, theta.get(), floor_.get(),
                            (const int*)nullptr, 0, (int*)nullptr, (uint2*)nullptr);
         KZ_HIP(hipGetLastError());
     }
