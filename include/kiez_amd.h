@@ -36,8 +36,11 @@ extern "C" {
 
 /* status codes */
 enum { KZ_OK = 0, KZ_ERR_INVALID = 1, KZ_ERR_HIP = 2, KZ_ERR_UNSUPPORTED = 3, KZ_ERR_NOMEM = 4, KZ_ERR_NONFINITE = 5 };
-/* element types of an embedding matrix */
-enum { KZ_F32 = 0, KZ_F64 = 1 };
+/* element types of an embedding matrix.  KZ_F16 (IEEE binary16) and KZ_BF16 (the upper half of a float32) are STORAGE types: rows of
+ * 2 bytes per element, read in place, for the metrics of the fused MFMA kernels (0 .. 2) only.  Such a matrix behaves in every
+ * call like the KZ_F64 matrix that holds the same values widened exactly: the same neighbours, the same distance bits, float64
+ * outputs, the same errors.  (Additive: the ABI version stays 7.) */
+enum { KZ_F32 = 0, KZ_F64 = 1, KZ_F16 = 2, KZ_BF16 = 3 };
 /* metrics of the exact backend; minkowski(p=2) == euclidean (sklearn_nearest_neighbors.py:51-65).  0 .. 2 run the fused MFMA
  * kernels; 3 .. 5 (the rest of the Minkowski family: manhattan = cityblock = l1, chebyshev, minkowski with any p >= 1 set by
  * kz_matrix_set_minkowski_p) have no inner-product form: a register-tiled VALU kernel computes scikit-learn's generic
@@ -140,7 +143,9 @@ int kz_memcpy_d2d(kz_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);
  * NaN/inf input is an error (KZ_ERR_NONFINITE; scikit-learn rejects those inputs too), and so is a row whose squared norm
  * |x|^2 exceeds 1e30 (|x| <= 1e15: the input limit of the float32 operand images and of the rounding bounds built on the row
  * norms; scikit-learn accepts such rows -- same error code, the message names the limit): reported here for host rows, by
- * the first kz_knn / kz_knn_dual that searches the matrix for device rows (this call then waits for nothing). */
+ * the first kz_knn / kz_knn_dual that searches the matrix for device rows (this call then waits for nothing).
+ * dtype KZ_F16 / KZ_BF16: metrics KZ_EUCLIDEAN, KZ_SQEUCLIDEAN and KZ_COSINE only (every rows_on_device mode); any other metric is
+ * KZ_ERR_UNSUPPORTED before anything is allocated. */
 int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t n, int64_t d, int dtype,
                      int metric, kz_matrix** out);
 /* metric KZ_MINKOWSKI: the exponent p >= 1 (default 2; both matrices of a search must agree). */

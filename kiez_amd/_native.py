@@ -24,6 +24,10 @@ _lib = None
 _lock = threading.Lock()
 
 KZ_F32, KZ_F64 = 0, 1
+KZ_F16, KZ_BF16 = 2, 3   # 2-byte STORAGE types (IEEE binary16, the upper half of a float32): rows read in place, float64 answers
+# element types by name: what DeviceMatrix.elem holds (bfloat16 has no numpy dtype; its rows travel as their uint16 bit patterns)
+ELEM_CODES = {"float32": KZ_F32, "float64": KZ_F64, "float16": KZ_F16, "bfloat16": KZ_BF16}
+HALF_ELEMS = ("float16", "bfloat16")
 KZ_EUCLIDEAN, KZ_SQEUCLIDEAN, KZ_COSINE, KZ_MANHATTAN, KZ_CHEBYSHEV, KZ_MINKOWSKI = 0, 1, 2, 3, 4, 5
 KZ_BRAYCURTIS, KZ_SEUCLIDEAN, KZ_CORRELATION, KZ_HAMMING = 6, 7, 8, 9
 KZ_JACCARD, KZ_DICE, KZ_ROGERSTANIMOTO, KZ_RUSSELLRAO, KZ_SOKALMICHENER, KZ_SOKALSNEATH, KZ_YULE = 10, 11, 12, 13, 14, 15, 16
@@ -35,6 +39,21 @@ METRIC_IDS = {"euclidean": KZ_EUCLIDEAN, "sqeuclidean": KZ_SQEUCLIDEAN, "cosine"
               "rogerstanimoto": KZ_ROGERSTANIMOTO, "russellrao": KZ_RUSSELLRAO, "sokalmichener": KZ_SOKALMICHENER,
               "sokalsneath": KZ_SOKALSNEATH, "yule": KZ_YULE}
 KZ_PRECOMPUTED = 17   # scikit-learn's metric="precomputed": not in METRIC_IDS -- kz_matrix_create refuses it, PrecomputedMatrix makes the handles
+
+
+def half_rows_supported(metric: str) -> bool:
+    """True for the metrics whose matrices take float16 / bfloat16 rows (the fused MFMA kernels: euclidean, sqeuclidean, cosine);
+    kz_matrix_create refuses the 2-byte types for every other metric."""
+    return METRIC_IDS.get(split_metric(metric)[0], KZ_PRECOMPUTED) <= KZ_COSINE
+
+
+def row_storage(metric: str, elem: str) -> str:
+    """The element type rows of type `elem` (a dtype name: 'float16', 'int32', ...) are stored as for `metric`: float32 / float64 as
+    they are; float16 / bfloat16 as they are where the metric takes 2-byte rows; anything else widened -- to float32 for the
+    boolean metrics (they read x != 0 only), else to float64."""
+    if elem in ("float32", "float64") or (elem in HALF_ELEMS and half_rows_supported(metric)):
+        return elem
+    return "float32" if split_metric(metric)[0] in BOOLEAN_METRICS else "float64"
 
 
 def split_metric(metric: str):
@@ -325,11 +344,16 @@ class DeviceMatrix:
     """kz_matrix: an embedding matrix in HBM (exact rows + float64 norms + MFMA operand images: float32 and split-bf16)."""
 
     def __init__(self, ctx: Context, data, metric: str, device_ptr: Optional[int] = None, shape=None, dtype=None,
-                 borrow: bool = False, keepalive=None, rows_only: bool = False, V=None):
+                 borrow: bool = False, keepalive=None, rows_only: bool = False, V=None, elem: Optional[str] = None):
         """`device_ptr` + `borrow=True`: zero-copy -- the matrix reads the caller's HBM buffer in place (kz_matrix_create
         rows_on_device = 2); `keepalive` (the tensor / array that owns it) is held until the matrix is destroyed and must
         not be modified meanwhile (the reference holds its inputs the same way, neighbor_algorithm_base.py:95-96).
-        `V`: metric 'seuclidean', the per-feature variances (kz_matrix_set_seuclidean_v; both matrices of a search need the same)."""
+        `V`: metric 'seuclidean', the per-feature variances (kz_matrix_set_seuclidean_v; both matrices of a search need the same).
+        `elem`: the element type by name (ELEM_CODES) where `dtype` cannot say it: 'bfloat16' rows have no numpy dtype and come as
+        their uint16 bit patterns (host `data` of dtype uint16, or a device pointer).  float16 numpy arrays are uploaded as they
+        are, 2 bytes per element, for the metrics that take 2-byte rows (`half_rows_supported`); for any other metric they are
+        widened to float64 like every other dtype.  `self.elem` is the stored element type, `self.dtype` its numpy dtype (uint16
+        for bfloat16)."""
         self.ctx = ctx
         self.metric = metric
         metric, mink_p = split_metric(metric)
@@ -338,22 +362,35 @@ class DeviceMatrix:
             arr = np.ascontiguousarray(data)
             if arr.ndim != 2:
                 raise ValueError(f"Expected 2D array, got {arr.ndim}D array instead")
-            if arr.dtype not in (np.float32, np.float64):
-                arr = arr.astype(np.float64)
+            if elem == "bfloat16":
+                if arr.dtype != np.uint16:
+                    raise ValueError(f"bfloat16 rows come as their uint16 bit patterns, got {arr.dtype}")
+            elif elem is not None:     # (said by the caller: taken as it is, and the library refuses what it does not take)
+                if elem not in ELEM_CODES or np.dtype(elem) != arr.dtype:
+                    raise ValueError(f"elem={elem!r} does not describe an array of dtype {arr.dtype}")
+            else:
+                elem = row_storage(self.metric, arr.dtype.name)
+                if arr.dtype.name != elem:
+                    arr = arr.astype(elem)
             self.shape = arr.shape
             self.dtype = arr.dtype
+            self.elem = elem
             _check(ctx.lib.kz_matrix_create(ctx.handle, arr.ctypes.data_as(_P), 0, arr.shape[0], arr.shape[1],
-                                            KZ_F32 if arr.dtype == np.float32 else KZ_F64, METRIC_IDS[metric], C.byref(h)),
+                                            ELEM_CODES[elem], METRIC_IDS[metric], C.byref(h)),
                    "kz_matrix_create")
         else:
             self.shape = tuple(shape)
-            self.dtype = np.dtype(dtype)
+            self.dtype = np.dtype(np.uint16 if elem == "bfloat16" else (dtype if dtype is not None else elem))
+            self.elem = elem if elem is not None else self.dtype.name
+            if self.elem not in ELEM_CODES or (self.elem != "bfloat16" and np.dtype(self.elem) != self.dtype):
+                raise ValueError(f"device rows must be float32, float64, float16 or bfloat16 (elem='bfloat16'), got dtype={dtype!r} elem={elem!r}")
             self._keepalive = keepalive if borrow else None
+            self.rows_ptr = int(device_ptr) if borrow else None   # borrowed rows: the caller's buffer, read in place
             if rows_only and not borrow:
                 raise ValueError("rows_only needs a borrowed device buffer")
             # (rows_only: kz_matrix_create rows_on_device = 3 -- a row source for kz_dsl_fit, nothing computed, not searchable)
             _check(ctx.lib.kz_matrix_create(ctx.handle, _P(device_ptr), (3 if rows_only else 2) if borrow else 1, self.shape[0], self.shape[1],
-                                            KZ_F32 if self.dtype == np.float32 else KZ_F64, METRIC_IDS[metric], C.byref(h)),
+                                            ELEM_CODES[self.elem], METRIC_IDS[metric], C.byref(h)),
                    "kz_matrix_create")
         self.handle = h
         if mink_p is not None:
@@ -362,6 +399,7 @@ class DeviceMatrix:
             v = np.ascontiguousarray(V, dtype=np.float64)
             _check(ctx.lib.kz_matrix_set_seuclidean_v(h, v.ctypes.data_as(_P), v.shape[0]), "kz_matrix_set_seuclidean_v")
 
+    rows_ptr = None   # borrowed rows only: the address of the caller's buffer the matrix reads in place
     view = None   # a view of a precomputed distance matrix: "rows" or "columns" (DeviceMatrix.precomputed); None: an embedding matrix
 
     @classmethod
@@ -393,6 +431,7 @@ class DeviceMatrix:
         for handle, view, shp in ((rows_h, "rows", (shape[0], shape[1])), (cols_h, "columns", (shape[1], shape[0]))):
             m = cls.__new__(cls)
             m.ctx, m.metric, m.shape, m.dtype, m.handle, m.view = ctx, "precomputed", shp, np.dtype(dtype), handle, view
+            m.elem = m.dtype.name
             m._keepalive = keepalive if (device_ptr is not None and borrow) else None
             views.append(m)
         return views[0], views[1]

@@ -38,10 +38,17 @@ int kz_bool_image(kz_matrix* m) {
         return KZ_ERR_NOMEM;
     }
     const dim3 grid((unsigned)((m->n + 3) / 4));
-    if (m->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_bool_pack_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)m->raw, m->n, (int)m->d, W, m->bits, m->bits_cnt);
-    else
-        hipLaunchKernelGGL(kz_bool_pack_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double*)m->raw, m->n, (int)m->d, W, m->bits, m->bits_cnt);
+    const int rcd = kz_dispatch_rows(m->dtype, "kz_matrix_create", [&](auto el) {
+        using T = typename decltype(el)::type;
+        if constexpr (kz_half_rows<T>) {   // (kz_matrix_create refuses the pair before it comes here)
+            kz_set_error("kz_matrix_create: the boolean metrics take float32 / float64 rows");
+            return (int)KZ_ERR_UNSUPPORTED;
+        } else {
+            hipLaunchKernelGGL(kz_bool_pack_kernel<T>, grid, dim3(256), 0, ctx->stream, (const T*)m->raw, m->n, (int)m->d, W, m->bits, m->bits_cnt);
+            return (int)KZ_OK;
+        }
+    });
+    if (rcd != KZ_OK) return rcd;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         kz_set_error("kz_matrix_create: bit-pack kernel failed: %s", hipGetErrorString(e));

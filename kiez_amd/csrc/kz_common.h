@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 #include "../../include/kiez_amd.h"
 #include "kz_pool_buf.h"
@@ -231,6 +232,77 @@ using KzMatrixPtr = std::unique_ptr<kz_matrix, KzMatrixDestroy>;
 // what kz_norms_kernel's flag means (KZ_ERR_NONFINITE): a NaN, an infinity, or a row whose squared norm exceeds the input limit
 #define KZ_MSG_NONFINITE "kz_matrix_create: input contains NaN, infinity or a row with |x|^2 > 1e30 (the input limit: squared row norms up to 1e30)"
 
+// ---------------------------------------------------------------------------------------------------
+// Element types of the raw rows.  float and double are themselves; the two 2-byte STORAGE types (KZ_F16, KZ_BF16) are a bit
+// pattern that widens exactly to double wherever a kernel reads `(double)row[k]`: a half matrix behaves like the KZ_F64 matrix
+// of the widened values, bit for bit.  They have no arithmetic of their own.
+// ---------------------------------------------------------------------------------------------------
+struct kz_f16 {
+    unsigned short bits;
+    __device__ __forceinline__ operator double() const { return (double)__builtin_bit_cast(_Float16, bits); }
+};
+struct kz_bf16 {
+    unsigned short bits;
+    __device__ __forceinline__ operator double() const { return (double)__uint_as_float((unsigned)bits << 16); }
+};
+// scikit-learn's float32 conventions (ArgKmin32, the float32 DistanceMetric) apply to float32 rows ONLY; every other element type
+// is on the float64 side.  (Asked by type, never by sizeof: "not 4 bytes" no longer means "8 bytes".)
+template <typename T>
+constexpr bool kz_f32_rows = std::is_same<T, float>::value;
+template <typename T>
+constexpr bool kz_half_rows = std::is_same<T, kz_f16>::value || std::is_same<T, kz_bf16>::value;
+
+// bytes per element of a dtype code (0: not an element type)
+static inline size_t kz_elem_size(int dtype) {
+    switch (dtype) {
+        case KZ_F32: return 4;
+        case KZ_F64: return 8;
+        case KZ_F16:
+        case KZ_BF16: return 2;
+        default: return 0;
+    }
+}
+static inline bool kz_dtype_is_half(int dtype) { return dtype == KZ_F16 || dtype == KZ_BF16; }
+static inline const char* kz_dtype_name(int dtype) {
+    switch (dtype) {
+        case KZ_F32: return "KZ_F32";
+        case KZ_F64: return "KZ_F64";
+        case KZ_F16: return "KZ_F16";
+        case KZ_BF16: return "KZ_BF16";
+        default: return "an unknown element type";
+    }
+}
+
+// THE dispatch on a matrix' element type: f(KzElem<T>()) with the row type T of `dtype`, KZ_ERR_UNSUPPORTED for a code that is none
+// of the four (nothing is launched: no unknown type is ever read as doubles).  f returns an int status (launch errors stay the
+// caller's hipGetLastError).
+template <typename T>
+struct KzElem {
+    using type = T;
+};
+template <typename F>
+static inline int kz_dispatch_rows(int dtype, const char* who, F&& f) {
+    switch (dtype) {
+        case KZ_F32: return f(KzElem<float>());
+        case KZ_F64: return f(KzElem<double>());
+        case KZ_F16: return f(KzElem<kz_f16>());
+        case KZ_BF16: return f(KzElem<kz_bf16>());
+        default: kz_set_error("%s: unsupported element type %d", who, dtype); return KZ_ERR_UNSUPPORTED;
+    }
+}
+// The same for kernels that never read raw rows and take T only for the OUTPUT convention (or work on the float64 value matrix):
+// float for float32 rows, double -- the float64 semantics -- for float64 and both half types.
+template <typename F>
+static inline int kz_dispatch_values(int dtype, const char* who, F&& f) {
+    switch (dtype) {
+        case KZ_F32: return f(KzElem<float>());
+        case KZ_F64:
+        case KZ_F16:
+        case KZ_BF16: return f(KzElem<double>());
+        default: kz_set_error("%s: unsupported element type %d", who, dtype); return KZ_ERR_UNSUPPORTED;
+    }
+}
+
 int kz_scratch(kz_ctx* ctx, size_t bytes, void** out);
 int kz_floor_buf(kz_ctx* ctx, size_t bytes, float** out);
 
@@ -250,13 +322,30 @@ __device__ __forceinline__ double kz_wave_sum(double acc) {
 // 4l .. 4l+3 (one 16-byte load for float32 rows), accumulated in increasing k by an fma chain per lane; then the butterfly
 // sum.  kz_row4 fetches a lane's four elements of a chunk (vector load when the row allows it, scalar loads with zero fill
 // at the tail: the fma of a zero leaves the chain unchanged, so both paths give identical bits).
+// The four elements one vector load of a lane brought in (KzRowFrag<T>: 16 bytes of float32, 8 bytes of a 2-byte type), in float64
+template <typename T>
+using KzRowFrag = typename std::conditional<kz_half_rows<T>, uint2, float4>::type;
+template <typename T, typename F>
+__device__ __forceinline__ void kz_frag4(const F& v, double (&out)[4]) {
+    if constexpr (kz_half_rows<T>) {
+        const T e0 = {(unsigned short)(v.x & 0xffffu)}, e1 = {(unsigned short)(v.x >> 16)};
+        const T e2 = {(unsigned short)(v.y & 0xffffu)}, e3 = {(unsigned short)(v.y >> 16)};
+        out[0] = (double)e0; out[1] = (double)e1; out[2] = (double)e2; out[3] = (double)e3;
+    } else {
+        out[0] = (double)v.x; out[1] = (double)v.y; out[2] = (double)v.z; out[3] = (double)v.w;
+    }
+}
 template <typename T>
 __device__ __forceinline__ void kz_row4(const T* __restrict__ row, int k0, int d, bool vec, double (&out)[4]) {
     if (vec && k0 + 3 < d) {
-        if (sizeof(T) == 4) {
+        if constexpr (kz_f32_rows<T>) {
             const float4 v = *reinterpret_cast<const float4*>(row + k0);
             out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+        } else if constexpr (kz_half_rows<T>) {
+            // 2-byte elements: ONE 8-byte load of the lane's four elements, widened exactly as the scalar path widens them
+            kz_frag4<T>(*reinterpret_cast<const uint2*>(row + k0), out);
         } else {
+            static_assert(std::is_same<T, double>::value, "kz_row4: float, double, kz_f16 or kz_bf16 rows");
             const double2 v0 = *reinterpret_cast<const double2*>(row + k0), v1 = *reinterpret_cast<const double2*>(row + k0 + 2);
             out[0] = v0.x; out[1] = v0.y; out[2] = v1.x; out[3] = v1.y;
         }
@@ -265,10 +354,12 @@ __device__ __forceinline__ void kz_row4(const T* __restrict__ row, int k0, int d
         for (int u = 0; u < 4; ++u) out[u] = k0 + u < d ? (double)row[k0 + u] : 0.0;
     }
 }
-// a row may be read with 16-byte loads when its start and its pitch are 16-byte aligned
+// a row may be read with kz_row4's vector loads when its start and its pitch are aligned to them: 16 bytes (float32, float64), 8 bytes
+// for the 2-byte types, whose four elements are one 8-byte load
 template <typename T>
 __device__ __forceinline__ bool kz_row_vec_ok(const T* base, int d) {
-    return ((reinterpret_cast<uintptr_t>(base) | ((uintptr_t)d * sizeof(T))) & 15u) == 0;
+    constexpr uintptr_t mask = kz_half_rows<T> ? 7u : 15u;
+    return ((reinterpret_cast<uintptr_t>(base) | ((uintptr_t)d * sizeof(T))) & mask) == 0;
 }
 
 template <typename T>
@@ -417,7 +508,7 @@ template <typename T, int METRIC>
 __device__ __forceinline__ double kz_family_finish(double a, double b, int d, double tail, double nx, double ny) {
     if constexpr (METRIC == KZ_BRAYCURTIS) {
         const double v = b != 0.0 ? a / b : 0.0;
-        return sizeof(T) == 4 ? (double)(float)v : v;
+        return kz_f32_rows<T> ? (double)(float)v : v;
     } else if constexpr (METRIC == KZ_CORRELATION) {
         double s = a + b;
         if (d & 1) s += tail;
@@ -428,7 +519,7 @@ __device__ __forceinline__ double kz_family_finish(double a, double b, int d, do
     } else if constexpr (METRIC == KZ_HAMMING) {
         return a / (double)d;
     } else {
-        return sizeof(T) == 4 ? (double)(float)a : a;
+        return kz_f32_rows<T> ? (double)(float)a : a;
     }
 }
 // per-search state of the metrics beyond the Minkowski family, for one pair: V (seuclidean), the (mean, centred norm) of both rows
@@ -458,7 +549,7 @@ __device__ __forceinline__ double kz_family_value_seq_m(const T* __restrict__ a,
 template <typename T>
 __device__ __forceinline__ double kz_family_value_seq(const T* __restrict__ a, const T* __restrict__ b, int d, int metric, double p,
                                                       const kz_family_pair_args& ex = {nullptr, nullptr, nullptr}) {
-    const int p_int = kz_family_p_int(metric, p, sizeof(T) == 4);
+    const int p_int = kz_family_p_int(metric, p, kz_f32_rows<T>);
     if (metric == KZ_MANHATTAN) return kz_family_value_seq_m<T, KZ_MANHATTAN>(a, b, d, p, p_int, ex);
     if (metric == KZ_CHEBYSHEV) return kz_family_value_seq_m<T, KZ_CHEBYSHEV>(a, b, d, p, p_int, ex);
     if (metric == KZ_BRAYCURTIS) return kz_family_value_seq_m<T, KZ_BRAYCURTIS>(a, b, d, p, p_int, ex);
@@ -480,7 +571,10 @@ template <typename T>
 __device__ __forceinline__ double kz_exact_value(const T* q, const T* y, double qs, double ys, int d, int metric, int lane, double p = 2.0) {
     // (every lane the whole pair: no fused kernel ranks by this metric.  Metrics 6 .. 9 never come here -- their per-search state
     //  travels in kz_family_pair_args: the tiled kernel and kz_pair_values call kz_family_value_seq themselves)
-    if (metric >= KZ_MANHATTAN) return kz_family_value_seq<T>(q, y, d, metric, p);
+    //  (the 2-byte storage types exist for metrics 0 .. 2 only, kz_matrix_create: they have no arithmetic for the family's differences)
+    if constexpr (!kz_half_rows<T>) {
+        if (metric >= KZ_MANHATTAN) return kz_family_value_seq<T>(q, y, d, metric, p);
+    }
     if (metric == KZ_COSINE) {
         const double sim = kz_wave_dot_normalized(q, qs, y, ys, d, lane);
         double v = 1.0 - sim;  // sklearn cosine_distances: S *= -1; S += 1; clip(0, 2)

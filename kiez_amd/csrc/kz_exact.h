@@ -437,9 +437,9 @@ __global__ __launch_bounds__(256) void kz_family_dist_kernel(const int* __restri
 template <typename T>
 static void kz_launch_family_dist(kz_ctx* ctx, const int* fl, int b0, int nb, int64_t cq_begin, const kz_matrix* query, const kz_matrix* index,
                                   double* vals) {
-    constexpr int DK = sizeof(T) == 4 ? 32 : 16;
+    constexpr int DK = kz_f32_rows<T> ? 32 : 16;
     const dim3 grid((unsigned)((index->n + 63) / 64), (unsigned)((nb + 63) / 64));
-    const int p_int = kz_family_p_int(index->metric, index->mink_p, sizeof(T) == 4);
+    const int p_int = kz_family_p_int(index->metric, index->mink_p, kz_f32_rows<T>);
 #define KZ_FAMILY_LAUNCH_DK(M, C, DKM)                                                                                                    \
     hipLaunchKernelGGL((kz_family_dist_kernel<T, M, DKM, C>), grid, dim3(256), 0, ctx->stream, fl, b0, nb, cq_begin, (const T*)query->raw, \
                        (const T*)index->raw, index->n, (int)index->d, index->mink_p, p_int, vals, index->seu_v, query->corr, index->corr)
@@ -860,21 +860,27 @@ static int kz_exact_distances(kz_ctx* ctx, const int* fl, int b0, int nb, int64_
     } else if (kz_is_bool_metric(metric))
         kz_bool_launch_dist(ctx, fl, b0, nb, q_begin, query, index, vals);
     else if (no_gemm_form) {
-        if (f32)
-            kz_launch_family_dist<float>(ctx, fl, b0, nb, q_begin, query, index, vals);
-        else
-            kz_launch_family_dist<double>(ctx, fl, b0, nb, q_begin, query, index, vals);
+        return kz_dispatch_rows(index->dtype, "kz_knn", [&](auto e) {
+            using T = typename decltype(e)::type;
+            if constexpr (kz_half_rows<T>) {   // (kz_matrix_create refuses the pair: the family's differences are taken in float32 / float64)
+                kz_set_error("kz_knn: metric %d is not supported for %s rows", metric, kz_dtype_name(index->dtype));
+                return (int)KZ_ERR_UNSUPPORTED;
+            } else {
+                kz_launch_family_dist<T>(ctx, fl, b0, nb, q_begin, query, index, vals);
+                return (int)KZ_OK;
+            }
+        });
     } else if (f32 && ctx->exact_rows && kz_launch_exact_rows(ctx, fl, b0, nb, q_begin, query, index, metric, vals, ln.dyn_n, ln.rows_per_wave)) {
     } else {
         int64_t blocks = (index->n + 3) / 4;
         if (ln.pair_blocks_max > 0 && blocks > ln.pair_blocks_max) blocks = ln.pair_blocks_max;
         const dim3 grid((unsigned)blocks, (unsigned)nb);
-        if (f32)
-            hipLaunchKernelGGL(kz_exact_dist_kernel<float>, grid, dim3(256), 0, ctx->stream, fl, b0, q_begin, (const float*)query->raw,
-                               (const float*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric, index->mink_p, vals, ln.dyn_n);
-        else
-            hipLaunchKernelGGL(kz_exact_dist_kernel<double>, grid, dim3(256), 0, ctx->stream, fl, b0, q_begin, (const double*)query->raw,
-                               (const double*)index->raw, query->sqn, index->sqn, index->n, (int)index->d, metric, index->mink_p, vals, ln.dyn_n);
+        return kz_dispatch_rows(index->dtype, "kz_knn", [&](auto e) {
+            using T = typename decltype(e)::type;
+            hipLaunchKernelGGL(kz_exact_dist_kernel<T>, grid, dim3(256), 0, ctx->stream, fl, b0, q_begin, (const T*)query->raw, (const T*)index->raw,
+                               query->sqn, index->sqn, index->n, (int)index->d, metric, index->mink_p, vals, ln.dyn_n);
+            return (int)KZ_OK;
+        });
     }
     return KZ_OK;
 }
@@ -893,7 +899,7 @@ static int kz_exact_selection(const kz_matrix* index, int k_eff, int two_level_f
     sel->k_sel = (int)(k_eff < index->n ? k_eff : index->n);
     sel->n_chunks = (int)((index->n + KZ_EXACT_CHUNK - 1) / KZ_EXACT_CHUNK);
     sel->two_level = sel->n_chunks >= two_level_from && sel->k_sel <= KZ_EXACT_CHUNK;
-    return index->dtype == KZ_F32 ? kz_exact_select_lds<float>(sel->k_sel, &sel->lds) : kz_exact_select_lds<double>(sel->k_sel, &sel->lds);
+    return kz_dispatch_values(index->dtype, "kz_knn", [&](auto e) { return kz_exact_select_lds<typename decltype(e)::type>(sel->k_sel, &sel->lds); });
 }
 // The k best of every row of vals [nb][index->n] (kz_exact_distances), written to rows q_begin + fl[b0 + b] of out_dist / out_ind as
 // every route writes them.  cand_v / cand_i [sel.cand_entries(nb)]: the survivors of the first level (unused on one level).
@@ -906,12 +912,13 @@ static void kz_exact_select(kz_ctx* ctx, const KzExactSelection& sel, const int*
     const double* sel_v = sel.two_level ? (const double*)cand_v : vals;
     const int* sel_i = sel.two_level ? (const int*)cand_i : (const int*)nullptr;
     const int64_t n_entries = sel.two_level ? (int64_t)sel.n_chunks * sel.k_sel : index->n;
-    if (index->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_exact_select_kernel<float>, dim3(nb), dim3(256), sel.lds, ctx->stream, fl, b0, q_begin, sel_v, sel_i, n_entries,
-                           index->n, k, exclude_self ? 1 : 0, d_self_ids, index->metric, index->mink_p, out_dist, out_ind, dyn_n);
-    else
-        hipLaunchKernelGGL(kz_exact_select_kernel<double>, dim3(nb), dim3(256), sel.lds, ctx->stream, fl, b0, q_begin, sel_v, sel_i, n_entries,
-                           index->n, k, exclude_self ? 1 : 0, d_self_ids, index->metric, index->mink_p, out_dist, out_ind, dyn_n);
+    // (an element type that is none of the four never comes here: kz_exact_selection, which made `sel`, has refused it)
+    (void)kz_dispatch_values(index->dtype, "kz_knn", [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(kz_exact_select_kernel<T>, dim3(nb), dim3(256), sel.lds, ctx->stream, fl, b0, q_begin, sel_v, sel_i, n_entries, index->n,
+                           k, exclude_self ? 1 : 0, d_self_ids, index->metric, index->mink_p, out_dist, out_ind, dyn_n);
+        return (int)KZ_OK;
+    });
 }
 
 // The begin of a walk over n_rows listed rows against the whole index.  Many rows of a cosine search: the normalised float64 index rows,

@@ -200,11 +200,13 @@ template <int V>
 using KzRankC = std::integral_constant<int, V>;
 template <typename F>
 static void kz_rank_dispatch_distance(const kz_matrix* index, F by_kind) {
+    // (these kernels read the float64 value matrix: T is the output convention -- float for float32 rows, double for float64 and the
+    //  2-byte types; an element type that is none of the four launches nothing, and kz_matrix_create never made such a matrix)
     auto by_dtype = [&](auto metric) {
-        if (index->dtype == KZ_F32)
-            by_kind(KzRankT<float>(), metric);
-        else
-            by_kind(KzRankT<double>(), metric);
+        (void)kz_dispatch_values(index->dtype, "kz_gold_ranks", [&](auto e) {
+            by_kind(KzRankT<typename decltype(e)::type>(), metric);
+            return (int)KZ_OK;
+        });
     };
     switch (kz_rank_out_metric(index->metric)) {
         case KZ_EUCLIDEAN: by_dtype(KzRankC<KZ_EUCLIDEAN>()); break;

@@ -620,12 +620,13 @@ int kz_dsl_fit(kz_ctx* ctx, const int64_t* d_ind_t2s, int64_t n_rows, int Kt, co
     KZ_REQUIRE(n_rows >= 0 && t_begin >= 0 && t_begin + n_rows <= target->n && Kt >= 1, "kz_dsl_fit: bad row range");
     KZ_HIP(hipSetDevice(ctx->device));
     if (n_rows == 0) return KZ_OK;
-    if (source->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_dsl_fit_kernel<float>, kz_grid1d(n_rows, 4), dim3(256), 0, ctx->stream, d_ind_t2s, n_rows, Kt,
-                           (const float*)source->raw, (const float*)target->raw, t_begin, (int)source->d, d_t2c);
-    else
-        hipLaunchKernelGGL(kz_dsl_fit_kernel<double>, kz_grid1d(n_rows, 4), dim3(256), 0, ctx->stream, d_ind_t2s, n_rows, Kt,
-                           (const double*)source->raw, (const double*)target->raw, t_begin, (int)source->d, d_t2c);
+    const int rcd = kz_dispatch_rows(source->dtype, "kz_dsl_fit", [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(kz_dsl_fit_kernel<T>, kz_grid1d(n_rows, 4), dim3(256), 0, ctx->stream, d_ind_t2s, n_rows, Kt, (const T*)source->raw,
+                           (const T*)target->raw, t_begin, (int)source->d, d_t2c);
+        return (int)KZ_OK;
+    });
+    if (rcd != KZ_OK) return rcd;
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }
@@ -638,12 +639,13 @@ int kz_dsl_transform(kz_ctx* ctx, const int64_t* d_ind, int64_t n, int K, const 
     KZ_REFUSE_PRECOMPUTED("kz_dsl_transform", target);
     KZ_REQUIRE(query->d == target->d && query->dtype == target->dtype, "kz_dsl_transform: query/target mismatch");
     KZ_REQUIRE(q_begin >= 0 && q_begin + n <= query->n, "kz_dsl_transform: bad row range");
-    if (query->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_dsl_transform_kernel<float>, kz_grid1d(n, 4), dim3(256), 0, ctx->stream, d_ind, n, K,
-                           (const float*)query->raw, q_begin, (const float*)target->raw, (int)query->d, d_t2c, d_out, d_min);
-    else
-        hipLaunchKernelGGL(kz_dsl_transform_kernel<double>, kz_grid1d(n, 4), dim3(256), 0, ctx->stream, d_ind, n, K,
-                           (const double*)query->raw, q_begin, (const double*)target->raw, (int)query->d, d_t2c, d_out, d_min);
+    const int rcd = kz_dispatch_rows(query->dtype, "kz_dsl_transform", [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(kz_dsl_transform_kernel<T>, kz_grid1d(n, 4), dim3(256), 0, ctx->stream, d_ind, n, K, (const T*)query->raw, q_begin,
+                           (const T*)target->raw, (int)query->d, d_t2c, d_out, d_min);
+        return (int)KZ_OK;
+    });
+    if (rcd != KZ_OK) return rcd;
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }

@@ -268,7 +268,14 @@ __global__ __launch_bounds__(256) void kz_gather_rows_kernel(const char* __restr
     const int64_t src = row0 + rows[r];
     const char* sp = raw + src * row_bytes;
     char* dp = out + (int64_t)r * row_bytes;
-    for (int64_t b = threadIdx.x * 4; b < row_bytes; b += 256 * 4) *reinterpret_cast<int*>(dp + b) = *reinterpret_cast<const int*>(sp + b);
+    // (float32 / float64 rows, and 2-byte rows of an even width on a 4-byte aligned base: 4 bytes per thread.  2-byte rows of an odd
+    //  width -- every other row starts 2 bytes off, and the last 4-byte copy would run 2 bytes past the row: 2 bytes per thread)
+    if (((row_bytes | (int64_t)reinterpret_cast<uintptr_t>(raw) | (int64_t)reinterpret_cast<uintptr_t>(out)) & 3) == 0) {
+        for (int64_t b = threadIdx.x * 4; b < row_bytes; b += 256 * 4) *reinterpret_cast<int*>(dp + b) = *reinterpret_cast<const int*>(sp + b);
+    } else {
+        for (int64_t b = threadIdx.x * 2; b < row_bytes; b += 256 * 2)
+            *reinterpret_cast<unsigned short*>(dp + b) = *reinterpret_cast<const unsigned short*>(sp + b);
+    }
     // index row to strip for this query: its own row, or (subset of a subset) what its parent recorded for it
     if (self_ids && threadIdx.x == 0) self_ids[r] = parent_self ? parent_self[src] : src;
 }
@@ -709,7 +716,7 @@ static int kz_escalate_rows(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, con
                             int64_t* out_ind, kz_knn_stats* st2, float* ms_out, const int* out_rows = nullptr) {
     // (out_rows: where the results of row i of the list go -- row out_rows[i] of out_dist / out_ind instead of the row's own place)
     KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-    const size_t row_bytes = (size_t)query->d * (query->dtype == KZ_F32 ? 4 : 8);
+    const size_t row_bytes = (size_t)query->d * kz_elem_size(query->dtype);
     // (released when the function returns: qsub, fl, sub_raw, sub_self, sub_dist, sub_ind)
     KzPoolBuf<int64_t> sub_ind;
     KzPoolBuf<double> sub_dist;

@@ -63,16 +63,16 @@ template <typename T>
 __device__ __forceinline__ double kz_output_distance(double v, int metric, double p = 2.0) {
     // (Minkowski family: the ranking value is the reduced distance; scikit-learn converts at the end,
     //  MinkowskiDistance._rdist_to_dist: rdist ** (1 / p), rounded to the input dtype -- measured on scikit-learn 1.7.2)
-    if (metric == KZ_MINKOWSKI) return sizeof(T) == 4 ? (double)(float)pow(v, 1.0 / p) : pow(v, 1.0 / p);
+    if (metric == KZ_MINKOWSKI) return kz_f32_rows<T> ? (double)(float)pow(v, 1.0 / p) : pow(v, 1.0 / p);
     // (seuclidean: SEuclideanDistance._rdist_to_dist, sqrt of the ranking value -- already rounded to the input dtype -- rounded
     //  again; correlation: the constant row's NaN, ranked as +inf (kz_family_finish), is NaN again)
-    if (metric == KZ_SEUCLIDEAN) return sizeof(T) == 4 ? (double)(float)sqrt(v) : sqrt(v);
+    if (metric == KZ_SEUCLIDEAN) return kz_f32_rows<T> ? (double)(float)sqrt(v) : sqrt(v);
     if ((metric == KZ_CORRELATION || metric == KZ_DICE || metric == KZ_SOKALSNEATH) && v == INFINITY) return NAN;   // (dice, sokalsneath: kz_bool.h)
     if (metric == KZ_EUCLIDEAN) {
         // ArgKmin32 converts the surrogate with the float32 metric object: (double)sqrtf((float)d2)
         // (_argkmin.pyx.tp:285-295 with INPUT_DTYPE_t = float32); ArgKmin64 uses sqrt in float64.
         // exactly what sklearn executes: float32 argument, double sqrt, result rounded back to float32
-        if (sizeof(T) == 4) return (double)(float)sqrt((double)(float)v);
+        if (kz_f32_rows<T>) return (double)(float)sqrt((double)(float)v);
         return sqrt(v);
     }
     return v;
@@ -551,9 +551,11 @@ __device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const i
 #ifdef KZ_NO_FIN_PIPE
     if (false) {
 #else
-    if (sizeof(T) == 4 && vec && p.d <= 256 * NV && Vr > 0) {
+    if ((kz_f32_rows<T> || kz_half_rows<T>) && vec && p.d <= 256 * NV && Vr > 0) {
 #endif   // (Vr == 0: a reverse-direction row without a single event)
-        // float32 rows of up to 256 NV elements (NV 16-byte loads per lane and row): the loads of the NEXT group of FROWS
+        // float32 rows of up to 256 NV elements (NV 16-byte loads per lane and row) and float16 / bfloat16 rows of as many (8-byte
+        // loads, widened in the reduce step as kz_row4 widens them; the generic loop below has no load in flight under the sums and
+        // is a quarter slower on such rows, profiles/half_inputs.md): the loads of the NEXT group of FROWS
         // candidates are issued before the current group's fma chains and butterfly sums -- same arithmetic in the same order
         // as the generic loop below (and as kz_wave_dot), only the memory latency of group g+1 hides under the sums of group g
         const int k0 = 4 * lane;
@@ -575,7 +577,8 @@ __device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const i
 #pragma unroll
             for (int e = 0; e < 4; ++e) qk[4 * c + e] = t[e];
         }
-        auto issue = [&](int c0, float4 (&buf)[FROWS][NV], double (&ysb)[FROWS]) {
+        using Frag = KzRowFrag<T>;
+        auto issue = [&](int c0, Frag (&buf)[FROWS][NV], double (&ysb)[FROWS]) {
 #pragma unroll
             for (int u = 0; u < FROWS; ++u) {
                 // (no branch around a load, and no load under a condition: with loads on some paths only the compiler waits for
@@ -587,10 +590,10 @@ __device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const i
                 ysb[u] = p.ysqn[yi];
 #pragma unroll
                 for (int c = 0; c < NV; ++c)
-                    buf[u][c] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(yraw) + (int64_t)yi * p.d + k0r[c]);
+                    buf[u][c] = *reinterpret_cast<const Frag*>(yraw + (int64_t)yi * p.d + k0r[c]);
             }
         };
-        auto reduce = [&](int c0, const float4 (&buf)[FROWS][NV], const double (&ysb)[FROWS]) {
+        auto reduce = [&](int c0, const Frag (&buf)[FROWS][NV], const double (&ysb)[FROWS]) {
 #pragma unroll
             for (int u = 0; u < FROWS; ++u) {
                 double a = 0.0;
@@ -601,7 +604,8 @@ __device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const i
                     if ((rcp_hi & 0x7ff00000) != 0x7ff00000) {
 #pragma unroll
                         for (int c = 0; c < NV; ++c) {
-                            const double yk[4] = {(double)buf[u][c].x, (double)buf[u][c].y, (double)buf[u][c].z, (double)buf[u][c].w};
+                            double yk[4];
+                            kz_frag4<T>(buf[u][c], yk);
                             if (act[c]) {
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) a = fma(qk[4 * c + e], kz_div_shared(yk[e], ysb[u], rcp), a);
@@ -613,7 +617,8 @@ __device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const i
                 if (!done) {
 #pragma unroll
                     for (int c = 0; c < NV; ++c) {
-                        const double yk[4] = {(double)buf[u][c].x, (double)buf[u][c].y, (double)buf[u][c].z, (double)buf[u][c].w};
+                        double yk[4];
+                        kz_frag4<T>(buf[u][c], yk);
                         if (act[c]) {
                             if (p.metric == KZ_COSINE) {
 #pragma unroll
@@ -639,7 +644,7 @@ __device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const i
         // three groups in flight (a rotating set of three register buffers, the loop unrolled by three: no copies): the gathers
         // of groups g + 1 and g + 2 are under way while group g is reduced
         constexpr int R = FROWS;
-        float4 b0[R][NV], b1[R][NV], b2[R][NV];
+        Frag b0[R][NV], b1[R][NV], b2[R][NV];
         double y0[R], y1[R], y2[R];
         issue(0, b0, y0);
         issue(R, b1, y1);
@@ -655,7 +660,7 @@ __device__ __forceinline__ void kz_finalize_query(const KnnFinParams& p, const i
             if ((c0 += R) >= Vr) break;
         }
 #else
-        float4 cur[FROWS][NV], nxt[FROWS][NV];
+        Frag cur[FROWS][NV], nxt[FROWS][NV];
         double ys_c[FROWS], ys_n[FROWS];
         issue(0, cur, ys_c);
         for (int c0 = 0; c0 < Vr; c0 += 2 * FROWS) {   // (unrolled by two: the buffers swap roles, no copies)
@@ -840,6 +845,38 @@ static int kz_launch_finalize(kz_ctx* ctx, KnnFinParams& fp, const KzListLayout&
     int big = 0;
     for (int g = 1; g < n_groups; ++g)
         if (groups[g].hi - groups[g].lo > groups[big].hi - groups[big].lo) big = g;
+    const bool wide = (fp.KSEL > 0 ? fp.KSEL : KP) > 160;   // the long-k route
+    // (many selected candidates + float32 rows on the fp16 tier, ordinary direction: kz_knn_fin_wide.h)
+    const bool rows_vec = fp.d <= 256 && (fp.d & 3) == 0 && (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & 15u) == 0;
+    const bool wide2 = wide && dtype == KZ_F32 && fp.tier_h && !fp.excl_floor && rows_vec;
+    // (float32 rows of 260 .. 512 elements, 16-byte aligned -- float16 / bfloat16 rows of as many, 8-byte aligned: the build whose
+    //  pipelined re-rank takes two loads per lane and row)
+    const bool two_chunks = !wide && (dtype == KZ_F32 || kz_dtype_is_half(dtype)) && fp.d > 256 && fp.d <= 512 && (fp.d & 3) == 0 &&
+                            (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & (dtype == KZ_F32 ? 15u : 7u)) == 0;
+    const void* fk = nullptr;   // (the kernel of every launch of this pass: chosen -- and an element type refused -- before the fork)
+    if (dtype != KZ_F32) {
+        // (float64 rows: the generic re-rank loop, whose loads go through kz_row4; the 2-byte types: the pipelined re-rank on
+        //  8-byte loads where the rows allow it -- the kernel decides, as for float32 -- else the generic loop too)
+        const int rcd = kz_dispatch_rows(dtype, "kz_knn", [&](auto e) {
+            using T = typename decltype(e)::type;
+            if constexpr (kz_half_rows<T>) {
+                if (two_chunks) {
+                    fk = (const void*)kz_knn_finalize_kernel<T, KZ_FIN_ROWS, KZ_FIN_WAVES_2, 2>;
+                    return (int)KZ_OK;
+                }
+            }
+            fk = wide ? (const void*)kz_knn_finalize_kernel<T, 4, 2> : (const void*)kz_knn_finalize_kernel<T, KZ_FIN_ROWS, KZ_FIN_WAVES>;
+            return (int)KZ_OK;
+        });
+        if (rcd != KZ_OK) return rcd;
+    } else if (wide2)
+        fk = (const void*)kz_knn_finalize_wide_kernel<float, 4>;
+    else if (wide)
+        fk = (const void*)kz_knn_finalize_kernel<float, 8, 2>;
+    else if (two_chunks)
+        fk = (const void*)kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES_2, 2>;
+    else
+        fk = (const void*)kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES>;
     if (fork) {
         KZ_HIP(hipEventRecord(ctx->ev[7], main_stream));
         KZ_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev[7], 0));
@@ -855,24 +892,6 @@ static int kz_launch_finalize(kz_ctx* ctx, KnnFinParams& fp, const KzListLayout&
             fp.fast_div = ctx->fin_fast_div;
             const int fin_blocks = (int)((fp.q_last - fp.q_first + KZ_FIN_QPB - 1) / KZ_FIN_QPB);
             size_t fin_lds = (size_t)4 * kz_fin_wave_bytes(fp.max_m, fp.KSEL > 0 ? fp.KSEL : KP);
-            const bool wide = (fp.KSEL > 0 ? fp.KSEL : KP) > 160;   // the long-k route
-            // (many selected candidates + float32 rows on the fp16 tier, ordinary direction: kz_knn_fin_wide.h)
-            const bool rows_vec = fp.d <= 256 && (fp.d & 3) == 0 && (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & 15u) == 0;
-            const bool wide2 = wide && dtype == KZ_F32 && fp.tier_h && !fp.excl_floor && rows_vec;
-            // (float32 rows of 260 .. 512 elements, 16-byte aligned: the build whose pipelined re-rank takes two loads per lane and row)
-            const bool two_chunks = !wide && dtype == KZ_F32 && fp.d > 256 && fp.d <= 512 && (fp.d & 3) == 0 &&
-                                    (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & 15u) == 0;
-            const void* fk;
-            if (dtype != KZ_F32)
-                fk = wide ? (const void*)kz_knn_finalize_kernel<double, 4, 2> : (const void*)kz_knn_finalize_kernel<double, KZ_FIN_ROWS, KZ_FIN_WAVES>;
-            else if (wide2)
-                fk = (const void*)kz_knn_finalize_wide_kernel<float, 4>;
-            else if (wide)
-                fk = (const void*)kz_knn_finalize_kernel<float, 8, 2>;
-            else if (two_chunks)
-                fk = (const void*)kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES_2, 2>;
-            else
-                fk = (const void*)kz_knn_finalize_kernel<float, KZ_FIN_ROWS, KZ_FIN_WAVES>;
             if (wide2) fin_lds = (size_t)4 * kz_fin_wide_wave_bytes(fp.max_m, fp.KSEL);
             if (fin_lds > 65536) KZ_HIP(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds));
             void* args[] = {&fp};

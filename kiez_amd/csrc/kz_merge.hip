@@ -26,6 +26,7 @@ __global__ __launch_bounds__(256) void kz_pair_values_kernel(const T* __restrict
     const int64_t qrow = q_begin + r;
     const T* q = qraw + qrow * (int64_t)d;
     const double qs = qsqn[qrow];
+    if constexpr (!kz_half_rows<T>)   // (2-byte rows exist for metrics 0 .. 2 only)
     if (metric >= KZ_MANHATTAN) {
         // the Minkowski family: one lane per pair, terms in feature order (kz_common.h: kz_family_value_seq) -- the order of the
         // tiled distance kernel the search ranked by, so that the values that travel between GPUs ARE the search's values
@@ -117,14 +118,16 @@ int kz_pair_values(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t
     const dim3 grid((unsigned)((q_count + 3) / 4));
     if (kz_is_bool_metric(query->metric))
         kz_bool_launch_pair_values(ctx, query, q_begin, q_count, index, d_ind, k, d_val);
-    else if (query->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_pair_values_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)query->raw, query->sqn, q_begin,
-                           q_count, (const float*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val,
-                           index->seu_v, query->corr, index->corr);
-    else
-        hipLaunchKernelGGL(kz_pair_values_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double*)query->raw, query->sqn, q_begin,
-                           q_count, (const double*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val,
-                           index->seu_v, query->corr, index->corr);
+    else {
+        const int rcd = kz_dispatch_rows(query->dtype, "kz_pair_values", [&](auto e) {
+            using T = typename decltype(e)::type;
+            hipLaunchKernelGGL(kz_pair_values_kernel<T>, grid, dim3(256), 0, ctx->stream, (const T*)query->raw, query->sqn, q_begin, q_count,
+                               (const T*)index->raw, index->sqn, index->n, (int)query->d, query->metric, query->mink_p, d_ind, k, d_val,
+                               index->seu_v, query->corr, index->corr);
+            return (int)KZ_OK;
+        });
+        if (rcd != KZ_OK) return rcd;
+    }
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }

@@ -412,12 +412,13 @@ int kz_matrix_image_f32(kz_matrix* m) {
     kz_ctx* ctx = m->ctx;
     const int64_t n_pad = m->n_tiles * KZ_TILE;
     if (kz_pool_alloc(ctx, (size_t)n_pad * (size_t)m->kg * 16, (void**)&m->packed) != KZ_OK) return KZ_ERR_NOMEM;
-    if (m->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_pack_f32_kernel<float>, dim3(kz_pack_blocks(n_pad)), dim3(256), 0, ctx->stream, (const float*)m->raw,
-                           m->sqn, m->n, (int)m->d, m->metric, m->kg, n_pad, m->packed);
-    else
-        hipLaunchKernelGGL(kz_pack_f32_kernel<double>, dim3(kz_pack_blocks(n_pad)), dim3(256), 0, ctx->stream, (const double*)m->raw,
-                           m->sqn, m->n, (int)m->d, m->metric, m->kg, n_pad, m->packed);
+    const int rcd = kz_dispatch_rows(m->dtype, "kz_matrix_image_f32", [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(kz_pack_f32_kernel<T>, dim3(kz_pack_blocks(n_pad)), dim3(256), 0, ctx->stream, (const T*)m->raw, m->sqn, m->n,
+                           (int)m->d, m->metric, m->kg, n_pad, m->packed);
+        return (int)KZ_OK;
+    });
+    if (rcd != KZ_OK) return rcd;
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }
@@ -457,12 +458,13 @@ int kz_matrix_image_bf(kz_matrix* m) {
     kz_ctx* ctx = m->ctx;
     const int64_t n_pad = m->n_tiles * KZ_TILE;
     if (kz_pool_alloc(ctx, (size_t)n_pad * (size_t)m->kg_bf * 16, (void**)&m->packed_bf) != KZ_OK) return KZ_ERR_NOMEM;
-    if (m->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_pack_bf_kernel<float>, dim3(kz_pack_blocks(n_pad)), dim3(256), 0, ctx->stream, (const float*)m->raw,
-                           m->sqn, m->n, (int)m->d, m->metric, m->kg_bf, n_pad, m->packed_bf);
-    else
-        hipLaunchKernelGGL(kz_pack_bf_kernel<double>, dim3(kz_pack_blocks(n_pad)), dim3(256), 0, ctx->stream, (const double*)m->raw,
-                           m->sqn, m->n, (int)m->d, m->metric, m->kg_bf, n_pad, m->packed_bf);
+    const int rcd = kz_dispatch_rows(m->dtype, "kz_matrix_image_bf", [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(kz_pack_bf_kernel<T>, dim3(kz_pack_blocks(n_pad)), dim3(256), 0, ctx->stream, (const T*)m->raw, m->sqn, m->n,
+                           (int)m->d, m->metric, m->kg_bf, n_pad, m->packed_bf);
+        return (int)KZ_OK;
+    });
+    if (rcd != KZ_OK) return rcd;
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }
@@ -505,12 +507,16 @@ static int kz_center_create(kz_ctx* ctx, const kz_matrix* from, kz_center** out)
         return KZ_ERR_NOMEM;
     }
     const int blocks = (int)(from->n < KZ_COLSUM_BLOCKS ? from->n : KZ_COLSUM_BLOCKS);
-    if (from->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_colsum_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, (const float*)from->raw, from->sqn,
-                           from->n, d, from->metric, partial.get());
-    else
-        hipLaunchKernelGGL(kz_colsum_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)from->raw, from->sqn,
-                           from->n, d, from->metric, partial.get());
+    const int rcd = kz_dispatch_rows(from->dtype, "kz_knn", [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(kz_colsum_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, (const T*)from->raw, from->sqn, from->n, d,
+                           from->metric, partial.get());
+        return (int)KZ_OK;
+    });
+    if (rcd != KZ_OK) {
+        kz_center_release(ctx, c);
+        return rcd;
+    }
     hipLaunchKernelGGL(kz_center_finish_kernel, dim3(d_pad), dim3(256), 0, ctx->stream, partial.get(), blocks, from->n, d, from->d_stats,
                        c->d_mu, c->d_scale);
     const hipError_t e = hipGetLastError();
@@ -522,6 +528,19 @@ static int kz_center_create(kz_ctx* ctx, const kz_matrix* from, kz_center** out)
     }
     *out = c;
     return KZ_OK;
+}
+
+// THE launch of kz_pack_h_kernel: n_rows live rows (in the order perm, or the matrix' own) into n_pad image rows; rowq / dmax only for
+// the matrix' own image.  (The launch error is the caller's hipGetLastError.)
+static int kz_launch_pack_h(kz_matrix* m, int64_t n_pad, int64_t n_rows, const kz_center* center, unsigned short* packed, float* bias,
+                            double* rowq, unsigned long long* dmax, const int* perm) {
+    const int nsr = kz_h_nsr(m->kg);
+    return kz_dispatch_rows(m->dtype, "kz_knn", [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL(kz_pack_h_kernel<T>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, m->ctx->stream, (const T*)m->raw, m->sqn, n_rows,
+                           (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, packed, bias, rowq, dmax, perm);
+        return (int)KZ_OK;
+    });
 }
 
 static int kz_himage_build(kz_matrix* m, kz_center* center) {
@@ -543,14 +562,11 @@ static int kz_himage_build(kz_matrix* m, kz_center* center) {
     }
     hipError_t e = hipMemsetAsync(im->d_max, 0, 32, ctx->stream);
     if (e == hipSuccess) {
-        if (m->dtype == KZ_F32)
-            hipLaunchKernelGGL(kz_pack_h_kernel<float>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const float*)m->raw,
-                               m->sqn, m->n, (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, im->packed, im->bias,
-                               im->rowq, (unsigned long long*)im->d_max, nullptr);
-        else
-            hipLaunchKernelGGL(kz_pack_h_kernel<double>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const double*)m->raw,
-                               m->sqn, m->n, (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, im->packed, im->bias,
-                               im->rowq, (unsigned long long*)im->d_max, nullptr);
+        const int rcd = kz_launch_pack_h(m, n_pad, m->n, center, im->packed, im->bias, im->rowq, (unsigned long long*)im->d_max, nullptr);
+        if (rcd != KZ_OK) {
+            kz_himage_free(m);
+            return rcd;
+        }
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
@@ -565,37 +581,21 @@ static int kz_himage_build(kz_matrix* m, kz_center* center) {
 // own centre and scale, into caller-provided buffers: packed [n_tiles][nsr] x 4 KiB (+ the DMA ring's padding), bias
 // [n_tiles * 128].  Bit-identical operands and biases to m's own image, row for row.
 int kz_himage_pack_permuted(kz_matrix* m, const int* d_perm, unsigned short* packed, float* bias) {
-    kz_ctx* ctx = m->ctx;
     KZ_REQUIRE(m->himg, "kz_himage_pack_permuted: the matrix has no fp16 image");
     const kz_center* center = m->himg->center;
-    const int nsr = kz_h_nsr(m->kg);
     const int64_t n_pad = m->n_tiles * KZ_TILE;
-    if (m->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_pack_h_kernel<float>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const float*)m->raw, m->sqn,
-                           m->n, (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, packed, bias, (double*)nullptr,
-                           (unsigned long long*)nullptr, d_perm);
-    else
-        hipLaunchKernelGGL(kz_pack_h_kernel<double>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const double*)m->raw, m->sqn,
-                           m->n, (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, packed, bias, (double*)nullptr,
-                           (unsigned long long*)nullptr, d_perm);
+    const int rcd = kz_launch_pack_h(m, n_pad, m->n, center, packed, bias, nullptr, nullptr, d_perm);
+    if (rcd != KZ_OK) return rcd;
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }
 
 // The same for ANY list of n_rows matrix rows (n_pad image rows, a multiple of 128; rows behind n_rows: zero image, bias -inf).
 int kz_himage_pack_rows(kz_matrix* m, const int* d_rows, int64_t n_rows, int64_t n_pad, unsigned short* packed, float* bias) {
-    kz_ctx* ctx = m->ctx;
     KZ_REQUIRE(m->himg && n_pad % KZ_TILE == 0 && n_rows <= n_pad, "kz_himage_pack_rows: no fp16 image / bad row counts");
     const kz_center* center = m->himg->center;
-    const int nsr = kz_h_nsr(m->kg);
-    if (m->dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_pack_h_kernel<float>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const float*)m->raw, m->sqn,
-                           n_rows, (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, packed, bias, (double*)nullptr,
-                           (unsigned long long*)nullptr, d_rows);
-    else
-        hipLaunchKernelGGL(kz_pack_h_kernel<double>, dim3(kz_rowgroup_blocks(n_pad, 4)), dim3(256), 0, ctx->stream, (const double*)m->raw, m->sqn,
-                           n_rows, (int)m->d, m->metric, nsr, n_pad, center->d_mu, center->d_scale, packed, bias, (double*)nullptr,
-                           (unsigned long long*)nullptr, d_rows);
+    const int rcd = kz_launch_pack_h(m, n_pad, n_rows, center, packed, bias, nullptr, nullptr, d_rows);
+    if (rcd != KZ_OK) return rcd;
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }
@@ -704,8 +704,15 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
     KZ_REQUIRE(n > 0 && d > 0, "kz_matrix_create: empty matrix (n=%lld, d=%lld)", (long long)n, (long long)d);
     KZ_REQUIRE(d <= 65536, "kz_matrix_create: d=%lld too large", (long long)d);
     KZ_REQUIRE(n < ((int64_t)1 << 31) - 256, "kz_matrix_create: n=%lld exceeds the int32 row-id range", (long long)n);
-    KZ_REQUIRE(dtype == KZ_F32 || dtype == KZ_F64, "kz_matrix_create: dtype must be KZ_F32 or KZ_F64");
+    KZ_REQUIRE(kz_elem_size(dtype) != 0, "kz_matrix_create: dtype must be KZ_F32, KZ_F64, KZ_F16 or KZ_BF16");
     KZ_REQUIRE(metric >= KZ_EUCLIDEAN && metric <= KZ_YULE, "kz_matrix_create: unknown metric %d", metric);
+    if (kz_dtype_is_half(dtype) && metric > KZ_COSINE) {
+        // (2-byte rows are a storage type of the fused MFMA kernels' metrics; the per-feature and boolean metrics take their
+        //  differences in the input dtype -- widen on the host for those)
+        kz_set_error("kz_matrix_create: metric %d is not supported for %s rows (2-byte rows: KZ_EUCLIDEAN, KZ_SQEUCLIDEAN, KZ_COSINE)", metric,
+                     kz_dtype_name(dtype));
+        return KZ_ERR_UNSUPPORTED;
+    }
     KZ_REQUIRE(rows_on_device >= 0 && rows_on_device <= 3, "kz_matrix_create: rows_on_device must be 0, 1, 2 or 3");
     KZ_HIP(hipSetDevice(ctx->device));
     kz_matrix* m = new kz_matrix();
@@ -721,7 +728,7 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
     m->kg = (int)(d_pad / 4);
     m->kg_bf = m->kg;
     const int64_t n_pad = m->n_tiles * KZ_TILE;
-    const size_t esz = dtype == KZ_F32 ? 4 : 8;
+    const size_t esz = kz_elem_size(dtype);
     const size_t raw_bytes = (size_t)n * (size_t)d * esz;
     auto fail = [&](int code) {
         kz_matrix_destroy(m);
@@ -758,12 +765,13 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
     }
     auto* st = (unsigned long long*)m->d_stats;
     int* bad = (int*)(m->d_stats + 4);
-    if (dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_norms_kernel<float>, dim3(kz_rowgroup_blocks(n_pad, KZ_NORM_ROWS)), dim3(256), 0, ctx->stream, (const float*)m->raw, n,
-                           (int)d, metric, n_pad, m->bias, m->sqn, st, bad);
-    else
-        hipLaunchKernelGGL(kz_norms_kernel<double>, dim3(kz_rowgroup_blocks(n_pad, KZ_NORM_ROWS)), dim3(256), 0, ctx->stream, (const double*)m->raw, n,
-                           (int)d, metric, n_pad, m->bias, m->sqn, st, bad);
+    const int rcd = kz_dispatch_rows(dtype, "kz_matrix_create", [&](auto el) {
+        using T = typename decltype(el)::type;
+        hipLaunchKernelGGL(kz_norms_kernel<T>, dim3(kz_rowgroup_blocks(n_pad, KZ_NORM_ROWS)), dim3(256), 0, ctx->stream, (const T*)m->raw, n, (int)d,
+                           metric, n_pad, m->bias, m->sqn, st, bad);
+        return (int)KZ_OK;
+    });
+    if (rcd != KZ_OK) return fail(rcd);
     e = hipGetLastError();
     if (e != hipSuccess) {
         kz_set_error("kz_matrix_create: norm kernel failed: %s", hipGetErrorString(e));
@@ -775,10 +783,12 @@ int kz_matrix_create(kz_ctx* ctx, const void* rows, int rows_on_device, int64_t 
             return fail(KZ_ERR_NOMEM);
         }
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (dtype == KZ_F32)
-            hipLaunchKernelGGL(kz_corr_rows_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, (const float*)m->raw, n, (int)d, m->corr);
-        else
-            hipLaunchKernelGGL(kz_corr_rows_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)m->raw, n, (int)d, m->corr);
+        const int rcc = kz_dispatch_rows(dtype, "kz_matrix_create", [&](auto el) {
+            using T = typename decltype(el)::type;
+            hipLaunchKernelGGL(kz_corr_rows_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, (const T*)m->raw, n, (int)d, m->corr);
+            return (int)KZ_OK;
+        });
+        if (rcc != KZ_OK) return fail(rcc);
         e = hipGetLastError();
         if (e != hipSuccess) {
             kz_set_error("kz_matrix_create: correlation row kernel failed: %s", hipGetErrorString(e));

@@ -666,15 +666,17 @@ class DisSimLocal(HubnessReduction):
         ctx = self.ctx
         i = ctx.as_device(neigh_ind, np.int64)
         n, K = i.shape
+        tm = self._target_m
         if query is self.source_:
             qm = self._source_m
         elif self._gpu_nn:
             qm = self.nn_algo._matrix_for(query)
+            tm = self.nn_algo._partner(qm, self._target_m)   # (2-byte target rows and a query of another type: the float64 pair)
         else:
             qm = N.DeviceMatrix(ctx, np.asarray(query, dtype=self._target_m.dtype), "sqeuclidean")
         out = ctx.empty((n, K), np.float64)
         gmin = ctx.to_device(np.array([np.inf], dtype=np.float64))
-        N._check(ctx.lib.kz_dsl_transform(ctx.handle, i.ptr, n, K, qm.handle, 0, self._target_m.handle,
+        N._check(ctx.lib.kz_dsl_transform(ctx.handle, i.ptr, n, K, qm.handle, 0, tm.handle,
                                           self.target_dist_to_centroids_.ptr, out.ptr, gmin.ptr), "kz_dsl_transform")
         mn = float(self._reduce_min(gmin.numpy()[0]))
         N._check(ctx.lib.kz_dsl_finalize(ctx.handle, out.ptr, n * K, mn, 1 if self.squared else 0), "kz_dsl_finalize")

@@ -247,6 +247,8 @@ class SklearnNN(NNAlgorithm):
                                       "MI355X exact backend supports")
         self._ctx = None
         self._aux = None  # (array, DeviceMatrix) of the most recent query array that is not a fitted side
+        self._wide = {}   # id(index matrix of 2-byte rows) -> (that matrix, its float64 copy): built when an ad-hoc query of another
+                          # element type arrives (`_partner`), kept beside _aux, dropped by the next fit
         self._forward = None  # (k, dist, ind): source -> target result that came out of a shared sweep (kneighbors_device_both)
         self.last_stats = None
         self.last_stats_reverse = None   # statistics of the target -> source direction of the last shared sweep (else None)
@@ -262,13 +264,21 @@ class SklearnNN(NNAlgorithm):
             self._ctx = N.Context.get(self.device)
         return self._ctx
 
-    def _prepare(self, data) -> np.ndarray:
+    def _storage(self, elem: str) -> str:
+        """The element type rows of dtype name `elem` are stored as under this backend's metric (`_native.row_storage`): float32 /
+        float64 as they are; float16 / bfloat16 as they are for euclidean, sqeuclidean and cosine (minkowski p = 2 IS euclidean);
+        anything else widened -- float32 for the boolean metrics (they read x != 0 only: half the bytes, a nonzero value stays
+        nonzero), else float64.  No device is touched."""
+        return N.row_storage(self._metric_c, elem)
+
+    def _prepare(self, data, elem: Optional[str] = None) -> np.ndarray:
+        """`data` as a contiguous 2-D array of its storage type, or of `elem` ('float32' / 'float64') where one is asked for."""
         arr = np.asarray(data)
         if arr.ndim != 2:
             raise ValueError(f"Expected 2D array, got {arr.ndim}D array instead")
-        if arr.dtype not in (np.float32, np.float64):
-            # (the boolean metrics read x != 0 only: bool, integer and float16 rows go up as float32 -- half the bytes; a nonzero value stays nonzero)
-            arr = arr.astype(np.float32 if self._metric_c in N.BOOLEAN_METRICS else np.float64)
+        store = elem if elem is not None else self._storage(arr.dtype.name)
+        if arr.dtype.name != store:
+            arr = arr.astype(store)
         return np.ascontiguousarray(arr)
 
     def _check_input_types(self, value):
@@ -282,18 +292,23 @@ class SklearnNN(NNAlgorithm):
         if self._V is not None and self._V.shape[0] != shape[1]:
             raise ValueError(f"metric_params['V'] has {self._V.shape[0]} entries, the data {shape[1]} features")
 
-    def _make_matrix(self, data, dtype=None) -> N.DeviceMatrix:
+    def _make_matrix(self, data, elem: Optional[str] = None) -> N.DeviceMatrix:
+        """The device matrix of `data` in its storage type (`_storage`), or in `elem` ('float32' / 'float64': the element type of the
+        index an ad-hoc query is searched against) -- a query is widened, never narrowed."""
         if _is_tensor(data):
             torch = _torch_if_loaded()
             t = data.detach()
             if t.dim() != 2:
                 raise ValueError(f"Expected 2D array, got {t.dim()}D array instead")
-            if t.dtype not in (torch.float32, torch.float64):
-                t = t.to(torch.float32 if self._metric_c in N.BOOLEAN_METRICS else torch.float64)
-            if dtype is not None and np.dtype(str(t.dtype).replace("torch.", "")) != dtype:
-                t = t.to(torch.float32 if dtype == np.float32 else torch.float64)
+            store = elem if elem is not None else self._storage(str(t.dtype).replace("torch.", ""))
+            if str(t.dtype).replace("torch.", "") != store:
+                t = t.to(getattr(torch, store))
             if not t.is_cuda:
-                return self._make_matrix(t.contiguous().numpy(), dtype)
+                t = t.contiguous()
+                if store == "bfloat16":   # (numpy has no bfloat16: the rows go up as their 16-bit patterns)
+                    self._check_V(tuple(t.shape))
+                    return N.DeviceMatrix(self.ctx, t.view(torch.int16).numpy().view(np.uint16), self._metric_c, V=self._V, elem="bfloat16")
+                return self._make_matrix(t.numpy(), store)
             t = t.contiguous()
             if t.device.index != self.ctx.device:
                 raise ValueError(f"tensor lives on cuda:{t.device.index}, the NN backend on device {self.ctx.device}")
@@ -301,28 +316,31 @@ class SklearnNN(NNAlgorithm):
             torch.cuda.current_stream(t.device).synchronize()   # the producer stream is not ours
             # zero-copy: the matrix reads the tensor's HBM in place and keeps it alive (the reference, too, only keeps
             # references to its inputs, neighbor_algorithm_base.py:95-96: they must not be modified while fitted)
-            return N.DeviceMatrix(self.ctx, None, self._metric_c, device_ptr=t.data_ptr(), shape=tuple(t.shape),
-                                  dtype=np.float32 if t.dtype == torch.float32 else np.float64, borrow=True, keepalive=t,
-                                  V=self._V)
+            return N.DeviceMatrix(self.ctx, None, self._metric_c, device_ptr=t.data_ptr(), shape=tuple(t.shape), elem=store, borrow=True,
+                                  keepalive=t, V=self._V)
         if isinstance(data, N.DeviceArray):
-            if len(data.shape) != 2 or data.dtype not in (np.float32, np.float64):
-                raise ValueError("device inputs must be 2D float32/float64 arrays")
-            if dtype is not None and data.dtype != dtype:
-                raise ValueError(f"device input has dtype {data.dtype}, the index has {dtype}")
+            half_ok = data.dtype == np.float16 and N.half_rows_supported(self._metric_c)
+            if len(data.shape) != 2 or not (data.dtype in (np.float32, np.float64) or half_ok):
+                raise ValueError("device inputs must be 2D float32/float64 arrays" +
+                                 (" (float16 too for euclidean, sqeuclidean and cosine)" if data.dtype == np.float16 else ""))
+            if elem is not None and data.dtype.name != elem:
+                raise ValueError(f"device input has dtype {data.dtype}, the index has {elem}")
             self._check_V(data.shape)
             return N.DeviceMatrix(self.ctx, None, self._metric_c, device_ptr=data.ptr.value, shape=data.shape,
                                   dtype=data.dtype, borrow=True, keepalive=data, V=self._V)
-        arr = self._prepare(data)
-        if dtype is not None and arr.dtype != dtype:
-            arr = arr.astype(dtype)
+        arr = self._prepare(data, elem)
         self._check_V(arr.shape)
         return N.DeviceMatrix(self.ctx, arr, self._metric_c, V=self._V)
 
     def _fit(self, data, is_source: bool):
         """Replaces SklearnNN._fit (sklearn_nearest_neighbors.py:83-94): upload + norms + MFMA tile packing."""
         self._aux = None
+        self._wide = {}
         self._forward = None
         self.last_stats_reverse = None
+        if self._half_as_float64 and self._storage(self._elem_name(data)) in N.HALF_ELEMS:
+            # (the other side of this fit has another element type: `fit`)
+            return self._make_matrix(data.numpy() if isinstance(data, N.DeviceArray) else data, elem="float64")
         return self._make_matrix(data)
 
     def _make_precomputed(self, data):
@@ -362,6 +380,7 @@ class SklearnNN(NNAlgorithm):
             if hasattr(self, stale):
                 delattr(self, stale)
         self._aux = None
+        self._wide = {}
         self._forward = None
         self.last_stats_reverse = None
         self.source_index, self.target_index = self._make_precomputed(matrix)
@@ -382,7 +401,25 @@ class SklearnNN(NNAlgorithm):
             super().fit(np.asarray(source, dtype=np.float64), np.asarray(target, dtype=np.float64), only_fit_target)
             self.source_, self.target_ = source, target  # keep the caller's arrays, as the reference does
             return
-        super().fit(source, target, only_fit_target)
+        # Tensors and DeviceArrays of two element types, one of them float16 / bfloat16: a 2-byte side is read in place only beside a
+        # side of its own type -- beside any other it is widened to float64, as every dtype other than float32 / float64 is (two
+        # half types: both to float64; the other side keeps its type, and float32 beside float64 is refused by the search as ever)
+        if target is not None:
+            es, et = self._storage(self._elem_name(source)), self._storage(self._elem_name(target))
+            self._half_as_float64 = es != et and (es in N.HALF_ELEMS or et in N.HALF_ELEMS)
+        try:
+            super().fit(source, target, only_fit_target)
+        finally:
+            self._half_as_float64 = False
+
+    _half_as_float64 = False   # set by `fit` around the `_fit` calls of a two-sided fit on mixed element types
+
+    @staticmethod
+    def _elem_name(x) -> str:
+        """dtype name ('float16', 'bfloat16', 'int64', ...) of a numpy array, DeviceArray or tensor."""
+        if _is_tensor(x):
+            return str(x.dtype).replace("torch.", "")
+        return (x.dtype if isinstance(x, N.DeviceArray) else np.asarray(x).dtype).name
 
     def _matrix_for(self, array) -> N.DeviceMatrix:
         """Device matrix of a query array: the index of a fitted side if it IS that side's array, else an upload.  The most
@@ -400,9 +437,28 @@ class SklearnNN(NNAlgorithm):
             return self._aux[1]
         self._check_input_types(array)
         ref = self.target_index if hasattr(self, "target_index") else self.source_index
-        m = self._make_matrix(array, dtype=ref.dtype)
+        want, have = ref.elem, self._elem_name(array)
+        if want in N.HALF_ELEMS:
+            # an index of 2-byte rows: a query of the same type goes up as it is; any other is widened to float64 and searched
+            # against the float64 copy of the index (`_partner`) -- a query is never narrowed
+            want = None if have == want else "float64"
+        # (a float16 DeviceArray beside an index of another type: widened through the host -- the device has no copy to borrow)
+        rows = array.numpy() if isinstance(array, N.DeviceArray) and want is not None and have == "float16" != want else array
+        m = self._make_matrix(rows, elem=want)
         self._aux = (array, m)
         return m
+
+    def _partner(self, qm: N.DeviceMatrix, index: N.DeviceMatrix) -> N.DeviceMatrix:
+        """The matrix `qm` is searched against: `index` itself, or -- an index of 2-byte rows and a query matrix of another element
+        type (`_matrix_for` has widened it to float64) -- the float64 copy of the index's rows, made once from the fitted array."""
+        if qm.elem == index.elem or index.elem not in N.HALF_ELEMS:
+            return index
+        hit = self._wide.get(id(index))
+        if hit is None:
+            side = self.target_ if index is getattr(self, "target_index", None) else self.source_
+            hit = (index, self._make_matrix(side, elem="float64"))
+            self._wide[id(index)] = hit
+        return hit[1]
 
     def _out_dtype(self, index: N.DeviceMatrix):
         # sklearn: euclidean family -> float64 always (ArgKmin); cosine -> dtype of the input; precomputed -> dtype of the matrix
@@ -421,6 +477,7 @@ class SklearnNN(NNAlgorithm):
                 return dist, ind
             del dist, ind
         qm = self._matrix_for(query)
+        index = self._partner(qm, index)
         dist, ind, stats = N.knn(self.ctx, qm, index, k, exclude_self=is_self_querying, q_begin=q_begin, q_count=q_count)
         self.last_stats = stats
         return dist, ind
@@ -436,7 +493,8 @@ class SklearnNN(NNAlgorithm):
         if index is None:   # e.g. target -> source after fit(..., only_fit_target=True)
             raise NotFittedError(f"'{type(self).__name__}' object has no attribute "
                                  f"'{'target_index' if s_to_t else 'source_index'}'")
-        return self._matrix_for(query), index
+        qm = self._matrix_for(query)
+        return qm, self._partner(qm, index)
 
     def _gold_rank_operands(self, gold, s_to_t=True):
         """(query matrix, index matrix, gold ids int64 on the device) of a `gold_ranks` call, after its checks."""
@@ -504,6 +562,7 @@ class SklearnNN(NNAlgorithm):
     def _kneighbors(self, k, query, index, return_distance, is_self_querying):
         """Replaces SklearnNN._kneighbors (sklearn_nearest_neighbors.py:96-101)."""
         qm = self._matrix_for(query)
+        index = self._partner(qm, index)
         dist, ind, stats = N.knn(self.ctx, qm, index, k, exclude_self=is_self_querying)
         self.last_stats = stats
         if _is_tensor(query):   # tensors in -> tensors out (on the query's device), as the reference does with Faiss
