@@ -117,6 +117,10 @@ int kz_ctx_sync(kz_ctx* ctx);
  * searches are kept for reuse -- up to 48 GiB -- so that a repeated fit() does not pay hipMalloc + hipFree; a process that
  * shares the GPU with another allocator, e.g. torch's, calls this after a large search).  Waits for the stream. */
 int kz_ctx_trim(kz_ctx* ctx);
+/* *h_free (host) = the bytes a kz_malloc can still get on the context's device -- what the driver reports free plus the released
+ * buffers the context keeps for reuse; *h_total = the device's memory.  What a caller sizes a variable-length result against
+ * (kz_radius_neighbors) before it allocates.  Additive, ABI v7. */
+int kz_ctx_mem_info(kz_ctx* ctx, size_t* h_free, size_t* h_total);
 /* Options (the public contract -- four names):
  *   "precision"    0 (default) = fp16 first pass on centred operands (16 <= d_pad <= 384), rows it cannot certify go down the
  *                  tiers (more / longer lists -> split-bf16 operands -> float32 operands -> exact float64); 2 = split-bf16 first
@@ -383,6 +387,32 @@ int kz_gold_ranks_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, 
 int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                    int k, int kind, const double* d_q_a, const double* d_q_b, const double* d_t_a, const double* d_t_b,
                    double* d_w, int64_t* d_ind);
+/* RADIUS NEIGHBOURS over the whole index -- ABI v7, additive: every pair within a threshold, as a CSR.  Pair (r, j) of query row
+ * q_begin + r and index row j is in the result exactly when w_rj <= radius, where w is what the list calls return for the pair:
+ * kz_radius_neighbors: the distance kz_knn returns (the exact float64 ranking value converted as kz_knn converts it);
+ * kz_radius_neighbors_reduced: the hubness-reduced distance of kz_gold_ranks_reduced / kz_knn_reduced (kind, the four state vectors
+ * and their validation as there) -- the same expressions and therefore the same bits.  A NaN w is never in the result, not even
+ * for radius = +inf.  radius NaN: KZ_ERR_INVALID; +-inf and negative radii are legal (CSLS values are routinely negative).
+ * d_indptr: [q_count + 1] int64 on the device: d_indptr[0] = 0, d_indptr[r + 1] - d_indptr[r] = the count of row q_begin + r;
+ * *h_total (host) = the number of pairs.  Both are ALWAYS complete and exact, whatever `capacity` is; capacity = 0 is the count-only
+ * call (d_ind / d_dist may be NULL).  d_ind / d_dist: [capacity] int64 / float64 on the device: the entries (index row, w) of every
+ * row whose end offset d_indptr[r + 1] is <= capacity, at d_indptr[r] ..; for any other row NOTHING is written, and the call
+ * returns KZ_OK all the same: the caller compares *h_total with capacity and calls again with an exact allocation.
+ * sorted == 0: a row's entries ascend by index row.  sorted != 0: they ascend by (w, index row) in the order of kz_knn_reduced
+ * (-0.0 equals +0.0; w is NaN-free by construction), a row of any length -- a row can hold the whole index; rows beyond 4096
+ * entries are sorted through a transient second copy of the output in device memory (KZ_ERR_NOMEM when it does not fit).
+ * Runs the exact float64 value kernels of kz_knn for every query row and, per batch of them, a count, an integer scan and a fill
+ * (the predicate again; places from integer prefix sums): no atomics on the output, nothing depends on the order anything runs
+ * in, and the result has the same bits however the call is cut into batches or row ranges (d_indptr relative to the range).
+ * Matrices that disagree (dtype, metric, exponent, seuclidean V), a negative capacity: KZ_ERR_INVALID.  No self-exclusion: the call
+ * is for two-sided data.  Synchronises the context's stream. */
+int kz_radius_neighbors(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                        double radius, int sorted, int64_t capacity, int64_t* d_indptr, int64_t* d_ind, double* d_dist,
+                        int64_t* h_total);
+int kz_radius_neighbors_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                                double radius, int sorted, int64_t capacity, int kind, const double* d_q_a, const double* d_q_b,
+                                const double* d_t_a, const double* d_t_b, int64_t* d_indptr, int64_t* d_ind, double* d_dist,
+                                int64_t* h_total);
 /* Row-wise SOFT-MIN over the whole index -- ABI v7, additive: the primitive of the Sinkhorn potentials and the inverted softmax.
  *   d_out[r] = softmin_eps over every index row j of (d_rj - d_off[j])  +  shift,   softmin_eps(x) = m - eps log sum exp(-(x - m) / eps),
  * m = min x, in float64; d_rj = the distance kz_knn returns for query row q_begin + r and index row j (the exact ranking value

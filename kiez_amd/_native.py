@@ -116,6 +116,7 @@ SYMBOLS = [
     ("kz_ctx_destroy", C.c_int, [_P]),
     ("kz_ctx_sync", C.c_int, [_P]),
     ("kz_ctx_trim", C.c_int, [_P]),
+    ("kz_ctx_mem_info", C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("kz_ctx_set_option", C.c_int, [_P, C.c_char_p, C.c_double]),
     ("kz_malloc", C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     ("kz_free", C.c_int, [_P, _P]),
@@ -158,6 +159,9 @@ SYMBOLS = [
     ("kz_gold_ranks", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    ("kz_radius_neighbors", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_radius_neighbors_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                              C.POINTER(_I64)]),
     ("kz_softmin_rows", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, _P, C.c_double, _P]),
     ("kz_max_abs_diff", C.c_int, [_P, _P, _P, _I64, C.POINTER(C.c_double)]),
     ("kz_lists_transpose", C.c_int, [_P, _P, _P, _I64, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64)]),
@@ -262,6 +266,12 @@ class Context:
     def trim(self):
         """Release the context's cached device buffers (kz_ctx_trim)."""
         _check(self.lib.kz_ctx_trim(self.handle), "kz_ctx_trim")
+
+    def mem_info(self) -> Tuple[int, int]:
+        """(bytes a device allocation can still get -- free HBM plus the released buffers the context keeps --, bytes of the device)."""
+        free, total = C.c_size_t(), C.c_size_t()
+        _check(self.lib.kz_ctx_mem_info(self.handle, C.byref(free), C.byref(total)), "kz_ctx_mem_info")
+        return int(free.value), int(total.value)
 
     # ---- device arrays -------------------------------------------------------------------------------
     def empty(self, shape, dtype) -> "DeviceArray":
@@ -542,6 +552,89 @@ def knn_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, 
     _check(ctx.lib.kz_knn_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, k, int(kind), *state, w.ptr, ind.ptr),
            "kz_knn_reduced")
     return w, ind
+
+
+def radius_value(radius, what: str = "radius_neighbors") -> float:
+    """The threshold of a radius call as a float: a real number -- +-inf and negative values are legal (CSLS values are routinely
+    negative); a bool or anything that is no real number raises TypeError, NaN raises ValueError.  Checked on the host, before the
+    device is touched."""
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{what} needs a real number as radius, got {radius!r}")
+    radius = float(radius)
+    if radius != radius:
+        raise ValueError(f"{what} needs a radius that is not NaN")
+    return radius
+
+
+# pairs per query row the first call of `radius_neighbors` leaves room for, before it knows the total
+RADIUS_FIRST_CAPACITY_PER_ROW = 32
+
+
+def _radius_call(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius: float, sort_results: bool, capacity: int, kind, state,
+                 q_begin: int, q_count: int):
+    """One kz_radius_neighbors / kz_radius_neighbors_reduced call -> (indptr [q_count + 1], ind [capacity], dist [capacity], total)."""
+    indptr = ctx.empty((q_count + 1,), np.int64)
+    ind = ctx.empty((capacity,), np.int64)
+    dist = ctx.empty((capacity,), np.float64)
+    total = _I64(0)
+    if kind is None:
+        _check(ctx.lib.kz_radius_neighbors(ctx.handle, query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)), capacity,
+                                           indptr.ptr, ind.ptr, dist.ptr, C.byref(total)), "kz_radius_neighbors")
+    else:
+        _check(ctx.lib.kz_radius_neighbors_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)),
+                                                   capacity, int(kind), *state, indptr.ptr, ind.ptr, dist.ptr, C.byref(total)),
+               "kz_radius_neighbors_reduced")
+    return indptr, ind, dist, int(total.value)
+
+
+def radius_neighbors(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius: float, kind: Optional[int] = None, q_state=None,
+                     t_state=None, sort_results: bool = True, capacity: Optional[int] = None, q_begin: int = 0,
+                     q_count: Optional[int] = None) -> Tuple[DeviceArray, DeviceArray, DeviceArray, int]:
+    """kz_radius_neighbors (`kind` None) / kz_radius_neighbors_reduced -> (indptr int64 [q_count + 1], ind int64, dist float64, total):
+    every index row j with w <= radius for query row q_begin + r, as a CSR on the device -- w the distance `knn` returns or, with a
+    `kind` of `gold_ranks_reduced` and its `q_state` / `t_state`, the hubness-reduced distance of `knn_reduced`; a NaN w is never in
+    the result.  Rows ascend by (w, index row) in `knn_reduced`'s order, or with `sort_results=False` by index row.
+
+    `capacity` None: the allocation policy -- a first call with room for min(n_q n_t, 32 n_q) pairs; when the total is larger, ONE
+    second call with room for exactly the total, refused with MemoryError (naming the total) when the output would not fit what
+    the device has free; ind / dist come back with `total` entries.  `capacity` given: that one call as the library makes it -- ind /
+    dist have `capacity` entries, hold the rows whose end offset is <= capacity and nothing defined beyond them; indptr and total
+    are exact either way (capacity 0: `radius_counts`)."""
+    radius = radius_value(radius)
+    if q_count is None:
+        q_count = query.shape[0] - q_begin
+    state = None
+    if kind is not None:
+        if q_state is None or t_state is None:
+            state = (None, None, None, None)   # (the library says which vectors the kind needs)
+        else:
+            state = _reduction_state(q_state, t_state, q_count, index.shape[0])
+    elif q_state is not None or t_state is not None:
+        raise ValueError("q_state / t_state belong to a reduced call: name its kind")
+    if capacity is not None:
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+            raise ValueError(f"capacity must be a non-negative integer, got {capacity!r}")
+        return _radius_call(ctx, query, index, radius, sort_results, int(capacity), kind, state, q_begin, q_count)
+    n_q = max(int(q_count), 0)
+    first = min(n_q * index.shape[0], RADIUS_FIRST_CAPACITY_PER_ROW * n_q)
+    indptr, ind, dist, total = _radius_call(ctx, query, index, radius, sort_results, first, kind, state, q_begin, q_count)
+    if total > first:
+        del ind, dist   # (back to the context's pool: counted as free below)
+        # 16 bytes per pair, and as much again while rows beyond the LDS sort's reach are sorted through HBM
+        need = 16 * total * (2 if sort_results else 1)
+        free, _ = ctx.mem_info()   # (the exact stage's value block is allocated by now: what is free is what it leaves)
+        if need > free:
+            raise MemoryError(f"radius_neighbors: total = {total} pairs within radius {radius!r} need {need} bytes of device memory, "
+                              f"{free} are free: use a smaller radius or a row range (q_begin / q_count)")
+        indptr, ind, dist, total = _radius_call(ctx, query, index, radius, sort_results, total, kind, state, q_begin, q_count)
+    return indptr, ind.view_rows(0, total), dist.view_rows(0, total), total
+
+
+def radius_counts(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius: float, kind: Optional[int] = None, q_state=None,
+                  t_state=None, q_begin: int = 0, q_count: Optional[int] = None) -> Tuple[DeviceArray, int]:
+    """`radius_neighbors` with capacity 0 -> (indptr int64 [q_count + 1] on the device, total): the counts alone, nothing else written."""
+    indptr, _, _, total = radius_neighbors(ctx, query, index, radius, kind, q_state, t_state, False, 0, q_begin, q_count)
+    return indptr, total
 
 
 # index rows per first-level workgroup of kz_softmin_rows (include/kiez_amd.h: KZ_SOFTMIN_CHUNK_ROWS): part of its summation order

@@ -100,6 +100,14 @@ int kz_ctx_trim(kz_ctx* c) {
     return KZ_OK;
 }
 
+int kz_ctx_mem_info(kz_ctx* c, size_t* h_free, size_t* h_total) {
+    KZ_REQUIRE(c && h_free && h_total, "kz_ctx_mem_info: null argument");
+    KZ_HIP(hipSetDevice(c->device));
+    KZ_HIP(hipMemGetInfo(h_free, h_total));
+    *h_free += c->pool_bytes;   // (released buffers kept for reuse: kz_pool_alloc hands them back to the driver when it must)
+    return KZ_OK;
+}
+
 int kz_ctx_sync(kz_ctx* c) {
     KZ_REQUIRE(c != nullptr, "kz_ctx_sync: null context");
     KZ_HIP(hipStreamSynchronize(c->stream));

@@ -245,6 +245,46 @@ class HubnessReduction(ABC):
         od, oi = self.kneighbors_whole_index_device(k)
         return self._to_host(od, oi)
 
+    # ---- every pair within a threshold of the reduced distance, whole index -----------------------------
+    def _radius_operands(self, what, s_to_t):
+        """(query matrix, index matrix, kind, q_state, t_state) of a radius call under the reduced distances, after its checks."""
+        if not s_to_t:
+            raise ValueError(f"{what} under a hubness reduction takes source rows against the target index only (s_to_t=True): the "
+                             "hubness reduction is fitted for that direction")
+        if not self._gpu_nn:
+            raise NotImplementedError(f"{what} needs one of the device-native reductions on the MI355X SklearnNN backend")
+        query, index = self.nn_algo._two_sided_operands(what)   # (NotFittedError, single-source fit: as gold_ranks)
+        if self._no_rank_reason:
+            raise NotImplementedError(f"{type(self).__name__}: {self._no_rank_reason}")
+        return (query, index) + tuple(self._forward_rank_state())
+
+    def radius_neighbors_device(self, radius, s_to_t=True, sort_results=True):
+        """`radius_neighbors` with the CSR left in HBM: (indptr, ind, dist) DeviceArrays."""
+        radius = N.radius_value(radius)
+        query, index, kind, q_state, t_state = self._radius_operands("radius_neighbors", s_to_t)
+        indptr, ind, dist, _ = N.radius_neighbors(self.ctx, query, index, radius, kind, q_state, t_state, sort_results)
+        return indptr, ind, self.nn_algo._radius_distances(dist, self.nn_algo.target_index)
+
+    def radius_neighbors(self, radius, s_to_t=True, return_distance=True, sort_results=True):
+        """Every target row whose HUBNESS-REDUCED distance to a source row is <= `radius`, over the whole target index
+        (`SklearnNN.radius_neighbors`: under the search metric; same result layout, same `radius` checks).  w = f(d, a_i, b_j) is
+        the value `kneighbors_whole_index` returns for the pair, with the state `fit` / `kneighbors` use; under MutualProximity
+        'normal' it is a probability, so `radius=0.05` asks for all pairs with MP <= 0.05.  CSLS values are routinely negative and
+        so may `radius` be.  A NaN w is never in the result.  Rows ascend by (w, target row) in `kneighbors_whole_index`'s order:
+        a row with at most 512 entries IS the head of that list.  MutualProximity 'empiric', DisSimLocal and user-written reductions
+        raise NotImplementedError, `s_to_t=False` ValueError; the shared sweep's cached forward lists are left as found."""
+        nn = self.nn_algo
+        indptr, ind, dist = self.radius_neighbors_device(radius, s_to_t, sort_results)
+        return nn._results_to_host(indptr, ind, dist) if return_distance else nn._results_to_host(indptr, ind)
+
+    def radius_counts(self, radius, s_to_t=True):
+        """The number of target rows within `radius` of every source row under the reduced distances: int64 [n_source]."""
+        radius = N.radius_value(radius, "radius_counts")
+        query, index, kind, q_state, t_state = self._radius_operands("radius_counts", s_to_t)
+        indptr, _ = N.radius_counts(self.ctx, query, index, radius, kind, q_state, t_state)
+        indptr, = self.nn_algo._results_to_host(indptr)
+        return indptr[1:] - indptr[:-1]
+
     def _to_host(self, od: N.DeviceArray, oi: N.DeviceArray):
         """A device result as `kneighbors` hands it out: tensors in -> tensors out on the source's device, else numpy."""
         src = self.nn_algo.source_
@@ -309,6 +349,16 @@ class NoHubnessReduction(HubnessReduction):
 
     def kneighbors_whole_index(self, k: int):
         return self.kneighbors(self._whole_index_k(k))
+
+    # (nothing is rescaled: the pairs within a threshold of the search metric)
+    def radius_neighbors_device(self, radius, s_to_t=True, sort_results=True):
+        return self.nn_algo.radius_neighbors_device(radius, s_to_t, sort_results)
+
+    def radius_neighbors(self, radius, s_to_t=True, return_distance=True, sort_results=True):
+        return self.nn_algo.radius_neighbors(radius, s_to_t, return_distance, sort_results)
+
+    def radius_counts(self, radius, s_to_t=True):
+        return self.nn_algo.radius_counts(radius, s_to_t)
 
     def __repr__(self):
         return f"{self.__class__.__name__}()"

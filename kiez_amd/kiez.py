@@ -115,6 +115,43 @@ class Kiez:
         dist, ind = self.hubness.kneighbors_whole_index(k)
         return (dist, ind) if return_distance else ind
 
+    def radius_neighbors(self, radius, reduced: bool = False, return_distance: bool = True, sort_results: bool = True,
+                         ragged: bool = False):
+        """Every target row within `radius` of every source row, over the whole target index: the similarity join by threshold, the
+        abstain rule for dangling entities (an empty row: no target is close enough) -- `radius_neighbors` of scikit-learn's
+        `NearestNeighbors`, without an n_source x n_target matrix and without `kneighbors_whole_index`'s fixed width.
+
+        `reduced` has the meaning it has in `gold_ranks`.  False: pair (i, j) is in the result exactly when d_ij <= radius under the
+        SEARCH METRIC, whatever the hubness setting (`SklearnNN.radius_neighbors`).  True: when w_ij <= radius under the
+        hubness-reduced distances of the fitted reduction (`HubnessReduction.radius_neighbors`: CSLS, LocalScaling 'standard' /
+        'nicdm', MutualProximity 'normal' -- there w is a probability --; none: the plain result); MutualProximity 'empiric' and
+        DisSimLocal raise NotImplementedError.  `radius` is a real number -- negative values and infinities are legal, NaN raises
+        ValueError, a bool TypeError.  A NaN value is never in the result.  A single-source fit raises NotImplementedError.
+
+        Returns the CSR `(indptr int64 [n_source + 1], ind int64 [total], dist [total])`, or `(indptr, ind)` with
+        `return_distance=False`: the targets of source row i are `ind[indptr[i]:indptr[i + 1]]`, ascending by (value, target row) or,
+        with `sort_results=False`, by target row.  numpy arrays, or tensors when fitted on tensors.  `dist` is in the dtype
+        `kneighbors` returns; for float32 cosine / precomputed input the float64 value is rounded to float32 AFTER it was compared, so
+        a float32 distance may round to just above `radius`.  `ragged=True` gives scikit-learn's layout instead -- `(dist, ind)` or
+        `ind`, numpy object arrays of one array per source row -- by one split on the host."""
+        algo = self.hubness if reduced else self.algorithm
+        res = algo.radius_neighbors(radius, return_distance=return_distance, sort_results=sort_results)
+        if not ragged:
+            return res
+        host = [r.cpu().numpy() if hasattr(r, "cpu") else r for r in res]
+        cuts = host[0][1:-1]
+
+        def rows(flat):
+            out = np.empty(len(host[0]) - 1, dtype=object)
+            out[:] = np.split(flat, cuts)
+            return out
+        return (rows(host[2]), rows(host[1])) if return_distance else rows(host[1])
+
+    def radius_counts(self, radius, reduced: bool = False):
+        """The number of target rows within `radius` of every source row (`radius_neighbors`' rule and `reduced`): int64 [n_source],
+        the per-row density count -- no pair is stored."""
+        return (self.hubness if reduced else self.algorithm).radius_counts(radius)
+
     def _lists_for_matching(self, k, whole_index):
         """The device lists a one-to-one step runs on -> (dist, ind, n_target)."""
         nn = self.algorithm

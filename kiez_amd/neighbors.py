@@ -525,6 +525,57 @@ class SklearnNN(NNAlgorithm):
         ranks into hits@k, MR and MRR."""
         return self.gold_ranks_device(gold, s_to_t).numpy()
 
+    # ---- every pair within a threshold, whole index ---------------------------------------------------
+    def _results_to_host(self, *arrays):
+        """Device results as `kneighbors` hands them out: tensors on the source's device after a fit on tensors, else numpy."""
+        src = self.source_
+        if _is_tensor(src):
+            torch = _torch_if_loaded()
+            self.ctx.sync()
+            out = tuple(torch.as_tensor(a, device="cuda").clone().to(src.device) if a.nbytes else
+                        torch.empty(a.shape, dtype=getattr(torch, a.dtype.name), device=src.device) for a in arrays)
+            torch.cuda.current_stream().synchronize()   # before the arrays go back to our stream-ordered pool
+            return out
+        return tuple(a.numpy() for a in arrays)
+
+    def _radius_distances(self, dist: N.DeviceArray, index: N.DeviceMatrix) -> N.DeviceArray:
+        """The float64 values of a radius call in the dtype `kneighbors` returns (the cast comes AFTER the predicate)."""
+        if self._out_dtype(index) == np.float32:
+            return N.cast_f32(self.ctx, dist) if dist.shape[0] else self.ctx.empty((0,), np.float32)
+        return dist
+
+    def radius_neighbors_device(self, radius, s_to_t=True, sort_results=True):
+        """`radius_neighbors` with the CSR left in HBM: (indptr int64 [n_query + 1], ind int64 [total], dist [total]) DeviceArrays."""
+        radius = N.radius_value(radius)
+        query, index = self._two_sided_operands("radius_neighbors", s_to_t)
+        indptr, ind, dist, _ = N.radius_neighbors(self.ctx, query, index, radius, sort_results=sort_results)
+        return indptr, ind, self._radius_distances(dist, self._direction(s_to_t)[1])
+
+    def radius_neighbors(self, radius, s_to_t=True, return_distance=True, sort_results=True):
+        """Every index row within `radius` of every query row under the search metric, over the whole index: the other half of
+        scikit-learn's `NearestNeighbors`.  Query rows are the fitted source rows and the index the fitted target (`s_to_t=False`:
+        the reverse).  Pair (i, j) is in the result exactly when d_ij <= radius, d the float64 distance `kneighbors` computes for
+        the pair; a NaN distance (correlation against a constant row) is never in it.  `radius` is a real number; infinities are
+        legal, NaN raises ValueError and a bool TypeError.
+
+        Returns the CSR `(indptr, ind, dist)` -- `ind[indptr[i]:indptr[i + 1]]` are the index rows of query row i, ascending by
+        (distance, index row), or by index row with `sort_results=False` -- or `(indptr, ind)` with `return_distance=False`; numpy
+        arrays, or tensors when fitted on tensors.  `dist` has the dtype `kneighbors` returns: for float32 cosine / precomputed
+        input it is the float64 distance rounded to float32 AFTER the comparison, so a returned value may round to just above
+        `radius`.  Memory is the result's, not n_query x n_index: a total that does not fit the device raises MemoryError.
+        NotFittedError before `fit`, NotImplementedError after a single-source fit, as `gold_ranks`."""
+        indptr, ind, dist = self.radius_neighbors_device(radius, s_to_t, sort_results)
+        return self._results_to_host(indptr, ind, dist) if return_distance else self._results_to_host(indptr, ind)
+
+    def radius_counts(self, radius, s_to_t=True):
+        """The number of index rows within `radius` of every query row (`radius_neighbors`' rule) -- int64 [n_query], numpy or a
+        tensor when fitted on tensors -- without the pairs: nothing but n_query + 1 offsets is allocated."""
+        radius = N.radius_value(radius, "radius_counts")
+        query, index = self._two_sided_operands("radius_counts", s_to_t)
+        indptr, _ = N.radius_counts(self.ctx, query, index, radius)
+        indptr, = self._results_to_host(indptr)
+        return indptr[1:] - indptr[:-1]
+
     def kneighbors_device_both(self, k=None):
         """Both directions between the fitted source and target from ONE sweep of the distance matrix (kz_knn_dual): returns
         the target -> source result (what HubnessReduction.fit needs, base.py:37-42) and keeps the source -> target result
