@@ -464,6 +464,7 @@ int kz_softmin_list_rows(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind
  * same bits wherever the column lies in the view, whatever other columns and rows are in the call, and from run to run.
  * Synchronises the context's stream. */
 #define KZ_SOFTMIN_LIST_CHUNK 512 /* entries of a column per first-level wave: part of the summation order */
+/* (Also THE ROW TREE OF A CSR ROW: kz_softmin_csr_rows reduces a row of n entries by the tree this call gives a column of n entries.) */
 int kz_softmin_list_cols(kz_ctx* ctx, const int64_t* d_colptr, const int32_t* d_col_row, const double* d_col_val, int64_t n_index,
                          int64_t nnz, double eps, const double* d_off, double shift, double* d_out);
 /* The Sinkhorn iteration over the lists: from f = 0, n_iter >= 1 times the column step g = kz_softmin_list_cols(d_off = f, shift =
@@ -525,6 +526,58 @@ int kz_assign_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64
  * defaults of unmatched_cost and eps are made of): *h_min, *h_max (host); *h_any = 0 and both 0.0 when there is no such entry. */
 int kz_assign_range(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index,
                     double* h_min, double* h_max, int* h_any);
+
+/* ---- the same three steps on RAGGED (CSR) pair lists (kz_match.hip, kz_assign.hip, kz_softmin_lists.hip) -- additive, ABI v7 -- */
+/* The second list layout: what kz_radius_neighbors returns, or a blocking step's candidate pairs.  d_indptr [n_q + 1] (int64),
+ * d_ind [nnz] (int64) and d_dist [nnz] (dist_dtype: KZ_F32 or KZ_F64; the soft-min calls take float64 only) on the device.  Entry
+ * p of row i (d_indptr[i] <= p < d_indptr[i + 1]) is a PAIR under exactly the rule of the fixed-width call of the same name: 0 <=
+ * d_ind[p] < n_index, and for kz_assign_csr additionally a finite value <= unmatched_cost.  A target may repeat inside a row, a
+ * row may be empty, and there is NO LIMIT on the length of a row (the fixed-width calls stop at KZ_MAX_CANDIDATES columns).
+ * n_q <= 2^31 - 2, 1 <= n_index <= 2^31 - 2, 0 <= nnz <= 2^31 - 2: KZ_ERR_INVALID otherwise.
+ * VALIDATION: every call first runs one small kernel that checks d_indptr[0] == 0, d_indptr non-decreasing and d_indptr[n_q] ==
+ * nnz, and reads its flag back BEFORE anything that depends on d_indptr is queued: a bad d_indptr is KZ_ERR_INVALID and never an
+ * address.  Each call therefore synchronises the context's stream at least once.
+ *
+ * kz_match_csr: kz_match_lists' matching, a row walked from d_indptr[i]; d_col[i] = the position of the matched entry INSIDE its
+ * row (p - d_indptr[i]) or -1; *h_rounds <= nnz + n_index.  One rule, one kernel body: the propose / tie / resolve kernels are
+ * instantiated per row layout.  kz_match_values_csr: d_out[i] = d_dist[d_indptr[i] + d_col[i]], NaN where d_col[i] is outside the
+ * row. */
+int kz_match_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const void* d_dist, int dist_dtype, int64_t n_q,
+                 int64_t nnz, int64_t n_index, int64_t* d_match, int64_t* d_col, int64_t* h_rounds);
+int kz_match_values_csr(kz_ctx* ctx, const int64_t* d_indptr, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q,
+                        int64_t nnz, void* d_out);
+/* kz_assign_csr: kz_assign_lists' auction -- the same synchronous rule, arguments, defaults and outputs, d_col as kz_match_csr.
+ * A FREE row reads its whole row in every round it bids, so a row of more than KZ_CSR_LONG_ROW entries bids with ONE WAVE: lane l
+ * takes the entries l, l + 64, ... in ascending order, and a 64-lane butterfly merges (v1, first position with v1, v2) by compares
+ * only -- ties in v1 go to the smaller position, v2 is the largest of everything else, the losing v1 included -- so the bid is bit
+ * for bit the one a single lane computes.  The long rows are found once per call by an ordered compaction of the row ids (no
+ * atomics); the wave kernel is indexed by rank.  While a long row is FREE the call stays in grid-wide rounds: the single-workgroup
+ * tail starts only when at most tail_rows rows are FREE and none of them is long.  The arrays that come out depend neither on
+ * that nor on tail_rows.  kz_assign_range_csr: kz_assign_range over the nnz entries. */
+#ifndef KZ_CSR_LONG_ROW
+#define KZ_CSR_LONG_ROW 256 /* a row with more entries bids with one wave (profiles/csr_lists.md) */
+#endif
+int kz_assign_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const void* d_dist, int dist_dtype, int64_t n_q,
+                  int64_t nnz, int64_t n_index, double unmatched_cost, double eps, int64_t max_rounds, int tail_rows, int64_t* d_match,
+                  int64_t* d_col, double* d_price, int64_t* h_rounds, int* h_converged);
+int kz_assign_range_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const void* d_dist, int dist_dtype, int64_t n_q,
+                        int64_t nnz, int64_t n_index, double* h_min, double* h_max, int* h_any);
+/* kz_csr_transpose: kz_lists_transpose's view (d_colptr [n_index + 1], d_col_row int32 [nnz], d_col_val [nnz]) of a CSR: the
+ * stable sort of (target id, flat position p), the source row of an entry recovered by binary search in d_indptr.
+ * kz_softmin_csr_rows: d_out[i] = softmin_eps over the pairs p of row i of (d_dist[p] - d_off[d_ind[p]]) + shift.  THE ROW TREE OF
+ * A CSR ROW IS, BY DEFINITION, THE COLUMN TREE OF ITS ENTRY COUNT: the row step is kz_softmin_list_cols' kernel pair applied to
+ * (d_indptr, d_ind, d_dist) with a 64-bit index type -- chunks of KZ_SOFTMIN_LIST_CHUNK entries from the row's own first entry,
+ * one wave per chunk, the parts folded by one wave -- so its bits are those of kz_softmin_list_cols on the view (colptr = indptr,
+ * col_row = ind, col_val = dist).  An entry that is no pair is +inf and adds an exact zero; a row without a pair gives NaN.
+ * kz_sinkhorn_csr: kz_sinkhorn_lists' loop over the two -- every step queued at once (behind the validation), the stopping rule on
+ * the device, no float atomics, the same bits from every run; arguments and outputs as kz_sinkhorn_lists. */
+int kz_csr_transpose(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
+                     int64_t n_index, int64_t* d_colptr, int32_t* d_col_row, double* d_col_val, int64_t* h_nnz);
+int kz_softmin_csr_rows(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
+                        int64_t n_index, double eps, const double* d_off, double shift, double* d_out);
+int kz_sinkhorn_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
+                    int64_t n_index, double eps, int n_iter, double tol, double* d_f, double* d_g, int* h_n_iter, double* h_change,
+                    int* h_measured);
 
 /* float64 -> float32 cast of an [count] array (cosine + float32 inputs keep the reference's output dtype). */
 int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count);

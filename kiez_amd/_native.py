@@ -176,6 +176,16 @@ SYMBOLS = [
                                   C.POINTER(_I64), C.POINTER(C.c_int)]),
     ("kz_assign_range", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]),
+    ("kz_match_csr", C.c_int, [_P, _P, _P, _P, C.c_int, _I64, _I64, _I64, _P, _P, C.POINTER(_I64)]),
+    ("kz_match_values_csr", C.c_int, [_P, _P, _P, C.c_int, _P, _I64, _I64, _P]),
+    ("kz_assign_csr", C.c_int, [_P, _P, _P, _P, C.c_int, _I64, _I64, _I64, C.c_double, C.c_double, _I64, C.c_int, _P, _P, _P,
+                                C.POINTER(_I64), C.POINTER(C.c_int)]),
+    ("kz_assign_range_csr", C.c_int, [_P, _P, _P, _P, C.c_int, _I64, _I64, _I64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_int)]),
+    ("kz_csr_transpose", C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_softmin_csr_rows", C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, C.c_double, _P, C.c_double, _P]),
+    ("kz_sinkhorn_csr", C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, C.c_double, C.c_int, C.c_double, _P, _P, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_comm_destroy", C.c_int, [_P]),
@@ -825,6 +835,120 @@ def assign_range(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int
     _check(ctx.lib.kz_assign_range(ctx.handle, dist.ptr, dtype, ind.ptr, n_q, k, int(n_index), C.byref(lo), C.byref(hi), C.byref(some)),
            "kz_assign_range")
     return (float(lo.value), float(hi.value)) if some.value else None
+
+
+# ---- the same calls on ragged (CSR) pair lists: indptr int64 [n_q + 1], ind int64 [nnz], dist [nnz], all on the device ----------
+# a row with more entries bids with one wave in kz_assign_csr (include/kiez_amd.h: KZ_CSR_LONG_ROW)
+CSR_LONG_ROW = 256
+
+
+def _csr_lists(indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray):
+    """(n_q, nnz, dtype code) of a CSR pair list on the device, as the kz_*_csr calls take it.  The CONTENT of indptr is checked on
+    the device, by the call itself, before anything reads through it."""
+    if not all(isinstance(a, DeviceArray) for a in (indptr, ind, dist)):
+        raise ValueError("indptr, ind and dist must be DeviceArrays")
+    if len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64:
+        raise ValueError(f"indptr must be a 1-D int64 array of n_q + 1 entries, got {indptr.dtype} {indptr.shape}")
+    if len(dist.shape) != 1 or dist.shape != ind.shape:
+        raise ValueError(f"with indptr, dist and ind must be 1-D and of one length, got {dist.shape} and {ind.shape}")
+    if dist.dtype not in (np.float32, np.float64) or ind.dtype != np.int64:
+        raise ValueError(f"dist must be float32 or float64 and ind int64, got {dist.dtype} and {ind.dtype}")
+    return indptr.shape[0] - 1, dist.shape[0], KZ_F32 if dist.dtype == np.float32 else KZ_F64
+
+
+def _f64_csr(indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray):
+    """(n_q, nnz) of a float64 CSR pair list on the device, as the soft-min calls over a CSR take it."""
+    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
+    if dtype != KZ_F64:
+        raise ValueError(f"the soft-min over a CSR pair list takes float64 values, got {dist.dtype}")
+    return n_q, nnz
+
+
+def match_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int) -> Tuple[DeviceArray, DeviceArray, int]:
+    """kz_match_csr -> (match int64 [n_q], col int64 [n_q], rounds): `match_lists` over a CSR pair list; col[i] is the position of the
+    matched entry inside row i.  A bad indptr (not starting at 0, decreasing, not ending at nnz) raises ValueError."""
+    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
+    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
+    rounds = _I64(0)
+    _check(ctx.lib.kz_match_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, dtype, n_q, nnz, int(n_index), match.ptr, col.ptr,
+                                C.byref(rounds)), "kz_match_csr")
+    return match, col, int(rounds.value)
+
+
+def match_values_csr(ctx: Context, indptr: DeviceArray, dist: DeviceArray, col: DeviceArray) -> DeviceArray:
+    """kz_match_values_csr -> dist[indptr[i] + col[i]] in dist's dtype, NaN where col[i] is outside row i: [n_q] on the device."""
+    if not isinstance(indptr, DeviceArray) or len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64:
+        raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries")
+    if not isinstance(dist, DeviceArray) or len(dist.shape) != 1 or dist.dtype not in (np.float32, np.float64):
+        raise ValueError("with indptr, dist must be a 1-D float32 or float64 DeviceArray")
+    n_q, nnz, dtype = indptr.shape[0] - 1, dist.shape[0], KZ_F32 if dist.dtype == np.float32 else KZ_F64
+    if col.dtype != np.int64 or col.shape != (n_q,):
+        raise ValueError(f"col must be int64 of shape ({n_q},), got {col.dtype} {col.shape}")
+    out = ctx.empty((n_q,), dist.dtype)
+    _check(ctx.lib.kz_match_values_csr(ctx.handle, indptr.ptr, dist.ptr, dtype, col.ptr, n_q, nnz, out.ptr), "kz_match_values_csr")
+    return out
+
+
+def assign_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, unmatched_cost: float, eps: float,
+               max_rounds: int, tail_rows: int = 0, want_prices: bool = False):
+    """kz_assign_csr -> (match, col, prices | None, rounds, converged): `assign_lists` over a CSR pair list, col as `match_csr`
+    returns it.  Rows of more than CSR_LONG_ROW entries bid with one wave; the arrays depend neither on that nor on tail_rows."""
+    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
+    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
+    prices = ctx.empty((int(n_index),), np.float64) if want_prices and 1 <= int(n_index) < 2 ** 31 - 1 else None
+    rounds, converged = _I64(0), C.c_int(0)
+    _check(ctx.lib.kz_assign_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, dtype, n_q, nnz, int(n_index), float(unmatched_cost), float(eps),
+                                 int(max_rounds), int(tail_rows), match.ptr, col.ptr, prices.ptr if prices is not None else None,
+                                 C.byref(rounds), C.byref(converged)), "kz_assign_csr")
+    return match, col, prices, int(rounds.value), bool(converged.value)
+
+
+def assign_range_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int):
+    """kz_assign_range_csr -> (smallest, largest) finite value listed with 0 <= ind < n_index, as float64; None when there is none."""
+    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
+    lo, hi, some = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    _check(ctx.lib.kz_assign_range_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, dtype, n_q, nnz, int(n_index), C.byref(lo), C.byref(hi),
+                                       C.byref(some)), "kz_assign_range_csr")
+    return (float(lo.value), float(hi.value)) if some.value else None
+
+
+def csr_transpose(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int) -> ListsTransposed:
+    """kz_csr_transpose -> the column-major view of the pairs of a float64 CSR pair list, as `lists_transpose` gives it for lists:
+    the entries of a column in ascending flat position (ascending source row).  The same arrays from every run."""
+    n_q, nnz = _f64_csr(indptr, ind, dist)
+    colptr = ctx.empty((int(n_index) + 1,), np.int64)
+    col_row, col_val = ctx.empty((nnz,), np.int32), ctx.empty((nnz,), np.float64)
+    used = _I64(0)
+    _check(ctx.lib.kz_csr_transpose(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, n_q, nnz, int(n_index), colptr.ptr, col_row.ptr,
+                                    col_val.ptr, C.byref(used)), "kz_csr_transpose")
+    return ListsTransposed(colptr, col_row, col_val, int(used.value), n_q, int(n_index))
+
+
+def softmin_csr_rows(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, eps: float,
+                     off: Optional[DeviceArray] = None, shift: float = 0.0) -> DeviceArray:
+    """kz_softmin_csr_rows -> float64 [n_q] on the device: per row of the CSR the soft-min over its PAIRS of (dist[p] - off[ind[p]]),
+    plus `shift`.  The summation tree of a row is the one `softmin_list_cols` gives a column of as many entries: the same bits as
+    that call on the view (colptr = indptr, col_row = ind, col_val = dist).  A row without a pair gives NaN."""
+    n_q, nnz = _f64_csr(indptr, ind, dist)
+    if off is not None:
+        _f64_vector("off", off, int(n_index))
+    out = ctx.empty((n_q,), np.float64)
+    _check(ctx.lib.kz_softmin_csr_rows(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, n_q, nnz, int(n_index), float(eps),
+                                       off.ptr if off is not None else None, float(shift), out.ptr), "kz_softmin_csr_rows")
+    return out
+
+
+def sinkhorn_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, eps: float, n_iter: int,
+                 tol: Optional[float] = None) -> Tuple[DeviceArray, DeviceArray, int, Optional[float]]:
+    """kz_sinkhorn_csr -> (f float64 [n_q], g float64 [n_index], iterations done, last measured change of g or None): `sinkhorn_lists`
+    over a CSR pair list -- the iteration of `softmin_list_cols` on `csr_transpose`'s view and `softmin_csr_rows`, queued at once."""
+    n_q, nnz = _f64_csr(indptr, ind, dist)
+    f, g = ctx.empty((n_q,), np.float64), ctx.empty((int(n_index),), np.float64)
+    done, change, measured = C.c_int(0), C.c_double(0.0), C.c_int(0)
+    _check(ctx.lib.kz_sinkhorn_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, n_q, nnz, int(n_index), float(eps), int(n_iter),
+                                   -1.0 if tol is None else float(tol), f.ptr, g.ptr, C.byref(done), C.byref(change), C.byref(measured)),
+           "kz_sinkhorn_csr")
+    return f, g, int(done.value), float(change.value) if measured.value else None
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):

@@ -19,6 +19,7 @@
 #include "kz_common.h"
 #include "kz_order_key.h"
 #include "kz_pool_buf.h"
+#include "kz_rows.h"   // KzRowsFixed, KzRowsCsr: the kernels below are instantiated for both (the CSR calls are at the end of the file)
 
 // rounds queued between two reads of the proposer counts: a read costs a stream synchronise, a surplus round three empty launches
 // (profiles/one_to_one.md; -DKZ_MATCH_ROUNDS=n builds the variants measured there)
@@ -60,18 +61,20 @@ __global__ __launch_bounds__(256) void kz_match_init_kernel(KzMatchState s, int 
     }
 }
 
-template <typename T>
+template <typename T, typename L>
 __global__ __launch_bounds__(256) void kz_match_propose_kernel(KzMatchState s, const T* __restrict__ dist, const int64_t* __restrict__ ind,
-                                                               int n_q, int k, int64_t n_index, unsigned* __restrict__ n_proposers) {
+                                                               int n_q, L rows, int64_t n_index, unsigned* __restrict__ n_proposers) {
     const int stride = gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_q; i += stride) {
         if (s.state[i] != KZ_MATCH_FREE) continue;
         int c = s.next[i];
+        const int k = rows.len(i);
         if (c >= k) continue;
+        const int64_t e0 = rows.start(i);
         for (; c < k; ++c) {
-            const int64_t t = ind[i * k + c];
+            const int64_t t = ind[e0 + c];
             if (t < 0 || t >= n_index) continue;   // no pair
-            const unsigned long long key = kz_knnr_key((double)dist[i * k + c]);
+            const unsigned long long key = kz_knnr_key((double)dist[e0 + c]);
             const unsigned long long hk = s.held_key[t];
             if (hk < key || (hk == key && s.held_row[t] < (int)i)) continue;   // the target holds a pair that beats this one for good
             atomicMin(s.prop_key + t, key);
@@ -83,13 +86,13 @@ __global__ __launch_bounds__(256) void kz_match_propose_kernel(KzMatchState s, c
     }
 }
 
-template <typename T>
+template <typename T, typename L>
 __global__ __launch_bounds__(256) void kz_match_tie_kernel(KzMatchState s, const T* __restrict__ dist, const int64_t* __restrict__ ind,
-                                                           int n_q, int k) {
+                                                           int n_q, L rows) {
     const int stride = gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_q; i += stride) {
         if (s.state[i] != KZ_MATCH_PROPOSING) continue;
-        const int64_t e = i * k + s.next[i];
+        const int64_t e = rows.start(i) + s.next[i];
         const int64_t t = ind[e];
         if (s.prop_key[t] == kz_knnr_key((double)dist[e])) atomicMin(s.prop_row + t, (int)i);
     }
@@ -99,15 +102,16 @@ __global__ __launch_bounds__(256) void kz_match_tie_kernel(KzMatchState s, const
 // relaxed agent-scope atomics, and a proposer that is not the winner finds "not mine" in either version -- no proposer has the key
 // KZ_KNNR_PAD.  The displaced source is engaged, so no proposer: its own thread reads its state and does nothing, whichever version
 // it sees; only the winner writes it.
-template <typename T>
+template <typename T, typename L>
 __global__ __launch_bounds__(256) void kz_match_resolve_kernel(KzMatchState s, const T* __restrict__ dist, const int64_t* __restrict__ ind,
-                                                               int n_q, int k, int64_t* __restrict__ match, int64_t* __restrict__ col) {
+                                                               int n_q, L rows, int64_t* __restrict__ match, int64_t* __restrict__ col) {
     const int stride = gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_q; i += stride) {
         if (s.state[i] != KZ_MATCH_PROPOSING) continue;
         const int c = s.next[i];
-        const int64_t t = ind[i * k + c];
-        const unsigned long long key = kz_knnr_key((double)dist[i * k + c]);
+        const int64_t e = rows.start(i) + c;
+        const int64_t t = ind[e];
+        const unsigned long long key = kz_knnr_key((double)dist[e]);
         const bool won = __hip_atomic_load(s.prop_key + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == key &&
                          __hip_atomic_load(s.prop_row + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)i;
         if (!won) {
@@ -133,13 +137,24 @@ __global__ __launch_bounds__(256) void kz_match_resolve_kernel(KzMatchState s, c
 }
 
 // d_out[i] = d_dist[i, d_col[i]], NaN where d_col[i] < 0
-template <typename T>
-__global__ __launch_bounds__(256) void kz_match_values_kernel(const T* __restrict__ dist, const int64_t* __restrict__ col, int n_q, int k,
+template <typename T, typename L>
+__global__ __launch_bounds__(256) void kz_match_values_kernel(const T* __restrict__ dist, const int64_t* __restrict__ col, int n_q, L rows,
                                                               T* __restrict__ out) {
     const int stride = gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_q; i += stride) {
         const int64_t c = col[i];
-        out[i] = c >= 0 && c < k ? dist[i * k + c] : (T)NAN;
+        out[i] = c >= 0 && c < rows.len(i) ? dist[rows.start(i) + c] : (T)NAN;
+    }
+}
+
+// ---- a CSR's indptr, checked before anything reads through it (shared with kz_assign.hip and kz_softmin_lists.hip) -------------
+// flag |= 1 unless indptr[0] == 0, indptr[i - 1] <= indptr[i] for every i and indptr[n_q] == nnz: together, every row lies in [0, nnz)
+__global__ __launch_bounds__(256) void kz_csr_validate_kernel(const int64_t* __restrict__ indptr, int64_t n_q, int64_t nnz, int* __restrict__ flag) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n_q; i += stride) {
+        const int64_t v = indptr[i];
+        const bool bad = (i == 0 && v != 0) || (i == n_q && v != nnz) || (i > 0 && indptr[i - 1] > v);
+        if (bad) atomicOr(flag, 1);
     }
 }
 
@@ -148,9 +163,10 @@ static int kz_match_blocks(int64_t n) {
     return (int)(b < 1 ? 1 : b < KZ_MATCH_BLOCKS ? b : KZ_MATCH_BLOCKS);
 }
 
-template <typename T>
-static int kz_match_lists_impl(kz_ctx* ctx, const T* d_dist, const int64_t* d_ind, int n_q, int k, int64_t n_index, int64_t* d_match,
-                               int64_t* d_col, int64_t* h_rounds) {
+// max_rounds: every round with a proposer advances a column pointer or fills an empty target -- entries + n_index
+template <typename T, typename L>
+static int kz_match_lists_impl(const char* who, kz_ctx* ctx, const T* d_dist, const int64_t* d_ind, int n_q, L rows, int64_t max_rounds,
+                               int64_t n_index, int64_t* d_match, int64_t* d_col, int64_t* h_rounds) {
     // (released when the function returns, behind its last synchronise)
     KzPoolBuf<unsigned long long> held_key, prop_key;
     KzPoolBuf<int> held_row, prop_row, next, state;
@@ -167,19 +183,17 @@ static int kz_match_lists_impl(kz_ctx* ctx, const T* d_dist, const int64_t* d_in
     const dim3 grid(kz_match_blocks(n_q)), block(256);
     hipLaunchKernelGGL(kz_match_init_kernel, dim3(kz_match_blocks(n_q > n_index ? n_q : n_index)), block, 0, ctx->stream, s, n_q,
                        (int)n_index, d_match, d_col);
-    // every round with a proposer advances a column pointer or fills an empty target
-    const int64_t max_rounds = (int64_t)n_q * k + n_index;
     int64_t rounds = 0, queued = 0;
     for (bool busy = true; busy;) {
         if (queued > max_rounds) {
-            kz_set_error("kz_match_lists: %lld rounds and still a proposer (the bound is %lld)", (long long)queued, (long long)max_rounds);
+            kz_set_error("%s: %lld rounds and still a proposer (the bound is %lld)", who, (long long)queued, (long long)max_rounds);
             return KZ_ERR_HIP;
         }
         KZ_HIP(hipMemsetAsync(counts.get(), 0, KZ_MATCH_ROUNDS_PER_READ * sizeof(unsigned), ctx->stream));
         for (int r = 0; r < KZ_MATCH_ROUNDS_PER_READ; ++r) {
-            hipLaunchKernelGGL(kz_match_propose_kernel<T>, grid, block, 0, ctx->stream, s, d_dist, d_ind, n_q, k, n_index, counts.get() + r);
-            hipLaunchKernelGGL(kz_match_tie_kernel<T>, grid, block, 0, ctx->stream, s, d_dist, d_ind, n_q, k);
-            hipLaunchKernelGGL(kz_match_resolve_kernel<T>, grid, block, 0, ctx->stream, s, d_dist, d_ind, n_q, k, d_match, d_col);
+            hipLaunchKernelGGL((kz_match_propose_kernel<T, L>), grid, block, 0, ctx->stream, s, d_dist, d_ind, n_q, rows, n_index, counts.get() + r);
+            hipLaunchKernelGGL((kz_match_tie_kernel<T, L>), grid, block, 0, ctx->stream, s, d_dist, d_ind, n_q, rows);
+            hipLaunchKernelGGL((kz_match_resolve_kernel<T, L>), grid, block, 0, ctx->stream, s, d_dist, d_ind, n_q, rows, d_match, d_col);
         }
         KZ_HIP(hipGetLastError());
         queued += KZ_MATCH_ROUNDS_PER_READ;
@@ -213,8 +227,10 @@ extern "C" int kz_match_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, c
     KZ_REQUIRE(d_ind && d_match && d_col, "kz_match_lists: null argument");
     KZ_HIP(hipSetDevice(ctx->device));
     if (dist_dtype == KZ_F32)
-        return kz_match_lists_impl(ctx, (const float*)d_dist, d_ind, (int)n_q, k, n_index, d_match, d_col, h_rounds);
-    return kz_match_lists_impl(ctx, (const double*)d_dist, d_ind, (int)n_q, k, n_index, d_match, d_col, h_rounds);
+        return kz_match_lists_impl("kz_match_lists", ctx, (const float*)d_dist, d_ind, (int)n_q, KzRowsFixed{k}, n_q * k + n_index, n_index, d_match,
+                                   d_col, h_rounds);
+    return kz_match_lists_impl("kz_match_lists", ctx, (const double*)d_dist, d_ind, (int)n_q, KzRowsFixed{k}, n_q * k + n_index, n_index, d_match,
+                               d_col, h_rounds);
 }
 
 extern "C" int kz_match_values(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q, int k, void* d_out) {
@@ -225,9 +241,76 @@ extern "C" int kz_match_values(kz_ctx* ctx, const void* d_dist, int dist_dtype, 
     KZ_HIP(hipSetDevice(ctx->device));
     const dim3 grid(kz_match_blocks(n_q)), block(256);
     if (dist_dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_match_values_kernel<float>, grid, block, 0, ctx->stream, (const float*)d_dist, d_col, (int)n_q, k, (float*)d_out);
+        hipLaunchKernelGGL((kz_match_values_kernel<float, KzRowsFixed>), grid, block, 0, ctx->stream, (const float*)d_dist, d_col, (int)n_q,
+                           KzRowsFixed{k}, (float*)d_out);
     else
-        hipLaunchKernelGGL(kz_match_values_kernel<double>, grid, block, 0, ctx->stream, (const double*)d_dist, d_col, (int)n_q, k, (double*)d_out);
+        hipLaunchKernelGGL((kz_match_values_kernel<double, KzRowsFixed>), grid, block, 0, ctx->stream, (const double*)d_dist, d_col, (int)n_q,
+                           KzRowsFixed{k}, (double*)d_out);
+    KZ_HIP(hipGetLastError());
+    return KZ_OK;
+}
+
+// ---- the CSR layout --------------------------------------------------------------------------------------------------------------
+// the limits every CSR call shares (shared with kz_assign.hip and kz_softmin_lists.hip)
+int kz_csr_require(const char* who, kz_ctx* ctx, int64_t n_q, int64_t nnz, int64_t n_index) {
+    KZ_REQUIRE(ctx != nullptr, "%s: null context", who);
+    KZ_REQUIRE(n_q >= 0 && n_q < 0x7fffffffLL, "%s: n_q = %lld is outside [0, 2^31 - 1)", who, (long long)n_q);
+    KZ_REQUIRE(nnz >= 0 && nnz < 0x7fffffffLL, "%s: nnz = %lld entries, the limit is 2^31 - 2", who, (long long)nnz);
+    KZ_REQUIRE(n_index >= 1 && n_index < 0x7fffffffLL, "%s: n_index = %lld is outside [1, 2^31 - 1)", who, (long long)n_index);
+    return KZ_OK;
+}
+
+// Runs the check kernel and READS ITS FLAG: nothing that reads through d_indptr is queued before this returns KZ_OK.
+int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz) {
+    KZ_REQUIRE(d_indptr != nullptr, "%s: null indptr", who);
+    KzPoolBuf<int> flag;
+    const int rc = flag.alloc(ctx, 16);
+    if (rc != KZ_OK) return rc;
+    KZ_HIP(hipMemsetAsync(flag.get(), 0, 16, ctx->stream));
+    hipLaunchKernelGGL(kz_csr_validate_kernel, dim3(kz_match_blocks(n_q + 1)), dim3(256), 0, ctx->stream, d_indptr, n_q, nnz, flag.get());
+    KZ_HIP(hipGetLastError());
+    int h_flag = 0;
+    KZ_HIP(hipMemcpyAsync(&h_flag, flag.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    KZ_REQUIRE(h_flag == 0, "%s: indptr must start at 0, never decrease and end at nnz = %lld", who, (long long)nnz);
+    return KZ_OK;
+}
+
+extern "C" int kz_match_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const void* d_dist, int dist_dtype, int64_t n_q,
+                            int64_t nnz, int64_t n_index, int64_t* d_match, int64_t* d_col, int64_t* h_rounds) {
+    const int rcq = kz_csr_require("kz_match_csr", ctx, n_q, nnz, n_index);
+    if (rcq != KZ_OK) return rcq;
+    KZ_REQUIRE(dist_dtype == KZ_F32 || dist_dtype == KZ_F64, "kz_match_csr: dist_dtype must be KZ_F32 or KZ_F64, got %d", dist_dtype);
+    if (h_rounds) *h_rounds = 0;
+    if (n_q == 0) return KZ_OK;
+    KZ_REQUIRE(d_match && d_col && (nnz == 0 || (d_ind && d_dist)), "kz_match_csr: null argument");
+    KZ_HIP(hipSetDevice(ctx->device));
+    const int rcv = kz_csr_validate("kz_match_csr", ctx, d_indptr, n_q, nnz);
+    if (rcv != KZ_OK) return rcv;
+    if (dist_dtype == KZ_F32)
+        return kz_match_lists_impl("kz_match_csr", ctx, (const float*)d_dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz + n_index, n_index, d_match,
+                                   d_col, h_rounds);
+    return kz_match_lists_impl("kz_match_csr", ctx, (const double*)d_dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz + n_index, n_index, d_match,
+                               d_col, h_rounds);
+}
+
+extern "C" int kz_match_values_csr(kz_ctx* ctx, const int64_t* d_indptr, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q,
+                                   int64_t nnz, void* d_out) {
+    const int rcq = kz_csr_require("kz_match_values_csr", ctx, n_q, nnz, 1);
+    if (rcq != KZ_OK) return rcq;
+    KZ_REQUIRE(dist_dtype == KZ_F32 || dist_dtype == KZ_F64, "kz_match_values_csr: dist_dtype must be KZ_F32 or KZ_F64, got %d", dist_dtype);
+    if (n_q == 0) return KZ_OK;
+    KZ_REQUIRE(d_col && d_out && (nnz == 0 || d_dist), "kz_match_values_csr: null argument");
+    KZ_HIP(hipSetDevice(ctx->device));
+    const int rcv = kz_csr_validate("kz_match_values_csr", ctx, d_indptr, n_q, nnz);
+    if (rcv != KZ_OK) return rcv;
+    const dim3 grid(kz_match_blocks(n_q)), block(256);
+    if (dist_dtype == KZ_F32)
+        hipLaunchKernelGGL((kz_match_values_kernel<float, KzRowsCsr>), grid, block, 0, ctx->stream, (const float*)d_dist, d_col, (int)n_q,
+                           KzRowsCsr{d_indptr}, (float*)d_out);
+    else
+        hipLaunchKernelGGL((kz_match_values_kernel<double, KzRowsCsr>), grid, block, 0, ctx->stream, (const double*)d_dist, d_col, (int)n_q,
+                           KzRowsCsr{d_indptr}, (double*)d_out);
     KZ_HIP(hipGetLastError());
     return KZ_OK;
 }

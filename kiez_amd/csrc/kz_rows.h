@@ -1,0 +1,25 @@
+// THE ROW LAYOUT of a pair list: where row i starts in dist / ind and how many entries it has.  Every kernel of kz_match.hip and
+// kz_assign.hip that walks a row is instantiated once per layout -- one rule, one body: KzRowsFixed the [n_q, k] neighbour lists,
+// KzRowsCsr a CSR's indptr.  A CSR's indptr is checked by kz_csr_validate BEFORE any kernel that reads through it is queued.
+#pragma once
+#include "kz_common.h"
+
+struct KzRowsFixed {
+    int k;
+    __device__ __forceinline__ int64_t start(int64_t i) const { return i * k; }
+    __device__ __forceinline__ int len(int64_t) const { return k; }
+    __device__ __forceinline__ bool is_long(int64_t) const { return false; }   // (kz_assign.hip: no wave bid, whatever k is)
+};
+
+// a row with more entries than this bids with one wave in kz_assign_csr (include/kiez_amd.h; -DKZ_CSR_LONG_ROW=2147483647 builds
+// the library without the wave path, the variant profiles/csr_lists.md measures it against)
+struct KzRowsCsr {
+    const int64_t* __restrict__ indptr;
+    __device__ __forceinline__ int64_t start(int64_t i) const { return indptr[i]; }
+    __device__ __forceinline__ int len(int64_t i) const { return (int)(indptr[i + 1] - indptr[i]); }   // (nnz < 2^31)
+    __device__ __forceinline__ bool is_long(int64_t i) const { return indptr[i + 1] - indptr[i] > (int64_t)KZ_CSR_LONG_ROW; }
+};
+
+// kz_match.hip: the limits every CSR call shares; the check kernel over indptr with its flag read back (synchronises the stream)
+int kz_csr_require(const char* who, kz_ctx* ctx, int64_t n_q, int64_t nnz, int64_t n_index);
+int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz);

@@ -167,26 +167,37 @@ __global__ __launch_bounds__(256) void kz_sl_rows_wave_kernel(const double* __re
 // ---- (b) columns ---------------------------------------------------------------------------------------------------------------
 // One wave: (m, s) of the entries [p0, p1) of a column, p1 - p0 <= KZ_SL_CHUNK.  Lane l holds the entries p0 + l, p0 + l + 64, ... in
 // registers; places behind p1 are +inf and add exact zeros, so the tree is that of a full chunk.  Every lane returns the same part.
-__device__ __forceinline__ KzSoftminPart kz_sl_chunk(const int* __restrict__ col_row, const double* __restrict__ col_val, int64_t p0, int64_t p1,
-                                                     const double* __restrict__ off, double eps, int lane) {
+// I: the type of the ids beside the values -- int32 source rows in the view kz_lists_transpose writes, int64 target ids where the
+// "columns" are the ROWS of a CSR (kz_softmin_csr_rows).  CHECK (the CSR rows): an id outside [0, n_off) is no pair -- +inf, an exact
+// zero in the same place of the same tree, and off is not read --, and a chunk without any pair is (+inf, -1): the mark the fold
+// turns into NaN (kz_softmin_rescaled gives 0 for any +inf part).  Without CHECK every entry is a pair, as the view holds pairs only.
+template <typename I, bool CHECK>
+__device__ __forceinline__ KzSoftminPart kz_sl_chunk(const I* __restrict__ col_row, const double* __restrict__ col_val, int64_t p0, int64_t p1,
+                                                     const double* __restrict__ off, int64_t n_off, double eps, int lane) {
     constexpr int U = KZ_SL_CHUNK / 64;
     double x[U];
     double m = INFINITY;
+    bool any = false;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int64_t p = p0 + 64 * u + lane;
         double xu = INFINITY;
         if (p < p1) {
-            xu = col_val[p];
-            if (off) xu = xu - off[col_row[p]];
-            xu = xu == xu ? xu : INFINITY;
+            const int64_t r = CHECK || off ? (int64_t)col_row[p] : 0;
+            if (!CHECK || (r >= 0 && r < n_off)) {
+                any = true;
+                xu = col_val[p];
+                if (off) xu = xu - off[r];
+                xu = xu == xu ? xu : INFINITY;
+            }
         }
         x[u] = xu;
         m = kz_sl_min(m, xu);
     }
 #pragma unroll
     for (int sh = 32; sh >= 1; sh >>= 1) m = kz_sl_min(m, __shfl_xor(m, sh, 64));
-    if (m == INFINITY || m == -INFINITY) return KzSoftminPart{m, m < 0.0 ? 1.0 : 0.0};   // (wave-uniform)
+    if (CHECK && m == INFINITY) return KzSoftminPart{m, __ballot(any) != 0ull ? 0.0 : -1.0};   // (wave-uniform, as the next)
+    if (m == INFINITY || m == -INFINITY) return KzSoftminPart{m, m < 0.0 ? 1.0 : 0.0};
     double s = 0.0;
 #pragma unroll
     for (int u = 0; u < U; ++u) s += kz_sl_term(x[u], m, eps);
@@ -208,6 +219,20 @@ __device__ __forceinline__ int64_t kz_sl_column_of(const int64_t* __restrict__ c
     return lo;
 }
 
+// the gather behind the sort of a CSR's entries: the source row of flat position q is the row of indptr that holds it (empty rows
+// hold nothing: the search steps over them)
+__global__ __launch_bounds__(256) void kz_sl_gather_csr_kernel(const int* __restrict__ key, const int* __restrict__ pos, int total,
+                                                               const int64_t* __restrict__ indptr, int64_t n_q, int64_t n_index,
+                                                               const double* __restrict__ dist, int* __restrict__ col_row, double* __restrict__ col_val) {
+    const int stride = gridDim.x * blockDim.x;
+    for (int64_t p = blockIdx.x * blockDim.x + threadIdx.x; p < total; p += stride) {
+        if (key[p] >= n_index) continue;
+        const int q = pos[p];
+        col_row[p] = (int)kz_sl_column_of(indptr, n_q, q);
+        col_val[p] = dist[q];
+    }
+}
+
 // where the part of chunk c of a column that starts at place `start` lies: chunk starts of one column are KZ_SL_CHUNK apart, and a
 // LONG column (more than one chunk) spans more than a block of KZ_SL_CHUNK places, so a block [b C, (b + 1) C) of places holds at
 // most two chunk starts of long columns -- one of a later chunk (c >= 1: slot 0; its column holds place b C) and one of a first
@@ -216,9 +241,10 @@ __device__ __forceinline__ int64_t kz_sl_part_slot(int64_t start, int64_t c) { r
 
 // Level 1, the LONG columns only: wave w = (block b of KZ_SL_CHUNK places, slot) finds the chunk start of its slot by binary search
 // in colptr, if there is one, and writes the chunk's part.  The grid covers the capacity of the view; blocks behind nnz return.
-__global__ __launch_bounds__(256) void kz_sl_cols_chunk_kernel(const int64_t* __restrict__ colptr, const int* __restrict__ col_row,
+template <typename I, bool CHECK>
+__global__ __launch_bounds__(256) void kz_sl_cols_chunk_kernel(const int64_t* __restrict__ colptr, const I* __restrict__ col_row,
                                                                const double* __restrict__ col_val, int64_t n_index, int64_t capacity, double eps,
-                                                               const double* __restrict__ off, KzSoftminPart* __restrict__ part,
+                                                               const double* __restrict__ off, int64_t n_off, KzSoftminPart* __restrict__ part,
                                                                const int* __restrict__ stop, int it) {
     if (kz_sl_stopped(stop, it)) return;
     const int lane = threadIdx.x & 63;
@@ -243,16 +269,18 @@ __global__ __launch_bounds__(256) void kz_sl_cols_chunk_kernel(const int64_t* __
         p0 = start;
     }
     const int64_t p1 = p0 + KZ_SL_CHUNK < end ? p0 + KZ_SL_CHUNK : end;
-    const KzSoftminPart pt = kz_sl_chunk(col_row, col_val, p0, p1, off, eps, lane);
+    const KzSoftminPart pt = kz_sl_chunk<I, CHECK>(col_row, col_val, p0, p1, off, n_off, eps, lane);
     if (lane == 0) part[2 * b + slot] = pt;
 }
 
 // Level 2: one wave per column, four columns per workgroup.  No entry: NaN.  One chunk: reduced here.  More: the parts of level 1
 // folded as kz_softmin_fold_kernel folds those of kz_softmin_rows.
-__global__ __launch_bounds__(256) void kz_sl_cols_kernel(const int64_t* __restrict__ colptr, const int* __restrict__ col_row,
+template <typename I, bool CHECK>
+__global__ __launch_bounds__(256) void kz_sl_cols_kernel(const int64_t* __restrict__ colptr, const I* __restrict__ col_row,
                                                          const double* __restrict__ col_val, int64_t n_index, int64_t capacity, double eps,
-                                                         const double* __restrict__ off, double shift, const KzSoftminPart* __restrict__ part,
-                                                         double* __restrict__ out, const int* __restrict__ stop, int it) {
+                                                         const double* __restrict__ off, int64_t n_off, double shift,
+                                                         const KzSoftminPart* __restrict__ part, double* __restrict__ out,
+                                                         const int* __restrict__ stop, int it) {
     if (kz_sl_stopped(stop, it)) return;
     const int lane = threadIdx.x & 63;
     const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -263,8 +291,8 @@ __global__ __launch_bounds__(256) void kz_sl_cols_kernel(const int64_t* __restri
         return;
     }
     if (n <= KZ_SL_CHUNK) {
-        const KzSoftminPart pt = kz_sl_chunk(col_row, col_val, start, end, off, eps, lane);
-        if (lane == 0) out[j] = kz_sl_finish(pt.m, pt.s, eps, shift);
+        const KzSoftminPart pt = kz_sl_chunk<I, CHECK>(col_row, col_val, start, end, off, n_off, eps, lane);
+        if (lane == 0) out[j] = CHECK && pt.m == INFINITY && pt.s < 0.0 ? (double)NAN : kz_sl_finish(pt.m, pt.s, eps, shift);
         return;
     }
     const int64_t n_chunks = (n + KZ_SL_CHUNK - 1) / KZ_SL_CHUNK;
@@ -272,6 +300,14 @@ __global__ __launch_bounds__(256) void kz_sl_cols_kernel(const int64_t* __restri
     for (int64_t c = lane; c < n_chunks; c += 64) m = kz_sl_min(m, part[kz_sl_part_slot(start, c)].m);
 #pragma unroll
     for (int sh = 32; sh >= 1; sh >>= 1) m = kz_sl_min(m, __shfl_xor(m, sh, 64));
+    if (CHECK && m == INFINITY) {   // (every part is +inf: a pair in any of them?)
+        bool any = false;
+        for (int64_t c = lane; c < n_chunks; c += 64) any = any || part[kz_sl_part_slot(start, c)].s >= 0.0;
+        if (__ballot(any) == 0ull) {
+            if (lane == 0) out[j] = (double)NAN;
+            return;
+        }
+    }
     if (m == INFINITY || m == -INFINITY) {
         if (lane == 0) out[j] = kz_sl_finish(m, 0.0, eps, shift);
         return;
@@ -353,20 +389,24 @@ void kz_sl_rows_launch(kz_ctx* ctx, const double* dist, const int64_t* ind, int 
 // capacity: the places the view may hold (>= nnz); part: 2 ceil(capacity / KZ_SL_CHUNK) parts
 int64_t kz_sl_part_count(int64_t capacity) { return 2 * ((capacity + KZ_SL_CHUNK - 1) / KZ_SL_CHUNK); }
 
-void kz_sl_cols_launch(kz_ctx* ctx, const int64_t* colptr, const int* col_row, const double* col_val, int64_t n_index, int64_t capacity, double eps,
-                       const double* off, double shift, KzSoftminPart* part, double* out, const int* stop, int it) {
+// <int, false>: the columns of a transposed view (n_off unused).  <int64_t, true>: the ROWS of a CSR -- colptr = indptr, n_index = its
+// row count, col_row = ind, n_off = the number of target rows.
+template <typename I, bool CHECK>
+void kz_sl_cols_launch(kz_ctx* ctx, const int64_t* colptr, const I* col_row, const double* col_val, int64_t n_index, int64_t capacity, double eps,
+                       const double* off, int64_t n_off, double shift, KzSoftminPart* part, double* out, const int* stop, int it) {
     const int64_t n_blocks = (capacity + KZ_SL_CHUNK - 1) / KZ_SL_CHUNK;
     if (n_blocks > 0)   // (two waves per block of places, four waves per workgroup)
-        hipLaunchKernelGGL(kz_sl_cols_chunk_kernel, dim3((unsigned)((2 * n_blocks + 3) / 4)), dim3(256), 0, ctx->stream, colptr, col_row, col_val,
-                           n_index, capacity, eps, off, part, stop, it);
-    hipLaunchKernelGGL(kz_sl_cols_kernel, dim3((unsigned)((n_index + 3) / 4)), dim3(256), 0, ctx->stream, colptr, col_row, col_val, n_index, capacity, eps,
-                       off, shift, part, out, stop, it);
+        hipLaunchKernelGGL((kz_sl_cols_chunk_kernel<I, CHECK>), dim3((unsigned)((2 * n_blocks + 3) / 4)), dim3(256), 0, ctx->stream, colptr, col_row,
+                           col_val, n_index, capacity, eps, off, n_off, part, stop, it);
+    hipLaunchKernelGGL((kz_sl_cols_kernel<I, CHECK>), dim3((unsigned)((n_index + 3) / 4)), dim3(256), 0, ctx->stream, colptr, col_row, col_val, n_index,
+                       capacity, eps, off, n_off, shift, part, out, stop, it);
 }
 
-// the whole transposition, queued: keys, the stable sort, the gather, colptr
+// the whole transposition, queued: keys, the stable sort, the gather, colptr.  d_indptr NULL: the [n_q, k] lists; else a CSR of
+// nnz > 0 entries (k unused), its flat position p the secondary key as i k + c is here.
 int kz_sl_transpose(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index, int64_t* d_colptr, int* d_col_row,
-                    double* d_col_val) {
-    const int total = (int)(n_q * k);
+                    double* d_col_val, const int64_t* d_indptr = nullptr, int64_t nnz = 0) {
+    const int total = (int)(d_indptr ? nnz : n_q * k);
     // (released when the function returns, stream-ordered behind the kernels that read them)
     KzPoolBuf<int> key_in, val_in, key_out, val_out;
     int rc = key_in.alloc(ctx, (size_t)total * 4);
@@ -380,8 +420,12 @@ int kz_sl_transpose(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int
     rc = kz_sort_pairs_f32_i32(ctx, reinterpret_cast<const float*>(key_in.get()), reinterpret_cast<float*>(key_out.get()), val_in.get(),
                                val_out.get(), total, 0);
     if (rc != KZ_OK) return rc;
-    hipLaunchKernelGGL(kz_sl_gather_kernel, dim3(kz_sl_blocks(total)), dim3(256), 0, ctx->stream, (const int*)key_out.get(), (const int*)val_out.get(),
-                       total, k, n_index, d_dist, d_col_row, d_col_val);
+    if (d_indptr)
+        hipLaunchKernelGGL(kz_sl_gather_csr_kernel, dim3(kz_sl_blocks(total)), dim3(256), 0, ctx->stream, (const int*)key_out.get(),
+                           (const int*)val_out.get(), total, d_indptr, n_q, n_index, d_dist, d_col_row, d_col_val);
+    else
+        hipLaunchKernelGGL(kz_sl_gather_kernel, dim3(kz_sl_blocks(total)), dim3(256), 0, ctx->stream, (const int*)key_out.get(), (const int*)val_out.get(),
+                           total, k, n_index, d_dist, d_col_row, d_col_val);
     hipLaunchKernelGGL(kz_sl_colptr_kernel, dim3(kz_sl_blocks(n_index + 1)), dim3(256), 0, ctx->stream, (const int*)key_out.get(), total, n_index,
                        d_colptr);
     KZ_HIP(hipGetLastError());
@@ -438,7 +482,7 @@ extern "C" int kz_softmin_list_cols(kz_ctx* ctx, const int64_t* d_colptr, const 
     KzPoolBuf<KzSoftminPart> part;   // (released when the function returns, behind its synchronise)
     const int rc = part.alloc(ctx, (size_t)(kz_sl_part_count(nnz) + 1) * sizeof(KzSoftminPart));
     if (rc != KZ_OK) return rc;
-    kz_sl_cols_launch(ctx, d_colptr, d_col_row, d_col_val, n_index, nnz, eps, d_off, shift, part.get(), d_out, nullptr, 0);
+    kz_sl_cols_launch<int, false>(ctx, d_colptr, d_col_row, d_col_val, n_index, nnz, eps, d_off, 0, shift, part.get(), d_out, nullptr, 0);
     KZ_HIP(hipGetLastError());
     KZ_HIP(hipStreamSynchronize(ctx->stream));
     return KZ_OK;
@@ -482,8 +526,8 @@ extern "C" int kz_sinkhorn_lists(kz_ctx* ctx, const double* d_dist, const int64_
     double* g_buf[2] = {g2.get(), g2.get() + n_index};
     for (int it = 1; it <= n_iter; ++it) {
         double* g_new = g_buf[it & 1];
-        kz_sl_cols_launch(ctx, colptr.get(), col_row.get(), col_val.get(), n_index, total, eps, it == 1 ? nullptr : d_f, shift, part.get(), g_new,
-                          stop.get(), it);
+        kz_sl_cols_launch<int, false>(ctx, colptr.get(), col_row.get(), col_val.get(), n_index, total, eps, it == 1 ? nullptr : d_f, 0, shift,
+                                      part.get(), g_new, stop.get(), it);
         if (it >= 2) {
             hipLaunchKernelGGL(kz_sl_change_kernel, dim3(kz_sl_blocks(n_index)), dim3(256), 0, ctx->stream, (const double*)g_new,
                                (const double*)g_buf[(it - 1) & 1], n_index, slot.get(), (const int*)stop.get(), it);
@@ -493,6 +537,125 @@ extern "C" int kz_sinkhorn_lists(kz_ctx* ctx, const double* d_dist, const int64_
     }
     KZ_HIP(hipGetLastError());
     // the one read: where the loop stopped and every iteration's change; then g of that iteration
+    int h_stop[4] = {0, 0, 0, 0};
+    std::unique_ptr<unsigned long long[]> h_slot(new unsigned long long[n_iter + 1]);
+    KZ_HIP(hipMemcpyAsync(h_stop, stop.get(), 16, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(h_slot.get(), slot.get(), (size_t)(n_iter + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    const int done = h_stop[0] != 0 ? h_stop[0] : n_iter;
+    KZ_HIP(hipMemcpyAsync(d_g, g_buf[done & 1], (size_t)n_index * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    if (h_n_iter) *h_n_iter = done;
+    if (done >= 2) {
+        if (h_change) memcpy(h_change, &h_slot[done], 8);
+        if (h_measured) *h_measured = 1;
+    }
+    return KZ_OK;
+}
+
+// ---- the CSR layout (include/kiez_amd.h: "the same three steps on RAGGED (CSR) pair lists") ------------------------------------
+int kz_csr_require(const char* who, kz_ctx* ctx, int64_t n_q, int64_t nnz, int64_t n_index);                     // kz_match.hip
+int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz);            // kz_match.hip
+
+extern "C" int kz_csr_transpose(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
+                                int64_t n_index, int64_t* d_colptr, int32_t* d_col_row, double* d_col_val, int64_t* h_nnz) {
+    const int rcq = kz_csr_require("kz_csr_transpose", ctx, n_q, nnz, n_index);
+    if (rcq != KZ_OK) return rcq;
+    KZ_REQUIRE(d_colptr != nullptr, "kz_csr_transpose: null colptr");
+    if (h_nnz) *h_nnz = 0;
+    KZ_HIP(hipSetDevice(ctx->device));
+    if (n_q > 0) {
+        const int rcv = kz_csr_validate("kz_csr_transpose", ctx, d_indptr, n_q, nnz);
+        if (rcv != KZ_OK) return rcv;
+    }
+    if (n_q == 0 || nnz == 0) {   // (no entry: every column is empty)
+        KZ_HIP(hipMemsetAsync(d_colptr, 0, (size_t)(n_index + 1) * 8, ctx->stream));
+        if (h_nnz) KZ_HIP(hipStreamSynchronize(ctx->stream));
+        return KZ_OK;
+    }
+    KZ_REQUIRE(d_dist && d_ind && d_col_row && d_col_val, "kz_csr_transpose: null argument");
+    const int rc = kz_sl_transpose(ctx, d_dist, d_ind, n_q, 0, n_index, d_colptr, d_col_row, d_col_val, d_indptr, nnz);
+    if (rc != KZ_OK) return rc;
+    if (h_nnz) {
+        KZ_HIP(hipMemcpyAsync(h_nnz, d_colptr + n_index, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KZ_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return KZ_OK;
+}
+
+extern "C" int kz_softmin_csr_rows(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
+                                   int64_t n_index, double eps, const double* d_off, double shift, double* d_out) {
+    int rc = kz_csr_require("kz_softmin_csr_rows", ctx, n_q, nnz, n_index);
+    if (rc == KZ_OK) rc = kz_sl_require_eps("kz_softmin_csr_rows", eps, shift);
+    if (rc != KZ_OK) return rc;
+    if (n_q == 0) return KZ_OK;
+    KZ_REQUIRE(d_out && (nnz == 0 || (d_dist && d_ind)), "kz_softmin_csr_rows: null argument");
+    KZ_HIP(hipSetDevice(ctx->device));
+    rc = kz_csr_validate("kz_softmin_csr_rows", ctx, d_indptr, n_q, nnz);
+    if (rc != KZ_OK) return rc;
+    KzPoolBuf<KzSoftminPart> part;   // (released when the function returns, behind its synchronise)
+    rc = part.alloc(ctx, (size_t)(kz_sl_part_count(nnz) + 1) * sizeof(KzSoftminPart));
+    if (rc != KZ_OK) return rc;
+    kz_sl_cols_launch<int64_t, true>(ctx, d_indptr, d_ind, d_dist, n_q, nnz, eps, d_off, n_index, shift, part.get(), d_out, nullptr, 0);
+    KZ_HIP(hipGetLastError());
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    return KZ_OK;
+}
+
+extern "C" int kz_sinkhorn_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
+                               int64_t n_index, double eps, int n_iter, double tol, double* d_f, double* d_g, int* h_n_iter, double* h_change,
+                               int* h_measured) {
+    const int rcq = kz_csr_require("kz_sinkhorn_csr", ctx, n_q, nnz, n_index);
+    if (rcq != KZ_OK) return rcq;
+    KZ_REQUIRE(eps > 0.0 && eps < INFINITY, "kz_sinkhorn_csr: the temperature eps must be finite and > 0, got %g", eps);
+    KZ_REQUIRE(n_iter >= 1, "kz_sinkhorn_csr: n_iter must be >= 1, got %d", n_iter);
+    KZ_REQUIRE(tol == tol, "kz_sinkhorn_csr: tol is NaN (negative: no tolerance)");
+    if (h_n_iter) *h_n_iter = 0;
+    if (h_change) *h_change = 0.0;
+    if (h_measured) *h_measured = 0;
+    if (n_q == 0) return KZ_OK;
+    KZ_REQUIRE(d_f && d_g && (nnz == 0 || (d_dist && d_ind)), "kz_sinkhorn_csr: null argument");
+    KZ_HIP(hipSetDevice(ctx->device));
+    int rc = kz_csr_validate("kz_sinkhorn_csr", ctx, d_indptr, n_q, nnz);
+    if (rc != KZ_OK) return rc;
+    const bool with_tol = tol >= 0.0;
+    // (released when the function returns, behind its last synchronise: the view lives for the call, g is double-buffered; the row
+    //  and the column step share the parts -- they follow each other on the stream)
+    KzPoolBuf<int64_t> colptr;
+    KzPoolBuf<int> col_row, stop;
+    KzPoolBuf<double> col_val, g2;
+    KzPoolBuf<KzSoftminPart> part;
+    KzPoolBuf<unsigned long long> slot;
+    rc = colptr.alloc(ctx, (size_t)(n_index + 1) * 8);
+    if (rc == KZ_OK) rc = col_row.alloc(ctx, (size_t)(nnz + 1) * 4);
+    if (rc == KZ_OK) rc = col_val.alloc(ctx, (size_t)(nnz + 1) * 8);
+    if (rc == KZ_OK) rc = g2.alloc(ctx, (size_t)n_index * 2 * 8);
+    if (rc == KZ_OK) rc = part.alloc(ctx, (size_t)(kz_sl_part_count(nnz) + 1) * sizeof(KzSoftminPart));
+    if (rc == KZ_OK) rc = slot.alloc(ctx, (size_t)(n_iter + 1) * 8);
+    if (rc == KZ_OK) rc = stop.alloc(ctx, 16);
+    if (rc != KZ_OK) return rc;
+    if (nnz > 0)
+        rc = kz_sl_transpose(ctx, d_dist, d_ind, n_q, 0, n_index, colptr.get(), col_row.get(), col_val.get(), d_indptr, nnz);
+    else
+        KZ_HIP(hipMemsetAsync(colptr.get(), 0, (size_t)(n_index + 1) * 8, ctx->stream));
+    if (rc != KZ_OK) return rc;
+    KZ_HIP(hipMemsetAsync(slot.get(), 0, (size_t)(n_iter + 1) * 8, ctx->stream));
+    KZ_HIP(hipMemsetAsync(stop.get(), 0, 16, ctx->stream));
+    const double shift = eps * log((double)n_q / (double)n_index);
+    double* g_buf[2] = {g2.get(), g2.get() + n_index};
+    for (int it = 1; it <= n_iter; ++it) {
+        double* g_new = g_buf[it & 1];
+        kz_sl_cols_launch<int, false>(ctx, colptr.get(), col_row.get(), col_val.get(), n_index, nnz, eps, it == 1 ? nullptr : d_f, 0, shift, part.get(),
+                                      g_new, stop.get(), it);
+        if (it >= 2) {
+            hipLaunchKernelGGL(kz_sl_change_kernel, dim3(kz_sl_blocks(n_index)), dim3(256), 0, ctx->stream, (const double*)g_new,
+                               (const double*)g_buf[(it - 1) & 1], n_index, slot.get(), (const int*)stop.get(), it);
+            if (with_tol) hipLaunchKernelGGL(kz_sl_decide_kernel, dim3(1), dim3(1), 0, ctx->stream, (const unsigned long long*)slot.get(), tol, stop.get(), it);
+        }
+        kz_sl_cols_launch<int64_t, true>(ctx, d_indptr, d_ind, d_dist, n_q, nnz, eps, g_new, n_index, 0.0, part.get(), d_f, stop.get(), it);
+    }
+    KZ_HIP(hipGetLastError());
+    // the one read behind the loop: where it stopped and every iteration's change; then g of that iteration
     int h_stop[4] = {0, 0, 0, 0};
     std::unique_ptr<unsigned long long[]> h_slot(new unsigned long long[n_iter + 1]);
     KZ_HIP(hipMemcpyAsync(h_stop, stop.get(), 16, hipMemcpyDeviceToHost, ctx->stream));

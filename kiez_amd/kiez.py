@@ -201,6 +201,43 @@ class Kiez:
         match_dist, match_ind = self.assign_device(k, whole_index, unmatched_cost, eps)
         return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
 
+    # ---- threshold, then one-to-one: the same two steps on the pairs within a radius (a CSR, rows of any length) ----------------
+    def _pairs_within_radius(self, radius, reduced):
+        """The device CSR of `radius_neighbors(radius, reduced=reduced)`, rows by (value, target row) -> (indptr, ind, dist, n_target)."""
+        algo = self.hubness if reduced else self.algorithm
+        indptr, ind, dist = algo.radius_neighbors_device(radius, sort_results=True)
+        return indptr, ind, dist, self.algorithm.target_.shape[0]
+
+    def match_radius_device(self, radius, reduced: bool = False):
+        """Like `match_radius` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+        indptr, ind, dist, n_target = self._pairs_within_radius(radius, reduced)
+        match, col, _ = N.match_csr(dist.ctx, indptr, ind, dist, n_target)
+        return N.match_values_csr(dist.ctx, indptr, dist, col), match
+
+    def match_radius(self, radius, reduced: bool = False, return_distance: bool = True):
+        """Threshold, then one-to-one: `match` over the pairs of `radius_neighbors(radius, reduced=reduced)` instead of neighbour lists
+        -- every check and error of that call applies, `reduced` has its meaning there.  Each row lists its targets by (value, target
+        row), so a pair above the threshold takes NO PART in the matching: the dangling-aware pipeline, which filtering the result
+        of `match(k)` is not.  The CSR never leaves HBM and its rows have no length limit -- a hub row of more than 4 096 targets
+        is fine (kz_match_csr).  Returns what `match` returns."""
+        match_dist, match_ind = self.match_radius_device(radius, reduced)
+        return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
+
+    def assign_radius_device(self, radius, reduced: bool = False, unmatched_cost: Optional[float] = None, eps: Optional[float] = None):
+        """Like `assign_radius` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+        from . import matching
+        unmatched_cost, eps, _ = matching._assignment_options(unmatched_cost, eps, 1)
+        indptr, ind, dist, n_target = self._pairs_within_radius(radius, reduced)
+        return matching.assignment_csr(indptr, ind, dist, n_target, unmatched_cost=unmatched_cost, eps=eps)
+
+    def assign_radius(self, radius, reduced: bool = False, return_distance: bool = True, unmatched_cost: Optional[float] = None,
+                      eps: Optional[float] = None):
+        """`assign` over the pairs of `radius_neighbors(radius, reduced=reduced)`, as `match_radius` takes them: the minimum-cost
+        one-to-one matching among the pairs within the threshold (kz_assign_csr); `unmatched_cost` and `eps` as in `assign`.
+        Returns what `match` returns."""
+        match_dist, match_ind = self.assign_radius_device(radius, reduced, unmatched_cost, eps)
+        return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
+
     def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
         """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
         ranks into hits@k, mean rank and mean reciprocal rank).

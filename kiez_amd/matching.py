@@ -25,6 +25,11 @@ def _checked_lists(dist, ind, n_target):
         ind = np.asarray(ind)
     if len(dist.shape) != 2 or len(ind.shape) != 2 or tuple(dist.shape) != tuple(ind.shape):
         raise ValueError(f"dist and ind must be 2-D neighbour lists of one shape, got {tuple(dist.shape)} and {tuple(ind.shape)}")
+    return _checked_dtypes(dist, ind)
+
+
+def _checked_dtypes(dist, ind):
+    """The dtype half of `_checked_lists`, shared with the CSR form."""
     if not np.issubdtype(ind.dtype, np.integer):
         raise ValueError(f"ind must hold integer row ids, got {ind.dtype}")
     if not np.issubdtype(dist.dtype, np.floating):
@@ -44,6 +49,64 @@ def _checked_lists(dist, ind, n_target):
     return dist, ind
 
 
+def _checked_csr(dist, ind, indptr, n_target):
+    """The argument checks of the CSR functions, all before the device is touched -> (dist, ind, indptr) as the native
+    calls take them.  A host `indptr` is checked in full here; one on the device is checked there, by the native call."""
+    if isinstance(n_target, (bool, np.bool_)) or not isinstance(n_target, (int, np.integer)) or n_target < 1:
+        raise ValueError(f"n_target must be a positive integer, got {n_target!r}")
+    if not isinstance(dist, N.DeviceArray):
+        dist = np.asarray(dist)
+    if not isinstance(ind, N.DeviceArray):
+        ind = np.asarray(ind)
+    if not isinstance(indptr, N.DeviceArray):
+        indptr = np.asarray(indptr)
+    if len(dist.shape) != 1 or len(ind.shape) != 1 or tuple(dist.shape) != tuple(ind.shape):
+        raise ValueError(f"dist and ind must be 1-D arrays of one length (the entries of a CSR), got {tuple(dist.shape)} "
+                         f"and {tuple(ind.shape)}")
+    if len(indptr.shape) != 1 or indptr.shape[0] < 1:
+        raise ValueError(f"indptr must be a 1-D array of n_source + 1 row starts, got shape {tuple(indptr.shape)}")
+    if not np.issubdtype(indptr.dtype, np.integer) or indptr.dtype == np.bool_:
+        raise ValueError(f"indptr must hold integer row starts, got {indptr.dtype}")
+    dist, ind = _checked_dtypes(dist, ind)
+    if isinstance(indptr, N.DeviceArray):
+        if indptr.dtype != np.int64:
+            raise ValueError(f"a device indptr must be int64, got {indptr.dtype}")
+    else:
+        nnz = dist.shape[0]
+        if indptr[0] != 0 or indptr[-1] != nnz or (indptr.shape[0] > 1 and bool((indptr[1:] < indptr[:-1]).any())):
+            raise ValueError(f"indptr must start at 0, never decrease and end at the number of entries {nnz}, got {indptr[0]} .. {indptr[-1]}")
+        indptr = indptr.astype(np.int64, copy=False)
+    return dist, ind, indptr
+
+
+def _csr_context(ctx, dist, ind, indptr):
+    if ctx is not None:
+        return ctx
+    for a in (dist, ind, indptr):
+        if isinstance(a, N.DeviceArray):
+            return a.ctx
+    return N.Context.get()
+
+
+def from_sparse(S):
+    """A scipy sparse matrix [n_source, n_target] whose STORED entries are the pairs (an explicit zero is a pair of value 0) ->
+    `(indptr, ind, dist)`, the CSR `one_to_one_csr`, `assignment_csr` and `sinkhorn_csr` take: every row sorted by
+    (value, target row), the order every list of this library has.  scipy orders a row by column id, and `one_to_one` reads a row's
+    order as the source's preference.  Host-side: one lexsort over the entries.  Duplicate entries are summed first, as scipy does."""
+    if not hasattr(S, "tocsr"):
+        raise ValueError(f"from_sparse takes a scipy sparse matrix, got {type(S).__name__}")
+    S = S.tocsr(copy=True)
+    S.sum_duplicates()
+    indptr = np.asarray(S.indptr, dtype=np.int64)
+    ind = np.asarray(S.indices, dtype=np.int64)
+    dist = np.asarray(S.data)
+    if not np.issubdtype(dist.dtype, np.floating) or dist.dtype not in (np.float32, np.float64):
+        dist = dist.astype(np.float64)
+    rows = np.repeat(np.arange(indptr.shape[0] - 1, dtype=np.int64), np.diff(indptr))
+    order = np.lexsort((ind, dist, rows))   # (row, then value, then target row; NaN values sort last in their row)
+    return indptr, ind[order], dist[order]
+
+
 def one_to_one(dist, ind, n_target: int, *, return_distance: bool = True, ctx: Optional[N.Context] = None):
     """The one-to-one assignment of source rows to target rows from neighbour lists: the source-proposing stable matching.
 
@@ -56,7 +119,8 @@ def one_to_one(dist, ind, n_target: int, *, return_distance: bool = True, ctx: O
 
     Returns `(match_dist, match_ind)`, each [n_q], or `match_ind` alone with `return_distance=False`: `match_ind[i]` is the target
     row of source row i or -1, `match_dist[i]` the value of that pair in `dist`'s dtype or NaN.  numpy lists give numpy arrays; if
-    `dist` is a `DeviceArray`, so are the results.  `evaluate.hits(match_ind[:, None], gold, k=[1])` is the matching's precision."""
+    `dist` is a `DeviceArray`, so are the results.  `evaluate.hits(match_ind[:, None], gold, k=[1])` is the matching's precision.
+    Ragged lists (a CSR): `one_to_one_csr`."""
     dist, ind = _checked_lists(dist, ind, n_target)
     on_device = isinstance(dist, N.DeviceArray)
     if ctx is None:
@@ -132,7 +196,8 @@ def assignment(dist, ind, n_target: int, *, unmatched_cost: Optional[float] = No
     The solver is a forward auction with synchronous rounds: every run returns the same arrays.
 
     Returns `(match_dist, match_ind)`, or `match_ind` alone with `return_distance=False`, as `one_to_one` does, with the float64
-    target prices [n_target] appended when `return_prices=True`.  More than `max_rounds` rounds raise RuntimeError."""
+    target prices [n_target] appended when `return_prices=True`.  More than `max_rounds` rounds raise RuntimeError.
+    Ragged lists (a CSR): `assignment_csr`."""
     dist, ind = _checked_lists(dist, ind, n_target)
     unmatched_cost, eps, max_rounds = _assignment_options(unmatched_cost, eps, max_rounds)
     on_device = isinstance(dist, N.DeviceArray)
@@ -152,6 +217,17 @@ def assignment(dist, ind, n_target: int, *, unmatched_cost: Optional[float] = No
     return out if len(out) > 1 else out[0]
 
 
+def _sinkhorn_options(temperature, n_iter, tol):
+    """The checks of the Sinkhorn options that need no data."""
+    if (isinstance(temperature, (bool, np.bool_)) or not isinstance(temperature, (int, float, np.integer, np.floating))
+            or not np.isfinite(temperature) or temperature <= 0):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    if isinstance(n_iter, (bool, np.bool_)) or not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
+    if tol is not None and (isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0):
+        raise ValueError(f"tol must be None or a number >= 0, got {tol!r}")
+
+
 def sinkhorn_lists(dist, ind, n_target: int, *, temperature: float = 0.05, n_iter: int = 10, tol: Optional[float] = None,
                    ctx: Optional[N.Context] = None, return_info: bool = False):
     """The Sinkhorn potentials of neighbour lists, on the device (`kz_sinkhorn_lists`): entropic optimal transport between the source
@@ -168,15 +244,10 @@ def sinkhorn_lists(dist, ind, n_target: int, *, temperature: float = 0.05, n_ite
 
     Returns `(f, g)`, float64 [n_q] and [n_target] -- numpy arrays for numpy lists, `DeviceArray`s if `dist` is one -- and with
     `return_info=True` a third item, the dict {"n_iter": iterations done, "potential_change": the last measured change of g or None}.
-    `(dist - f[:, None]) - g[ind]` is the reduced distance of the listed pairs (`Sinkhorn.transform`)."""
+    `(dist - f[:, None]) - g[ind]` is the reduced distance of the listed pairs (`Sinkhorn.transform`).  Ragged lists (a CSR):
+    `sinkhorn_csr`."""
     dist, ind = _checked_lists(dist, ind, n_target)
-    if (isinstance(temperature, (bool, np.bool_)) or not isinstance(temperature, (int, float, np.integer, np.floating))
-            or not np.isfinite(temperature) or temperature <= 0):
-        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
-    if isinstance(n_iter, (bool, np.bool_)) or not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
-        raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
-    if tol is not None and (isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0):
-        raise ValueError(f"tol must be None or a number >= 0, got {tol!r}")
+    _sinkhorn_options(temperature, n_iter, tol)
     on_device = isinstance(dist, N.DeviceArray)
     if on_device and dist.dtype != np.float64:
         raise ValueError(f"a device dist must be float64 here, got {dist.dtype}")
@@ -185,5 +256,72 @@ def sinkhorn_lists(dist, ind, n_target: int, *, temperature: float = 0.05, n_ite
     if ctx is None:
         ctx = dist.ctx if on_device else ind.ctx if isinstance(ind, N.DeviceArray) else N.Context.get()
     f, g, done, change = N.sinkhorn_lists(ctx, ctx.as_device(dist), ctx.as_device(ind), int(n_target), float(temperature), int(n_iter), tol)
+    out = (f, g) if on_device else (f.numpy(), g.numpy())
+    return out + ({"n_iter": done, "potential_change": change},) if return_info else out
+
+
+# ---- the same three steps on RAGGED lists: a CSR (indptr, ind, dist) as `radius_neighbors` or `from_sparse` return it ----------------
+def one_to_one_csr(indptr, ind, dist, n_target: int, *, return_distance: bool = True, ctx: Optional[N.Context] = None):
+    """`one_to_one` over ragged lists (kz_match_csr).  `indptr` [n_q + 1], `ind` and `dist` 1-D arrays of one length: row i lists the
+    targets `ind[indptr[i]:indptr[i + 1]]` with the values `dist[...]`, in its order of preference (`radius_neighbors` and
+    `from_sparse` order a row by (value, target row)).  Rows may be empty and have NO length limit (`one_to_one` stops at 4 096
+    columns); an entry with `ind` outside [0, n_target) is no pair, a target may repeat inside a row.  numpy arrays or `DeviceArray`s,
+    with `one_to_one`'s rule for where the result lives.  An `indptr` that does not start at 0, decreases or does not end at the
+    number of entries raises ValueError -- a host one before the device is touched, a device one on the device before anything
+    reads through it.  Returns what `one_to_one` returns."""
+    dist, ind, indptr = _checked_csr(dist, ind, indptr, n_target)
+    on_device = isinstance(dist, N.DeviceArray)
+    ctx = _csr_context(ctx, dist, ind, indptr)
+    dist_dev, ind_dev, ptr_dev = ctx.as_device(dist), ctx.as_device(ind), ctx.as_device(indptr)
+    match, col, _ = N.match_csr(ctx, ptr_dev, ind_dev, dist_dev, int(n_target))
+    if not return_distance:
+        return match if on_device else match.numpy()
+    match_dist = N.match_values_csr(ctx, ptr_dev, dist_dev, col)
+    return (match_dist, match) if on_device else (match_dist.numpy(), match.numpy())
+
+
+def assignment_csr(indptr, ind, dist, n_target: int, *, unmatched_cost: Optional[float] = None, eps: Optional[float] = None,
+                   max_rounds: int = 1_000_000, return_distance: bool = True, return_prices: bool = False,
+                   ctx: Optional[N.Context] = None):
+    """`assignment` over ragged lists (kz_assign_csr): the CSR as `one_to_one_csr` takes it, every option, default (from the range
+    of the listed values), error and result as `assignment`."""
+    dist, ind, indptr = _checked_csr(dist, ind, indptr, n_target)
+    unmatched_cost, eps, max_rounds = _assignment_options(unmatched_cost, eps, max_rounds)
+    on_device = isinstance(dist, N.DeviceArray)
+    n_q = indptr.shape[0] - 1
+    host = not on_device and not isinstance(ind, N.DeviceArray)
+    if host:   # (the eps check comes before the device is touched)
+        unmatched_cost, eps = _assignment_defaults(_host_value_range(dist, ind, n_target), n_q, unmatched_cost, eps)
+    ctx = _csr_context(ctx, dist, ind, indptr)
+    dist_dev, ind_dev, ptr_dev = ctx.as_device(dist), ctx.as_device(ind), ctx.as_device(indptr)
+    if not host:
+        unmatched_cost, eps = _assignment_defaults(N.assign_range_csr(ctx, ptr_dev, ind_dev, dist_dev, int(n_target)), n_q, unmatched_cost, eps)
+    match, col, prices, rounds, converged = N.assign_csr(ctx, ptr_dev, ind_dev, dist_dev, int(n_target), unmatched_cost, eps, max_rounds,
+                                                         want_prices=return_prices)
+    if not converged:
+        raise RuntimeError(f"assignment: rows are still free after {rounds} rounds (max_rounds) with eps = {eps!r} and "
+                           f"unmatched_cost = {unmatched_cost!r}; a larger eps or a smaller unmatched_cost shortens the run")
+    out = (N.match_values_csr(ctx, ptr_dev, dist_dev, col), match) if return_distance else (match,)
+    if return_prices:
+        out = out + (prices,)
+    if not on_device:
+        out = tuple(x.numpy() for x in out)
+    return out if len(out) > 1 else out[0]
+
+
+def sinkhorn_csr(indptr, ind, dist, n_target: int, *, temperature: float = 0.05, n_iter: int = 10, tol: Optional[float] = None,
+                 ctx: Optional[N.Context] = None, return_info: bool = False):
+    """`sinkhorn_lists` over ragged lists (kz_sinkhorn_csr): the CSR as `one_to_one_csr` takes it (values taken as float64), every
+    option and result as `sinkhorn_lists`; f has one entry per row of `indptr`."""
+    dist, ind, indptr = _checked_csr(dist, ind, indptr, n_target)
+    _sinkhorn_options(temperature, n_iter, tol)
+    on_device = isinstance(dist, N.DeviceArray)
+    if on_device and dist.dtype != np.float64:
+        raise ValueError(f"a device dist must be float64 here, got {dist.dtype}")
+    if not on_device:
+        dist = dist.astype(np.float64, copy=False)
+    ctx = _csr_context(ctx, dist, ind, indptr)
+    f, g, done, change = N.sinkhorn_csr(ctx, ctx.as_device(indptr), ctx.as_device(ind), ctx.as_device(dist), int(n_target), float(temperature),
+                                        int(n_iter), tol)
     out = (f, g) if on_device else (f.numpy(), g.numpy())
     return out + ({"n_iter": done, "potential_change": change},) if return_info else out
