@@ -1,8 +1,10 @@
 """Every pair within a threshold over the whole index on the device (kz_radius_neighbors, kz_radius_neighbors_reduced and the
 methods above them up to Kiez.radius_neighbors): with lists over the whole index the result is the threshold of the row `transform`
-/ `kneighbors` writes, bit for bit, for every kind and every branch of the distance conversion; the count, scan and fill passes
-around the chunk length and both parities of a value row's start; rows beyond any LDS sort; NaN states; the capacity contract and
-the two-call allocation policy; batches and row ranges; what the calls refuse; the facade.  `pytest -m gpu`."""
+/ `kneighbors` writes, bit for bit, for every kind and four branches of the distance conversion (euclidean float32 / float64,
+cosine, minkowski float32); the count, scan and fill passes around the chunk length and both parities of a value row's start; rows
+of 9001 entries, beyond the LDS sort; NaN states; the capacity contract and the two-call allocation policy; batches and row ranges;
+what the calls refuse; the facade.  The sort's size branches and key regimes, the scan beyond 256 chunks and the other conversions
+and element types: tests/test_gpu_radius_sort.py.  `pytest -m gpu`."""
 import subprocess
 import sys
 from pathlib import Path

@@ -1,6 +1,7 @@
 """The numpy restatement of the radius calls (tests/radius_restate.py) against scikit-learn's
-NearestNeighbors(algorithm="brute").radius_neighbors(sort_results=True), and the argument errors the new methods raise on the host
-before any device call.  No GPU."""
+NearestNeighbors(algorithm="brute").radius_neighbors(sort_results=True), the argument errors the new methods raise on the host
+before any device call, and the restated sort key and planted matrices of tests/test_gpu_radius_sort.py: row lengths, radix pass
+sets, finite and non-negative entries.  No GPU."""
 import numpy as np
 import pytest
 from scipy.spatial.distance import cdist
@@ -90,3 +91,96 @@ def test_radius_is_checked_on_the_host():
     for call in (kz.hubness.radius_neighbors, kz.hubness.radius_neighbors_device, kz.hubness.radius_counts):
         with pytest.raises(ValueError, match="s_to_t=True"):
             call(0.5, s_to_t=False)
+
+
+# ---- the helpers and the planted inputs of tests/test_gpu_radius_sort.py ----
+
+def test_order_key_orders_like_the_doubles():
+    """kz_knnr_key restated: keys ascend exactly as np.sort orders the values (NaN last, beside +inf), -0.0 and +0.0 share a key,
+    NaN shares +inf's."""
+    tiny = np.float64(5e-324)
+    v = np.array([np.inf, np.nan, -np.inf, 0.0, -0.0, tiny, -tiny, 2.5e-310, -2.5e-310, 1.0, -1.0, 1e300, -1e300, 0.625, -3.0,
+                  np.nextafter(1.0, 2.0), np.nextafter(-1.0, -2.0), 2.2250738585072014e-308])
+    key = RA.order_key(v)
+    assert key.dtype == np.uint64 and key.shape == v.shape
+    by_key = v[np.argsort(key, kind="stable")]                 # (NaN stands behind +inf in v: they share a key and go by place)
+    np.testing.assert_array_equal(by_key, np.sort(v))          # (array_equal: NaN == NaN in place, -0.0 == +0.0)
+    finite = v[~np.isnan(v)]
+    fk = RA.order_key(finite)
+    assert ((fk[:, None] < fk[None, :]) == (finite[:, None] < finite[None, :])).all()
+    assert ((fk[:, None] == fk[None, :]) == (finite[:, None] == finite[None, :])).all()
+    assert RA.order_key([np.nan])[0] == RA.order_key([np.inf])[0] == 0xFFF0000000000000
+    assert RA.order_key([-0.0])[0] == RA.order_key([0.0])[0] == 0x8000000000000000
+    assert RA.order_key([-np.inf])[0] == 0x000FFFFFFFFFFFFF and RA.order_key([1.0])[0] == 0xBFF0000000000000
+
+
+def test_byte_values_and_radix_passes():
+    rng = np.random.default_rng(0)
+    assert RA.radix_passes([0.625] * 50) == [] and RA.radix_passes([-0.0, 0.0]) == []
+    assert RA.radix_passes([1.0, -1.0]) == list(range(0, 64, 8))
+    for shifts in RA.BYTE_REGIMES:
+        v = RA.byte_values(rng, 9000, shifts)
+        assert v.dtype == np.float64 and np.isfinite(v).all() and (v >= 0).all() and not np.signbit(v).any()
+        assert RA.radix_passes(v) == list(shifts)
+        for s in shifts:                                    # every digit value of the byte occurs
+            assert len(np.unique((RA.order_key(v) >> np.uint64(s)) & np.uint64(0xFF))) == (0x40 if s == 56 else 256)
+
+
+@pytest.mark.parametrize("regime", RA.REGIMES, ids=RA.regime_id)
+def test_planted_matrix_has_the_lengths_and_the_passes_of_its_regime(regime):
+    assert sorted(RA.LENGTHS)[0] == 0 and max(RA.LENGTHS) == RA.PLANT_N_INDEX and len(RA.LENGTHS) == 24
+    for edge in (2, 256, 512, 1024, 2048, 4096):             # both sides of every size the sort branches at
+        assert {edge - 1, edge, edge + 1} <= set(RA.LENGTHS) | {1, 3}
+    assert {n % 256 for n in RA.LENGTHS if n > RA.SORT_LDS} >= {0, 1, 255}          # the radix path's last tile
+    for dtype in (np.float64, np.float32):
+        D, radius = RA.planted(regime, dtype)
+        assert D.dtype == dtype and D.shape == (24, 9000) and np.isfinite(D).all() and (D >= 0).all()
+        np.testing.assert_array_equal((D <= radius).sum(axis=1), RA.LENGTHS)
+        assert (D[D > radius] >= 1e30).all() and radius <= 2.0
+        indptr, ind, val = RA.csr(D, radius)
+        np.testing.assert_array_equal(np.diff(indptr), RA.LENGTHS)
+        assert (np.diff(RA.csr(D.T, radius)[0]) <= 24).all()
+    D, radius = RA.planted(regime)
+    for n, row in zip(RA.LENGTHS, D):
+        if n > RA.SORT_LDS:
+            passes = RA.radix_passes(row[row <= radius])
+            if n == 9000 or regime != "distinct":
+                assert passes == RA.REGIME_PASSES[regime], (n, passes)
+            else:                                               # (a shorter row need not reach below 2^-15, the top byte's edge)
+                assert passes[:7] == RA.REGIME_PASSES[regime], (n, passes)
+    assert len(RA.REGIME_PASSES["distinct"]) % 2 == 1           # an odd number of passes: the copy back
+    if regime == "grid8":
+        zeros = D[D == 0.0]
+        assert np.signbit(zeros).any() and not np.signbit(zeros).all()
+        assert len(np.unique(D[D <= radius])) == 9 and radius == 1.0
+    if regime == "distinct":
+        assert len(np.unique(D[D <= radius])) == sum(RA.LENGTHS)
+
+
+def test_signed_case_is_exact_and_has_the_row_lengths_of_both_sort_paths():
+    D, q_a, t_a, w = RA.signed_case()
+    assert np.isfinite(D).all() and (D >= 0).all() and D.shape == (6, 9000)
+    # exact: every term is a multiple of 1 / 128 below 2^4, so the differences round nowhere and any order gives the same bits
+    ok = np.isfinite(w)
+    assert (w[ok] * 128 == np.round(w[ok] * 128)).all() and np.abs(w[ok]).max() < 16
+    assert np.isnan(w[:, list(RA.SIGNED_NAN)]).all() and np.isnan(w).sum() == 6 * 3
+    assert (w[:, list(RA.SIGNED_TO_MINUS_INF)] == -np.inf).all() and (w[:, list(RA.SIGNED_TO_PLUS_INF)] == np.inf).all()
+    assert (w[ok] == 0).any() and (w[ok] < 0).any() and (w[ok] > 0).any()
+    bounds = {np.inf: (8997, 8997), 0.0: (RA.SORT_LDS + 1, 9000), -3.0: (1025, 2048), -4.5: (65, 512), -np.inf: (2, 2)}
+    for radius in RA.SIGNED_RADII:
+        counts = np.diff(RA.csr(w, radius)[0])
+        print("radius", radius, "rows of", counts.min(), "to", counts.max())
+        lo, hi = bounds[radius]
+        assert lo <= counts.min() and counts.max() <= hi
+    assert RA.radix_passes(w[0][w[0] <= np.inf]) == list(range(0, 64, 8))       # -inf .. +inf: all eight passes
+
+
+def test_carry_case():
+    D, radius = RA.carry_case()
+    assert D.dtype == np.float32 and D.shape == (2, 256 * 8192 + 1) and np.isfinite(D).all() and (D >= 0).all()
+    indptr, ind, val = RA.csr(D, radius, sort_results=False)
+    np.testing.assert_array_equal(indptr, [0, 8, 8 + 5001])
+    np.testing.assert_array_equal(ind[:8], RA.CARRY_ROW0)
+    assert ind[-1] == 256 * 8192 and val[-1] == 0.0 and ind[7] // 8192 == 256 and ind[5] // 8192 == ind[6] // 8192 == 255
+    assert RA.csr(D, radius)[1][8] == 256 * 8192                # sorted: the entry of the last chunk comes first in row 1
+    np.testing.assert_array_equal(RA.csr(D, radius)[1][:8], RA.CARRY_ROW0[::-1])
