@@ -579,6 +579,57 @@ int kz_sinkhorn_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, 
                     int64_t n_index, double eps, int n_iter, double tol, double* d_f, double* d_g, int* h_n_iter, double* h_change,
                     int* h_measured);
 
+/* ---- NEIGHBOUR PAIRS OF BOTH DIRECTIONS AS A CSR (kz_pairs.hip, kz_pairs.h) -- additive, ABI v7 -------------------------------- */
+/* The producer in front of the three CSR calls above.  F = the pairs (i, j) with target row j in the forward list of source row i,
+ * R = the pairs (i, j) with source row i in the reverse list of target row j.  MEMBERSHIP IS BY THE LISTS the caller brings (the raw
+ * lists of two kz_knn searches: ties are the search's business), never by a value.
+ *
+ * kz_lists_combine: the set step.  d_fwd_ind [n_q, k_f]: target ids per source row; d_rev_ind [n_index, k_r]: source ids per target
+ * row (int64, on the device; k_f != k_r is fine).  An entry whose id is outside its range -- a target id outside [0, n_index) in a
+ * forward list, a source id outside [0, n_q) in a reverse list: kz_match_lists' rule, so -1, kz_knn_reduced's INT_MAX padding and an
+ * id >= n -- is no pair; an id repeated inside a row counts once.  mode: KZ_PAIRS_FORWARD = F, KZ_PAIRS_REVERSE = R grouped by source
+ * row (the transposed reverse lists), KZ_PAIRS_UNION = F u R, KZ_PAIRS_MUTUAL = F n R; every pair once.  FORWARD does not read
+ * d_rev_ind and REVERSE does not read d_fwd_ind (they may be NULL).
+ * Output and CAPACITY CONTRACT: kz_radius_neighbors'.  d_indptr [n_q + 1] (int64, device) and *h_total (host) = the number of pairs
+ * are ALWAYS complete and exact; capacity = 0 is the count-only call (d_ind may be NULL); d_ind [capacity] (int64, device) receives
+ * the target ids of every row whose end offset d_indptr[i + 1] is <= capacity, at d_indptr[i] .., ascending by target id; for any
+ * other row NOTHING is written, and the call returns KZ_OK all the same.
+ * How: the entries the mode reads are ordered by (source row, target row) with two passes of the stable radix sort (kz_sort.hip); the
+ * first entry of every run of equal pairs decides by the sides present in its run; places are an integer prefix sum of those flags.
+ * Integer keys, counts and scans; no atomics on the output; nothing depends on the order anything runs in: two calls give identical
+ * bytes.  One thread per ENTRY: a row of any length (a hub source can be listed by every target) costs what its entries cost.
+ * 1 <= k_f, k_r <= KZ_MAX_CANDIDATES, 0 <= n_q <= 2^31 - 2, 1 <= n_index <= 2^31 - 2, capacity >= 0, a known mode: KZ_ERR_INVALID
+ * otherwise; more than 2^31 - 2 list entries read (n_q k_f + n_index k_r for UNION / MUTUAL; the total is at most that):
+ * KZ_ERR_UNSUPPORTED; n_q == 0: KZ_OK with d_indptr[0] = 0.  Transient device memory: about 32 bytes per list entry read (the sort's included).  Synchronises the
+ * context's stream. */
+#define KZ_PAIRS_FORWARD 0
+#define KZ_PAIRS_REVERSE 1
+#define KZ_PAIRS_UNION 2
+#define KZ_PAIRS_MUTUAL 3
+int kz_lists_combine(kz_ctx* ctx, const int64_t* d_fwd_ind, int64_t n_q, int k_f, const int64_t* d_rev_ind, int64_t n_index, int k_r,
+                     int mode, int64_t capacity, int64_t* d_indptr, int64_t* d_ind, int64_t* h_total);
+/* kz_pairs_values: d_out[p] (float64 [nnz], device) = the value of entry p of the CSR (d_indptr [n_q + 1], d_ind [nnz]) between the
+ * query row i that holds p (rows 0 .. n_q - 1 of `query`, n_q <= query.n) and index row d_ind[p]:
+ *   kind 0               the distance kz_knn returns for query row i and index row d_ind[p] -- kz_output_distance of the exact ranking
+ *                        value, kz_pair_values' canonical dot product; ALWAYS this direction's value, whichever list named the pair;
+ *   a KZ_RANK_* kind     w of kz_gold_ranks_reduced / kz_knn_reduced (kind, the four state vectors and their validation as there;
+ *                        kind 0: all four NULL), d_q_a / d_q_b indexed by i, d_t_a / d_t_b by d_ind[p].
+ * The same expressions as kz_radius_neighbors[_reduced], so a pair has the bits that call returns for it with radius = +inf -- and,
+ * for a pair of a forward list, the bits of kz_knn's distance (kind 0) or of kz_csls / kz_local_scaling / kz_mp_normal / kz_dual_shift.
+ * Every metric and row dtype kz_pair_values serves (float16 / bfloat16 rows included), and a precomputed pair of views: the matrix
+ * entry, widened.  A NaN value is written as it is (the caller decides what it means); an entry whose id is outside [0, index.n):
+ * NaN.  The indptr validation of the CSR calls runs first; limits as there (kz_csr_require); matrices that disagree: KZ_ERR_INVALID.
+ * One wave per entry (one lane for the Minkowski family, the boolean metrics and precomputed values), the row of an entry by binary
+ * search in d_indptr; then one pointwise kernel in place.  Synchronises the context's stream. */
+int kz_pairs_values(kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index, const int64_t* d_indptr, const int64_t* d_ind,
+                    int64_t n_q, int64_t nnz, int kind, const double* d_q_a, const double* d_q_b, const double* d_t_a,
+                    const double* d_t_b, double* d_out);
+/* kz_csr_sort_rows: every row of a float64 CSR (d_ind / d_dist [nnz], permuted together, in place) ascending by (value, index row) in
+ * the order of kz_knn_reduced -- kz_radius_neighbors' sort with both of its branches (a row of up to 4096 entries in LDS, a longer
+ * one by a stable radix sort through a transient second copy of the CSR: KZ_ERR_NOMEM when it does not fit).  A NaN value orders as
+ * +inf: last, by index row.  Ids must be below 2^31 - 1.  The indptr validation runs first.  Synchronises the context's stream. */
+int kz_csr_sort_rows(kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz, int64_t n_index, int64_t* d_ind, double* d_dist);
+
 /* float64 -> float32 cast of an [count] array (cosine + float32 inputs keep the reference's output dtype). */
 int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count);
 

@@ -186,6 +186,9 @@ SYMBOLS = [
     ("kz_softmin_csr_rows", C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, C.c_double, _P, C.c_double, _P]),
     ("kz_sinkhorn_csr", C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, C.c_double, C.c_int, C.c_double, _P, _P, C.POINTER(C.c_int),
                                   C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("kz_lists_combine", C.c_int, [_P, _P, _I64, C.c_int, _P, _I64, C.c_int, C.c_int, _I64, _P, _P, C.POINTER(_I64)]),
+    ("kz_pairs_values", C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.c_int, _P, _P, _P, _P, _P]),
+    ("kz_csr_sort_rows", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_comm_destroy", C.c_int, [_P]),
@@ -949,6 +952,116 @@ def sinkhorn_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: Devi
                                    -1.0 if tol is None else float(tol), f.ptr, g.ptr, C.byref(done), C.byref(change), C.byref(measured)),
            "kz_sinkhorn_csr")
     return f, g, int(done.value), float(change.value) if measured.value else None
+
+
+# ---- neighbour pairs of both directions as a CSR (include/kiez_amd.h: KZ_PAIRS_*) ----------------------------------------------
+PAIR_MODES = {"forward": 0, "reverse": 1, "union": 2, "mutual": 3}
+
+
+def pair_mode(mode, what: str = "neighbor_pairs") -> str:
+    """`mode` if it names one of the four set combinations, else ValueError -- on the host, before the device is touched."""
+    if not isinstance(mode, str) or mode not in PAIR_MODES:
+        raise ValueError(f"{what}: mode must be one of {tuple(PAIR_MODES)}, got {mode!r}")
+    return mode
+
+
+def _list_ids(what: str, ind: DeviceArray):
+    if not isinstance(ind, DeviceArray) or len(ind.shape) != 2 or ind.dtype != np.int64:
+        raise ValueError(f"{what} must be a 2-D int64 DeviceArray of ids, got "
+                         f"{getattr(ind, 'dtype', type(ind).__name__)} {getattr(ind, 'shape', '')}")
+    return ind.shape
+
+
+def _combine_call(ctx: Context, fwd_ind, rev_ind, n_q: int, k_f: int, n_index: int, k_r: int, mode: int, capacity: int):
+    """One kz_lists_combine call -> (indptr [n_q + 1], ind [capacity], total)."""
+    indptr = ctx.empty((n_q + 1,), np.int64)
+    ind = ctx.empty((capacity,), np.int64)
+    total = _I64(0)
+    _check(ctx.lib.kz_lists_combine(ctx.handle, fwd_ind.ptr if fwd_ind is not None else None, n_q, k_f,
+                                    rev_ind.ptr if rev_ind is not None else None, n_index, k_r, mode, capacity, indptr.ptr, ind.ptr,
+                                    C.byref(total)), "kz_lists_combine")
+    return indptr, ind, int(total.value)
+
+
+def lists_combine(ctx: Context, fwd_ind: Optional[DeviceArray], rev_ind: Optional[DeviceArray], mode: str, n_q: Optional[int] = None,
+                  n_index: Optional[int] = None, capacity: Optional[int] = None) -> Tuple[DeviceArray, DeviceArray, int]:
+    """kz_lists_combine -> (indptr int64 [n_q + 1], ind int64, total): the pairs (source row, target row) of the forward lists
+    `fwd_ind` [n_q, k_f] (target ids per source row), of the reverse lists `rev_ind` [n_index, k_r] (source ids per target row:
+    "reverse", grouped by source row), of their union or of their intersection ("mutual"), every pair once, as a CSR over the source
+    rows on the device, a row ascending by target id.  An id outside its range (-1, INT_MAX padding, >= n) is no pair; a repeated id
+    counts once.  "forward" takes no `rev_ind` and "reverse" no `fwd_ind` (None); `n_q` / `n_index` default to the row count of the
+    array that has them as rows.
+
+    `capacity` None: the allocation policy -- ONE call with room for the obvious upper bound (the entries of the lists the mode reads;
+    "mutual": of the smaller one), so that a second call is never needed -- unless that bound does not fit a quarter of what the
+    device has free: then a count-only call and a second one with room for exactly the total, refused with MemoryError (naming the
+    total) when that does not fit either.  ind comes back with `total` entries.  `capacity` given: that one call as the library
+    makes it (`radius_neighbors`' contract: rows that end beyond the capacity are not written; indptr and total are exact)."""
+    mode_c = PAIR_MODES[pair_mode(mode, "lists_combine")]
+    use_f, use_r = mode != "reverse", mode != "forward"
+    if use_f:
+        shape = _list_ids("fwd_ind", fwd_ind)
+        n_q = shape[0] if n_q is None else n_q
+        if shape[0] != n_q:
+            raise ValueError(f"fwd_ind has {shape[0]} rows, n_source is {n_q}")
+    if use_r:
+        shape = _list_ids("rev_ind", rev_ind)
+        n_index = shape[0] if n_index is None else n_index
+        if shape[0] != n_index:
+            raise ValueError(f"rev_ind has {shape[0]} rows, n_target is {n_index}")
+    if n_q is None or n_index is None:
+        raise ValueError(f"lists_combine(mode={mode!r}): name n_source and n_target, the one list array does not say both")
+    n_q, n_index = int(n_q), int(n_index)
+    k_f = fwd_ind.shape[1] if use_f else 1
+    k_r = rev_ind.shape[1] if use_r else 1
+    args = (fwd_ind if use_f else None, rev_ind if use_r else None, n_q, k_f, n_index, k_r, mode_c)
+    if capacity is not None:
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+            raise ValueError(f"capacity must be a non-negative integer, got {capacity!r}")
+        return _combine_call(ctx, *args, int(capacity))
+    n_f, n_r = (n_q * k_f if use_f else 0), (n_index * k_r if use_r else 0)
+    bound = min(n_f, n_r) if mode == "mutual" else n_f + n_r
+    free, _ = ctx.mem_info()
+    first = bound if 8 * bound <= free // 4 else 0
+    indptr, ind, total = _combine_call(ctx, *args, first)
+    if total > first:
+        del ind
+        free, _ = ctx.mem_info()
+        if 8 * total > free:
+            raise MemoryError(f"lists_combine: total = {total} pairs need {8 * total} bytes of device memory for their ids (and as much "
+                              f"again per value), {free} are free")
+        indptr, ind, total = _combine_call(ctx, *args, total)
+    return indptr, ind.view_rows(0, total), total
+
+
+def pairs_values(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, indptr: DeviceArray, ind: DeviceArray, kind: Optional[int] = None,
+                 q_state=None, t_state=None) -> DeviceArray:
+    """kz_pairs_values -> float64 [nnz] on the device: the value of every entry of the CSR (indptr [n_q + 1], ind [nnz]) between the
+    query row that holds it and index row ind[p] -- the distance `knn` returns for the pair (`kind` None) or, with a `kind` of
+    `gold_ranks_reduced` and its `q_state` / `t_state`, the hubness-reduced distance: the bits `radius_neighbors` returns for the
+    pair, whether or not a neighbour list holds it."""
+    if (not isinstance(indptr, DeviceArray) or len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64
+            or not isinstance(ind, DeviceArray) or len(ind.shape) != 1 or ind.dtype != np.int64):
+        raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries and ind a 1-D int64 DeviceArray")
+    n_q, nnz = indptr.shape[0] - 1, ind.shape[0]
+    if kind is None:
+        if q_state is not None or t_state is not None:
+            raise ValueError("q_state / t_state belong to a reduced call: name its kind")
+        kind_c, state = 0, (None, None, None, None)
+    else:
+        kind_c = int(kind)
+        state = (None, None, None, None) if q_state is None or t_state is None else _reduction_state(q_state, t_state, n_q, index.shape[0])
+    out = ctx.empty((nnz,), np.float64)
+    _check(ctx.lib.kz_pairs_values(ctx.handle, query.handle, index.handle, indptr.ptr, ind.ptr, n_q, nnz, kind_c, *state, out.ptr),
+           "kz_pairs_values")
+    return out
+
+
+def csr_sort_rows(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int):
+    """kz_csr_sort_rows: every row of the float64 CSR ascending by (value, index row) in `knn_reduced`'s order, NaN last -- ind and
+    dist permuted in place (`radius_neighbors`' row sort, a row of any length)."""
+    n_q, nnz = _f64_csr(indptr, ind, dist)
+    _check(ctx.lib.kz_csr_sort_rows(ctx.handle, indptr.ptr, n_q, nnz, int(n_index), ind.ptr, dist.ptr), "kz_csr_sort_rows")
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):

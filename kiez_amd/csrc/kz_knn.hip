@@ -1583,5 +1583,6 @@ extern "C" int kz_knn(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int6
 #include "kz_gold_ranks.h"
 #include "kz_knn_reduced.h"
 #include "kz_radius.h"
+#include "kz_pairs.h"
 #include "kz_softmin.h"
 #include "kz_knn_dual.h"

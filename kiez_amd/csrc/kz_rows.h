@@ -20,6 +20,20 @@ struct KzRowsCsr {
     __device__ __forceinline__ bool is_long(int64_t i) const { return indptr[i + 1] - indptr[i] > (int64_t)KZ_CSR_LONG_ROW; }
 };
 
+// The row of a validated CSR that holds entry p (0 <= p < nnz = indptr[n_q]): the largest i with indptr[i] <= p.  Empty rows hold
+// nothing: the search steps over them.  (kz_pairs.hip, kz_pairs.h: the kernels that take one thread or one wave per ENTRY.)
+__device__ __forceinline__ int64_t kz_csr_row_of(const int64_t* __restrict__ indptr, int64_t n_q, int64_t p) {
+    int64_t lo = 0, hi = n_q;   // (indptr[lo] <= p < indptr[hi])
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (indptr[mid] <= p)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
 // kz_match.hip: the limits every CSR call shares; the check kernel over indptr with its flag read back (synchronises the stream)
 int kz_csr_require(const char* who, kz_ctx* ctx, int64_t n_q, int64_t nnz, int64_t n_index);
 int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz);

@@ -285,6 +285,32 @@ class HubnessReduction(ABC):
         indptr, = self.nn_algo._results_to_host(indptr)
         return indptr[1:] - indptr[:-1]
 
+    # ---- the neighbour pairs of both directions, valued by the reduced distance -------------------------
+    def neighbor_pairs_device(self, k=None, mode="union", sort_results=True, return_distance=True):
+        """`neighbor_pairs` with the CSR left in HBM: (indptr, ind, dist) DeviceArrays, or (indptr, ind)."""
+        nn = self.nn_algo
+        if not self._gpu_nn:
+            N.pair_mode(mode)
+            raise NotImplementedError("neighbor_pairs needs one of the device-native reductions on the MI355X SklearnNN backend")
+        k, mode = nn._pairs_args(k, mode)
+        nn._two_sided_operands("neighbor_pairs")   # (NotFittedError, single-source fit: as gold_ranks)
+        if self._no_rank_reason:
+            raise NotImplementedError(f"{type(self).__name__}: {self._no_rank_reason}")
+        kind, q_state, t_state = self._forward_rank_state()
+        indptr, ind, dist, _ = nn._neighbor_pairs(k, mode, sort_results, return_distance, kind, q_state, t_state)
+        return (indptr, ind, dist) if return_distance else (indptr, ind)
+
+    def neighbor_pairs(self, k=None, mode="union", return_distance=True, sort_results=True):
+        """`SklearnNN.neighbor_pairs` with every pair valued by its HUBNESS-REDUCED distance: the same pairs -- membership is decided
+        by the raw lists of the two searches, also here: the reduction is fitted one way, and with k = `n_candidates` these are
+        exactly the two candidate sets its state is built from -- and w = f(d, a_i, b_j) with the state `fit` / `kneighbors` use, the
+        value `radius_neighbors(inf)` and `kneighbors_whole_index` return for the pair; for a pair of the forward lists that is
+        `transform`'s output.  A pair only the reverse lists hold is valued all the same (CSLS, LocalScaling 'standard' / 'nicdm',
+        MutualProximity 'normal', Sinkhorn / InvertedSoftmax: functions of the pair's distance and one state per side).
+        MutualProximity 'empiric', DisSimLocal and user-written reductions raise NotImplementedError; NoHubnessReduction returns the
+        plain result.  Rows ascend by (w, target row), a NaN w last.  The shared sweep's cached forward lists are left as found."""
+        return self.nn_algo._results_to_host(*self.neighbor_pairs_device(k, mode, sort_results, return_distance))
+
     def _to_host(self, od: N.DeviceArray, oi: N.DeviceArray):
         """A device result as `kneighbors` hands it out: tensors in -> tensors out on the source's device, else numpy."""
         src = self.nn_algo.source_
@@ -359,6 +385,13 @@ class NoHubnessReduction(HubnessReduction):
 
     def radius_counts(self, radius, s_to_t=True):
         return self.nn_algo.radius_counts(radius, s_to_t)
+
+    # (nothing is rescaled: the pairs with the search's own distances)
+    def neighbor_pairs_device(self, k=None, mode="union", sort_results=True, return_distance=True):
+        return self.nn_algo.neighbor_pairs_device(k, mode, sort_results, return_distance)
+
+    def neighbor_pairs(self, k=None, mode="union", return_distance=True, sort_results=True):
+        return self.nn_algo.neighbor_pairs(k, mode, return_distance, sort_results)
 
     def __repr__(self):
         return f"{self.__class__.__name__}()"
@@ -510,11 +543,15 @@ class _DualPotentials(HubnessReduction):
     `fit` + `kneighbors` run ONE search.  The result is an approximation whose quality depends on `n_candidates` (on the 300 x 300
     test case at eps = 0.02: hits@1 0.803 with 10 candidates as over the whole index, 0.780 with 5; raw distance 0.723).  A target
     row that no source row lists has no potential: its `target_potential_` is NaN, and it ranks last (by row) in
-    `kneighbors_whole_index` and `gold_ranks(reduced=True)`."""
+    `kneighbors_whole_index` and `gold_ranks(reduced=True)`.  "union": the pairs of the forward AND the reverse candidate lists
+    (`SklearnNN.neighbor_pairs(n_candidates, mode="union")`, a CSR; kz_sinkhorn_csr): every target row lists `n_candidates` sources, so
+    every target row has pairs and `target_potential_` holds no NaN; a step reads at most n_source x n_candidates + n_target x
+    n_candidates values, `fit` takes both directions from one shared sweep where that applies, and the forward lists stay cached for
+    the `kneighbors` that follows."""
 
     _device_native = True
     _no_rank_reason = None
-    _SUPPORTS = ("index", "candidates")
+    _SUPPORTS = ("index", "candidates", "union")
 
     def __init__(self, temperature: float = 0.05, support: str = "index", **kwargs):
         if (isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.integer, np.floating))
@@ -537,6 +574,10 @@ class _DualPotentials(HubnessReduction):
     def _potentials_lists(self, dist, ind, n_target):
         """The same from the forward candidate lists dist / ind [n_s, K] (DeviceArrays) and the number of target rows."""
 
+    @abstractmethod
+    def _potentials_csr(self, indptr, ind, dist, n_target):
+        """The same from a CSR of pairs over the source rows (float64 values, DeviceArrays) and the number of target rows."""
+
     def fit(self, source, target=None):
         if target is None and not _is_precomputed(self.nn_algo):   # (a precomputed distance matrix IS two-sided)
             raise ValueError(f"{type(self).__name__} normalises between two sides: two-sided data only (fit(source, target))")
@@ -553,6 +594,14 @@ class _DualPotentials(HubnessReduction):
             dist, ind = nn.kneighbors_device(query=None, k=nn.n_candidates)
             self._f_dev, self._g_dev = self._potentials_lists(dist, ind, target_m.shape[0])
             nn._forward = (dist.shape[1], dist, ind)
+        elif self.support == "union":
+            # the raw lists of BOTH directions at n_candidates (one shared sweep where it applies), their union as a CSR with the plain
+            # float64 distances, rows by (value, target row): `neighbor_pairs(n_candidates, mode="union")` before its output cast.
+            # Every target row lists n_candidates sources, so every column has pairs.  The forward lists go back into the one-shot cache.
+            k, _ = nn._pairs_args(None, "union", type(self).__name__)
+            indptr, ind, dist, fwd = nn._neighbor_pairs(k, "union", True, True, cast=False)
+            self._f_dev, self._g_dev = self._potentials_csr(indptr, ind, dist, target_m.shape[0])
+            nn._forward = (fwd[0].shape[1],) + tuple(fwd)
         else:
             self._f_dev, self._g_dev = self._potentials(source_m, target_m)
 
@@ -599,7 +648,8 @@ class Sinkhorn(_DualPotentials):
     `source_potential_` / `target_potential_` (numpy), `n_iter_`, `potential_change_` (the last measured change of g: None after a
     single iteration).  `support="candidates"`: the same iteration with both soft-mins taken over the pairs of the forward candidate
     lists only (`_DualPotentials`): the cost of a step no longer grows with n_source x n_target, the result depends on
-    `n_candidates`.  Not a name of the resolver: pass the class or an instance, `Kiez(hubness=Sinkhorn, hubness_kwargs={...})`."""
+    `n_candidates`; `support="union"`: over the pairs of the forward and the reverse candidate lists -- no target row is left without a
+    potential.  Not a name of the resolver: pass the class or an instance, `Kiez(hubness=Sinkhorn, hubness_kwargs={...})`."""
 
     def __init__(self, temperature: float = 0.05, n_iter: int = 10, tol: Optional[float] = None, support: str = "index", **kwargs):
         if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
@@ -617,6 +667,11 @@ class Sinkhorn(_DualPotentials):
     def _potentials_lists(self, dist, ind, n_target):
         """The same iteration over the pairs of the lists, in one native call (kz_sinkhorn_lists: the stop is decided on the device)."""
         f, g, self.n_iter_, self.potential_change_ = N.sinkhorn_lists(self.ctx, dist, ind, n_target, self.temperature, self.n_iter, self.tol)
+        return f, g
+
+    def _potentials_csr(self, indptr, ind, dist, n_target):
+        """The same iteration over the pairs of a CSR, in one native call (kz_sinkhorn_csr)."""
+        f, g, self.n_iter_, self.potential_change_ = N.sinkhorn_csr(self.ctx, indptr, ind, dist, n_target, self.temperature, self.n_iter, self.tol)
         return f, g
 
     def _potentials(self, source_m, target_m):
@@ -642,6 +697,7 @@ class InvertedSoftmax(_DualPotentials):
     step from f = 0 with the constant left out, g_j = softmin_eps over i of d_ij, and f stays 0: the lists are ranked by d_ij - g_j.
     `temperature`: eps > 0, in the units of the distance the search returns.  `support="candidates"`: the log-sum-exp runs over the
     source rows that list the target among their `n_candidates` nearest only (`_DualPotentials`); a target nobody lists gets NaN.
+    `support="union"`: over those and the target's own `n_candidates` nearest source rows: every target has a value.
     Not a name of the resolver: pass the class or an instance."""
 
     def __repr__(self):
@@ -657,6 +713,12 @@ class InvertedSoftmax(_DualPotentials):
         self.n_iter_, self.potential_change_ = 1, None
         g = N.softmin_list_cols(self.ctx, N.lists_transpose(self.ctx, dist, ind, n_target), self.temperature)
         return self.ctx.to_device(np.zeros(dist.shape[0], dtype=np.float64)), g
+
+    def _potentials_csr(self, indptr, ind, dist, n_target):
+        """One column step over the transposed view of the CSR, without offset or constant."""
+        self.n_iter_, self.potential_change_ = 1, None
+        g = N.softmin_list_cols(self.ctx, N.csr_transpose(self.ctx, indptr, ind, dist, n_target), self.temperature)
+        return self.ctx.to_device(np.zeros(indptr.shape[0] - 1, dtype=np.float64)), g
 
 
 _DESIRED_P_VALUE = 2

@@ -238,6 +238,70 @@ class Kiez:
         match_dist, match_ind = self.assign_radius_device(radius, reduced, unmatched_cost, eps)
         return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
 
+    # ---- both directions, then one-to-one: the same two steps on the neighbour pairs of both searches (a CSR, rows of any length) --
+    def neighbor_pairs_device(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_distance: bool = True,
+                              sort_results: bool = True):
+        """Like `neighbor_pairs` but the CSR stays in HBM as DeviceArrays."""
+        algo = self.hubness if reduced else self.algorithm
+        return algo.neighbor_pairs_device(k, mode, sort_results, return_distance)
+
+    def neighbor_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_distance: bool = True,
+                       sort_results: bool = True):
+        """The neighbour pairs of BOTH search directions as one CSR over the source rows: F = (i, j) with target j among the k nearest
+        targets of source i, R = (i, j) with source i among the k nearest sources of target j, and `mode` "forward" (F), "reverse" (R,
+        grouped by source row), "union" (F | R: bidirectional candidate generation -- a target that no source lists still takes
+        part) or "mutual" (F & R: mutual nearest neighbours, the high-precision filter of bootstrapping alignment).  Membership is
+        always decided by the raw lists of the two searches under the search metric, ties included; every pair appears once.
+
+        `reduced` has the meaning it has in `radius_neighbors`: False values a pair by the distance `kneighbors` computes from source
+        i to target j -- also a pair only R holds --, True by the hubness-reduced distance of the fitted reduction
+        (`HubnessReduction.neighbor_pairs`; none: the plain values; MutualProximity 'empiric' and DisSimLocal raise
+        NotImplementedError).  Either way the value has the bits `radius_neighbors(inf, reduced=...)` returns for the pair.  A NaN
+        value stays in the result and sorts last.  `k`: None means `n_candidates`, else an int >= 1 that is NOT clamped to
+        `n_candidates`.
+
+        Returns the CSR `(indptr int64 [n_source + 1], ind int64 [total], dist [total])`, or `(indptr, ind)` with
+        `return_distance=False`, rows ascending by (value, target row) or, with `sort_results=False`, by target row; numpy arrays, or
+        tensors when fitted on tensors.  ValueError for another `mode` or a k that is no positive int, NotFittedError before `fit`,
+        NotImplementedError after a single-source fit."""
+        algo = self.hubness if reduced else self.algorithm
+        return algo.neighbor_pairs(k, mode, return_distance, sort_results)
+
+    def _pairs_of_both_directions(self, k, mode, reduced):
+        """The device CSR of `neighbor_pairs(k, mode, reduced)`, rows by (value, target row) -> (indptr, ind, dist, n_target)."""
+        indptr, ind, dist = self.neighbor_pairs_device(k, mode, reduced)
+        return indptr, ind, dist, self.algorithm.target_.shape[0]
+
+    def match_pairs_device(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False):
+        """Like `match_pairs` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+        indptr, ind, dist, n_target = self._pairs_of_both_directions(k, mode, reduced)
+        match, col, _ = N.match_csr(dist.ctx, indptr, ind, dist, n_target)
+        return N.match_values_csr(dist.ctx, indptr, dist, col), match
+
+    def match_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_distance: bool = True):
+        """Both directions, then one-to-one: `match` over the pairs of `neighbor_pairs(k, mode, reduced)` instead of the forward lists
+        -- every check and error of that call applies.  "mutual" matches among mutual nearest neighbours only; "union" lets a source
+        propose to a target that lists it although it does not list the target.  The CSR never leaves HBM and its rows have no length
+        limit (kz_match_csr).  Returns what `match` returns."""
+        match_dist, match_ind = self.match_pairs_device(k, mode, reduced)
+        return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
+
+    def assign_pairs_device(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, unmatched_cost: Optional[float] = None,
+                            eps: Optional[float] = None):
+        """Like `assign_pairs` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
+        from . import matching
+        unmatched_cost, eps, _ = matching._assignment_options(unmatched_cost, eps, 1)
+        indptr, ind, dist, n_target = self._pairs_of_both_directions(k, mode, reduced)
+        return matching.assignment_csr(indptr, ind, dist, n_target, unmatched_cost=unmatched_cost, eps=eps)
+
+    def assign_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_distance: bool = True,
+                     unmatched_cost: Optional[float] = None, eps: Optional[float] = None):
+        """`assign` over the pairs of `neighbor_pairs(k, mode, reduced)`, as `match_pairs` takes them: the minimum-cost one-to-one
+        matching among the pairs of both directions (kz_assign_csr); `unmatched_cost` and `eps` as in `assign`.  Returns what `match`
+        returns."""
+        match_dist, match_ind = self.assign_pairs_device(k, mode, reduced, unmatched_cost, eps)
+        return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
+
     def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
         """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
         ranks into hits@k, mean rank and mean reciprocal rank).

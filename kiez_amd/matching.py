@@ -325,3 +325,61 @@ def sinkhorn_csr(indptr, ind, dist, n_target: int, *, temperature: float = 0.05,
                                         int(n_iter), tol)
     out = (f, g) if on_device else (f.numpy(), g.numpy())
     return out + ({"n_iter": done, "potential_change": change},) if return_info else out
+
+
+# ---- the producer of such a CSR from two list arrays: forward, reverse, union, mutual --------------------------------------------
+def _checked_ids(what, ind):
+    """One list array of `combine_lists` -> a 2-D int64 array (numpy or `DeviceArray`), before the device is touched."""
+    if not isinstance(ind, N.DeviceArray):
+        ind = np.asarray(ind)
+    if len(ind.shape) != 2 or ind.shape[1] < 1:
+        raise ValueError(f"{what} must be a 2-D array of ids with at least one column, got shape {tuple(ind.shape)}")
+    if not np.issubdtype(ind.dtype, np.integer) or ind.dtype == np.bool_:
+        raise ValueError(f"{what} must hold integer row ids, got {ind.dtype}")
+    if isinstance(ind, N.DeviceArray):
+        if ind.dtype != np.int64:
+            raise ValueError(f"a device {what} must be int64, got {ind.dtype}")
+    elif ind.dtype != np.int64:
+        if ind.dtype == np.uint64 and ind.size and ind.max() > np.iinfo(np.int64).max:
+            raise ValueError(f"{what} holds ids beyond int64")
+        ind = ind.astype(np.int64)
+    return ind
+
+
+def combine_lists(fwd_ind, rev_ind, *, mode: str, n_source: Optional[int] = None, n_target: Optional[int] = None,
+                  ctx: Optional[N.Context] = None):
+    """The set combination of a forward and a reverse list array into a CSR over the source rows (kz_lists_combine), for lists from
+    anywhere.  `fwd_ind` [n_source, k_f]: target ids per source row; `rev_ind` [n_target, k_r]: source ids per target row; k_f != k_r
+    is fine.  With F = {(i, fwd_ind[i, c])} and R = {(rev_ind[j, c], j)}, `mode` "forward" gives F, "reverse" R grouped by source row
+    (the transposed reverse lists), "union" F | R and "mutual" F & R -- every pair once.  An id outside its range is no pair,
+    `one_to_one`'s rule: -1, the INT_MAX padding of `kneighbors_whole_index`, an id >= n.  An id repeated inside a row counts once.
+    "forward" ignores `rev_ind` and "reverse" `fwd_ind` (None is fine); `n_source` / `n_target` default to the row counts of the arrays
+    and must be named where the one array read does not say them.
+
+    Returns `(indptr int64 [n_source + 1], ind int64 [total])`: the targets of source row i are `ind[indptr[i]:indptr[i + 1]]`,
+    ascending by target id.  numpy arrays give numpy arrays; if the array read first is a `DeviceArray`, so are the results.  The
+    same bytes from every call.  Values for the pairs: `Kiez.neighbor_pairs` computes them for a fitted instance."""
+    mode = N.pair_mode(mode, "combine_lists")
+    use_f, use_r = mode != "reverse", mode != "forward"
+    fwd = _checked_ids("fwd_ind", fwd_ind) if use_f else None
+    rev = _checked_ids("rev_ind", rev_ind) if use_r else None
+    for what, n in (("n_source", n_source), ("n_target", n_target)):
+        if n is not None and (isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < (what == "n_target")):
+            raise ValueError(f"{what} must be a {'positive' if what == 'n_target' else 'non-negative'} integer, got {n!r}")
+    # (the array a one-sided mode does not read still says how many rows its side has, where it is given)
+    if n_source is None and (use_f or fwd_ind is not None):
+        n_source = fwd.shape[0] if use_f else _checked_ids("fwd_ind", fwd_ind).shape[0]
+    if n_target is None and (use_r or rev_ind is not None):
+        n_target = rev.shape[0] if use_r else _checked_ids("rev_ind", rev_ind).shape[0]
+    if n_source is None or n_target is None:
+        raise ValueError(f"combine_lists(mode={mode!r}) reads one list array: name n_source and n_target")
+    if (use_f and fwd.shape[0] != n_source) or (use_r and rev.shape[0] != n_target):
+        raise ValueError(f"fwd_ind has one row per source row and rev_ind one per target row: got n_source = {n_source}, n_target = "
+                         f"{n_target} and shapes {tuple(fwd.shape) if use_f else None}, {tuple(rev.shape) if use_r else None}")
+    first = fwd if use_f else rev
+    on_device = isinstance(first, N.DeviceArray)
+    if ctx is None:
+        ctx = next((a.ctx for a in (fwd, rev) if isinstance(a, N.DeviceArray)), None) or N.Context.get()
+    indptr, ind, _ = N.lists_combine(ctx, ctx.as_device(fwd) if use_f else None, ctx.as_device(rev) if use_r else None, mode,
+                                     int(n_source), int(n_target))
+    return (indptr, ind) if on_device else (indptr.numpy(), ind.numpy())

@@ -576,6 +576,88 @@ class SklearnNN(NNAlgorithm):
         indptr, = self._results_to_host(indptr)
         return indptr[1:] - indptr[:-1]
 
+    # ---- the neighbour pairs of both directions as a CSR ----------------------------------------------
+    def _pairs_args(self, k, mode, what="neighbor_pairs"):
+        """(k, mode) of a `neighbor_pairs` call after the checks that need no device: `mode` one of the four, k None (`n_candidates`,
+        silently: this is not `kneighbors`) or an int >= 1 -- never clamped to `n_candidates`."""
+        mode = N.pair_mode(mode, what)
+        if k is None:
+            k = self.n_candidates
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"{what} needs a positive integer k (or None: n_candidates), got {k!r}")
+        return int(k), mode
+
+    def _raw_pair_lists(self, k, mode, query, index):
+        """The raw lists the pairs are taken from -> (forward (dist, ind) | None, reverse ind | None): the k nearest targets of every
+        source row and the k nearest sources of every target row, each as far as `mode` reads it and each with the search's own checks
+        on k.  Where both are asked for and one sweep can serve both (`kneighbors_device_both`) it does; forward lists a shared
+        sweep left cached are read, not consumed: `_forward` is left as found."""
+        fwd = rev = None
+        cached = self._forward
+        try:
+            if mode != "reverse":
+                k_f = self._check_k_value(k, index.shape[0])
+                if cached is not None and cached[0] == k_f:
+                    fwd = cached[1:]
+            if mode != "forward":
+                k_r = self._check_k_value(k, query.shape[0])
+                if (mode != "reverse" and fwd is None and query is getattr(self, "source_index", None)
+                        and index is getattr(self, "target_index", None)):
+                    both = self.kneighbors_device_both(k)
+                    if both is not None:
+                        rev, fwd = both[1], self._forward[1:]
+                if rev is None:
+                    _, rev, self.last_stats_reverse = N.knn(self.ctx, index, query, k_r)
+            if mode != "reverse" and fwd is None:
+                dist, ind, self.last_stats = N.knn(self.ctx, query, index, k_f)
+                fwd = (dist, ind)
+        finally:
+            self._forward = cached
+        return fwd, rev
+
+    def _neighbor_pairs(self, k, mode, sort_results, return_distance, kind=None, q_state=None, t_state=None, cast=True):
+        """The device CSR of `neighbor_pairs` -> (indptr, ind, dist | None, forward lists | None): the set step on the raw lists, the
+        value of every pair (plain, or reduced by `kind` and its state), the row sort, the output dtype LAST."""
+        query, index = self._two_sided_operands("neighbor_pairs")
+        fwd, rev = self._raw_pair_lists(k, mode, query, index)
+        ctx = self.ctx
+        indptr, ind, _ = N.lists_combine(ctx, fwd[1] if fwd is not None else None, rev, mode, query.shape[0], index.shape[0])
+        del rev
+        if not (return_distance or sort_results):
+            return indptr, ind, None, fwd
+        dist = N.pairs_values(ctx, query, index, indptr, ind, kind, q_state, t_state)
+        if sort_results:
+            N.csr_sort_rows(ctx, indptr, ind, dist, index.shape[0])
+        if not return_distance:
+            return indptr, ind, None, fwd
+        return indptr, ind, (self._radius_distances(dist, self.target_index) if cast else dist), fwd
+
+    def neighbor_pairs_device(self, k=None, mode="union", sort_results=True, return_distance=True):
+        """`neighbor_pairs` with the CSR left in HBM: (indptr int64 [n_source + 1], ind int64 [total], dist [total]) DeviceArrays, or
+        (indptr, ind) with `return_distance=False`."""
+        k, mode = self._pairs_args(k, mode)
+        indptr, ind, dist, _ = self._neighbor_pairs(k, mode, sort_results, return_distance)
+        return (indptr, ind, dist) if return_distance else (indptr, ind)
+
+    def neighbor_pairs(self, k=None, mode="union", return_distance=True, sort_results=True):
+        """The neighbour pairs of BOTH search directions as one CSR over the source rows.  F = the pairs (i, j) with target row j among
+        the k nearest targets of source row i (`kneighbors(k)`), R = the pairs (i, j) with source row i among the k nearest sources
+        of target row j (`kneighbors(k, query=target, s_to_t=False)`); membership is decided by those raw lists, ties included.
+        `mode`: "forward" = F, "reverse" = R grouped by source row, "union" = F | R (bidirectional candidates: a target that no source
+        lists still takes part), "mutual" = F & R (mutual nearest neighbours).  Every pair appears once.  The value of a pair is
+        ALWAYS the distance `kneighbors` computes from source row i to target row j -- also for a pair only R holds -- with the bits
+        `radius_neighbors(inf)` returns for it; a NaN value stays (membership is by lists) and sorts last.
+
+        `k`: None means `n_candidates` (no warning); else an int >= 1, not clamped to `n_candidates`; each direction's search applies
+        its own checks.  Returns `(indptr int64 [n_source + 1], ind int64 [total], dist [total])`, or `(indptr, ind)` with
+        `return_distance=False`: the targets of source row i are `ind[indptr[i]:indptr[i + 1]]`, ascending by (value, target row) or,
+        with `sort_results=False`, by target row; rows have no length limit (a hub source can be listed by every target).  numpy
+        arrays, or tensors when fitted on tensors; `dist` in the dtype `kneighbors` returns (for float32 cosine / precomputed input
+        the cast comes last).  A fit that indexed the target only (NoHubnessReduction) searches the reverse direction against an
+        upload of the source.  NotFittedError before `fit`, NotImplementedError after a single-source fit, ValueError for a `mode`
+        outside the four or a k that is no positive int.  A shared sweep's cached forward lists are left as found."""
+        return self._results_to_host(*self.neighbor_pairs_device(k, mode, sort_results, return_distance))
+
     def kneighbors_device_both(self, k=None):
         """Both directions between the fitted source and target from ONE sweep of the distance matrix (kz_knn_dual): returns
         the target -> source result (what HubnessReduction.fit needs, base.py:37-42) and keeps the source -> target result
