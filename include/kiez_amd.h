@@ -630,6 +630,35 @@ int kz_pairs_values(kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index,
  * +inf: last, by index row.  Ids must be below 2^31 - 1.  The indptr validation runs first.  Synchronises the context's stream. */
 int kz_csr_sort_rows(kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz, int64_t n_index, int64_t* d_ind, double* d_dist);
 
+/* ---- ENTITY CLUSTERS: the connected components of a pair list (kz_components.hip) -- additive, ABI v7 ------------------------- */
+/* The third way to resolve a many-to-many pair list, beside the one-to-one calls and Sinkhorn: its transitive closure.  The graph is
+ * bipartite: source row i is node i, target row j is node n_q + j, and every stored entry (i, d_ind[p]) with 0 <= d_ind[p] < n_index
+ * is an edge (any other entry -- a -1, kz_knn_reduced's INT_MAX padding, an id >= n_index -- is no pair: kz_match_lists' rule; a pair
+ * stored twice is one edge; values are not read).  EVERY node belongs to a component: a source row without a pair and a target row
+ * nobody lists are components of one node.  Components are numbered 0 .. C - 1 IN THE ORDER OF THEIR SMALLEST NODE, source rows before
+ * target rows (so d_label_q[0] == 0 whenever n_q > 0): one answer, the same bytes in every run, whatever order anything ran in.
+ *   d_label_q [n_q], d_label_t [n_index]   (int64, device) the component of every source row and of every target row;
+ *   d_size_q, d_size_t                     (int64, device; BOTH NULL or both given, each with room for n_q + n_index entries) the
+ *                                          number of source rows and of target rows of component c, c < *h_n_components; entries
+ *                                          behind that are not written.  A source singleton has (1, 0), a target singleton (0, 1);
+ *   *h_n_components                        (host) C.
+ * kz_components_csr reads the CSR (d_indptr [n_q + 1], d_ind [nnz]) after the indptr validation of every CSR call;
+ * kz_components_lists reads fixed-width lists d_ind [n_q, k] (any k >= 1: k is no candidate count here).
+ * How: union-find on int32 parent words with parent[v] <= v ALWAYS.  One thread per ENTRY (a hub row of 10^5 entries costs what 10^5
+ * entries of short rows cost) finds the two roots with path halving and links the larger root under the smaller with one
+ * compare-and-swap, continuing from the value it read when it loses.  The root of a finished tree is the smallest node of the
+ * component.  Then: every node stores its root, an exclusive integer prefix sum of the root flags numbers the roots, and (when asked)
+ * the sizes are integer adds, pre-aggregated per wave.  Integer arithmetic and integer atomics only; no kernel waits for another
+ * workgroup; every loop is bounded by decreasing node ids.
+ * Limits, all decided BEFORE anything is launched: kz_csr_require's (0 <= n_q, nnz <= 2^31 - 2, 1 <= n_index <= 2^31 - 2), k >= 1,
+ * one size array without the other: KZ_ERR_INVALID; n_q + n_index >= 2^31 - 1 (node ids are int32) or, for lists, n_q k > 2^31 - 2:
+ * KZ_ERR_UNSUPPORTED.  n_q == 0 and nnz == 0 are legal (every node a singleton).  Transient device memory: 12 bytes per node.
+ * Synchronises the context's stream. */
+int kz_components_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, int64_t n_q, int64_t nnz, int64_t n_index,
+                      int64_t* d_label_q, int64_t* d_label_t, int64_t* d_size_q, int64_t* d_size_t, int64_t* h_n_components);
+int kz_components_lists(kz_ctx* ctx, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index, int64_t* d_label_q,
+                        int64_t* d_label_t, int64_t* d_size_q, int64_t* d_size_t, int64_t* h_n_components);
+
 /* float64 -> float32 cast of an [count] array (cosine + float32 inputs keep the reference's output dtype). */
 int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count);
 

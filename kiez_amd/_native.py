@@ -189,6 +189,8 @@ SYMBOLS = [
     ("kz_lists_combine", C.c_int, [_P, _P, _I64, C.c_int, _P, _I64, C.c_int, C.c_int, _I64, _P, _P, C.POINTER(_I64)]),
     ("kz_pairs_values", C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_csr_sort_rows", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
+    ("kz_components_csr", C.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_components_lists", C.c_int, [_P, _P, _I64, C.c_int, _I64, _P, _P, _P, _P, C.POINTER(_I64)]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_comm_destroy", C.c_int, [_P]),
@@ -1062,6 +1064,48 @@ def csr_sort_rows(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: Dev
     dist permuted in place (`radius_neighbors`' row sort, a row of any length)."""
     n_q, nnz = _f64_csr(indptr, ind, dist)
     _check(ctx.lib.kz_csr_sort_rows(ctx.handle, indptr.ptr, n_q, nnz, int(n_index), ind.ptr, dist.ptr), "kz_csr_sort_rows")
+
+
+# ---- entity clusters: the connected components of a pair list (include/kiez_amd.h: kz_components_*) ----------------------------
+COMPONENTS_MAX_NODES = 2 ** 31 - 2   # n_source + n_target: node ids are int32 on the device
+
+
+def _components_result(ctx: Context, n_q: int, n_index: int, sizes: bool, call):
+    """Allocates the outputs of a kz_components_* call, runs `call(label_q, label_t, size_q | None, size_t | None, byref(count))` and
+    returns (label_q, label_t, n_components) or, with sizes, (label_q, label_t, size_q, size_t, n_components), the two size arrays
+    sliced to n_components."""
+    label_q, label_t = ctx.empty((n_q,), np.int64), ctx.empty((n_index,), np.int64)
+    room = n_q + n_index if sizes and 1 <= n_q + n_index <= COMPONENTS_MAX_NODES else 0
+    size_q = ctx.empty((room,), np.int64) if sizes else None
+    size_t = ctx.empty((room,), np.int64) if sizes else None
+    count = _I64(0)
+    call(label_q, label_t, size_q.ptr if sizes else None, size_t.ptr if sizes else None, C.byref(count))
+    n = int(count.value)
+    if not sizes:
+        return label_q, label_t, n
+    return label_q, label_t, size_q.view_rows(0, n), size_t.view_rows(0, n), n
+
+
+def components_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, n_target: int, sizes: bool = False):
+    """kz_components_csr -> (source_label int64 [n_q], target_label int64 [n_target], n_components) on the device, with `sizes` the
+    int64 arrays (n_source_in, n_target_in) [n_components] in front of the count: the connected components of the bipartite graph whose
+    edges are the entries of the CSR (indptr [n_q + 1], ind [nnz]) with 0 <= ind < n_target, numbered in the order of their smallest
+    node, source rows before target rows.  A bad indptr raises ValueError, more than COMPONENTS_MAX_NODES rows NotImplementedError."""
+    if (not isinstance(indptr, DeviceArray) or len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64
+            or not isinstance(ind, DeviceArray) or len(ind.shape) != 1 or ind.dtype != np.int64):
+        raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries and ind a 1-D int64 DeviceArray")
+    n_q, nnz, n_index = indptr.shape[0] - 1, ind.shape[0], int(n_target)
+    return _components_result(ctx, n_q, n_index, sizes, lambda lq, lt, sq, st, count: _check(
+        ctx.lib.kz_components_csr(ctx.handle, indptr.ptr, ind.ptr, n_q, nnz, n_index, lq.ptr, lt.ptr, sq, st, count), "kz_components_csr"))
+
+
+def components_lists(ctx: Context, ind: DeviceArray, n_target: int, sizes: bool = False):
+    """kz_components_lists -> what `components_csr` returns, for fixed-width lists ind [n_q, k] (any k >= 1); an entry outside
+    [0, n_target) -- a -1, INT_MAX padding -- is no pair."""
+    n_q, k = _list_ids("ind", ind)
+    n_index = int(n_target)
+    return _components_result(ctx, n_q, n_index, sizes, lambda lq, lt, sq, st, count: _check(
+        ctx.lib.kz_components_lists(ctx.handle, ind.ptr, n_q, k, n_index, lq.ptr, lt.ptr, sq, st, count), "kz_components_lists"))
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):

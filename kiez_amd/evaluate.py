@@ -140,3 +140,44 @@ def hits(nn_ind: Union[np.ndarray, list, Dict[Any, List], "N.DeviceArray"], gold
     N._check(ctx.lib.kz_hit_positions(ctx.handle, ind_dev.ptr, gold_dev.ptr, n, cols, hist.ptr), "kz_hit_positions")
     cum = np.cumsum(hist.numpy()[:cols])
     return {kk: (float(cum[min(kk, cols) - 1]) / len(gold) if kk >= 1 else 0.0) for kk in k}
+
+
+def _labels(what: str, label) -> np.ndarray:
+    """One label vector of a clustering on the host: a 1-D array of integers >= 0."""
+    arr = label.numpy() if isinstance(label, N.DeviceArray) else np.asarray(label)
+    if arr.ndim != 1 or not (np.issubdtype(arr.dtype, np.integer) or arr.size == 0) or arr.dtype == np.bool_:
+        raise ValueError(f"{what} must be a one-dimensional integer vector of cluster ids")
+    arr = arr.astype(np.int64, copy=False)
+    if arr.size and arr.min() < 0:
+        raise ValueError(f"{what} holds a negative cluster id")
+    return arr
+
+
+def cluster_metrics(source_label, target_label, gold) -> Dict[str, Any]:
+    """Precision, recall and F1 of the pairs a clustering of source and target rows IMPLIES -- every (i, j) with
+    `source_label[i] == target_label[j]` -- against the gold pairs: the score of `matching.components_csr`, `Kiez.components_radius`
+    and `Kiez.components_pairs` (numpy arrays or `DeviceArray`s, which are brought to the host).
+
+    `gold`: the dict of `hits`, or the integer array with one gold target per source row and -1 for none.  Returns {"precision":
+    n_true / n_pairs (0.0 without a pair), "recall": n_true / n_gold, "f1", "n_pairs": the sum over the clusters of (source rows x
+    target rows), a Python int, "n_true": the gold pairs (i, gold[i]) with gold[i] a target row and both ends in one cluster,
+    "n_gold": as `rank_metrics` counts it, "n_components"}.  A gold id that is no target row counts in n_gold only.  O(n) integer
+    work on the host, the sizes by one bincount per side."""
+    src, tgt = _labels("source_label", source_label), _labels("target_label", target_label)
+    gold_arr = _gold_rows(gold, src.shape[0])
+    n_gold = len(gold) if isinstance(gold, dict) else int(np.count_nonzero(gold_arr != _NO_GOLD))
+    n_components = int(max(src.max(initial=-1), tgt.max(initial=-1))) + 1
+    n_source_in = np.bincount(src, minlength=n_components)
+    n_target_in = np.bincount(tgt, minlength=n_components)
+    # (at most n_source x n_target: exact in int64 for every row count the library takes, and beyond in float-free Python ints)
+    if src.shape[0] * tgt.shape[0] < 2 ** 63:
+        n_pairs = int(np.dot(n_source_in.astype(np.int64), n_target_in.astype(np.int64)))
+    else:
+        n_pairs = sum(int(a) * int(b) for a, b in zip(n_source_in, n_target_in))
+    rows = np.flatnonzero((gold_arr >= 0) & (gold_arr < tgt.shape[0]))
+    n_true = int(np.count_nonzero(src[rows] == tgt[gold_arr[rows]]))
+    precision = n_true / n_pairs if n_pairs else 0.0
+    recall = n_true / n_gold if n_gold else 0.0
+    f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
+    return {"precision": precision, "recall": recall, "f1": f1, "n_pairs": n_pairs, "n_true": n_true, "n_gold": n_gold,
+            "n_components": n_components}

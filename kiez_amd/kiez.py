@@ -302,6 +302,42 @@ class Kiez:
         match_dist, match_ind = self.assign_pairs_device(k, mode, reduced, unmatched_cost, eps)
         return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
 
+    # ---- threshold or both directions, then the transitive closure: entity clusters of the same two CSRs ------------------------
+    @staticmethod
+    def _components_of(indptr, ind, n_target, return_sizes):
+        res = N.components_csr(ind.ctx, indptr, ind, n_target, sizes=bool(return_sizes))
+        return tuple(res[:4] if return_sizes else res[:2])
+
+    def components_radius_device(self, radius, reduced: bool = False, return_sizes: bool = False):
+        """Like `components_radius` but the label (and size) arrays stay in HBM as DeviceArrays."""
+        indptr, ind, _, n_target = self._pairs_within_radius(radius, reduced)
+        return self._components_of(indptr, ind, n_target, return_sizes)
+
+    def components_radius(self, radius, reduced: bool = False, return_sizes: bool = False):
+        """Threshold, then the transitive closure: the entity clusters of the pairs of `radius_neighbors(radius, reduced=reduced)` --
+        every source and target row connected through accepted pairs is one cluster (`matching.components_csr`), where `match_radius`
+        forces a one-to-one answer.  Every check and error of the radius call applies, `reduced` has its meaning there.  The CSR
+        never leaves HBM (kz_components_csr).
+
+        Returns `(source_label int64 [n_source], target_label int64 [n_target])`, clusters numbered in the order of their smallest
+        node, source rows before target rows; with `return_sizes=True` also `(n_source_in, n_target_in)`, the rows of every cluster
+        per side: `(n_source_in == 1) & (n_target_in == 1)` are the unambiguous alignments, 1:n and n:m clusters the non-bijective
+        ones, one giant cluster the sign of a threshold that is too loose.  numpy arrays, also after a fit on tensors.
+        `evaluate.cluster_metrics(source_label, target_label, gold)` scores the implied pairs."""
+        return tuple(x.numpy() for x in self.components_radius_device(radius, reduced, return_sizes))
+
+    def components_pairs_device(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_sizes: bool = False):
+        """Like `components_pairs` but the label (and size) arrays stay in HBM as DeviceArrays."""
+        indptr, ind, _, n_target = self._pairs_of_both_directions(k, mode, reduced)
+        return self._components_of(indptr, ind, n_target, return_sizes)
+
+    def components_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_sizes: bool = False):
+        """Both directions, then the transitive closure: the entity clusters of the pairs of `neighbor_pairs(k, mode, reduced)` --
+        every check and error of that call applies.  With "mutual" and k = 1 every cluster has at most one row per side, and the
+        (1, 1) clusters are the pairs `match_pairs(1, "mutual")` returns.  The CSR never leaves HBM (kz_components_csr).  Returns what
+        `components_radius` returns."""
+        return tuple(x.numpy() for x in self.components_pairs_device(k, mode, reduced, return_sizes))
+
     def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
         """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
         ranks into hits@k, mean rank and mean reciprocal rank).

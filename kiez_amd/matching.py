@@ -51,28 +51,35 @@ def _checked_dtypes(dist, ind):
 
 def _checked_csr(dist, ind, indptr, n_target):
     """The argument checks of the CSR functions, all before the device is touched -> (dist, ind, indptr) as the native
-    calls take them.  A host `indptr` is checked in full here; one on the device is checked there, by the native call."""
+    calls take them.  A host `indptr` is checked in full here; one on the device is checked there, by the native call.
+    `dist` None (`components_csr`: a CSR without values): the same checks of `ind` and `indptr`, and None comes back for it."""
     if isinstance(n_target, (bool, np.bool_)) or not isinstance(n_target, (int, np.integer)) or n_target < 1:
         raise ValueError(f"n_target must be a positive integer, got {n_target!r}")
-    if not isinstance(dist, N.DeviceArray):
+    if dist is not None and not isinstance(dist, N.DeviceArray):
         dist = np.asarray(dist)
     if not isinstance(ind, N.DeviceArray):
         ind = np.asarray(ind)
     if not isinstance(indptr, N.DeviceArray):
         indptr = np.asarray(indptr)
-    if len(dist.shape) != 1 or len(ind.shape) != 1 or tuple(dist.shape) != tuple(ind.shape):
+    if dist is None:
+        if len(ind.shape) != 1:
+            raise ValueError(f"ind must be a 1-D array (the entries of a CSR), got shape {tuple(ind.shape)}")
+    elif len(dist.shape) != 1 or len(ind.shape) != 1 or tuple(dist.shape) != tuple(ind.shape):
         raise ValueError(f"dist and ind must be 1-D arrays of one length (the entries of a CSR), got {tuple(dist.shape)} "
                          f"and {tuple(ind.shape)}")
     if len(indptr.shape) != 1 or indptr.shape[0] < 1:
         raise ValueError(f"indptr must be a 1-D array of n_source + 1 row starts, got shape {tuple(indptr.shape)}")
     if not np.issubdtype(indptr.dtype, np.integer) or indptr.dtype == np.bool_:
         raise ValueError(f"indptr must hold integer row starts, got {indptr.dtype}")
-    dist, ind = _checked_dtypes(dist, ind)
+    if dist is None:
+        ind = _checked_ids("ind", ind, ndim=1)
+    else:
+        dist, ind = _checked_dtypes(dist, ind)
     if isinstance(indptr, N.DeviceArray):
         if indptr.dtype != np.int64:
             raise ValueError(f"a device indptr must be int64, got {indptr.dtype}")
     else:
-        nnz = dist.shape[0]
+        nnz = ind.shape[0]
         if indptr[0] != 0 or indptr[-1] != nnz or (indptr.shape[0] > 1 and bool((indptr[1:] < indptr[:-1]).any())):
             raise ValueError(f"indptr must start at 0, never decrease and end at the number of entries {nnz}, got {indptr[0]} .. {indptr[-1]}")
         indptr = indptr.astype(np.int64, copy=False)
@@ -328,11 +335,12 @@ def sinkhorn_csr(indptr, ind, dist, n_target: int, *, temperature: float = 0.05,
 
 
 # ---- the producer of such a CSR from two list arrays: forward, reverse, union, mutual --------------------------------------------
-def _checked_ids(what, ind):
-    """One list array of `combine_lists` -> a 2-D int64 array (numpy or `DeviceArray`), before the device is touched."""
+def _checked_ids(what, ind, ndim=2):
+    """One list array of `combine_lists` or `components` -> a 2-D int64 array (numpy or `DeviceArray`), before the device is touched.
+    (`ndim` 1: the entries of a CSR, whose shape `_checked_csr` has checked.)"""
     if not isinstance(ind, N.DeviceArray):
         ind = np.asarray(ind)
-    if len(ind.shape) != 2 or ind.shape[1] < 1:
+    if ndim == 2 and (len(ind.shape) != 2 or ind.shape[1] < 1):
         raise ValueError(f"{what} must be a 2-D array of ids with at least one column, got shape {tuple(ind.shape)}")
     if not np.issubdtype(ind.dtype, np.integer) or ind.dtype == np.bool_:
         raise ValueError(f"{what} must hold integer row ids, got {ind.dtype}")
@@ -383,3 +391,57 @@ def combine_lists(fwd_ind, rev_ind, *, mode: str, n_source: Optional[int] = None
     indptr, ind, _ = N.lists_combine(ctx, ctx.as_device(fwd) if use_f else None, ctx.as_device(rev) if use_r else None, mode,
                                      int(n_source), int(n_target))
     return (indptr, ind) if on_device else (indptr.numpy(), ind.numpy())
+
+
+# ---- the transitive closure of a pair list: entity clusters (kz_components_csr, kz_components_lists) ------------------------------
+def _checked_node_count(n_source, n_target):
+    if n_source + n_target > N.COMPONENTS_MAX_NODES:
+        raise ValueError(f"n_source + n_target = {n_source + n_target} rows, the limit is {N.COMPONENTS_MAX_NODES} (2**31 - 2)")
+
+
+def _components_out(res, return_sizes, on_device):
+    out = res[:4] if return_sizes else res[:2]
+    return tuple(out) if on_device else tuple(x.numpy() for x in out)
+
+
+def components_csr(indptr, ind, n_target: int, *, return_sizes: bool = False, ctx: Optional[N.Context] = None):
+    """Entity clusters: the connected components of the bipartite graph of a pair list, on the device (kz_components_csr) -- the
+    transitive closure "everything connected by accepted pairs is one entity", the third way to resolve a many-to-many pair list
+    beside `one_to_one_csr` / `assignment_csr` and `sinkhorn_csr`.
+
+    `indptr` [n_source + 1] and `ind`: a CSR as `one_to_one_csr` takes it, without values -- of `Kiez.radius_neighbors`,
+    `Kiez.neighbor_pairs`, `from_sparse`, `combine_lists` or anything else; numpy arrays or `DeviceArray`s.  Source row i and target row
+    j are joined by every entry `j = ind[p]` of row i with 0 <= j < n_target; any other entry is no pair, a pair may repeat.  EVERY
+    row belongs to a cluster: a source row without a pair and a target row nobody lists are clusters of one row.  Clusters are numbered
+    0 .. C - 1 in the order of their smallest node, source rows before target rows -- what
+    `scipy.sparse.csgraph.connected_components([[0, B], [B.T, 0]], directed=False)` returns, bit for bit, from every run.
+
+    Returns `(source_label int64 [n_source], target_label int64 [n_target])`; with `return_sizes=True` also
+    `(n_source_in, n_target_in)`, int64 [C]: the source and target rows of every cluster.  `(n_source_in == 1) & (n_target_in == 1)`
+    are the unambiguous alignments, a giant cluster says the threshold is too loose.  numpy arrays in give numpy arrays, if `ind` is a
+    `DeviceArray` so are the results.  `evaluate.cluster_metrics` scores the pairs the clustering implies.  Argument errors are raised
+    before the device is touched; an `indptr` on the device that does not start at 0, decreases or does not end at the number of
+    entries raises ValueError there, before anything reads through it.  Fixed-width lists: `components`."""
+    _, ind, indptr = _checked_csr(None, ind, indptr, n_target)
+    _checked_node_count(indptr.shape[0] - 1, int(n_target))
+    on_device = isinstance(ind, N.DeviceArray)
+    ctx = _csr_context(ctx, ind, indptr, None)
+    res = N.components_csr(ctx, ctx.as_device(indptr), ctx.as_device(ind), int(n_target), sizes=bool(return_sizes))
+    return _components_out(res, return_sizes, on_device)
+
+
+def components(ind, n_target: int, *, return_sizes: bool = False, ctx: Optional[N.Context] = None):
+    """`components_csr` over fixed-width lists (kz_components_lists): `ind` [n_source, k] as `kneighbors` returns it, any k >= 1; an
+    entry outside [0, n_target) -- a -1, the INT_MAX padding of `kneighbors_whole_index` -- is no pair.  Every result and error as
+    `components_csr`."""
+    if isinstance(n_target, (bool, np.bool_)) or not isinstance(n_target, (int, np.integer)) or n_target < 1:
+        raise ValueError(f"n_target must be a positive integer, got {n_target!r}")
+    ind = _checked_ids("ind", ind)
+    _checked_node_count(ind.shape[0], int(n_target))
+    if ind.shape[0] * ind.shape[1] > 2 ** 31 - 2:
+        raise ValueError(f"ind has {ind.shape[0] * ind.shape[1]} entries, the limit is 2**31 - 2")
+    on_device = isinstance(ind, N.DeviceArray)
+    if ctx is None:
+        ctx = ind.ctx if on_device else N.Context.get()
+    res = N.components_lists(ctx, ctx.as_device(ind), int(n_target), sizes=bool(return_sizes))
+    return _components_out(res, return_sizes, on_device)
