@@ -707,65 +707,301 @@ def max_abs_diff(ctx: Context, a: DeviceArray, b: DeviceArray) -> float:
     return float(h.value)
 
 
-def _list_pair(dist: DeviceArray, ind: DeviceArray):
-    """(n_q, k, dtype code) of a pair of neighbour lists on the device, as kz_match_lists / kz_match_values take them."""
-    if not isinstance(dist, DeviceArray) or not isinstance(ind, DeviceArray):
-        raise ValueError("dist and ind must be DeviceArrays")
-    if len(dist.shape) != 2 or dist.shape != ind.shape:
-        raise ValueError(f"dist and ind must be 2-D and of one shape, got {dist.shape} and {ind.shape}")
-    if dist.dtype not in (np.float32, np.float64) or ind.dtype != np.int64:
-        raise ValueError(f"dist must be float32 or float64 and ind int64, got {dist.dtype} and {ind.dtype}")
-    return dist.shape[0], dist.shape[1], KZ_F32 if dist.dtype == np.float32 else KZ_F64
-
-
 # entries of a column per first-level wave of kz_softmin_list_cols (include/kiez_amd.h: KZ_SOFTMIN_LIST_CHUNK): part of its summation order
 SOFTMIN_LIST_CHUNK = 512
+# a row with more entries bids with one wave in kz_assign_csr (include/kiez_amd.h: KZ_CSR_LONG_ROW)
+CSR_LONG_ROW = 256
+COMPONENTS_MAX_NODES = 2 ** 31 - 2   # n_source + n_target of kz_components_*: node ids are int32 on the device
 
 
-def _f64_lists(dist: DeviceArray, ind: DeviceArray):
-    """(n_q, k) of float64 / int64 neighbour lists on the device, as the soft-min calls over the lists take them."""
-    n_q, k, dtype = _list_pair(dist, ind)
-    if dtype != KZ_F64:
-        raise ValueError(f"the soft-min over neighbour lists takes float64 values, got {dist.dtype}")
-    return n_q, k
+def _list_ids(what: str, ind: DeviceArray):
+    if not isinstance(ind, DeviceArray) or len(ind.shape) != 2 or ind.dtype != np.int64:
+        raise ValueError(f"{what} must be a 2-D int64 DeviceArray of ids, got "
+                         f"{getattr(ind, 'dtype', type(ind).__name__)} {getattr(ind, 'shape', '')}")
+    return ind.shape
 
 
 class ListsTransposed:
-    """The column-major view of the pairs of neighbour lists (kz_lists_transpose): `colptr` int64 [n_index + 1], `col_row` int32 and
-    `col_val` float64 with `nnz` entries used (the arrays hold n_q k); column j is colptr[j] .. colptr[j + 1] - 1, ascending source row."""
+    """The column-major view of the pairs of a pair list (`PairList.transpose`): `colptr` int64 [n_index + 1], `col_row` int32 and
+    `col_val` float64 with `nnz` entries used (the arrays hold every entry); column j is colptr[j] .. colptr[j + 1] - 1, ascending
+    source row."""
 
     def __init__(self, colptr, col_row, col_val, nnz, n_q, n_index):
         self.colptr, self.col_row, self.col_val, self.nnz, self.n_q, self.n_index = colptr, col_row, col_val, nnz, n_q, n_index
 
 
+class PairList:
+    """A PAIR LIST on the device in either of its two layouts -- THE place of the Python side that knows them apart (the native one:
+    kz_rows.h / kz_rows.hip).  Fixed width (`PairList.lists`): dist / ind [n_q, k], entry (i, c) pairs source row i with target row
+    ind[i, c].  CSR (`PairList.csr`): indptr int64 [n_q + 1], ind and dist [nnz], row i holds the entries indptr[i] ..
+    indptr[i + 1] - 1; rows of any length, also none.  Either way an entry is a pair when 0 <= ind < n_target (a -1, the INT_MAX
+    padding of `knn_reduced`: none), ind is int64 and dist float32 or float64; `dist` None: a list without values (`components`),
+    `ind` None: values alone (`values`).  The constructors check shapes and dtypes; the CONTENT of a CSR's indptr is checked on the
+    device, by every call, before anything reads through it (a bad one raises ValueError).
+
+    Every operation is one method with one body: it allocates the outputs, puts the layout's leading arguments in the order its
+    native symbol takes them (`_head`) and calls the symbol of the layout (`OPS`); what follows the head is the same for both."""
+
+    # operation -> (the fixed-width symbol, the CSR symbol, which leading arguments the pair takes: `_head`'s keywords)
+    OPS = {
+        "match": ("kz_match_lists", "kz_match_csr", {"dtype": True}),
+        "values": ("kz_match_values", "kz_match_values_csr", {"dtype": True, "ids": False, "col": True}),
+        "assign": ("kz_assign_lists", "kz_assign_csr", {"dtype": True}),
+        "value_range": ("kz_assign_range", "kz_assign_range_csr", {"dtype": True}),
+        "transpose": ("kz_lists_transpose", "kz_csr_transpose", {}),
+        "softmin_rows": ("kz_softmin_list_rows", "kz_softmin_csr_rows", {}),
+        "sinkhorn": ("kz_sinkhorn_lists", "kz_sinkhorn_csr", {}),
+        "components": ("kz_components_lists", "kz_components_csr", {"values": False}),
+    }
+
+    def __init__(self, ctx, dist, ind, indptr, n_target, n_q, width):
+        self.ctx, self.dist, self.ind, self.indptr = ctx, dist, ind, indptr
+        self.n_target = None if n_target is None else int(n_target)
+        self.n_q = n_q
+        self._width = width   # fixed width: k; CSR: nnz -- what follows n_q in a native call
+
+    @classmethod
+    def lists(cls, ctx: "Context", dist: Optional[DeviceArray], ind: Optional[DeviceArray], n_target: Optional[int]) -> "PairList":
+        """The fixed-width lists dist / ind [n_q, k]."""
+        if dist is None:
+            n_q, k = _list_ids("ind", ind)
+        elif ind is None:
+            if len(dist.shape) != 2 or dist.dtype not in (np.float32, np.float64):
+                raise ValueError(f"dist must be a 2-D float32 or float64 device array, got {dist.dtype} {dist.shape}")
+            n_q, k = dist.shape
+        else:
+            if not isinstance(dist, DeviceArray) or not isinstance(ind, DeviceArray):
+                raise ValueError("dist and ind must be DeviceArrays")
+            if len(dist.shape) != 2 or dist.shape != ind.shape:
+                raise ValueError(f"dist and ind must be 2-D and of one shape, got {dist.shape} and {ind.shape}")
+            if dist.dtype not in (np.float32, np.float64) or ind.dtype != np.int64:
+                raise ValueError(f"dist must be float32 or float64 and ind int64, got {dist.dtype} and {ind.dtype}")
+            n_q, k = dist.shape
+        return cls(ctx, dist, ind, None, n_target, n_q, k)
+
+    @classmethod
+    def csr(cls, ctx: "Context", indptr: DeviceArray, ind: Optional[DeviceArray], dist: Optional[DeviceArray],
+            n_target: Optional[int]) -> "PairList":
+        """The CSR (indptr, ind, dist)."""
+        ptr_ok = isinstance(indptr, DeviceArray) and len(indptr.shape) == 1 and indptr.shape[0] >= 1 and indptr.dtype == np.int64
+        if dist is None:
+            if not ptr_ok or not isinstance(ind, DeviceArray) or len(ind.shape) != 1 or ind.dtype != np.int64:
+                raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries and ind a 1-D int64 DeviceArray")
+        elif ind is None:
+            if not ptr_ok:
+                raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries")
+            if not isinstance(dist, DeviceArray) or len(dist.shape) != 1 or dist.dtype not in (np.float32, np.float64):
+                raise ValueError("with indptr, dist must be a 1-D float32 or float64 DeviceArray")
+        else:
+            if not all(isinstance(a, DeviceArray) for a in (indptr, ind, dist)):
+                raise ValueError("indptr, ind and dist must be DeviceArrays")
+            if not ptr_ok:
+                raise ValueError(f"indptr must be a 1-D int64 array of n_q + 1 entries, got {indptr.dtype} {indptr.shape}")
+            if len(dist.shape) != 1 or dist.shape != ind.shape:
+                raise ValueError(f"with indptr, dist and ind must be 1-D and of one length, got {dist.shape} and {ind.shape}")
+            if dist.dtype not in (np.float32, np.float64) or ind.dtype != np.int64:
+                raise ValueError(f"dist must be float32 or float64 and ind int64, got {dist.dtype} and {ind.dtype}")
+        return cls(ctx, dist, ind, indptr, n_target, indptr.shape[0] - 1, (dist if ind is None else ind).shape[0])
+
+    @property
+    def is_csr(self) -> bool:
+        return self.indptr is not None
+
+    @property
+    def n_entries(self) -> int:
+        return self._width if self.is_csr else self.n_q * self._width
+
+    @property
+    def dtype_code(self) -> int:
+        return KZ_F32 if self.dist.dtype == np.float32 else KZ_F64
+
+    def require_f64(self) -> "PairList":
+        """`self` if its values are float64, as the soft-min calls and the row sort take them."""
+        if self.dist.dtype != np.float64:
+            raise ValueError(f"the soft-min over {'a CSR pair list' if self.is_csr else 'neighbour lists'} takes float64 values, "
+                             f"got {self.dist.dtype}")
+        return self
+
+    def _head(self, values: bool = True, dtype: bool = False, ids: bool = True, col: Optional[DeviceArray] = None) -> tuple:
+        """The leading arguments of a native call: fixed width `ctx, dist[, dtype], ind[, col], n_q, k`, CSR
+        `ctx, indptr, ind, dist[, dtype][, col], n_q, nnz` -- without the values, the ids or with `col` where the call says so."""
+        d = ((self.dist.ptr,) + ((self.dtype_code,) if dtype else ())) if values else ()
+        i = (self.ind.ptr,) if ids else ()
+        c = () if col is None else (col.ptr,)
+        if self.is_csr:
+            return (self.ctx.handle, self.indptr.ptr) + i + d + c + (self.n_q, self._width)
+        return (self.ctx.handle,) + d + i + c + (self.n_q, self._width)
+
+    def _call(self, op: str, *tail, col: Optional[DeviceArray] = None):
+        """The native symbol of `op` for this layout: its head, then `tail`."""
+        name = self.OPS[op][self.is_csr]
+        head = {key: (col if key == "col" else flag) for key, flag in self.OPS[op][2].items()}
+        _check(getattr(self.ctx.lib, name)(*self._head(**head), *tail), name)
+
+    def match(self) -> Tuple[DeviceArray, DeviceArray, int]:
+        """kz_match_lists / kz_match_csr -> (match int64 [n_q], col int64 [n_q], rounds): the source-proposing stable matching against
+        n_target target rows.  match[i] is the target row of source row i and col[i] the column of that pair -- in a CSR the position
+        of the entry inside row i --, -1 both where the row stays unmatched; rounds counts the proposal rounds."""
+        match, col = self.ctx.empty((self.n_q,), np.int64), self.ctx.empty((self.n_q,), np.int64)
+        rounds = _I64(0)
+        self._call("match", self.n_target, match.ptr, col.ptr, C.byref(rounds))
+        return match, col, int(rounds.value)
+
+    def values(self, col: DeviceArray) -> DeviceArray:
+        """kz_match_values[_csr] -> the value of entry col[i] of row i in dist's dtype, NaN where col[i] is outside the row (-1): [n_q]
+        on the device."""
+        if col.dtype != np.int64 or col.shape != (self.n_q,):
+            raise ValueError(f"col must be int64 of shape ({self.n_q},), got {col.dtype} {col.shape}")
+        out = self.ctx.empty((self.n_q,), self.dist.dtype)
+        self._call("values", out.ptr, col=col)
+        return out
+
+    def assign(self, unmatched_cost: float, eps: float, max_rounds: int, tail_rows: int = 0, want_prices: bool = False):
+        """kz_assign_lists / kz_assign_csr -> (match int64 [n_q], col int64 [n_q], prices float64 [n_target] | None, rounds,
+        converged): the forward auction against n_target target rows -- a one-to-one matching whose cost (the values of the matched
+        pairs plus unmatched_cost per unmatched row) is within n_q * eps of the minimum.  match / col as `match` returns them.
+        tail_rows: 0 the default switch to the single-workgroup kernel, 1 .. 1024 that many FREE rows, negative never; rows of a CSR
+        with more than CSR_LONG_ROW entries bid with one wave; the arrays depend on neither.  converged False: max_rounds ended the
+        run, the matching is valid but not optimal."""
+        match, col = self.ctx.empty((self.n_q,), np.int64), self.ctx.empty((self.n_q,), np.int64)
+        prices = self.ctx.empty((self.n_target,), np.float64) if want_prices and 1 <= self.n_target < 2 ** 31 - 1 else None
+        rounds, converged = _I64(0), C.c_int(0)
+        self._call("assign", self.n_target, float(unmatched_cost), float(eps), int(max_rounds), int(tail_rows), match.ptr, col.ptr,
+                   prices.ptr if prices is not None else None, C.byref(rounds), C.byref(converged))
+        return match, col, prices, int(rounds.value), bool(converged.value)
+
+    def value_range(self):
+        """kz_assign_range[_csr] -> (smallest, largest) finite value listed with 0 <= ind < n_target, as float64; None when there is
+        none."""
+        lo, hi, some = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+        self._call("value_range", self.n_target, C.byref(lo), C.byref(hi), C.byref(some))
+        return (float(lo.value), float(hi.value)) if some.value else None
+
+    def transpose(self) -> ListsTransposed:
+        """kz_lists_transpose / kz_csr_transpose -> the column-major view of the pairs (float64 values): the entries of a column in
+        ascending flat position (ascending source row).  The same arrays from every run."""
+        ctx = self.require_f64().ctx
+        colptr = ctx.empty((self.n_target + 1,), np.int64)
+        col_row, col_val = ctx.empty((self.n_entries,), np.int32), ctx.empty((self.n_entries,), np.float64)
+        nnz = _I64(0)
+        self._call("transpose", self.n_target, colptr.ptr, col_row.ptr, col_val.ptr, C.byref(nnz))
+        return ListsTransposed(colptr, col_row, col_val, int(nnz.value), self.n_q, self.n_target)
+
+    def softmin_rows(self, eps: float, off: Optional[DeviceArray] = None, shift: float = 0.0) -> DeviceArray:
+        """kz_softmin_list_rows / kz_softmin_csr_rows -> float64 [n_q] on the device: per row the soft-min at temperature `eps` over
+        the row's PAIRS of (dist - off[ind]), plus `shift`.  `off`: a float64 DeviceArray [n_target] or None.  A row without a pair
+        gives NaN; the bits of a row do not depend on the other rows of the call.  The summation tree differs by layout: fixed width
+        the tree of k, a CSR row the one `softmin_list_cols` gives a column of as many entries -- the same bits as that call on the
+        view (colptr = indptr, col_row = ind, col_val = dist)."""
+        self.require_f64()
+        if off is not None:
+            _f64_vector("off", off, self.n_target)
+        out = self.ctx.empty((self.n_q,), np.float64)
+        self._call("softmin_rows", self.n_target, float(eps), off.ptr if off is not None else None, float(shift), out.ptr)
+        return out
+
+    def sinkhorn(self, eps: float, n_iter: int, tol: Optional[float] = None) -> Tuple[DeviceArray, DeviceArray, int, Optional[float]]:
+        """kz_sinkhorn_lists / kz_sinkhorn_csr -> (f float64 [n_q], g float64 [n_target], iterations done, last measured change of g or
+        None): the Sinkhorn iteration of `softmin_list_cols` on `transpose`'s view and `softmin_rows` from f = 0, queued at once, the
+        stopping rule (`tol`; None: none) decided on the device."""
+        ctx = self.require_f64().ctx
+        f, g = ctx.empty((self.n_q,), np.float64), ctx.empty((self.n_target,), np.float64)
+        done, change, measured = C.c_int(0), C.c_double(0.0), C.c_int(0)
+        self._call("sinkhorn", self.n_target, float(eps), int(n_iter), -1.0 if tol is None else float(tol), f.ptr, g.ptr, C.byref(done),
+                   C.byref(change), C.byref(measured))
+        return f, g, int(done.value), float(change.value) if measured.value else None
+
+    def components(self, sizes: bool = False):
+        """kz_components_lists / kz_components_csr -> (source_label int64 [n_q], target_label int64 [n_target], n_components) on the
+        device, with `sizes` the int64 arrays (n_source_in, n_target_in) [n_components] in front of the count: the connected
+        components of the bipartite graph whose edges are the pairs (fixed width: any k >= 1), numbered in the order of their smallest
+        node, source rows before target rows.  More than COMPONENTS_MAX_NODES rows raise NotImplementedError."""
+        ctx, n_q, n_t = self.ctx, self.n_q, self.n_target
+        label_q, label_t = ctx.empty((n_q,), np.int64), ctx.empty((n_t,), np.int64)
+        room = n_q + n_t if sizes and 1 <= n_q + n_t <= COMPONENTS_MAX_NODES else 0
+        size_q = ctx.empty((room,), np.int64) if sizes else None
+        size_t = ctx.empty((room,), np.int64) if sizes else None
+        count = _I64(0)
+        self._call("components", n_t, label_q.ptr, label_t.ptr, size_q.ptr if sizes else None, size_t.ptr if sizes else None, C.byref(count))
+        n = int(count.value)
+        if not sizes:
+            return label_q, label_t, n
+        return label_q, label_t, size_q.view_rows(0, n), size_t.view_rows(0, n), n
+
+
+# ---- the calls of `PairList` by name and layout, as tests and tools take them ---------------------------------------------------
+def match_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int) -> Tuple[DeviceArray, DeviceArray, int]:
+    return PairList.lists(ctx, dist, ind, n_index).match()
+
+
+def match_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int) -> Tuple[DeviceArray, DeviceArray, int]:
+    return PairList.csr(ctx, indptr, ind, dist, n_index).match()
+
+
+def match_values(ctx: Context, dist: DeviceArray, col: DeviceArray) -> DeviceArray:
+    return PairList.lists(ctx, dist, None, None).values(col)
+
+
+def match_values_csr(ctx: Context, indptr: DeviceArray, dist: DeviceArray, col: DeviceArray) -> DeviceArray:
+    return PairList.csr(ctx, indptr, None, dist, None).values(col)
+
+
+def assign_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, unmatched_cost: float, eps: float, max_rounds: int,
+                 tail_rows: int = 0, want_prices: bool = False):
+    return PairList.lists(ctx, dist, ind, n_index).assign(unmatched_cost, eps, max_rounds, tail_rows, want_prices)
+
+
+def assign_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, unmatched_cost: float, eps: float,
+               max_rounds: int, tail_rows: int = 0, want_prices: bool = False):
+    return PairList.csr(ctx, indptr, ind, dist, n_index).assign(unmatched_cost, eps, max_rounds, tail_rows, want_prices)
+
+
+def assign_range(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int):
+    return PairList.lists(ctx, dist, ind, n_index).value_range()
+
+
+def assign_range_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int):
+    return PairList.csr(ctx, indptr, ind, dist, n_index).value_range()
+
+
 def lists_transpose(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int) -> ListsTransposed:
-    """kz_lists_transpose -> the column-major view of the pairs of dist / ind [n_q, k] (float64 / int64, on the device): entry (i, c)
-    with 0 <= ind[i, c] < n_index is a pair, any other id is none.  The same arrays from every run."""
-    n_q, k = _f64_lists(dist, ind)
-    colptr = ctx.empty((int(n_index) + 1,), np.int64)
-    col_row, col_val = ctx.empty((n_q * k,), np.int32), ctx.empty((n_q * k,), np.float64)
-    nnz = _I64(0)
-    _check(ctx.lib.kz_lists_transpose(ctx.handle, dist.ptr, ind.ptr, n_q, k, int(n_index), colptr.ptr, col_row.ptr, col_val.ptr, C.byref(nnz)),
-           "kz_lists_transpose")
-    return ListsTransposed(colptr, col_row, col_val, int(nnz.value), n_q, int(n_index))
+    return PairList.lists(ctx, dist, ind, n_index).transpose()
+
+
+def csr_transpose(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int) -> ListsTransposed:
+    return PairList.csr(ctx, indptr, ind, dist, n_index).transpose()
 
 
 def softmin_list_rows(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, eps: float, off: Optional[DeviceArray] = None,
                       shift: float = 0.0) -> DeviceArray:
-    """kz_softmin_list_rows -> float64 [n_q] on the device: per row the soft-min at temperature `eps` over the row's PAIRS of
-    (dist[i, c] - off[ind[i, c]]), plus `shift`.  `off`: a float64 DeviceArray [n_index] or None.  A row without a pair gives NaN; the
-    bits of a row do not depend on the other rows of the call."""
-    n_q, k = _f64_lists(dist, ind)
-    if off is not None:
-        _f64_vector("off", off, int(n_index))
-    out = ctx.empty((n_q,), np.float64)
-    _check(ctx.lib.kz_softmin_list_rows(ctx.handle, dist.ptr, ind.ptr, n_q, k, int(n_index), float(eps), off.ptr if off is not None else None,
-                                        float(shift), out.ptr), "kz_softmin_list_rows")
-    return out
+    return PairList.lists(ctx, dist, ind, n_index).softmin_rows(eps, off, shift)
+
+
+def softmin_csr_rows(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, eps: float,
+                     off: Optional[DeviceArray] = None, shift: float = 0.0) -> DeviceArray:
+    return PairList.csr(ctx, indptr, ind, dist, n_index).softmin_rows(eps, off, shift)
+
+
+def sinkhorn_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, eps: float, n_iter: int,
+                   tol: Optional[float] = None) -> Tuple[DeviceArray, DeviceArray, int, Optional[float]]:
+    return PairList.lists(ctx, dist, ind, n_index).sinkhorn(eps, n_iter, tol)
+
+
+def sinkhorn_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, eps: float, n_iter: int,
+                 tol: Optional[float] = None) -> Tuple[DeviceArray, DeviceArray, int, Optional[float]]:
+    return PairList.csr(ctx, indptr, ind, dist, n_index).sinkhorn(eps, n_iter, tol)
+
+
+def components_lists(ctx: Context, ind: DeviceArray, n_target: int, sizes: bool = False):
+    return PairList.lists(ctx, None, ind, n_target).components(sizes)
+
+
+def components_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, n_target: int, sizes: bool = False):
+    return PairList.csr(ctx, indptr, ind, None, n_target).components(sizes)
 
 
 def softmin_list_cols(ctx: Context, view: ListsTransposed, eps: float, off: Optional[DeviceArray] = None, shift: float = 0.0) -> DeviceArray:
-    """kz_softmin_list_cols -> float64 [n_index] on the device: per column of the view `lists_transpose` returned the soft-min over
+    """kz_softmin_list_cols -> float64 [n_index] on the device: per column of the view `PairList.transpose` returned the soft-min over
     its entries of (col_val[p] - off[col_row[p]]), plus `shift`.  `off`: a float64 DeviceArray [n_q] or None.  A column without an
     entry gives NaN; the bits of a column depend on its entry count and SOFTMIN_LIST_CHUNK only."""
     if off is not None:
@@ -774,186 +1010,6 @@ def softmin_list_cols(ctx: Context, view: ListsTransposed, eps: float, off: Opti
     _check(ctx.lib.kz_softmin_list_cols(ctx.handle, view.colptr.ptr, view.col_row.ptr, view.col_val.ptr, view.n_index, view.nnz, float(eps),
                                         off.ptr if off is not None else None, float(shift), out.ptr), "kz_softmin_list_cols")
     return out
-
-
-def sinkhorn_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, eps: float, n_iter: int,
-                   tol: Optional[float] = None) -> Tuple[DeviceArray, DeviceArray, int, Optional[float]]:
-    """kz_sinkhorn_lists -> (f float64 [n_q], g float64 [n_index], iterations done, last measured change of g or None): the Sinkhorn
-    iteration of `softmin_list_cols` / `softmin_list_rows` from f = 0, queued at once, the stopping rule (`tol`; None: none) decided
-    on the device."""
-    n_q, k = _f64_lists(dist, ind)
-    f, g = ctx.empty((n_q,), np.float64), ctx.empty((int(n_index),), np.float64)
-    done, change, measured = C.c_int(0), C.c_double(0.0), C.c_int(0)
-    _check(ctx.lib.kz_sinkhorn_lists(ctx.handle, dist.ptr, ind.ptr, n_q, k, int(n_index), float(eps), int(n_iter),
-                                     -1.0 if tol is None else float(tol), f.ptr, g.ptr, C.byref(done), C.byref(change), C.byref(measured)),
-           "kz_sinkhorn_lists")
-    return f, g, int(done.value), float(change.value) if measured.value else None
-
-
-def match_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int) -> Tuple[DeviceArray, DeviceArray, int]:
-    """kz_match_lists -> (match int64 [n_q], col int64 [n_q], rounds): the source-proposing stable matching over the neighbour lists
-    dist / ind [n_q, k] (float32 or float64 / int64, on the device) against n_index target rows.  match[i] is the target row of
-    source row i and col[i] the column of that pair, -1 both where the row stays unmatched; rounds counts the proposal rounds."""
-    n_q, k, dtype = _list_pair(dist, ind)
-    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
-    rounds = _I64(0)
-    _check(ctx.lib.kz_match_lists(ctx.handle, dist.ptr, dtype, ind.ptr, n_q, k, int(n_index), match.ptr, col.ptr, C.byref(rounds)),
-           "kz_match_lists")
-    return match, col, int(rounds.value)
-
-
-def match_values(ctx: Context, dist: DeviceArray, col: DeviceArray) -> DeviceArray:
-    """kz_match_values -> dist[i, col[i]] in dist's dtype, NaN where col[i] < 0: [n_q] on the device."""
-    if len(dist.shape) != 2 or dist.dtype not in (np.float32, np.float64):
-        raise ValueError(f"dist must be a 2-D float32 or float64 device array, got {dist.dtype} {dist.shape}")
-    n_q, k = dist.shape
-    if col.dtype != np.int64 or col.shape != (n_q,):
-        raise ValueError(f"col must be int64 of shape ({n_q},), got {col.dtype} {col.shape}")
-    out = ctx.empty((n_q,), dist.dtype)
-    _check(ctx.lib.kz_match_values(ctx.handle, dist.ptr, KZ_F32 if dist.dtype == np.float32 else KZ_F64, col.ptr, n_q, k, out.ptr),
-           "kz_match_values")
-    return out
-
-
-def assign_lists(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int, unmatched_cost: float, eps: float, max_rounds: int,
-                 tail_rows: int = 0, want_prices: bool = False):
-    """kz_assign_lists -> (match int64 [n_q], col int64 [n_q], prices float64 [n_index] | None, rounds, converged): the forward
-    auction over the neighbour lists dist / ind [n_q, k] against n_index target rows -- a one-to-one matching whose cost (the
-    values of the matched pairs plus unmatched_cost per unmatched row) is within n_q * eps of the minimum.  match / col as
-    `match_lists` returns them.  tail_rows: 0 the default switch to the single-workgroup kernel, 1 .. 1024 that many FREE rows,
-    negative never; the arrays do not depend on it.  converged False: max_rounds ended the run, the matching is valid but not
-    optimal."""
-    n_q, k, dtype = _list_pair(dist, ind)
-    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
-    prices = ctx.empty((int(n_index),), np.float64) if want_prices and 1 <= int(n_index) < 2 ** 31 - 1 else None
-    rounds, converged = _I64(0), C.c_int(0)
-    _check(ctx.lib.kz_assign_lists(ctx.handle, dist.ptr, dtype, ind.ptr, n_q, k, int(n_index), float(unmatched_cost), float(eps),
-                                   int(max_rounds), int(tail_rows), match.ptr, col.ptr, prices.ptr if prices is not None else None,
-                                   C.byref(rounds), C.byref(converged)), "kz_assign_lists")
-    return match, col, prices, int(rounds.value), bool(converged.value)
-
-
-def assign_range(ctx: Context, dist: DeviceArray, ind: DeviceArray, n_index: int):
-    """kz_assign_range -> (smallest, largest) finite value listed with 0 <= ind < n_index, as float64; None when there is none."""
-    n_q, k, dtype = _list_pair(dist, ind)
-    lo, hi, some = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
-    _check(ctx.lib.kz_assign_range(ctx.handle, dist.ptr, dtype, ind.ptr, n_q, k, int(n_index), C.byref(lo), C.byref(hi), C.byref(some)),
-           "kz_assign_range")
-    return (float(lo.value), float(hi.value)) if some.value else None
-
-
-# ---- the same calls on ragged (CSR) pair lists: indptr int64 [n_q + 1], ind int64 [nnz], dist [nnz], all on the device ----------
-# a row with more entries bids with one wave in kz_assign_csr (include/kiez_amd.h: KZ_CSR_LONG_ROW)
-CSR_LONG_ROW = 256
-
-
-def _csr_lists(indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray):
-    """(n_q, nnz, dtype code) of a CSR pair list on the device, as the kz_*_csr calls take it.  The CONTENT of indptr is checked on
-    the device, by the call itself, before anything reads through it."""
-    if not all(isinstance(a, DeviceArray) for a in (indptr, ind, dist)):
-        raise ValueError("indptr, ind and dist must be DeviceArrays")
-    if len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64:
-        raise ValueError(f"indptr must be a 1-D int64 array of n_q + 1 entries, got {indptr.dtype} {indptr.shape}")
-    if len(dist.shape) != 1 or dist.shape != ind.shape:
-        raise ValueError(f"with indptr, dist and ind must be 1-D and of one length, got {dist.shape} and {ind.shape}")
-    if dist.dtype not in (np.float32, np.float64) or ind.dtype != np.int64:
-        raise ValueError(f"dist must be float32 or float64 and ind int64, got {dist.dtype} and {ind.dtype}")
-    return indptr.shape[0] - 1, dist.shape[0], KZ_F32 if dist.dtype == np.float32 else KZ_F64
-
-
-def _f64_csr(indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray):
-    """(n_q, nnz) of a float64 CSR pair list on the device, as the soft-min calls over a CSR take it."""
-    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
-    if dtype != KZ_F64:
-        raise ValueError(f"the soft-min over a CSR pair list takes float64 values, got {dist.dtype}")
-    return n_q, nnz
-
-
-def match_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int) -> Tuple[DeviceArray, DeviceArray, int]:
-    """kz_match_csr -> (match int64 [n_q], col int64 [n_q], rounds): `match_lists` over a CSR pair list; col[i] is the position of the
-    matched entry inside row i.  A bad indptr (not starting at 0, decreasing, not ending at nnz) raises ValueError."""
-    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
-    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
-    rounds = _I64(0)
-    _check(ctx.lib.kz_match_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, dtype, n_q, nnz, int(n_index), match.ptr, col.ptr,
-                                C.byref(rounds)), "kz_match_csr")
-    return match, col, int(rounds.value)
-
-
-def match_values_csr(ctx: Context, indptr: DeviceArray, dist: DeviceArray, col: DeviceArray) -> DeviceArray:
-    """kz_match_values_csr -> dist[indptr[i] + col[i]] in dist's dtype, NaN where col[i] is outside row i: [n_q] on the device."""
-    if not isinstance(indptr, DeviceArray) or len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64:
-        raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries")
-    if not isinstance(dist, DeviceArray) or len(dist.shape) != 1 or dist.dtype not in (np.float32, np.float64):
-        raise ValueError("with indptr, dist must be a 1-D float32 or float64 DeviceArray")
-    n_q, nnz, dtype = indptr.shape[0] - 1, dist.shape[0], KZ_F32 if dist.dtype == np.float32 else KZ_F64
-    if col.dtype != np.int64 or col.shape != (n_q,):
-        raise ValueError(f"col must be int64 of shape ({n_q},), got {col.dtype} {col.shape}")
-    out = ctx.empty((n_q,), dist.dtype)
-    _check(ctx.lib.kz_match_values_csr(ctx.handle, indptr.ptr, dist.ptr, dtype, col.ptr, n_q, nnz, out.ptr), "kz_match_values_csr")
-    return out
-
-
-def assign_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, unmatched_cost: float, eps: float,
-               max_rounds: int, tail_rows: int = 0, want_prices: bool = False):
-    """kz_assign_csr -> (match, col, prices | None, rounds, converged): `assign_lists` over a CSR pair list, col as `match_csr`
-    returns it.  Rows of more than CSR_LONG_ROW entries bid with one wave; the arrays depend neither on that nor on tail_rows."""
-    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
-    match, col = ctx.empty((n_q,), np.int64), ctx.empty((n_q,), np.int64)
-    prices = ctx.empty((int(n_index),), np.float64) if want_prices and 1 <= int(n_index) < 2 ** 31 - 1 else None
-    rounds, converged = _I64(0), C.c_int(0)
-    _check(ctx.lib.kz_assign_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, dtype, n_q, nnz, int(n_index), float(unmatched_cost), float(eps),
-                                 int(max_rounds), int(tail_rows), match.ptr, col.ptr, prices.ptr if prices is not None else None,
-                                 C.byref(rounds), C.byref(converged)), "kz_assign_csr")
-    return match, col, prices, int(rounds.value), bool(converged.value)
-
-
-def assign_range_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int):
-    """kz_assign_range_csr -> (smallest, largest) finite value listed with 0 <= ind < n_index, as float64; None when there is none."""
-    n_q, nnz, dtype = _csr_lists(indptr, ind, dist)
-    lo, hi, some = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
-    _check(ctx.lib.kz_assign_range_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, dtype, n_q, nnz, int(n_index), C.byref(lo), C.byref(hi),
-                                       C.byref(some)), "kz_assign_range_csr")
-    return (float(lo.value), float(hi.value)) if some.value else None
-
-
-def csr_transpose(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int) -> ListsTransposed:
-    """kz_csr_transpose -> the column-major view of the pairs of a float64 CSR pair list, as `lists_transpose` gives it for lists:
-    the entries of a column in ascending flat position (ascending source row).  The same arrays from every run."""
-    n_q, nnz = _f64_csr(indptr, ind, dist)
-    colptr = ctx.empty((int(n_index) + 1,), np.int64)
-    col_row, col_val = ctx.empty((nnz,), np.int32), ctx.empty((nnz,), np.float64)
-    used = _I64(0)
-    _check(ctx.lib.kz_csr_transpose(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, n_q, nnz, int(n_index), colptr.ptr, col_row.ptr,
-                                    col_val.ptr, C.byref(used)), "kz_csr_transpose")
-    return ListsTransposed(colptr, col_row, col_val, int(used.value), n_q, int(n_index))
-
-
-def softmin_csr_rows(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, eps: float,
-                     off: Optional[DeviceArray] = None, shift: float = 0.0) -> DeviceArray:
-    """kz_softmin_csr_rows -> float64 [n_q] on the device: per row of the CSR the soft-min over its PAIRS of (dist[p] - off[ind[p]]),
-    plus `shift`.  The summation tree of a row is the one `softmin_list_cols` gives a column of as many entries: the same bits as
-    that call on the view (colptr = indptr, col_row = ind, col_val = dist).  A row without a pair gives NaN."""
-    n_q, nnz = _f64_csr(indptr, ind, dist)
-    if off is not None:
-        _f64_vector("off", off, int(n_index))
-    out = ctx.empty((n_q,), np.float64)
-    _check(ctx.lib.kz_softmin_csr_rows(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, n_q, nnz, int(n_index), float(eps),
-                                       off.ptr if off is not None else None, float(shift), out.ptr), "kz_softmin_csr_rows")
-    return out
-
-
-def sinkhorn_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int, eps: float, n_iter: int,
-                 tol: Optional[float] = None) -> Tuple[DeviceArray, DeviceArray, int, Optional[float]]:
-    """kz_sinkhorn_csr -> (f float64 [n_q], g float64 [n_index], iterations done, last measured change of g or None): `sinkhorn_lists`
-    over a CSR pair list -- the iteration of `softmin_list_cols` on `csr_transpose`'s view and `softmin_csr_rows`, queued at once."""
-    n_q, nnz = _f64_csr(indptr, ind, dist)
-    f, g = ctx.empty((n_q,), np.float64), ctx.empty((int(n_index),), np.float64)
-    done, change, measured = C.c_int(0), C.c_double(0.0), C.c_int(0)
-    _check(ctx.lib.kz_sinkhorn_csr(ctx.handle, indptr.ptr, ind.ptr, dist.ptr, n_q, nnz, int(n_index), float(eps), int(n_iter),
-                                   -1.0 if tol is None else float(tol), f.ptr, g.ptr, C.byref(done), C.byref(change), C.byref(measured)),
-           "kz_sinkhorn_csr")
-    return f, g, int(done.value), float(change.value) if measured.value else None
 
 
 # ---- neighbour pairs of both directions as a CSR (include/kiez_amd.h: KZ_PAIRS_*) ----------------------------------------------
@@ -965,13 +1021,6 @@ def pair_mode(mode, what: str = "neighbor_pairs") -> str:
     if not isinstance(mode, str) or mode not in PAIR_MODES:
         raise ValueError(f"{what}: mode must be one of {tuple(PAIR_MODES)}, got {mode!r}")
     return mode
-
-
-def _list_ids(what: str, ind: DeviceArray):
-    if not isinstance(ind, DeviceArray) or len(ind.shape) != 2 or ind.dtype != np.int64:
-        raise ValueError(f"{what} must be a 2-D int64 DeviceArray of ids, got "
-                         f"{getattr(ind, 'dtype', type(ind).__name__)} {getattr(ind, 'shape', '')}")
-    return ind.shape
 
 
 def _combine_call(ctx: Context, fwd_ind, rev_ind, n_q: int, k_f: int, n_index: int, k_r: int, mode: int, capacity: int):
@@ -1042,10 +1091,8 @@ def pairs_values(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, indptr:
     query row that holds it and index row ind[p] -- the distance `knn` returns for the pair (`kind` None) or, with a `kind` of
     `gold_ranks_reduced` and its `q_state` / `t_state`, the hubness-reduced distance: the bits `radius_neighbors` returns for the
     pair, whether or not a neighbour list holds it."""
-    if (not isinstance(indptr, DeviceArray) or len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64
-            or not isinstance(ind, DeviceArray) or len(ind.shape) != 1 or ind.dtype != np.int64):
-        raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries and ind a 1-D int64 DeviceArray")
-    n_q, nnz = indptr.shape[0] - 1, ind.shape[0]
+    pairs = PairList.csr(ctx, indptr, ind, None, index.shape[0])
+    n_q, nnz = pairs.n_q, pairs.n_entries
     if kind is None:
         if q_state is not None or t_state is not None:
             raise ValueError("q_state / t_state belong to a reduced call: name its kind")
@@ -1062,50 +1109,8 @@ def pairs_values(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, indptr:
 def csr_sort_rows(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: DeviceArray, n_index: int):
     """kz_csr_sort_rows: every row of the float64 CSR ascending by (value, index row) in `knn_reduced`'s order, NaN last -- ind and
     dist permuted in place (`radius_neighbors`' row sort, a row of any length)."""
-    n_q, nnz = _f64_csr(indptr, ind, dist)
-    _check(ctx.lib.kz_csr_sort_rows(ctx.handle, indptr.ptr, n_q, nnz, int(n_index), ind.ptr, dist.ptr), "kz_csr_sort_rows")
-
-
-# ---- entity clusters: the connected components of a pair list (include/kiez_amd.h: kz_components_*) ----------------------------
-COMPONENTS_MAX_NODES = 2 ** 31 - 2   # n_source + n_target: node ids are int32 on the device
-
-
-def _components_result(ctx: Context, n_q: int, n_index: int, sizes: bool, call):
-    """Allocates the outputs of a kz_components_* call, runs `call(label_q, label_t, size_q | None, size_t | None, byref(count))` and
-    returns (label_q, label_t, n_components) or, with sizes, (label_q, label_t, size_q, size_t, n_components), the two size arrays
-    sliced to n_components."""
-    label_q, label_t = ctx.empty((n_q,), np.int64), ctx.empty((n_index,), np.int64)
-    room = n_q + n_index if sizes and 1 <= n_q + n_index <= COMPONENTS_MAX_NODES else 0
-    size_q = ctx.empty((room,), np.int64) if sizes else None
-    size_t = ctx.empty((room,), np.int64) if sizes else None
-    count = _I64(0)
-    call(label_q, label_t, size_q.ptr if sizes else None, size_t.ptr if sizes else None, C.byref(count))
-    n = int(count.value)
-    if not sizes:
-        return label_q, label_t, n
-    return label_q, label_t, size_q.view_rows(0, n), size_t.view_rows(0, n), n
-
-
-def components_csr(ctx: Context, indptr: DeviceArray, ind: DeviceArray, n_target: int, sizes: bool = False):
-    """kz_components_csr -> (source_label int64 [n_q], target_label int64 [n_target], n_components) on the device, with `sizes` the
-    int64 arrays (n_source_in, n_target_in) [n_components] in front of the count: the connected components of the bipartite graph whose
-    edges are the entries of the CSR (indptr [n_q + 1], ind [nnz]) with 0 <= ind < n_target, numbered in the order of their smallest
-    node, source rows before target rows.  A bad indptr raises ValueError, more than COMPONENTS_MAX_NODES rows NotImplementedError."""
-    if (not isinstance(indptr, DeviceArray) or len(indptr.shape) != 1 or indptr.shape[0] < 1 or indptr.dtype != np.int64
-            or not isinstance(ind, DeviceArray) or len(ind.shape) != 1 or ind.dtype != np.int64):
-        raise ValueError("indptr must be a 1-D int64 DeviceArray of n_q + 1 entries and ind a 1-D int64 DeviceArray")
-    n_q, nnz, n_index = indptr.shape[0] - 1, ind.shape[0], int(n_target)
-    return _components_result(ctx, n_q, n_index, sizes, lambda lq, lt, sq, st, count: _check(
-        ctx.lib.kz_components_csr(ctx.handle, indptr.ptr, ind.ptr, n_q, nnz, n_index, lq.ptr, lt.ptr, sq, st, count), "kz_components_csr"))
-
-
-def components_lists(ctx: Context, ind: DeviceArray, n_target: int, sizes: bool = False):
-    """kz_components_lists -> what `components_csr` returns, for fixed-width lists ind [n_q, k] (any k >= 1); an entry outside
-    [0, n_target) -- a -1, INT_MAX padding -- is no pair."""
-    n_q, k = _list_ids("ind", ind)
-    n_index = int(n_target)
-    return _components_result(ctx, n_q, n_index, sizes, lambda lq, lt, sq, st, count: _check(
-        ctx.lib.kz_components_lists(ctx.handle, ind.ptr, n_q, k, n_index, lq.ptr, lt.ptr, sq, st, count), "kz_components_lists"))
+    pairs = PairList.csr(ctx, indptr, ind, dist, n_index).require_f64()
+    _check(ctx.lib.kz_csr_sort_rows(ctx.handle, indptr.ptr, pairs.n_q, pairs.n_entries, pairs.n_target, ind.ptr, dist.ptr), "kz_csr_sort_rows")
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):

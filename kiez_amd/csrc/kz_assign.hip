@@ -41,8 +41,6 @@ enum { KZ_ASSIGN_FREE = 0, KZ_ASSIGN_BIDDING = 1, KZ_ASSIGN_OWNER = 2, KZ_ASSIGN
 constexpr int KZ_ASSIGN_NO_ROW = 0x7fffffff;          // the second bid word of a target nobody bids on
 constexpr unsigned long long KZ_ASSIGN_NO_BID = 0ull; // the first: below the key of every double
 
-int kz_match_require(const char* who, kz_ctx* ctx, const void* d_dist, int dist_dtype, int64_t n_q, int k);   // kz_match.hip
-
 // working arrays (the context's scoped scratch)
 struct KzAssignState {
     unsigned long long* price;     // [n_index] the price as the bits of a double (d_price, or scratch)
@@ -386,11 +384,6 @@ __global__ __launch_bounds__(KZ_ASSIGN_TAIL_MAX) void kz_assign_tail_kernel(KzAs
     }
 }
 
-static int kz_assign_blocks(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : b < KZ_ASSIGN_BLOCKS ? b : KZ_ASSIGN_BLOCKS);
-}
-
 // nnz: the entries of a CSR (sizes the list of its long rows); unused for the fixed layout
 template <typename T, typename L>
 static int kz_assign_lists_impl(const char* who, kz_ctx* ctx, const T* d_dist, const int64_t* d_ind, int n_q, L rows, int64_t nnz,
@@ -419,8 +412,8 @@ static int kz_assign_lists_impl(const char* who, kz_ctx* ctx, const T* d_dist, c
     if (rc != KZ_OK) return rc;
     const KzAssignState s{d_price ? (unsigned long long*)d_price : price.get(), owner.get(), bid_key.get(), bid_row.get(), state.get(),
                           bid_col.get(), bid_val.get()};
-    const dim3 grid(kz_assign_blocks(n_q)), block(256);
-    hipLaunchKernelGGL(kz_assign_init_kernel, dim3(kz_assign_blocks(n_q > n_index ? n_q : n_index)), block, 0, ctx->stream, s, n_q,
+    const dim3 grid(kz_blocks(n_q, KZ_ASSIGN_BLOCKS)), block(256);
+    hipLaunchKernelGGL(kz_assign_init_kernel, dim3(kz_blocks(n_q > n_index ? n_q : n_index, KZ_ASSIGN_BLOCKS)), block, 0, ctx->stream, s, n_q,
                        (int)n_index, d_match, d_col);
     KZ_HIP(hipGetLastError());
     int n_long = 0;   // the long rows of the call, found once: every row starts FREE, so they are the long rows FREE now
@@ -510,11 +503,10 @@ extern "C" int kz_assign_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, 
     if (n_q == 0) return KZ_OK;
     KZ_REQUIRE(d_ind && d_match && d_col, "kz_assign_lists: null argument");
     if (tail_rows == 0) tail_rows = KZ_ASSIGN_TAIL_MAX;
-    if (dist_dtype == KZ_F32)
-        return kz_assign_lists_impl("kz_assign_lists", ctx, (const float*)d_dist, d_ind, (int)n_q, KzRowsFixed{k}, 0, n_index, unmatched_cost, eps,
-                                    max_rounds, tail_rows, d_match, d_col, d_price, h_rounds, h_converged);
-    return kz_assign_lists_impl("kz_assign_lists", ctx, (const double*)d_dist, d_ind, (int)n_q, KzRowsFixed{k}, 0, n_index, unmatched_cost, eps,
-                                max_rounds, tail_rows, d_match, d_col, d_price, h_rounds, h_converged);
+    return kz_with_values(dist_dtype, d_dist, [&](auto* dist) {
+        return kz_assign_lists_impl("kz_assign_lists", ctx, dist, d_ind, (int)n_q, KzRowsFixed{k}, 0, n_index, unmatched_cost, eps, max_rounds,
+                                    tail_rows, d_match, d_col, d_price, h_rounds, h_converged);
+    });
 }
 
 extern "C" int kz_assign_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const void* d_dist, int dist_dtype, int64_t n_q,
@@ -534,11 +526,10 @@ extern "C" int kz_assign_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t
     const int rcv = kz_csr_validate("kz_assign_csr", ctx, d_indptr, n_q, nnz);
     if (rcv != KZ_OK) return rcv;
     if (tail_rows == 0) tail_rows = KZ_ASSIGN_TAIL_MAX;
-    if (dist_dtype == KZ_F32)
-        return kz_assign_lists_impl("kz_assign_csr", ctx, (const float*)d_dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz, n_index, unmatched_cost,
-                                    eps, max_rounds, tail_rows, d_match, d_col, d_price, h_rounds, h_converged);
-    return kz_assign_lists_impl("kz_assign_csr", ctx, (const double*)d_dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz, n_index, unmatched_cost, eps,
-                                max_rounds, tail_rows, d_match, d_col, d_price, h_rounds, h_converged);
+    return kz_with_values(dist_dtype, d_dist, [&](auto* dist) {
+        return kz_assign_lists_impl("kz_assign_csr", ctx, dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz, n_index, unmatched_cost, eps, max_rounds,
+                                    tail_rows, d_match, d_col, d_price, h_rounds, h_converged);
+    });
 }
 
 // ---- the range of the listed values: what the defaults of unmatched_cost and eps are made of -----------------------------------
@@ -588,11 +579,10 @@ static int kz_assign_range_impl(kz_ctx* ctx, const void* d_dist, int dist_dtype,
     if (rc != KZ_OK) return rc;
     unsigned long long h_keys[2] = {~0ull, 0ull};
     KZ_HIP(hipMemcpyAsync(keys.get(), h_keys, sizeof(h_keys), hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid(kz_assign_blocks(count)), block(256);
-    if (dist_dtype == KZ_F32)
-        hipLaunchKernelGGL(kz_assign_range_kernel<float>, grid, block, 0, ctx->stream, (const float*)d_dist, d_ind, count, n_index, keys.get());
-    else
-        hipLaunchKernelGGL(kz_assign_range_kernel<double>, grid, block, 0, ctx->stream, (const double*)d_dist, d_ind, count, n_index, keys.get());
+    const dim3 grid(kz_blocks(count, KZ_ASSIGN_BLOCKS)), block(256);
+    kz_with_values(dist_dtype, d_dist, [&](auto* dist) {   // (the kernel's T follows from the pointer)
+        hipLaunchKernelGGL(kz_assign_range_kernel, grid, block, 0, ctx->stream, dist, d_ind, count, n_index, keys.get());
+    });
     KZ_HIP(hipGetLastError());
     KZ_HIP(hipMemcpyAsync(h_keys, keys.get(), sizeof(h_keys), hipMemcpyDeviceToHost, ctx->stream));
     KZ_HIP(hipStreamSynchronize(ctx->stream));

@@ -306,6 +306,12 @@ static inline int kz_dispatch_values(int dtype, const char* who, F&& f) {
 int kz_scratch(kz_ctx* ctx, size_t bytes, void** out);
 int kz_floor_buf(kz_ctx* ctx, size_t bytes, float** out);
 
+// workgroups of 256 threads for a grid-stride kernel over n items: ceil(n / 256) in [1, cap]
+static inline int kz_blocks(int64_t n, int cap) {
+    const int64_t b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : b < cap ? b : cap);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Canonical wave-cooperative float64 dot product.  Every exact distance in the library (row norms, the
 // re-rank, the exact fallback) goes through this routine so that |x|^2 + |y|^2 - 2 x.y is EXACTLY 0 for

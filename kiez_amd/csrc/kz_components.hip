@@ -190,11 +190,6 @@ __global__ __launch_bounds__(256) void kz_cc_labels_kernel(const int* __restrict
     }
 }
 
-int kz_cc_blocks(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : b < 4096 ? b : 4096);
-}
-
 // the checks both layouts share beyond kz_csr_require's, all before anything is launched
 int kz_cc_require(const char* who, int64_t n_q, int64_t n_index, const int64_t* d_label_q, const int64_t* d_label_t, const int64_t* d_size_q,
                   const int64_t* d_size_t, const int64_t* h_n_components) {
@@ -220,10 +215,10 @@ int kz_components_impl(kz_ctx* ctx, const int64_t* d_ind, L rows, int64_t n_q, i
     if (rc == KZ_OK) rc = tile.alloc(ctx, (size_t)n_tiles * 4);
     if (rc == KZ_OK) rc = count.alloc(ctx, 16);
     if (rc != KZ_OK) return rc;
-    const dim3 nodes(kz_cc_blocks(n_nodes)), wg(256);
+    const dim3 nodes(kz_blocks(n_nodes, 4096)), wg(256);
     hipLaunchKernelGGL(kz_cc_init_kernel, nodes, wg, 0, ctx->stream, parent.get(), n_nodes);
     if (n_entries > 0)
-        hipLaunchKernelGGL((kz_cc_hook_kernel<L>), dim3(kz_cc_blocks(n_entries)), wg, 0, ctx->stream, parent.get(), d_ind, rows, n_q, n_entries,
+        hipLaunchKernelGGL((kz_cc_hook_kernel<L>), dim3(kz_blocks(n_entries, 4096)), wg, 0, ctx->stream, parent.get(), d_ind, rows, n_q, n_entries,
                            n_index);
     hipLaunchKernelGGL(kz_cc_flatten_kernel, nodes, wg, 0, ctx->stream, (const int*)parent.get(), root.get(), n_nodes);
     hipLaunchKernelGGL(kz_cc_tile_sums_kernel, dim3(n_tiles), wg, 0, ctx->stream, (const int*)root.get(), n_nodes, tile.get());

@@ -147,22 +147,6 @@ __global__ __launch_bounds__(256) void kz_match_values_kernel(const T* __restric
     }
 }
 
-// ---- a CSR's indptr, checked before anything reads through it (shared with kz_assign.hip and kz_softmin_lists.hip) -------------
-// flag |= 1 unless indptr[0] == 0, indptr[i - 1] <= indptr[i] for every i and indptr[n_q] == nnz: together, every row lies in [0, nnz)
-__global__ __launch_bounds__(256) void kz_csr_validate_kernel(const int64_t* __restrict__ indptr, int64_t n_q, int64_t nnz, int* __restrict__ flag) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n_q; i += stride) {
-        const int64_t v = indptr[i];
-        const bool bad = (i == 0 && v != 0) || (i == n_q && v != nnz) || (i > 0 && indptr[i - 1] > v);
-        if (bad) atomicOr(flag, 1);
-    }
-}
-
-static int kz_match_blocks(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : b < KZ_MATCH_BLOCKS ? b : KZ_MATCH_BLOCKS);
-}
-
 // max_rounds: every round with a proposer advances a column pointer or fills an empty target -- entries + n_index
 template <typename T, typename L>
 static int kz_match_lists_impl(const char* who, kz_ctx* ctx, const T* d_dist, const int64_t* d_ind, int n_q, L rows, int64_t max_rounds,
@@ -180,8 +164,8 @@ static int kz_match_lists_impl(const char* who, kz_ctx* ctx, const T* d_dist, co
     if (rc == KZ_OK) rc = counts.alloc(ctx, KZ_MATCH_ROUNDS_PER_READ * sizeof(unsigned));
     if (rc != KZ_OK) return rc;
     const KzMatchState s{held_key.get(), held_row.get(), prop_key.get(), prop_row.get(), next.get(), state.get()};
-    const dim3 grid(kz_match_blocks(n_q)), block(256);
-    hipLaunchKernelGGL(kz_match_init_kernel, dim3(kz_match_blocks(n_q > n_index ? n_q : n_index)), block, 0, ctx->stream, s, n_q,
+    const dim3 grid(kz_blocks(n_q, KZ_MATCH_BLOCKS)), block(256);
+    hipLaunchKernelGGL(kz_match_init_kernel, dim3(kz_blocks(n_q > n_index ? n_q : n_index, KZ_MATCH_BLOCKS)), block, 0, ctx->stream, s, n_q,
                        (int)n_index, d_match, d_col);
     int64_t rounds = 0, queued = 0;
     for (bool busy = true; busy;) {
@@ -207,13 +191,15 @@ static int kz_match_lists_impl(const char* who, kz_ctx* ctx, const T* d_dist, co
     return KZ_OK;
 }
 
-// (shared with kz_assign.hip)
-int kz_match_require(const char* who, kz_ctx* ctx, const void* d_dist, int dist_dtype, int64_t n_q, int k) {
-    KZ_REQUIRE(ctx != nullptr, "%s: null context", who);
-    KZ_REQUIRE(dist_dtype == KZ_F32 || dist_dtype == KZ_F64, "%s: dist_dtype must be KZ_F32 or KZ_F64, got %d", who, dist_dtype);
-    KZ_REQUIRE(k >= 1 && k <= KZ_MAX_CANDIDATES, "%s: lists of 1 .. %d columns, got k = %d", who, KZ_MAX_CANDIDATES, k);
-    KZ_REQUIRE(n_q >= 0 && n_q < 0x7fffffffLL, "%s: n_q = %lld is outside [0, 2^31 - 1)", who, (long long)n_q);
-    KZ_REQUIRE(n_q == 0 || d_dist != nullptr, "%s: null list", who);
+// the launch of kz_match_values_kernel for either layout and value type
+template <typename L>
+static int kz_match_values_launch(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q, L rows, void* d_out) {
+    kz_with_values(dist_dtype, d_dist, [&](auto* dist) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(dist)>>;
+        hipLaunchKernelGGL((kz_match_values_kernel<T, L>), dim3(kz_blocks(n_q, KZ_MATCH_BLOCKS)), dim3(256), 0, ctx->stream, dist, d_col, (int)n_q,
+                           rows, (T*)d_out);
+    });
+    KZ_HIP(hipGetLastError());
     return KZ_OK;
 }
 
@@ -226,11 +212,9 @@ extern "C" int kz_match_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, c
     if (n_q == 0) return KZ_OK;
     KZ_REQUIRE(d_ind && d_match && d_col, "kz_match_lists: null argument");
     KZ_HIP(hipSetDevice(ctx->device));
-    if (dist_dtype == KZ_F32)
-        return kz_match_lists_impl("kz_match_lists", ctx, (const float*)d_dist, d_ind, (int)n_q, KzRowsFixed{k}, n_q * k + n_index, n_index, d_match,
-                                   d_col, h_rounds);
-    return kz_match_lists_impl("kz_match_lists", ctx, (const double*)d_dist, d_ind, (int)n_q, KzRowsFixed{k}, n_q * k + n_index, n_index, d_match,
-                               d_col, h_rounds);
+    return kz_with_values(dist_dtype, d_dist, [&](auto* dist) {
+        return kz_match_lists_impl("kz_match_lists", ctx, dist, d_ind, (int)n_q, KzRowsFixed{k}, n_q * k + n_index, n_index, d_match, d_col, h_rounds);
+    });
 }
 
 extern "C" int kz_match_values(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q, int k, void* d_out) {
@@ -239,42 +223,10 @@ extern "C" int kz_match_values(kz_ctx* ctx, const void* d_dist, int dist_dtype, 
     if (n_q == 0) return KZ_OK;
     KZ_REQUIRE(d_col && d_out, "kz_match_values: null argument");
     KZ_HIP(hipSetDevice(ctx->device));
-    const dim3 grid(kz_match_blocks(n_q)), block(256);
-    if (dist_dtype == KZ_F32)
-        hipLaunchKernelGGL((kz_match_values_kernel<float, KzRowsFixed>), grid, block, 0, ctx->stream, (const float*)d_dist, d_col, (int)n_q,
-                           KzRowsFixed{k}, (float*)d_out);
-    else
-        hipLaunchKernelGGL((kz_match_values_kernel<double, KzRowsFixed>), grid, block, 0, ctx->stream, (const double*)d_dist, d_col, (int)n_q,
-                           KzRowsFixed{k}, (double*)d_out);
-    KZ_HIP(hipGetLastError());
-    return KZ_OK;
+    return kz_match_values_launch(ctx, d_dist, dist_dtype, d_col, n_q, KzRowsFixed{k}, d_out);
 }
 
 // ---- the CSR layout --------------------------------------------------------------------------------------------------------------
-// the limits every CSR call shares (shared with kz_assign.hip and kz_softmin_lists.hip)
-int kz_csr_require(const char* who, kz_ctx* ctx, int64_t n_q, int64_t nnz, int64_t n_index) {
-    KZ_REQUIRE(ctx != nullptr, "%s: null context", who);
-    KZ_REQUIRE(n_q >= 0 && n_q < 0x7fffffffLL, "%s: n_q = %lld is outside [0, 2^31 - 1)", who, (long long)n_q);
-    KZ_REQUIRE(nnz >= 0 && nnz < 0x7fffffffLL, "%s: nnz = %lld entries, the limit is 2^31 - 2", who, (long long)nnz);
-    KZ_REQUIRE(n_index >= 1 && n_index < 0x7fffffffLL, "%s: n_index = %lld is outside [1, 2^31 - 1)", who, (long long)n_index);
-    return KZ_OK;
-}
-
-// Runs the check kernel and READS ITS FLAG: nothing that reads through d_indptr is queued before this returns KZ_OK.
-int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz) {
-    KZ_REQUIRE(d_indptr != nullptr, "%s: null indptr", who);
-    KzPoolBuf<int> flag;
-    const int rc = flag.alloc(ctx, 16);
-    if (rc != KZ_OK) return rc;
-    KZ_HIP(hipMemsetAsync(flag.get(), 0, 16, ctx->stream));
-    hipLaunchKernelGGL(kz_csr_validate_kernel, dim3(kz_match_blocks(n_q + 1)), dim3(256), 0, ctx->stream, d_indptr, n_q, nnz, flag.get());
-    KZ_HIP(hipGetLastError());
-    int h_flag = 0;
-    KZ_HIP(hipMemcpyAsync(&h_flag, flag.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipStreamSynchronize(ctx->stream));
-    KZ_REQUIRE(h_flag == 0, "%s: indptr must start at 0, never decrease and end at nnz = %lld", who, (long long)nnz);
-    return KZ_OK;
-}
 
 extern "C" int kz_match_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const void* d_dist, int dist_dtype, int64_t n_q,
                             int64_t nnz, int64_t n_index, int64_t* d_match, int64_t* d_col, int64_t* h_rounds) {
@@ -287,11 +239,9 @@ extern "C" int kz_match_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t*
     KZ_HIP(hipSetDevice(ctx->device));
     const int rcv = kz_csr_validate("kz_match_csr", ctx, d_indptr, n_q, nnz);
     if (rcv != KZ_OK) return rcv;
-    if (dist_dtype == KZ_F32)
-        return kz_match_lists_impl("kz_match_csr", ctx, (const float*)d_dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz + n_index, n_index, d_match,
-                                   d_col, h_rounds);
-    return kz_match_lists_impl("kz_match_csr", ctx, (const double*)d_dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz + n_index, n_index, d_match,
-                               d_col, h_rounds);
+    return kz_with_values(dist_dtype, d_dist, [&](auto* dist) {
+        return kz_match_lists_impl("kz_match_csr", ctx, dist, d_ind, (int)n_q, KzRowsCsr{d_indptr}, nnz + n_index, n_index, d_match, d_col, h_rounds);
+    });
 }
 
 extern "C" int kz_match_values_csr(kz_ctx* ctx, const int64_t* d_indptr, const void* d_dist, int dist_dtype, const int64_t* d_col, int64_t n_q,
@@ -304,13 +254,5 @@ extern "C" int kz_match_values_csr(kz_ctx* ctx, const int64_t* d_indptr, const v
     KZ_HIP(hipSetDevice(ctx->device));
     const int rcv = kz_csr_validate("kz_match_values_csr", ctx, d_indptr, n_q, nnz);
     if (rcv != KZ_OK) return rcv;
-    const dim3 grid(kz_match_blocks(n_q)), block(256);
-    if (dist_dtype == KZ_F32)
-        hipLaunchKernelGGL((kz_match_values_kernel<float, KzRowsCsr>), grid, block, 0, ctx->stream, (const float*)d_dist, d_col, (int)n_q,
-                           KzRowsCsr{d_indptr}, (float*)d_out);
-    else
-        hipLaunchKernelGGL((kz_match_values_kernel<double, KzRowsCsr>), grid, block, 0, ctx->stream, (const double*)d_dist, d_col, (int)n_q,
-                           KzRowsCsr{d_indptr}, (double*)d_out);
-    KZ_HIP(hipGetLastError());
-    return KZ_OK;
+    return kz_match_values_launch(ctx, d_dist, dist_dtype, d_col, n_q, KzRowsCsr{d_indptr}, d_out);
 }

@@ -192,11 +192,6 @@ __global__ __launch_bounds__(256) void kz_pc_fill_kernel(const int* __restrict__
     }
 }
 
-int kz_pc_blocks(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : b < 4096 ? b : 4096);
-}
-
 // ---- (b) the exact ranking value of every entry of a CSR ------------------------------------------------------------------------
 // kz_pair_values_kernel's arithmetic with the query row of an entry taken from indptr.  An entry whose id is no index row: +inf.
 // One WAVE per entry (euclidean, sqeuclidean, cosine: the canonical dot product of kz_exact_value, every element type)
@@ -279,7 +274,7 @@ __global__ __launch_bounds__(256) void kz_pairs_precomputed_kernel(const T* __re
 int kz_pairs_raw_values(kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index, const int64_t* d_indptr, const int64_t* d_ind, int64_t n_q,
                         int64_t nnz, double* d_out) {
     const int metric = index->metric;
-    const dim3 lanes(kz_pc_blocks(nnz));
+    const dim3 lanes(kz_blocks(nnz, 4096));
     if (metric == KZ_PRECOMPUTED) {
         const kz_precomputed* p = query->pre;
         if (p->dtype == KZ_F32)
@@ -350,7 +345,7 @@ extern "C" int kz_lists_combine(kz_ctx* ctx, const int64_t* d_fwd_ind, int64_t n
     if (rc == KZ_OK) rc = place.alloc(ctx, ((size_t)total + 1) * 4);
     if (rc == KZ_OK) rc = tile.alloc(ctx, (size_t)n_tiles * 4);
     if (rc != KZ_OK) return rc;
-    const dim3 grid(kz_pc_blocks(total)), wg(256);
+    const dim3 grid(kz_blocks(total, 4096)), wg(256);
     // by target row: a = keys, b = positions -> c, d   (the sort moves the keys as bit patterns: non-negative ints come back as they
     // went in, ordered as integers)
     hipLaunchKernelGGL(kz_pc_target_keys_kernel, grid, wg, 0, ctx->stream, in, a.get(), b.get());
@@ -371,7 +366,7 @@ extern "C" int kz_lists_combine(kz_ctx* ctx, const int64_t* d_fwd_ind, int64_t n
     hipLaunchKernelGGL(kz_pc_tile_sums_kernel, dim3(n_tiles), wg, 0, ctx->stream, (const int*)keep, total, tile.get());
     hipLaunchKernelGGL(kz_pc_tile_bases_kernel, dim3(1), wg, 0, ctx->stream, tile.get(), n_tiles, total, place.get());
     hipLaunchKernelGGL(kz_pc_places_kernel, dim3(n_tiles), wg, 0, ctx->stream, (const int*)keep, total, (const int*)tile.get(), place.get());
-    hipLaunchKernelGGL(kz_pc_indptr_kernel, dim3(kz_pc_blocks(n_q + 1)), wg, 0, ctx->stream, row_key, total, n_q, (const int*)place.get(), d_indptr);
+    hipLaunchKernelGGL(kz_pc_indptr_kernel, dim3(kz_blocks(n_q + 1, 4096)), wg, 0, ctx->stream, row_key, total, n_q, (const int*)place.get(), d_indptr);
     if (capacity > 0)
         hipLaunchKernelGGL(kz_pc_fill_kernel, grid, wg, 0, ctx->stream, row_key, (const int*)tgt, (const int*)keep, (const int*)place.get(), total,
                            (const int64_t*)d_indptr, capacity, d_ind);

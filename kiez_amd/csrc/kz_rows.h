@@ -1,6 +1,7 @@
-// THE ROW LAYOUT of a pair list: where row i starts in dist / ind and how many entries it has.  Every kernel of kz_match.hip and
-// kz_assign.hip that walks a row is instantiated once per layout -- one rule, one body: KzRowsFixed the [n_q, k] neighbour lists,
-// KzRowsCsr a CSR's indptr.  A CSR's indptr is checked by kz_csr_validate BEFORE any kernel that reads through it is queued.
+// THE ROW LAYOUT of a pair list: where row i starts in dist / ind and how many entries it has.  Every kernel of kz_match.hip,
+// kz_assign.hip and kz_components.hip that walks a row is instantiated once per layout -- one rule, one body: KzRowsFixed the
+// [n_q, k] neighbour lists, KzRowsCsr a CSR's indptr.  A CSR's indptr is checked by kz_csr_validate BEFORE any kernel that reads
+// through it is queued.  This header and kz_rows.hip are the one place of the native code that knows the two layouts apart.
 #pragma once
 #include "kz_common.h"
 
@@ -34,6 +35,16 @@ __device__ __forceinline__ int64_t kz_csr_row_of(const int64_t* __restrict__ ind
     return lo;
 }
 
-// kz_match.hip: the limits every CSR call shares; the check kernel over indptr with its flag read back (synchronises the stream)
+// THE HOST SIDE of the layout (kz_rows.hip): the limits every CSR call shares and the check kernel over indptr with its flag read
+// back (synchronises the stream); the limits of the fixed-width calls -- kz_match_require those that take float32 or float64 values
+// (kz_match.hip, kz_assign.hip), kz_sl_require those that take float64 ones and an entry count (kz_softmin_lists.hip)
 int kz_csr_require(const char* who, kz_ctx* ctx, int64_t n_q, int64_t nnz, int64_t n_index);
 int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz);
+int kz_match_require(const char* who, kz_ctx* ctx, const void* d_dist, int dist_dtype, int64_t n_q, int k);
+int kz_sl_require(const char* who, kz_ctx* ctx, int64_t n_q, int k, int64_t n_index);
+
+// THE dispatch on a pair list's value type: f(the typed pointer) for a dist_dtype a *_require has checked (KZ_F32 or KZ_F64)
+template <typename F>
+static inline auto kz_with_values(int dist_dtype, const void* d_dist, F&& f) {
+    return dist_dtype == KZ_F32 ? f((const float*)d_dist) : f((const double*)d_dist);
+}

@@ -26,6 +26,7 @@
 // that nobody lists has no potential.
 #include "kz_common.h"
 #include "kz_reduce.h"   // KzSoftminPart, kz_softmin_rescaled
+#include "kz_rows.h"     // kz_csr_row_of (also the column of a place of the view), kz_sl_require, kz_csr_require, kz_csr_validate
 
 constexpr int KZ_SL_CHUNK = 512;   // entries of a column per first-level wave: 8 loads per lane, all in flight
 static_assert(KZ_SL_CHUNK == KZ_SOFTMIN_LIST_CHUNK, "include/kiez_amd.h documents the chunk size");
@@ -206,19 +207,6 @@ __device__ __forceinline__ KzSoftminPart kz_sl_chunk(const I* __restrict__ col_r
     return KzSoftminPart{m, s};
 }
 
-// the column that holds place `pos` of the column-major view (0 <= pos < nnz): the largest j with colptr[j] <= pos
-__device__ __forceinline__ int64_t kz_sl_column_of(const int64_t* __restrict__ colptr, int64_t n_index, int64_t pos) {
-    int64_t lo = 0, hi = n_index;   // (colptr[lo] <= pos < colptr[hi])
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (colptr[mid] <= pos)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 // the gather behind the sort of a CSR's entries: the source row of flat position q is the row of indptr that holds it (empty rows
 // hold nothing: the search steps over them)
 __global__ __launch_bounds__(256) void kz_sl_gather_csr_kernel(const int* __restrict__ key, const int* __restrict__ pos, int total,
@@ -228,7 +216,7 @@ __global__ __launch_bounds__(256) void kz_sl_gather_csr_kernel(const int* __rest
     for (int64_t p = blockIdx.x * blockDim.x + threadIdx.x; p < total; p += stride) {
         if (key[p] >= n_index) continue;
         const int q = pos[p];
-        col_row[p] = (int)kz_sl_column_of(indptr, n_q, q);
+        col_row[p] = (int)kz_csr_row_of(indptr, n_q, q);
         col_val[p] = dist[q];
     }
 }
@@ -256,7 +244,7 @@ __global__ __launch_bounds__(256) void kz_sl_cols_chunk_kernel(const int64_t* __
     if (nnz > capacity) return;   // (a colptr that does not belong to this view: nothing is read)
     const int64_t lo = b * KZ_SL_CHUNK, hi = lo + KZ_SL_CHUNK;
     if (lo >= nnz || (slot == 1 && hi > nnz)) return;   // (a long column that starts in the block ends behind it)
-    const int64_t j = kz_sl_column_of(colptr, n_index, slot == 0 ? lo : hi - 1);
+    const int64_t j = kz_csr_row_of(colptr, n_index, slot == 0 ? lo : hi - 1);   // (the column that holds the place: colptr is the view's indptr)
     const int64_t start = colptr[j], end = colptr[j + 1];
     if (end - start <= KZ_SL_CHUNK) return;   // (a short column: level 2 reduces it by itself)
     int64_t p0;
@@ -352,19 +340,6 @@ __global__ void kz_sl_decide_kernel(const unsigned long long* __restrict__ slot,
     if (__longlong_as_double((long long)slot[it]) <= tol) *stop = it;
 }
 
-int kz_sl_blocks(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : b < 4096 ? b : 4096);
-}
-
-// the checks the four entry points share
-int kz_sl_require(const char* who, kz_ctx* ctx, int64_t n_q, int k, int64_t n_index) {
-    KZ_REQUIRE(ctx != nullptr, "%s: null context", who);
-    KZ_REQUIRE(k >= 1 && k <= KZ_MAX_CANDIDATES, "%s: lists of 1 .. %d columns, got k = %d", who, KZ_MAX_CANDIDATES, k);
-    KZ_REQUIRE(n_index >= 1 && n_index < 0x7fffffffLL, "%s: n_index = %lld is outside [1, 2^31 - 1)", who, (long long)n_index);
-    KZ_REQUIRE(n_q >= 0 && n_q * (int64_t)k < 0x7fffffffLL, "%s: n_q k = %lld entries, the limit is 2^31 - 2", who, (long long)(n_q * (int64_t)k));
-    return KZ_OK;
-}
 int kz_sl_require_eps(const char* who, double eps, double shift) {
     KZ_REQUIRE(eps > 0.0 && eps < INFINITY, "%s: the temperature eps must be finite and > 0, got %g", who, eps);
     KZ_REQUIRE(shift > -INFINITY && shift < INFINITY, "%s: shift must be finite, got %g", who, shift);
@@ -414,21 +389,107 @@ int kz_sl_transpose(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int
     if (rc == KZ_OK) rc = key_out.alloc(ctx, (size_t)total * 4);
     if (rc == KZ_OK) rc = val_out.alloc(ctx, (size_t)total * 4);
     if (rc != KZ_OK) return rc;
-    hipLaunchKernelGGL(kz_sl_keys_kernel, dim3(kz_sl_blocks(total)), dim3(256), 0, ctx->stream, d_ind, total, n_index, key_in.get(), val_in.get());
+    hipLaunchKernelGGL(kz_sl_keys_kernel, dim3(kz_blocks(total, 4096)), dim3(256), 0, ctx->stream, d_ind, total, n_index, key_in.get(), val_in.get());
     KZ_HIP(hipGetLastError());
     // (the sort moves the keys as bit patterns: non-negative ints come back as they went in, ordered as integers)
     rc = kz_sort_pairs_f32_i32(ctx, reinterpret_cast<const float*>(key_in.get()), reinterpret_cast<float*>(key_out.get()), val_in.get(),
                                val_out.get(), total, 0);
     if (rc != KZ_OK) return rc;
     if (d_indptr)
-        hipLaunchKernelGGL(kz_sl_gather_csr_kernel, dim3(kz_sl_blocks(total)), dim3(256), 0, ctx->stream, (const int*)key_out.get(),
+        hipLaunchKernelGGL(kz_sl_gather_csr_kernel, dim3(kz_blocks(total, 4096)), dim3(256), 0, ctx->stream, (const int*)key_out.get(),
                            (const int*)val_out.get(), total, d_indptr, n_q, n_index, d_dist, d_col_row, d_col_val);
     else
-        hipLaunchKernelGGL(kz_sl_gather_kernel, dim3(kz_sl_blocks(total)), dim3(256), 0, ctx->stream, (const int*)key_out.get(), (const int*)val_out.get(),
+        hipLaunchKernelGGL(kz_sl_gather_kernel, dim3(kz_blocks(total, 4096)), dim3(256), 0, ctx->stream, (const int*)key_out.get(), (const int*)val_out.get(),
                            total, k, n_index, d_dist, d_col_row, d_col_val);
-    hipLaunchKernelGGL(kz_sl_colptr_kernel, dim3(kz_sl_blocks(n_index + 1)), dim3(256), 0, ctx->stream, (const int*)key_out.get(), total, n_index,
+    hipLaunchKernelGGL(kz_sl_colptr_kernel, dim3(kz_blocks(n_index + 1, 4096)), dim3(256), 0, ctx->stream, (const int*)key_out.get(), total, n_index,
                        d_colptr);
     KZ_HIP(hipGetLastError());
+    return KZ_OK;
+}
+
+// The tail kz_lists_transpose and kz_csr_transpose share.  No entry: every column is empty.  Else `transpose()` checks the arrays
+// and queues the view, and its entry count is read back where the caller asks for it.
+template <typename Transpose>
+int kz_sl_transpose_finish(kz_ctx* ctx, bool no_entry, int64_t n_index, int64_t* d_colptr, int64_t* h_nnz, Transpose&& transpose) {
+    if (no_entry) {
+        KZ_HIP(hipMemsetAsync(d_colptr, 0, (size_t)(n_index + 1) * 8, ctx->stream));
+        if (h_nnz) KZ_HIP(hipStreamSynchronize(ctx->stream));
+        return KZ_OK;
+    }
+    const int rc = transpose();
+    if (rc != KZ_OK) return rc;
+    if (h_nnz) {
+        KZ_HIP(hipMemcpyAsync(h_nnz, d_colptr + n_index, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KZ_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return KZ_OK;
+}
+
+// the option checks kz_sinkhorn_lists and kz_sinkhorn_csr share
+int kz_sl_require_loop(const char* who, double eps, int n_iter, double tol) {
+    KZ_REQUIRE(eps > 0.0 && eps < INFINITY, "%s: the temperature eps must be finite and > 0, got %g", who, eps);
+    KZ_REQUIRE(n_iter >= 1, "%s: n_iter must be >= 1, got %d", who, n_iter);
+    KZ_REQUIRE(tol == tol, "%s: tol is NaN (negative: no tolerance)", who);
+    return KZ_OK;
+}
+
+// THE LOOP of kz_sinkhorn_lists and kz_sinkhorn_csr (Sinkhorn._potentials: from f = 0 -- no offset in the first column step --, the
+// column step with the constant, the row step), the read-out and the copy of g.  The two layouts differ in three things:
+//   capacity / room   the places the column-major view may hold (n_q k, or nnz) and the entries its arrays get (a CSR's may be none);
+//   transpose         (colptr, col_row, col_val) -> queues the view;
+//   row_step          (g, part, stop, it) -> queues the row step into d_f -- kz_sl_rows_launch for the lists, the chunk tree
+//                     kz_sl_cols_launch<int64_t, true> over indptr for a CSR, which shares the parts with the column step (they follow
+//                     each other on the stream).
+template <typename Transpose, typename RowStep>
+int kz_sl_sinkhorn_run(kz_ctx* ctx, int64_t n_q, int64_t n_index, int64_t capacity, int64_t room, double eps, int n_iter, double tol,
+                       Transpose&& transpose, RowStep&& row_step, double* d_f, double* d_g, int* h_n_iter, double* h_change, int* h_measured) {
+    const bool with_tol = tol >= 0.0;
+    // (released when the function returns, behind its last synchronise: the view lives for the call, g is double-buffered)
+    KzPoolBuf<int64_t> colptr;
+    KzPoolBuf<int> col_row, stop;
+    KzPoolBuf<double> col_val, g2;
+    KzPoolBuf<KzSoftminPart> part;
+    KzPoolBuf<unsigned long long> slot;
+    int rc = colptr.alloc(ctx, (size_t)(n_index + 1) * 8);
+    if (rc == KZ_OK) rc = col_row.alloc(ctx, (size_t)room * 4);
+    if (rc == KZ_OK) rc = col_val.alloc(ctx, (size_t)room * 8);
+    if (rc == KZ_OK) rc = g2.alloc(ctx, (size_t)n_index * 2 * 8);
+    if (rc == KZ_OK) rc = part.alloc(ctx, (size_t)(kz_sl_part_count(capacity) + 1) * sizeof(KzSoftminPart));
+    if (rc == KZ_OK) rc = slot.alloc(ctx, (size_t)(n_iter + 1) * 8);
+    if (rc == KZ_OK) rc = stop.alloc(ctx, 16);
+    if (rc != KZ_OK) return rc;
+    rc = transpose(colptr.get(), col_row.get(), col_val.get());
+    if (rc != KZ_OK) return rc;
+    KZ_HIP(hipMemsetAsync(slot.get(), 0, (size_t)(n_iter + 1) * 8, ctx->stream));
+    KZ_HIP(hipMemsetAsync(stop.get(), 0, 16, ctx->stream));
+    const double shift = eps * log((double)n_q / (double)n_index);
+    double* g_buf[2] = {g2.get(), g2.get() + n_index};
+    for (int it = 1; it <= n_iter; ++it) {
+        double* g_new = g_buf[it & 1];
+        kz_sl_cols_launch<int, false>(ctx, colptr.get(), col_row.get(), col_val.get(), n_index, capacity, eps, it == 1 ? nullptr : d_f, 0, shift,
+                                      part.get(), g_new, stop.get(), it);
+        if (it >= 2) {
+            hipLaunchKernelGGL(kz_sl_change_kernel, dim3(kz_blocks(n_index, 4096)), dim3(256), 0, ctx->stream, (const double*)g_new,
+                               (const double*)g_buf[(it - 1) & 1], n_index, slot.get(), (const int*)stop.get(), it);
+            if (with_tol) hipLaunchKernelGGL(kz_sl_decide_kernel, dim3(1), dim3(1), 0, ctx->stream, (const unsigned long long*)slot.get(), tol, stop.get(), it);
+        }
+        row_step((const double*)g_new, part.get(), (const int*)stop.get(), it);
+    }
+    KZ_HIP(hipGetLastError());
+    // the one read behind the loop: where it stopped and every iteration's change; then g of that iteration
+    int h_stop[4] = {0, 0, 0, 0};
+    std::unique_ptr<unsigned long long[]> h_slot(new unsigned long long[n_iter + 1]);
+    KZ_HIP(hipMemcpyAsync(h_stop, stop.get(), 16, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(h_slot.get(), slot.get(), (size_t)(n_iter + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    const int done = h_stop[0] != 0 ? h_stop[0] : n_iter;
+    KZ_HIP(hipMemcpyAsync(d_g, g_buf[done & 1], (size_t)n_index * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    if (h_n_iter) *h_n_iter = done;
+    if (done >= 2) {
+        if (h_change) memcpy(h_change, &h_slot[done], 8);
+        if (h_measured) *h_measured = 1;
+    }
     return KZ_OK;
 }
 
@@ -441,19 +502,10 @@ extern "C" int kz_lists_transpose(kz_ctx* ctx, const double* d_dist, const int64
     KZ_REQUIRE(d_colptr != nullptr, "kz_lists_transpose: null colptr");
     if (h_nnz) *h_nnz = 0;
     KZ_HIP(hipSetDevice(ctx->device));
-    if (n_q == 0) {   // (no row: every column is empty)
-        KZ_HIP(hipMemsetAsync(d_colptr, 0, (size_t)(n_index + 1) * 8, ctx->stream));
-        if (h_nnz) KZ_HIP(hipStreamSynchronize(ctx->stream));
-        return KZ_OK;
-    }
-    KZ_REQUIRE(d_dist && d_ind && d_col_row && d_col_val, "kz_lists_transpose: null argument");
-    const int rc = kz_sl_transpose(ctx, d_dist, d_ind, n_q, k, n_index, d_colptr, d_col_row, d_col_val);
-    if (rc != KZ_OK) return rc;
-    if (h_nnz) {
-        KZ_HIP(hipMemcpyAsync(h_nnz, d_colptr + n_index, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KZ_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return KZ_OK;
+    return kz_sl_transpose_finish(ctx, n_q == 0, n_index, d_colptr, h_nnz, [&]() -> int {
+        KZ_REQUIRE(d_dist && d_ind && d_col_row && d_col_val, "kz_lists_transpose: null argument");
+        return kz_sl_transpose(ctx, d_dist, d_ind, n_q, k, n_index, d_colptr, d_col_row, d_col_val);
+    });
 }
 
 extern "C" int kz_softmin_list_rows(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index, double eps,
@@ -492,70 +544,24 @@ extern "C" int kz_sinkhorn_lists(kz_ctx* ctx, const double* d_dist, const int64_
                                  double tol, double* d_f, double* d_g, int* h_n_iter, double* h_change, int* h_measured) {
     const int rcq = kz_sl_require("kz_sinkhorn_lists", ctx, n_q, k, n_index);
     if (rcq != KZ_OK) return rcq;
-    KZ_REQUIRE(eps > 0.0 && eps < INFINITY, "kz_sinkhorn_lists: the temperature eps must be finite and > 0, got %g", eps);
-    KZ_REQUIRE(n_iter >= 1, "kz_sinkhorn_lists: n_iter must be >= 1, got %d", n_iter);
-    KZ_REQUIRE(tol == tol, "kz_sinkhorn_lists: tol is NaN (negative: no tolerance)");
+    const int rcl = kz_sl_require_loop("kz_sinkhorn_lists", eps, n_iter, tol);
+    if (rcl != KZ_OK) return rcl;
     if (h_n_iter) *h_n_iter = 0;
     if (h_change) *h_change = 0.0;
     if (h_measured) *h_measured = 0;
     if (n_q == 0) return KZ_OK;
     KZ_REQUIRE(d_dist && d_ind && d_f && d_g, "kz_sinkhorn_lists: null argument");
     KZ_HIP(hipSetDevice(ctx->device));
-    const int64_t total = n_q * k;
-    const bool with_tol = tol >= 0.0;
-    // (released when the function returns, behind its last synchronise: the view lives for the call, g is double-buffered)
-    KzPoolBuf<int64_t> colptr;
-    KzPoolBuf<int> col_row, stop;
-    KzPoolBuf<double> col_val, g2;
-    KzPoolBuf<KzSoftminPart> part;
-    KzPoolBuf<unsigned long long> slot;
-    int rc = colptr.alloc(ctx, (size_t)(n_index + 1) * 8);
-    if (rc == KZ_OK) rc = col_row.alloc(ctx, (size_t)total * 4);
-    if (rc == KZ_OK) rc = col_val.alloc(ctx, (size_t)total * 8);
-    if (rc == KZ_OK) rc = g2.alloc(ctx, (size_t)n_index * 2 * 8);
-    if (rc == KZ_OK) rc = part.alloc(ctx, (size_t)(kz_sl_part_count(total) + 1) * sizeof(KzSoftminPart));
-    if (rc == KZ_OK) rc = slot.alloc(ctx, (size_t)(n_iter + 1) * 8);
-    if (rc == KZ_OK) rc = stop.alloc(ctx, 16);
-    if (rc != KZ_OK) return rc;
-    rc = kz_sl_transpose(ctx, d_dist, d_ind, n_q, k, n_index, colptr.get(), col_row.get(), col_val.get());
-    if (rc != KZ_OK) return rc;
-    KZ_HIP(hipMemsetAsync(slot.get(), 0, (size_t)(n_iter + 1) * 8, ctx->stream));
-    KZ_HIP(hipMemsetAsync(stop.get(), 0, 16, ctx->stream));
-    // Sinkhorn._potentials: from f = 0 (no offset in the first column step), the column step with the constant, the row step
-    const double shift = eps * log((double)n_q / (double)n_index);
-    double* g_buf[2] = {g2.get(), g2.get() + n_index};
-    for (int it = 1; it <= n_iter; ++it) {
-        double* g_new = g_buf[it & 1];
-        kz_sl_cols_launch<int, false>(ctx, colptr.get(), col_row.get(), col_val.get(), n_index, total, eps, it == 1 ? nullptr : d_f, 0, shift,
-                                      part.get(), g_new, stop.get(), it);
-        if (it >= 2) {
-            hipLaunchKernelGGL(kz_sl_change_kernel, dim3(kz_sl_blocks(n_index)), dim3(256), 0, ctx->stream, (const double*)g_new,
-                               (const double*)g_buf[(it - 1) & 1], n_index, slot.get(), (const int*)stop.get(), it);
-            if (with_tol) hipLaunchKernelGGL(kz_sl_decide_kernel, dim3(1), dim3(1), 0, ctx->stream, (const unsigned long long*)slot.get(), tol, stop.get(), it);
-        }
-        kz_sl_rows_launch(ctx, d_dist, d_ind, (int)n_q, k, n_index, eps, g_new, 0.0, d_f, stop.get(), it);
-    }
-    KZ_HIP(hipGetLastError());
-    // the one read: where the loop stopped and every iteration's change; then g of that iteration
-    int h_stop[4] = {0, 0, 0, 0};
-    std::unique_ptr<unsigned long long[]> h_slot(new unsigned long long[n_iter + 1]);
-    KZ_HIP(hipMemcpyAsync(h_stop, stop.get(), 16, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(h_slot.get(), slot.get(), (size_t)(n_iter + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipStreamSynchronize(ctx->stream));
-    const int done = h_stop[0] != 0 ? h_stop[0] : n_iter;
-    KZ_HIP(hipMemcpyAsync(d_g, g_buf[done & 1], (size_t)n_index * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    KZ_HIP(hipStreamSynchronize(ctx->stream));
-    if (h_n_iter) *h_n_iter = done;
-    if (done >= 2) {
-        if (h_change) memcpy(h_change, &h_slot[done], 8);
-        if (h_measured) *h_measured = 1;
-    }
-    return KZ_OK;
+    return kz_sl_sinkhorn_run(
+        ctx, n_q, n_index, n_q * k, n_q * k, eps, n_iter, tol,
+        [&](int64_t* colptr, int* col_row, double* col_val) { return kz_sl_transpose(ctx, d_dist, d_ind, n_q, k, n_index, colptr, col_row, col_val); },
+        [&](const double* g, KzSoftminPart*, const int* stop, int it) {
+            kz_sl_rows_launch(ctx, d_dist, d_ind, (int)n_q, k, n_index, eps, g, 0.0, d_f, stop, it);
+        },
+        d_f, d_g, h_n_iter, h_change, h_measured);
 }
 
 // ---- the CSR layout (include/kiez_amd.h: "the same three steps on RAGGED (CSR) pair lists") ------------------------------------
-int kz_csr_require(const char* who, kz_ctx* ctx, int64_t n_q, int64_t nnz, int64_t n_index);                     // kz_match.hip
-int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64_t n_q, int64_t nnz);            // kz_match.hip
 
 extern "C" int kz_csr_transpose(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
                                 int64_t n_index, int64_t* d_colptr, int32_t* d_col_row, double* d_col_val, int64_t* h_nnz) {
@@ -568,19 +574,10 @@ extern "C" int kz_csr_transpose(kz_ctx* ctx, const int64_t* d_indptr, const int6
         const int rcv = kz_csr_validate("kz_csr_transpose", ctx, d_indptr, n_q, nnz);
         if (rcv != KZ_OK) return rcv;
     }
-    if (n_q == 0 || nnz == 0) {   // (no entry: every column is empty)
-        KZ_HIP(hipMemsetAsync(d_colptr, 0, (size_t)(n_index + 1) * 8, ctx->stream));
-        if (h_nnz) KZ_HIP(hipStreamSynchronize(ctx->stream));
-        return KZ_OK;
-    }
-    KZ_REQUIRE(d_dist && d_ind && d_col_row && d_col_val, "kz_csr_transpose: null argument");
-    const int rc = kz_sl_transpose(ctx, d_dist, d_ind, n_q, 0, n_index, d_colptr, d_col_row, d_col_val, d_indptr, nnz);
-    if (rc != KZ_OK) return rc;
-    if (h_nnz) {
-        KZ_HIP(hipMemcpyAsync(h_nnz, d_colptr + n_index, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KZ_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return KZ_OK;
+    return kz_sl_transpose_finish(ctx, n_q == 0 || nnz == 0, n_index, d_colptr, h_nnz, [&]() -> int {
+        KZ_REQUIRE(d_dist && d_ind && d_col_row && d_col_val, "kz_csr_transpose: null argument");
+        return kz_sl_transpose(ctx, d_dist, d_ind, n_q, 0, n_index, d_colptr, d_col_row, d_col_val, d_indptr, nnz);
+    });
 }
 
 extern "C" int kz_softmin_csr_rows(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const double* d_dist, int64_t n_q, int64_t nnz,
@@ -607,67 +604,25 @@ extern "C" int kz_sinkhorn_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64
                                int* h_measured) {
     const int rcq = kz_csr_require("kz_sinkhorn_csr", ctx, n_q, nnz, n_index);
     if (rcq != KZ_OK) return rcq;
-    KZ_REQUIRE(eps > 0.0 && eps < INFINITY, "kz_sinkhorn_csr: the temperature eps must be finite and > 0, got %g", eps);
-    KZ_REQUIRE(n_iter >= 1, "kz_sinkhorn_csr: n_iter must be >= 1, got %d", n_iter);
-    KZ_REQUIRE(tol == tol, "kz_sinkhorn_csr: tol is NaN (negative: no tolerance)");
+    const int rcl = kz_sl_require_loop("kz_sinkhorn_csr", eps, n_iter, tol);
+    if (rcl != KZ_OK) return rcl;
     if (h_n_iter) *h_n_iter = 0;
     if (h_change) *h_change = 0.0;
     if (h_measured) *h_measured = 0;
     if (n_q == 0) return KZ_OK;
     KZ_REQUIRE(d_f && d_g && (nnz == 0 || (d_dist && d_ind)), "kz_sinkhorn_csr: null argument");
     KZ_HIP(hipSetDevice(ctx->device));
-    int rc = kz_csr_validate("kz_sinkhorn_csr", ctx, d_indptr, n_q, nnz);
-    if (rc != KZ_OK) return rc;
-    const bool with_tol = tol >= 0.0;
-    // (released when the function returns, behind its last synchronise: the view lives for the call, g is double-buffered; the row
-    //  and the column step share the parts -- they follow each other on the stream)
-    KzPoolBuf<int64_t> colptr;
-    KzPoolBuf<int> col_row, stop;
-    KzPoolBuf<double> col_val, g2;
-    KzPoolBuf<KzSoftminPart> part;
-    KzPoolBuf<unsigned long long> slot;
-    rc = colptr.alloc(ctx, (size_t)(n_index + 1) * 8);
-    if (rc == KZ_OK) rc = col_row.alloc(ctx, (size_t)(nnz + 1) * 4);
-    if (rc == KZ_OK) rc = col_val.alloc(ctx, (size_t)(nnz + 1) * 8);
-    if (rc == KZ_OK) rc = g2.alloc(ctx, (size_t)n_index * 2 * 8);
-    if (rc == KZ_OK) rc = part.alloc(ctx, (size_t)(kz_sl_part_count(nnz) + 1) * sizeof(KzSoftminPart));
-    if (rc == KZ_OK) rc = slot.alloc(ctx, (size_t)(n_iter + 1) * 8);
-    if (rc == KZ_OK) rc = stop.alloc(ctx, 16);
-    if (rc != KZ_OK) return rc;
-    if (nnz > 0)
-        rc = kz_sl_transpose(ctx, d_dist, d_ind, n_q, 0, n_index, colptr.get(), col_row.get(), col_val.get(), d_indptr, nnz);
-    else
-        KZ_HIP(hipMemsetAsync(colptr.get(), 0, (size_t)(n_index + 1) * 8, ctx->stream));
-    if (rc != KZ_OK) return rc;
-    KZ_HIP(hipMemsetAsync(slot.get(), 0, (size_t)(n_iter + 1) * 8, ctx->stream));
-    KZ_HIP(hipMemsetAsync(stop.get(), 0, 16, ctx->stream));
-    const double shift = eps * log((double)n_q / (double)n_index);
-    double* g_buf[2] = {g2.get(), g2.get() + n_index};
-    for (int it = 1; it <= n_iter; ++it) {
-        double* g_new = g_buf[it & 1];
-        kz_sl_cols_launch<int, false>(ctx, colptr.get(), col_row.get(), col_val.get(), n_index, nnz, eps, it == 1 ? nullptr : d_f, 0, shift, part.get(),
-                                      g_new, stop.get(), it);
-        if (it >= 2) {
-            hipLaunchKernelGGL(kz_sl_change_kernel, dim3(kz_sl_blocks(n_index)), dim3(256), 0, ctx->stream, (const double*)g_new,
-                               (const double*)g_buf[(it - 1) & 1], n_index, slot.get(), (const int*)stop.get(), it);
-            if (with_tol) hipLaunchKernelGGL(kz_sl_decide_kernel, dim3(1), dim3(1), 0, ctx->stream, (const unsigned long long*)slot.get(), tol, stop.get(), it);
-        }
-        kz_sl_cols_launch<int64_t, true>(ctx, d_indptr, d_ind, d_dist, n_q, nnz, eps, g_new, n_index, 0.0, part.get(), d_f, stop.get(), it);
-    }
-    KZ_HIP(hipGetLastError());
-    // the one read behind the loop: where it stopped and every iteration's change; then g of that iteration
-    int h_stop[4] = {0, 0, 0, 0};
-    std::unique_ptr<unsigned long long[]> h_slot(new unsigned long long[n_iter + 1]);
-    KZ_HIP(hipMemcpyAsync(h_stop, stop.get(), 16, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(h_slot.get(), slot.get(), (size_t)(n_iter + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipStreamSynchronize(ctx->stream));
-    const int done = h_stop[0] != 0 ? h_stop[0] : n_iter;
-    KZ_HIP(hipMemcpyAsync(d_g, g_buf[done & 1], (size_t)n_index * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    KZ_HIP(hipStreamSynchronize(ctx->stream));
-    if (h_n_iter) *h_n_iter = done;
-    if (done >= 2) {
-        if (h_change) memcpy(h_change, &h_slot[done], 8);
-        if (h_measured) *h_measured = 1;
-    }
-    return KZ_OK;
+    const int rcv = kz_csr_validate("kz_sinkhorn_csr", ctx, d_indptr, n_q, nnz);
+    if (rcv != KZ_OK) return rcv;
+    return kz_sl_sinkhorn_run(
+        ctx, n_q, n_index, nnz, nnz + 1, eps, n_iter, tol,
+        [&](int64_t* colptr, int* col_row, double* col_val) -> int {
+            if (nnz > 0) return kz_sl_transpose(ctx, d_dist, d_ind, n_q, 0, n_index, colptr, col_row, col_val, d_indptr, nnz);
+            KZ_HIP(hipMemsetAsync(colptr, 0, (size_t)(n_index + 1) * 8, ctx->stream));   // (no entry: every column is empty)
+            return KZ_OK;
+        },
+        [&](const double* g, KzSoftminPart* part, const int* stop, int it) {
+            kz_sl_cols_launch<int64_t, true>(ctx, d_indptr, d_ind, d_dist, n_q, nnz, eps, g, n_index, 0.0, part, d_f, stop, it);
+        },
+        d_f, d_g, h_n_iter, h_change, h_measured);
 }

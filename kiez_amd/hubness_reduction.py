@@ -571,12 +571,8 @@ class _DualPotentials(HubnessReduction):
         """(f [n_s], g [n_t]) as float64 DeviceArrays from the two fitted device matrices; sets n_iter_ / potential_change_."""
 
     @abstractmethod
-    def _potentials_lists(self, dist, ind, n_target):
-        """The same from the forward candidate lists dist / ind [n_s, K] (DeviceArrays) and the number of target rows."""
-
-    @abstractmethod
-    def _potentials_csr(self, indptr, ind, dist, n_target):
-        """The same from a CSR of pairs over the source rows (float64 values, DeviceArrays) and the number of target rows."""
+    def _potentials_pairs(self, pairs):
+        """The same from a `PairList` over the source rows (float64 values): the forward candidate lists, or a CSR of pairs."""
 
     def fit(self, source, target=None):
         if target is None and not _is_precomputed(self.nn_algo):   # (a precomputed distance matrix IS two-sided)
@@ -592,7 +588,7 @@ class _DualPotentials(HubnessReduction):
             # the forward search of kneighbors(), taken here; handed back to the backend's one-shot cache (the shared sweep's), so
             # that the kneighbors() that follows runs no second search
             dist, ind = nn.kneighbors_device(query=None, k=nn.n_candidates)
-            self._f_dev, self._g_dev = self._potentials_lists(dist, ind, target_m.shape[0])
+            self._f_dev, self._g_dev = self._potentials_pairs(N.PairList.lists(self.ctx, dist, ind, target_m.shape[0]))
             nn._forward = (dist.shape[1], dist, ind)
         elif self.support == "union":
             # the raw lists of BOTH directions at n_candidates (one shared sweep where it applies), their union as a CSR with the plain
@@ -600,7 +596,7 @@ class _DualPotentials(HubnessReduction):
             # Every target row lists n_candidates sources, so every column has pairs.  The forward lists go back into the one-shot cache.
             k, _ = nn._pairs_args(None, "union", type(self).__name__)
             indptr, ind, dist, fwd = nn._neighbor_pairs(k, "union", True, True, cast=False)
-            self._f_dev, self._g_dev = self._potentials_csr(indptr, ind, dist, target_m.shape[0])
+            self._f_dev, self._g_dev = self._potentials_pairs(N.PairList.csr(self.ctx, indptr, ind, dist, target_m.shape[0]))
             nn._forward = (fwd[0].shape[1],) + tuple(fwd)
         else:
             self._f_dev, self._g_dev = self._potentials(source_m, target_m)
@@ -664,14 +660,9 @@ class Sinkhorn(_DualPotentials):
         return (f"{self.__class__.__name__}(temperature = {self.temperature}, n_iter = {self.n_iter}, tol = {self.tol}, "
                 f"support = {self.support})")
 
-    def _potentials_lists(self, dist, ind, n_target):
-        """The same iteration over the pairs of the lists, in one native call (kz_sinkhorn_lists: the stop is decided on the device)."""
-        f, g, self.n_iter_, self.potential_change_ = N.sinkhorn_lists(self.ctx, dist, ind, n_target, self.temperature, self.n_iter, self.tol)
-        return f, g
-
-    def _potentials_csr(self, indptr, ind, dist, n_target):
-        """The same iteration over the pairs of a CSR, in one native call (kz_sinkhorn_csr)."""
-        f, g, self.n_iter_, self.potential_change_ = N.sinkhorn_csr(self.ctx, indptr, ind, dist, n_target, self.temperature, self.n_iter, self.tol)
+    def _potentials_pairs(self, pairs):
+        """The same iteration over the pairs of the list, in one native call (`PairList.sinkhorn`: the stop is decided on the device)."""
+        f, g, self.n_iter_, self.potential_change_ = pairs.sinkhorn(self.temperature, self.n_iter, self.tol)
         return f, g
 
     def _potentials(self, source_m, target_m):
@@ -708,17 +699,11 @@ class InvertedSoftmax(_DualPotentials):
         g = N.softmin_rows(self.ctx, target_m, source_m, self.temperature)
         return self.ctx.to_device(np.zeros(source_m.shape[0], dtype=np.float64)), g
 
-    def _potentials_lists(self, dist, ind, n_target):
-        """One column step over the pairs of the lists, without offset or constant."""
+    def _potentials_pairs(self, pairs):
+        """One column step over the transposed view of the pairs, without offset or constant."""
         self.n_iter_, self.potential_change_ = 1, None
-        g = N.softmin_list_cols(self.ctx, N.lists_transpose(self.ctx, dist, ind, n_target), self.temperature)
-        return self.ctx.to_device(np.zeros(dist.shape[0], dtype=np.float64)), g
-
-    def _potentials_csr(self, indptr, ind, dist, n_target):
-        """One column step over the transposed view of the CSR, without offset or constant."""
-        self.n_iter_, self.potential_change_ = 1, None
-        g = N.softmin_list_cols(self.ctx, N.csr_transpose(self.ctx, indptr, ind, dist, n_target), self.temperature)
-        return self.ctx.to_device(np.zeros(indptr.shape[0] - 1, dtype=np.float64)), g
+        g = N.softmin_list_cols(self.ctx, pairs.transpose(), self.temperature)
+        return self.ctx.to_device(np.zeros(pairs.n_q, dtype=np.float64)), g
 
 
 _DESIRED_P_VALUE = 2

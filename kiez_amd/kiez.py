@@ -153,20 +153,34 @@ class Kiez:
         return (self.hubness if reduced else self.algorithm).radius_counts(radius)
 
     def _lists_for_matching(self, k, whole_index):
-        """The device lists a one-to-one step runs on -> (dist, ind, n_target)."""
+        """The device lists a one-to-one step runs on -> a `PairList`."""
         nn = self.algorithm
         cached = getattr(nn, "_forward", None)
         dist, ind = self.kneighbors_whole_index_device(k) if whole_index else self.kneighbors_device(k)
         if cached is not None and nn._forward is None:
             nn._forward = cached   # (the shared sweep's forward lists stay cached for the kneighbors() that follows, as after gold_ranks)
-        return dist, ind, nn.target_.shape[0]
+        return N.PairList.lists(dist.ctx, dist, ind, nn.target_.shape[0])
+
+    # the three consumers of a `PairList`, whichever producer made it and whichever layout it has
+    @staticmethod
+    def _match_of(pairs):
+        match, col, _ = pairs.match()
+        return pairs.values(col), match
+
+    @staticmethod
+    def _assign_of(make_pairs, unmatched_cost, eps):
+        from . import matching
+        unmatched_cost, eps, _ = matching._assignment_options(unmatched_cost, eps, 1)   # (checked before the search runs)
+        return matching._assignment_of(make_pairs(), unmatched_cost, eps)
+
+    @staticmethod
+    def _components_of(pairs, return_sizes):
+        from . import matching
+        return matching._components_of(pairs, return_sizes)
 
     def match_device(self, k: Optional[int] = None, whole_index: bool = False):
         """Like `match` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
-        dist, ind, n_target = self._lists_for_matching(k, whole_index)
-        ctx = dist.ctx
-        match, col, _ = N.match_lists(ctx, dist, ind, n_target)
-        return N.match_values(ctx, dist, col), match
+        return self._match_of(self._lists_for_matching(k, whole_index))
 
     def match(self, k: Optional[int] = None, whole_index: bool = False, return_distance: bool = True):
         """One-to-one alignment of the fitted source and target rows: the source-proposing stable matching (`matching.one_to_one`)
@@ -185,10 +199,7 @@ class Kiez:
     def assign_device(self, k: Optional[int] = None, whole_index: bool = False, unmatched_cost: Optional[float] = None,
                       eps: Optional[float] = None):
         """Like `assign` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
-        from . import matching
-        unmatched_cost, eps, _ = matching._assignment_options(unmatched_cost, eps, 1)
-        dist, ind, n_target = self._lists_for_matching(k, whole_index)
-        return matching.assignment(dist, ind, n_target, unmatched_cost=unmatched_cost, eps=eps)
+        return self._assign_of(lambda: self._lists_for_matching(k, whole_index), unmatched_cost, eps)
 
     def assign(self, k: Optional[int] = None, whole_index: bool = False, return_distance: bool = True,
                unmatched_cost: Optional[float] = None, eps: Optional[float] = None):
@@ -203,16 +214,14 @@ class Kiez:
 
     # ---- threshold, then one-to-one: the same two steps on the pairs within a radius (a CSR, rows of any length) ----------------
     def _pairs_within_radius(self, radius, reduced):
-        """The device CSR of `radius_neighbors(radius, reduced=reduced)`, rows by (value, target row) -> (indptr, ind, dist, n_target)."""
+        """The device CSR of `radius_neighbors(radius, reduced=reduced)`, rows by (value, target row) -> a `PairList`."""
         algo = self.hubness if reduced else self.algorithm
         indptr, ind, dist = algo.radius_neighbors_device(radius, sort_results=True)
-        return indptr, ind, dist, self.algorithm.target_.shape[0]
+        return N.PairList.csr(dist.ctx, indptr, ind, dist, self.algorithm.target_.shape[0])
 
     def match_radius_device(self, radius, reduced: bool = False):
         """Like `match_radius` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
-        indptr, ind, dist, n_target = self._pairs_within_radius(radius, reduced)
-        match, col, _ = N.match_csr(dist.ctx, indptr, ind, dist, n_target)
-        return N.match_values_csr(dist.ctx, indptr, dist, col), match
+        return self._match_of(self._pairs_within_radius(radius, reduced))
 
     def match_radius(self, radius, reduced: bool = False, return_distance: bool = True):
         """Threshold, then one-to-one: `match` over the pairs of `radius_neighbors(radius, reduced=reduced)` instead of neighbour lists
@@ -225,10 +234,7 @@ class Kiez:
 
     def assign_radius_device(self, radius, reduced: bool = False, unmatched_cost: Optional[float] = None, eps: Optional[float] = None):
         """Like `assign_radius` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
-        from . import matching
-        unmatched_cost, eps, _ = matching._assignment_options(unmatched_cost, eps, 1)
-        indptr, ind, dist, n_target = self._pairs_within_radius(radius, reduced)
-        return matching.assignment_csr(indptr, ind, dist, n_target, unmatched_cost=unmatched_cost, eps=eps)
+        return self._assign_of(lambda: self._pairs_within_radius(radius, reduced), unmatched_cost, eps)
 
     def assign_radius(self, radius, reduced: bool = False, return_distance: bool = True, unmatched_cost: Optional[float] = None,
                       eps: Optional[float] = None):
@@ -268,15 +274,13 @@ class Kiez:
         return algo.neighbor_pairs(k, mode, return_distance, sort_results)
 
     def _pairs_of_both_directions(self, k, mode, reduced):
-        """The device CSR of `neighbor_pairs(k, mode, reduced)`, rows by (value, target row) -> (indptr, ind, dist, n_target)."""
+        """The device CSR of `neighbor_pairs(k, mode, reduced)`, rows by (value, target row) -> a `PairList`."""
         indptr, ind, dist = self.neighbor_pairs_device(k, mode, reduced)
-        return indptr, ind, dist, self.algorithm.target_.shape[0]
+        return N.PairList.csr(dist.ctx, indptr, ind, dist, self.algorithm.target_.shape[0])
 
     def match_pairs_device(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False):
         """Like `match_pairs` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
-        indptr, ind, dist, n_target = self._pairs_of_both_directions(k, mode, reduced)
-        match, col, _ = N.match_csr(dist.ctx, indptr, ind, dist, n_target)
-        return N.match_values_csr(dist.ctx, indptr, dist, col), match
+        return self._match_of(self._pairs_of_both_directions(k, mode, reduced))
 
     def match_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_distance: bool = True):
         """Both directions, then one-to-one: `match` over the pairs of `neighbor_pairs(k, mode, reduced)` instead of the forward lists
@@ -289,10 +293,7 @@ class Kiez:
     def assign_pairs_device(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, unmatched_cost: Optional[float] = None,
                             eps: Optional[float] = None):
         """Like `assign_pairs` but the (match_dist, match_ind) result stays in HBM as DeviceArrays."""
-        from . import matching
-        unmatched_cost, eps, _ = matching._assignment_options(unmatched_cost, eps, 1)
-        indptr, ind, dist, n_target = self._pairs_of_both_directions(k, mode, reduced)
-        return matching.assignment_csr(indptr, ind, dist, n_target, unmatched_cost=unmatched_cost, eps=eps)
+        return self._assign_of(lambda: self._pairs_of_both_directions(k, mode, reduced), unmatched_cost, eps)
 
     def assign_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_distance: bool = True,
                      unmatched_cost: Optional[float] = None, eps: Optional[float] = None):
@@ -303,15 +304,9 @@ class Kiez:
         return (match_dist.numpy(), match_ind.numpy()) if return_distance else match_ind.numpy()
 
     # ---- threshold or both directions, then the transitive closure: entity clusters of the same two CSRs ------------------------
-    @staticmethod
-    def _components_of(indptr, ind, n_target, return_sizes):
-        res = N.components_csr(ind.ctx, indptr, ind, n_target, sizes=bool(return_sizes))
-        return tuple(res[:4] if return_sizes else res[:2])
-
     def components_radius_device(self, radius, reduced: bool = False, return_sizes: bool = False):
         """Like `components_radius` but the label (and size) arrays stay in HBM as DeviceArrays."""
-        indptr, ind, _, n_target = self._pairs_within_radius(radius, reduced)
-        return self._components_of(indptr, ind, n_target, return_sizes)
+        return self._components_of(self._pairs_within_radius(radius, reduced), return_sizes)
 
     def components_radius(self, radius, reduced: bool = False, return_sizes: bool = False):
         """Threshold, then the transitive closure: the entity clusters of the pairs of `radius_neighbors(radius, reduced=reduced)` --
@@ -328,8 +323,7 @@ class Kiez:
 
     def components_pairs_device(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_sizes: bool = False):
         """Like `components_pairs` but the label (and size) arrays stay in HBM as DeviceArrays."""
-        indptr, ind, _, n_target = self._pairs_of_both_directions(k, mode, reduced)
-        return self._components_of(indptr, ind, n_target, return_sizes)
+        return self._components_of(self._pairs_of_both_directions(k, mode, reduced), return_sizes)
 
     def components_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False, return_sizes: bool = False):
         """Both directions, then the transitive closure: the entity clusters of the pairs of `neighbor_pairs(k, mode, reduced)` --

@@ -15,21 +15,8 @@ import numpy as np
 from . import _native as N
 
 
-def _checked_lists(dist, ind, n_target):
-    """The argument checks of `one_to_one`, all before the device is touched -> (dist, ind) as the native call takes them."""
-    if isinstance(n_target, (bool, np.bool_)) or not isinstance(n_target, (int, np.integer)) or n_target < 1:
-        raise ValueError(f"n_target must be a positive integer, got {n_target!r}")
-    if not isinstance(dist, N.DeviceArray):
-        dist = np.asarray(dist)
-    if not isinstance(ind, N.DeviceArray):
-        ind = np.asarray(ind)
-    if len(dist.shape) != 2 or len(ind.shape) != 2 or tuple(dist.shape) != tuple(ind.shape):
-        raise ValueError(f"dist and ind must be 2-D neighbour lists of one shape, got {tuple(dist.shape)} and {tuple(ind.shape)}")
-    return _checked_dtypes(dist, ind)
-
-
 def _checked_dtypes(dist, ind):
-    """The dtype half of `_checked_lists`, shared with the CSR form."""
+    """The dtype half of `_checked`, shared by the two layouts."""
     if not np.issubdtype(ind.dtype, np.integer):
         raise ValueError(f"ind must hold integer row ids, got {ind.dtype}")
     if not np.issubdtype(dist.dtype, np.floating):
@@ -49,18 +36,20 @@ def _checked_dtypes(dist, ind):
     return dist, ind
 
 
-def _checked_csr(dist, ind, indptr, n_target):
-    """The argument checks of the CSR functions, all before the device is touched -> (dist, ind, indptr) as the native
-    calls take them.  A host `indptr` is checked in full here; one on the device is checked there, by the native call.
-    `dist` None (`components_csr`: a CSR without values): the same checks of `ind` and `indptr`, and None comes back for it."""
+def _checked(dist, ind, indptr, n_target):
+    """The argument checks of every function here that takes a pair list, all before the device is touched -> (dist, ind, indptr) as
+    `_uploaded` takes them.  `indptr` None: fixed-width lists [n_q, k]; else a CSR, whose host `indptr` is checked in full here (one
+    on the device is checked there, by the native call).  `dist` None (`components`: a list without values): the same checks of the
+    rest, and None comes back for it."""
     if isinstance(n_target, (bool, np.bool_)) or not isinstance(n_target, (int, np.integer)) or n_target < 1:
         raise ValueError(f"n_target must be a positive integer, got {n_target!r}")
-    if dist is not None and not isinstance(dist, N.DeviceArray):
-        dist = np.asarray(dist)
-    if not isinstance(ind, N.DeviceArray):
-        ind = np.asarray(ind)
-    if not isinstance(indptr, N.DeviceArray):
-        indptr = np.asarray(indptr)
+    dist, ind, indptr = (a if a is None or isinstance(a, N.DeviceArray) else np.asarray(a) for a in (dist, ind, indptr))
+    if indptr is None:
+        if dist is None:
+            return None, _checked_ids("ind", ind), None
+        if len(dist.shape) != 2 or len(ind.shape) != 2 or tuple(dist.shape) != tuple(ind.shape):
+            raise ValueError(f"dist and ind must be 2-D neighbour lists of one shape, got {tuple(dist.shape)} and {tuple(ind.shape)}")
+        return _checked_dtypes(dist, ind) + (None,)
     if dist is None:
         if len(ind.shape) != 1:
             raise ValueError(f"ind must be a 1-D array (the entries of a CSR), got shape {tuple(ind.shape)}")
@@ -86,13 +75,17 @@ def _checked_csr(dist, ind, indptr, n_target):
     return dist, ind, indptr
 
 
-def _csr_context(ctx, dist, ind, indptr):
-    if ctx is not None:
-        return ctx
-    for a in (dist, ind, indptr):
-        if isinstance(a, N.DeviceArray):
-            return a.ctx
-    return N.Context.get()
+def _uploaded(checked, n_target, ctx):
+    """(dist | None, ind, indptr | None) as `_checked` returns them -> (the `PairList` on the device -- the one object that knows the
+    layout from here on --, whether the results stay on the device: they do if `dist`, or `ind` where there is no `dist`, is a
+    `DeviceArray`)."""
+    on_device = isinstance(checked[1] if checked[0] is None else checked[0], N.DeviceArray)
+    if ctx is None:
+        ctx = next((a.ctx for a in checked if isinstance(a, N.DeviceArray)), None) or N.Context.get()
+    dist, ind, indptr = (None if a is None else ctx.as_device(a) for a in checked)
+    if indptr is None:
+        return N.PairList.lists(ctx, dist, ind, int(n_target)), on_device
+    return N.PairList.csr(ctx, indptr, ind, dist, int(n_target)), on_device
 
 
 def from_sparse(S):
@@ -128,15 +121,15 @@ def one_to_one(dist, ind, n_target: int, *, return_distance: bool = True, ctx: O
     row of source row i or -1, `match_dist[i]` the value of that pair in `dist`'s dtype or NaN.  numpy lists give numpy arrays; if
     `dist` is a `DeviceArray`, so are the results.  `evaluate.hits(match_ind[:, None], gold, k=[1])` is the matching's precision.
     Ragged lists (a CSR): `one_to_one_csr`."""
-    dist, ind = _checked_lists(dist, ind, n_target)
-    on_device = isinstance(dist, N.DeviceArray)
-    if ctx is None:
-        ctx = dist.ctx if on_device else ind.ctx if isinstance(ind, N.DeviceArray) else N.Context.get()
-    dist_dev, ind_dev = ctx.as_device(dist), ctx.as_device(ind)
-    match, col, _ = N.match_lists(ctx, dist_dev, ind_dev, int(n_target))
+    return _one_to_one(dist, ind, None, n_target, return_distance, ctx)
+
+
+def _one_to_one(dist, ind, indptr, n_target, return_distance, ctx):
+    pairs, on_device = _uploaded(_checked(dist, ind, indptr, n_target), n_target, ctx)
+    match, col, _ = pairs.match()
     if not return_distance:
         return match if on_device else match.numpy()
-    match_dist = N.match_values(ctx, dist_dev, col)
+    match_dist = pairs.values(col)
     return (match_dist, match) if on_device else (match_dist.numpy(), match.numpy())
 
 
@@ -180,13 +173,31 @@ def _assignment_defaults(value_range, n_q, unmatched_cost, eps):
     return unmatched_cost, eps
 
 
-def _assign(ctx, dist_dev, ind_dev, n_target, unmatched_cost, eps, max_rounds, want_prices):
-    match, col, prices, rounds, converged = N.assign_lists(ctx, dist_dev, ind_dev, n_target, unmatched_cost, eps, max_rounds,
-                                                           want_prices=want_prices)
+def _assignment_of(pairs, unmatched_cost, eps, max_rounds=1_000_000, return_distance=True, return_prices=False, defaults=True):
+    """The auction over a `PairList` -> the tuple ([match_dist,] match_ind[, prices]) of `DeviceArray`s.  `defaults`: unmatched_cost
+    and eps are completed and checked here, from the value range taken on the device (False: the caller did, from lists on the host)."""
+    if defaults:
+        unmatched_cost, eps = _assignment_defaults(pairs.value_range(), pairs.n_q, unmatched_cost, eps)
+    match, col, prices, rounds, converged = pairs.assign(unmatched_cost, eps, max_rounds, want_prices=return_prices)
     if not converged:
         raise RuntimeError(f"assignment: rows are still free after {rounds} rounds (max_rounds) with eps = {eps!r} and "
                            f"unmatched_cost = {unmatched_cost!r}; a larger eps or a smaller unmatched_cost shortens the run")
-    return match, col, prices
+    out = (pairs.values(col), match) if return_distance else (match,)
+    return out + (prices,) if return_prices else out
+
+
+def _assignment(dist, ind, indptr, n_target, unmatched_cost, eps, max_rounds, return_distance, return_prices, ctx):
+    dist, ind, indptr = _checked(dist, ind, indptr, n_target)
+    unmatched_cost, eps, max_rounds = _assignment_options(unmatched_cost, eps, max_rounds)
+    host = not isinstance(dist, N.DeviceArray) and not isinstance(ind, N.DeviceArray)
+    if host:   # (host lists: the eps check comes before the device is touched)
+        n_q = dist.shape[0] if indptr is None else indptr.shape[0] - 1
+        unmatched_cost, eps = _assignment_defaults(_host_value_range(dist, ind, n_target), n_q, unmatched_cost, eps)
+    pairs, on_device = _uploaded((dist, ind, indptr), n_target, ctx)
+    out = _assignment_of(pairs, unmatched_cost, eps, max_rounds, return_distance, return_prices, defaults=not host)
+    if not on_device:
+        out = tuple(x.numpy() for x in out)
+    return out if len(out) > 1 else out[0]
 
 
 def assignment(dist, ind, n_target: int, *, unmatched_cost: Optional[float] = None, eps: Optional[float] = None,
@@ -205,23 +216,7 @@ def assignment(dist, ind, n_target: int, *, unmatched_cost: Optional[float] = No
     Returns `(match_dist, match_ind)`, or `match_ind` alone with `return_distance=False`, as `one_to_one` does, with the float64
     target prices [n_target] appended when `return_prices=True`.  More than `max_rounds` rounds raise RuntimeError.
     Ragged lists (a CSR): `assignment_csr`."""
-    dist, ind = _checked_lists(dist, ind, n_target)
-    unmatched_cost, eps, max_rounds = _assignment_options(unmatched_cost, eps, max_rounds)
-    on_device = isinstance(dist, N.DeviceArray)
-    if not on_device and not isinstance(ind, N.DeviceArray):   # (host lists: the eps check comes before the device is touched)
-        unmatched_cost, eps = _assignment_defaults(_host_value_range(dist, ind, n_target), dist.shape[0], unmatched_cost, eps)
-    if ctx is None:
-        ctx = dist.ctx if on_device else ind.ctx if isinstance(ind, N.DeviceArray) else N.Context.get()
-    dist_dev, ind_dev = ctx.as_device(dist), ctx.as_device(ind)
-    if on_device or isinstance(ind, N.DeviceArray):
-        unmatched_cost, eps = _assignment_defaults(N.assign_range(ctx, dist_dev, ind_dev, int(n_target)), dist.shape[0], unmatched_cost, eps)
-    match, col, prices = _assign(ctx, dist_dev, ind_dev, int(n_target), unmatched_cost, eps, max_rounds, return_prices)
-    out = (N.match_values(ctx, dist_dev, col), match) if return_distance else (match,)
-    if return_prices:
-        out = out + (prices,)
-    if not on_device:
-        out = tuple(x.numpy() for x in out)
-    return out if len(out) > 1 else out[0]
+    return _assignment(dist, ind, None, n_target, unmatched_cost, eps, max_rounds, return_distance, return_prices, ctx)
 
 
 def _sinkhorn_options(temperature, n_iter, tol):
@@ -253,16 +248,18 @@ def sinkhorn_lists(dist, ind, n_target: int, *, temperature: float = 0.05, n_ite
     `return_info=True` a third item, the dict {"n_iter": iterations done, "potential_change": the last measured change of g or None}.
     `(dist - f[:, None]) - g[ind]` is the reduced distance of the listed pairs (`Sinkhorn.transform`).  Ragged lists (a CSR):
     `sinkhorn_csr`."""
-    dist, ind = _checked_lists(dist, ind, n_target)
+    return _sinkhorn(dist, ind, None, n_target, temperature, n_iter, tol, ctx, return_info)
+
+
+def _sinkhorn(dist, ind, indptr, n_target, temperature, n_iter, tol, ctx, return_info):
+    dist, ind, indptr = _checked(dist, ind, indptr, n_target)
     _sinkhorn_options(temperature, n_iter, tol)
-    on_device = isinstance(dist, N.DeviceArray)
-    if on_device and dist.dtype != np.float64:
-        raise ValueError(f"a device dist must be float64 here, got {dist.dtype}")
-    if not on_device:
+    if not isinstance(dist, N.DeviceArray):
         dist = dist.astype(np.float64, copy=False)
-    if ctx is None:
-        ctx = dist.ctx if on_device else ind.ctx if isinstance(ind, N.DeviceArray) else N.Context.get()
-    f, g, done, change = N.sinkhorn_lists(ctx, ctx.as_device(dist), ctx.as_device(ind), int(n_target), float(temperature), int(n_iter), tol)
+    elif dist.dtype != np.float64:
+        raise ValueError(f"a device dist must be float64 here, got {dist.dtype}")
+    pairs, on_device = _uploaded((dist, ind, indptr), n_target, ctx)
+    f, g, done, change = pairs.sinkhorn(float(temperature), int(n_iter), tol)
     out = (f, g) if on_device else (f.numpy(), g.numpy())
     return out + ({"n_iter": done, "potential_change": change},) if return_info else out
 
@@ -276,15 +273,7 @@ def one_to_one_csr(indptr, ind, dist, n_target: int, *, return_distance: bool = 
     with `one_to_one`'s rule for where the result lives.  An `indptr` that does not start at 0, decreases or does not end at the
     number of entries raises ValueError -- a host one before the device is touched, a device one on the device before anything
     reads through it.  Returns what `one_to_one` returns."""
-    dist, ind, indptr = _checked_csr(dist, ind, indptr, n_target)
-    on_device = isinstance(dist, N.DeviceArray)
-    ctx = _csr_context(ctx, dist, ind, indptr)
-    dist_dev, ind_dev, ptr_dev = ctx.as_device(dist), ctx.as_device(ind), ctx.as_device(indptr)
-    match, col, _ = N.match_csr(ctx, ptr_dev, ind_dev, dist_dev, int(n_target))
-    if not return_distance:
-        return match if on_device else match.numpy()
-    match_dist = N.match_values_csr(ctx, ptr_dev, dist_dev, col)
-    return (match_dist, match) if on_device else (match_dist.numpy(), match.numpy())
+    return _one_to_one(dist, ind, indptr, n_target, return_distance, ctx)
 
 
 def assignment_csr(indptr, ind, dist, n_target: int, *, unmatched_cost: Optional[float] = None, eps: Optional[float] = None,
@@ -292,52 +281,20 @@ def assignment_csr(indptr, ind, dist, n_target: int, *, unmatched_cost: Optional
                    ctx: Optional[N.Context] = None):
     """`assignment` over ragged lists (kz_assign_csr): the CSR as `one_to_one_csr` takes it, every option, default (from the range
     of the listed values), error and result as `assignment`."""
-    dist, ind, indptr = _checked_csr(dist, ind, indptr, n_target)
-    unmatched_cost, eps, max_rounds = _assignment_options(unmatched_cost, eps, max_rounds)
-    on_device = isinstance(dist, N.DeviceArray)
-    n_q = indptr.shape[0] - 1
-    host = not on_device and not isinstance(ind, N.DeviceArray)
-    if host:   # (the eps check comes before the device is touched)
-        unmatched_cost, eps = _assignment_defaults(_host_value_range(dist, ind, n_target), n_q, unmatched_cost, eps)
-    ctx = _csr_context(ctx, dist, ind, indptr)
-    dist_dev, ind_dev, ptr_dev = ctx.as_device(dist), ctx.as_device(ind), ctx.as_device(indptr)
-    if not host:
-        unmatched_cost, eps = _assignment_defaults(N.assign_range_csr(ctx, ptr_dev, ind_dev, dist_dev, int(n_target)), n_q, unmatched_cost, eps)
-    match, col, prices, rounds, converged = N.assign_csr(ctx, ptr_dev, ind_dev, dist_dev, int(n_target), unmatched_cost, eps, max_rounds,
-                                                         want_prices=return_prices)
-    if not converged:
-        raise RuntimeError(f"assignment: rows are still free after {rounds} rounds (max_rounds) with eps = {eps!r} and "
-                           f"unmatched_cost = {unmatched_cost!r}; a larger eps or a smaller unmatched_cost shortens the run")
-    out = (N.match_values_csr(ctx, ptr_dev, dist_dev, col), match) if return_distance else (match,)
-    if return_prices:
-        out = out + (prices,)
-    if not on_device:
-        out = tuple(x.numpy() for x in out)
-    return out if len(out) > 1 else out[0]
+    return _assignment(dist, ind, indptr, n_target, unmatched_cost, eps, max_rounds, return_distance, return_prices, ctx)
 
 
 def sinkhorn_csr(indptr, ind, dist, n_target: int, *, temperature: float = 0.05, n_iter: int = 10, tol: Optional[float] = None,
                  ctx: Optional[N.Context] = None, return_info: bool = False):
     """`sinkhorn_lists` over ragged lists (kz_sinkhorn_csr): the CSR as `one_to_one_csr` takes it (values taken as float64), every
     option and result as `sinkhorn_lists`; f has one entry per row of `indptr`."""
-    dist, ind, indptr = _checked_csr(dist, ind, indptr, n_target)
-    _sinkhorn_options(temperature, n_iter, tol)
-    on_device = isinstance(dist, N.DeviceArray)
-    if on_device and dist.dtype != np.float64:
-        raise ValueError(f"a device dist must be float64 here, got {dist.dtype}")
-    if not on_device:
-        dist = dist.astype(np.float64, copy=False)
-    ctx = _csr_context(ctx, dist, ind, indptr)
-    f, g, done, change = N.sinkhorn_csr(ctx, ctx.as_device(indptr), ctx.as_device(ind), ctx.as_device(dist), int(n_target), float(temperature),
-                                        int(n_iter), tol)
-    out = (f, g) if on_device else (f.numpy(), g.numpy())
-    return out + ({"n_iter": done, "potential_change": change},) if return_info else out
+    return _sinkhorn(dist, ind, indptr, n_target, temperature, n_iter, tol, ctx, return_info)
 
 
 # ---- the producer of such a CSR from two list arrays: forward, reverse, union, mutual --------------------------------------------
 def _checked_ids(what, ind, ndim=2):
     """One list array of `combine_lists` or `components` -> a 2-D int64 array (numpy or `DeviceArray`), before the device is touched.
-    (`ndim` 1: the entries of a CSR, whose shape `_checked_csr` has checked.)"""
+    (`ndim` 1: the entries of a CSR, whose shape `_checked` has checked.)"""
     if not isinstance(ind, N.DeviceArray):
         ind = np.asarray(ind)
     if ndim == 2 and (len(ind.shape) != 2 or ind.shape[1] < 1):
@@ -399,9 +356,20 @@ def _checked_node_count(n_source, n_target):
         raise ValueError(f"n_source + n_target = {n_source + n_target} rows, the limit is {N.COMPONENTS_MAX_NODES} (2**31 - 2)")
 
 
-def _components_out(res, return_sizes, on_device):
-    out = res[:4] if return_sizes else res[:2]
-    return tuple(out) if on_device else tuple(x.numpy() for x in out)
+def _components_of(pairs, return_sizes):
+    """The labels (and sizes) of a `PairList`'s components -> a tuple of `DeviceArray`s."""
+    res = pairs.components(bool(return_sizes))
+    return tuple(res[:4] if return_sizes else res[:2])
+
+
+def _components(ind, indptr, n_target, return_sizes, ctx):
+    _, ind, indptr = _checked(None, ind, indptr, n_target)
+    _checked_node_count(ind.shape[0] if indptr is None else indptr.shape[0] - 1, int(n_target))
+    if indptr is None and ind.shape[0] * ind.shape[1] > 2 ** 31 - 2:
+        raise ValueError(f"ind has {ind.shape[0] * ind.shape[1]} entries, the limit is 2**31 - 2")
+    pairs, on_device = _uploaded((None, ind, indptr), n_target, ctx)
+    out = _components_of(pairs, return_sizes)
+    return out if on_device else tuple(x.numpy() for x in out)
 
 
 def components_csr(indptr, ind, n_target: int, *, return_sizes: bool = False, ctx: Optional[N.Context] = None):
@@ -422,26 +390,11 @@ def components_csr(indptr, ind, n_target: int, *, return_sizes: bool = False, ct
     `DeviceArray` so are the results.  `evaluate.cluster_metrics` scores the pairs the clustering implies.  Argument errors are raised
     before the device is touched; an `indptr` on the device that does not start at 0, decreases or does not end at the number of
     entries raises ValueError there, before anything reads through it.  Fixed-width lists: `components`."""
-    _, ind, indptr = _checked_csr(None, ind, indptr, n_target)
-    _checked_node_count(indptr.shape[0] - 1, int(n_target))
-    on_device = isinstance(ind, N.DeviceArray)
-    ctx = _csr_context(ctx, ind, indptr, None)
-    res = N.components_csr(ctx, ctx.as_device(indptr), ctx.as_device(ind), int(n_target), sizes=bool(return_sizes))
-    return _components_out(res, return_sizes, on_device)
+    return _components(ind, indptr, n_target, return_sizes, ctx)
 
 
 def components(ind, n_target: int, *, return_sizes: bool = False, ctx: Optional[N.Context] = None):
     """`components_csr` over fixed-width lists (kz_components_lists): `ind` [n_source, k] as `kneighbors` returns it, any k >= 1; an
     entry outside [0, n_target) -- a -1, the INT_MAX padding of `kneighbors_whole_index` -- is no pair.  Every result and error as
     `components_csr`."""
-    if isinstance(n_target, (bool, np.bool_)) or not isinstance(n_target, (int, np.integer)) or n_target < 1:
-        raise ValueError(f"n_target must be a positive integer, got {n_target!r}")
-    ind = _checked_ids("ind", ind)
-    _checked_node_count(ind.shape[0], int(n_target))
-    if ind.shape[0] * ind.shape[1] > 2 ** 31 - 2:
-        raise ValueError(f"ind has {ind.shape[0] * ind.shape[1]} entries, the limit is 2**31 - 2")
-    on_device = isinstance(ind, N.DeviceArray)
-    if ctx is None:
-        ctx = ind.ctx if on_device else N.Context.get()
-    res = N.components_lists(ctx, ctx.as_device(ind), int(n_target), sizes=bool(return_sizes))
-    return _components_out(res, return_sizes, on_device)
+    return _components(ind, None, n_target, return_sizes, ctx)

@@ -227,6 +227,91 @@ def test_sinkhorn_csr_is_the_composition_of_its_steps(ctx, name):
     np.testing.assert_array_equal(_bits(g.numpy()), _bits(cg))
 
 
+# ---- the ONE loop behind kz_sinkhorn_lists and kz_sinkhorn_csr (kz_sl_sinkhorn_run), on both layouts ----------------------------------
+def _loop_lists(shape):
+    """(dist, ind [n_q, k], n_index), seeded.  "small": 5 x 7, k = 3.  "long column": 600 x 3, k = 2 and every row lists target 0 -- a
+    column of more than SOFTMIN_LIST_CHUNK = 512 entries: two chunks and the fold of their parts."""
+    rng = np.random.default_rng(5)
+    if shape == "small":
+        return rng.random((5, 3)), np.stack([rng.permutation(7)[:3] for _ in range(5)]).astype(np.int64), 7
+    return rng.random((600, 2)), np.stack([np.zeros(600, dtype=np.int64), rng.integers(1, 3, 600)], axis=1), 3
+
+
+def _composed_lists(ctx, d_dev, i_dev, n_index, eps, n_iter, tol=None):
+    """`_composed` for fixed-width lists (tests/test_gpu_sinkhorn_lists.py's helper)."""
+    from kiez_amd import _native as N
+    view = N.lists_transpose(ctx, d_dev, i_dev, n_index)
+    shift = eps * math.log(d_dev.shape[0] / n_index)
+    f = g = change = None
+    for it in range(1, n_iter + 1):
+        g_new = N.softmin_list_cols(ctx, view, eps, off=f, shift=shift)
+        if g is not None:
+            change = N.max_abs_diff(ctx, g_new, g)
+        g = g_new
+        f = N.softmin_list_rows(ctx, d_dev, i_dev, n_index, eps, off=g)
+        if tol is not None and change is not None and change <= tol:
+            break
+    return f.numpy(), g.numpy(), it, change
+
+
+@pytest.mark.parametrize("layout", ["lists", "csr", "csr with an empty row"])
+@pytest.mark.parametrize("shape,n_iter,stop_at", [("small", 1, None), ("small", 30, 4), ("small", 30, 5), ("long column", 3, None)],
+                         ids=["one iteration", "tol met at an even iteration", "tol met at an odd iteration", "a column of two chunks"])
+def test_the_loop_on_both_layouts(ctx, layout, shape, n_iter, stop_at):
+    """One iteration (nothing measured), a tolerance met at an even and at an odd iteration >= 3 (either half of the double-buffered g
+    is the one copied out) and a column of more than one chunk, on the fixed-width lists, on the same pairs as a CSR and on that CSR
+    with its middle row emptied.  Bit for bit the composition of the step calls; the numpy restatement (tests/sinkhorn_lists_restate.py
+    on the padded arrays) stops at the same iteration and agrees within 2 L brackets, as everywhere in this file -- its exp and log are
+    numpy's, so its bits are not the device's."""
+    from kiez_amd import _native as N
+    eps = 0.2
+    p_dist, p_ind, n_index = _loop_lists(shape)
+    if layout == "lists":
+        dev = _dev(ctx, p_dist, p_ind)
+        run, composed = N.sinkhorn_lists, _composed_lists
+    else:
+        lens = np.full(p_ind.shape[0], p_ind.shape[1])
+        if layout == "csr with an empty row":
+            lens[p_ind.shape[0] // 2] = 0
+        keep = np.repeat(lens > 0, p_ind.shape[1])
+        indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        dev = _dev(ctx, indptr, p_ind.ravel()[keep], p_dist.ravel()[keep])
+        p_dist, p_ind = CR.pad(indptr, p_ind.ravel()[keep], p_dist.ravel()[keep])
+        run, composed = N.sinkhorn_csr, _composed
+    tol = None
+    if stop_at is not None:   # a tolerance between the restated changes of iterations stop_at - 1 and stop_at, far from both
+        changes = [LR.sinkhorn_potentials(p_dist, p_ind, n_index, eps, L)[3] for L in range(2, stop_at + 1)]
+        tol = math.sqrt(changes[-1] * min(changes[:-1]))
+        assert changes[-1] * 1.02 < tol < min(changes[:-1]) / 1.02, changes
+    wf, wg, w_done, _ = LR.sinkhorn_potentials(p_dist, p_ind, n_index, eps, n_iter, tol)
+    f, g, done, change = run(ctx, *dev, n_index, eps, n_iter, tol)
+    cf, cg, c_done, c_change = composed(ctx, *dev, n_index, eps, n_iter, tol)
+    assert done == c_done == w_done == (stop_at or n_iter) and change == c_change and (change is None) == (done == 1)
+    np.testing.assert_array_equal(_bits(f.numpy()), _bits(cf))
+    np.testing.assert_array_equal(_bits(g.numpy()), _bits(cg))
+    _assert_in_bracket(f.numpy(), wf, eps, f"f after {done} iterations", factor=2 * done)
+    _assert_in_bracket(g.numpy(), wg, eps, f"g after {done} iterations", factor=2 * done)
+    if layout == "csr with an empty row":
+        assert np.isnan(f.numpy()[p_ind.shape[0] // 2]) and np.isnan(f.numpy()).sum() == 1
+
+
+def test_the_loop_without_an_entry_and_without_a_row(ctx):
+    from kiez_amd import _native as N
+    none_i, none_d = np.zeros(0, dtype=np.int64), np.zeros(0)
+    # a CSR with nnz = 0 (colptr is a memset, the view has no place): no row and no column has a pair
+    dev = _dev(ctx, np.zeros(5, dtype=np.int64), none_i, none_d)
+    for tol, want_done in ((None, 3), (0.0, 2)):                                   # (the change of all-NaN vectors is 0.0: met at once)
+        f, g, done, change = N.sinkhorn_csr(ctx, *dev, 3, 0.05, 3, tol)
+        cf, cg, c_done, c_change = _composed(ctx, *dev, 3, 0.05, 3, tol)
+        assert (done, change) == (c_done, c_change) == (want_done, 0.0)
+        assert f.shape == (4,) and g.shape == (3,) and np.isnan(f.numpy()).all() and np.isnan(g.numpy()).all()
+        assert np.isnan(cf).all() and np.isnan(cg).all()
+    # n_q = 0: nothing runs, nothing is measured
+    for got in (N.sinkhorn_csr(ctx, *_dev(ctx, np.zeros(1, dtype=np.int64), none_i, none_d), 3, 0.05, 3),
+                N.sinkhorn_lists(ctx, *_dev(ctx, np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64)), 3, 0.05, 3)):
+        assert (got[0].shape, got[1].shape, got[2], got[3]) == ((0,), (3,), 0, None)
+
+
 def test_a_decreasing_device_indptr_is_a_value_error(ctx):
     """[0, 5, 3, 8]: inside bounds everywhere -- an unchecked walk over it would read nothing out of bounds either."""
     from kiez_amd import _native as N
