@@ -11,6 +11,7 @@ importable and KIEZ_AMD_WITH_TORCH=1 is set (bench.py and kiez_amd.distributed d
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import sys
 import threading
@@ -239,6 +240,11 @@ def _check(rc: int, what: str = ""):
         raise _ERR_TYPES.get(rc, RuntimeError)(msg or f"{what} failed with status {rc}")
 
 
+def _call(owner, name: str, *args):
+    """The library call `name(owner.handle, *args)` of a Context (or anything with its `lib` and `handle`), checked."""
+    _check(getattr(owner.lib, name)(owner.handle, *args), name)
+
+
 class Context:
     """One GPU (kz_ctx).  Contexts are cached per (device, stream)."""
 
@@ -273,19 +279,19 @@ class Context:
         return ctx
 
     def set_option(self, name: str, value: float):
-        _check(self.lib.kz_ctx_set_option(self.handle, name.encode(), float(value)), "kz_ctx_set_option")
+        _call(self, "kz_ctx_set_option", name.encode(), float(value))
 
     def sync(self):
-        _check(self.lib.kz_ctx_sync(self.handle), "kz_ctx_sync")
+        _call(self, "kz_ctx_sync")
 
     def trim(self):
         """Release the context's cached device buffers (kz_ctx_trim)."""
-        _check(self.lib.kz_ctx_trim(self.handle), "kz_ctx_trim")
+        _call(self, "kz_ctx_trim")
 
     def mem_info(self) -> Tuple[int, int]:
         """(bytes a device allocation can still get -- free HBM plus the released buffers the context keeps --, bytes of the device)."""
         free, total = C.c_size_t(), C.c_size_t()
-        _check(self.lib.kz_ctx_mem_info(self.handle, C.byref(free), C.byref(total)), "kz_ctx_mem_info")
+        _call(self, "kz_ctx_mem_info", C.byref(free), C.byref(total))
         return int(free.value), int(total.value)
 
     # ---- device arrays -------------------------------------------------------------------------------
@@ -296,7 +302,7 @@ class Context:
         arr = np.ascontiguousarray(arr)
         out = DeviceArray(self, arr.shape, arr.dtype)
         if arr.nbytes:
-            _check(self.lib.kz_memcpy_h2d(self.handle, out.ptr, arr.ctypes.data_as(_P), arr.nbytes), "kz_memcpy_h2d")
+            _call(self, "kz_memcpy_h2d", out.ptr, arr.ctypes.data_as(_P), arr.nbytes)
         return out
 
     def as_device(self, arr, dtype=None) -> "DeviceArray":
@@ -322,7 +328,7 @@ class DeviceArray:
         self._owner = owner
         if ptr is None:
             p = _P()
-            _check(ctx.lib.kz_malloc(ctx.handle, max(self.nbytes, 16), C.byref(p)), "kz_malloc")
+            _call(ctx, "kz_malloc", max(self.nbytes, 16), C.byref(p))
             self.ptr = p
             self._owned = True
         else:
@@ -346,7 +352,7 @@ class DeviceArray:
     def numpy(self) -> np.ndarray:
         out = np.empty(self.shape, dtype=self.dtype)
         if self.nbytes:
-            _check(self.ctx.lib.kz_memcpy_d2h(self.ctx.handle, out.ctypes.data_as(_P), self.ptr, self.nbytes), "kz_memcpy_d2h")
+            _call(self.ctx, "kz_memcpy_d2h", out.ctypes.data_as(_P), self.ptr, self.nbytes)
         return out
 
     def view_rows(self, begin: int, count: int) -> "DeviceArray":
@@ -357,12 +363,12 @@ class DeviceArray:
 
     def copy_from(self, other: "DeviceArray"):
         assert other.nbytes == self.nbytes
-        _check(self.ctx.lib.kz_memcpy_d2d(self.ctx.handle, self.ptr, other.ptr, self.nbytes), "kz_memcpy_d2d")
+        _call(self.ctx, "kz_memcpy_d2d", self.ptr, other.ptr, self.nbytes)
 
     def fill_from_host(self, arr: np.ndarray):
         arr = np.ascontiguousarray(arr, dtype=self.dtype)
         assert arr.nbytes == self.nbytes
-        _check(self.ctx.lib.kz_memcpy_h2d(self.ctx.handle, self.ptr, arr.ctypes.data_as(_P), arr.nbytes), "kz_memcpy_h2d")
+        _call(self.ctx, "kz_memcpy_h2d", self.ptr, arr.ctypes.data_as(_P), arr.nbytes)
 
 
 class DeviceMatrix:
@@ -400,9 +406,7 @@ class DeviceMatrix:
             self.shape = arr.shape
             self.dtype = arr.dtype
             self.elem = elem
-            _check(ctx.lib.kz_matrix_create(ctx.handle, arr.ctypes.data_as(_P), 0, arr.shape[0], arr.shape[1],
-                                            ELEM_CODES[elem], METRIC_IDS[metric], C.byref(h)),
-                   "kz_matrix_create")
+            _call(ctx, "kz_matrix_create", arr.ctypes.data_as(_P), 0, arr.shape[0], arr.shape[1], ELEM_CODES[elem], METRIC_IDS[metric], C.byref(h))
         else:
             self.shape = tuple(shape)
             self.dtype = np.dtype(np.uint16 if elem == "bfloat16" else (dtype if dtype is not None else elem))
@@ -414,9 +418,8 @@ class DeviceMatrix:
             if rows_only and not borrow:
                 raise ValueError("rows_only needs a borrowed device buffer")
             # (rows_only: kz_matrix_create rows_on_device = 3 -- a row source for kz_dsl_fit, nothing computed, not searchable)
-            _check(ctx.lib.kz_matrix_create(ctx.handle, _P(device_ptr), (3 if rows_only else 2) if borrow else 1, self.shape[0], self.shape[1],
-                                            ELEM_CODES[self.elem], METRIC_IDS[metric], C.byref(h)),
-                   "kz_matrix_create")
+            _call(ctx, "kz_matrix_create", _P(device_ptr), (3 if rows_only else 2) if borrow else 1, self.shape[0], self.shape[1],
+                  ELEM_CODES[self.elem], METRIC_IDS[metric], C.byref(h))
         self.handle = h
         if mink_p is not None:
             _check(ctx.lib.kz_matrix_set_minkowski_p(h, mink_p), "kz_matrix_set_minkowski_p")
@@ -450,8 +453,8 @@ class DeviceMatrix:
             if len(shape) != 2 or dtype not in (np.float32, np.float64):
                 raise ValueError("a precomputed device matrix must be a 2D float32/float64 array")
             ptr, where = _P(device_ptr), 2 if borrow else 1
-        _check(ctx.lib.kz_matrix_create_precomputed(ctx.handle, ptr, where, shape[0], shape[1], KZ_F32 if dtype == np.float32 else KZ_F64,
-                                                    C.byref(rows_h), C.byref(cols_h)), "kz_matrix_create_precomputed")
+        _call(ctx, "kz_matrix_create_precomputed", ptr, where, shape[0], shape[1], KZ_F32 if dtype == np.float32 else KZ_F64, C.byref(rows_h),
+              C.byref(cols_h))
         views = []
         for handle, view, shp in ((rows_h, "rows", (shape[0], shape[1])), (cols_h, "columns", (shape[1], shape[0]))):
             m = cls.__new__(cls)
@@ -471,30 +474,54 @@ class DeviceMatrix:
             self.handle = None
 
 
+# ---- the two buffer kinds ---------------------------------------------------------------------------------------------------------
+# This module is the only one that calls the library.  The wrappers `distributed.HipEngine` shares with the single-GPU classes take
+# device buffers as DeviceArrays or contiguous torch CUDA tensors (`_ptr`; no dtype check: callers pass reinterpreted views) and allocate
+# outputs through `alloc`: (shape, numpy dtype) -> buffer, None: `ctx.empty`.  What a call computes: its declaration in include/kiez_amd.h.
+def _ptr(buf, what: str = "an output"):
+    """The device address of `buf` as a c_void_p: a DeviceArray's `.ptr`, None for None, a tensor's `data_ptr()` -- of a contiguous
+    CUDA tensor only: anything else raises TypeError naming the argument `what` (a host pointer must never reach a kernel)."""
+    if hasattr(buf, "data_ptr"):
+        if not (buf.is_cuda and buf.is_contiguous()):
+            raise TypeError(f"{what} must be a DeviceArray or a contiguous CUDA tensor")
+        return _P(buf.data_ptr())
+    return None if buf is None else buf.ptr
+
+
 def knn(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, exclude_self: bool = False,
-        q_begin: int = 0, q_count: Optional[int] = None) -> Tuple[DeviceArray, DeviceArray, dict]:
+        q_begin: int = 0, q_count: Optional[int] = None, alloc=None) -> Tuple[DeviceArray, DeviceArray, dict]:
     """kz_knn -> (dist float64 [q, k], ind int64 [q, k], stats) on the device."""
+    alloc = alloc or ctx.empty
     if q_count is None:
         q_count = query.shape[0] - q_begin
-    dist = ctx.empty((q_count, k), np.float64)
-    ind = ctx.empty((q_count, k), np.int64)
-    st = KnnStats()
-    _check(ctx.lib.kz_knn(ctx.handle, query.handle, q_begin, q_count, index.handle, int(k), int(bool(exclude_self)),
-                          dist.ptr, ind.ptr, C.byref(st)), "kz_knn")
+    dist, ind, st = alloc((q_count, k), np.float64), alloc((q_count, k), np.int64), KnnStats()
+    _call(ctx, "kz_knn", query.handle, q_begin, q_count, index.handle, int(k), int(bool(exclude_self)), _ptr(dist), _ptr(ind), C.byref(st))
     return dist, ind, st.as_dict()
 
 
-def knn_dual(ctx: Context, a: DeviceMatrix, b: DeviceMatrix, k: int):
+def knn_dual(ctx: Context, a: DeviceMatrix, b: DeviceMatrix, k: int, alloc=None):
     """kz_knn_dual: both directions between two matrices from one sweep of the distance matrix.
     Returns ((dist, ind, stats) of a -> b [a.n, k], (dist, ind, stats) of b -> a [b.n, k])."""
-    d_ab = ctx.empty((a.shape[0], k), np.float64)
-    i_ab = ctx.empty((a.shape[0], k), np.int64)
-    d_ba = ctx.empty((b.shape[0], k), np.float64)
-    i_ba = ctx.empty((b.shape[0], k), np.int64)
+    alloc = alloc or ctx.empty
+    d_ab, i_ab = alloc((a.shape[0], k), np.float64), alloc((a.shape[0], k), np.int64)
+    d_ba, i_ba = alloc((b.shape[0], k), np.float64), alloc((b.shape[0], k), np.int64)
     s_ab, s_ba = KnnStats(), KnnStats()
-    _check(ctx.lib.kz_knn_dual(ctx.handle, a.handle, b.handle, int(k), d_ab.ptr, i_ab.ptr, d_ba.ptr, i_ba.ptr,
-                               C.byref(s_ab), C.byref(s_ba)), "kz_knn_dual")
+    _call(ctx, "kz_knn_dual", a.handle, b.handle, int(k), _ptr(d_ab), _ptr(i_ab), _ptr(d_ba), _ptr(i_ba), C.byref(s_ab), C.byref(s_ba))
     return (d_ab, i_ab, s_ab.as_dict()), (d_ba, i_ba, s_ba.as_dict())
+
+
+def pair_values(ctx: Context, query: DeviceMatrix, q_begin: int, q_count: int, index: DeviceMatrix, ind, alloc=None):
+    out = (alloc or ctx.empty)(tuple(ind.shape), np.float64)
+    _call(ctx, "kz_pair_values", query.handle, q_begin, q_count, index.handle, _ptr(ind, "ind"), ind.shape[1], _ptr(out))
+    return out
+
+
+def merge_topk(ctx: Context, key, ind, dist, segs: int, seg_len: int, k: int, alloc=None):
+    """kz_merge_topk -> (dist or key [n, k], ind [n, k]) of key [n, segs * seg_len <= MERGE_MAX_ENTRIES]; `ind` / `dist` may be None."""
+    alloc = alloc or ctx.empty
+    od, oi = alloc((key.shape[0], k), np.float64), alloc((key.shape[0], k), np.int64)
+    _call(ctx, "kz_merge_topk", _ptr(key, "key"), _ptr(ind, "ind"), _ptr(dist, "dist"), key.shape[0], segs, seg_len, k, _ptr(od), _ptr(oi))
+    return od, oi
 
 
 def gold_ranks(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev: DeviceArray, q_begin: int = 0,
@@ -506,7 +533,7 @@ def gold_ranks(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev:
     if gold_dev.dtype != np.int64 or gold_dev.shape != (q_count,):
         raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
     rank = ctx.empty((q_count,), np.int64)
-    _check(ctx.lib.kz_gold_ranks(ctx.handle, query.handle, q_begin, q_count, index.handle, gold_dev.ptr, rank.ptr), "kz_gold_ranks")
+    _call(ctx, "kz_gold_ranks", query.handle, q_begin, q_count, index.handle, gold_dev.ptr, rank.ptr)
     return rank
 
 
@@ -527,8 +554,7 @@ def gold_ranks_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, g
         raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
     state = _reduction_state(q_state, t_state, q_count, index.shape[0])
     rank = ctx.empty((q_count,), np.int64)
-    _check(ctx.lib.kz_gold_ranks_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, gold_dev.ptr, int(kind), *state,
-                                         rank.ptr), "kz_gold_ranks_reduced")
+    _call(ctx, "kz_gold_ranks_reduced", query.handle, q_begin, q_count, index.handle, gold_dev.ptr, int(kind), *state, rank.ptr)
     return rank
 
 
@@ -564,8 +590,7 @@ def knn_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, 
     shape = (q_count, k) if 1 <= k <= min(index.shape[0], KNN_REDUCED_MAX_K) else (0, 0)
     w = ctx.empty(shape, np.float64)
     ind = ctx.empty(shape, np.int64)
-    _check(ctx.lib.kz_knn_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, k, int(kind), *state, w.ptr, ind.ptr),
-           "kz_knn_reduced")
+    _call(ctx, "kz_knn_reduced", query.handle, q_begin, q_count, index.handle, k, int(kind), *state, w.ptr, ind.ptr)
     return w, ind
 
 
@@ -593,12 +618,11 @@ def _radius_call(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius:
     dist = ctx.empty((capacity,), np.float64)
     total = _I64(0)
     if kind is None:
-        _check(ctx.lib.kz_radius_neighbors(ctx.handle, query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)), capacity,
-                                           indptr.ptr, ind.ptr, dist.ptr, C.byref(total)), "kz_radius_neighbors")
+        _call(ctx, "kz_radius_neighbors", query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)), capacity, indptr.ptr,
+              ind.ptr, dist.ptr, C.byref(total))
     else:
-        _check(ctx.lib.kz_radius_neighbors_reduced(ctx.handle, query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)),
-                                                   capacity, int(kind), *state, indptr.ptr, ind.ptr, dist.ptr, C.byref(total)),
-               "kz_radius_neighbors_reduced")
+        _call(ctx, "kz_radius_neighbors_reduced", query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)), capacity, int(kind),
+              *state, indptr.ptr, ind.ptr, dist.ptr, C.byref(total))
     return indptr, ind, dist, int(total.value)
 
 
@@ -673,8 +697,8 @@ def softmin_rows(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, eps: fl
     if off is not None:
         _f64_vector("off", off, index.shape[0])
     out = ctx.empty((max(q_count, 0),), np.float64)
-    _check(ctx.lib.kz_softmin_rows(ctx.handle, query.handle, q_begin, q_count, index.handle, float(eps), off.ptr if off is not None else None,
-                                   float(shift), out.ptr), "kz_softmin_rows")
+    _call(ctx, "kz_softmin_rows", query.handle, q_begin, q_count, index.handle, float(eps), off.ptr if off is not None else None, float(shift),
+          out.ptr)
     return out
 
 
@@ -688,14 +712,14 @@ def dual_shift(ctx: Context, dist: DeviceArray, ind: DeviceArray, f: DeviceArray
     _f64_vector("f", f, n)
     _f64_vector("g", g)
     out = ctx.empty((n, K), np.float64)
-    _check(ctx.lib.kz_dual_shift(ctx.handle, dist.ptr, ind.ptr, n, K, f.ptr, g.ptr, out.ptr), "kz_dual_shift")
+    _call(ctx, "kz_dual_shift", dist.ptr, ind.ptr, n, K, f.ptr, g.ptr, out.ptr)
     return out
 
 
 def index_range(ctx: Context, ind: DeviceArray) -> Tuple[int, int]:
     """kz_minmax_i64 -> (smallest, largest) entry of a non-empty int64 device array."""
     lo, hi = _I64(0), _I64(0)
-    _check(ctx.lib.kz_minmax_i64(ctx.handle, ind.ptr, int(np.prod(ind.shape, dtype=np.int64)), C.byref(lo), C.byref(hi)), "kz_minmax_i64")
+    _call(ctx, "kz_minmax_i64", ind.ptr, int(np.prod(ind.shape, dtype=np.int64)), C.byref(lo), C.byref(hi))
     return int(lo.value), int(hi.value)
 
 
@@ -703,7 +727,7 @@ def max_abs_diff(ctx: Context, a: DeviceArray, b: DeviceArray) -> float:
     """kz_max_abs_diff -> max |a - b| of two float64 device vectors of one shape, NaN differences ignored (0.0 when none is left)."""
     _f64_vector("b", b, _f64_vector("a", a).shape[0])
     h = C.c_double(0.0)
-    _check(ctx.lib.kz_max_abs_diff(ctx.handle, a.ptr, b.ptr, a.shape[0], C.byref(h)), "kz_max_abs_diff")
+    _call(ctx, "kz_max_abs_diff", a.ptr, b.ptr, a.shape[0], C.byref(h))
     return float(h.value)
 
 
@@ -1007,8 +1031,8 @@ def softmin_list_cols(ctx: Context, view: ListsTransposed, eps: float, off: Opti
     if off is not None:
         _f64_vector("off", off, view.n_q)
     out = ctx.empty((view.n_index,), np.float64)
-    _check(ctx.lib.kz_softmin_list_cols(ctx.handle, view.colptr.ptr, view.col_row.ptr, view.col_val.ptr, view.n_index, view.nnz, float(eps),
-                                        off.ptr if off is not None else None, float(shift), out.ptr), "kz_softmin_list_cols")
+    _call(ctx, "kz_softmin_list_cols", view.colptr.ptr, view.col_row.ptr, view.col_val.ptr, view.n_index, view.nnz, float(eps),
+          off.ptr if off is not None else None, float(shift), out.ptr)
     return out
 
 
@@ -1028,9 +1052,8 @@ def _combine_call(ctx: Context, fwd_ind, rev_ind, n_q: int, k_f: int, n_index: i
     indptr = ctx.empty((n_q + 1,), np.int64)
     ind = ctx.empty((capacity,), np.int64)
     total = _I64(0)
-    _check(ctx.lib.kz_lists_combine(ctx.handle, fwd_ind.ptr if fwd_ind is not None else None, n_q, k_f,
-                                    rev_ind.ptr if rev_ind is not None else None, n_index, k_r, mode, capacity, indptr.ptr, ind.ptr,
-                                    C.byref(total)), "kz_lists_combine")
+    _call(ctx, "kz_lists_combine", fwd_ind.ptr if fwd_ind is not None else None, n_q, k_f, rev_ind.ptr if rev_ind is not None else None, n_index, k_r,
+          mode, capacity, indptr.ptr, ind.ptr, C.byref(total))
     return indptr, ind, int(total.value)
 
 
@@ -1101,8 +1124,7 @@ def pairs_values(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, indptr:
         kind_c = int(kind)
         state = (None, None, None, None) if q_state is None or t_state is None else _reduction_state(q_state, t_state, n_q, index.shape[0])
     out = ctx.empty((nnz,), np.float64)
-    _check(ctx.lib.kz_pairs_values(ctx.handle, query.handle, index.handle, indptr.ptr, ind.ptr, n_q, nnz, kind_c, *state, out.ptr),
-           "kz_pairs_values")
+    _call(ctx, "kz_pairs_values", query.handle, index.handle, indptr.ptr, ind.ptr, n_q, nnz, kind_c, *state, out.ptr)
     return out
 
 
@@ -1110,7 +1132,7 @@ def csr_sort_rows(ctx: Context, indptr: DeviceArray, ind: DeviceArray, dist: Dev
     """kz_csr_sort_rows: every row of the float64 CSR ascending by (value, index row) in `knn_reduced`'s order, NaN last -- ind and
     dist permuted in place (`radius_neighbors`' row sort, a row of any length)."""
     pairs = PairList.csr(ctx, indptr, ind, dist, n_index).require_f64()
-    _check(ctx.lib.kz_csr_sort_rows(ctx.handle, indptr.ptr, pairs.n_q, pairs.n_entries, pairs.n_target, ind.ptr, dist.ptr), "kz_csr_sort_rows")
+    _call(ctx, "kz_csr_sort_rows", indptr.ptr, pairs.n_q, pairs.n_entries, pairs.n_target, ind.ptr, dist.ptr)
 
 
 def rank_stats(ctx: Context, rank: DeviceArray, ks):
@@ -1119,7 +1141,7 @@ def rank_stats(ctx: Context, rank: DeviceArray, ks):
     h_ks = (_I64 * max(n_k, 1))(*[int(k) for k in ks])
     h_hits = (_I64 * max(n_k, 1))()
     h_out = (C.c_double * 3)()
-    _check(ctx.lib.kz_rank_stats(ctx.handle, rank.ptr, rank.shape[0], h_ks, n_k, h_hits, h_out), "kz_rank_stats")
+    _call(ctx, "kz_rank_stats", rank.ptr, rank.shape[0], h_ks, n_k, h_hits, h_out)
     return [int(h_hits[j]) for j in range(n_k)], int(h_out[0]), float(h_out[1]), float(h_out[2])
 
 
@@ -1128,38 +1150,143 @@ def split_self(ctx: Context, dist: DeviceArray, ind: DeviceArray, row0: int = 0)
     n, k1 = dist.shape
     outs = [ctx.empty((n, k1 - 1), np.float64), ctx.empty((n, k1 - 1), np.int64), ctx.empty((n, k1 - 1), np.float64),
             ctx.empty((n, k1 - 1), np.int64)]
-    _check(ctx.lib.kz_split_self(ctx.handle, dist.ptr, ind.ptr, n, int(k1), int(row0), outs[0].ptr, outs[1].ptr, outs[2].ptr,
-                                 outs[3].ptr), "kz_split_self")
+    _call(ctx, "kz_split_self", dist.ptr, ind.ptr, n, int(k1), int(row0), outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr)
     return (outs[0], outs[1]), (outs[2], outs[3])
 
 
-def row_stats(ctx: Context, dist: DeviceArray, mean=False, std=False, last=False):
-    n, K = dist.shape
-    m = ctx.empty((n,), np.float64) if mean else None
-    s = ctx.empty((n,), np.float64) if std else None
-    l_ = ctx.empty((n,), np.float64) if last else None
-    _check(ctx.lib.kz_row_stats(ctx.handle, dist.ptr, n, K, m.ptr if m else None, s.ptr if s else None,
-                                l_.ptr if l_ else None), "kz_row_stats")
+def row_stats(ctx: Context, dist, mean=False, std=False, last=False, alloc=None):
+    alloc = alloc or ctx.empty
+    m, s, l_ = (alloc((dist.shape[0],), np.float64) if want else None for want in (mean, std, last))
+    _call(ctx, "kz_row_stats", _ptr(dist, "dist"), *dist.shape, _ptr(m), _ptr(s), _ptr(l_))
     return m, s, l_
 
 
-def row_nanstats(ctx: Context, dist: DeviceArray):
+def row_nanstats(ctx: Context, dist, alloc=None):
     """kz_row_nanstats -> (np.nanmean, np.nanstd) of every row, each [n]."""
-    n, K = dist.shape
-    m, s = ctx.empty((n,), np.float64), ctx.empty((n,), np.float64)
-    _check(ctx.lib.kz_row_nanstats(ctx.handle, dist.ptr, n, K, m.ptr, s.ptr), "kz_row_nanstats")
+    alloc = alloc or ctx.empty
+    m, s = alloc((dist.shape[0],), np.float64), alloc((dist.shape[0],), np.float64)
+    _call(ctx, "kz_row_nanstats", _ptr(dist, "dist"), *dist.shape, _ptr(m), _ptr(s))
     return m, s
 
 
-def select_topk(ctx: Context, dist: DeviceArray, ind: DeviceArray, k: int):
-    n, K = dist.shape
-    od = ctx.empty((n, k), np.float64)
-    oi = ctx.empty((n, k), np.int64)
-    _check(ctx.lib.kz_select_topk(ctx.handle, dist.ptr, ind.ptr, n, K, int(k), od.ptr, oi.ptr), "kz_select_topk")
+def select_topk(ctx: Context, dist, ind, k: int, alloc=None):
+    alloc = alloc or ctx.empty
+    od, oi = alloc((dist.shape[0], k), np.float64), alloc((dist.shape[0], k), np.int64)
+    _call(ctx, "kz_select_topk", _ptr(dist, "dist"), _ptr(ind, "ind"), *dist.shape, int(k), _ptr(od), _ptr(oi))
     return od, oi
+
+
+# ---- the hubness reductions of candidate lists dist / ind [n, K] -> float64 [n, K], and DisSimLocal's three steps -----------------
+def csls(ctx: Context, dist, ind, r_train, alloc=None):
+    out = (alloc or ctx.empty)(tuple(dist.shape), np.float64)
+    _call(ctx, "kz_csls", _ptr(dist, "dist"), _ptr(ind, "ind"), *dist.shape, _ptr(r_train, "r_train"), _ptr(out))
+    return out
+
+
+def local_scaling(ctx: Context, dist, ind, r_t, nicdm: bool, alloc=None):
+    out = (alloc or ctx.empty)(tuple(dist.shape), np.float64)
+    _call(ctx, "kz_local_scaling", _ptr(dist, "dist"), _ptr(ind, "ind"), *dist.shape, _ptr(r_t, "r_t"), int(nicdm), _ptr(out))
+    return out
+
+
+def mp_normal(ctx: Context, dist, ind, mu_t, sd_t, alloc=None):
+    out = (alloc or ctx.empty)(tuple(dist.shape), np.float64)
+    _call(ctx, "kz_mp_normal", _ptr(dist, "dist"), _ptr(ind, "ind"), *dist.shape, _ptr(mu_t, "mu_t"), _ptr(sd_t, "sd_t"), _ptr(out))
+    return out
+
+
+def mp_empiric(ctx: Context, dist, ind, dist_t2s, ind_t2s, alloc=None):
+    out = (alloc or ctx.empty)(tuple(dist.shape), np.float64)
+    _call(ctx, "kz_mp_empiric", _ptr(dist, "dist"), _ptr(ind, "ind"), *dist.shape, _ptr(dist_t2s, "dist_t2s"), _ptr(ind_t2s, "ind_t2s"),
+          *dist_t2s.shape, _ptr(out))
+    return out
+
+
+def dsl_fit(ctx: Context, ind_t2s, sm: DeviceMatrix, tm: DeviceMatrix, t_begin: int = 0, alloc=None):
+    out = (alloc or ctx.empty)((ind_t2s.shape[0],), np.float64)
+    _call(ctx, "kz_dsl_fit", _ptr(ind_t2s, "ind_t2s"), *ind_t2s.shape, sm.handle, tm.handle, t_begin, _ptr(out))
+    return out
+
+
+def dsl_transform(ctx: Context, ind, qm: DeviceMatrix, q_begin: int, tm: DeviceMatrix, t2c, gmin, alloc=None):
+    """kz_dsl_transform -> the values before `dsl_finalize`; `gmin`: the caller's one-element float64 buffer, initialised to +inf."""
+    out = (alloc or ctx.empty)(tuple(ind.shape), np.float64)
+    _call(ctx, "kz_dsl_transform", _ptr(ind, "ind"), *ind.shape, qm.handle, q_begin, tm.handle, _ptr(t2c, "t2c"), _ptr(out), _ptr(gmin, "gmin"))
+    return out
+
+
+def dsl_finalize(ctx: Context, out, min_value: float, squared: bool):
+    _call(ctx, "kz_dsl_finalize", _ptr(out), math.prod(out.shape), float(min_value), int(squared))
+    return out
+
+
+# ---- k-occurrence and hits@k over a neighbour matrix ind int64 [n, cols] (analysis.py, evaluate.py) -------------------------------
+def minmax_i64_2d(ctx: Context, ind, k: int) -> Tuple[int, int]:
+    lo, hi = _I64(0), _I64(0)
+    _call(ctx, "kz_minmax_i64_2d", _ptr(ind, "ind"), *ind.shape, int(k), C.byref(lo), C.byref(hi))
+    return int(lo.value), int(hi.value)
+
+
+def k_occurrence(ctx: Context, ind, k: int, n_bins: int, alloc=None):
+    kocc = (alloc or ctx.empty)((n_bins,), np.int64)
+    _call(ctx, "kz_k_occurrence", _ptr(ind, "ind"), *ind.shape, int(k), n_bins, _ptr(kocc))
+    return kocc
+
+
+def kocc_stats(ctx: Context, kocc, thr: float, want_gini: bool) -> Tuple[float, ...]:
+    st = (C.c_double * 10)()
+    _call(ctx, "kz_kocc_stats", _ptr(kocc, "kocc"), kocc.shape[0], float(thr), int(want_gini), st)
+    return tuple(float(x) for x in st)
+
+
+def kocc_select(ctx: Context, kocc, mode: int, thr: float, alloc=None):
+    """kz_kocc_select -> (ids int64 [n_bins], count): the `count` ids with kocc == 0 (mode 0) or kocc >= thr (mode 1), ascending."""
+    out, cnt = (alloc or ctx.empty)((kocc.shape[0],), np.int64), _I64(0)
+    _call(ctx, "kz_kocc_select", _ptr(kocc, "kocc"), kocc.shape[0], mode, float(thr), _ptr(out), C.byref(cnt))
+    return out, int(cnt.value)
+
+
+def hit_positions(ctx: Context, ind, gold, alloc=None):
+    hist = (alloc or ctx.empty)((ind.shape[1] + 1,), np.int64)
+    _call(ctx, "kz_hit_positions", _ptr(ind, "ind"), _ptr(gold, "gold"), *ind.shape, _ptr(hist))
+    return hist
+
+
+# ---- the library's own collectives (RCCL on the context's stream); buffers as above, sizes, offsets[r] and lengths[r] in bytes -----
+def comm_unique_id() -> bytes:
+    buf = C.create_string_buffer(128)
+    _check(load().kz_comm_unique_id(buf), "kz_comm_unique_id")
+    return buf.raw
+
+
+def comm_create(ctx: Context, unique_id: bytes, rank: int, world: int):
+    h = _P()
+    _call(ctx, "kz_comm_create", C.create_string_buffer(bytes(unique_id), 128), rank, world, C.byref(h))
+    return h
+
+
+def comm_destroy(comm):
+    load().kz_comm_destroy(comm)   # (status dropped: this runs from close() / __del__, where nothing can act on it)
+
+
+def comm_broadcast(comm, buf, nbytes: int, root: int):
+    _check(load().kz_comm_broadcast(comm, _ptr(buf, "buf"), nbytes, int(root)), "kz_comm_broadcast")
+
+
+def comm_all_gather(comm, send, recv, nbytes: int):
+    _check(load().kz_comm_all_gather(comm, _ptr(send, "send"), _ptr(recv, "recv"), nbytes), "kz_comm_all_gather")
+
+
+def comm_all_to_all(comm, send, offsets, lengths, recv, recv_bytes: int):
+    offs, lens = (C.c_size_t * len(offsets))(*offsets), (C.c_size_t * len(lengths))(*lengths)
+    _check(load().kz_comm_all_to_all(comm, _ptr(send, "send"), offs, lens, _ptr(recv, "recv"), recv_bytes), "kz_comm_all_to_all")
+
+
+def comm_all_reduce_min(comm, buf, count: int):
+    _check(load().kz_comm_all_reduce_min_f64(comm, _ptr(buf, "buf"), count), "kz_comm_all_reduce_min_f64")
 
 
 def cast_f32(ctx: Context, arr: DeviceArray) -> DeviceArray:
     out = ctx.empty(arr.shape, np.float32)
-    _check(ctx.lib.kz_cast_f64_f32(ctx.handle, arr.ptr, out.ptr, int(np.prod(arr.shape, dtype=np.int64))), "kz_cast_f64_f32")
+    _call(ctx, "kz_cast_f64_f32", arr.ptr, out.ptr, int(np.prod(arr.shape, dtype=np.int64)))
     return out

@@ -6,7 +6,6 @@ array (`Kiez.kneighbors_device`).  Scalar post-processing of the handful of redu
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import warnings
 from typing import Optional, Union
@@ -61,20 +60,14 @@ def hubness_score(nn_ind, target_samples: int, *, k: Optional[int] = None, hub_s
     elif k > cols:
         k = cols
         warnings.warn(f"k > nn_ind.shape[1], k will be set to {k}", stacklevel=2)
-    lib = ctx.lib
-    lo, hi = C.c_int64(0), C.c_int64(0)
     # the histogram is sized by the ids of the first k columns only: the reference slices nn_ind[:, :k] before
     # np.bincount(..., minlength=n_train) (estimation.py:276-292)
-    N._check(lib.kz_minmax_i64_2d(ctx.handle, ind.ptr, n_train, cols, int(k), C.byref(lo), C.byref(hi)), "kz_minmax_i64_2d")
-    n_bins = max(n_train, int(hi.value) + 1)
-    kocc = ctx.empty((n_bins,), np.int64)
-    N._check(lib.kz_k_occurrence(ctx.handle, ind.ptr, n_train, cols, int(k), n_bins, kocc.ptr), "kz_k_occurrence")
+    n_bins = max(n_train, N.minmax_i64_2d(ctx, ind, k)[1] + 1)
+    kocc = N.k_occurrence(ctx, ind, k, n_bins)
 
     want_gini = return_value in ("gini", "all")
     thr = hub_size * k
-    st = (C.c_double * 10)()
-    N._check(lib.kz_kocc_stats(ctx.handle, kocc.ptr, n_bins, float(thr), int(want_gini), st), "kz_kocc_stats")
-    total, abs_dev, m2s, m3s, sqrt_sum, kmax, n_zero, hub_sum, n_hub, gini_num = (float(x) for x in st)
+    total, abs_dev, m2s, m3s, sqrt_sum, kmax, n_zero, hub_sum, n_hub, gini_num = N.kocc_stats(ctx, kocc, thr, want_gini)
     n = float(n_bins)
     mean = total / n
     m2, m3 = m2s / n, m3s / n
@@ -89,10 +82,8 @@ def hubness_score(nn_ind, target_samples: int, *, k: Optional[int] = None, hub_s
     groupie_ratio = kmax / n_test / k                                         # :326
 
     def _select(mode):
-        out = ctx.empty((n_bins,), np.int64)
-        cnt = C.c_int64(0)
-        N._check(lib.kz_kocc_select(ctx.handle, kocc.ptr, n_bins, mode, float(thr), out.ptr, C.byref(cnt)), "kz_kocc_select")
-        return out.numpy()[: cnt.value]
+        out, count = N.kocc_select(ctx, kocc, mode, thr)
+        return out.numpy()[:count]
 
     measures = {
         "k_skewness": k_skewness,

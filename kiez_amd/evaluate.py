@@ -134,10 +134,8 @@ def hits(nn_ind: Union[np.ndarray, list, Dict[Any, List], "N.DeviceArray"], gold
     else:
         ctx = ctx or N.Context.get()
         ind_dev = ctx.to_device(ind_host)
-    n, cols = ind_dev.shape
-    hist = ctx.empty((cols + 1,), np.int64)
-    gold_dev = ctx.to_device(gold_arr)   # (held until the call returns: a device array is released with its Python object)
-    N._check(ctx.lib.kz_hit_positions(ctx.handle, ind_dev.ptr, gold_dev.ptr, n, cols, hist.ptr), "kz_hit_positions")
+    cols = ind_dev.shape[1]
+    hist = N.hit_positions(ctx, ind_dev, ctx.to_device(gold_arr))   # (the uploaded gold vector is held until the call returns)
     cum = np.cumsum(hist.numpy()[:cols])
     return {kk: (float(cum[min(kk, cols) - 1]) / len(gold) if kk >= 1 else 0.0) for kk in k}
 

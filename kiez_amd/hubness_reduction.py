@@ -8,7 +8,6 @@ result crosses PCIe.
 """
 from __future__ import annotations
 
-import ctypes as C
 import warnings
 from abc import ABC, abstractmethod
 from typing import Optional, Tuple
@@ -17,8 +16,6 @@ import numpy as np
 
 from . import _native as N
 from .neighbors import NNAlgorithm, SklearnNN, check_is_fitted
-
-_P = C.c_void_p
 
 
 def _is_dev(x):
@@ -422,10 +419,7 @@ class CSLS(HubnessReduction):
     def transform(self, neigh_dist, neigh_ind, query):
         check_is_fitted(self, "r_dist_train_")
         d, i = self._device_inputs(neigh_dist, neigh_ind)
-        n, K = d.shape
-        out = self.ctx.empty((n, K), np.float64)
-        N._check(self.ctx.lib.kz_csls(self.ctx.handle, d.ptr, i.ptr, n, K, self._r_train_dev.ptr, out.ptr), "kz_csls")
-        return self._finish(out, neigh_dist, neigh_ind)
+        return self._finish(N.csls(self.ctx, d, i, self._r_train_dev), neigh_dist, neigh_ind)
 
 
 class LocalScaling(HubnessReduction):
@@ -463,11 +457,7 @@ class LocalScaling(HubnessReduction):
     def transform(self, neigh_dist, neigh_ind, query=None):
         check_is_fitted(self, "r_dist_t_to_s_")
         d, i = self._device_inputs(neigh_dist, neigh_ind)
-        n, K = d.shape
-        out = self.ctx.empty((n, K), np.float64)
-        N._check(self.ctx.lib.kz_local_scaling(self.ctx.handle, d.ptr, i.ptr, n, K, self._r_t_dev.ptr,
-                                               1 if self.method == "nicdm" else 0, out.ptr), "kz_local_scaling")
-        return self._finish(out, neigh_dist, neigh_ind)
+        return self._finish(N.local_scaling(self.ctx, d, i, self._r_t_dev, self.method == "nicdm"), neigh_dist, neigh_ind)
 
 
 class MutualProximity(HubnessReduction):
@@ -516,15 +506,8 @@ class MutualProximity(HubnessReduction):
     def transform(self, neigh_dist, neigh_ind, query):
         check_is_fitted(self, ["mu_t_to_s_", "sd_t_to_s_", "neigh_dist_t_to_s_", "neigh_ind_t_to_s_"], all_or_any=any)
         d, i = self._device_inputs(neigh_dist, neigh_ind)
-        n, K = d.shape
-        out = self.ctx.empty((n, K), np.float64)
-        if self.method == "normal":
-            N._check(self.ctx.lib.kz_mp_normal(self.ctx.handle, d.ptr, i.ptr, n, K, self._mu_dev.ptr, self._sd_dev.ptr,
-                                               out.ptr), "kz_mp_normal")
-        else:
-            n_t, Kt = self._dist_t2s_dev.shape
-            N._check(self.ctx.lib.kz_mp_empiric(self.ctx.handle, d.ptr, i.ptr, n, K, self._dist_t2s_dev.ptr,
-                                                self._ind_t2s_dev.ptr, n_t, Kt, out.ptr), "kz_mp_empiric")
+        out = (N.mp_normal(self.ctx, d, i, self._mu_dev, self._sd_dev) if self.method == "normal"
+               else N.mp_empiric(self.ctx, d, i, self._dist_t2s_dev, self._ind_t2s_dev))
         return self._finish(out, neigh_dist, neigh_ind)
 
 
@@ -745,12 +728,8 @@ class DisSimLocal(HubnessReduction):
         return sm, tm
 
     def _fit(self, neigh_dist, neigh_ind, source, target) -> "DisSimLocal":
-        ctx = self.ctx
         sm, tm = self._matrices(source, target)
-        ind = ctx.as_device(neigh_ind, np.int64)
-        n_t, Kt = ind.shape
-        t2c = ctx.empty((n_t,), np.float64)
-        N._check(ctx.lib.kz_dsl_fit(ctx.handle, ind.ptr, n_t, Kt, sm.handle, tm.handle, 0, t2c.ptr), "kz_dsl_fit")
+        t2c = N.dsl_fit(self.ctx, self.ctx.as_device(neigh_ind, np.int64), sm, tm)
         self.source_ = source
         self.target_ = target
         self._source_m, self._target_m = sm, tm
@@ -762,7 +741,6 @@ class DisSimLocal(HubnessReduction):
         check_is_fitted(self, ["target_", "target_dist_to_centroids_"])
         ctx = self.ctx
         i = ctx.as_device(neigh_ind, np.int64)
-        n, K = i.shape
         tm = self._target_m
         if query is self.source_:
             qm = self._source_m
@@ -771,13 +749,9 @@ class DisSimLocal(HubnessReduction):
             tm = self.nn_algo._partner(qm, self._target_m)   # (2-byte target rows and a query of another type: the float64 pair)
         else:
             qm = N.DeviceMatrix(ctx, np.asarray(query, dtype=self._target_m.dtype), "sqeuclidean")
-        out = ctx.empty((n, K), np.float64)
         gmin = ctx.to_device(np.array([np.inf], dtype=np.float64))
-        N._check(ctx.lib.kz_dsl_transform(ctx.handle, i.ptr, n, K, qm.handle, 0, tm.handle,
-                                          self.target_dist_to_centroids_.ptr, out.ptr, gmin.ptr), "kz_dsl_transform")
-        mn = float(self._reduce_min(gmin.numpy()[0]))
-        N._check(ctx.lib.kz_dsl_finalize(ctx.handle, out.ptr, n * K, mn, 1 if self.squared else 0), "kz_dsl_finalize")
-        return self._finish(out, neigh_dist, neigh_ind)
+        out = N.dsl_transform(ctx, i, qm, 0, tm, self.target_dist_to_centroids_, gmin)
+        return self._finish(N.dsl_finalize(ctx, out, float(self._reduce_min(gmin.numpy()[0])), bool(self.squared)), neigh_dist, neigh_ind)
 
     _no_rank_reason = ("DisSimLocal's values come from its own gather of the embeddings around the candidate list's centroid, not from "
                        "the search's distances: a target row outside the list has no value, so there is no rank over the whole index")

@@ -56,6 +56,75 @@ def test_product_package_never_imports_the_oracle_or_a_cpu_math_library():
                 assert "sklearn" not in s and "scipy" not in s, f"{f}: product path must not compute on the CPU ({s})"
 
 
+def _library_calls(tree):
+    """The `kz_*` names a module calls as attributes (`x.kz_name(...)`), and whether it names `_check` at all."""
+    import ast
+    calls = {n.func.attr for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr.startswith("kz_")}
+    check = any((isinstance(n, ast.Attribute) and n.attr == "_check") or (isinstance(n, ast.Name) and n.id == "_check") or
+                (isinstance(n, ast.alias) and n.name == "_check") for n in ast.walk(tree))
+    return calls, check
+
+
+def test_native_module_is_the_only_caller_of_the_library():
+    """No module of the package but _native.py calls a `kz_*` entry point or touches `_check`: parsed, so comments and docstrings
+    may name the symbols."""
+    import ast
+    seen = 0
+    for f in sorted((ROOT / "kiez_amd").glob("*.py")):
+        calls, check = _library_calls(ast.parse(f.read_text()))
+        if f.name == "_native.py":
+            assert calls and check, "the check does not see the calls it looks for"
+            continue
+        seen += 1
+        assert not calls, f"{f.name} calls the library itself: {sorted(calls)}"
+        assert not check, f"{f.name} uses _native._check: the wrapper of the call belongs into _native.py"
+    assert seen >= 9
+
+
+# entry points of tests and self-tests, and the one nothing uses: every other symbol has its wrapper in _native.py
+UNWRAPPED = {"kz_ctx_destroy", "kz_matrix_shape", "kz_knn_plan", "kz_selftest_div", "kz_selftest_image", "kz_comm_rank"}
+
+
+def test_every_symbol_has_a_wrapper_but_the_six_named():
+    from kiez_amd import _native as N
+    text = (ROOT / "kiez_amd" / "_native.py").read_text()
+    begin, end = text.index("SYMBOLS = ["), text.index("def library_path")
+    assert begin < end and text[begin:end].count('("kz_') == len(N.SYMBOLS)
+    rest = text[:begin] + text[end:]
+    missing = {name for name, _, _ in N.SYMBOLS if not re.search(rf"\b{name}\b", rest)}
+    assert missing == UNWRAPPED, f"without a wrapper: {sorted(missing - UNWRAPPED)}; wrapped after all: {sorted(UNWRAPPED - missing)}"
+
+
+class _FakeTensor:
+    def __init__(self, is_cuda=True, contiguous=True):
+        self.is_cuda, self._contiguous = is_cuda, contiguous
+
+    def is_contiguous(self):
+        return self._contiguous
+
+    def data_ptr(self):
+        return 0x7f0000001000
+
+
+def test_pointer_rule_of_the_two_buffer_kinds():
+    """_native._ptr: a DeviceArray gives its .ptr, None gives None, a tensor its data_ptr() -- and a tensor that is not on the device or
+    not contiguous raises TypeError naming the argument (no assert: the check survives python -O)."""
+    from types import SimpleNamespace
+
+    from kiez_amd import _native as N
+    p = ctypes.c_void_p(0x1000)
+    assert N._ptr(SimpleNamespace(ptr=p), "dist") is p
+    assert N._ptr(None, "dist") is None
+    got = N._ptr(_FakeTensor(), "dist")
+    assert isinstance(got, ctypes.c_void_p) and got.value == 0x7f0000001000
+    for bad in (_FakeTensor(is_cuda=False), _FakeTensor(contiguous=False)):
+        with pytest.raises(TypeError, match="r_train must be a DeviceArray or a contiguous CUDA tensor"):
+            N._ptr(bad, "r_train")
+    src = (ROOT / "kiez_amd" / "_native.py").read_text()
+    body = src[src.index("def _ptr("):src.index("def knn(")]
+    assert "assert" not in body
+
+
 @pytest.mark.gpu
 def test_context_and_error_reporting():
     from kiez_amd import _native as N
