@@ -11,6 +11,7 @@
 
 #include "../../include/kiez_amd.h"
 #include "kz_pool_buf.h"
+#include "kz_route.h"
 
 #define KZ_TILE 128   // rows per packed tile (= MFMA block tile edge)
 #define KZ_KSLICE 16  // k elements staged per LDS slice (4 k-groups of 4)
@@ -20,10 +21,7 @@
 // Former context options that no tool or test set (round 6: one table of <= 30 options): the values every build ran with.
 // (The on / off switches among them are gone with the branches they guarded; what is left are values.)
 constexpr double KZ_K_NESTED_MIN_MS = 2.0;   // the nested sample of the shared sweep is taken when it saves at least this many model-ms (sweep / stride)
-constexpr int KZ_K_DUAL_SHORT_DIV = 5;   // short-list routes: one list of 16 per this many neighbours (k / 5 lists)
-constexpr int KZ_K_DUAL_SHORT_KP = 16;   // ... of this length
-constexpr double KZ_K_PROBE_MIN_MS = 12.0;   // searches below "probe_min_pairs" distance pairs take neither the tier probe nor a floor -- unless the sweep is at least this many model-ms (2 n_q n_i d / 1e12) long
-constexpr int KZ_K_EXACT_DIRECT_ROWS = 32;   // at most this many rows left by the split-bf16 tier skip the float32-operand kernel and go to the exact kernels
+constexpr int KZ_K_DUAL_SHORT_KP = 16;   // short-list routes: lists of this length, one per KZ_K_DUAL_SHORT_DIV neighbours (kz_route.h)
 constexpr double KZ_K_SPEC_ELEMS = 1.6e9;   // speculative rescue: at most this / (index rows x d) rows (and at most "spec_rows")
 constexpr int KZ_K_FLOOR_PROBE = 1024;   // seeded lists: rows of the probe in kz_knn_dual
 constexpr double KZ_K_MODEL_MIN_R2 = 0.45;  // model thresholds of the shared sweep: the forward floor fit must explain at least this share of the k-th key's variance, or the reverse probe is not run (kz_knn_dual.h "MODEL THRESHOLDS")
@@ -94,20 +92,7 @@ struct kz_ctx {
 // Shift and scale shared by the fp16 images of the matrices that are searched against each other (kz_pack.hip):
 // distances are translation invariant, so both sides are centred with ONE vector mu (the column mean of the first index
 // of the pair) and scaled by ONE power of two S into the fp16 range.  Reference counted: images keep it alive.
-// Slices (16 features) of the fp16 image of a matrix with kg k-groups: d_pad / 16 -- rounded up to a multiple of 8 beyond 32
-// slices (the wide-row builds of the fp16 kernel, kz_knn_h_inst.h, exist for 32, 40, 48, 56 and 64 slices only; the padding
-// slices are zero, and zero products add exactly nothing to the float32 accumulators) and to a multiple of 16 beyond 64 (the
-// parity-split builds, kz_knn_hx16.h: 80, 96, 112 and 128 slices -- each wave pair splits them into two of the counts above).
-__host__ __device__ __forceinline__ int kz_h_nsr(int kg) {
-    const int s = kg / 4;
-    return s <= 32 ? s : (s <= 64 ? (s + 7) & ~7 : (s + 15) & ~15);
-}
-// The fp16 tier exists for 2 .. 24 slices (d <= 384) and 32 .. 128 slices (d = 497 .. 2048: the wide-row builds up to 64 slices,
-// the parity-split builds beyond); 25 .. 31 slices and more than 128 run on float32 operands.
-__host__ __device__ __forceinline__ bool kz_h_slices_ok(int kg) {
-    const int s = kg / 4;
-    return (s >= 2 && s <= 24) || (s >= 32 && s <= 128);
-}
+// (kz_h_nsr, kz_h_slices_ok -- the slices of the fp16 image and where the fp16 tier exists: kz_route.h)
 // Work items the planner may put into one round of an fp16 launch: the resident workgroups -- half of them where two workgroups
 // sweep one item (wg_per_item of the kernel's descriptor, kz_knn_kernels.h: the parity-split builds own 64 queries each).
 __host__ __forceinline__ int kz_h_slots(int wg_per_item, int blocks_per_cu, int n_cus) {

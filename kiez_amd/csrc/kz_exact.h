@@ -824,7 +824,7 @@ static int kz_exact_select_lds(int k_sel, size_t* dyn_bytes) {
 // neighbours per query on the exact-only route.  Selection state: 12 bytes per neighbour, 48 KiB of dynamic LDS at 4096 -- on top
 // of kz_exact_select_kernel's ~20 KiB of static LDS: more than 64 KiB in all from 3749 neighbours on, hence the opt-in of
 // kz_exact_select_lds (68.2 KiB of a CU's 160 at 4096)
-constexpr int KZ_EXACT_MAX_K = 4096;
+// (KZ_EXACT_MAX_K = 4096: kz_route.h)
 
 // What differs between the callers of the stage.  The defaults are the whole-index fallback's (and kz_gold_ranks'); kz_spec_rescue
 // sets every field.

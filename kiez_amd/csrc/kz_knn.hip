@@ -201,11 +201,7 @@ __global__ __launch_bounds__(256, 3) void kz_knn_cand_kernel(KnnCandParams p) {
 
 #include "kz_knn_finalize.h"
 
-// Rows a K' = 16 pass could not certify: few (the usual handful) -> more lists of 16, it is all latency; many (hard data) -> lists
-// of 64, which certify more of them in one go (400k x 400k, k = 10, clusters of very different density: 140 against 112 ms)
-constexpr int KZ_ESC_SHORT_MAX_ROWS = 2048;
-constexpr int KZ_MAX_PIECES = 128;  // index ranges per query tile (each range keeps its own K'-entry list per query).  Round 4: 64 -> 128
-                                    // (a search of 8 .. 700 rows against 1 M: 0.84 .. 0.92 -> 0.61 .. 0.74 ms; 256: the finalize kernel's selection eats the gain)
+// (KZ_ESC_SHORT_MAX_ROWS, KZ_MAX_PIECES: kz_route.h)
 static int kz_max_pieces(int KP, int halves) {
     const int m = KZ_FIN_MAXM / (halves * KP);
     return m < KZ_MAX_PIECES ? m : KZ_MAX_PIECES;
@@ -216,13 +212,7 @@ static int kz_max_pieces(int KP, int halves) {
 // ---------------------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------------------
-static int kz_pick_list_len(int k_eff) {
-    if (k_eff <= 12) return 16;
-    if (k_eff <= 26) return 32;
-    if (k_eff <= 54) return 64;
-    if (k_eff <= 110) return 128;
-    return 0;
-}
+// (kz_pick_list_len: kz_route.h)
 
 // The float32-operand kernel's entries of the kernel table (kz_knn_kernels.h): one build per list length, any slice count
 template <int... KPS>
@@ -611,20 +601,7 @@ static int kz_spec_rescue(kz_ctx* ctx, KzSpec& sp, int R, const kz_matrix* query
     return KZ_OK;
 }
 
-// What a re-search asks of kz_knn_impl (the default asks for nothing: the context's settings).  The caller decides the fields together.
-struct KzResearch {
-    int prec = -1;            // operands: -1 = the context's setting (kz_ctx::precision), else 0 / 1 / 2
-    int min_kp = 0;           // smallest list length, 16 .. 128 (escalated rows of the fp16 tier: longer lists on the same operand images)
-    bool more_lists = false;  // escalated rows of a K' = 16 pass: more lists of 16 instead of longer ones (min_kp 0)
-    int wide_lists = 0;       // > 0: the fp16 tier's WIDE route with this many lists of 16 per query (min_kp 0)
-    bool no_short = false;    // not the short-list route (rows that route could not certify: a re-search differs from the pass that failed)
-};
-static KzResearch kz_research_wide(int lists) {   // (a caller's probe has found that this data needs margin in ranks, not better operands)
-    KzResearch r;
-    r.prec = 0;
-    r.wide_lists = lists;
-    return r;
-}
+// (KzResearch -- what a re-search asks of kz_knn_impl -- and kz_research_wide: kz_route.h)
 
 // What every entry point asks of a query / index pair and its two output arrays (`who`: the entry point, as its messages name it)
 static int kz_require_pair(const char* who, const kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
@@ -813,6 +790,500 @@ static int kz_escalate_ladder(kz_ctx* ctx, kz_matrix* query, int64_t cq_begin, c
 
 #include "kz_range.h"
 
+// ---------------------------------------------------------------------------------------------------
+// kz_knn_impl.  The route of a call is DECIDED in kz_route.h (pure: KzRouteIn, KzResearch -> KzRoute, KzAfterPass) and EXECUTED by
+// the stages below, which kz_knn_impl runs in sequence: lists and tier, the routes of lists of 16 on the dealt image, the tier
+// probe, then per chunk of query rows: plan, sweep, finalize, read-back, and the way down for the rows left uncertified.
+// ---------------------------------------------------------------------------------------------------
+// The arguments of one kz_knn_impl call, as every stage reads them (none of them changes during the call).
+struct KzCall {
+    kz_ctx* ctx;
+    kz_matrix* query;
+    int64_t q_begin, q_count;
+    kz_matrix* index;
+    int k, exclude_self;
+    const int64_t* d_self_ids;
+    double* d_dist;
+    int64_t* d_ind;
+    KzDualPass* dual;
+};
+// The tallies of one call (kz_knn_stats without the route fields).
+struct KzTally {
+    double main_ms = 0, fin_ms = 0, fb_ms = 0;
+    float probe_ms = 0;   // (tier probe: reported under its own field, kz_knn_stats.probe_ms)
+    int64_t n_fail_total = 0, n_escalated = 0, n_first_fail = 0, n_spec = 0, n_range = 0, n_range_pairs = 0, n_range_group = 0;
+    double max_err_ratio = 0.0;
+    int last_splits = 1, last_blocks = 0;
+    void add(const kz_knn_stats& s) {   // a sub-search's (its own escalated rows, and what it sent further down)
+        n_escalated += s.n_escalated_rows;
+        n_fail_total += s.n_fallback_rows;
+        n_range += s.n_range_rows;
+        n_range_pairs += s.n_range_pairs;
+        n_range_group += s.n_range_group_rows;
+        if (s.max_err_ratio > max_err_ratio) max_err_ratio = s.max_err_ratio;
+    }
+    void write(kz_knn_stats* st) const {
+        st->main_kernel_ms = main_ms;
+        st->finalize_ms = fin_ms;
+        st->fallback_ms = fb_ms;
+        st->probe_ms = probe_ms;
+        st->n_fallback_rows = n_fail_total;
+        st->n_splits = last_splits;
+        st->n_blocks = last_blocks;
+        st->n_escalated_rows = n_escalated;
+        st->max_err_ratio = max_err_ratio;
+        st->n_first_pass_fail = n_first_fail > 0x7fffffff ? 0x7fffffff : (int32_t)n_first_fail;
+        st->n_spec_rows = n_spec > 0x7fffffff ? 0x7fffffff : (int32_t)n_spec;
+        st->n_range_rows = n_range;
+        st->n_range_pairs = n_range_pairs;
+        st->n_range_group_rows = n_range_group;
+    }
+};
+// One chunk of the call's query rows: one launch of the tier's kernel.
+struct KzChunk {
+    int64_t cq_begin, cq_count;
+    int qt0, n_qtiles, force_pieces;
+    KzPlan pl;
+};
+
+static KzRouteIn kz_route_in(const KzCall& c, int k_eff) {
+    const kz_ctx* ctx = c.ctx;
+    KzRouteIn in;
+    in.n_tiles = c.index->n_tiles;
+    in.n = c.index->n;
+    in.kg = c.index->kg;
+    // (slices of the fp16 image: kz_h_nsr pads 32 .. 64 to a multiple of 8 and 65 .. 128 to a multiple of 16 -- the other tiers never
+    //  read n_slices beyond 24)
+    in.n_slices = kz_h_nsr(c.index->kg);
+    in.gemm_form = c.index->metric < KZ_MANHATTAN;
+    in.same_kg = c.query->kg == c.index->kg;
+    in.range_ok = kz_range_shapes_ok(ctx, c.query, c.index);
+    in.k_eff = k_eff;
+    in.dual = c.dual != nullptr;
+    in.precision = ctx->precision;
+    in.esc_bf = ctx->esc_bf;
+    in.short_ord = ctx->short_ord;
+    in.short_ord_min_tiles = ctx->short_ord_min_tiles;
+    in.wide_lists = ctx->wide_lists;
+    in.wide_sel = ctx->wide_sel;
+    in.tier_probe = ctx->tier_probe;
+    in.chunk_rows = ctx->chunk_rows;
+    in.probe_min_pairs = ctx->probe_min_pairs;
+    if (c.dual) {
+        in.short_pieces = c.dual->short_pieces;
+        in.short_ksel = c.dual->short_ksel;
+        in.short_kp = c.dual->short_kp;
+        in.dual_probed = c.dual->probed != 0;
+    }
+    return in;
+}
+
+// The wide route with P lists, if its geometry allows (KZ_ERR_UNSUPPORTED) and the dealt image can be had (KZ_ERR_NOMEM).
+static int kz_take_wide(kz_matrix* index, const KzRouteIn& in, KzRoute* route, int P) {
+    int sel = 0;
+    if (!kz_route_wide_geometry(in, *route, P, &sel)) return KZ_ERR_UNSUPPORTED;
+    const int rc = kz_himage_dealt(index, P);
+    if (rc != KZ_OK) return rc;
+    kz_route_take_dealt(route, P, sel, true);
+    return KZ_OK;
+}
+
+// TIER PROBE (kz_route.h: kz_probe_wanted has said yes): a strided sample of the query rows through the fp16 pass, its verdict applied
+// to the route; on data that is fine, the population floor of the seeded lists from the sample's results (*qfloor_ord).
+static int kz_tier_probe(const KzCall& c, const KzRouteIn& in, KzRoute* route, float** qfloor_ord, float* probe_ms) {
+    kz_ctx* ctx = c.ctx;
+    const int n_probe = ctx->tier_probe;
+    KzPoolBuf<int> plist;
+    int rc = plist.alloc(ctx, (size_t)n_probe * sizeof(int));
+    if (rc != KZ_OK) return rc;
+    hipLaunchKernelGGL(kz_strided_rows_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, plist.get(), n_probe,
+                       c.q_count / n_probe);
+    kz_knn_stats stp;
+    float pms = 0;
+    KzResearch probe_rs;
+    probe_rs.prec = 0;
+    rc = kz_escalate_rows(ctx, c.query, c.q_begin, plist.get(), n_probe, c.index, c.k, c.exclude_self, c.d_self_ids, probe_rs, c.d_dist, c.d_ind, &stp,
+                          &pms);
+    if (rc != KZ_OK) return rc;
+    *probe_ms = pms;
+    const KzProbeVerdict verdict = kz_probe_verdict(n_probe, stp.n_first_pass_fail, ctx->wide_lists);
+    bool hard = verdict.hard;
+    if (verdict.try_wide) {
+        int sel = 0;
+        if (kz_route_wide_geometry(in, *route, ctx->wide_lists, &sel)) {
+            kz_knn_stats stw;
+            float wms = 0;
+            rc = kz_escalate_rows(ctx, c.query, c.q_begin, plist.get(), n_probe, c.index, c.k, c.exclude_self, c.d_self_ids,
+                                  kz_research_wide(ctx->wide_lists), c.d_dist, c.d_ind, &stw, &wms);
+            if (rc != KZ_OK) return rc;
+            *probe_ms += wms;
+            if (kz_probe_wide_wins(n_probe, stp.n_first_pass_fail, stw.n_first_pass_fail) && kz_take_wide(c.index, in, route, ctx->wide_lists) == KZ_OK)
+                hard = false;
+        }
+    }
+    plist.reset();
+    if (hard) {
+        kz_route_start_hard(in, route);
+    } else if (ctx->list_floor && !route->wide_route) {
+        // POPULATION FLOOR (above kz_escalate_rows): the probe's results are the model's input
+        double model[3];
+        bool ok = false;
+        rc = kz_floor_model(ctx, c.d_dist, c.query->himg->rowq + c.q_begin * 3, n_probe, c.q_count / n_probe, c.k, c.index->metric, model, &ok);
+        if (rc != KZ_OK) return rc;
+        const int64_t n_pad = (int64_t)c.query->n_tiles * KZ_TILE;
+        if (ok) rc = kz_floor_buf(ctx, (size_t)n_pad * 4, qfloor_ord);
+        if (rc != KZ_OK) return rc;
+        if (*qfloor_ord) {
+            hipLaunchKernelGGL(kz_floor_rows_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, (const int*)nullptr, c.query->n,
+                               n_pad, c.query->himg->rowq, c.index->himg->d_max, c.index->himg->center->d_scale, model[0], model[1], model[2],
+                               ctx->eps_scale, kz_gamma_acc_h(c.index->kg), *qfloor_ord);
+            KZ_HIP(hipGetLastError());
+        }
+    }
+    return KZ_OK;
+}
+
+// 64 QUERIES PER WAVE (kz_knn_h64.h): K' = 16 sweeps of 4 .. 13 slices -- half the LDS fragment reads per MFMA and half the
+// LDS-DMA volume per query of the 32-query kernel at two waves per SIMD instead of three; a work item = a unit of two query
+// tiles (tpw = 2).  Measured (profiles/r04_ablation.md section 2): the shared sweep at 13 slices -1.5 % (250k x 1M x 200: 90.6 ->
+// 89.2 ms), the ordinary kernel +0.8 % there, +8 % at 8 slices, and a launch of fewer than ~4 rounds of units does not fill the
+// chip (100k x 100k: +30 %).  Option "h_q64": 2 (default) = the shared sweep from 9 slices on over >= 4 rounds of units,
+// 1 = wherever the kernel is built for (tests), 0 = never.
+static int kz_q64_wanted(const KzCall& c, const KzRoute& route, int n_slices, bool* q64) {
+    const kz_ctx* ctx = c.ctx;
+    const KzDualPass* dual = c.dual;
+    bool q64_ok = false;
+    if (route.tier == KZ_TIER_H && route.cur.KP == 16 && !route.exact_only) {   // (is there a 64-query build for these rows?  The resolver may come back empty)
+        KzSweepKernel k64;
+        const int rc = kz_sweep_kernel(KZ_TIER_H, dual != nullptr, true, route.cur.KP, n_slices, &k64, true);
+        if (rc != KZ_OK) return rc;
+        q64_ok = k64.fn != nullptr;
+    }
+    *q64 = q64_ok && !(dual && dual->no_q64) && (ctx->h_q64 == 1 || (ctx->h_q64 == 2 && dual && n_slices >= 9 &&
+                                                 (c.q_count + 2 * KZ_TILE - 1) / (2 * KZ_TILE) >= (int64_t)4 * 2 * ctx->n_cus));
+    return KZ_OK;
+}
+
+// The operand images the chunk's tier sweeps (built on first use).
+static int kz_tier_images(const KzCall& c, const KzResearch& rs, const KzRoute& route) {
+    if (route.tier == KZ_TIER_BF) {
+        int rc = kz_matrix_image_bf(c.query);
+        if (rc == KZ_OK) rc = kz_matrix_image_bf(c.index);
+        if (rc != KZ_OK) return rc;
+    } else if (route.tier == KZ_TIER_F32 && !route.exact_only) {
+        int rc = kz_matrix_image_f32(c.query);
+        if (rc == KZ_OK) rc = kz_matrix_image_f32(c.index);
+        if (rc != KZ_OK) return rc;
+    }
+    if (route.tier == KZ_TIER_H && route.short_ord && route.cur.pieces >= 2) {
+        // (a re-search of the previous chunk's uncertified rows may have selected -- or packed -- the index dealt over another
+        //  number of ranges: this route's own image again; cached, two are kept)
+        // (any failure ends the call: launching on whatever image the last sub-search selected would certify against the wrong
+        //  range layout; unreachable while a slot exists once the route is chosen)
+        const int rcd = kz_himage_dealt(c.index, route.wide_route || rs.wide_lists > 0 ? route.cur.pieces : route.route_P);
+        if (rcd != KZ_OK) {
+            if (rcd == KZ_ERR_NOMEM) kz_set_error("kz_knn: out of device memory for the row-dealt image of the index");
+            return rcd;
+        }
+    }
+    return KZ_OK;
+}
+
+// ---- schedule: which workgroup sweeps which (query tile, index-tile range): kz_prepare_pass above --------------
+// The chunk that starts at row c0 of the call and its plan; *max_rows_per_chunk is halved where a chunk's lists would pass 2^32 entries.
+static void kz_chunk_plan(const KzCall& c, const KzRoute& route, int slots, int tpw_h, int n_ytiles, int64_t c0, int64_t* max_rows_per_chunk,
+                          KzChunk* ch) {
+    const KzDualPass* dual = c.dual;
+    const int tier = route.tier, KP = route.cur.KP;
+    ch->cq_begin = c.q_begin + c0;
+    ch->qt0 = (int)(ch->cq_begin / KZ_TILE);
+    for (;;) {
+        ch->cq_count = (c.q_count - c0 < *max_rows_per_chunk) ? (c.q_count - c0) : *max_rows_per_chunk;
+        ch->n_qtiles = (int)((ch->cq_begin + ch->cq_count - 1) / KZ_TILE) - ch->qt0 + 1;
+        ch->force_pieces = kz_route_sub_pieces(route, (ch->n_qtiles + tpw_h - 1) / tpw_h, slots, n_ytiles);
+        int max_pieces = kz_max_pieces(KP, tier == KZ_TIER_F32 ? 2 : 1);
+        if (dual && dual->max_entries > 0 && max_pieces > dual->max_entries / KP) max_pieces = dual->max_entries / KP;
+        // The kernels address a launch's lists with 32-bit element offsets: a chunk whose plan would pass 2^32 entries (K' = 16,
+        // 2 M rows over 128 ranges) is halved.
+        kz_plan_tier_pass(c.ctx, ch->n_qtiles, n_ytiles, slots, max_pieces, KP, tier, tier == KZ_TIER_H ? tpw_h : 1, ch->force_pieces,
+                          route.min_pieces_call, &ch->pl);
+        if (ch->pl.list_elems < ((size_t)1 << 32) || ch->cq_count <= 8 * KZ_TILE || (dual && dual->raw_lists)) break;
+        *max_rows_per_chunk = ((ch->cq_count / 2 + KZ_TILE - 1) / KZ_TILE) * KZ_TILE;
+    }
+}
+
+// The chunk's sweep, between ev[0] and the caller's ev[1]: the dual build, the range-0 boot, the plain launch (and its two diagnostic
+// variants), or -- exact-only -- the list of every row.  boot_floor: this chunk's range-0 floor, if any (the finalize kernel must
+// know it); stamp_buf: diagnostic "abl_stamp".
+static int kz_chunk_sweep(const KzCall& c, const KzRoute& route, const KzSweepKernel& kern, const KzChunk& ch, const KzPass& ps, bool q64, bool boot,
+                          const float* qfloor_ord, int n_ytiles, KzPoolBuf<float>& boot_floor, KzPoolBuf<unsigned long long>& stamp_buf) {
+    kz_ctx* ctx = c.ctx;
+    kz_matrix *query = c.query, *index = c.index;
+    const KzDualPass* dual = c.dual;
+    const int tier = route.tier, KP = route.cur.KP, W = ps.W;
+    const bool short_ord = route.short_ord;
+    int rc = KZ_OK;
+    KnnCandParams cp;
+    memset(&cp, 0, sizeof(cp));
+    if (tier == KZ_TIER_H) {
+        cp.qpack = (const float*)query->himg->packed;
+        cp.ypack = (const float*)(short_ord ? index->himg->dealt_packed : index->himg->packed);
+        cp.ybias = short_ord ? index->himg->dealt_bias : index->himg->bias;
+    } else {
+        cp.qpack = tier == KZ_TIER_BF ? (const float*)query->packed_bf : query->packed;
+        cp.ypack = tier == KZ_TIER_BF ? (const float*)index->packed_bf : index->packed;
+        cp.ybias = index->bias;
+    }
+    cp.work = ps.d_work;
+    cp.qt0 = ch.qt0;
+    cp.n_ytiles = n_ytiles;
+    cp.n_qtiles = ch.n_qtiles;
+    cp.lay = ps.lay;
+    cp.kg = index->kg;
+    cp.out_key = ps.out_key;
+    cp.out_idx = ps.out_idx;
+    if (tier == KZ_TIER_H && !dual) cp.qfloor = qfloor_ord;
+    KZ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+    if (route.exact_only) {
+        // every row of the chunk goes to the exact kernels: the "fail list" is 0 .. cq_count-1
+        hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((ch.cq_count + 255) / 256)), dim3(256), 0, ctx->stream, ps.fail_list, (int)ch.cq_count);
+        KZ_HIP(hipGetLastError());
+    } else if (tier == KZ_TIER_H && dual) {
+        cp.qpack = dual->qpack;
+        cp.ypack = dual->ypack;
+        cp.ybias = dual->ybias;
+        cp.theta = dual->theta;
+        cp.qnbias = dual->qnbias;
+        cp.qfloor = dual->qfloor;
+        cp.log_keys = dual->log_keys;
+        cp.log_meta = dual->log_meta;
+        cp.log_cnt = dual->log_cnt;
+        cp.log_cap = dual->log_cap;
+        rc = kz_sweep_launch(ctx, kern, cp, W);
+    } else if (tier == KZ_TIER_H && boot && ps.W0 > 0 && ps.W0 < W) {
+        // range 0 of every query tile, the floor off its lists, then the other ranges
+        rc = kz_sweep_launch(ctx, kern, cp, ps.W0);
+        if (rc != KZ_OK) return rc;
+        const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
+        rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);   // (a buffer of this chunk: escalated sub-searches boot too)
+        if (rc != KZ_OK) return rc;
+        hipLaunchKernelGGL(kz_boot_floor_kernel, dim3((unsigned)((ch.cq_count + 255) / 256)), dim3(256), 0, ctx->stream, ps.out_key, ps.out_idx, ps.lay,
+                           KP, ch.cq_begin - (int64_t)ch.qt0 * KZ_TILE, ch.cq_begin, ch.cq_count, cp.qfloor, boot_floor.get());
+        KZ_HIP(hipGetLastError());
+        cp.qfloor = boot_floor.get();
+        cp.work = ps.d_work + ps.W0;
+        rc = kz_sweep_launch(ctx, kern, cp, W - ps.W0);
+    } else if (tier == KZ_TIER_H && !q64) {
+        if ((ctx->abl & 2) && getenv("KZ_STAMP_FILE")) {   // (diagnostic: a -DKZ_ABL_STAMP build of the fp16 units fills it)
+            rc = stamp_buf.alloc(ctx, (size_t)W * (16 + 1024));
+            if (rc != KZ_OK) return rc;
+            KZ_HIP(hipMemsetAsync(stamp_buf.get(), 0, (size_t)W * (16 + 1024), ctx->stream));
+            cp.log_meta = stamp_buf.get();
+            cp.log_keys = stamp_buf.get() + 2 * (size_t)W;
+        }
+        rc = kz_sweep_launch(ctx, kern, cp, W);
+        cp.log_meta = nullptr;
+        cp.log_keys = nullptr;
+        if (rc == KZ_OK && (ctx->abl & 1) && !short_ord && ps.lay.n_regions == 1 && ps.lay.pieces[0] == 1) {
+            // DIAGNOSTIC ("abl_refloor", profiles/r06_event_ablation.md): the same sweep AGAIN with every list starting at the
+            // threshold it ENDED on (the K'-th best key of the first sweep's list): K' insertions per query instead of
+            // K' (1 + ln(n / K')) -- the time any seeding of the lists could at best reach.  The second sweep is the one timed.
+            const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
+            rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);
+            if (rc != KZ_OK) return rc;
+            hipLaunchKernelGGL(kz_boot_floor_kernel, dim3((unsigned)((ch.cq_count + 255) / 256)), dim3(256), 0, ctx->stream, ps.out_key, ps.out_idx,
+                               ps.lay, KP, ch.cq_begin - (int64_t)ch.qt0 * KZ_TILE, ch.cq_begin, ch.cq_count, cp.qfloor, boot_floor.get());
+            // (one ulp below: entries equal to the threshold must get in again)
+            hipLaunchKernelGGL(kz_floor_nudge_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, boot_floor.get(), n_pad);
+            KZ_HIP(hipGetLastError());
+            cp.qfloor = boot_floor.get();
+            KZ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+            rc = kz_sweep_launch(ctx, kern, cp, W);
+        }
+    } else   // (the 64-query kernel, the split-bf16 and the float32 operands: one plain launch)
+        rc = kz_sweep_launch(ctx, kern, cp, W);
+    return rc;
+}
+
+// The finalize kernel's parameters that every launch fills the same way: the two matrices and -- fp16 tier: qi / ii, the images the
+// lists were swept on; nullptr on the other tiers -- the terms of that tier's certification bound.  The lists, the rows and the
+// outputs are the caller's.
+static KnnFinParams kz_fin_params(const kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index, const kz_himage* qi, const kz_himage* ii, int k) {
+    KnnFinParams fp;
+    memset(&fp, 0, sizeof(fp));
+    fp.qraw = query->raw;
+    fp.yraw = index->raw;
+    fp.qsqn = query->sqn;
+    fp.ysqn = index->sqn;
+    fp.n_i = index->n;
+    fp.d = (int)index->d;
+    fp.metric = index->metric;
+    fp.k = k;
+    fp.ystats = index->d_stats;
+    fp.tier_h = qi ? 1 : 0;
+    if (fp.tier_h) {
+        fp.eps_mult = ctx->eps_scale;
+        fp.gamma_acc = kz_gamma_acc_h(index->kg);
+        fp.q_rowq = qi->rowq;
+        fp.y_hmax = ii->d_max;
+        fp.hscale = ii->center->d_scale;
+    }
+    return fp;
+}
+
+// The chunk's finalize launch (none for an exact-only call or a raw-list pass) and the parameters it ran with, which the stages behind
+// it read (*fp: where results go, the fail list).  c0: first row of the chunk in the call; gamma: the tier's a-priori bound factor;
+// list_floor: what the lists of an ordinary fp16 sweep started at (range-0 floor, else the population floor, else nullptr).
+static int kz_chunk_finalize(const KzCall& c, const KzRoute& route, const KzChunk& ch, const KzPass& ps, int64_t c0, double gamma,
+                             const float* list_floor, KnnFinParams* out) {
+    kz_ctx* ctx = c.ctx;
+    kz_matrix *query = c.query, *index = c.index;
+    const KzDualPass* dual = c.dual;
+    const int tier = route.tier, KP = route.cur.KP;
+    KnnFinParams fp = kz_fin_params(ctx, query, index, tier == KZ_TIER_H ? query->himg : nullptr, tier == KZ_TIER_H ? index->himg : nullptr, c.k);
+    fp.in_key = ps.out_key;
+    fp.in_idx = ps.out_idx;
+    fp.lay = ps.lay;
+    fp.KP = KP;
+    fp.KSEL = route.cur.KSEL;
+    fp.list_row0 = ch.cq_begin - (int64_t)ch.qt0 * KZ_TILE;
+    fp.q_begin = ch.cq_begin;
+    fp.q_count = ch.cq_count;
+    fp.exclude_self = c.exclude_self ? 1 : 0;
+    fp.self_ids = c.d_self_ids;
+    fp.gamma = gamma;
+    fp.out_dist = c.d_dist + c0 * (int64_t)c.k;
+    fp.out_ind = c.d_ind + c0 * (int64_t)c.k;
+    if (tier == KZ_TIER_H && route.short_ord) fp.idx_map = index->himg->dealt_perm;   // the lists hold rows of the dealt index image
+    if (tier == KZ_TIER_H && !dual) fp.list_floor = list_floor;
+    if (tier == KZ_TIER_H && dual) {
+        fp.idx_map = dual->perm;      // the lists hold rows of the sorted index image
+        fp.row_map = dual->row_map;   // the chunk is a range of IMAGE rows: results and failures go by matrix row
+        fp.list_floor = dual->qfloor;
+        fp.out_dist = c.d_dist;
+        fp.out_ind = c.d_ind;
+    }
+    fp.fail_count = ctx->d_counters + 8;
+    fp.fail_list = ps.fail_list;
+    fp.fail_tau = ps.fail_tau;
+    fp.err_ratio_bits = (unsigned long long*)(ctx->d_counters + 10);
+    if (fp.tier_h && index->metric == KZ_COSINE && (fp.KSEL > 0 ? fp.KSEL : KP) > 160 && !(dual && dual->raw_lists)) {
+        // (hundreds of re-ranked candidates per query: the normalised float64 rows of the index, built once -- kz_pack.hip)
+        const int rc = kz_matrix_norm64(index);
+        if (rc != KZ_OK) return rc;
+        fp.ynorm64 = index->norm64;
+    }
+    *out = fp;
+    if (!route.exact_only && !(dual && dual->raw_lists))   // (raw lists: the caller's hook has read them; nothing is finalized)
+        return kz_launch_finalize(ctx, *out, ps.lay, KP, ch.cq_count, index->dtype);
+    return KZ_OK;
+}
+
+// Behind the finalize kernel: the speculative rescue, the read-back of the fail counter (and of the matrices' deferred finiteness
+// verdicts), the synchronisation; *spec_R = rows the speculative launches covered.
+static int kz_chunk_readback(const KzCall& c, const KzRoute& route, const KzChunk& ch, const KzPass& ps, const KnnFinParams& fp, int k_eff,
+                             int n_ytiles, int n_slices, KzPoolBuf<unsigned long long>& stamp_buf, int* spec_R) {
+    kz_ctx* ctx = c.ctx;
+    kz_matrix *query = c.query, *index = c.index;
+    const KzDualPass* dual = c.dual;
+    const int W = ps.W;
+    int* fail_count = ctx->d_counters + 8;
+    // matrices created from device rows have not had their finiteness verdict read yet (kz_matrix_create waits for
+    // nothing): it rides on this call's read-back
+    kz_matrix* unchecked[2] = {query->checked ? nullptr : query, (index->checked || index == query) ? nullptr : index};
+    *spec_R = 0;
+    hipError_t es;
+    {
+        // SPECULATIVE RESCUE (above kz_escalate_rows): the exact kernels for up to R uncertified rows, before the count is known
+        KzSpec spec;   // (its buffers go right after the read-back -- stream-ordered: the launches that used them are on the stream)
+        if (!route.exact_only && !(dual && dual->raw_lists) && route.tier != KZ_TIER_F32) {
+            const int R = kz_spec_rows(ctx, index, k_eff);
+            if (R > 0) {
+                const int rc = kz_spec_rescue(ctx, spec, R, query, fp.row_map ? 0 : ch.cq_begin, ps.fail_list, fail_count, index, c.k, c.exclude_self,
+                                              c.d_self_ids, fp.out_dist, fp.out_ind);
+                if (rc != KZ_OK) return rc;
+                if (spec.R > 0) KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+            }
+        }
+        KZ_HIP(hipMemcpyAsync(ctx->h_counters + 8, fail_count, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        for (int u = 0; u < 2; ++u)
+            if (unchecked[u])
+                KZ_HIP(hipMemcpyAsync(ctx->h_counters + 44 + 10 * u, unchecked[u]->d_stats, 40, hipMemcpyDeviceToHost, ctx->stream));
+        es = hipStreamSynchronize(ctx->stream);
+        *spec_R = spec.R;
+    }
+    KZ_HIP(es);
+    if (stamp_buf.get()) {   // (diagnostic: start / end of every workgroup of the sweep, in work-table order, appended to the file)
+        std::vector<unsigned long long> hs((size_t)W * 130);
+        KZ_HIP(hipMemcpy(hs.data(), stamp_buf.get(), (size_t)W * (16 + 1024), hipMemcpyDeviceToHost));
+        stamp_buf.reset();
+        if (FILE* f = fopen(getenv("KZ_STAMP_FILE"), "a")) {
+            fprintf(f, "# launch W=%d n_qtiles=%d n_ytiles=%d slices=%d\n", W, ch.n_qtiles, n_ytiles, n_slices);
+            for (int w = 0; w < W; ++w) {
+                fprintf(f, "%d %llu %llu", w, hs[2 * (size_t)w], hs[2 * (size_t)w + 1]);
+                if (w < 8 || w % 97 == 0)   // (per-tile stamps of a few workgroups: the first 64 tiles, then every 16th)
+                    for (int t = 0; t < 128; ++t) fprintf(f, " %llu", hs[2 * (size_t)W + (size_t)w * 128 + t]);
+                fprintf(f, "\n");
+            }
+            fclose(f);
+        }
+    }
+    for (int u = 0; u < 2; ++u) {
+        if (!unchecked[u]) continue;
+        if (ctx->h_counters[44 + 10 * u + 8] != 0) {
+            kz_set_error(KZ_MSG_NONFINITE);
+            return KZ_ERR_NONFINITE;
+        }
+        memcpy(&unchecked[u]->max_norm, ctx->h_counters + 44 + 10 * u, 8);
+        unchecked[u]->checked = true;
+    }
+    return KZ_OK;
+}
+
+// EARLY RANGE RE-SEARCH (kz_route.h: kz_after_pass has said early_range): the grouped ranges are tried on the *n_fail rows of
+// ps.fail_list; the rows they leave are in early_left (*esc_list, *n_fail) -- or, with no room for the lists, everything as it was.
+static int kz_early_range(const KzCall& c, const KzPass& ps, const KnnFinParams& fp, int64_t cq_begin, int* n_fail, KzPoolBuf<int>& early_left,
+                          const int** esc_list, KzTally* tally) {
+    kz_ctx* ctx = c.ctx;
+    KzPoolBuf<int> fl0;
+    KzPoolBuf<double> tau0;
+    int rc = fl0.alloc(ctx, (size_t)*n_fail * sizeof(int));
+    if (rc == KZ_OK) rc = tau0.alloc(ctx, (size_t)*n_fail * 8);
+    if (rc == KZ_OK) rc = early_left.alloc(ctx, (size_t)*n_fail * sizeof(int));
+    if (rc == KZ_OK && (hipMemcpyAsync(fl0.get(), ps.fail_list, (size_t)*n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+                        hipMemcpyAsync(tau0.get(), ps.fail_tau, (size_t)*n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)) {
+        kz_set_error("kz_knn: copying the uncertified rows failed");
+        rc = KZ_ERR_HIP;
+    }
+    int n_after = *n_fail;
+    long long pairs = 0, grouped = 0;
+    const bool no_mem = rc == KZ_ERR_NOMEM;   // (no room for the lists: the next tier as before -- the step is an optimisation)
+    if (rc == KZ_OK) {
+        KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+        rc = kz_range_rescue(ctx, c.query, fp.row_map ? 0 : cq_begin, fl0.get(), tau0.get(), *n_fail, c.index, c.k, c.exclude_self, c.d_self_ids,
+                             fp.out_dist, fp.out_ind, early_left.get(), &n_after, &pairs, &grouped, true, KZ_RANGE_EARLY_PER_ROW);
+    }
+    fl0.reset();
+    tau0.reset();
+    if (no_mem) {
+        early_left.reset();
+        return KZ_OK;
+    }
+    if (rc != KZ_OK) return rc;
+    KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
+    KZ_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
+    tally->fb_ms += ms;
+    tally->n_range += *n_fail - n_after;
+    tally->n_range_group += grouped;
+    tally->n_range_pairs += pairs;
+    tally->n_fail_total += *n_fail - n_after;   // (answered by the exact kernels)
+    *n_fail = n_after;
+    *esc_list = early_left.get();
+    return KZ_OK;
+}
+
 static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index, int k,
                        int exclude_self, const int64_t* d_self_ids, KzResearch rs, double* d_dist,
                        int64_t* d_ind, kz_knn_stats* stats, KzDualPass* dual) {
@@ -830,262 +1301,71 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     if (index->metric == KZ_PRECOMPUTED) return kz_knn_precomputed(ctx, query, q_begin, q_count, index, k, d_dist, d_ind, stats);
     if (exclude_self && !d_self_ids)
         KZ_REQUIRE(query->n == index->n, "kz_knn: exclude_self needs query and index of equal length");
-    // More than 110 neighbours per query: no fused kernel keeps a list that long -- but the kernels keep ONE list per query and
-    // index RANGE, and the finalize kernel merges them.  LONG-k ROUTE (111 .. ~540 neighbours): lists of 128 over S >= k / 24
-    // index ranges (a range then holds ~24 of a query's k nearest rows on average; a range that holds more than its list does is
-    // seen by the certification -- kz_finalize_query: piece_bound -- and the row goes down the tiers), from which the finalize
-    // kernel selects and re-ranks KSEL = k + max(16, k / 8) candidates.  Beyond that (or an index too short to cut into S
-    // ranges of >= 4 tiles) the call runs entirely on the exact float64 kernels (k selection rounds over the full distance row
-    // per query: correct for any k <= n, and slow -- the reference's scikit-learn path has no such limit either,
-    // sklearn_nearest_neighbors.py:51-65; INTEGRATION.md "Deviations").
-    // The Minkowski family beyond p = 2 (KZ_MANHATTAN, KZ_CHEBYSHEV, KZ_MINKOWSKI) has no inner-product form: no MFMA kernel, the
-    // call runs entirely on the exact float64 kernels (scikit-learn's own generic DatasetsPair path is the slow one there too).
-    const bool no_gemm_form = index->metric >= KZ_MANHATTAN;
-    int KP = no_gemm_form ? 0 : kz_pick_list_len(k_eff);
-    int KSEL = 0, long_pieces = 0;
-    if (KP == 0 && !dual && !no_gemm_form) {
-        const int S = k_eff / 24 + 1 > 4 ? k_eff / 24 + 1 : 4;
-        const int sel = k_eff + (k_eff / 8 > 16 ? k_eff / 8 : 16);
-        // (finalize: 4 waves x (S 128 entries x 8 B + KSEL x 28 B) of LDS per workgroup)
-        // (float32-operand tier: two lane-half lists per range, hence at most 8 ranges = 16 lists, see kz_prepare_pass below)
-        if (S <= KZ_FIN_MAXM / 128 && 4 * kz_fin_wave_bytes(S * 128, sel) <= 160 * 1024 &&
-            4 * kz_fin_wave_bytes((S < 8 ? S : 8) * 256, sel) <= 160 * 1024 && (int64_t)index->n_tiles >= (int64_t)4 * S) {
-            KP = 128;
-            KSEL = sel;
-            long_pieces = S;
-        }
-    }
-    // SHORT-LIST ROUTE of the dual pass (13 .. 110 neighbours): the same construction the other way round -- lists
-    // of 16 over k / 5 index ranges instead of one list of 32 / 64 / 128 per query.  The K' = 16 kernel keeps three workgroups per CU
-    // and its merges short; a range that holds 16 or more of a query's nearest rows is seen by the certification (piece_bound).
-    // The caller has dealt the index tiles over the ranges (kz_knn_dual.h): near rows of a query sit in ALL ranges alike.
-    const int KP_class = KP;
-    if (dual && dual->short_pieces > 0 && KP > dual->short_kp && rs.min_kp <= dual->short_kp) {
-        KP = dual->short_kp;
-        KSEL = dual->short_ksel;
-        long_pieces = dual->short_pieces;
-    }
-    const bool exact_only = KP == 0;
-    if (exact_only) {
-        if (k_eff > KZ_EXACT_MAX_K) {
-            kz_set_error("kz_knn: k=%d exceeds the supported maximum of %d neighbours per query", k_eff, KZ_EXACT_MAX_K);
-            return KZ_ERR_UNSUPPORTED;
-        }
-        KP = 128;   // (list geometry of the scratch block only; no list kernel runs)
-    }
-    if (KP < rs.min_kp) KP = rs.min_kp < 128 ? rs.min_kp : 128;   // (list lengths are 16 / 32 / 64 / 128)
-    // rs.more_lists (escalated rows of a K' = 16 pass): MORE LISTS instead of longer ones -- a list of 16 per index range over at
-    // least four ranges, the finalize kernel selecting k + 16 of their entries.  The bound of the certification becomes the
-    // largest 16th-best key of a RANGE (a quarter of the index or less) instead of the 16th-best key of the whole index: the
-    // margin in ranks a failed row needs, with the K' = 16 kernel and a quarter of the entries to merge (14 rows of a 1M-row
-    // index: 0.75 + 0.62 ms with lists of 64 over 64 ranges).
-    int min_pieces_call = 0;
-    if (rs.more_lists) {
-        if (KP == 16 && !exact_only && KSEL == 0 && index->n_tiles >= 16) {
-            KSEL = k_eff + 48;   // (<= 60 of the >= 64 entries)
-            min_pieces_call = 4;
-        } else if (!exact_only && KP < 64) {
-            KP = 64;   // (an index of a few tiles: lists of 64 -- every re-search must ask for MORE than the pass that failed)
-        }
+    const KzCall c = {ctx, query, q_begin, q_count, index, k, exclude_self, d_self_ids, d_dist, d_ind, dual};
+    const KzRouteIn in = kz_route_in(c, k_eff);
+
+    // ---- the lists of this call (kz_route.h: long-k route, the dual pass' short lists, exact-only, what a re-search raises) ----------
+    KzRoute route;
+    if (!kz_route_lists(in, rs, &route)) {
+        kz_set_error("kz_knn: k=%d exceeds the supported maximum of %d neighbours per query", k_eff, KZ_EXACT_MAX_K);
+        return KZ_ERR_UNSUPPORTED;
     }
     if (stats) memset(stats, 0, sizeof(*stats));
     if (q_count == 0) return KZ_OK;
     KZ_HIP(hipSetDevice(ctx->device));
 
-    const int metric = index->metric;
     const int n_ytiles = (dual && dual->n_ytiles > 0) ? dual->n_ytiles : (int)index->n_tiles;
-    // (slices of the fp16 image: kz_h_nsr pads 32 .. 64 to a multiple of 8 and 65 .. 128 to a multiple of 16 -- the other tiers never
-    //  read n_slices beyond 24)
-    const int n_slices = kz_h_nsr(index->kg);
+    const int n_slices = in.n_slices;
     // rounding bound factors.  float32 operands: (d_pad + 16) 2^-24 covers the d+1 step fma chain, the float32 rounding of
     // the bias and (float64 inputs) of the operands; 1e-12 covers the float64 re-rank's own rounding.  fp16 operands: the
     // float32 accumulation of d_pad exact products + bias in an unspecified order, (n + 16) u doubled to allow for
-    // truncating internal adds (the operand rounding is measured per row, kz_pack.hip).
+    // truncating internal adds (the operand rounding is measured per row, kz_pack.hip): kz_gamma_acc_h, kz_fin_params.
     const double gamma_f32 = ((double)(index->kg * 4 + 16) * 5.9604644775390625e-08 + 1e-12) * ctx->eps_scale;
     const double gamma_bf = kz_bf16_gamma(index->kg_bf * 4) * ctx->eps_scale;
-    const double gamma_acc_h = kz_gamma_acc_h(index->kg);
 
-    // ---- tier of this call ------------------------------------------------------------------------------------------
-    const int precision = rs.prec >= 0 ? rs.prec : ctx->precision;
-    int tier = KZ_TIER_F32;
-    // (d = 497 .. 2048, 32 .. 128 slices: the fp16 tier's wide-row and parity-split builds -- and no split-bf16 tier: precision = 2 runs on float32
-    //  operands there, and so does every row the fp16 pass leaves that would have gone to the split-bf16 operands: esc_bf)
-    const bool bf_ok = n_slices >= 2 && n_slices <= 24 && query->kg == index->kg;
-    const bool esc_bf = ctx->esc_bf && bf_ok;
-    if (precision != 1 && kz_h_slices_ok(index->kg) && query->kg == index->kg) {
-        if (precision != 2) tier = KZ_TIER_H;
-        else if (bf_ok) tier = KZ_TIER_BF;
-    }
-    if (exact_only) tier = KZ_TIER_F32;   // (nothing is packed or launched for it below)
-    if (tier == KZ_TIER_H) {
+    // ---- tier of this call, and the routes of lists of 16 on the row-dealt image (kz_route.h) ---------------------------------------
+    kz_route_tier(in, rs, &route);
+    if (route.tier == KZ_TIER_H) {
         const int rc = kz_himage_ensure(query, index);
         if (rc != KZ_OK) return rc;
     }
-    // SHORT-LIST ROUTE of the ordinary kernel: as in the dual pass, lists of 16 over P index ranges instead of one list of 32 /
-    // 64 / 128 per query -- on a second image of the index whose ROWS are dealt over the ranges (kz_himage_dealt; in the caller's
-    // row order the near rows of a query may all sit in one stretch).  P lists hold at least as many entries as the list they
-    // replace; taken when a range has at least 48 tiles (measured down to 49: k = 100 on 125k index rows 15.3 -> 8.2 ms, k = 50 on
-    // 83k rows 11.3 -> 9.6, k = 26 on 60k rows 6.9 -> 6.5).  (The long lists' kernels stay for small indexes.)
-    const int KP_long = KP, KSEL_long = KSEL, pieces_long = long_pieces;   // (the list geometry this call would use without the route)
-    bool short_ord = false;
-    int route_P = 0;      // ranges the short-list route dealt the index over (kz_himage_dealt)
-    float probe_ms = 0;   // (tier probe, below: reported with the fallback time)
-    // (the long-k route up to 320 neighbours as well: k / 5 <= 64 lists of 16 instead of 4 .. 14 lists of 128 -- 50k x 500k x 200, main
-    //  kernel: k = 128 32.4 -> 12.5 ms, k = 160 35.4 -> 13.3; beyond 32 lists the finalize kernel selects by repeated arg-max)
-    const bool longk_lists = KSEL > 0 && long_pieces > 0 && KP == 128 && rs.min_kp == 0 && k_eff <= 320;
-    if (!dual && !rs.no_short && tier == KZ_TIER_H && ctx->short_ord && KP > 16 && (KSEL == 0 || longk_lists) && !exact_only) {
-        int P = (k_eff + KZ_K_DUAL_SHORT_DIV - 1) / KZ_K_DUAL_SHORT_DIV;
-        if (P < KP / 16) P = KP / 16;
-        if (rs.min_kp >= 128) P = 16;   // (a re-search that asks for lists of 128: all the ranges the finalize kernel's fast selection takes)
-        const int sel = k_eff + (KP >= 128 ? 80 : 48) < P * 16 ? k_eff + (KP >= 128 ? 80 : 48) : P * 16;
-        if (P <= (longk_lists ? 64 : 32) && (int64_t)index->n_tiles >= (int64_t)ctx->short_ord_min_tiles * P && sel >= k_eff &&
-            4 * kz_fin_wave_bytes(P * 16, sel) <= 160 * 1024) {   // (<= 512 entries: kz_rank_select<8>; up to 1024 -- 33 .. 64 lists of the long-k route -- the radix select)
+    {   // SHORT-LIST ROUTE of the ordinary kernel
+        int P = 0, sel = 0;
+        if (kz_route_short_geometry(in, rs, route, &P, &sel)) {
             const int rc = kz_himage_dealt(index, P);
-            if (rc == KZ_OK) {
-                short_ord = true;
-                KP = 16;
-                KSEL = sel;
-                long_pieces = P;
-                route_P = P;
-            } else if (rc != KZ_ERR_NOMEM) {
-                return rc;
-            }   // (no memory for the second image: the long list)
+            if (rc == KZ_OK)
+                kz_route_take_dealt(&route, P, sel, false);
+            else if (rc != KZ_ERR_NOMEM)
+                return rc;   // (no memory for the second image: the long list)
         }
     }
-    // WIDE ROUTE (round 5): many lists of 16 -- "wide_lists" (32) of them over as many ranges of the row-dealt image, the finalize
-    // kernel selecting "wide_sel" (256) of their entries.  For data whose keys are DENSE around the k-th neighbour (tight clusters:
-    // hundreds of rows of a cluster lie within the rounding bound of the k-th key).  What such a row needs to be certified is margin
-    // in RANKS -- the bound on the rows outside the candidate set must fall 2 eps below the k-th key, i.e. the set must reach down
-    // to the ~250th key -- and that costs list events and re-ranked rows, not MFMA products: the fp16 kernel with one product per
-    // multiply-add stays, where the split-bf16 tier pays three (bench.py "hard": every row failed the fp16 pass with lists worth
-    // ~100 ranks; with 256 they are certified).  Taken when the tier probe says so (below) or a caller asks for it (rs.wide_lists).
-    bool wide_route = false;
-    auto wide_geometry = [&](int P, int* sel_out) -> bool {
-        int sel = ctx->wide_sel < P * 16 ? ctx->wide_sel : P * 16;
-        if (sel < k_eff + 16) sel = k_eff + 16 < P * 16 ? k_eff + 16 : P * 16;
-        *sel_out = sel;
-        return !dual && tier == KZ_TIER_H && !exact_only && KP_long <= 128 && KSEL_long == 0 && P >= 2 && P <= 32 && P * 16 > KP_long &&
-               sel >= k_eff && (int64_t)index->n_tiles >= (int64_t)8 * P && 4 * kz_fin_wave_bytes(P * 16, sel) <= 160 * 1024;
-    };
-    auto take_wide = [&](int P) -> int {
-        int sel = 0;
-        if (!wide_geometry(P, &sel)) return KZ_ERR_UNSUPPORTED;
-        const int rc = kz_himage_dealt(index, P);
-        if (rc != KZ_OK) return rc;
-        short_ord = true;
-        wide_route = true;
-        KP = 16;
-        KSEL = sel;
-        long_pieces = P;
-        return KZ_OK;
-    };
-    if (rs.wide_lists > 0) {
-        const int rc = take_wide(rs.wide_lists);
+    if (rs.wide_lists > 0) {   // WIDE ROUTE, asked for by the caller
+        const int rc = kz_take_wide(index, in, &route, rs.wide_lists);
         if (rc != KZ_OK && rc != KZ_ERR_UNSUPPORTED && rc != KZ_ERR_NOMEM) return rc;   // (not available: this call's ordinary route)
     }
-    // TIER PROBE.  Data that is hard for fp16 as a whole (tight clusters far from the centre: nearly every row fails the first pass'
-    // certification) used to pay for a complete fp16 sweep and its finalize before anything went down the tiers (bench.py "hard":
-    // 2 x 31.6 of 150 ms per step).  A large ordinary search therefore first sends a STRIDED sample of its query rows (1024 rows since the end of round 4, 4096 before:
-    // representative whatever the row order) through the fp16 pass as an escalation-style sub-search; if more than half of them
-    // cannot be certified, the call starts at the split-bf16 tier.  The sample's results are written to their places (the main
-    // pass writes the same values again).  Cost on data that is fine: ~0.35 % of a 300k-row sweep + ~0.3 ms (230k x 230k x 128: 13.5 -> 13.2 ms
-    // with 1024 instead of 4096 rows; 200k x 400k x 200, cosine, k = 50: 32.4 -> 31.8); only top-level searches of >= 5e10 distance pairs
-    // and >= 16 probe sizes of query rows take it (C1 / C2 do not).  Option "tier_probe" = 0: off.
+    // ---- tier probe: may move the call to the wide route or down a tier, or seed its lists ------------------------------------------
+    KzTally tally;
     float* qfloor_ord = nullptr;   // seeded lists of an ordinary search (the context's buffer: nothing to release)
-    bool probed = false;           // the tier probe below has run: its verdict stands (no ladder after the fact)
-    const bool default_request = rs.prec < 0 && rs.min_kp == 0 && !rs.more_lists && rs.wide_lists == 0;   // (a top-level call's)
-    if (tier == KZ_TIER_H && !dual && default_request && !exact_only && ctx->tier_probe > 0 && ctx->esc_bf &&
-        q_count >= (int64_t)16 * ctx->tier_probe && ctx->chunk_rows == 0 &&
-        ((double)q_count * (double)index->n >= ctx->probe_min_pairs ||
-         2.0 * (double)q_count * (double)index->n * (double)(index->kg * 4) / 1e12 >= KZ_K_PROBE_MIN_MS)) {
-        const int n_probe = ctx->tier_probe;
-        KzPoolBuf<int> plist;
-        int rc = plist.alloc(ctx, (size_t)n_probe * sizeof(int));
+    bool probed = false;           // the tier probe has run: its verdict stands (no ladder after the fact)
+    if (kz_probe_wanted(in, rs, route, q_count)) {
+        const int rc = kz_tier_probe(c, in, &route, &qfloor_ord, &tally.probe_ms);
         if (rc != KZ_OK) return rc;
-        hipLaunchKernelGGL(kz_strided_rows_kernel, dim3((unsigned)((n_probe + 255) / 256)), dim3(256), 0, ctx->stream, plist.get(), n_probe,
-                           q_count / n_probe);
-        kz_knn_stats stp;
-        float pms = 0;
-        KzResearch probe_rs;
-        probe_rs.prec = 0;
-        rc = kz_escalate_rows(ctx, query, q_begin, plist.get(), n_probe, index, k, exclude_self, d_self_ids, probe_rs, d_dist, d_ind, &stp, &pms);
-        if (rc != KZ_OK) return rc;
-        probe_ms = pms;
         probed = true;
-        // (the verdict counts the rows that left the probe's FIRST pass uncertified, once each -- not the cumulative count of the
-        //  levels below it, which counted a row that went two levels down twice)
-        bool hard = (int64_t)stp.n_first_pass_fail * 2 > n_probe;
-        if ((int64_t)stp.n_first_pass_fail * 8 > n_probe && ctx->wide_lists >= 2) {
-            // LADDER: before better operands, more margin in ranks on the SAME operands -- the probe rows again through the wide
-            // route.  Tried from an eighth of the probe uncertified on: re-searching a quarter of the rows one by one costs more
-            // than the sweep itself (300 k x 300 k x 96, clusters of very different spread, k = 10: 24 % of the rows re-searched,
-            // 24 ms of sweep in a 93 ms call).  Taken when at most a quarter of the probe stays uncertified there AND that is less
-            // than half of what the ordinary lists left.
-            int sel = 0;
-            if (wide_geometry(ctx->wide_lists, &sel)) {
-                kz_knn_stats stw;
-                float wms = 0;
-                rc = kz_escalate_rows(ctx, query, q_begin, plist.get(), n_probe, index, k, exclude_self, d_self_ids, kz_research_wide(ctx->wide_lists),
-                                      d_dist, d_ind, &stw, &wms);
-                if (rc != KZ_OK) return rc;
-                probe_ms += wms;
-                if ((int64_t)stw.n_first_pass_fail * 4 <= n_probe && (int64_t)stw.n_first_pass_fail * 2 < stp.n_first_pass_fail &&
-                    take_wide(ctx->wide_lists) == KZ_OK)
-                    hard = false;
-            }
-        }
-        plist.reset();
-        if (hard) {
-            tier = bf_ok ? KZ_TIER_BF : KZ_TIER_F32;   // (wide rows: no split-bf16 operands, the float32 ones)
-            // (data this hard for fp16 is hard for the split-bf16 operands, too, wherever the keys are dense: lists of 64 from the
-            //  start -- 300k x 300k x 96, k = 10, clusters of very different spread: rows searched again 135 k -> 51 k, call 170 -> 110 ms)
-            if (KSEL == 0 && KP < 64) KP = 64;
-            if (short_ord) {   // (the other tiers' kernels keep one list of K' per query)
-                short_ord = false;
-                KP = KP_long;
-                KSEL = KSEL_long;
-                long_pieces = pieces_long;
-            }
-        } else if (ctx->list_floor && !wide_route) {
-            // POPULATION FLOOR (above kz_escalate_rows): the probe's results are the model's input
-            double model[3];
-            bool ok = false;
-            rc = kz_floor_model(ctx, d_dist, query->himg->rowq + q_begin * 3, n_probe, q_count / n_probe, k, metric, model, &ok);
-            if (rc != KZ_OK) return rc;
-            const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
-            if (ok) rc = kz_floor_buf(ctx, (size_t)n_pad * 4, &qfloor_ord);
-            if (rc != KZ_OK) return rc;
-            if (qfloor_ord) {
-                hipLaunchKernelGGL(kz_floor_rows_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, (const int*)nullptr, query->n,
-                                   n_pad, query->himg->rowq, index->himg->d_max, index->himg->center->d_scale, model[0], model[1], model[2],
-                                   ctx->eps_scale, gamma_acc_h, qfloor_ord);
-                KZ_HIP(hipGetLastError());
-            }
-        }
     }
-    // 64 QUERIES PER WAVE (kz_knn_h64.h): K' = 16 sweeps of 4 .. 13 slices -- half the LDS fragment reads per MFMA and half the
-    // LDS-DMA volume per query of the 32-query kernel at two waves per SIMD instead of three; a work item = a unit of two query
-    // tiles (tpw = 2).  Measured (profiles/r04_ablation.md section 2): the shared sweep at 13 slices -1.5 % (250k x 1M x 200: 90.6 ->
-    // 89.2 ms), the ordinary kernel +0.8 % there, +8 % at 8 slices, and a launch of fewer than ~4 rounds of units does not fill the
-    // chip (100k x 100k: +30 %).  Option "h_q64": 2 (default) = the shared sweep from 9 slices on over >= 4 rounds of units,
-    // 1 = wherever the kernel is built for (tests), 0 = never.
-    bool q64_ok = false;
-    if (tier == KZ_TIER_H && KP == 16 && !exact_only) {   // (is there a 64-query build for these rows?  The resolver may come back empty)
-        KzSweepKernel k64;
-        const int rc = kz_sweep_kernel(KZ_TIER_H, dual != nullptr, true, KP, n_slices, &k64, true);
+    bool q64 = false;   // the 64-queries-per-wave build of the fp16 kernel for this call
+    {
+        const int rc = kz_q64_wanted(c, route, n_slices, &q64);
         if (rc != KZ_OK) return rc;
-        q64_ok = k64.fn != nullptr;
     }
-    const bool q64 = q64_ok && !(dual && dual->no_q64) && (ctx->h_q64 == 1 || (ctx->h_q64 == 2 && dual && n_slices >= 9 &&
-                                                     (q_count + 2 * KZ_TILE - 1) / (2 * KZ_TILE) >= (int64_t)4 * 2 * ctx->n_cus));
     const int tpw_h = q64 ? 2 : 1;   // query tiles per workgroup of the fp16 kernel this call runs
     // The sweep kernel of the call's tier and the work items a round of it may hold: resolved (and its occupancy queried) once, and
-    // again only when the call goes down a tier.  The one choice of kernel: every launch below starts `kern`.
+    // again only when the call goes down a tier (after kz_route_next_tier: the list length may have changed with it).  The one choice
+    // of kernel: every launch below starts `kern`.
     KzSweepKernel kern;
     int kern_tier = -1, kern_slots = 0;
     auto kernel_for = [&](int t) -> int {
-        if (kern_tier == t && kern.KP == KP) return KZ_OK;
-        int rc0 = kz_sweep_kernel(t, dual != nullptr, q64, KP, n_slices, &kern);
+        if (kern_tier == t && kern.KP == route.cur.KP) return KZ_OK;
+        int rc0 = kz_sweep_kernel(t, dual != nullptr, q64, route.cur.KP, n_slices, &kern);
         if (rc0 != KZ_OK) return rc0;
         int blocks_per_cu = 1;
         rc0 = kz_sweep_occupancy(ctx, kern, &blocks_per_cu);
@@ -1097,481 +1377,131 @@ static int kz_knn_impl(kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q
     // query rows are processed in chunks so that the candidate lists stay below ~1 GiB: 524288 rows for K' >= 64, up to four
     // times as many for shorter lists (1 M x 250 k, K' = 16: one launch instead of two -- one tail round, one read-back, one
     // re-search of the uncertified rows)
-    const int KP_mem = KP_class > KP ? KP_class : KP;   // (short-list route: several lists of 16 -- the chunk of the replaced list length)
+    // (taken after the probe has possibly changed the route, like first_tier)
+    const int KP_mem = route.KP_class > route.cur.KP ? route.KP_class : route.cur.KP;   // (short-list route: several lists of 16 -- the chunk of the replaced list length)
     // (the wide route keeps 32 lists of 16 per query -- 4 KiB: 524288 rows)
-    int64_t max_rows_per_chunk = kz_rows_per_chunk(ctx, KP_mem, wide_route);   // (halved below where a chunk's lists would pass 2^32 entries)
+    int64_t max_rows_per_chunk = kz_rows_per_chunk(ctx, KP_mem, route.wide_route);   // (halved by kz_chunk_plan where a chunk's lists would pass 2^32 entries)
     if (dual && dual->raw_lists && q_count > max_rows_per_chunk) {
         kz_set_error("kz_knn: internal: a raw-list pass must be one launch");
         return KZ_ERR_INVALID;
     }
-    double main_ms = 0, fin_ms = 0, fb_ms = 0;   // (the tier probe's time is reported under its own field, kz_knn_stats.probe_ms)
-    int64_t n_fail_total = 0, n_escalated = 0, n_first_fail = 0, n_spec = 0, n_range = 0, n_range_pairs = 0, n_range_group = 0;
-    double max_err_ratio = 0.0;
-    int last_splits = 1, last_blocks = 0, first_tier = tier;
+    const int first_tier = route.tier;
     for (int64_t c0 = 0; c0 < q_count;) {
-        if (tier == KZ_TIER_BF) {
-            int rc = kz_matrix_image_bf(query);
-            if (rc == KZ_OK) rc = kz_matrix_image_bf(index);
-            if (rc != KZ_OK) return rc;
-        } else if (tier == KZ_TIER_F32 && !exact_only) {
-            int rc = kz_matrix_image_f32(query);
-            if (rc == KZ_OK) rc = kz_matrix_image_f32(index);
-            if (rc != KZ_OK) return rc;
-        }
-        if (tier == KZ_TIER_H && short_ord && long_pieces >= 2) {
-            // (a re-search of the previous chunk's uncertified rows may have selected -- or packed -- the index dealt over another
-            //  number of ranges: this route's own image again; cached, two are kept)
-            // (any failure ends the call: launching on whatever image the last sub-search selected would certify against the wrong
-            //  range layout; unreachable while a slot exists once the route is chosen)
-            const int rcd = kz_himage_dealt(index, wide_route || rs.wide_lists > 0 ? long_pieces : route_P);
-            if (rcd != KZ_OK) {
-                if (rcd == KZ_ERR_NOMEM) kz_set_error("kz_knn: out of device memory for the row-dealt image of the index");
-                return rcd;
-            }
-        }
-        {
-            const int rck = kernel_for(tier);
-            if (rck != KZ_OK) return rck;
-        }
-        const int slots = kern_slots;
-        const int64_t cq_begin = q_begin + c0;
-        const int qt0 = (int)(cq_begin / KZ_TILE);
-        int64_t cq_count = 0;
-        int n_qtiles = 0, force_pieces = 0, max_pieces = 0;
-        KzPlan pl;
-        // ---- schedule: which workgroup sweeps which (query tile, index-tile range): kz_prepare_pass above --------------
-        for (;;) {
-            cq_count = (q_count - c0 < max_rows_per_chunk) ? (q_count - c0) : max_rows_per_chunk;
-            n_qtiles = (int)((cq_begin + cq_count - 1) / KZ_TILE) - qt0 + 1;
-            // (long-k route: exactly long_pieces index ranges per query tile, one round)
-            force_pieces = (tier == KZ_TIER_F32 && long_pieces > 8) ? 8 : long_pieces;
-            if (tier == KZ_TIER_H && short_ord && force_pieces > 0) {
-                // a SMALL launch on the short-list route (a re-search of a few hundred uncertified rows, a probe): P ranges per query
-                // tile leave most of the chip idle (216 rows x 10 ranges: 20 workgroups sweeping 390 tiles each, 1.98 ms) -- every
-                // range is cut further, s P lists of 16 per query (the finalize kernel selects from any number of lists), as long as
-                // a piece keeps at least 8 tiles and a query at most KZ_MAX_PIECES (128) lists
-                const int units = (n_qtiles + tpw_h - 1) / tpw_h;
-                int sub = slots / (units * force_pieces);
-                if (sub > KZ_MAX_PIECES / force_pieces) sub = KZ_MAX_PIECES / force_pieces;
-                if (sub > n_ytiles / (8 * force_pieces)) sub = n_ytiles / (8 * force_pieces);
-                if (sub > 1 && 4 * kz_fin_wave_bytes(force_pieces * sub * 16, KSEL) <= 160 * 1024) force_pieces *= sub;
-            }
-            max_pieces = kz_max_pieces(KP, tier == KZ_TIER_F32 ? 2 : 1);
-            if (dual && dual->max_entries > 0 && max_pieces > dual->max_entries / KP) max_pieces = dual->max_entries / KP;
-            // The kernels address a launch's lists with 32-bit element offsets: a chunk whose plan would pass 2^32 entries (K' = 16,
-            // 2 M rows over 128 ranges) is halved.
-            kz_plan_tier_pass(ctx, n_qtiles, n_ytiles, slots, max_pieces, KP, tier, tier == KZ_TIER_H ? tpw_h : 1, force_pieces, min_pieces_call, &pl);
-            if (pl.list_elems < ((size_t)1 << 32) || cq_count <= 8 * KZ_TILE || (dual && dual->raw_lists)) break;
-            max_rows_per_chunk = ((cq_count / 2 + KZ_TILE - 1) / KZ_TILE) * KZ_TILE;
-        }
+        int rc = kz_tier_images(c, rs, route);
+        if (rc != KZ_OK) return rc;
+        rc = kernel_for(route.tier);
+        if (rc != KZ_OK) return rc;
+        const int tier = route.tier, KP = route.cur.KP, slots = kern_slots;
+        KzChunk ch;
+        kz_chunk_plan(c, route, slots, tpw_h, n_ytiles, c0, &max_rows_per_chunk, &ch);
         KzPass ps;
         // (range-0 bootstrap: the short-list routes of the ordinary 32-query kernel, from four ranges on)
-        const bool boot = tier == KZ_TIER_H && short_ord && !dual && !q64 && force_pieces >= 4;
-        int rc = kz_prepare_pass(ctx, pl, n_ytiles, slots, tier, cq_count, &ps, tier == KZ_TIER_H ? tpw_h : 1, boot);
+        const bool boot = tier == KZ_TIER_H && route.short_ord && !dual && !q64 && ch.force_pieces >= 4;
+        rc = kz_prepare_pass(ctx, ch.pl, n_ytiles, slots, tier, ch.cq_count, &ps, tier == KZ_TIER_H ? tpw_h : 1, boot);
         if (rc != KZ_OK) return rc;
-        const KzListLayout& lay = ps.lay;
-        const int W = ps.W;
-        float* out_key = ps.out_key;
-        int* out_idx = ps.out_idx;
-        int* fail_list = ps.fail_list;
-        int4* d_work = ps.d_work;
         int* fail_count = ctx->d_counters + 8;
         KZ_HIP(hipMemsetAsync(fail_count, 0, 4 * sizeof(int), ctx->stream));  // fail counter, (unused), error-ratio bits
         KzPoolBuf<float> boot_floor;   // (this chunk's range-0 floor, if any: the finalize kernel must know it)
         KzPoolBuf<unsigned long long> stamp_buf;   // (diagnostic "abl_stamp")
-        KnnCandParams cp;
-        memset(&cp, 0, sizeof(cp));
-        if (tier == KZ_TIER_H) {
-            cp.qpack = (const float*)query->himg->packed;
-            cp.ypack = (const float*)(short_ord ? index->himg->dealt_packed : index->himg->packed);
-            cp.ybias = short_ord ? index->himg->dealt_bias : index->himg->bias;
-        } else {
-            cp.qpack = tier == KZ_TIER_BF ? (const float*)query->packed_bf : query->packed;
-            cp.ypack = tier == KZ_TIER_BF ? (const float*)index->packed_bf : index->packed;
-            cp.ybias = index->bias;
-        }
-        cp.work = d_work;
-        cp.qt0 = qt0;
-        cp.n_ytiles = n_ytiles;
-        cp.n_qtiles = n_qtiles;
-        cp.lay = lay;
-        cp.kg = index->kg;
-        cp.out_key = out_key;
-        cp.out_idx = out_idx;
-        if (tier == KZ_TIER_H && !dual) cp.qfloor = qfloor_ord;
-        KZ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-        if (exact_only) {
-            // every row of the chunk goes to the exact kernels: the "fail list" is 0 .. cq_count-1
-            hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((cq_count + 255) / 256)), dim3(256), 0, ctx->stream, fail_list, (int)cq_count);
-            KZ_HIP(hipGetLastError());
-        } else if (tier == KZ_TIER_H && dual) {
-            cp.qpack = dual->qpack;
-            cp.ypack = dual->ypack;
-            cp.ybias = dual->ybias;
-            cp.theta = dual->theta;
-            cp.qnbias = dual->qnbias;
-            cp.qfloor = dual->qfloor;
-            cp.log_keys = dual->log_keys;
-            cp.log_meta = dual->log_meta;
-            cp.log_cnt = dual->log_cnt;
-            cp.log_cap = dual->log_cap;
-            rc = kz_sweep_launch(ctx, kern, cp, W);
-        } else if (tier == KZ_TIER_H && boot && ps.W0 > 0 && ps.W0 < W) {
-            // range 0 of every query tile, the floor off its lists, then the other ranges
-            rc = kz_sweep_launch(ctx, kern, cp, ps.W0);
-            if (rc != KZ_OK) return rc;
-            const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
-            rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);   // (a buffer of this chunk: escalated sub-searches boot too)
-            if (rc != KZ_OK) return rc;
-            hipLaunchKernelGGL(kz_boot_floor_kernel, dim3((unsigned)((cq_count + 255) / 256)), dim3(256), 0, ctx->stream, out_key, out_idx, lay, KP,
-                               cq_begin - (int64_t)qt0 * KZ_TILE, cq_begin, cq_count, cp.qfloor, boot_floor.get());
-            KZ_HIP(hipGetLastError());
-            cp.qfloor = boot_floor.get();
-            cp.work = d_work + ps.W0;
-            rc = kz_sweep_launch(ctx, kern, cp, W - ps.W0);
-            cp.work = d_work;
-        } else if (tier == KZ_TIER_H && !q64) {
-            if ((ctx->abl & 2) && getenv("KZ_STAMP_FILE")) {   // (diagnostic: a -DKZ_ABL_STAMP build of the fp16 units fills it)
-                rc = stamp_buf.alloc(ctx, (size_t)W * (16 + 1024));
-                if (rc != KZ_OK) return rc;
-                KZ_HIP(hipMemsetAsync(stamp_buf.get(), 0, (size_t)W * (16 + 1024), ctx->stream));
-                cp.log_meta = stamp_buf.get();
-                cp.log_keys = stamp_buf.get() + 2 * (size_t)W;
-            }
-            rc = kz_sweep_launch(ctx, kern, cp, W);
-            cp.log_meta = nullptr;
-            cp.log_keys = nullptr;
-            if (rc == KZ_OK && (ctx->abl & 1) && !short_ord && ps.lay.n_regions == 1 && ps.lay.pieces[0] == 1) {
-                // DIAGNOSTIC ("abl_refloor", profiles/r06_event_ablation.md): the same sweep AGAIN with every list starting at the
-                // threshold it ENDED on (the K'-th best key of the first sweep's list): K' insertions per query instead of
-                // K' (1 + ln(n / K')) -- the time any seeding of the lists could at best reach.  The second sweep is the one timed.
-                const int64_t n_pad = (int64_t)query->n_tiles * KZ_TILE;
-                rc = boot_floor.alloc(ctx, (size_t)n_pad * 4);
-                if (rc != KZ_OK) return rc;
-                hipLaunchKernelGGL(kz_boot_floor_kernel, dim3((unsigned)((cq_count + 255) / 256)), dim3(256), 0, ctx->stream, out_key, out_idx, lay, KP,
-                                   cq_begin - (int64_t)qt0 * KZ_TILE, cq_begin, cq_count, cp.qfloor, boot_floor.get());
-                // (one ulp below: entries equal to the threshold must get in again)
-                hipLaunchKernelGGL(kz_floor_nudge_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, boot_floor.get(), n_pad);
-                KZ_HIP(hipGetLastError());
-                cp.qfloor = boot_floor.get();
-                KZ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-                rc = kz_sweep_launch(ctx, kern, cp, W);
-            }
-        } else   // (the 64-query kernel, the split-bf16 and the float32 operands: one plain launch)
-            rc = kz_sweep_launch(ctx, kern, cp, W);
+        rc = kz_chunk_sweep(c, route, kern, ch, ps, q64, boot, qfloor_ord, n_ytiles, boot_floor, stamp_buf);
         if (rc != KZ_OK) return rc;
         if (dual && tier != KZ_TIER_H) dual->broken = 1;   // this chunk's pairs were not scanned for events
         KZ_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
         if (dual) {
-            dual->lists_key = out_key;
-            dual->lists_idx = out_idx;
-            dual->lists_lay = lay;
+            dual->lists_key = ps.out_key;
+            dual->lists_idx = ps.out_idx;
+            dual->lists_lay = ps.lay;
             dual->lists_KP = KP;
         }
-        if (dual && dual->post_sweep && !dual->broken && c0 + cq_count >= q_count) {
+        if (dual && dual->post_sweep && !dual->broken && c0 + ch.cq_count >= q_count) {
             dual->post_called = 1;
             rc = dual->post_sweep(dual->post_user);
             if (rc != KZ_OK) return rc;
         }
 
+        // ---- finalize: select, re-rank in float64, certify ---------------------------------------------------------------------------
         KnnFinParams fp;
-        memset(&fp, 0, sizeof(fp));
-        fp.in_key = out_key;
-        fp.in_idx = out_idx;
-        fp.lay = lay;
-        fp.KP = KP;
-        fp.KSEL = KSEL;
-        fp.list_row0 = cq_begin - (int64_t)qt0 * KZ_TILE;
-        fp.q_begin = cq_begin;
-        fp.q_count = cq_count;
-        fp.qraw = query->raw;
-        fp.yraw = index->raw;
-        fp.qsqn = query->sqn;
-        fp.ysqn = index->sqn;
-        fp.n_i = index->n;
-        fp.d = (int)index->d;
-        fp.metric = metric;
-        fp.k = k;
-        fp.exclude_self = exclude_self ? 1 : 0;
-        fp.self_ids = d_self_ids;
-        fp.gamma = tier == KZ_TIER_BF ? gamma_bf : gamma_f32;
-        fp.ystats = index->d_stats;
-        fp.tier_h = tier == KZ_TIER_H ? 1 : 0;
-        if (fp.tier_h) {
-            fp.eps_mult = ctx->eps_scale;
-            fp.gamma_acc = gamma_acc_h;
-            fp.q_rowq = query->himg->rowq;
-            fp.y_hmax = index->himg->d_max;
-            fp.hscale = index->himg->center->d_scale;
-        }
-        fp.out_dist = d_dist + c0 * (int64_t)k;
-        fp.out_ind = d_ind + c0 * (int64_t)k;
-        if (tier == KZ_TIER_H && short_ord) fp.idx_map = index->himg->dealt_perm;   // the lists hold rows of the dealt index image
-        if (tier == KZ_TIER_H && !dual) fp.list_floor = boot_floor.get() ? boot_floor.get() : qfloor_ord;
-        if (tier == KZ_TIER_H && dual) {
-            fp.idx_map = dual->perm;      // the lists hold rows of the sorted index image
-            fp.row_map = dual->row_map;   // the chunk is a range of IMAGE rows: results and failures go by matrix row
-            fp.list_floor = dual->qfloor;
-            fp.out_dist = d_dist;
-            fp.out_ind = d_ind;
-        }
-        fp.fail_count = fail_count;
-        fp.fail_list = fail_list;
-        fp.fail_tau = ps.fail_tau;
-        fp.err_ratio_bits = (unsigned long long*)(ctx->d_counters + 10);
-        if (fp.tier_h && metric == KZ_COSINE && (fp.KSEL > 0 ? fp.KSEL : KP) > 160 && !(dual && dual->raw_lists)) {
-            // (hundreds of re-ranked candidates per query: the normalised float64 rows of the index, built once -- kz_pack.hip)
-            rc = kz_matrix_norm64(index);
-            if (rc != KZ_OK) return rc;
-            fp.ynorm64 = index->norm64;
-        }
-        if (!exact_only && !(dual && dual->raw_lists)) {   // (raw lists: the caller's hook has read them; nothing is finalized)
-            rc = kz_launch_finalize(ctx, fp, lay, KP, cq_count, index->dtype);
-            if (rc != KZ_OK) return rc;
-        }
+        rc = kz_chunk_finalize(c, route, ch, ps, c0, tier == KZ_TIER_BF ? gamma_bf : gamma_f32, boot_floor.get() ? boot_floor.get() : qfloor_ord, &fp);
+        if (rc != KZ_OK) return rc;
         boot_floor.reset();   // (stream-ordered: the launches above have it)
         KZ_HIP(hipGetLastError());
         KZ_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-        // matrices created from device rows have not had their finiteness verdict read yet (kz_matrix_create waits for
-        // nothing): it rides on this call's read-back
-        kz_matrix* unchecked[2] = {query->checked ? nullptr : query, (index->checked || index == query) ? nullptr : index};
-        int spec_R = 0;   // rows the speculative launches below covered
-        hipError_t es;
-        {
-            // SPECULATIVE RESCUE (above kz_escalate_rows): the exact kernels for up to R uncertified rows, before the count is known
-            KzSpec spec;   // (its buffers go right after the read-back -- stream-ordered: the launches that used them are on the stream)
-            if (!exact_only && !(dual && dual->raw_lists) && tier != KZ_TIER_F32) {
-                const int R = kz_spec_rows(ctx, index, k_eff);
-                if (R > 0) {
-                    rc = kz_spec_rescue(ctx, spec, R, query, fp.row_map ? 0 : cq_begin, fail_list, fail_count, index, k, exclude_self, d_self_ids,
-                                        fp.out_dist, fp.out_ind);
-                    if (rc != KZ_OK) return rc;
-                    if (spec.R > 0) KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-                }
-            }
-            KZ_HIP(hipMemcpyAsync(ctx->h_counters + 8, fail_count, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            for (int u = 0; u < 2; ++u)
-                if (unchecked[u])
-                    KZ_HIP(hipMemcpyAsync(ctx->h_counters + 44 + 10 * u, unchecked[u]->d_stats, 40, hipMemcpyDeviceToHost, ctx->stream));
-            es = hipStreamSynchronize(ctx->stream);
-            spec_R = spec.R;
-        }
-        KZ_HIP(es);
-        if (stamp_buf.get()) {   // (diagnostic: start / end of every workgroup of the sweep, in work-table order, appended to the file)
-            std::vector<unsigned long long> hs((size_t)W * 130);
-            KZ_HIP(hipMemcpy(hs.data(), stamp_buf.get(), (size_t)W * (16 + 1024), hipMemcpyDeviceToHost));
-            stamp_buf.reset();
-            if (FILE* f = fopen(getenv("KZ_STAMP_FILE"), "a")) {
-                fprintf(f, "# launch W=%d n_qtiles=%d n_ytiles=%d slices=%d\n", W, n_qtiles, n_ytiles, n_slices);
-                for (int w = 0; w < W; ++w) {
-                    fprintf(f, "%d %llu %llu", w, hs[2 * (size_t)w], hs[2 * (size_t)w + 1]);
-                    if (w < 8 || w % 97 == 0)   // (per-tile stamps of a few workgroups: the first 64 tiles, then every 16th)
-                        for (int t = 0; t < 128; ++t) fprintf(f, " %llu", hs[2 * (size_t)W + (size_t)w * 128 + t]);
-                    fprintf(f, "\n");
-                }
-                fclose(f);
-            }
-        }
-        for (int u = 0; u < 2; ++u) {
-            if (!unchecked[u]) continue;
-            if (ctx->h_counters[44 + 10 * u + 8] != 0) {
-                kz_set_error(KZ_MSG_NONFINITE);
-                return KZ_ERR_NONFINITE;
-            }
-            memcpy(&unchecked[u]->max_norm, ctx->h_counters + 44 + 10 * u, 8);
-            unchecked[u]->checked = true;
-        }
-        int n_fail = exact_only ? (int)cq_count : ctx->h_counters[8];
-        n_first_fail += n_fail;
+
+        // ---- read-back: how many rows are left, and where they go (kz_route.h: kz_after_pass) ----------------------------------------
+        int spec_R = 0;   // rows the speculative launches covered
+        rc = kz_chunk_readback(c, route, ch, ps, fp, k_eff, n_ytiles, n_slices, stamp_buf, &spec_R);
+        if (rc != KZ_OK) return rc;
+        int n_fail = route.exact_only ? (int)ch.cq_count : ctx->h_counters[8];
+        tally.n_first_fail += n_fail;
         {
             double ratio;
             memcpy(&ratio, ctx->h_counters + 10, 8);
-            if (ratio > max_err_ratio) max_err_ratio = ratio;
+            if (ratio > tally.max_err_ratio) tally.max_err_ratio = ratio;
         }
         float ms = 0;
         KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        main_ms += ms;
+        tally.main_ms += ms;
         KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-        fin_ms += ms;
-        last_splits = lay.pieces[0];
-        last_blocks = W;
-        // More than a quarter of the chunk's rows uncertified: this data needs better operands -- the REST of the call starts at
-        // the next tier (not in the dual pass: its kernel exists for the fp16 tier only).  THIS chunk's uncertified rows go down
-        // like any others: searching a quarter (or all) of the rows again at the next tier is never more work than redoing the
-        // whole chunk there, which is what an earlier version did -- and abandoned the shared sweep altogether (500k x 62.5k, k = 50, 40
-        // tight clusters: 579 -> 540 ms cluster by cluster, 528 -> 348 ms shuffled; nearly every row of that set needs better operands).
-        int tier_next = tier;
-        if (!dual && tier != KZ_TIER_F32 && (int64_t)n_fail * 4 > cq_count)
-            tier_next = (tier == KZ_TIER_H && esc_bf && long_pieces == 0) ? KZ_TIER_BF : KZ_TIER_F32;
-        // A HANDFUL of rows left by the split-bf16 operands skips the float32-operand kernel: that kernel sweeps the whole index for
-        // one query tile in at most eight pieces -- 2.2 ms on 300 k rows of d = 64 whatever the row count -- while the exact kernels
-        // cost ~35 us a row there (both scale with n d): bench.py "hard", ~20 rows per direction and step: 60.6 -> see r05_notes.
-        // (... and so do a few hundred to a few thousand rows where the range re-search applies and the index is large: that kernel's
-        //  sweep of the whole index per launch -- 3 ms on 200 k x 200 -- against one fp16 sweep of the failed rows and their pairs;
-        //  the tier probe's 1 024 rows paid 2 x 3 ms there on hard data)
-        const bool range_direct = tier == KZ_TIER_BF && !dual && !exact_only && n_fail >= KZ_RANGE_MIN_ROWS && n_fail < KZ_RG_MIN_ROWS &&
-                                  index->n >= 65536 && kz_range_shapes_ok(ctx, query, index);
-        const bool exact_direct = (tier == KZ_TIER_BF && !dual && n_fail > 0 && n_fail <= KZ_K_EXACT_DIRECT_ROWS) || range_direct;
-        // (the speculative launches behind the finalize kernel have answered them all)
-        const bool rescued = spec_R > 0 && n_fail > 0 && n_fail <= spec_R;
-        if (rescued) {
+        tally.fin_ms += ms;
+        tally.last_splits = ps.lay.pieces[0];
+        tally.last_blocks = ps.W;
+        const KzAfterPass ap = kz_after_pass(in, rs, route, probed, n_fail, ch.cq_count, spec_R);
+        if (ap.rescued) {
             KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-            fb_ms += ms;
-            n_spec += n_fail;
+            tally.fb_ms += ms;
+            tally.n_spec += n_fail;
         }
-        if (tier != KZ_TIER_F32 && n_fail > 0 && !exact_direct && !rescued) {
-            // Escalate only the uncertified rows: gather them into a dense query block and search it again -- fp16 tier
-            // with lists shorter than 128: same operands, lists four times as long (no new image of the index: 14 rows
-            // of a 1M-row index cost 0.4 ms this way against 7 ms for packing its float32 image); otherwise the split-bf16
-            // operands (from the fp16 tier), then the float32-operand kernel.  The inner call sends its own uncertified rows further down (float32 operands,
-            // exact float64 kernels).  Results are scattered back.
-            // (more than half of the chunk uncertified: the fp16 operands are the wrong tool for this data, longer lists of the
-            //  same keys will not help most of them -- straight to the split-bf16 operands)
-            // (... and so are the rows the WIDE route leaves: it already is the fp16 tier's largest margin in ranks)
-            const bool fp16_hard = tier == KZ_TIER_H && ctx->esc_bf && (wide_route || ((int64_t)n_fail * 2 > cq_count && (long_pieces == 0 || short_ord || (dual && dual->short_pieces > 0))));
-            const bool widen = tier == KZ_TIER_H && KP < 128 && !fp16_hard;
-            // (short-list route: the rows it cannot certify are mostly the ones a list of K' could not certify either -- they go
-            //  where that list's failures would have gone, lists four times K', not through a list of K' first)
-            const int KP_esc = short_ord ? KP_long : (KP_class > KP ? KP_class : KP);
-            // (... when they are many: lists of 128 -- which the callee turns into 16 lists of 16 on the dealt image when the index
-            //  is large: more ranges than this pass had, so not the same search again.  A handful -- uniform data: ~2e-4 of the
-            //  queries, those whose near rows crowd one range -- is certified by ONE list of K' at a quarter of the cost: 500k x
-            //  500k, k = 50: 4.7 -> 1.7 ms per step)
-            const bool crowding_only = KP_esc > KP && n_fail <= KZ_ESC_SHORT_MAX_ROWS;
-            // what the re-search asks for: (operand tier, list length) -- never what this pass just tried
-            KzResearch next;
-            if (!widen) {   // fp16 with its longest lists, or fp16 altogether, has failed: better operands, this call's own list length
-                next.prec = (tier == KZ_TIER_H && esc_bf && (long_pieces == 0 || fp16_hard)) ? 2 : 1;
-                // (the float32 operands are the LAST approximate tier and their a-priori bound is the loosest: with this call's own
-                //  list length -- 16 for k = 10 -- the K'-th key lies a handful of keys below the k-th and inside the bound wherever
-                //  the keys are dense; lists of 64 certify such rows instead of handing them to the exact kernels at ~60 us a row:
-                //  300k x 300k x 96, clusters of very different spread: 9 968 rows to the exact kernels and 726 ms per call before, none and
-                //  169 ms now; lists of 128 for every call: bench.py "hard", k = 50, 118 -> 225 ms -- its lists of 64 were long enough)
-                next.min_kp = ((next.prec == 1 || wide_route) && KP_class < 64) ? 64 : 0;
-            } else if (KP == 16 && KSEL == 0 && n_fail <= KZ_ESC_SHORT_MAX_ROWS) {
-                next.prec = 0;
-                next.more_lists = true;   // a handful of rows of a K' = 16 pass: more lists of 16
-            } else {
-                next.prec = 0;
-                next.min_kp = crowding_only ? KP_esc : (KP_esc * 4 < 128 ? KP_esc * 4 : 128);
-                // (after a short-list pass: one LONG list -- unless many rows failed and the callee can still add ranges)
-                next.no_short = KP_esc > KP && (crowding_only || long_pieces >= 16);
-            }
-            // EARLY RANGE RE-SEARCH (kz_range.h "grouped"): thousands of rows the split-bf16 operands could not certify are, on data
-            // with clusters far tighter than its extent, rows the float32 operands cannot certify either -- they used to cost a sweep
-            // of the whole index there (85 of 180 ms per direction, 200 k x 200 k x 200) before the exact kernels got them.  The
-            // groups are tried HERE: rows that share a representative's range are answered by the exact kernels at once; the others
-            // go on to the next tier as before.
+        if (ap.escalate) {
+            // the uncertified rows again, as a dense block, with what ap.next asks for; the rest of the call at ap.tier_next
             KzPoolBuf<int> early_left;
-            const int* esc_list = fail_list;
-            // (NOT on what an fp16 pass leaves: rows that only lack margin in ranks -- 40 tight clusters, 100 k x 101 k x 128 -- are
-            //  cheaper on the ladder's wide route than as 2.4e8 exact pairs: 26.5 -> 33.7 ms with the groups tried there, removed)
-            if (tier == KZ_TIER_BF && !dual && n_fail >= KZ_RG_MIN_ROWS && kz_range_shapes_ok(ctx, query, index)) {
-                KzPoolBuf<int> fl0;
-                KzPoolBuf<double> tau0;
-                rc = fl0.alloc(ctx, (size_t)n_fail * sizeof(int));
-                if (rc == KZ_OK) rc = tau0.alloc(ctx, (size_t)n_fail * 8);
-                if (rc == KZ_OK) rc = early_left.alloc(ctx, (size_t)n_fail * sizeof(int));
-                if (rc == KZ_OK && (hipMemcpyAsync(fl0.get(), fail_list, (size_t)n_fail * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                                    hipMemcpyAsync(tau0.get(), ps.fail_tau, (size_t)n_fail * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)) {
-                    kz_set_error("kz_knn: copying the uncertified rows failed");
-                    rc = KZ_ERR_HIP;
-                }
-                int n_after = n_fail;
-                long long pairs = 0, grouped = 0;
-                const bool no_mem = rc == KZ_ERR_NOMEM;   // (no room for the lists: the next tier as before -- the step is an optimisation)
-                if (rc == KZ_OK) {
-                    KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-                    rc = kz_range_rescue(ctx, query, fp.row_map ? 0 : cq_begin, fl0.get(), tau0.get(), n_fail, index, k, exclude_self, d_self_ids,
-                                         fp.out_dist, fp.out_ind, early_left.get(), &n_after, &pairs, &grouped, true, KZ_RANGE_EARLY_PER_ROW);
-                }
-                fl0.reset();
-                tau0.reset();
-                if (no_mem) {
-                    early_left.reset();
-                    rc = KZ_OK;
-                } else {
-                    if (rc != KZ_OK) return rc;
-                    KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-                    KZ_HIP(hipStreamSynchronize(ctx->stream));
-                    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-                    fb_ms += ms;
-                    n_range += n_fail - n_after;
-                    n_range_group += grouped;
-                    n_range_pairs += pairs;
-                    n_fail_total += n_fail - n_after;   // (answered by the exact kernels)
-                    n_fail = n_after;
-                    esc_list = early_left.get();
-                }
+            const int* esc_list = ps.fail_list;
+            if (ap.early_range) {
+                rc = kz_early_range(c, ps, fp, ch.cq_begin, &n_fail, early_left, &esc_list, &tally);
+                if (rc != KZ_OK) return rc;
             }
             kz_knn_stats st2;
             memset(&st2, 0, sizeof(st2));
-            // (fp16 found hard after the fact, no probe beforehand: the ladder on the failed rows -- top-level calls only)
-            const bool ladder = fp16_hard && !wide_route && next.prec == 2 && !probed && default_request && !(dual && dual->probed);
             ms = 0;
             if (n_fail == 0) {
-            } else if (ladder)
-                rc = kz_escalate_ladder(ctx, query, fp.row_map ? 0 : cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, next,
+            } else if (ap.ladder)
+                rc = kz_escalate_ladder(ctx, query, fp.row_map ? 0 : ch.cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, ap.next,
                                         fp.out_dist, fp.out_ind, &st2, &ms);
             else
-                rc = kz_escalate_rows(ctx, query, fp.row_map ? 0 : cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, next,
+                rc = kz_escalate_rows(ctx, query, fp.row_map ? 0 : ch.cq_begin, esc_list, n_fail, index, k, exclude_self, d_self_ids, ap.next,
                                       fp.out_dist, fp.out_ind, &st2, &ms);
             early_left.reset();
             if (rc != KZ_OK) return rc;
-            fb_ms += ms;
-            n_escalated += n_fail + st2.n_escalated_rows;
-            n_fail_total += st2.n_fallback_rows;
-            n_range += st2.n_range_rows;
-            n_range_pairs += st2.n_range_pairs;
-            n_range_group += st2.n_range_group_rows;
-            if (st2.max_err_ratio > max_err_ratio) max_err_ratio = st2.max_err_ratio;
+            tally.fb_ms += ms;
+            tally.n_escalated += n_fail;
+            tally.add(st2);
             c0 += max_rows_per_chunk;
-            if (tier_next != tier && short_ord) {   // (the other tiers' kernels keep one list of K' per query)
-                short_ord = false;
-                KP = KP_long;
-                KSEL = KSEL_long;
-                long_pieces = pieces_long;
-            }
-            tier = tier_next;
+            kz_route_next_tier(&route, ap.tier_next);   // (kernel_for re-resolves at the top of the next chunk)
             continue;
         }
-        n_fail_total += n_fail;
+        tally.n_fail_total += n_fail;
 
-        if (n_fail > 0 && !rescued) {
+        if (n_fail > 0 && !ap.rescued) {
             // exact brute force against the whole index (kz_exact.h), behind the range re-search where that applies
             KzExactTaken taken;
-            rc = kz_exact_whole_index(ctx, query, cq_begin, fail_list, ps.fail_tau, n_fail,
-                                      !exact_only && n_fail >= KZ_RANGE_MIN_ROWS && kz_range_shapes_ok(ctx, query, index), index, k, exclude_self,
-                                      d_self_ids, fp.out_dist, fp.out_ind, &taken);
+            rc = kz_exact_whole_index(ctx, query, ch.cq_begin, ps.fail_list, ps.fail_tau, n_fail, ap.range_first, index, k, exclude_self, d_self_ids,
+                                      fp.out_dist, fp.out_ind, &taken);
             if (rc != KZ_OK) return rc;
-            n_range += taken.range_rows;
-            n_range_pairs += taken.range_pairs;
-            n_range_group += taken.range_group_rows;
-            fb_ms += taken.ms;
+            tally.n_range += taken.range_rows;
+            tally.n_range_pairs += taken.range_pairs;
+            tally.n_range_group += taken.range_group_rows;
+            tally.fb_ms += taken.ms;
         }
         c0 += max_rows_per_chunk;
     }
     if (stats) {
-        stats->main_kernel_ms = main_ms;
-        stats->finalize_ms = fin_ms;
-        stats->fallback_ms = fb_ms;
-        stats->probe_ms = probe_ms;
-        stats->n_fallback_rows = n_fail_total;
-        stats->list_len = KP;
-        stats->n_splits = last_splits;
-        stats->n_blocks = last_blocks;
+        tally.write(stats);
+        stats->list_len = route.cur.KP;
         stats->first_pass = first_tier;
-        stats->n_escalated_rows = n_escalated;
-        stats->max_err_ratio = max_err_ratio;
-        stats->n_first_pass_fail = n_first_fail > 0x7fffffff ? 0x7fffffff : (int32_t)n_first_fail;
-        stats->wide_lists = wide_route ? long_pieces : 0;
-        stats->n_spec_rows = n_spec > 0x7fffffff ? 0x7fffffff : (int32_t)n_spec;
-        stats->n_range_rows = n_range;
-        stats->n_range_pairs = n_range_pairs;
-        stats->n_range_group_rows = n_range_group;
+        stats->wide_lists = route.wide_route ? route.cur.pieces : 0;
     }
     return KZ_OK;
 }
+
 
 extern "C" int kz_knn(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index, int k,
                       int exclude_self, double* d_dist, int64_t* d_ind, kz_knn_stats* stats) {

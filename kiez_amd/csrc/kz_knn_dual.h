@@ -615,8 +615,7 @@ static int kz_dual_enqueue_chain(KzRevChain& r) {
         lay.halves = 1;
         lay.contig = 1;
         KZ_HIP(hipMemsetAsync(r.fail_count, 0, 4 * sizeof(int), ctx->stream));
-        KnnFinParams fp;
-        memset(&fp, 0, sizeof(fp));
+        KnnFinParams fp = kz_fin_params(ctx, r.qm, r.im, r.qi, r.ii, r.k);   // (always the fp16 tier: its images)
         fp.in_key = r.col_key;
         fp.in_idx = r.col_idx;
         fp.lay = lay;
@@ -625,21 +624,6 @@ static int kz_dual_enqueue_chain(KzRevChain& r) {
         fp.q_begin = 0;
         fp.q_count = r.n_rows;
         fp.row_map = r.fin_row_map;
-        fp.qraw = r.qm->raw;
-        fp.yraw = r.im->raw;
-        fp.qsqn = r.qm->sqn;
-        fp.ysqn = r.im->sqn;
-        fp.n_i = r.im->n;
-        fp.d = (int)r.im->d;
-        fp.metric = r.im->metric;
-        fp.k = r.k;
-        fp.ystats = r.im->d_stats;
-        fp.tier_h = 1;
-        fp.eps_mult = ctx->eps_scale;
-        fp.gamma_acc = 2.0 * (double)(r.im->kg * 4 + 16) * 5.9604644775390625e-08;
-        fp.q_rowq = r.qi->rowq;
-        fp.y_hmax = r.ii->d_max;
-        fp.hscale = r.ii->center->d_scale;
         fp.excl_floor = r.floor_fin;
         fp.dual_col = 1;
         fp.out_dist = r.d_dist;

@@ -123,12 +123,7 @@ __device__ __forceinline__ void kz_emit_sorted(const double* sval, const int* si
 #define KZ_FIN_DEPTH 3
 #endif
 constexpr int KZ_FIN_ROWS = KZ_FIN_ROWS_N;
-constexpr int KZ_FIN_MAXM = 4096;  // list entries per query: 4 waves x (4096*8 + 128*28) B = 142 KiB of LDS at most
-
-// Per-wave LDS of the finalize kernel for a launch whose queries hold at most max_m list entries.
-__host__ __device__ __forceinline__ int kz_fin_wave_bytes(int max_m, int KP) {
-    return ((max_m * 8 + KP * 28) + 15) & ~15;
-}
+// (KZ_FIN_MAXM, kz_fin_wave_bytes: kz_route.h)
 // (the finalize kernel for many candidates shares bytes between arrays that are never live together: kz_knn_fin_wide.h)
 __host__ __device__ __forceinline__ int kz_fin_wide_wave_bytes(int max_m, int KS) {
     return ((max_m * 8 + KS * 20) + 15) & ~15;

@@ -12,7 +12,7 @@
 // Operand precision of the fused kernel ("tier").  kz_knn starts at the highest tier the shapes allow; rows whose
 // candidate set cannot be certified under that tier's bound go down: fp16 / split-bf16 -> float32 operands (gathered into
 // a dense query block) -> exact float64 brute force.  The result is the float64 neighbour order at every tier.
-enum { KZ_TIER_F32 = 0, KZ_TIER_BF = 1, KZ_TIER_H = 2 };
+// (KZ_TIER_F32 / KZ_TIER_BF / KZ_TIER_H: kz_route.h)
 
 struct KzSweepKernel {
     const void* fn;       // host stub of the __global__ (nullptr: no such build)

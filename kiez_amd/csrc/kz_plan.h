@@ -13,7 +13,7 @@
 #endif
 constexpr int KZ_MAX_REGIONS = 8;
 constexpr int KZ_QGROUP = 24;
-constexpr int KZ_PLAN_START_TILES = 24;   // what the start of an item costs, in tiles of steady sweep (kz_plan_rounds)   // query tiles sharing an XCD at a time (x splits ~= resident workgroups)
+constexpr int KZ_PLAN_START_TILES = 24;   // what the start of an item costs, in tiles of steady sweep (kz_plan_rounds)
 
 // Candidate-list storage.  The host schedule cuts the query tiles of a launch into a few REGIONS; every query of region r owns
 // pieces[r] lists (one per index-range piece; two per piece -- one per lane half -- for the float32 kernels).

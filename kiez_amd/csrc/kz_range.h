@@ -27,7 +27,7 @@
 // Reference: the brute-force search it replaces row by row, kiez/neighbors/exact/sklearn_nearest_neighbors.py:96-101.
 #pragma once
 
-constexpr int KZ_RANGE_MIN_ROWS = 128;      // fewer rows: the whole-index kernels (a sweep for a handful of rows costs more than it saves)
+// (KZ_RANGE_MIN_ROWS -- fewer rows: the whole-index kernels -- and KZ_RG_MIN_ROWS: kz_route.h)
 constexpr int KZ_RANGE_BATCH = 32768;       // failed rows per sweep
 constexpr int KZ_RANGE_MIN_BATCH = 1024;    // a log that overflows at this batch size: the batch goes to `left`
 constexpr int KZ_RANGE_PPW = 256;           // pairs per wave of kz_exact_pairs_kernel
@@ -395,7 +395,6 @@ static int kz_range_sweep_rows(kz_ctx* ctx, kz_matrix* qsub, const double* tau, 
 // Where the data has no such structure the radius R(r) covers most of the index: groups whose range holds more than half of it, or
 // whose blocks do not fit the memory budget, are not taken -- their rows go through the per-row range above.  Values and order are
 // the exact kernels' as everywhere.
-constexpr int KZ_RG_MIN_ROWS = 2048;   // failed rows from which representatives are tried
 constexpr int KZ_RG_STRIDE = 256;      // one representative per this many failed rows (at least KZ_XL_MIN_ROWS of them) ...
 constexpr int KZ_RG_MAX_REPS = 1024;   // ... at most this many
 
