@@ -698,6 +698,46 @@ enum {
 int kz_selftest_image(kz_ctx* ctx, kz_matrix* m, kz_matrix* partner, int what, int64_t arg, const int* h_rows, void* h_dst,
                       size_t capacity, size_t* h_bytes);
 
+/* Self-test hook (tests/test_gpu_finalize_direct.py): the finalize kernels of kz_knn (merge a query's candidate lists, select, re-rank
+ * in float64, certify) on candidate lists the CALLER supplies, through the launcher and the parameter fill every search uses.  Nothing
+ * of the kernels is restated: the hook validates the geometry, copies the host arrays to the device, launches and copies back.
+ *   tier      0: the float32 / split-bf16 bound with the caller's `gamma`;  2: the fp16 bound (the images are built as kz_knn builds
+ *             them, the context's eps_scale applies; needs contig = 1 and a width that has an fp16 image)
+ *   layout    n_regions regions of query tiles [qt_end[r-1], qt_end[r]) with pieces[r] index ranges each; `halves` lists per (query,
+ *             range); contig 1: every list is KP contiguous entries, 0: the wave-interleaved layout.  The region bases follow as the
+ *             planner lays them out; h_key / h_idx hold n_list = sum over regions of tiles x 128 x pieces x (contig ? KP : 2 KP) entries.
+ *   rows      local query q = 0 .. q_count - 1 is list row list_row0 + q and query row q_begin + q (image row, with h_row_map)
+ *   optional  (NULL: absent) h_self_ids [q_count]; h_list_floor, h_excl_floor, h_row_map [query rows]; h_idx_map [n_idx_map]
+ *   outputs   h_out_dist / h_out_ind [rows][k] (rows = q_count, with h_row_map: the query's rows), NaN / -1 where nothing was written;
+ *             h_fail_list / h_fail_tau [q_count], *n_fail entries of them set; *err_ratio; *build = KZ_FIN_BUILD_* of the launches
+ * KZ_ERR_INVALID, before anything is launched, for: an id outside [-1, n_i) (after h_idx_map), a map entry that is no row, KP outside
+ * {16, 32, 64, 128}, more than 4096 entries per query, lists that do not fit the kernel's LDS, 0 < KSEL < k_eff (KSEL = 0: KP < k_eff),
+ * tier 2 on an interleaved layout or a width without fp16 image, h_idx_map on an interleaved layout (only the contiguous gather applies
+ * it), h_excl_floor with anything but one list of KP entries per query, all selected, and no h_list_floor (the reverse direction of a
+ * shared sweep, whose bound counts nothing else), metrics other than the euclidean family and cosine.  Synchronises. */
+enum { KZ_FIN_BUILD_ORDINARY = 0, KZ_FIN_BUILD_TWO_LOADS, KZ_FIN_BUILD_MANY, KZ_FIN_BUILD_WIDE };
+typedef struct kz_selftest_fin {
+    int32_t k, exclude_self, tier, KP, KSEL;
+    int32_t n_regions, halves, contig, dual_col, n_idx_map;
+    int32_t qt_end[8], pieces[8];
+    double gamma;
+    int64_t q_begin, q_count, list_row0, n_list;
+    const float* h_key;
+    const int32_t* h_idx;
+    const int64_t* h_self_ids;
+    const float* h_list_floor;
+    const float* h_excl_floor;
+    const int32_t* h_idx_map;
+    const int32_t* h_row_map;
+    double* h_out_dist;
+    int64_t* h_out_ind;
+    int32_t* h_fail_list;
+    double* h_fail_tau;
+    int32_t n_fail, build;
+    double err_ratio;
+} kz_selftest_fin;
+int kz_selftest_finalize(kz_ctx* ctx, kz_matrix* query, kz_matrix* index, kz_selftest_fin* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1179,6 +1179,169 @@ static int kz_chunk_finalize(const KzCall& c, const KzRoute& route, const KzChun
     return KZ_OK;
 }
 
+// Test hook (kiez_amd.h; tests/test_gpu_finalize_direct.py): the finalize launch of a pass on lists the caller wrote.  Parameters by
+// kz_fin_params, launch by kz_launch_finalize, as kz_chunk_finalize above; everything the kernels index with is checked here first.
+extern "C" int kz_selftest_finalize(kz_ctx* ctx, kz_matrix* query, kz_matrix* index, kz_selftest_fin* t) {
+    KZ_REQUIRE(ctx && query && index && t && query->ctx == ctx && index->ctx == ctx, "kz_selftest_finalize: null argument / foreign matrix");
+    for (const kz_matrix* x : {(const kz_matrix*)query, (const kz_matrix*)index}) {
+        KZ_REFUSE_PRECOMPUTED("kz_selftest_finalize", x);
+        KZ_REQUIRE(!x->raw_only && x->metric <= KZ_COSINE, "kz_selftest_finalize: searchable matrices of the euclidean family or cosine only");
+    }
+    KZ_REQUIRE(query->d == index->d && query->metric == index->metric && query->dtype == index->dtype,
+               "kz_selftest_finalize: the matrices must share width, metric and element type");
+    KZ_REQUIRE(t->h_key && t->h_idx && t->h_out_dist && t->h_out_ind && t->h_fail_list && t->h_fail_tau, "kz_selftest_finalize: null array");
+    const int KP = t->KP, k_eff = t->k + (t->exclude_self ? 1 : 0), KS = t->KSEL > 0 ? t->KSEL : KP;
+    KZ_REQUIRE(KP == 16 || KP == 32 || KP == 64 || KP == 128, "kz_selftest_finalize: lists of %d entries", KP);
+    KZ_REQUIRE(t->k >= 1 && k_eff <= KZ_EXACT_MAX_K && t->KSEL >= 0 && t->KSEL <= KZ_FIN_MAXM && KS >= k_eff,
+               "kz_selftest_finalize: k=%d (+ self) against %d selected candidates", t->k, KS);
+    KZ_REQUIRE(t->tier == KZ_TIER_F32 || t->tier == KZ_TIER_H, "kz_selftest_finalize: tier %d", t->tier);
+    KZ_REQUIRE(t->tier == KZ_TIER_H || (t->gamma >= 0.0 && t->gamma < INFINITY), "kz_selftest_finalize: gamma must be finite and non-negative");
+    KZ_REQUIRE(t->tier != KZ_TIER_H || (t->contig == 1 && kz_h_slices_ok(index->kg)),
+               "kz_selftest_finalize: the fp16 tier needs contiguous lists and a width with an fp16 image (d=%lld)", (long long)index->d);
+    KZ_REQUIRE((t->contig == 0 || t->contig == 1) && (t->halves == 1 || t->halves == 2) && t->n_regions >= 1 && t->n_regions <= KZ_MAX_REGIONS,
+               "kz_selftest_finalize: layout with %d regions, %d halves, contig=%d", t->n_regions, t->halves, t->contig);
+    // ---- the layout, its bases as kz_plan_pass lays them out ----
+    KzListLayout lay;
+    memset(&lay, 0, sizeof(lay));
+    lay.n_regions = t->n_regions;
+    lay.halves = t->halves;
+    lay.contig = t->contig;
+    const int entries_per_list = t->contig ? KP : 2 * KP;
+    KZ_REQUIRE(t->contig == 0 || t->halves == 1, "kz_selftest_finalize: contiguous lists have one list per query and range");
+    int64_t list_elems = 0;
+    int max_m = 0;
+    for (int r = 0; r < t->n_regions; ++r) {
+        const int t0 = r > 0 ? t->qt_end[r - 1] : 0;
+        KZ_REQUIRE(t->qt_end[r] > t0 && t->qt_end[r] <= (1 << 16) && t->pieces[r] >= 1 && t->pieces[r] <= KZ_FIN_MAXM,
+                   "kz_selftest_finalize: region %d ends at tile %d with %d pieces", r, t->qt_end[r], t->pieces[r]);
+        const int m = t->pieces[r] * t->halves * KP;
+        KZ_REQUIRE(m <= KZ_FIN_MAXM, "kz_selftest_finalize: %d list entries per query (at most %d)", m, KZ_FIN_MAXM);
+        if (m > max_m) max_m = m;
+        lay.qt_end[r] = t->qt_end[r];
+        lay.pieces[r] = t->pieces[r];
+        lay.base[r] = (long long)list_elems;
+        list_elems += (int64_t)(t->qt_end[r] - t0) * KZ_TILE * (int64_t)t->pieces[r] * entries_per_list;
+    }
+    KZ_REQUIRE(t->n_list == list_elems && list_elems < ((int64_t)1 << 28), "kz_selftest_finalize: the layout holds %lld entries, the arrays %lld",
+               (long long)list_elems, (long long)t->n_list);
+    KZ_REQUIRE(t->q_count >= 1 && t->q_begin >= 0 && t->q_begin + t->q_count <= query->n && t->list_row0 >= 0 &&
+                   t->list_row0 + t->q_count <= (int64_t)t->qt_end[t->n_regions - 1] * KZ_TILE,
+               "kz_selftest_finalize: rows [%lld, +%lld) at list row %lld", (long long)t->q_begin, (long long)t->q_count, (long long)t->list_row0);
+    // ---- every index the kernels read through ----
+    // (the wave-interleaved gather stores the list's ids as they are: a map there would be checked here and never applied)
+    KZ_REQUIRE(!t->h_idx_map || t->contig == 1, "kz_selftest_finalize: idx_map needs contiguous lists");
+    // (the reverse direction's bound is excl_floor and the cut of its ONE list of KP entries: kz_finalize_query counts neither
+    //  list_floor nor an evicting list's minimum beside it)
+    KZ_REQUIRE(!t->h_excl_floor || (!t->h_list_floor && KS == KP && t->halves == 1 && max_m == KP),
+               "kz_selftest_finalize: excl_floor goes with one list of KP entries, all selected, and no list_floor");
+    KZ_REQUIRE(!t->h_idx_map || t->n_idx_map >= 1, "kz_selftest_finalize: empty idx_map");
+    const int64_t id_end = t->h_idx_map ? (int64_t)t->n_idx_map : index->n;
+    for (int64_t e = 0; e < t->n_list; ++e)
+        KZ_REQUIRE(t->h_idx[e] >= -1 && t->h_idx[e] < id_end, "kz_selftest_finalize: list entry %lld holds id %d", (long long)e, t->h_idx[e]);
+    if (t->h_idx_map)
+        for (int i = 0; i < t->n_idx_map; ++i)
+            KZ_REQUIRE(t->h_idx_map[i] >= -1 && t->h_idx_map[i] < index->n, "kz_selftest_finalize: idx_map[%d] = %d is no index row", i, t->h_idx_map[i]);
+    if (t->h_row_map)
+        for (int64_t i = 0; i < query->n; ++i)
+            KZ_REQUIRE(t->h_row_map[i] >= 0 && t->h_row_map[i] < query->n, "kz_selftest_finalize: row_map[%lld] = %d is no query row", (long long)i,
+                       t->h_row_map[i]);
+    if (t->h_self_ids)
+        for (int64_t i = 0; i < t->q_count; ++i)
+            KZ_REQUIRE(t->h_self_ids[i] >= 0 && t->h_self_ids[i] < index->n, "kz_selftest_finalize: self_ids[%lld] is no index row", (long long)i);
+    KZ_HIP(hipSetDevice(ctx->device));
+    int rc = kz_matrix_check(query);
+    if (rc == KZ_OK) rc = kz_matrix_check(index);
+    if (rc != KZ_OK) return rc;
+    if (t->tier == KZ_TIER_H) {
+        rc = kz_himage_ensure(query, index);
+        if (rc != KZ_OK) return rc;
+    }
+    KnnFinParams fp = kz_fin_params(ctx, query, index, t->tier == KZ_TIER_H ? query->himg : nullptr, t->tier == KZ_TIER_H ? index->himg : nullptr, t->k);
+    // (the kernel's build, and with it the LDS a wave needs, follows from the parameters filled so far plus these three)
+    fp.KP = KP;
+    fp.KSEL = t->KSEL;
+    KzPoolBuf<float> d_efloor;
+    if (t->h_excl_floor && d_efloor.alloc(ctx, (size_t)query->n * 4) != KZ_OK) {
+        kz_set_error("kz_selftest_finalize: out of device memory");
+        return KZ_ERR_NOMEM;
+    }
+    fp.excl_floor = d_efloor.get();   // (kz_fin_build reads whether there is one; filled with the other copies below)
+    const int build = kz_fin_build(fp, KP, index->dtype);
+    const int wave_bytes = build == KZ_FIN_BUILD_WIDE ? kz_fin_wide_wave_bytes(max_m, KS) : kz_fin_wave_bytes(max_m, KS);
+    KZ_REQUIRE(4 * wave_bytes <= KZ_FIN_LDS_BYTES, "kz_selftest_finalize: %d entries, %d selected: %d bytes of LDS", max_m, KS, 4 * wave_bytes);
+    // ---- device copies ----
+    const int64_t out_rows = t->h_row_map ? query->n : t->q_count;
+    const size_t out_n = (size_t)out_rows * (size_t)t->k;
+    KzPoolBuf<float> d_key, d_lfloor;
+    KzPoolBuf<int> d_idx, d_imap, d_rmap, d_fail;
+    KzPoolBuf<int64_t> d_self, d_oind;
+    KzPoolBuf<double> d_odist, d_tau;
+    bool ok = d_key.alloc(ctx, (size_t)t->n_list * 4) == KZ_OK && d_idx.alloc(ctx, (size_t)t->n_list * 4) == KZ_OK &&
+              d_fail.alloc(ctx, (size_t)t->q_count * 4) == KZ_OK && d_tau.alloc(ctx, (size_t)t->q_count * 8) == KZ_OK &&
+              d_odist.alloc(ctx, out_n * 8) == KZ_OK && d_oind.alloc(ctx, out_n * 8) == KZ_OK;
+    ok = ok && (!t->h_list_floor || d_lfloor.alloc(ctx, (size_t)query->n * 4) == KZ_OK) &&
+         (!t->h_idx_map || d_imap.alloc(ctx, (size_t)t->n_idx_map * 4) == KZ_OK) && (!t->h_row_map || d_rmap.alloc(ctx, (size_t)query->n * 4) == KZ_OK) &&
+         (!t->h_self_ids || d_self.alloc(ctx, (size_t)t->q_count * 8) == KZ_OK);
+    if (!ok) {
+        kz_set_error("kz_selftest_finalize: out of device memory");
+        return KZ_ERR_NOMEM;
+    }
+    const hipStream_t st = ctx->stream;
+    KZ_HIP(hipMemcpyAsync(d_key.get(), t->h_key, (size_t)t->n_list * 4, hipMemcpyHostToDevice, st));
+    KZ_HIP(hipMemcpyAsync(d_idx.get(), t->h_idx, (size_t)t->n_list * 4, hipMemcpyHostToDevice, st));
+    if (t->h_list_floor) KZ_HIP(hipMemcpyAsync(d_lfloor.get(), t->h_list_floor, (size_t)query->n * 4, hipMemcpyHostToDevice, st));
+    if (t->h_excl_floor) KZ_HIP(hipMemcpyAsync(d_efloor.get(), t->h_excl_floor, (size_t)query->n * 4, hipMemcpyHostToDevice, st));
+    if (t->h_idx_map) KZ_HIP(hipMemcpyAsync(d_imap.get(), t->h_idx_map, (size_t)t->n_idx_map * 4, hipMemcpyHostToDevice, st));
+    if (t->h_row_map) KZ_HIP(hipMemcpyAsync(d_rmap.get(), t->h_row_map, (size_t)query->n * 4, hipMemcpyHostToDevice, st));
+    if (t->h_self_ids) KZ_HIP(hipMemcpyAsync(d_self.get(), t->h_self_ids, (size_t)t->q_count * 8, hipMemcpyHostToDevice, st));
+    // (all-ones bytes: a NaN distance, id -1, row -1, a NaN tau wherever the kernels write nothing)
+    KZ_HIP(hipMemsetAsync(d_odist.get(), 0xFF, out_n * 8, st));
+    KZ_HIP(hipMemsetAsync(d_oind.get(), 0xFF, out_n * 8, st));
+    KZ_HIP(hipMemsetAsync(d_fail.get(), 0xFF, (size_t)t->q_count * 4, st));
+    KZ_HIP(hipMemsetAsync(d_tau.get(), 0xFF, (size_t)t->q_count * 8, st));
+    int* fail_count = ctx->d_counters + 8;
+    KZ_HIP(hipMemsetAsync(fail_count, 0, 4 * sizeof(int), st));   // fail counter, (unused), error-ratio bits
+    KZ_HIP(hipStreamSynchronize(st));   // (the host arrays are the caller's pageable buffers)
+    // ---- the rest of the parameters, field by field as kz_chunk_finalize fills them ----
+    fp.in_key = d_key.get();
+    fp.in_idx = d_idx.get();
+    fp.lay = lay;
+    fp.list_row0 = t->list_row0;
+    fp.q_begin = t->q_begin;
+    fp.q_count = t->q_count;
+    fp.exclude_self = t->exclude_self ? 1 : 0;
+    fp.self_ids = d_self.get();
+    fp.gamma = t->gamma;
+    fp.out_dist = d_odist.get();
+    fp.out_ind = d_oind.get();
+    fp.idx_map = d_imap.get();
+    fp.row_map = d_rmap.get();
+    fp.list_floor = d_lfloor.get();
+    fp.excl_floor = d_efloor.get();
+    fp.dual_col = t->dual_col ? 1 : 0;
+    fp.fail_count = fail_count;
+    fp.fail_list = d_fail.get();
+    fp.fail_tau = d_tau.get();
+    fp.err_ratio_bits = (unsigned long long*)(ctx->d_counters + 10);
+    if (fp.tier_h && index->metric == KZ_COSINE && KS > 160) {   // (kz_chunk_finalize's condition)
+        rc = kz_matrix_norm64(index);
+        if (rc != KZ_OK) return rc;
+        fp.ynorm64 = index->norm64;
+    }
+    rc = kz_launch_finalize(ctx, fp, lay, KP, t->q_count, index->dtype);
+    if (rc != KZ_OK) return rc;
+    KZ_HIP(hipMemcpyAsync(ctx->h_counters + 8, fail_count, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+    KZ_HIP(hipMemcpyAsync(t->h_out_dist, d_odist.get(), out_n * 8, hipMemcpyDeviceToHost, st));
+    KZ_HIP(hipMemcpyAsync(t->h_out_ind, d_oind.get(), out_n * 8, hipMemcpyDeviceToHost, st));
+    KZ_HIP(hipMemcpyAsync(t->h_fail_list, d_fail.get(), (size_t)t->q_count * 4, hipMemcpyDeviceToHost, st));
+    KZ_HIP(hipMemcpyAsync(t->h_fail_tau, d_tau.get(), (size_t)t->q_count * 8, hipMemcpyDeviceToHost, st));
+    KZ_HIP(hipStreamSynchronize(st));
+    t->n_fail = ctx->h_counters[8];
+    memcpy(&t->err_ratio, ctx->h_counters + 10, 8);
+    t->build = build;
+    return KZ_OK;
+}
+
 // Behind the finalize kernel: the speculative rescue, the read-back of the fail counter (and of the matrices' deferred finiteness
 // verdicts), the synchronisation; *spec_R = rows the speculative launches covered.
 static int kz_chunk_readback(const KzCall& c, const KzRoute& route, const KzChunk& ch, const KzPass& ps, const KnnFinParams& fp, int k_eff,

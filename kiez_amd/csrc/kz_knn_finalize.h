@@ -817,6 +817,20 @@ __global__ __launch_bounds__(256, MINW) void kz_knn_finalize_kernel(KnnFinParams
 
 #include "kz_knn_fin_wide.h"
 
+// Which build of the finalize kernel a pass launches (KZ_FIN_BUILD_*, kiez_amd.h): decided once per pass, from the parameters alone.
+static int kz_fin_build(const KnnFinParams& fp, int KP, int dtype) {
+    const bool wide = (fp.KSEL > 0 ? fp.KSEL : KP) > 160;   // the long-k route
+    // (many selected candidates + float32 rows on the fp16 tier, ordinary direction: kz_knn_fin_wide.h)
+    const bool rows_vec = fp.d <= 256 && (fp.d & 3) == 0 && (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & 15u) == 0;
+    if (wide && dtype == KZ_F32 && fp.tier_h && !fp.excl_floor && rows_vec) return KZ_FIN_BUILD_WIDE;
+    if (wide) return KZ_FIN_BUILD_MANY;
+    // (float32 rows of 260 .. 512 elements, 16-byte aligned -- float16 / bfloat16 rows of as many, 8-byte aligned: the build whose
+    //  pipelined re-rank takes two loads per lane and row)
+    const bool two_chunks = (dtype == KZ_F32 || kz_dtype_is_half(dtype)) && fp.d > 256 && fp.d <= 512 && (fp.d & 3) == 0 &&
+                            (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & (dtype == KZ_F32 ? 15u : 7u)) == 0;
+    return two_chunks ? KZ_FIN_BUILD_TWO_LOADS : KZ_FIN_BUILD_ORDINARY;
+}
+
 // The finalize launches of one pass: one per list region (the dynamic LDS follows the region's entry count: occupancy of
 // the gather).  fp.q_first / q_last / max_m are filled here.
 static int kz_launch_finalize(kz_ctx* ctx, KnnFinParams& fp, const KzListLayout& lay, int KP, int64_t q_count, int dtype) {
@@ -840,14 +854,8 @@ static int kz_launch_finalize(kz_ctx* ctx, KnnFinParams& fp, const KzListLayout&
     int big = 0;
     for (int g = 1; g < n_groups; ++g)
         if (groups[g].hi - groups[g].lo > groups[big].hi - groups[big].lo) big = g;
-    const bool wide = (fp.KSEL > 0 ? fp.KSEL : KP) > 160;   // the long-k route
-    // (many selected candidates + float32 rows on the fp16 tier, ordinary direction: kz_knn_fin_wide.h)
-    const bool rows_vec = fp.d <= 256 && (fp.d & 3) == 0 && (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & 15u) == 0;
-    const bool wide2 = wide && dtype == KZ_F32 && fp.tier_h && !fp.excl_floor && rows_vec;
-    // (float32 rows of 260 .. 512 elements, 16-byte aligned -- float16 / bfloat16 rows of as many, 8-byte aligned: the build whose
-    //  pipelined re-rank takes two loads per lane and row)
-    const bool two_chunks = !wide && (dtype == KZ_F32 || kz_dtype_is_half(dtype)) && fp.d > 256 && fp.d <= 512 && (fp.d & 3) == 0 &&
-                            (((uintptr_t)fp.qraw | (uintptr_t)fp.yraw) & (dtype == KZ_F32 ? 15u : 7u)) == 0;
+    const int build = kz_fin_build(fp, KP, dtype);
+    const bool wide2 = build == KZ_FIN_BUILD_WIDE, wide = wide2 || build == KZ_FIN_BUILD_MANY, two_chunks = build == KZ_FIN_BUILD_TWO_LOADS;
     const void* fk = nullptr;   // (the kernel of every launch of this pass: chosen -- and an element type refused -- before the fork)
     if (dtype != KZ_F32) {
         // (float64 rows: the generic re-rank loop, whose loads go through kz_row4; the 2-byte types: the pipelined re-rank on

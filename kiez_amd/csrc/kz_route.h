@@ -228,7 +228,8 @@ static inline bool kz_route_short_geometry(const KzRouteIn& in, const KzResearch
     const int sel = k_eff + (KP >= 128 ? 80 : 48) < P * 16 ? k_eff + (KP >= 128 ? 80 : 48) : P * 16;
     *P_out = P;
     *sel_out = sel;
-    // (<= 512 entries: kz_rank_select<8>; up to 1024 -- 33 .. 64 lists of the long-k route -- the radix select)
+    // (the finalize kernel selects by rank counting, kz_rank_select<1>, up to 64 entries and by radix select beyond -- held in registers up
+    //  to 512 entries in the build for many candidates, read from LDS up to the 1024 of the long-k route's 33 .. 64 lists)
     return P <= (longk_lists ? 64 : 32) && in.n_tiles >= (int64_t)in.short_ord_min_tiles * P && sel >= k_eff &&
            4 * kz_fin_wave_bytes(P * 16, sel) <= KZ_FIN_LDS_BYTES;
 }
