@@ -738,6 +738,46 @@ typedef struct kz_selftest_fin {
 } kz_selftest_fin;
 int kz_selftest_finalize(kz_ctx* ctx, kz_matrix* query, kz_matrix* index, kz_selftest_fin* t);
 
+/* Self-test hook (tests/test_gpu_sweep_direct.py): ONE launch of one entry of the sweep-kernel table over query rows [q_begin, q_begin
+ * + q_count) against the whole index, through the stages every search runs -- the tier's operand images, the resolver, the chunk's
+ * plan, scratch carve-up and work table, the sweep launch -- and nothing behind them: the candidate lists (and, dual builds, the event
+ * log) come back as they lie on the device.  Nothing of the kernels is restated.  The plain images are swept (not the row-dealt or the
+ * sorted ones).
+ *   entry     tier 0 float32 / 1 split-bf16 / 2 fp16; KP 16 / 32 / 64 / 128; q64: the 64-queries-per-wave build; dual: the dual-pass
+ *             build (fp16 only, as q64); n_ranges >= 1: index ranges per query tile (what option "force_splits" sets)
+ *   optional  h_qfloor [query rows padded to 128] (fp16 only): the lists start full of (qfloor, no row) entries
+ *   dual      h_theta [index tiles x 128], h_qnbias [query rows padded to 128], log_cap >= 1; h_log_keys [4 log_cap] / h_log_meta
+ *             [2 log_cap] receive the first min(log_count, log_cap) entries, log_count the device counter
+ *   outputs   n_list = entries of the launch's lists; the layout (n_regions, qt_end, pieces, base, halves, contig), KP, qt0 (first query
+ *             tile of the launch: list row = query row - 128 qt0) and the entry that ran (wg_per_item, tiles_per_item, n_slices).
+ *             With h_out_key == NULL nothing is launched and these are all the call returns (the caller sizes its arrays by n_list);
+ *             else list_capacity >= n_list entries of h_out_key / h_out_idx receive the raw arrays (bytes the kernel did not write
+ *             read as NaN / -1).
+ * KZ_ERR_UNSUPPORTED for a combination without a build (q64 or dual off the fp16 tier, a width the tier has no kernel for);
+ * KZ_ERR_INVALID, before anything is launched, for: q_count < 1, rows a single launch does not take, precomputed / boolean / rows-only
+ * matrices, metrics other than the euclidean family and cosine, matrices of another context, a floor off the fp16 tier, a dual build
+ * without its three inputs.  Synchronises. */
+typedef struct kz_selftest_swp {
+    int32_t tier, KP, q64, dual, n_ranges;
+    int64_t q_begin, q_count;
+    const float* h_qfloor;
+    const float* h_theta;
+    const float* h_qnbias;
+    int64_t log_cap;
+    int64_t list_capacity;
+    float* h_out_key;
+    int32_t* h_out_idx;
+    float* h_log_keys;
+    int32_t* h_log_meta;
+    int64_t n_list;
+    uint64_t log_count;
+    int32_t n_regions, halves, contig, qt0;
+    int32_t qt_end[8], pieces[8];
+    int64_t base[8];
+    int32_t wg_per_item, tiles_per_item, n_slices, entry_KP, n_items, reserved;
+} kz_selftest_swp;
+int kz_selftest_sweep(kz_ctx* ctx, kz_matrix* query, kz_matrix* index, kz_selftest_swp* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,7 @@ SYMBOLS = [
     ("kz_selftest_div", C.c_int, [_P, _I64, C.c_uint64, C.c_int, C.POINTER(_I64)]),
     ("kz_selftest_image", C.c_int, [_P, _P, _P, C.c_int, _I64, C.POINTER(C.c_int), _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("kz_selftest_finalize", C.c_int, [_P, _P, _P, _P]),
+    ("kz_selftest_sweep", C.c_int, [_P, _P, _P, _P]),
     ("kz_row_stats", C.c_int, [_P, _P, _I64, C.c_int, _P, _P, _P]),
     ("kz_row_nanstats", C.c_int, [_P, _P, _I64, C.c_int, _P, _P]),
     ("kz_csls", C.c_int, [_P, _P, _P, _I64, C.c_int, _P, _P]),

@@ -1342,6 +1342,161 @@ extern "C" int kz_selftest_finalize(kz_ctx* ctx, kz_matrix* query, kz_matrix* in
     return KZ_OK;
 }
 
+// Test hook (kiez_amd.h; tests/test_gpu_sweep_direct.py): one sweep launch of one table entry, its lists and event log as they lie on
+// the device.  The stages are kz_knn_impl's own, called in its order with a route filled in by hand (tier, list length and the number
+// of index ranges are the caller's choice here, not kz_route.h's): kz_himage_ensure / kz_tier_images, kz_sweep_kernel, kz_chunk_plan,
+// kz_prepare_pass, kz_chunk_sweep -- and nothing behind them.  The dual builds get a KzDualPass on the PLAIN images, as
+// kz_range_sweep_rows fills one.
+extern "C" int kz_selftest_sweep(kz_ctx* ctx, kz_matrix* query, kz_matrix* index, kz_selftest_swp* t) {
+    KZ_REQUIRE(ctx && query && index && t && query->ctx == ctx && index->ctx == ctx, "kz_selftest_sweep: null argument / foreign matrix");
+    for (const kz_matrix* x : {(const kz_matrix*)query, (const kz_matrix*)index}) {
+        KZ_REFUSE_PRECOMPUTED("kz_selftest_sweep", x);
+        KZ_REQUIRE(!x->raw_only && x->metric <= KZ_COSINE, "kz_selftest_sweep: searchable matrices of the euclidean family or cosine only");
+    }
+    KZ_REQUIRE(query->d == index->d && query->metric == index->metric && query->dtype == index->dtype,
+               "kz_selftest_sweep: the matrices must share width, metric and element type");
+    const int tier = t->tier, KP = t->KP;
+    const bool dual = t->dual != 0, q64 = t->q64 != 0;
+    KZ_REQUIRE(tier == KZ_TIER_F32 || tier == KZ_TIER_BF || tier == KZ_TIER_H, "kz_selftest_sweep: tier %d", tier);
+    KZ_REQUIRE(KP == 16 || KP == 32 || KP == 64 || KP == 128, "kz_selftest_sweep: lists of %d entries", KP);
+    KZ_REQUIRE(t->n_ranges >= 1 && t->n_ranges <= KZ_MAX_PIECES, "kz_selftest_sweep: %d index ranges", t->n_ranges);
+    KZ_REQUIRE(t->q_count >= 1 && t->q_begin >= 0 && t->q_begin + t->q_count <= query->n, "kz_selftest_sweep: query rows [%lld, +%lld)",
+               (long long)t->q_begin, (long long)t->q_count);
+    KZ_REQUIRE(!t->h_qfloor || tier == KZ_TIER_H, "kz_selftest_sweep: seeded lists exist on the fp16 tier only");
+    KZ_REQUIRE(!dual || (t->h_theta && t->h_qnbias && t->log_cap >= 1 && t->log_cap < ((int64_t)1 << 26) && t->h_log_keys && t->h_log_meta),
+               "kz_selftest_sweep: a dual build needs h_theta, h_qnbias, log_cap >= 1 and the two log arrays");
+    KZ_REQUIRE(!t->h_out_key || (t->h_out_idx && t->list_capacity >= 1), "kz_selftest_sweep: h_out_key without h_out_idx / list_capacity");
+    // ---- the entry: a combination without a build is refused here, before any image is built ----
+    const int n_slices = kz_h_nsr(index->kg);
+    if ((dual || q64) && tier != KZ_TIER_H) {
+        kz_set_error("kz_selftest_sweep: the dual-pass and 64-query builds exist on the fp16 tier only");
+        return KZ_ERR_UNSUPPORTED;
+    }
+    if ((tier == KZ_TIER_H && !kz_h_slices_ok(index->kg)) || (tier == KZ_TIER_BF && !(index->kg / 4 >= 2 && index->kg / 4 <= 24)) ||
+        (tier != KZ_TIER_F32 && query->kg != index->kg)) {
+        kz_set_error("kz_selftest_sweep: tier %d has no kernel for d=%lld", tier, (long long)index->d);
+        return KZ_ERR_UNSUPPORTED;
+    }
+    KzSweepKernel kern;
+    int rc = kz_sweep_kernel(tier, dual, q64, KP, n_slices, &kern);
+    if (rc != KZ_OK) return rc;
+    KZ_REQUIRE(t->q_count <= kz_rows_per_chunk(ctx, KP, false), "kz_selftest_sweep: %lld rows are more than one launch takes", (long long)t->q_count);
+    KZ_HIP(hipSetDevice(ctx->device));
+    // ---- route and call as the stages read them ----
+    KzRoute route;
+    route.tier = tier;
+    route.cur.KP = KP;
+    route.cur.pieces = t->n_ranges;
+    route.lng = route.cur;
+    route.KP_class = KP;
+    KzDualPass dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.raw_lists = 1;
+    dp.no_q64 = q64 ? 0 : 1;
+    const KzCall c = {ctx, query, t->q_begin, t->q_count, index, 1, 0, nullptr, nullptr, nullptr, dual ? &dp : nullptr};
+    int blocks_per_cu = 1;
+    rc = kz_sweep_occupancy(ctx, kern, &blocks_per_cu);
+    if (rc != KZ_OK) return rc;
+    const int slots = kz_h_slots(kern.wg_per_item, blocks_per_cu, ctx->n_cus);
+    const int tpw_h = q64 ? 2 : 1, n_ytiles = (int)index->n_tiles;
+    int64_t max_rows = kz_rows_per_chunk(ctx, KP, false);
+    KzChunk ch;
+    kz_chunk_plan(c, route, slots, tpw_h, n_ytiles, 0, &max_rows, &ch);
+    KZ_REQUIRE(ch.cq_count == t->q_count && ch.pl.list_elems < ((size_t)1 << 28), "kz_selftest_sweep: the rows do not fit one launch (%zu list entries)",
+               ch.pl.list_elems);
+    const KzListLayout& lay = ch.pl.lay;
+    t->n_list = (int64_t)ch.pl.list_elems;
+    t->n_regions = lay.n_regions;
+    t->halves = lay.halves;
+    t->contig = lay.contig;
+    t->qt0 = ch.qt0;
+    for (int r = 0; r < KZ_MAX_REGIONS; ++r) {
+        t->qt_end[r] = r < lay.n_regions ? lay.qt_end[r] : 0;
+        t->pieces[r] = r < lay.n_regions ? lay.pieces[r] : 0;
+        t->base[r] = r < lay.n_regions ? lay.base[r] : 0;
+    }
+    t->wg_per_item = kern.wg_per_item;
+    t->tiles_per_item = kern.tiles_per_item;
+    t->n_slices = kern.n_slices;
+    t->entry_KP = kern.KP;
+    t->n_items = ch.pl.W;
+    t->log_count = 0;
+    if (!t->h_out_key) return KZ_OK;   // (the geometry only: the caller sizes its arrays)
+    KZ_REQUIRE(t->list_capacity >= t->n_list, "kz_selftest_sweep: the lists hold %lld entries, the arrays %lld", (long long)t->n_list,
+               (long long)t->list_capacity);
+    rc = kz_matrix_check(query);
+    if (rc == KZ_OK) rc = kz_matrix_check(index);
+    if (rc != KZ_OK) return rc;
+    // ---- the operand images, as kz_knn_impl builds them ----
+    if (tier == KZ_TIER_H) {
+        rc = kz_himage_ensure(query, index);
+        if (rc != KZ_OK) return rc;
+    }
+    rc = kz_tier_images(c, KzResearch(), route);
+    if (rc != KZ_OK) return rc;
+    // ---- device copies of the caller's arrays ----
+    const size_t q_pad = (size_t)query->n_tiles * KZ_TILE, y_pad = (size_t)n_ytiles * KZ_TILE;
+    KzPoolBuf<float> d_floor, d_theta, d_qnbias;
+    KzPoolBuf<void> d_lkeys, d_lmeta;
+    KzPoolBuf<unsigned long long> d_lcnt;
+    bool ok = !t->h_qfloor || d_floor.alloc(ctx, q_pad * 4) == KZ_OK;
+    if (dual)
+        ok = ok && d_theta.alloc(ctx, y_pad * 4) == KZ_OK && d_qnbias.alloc(ctx, q_pad * 4) == KZ_OK && d_lkeys.alloc(ctx, (size_t)t->log_cap * 16) == KZ_OK &&
+             d_lmeta.alloc(ctx, (size_t)t->log_cap * 8) == KZ_OK && d_lcnt.alloc(ctx, 8) == KZ_OK;
+    if (!ok) {
+        kz_set_error("kz_selftest_sweep: out of device memory");
+        return KZ_ERR_NOMEM;
+    }
+    const hipStream_t st = ctx->stream;
+    if (t->h_qfloor) KZ_HIP(hipMemcpyAsync(d_floor.get(), t->h_qfloor, q_pad * 4, hipMemcpyHostToDevice, st));
+    if (dual) {
+        KZ_HIP(hipMemcpyAsync(d_theta.get(), t->h_theta, y_pad * 4, hipMemcpyHostToDevice, st));
+        KZ_HIP(hipMemcpyAsync(d_qnbias.get(), t->h_qnbias, q_pad * 4, hipMemcpyHostToDevice, st));
+        KZ_HIP(hipMemsetAsync(d_lkeys.get(), 0xFF, (size_t)t->log_cap * 16, st));
+        KZ_HIP(hipMemsetAsync(d_lmeta.get(), 0xFF, (size_t)t->log_cap * 8, st));
+        KZ_HIP(hipMemsetAsync(d_lcnt.get(), 0, 8, st));
+        dp.probed = 1;
+        dp.qpack = (const float*)query->himg->packed;
+        dp.ypack = (const float*)index->himg->packed;
+        dp.ybias = index->himg->bias;
+        dp.theta = d_theta.get();
+        dp.qnbias = d_qnbias.get();
+        dp.qfloor = d_floor.get();
+        dp.log_keys = d_lkeys.get();
+        dp.log_meta = d_lmeta.get();
+        dp.log_cnt = d_lcnt.get();
+        dp.log_cap = t->log_cap;
+    }
+    KZ_HIP(hipStreamSynchronize(st));   // (the host arrays are the caller's pageable buffers)
+    // ---- scratch, work table, launch ----
+    KzPass ps;
+    rc = kz_prepare_pass(ctx, ch.pl, n_ytiles, slots, tier, ch.cq_count, &ps, tier == KZ_TIER_H ? tpw_h : 1, false);
+    if (rc != KZ_OK) return rc;
+    // (all-ones bytes: a NaN key, id -1 wherever the kernel writes nothing)
+    KZ_HIP(hipMemsetAsync(ps.out_key, 0xFF, (size_t)t->n_list * 4, st));
+    KZ_HIP(hipMemsetAsync(ps.out_idx, 0xFF, (size_t)t->n_list * 4, st));
+    KzPoolBuf<float> boot_floor;
+    KzPoolBuf<unsigned long long> stamp_buf;
+    rc = kz_chunk_sweep(c, route, kern, ch, ps, q64, false, d_floor.get(), n_ytiles, boot_floor, stamp_buf);
+    if (rc != KZ_OK) return rc;
+    KZ_HIP(hipGetLastError());
+    KZ_HIP(hipMemcpyAsync(t->h_out_key, ps.out_key, (size_t)t->n_list * 4, hipMemcpyDeviceToHost, st));
+    KZ_HIP(hipMemcpyAsync(t->h_out_idx, ps.out_idx, (size_t)t->n_list * 4, hipMemcpyDeviceToHost, st));
+    unsigned long long h_cnt = 0;
+    if (dual) KZ_HIP(hipMemcpyAsync(&h_cnt, d_lcnt.get(), 8, hipMemcpyDeviceToHost, st));
+    KZ_HIP(hipStreamSynchronize(st));
+    if (dual) {
+        t->log_count = h_cnt;
+        const size_t n_log = h_cnt < (unsigned long long)t->log_cap ? (size_t)h_cnt : (size_t)t->log_cap;
+        if (n_log > 0) {
+            KZ_HIP(hipMemcpyAsync(t->h_log_keys, d_lkeys.get(), n_log * 16, hipMemcpyDeviceToHost, st));
+            KZ_HIP(hipMemcpyAsync(t->h_log_meta, d_lmeta.get(), n_log * 8, hipMemcpyDeviceToHost, st));
+            KZ_HIP(hipStreamSynchronize(st));
+        }
+    }
+    return KZ_OK;
+}
+
 // Behind the finalize kernel: the speculative rescue, the read-back of the fail counter (and of the matrices' deferred finiteness
 // verdicts), the synchronisation; *spec_R = rows the speculative launches covered.
 static int kz_chunk_readback(const KzCall& c, const KzRoute& route, const KzChunk& ch, const KzPass& ps, const KnnFinParams& fp, int k_eff,
