@@ -659,6 +659,46 @@ int kz_components_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind
 int kz_components_lists(kz_ctx* ctx, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index, int64_t* d_label_q,
                         int64_t* d_label_t, int64_t* d_size_q, int64_t* d_size_t, int64_t* h_n_components);
 
+/* kz_components_edges: the same answer for an EDGE ARRAY -- edge e joins source row d_source[e] and target row d_target[e], e < count
+ * (int64 [count], device; any order, an edge may repeat; an edge with an id outside [0, n_q) / [0, n_index) is no pair).  Outputs,
+ * numbering and limits as kz_components_csr (count in the place of nnz); the same stage kernels behind a hook with one thread per edge.
+ * This is what labels a cut of kz_forest_*'s forest: its first `searchsorted(value, t)` edges.  Synchronises the context's stream. */
+int kz_components_edges(kz_ctx* ctx, const int64_t* d_source, const int64_t* d_target, int64_t count, int64_t n_q, int64_t n_index,
+                        int64_t* d_label_q, int64_t* d_label_t, int64_t* d_size_q, int64_t* d_size_t, int64_t* h_n_components);
+
+/* ---- THE SINGLE-LINKAGE HIERARCHY of a pair list: its minimum spanning forest (kz_forest.hip) -- additive, ABI v7 ------------------ */
+/* The components of the pairs with value <= t, for EVERY threshold t, from one call: the minimum spanning forest (MSF) of the weighted
+ * pair graph.  The graph is kz_components_*'s (source row i is node i, target row j node n_q + j) with one more rule: entry p is an
+ * EDGE when 0 <= d_ind[p] < n_index AND its value is not NaN (NaN is <= no threshold); -inf, +inf, -0.0 and negative values are
+ * legal; a pair stored twice is two edges.  p is the entry's flat position: the CSR position, or i k + c for lists [n_q, k].
+ * ORDER: edge p comes before p' when (key(w_p), p) < (key(w_p'), p'), key the order-preserving 64-bit pattern of the value widened
+ * to float64 with -0.0 == +0.0 and -inf first (kz_order_key.h).  A strict total order: the MSF under it is unique -- the forest
+ * Kruskal's algorithm builds taking the edges in that order -- and the result has the same bytes in every run.
+ *   d_source, d_target, d_entry (int64), d_value (float64)   (device, each with room for max(n_q + n_index - 1, 1) entries) the
+ *                                          m = n_q + n_index - C forest edges ascending in the order above: the two rows, the value
+ *                                          widened, the position p; entries behind m are not written;
+ *   *h_n_edges, *h_n_components            (host) m and C, the number of components of all edges;
+ *   *h_rounds                              (host, may be NULL) the Boruvka rounds that joined something (<= 31).
+ * The components at threshold t are those of the first `number of d_value <= t` edges (the values are non-decreasing under the
+ * IEEE comparison): kz_components_edges on that prefix equals kz_components_csr on the entries with value <= t, bit for bit.
+ * How: Boruvka in rounds, one thread per ENTRY.  Per round every entry between two components offers its key to both with an
+ * unsigned 64-bit atomicMin (behind a relaxed load that skips the atomic when the key is not smaller), a second pass breaks ties by
+ * position with an int atomicMin, every component marks its pick and hooks under the other end's component (of a mutual pick the
+ * smaller root stays), and the component array is flattened by pointer jumping.  One flag word is read back per round; the loop
+ * stops at the first round that joined nothing.  The marked entries are compacted by an integer scan and sorted by (key, p) with
+ * kz_csr_sort_rows' kernel.  Integer atomics only; no kernel waits for another workgroup; every loop is bounded.
+ * Limits, decided BEFORE anything is launched: kz_csr_require's (CSR), k >= 1 and the n_q / n_index ranges (lists), a dist_dtype that
+ * is not KZ_F32 / KZ_F64, a null output: KZ_ERR_INVALID; n_q + n_index >= 2^31 - 1 or n_q k > 2^31 - 2: KZ_ERR_UNSUPPORTED.  The CSR
+ * call runs the indptr validation of every CSR call first.  n_q == 0 and nnz == 0 are legal: m = 0, C = n_q + n_index.
+ * Transient device memory: 20 bytes per node and 12 bytes per entry, plus 16 bytes per forest edge for the sort when m > 4096.
+ * Synchronises the context's stream (once per round). */
+int kz_forest_csr(kz_ctx* ctx, const int64_t* d_indptr, const int64_t* d_ind, const void* d_dist, int dist_dtype, int64_t n_q, int64_t nnz,
+                  int64_t n_index, int64_t* d_source, int64_t* d_target, double* d_value, int64_t* d_entry, int64_t* h_n_edges,
+                  int64_t* h_n_components, int* h_rounds);
+int kz_forest_lists(kz_ctx* ctx, const void* d_dist, int dist_dtype, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index,
+                    int64_t* d_source, int64_t* d_target, double* d_value, int64_t* d_entry, int64_t* h_n_edges, int64_t* h_n_components,
+                    int* h_rounds);
+
 /* float64 -> float32 cast of an [count] array (cosine + float32 inputs keep the reference's output dtype). */
 int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count);
 

@@ -194,6 +194,11 @@ SYMBOLS = [
     ("kz_csr_sort_rows", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     ("kz_components_csr", C.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, C.POINTER(_I64)]),
     ("kz_components_lists", C.c_int, [_P, _P, _I64, C.c_int, _I64, _P, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_components_edges", C.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_forest_csr", C.c_int, [_P, _P, _P, _P, C.c_int, _I64, _I64, _I64, _P, _P, _P, _P, C.POINTER(_I64), C.POINTER(_I64),
+                                C.POINTER(C.c_int)]),
+    ("kz_forest_lists", C.c_int, [_P, _P, C.c_int, _P, _I64, C.c_int, _I64, _P, _P, _P, _P, C.POINTER(_I64), C.POINTER(_I64),
+                                  C.POINTER(C.c_int)]),
     ("kz_comm_unique_id", C.c_int, [_P]),
     ("kz_comm_create", C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("kz_comm_destroy", C.c_int, [_P]),
@@ -779,6 +784,8 @@ class PairList:
         "sinkhorn": ("kz_sinkhorn_lists", "kz_sinkhorn_csr", {}),
         "components": ("kz_components_lists", "kz_components_csr", {"values": False}),
     }
+    # the hierarchy of a pair list is no operation ON its pairs but another structure made from them: its pair of symbols, by layout
+    FOREST = ("kz_forest_lists", "kz_forest_csr")
 
     def __init__(self, ctx, dist, ind, indptr, n_target, n_q, width):
         self.ctx, self.dist, self.ind, self.indptr = ctx, dist, ind, indptr
@@ -953,6 +960,50 @@ class PairList:
         if not sizes:
             return label_q, label_t, n
         return label_q, label_t, size_q.view_rows(0, n), size_t.view_rows(0, n), n
+
+    def forest(self):
+        """kz_forest_lists / kz_forest_csr -> (source int64 [m], target int64 [m], value float64 [m], entry int64 [m], n_components,
+        rounds): the minimum spanning forest of the weighted pair graph on the device, its m = n_q + n_target - n_components edges
+        ascending by (the order key of the value, the entry's flat position `entry`); an entry with a NaN value is no edge.  The
+        components of the pairs with value <= t are those of the forest's edges with value <= t (`components_edges` on that prefix);
+        `rounds` counts the Boruvka rounds that joined something.  The same bytes from every run.  More than COMPONENTS_MAX_NODES
+        rows raise NotImplementedError."""
+        ctx, n_q, n_t = self.ctx, self.n_q, self.n_target
+        room = max(n_q + n_t - 1, 1) if n_q + n_t <= COMPONENTS_MAX_NODES else 1
+        source, target, entry = (ctx.empty((room,), np.int64) for _ in range(3))
+        value = ctx.empty((room,), np.float64)
+        m, count, rounds = _I64(0), _I64(0), C.c_int(0)
+        name = self.FOREST[self.is_csr]
+        _check(getattr(ctx.lib, name)(*self._head(dtype=True), n_t, source.ptr, target.ptr, value.ptr, entry.ptr, C.byref(m), C.byref(count),
+                                      C.byref(rounds)), name)
+        m = int(m.value)
+        return source.view_rows(0, m), target.view_rows(0, m), value.view_rows(0, m), entry.view_rows(0, m), int(count.value), int(rounds.value)
+
+
+def components_edges(ctx: Context, source: DeviceArray, target: DeviceArray, n_source: int, n_target: int, sizes: bool = False,
+                     count: Optional[int] = None):
+    """kz_components_edges -> what `PairList.components` returns, for the first `count` (default: all) edges of the int64 arrays
+    (source[e], target[e]): any order, an edge may repeat, an edge with an id out of range is no pair."""
+    for what, a in (("source", source), ("target", target)):
+        if not isinstance(a, DeviceArray) or len(a.shape) != 1 or a.dtype != np.int64:
+            raise ValueError(f"{what} must be a 1-D int64 DeviceArray, got {getattr(a, 'dtype', type(a).__name__)} {getattr(a, 'shape', '')}")
+    if source.shape != target.shape:
+        raise ValueError(f"source and target must be of one length, got {source.shape} and {target.shape}")
+    count = source.shape[0] if count is None else int(count)
+    if not 0 <= count <= source.shape[0]:
+        raise ValueError(f"count = {count} is outside [0, {source.shape[0]}]")
+    n_q, n_t = int(n_source), int(n_target)
+    label_q, label_t = ctx.empty((n_q,), np.int64), ctx.empty((n_t,), np.int64)
+    room = n_q + n_t if sizes and 1 <= n_q + n_t <= COMPONENTS_MAX_NODES else 0
+    size_q = ctx.empty((room,), np.int64) if sizes else None
+    size_t = ctx.empty((room,), np.int64) if sizes else None
+    n = _I64(0)
+    _call(ctx, "kz_components_edges", source.ptr, target.ptr, count, n_q, n_t, label_q.ptr, label_t.ptr, size_q.ptr if sizes else None,
+          size_t.ptr if sizes else None, C.byref(n))
+    n = int(n.value)
+    if not sizes:
+        return label_q, label_t, n
+    return label_q, label_t, size_q.view_rows(0, n), size_t.view_rows(0, n), n
 
 
 # ---- the calls of `PairList` by name and layout, as tests and tools take them ---------------------------------------------------

@@ -3,7 +3,8 @@
 // soft one (kz_softmin_lists.hip).  The graph is bipartite: source row i is node i, target row j is node n_q + j, and entry (i, t) of
 // the list with 0 <= t < n_index is an edge; any other entry is no pair (kz_match_lists' rule).  Every node gets the number of its
 // component, components counted 0 .. C - 1 in the order of their smallest node; every component its number of source and of target
-// rows.
+// rows.  Three front ends feed the same stages: a CSR, fixed-width lists, and an edge array (kz_components_edges: what labels a cut
+// of kz_forest.hip's forest).
 //
 // UNION-FIND ON int32 PARENT WORDS WITH parent[v] <= v, ALWAYS.  The invariant makes every tree acyclic and every walk a sequence of
 // strictly decreasing node ids, and the root of a finished tree the smallest node of its component: the answer does not depend on
@@ -61,6 +62,18 @@ __global__ __launch_bounds__(256) void kz_cc_init_kernel(int* __restrict__ paren
 // When it fails, hi had a parent `seen` < hi already: go on with (root above seen, lo) -- both below hi, so the larger of the pair
 // strictly decreases: at most max(a, b) rounds.  lo may have stopped being a root meanwhile: the link is then to an inner node,
 // which keeps parent[v] <= v and joins the two trees all the same.
+__device__ __forceinline__ void kz_cc_link(int* parent, int a, int b) {
+    a = kz_cc_find(parent, a);
+    b = kz_cc_find(parent, b);
+    while (a != b) {
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        int seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        a = kz_cc_find(parent, seen);   // (seen < hi: parent[hi] <= hi and it is not hi)
+        b = lo;
+    }
+}
+
 template <typename L>
 __global__ __launch_bounds__(256) void kz_cc_hook_kernel(int* parent, const int64_t* __restrict__ ind, L rows, int64_t n_q, int64_t n_entries,
                                                          int64_t n_index) {
@@ -68,15 +81,19 @@ __global__ __launch_bounds__(256) void kz_cc_hook_kernel(int* parent, const int6
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_entries; e += stride) {
         const int64_t t = ind[e];
         if (t < 0 || t >= n_index) continue;   // no pair
-        int a = kz_cc_find(parent, (int)kz_cc_row_of(rows, n_q, e));
-        int b = kz_cc_find(parent, (int)(n_q + t));
-        while (a != b) {
-            const int hi = a > b ? a : b, lo = a > b ? b : a;
-            int seen = hi;
-            if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-            a = kz_cc_find(parent, seen);   // (seen < hi: parent[hi] <= hi and it is not hi)
-            b = lo;
-        }
+        kz_cc_link(parent, (int)kz_cc_row_of(rows, n_q, e), (int)(n_q + t));
+    }
+}
+
+// The EDGE-ARRAY front end (kz_components_edges): edge e joins source row source[e] and target row target[e]; an edge with either id
+// out of range is no pair (the rule above, for both ends: nothing vouches for the source ids of a free-standing edge array).
+__global__ __launch_bounds__(256) void kz_cc_hook_edges_kernel(int* parent, const int64_t* __restrict__ source, const int64_t* __restrict__ target,
+                                                               int64_t n_q, int64_t n_edges, int64_t n_index) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_edges; e += stride) {
+        const int64_t i = source[e], t = target[e];
+        if (i < 0 || i >= n_q || t < 0 || t >= n_index) continue;   // no pair
+        kz_cc_link(parent, (int)i, (int)(n_q + t));
     }
 }
 
@@ -202,9 +219,10 @@ int kz_cc_require(const char* who, int64_t n_q, int64_t n_index, const int64_t* 
     return KZ_OK;
 }
 
-template <typename L>
-int kz_components_impl(kz_ctx* ctx, const int64_t* d_ind, L rows, int64_t n_q, int64_t n_entries, int64_t n_index, int64_t* d_label_q,
-                       int64_t* d_label_t, int64_t* d_size_q, int64_t* d_size_t, int64_t* h_n_components) {
+// `hook(parent)` queues the front end's hook launch (none when there is no entry): the one stage that reads the pairs
+template <typename H>
+int kz_components_impl(kz_ctx* ctx, H&& hook, int64_t n_q, int64_t n_index, int64_t* d_label_q, int64_t* d_label_t, int64_t* d_size_q,
+                       int64_t* d_size_t, int64_t* h_n_components) {
     const int n_nodes = (int)(n_q + n_index), n_tiles = (int)((n_q + n_index + 255) / 256);
     // (released when the function returns, behind its synchronise)
     KzPoolBuf<int> parent, root, rank, tile;
@@ -217,9 +235,7 @@ int kz_components_impl(kz_ctx* ctx, const int64_t* d_ind, L rows, int64_t n_q, i
     if (rc != KZ_OK) return rc;
     const dim3 nodes(kz_blocks(n_nodes, 4096)), wg(256);
     hipLaunchKernelGGL(kz_cc_init_kernel, nodes, wg, 0, ctx->stream, parent.get(), n_nodes);
-    if (n_entries > 0)
-        hipLaunchKernelGGL((kz_cc_hook_kernel<L>), dim3(kz_blocks(n_entries, 4096)), wg, 0, ctx->stream, parent.get(), d_ind, rows, n_q, n_entries,
-                           n_index);
+    hook(parent.get());
     hipLaunchKernelGGL(kz_cc_flatten_kernel, nodes, wg, 0, ctx->stream, (const int*)parent.get(), root.get(), n_nodes);
     hipLaunchKernelGGL(kz_cc_tile_sums_kernel, dim3(n_tiles), wg, 0, ctx->stream, (const int*)root.get(), n_nodes, tile.get());
     hipLaunchKernelGGL(kz_cc_tile_bases_kernel, dim3(1), wg, 0, ctx->stream, tile.get(), n_tiles, count.get());
@@ -232,6 +248,16 @@ int kz_components_impl(kz_ctx* ctx, const int64_t* d_ind, L rows, int64_t n_q, i
     KZ_HIP(hipMemcpyAsync(h_n_components, count.get(), sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     KZ_HIP(hipStreamSynchronize(ctx->stream));
     return KZ_OK;
+}
+
+// the hook launch of the two list layouts
+template <typename L>
+auto kz_cc_list_hook(kz_ctx* ctx, const int64_t* d_ind, L rows, int64_t n_q, int64_t n_entries, int64_t n_index) {
+    return [=](int* parent) {
+        if (n_entries > 0)
+            hipLaunchKernelGGL((kz_cc_hook_kernel<L>), dim3(kz_blocks(n_entries, 4096)), dim3(256), 0, ctx->stream, parent, d_ind, rows, n_q,
+                               n_entries, n_index);
+    };
 }
 
 }  // namespace
@@ -247,7 +273,8 @@ extern "C" int kz_components_csr(kz_ctx* ctx, const int64_t* d_indptr, const int
     KZ_HIP(hipSetDevice(ctx->device));
     const int rcv = kz_csr_validate("kz_components_csr", ctx, d_indptr, n_q, nnz);
     if (rcv != KZ_OK) return rcv;
-    return kz_components_impl(ctx, d_ind, KzRowsCsr{d_indptr}, n_q, nnz, n_index, d_label_q, d_label_t, d_size_q, d_size_t, h_n_components);
+    return kz_components_impl(ctx, kz_cc_list_hook(ctx, d_ind, KzRowsCsr{d_indptr}, n_q, nnz, n_index), n_q, n_index, d_label_q, d_label_t, d_size_q,
+                              d_size_t, h_n_components);
 }
 
 extern "C" int kz_components_lists(kz_ctx* ctx, const int64_t* d_ind, int64_t n_q, int k, int64_t n_index, int64_t* d_label_q,
@@ -266,5 +293,25 @@ extern "C" int kz_components_lists(kz_ctx* ctx, const int64_t* d_ind, int64_t n_
     KZ_REQUIRE(n_q == 0 || d_ind, "kz_components_lists: null argument");
     *h_n_components = 0;
     KZ_HIP(hipSetDevice(ctx->device));
-    return kz_components_impl(ctx, d_ind, KzRowsFixed{k}, n_q, n_entries, n_index, d_label_q, d_label_t, d_size_q, d_size_t, h_n_components);
+    return kz_components_impl(ctx, kz_cc_list_hook(ctx, d_ind, KzRowsFixed{k}, n_q, n_entries, n_index), n_q, n_index, d_label_q, d_label_t, d_size_q,
+                              d_size_t, h_n_components);
+}
+
+// The same five stages behind an EDGE ARRAY (source[e], target[e]), e < count, in any order, edges repeated or not: what a cut of
+// kz_forest_*'s forest is labelled with.  One thread per edge.
+extern "C" int kz_components_edges(kz_ctx* ctx, const int64_t* d_source, const int64_t* d_target, int64_t count, int64_t n_q, int64_t n_index,
+                                   int64_t* d_label_q, int64_t* d_label_t, int64_t* d_size_q, int64_t* d_size_t, int64_t* h_n_components) {
+    const int rcq = kz_csr_require("kz_components_edges", ctx, n_q, count, n_index);   // (the limits of a CSR of `count` entries)
+    if (rcq != KZ_OK) return rcq;
+    const int rcc = kz_cc_require("kz_components_edges", n_q, n_index, d_label_q, d_label_t, d_size_q, d_size_t, h_n_components);
+    if (rcc != KZ_OK) return rcc;
+    KZ_REQUIRE(count == 0 || (d_source && d_target), "kz_components_edges: null argument");
+    *h_n_components = 0;
+    KZ_HIP(hipSetDevice(ctx->device));
+    auto hook = [=](int* parent) {
+        if (count > 0)
+            hipLaunchKernelGGL(kz_cc_hook_edges_kernel, dim3(kz_blocks(count, 4096)), dim3(256), 0, ctx->stream, parent, d_source, d_target, n_q,
+                               count, n_index);
+    };
+    return kz_components_impl(ctx, hook, n_q, n_index, d_label_q, d_label_t, d_size_q, d_size_t, h_n_components);
 }

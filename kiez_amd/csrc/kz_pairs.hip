@@ -310,6 +310,15 @@ int kz_pairs_raw_values(kz_ctx* ctx, const kz_matrix* query, const kz_matrix* in
     return KZ_OK;
 }
 
+// THE FLAG SCAN (kz_rows.h): the three launches above on the context's stream, total >= 1.  Shared with kz_forest.hip's compaction.
+void kz_scan_flags(kz_ctx* ctx, const int* d_keep, int total, int* d_tile, int* d_place) {
+    const int n_tiles = (total + 255) / 256;
+    const dim3 wg(256);
+    hipLaunchKernelGGL(kz_pc_tile_sums_kernel, dim3(n_tiles), wg, 0, ctx->stream, d_keep, total, d_tile);
+    hipLaunchKernelGGL(kz_pc_tile_bases_kernel, dim3(1), wg, 0, ctx->stream, d_tile, n_tiles, total, d_place);
+    hipLaunchKernelGGL(kz_pc_places_kernel, dim3(n_tiles), wg, 0, ctx->stream, d_keep, total, (const int*)d_tile, d_place);
+}
+
 extern "C" int kz_lists_combine(kz_ctx* ctx, const int64_t* d_fwd_ind, int64_t n_q, int k_f, const int64_t* d_rev_ind, int64_t n_index, int k_r,
                                 int mode, int64_t capacity, int64_t* d_indptr, int64_t* d_ind, int64_t* h_total) {
     KZ_REQUIRE(ctx && d_indptr && h_total, "kz_lists_combine: null argument");
@@ -363,9 +372,7 @@ extern "C" int kz_lists_combine(kz_ctx* ctx, const int64_t* d_fwd_ind, int64_t n
     int* keep = d.get();
     hipLaunchKernelGGL(kz_pc_targets_kernel, grid, wg, 0, ctx->stream, in, row_key, pos, tgt);
     hipLaunchKernelGGL(kz_pc_keep_kernel, grid, wg, 0, ctx->stream, in, mode, row_key, (const int*)tgt, pos, keep);
-    hipLaunchKernelGGL(kz_pc_tile_sums_kernel, dim3(n_tiles), wg, 0, ctx->stream, (const int*)keep, total, tile.get());
-    hipLaunchKernelGGL(kz_pc_tile_bases_kernel, dim3(1), wg, 0, ctx->stream, tile.get(), n_tiles, total, place.get());
-    hipLaunchKernelGGL(kz_pc_places_kernel, dim3(n_tiles), wg, 0, ctx->stream, (const int*)keep, total, (const int*)tile.get(), place.get());
+    kz_scan_flags(ctx, keep, total, tile.get(), place.get());
     hipLaunchKernelGGL(kz_pc_indptr_kernel, dim3(kz_blocks(n_q + 1, 4096)), wg, 0, ctx->stream, row_key, total, n_q, (const int*)place.get(), d_indptr);
     if (capacity > 0)
         hipLaunchKernelGGL(kz_pc_fill_kernel, grid, wg, 0, ctx->stream, row_key, (const int*)tgt, (const int*)keep, (const int*)place.get(), total,

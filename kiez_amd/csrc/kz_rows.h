@@ -43,6 +43,11 @@ int kz_csr_validate(const char* who, kz_ctx* ctx, const int64_t* d_indptr, int64
 int kz_match_require(const char* who, kz_ctx* ctx, const void* d_dist, int dist_dtype, int64_t n_q, int k);
 int kz_sl_require(const char* who, kz_ctx* ctx, int64_t n_q, int k, int64_t n_index);
 
+// The exclusive prefix sum of `total` >= 1 int flags (kz_pairs.hip: tile sums, one workgroup over the tile totals, the tile again),
+// queued on the context's stream: d_place[p] = the flags in front of place p, d_place[total] = their sum; d_tile: scratch of
+// ceil(total / 256) ints.  Integer adds: the same bytes from every run.
+void kz_scan_flags(kz_ctx* ctx, const int* d_keep, int total, int* d_tile, int* d_place);
+
 // THE dispatch on a pair list's value type: f(the typed pointer) for a dist_dtype a *_require has checked (KZ_F32 or KZ_F64)
 template <typename F>
 static inline auto kz_with_values(int dist_dtype, const void* d_dist, F&& f) {

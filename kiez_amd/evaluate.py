@@ -179,3 +179,37 @@ def cluster_metrics(source_label, target_label, gold) -> Dict[str, Any]:
     f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
     return {"precision": precision, "recall": recall, "f1": f1, "n_pairs": n_pairs, "n_true": n_true, "n_gold": n_gold,
             "n_components": n_components}
+
+
+def cluster_curve(hierarchy, gold, thresholds=None, max_points: int = 64) -> Dict[str, Any]:
+    """Precision, recall and F1 of the clustering at a sweep of thresholds, from one single-linkage hierarchy
+    (`matching.single_linkage_csr`, `Kiez.hierarchy_radius`, `Kiez.hierarchy_pairs`): every point is `hierarchy.cut(t)` scored by
+    `cluster_metrics` -- a components call over at most n_source + n_target - 1 edges, no join.
+
+    `thresholds`: the values of t (any order, no NaN); None: at most `max_points` of the DISTINCT forest values at evenly spaced
+    positions, the largest one included -- the thresholds at which the clustering changes.  Returns {"threshold", "precision",
+    "recall", "f1" (float64 arrays), "n_components", "n_pairs" (int64 arrays; n_pairs as Python ints in an object array where it
+    exceeds int64), "best": the first index of the largest F1 (None for an empty sweep)}."""
+    if thresholds is None:
+        if isinstance(max_points, (bool, np.bool_)) or not isinstance(max_points, (int, np.integer)) or max_points < 1:
+            raise ValueError(f"max_points must be a positive integer, got {max_points!r}")
+        distinct = np.unique(hierarchy.value)   # (ascending; -0.0 and +0.0 are one value)
+        if distinct.size > max_points:
+            # evenly spaced positions that end at the last one (one point: the last)
+            pos = np.round(np.linspace(0 if max_points > 1 else distinct.size - 1, distinct.size - 1, max_points)).astype(np.int64)
+            distinct = distinct[np.unique(pos)]
+        ts = distinct
+    else:
+        ts = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+        if np.isnan(ts).any():
+            raise ValueError("thresholds must not hold NaN")
+    points = [cluster_metrics(*hierarchy.cut(float(t)), gold) for t in ts]
+    n_pairs = [p["n_pairs"] for p in points]
+    f1 = np.array([p["f1"] for p in points], dtype=np.float64)
+    return {"threshold": np.asarray(ts, dtype=np.float64),
+            "precision": np.array([p["precision"] for p in points], dtype=np.float64),
+            "recall": np.array([p["recall"] for p in points], dtype=np.float64),
+            "f1": f1,
+            "n_components": np.array([p["n_components"] for p in points], dtype=np.int64),
+            "n_pairs": np.array(n_pairs, dtype=np.int64 if all(n < 2 ** 63 for n in n_pairs) else object),
+            "best": int(np.argmax(f1)) if f1.size else None}

@@ -332,6 +332,21 @@ class Kiez:
         `components_radius` returns."""
         return tuple(x.numpy() for x in self.components_pairs_device(k, mode, reduced, return_sizes))
 
+    # ---- the same two CSRs, then the single-linkage hierarchy: the clusters at EVERY tighter threshold from one join ------------
+    def hierarchy_radius(self, radius, reduced: bool = False):
+        """One loose join, every tighter threshold: the single-linkage hierarchy (`matching.Hierarchy`) of the pairs of
+        `radius_neighbors(radius, reduced=reduced)` -- every check and error of that call applies.  `h.cut(t)` for t <= radius equals
+        `components_radius(t, reduced=reduced)` without walking the index again, `h.n_clusters(t)` is host arithmetic and
+        `evaluate.cluster_curve(h, gold)` scores a sweep of thresholds.  The CSR never leaves HBM (kz_forest_csr)."""
+        from . import matching
+        return matching._hierarchy_of(self._pairs_within_radius(radius, reduced))
+
+    def hierarchy_pairs(self, k: Optional[int] = None, mode: str = "union", reduced: bool = False):
+        """`hierarchy_radius` over the pairs of `neighbor_pairs(k, mode, reduced)` -- every check and error of that call applies:
+        `h.cut(t)` are the clusters of those pairs with value <= t.  The CSR never leaves HBM (kz_forest_csr)."""
+        from . import matching
+        return matching._hierarchy_of(self._pairs_of_both_directions(k, mode, reduced))
+
     def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
         """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
         ranks into hits@k, mean rank and mean reciprocal rank).

@@ -398,3 +398,101 @@ def components(ind, n_target: int, *, return_sizes: bool = False, ctx: Optional[
     entry outside [0, n_target) -- a -1, the INT_MAX padding of `kneighbors_whole_index` -- is no pair.  Every result and error as
     `components_csr`."""
     return _components(ind, None, n_target, return_sizes, ctx)
+
+
+# ---- the single-linkage hierarchy of a weighted pair list: clusters at every threshold (kz_forest_csr, kz_forest_lists) -----------
+def _checked_threshold(t) -> float:
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)):
+        raise ValueError(f"the threshold must be a real number, got {t!r}")
+    t = float(t)
+    if t != t:
+        raise ValueError("the threshold must not be NaN (+inf and -inf are fine)")
+    return t
+
+
+class Hierarchy:
+    """The single-linkage hierarchy of a weighted pair list: its minimum spanning forest, which holds the clusters of the pairs with
+    value <= t for EVERY threshold t (`single_linkage_csr`, `single_linkage`, `Kiez.hierarchy_radius`, `Kiez.hierarchy_pairs`).
+
+    `n_source`, `n_target`; `n_components`: the clusters of all pairs; `source`, `target` (int64), `value` (float64), `entry` (int64)
+    [m], m = n_source + n_target - n_components: the forest's edges as numpy arrays, ascending by (value, `entry`) with -0.0 equal to
+    +0.0 -- `entry` is the position of the edge in the pair list it came from (the CSR position, or i * k + c).  `rounds`: the rounds
+    the device took (None for a hierarchy built from arrays).  The device copies of `source` / `target` are kept for the cuts."""
+
+    def __init__(self, n_source, n_target, n_components, source, target, value, entry, *, rounds=None, device=None, ctx=None):
+        self.n_source, self.n_target, self.n_components = int(n_source), int(n_target), int(n_components)
+        self.source, self.target = np.asarray(source, dtype=np.int64), np.asarray(target, dtype=np.int64)
+        self.value, self.entry = np.asarray(value, dtype=np.float64), np.asarray(entry, dtype=np.int64)
+        m = self.value.shape[0]
+        if not (self.source.shape == self.target.shape == self.entry.shape == self.value.shape == (m,)):
+            raise ValueError("source, target, value and entry must be 1-D arrays of one length")
+        if m != self.n_source + self.n_target - self.n_components:
+            raise ValueError(f"a forest of {self.n_source + self.n_target} nodes and {self.n_components} components has "
+                             f"{self.n_source + self.n_target - self.n_components} edges, got {m}")
+        if m and (np.isnan(self.value).any() or bool((self.value[1:] < self.value[:-1]).any())):
+            raise ValueError("value must be ascending and hold no NaN")
+        self.rounds = rounds
+        self._device, self._ctx = device, ctx   # (source, target) as DeviceArrays, uploaded by the first cut when not given
+
+    def n_edges(self, t) -> int:
+        """The forest edges with value <= t: the length of the prefix a cut at t uses."""
+        return int(np.searchsorted(self.value, _checked_threshold(t), side="right"))
+
+    def n_clusters(self, t) -> int:
+        """The number of clusters of the pairs with value <= t: every forest edge joins two.  Host arithmetic."""
+        return self.n_source + self.n_target - self.n_edges(t)
+
+    def cut_device(self, t, return_sizes: bool = False):
+        """Like `cut` but the label (and size) arrays stay in HBM as DeviceArrays."""
+        count = self.n_edges(t)
+        if self._device is None:
+            ctx = self._ctx or N.Context.get()
+            self._device, self._ctx = (ctx.to_device(self.source), ctx.to_device(self.target)), ctx
+        source, target = self._device
+        res = N.components_edges(source.ctx, source, target, self.n_source, self.n_target, bool(return_sizes), count=count)
+        return tuple(res[:4] if return_sizes else res[:2])
+
+    def cut(self, t, return_sizes: bool = False):
+        """The clusters of the pairs with value <= t (IEEE comparison; t = +-inf is fine, NaN raises ValueError before the device is
+        touched): what `components_csr` returns for the pair list restricted to those entries, bit for bit -- `(source_label,
+        target_label)`, with `return_sizes=True` also `(n_source_in, n_target_in)` -- from a components call over the forest's prefix
+        (kz_components_edges), at most n_source + n_target - 1 edges however many pairs the list held."""
+        return tuple(x.numpy() for x in self.cut_device(t, return_sizes))
+
+
+def _single_linkage(dist, ind, indptr, n_target, ctx):
+    if dist is None:
+        raise ValueError("single linkage needs the values of the pairs: dist is None")
+    dist, ind, indptr = _checked(dist, ind, indptr, n_target)
+    n_source = ind.shape[0] if indptr is None else indptr.shape[0] - 1
+    _checked_node_count(n_source, int(n_target))
+    if indptr is None and ind.shape[0] * ind.shape[1] > 2 ** 31 - 2:
+        raise ValueError(f"ind has {ind.shape[0] * ind.shape[1]} entries, the limit is 2**31 - 2")
+    pairs, _ = _uploaded((dist, ind, indptr), n_target, ctx)
+    return _hierarchy_of(pairs)
+
+
+def _hierarchy_of(pairs):
+    """The forest of a `PairList` with values -> a `Hierarchy` (numpy copies for the host side, the device edges for the cuts)."""
+    source, target, value, entry, n_components, rounds = pairs.forest()
+    return Hierarchy(pairs.n_q, pairs.n_target, n_components, source.numpy(), target.numpy(), value.numpy(), entry.numpy(), rounds=rounds,
+                     device=(source, target), ctx=pairs.ctx)
+
+
+def single_linkage_csr(indptr, ind, dist, n_target: int, *, ctx: Optional[N.Context] = None) -> Hierarchy:
+    """The single-linkage hierarchy of a weighted pair list, on the device (kz_forest_csr): ONE call that answers "which clusters do the
+    pairs with value <= t form" for every t, where `components_csr` answers it for the one threshold the list was produced with.
+
+    `indptr`, `ind`, `dist`: a CSR as `one_to_one_csr` takes it (numpy arrays or `DeviceArray`s; float32 or float64 values).  An entry
+    is an edge when 0 <= ind < n_target and its value is not NaN; -inf, +inf, -0.0 and negative values are legal; a pair stored twice
+    counts with its smaller value.  The result is the minimum spanning forest under the order (value, position of the entry), -0.0
+    equal to +0.0: unique, the same bytes from every run.  Returns a `Hierarchy`; `Hierarchy.cut(t)` equals `components_csr` of the
+    entries with value <= t bit for bit, `evaluate.cluster_curve` scores a sweep of thresholds against gold.  Argument errors are
+    raised before the device is touched.  Fixed-width lists: `single_linkage`."""
+    return _single_linkage(dist, ind, indptr, n_target, ctx)
+
+
+def single_linkage(dist, ind, n_target: int, *, ctx: Optional[N.Context] = None) -> Hierarchy:
+    """`single_linkage_csr` over fixed-width lists `dist`, `ind` [n_source, k] (kz_forest_lists), any k >= 1; `Hierarchy.entry` is
+    i * k + c.  An entry outside [0, n_target) -- a -1, the INT_MAX padding of `kneighbors_whole_index` -- is no pair."""
+    return _single_linkage(dist, ind, None, n_target, ctx)
