@@ -266,6 +266,68 @@ int kz_dsl_finalize(kz_ctx* ctx, double* d_out, int64_t count, double min_value,
 int kz_select_topk(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, int k,
                    double* d_odist, int64_t* d_oind);
 
+/* ---- the tail of kneighbors in one launch: rescale + final sort + output cast -- ABI v7, additive ------------------------------ */
+/* The hubness kinds of kz_rescale_select and kz_fit.  1 .. 4 share the numbering of KZ_RANK_* below (the pointwise reductions);
+ * KZ_HUB_NONE leaves the distances as they are, KZ_HUB_MP_EMPIRIC is a kind of kz_fit only. */
+enum { KZ_HUB_NONE = 0, KZ_HUB_CSLS = 1, KZ_HUB_LS = 2, KZ_HUB_NICDM = 3, KZ_HUB_MP_NORMAL = 4, KZ_HUB_MP_EMPIRIC = 5 };
+/* For the forward candidates d_dist / d_ind [n, K]: per row the query-side statistic (CSLS, NICDM: ndarray.mean in numpy's pairwise
+ * order; LS: the last entry; MP normal: np.nanmean / np.nanstd), w of every candidate (kind KZ_HUB_NONE: w = d), the selection of
+ * kz_select_topk (first minimum wins, swap history kept, NaN last) and the store of the first k values and ids -- bit for bit what
+ * kz_csls / kz_local_scaling / kz_mp_normal -> kz_select_topk -> kz_cast_f64_f32 give, NaN payloads included, without the two [n, K]
+ * intermediates.  d_t_a / d_t_b: the index-side state vectors as those calls take them (CSLS r_train; LS / NICDM r_t; MP normal
+ * mu_t and sd_t; d_t_b is read by MP normal only, neither by KZ_HUB_NONE).  out_dtype KZ_F64 or KZ_F32: the type of d_odist [n, k]; for
+ * KZ_F32 the cast comes LAST, after the selection.  d_oind: [n, k].  K <= 128 runs ONE kernel (64 rows per wave on a transposed image
+ * in LDS); beyond that the call runs the kernels named above in sequence on transient buffers itself: same result.
+ * k outside [1, K], an unknown kind (KZ_HUB_MP_EMPIRIC included: kz_mp_empiric reads the reverse lists), another out_dtype or a NULL
+ * state the kind reads: KZ_ERR_INVALID before anything is written.  d_ind is trusted as in kz_csls. */
+int kz_rescale_select(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, int k, int kind,
+                      const double* d_t_a, const double* d_t_b, int out_dtype, void* d_odist, int64_t* d_oind);
+
+/* ---- one call per fit and per kneighbors: HubnessReduction.fit / .kneighbors (base.py:33-50, 89-105) -- ABI v7, additive -------- */
+/* kz_fit decides which searches serve the two directions, runs those that belong to the fit and computes the fit state of the
+ * reduction; kz_kneighbors runs the forward search where the fit did not, the rescaling, the final sort and the output cast, and
+ * writes into the caller's buffers.  The decisions are a pure host function (kiez_amd/csrc/kz_fit_plan.h):
+ *   two-sided, shared_sweep != 0   kz_knn_dual with the larger matrix first (it searches twice by itself where no sweep applies)
+ *   shared_sweep == 0              the reverse kz_knn only (target rows against the source, nothing stripped); the forward search
+ *                                  runs at the first kz_kneighbors
+ *   single source (target NULL), shared_sweep != 0, n_candidates + 1 <= min(n, 110)
+ *                                  ONE kz_knn(source, source, n_candidates + 1, exclude_self = 0) + kz_split_self
+ *   any other single-source fit    the reverse search without stripping; the forward search (exclude_self = 1) at the first kz_kneighbors
+ *   KZ_HUB_NONE                    no search at all: kz_kneighbors is one kz_knn for k neighbours (exclude_self for single source)
+ * Refused before any launch: a reduction with n_candidates < 2, n_candidates above min(n_source, n_target) (above n - 1 for single
+ * source: clamping with a warning is the caller's business) and matrices that disagree in context, feature count, element type or
+ * metric: KZ_ERR_INVALID; n_candidates > 4095 and a precomputed matrix: KZ_ERR_UNSUPPORTED.
+ * The fitted object BORROWS the two matrices (the caller keeps them alive until kz_fitted_destroy) and OWNS the reverse lists, the
+ * fit state and -- once they exist, until kz_fitted_destroy -- the forward lists (16 n_source n_candidates bytes): a second
+ * kz_kneighbors with another k runs no search (KZ_HUB_NONE searches for k neighbours each time).
+ * Not here: ad-hoc query rows, the target -> source direction, DisSimLocal and the dual-potential reductions. */
+typedef struct kz_fitted kz_fitted;
+typedef struct kz_fit_info {
+    int64_t n_source, n_target;  /* n_target = n_source for single source */
+    int32_t n_candidates, hubness, single_source, shared_sweep;
+    int32_t search;              /* the plan that ran: 0 none, 1 kz_knn_dual, 2 reverse search only, 3 single-source split */
+    int32_t larger_first;        /* search 1: 1 = the source was kz_knn_dual's first matrix, 0 = the target */
+    int32_t tail;                /* 0 kz_knn, 1 kz_rescale_select, 2 kz_mp_empiric + kz_select_topk + cast */
+    int32_t fused;               /* tail 1: 1 = the fused kernel serves n_candidates, 0 = the kernel sequence */
+    int32_t forward_ready;       /* the forward lists exist */
+    int32_t n_searches;          /* search calls (kz_knn / kz_knn_dual) made for this object so far */
+    kz_knn_stats stats_forward;  /* of the source -> target search (the one search of a single-source split); zero before it ran */
+    kz_knn_stats stats_reverse;  /* of the target -> source search; zero where none ran (split, KZ_HUB_NONE) */
+} kz_fit_info;
+/* hubness: KZ_HUB_*; n_candidates: K; target NULL: single source.  *out: the fitted object. */
+int kz_fit(kz_ctx* ctx, const kz_matrix* source, const kz_matrix* target, int hubness, int n_candidates, int shared_sweep,
+           kz_fitted** out);
+/* 1 <= k <= n_candidates; out_dtype KZ_F64 / KZ_F32: the type of d_dist [n_source, k] (the cast comes last); d_ind: [n_source, k]. */
+int kz_kneighbors(kz_fitted* f, int k, int out_dtype, void* d_dist, int64_t* d_ind);
+int kz_fitted_info(const kz_fitted* f, kz_fit_info* out);
+/* Borrowed device pointers into the fitted object, valid until kz_fitted_destroy: *d_ptr (NULL where the object holds no such array:
+ * the forward lists before they exist, a state the kind does not have), *rows and *cols (1 for a state vector). */
+enum { KZ_FIT_REVERSE_DIST = 0, KZ_FIT_REVERSE_IND = 1, KZ_FIT_FORWARD_DIST = 2, KZ_FIT_FORWARD_IND = 3, KZ_FIT_STATE_A = 4,
+       KZ_FIT_STATE_B = 5 };
+int kz_fitted_state(const kz_fitted* f, int what, const void** d_ptr, int64_t* rows, int* cols);
+/* Releases what the object owns (stream-ordered, as kz_free); NULL is fine. */
+int kz_fitted_destroy(kz_fitted* f);
+
 /* ---- multi-GPU exchange step (source row-sharded, SURVEY.md section 8e "alternative": per-shard partial top-K + merge) ----- */
 /* The reverse search of HubnessReduction.fit (every target row against ALL source rows, base.py:37-42) over a row-sharded
  * source is the merge of the per-shard searches.  kz_knn orders neighbours by the exact float64 value (squared euclidean /

@@ -106,6 +106,29 @@ class KnnStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class FitInfo(C.Structure):
+    """kz_fit_info: the sizes, the plan that ran and the statistics of the searches of a fitted object."""
+    _fields_ = [
+        ("n_source", C.c_int64),
+        ("n_target", C.c_int64),
+        ("n_candidates", C.c_int32),
+        ("hubness", C.c_int32),
+        ("single_source", C.c_int32),
+        ("shared_sweep", C.c_int32),
+        ("search", C.c_int32),
+        ("larger_first", C.c_int32),
+        ("tail", C.c_int32),
+        ("fused", C.c_int32),
+        ("forward_ready", C.c_int32),
+        ("n_searches", C.c_int32),
+        ("stats_forward", KnnStats),
+        ("stats_reverse", KnnStats),
+    ]
+
+    def as_dict(self):
+        return {name: (getattr(self, name).as_dict() if name.startswith("stats_") else getattr(self, name)) for name, _ in self._fields_}
+
+
 # every symbol include/kiez_amd.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -153,6 +176,12 @@ SYMBOLS = [
     ("kz_dsl_finalize", C.c_int, [_P, _P, _I64, C.c_double, C.c_int]),
     ("kz_select_topk", C.c_int, [_P, _P, _P, _I64, C.c_int, C.c_int, _P, _P]),
     ("kz_cast_f64_f32", C.c_int, [_P, _P, _P, _I64]),
+    ("kz_rescale_select", C.c_int, [_P, _P, _P, _I64, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    ("kz_fit", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    ("kz_kneighbors", C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    ("kz_fitted_info", C.c_int, [_P, C.POINTER(FitInfo)]),
+    ("kz_fitted_state", C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_I64), C.POINTER(C.c_int)]),
+    ("kz_fitted_destroy", C.c_int, [_P]),
     ("kz_minmax_i64", C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     ("kz_minmax_i64_2d", C.c_int, [_P, _P, _I64, C.c_int, C.c_int, C.POINTER(_I64), C.POINTER(_I64)]),
     ("kz_k_occurrence", C.c_int, [_P, _P, _I64, C.c_int, C.c_int, _I64, _P]),
@@ -1343,3 +1372,96 @@ def cast_f32(ctx: Context, arr: DeviceArray) -> DeviceArray:
     out = ctx.empty(arr.shape, np.float32)
     _call(ctx, "kz_cast_f64_f32", arr.ptr, out.ptr, int(np.prod(arr.shape, dtype=np.int64)))
     return out
+
+
+# ---- the tail of kneighbors in one launch, and one call per fit / kneighbors --------------------------------------------------------
+HUB_NONE, HUB_CSLS, HUB_LS, HUB_NICDM, HUB_MP_NORMAL, HUB_MP_EMPIRIC = 0, 1, 2, 3, 4, 5   # KZ_HUB_*: 1 .. 4 are RANK_CSLS .. RANK_MP_NORMAL
+FIT_SEARCH_NONE, FIT_SEARCH_DUAL, FIT_SEARCH_REVERSE, FIT_SEARCH_SPLIT = 0, 1, 2, 3       # FitInfo.search
+FIT_TAIL_KNN, FIT_TAIL_FUSED, FIT_TAIL_EMPIRIC = 0, 1, 2                                  # FitInfo.tail
+RESCALE_SELECT_FUSED_MAX_K = 128   # candidates per row the fused kernel takes; beyond, kz_rescale_select runs the kernel sequence itself
+
+
+def _dtype_code(out_dtype) -> int:
+    dt = np.dtype(out_dtype)
+    if dt not in (np.float32, np.float64):
+        raise ValueError(f"out_dtype must be float32 or float64, got {dt}")
+    return KZ_F32 if dt == np.float32 else KZ_F64
+
+
+def rescale_select(ctx: Context, dist, ind, k: int, kind: int, t_a=None, t_b=None, out_dtype=np.float64, alloc=None):
+    """kz_rescale_select: rescale (`kind`: HUB_NONE .. HUB_MP_NORMAL, index-side state `t_a` / `t_b`) + `_sort` selection + output cast
+    of candidate lists dist / ind [n, K] -> (dist `out_dtype` [n, k], ind int64 [n, k])."""
+    alloc = alloc or ctx.empty
+    code = _dtype_code(out_dtype)
+    n, K = dist.shape
+    cols = int(k) if 1 <= int(k) <= K else 1   # (a k the library refuses sizes nothing: the refusal is the library's, nothing is written)
+    od, oi = alloc((n, cols), np.dtype(out_dtype)), alloc((n, cols), np.int64)
+    _call(ctx, "kz_rescale_select", _ptr(dist, "dist"), _ptr(ind, "ind"), n, K, int(k), int(kind), _ptr(t_a, "t_a"), _ptr(t_b, "t_b"), code,
+          _ptr(od), _ptr(oi))
+    return od, oi
+
+
+class Fitted:
+    """kz_fitted: a whole fit in the library -- the reverse lists, the fit state of the reduction and, once they exist, the forward
+    lists.  It borrows the two matrices (held here, so they outlive it) and is released by `close()` or garbage collection."""
+
+    STATE = {"reverse_dist": (0, np.float64), "reverse_ind": (1, np.int64), "forward_dist": (2, np.float64), "forward_ind": (3, np.int64),
+             "state_a": (4, np.float64), "state_b": (5, np.float64)}
+
+    def __init__(self, ctx: Context, handle, source_m: DeviceMatrix, target_m: Optional[DeviceMatrix]):
+        self.ctx, self.handle = ctx, handle
+        self._matrices = (source_m, target_m)
+        self.n_query = source_m.shape[0]
+        self.n_candidates = self.info["n_candidates"]
+
+    def kneighbors(self, k: int, out_dtype=np.float64, alloc=None):
+        """kz_kneighbors -> (dist `out_dtype` [n_source, k], ind int64 [n_source, k]) on the device; 1 <= k <= n_candidates."""
+        if not self.handle:
+            raise ValueError("the fitted object has been closed")
+        alloc = alloc or self.ctx.empty
+        code = _dtype_code(out_dtype)
+        cols = int(k) if 1 <= int(k) <= self.n_candidates else 1   # (a k the library refuses sizes nothing: the refusal is the library's)
+        od, oi = alloc((self.n_query, cols), np.dtype(out_dtype)), alloc((self.n_query, cols), np.int64)
+        _check(self.ctx.lib.kz_kneighbors(self.handle, int(k), code, _ptr(od), _ptr(oi)), "kz_kneighbors")
+        return od, oi
+
+    @property
+    def info(self) -> dict:
+        """kz_fitted_info as a dict: sizes, the plan that ran (`search`, `tail`, ...) and `stats_forward` / `stats_reverse`."""
+        if not self.handle:
+            raise ValueError("the fitted object has been closed")
+        st = FitInfo()
+        _check(self.ctx.lib.kz_fitted_info(self.handle, C.byref(st)), "kz_fitted_info")
+        return st.as_dict()
+
+    def state(self, name: str) -> Optional[DeviceArray]:
+        """kz_fitted_state: a non-owning DeviceArray over one of `Fitted.STATE` (lists [rows, n_candidates], state vectors [rows]) that
+        keeps this object alive; None where the object holds no such array (forward lists before they exist, a state the kind lacks)."""
+        if not self.handle:
+            raise ValueError("the fitted object has been closed")
+        if name not in self.STATE:
+            raise ValueError(f"unknown state {name!r}: one of {sorted(self.STATE)}")
+        what, dtype = self.STATE[name]
+        p, rows, cols = _P(), _I64(0), C.c_int(0)
+        _check(self.ctx.lib.kz_fitted_state(self.handle, what, C.byref(p), C.byref(rows), C.byref(cols)), "kz_fitted_state")
+        if not p.value:
+            return None
+        shape = (rows.value,) if what >= 4 else (rows.value, cols.value)
+        return DeviceArray(self.ctx, shape, dtype, ptr=p.value, owner=self)
+
+    def close(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            try:
+                self.ctx.lib.kz_fitted_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def fit(ctx: Context, source_m: DeviceMatrix, target_m: Optional[DeviceMatrix], kind: int, K: int, shared_sweep: bool = True) -> Fitted:
+    """kz_fit: the searches and the fit state of a hubness-reduced fit (`kind`: HUB_*; `target_m` None: single source) in one call."""
+    h = _P()
+    _call(ctx, "kz_fit", source_m.handle, target_m.handle if target_m is not None else None, int(kind), int(K), int(bool(shared_sweep)), C.byref(h))
+    return Fitted(ctx, h, source_m, target_m)

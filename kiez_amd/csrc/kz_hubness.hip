@@ -13,25 +13,29 @@
 
 // (kz_np_pairwise_sum, numpy's pairwise summation: kz_common.h)
 
-// numpy's pairwise summation tree (kz_np_pairwise_sum, kz_common.h) over n terms term(lo) .. term(lo + n - 1)
+// numpy's pairwise summation tree (kz_np_pairwise_sum, kz_common.h) over n terms term(lo) .. term(lo + n - 1): the leaves of the
+// tree (n <= 128; no recursion, so a kernel whose rows are that short -- kz_rescale_select_kernel -- needs no stack) ...
 template <typename F>
-__device__ double kz_np_pairwise_terms(int lo, int n, const F& term) {
+__device__ __forceinline__ double kz_np_pairwise_leaf(int lo, int n, const F& term) {
     if (n < 8) {
         double res = 0.0;
         for (int i = 0; i < n; ++i) res += term(lo + i);
         return res;
     }
-    if (n <= 128) {
-        double r[8];
-        for (int u = 0; u < 8; ++u) r[u] = term(lo + u);
-        int i;
-        for (i = 8; i < n - (n % 8); i += 8) {
-            for (int u = 0; u < 8; ++u) r[u] += term(lo + i + u);
-        }
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += term(lo + i);
-        return res;
+    double r[8];
+    for (int u = 0; u < 8; ++u) r[u] = term(lo + u);
+    int i;
+    for (i = 8; i < n - (n % 8); i += 8) {
+        for (int u = 0; u < 8; ++u) r[u] += term(lo + i + u);
     }
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += term(lo + i);
+    return res;
+}
+// ... and the tree over any n
+template <typename F>
+__device__ double kz_np_pairwise_terms(int lo, int n, const F& term) {
+    if (n <= 128) return kz_np_pairwise_leaf(lo, n, term);
     int n2 = n / 2;
     n2 -= n2 % 8;
     return kz_np_pairwise_terms(lo, n2, term) + kz_np_pairwise_terms(lo + n2, n - n2, term);
@@ -528,6 +532,119 @@ __global__ void kz_cast_f64_f32_kernel(const double* __restrict__ in, float* __r
     if (e < count) out[e] = (float)in[e];
 }
 
+// The tail of kneighbors in ONE launch (kz_rescale_select, K <= 128): the rescale kernel's row statistic and pointwise formula,
+// kz_select_topk_kernel's selection and kz_cast_f64_f32_kernel's cast on one transposed image of 64 rows in LDS -- the same device
+// functions in the same order, so the same bits, without the two [n, K] round trips through HBM.  Layout of kz_select_topk_kernel
+// (one wave, one lane per row for the statistic and the selection) plus two doubles of state per row in front of the image:
+//   1. coalesced load, transposed: v[pos][row]
+//   2. lane r: the statistic of row r from its column of the image (kz_np_pairwise_leaf: numpy's tree up to 128 terms over any term function)
+//   3. all lanes, entry by entry as loaded: w = f(d, statistic of the entry's row, state of the entry's id) back into the image --
+//      the ids are read coalesced, the state vectors gathered
+//   4. lane r: the selection sort of row r;  5. coalesced store of k values (cast last) and of the ids through the sorted positions
+constexpr int KZ_RS_MAX_K = 128;
+constexpr int KZ_RS_STATE_BYTES = 2 * KZ_SEL_ROWS * 8;
+__host__ __device__ constexpr int kz_rs_lds_bytes(int K) { return KZ_RS_STATE_BYTES + kz_sel_lds_bytes(K); }
+
+template <typename OUT>
+__global__ __launch_bounds__(64) void kz_rescale_select_kernel(const double* __restrict__ dist, const int64_t* __restrict__ ind, int64_t n,
+                                                               int K, int k, int kind, const double* __restrict__ t_a,
+                                                               const double* __restrict__ t_b, OUT* __restrict__ odist,
+                                                               int64_t* __restrict__ oind) {
+    extern __shared__ __attribute__((aligned(16))) char rs_smem[];
+    double* sa = reinterpret_cast<double*>(rs_smem);            // sa[row]: mean (CSLS, NICDM, MP normal) or last entry (LS)
+    double* sb = sa + KZ_SEL_ROWS;                              // sb[row]: np.nanstd (MP normal)
+    double* v = sb + KZ_SEL_ROWS;                               // v[pos * LD + row]
+    unsigned char* ps = reinterpret_cast<unsigned char*>(rs_smem + KZ_RS_STATE_BYTES + (size_t)K * KZ_SEL_LD * 8);   // ps[pos * 64 + row]
+    const int lane = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * KZ_SEL_ROWS;
+    const int rows = (int)((n - row0) < KZ_SEL_ROWS ? (n - row0) : KZ_SEL_ROWS);
+    const double* src = dist + row0 * (int64_t)K;
+    const int64_t* id = ind + row0 * (int64_t)K;
+    const int total = rows * K;
+    for (int e = lane; e < total; e += 64) {
+        const int r = e / K, j = e - r * K;
+        v[j * KZ_SEL_LD + r] = src[e];
+    }
+    for (int j = 0; j < K; ++j) ps[j * KZ_SEL_ROWS + lane] = (unsigned char)j;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (kind != KZ_HUB_NONE) {
+        if (lane < rows) {
+            const double* vr = v + lane;
+            if (kind == KZ_HUB_LS) {
+                sa[lane] = vr[(K - 1) * KZ_SEL_LD];
+            } else if (kind == KZ_HUB_MP_NORMAL) {
+                // (kz_np_nanmean_nanstd on the column: the same count, trees and divisions)
+                int cnt = 0;
+                for (int c = 0; c < K; ++c) {
+                    const double x = vr[c * KZ_SEL_LD];
+                    cnt += x == x ? 1 : 0;
+                }
+                const double m = kz_np_pairwise_leaf(0, K, [vr](int i) { const double x = vr[i * KZ_SEL_LD]; return x == x ? x : 0.0; }) / (double)cnt;
+                sa[lane] = m;
+                sb[lane] = sqrt(kz_np_pairwise_leaf(0, K, [vr, m](int i) {
+                               const double x = vr[i * KZ_SEL_LD];
+                               const double t = x == x ? x - m : 0.0;
+                               return t * t;
+                           }) / (double)cnt);
+            } else {
+                sa[lane] = kz_np_pairwise_leaf(0, K, [vr](int i) { return vr[i * KZ_SEL_LD]; }) / (double)K;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int e = lane; e < total; e += 64) {
+            const int r = e / K, j = e - r * K;
+            const int64_t t = id[e];
+            const double d = v[j * KZ_SEL_LD + r];
+            double w;
+            if (kind == KZ_HUB_CSLS) w = kz_reduce_csls(d, sa[r], t_a[t]);
+            else if (kind == KZ_HUB_LS) w = kz_reduce_ls(d, sa[r], t_a[t]);
+            else if (kind == KZ_HUB_NICDM) w = kz_reduce_nicdm(d, sa[r], t_a[t]);
+            else w = kz_reduce_mp_normal(d, sa[r], sb[r], t_a[t], t_b[t]);
+            v[j * KZ_SEL_LD + r] = w;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (lane < rows) {   // (kz_select_topk_kernel's selection, step by step)
+        double* vr = v + lane;
+        unsigned char* pr = ps + lane;
+        for (int i = 0; i < k; ++i) {
+            double m = vr[i * KZ_SEL_LD];
+            int mp = i;
+            for (int j = i + 1; j < K; ++j) {
+                const double x = vr[j * KZ_SEL_LD];
+                const bool less = (x < m) || ((m != m) && (x == x));
+                m = less ? x : m;
+                mp = less ? j : mp;
+            }
+            if (mp != i) {
+                const double vi = vr[i * KZ_SEL_LD];
+                vr[mp * KZ_SEL_LD] = vi;
+                vr[i * KZ_SEL_LD] = m;
+                const unsigned char a = pr[i * KZ_SEL_ROWS], b = pr[mp * KZ_SEL_ROWS];
+                pr[i * KZ_SEL_ROWS] = b;
+                pr[mp * KZ_SEL_ROWS] = a;
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int out_total = rows * k;
+    OUT* od = odist + row0 * (int64_t)k;
+    int64_t* oi = oind + row0 * (int64_t)k;
+    for (int e = lane; e < out_total; e += 64) {
+        const int r = e / k, i = e - r * k;
+        od[e] = (OUT)v[i * KZ_SEL_LD + r];
+        oi[e] = id[(int64_t)r * K + ps[i * KZ_SEL_ROWS + r]];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 static inline dim3 kz_grid1d(int64_t n, int per_block) { return dim3((unsigned)((n + per_block - 1) / per_block)); }
 
@@ -728,6 +845,60 @@ int kz_cast_f64_f32(kz_ctx* ctx, const double* d_in, float* d_out, int64_t count
     hipLaunchKernelGGL(kz_cast_f64_f32_kernel, kz_grid1d(count, 256), dim3(256), 0, ctx->stream, d_in, d_out, count);
     KZ_HIP(hipGetLastError());
     return KZ_OK;
+}
+
+}  // extern "C"
+
+template <typename OUT>
+static int kz_rescale_select_launch(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, int k, int kind,
+                                    const double* d_t_a, const double* d_t_b, OUT* d_odist, int64_t* d_oind) {
+    const int lds = kz_rs_lds_bytes(K);
+    if (lds > 65536)
+        KZ_HIP(hipFuncSetAttribute((const void*)kz_rescale_select_kernel<OUT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(kz_rescale_select_kernel<OUT>, kz_grid1d(n, KZ_SEL_ROWS), dim3(64), lds, ctx->stream, d_dist, d_ind, n, K, k, kind,
+                       d_t_a, d_t_b, d_odist, d_oind);
+    KZ_HIP(hipGetLastError());
+    return KZ_OK;
+}
+
+extern "C" {
+
+int kz_rescale_select(kz_ctx* ctx, const double* d_dist, const int64_t* d_ind, int64_t n, int K, int k, int kind, const double* d_t_a,
+                      const double* d_t_b, int out_dtype, void* d_odist, int64_t* d_oind) {
+    KZ_REQUIRE(ctx != nullptr, "kz_rescale_select: null context");
+    KZ_REQUIRE(n >= 0 && K >= 1 && K <= KZ_MAX_CANDIDATES, "kz_rescale_select: bad shape n=%lld K=%d (K must be in [1,%d])", (long long)n, K,
+               KZ_MAX_CANDIDATES);
+    KZ_REQUIRE(d_dist && d_ind && d_odist && d_oind, "kz_rescale_select: null argument");
+    KZ_REQUIRE(k >= 1 && k <= K, "kz_rescale_select: k=%d must be in [1, K=%d]", k, K);
+    KZ_REQUIRE(kind >= KZ_HUB_NONE && kind <= KZ_HUB_MP_NORMAL,
+               "kz_rescale_select: unknown kind %d (KZ_HUB_NONE, _CSLS, _LS, _NICDM, _MP_NORMAL; MP empiric reads the reverse lists: kz_mp_empiric)", kind);
+    KZ_REQUIRE(out_dtype == KZ_F64 || out_dtype == KZ_F32, "kz_rescale_select: out_dtype must be KZ_F64 or KZ_F32, got %d", out_dtype);
+    KZ_REQUIRE(kind == KZ_HUB_NONE || d_t_a, "kz_rescale_select: kind %d reads the state vector d_t_a", kind);
+    KZ_REQUIRE(kind != KZ_HUB_MP_NORMAL || d_t_b, "kz_rescale_select: MP normal reads the state vector d_t_b (sd_t)");
+    KZ_HIP(hipSetDevice(ctx->device));
+    if (n == 0) return KZ_OK;
+    if (K <= KZ_RS_MAX_K)
+        return out_dtype == KZ_F32 ? kz_rescale_select_launch(ctx, d_dist, d_ind, n, K, k, kind, d_t_a, d_t_b, (float*)d_odist, d_oind)
+                                   : kz_rescale_select_launch(ctx, d_dist, d_ind, n, K, k, kind, d_t_a, d_t_b, (double*)d_odist, d_oind);
+    // more candidates than the image of 64 rows takes: the kernels the fused one stands for, in sequence, on transient buffers
+    KzPoolBuf<double> w, od;
+    const double* sel_in = d_dist;
+    if (kind != KZ_HUB_NONE) {
+        const int rca = w.alloc(ctx, (size_t)n * (size_t)K * 8);
+        if (rca != KZ_OK) return rca;
+        int rc;
+        if (kind == KZ_HUB_CSLS) rc = kz_csls(ctx, d_dist, d_ind, n, K, d_t_a, w.get());
+        else if (kind == KZ_HUB_MP_NORMAL) rc = kz_mp_normal(ctx, d_dist, d_ind, n, K, d_t_a, d_t_b, w.get());
+        else rc = kz_local_scaling(ctx, d_dist, d_ind, n, K, d_t_a, kind == KZ_HUB_NICDM ? 1 : 0, w.get());
+        if (rc != KZ_OK) return rc;
+        sel_in = w.get();
+    }
+    if (out_dtype == KZ_F64) return kz_select_topk(ctx, sel_in, d_ind, n, K, k, (double*)d_odist, d_oind);
+    const int rcb = od.alloc(ctx, (size_t)n * (size_t)k * 8);
+    if (rcb != KZ_OK) return rcb;
+    const int rcs = kz_select_topk(ctx, sel_in, d_ind, n, K, k, od.get(), d_oind);
+    if (rcs != KZ_OK) return rcs;
+    return kz_cast_f64_f32(ctx, od.get(), (float*)d_odist, n * (int64_t)k);
 }
 
 }  // extern "C"

@@ -34,6 +34,9 @@ class HubnessReduction(ABC):
         self.nn_algo = nn_algo
         self.verbose = verbose
         self._use_torch = False
+        if "native_fit" in kwargs:
+            self._native_fit = bool(kwargs["native_fit"])
+        self._fitted = None
         if nn_algo.n_candidates == 1:
             raise ValueError("Cannot perform hubness reduction with a single candidate per query!")
         # known at construction, so say it at construction (not after a long fit): the device transforms and the final
@@ -50,6 +53,45 @@ class HubnessReduction(ABC):
     # distance matrix where the native library can (kz_knn_dual; results identical to the two searches).  Set to False on
     # an instance to search twice, as the reference does.
     _shared_sweep = True
+    # Opt-in (`hubness_kwargs={"native_fit": True}`): fit() and kneighbors() are ONE native call each (kz_fit / kz_kneighbors: the
+    # searches, the fit state, the fused rescale + sort + cast) for the reductions that name a `_native_kind` -- CSLS, LocalScaling,
+    # MutualProximity -- on the MI355X backend with an embedding metric.  Same results, bit for bit.  Where the library's plan refuses
+    # the fit (a k that would be clamped, a precomputed matrix) and for every other reduction the pipeline below runs as ever.
+    _native_fit = False
+
+    def _native_kind(self) -> Optional[int]:
+        """The KZ_HUB_* kind `_native.fit` takes for this reduction; None: no native fit."""
+        return None
+
+    def _set_native_state(self, fitted: "N.Fitted"):
+        """The fitted attributes `_fit` sets, as views into the fitted object."""
+        raise NotImplementedError  # pragma: no cover
+
+    def _fit_native(self, source, target) -> bool:
+        """fit() through kz_fit.  False -- nothing changed -- where the flag is off, the reduction or the backend has no native fit, or
+        the plan refuses (the present pipeline then produces the clamp, the warning or the error)."""
+        self._fitted = None
+        kind = self._native_kind() if self._native_fit and self._gpu_nn else None
+        nn = self.nn_algo
+        K = nn.n_candidates
+        if kind is None or _is_precomputed(nn) or isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)):
+            return False
+        try:
+            fitted = N.fit(self.ctx, nn.source_index, None if nn.source_equals_target else nn.target_index, kind, int(K), self._shared_sweep)
+        except (ValueError, NotImplementedError):
+            return False
+        self._fitted = fitted
+        self._set_native_state(fitted)
+        self._native_stats()
+        return True
+
+    def _native_stats(self):
+        """`last_stats` / `last_stats_reverse` of the backend from the fitted object's record of its searches."""
+        info = self._fitted.info
+        nn = self.nn_algo
+        if info["forward_ready"]:
+            nn.last_stats = info["stats_forward"]
+        nn.last_stats_reverse = info["stats_reverse"] if info["search"] in (N.FIT_SEARCH_DUAL, N.FIT_SEARCH_REVERSE) else None
 
     # ---- device helpers ---------------------------------------------------------------------------
     @property
@@ -81,6 +123,8 @@ class HubnessReduction(ABC):
             # (a precomputed distance matrix is two-sided by itself: its target side is the backend's `target_`, a distinct object
             #  that the backend resolves to the matrix' COLUMNS view -- `source` again would resolve to the rows view)
             target = self.nn_algo.target_ if _is_precomputed(self.nn_algo) else source
+        if self._fit_native(source, target):
+            return
         if self._gpu_nn:
             # one sweep of the distance matrix serves this reverse search AND the forward search of kneighbors()
             # (kz_knn_dual); where that does not apply, the reverse search alone
@@ -132,6 +176,10 @@ class HubnessReduction(ABC):
             raise TypeError("kneighbors_device needs the MI355X SklearnNN backend")
         n_neighbors = self._set_k_if_needed(k)
         nn = self.nn_algo
+        if self._fitted is not None:   # (native_fit: the forward search if the fit left it, rescale + sort + cast, one call)
+            od, oi = self._fitted.kneighbors(n_neighbors, nn._out_dtype(nn.target_index))
+            self._native_stats()
+            return od, oi
         query_dist, query_ind = nn.kneighbors_device(query=None, k=nn.n_candidates)
         hub_dist, query_ind = self.transform(query_dist, query_ind, nn.source_)
         od, oi = HubnessReduction._sort(hub_dist, query_ind, n_neighbors, ctx=self.ctx)
@@ -409,6 +457,14 @@ class CSLS(HubnessReduction):
         self._r_train_dev, _, _ = N.row_stats(self.ctx, d, mean=True)   # csls.py:90, hoisted into fit
         return self
 
+    def _native_kind(self):
+        return N.HUB_CSLS
+
+    def _set_native_state(self, fitted):
+        self.r_dist_train_ = fitted.state("reverse_dist")
+        self.r_ind_train_ = fitted.state("reverse_ind")
+        self._r_train_dev = fitted.state("state_a")
+
     _no_rank_reason = None
 
     def _rank_state(self, query_dist):
@@ -445,6 +501,14 @@ class LocalScaling(HubnessReduction):
         else:
             _, _, self._r_t_dev = N.row_stats(self.ctx, d, last=True)       # :136
         return self
+
+    def _native_kind(self):
+        return N.HUB_NICDM if self.method == "nicdm" else N.HUB_LS
+
+    def _set_native_state(self, fitted):
+        self.r_dist_t_to_s_ = fitted.state("reverse_dist")
+        self.r_ind_t_to_s_ = fitted.state("reverse_ind")
+        self._r_t_dev = fitted.state("state_a")
 
     _no_rank_reason = None
 
@@ -491,6 +555,18 @@ class MutualProximity(HubnessReduction):
             self.mu_t_to_s_ = mu
             self.sd_t_to_s_ = sd
         return self
+
+    def _native_kind(self):
+        return N.HUB_MP_EMPIRIC if self.method == "empiric" else N.HUB_MP_NORMAL
+
+    def _set_native_state(self, fitted):
+        self.n_train = fitted.info["n_target"]
+        if self.method == "empiric":
+            self.neigh_dist_t_to_s_ = self._dist_t2s_dev = fitted.state("reverse_dist")
+            self.neigh_ind_t_to_s_ = self._ind_t2s_dev = fitted.state("reverse_ind")
+        else:
+            self.mu_t_to_s_ = self._mu_dev = fitted.state("state_a")
+            self.sd_t_to_s_ = self._sd_dev = fitted.state("state_b")
 
     @property
     def _no_rank_reason(self):
