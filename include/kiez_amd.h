@@ -409,6 +409,21 @@ int kz_hit_positions(kz_ctx* ctx, const int64_t* d_ind, const int64_t* d_gold, i
  * and a counting kernel in place of the selection; rows without gold cost no distance work.  Synchronises the context's stream. */
 int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                   const int64_t* d_gold, int64_t* d_rank);
+/* kz_gold_ranks on a certified fp16 MFMA count sweep -- ABI v7, additive, opt-in: the same d_rank on every row, by another route.
+ * Per row with a gold id the exact value of the gold pair and the fp16 tier's rounding bound give an interval of approximate keys;
+ * one sweep of the fp16 operand images counts the index rows surely closer and logs the rows inside the interval (the band), whose
+ * exact float64 values then decide.  Rows that are not trusted (a non-finite value or bound, more than 1 024 band entries, a bound
+ * that its own check finds violated, every row when the band log overflows) are answered by the exact route of kz_gold_ranks.
+ * Shapes outside the sweep -- rows that are not KZ_F32, a metric beyond KZ_COSINE, d > 384 (or fewer than 17 features), precomputed
+ * handles, option "precision" = 1, an index of fewer than 128 rows -- take the exact route whole: route_taken = 0, never an error.
+ * Validation, d_gold, -1 rows and the synchronisation are kz_gold_ranks'.  stats may be NULL. */
+typedef struct kz_rank_sweep_stats {
+    int32_t route_taken;      /* 1 sweep, 0 exact route (shape outside the sweep) */
+    int64_t n_rows, n_sweep_rows, n_fallback_rows, n_band_pairs;   /* rows with a gold id; answered by the sweep; sent to the exact route; band entries */
+    double  max_err_ratio, sweep_ms, band_ms, fallback_ms;         /* largest |key~ - key| / bound over the band; device times */
+} kz_rank_sweep_stats;
+int kz_gold_ranks_sweep(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                        const int64_t* d_gold, int64_t* d_rank, kz_rank_sweep_stats* stats);
 /* The same ranks under a POINTWISE hubness reduction -- ABI v7, additive: CSLS, LocalScaling 'standard', NICDM and MutualProximity
  * 'normal' rescale a pair's distance d with one state of the query row and one of the index row (two each for MP), so the reduced
  * distance w exists for EVERY index row, not for the K candidates alone.  d_rank[r] = #{ j : w_j < w_g or (w_j == w_g and j < g) }

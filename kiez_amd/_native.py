@@ -106,6 +106,24 @@ class KnnStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RankSweepStats(C.Structure):
+    """kz_rank_sweep_stats: which route a `gold_ranks(route="sweep")` call took and what its band and fallbacks came to."""
+    _fields_ = [
+        ("route_taken", C.c_int32),
+        ("n_rows", C.c_int64),
+        ("n_sweep_rows", C.c_int64),
+        ("n_fallback_rows", C.c_int64),
+        ("n_band_pairs", C.c_int64),
+        ("max_err_ratio", C.c_double),
+        ("sweep_ms", C.c_double),
+        ("band_ms", C.c_double),
+        ("fallback_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FitInfo(C.Structure):
     """kz_fit_info: the sizes, the plan that ran and the statistics of the searches of a fitted object."""
     _fields_ = [
@@ -189,6 +207,7 @@ SYMBOLS = [
     ("kz_kocc_select", C.c_int, [_P, _P, _I64, C.c_int, C.c_double, _P, C.POINTER(_I64)]),
     ("kz_hit_positions", C.c_int, [_P, _P, _P, _I64, C.c_int, _P]),
     ("kz_gold_ranks", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
+    ("kz_gold_ranks_sweep", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_radius_neighbors", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64)]),
@@ -560,16 +579,34 @@ def merge_topk(ctx: Context, key, ind, dist, segs: int, seg_len: int, k: int, al
     return od, oi
 
 
+RANK_ROUTES = ("exact", "sweep")
+
+
+def checked_rank_route(route) -> str:
+    if route not in RANK_ROUTES:
+        raise ValueError(f"route must be one of {RANK_ROUTES}, got {route!r}")
+    return route
+
+
 def gold_ranks(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev: DeviceArray, q_begin: int = 0,
-               q_count: Optional[int] = None) -> DeviceArray:
+               q_count: Optional[int] = None, route: str = "exact", stats: Optional[dict] = None) -> DeviceArray:
     """kz_gold_ranks -> int64 [q_count] on the device: the 0-based rank of index row gold_dev[r] for query row q_begin + r against
-    the whole index (the position it holds in kz_knn with k = index.n), -1 where gold_dev[r] is INT64_MIN or no index row."""
+    the whole index (the position it holds in kz_knn with k = index.n), -1 where gold_dev[r] is INT64_MIN or no index row.
+    `route="sweep"`: kz_gold_ranks_sweep -- the same ranks from a count sweep of the fp16 images with the exact values of the
+    undecided pairs; `stats` (a dict) then receives kz_rank_sweep_stats."""
+    checked_rank_route(route)
     if q_count is None:
         q_count = query.shape[0] - q_begin
     if gold_dev.dtype != np.int64 or gold_dev.shape != (q_count,):
         raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
     rank = ctx.empty((q_count,), np.int64)
-    _call(ctx, "kz_gold_ranks", query.handle, q_begin, q_count, index.handle, gold_dev.ptr, rank.ptr)
+    if route == "sweep":
+        st = RankSweepStats()
+        _call(ctx, "kz_gold_ranks_sweep", query.handle, q_begin, q_count, index.handle, gold_dev.ptr, rank.ptr, C.byref(st))
+        if stats is not None:
+            stats.update(st.as_dict())
+    else:
+        _call(ctx, "kz_gold_ranks", query.handle, q_begin, q_count, index.handle, gold_dev.ptr, rank.ptr)
     return rank
 
 

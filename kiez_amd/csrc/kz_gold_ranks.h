@@ -240,33 +240,29 @@ static int kz_rank_require_reduction(const char* who, int kind, const double* q_
     return KZ_OK;
 }
 
-// The host side of both entry points: the compaction, then the walk of the exact stage (kz_exact_walk) over the listed rows with the
-// count per batch -- of the values themselves (red == nullptr: the one instantiation <double, KZ_RANK_NONE, KZ_COSINE>) or of their
-// reduced distances.
-static int kz_gold_ranks_impl(const char* who, kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index,
-                              const int64_t* d_gold, const KzRankReduction* red, int64_t* d_rank) {
-    KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "%s: more than 2^31 - 1 rows", who);
-    if (q_count == 0) return KZ_OK;
-    KZ_HIP(hipSetDevice(ctx->device));
-
-    KzPoolBuf<int> fl;   // [q_count] listed rows + the count
+// The compaction of a call: fl [q_count + 1] = the listed rows and their count (read back: one synchronisation), d_rank = 0 / -1.
+static int kz_rank_compact(kz_ctx* ctx, int64_t q_count, const kz_matrix* index, const int64_t* d_gold, int64_t* d_rank, KzPoolBuf<int>& fl,
+                           int* n_list) {
     int rc = fl.alloc(ctx, ((size_t)q_count + 1) * sizeof(int));
     if (rc != KZ_OK) return rc;
     hipLaunchKernelGGL(kz_rank_compact_kernel, dim3(1), dim3(256), 0, ctx->stream, d_gold, (int)q_count, index->n, fl.get(), d_rank);
     KZ_HIP(hipGetLastError());
-    int n_list = 0;
-    KZ_HIP(hipMemcpyAsync(&n_list, fl.get() + q_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(n_list, fl.get() + q_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     KZ_HIP(hipStreamSynchronize(ctx->stream));
-    if (n_list == 0) return KZ_OK;
+    return KZ_OK;
+}
 
+// The walk of the exact stage (kz_exact_walk) over a compacted row list (d_rank = 0 at its rows) with the count per batch -- of the
+// values themselves (red == nullptr: the one instantiation <double, KZ_RANK_NONE, KZ_COSINE>) or of their reduced distances.  Ends
+// synchronised with the stream.
+static int kz_gold_ranks_walk(const char* who, kz_ctx* ctx, kz_matrix* query, int64_t q_begin, kz_matrix* index, const int64_t* d_gold,
+                              const KzRankReduction* red, const int* list, int n_list, int64_t* d_rank) {
     // the value matrix of the exact stage (kz_exact.h), batch by batch; the count in place of its selection
     int batch = 0;
     double* vals = nullptr;
-    rc = kz_exact_begin(ctx, index, n_list, &batch, &vals);
+    const int rc = kz_exact_begin(ctx, index, n_list, &batch, &vals);
     if (rc != KZ_OK) return rc;
     const int n_chunks = (int)((index->n + KZ_RANK_CHUNK - 1) / KZ_RANK_CHUNK);
-    const int* list = fl.get();
-    // (fl goes back to the pool behind the walk's synchronise; the caller reads d_rank next)
     return kz_exact_walk(who, ctx, list, n_list, batch, vals, q_begin, query, index, [&](int b0, int nb) {
         const dim3 grid(n_chunks, nb);
         if (!red)
@@ -279,6 +275,24 @@ static int kz_gold_ranks_impl(const char* who, kz_ctx* ctx, kz_matrix* query, in
                                    red->t_b, d_rank);
             });
     });
+}
+
+// The host side of the exact entry points: the compaction, then the walk over the listed rows.  *n_listed (may be null): their number.
+static int kz_gold_ranks_impl(const char* who, kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index,
+                              const int64_t* d_gold, const KzRankReduction* red, int64_t* d_rank, int* n_listed = nullptr) {
+    KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "%s: more than 2^31 - 1 rows", who);
+    if (n_listed) *n_listed = 0;
+    if (q_count == 0) return KZ_OK;
+    KZ_HIP(hipSetDevice(ctx->device));
+
+    KzPoolBuf<int> fl;   // [q_count] listed rows + the count
+    int n_list = 0;
+    const int rc = kz_rank_compact(ctx, q_count, index, d_gold, d_rank, fl, &n_list);
+    if (rc != KZ_OK) return rc;
+    if (n_listed) *n_listed = n_list;
+    if (n_list == 0) return KZ_OK;
+    // (fl goes back to the pool behind the walk's synchronise; the caller reads d_rank next)
+    return kz_gold_ranks_walk(who, ctx, query, q_begin, index, d_gold, red, fl.get(), n_list, d_rank);
 }
 
 extern "C" int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_begin, int64_t q_count, const kz_matrix* index_c,

@@ -1829,6 +1829,7 @@ extern "C" int kz_knn(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int6
 }
 
 #include "kz_gold_ranks.h"
+#include "kz_rank_sweep.h"
 #include "kz_knn_reduced.h"
 #include "kz_radius.h"
 #include "kz_pairs.h"

@@ -33,6 +33,21 @@ constexpr int KZ_RANGE_MIN_BATCH = 1024;    // a log that overflows at this batc
 constexpr int KZ_RANGE_PPW = 256;           // pairs per wave of kz_exact_pairs_kernel
 constexpr int KZ_RANGE_EARLY_PER_ROW = 4096;   // the early call: at most this many rows outside the groups take their own ranges there
 
+// THE rounding bound of an fp16-tier key of query row `rowq` (|q_c|^2, |q_h|, |q_c - q_h|) against any index row, in exact key units:
+// kz_finalize_query's eps_q, term by term -- the operand residuals (measured at pack time), the float32 accumulation, the float32
+// rounding of the key, the float64 evaluation of the exact value.  One expression for every caller that turns an exact value into a
+// threshold on approximate keys (kz_range_thr_kernel below, kz_rank_band_kernel in kz_rank_sweep.h).
+__device__ __forceinline__ double kz_h_key_eps(const double* __restrict__ rowq, const double* __restrict__ y_hmax, const double* __restrict__ ystats,
+                                               double qsqn, int metric, double eps_mult, double gamma_acc) {
+    const double qc2 = rowq[0], qh = rowq[1], qr = rowq[2];
+    const double Yh = y_hmax[0], Ry = y_hmax[1], Yc2 = y_hmax[2];
+    const double qc = sqrt(qc2), yc = sqrt(Yc2);
+    const double ymax = ystats[0];
+    const double raw2 = metric == KZ_COSINE ? 2.0 : qsqn + ymax * ymax;
+    return eps_mult * (qr * Yh + qh * Ry + qr * Ry + gamma_acc * (0.5 * Yc2 + qh * Yh) + 1.1920928955078125e-07 * (qc + yc) * (qc + yc) +
+                       1e-12 * (0.5 * Yc2 + qc2) + 1e-14 * raw2);
+}
+
 // thr [n_pad]: the threshold of batch row i in the fp16 tier's key units (+inf: nothing is logged -- pad rows, tau = +inf; diagnostic
 // "abl" bit 8: every row, as if no row had k candidates);
 // inf_floor [n_pad] = +inf: the floor the sweep's lists start from (they stay empty).  The bound is kz_finalize_query's, term by term.
@@ -47,13 +62,8 @@ __global__ void kz_range_thr_kernel(const double* __restrict__ tau, int nb, int6
     if (i < nb) {
         const double tv = tau[i];
         if (tv < (double)INFINITY) {
-            const double qc2 = rowq[i * 3 + 0], qh = rowq[i * 3 + 1], qr = rowq[i * 3 + 2];
-            const double Yh = y_hmax[0], Ry = y_hmax[1], Yc2 = y_hmax[2];
-            const double qc = sqrt(qc2), yc = sqrt(Yc2);
-            const double ymax = ystats[0];
-            const double raw2 = metric == KZ_COSINE ? 2.0 : qsqn[i] + ymax * ymax;
-            const double eps = eps_mult * (qr * Yh + qh * Ry + qr * Ry + gamma_acc * (0.5 * Yc2 + qh * Yh) +
-                                           1.1920928955078125e-07 * (qc + yc) * (qc + yc) + 1e-12 * (0.5 * Yc2 + qc2) + 1e-14 * raw2);
+            const double qc2 = rowq[i * 3 + 0];
+            const double eps = kz_h_key_eps(rowq + i * 3, y_hmax, ystats, metric == KZ_COSINE ? 0.0 : qsqn[i], metric, eps_mult, gamma_acc);
             const double key = 0.5 * (qc2 - (metric == KZ_COSINE ? 2.0 * tv : tv));
             const double want = (key - eps) / hscale[1];
             float f = (float)want;

@@ -347,7 +347,7 @@ class Kiez:
         from . import matching
         return matching._hierarchy_of(self._pairs_of_both_directions(k, mode, reduced))
 
-    def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False):
+    def gold_ranks(self, gold, s_to_t: bool = True, reduced: bool = False, route: str = "exact"):
         """Exact 0-based rank of every source row's gold target against the whole target index (`evaluate.rank_metrics` turns the
         ranks into hits@k, mean rank and mean reciprocal rank).
 
@@ -356,9 +356,17 @@ class Kiez:
         MutualProximity 'normal'; none: the plain ranks) -- every target row is ranked by its reduced distance, with the state taken
         from the `n_candidates` neighbours as `fit` / `kneighbors` use them, so a gold row outside the candidate list has a rank too.
         MutualProximity 'empiric' and DisSimLocal raise NotImplementedError.  The fit state exists for the source -> target
-        direction: `reduced=True` with `s_to_t=False` raises ValueError."""
+        direction: `reduced=True` with `s_to_t=False` raises ValueError.
+
+        `route="sweep"` (opt-in, `reduced=False` only): the same ranks from a count sweep of the fp16 MFMA kernels
+        (`SklearnNN.gold_ranks`); its statistics are `algorithm.rank_stats_`.  With `reduced=True` it raises NotImplementedError:
+        ranks under a reduction have no sweep yet.  An unknown route raises ValueError."""
+        N.checked_rank_route(route)
         if not reduced:
-            return self.algorithm.gold_ranks(gold, s_to_t=s_to_t)
+            return self.algorithm.gold_ranks(gold, s_to_t=s_to_t, route=route)
+        if route == "sweep":
+            raise NotImplementedError("gold_ranks(route='sweep') ranks by the search metric only: with reduced=True use route='exact' "
+                                      "(ranks under a hubness reduction have no sweep yet)")
         if not s_to_t:
             raise ValueError("gold_ranks(reduced=True) ranks source rows against the target index only (s_to_t=True): the hubness "
                              "reduction is fitted for that direction")

@@ -252,6 +252,7 @@ class SklearnNN(NNAlgorithm):
         self._forward = None  # (k, dist, ind): source -> target result that came out of a shared sweep (kneighbors_device_both)
         self.last_stats = None
         self.last_stats_reverse = None   # statistics of the target -> source direction of the last shared sweep (else None)
+        self.rank_stats_ = None          # kz_rank_sweep_stats of the last gold_ranks(route="sweep") (None after route="exact")
 
     def __repr__(self):
         return (f"{self.__class__.__name__}(n_candidates={self.n_candidates},algorithm={self.algorithm},"
@@ -503,12 +504,14 @@ class SklearnNN(NNAlgorithm):
         query, index = self._two_sided_operands("gold_ranks", s_to_t)
         return query, index, self.ctx.to_device(_gold_rows(gold, query.shape[0]))
 
-    def gold_ranks_device(self, gold, s_to_t=True) -> N.DeviceArray:
+    def gold_ranks_device(self, gold, s_to_t=True, route="exact") -> N.DeviceArray:
         """`gold_ranks` that leaves the int64 rank vector in HBM (evaluate.rank_metrics reduces it there)."""
+        N.checked_rank_route(route)
         query, index, gold_dev = self._gold_rank_operands(gold, s_to_t)
-        return N.gold_ranks(self.ctx, query, index, gold_dev)
+        self.rank_stats_ = {} if route == "sweep" else None
+        return N.gold_ranks(self.ctx, query, index, gold_dev, route=route, stats=self.rank_stats_)
 
-    def gold_ranks(self, gold, s_to_t=True) -> np.ndarray:
+    def gold_ranks(self, gold, s_to_t=True, route="exact") -> np.ndarray:
         """Exact 0-based rank of every query row's gold answer against the WHOLE index: the position the gold row would hold in
         `kneighbors(k = index size)` -- without that list, so for an index of any size (a search returns at most
         `_native.MAX_NEIGHBORS` neighbours).  Query rows are the fitted source rows and the index the fitted target; with
@@ -522,8 +525,12 @@ class SklearnNN(NNAlgorithm):
         (`HubnessReduction.gold_ranks`): those reductions are functions of a pair's distance and one state per side, defined for
         every index row and not for the candidate list alone.  Raises NotFittedError before `fit` and NotImplementedError after a
         single-source fit (`fit(source)`): sklearn's self-removal rule has no meaning for a rank.  `evaluate.rank_metrics` turns the
-        ranks into hits@k, MR and MRR."""
-        return self.gold_ranks_device(gold, s_to_t).numpy()
+        ranks into hits@k, MR and MRR.
+
+        `route="sweep"` (opt-in): the same ranks from one count sweep of the fp16 MFMA kernels plus the exact values of the pairs it
+        cannot decide (kz_gold_ranks_sweep); what it did -- route taken, band pairs, fallback rows, times -- is `rank_stats_`
+        afterwards.  Any other string raises ValueError."""
+        return self.gold_ranks_device(gold, s_to_t, route).numpy()
 
     # ---- every pair within a threshold, whole index ---------------------------------------------------
     def _results_to_host(self, *arrays):

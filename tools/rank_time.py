@@ -4,7 +4,12 @@ the times are host wall times around one call, best of three after a warm-up.  T
 kz_gold_ranks_reduced on the same matrices and gold ids, once per kind, with arbitrary positive state vectors (the native call takes
 any): `reduced_ms` and the ratio to the plain call.  One JSON line per case.
 
-    python tools/rank_time.py [--out FILE] [--cases small|large|all] [--metric NAME] [--ranks-only]
+    python tools/rank_time.py [--out FILE] [--cases small|large|all] [--metric NAME] [--ranks-only] [--route exact|sweep|both] [--gold uniform|correlated]
+
+`--route both` (euclidean float32 cases) times gold_ranks(route="exact") and gold_ranks(route="sweep") ALTERNATED in one process -- seven
+rounds after a warm-up of each, median and min .. max per route -- checks that the two rank vectors are equal and adds the sweep's
+statistics (kz_rank_sweep_stats: band pairs, fallback rows, max_err_ratio, device times).  `--gold correlated`: the index row of every
+gold id is its query row plus noise (ranks near 0), instead of uniform random gold ids (ranks near n / 2).
 
 `--metric euclidean --ranks-only` is the run to put under `rocprofv3 --kernel-trace --stats`: only the rank calls of one metric, so
 that the trace's per-kernel totals split into the distance kernel and the two count kernels.
@@ -42,6 +47,8 @@ def main():
     ap.add_argument("--cases", default="all", choices=sorted(CASES))
     ap.add_argument("--metric", default=None, help="only the cases of this metric")
     ap.add_argument("--ranks-only", action="store_true", help="skip the kz_knn comparison")
+    ap.add_argument("--route", default="exact", choices=["exact", "sweep", "both"])
+    ap.add_argument("--gold", default="uniform", choices=["uniform", "correlated"])
     args = ap.parse_args()
     ctx = N.Context.get()
     rng = np.random.default_rng(0)
@@ -53,10 +60,30 @@ def main():
             s, t = (rng.random((n, d)) < 0.4).astype(np.float32), (rng.random((n, d)) < 0.4).astype(np.float32)
         else:
             s, t = rng.standard_normal((n, d)).astype(np.float32), rng.standard_normal((n, d)).astype(np.float32)
+        gold_ids = rng.integers(0, n, n).astype(np.int64)
+        if args.gold == "correlated" and metric != "jaccard":
+            gold_ids = rng.permutation(n).astype(np.int64)
+            t[gold_ids] = s + 0.05 * rng.standard_normal((n, d)).astype(np.float32)
         sm, tm = N.DeviceMatrix(ctx, s, metric), N.DeviceMatrix(ctx, t, metric)
-        gold = ctx.to_device(rng.integers(0, n, n).astype(np.int64))
-        rank_ms = best_of(lambda: N.gold_ranks(ctx, sm, tm, gold), ctx)
-        ranks = N.gold_ranks(ctx, sm, tm, gold).numpy()
+        gold = ctx.to_device(gold_ids)
+        route = "sweep" if args.route == "sweep" else "exact"
+        rank_ms = best_of(lambda: N.gold_ranks(ctx, sm, tm, gold, route=route), ctx)
+        ranks = N.gold_ranks(ctx, sm, tm, gold, route=route).numpy()
+        routes = {}
+        if args.route == "both" and metric == "euclidean":
+            times, st = {"exact": [], "sweep": []}, {}
+            for r in times:
+                N.gold_ranks(ctx, sm, tm, gold, route=r)
+            ctx.sync()
+            for _ in range(7):
+                for r in times:
+                    t0 = time.perf_counter()
+                    got = N.gold_ranks(ctx, sm, tm, gold, route=r, stats=st if r == "sweep" else None)
+                    ctx.sync()
+                    times[r].append((time.perf_counter() - t0) * 1e3)
+                    assert np.array_equal(got.numpy(), ranks), "the routes disagree"
+            routes = {"gold": args.gold, "sweep_stats": st,
+                      **{f"{r}_ms": {"median": round(float(np.median(v)), 3), "min": round(min(v), 3), "max": round(max(v), 3)} for r, v in times.items()}}
         reduced = {}
         if metric == "euclidean":
             # (states of the data's own scale: means near the typical distance, deviations a tenth of it)
@@ -69,6 +96,7 @@ def main():
                 reduced[name] = best_of(lambda: N.gold_ranks_reduced(ctx, sm, tm, gold, kind, q_state, t_state), ctx)
         line = {"metric": metric, "dtype": "float32", "n_query": n, "n_index": n, "d": d, "gold_ranks_ms": round(rank_ms, 2),
                 "pairs_per_s_gold_ranks": round(n * n / rank_ms * 1e3, 0), "mean_rank": float(ranks.mean()), "min_rank": int(ranks.min())}
+        line.update(routes)
         if not args.ranks_only:
             stats = {}
 
