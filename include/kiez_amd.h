@@ -490,6 +490,28 @@ int kz_radius_neighbors_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_b
                                 double radius, int sorted, int64_t capacity, int kind, const double* d_q_a, const double* d_q_b,
                                 const double* d_t_a, const double* d_t_b, int64_t* d_indptr, int64_t* d_ind, double* d_dist,
                                 int64_t* h_total);
+/* kz_radius_neighbors ON THE CERTIFIED fp16 SWEEP -- additive, opt-in: the same bytes in d_indptr, d_ind, d_dist and *h_total as
+ * kz_radius_neighbors on the same arguments, for every input.  The argument rules, the capacity contract, the row orders and the
+ * NaN rule are kz_radius_neighbors' word for word: d_indptr and *h_total always complete and exact; capacity == 0 the count-only
+ * call; rows ending beyond `capacity` not written; sorted == 0 a row ascends by index row, sorted != 0 by (w, index row) in
+ * kz_knn_reduced's order; a NaN w never in the result; the call synchronises the stream.
+ * A radius is a per-row threshold on the fp16 tier's key: a sweep of the fp16 images decides which pairs are surely outside
+ * (capacity == 0: also which are surely inside, counted in the kernel); the few pairs a row that remain get the exact float64 value
+ * -- the value the call returns -- and the predicate w <= radius.  The rounding bound checks itself on every such pair.
+ * The WHOLE call takes kz_radius_neighbors (route_taken = 0, never an error) for: a shape outside the sweep -- rows that are not
+ * KZ_F32, a metric beyond KZ_COSINE, d > 384 (or fewer than 17 features), precomputed handles, option "precision" = 1, an index of
+ * fewer than 128 rows --; a radius that is not finite or is negative; a candidate log that overflowed (64 entries per query row, at
+ * least 2^20, at most a quarter of the free memory); a bound its own check finds violated; a query row whose norm or bound is not finite
+ * (a NaN operand among them: the exact route's clamp fmax(NaN, 0) gives such a row the value 0 against every index row).  There is no per-row fallback.  stats may be NULL. */
+typedef struct kz_radius_sweep_stats {
+    int32_t route_taken;      /* 1 sweep, 0 exact route */
+    int32_t overflowed;       /* 1: the candidate log was too small (the call then took the exact route) */
+    int64_t n_rows, n_candidates, n_pairs;   /* query rows; log entries of the sweep; pairs of the result */
+    double  max_err_ratio, sweep_ms, resolve_ms, fallback_ms;   /* largest |key~ - key| / bound over the evaluated pairs; device times */
+} kz_radius_sweep_stats;
+int kz_radius_neighbors_sweep(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                              double radius, int sorted, int64_t capacity, int64_t* d_indptr, int64_t* d_ind, double* d_dist,
+                              int64_t* h_total, kz_radius_sweep_stats* stats);
 /* Row-wise SOFT-MIN over the whole index -- ABI v7, additive: the primitive of the Sinkhorn potentials and the inverted softmax.
  *   d_out[r] = softmin_eps over every index row j of (d_rj - d_off[j])  +  shift,   softmin_eps(x) = m - eps log sum exp(-(x - m) / eps),
  * m = min x, in float64; d_rj = the distance kz_knn returns for query row q_begin + r and index row j (the exact ranking value

@@ -124,6 +124,24 @@ class RankSweepStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RadiusSweepStats(C.Structure):
+    """kz_radius_sweep_stats: which route a `radius_neighbors(route="sweep")` call took, what its candidate log held and the times."""
+    _fields_ = [
+        ("route_taken", C.c_int32),
+        ("overflowed", C.c_int32),
+        ("n_rows", C.c_int64),
+        ("n_candidates", C.c_int64),
+        ("n_pairs", C.c_int64),
+        ("max_err_ratio", C.c_double),
+        ("sweep_ms", C.c_double),
+        ("resolve_ms", C.c_double),
+        ("fallback_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FitInfo(C.Structure):
     """kz_fit_info: the sizes, the plan that ran and the statistics of the searches of a fitted object."""
     _fields_ = [
@@ -211,6 +229,7 @@ SYMBOLS = [
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_radius_neighbors", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_radius_neighbors_sweep", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64), _P]),
     ("kz_radius_neighbors_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                               C.POINTER(_I64)]),
     ("kz_softmin_rows", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, _P, C.c_double, _P]),
@@ -684,13 +703,22 @@ RADIUS_FIRST_CAPACITY_PER_ROW = 32
 
 
 def _radius_call(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius: float, sort_results: bool, capacity: int, kind, state,
-                 q_begin: int, q_count: int):
-    """One kz_radius_neighbors / kz_radius_neighbors_reduced call -> (indptr [q_count + 1], ind [capacity], dist [capacity], total)."""
+                 q_begin: int, q_count: int, route: str = "exact", stats: Optional[dict] = None):
+    """One kz_radius_neighbors / kz_radius_neighbors_sweep / kz_radius_neighbors_reduced call -> (indptr [q_count + 1], ind [capacity],
+    dist [capacity], total).  A sweep call's kz_radius_sweep_stats go into `stats` and are appended to stats["calls"]."""
     indptr = ctx.empty((q_count + 1,), np.int64)
     ind = ctx.empty((capacity,), np.int64)
     dist = ctx.empty((capacity,), np.float64)
     total = _I64(0)
-    if kind is None:
+    if route == "sweep":
+        st = RadiusSweepStats()
+        _call(ctx, "kz_radius_neighbors_sweep", query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)), capacity,
+              indptr.ptr, ind.ptr, dist.ptr, C.byref(total), C.byref(st))
+        if stats is not None:
+            calls = stats.get("calls", []) + [st.as_dict()]
+            stats.update(st.as_dict())
+            stats["calls"] = calls
+    elif kind is None:
         _call(ctx, "kz_radius_neighbors", query.handle, q_begin, q_count, index.handle, radius, int(bool(sort_results)), capacity, indptr.ptr,
               ind.ptr, dist.ptr, C.byref(total))
     else:
@@ -701,7 +729,8 @@ def _radius_call(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius:
 
 def radius_neighbors(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius: float, kind: Optional[int] = None, q_state=None,
                      t_state=None, sort_results: bool = True, capacity: Optional[int] = None, q_begin: int = 0,
-                     q_count: Optional[int] = None) -> Tuple[DeviceArray, DeviceArray, DeviceArray, int]:
+                     q_count: Optional[int] = None, route: str = "exact",
+                     stats: Optional[dict] = None) -> Tuple[DeviceArray, DeviceArray, DeviceArray, int]:
     """kz_radius_neighbors (`kind` None) / kz_radius_neighbors_reduced -> (indptr int64 [q_count + 1], ind int64, dist float64, total):
     every index row j with w <= radius for query row q_begin + r, as a CSR on the device -- w the distance `knn` returns or, with a
     `kind` of `gold_ranks_reduced` and its `q_state` / `t_state`, the hubness-reduced distance of `knn_reduced`; a NaN w is never in
@@ -711,10 +740,18 @@ def radius_neighbors(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, rad
     second call with room for exactly the total, refused with MemoryError (naming the total) when the output would not fit what
     the device has free; ind / dist come back with `total` entries.  `capacity` given: that one call as the library makes it -- ind /
     dist have `capacity` entries, hold the rows whose end offset is <= capacity and nothing defined beyond them; indptr and total
-    are exact either way (capacity 0: `radius_counts`)."""
+    are exact either way (capacity 0: `radius_counts`).
+
+    `route="sweep"` (plain calls only): kz_radius_neighbors_sweep -- the same bytes, the pairs found by a sweep of the fp16 images and
+    evaluated exactly; `stats` (a dict) receives the kz_radius_sweep_stats of the last native call and, under "calls", of every one."""
+    checked_rank_route(route)
     radius = radius_value(radius)
     if q_count is None:
         q_count = query.shape[0] - q_begin
+    if route == "sweep" and kind is not None:
+        raise NotImplementedError("radius_neighbors: route='sweep' serves the plain distance only, not a hubness-reduced one")
+    if stats is not None:
+        stats.pop("calls", None)
     state = None
     if kind is not None:
         if q_state is None or t_state is None:
@@ -726,10 +763,10 @@ def radius_neighbors(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, rad
     if capacity is not None:
         if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
             raise ValueError(f"capacity must be a non-negative integer, got {capacity!r}")
-        return _radius_call(ctx, query, index, radius, sort_results, int(capacity), kind, state, q_begin, q_count)
+        return _radius_call(ctx, query, index, radius, sort_results, int(capacity), kind, state, q_begin, q_count, route, stats)
     n_q = max(int(q_count), 0)
     first = min(n_q * index.shape[0], RADIUS_FIRST_CAPACITY_PER_ROW * n_q)
-    indptr, ind, dist, total = _radius_call(ctx, query, index, radius, sort_results, first, kind, state, q_begin, q_count)
+    indptr, ind, dist, total = _radius_call(ctx, query, index, radius, sort_results, first, kind, state, q_begin, q_count, route, stats)
     if total > first:
         del ind, dist   # (back to the context's pool: counted as free below)
         # 16 bytes per pair, and as much again while rows beyond the LDS sort's reach are sorted through HBM
@@ -738,14 +775,15 @@ def radius_neighbors(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, rad
         if need > free:
             raise MemoryError(f"radius_neighbors: total = {total} pairs within radius {radius!r} need {need} bytes of device memory, "
                               f"{free} are free: use a smaller radius or a row range (q_begin / q_count)")
-        indptr, ind, dist, total = _radius_call(ctx, query, index, radius, sort_results, total, kind, state, q_begin, q_count)
+        indptr, ind, dist, total = _radius_call(ctx, query, index, radius, sort_results, total, kind, state, q_begin, q_count, route, stats)
     return indptr, ind.view_rows(0, total), dist.view_rows(0, total), total
 
 
 def radius_counts(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, radius: float, kind: Optional[int] = None, q_state=None,
-                  t_state=None, q_begin: int = 0, q_count: Optional[int] = None) -> Tuple[DeviceArray, int]:
+                  t_state=None, q_begin: int = 0, q_count: Optional[int] = None, route: str = "exact",
+                  stats: Optional[dict] = None) -> Tuple[DeviceArray, int]:
     """`radius_neighbors` with capacity 0 -> (indptr int64 [q_count + 1] on the device, total): the counts alone, nothing else written."""
-    indptr, _, _, total = radius_neighbors(ctx, query, index, radius, kind, q_state, t_state, False, 0, q_begin, q_count)
+    indptr, _, _, total = radius_neighbors(ctx, query, index, radius, kind, q_state, t_state, False, 0, q_begin, q_count, route, stats)
     return indptr, total
 
 

@@ -116,7 +116,7 @@ class Kiez:
         return (dist, ind) if return_distance else ind
 
     def radius_neighbors(self, radius, reduced: bool = False, return_distance: bool = True, sort_results: bool = True,
-                         ragged: bool = False):
+                         ragged: bool = False, route: str = "exact"):
         """Every target row within `radius` of every source row, over the whole target index: the similarity join by threshold, the
         abstain rule for dangling entities (an empty row: no target is close enough) -- `radius_neighbors` of scikit-learn's
         `NearestNeighbors`, without an n_source x n_target matrix and without `kneighbors_whole_index`'s fixed width.
@@ -133,9 +133,16 @@ class Kiez:
         with `sort_results=False`, by target row.  numpy arrays, or tensors when fitted on tensors.  `dist` is in the dtype
         `kneighbors` returns; for float32 cosine / precomputed input the float64 value is rounded to float32 AFTER it was compared, so
         a float32 distance may round to just above `radius`.  `ragged=True` gives scikit-learn's layout instead -- `(dist, ind)` or
-        `ind`, numpy object arrays of one array per source row -- by one split on the host."""
-        algo = self.hubness if reduced else self.algorithm
-        res = algo.radius_neighbors(radius, return_distance=return_distance, sort_results=sort_results)
+        `ind`, numpy object arrays of one array per source row -- by one split on the host.
+
+        `route="sweep"` (opt-in, `reduced=False` only): the same result from a sweep of the fp16 MFMA kernels plus the exact values of
+        its candidate pairs (`SklearnNN.radius_neighbors`); its statistics are `algorithm.radius_stats_`.  With `reduced=True` it
+        raises NotImplementedError: reduced radii have no sweep yet.  An unknown route raises ValueError."""
+        self._checked_radius_route(route, reduced)
+        if reduced:
+            res = self.hubness.radius_neighbors(radius, return_distance=return_distance, sort_results=sort_results)
+        else:
+            res = self.algorithm.radius_neighbors(radius, return_distance=return_distance, sort_results=sort_results, route=route)
         if not ragged:
             return res
         host = [r.cpu().numpy() if hasattr(r, "cpu") else r for r in res]
@@ -147,10 +154,20 @@ class Kiez:
             return out
         return (rows(host[2]), rows(host[1])) if return_distance else rows(host[1])
 
-    def radius_counts(self, radius, reduced: bool = False):
-        """The number of target rows within `radius` of every source row (`radius_neighbors`' rule and `reduced`): int64 [n_source],
-        the per-row density count -- no pair is stored."""
-        return (self.hubness if reduced else self.algorithm).radius_counts(radius)
+    def radius_counts(self, radius, reduced: bool = False, route: str = "exact"):
+        """The number of target rows within `radius` of every source row (`radius_neighbors`' rule, `reduced` and `route`): int64
+        [n_source], the per-row density count -- no pair is stored."""
+        self._checked_radius_route(route, reduced)
+        if reduced:
+            return self.hubness.radius_counts(radius)
+        return self.algorithm.radius_counts(radius, route=route)
+
+    @staticmethod
+    def _checked_radius_route(route, reduced):
+        N.checked_rank_route(route)
+        if reduced and route == "sweep":
+            raise NotImplementedError("route='sweep' thresholds the search metric only: with reduced=True use route='exact' "
+                                      "(radii under a hubness reduction have no sweep yet)")
 
     def _lists_for_matching(self, k, whole_index):
         """The device lists a one-to-one step runs on -> a `PairList`."""

@@ -253,6 +253,7 @@ class SklearnNN(NNAlgorithm):
         self.last_stats = None
         self.last_stats_reverse = None   # statistics of the target -> source direction of the last shared sweep (else None)
         self.rank_stats_ = None          # kz_rank_sweep_stats of the last gold_ranks(route="sweep") (None after route="exact")
+        self.radius_stats_ = None        # kz_radius_sweep_stats of the last radius call with route="sweep" (None after route="exact")
 
     def __repr__(self):
         return (f"{self.__class__.__name__}(n_candidates={self.n_candidates},algorithm={self.algorithm},"
@@ -551,14 +552,17 @@ class SklearnNN(NNAlgorithm):
             return N.cast_f32(self.ctx, dist) if dist.shape[0] else self.ctx.empty((0,), np.float32)
         return dist
 
-    def radius_neighbors_device(self, radius, s_to_t=True, sort_results=True):
+    def radius_neighbors_device(self, radius, s_to_t=True, sort_results=True, route="exact"):
         """`radius_neighbors` with the CSR left in HBM: (indptr int64 [n_query + 1], ind int64 [total], dist [total]) DeviceArrays."""
+        N.checked_rank_route(route)
         radius = N.radius_value(radius)
         query, index = self._two_sided_operands("radius_neighbors", s_to_t)
-        indptr, ind, dist, _ = N.radius_neighbors(self.ctx, query, index, radius, sort_results=sort_results)
+        self.radius_stats_ = {} if route == "sweep" else None
+        indptr, ind, dist, _ = N.radius_neighbors(self.ctx, query, index, radius, sort_results=sort_results, route=route,
+                                                  stats=self.radius_stats_)
         return indptr, ind, self._radius_distances(dist, self._direction(s_to_t)[1])
 
-    def radius_neighbors(self, radius, s_to_t=True, return_distance=True, sort_results=True):
+    def radius_neighbors(self, radius, s_to_t=True, return_distance=True, sort_results=True, route="exact"):
         """Every index row within `radius` of every query row under the search metric, over the whole index: the other half of
         scikit-learn's `NearestNeighbors`.  Query rows are the fitted source rows and the index the fitted target (`s_to_t=False`:
         the reverse).  Pair (i, j) is in the result exactly when d_ij <= radius, d the float64 distance `kneighbors` computes for
@@ -570,16 +574,22 @@ class SklearnNN(NNAlgorithm):
         arrays, or tensors when fitted on tensors.  `dist` has the dtype `kneighbors` returns: for float32 cosine / precomputed
         input it is the float64 distance rounded to float32 AFTER the comparison, so a returned value may round to just above
         `radius`.  Memory is the result's, not n_query x n_index: a total that does not fit the device raises MemoryError.
-        NotFittedError before `fit`, NotImplementedError after a single-source fit, as `gold_ranks`."""
-        indptr, ind, dist = self.radius_neighbors_device(radius, s_to_t, sort_results)
+        NotFittedError before `fit`, NotImplementedError after a single-source fit, as `gold_ranks`.
+
+        `route="sweep"` (opt-in): the same result, byte for byte, from a sweep of the fp16 MFMA kernels that finds the candidate
+        pairs plus their exact values (kz_radius_neighbors_sweep); what it did -- route taken, candidates, overflow, times -- is
+        `radius_stats_`.  Shapes outside the sweep take the exact route whole.  An unknown route raises ValueError."""
+        indptr, ind, dist = self.radius_neighbors_device(radius, s_to_t, sort_results, route)
         return self._results_to_host(indptr, ind, dist) if return_distance else self._results_to_host(indptr, ind)
 
-    def radius_counts(self, radius, s_to_t=True):
+    def radius_counts(self, radius, s_to_t=True, route="exact"):
         """The number of index rows within `radius` of every query row (`radius_neighbors`' rule) -- int64 [n_query], numpy or a
-        tensor when fitted on tensors -- without the pairs: nothing but n_query + 1 offsets is allocated."""
+        tensor when fitted on tensors -- without the pairs: nothing but n_query + 1 offsets is allocated.  `route` as there."""
+        N.checked_rank_route(route)
         radius = N.radius_value(radius, "radius_counts")
         query, index = self._two_sided_operands("radius_counts", s_to_t)
-        indptr, _ = N.radius_counts(self.ctx, query, index, radius)
+        self.radius_stats_ = {} if route == "sweep" else None
+        indptr, _ = N.radius_counts(self.ctx, query, index, radius, route=route, stats=self.radius_stats_)
         indptr, = self._results_to_host(indptr)
         return indptr[1:] - indptr[:-1]
 
