@@ -464,6 +464,27 @@ int kz_gold_ranks_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, 
 int kz_knn_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                    int k, int kind, const double* d_q_a, const double* d_q_b, const double* d_t_a, const double* d_t_b,
                    double* d_w, int64_t* d_ind);
+/* kz_knn_reduced on the certified fp16 sweep -- ABI v7, additive, opt-in: the SAME BYTES in d_w / d_ind for every input.
+ * d_seed_ind: [q_count, k_seed] int64 on the device, k_seed >= k (else KZ_ERR_INVALID): per query row any index rows -- after a fit
+ * the forward candidate lists.  The k-th smallest exact w among a row's valid, distinct seeds bounds its k-th smallest w over the
+ * whole index from above; under CSLS, LS, NICDM and the dual potentials "w <= that bound" is a threshold on the fp16 tier's key that
+ * is rank one in (query row, index row), so one sweep of the fp16 images logs every pair that may qualify, those get the exact float64
+ * w -- the value the call returns -- and each row's k smallest by (w, index row) are selected.  The rounding bound checks itself on
+ * every logged pair and every row checks that its seeds came back.
+ * The WHOLE call takes kz_knn_reduced (route_taken = 0, never an error) for: rows that are not float32, metrics other than euclidean /
+ * sqeuclidean / cosine, d < 17 or d > 384, fewer than 128 index rows, a precomputed handle, k > 128, k_seed > 1024,
+ * KZ_RANK_MP_NORMAL, a row with fewer than k valid distinct seeds, a state that is not finite or outside a form's domain (NICDM / LS:
+ * entries <= 0; LS: a bound >= 1), a candidate log that overflowed, a violated bound.  Errors are kz_knn_reduced's. */
+typedef struct kz_knn_reduced_sweep_stats {
+    int32_t route_taken;      /* 1 sweep, 0 exact route */
+    int32_t overflowed;       /* 1: the candidate log was too small (the call then took the exact route) */
+    int64_t n_rows, n_candidates;   /* query rows; log entries of the sweep */
+    double max_err_ratio;     /* max over the logged pairs of |approximate - exact left-hand side| / bound: <= 1 */
+    double sweep_ms, resolve_ms, fallback_ms;
+} kz_knn_reduced_sweep_stats;
+int kz_knn_reduced_sweep(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                         int k, int kind, const double* d_q_a, const double* d_q_b, const double* d_t_a, const double* d_t_b,
+                         const int64_t* d_seed_ind, int k_seed, double* d_w, int64_t* d_ind, kz_knn_reduced_sweep_stats* stats);
 /* RADIUS NEIGHBOURS over the whole index -- ABI v7, additive: every pair within a threshold, as a CSR.  Pair (r, j) of query row
  * q_begin + r and index row j is in the result exactly when w_rj <= radius, where w is what the list calls return for the pair:
  * kz_radius_neighbors: the distance kz_knn returns (the exact float64 ranking value converted as kz_knn converts it);

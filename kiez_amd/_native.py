@@ -142,6 +142,23 @@ class RadiusSweepStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class KnnReducedSweepStats(C.Structure):
+    """kz_knn_reduced_sweep_stats: which route a `knn_reduced_sweep` call took, what its candidate log held and the times."""
+    _fields_ = [
+        ("route_taken", C.c_int32),
+        ("overflowed", C.c_int32),
+        ("n_rows", C.c_int64),
+        ("n_candidates", C.c_int64),
+        ("max_err_ratio", C.c_double),
+        ("sweep_ms", C.c_double),
+        ("resolve_ms", C.c_double),
+        ("fallback_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FitInfo(C.Structure):
     """kz_fit_info: the sizes, the plan that ran and the statistics of the searches of a fitted object."""
     _fields_ = [
@@ -229,6 +246,7 @@ SYMBOLS = [
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_radius_neighbors", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64)]),
+    ("kz_knn_reduced_sweep", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("kz_radius_neighbors_sweep", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64), _P]),
     ("kz_radius_neighbors_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                               C.POINTER(_I64)]),
@@ -673,7 +691,8 @@ def knn_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, 
                 q_count: Optional[int] = None) -> Tuple[DeviceArray, DeviceArray]:
     """kz_knn_reduced -> (w float64 [q_count, k], ind int64 [q_count, k]) on the device: the k index rows with the smallest
     hubness-reduced distance to query row q_begin + r over the WHOLE index, ascending by (w, index row) -- the list the ranks of
-    `gold_ranks_reduced` are positions in.  `kind`, `q_state` and `t_state` as there."""
+    `gold_ranks_reduced` are positions in.  `kind`, `q_state` and `t_state` as there.  (`knn_reduced_sweep`: the same bytes from the
+    fp16 sweep.)"""
     if q_count is None:
         q_count = query.shape[0] - q_begin
     state = _reduction_state(q_state, t_state, q_count, index.shape[0])
@@ -683,6 +702,29 @@ def knn_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, 
     w = ctx.empty(shape, np.float64)
     ind = ctx.empty(shape, np.int64)
     _call(ctx, "kz_knn_reduced", query.handle, q_begin, q_count, index.handle, k, int(kind), *state, w.ptr, ind.ptr)
+    return w, ind
+
+
+def knn_reduced_sweep(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, k: int, kind: int, q_state, t_state, seed_ind: DeviceArray,
+                      q_begin: int = 0, q_count: Optional[int] = None, stats: Optional[dict] = None) -> Tuple[DeviceArray, DeviceArray]:
+    """kz_knn_reduced_sweep -> what `knn_reduced` returns for the same arguments, byte for byte: the pairs found by a sweep of the fp16
+    images under a threshold seeded from `seed_ind` (int64 DeviceArray [q_count, k_seed], k_seed >= k: any index rows per query row,
+    e.g. its forward candidates) and evaluated exactly.  `stats` (a dict) receives the call's kz_knn_reduced_sweep_stats.  What the
+    sweep does not serve takes the exact route inside the call (`route_taken` 0)."""
+    if q_count is None:
+        q_count = query.shape[0] - q_begin
+    state = _reduction_state(q_state, t_state, q_count, index.shape[0])
+    k = int(k)
+    if not isinstance(seed_ind, DeviceArray) or seed_ind.dtype != np.int64 or len(seed_ind.shape) != 2 or seed_ind.shape[0] != q_count:
+        raise ValueError(f"seed_ind must be an int64 DeviceArray of shape ({q_count}, k_seed)")
+    shape = (q_count, k) if 1 <= k <= min(index.shape[0], KNN_REDUCED_MAX_K) else (0, 0)
+    w = ctx.empty(shape, np.float64)
+    ind = ctx.empty(shape, np.int64)
+    st = KnnReducedSweepStats()
+    _call(ctx, "kz_knn_reduced_sweep", query.handle, q_begin, q_count, index.handle, k, int(kind), *state, seed_ind.ptr, int(seed_ind.shape[1]),
+          w.ptr, ind.ptr, C.byref(st))
+    if stats is not None:
+        stats.update(st.as_dict())
     return w, ind
 
 

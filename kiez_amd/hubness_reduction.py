@@ -253,9 +253,10 @@ class HubnessReduction(ABC):
             raise ValueError(f"kneighbors_whole_index needs a positive integer k, got {k!r}")
         return int(k)
 
-    def kneighbors_whole_index_device(self, k: int):
+    def kneighbors_whole_index_device(self, k: int, route: str = "exact"):
         """`kneighbors_whole_index` with the result left in HBM: (dist, ind) DeviceArrays."""
         k = self._whole_index_k(k)
+        N.checked_rank_route(route)
         if not self._gpu_nn:
             raise NotImplementedError("kneighbors_whole_index needs one of the device-native reductions on the MI355X SklearnNN backend")
         nn = self.nn_algo
@@ -268,12 +269,24 @@ class HubnessReduction(ABC):
             raise NotImplementedError(f"kneighbors_whole_index returns up to {N.KNN_REDUCED_MAX_K} neighbours per query, got k = {k}: "
                                       "beyond that, gold_ranks ranks any target row against the whole index")
         kind, q_state, t_state = self._forward_rank_state()
-        od, oi = N.knn_reduced(self.ctx, query, index, k, kind, q_state, t_state)
+        nn.reduced_stats_ = {} if route == "sweep" else None
+        seed_ind = None
+        if route == "sweep":
+            # the rows whose exact w seed the thresholds: the forward candidate lists, or one plain search when k exceeds them
+            # (a cached shared-sweep result is put back, as `_forward_rank_state` does)
+            cached = nn._forward
+            _, seed_ind = nn.kneighbors_device(query=None, k=nn.n_candidates if k <= nn.n_candidates else k)
+            if cached is not None:
+                nn._forward = cached
+        if route == "sweep":
+            od, oi = N.knn_reduced_sweep(self.ctx, query, index, k, kind, q_state, t_state, seed_ind, stats=nn.reduced_stats_)
+        else:
+            od, oi = N.knn_reduced(self.ctx, query, index, k, kind, q_state, t_state)
         if nn._out_dtype(nn.target_index) == np.float32:
             od = N.cast_f32(self.ctx, od)
         return od, oi
 
-    def kneighbors_whole_index(self, k: int):
+    def kneighbors_whole_index(self, k: int, route: str = "exact"):
         """The k nearest target rows of every source row by the HUBNESS-REDUCED distance over the WHOLE target index: the exact
         CSLS / LocalScaling / NICDM / MutualProximity-'normal' neighbour list, as CSLS was defined over the full similarity matrix.
 
@@ -286,8 +299,13 @@ class HubnessReduction(ABC):
 
         Returns (dist, ind) like `kneighbors`: numpy arrays, or tensors when fitted on tensors; dist in the dtype `kneighbors`
         returns.  NoHubnessReduction returns the plain `kneighbors(k)`.  MutualProximity 'empiric', DisSimLocal and user-written
-        reductions raise NotImplementedError (no value outside the list), a single-source fit too (two-sided data only)."""
-        od, oi = self.kneighbors_whole_index_device(k)
+        reductions raise NotImplementedError (no value outside the list), a single-source fit too (two-sided data only).
+
+        `route="sweep"` (opt-in): the same lists, bit for bit, from kz_knn_reduced_sweep -- a sweep of the fp16 images under per-row
+        thresholds seeded from the forward candidate lists (one plain search of k neighbours when k > n_candidates), the surviving
+        pairs evaluated exactly.  MutualProximity 'normal' and shapes outside the sweep take the exact route inside the call; which
+        route ran, the candidate count and the times are in `nn_algo.reduced_stats_`.  An unknown route raises ValueError."""
+        od, oi = self.kneighbors_whole_index_device(k, route)
         return self._to_host(od, oi)
 
     # ---- every pair within a threshold of the reduced distance, whole index -----------------------------
@@ -415,10 +433,12 @@ class NoHubnessReduction(HubnessReduction):
         return self.nn_algo.gold_ranks_device(gold)   # (nothing is rescaled: the ranks under the search metric)
 
     # (nothing is rescaled: the search's own lists ARE over the whole index)
-    def kneighbors_whole_index_device(self, k: int):
+    def kneighbors_whole_index_device(self, k: int, route: str = "exact"):
+        N.checked_rank_route(route)
         return self.kneighbors_device(self._whole_index_k(k))
 
-    def kneighbors_whole_index(self, k: int):
+    def kneighbors_whole_index(self, k: int, route: str = "exact"):
+        N.checked_rank_route(route)
         return self.kneighbors(self._whole_index_k(k))
 
     # (nothing is rescaled: the pairs within a threshold of the search metric)

@@ -102,16 +102,20 @@ class Kiez:
         dist, ind = self.hubness.kneighbors(k)
         return (dist, ind) if return_distance else ind
 
-    def kneighbors_whole_index_device(self, k: int):
+    def kneighbors_whole_index_device(self, k: int, route: str = "exact"):
         """Like `kneighbors_whole_index` but the (dist, ind) result stays in HBM as DeviceArrays."""
-        return self.hubness.kneighbors_whole_index_device(k)
+        N.checked_rank_route(route)
+        return self.hubness.kneighbors_whole_index_device(k) if route == "exact" else self.hubness.kneighbors_whole_index_device(k, route)
 
     def kneighbors_whole_index(self, k: int, return_distance: bool = True):
         """The k nearest targets of every source row by the hubness-reduced distance over the WHOLE target index
         (`HubnessReduction.kneighbors_whole_index`: CSLS, LocalScaling 'standard' / 'nicdm', MutualProximity 'normal'; none: the plain
         `kneighbors(k)`), where `kneighbors(k)` rescales the `n_candidates` nearest targets only.  The lists `gold_ranks(gold,
         reduced=True)` ranks in: hits@k of the two agree.  `k` is required, at most min(n_target, 512), and not clamped to
-        `n_candidates`.  MutualProximity 'empiric' and DisSimLocal raise NotImplementedError."""
+        `n_candidates`.  MutualProximity 'empiric' and DisSimLocal raise NotImplementedError.
+        The same lists, bit for bit, from a sweep of the fp16 images with exact evaluation of the surviving pairs (opt-in):
+        `hubness.kneighbors_whole_index(k, route="sweep")` or `kneighbors_whole_index_device(k, route="sweep")`; its statistics are
+        `algorithm.reduced_stats_`."""
         dist, ind = self.hubness.kneighbors_whole_index(k)
         return (dist, ind) if return_distance else ind
 

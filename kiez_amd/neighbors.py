@@ -253,6 +253,7 @@ class SklearnNN(NNAlgorithm):
         self.last_stats = None
         self.last_stats_reverse = None   # statistics of the target -> source direction of the last shared sweep (else None)
         self.rank_stats_ = None          # kz_rank_sweep_stats of the last gold_ranks(route="sweep") (None after route="exact")
+        self.reduced_stats_ = None       # kz_knn_reduced_sweep_stats of the last kneighbors_whole_index(route="sweep") (None after "exact")
         self.radius_stats_ = None        # kz_radius_sweep_stats of the last radius call with route="sweep" (None after route="exact")
 
     def __repr__(self):
