@@ -448,6 +448,18 @@ int kz_gold_ranks_sweep(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, in
 int kz_gold_ranks_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
                           const int64_t* d_gold, int kind, const double* d_q_a, const double* d_q_b,
                           const double* d_t_a, const double* d_t_b, int64_t* d_rank);
+/* kz_gold_ranks_reduced on the certified fp16 MFMA count sweep -- ABI v7, additive, opt-in: the same d_rank on every row.  Per row
+ * with a gold id tau = the exact w of the gold pair.  Under CSLS, LS, NICDM and the dual potentials "w_j against tau" is a threshold on
+ * the fp16 tier's key that is rank one in (query row, index row); one sweep of the fp16 images counts the index rows surely closer
+ * (above the high edge) and logs the rows between the two edges (the band), whose exact float64 w then decide, ties by index row.
+ * Rows that are not trusted (a tau or an edge that is not finite or outside a form's domain -- LS: tau > 1 - 2^-20 --, more than
+ * 1 024 band entries, a bound that its own check finds violated, every row when the band log overflows) are answered by the exact
+ * route.  The WHOLE call takes kz_gold_ranks_reduced's route (route_taken = 0, never an error) for the shapes kz_gold_ranks_sweep
+ * sends to the exact route, KZ_RANK_MP_NORMAL and a state that is not finite or outside a form's domain (NICDM / LS: entries <= 0).
+ * Arguments, validation and errors are kz_gold_ranks_reduced's; stats (kz_gold_ranks_sweep's record) may be NULL. */
+int kz_gold_ranks_reduced_sweep(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t q_count, const kz_matrix* index,
+                                const int64_t* d_gold, int kind, const double* d_q_a, const double* d_q_b,
+                                const double* d_t_a, const double* d_t_b, int64_t* d_rank, kz_rank_sweep_stats* stats);
 /* The list those ranks are positions in -- ABI v7, additive: the k nearest index rows of every query row by the REDUCED distance w
  * over the WHOLE index, not over a candidate list (kz_csls / kz_local_scaling / kz_mp_normal rescale K candidates; an index row
  * outside them can have a smaller w).  Row r of d_w / d_ind ([q_count, k] on the device) holds the k index rows with the smallest w

@@ -107,7 +107,8 @@ class KnnStats(C.Structure):
 
 
 class RankSweepStats(C.Structure):
-    """kz_rank_sweep_stats: which route a `gold_ranks(route="sweep")` call took and what its band and fallbacks came to."""
+    """kz_rank_sweep_stats: which route a `gold_ranks(route="sweep")` / `gold_ranks_reduced_sweep` call took and what its band and
+    fallbacks came to."""
     _fields_ = [
         ("route_taken", C.c_int32),
         ("n_rows", C.c_int64),
@@ -244,6 +245,7 @@ SYMBOLS = [
     ("kz_gold_ranks", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
     ("kz_gold_ranks_sweep", C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
     ("kz_gold_ranks_reduced", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    ("kz_gold_ranks_reduced_sweep", C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_knn_reduced", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("kz_radius_neighbors", C.c_int, [_P, _P, _I64, _I64, _P, C.c_double, C.c_int, _I64, _P, _P, _P, C.POINTER(_I64)]),
     ("kz_knn_reduced_sweep", C.c_int, [_P, _P, _I64, _I64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
@@ -665,6 +667,25 @@ def gold_ranks_reduced(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, g
     state = _reduction_state(q_state, t_state, q_count, index.shape[0])
     rank = ctx.empty((q_count,), np.int64)
     _call(ctx, "kz_gold_ranks_reduced", query.handle, q_begin, q_count, index.handle, gold_dev.ptr, int(kind), *state, rank.ptr)
+    return rank
+
+
+def gold_ranks_reduced_sweep(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev: DeviceArray, kind: int, q_state, t_state,
+                             q_begin: int = 0, q_count: Optional[int] = None, stats: Optional[dict] = None) -> DeviceArray:
+    """kz_gold_ranks_reduced_sweep -> what `gold_ranks_reduced` returns for the same arguments, on every row: the ranks from a count
+    sweep of the fp16 images under a rank-one threshold at the gold pair's own w, with the exact w of the undecided pairs.  `stats`
+    (a dict) receives the call's kz_rank_sweep_stats.  What the sweep does not serve (MP normal, shapes outside it, a state outside a
+    form's domain) takes the exact route inside the call (`route_taken` 0)."""
+    if q_count is None:
+        q_count = query.shape[0] - q_begin
+    if gold_dev.dtype != np.int64 or gold_dev.shape != (q_count,):
+        raise ValueError(f"gold_dev must be int64 of shape ({q_count},), got {gold_dev.dtype} {gold_dev.shape}")
+    state = _reduction_state(q_state, t_state, q_count, index.shape[0])
+    rank = ctx.empty((q_count,), np.int64)
+    st = RankSweepStats()
+    _call(ctx, "kz_gold_ranks_reduced_sweep", query.handle, q_begin, q_count, index.handle, gold_dev.ptr, int(kind), *state, rank.ptr, C.byref(st))
+    if stats is not None:
+        stats.update(st.as_dict())
     return rank
 
 

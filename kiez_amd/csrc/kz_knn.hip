@@ -1834,6 +1834,7 @@ extern "C" int kz_knn(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int6
 #include "kz_radius.h"
 #include "kz_radius_sweep.h"
 #include "kz_knn_reduced_sweep.h"
+#include "kz_rank_r1_sweep.h"
 #include "kz_pairs.h"
 #include "kz_softmin.h"
 #include "kz_knn_dual.h"

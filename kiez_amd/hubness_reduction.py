@@ -216,8 +216,9 @@ class HubnessReduction(ABC):
             nn._forward = cached
         return self._rank_state(query_dist)
 
-    def gold_ranks_device(self, gold) -> N.DeviceArray:
+    def gold_ranks_device(self, gold, route: str = "exact") -> N.DeviceArray:
         """`gold_ranks` that leaves the int64 rank vector in HBM (evaluate.rank_metrics reduces it there)."""
+        N.checked_rank_route(route)
         if not self._gpu_nn:
             raise NotImplementedError("gold_ranks under a hubness reduction needs one of the device-native reductions on the "
                                       "MI355X SklearnNN backend")
@@ -226,9 +227,12 @@ class HubnessReduction(ABC):
         if self._no_rank_reason:
             raise NotImplementedError(f"{type(self).__name__}: {self._no_rank_reason}")
         kind, q_state, t_state = self._forward_rank_state()
+        nn.rank_stats_ = {} if route == "sweep" else None
+        if route == "sweep":
+            return N.gold_ranks_reduced_sweep(self.ctx, query, index, gold_dev, kind, q_state, t_state, stats=nn.rank_stats_)
         return N.gold_ranks_reduced(self.ctx, query, index, gold_dev, kind, q_state, t_state)
 
-    def gold_ranks(self, gold) -> np.ndarray:
+    def gold_ranks(self, gold, route: str = "exact") -> np.ndarray:
         """Exact 0-based rank of every source row's gold target against the WHOLE target index under the HUBNESS-REDUCED distances
         (`SklearnNN.gold_ranks`: under the search metric; same `gold`, same result vector, -1 = no gold id).
 
@@ -243,8 +247,13 @@ class HubnessReduction(ABC):
         * MutualProximity 'normal' is exactly 1.0 for pairs far beyond both lists (the product of two survival functions falls
           below 2^-53): with small K most pairs tie there and are ordered by target row.
         MutualProximity 'empiric' (its value depends on list membership) and DisSimLocal (its values come from its own gather of
-        the embeddings, not from the search's distances) raise NotImplementedError, as does a user-written reduction."""
-        return self.gold_ranks_device(gold).numpy()
+        the embeddings, not from the search's distances) raise NotImplementedError, as does a user-written reduction.
+
+        `route="sweep"` (opt-in): the same ranks from kz_gold_ranks_reduced_sweep -- one count sweep of the fp16 images under a
+        rank-one threshold at each gold pair's own reduced distance, plus the exact values of the pairs it cannot decide.
+        MutualProximity 'normal' and shapes outside the sweep take the exact route inside the call; which route ran, the band pairs,
+        the fallback rows and the times are in `nn_algo.rank_stats_`.  An unknown route raises ValueError."""
+        return self.gold_ranks_device(gold, route).numpy()
 
     # ---- neighbour lists by the reduced distance over the whole index ----------------------------------
     def _whole_index_k(self, k) -> int:
@@ -429,8 +438,8 @@ class NoHubnessReduction(HubnessReduction):
         n_neighbors = self._set_k_if_needed(k)
         return self.nn_algo.kneighbors(query=None, k=n_neighbors, return_distance=True)
 
-    def gold_ranks_device(self, gold) -> N.DeviceArray:
-        return self.nn_algo.gold_ranks_device(gold)   # (nothing is rescaled: the ranks under the search metric)
+    def gold_ranks_device(self, gold, route: str = "exact") -> N.DeviceArray:
+        return self.nn_algo.gold_ranks_device(gold, route=route)   # (nothing is rescaled: the ranks under the search metric)
 
     # (nothing is rescaled: the search's own lists ARE over the whole index)
     def kneighbors_whole_index_device(self, k: int, route: str = "exact"):

@@ -381,13 +381,13 @@ class Kiez:
 
         `route="sweep"` (opt-in, `reduced=False` only): the same ranks from a count sweep of the fp16 MFMA kernels
         (`SklearnNN.gold_ranks`); its statistics are `algorithm.rank_stats_`.  With `reduced=True` it raises NotImplementedError:
-        ranks under a reduction have no sweep yet.  An unknown route raises ValueError."""
+        the sweep under a reduction is `kz.hubness.gold_ranks(gold, route="sweep")`.  An unknown route raises ValueError."""
         N.checked_rank_route(route)
         if not reduced:
             return self.algorithm.gold_ranks(gold, s_to_t=s_to_t, route=route)
         if route == "sweep":
-            raise NotImplementedError("gold_ranks(route='sweep') ranks by the search metric only: with reduced=True use route='exact' "
-                                      "(ranks under a hubness reduction have no sweep yet)")
+            raise NotImplementedError("gold_ranks(route='sweep') ranks by the search metric only: with reduced=True use route='exact', "
+                                      "or hubness.gold_ranks(gold, route='sweep') for the sweep under the reduction")
         if not s_to_t:
             raise ValueError("gold_ranks(reduced=True) ranks source rows against the target index only (s_to_t=True): the hubness "
                              "reduction is fitted for that direction")

@@ -8,7 +8,8 @@ any): `reduced_ms` and the ratio to the plain call.  One JSON line per case.
 
 `--route both` (euclidean float32 cases) times gold_ranks(route="exact") and gold_ranks(route="sweep") ALTERNATED in one process -- seven
 rounds after a warm-up of each, median and min .. max per route -- checks that the two rank vectors are equal and adds the sweep's
-statistics (kz_rank_sweep_stats: band pairs, fallback rows, max_err_ratio, device times).  `--gold correlated`: the index row of every
+statistics (kz_rank_sweep_stats: band pairs, fallback rows, max_err_ratio, device times); it does the same for
+gold_ranks_reduced against gold_ranks_reduced_sweep under CSLS and NICDM (`reduced_csls`, `reduced_nicdm`).  `--gold correlated`: the index row of every
 gold id is its query row plus noise (ranks near 0), instead of uniform random gold ids (ranks near n / 2).
 
 `--metric euclidean --ranks-only` is the run to put under `rocprofv3 --kernel-trace --stats`: only the rank calls of one metric, so
@@ -94,6 +95,22 @@ def main():
                 two = kind == N.RANK_MP_NORMAL
                 q_state, t_state = ((q_a, q_b), (t_a, t_b)) if two else (q_a, t_a)
                 reduced[name] = best_of(lambda: N.gold_ranks_reduced(ctx, sm, tm, gold, kind, q_state, t_state), ctx)
+            if args.route == "both":   # kz_gold_ranks_reduced against kz_gold_ranks_reduced_sweep, alternated as above
+                calls = {"exact": N.gold_ranks_reduced, "sweep": N.gold_ranks_reduced_sweep}
+                for name, kind in (("csls", N.RANK_CSLS), ("nicdm", N.RANK_NICDM)):
+                    times, st = {"exact": [], "sweep": []}, {}
+                    want = calls["exact"](ctx, sm, tm, gold, kind, q_a, t_a).numpy()
+                    calls["sweep"](ctx, sm, tm, gold, kind, q_a, t_a)
+                    ctx.sync()
+                    for _ in range(7):
+                        for r in times:
+                            t0 = time.perf_counter()
+                            got = calls[r](ctx, sm, tm, gold, kind, q_a, t_a, **({"stats": st} if r == "sweep" else {}))
+                            ctx.sync()
+                            times[r].append((time.perf_counter() - t0) * 1e3)
+                            assert np.array_equal(got.numpy(), want), "the reduced routes disagree"
+                    routes[f"reduced_{name}"] = {"sweep_stats": dict(st), **{f"{r}_ms": {"median": round(float(np.median(v)), 3), "min": round(min(v), 3),
+                                                                                        "max": round(max(v), 3)} for r, v in times.items()}}
         line = {"metric": metric, "dtype": "float32", "n_query": n, "n_index": n, "d": d, "gold_ranks_ms": round(rank_ms, 2),
                 "pairs_per_s_gold_ranks": round(n * n / rank_ms * 1e3, 0), "mean_rank": float(ranks.mean()), "min_rank": int(ranks.min())}
         line.update(routes)
