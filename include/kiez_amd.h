@@ -414,7 +414,7 @@ int kz_gold_ranks(kz_ctx* ctx, const kz_matrix* query, int64_t q_begin, int64_t 
  * one sweep of the fp16 operand images counts the index rows surely closer and logs the rows inside the interval (the band), whose
  * exact float64 values then decide.  Rows that are not trusted (a non-finite value or bound, more than 1 024 band entries, a bound
  * that its own check finds violated, every row when the band log overflows) are answered by the exact route of kz_gold_ranks.
- * Shapes outside the sweep -- rows that are not KZ_F32, a metric beyond KZ_COSINE, d > 384 (or fewer than 17 features), precomputed
+ * Shapes outside the sweep -- rows that are not KZ_F32, a metric beyond KZ_COSINE, d < 17, 385 .. 496 or > 2048, precomputed
  * handles, option "precision" = 1, an index of fewer than 128 rows -- take the exact route whole: route_taken = 0, never an error.
  * Validation, d_gold, -1 rows and the synchronisation are kz_gold_ranks'.  stats may be NULL. */
 typedef struct kz_rank_sweep_stats {
@@ -532,7 +532,7 @@ int kz_radius_neighbors_reduced(kz_ctx* ctx, const kz_matrix* query, int64_t q_b
  * (capacity == 0: also which are surely inside, counted in the kernel); the few pairs a row that remain get the exact float64 value
  * -- the value the call returns -- and the predicate w <= radius.  The rounding bound checks itself on every such pair.
  * The WHOLE call takes kz_radius_neighbors (route_taken = 0, never an error) for: a shape outside the sweep -- rows that are not
- * KZ_F32, a metric beyond KZ_COSINE, d > 384 (or fewer than 17 features), precomputed handles, option "precision" = 1, an index of
+ * KZ_F32, a metric beyond KZ_COSINE, d < 17, 385 .. 496 or > 2048, precomputed handles, option "precision" = 1, an index of
  * fewer than 128 rows --; a radius that is not finite or is negative; a candidate log that overflowed (64 entries per query row, at
  * least 2^20, at most a quarter of the free memory); a bound its own check finds violated; a query row whose norm or bound is not finite
  * (a NaN operand among them: the exact route's clamp fmax(NaN, 0) gives such a row the value 0 against every index row).  There is no per-row fallback.  stats may be NULL. */

@@ -631,8 +631,8 @@ def gold_ranks(ctx: Context, query: DeviceMatrix, index: DeviceMatrix, gold_dev:
                q_count: Optional[int] = None, route: str = "exact", stats: Optional[dict] = None) -> DeviceArray:
     """kz_gold_ranks -> int64 [q_count] on the device: the 0-based rank of index row gold_dev[r] for query row q_begin + r against
     the whole index (the position it holds in kz_knn with k = index.n), -1 where gold_dev[r] is INT64_MIN or no index row.
-    `route="sweep"`: kz_gold_ranks_sweep -- the same ranks from a count sweep of the fp16 images with the exact values of the
-    undecided pairs; `stats` (a dict) then receives kz_rank_sweep_stats."""
+    `route="sweep"`: kz_gold_ranks_sweep -- the same ranks from a count sweep of the fp16 images (17 <= d <= 384, 497 <= d <= 2048)
+    with the exact values of the undecided pairs; `stats` (a dict) then receives kz_rank_sweep_stats."""
     checked_rank_route(route)
     if q_count is None:
         q_count = query.shape[0] - q_begin

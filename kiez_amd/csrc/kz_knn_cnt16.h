@@ -263,6 +263,13 @@ __global__ __launch_bounds__(256, WPS) void kz_knn_count_h_kernel(KnnCountParams
                     c += v > lh.y ? 1 : 0;
                     nb += (v >= lh.x && v <= lh.y) ? 1 : 0;
                 }
+                // (one workgroup per CU: with the whole register file to itself the scheduler issues the compares of all 64 keys ahead
+                //  of the serial add chain, their masks fill the scalar registers and 19 .. 21 kernel arguments and lane masks are
+                //  spilled to make room.  The two sums are pinned after every accumulator: 16 masks at a time.  Folds away at WPS >= 2)
+                if constexpr (WPS == 1) {
+                    asm volatile("" : "+v"(c), "+v"(nb));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
             cnt += c;
             if (__builtin_amdgcn_ballot_w64(nb > 0) != 0ull) kz_count_band(acc, lh.x, lh.y, nb, tile, qrow, p);
@@ -287,16 +294,21 @@ __global__ __launch_bounds__(256, WPS) void kz_knn_count_h_kernel(KnnCountParams
     }
 }
 
-// What the host needs of a build.  The builds live in two instantiation units (kz_knn_cnt_lo.hip: 2 .. 13 slices, three workgroups
-// per CU; kz_knn_cnt_hi.hip: 14 .. 24 slices, two), each exporting the lookup over its slice counts: a count without a build gets
-// the empty descriptor, never a neighbouring entry.
+// What the host needs of a build.  The builds live in instantiation units of their own (kz_knn_cnt_lo.hip: 2 .. 13 slices, three
+// workgroups per CU; kz_knn_cnt_hi.hip: 14 .. 24 slices, two; kz_knn_cnt_w.hip: the WIDE ROWS, 32 .. 64 slices in steps of 8 -- one
+// workgroup per CU, one wave per SIMD, the stationary query tile qf[NSR] of 128 .. 256 registers in the unified VGPR + AGPR file,
+// as kz_knn_h_inst.h "WIDE ROWS"; KzCntCfg<1, NSR> is the eight-slot ring, and the loop's switches at WPS = 1 are the list
+// kernel's: late copies, fragment carry, two fragment sets), each exporting the lookup over its slice counts: a count without a
+// build gets the empty descriptor, never a neighbouring entry.  (80 .. 128 slices: kz_knn_cntx16.h.)
 struct KzCountKernel {
     const void* fn;   // nullptr: no build for this slice count
     int lds_bytes;
     int n_slices;
+    int wg_per_item = 1;   // workgroups that sweep one work item (2: the parity-split builds, kz_knn_cntx16.h)
 };
 KzCountKernel kz_count_lookup_lo(int n_slices);
 KzCountKernel kz_count_lookup_hi(int n_slices);
+KzCountKernel kz_count_lookup_w(int n_slices);
 
 template <int WPS, int... NS>
 static KzCountKernel kz_count_table(int n_slices, std::integer_sequence<int, NS...>) {

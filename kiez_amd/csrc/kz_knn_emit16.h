@@ -248,11 +248,12 @@ __global__ __launch_bounds__(256, WPS) void kz_knn_emit_h_kernel(KnnEmitParams p
     }
 }
 
-// The builds live in two instantiation units beside the count kernel's (kz_knn_emit_lo.hip: 2 .. 13 slices, three workgroups per CU;
-// kz_knn_emit_hi.hip: 14 .. 24 slices, two) and come back in the count kernel's descriptor: a slice count without a build gets the
-// empty descriptor.
+// The builds live in instantiation units beside the count kernel's (kz_knn_emit_lo.hip: 2 .. 13 slices, three workgroups per CU;
+// kz_knn_emit_hi.hip: 14 .. 24 slices, two; kz_knn_emit_w.hip: the wide rows, 32 .. 64 slices, one) and come back in the count
+// kernel's descriptor: a slice count without a build gets the empty descriptor.
 KzCountKernel kz_emit_lookup_lo(int n_slices);
 KzCountKernel kz_emit_lookup_hi(int n_slices);
+KzCountKernel kz_emit_lookup_w(int n_slices);
 
 template <int WPS, int... NS>
 static KzCountKernel kz_emit_table(int n_slices, std::integer_sequence<int, NS...>) {

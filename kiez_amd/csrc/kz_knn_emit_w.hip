@@ -1,0 +1,7 @@
+// Emit sweep of the fp16 tier (kz_knn_emit16.h), the wide-row builds of 32 .. 64 slices (d = 497 .. 1024): one workgroup per CU.
+#include "kz_common.h"
+#include "kz_knn_emit16.h"
+
+KzCountKernel kz_emit_lookup_w(int n_slices) {
+    return kz_emit_table<1>(n_slices, std::integer_sequence<int, 32, 40, 48, 56, 64>{});
+}

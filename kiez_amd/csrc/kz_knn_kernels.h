@@ -104,15 +104,17 @@ static int kz_sweep_kernel(int tier, bool dual, bool q64, int KP, int n_slices, 
 // A workgroup may take more than 64 KiB of dynamic LDS only once the function's limit has been raised on the device.  This is the
 // only place that does so, and BOTH the occupancy query and the launch go through it: neither depends on the other having run.
 // The context remembers the functions it has raised (a context is one device), so a call pays for it once per kernel.
-static int kz_sweep_raise_lds(kz_ctx* ctx, const KzSweepKernel& k) {
+// (by function and size: the count and emit sweeps, kz_rank_sweep.h, have a descriptor of their own)
+static int kz_raise_lds(kz_ctx* ctx, const void* fn, int lds_bytes) {
     constexpr int N = (int)(sizeof(kz_ctx::lds_raised) / sizeof(kz_ctx::lds_raised[0]));
-    if (k.lds_bytes <= 64 * 1024) return KZ_OK;
+    if (lds_bytes <= 64 * 1024) return KZ_OK;
     for (int i = 0; i < N; ++i)
-        if (ctx->lds_raised[i] == k.fn) return KZ_OK;
-    KZ_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes));
-    ctx->lds_raised[ctx->lds_raised_next++ % N] = k.fn;   // (full: the oldest entry goes, and is raised again when it comes back)
+        if (ctx->lds_raised[i] == fn) return KZ_OK;
+    KZ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    ctx->lds_raised[ctx->lds_raised_next++ % N] = fn;   // (full: the oldest entry goes, and is raised again when it comes back)
     return KZ_OK;
 }
+static int kz_sweep_raise_lds(kz_ctx* ctx, const KzSweepKernel& k) { return kz_raise_lds(ctx, k.fn, k.lds_bytes); }
 
 // *blocks_per_cu = workgroups of the kernel resident per CU
 static int kz_sweep_occupancy(kz_ctx* ctx, const KzSweepKernel& k, int* blocks_per_cu) {

@@ -15,10 +15,11 @@
 //      route does.
 // The bound checks itself on every evaluated entry (|key~ scale - key| / eps <= 1; an entry logged as "above hi" must pass the
 // predicate).  The WHOLE call takes kz_radius_impl -- route_taken = 0, never an error -- for a shape outside the sweep
-// (kz_rank_sweep_shapes_ok), a radius that is not finite or is negative, a log that overflowed, a violated bound and a row whose
+// (kz_plain_sweep_shapes_ok), a radius that is not finite or is negative, a log that overflowed, a violated bound and a row whose
 // norm or interval is not finite: rows of a CSR are not independent the way ranks are, so there is no per-row fallback.
+// Rows of 80 .. 128 slices (d = 1025 .. 2048): both sweeps are builds of kz_knn_cntx_h_kernel (kz_knn_cntx16.h), two workgroups an item.
 #pragma once
-#include "kz_knn_emit16.h"
+#include "kz_knn_cntx16.h"
 
 enum { KZ_RSW_F_NONFINITE = 1, KZ_RSW_F_VIOLATED = 2 };
 
@@ -185,13 +186,17 @@ __global__ __launch_bounds__(256) void kz_radius_clear_kernel(int* __restrict__ 
     if (i < n) words[i] = 0;
 }
 
-static KzCountKernel kz_emit_lookup(int n_slices) {
+static KzCountKernel kz_emit_lookup(int n_slices) {   // (kz_count_lookup's rule)
+    if (n_slices > 64) return kz_emit_lookup_x(n_slices);
+    if (n_slices > 24) return kz_emit_lookup_w(n_slices);
     return n_slices <= KZ_CNT_WPS3_MAX ? kz_emit_lookup_lo(n_slices) : kz_emit_lookup_hi(n_slices);
 }
 static int kz_emit_launch(kz_ctx* ctx, const KzCountKernel& k, const KnnEmitParams& p, int n_items) {
+    const int rc = kz_raise_lds(ctx, k.fn, k.lds_bytes);
+    if (rc != KZ_OK) return rc;
     KnnEmitParams pc = p;
     void* args[] = {&pc};
-    KZ_HIP(hipLaunchKernel(k.fn, dim3(n_items), dim3(256), args, (size_t)k.lds_bytes, ctx->stream));
+    KZ_HIP(hipLaunchKernel(k.fn, dim3(k.wg_per_item * n_items), dim3(256), args, (size_t)k.lds_bytes, ctx->stream));
     return KZ_OK;
 }
 
@@ -265,14 +270,14 @@ static int kz_radius_sweep_run(const char* who, kz_ctx* ctx, kz_matrix* query, i
                        epsb.get(), flag);
     KZ_HIP(hipGetLastError());
     // ---- the sweep: work items of kz_plan.h unchanged (query tile x index range, rounds in lockstep) -----------------------------
-    const int n_slices = index->kg / 4;
+    const int n_slices = kz_h_nsr(index->kg);   // (the padded count the images are packed with)
     const KzCountKernel kern = emit ? kz_emit_lookup(n_slices) : kz_count_lookup(n_slices);
     if (!kern.fn) {
         kz_set_error("%s: internal: no sweep kernel for %d slices", who, n_slices);
         return KZ_ERR_UNSUPPORTED;
     }
     int per_cu = 1;
-    rc = kz_count_occupancy(kern, &per_cu);
+    rc = kz_count_occupancy(ctx, kern, &per_cu);
     if (rc != KZ_OK) return rc;
     const int slots = per_cu * ctx->n_cus;
     KzPlan pl;
@@ -454,7 +459,7 @@ extern "C" int kz_radius_neighbors_sweep(kz_ctx* ctx, const kz_matrix* query_c, 
     KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "%s: more than 2^31 - 1 rows", who);
     KZ_HIP(hipSetDevice(ctx->device));
     int done = 0;
-    if (q_count > 0 && radius >= 0.0 && radius < (double)INFINITY && kz_rank_sweep_shapes_ok(ctx, query, index)) {
+    if (q_count > 0 && radius >= 0.0 && radius < (double)INFINITY && kz_plain_sweep_shapes_ok(ctx, query, index)) {
         const int rc = kz_radius_sweep_run(who, ctx, query, q_begin, q_count, index, radius, sorted, capacity, d_indptr, d_ind, d_dist, h_total, &st, &done);
         if (rc != KZ_OK) return rc;
     }

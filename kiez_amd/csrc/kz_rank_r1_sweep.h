@@ -315,7 +315,7 @@ static int kz_gold_ranks_r1_run(const char* who, kz_ctx* ctx, kz_matrix* query, 
         return KZ_ERR_UNSUPPORTED;
     }
     int per_cu = 1;
-    rc = kz_count_occupancy(kern, &per_cu);
+    rc = kz_count_occupancy(ctx, kern, &per_cu);
     if (rc != KZ_OK) return rc;
     const int slots = per_cu * ctx->n_cus;
     KzPlan pl;

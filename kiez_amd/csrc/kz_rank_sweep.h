@@ -9,11 +9,11 @@
 //   4. kz_rank_fallback_kernel: rows that are not trusted -- a non-finite value or bound, a band beyond the per-row cap, a violated
 //      bound, a gold row that did not show up in its own band, every row when the log overflowed -- are reset and go through the
 //      exact walk (kz_gold_ranks_walk), as a compacted list.
-// Shapes outside the sweep (kz_rank_sweep_shapes_ok) take kz_gold_ranks_impl whole: same answer, route_taken = 0, never an error.
+// Shapes outside the sweep (kz_plain_sweep_shapes_ok) take kz_gold_ranks_impl whole: same answer, route_taken = 0, never an error.
 // Element types: float32 rows run the sweep; float64, float16 and bfloat16 rows take the exact route (the band's values are read by
 // the float32 kernels' rule only, as kz_exact_pairs_kernel's are).
 #pragma once
-#include "kz_knn_cnt16.h"
+#include "kz_knn_cntx16.h"
 
 // Sizing choices, not tuned figures: a row whose band holds more entries than this is cheaper on the exact walk than worth arguing
 // about (ties by the thousand, a gold row deep inside a tight cluster); the log holds 64 entries per listed row, at least 2^20.
@@ -121,28 +121,47 @@ __global__ __launch_bounds__(256) void kz_rank_fallback_kernel(const int* __rest
     if (tid == 0) fb[n_list] = base;
 }
 
+// By slice count (kz_h_nsr): lo / hi (2 .. 24), the wide rows (32 .. 64), the parity-split builds (80 .. 128).  A count without a
+// build gets the empty descriptor of the unit that would hold it.
 static KzCountKernel kz_count_lookup(int n_slices) {
+    if (n_slices > 64) return kz_count_lookup_x(n_slices);
+    if (n_slices > 24) return kz_count_lookup_w(n_slices);
     return n_slices <= KZ_CNT_WPS3_MAX ? kz_count_lookup_lo(n_slices) : kz_count_lookup_hi(n_slices);
 }
 // The count kernel's own occupancy query and launcher (beside kz_sweep_occupancy / kz_sweep_launch: it is no entry of kz_sweep_kernel's
-// table, whose contract is "lists of K'").  Its workgroups stay below 64 KiB of LDS: no limit to raise.
-static int kz_count_occupancy(const KzCountKernel& k, int* blocks_per_cu) {
+// table, whose contract is "lists of K'").  The builds of 2 .. 24 slices stay below 64 KiB of LDS; the parity-split builds take
+// 97.5 KiB, and BOTH the query and the launch raise the function's limit first (kz_raise_lds: neither depends on the other).
+static int kz_count_occupancy(kz_ctx* ctx, const KzCountKernel& k, int* blocks_per_cu) {
+    const int rc = kz_raise_lds(ctx, k.fn, k.lds_bytes);
+    if (rc != KZ_OK) return rc;
     int nb = 0;
     KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, 256, k.lds_bytes));
     *blocks_per_cu = nb < 1 ? 1 : nb;
     return KZ_OK;
 }
+// n_items work items of the plan: wg_per_item workgroups each
 static int kz_count_launch(kz_ctx* ctx, const KzCountKernel& k, const KnnCountParams& p, int n_items) {
+    const int rc = kz_raise_lds(ctx, k.fn, k.lds_bytes);
+    if (rc != KZ_OK) return rc;
     KnnCountParams pc = p;
     void* args[] = {&pc};
-    KZ_HIP(hipLaunchKernel(k.fn, dim3(n_items), dim3(256), args, (size_t)k.lds_bytes, ctx->stream));
+    KZ_HIP(hipLaunchKernel(k.fn, dim3(k.wg_per_item * n_items), dim3(256), args, (size_t)k.lds_bytes, ctx->stream));
     return KZ_OK;
 }
 
+// Where the sweeps exist.  The rank-one sweeps (kz_rank_r1_sweep.h, kz_knn_reduced_sweep.h) have builds of 2 .. 24 slices; the plain
+// count and emit sweeps (here, kz_radius_sweep.h) of every slice count of the fp16 tier (kz_h_slices_ok: 2 .. 24 and 32 .. 128,
+// d = 17 .. 384 and 497 .. 2048).
+static bool kz_sweep_operands_ok(const kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index) {
+    return !query->pre && !index->pre && ctx->precision != 1 && index->dtype == KZ_F32 && query->dtype == KZ_F32 && index->metric <= KZ_COSINE &&
+           query->kg == index->kg && index->n >= KZ_TILE;
+}
 static bool kz_rank_sweep_shapes_ok(const kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index) {
     const int n_slices = index->kg / 4;
-    return !query->pre && !index->pre && ctx->precision != 1 && index->dtype == KZ_F32 && query->dtype == KZ_F32 && index->metric <= KZ_COSINE &&
-           n_slices >= 2 && n_slices <= 24 && query->kg == index->kg && index->n >= KZ_TILE;
+    return kz_sweep_operands_ok(ctx, query, index) && n_slices >= 2 && n_slices <= 24;
+}
+static bool kz_plain_sweep_shapes_ok(const kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index) {
+    return kz_sweep_operands_ok(ctx, query, index) && kz_h_slices_ok(index->kg);
 }
 
 extern "C" int kz_gold_ranks_sweep(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_begin, int64_t q_count, const kz_matrix* index_c,
@@ -159,7 +178,7 @@ extern "C" int kz_gold_ranks_sweep(kz_ctx* ctx, const kz_matrix* query_c, int64_
     if (q_count == 0) return KZ_OK;
     KZ_HIP(hipSetDevice(ctx->device));
     float ms = 0;
-    if (!kz_rank_sweep_shapes_ok(ctx, query, index)) {   // the whole call on the exact route
+    if (!kz_plain_sweep_shapes_ok(ctx, query, index)) {   // the whole call on the exact route
         KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
         int n_listed = 0;
         const int rc = kz_gold_ranks_impl(who, ctx, query, q_begin, q_count, index, d_gold, nullptr, d_rank, &n_listed);
@@ -233,13 +252,14 @@ extern "C" int kz_gold_ranks_sweep(kz_ctx* ctx, const kz_matrix* query_c, int64_
                        ctx->eps_scale, kz_gamma_acc_h(index->kg), lohi.get(), vg, eps, flag);
     KZ_HIP(hipGetLastError());
     // ---- the sweep: work items of kz_plan.h unchanged (query tile x index range, rounds in lockstep) ---------------------------
-    const KzCountKernel kern = kz_count_lookup(index->kg / 4);
+    const int n_slices = kz_h_nsr(index->kg);   // (the padded count the images are packed with)
+    const KzCountKernel kern = kz_count_lookup(n_slices);
     if (!kern.fn) {
-        kz_set_error("%s: internal: no count kernel for %d slices", who, index->kg / 4);
+        kz_set_error("%s: internal: no count kernel for %d slices", who, n_slices);
         return KZ_ERR_UNSUPPORTED;
     }
     int per_cu = 1;
-    rc = kz_count_occupancy(kern, &per_cu);
+    rc = kz_count_occupancy(ctx, kern, &per_cu);
     if (rc != KZ_OK) return rc;
     const int slots = per_cu * ctx->n_cus;
     KzPlan pl;

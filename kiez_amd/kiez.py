@@ -140,7 +140,7 @@ class Kiez:
         `ind`, numpy object arrays of one array per source row -- by one split on the host.
 
         `route="sweep"` (opt-in, `reduced=False` only): the same result from a sweep of the fp16 MFMA kernels plus the exact values of
-        its candidate pairs (`SklearnNN.radius_neighbors`); its statistics are `algorithm.radius_stats_`.  With `reduced=True` it
+        its candidate pairs (`SklearnNN.radius_neighbors`; 17 <= d <= 384 and 497 <= d <= 2048); its statistics are `algorithm.radius_stats_`.  With `reduced=True` it
         raises NotImplementedError: reduced radii have no sweep yet.  An unknown route raises ValueError."""
         self._checked_radius_route(route, reduced)
         if reduced:
@@ -380,7 +380,7 @@ class Kiez:
         direction: `reduced=True` with `s_to_t=False` raises ValueError.
 
         `route="sweep"` (opt-in, `reduced=False` only): the same ranks from a count sweep of the fp16 MFMA kernels
-        (`SklearnNN.gold_ranks`); its statistics are `algorithm.rank_stats_`.  With `reduced=True` it raises NotImplementedError:
+        (`SklearnNN.gold_ranks`; 17 <= d <= 384 and 497 <= d <= 2048); its statistics are `algorithm.rank_stats_`.  With `reduced=True` it raises NotImplementedError:
         the sweep under a reduction is `kz.hubness.gold_ranks(gold, route="sweep")`.  An unknown route raises ValueError."""
         N.checked_rank_route(route)
         if not reduced:

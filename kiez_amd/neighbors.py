@@ -530,8 +530,8 @@ class SklearnNN(NNAlgorithm):
         ranks into hits@k, MR and MRR.
 
         `route="sweep"` (opt-in): the same ranks from one count sweep of the fp16 MFMA kernels plus the exact values of the pairs it
-        cannot decide (kz_gold_ranks_sweep); what it did -- route taken, band pairs, fallback rows, times -- is `rank_stats_`
-        afterwards.  Any other string raises ValueError."""
+        cannot decide (kz_gold_ranks_sweep; float32 rows of 17 <= d <= 384 or 497 <= d <= 2048, else the exact route whole); what it
+        did -- route taken, band pairs, fallback rows, times -- is `rank_stats_` afterwards.  Any other string raises ValueError."""
         return self.gold_ranks_device(gold, s_to_t, route).numpy()
 
     # ---- every pair within a threshold, whole index ---------------------------------------------------
@@ -579,7 +579,8 @@ class SklearnNN(NNAlgorithm):
 
         `route="sweep"` (opt-in): the same result, byte for byte, from a sweep of the fp16 MFMA kernels that finds the candidate
         pairs plus their exact values (kz_radius_neighbors_sweep); what it did -- route taken, candidates, overflow, times -- is
-        `radius_stats_`.  Shapes outside the sweep take the exact route whole.  An unknown route raises ValueError."""
+        `radius_stats_`.  Shapes outside the sweep (float32 rows of 17 <= d <= 384 or 497 <= d <= 2048) take the exact route whole.
+        An unknown route raises ValueError."""
         indptr, ind, dist = self.radius_neighbors_device(radius, s_to_t, sort_results, route)
         return self._results_to_host(indptr, ind, dist) if return_distance else self._results_to_host(indptr, ind)
 

@@ -10,7 +10,12 @@ context's stream), one warm-up each, the median of five.  The two routes' result
 The stats of every native call of the last timed sweep call are part of the row.  Writes a markdown table (`--out`, default
 profiles/radius_sweep.md) and one JSON line per row (`--jsonl`, default profiles/radius_sweep.jsonl).
 
-    python tools/radius_sweep_time.py [--out FILE] [--jsonl FILE] [--cases small|large|all] [--reps 5]
+    python tools/radius_sweep_time.py [--out FILE] [--jsonl FILE] [--cases small|large|all|wide|wide_small|wide_large] [--reps 5]
+                                      [--per-row 15,50] [--overflow]
+
+`--cases wide`: the text-encoder widths of the wide-row and parity-split sweeps, 15 k x 15 k (`wide_small`) and 100 k x 100 k
+(`wide_large`) at d = 768, 1024, 1536 and 2048.  `--overflow` adds, per shape and metric, a radius of about 90 pairs a row: beyond the
+sweep's log (64 entries a row, at least 2^20), so route="sweep" pays the sweep AND the exact route.
 
 Under `rocprofv3 --kernel-trace --stats -- python tools/radius_sweep_time.py --out /dev/null --jsonl /dev/null --reps 1` the
 per-kernel totals split the sweep route into the emit / count sweep, the two sorts, the resolve, the row kernels and the row sort.
@@ -25,6 +30,9 @@ import numpy as np
 sys.path.insert(0, ".")
 from kiez_amd import _native as N  # noqa: E402
 from tools.whole_index_time import CASES, Events  # noqa: E402
+
+CASES = dict(CASES, wide_small=[(15_000, d) for d in (768, 1024, 1536, 2048)], wide_large=[(100_000, d) for d in (768, 1024, 1536, 2048)])
+CASES["wide"] = CASES["wide_small"] + CASES["wide_large"]
 
 
 def alternated_ms(ev, calls, reps):
@@ -71,6 +79,8 @@ def main():
     ap.add_argument("--jsonl", default="profiles/radius_sweep.jsonl")
     ap.add_argument("--cases", default="all", choices=sorted(CASES))
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--per-row", type=lambda v: [int(x) for x in v.split(",")], default=[15, 50], help="pairs a row of the radii")
+    ap.add_argument("--overflow", action="store_true", help="also a radius whose candidates overflow the sweep's log")
     args = ap.parse_args()
     ctx = N.Context.get()
     ev = Events()
@@ -81,7 +91,7 @@ def main():
         for metric in ("euclidean", "cosine"):
             sm, tm = N.DeviceMatrix(ctx, s, metric), N.DeviceMatrix(ctx, t, metric)
             flat = np.sort(N.knn(ctx, sm, tm, 100)[0].numpy(), axis=None)   # (the pairs within a radius that admits 50 a row: in the lists,
-            for per_row in (15, 50):                                         #  but for hubs with more than 100)
+            for per_row in args.per_row + ([90] if args.overflow else []):   #  but for hubs with more than 100)
                 radius = gap_near(flat, per_row * n)
                 stats = {}
                 exact = N.radius_neighbors(ctx, sm, tm, radius)

@@ -4,9 +4,13 @@ the times are host wall times around one call, best of three after a warm-up.  T
 kz_gold_ranks_reduced on the same matrices and gold ids, once per kind, with arbitrary positive state vectors (the native call takes
 any): `reduced_ms` and the ratio to the plain call.  One JSON line per case.
 
-    python tools/rank_time.py [--out FILE] [--cases small|large|all] [--metric NAME] [--ranks-only] [--route exact|sweep|both] [--gold uniform|correlated]
+    python tools/rank_time.py [--out FILE] [--cases small|large|all|wide] [--metric NAME] [--ranks-only] [--route exact|sweep|both]
+                              [--gold uniform|correlated] [--n ROWS] [--rounds 7] [--no-reduced]
 
-`--route both` (euclidean float32 cases) times gold_ranks(route="exact") and gold_ranks(route="sweep") ALTERNATED in one process -- seven
+`--cases wide`: the text-encoder widths of the wide-row and parity-split count sweeps, 15 k x 15 k and 100 k x 100 k at d = 768, 1024,
+1536 and 2048, euclidean and cosine on the same data (run it with `--route both --ranks-only --no-reduced --rounds 3`).
+
+`--route both` (euclidean and cosine float32 cases) times gold_ranks(route="exact") and gold_ranks(route="sweep") ALTERNATED in one process -- seven
 rounds after a warm-up of each, median and min .. max per route -- checks that the two rank vectors are equal and adds the sweep's
 statistics (kz_rank_sweep_stats: band pairs, fallback rows, max_err_ratio, device times); it does the same for
 gold_ranks_reduced against gold_ranks_reduced_sweep under CSLS and NICDM (`reduced_csls`, `reduced_nicdm`).  `--gold correlated`: the index row of every
@@ -28,6 +32,7 @@ from kiez_amd import _native as N  # noqa: E402
 CASES = {"small": [("euclidean", 15_000, 300), ("manhattan", 15_000, 300), ("jaccard", 15_000, 300)],
          "large": [("euclidean", 100_000, 128)]}
 CASES["all"] = CASES["small"] + CASES["large"]
+CASES["wide"] = [(m, n, d) for n in (15_000, 100_000) for d in (768, 1024, 1536, 2048) for m in ("euclidean", "cosine")]
 
 
 def best_of(fn, ctx, reps=3):
@@ -50,33 +55,42 @@ def main():
     ap.add_argument("--ranks-only", action="store_true", help="skip the kz_knn comparison")
     ap.add_argument("--route", default="exact", choices=["exact", "sweep", "both"])
     ap.add_argument("--gold", default="uniform", choices=["uniform", "correlated"])
+    ap.add_argument("--n", type=int, default=None, help="only the cases of this many rows")
+    ap.add_argument("--rounds", type=int, default=7, help="alternated rounds of --route both")
+    ap.add_argument("--no-reduced", action="store_true", help="skip the kz_gold_ranks_reduced timings")
     args = ap.parse_args()
     ctx = N.Context.get()
     rng = np.random.default_rng(0)
     lines = []
+    shape = None
     for metric, n, d in CASES[args.cases]:
-        if args.metric and metric != args.metric:
+        if (args.metric and metric != args.metric) or (args.n and n != args.n):
             continue
-        if metric == "jaccard":
+        if args.cases == "wide" and shape == (n, d):
+            pass   # (the metrics of a wide shape share its data and gold ids)
+        elif metric == "jaccard":
             s, t = (rng.random((n, d)) < 0.4).astype(np.float32), (rng.random((n, d)) < 0.4).astype(np.float32)
         else:
             s, t = rng.standard_normal((n, d)).astype(np.float32), rng.standard_normal((n, d)).astype(np.float32)
-        gold_ids = rng.integers(0, n, n).astype(np.int64)
-        if args.gold == "correlated" and metric != "jaccard":
-            gold_ids = rng.permutation(n).astype(np.int64)
-            t[gold_ids] = s + 0.05 * rng.standard_normal((n, d)).astype(np.float32)
+        if args.cases != "wide" or shape != (n, d):
+            gold_ids = rng.integers(0, n, n).astype(np.int64)
+            if args.gold == "correlated" and metric != "jaccard":
+                gold_ids = rng.permutation(n).astype(np.int64)
+                t[gold_ids] = s + 0.05 * rng.standard_normal((n, d)).astype(np.float32)
+        shape = (n, d)
         sm, tm = N.DeviceMatrix(ctx, s, metric), N.DeviceMatrix(ctx, t, metric)
         gold = ctx.to_device(gold_ids)
         route = "sweep" if args.route == "sweep" else "exact"
-        rank_ms = best_of(lambda: N.gold_ranks(ctx, sm, tm, gold, route=route), ctx)
-        ranks = N.gold_ranks(ctx, sm, tm, gold, route=route).numpy()
+        keep = []   # (--cases wide: one timed call, whose ranks are kept -- the alternated rounds below are the measurement)
+        rank_ms = best_of(lambda: keep.append(N.gold_ranks(ctx, sm, tm, gold, route=route)), ctx, reps=1 if args.cases == "wide" else 3)
+        ranks = keep[-1].numpy()
         routes = {}
-        if args.route == "both" and metric == "euclidean":
+        if args.route == "both" and metric in ("euclidean", "cosine"):
             times, st = {"exact": [], "sweep": []}, {}
             for r in times:
                 N.gold_ranks(ctx, sm, tm, gold, route=r)
             ctx.sync()
-            for _ in range(7):
+            for _ in range(args.rounds):
                 for r in times:
                     t0 = time.perf_counter()
                     got = N.gold_ranks(ctx, sm, tm, gold, route=r, stats=st if r == "sweep" else None)
@@ -86,7 +100,7 @@ def main():
             routes = {"gold": args.gold, "sweep_stats": st,
                       **{f"{r}_ms": {"median": round(float(np.median(v)), 3), "min": round(min(v), 3), "max": round(max(v), 3)} for r, v in times.items()}}
         reduced = {}
-        if metric == "euclidean":
+        if metric == "euclidean" and not args.no_reduced:
             # (states of the data's own scale: means near the typical distance, deviations a tenth of it)
             scale = float(np.sqrt(2.0 * d))
             q_a, t_a = (ctx.to_device(scale * (0.5 + 0.5 * rng.random(n))) for _ in range(2))
