@@ -8,7 +8,7 @@
 //      (kz_r1_forms below); kz_r1_index_kernel writes the index side (V folded into a copy of the image's bias row, U, per-tile
 //      Umin / Umax), kz_r1_query_kernel the query side {P', Q'} in key units, lowered by the rounding bound;
 //   3. kz_knn_emit_r1_h_kernel (kz_knn_emit_r1_16.h) logs every pair the fp16 tier cannot exclude;
-//   4. the log is ordered by (query row, index row) with the radius sweep's two stable sort passes; kz_r1_resolve_kernel evaluates
+//   4. the log is ordered by (query row, index row) (kz_cert_order_log: two stable sort passes); kz_r1_resolve_kernel evaluates
 //      every entry exactly and checks the bound on it; kz_r1_select_kernel writes each row's k smallest by (w, index row) in
 //      kz_knn_reduced's integer order and checks the row: at least k entries with w <= tau_i, every seed that defined tau_i among them.
 // The WHOLE call takes kz_knn_reduced -- route_taken = 0, never an error -- for a shape outside the sweep (kz_rank_sweep_shapes_ok),
@@ -50,12 +50,12 @@
 // Pad index rows keep bias -inf (U = 0); pad query rows get P' = +inf, Q' = 0.
 #pragma once
 #include "kz_knn_emit_r1_16.h"
+#include "kz_cert_sweep.h"
 
 enum { KZ_R1_F_INVALID = 1, KZ_R1_F_VIOLATED = 2 };
 constexpr int KZ_R1_MAX_K = 128;
 constexpr int KZ_R1_MAX_SEEDS = 1024;
-// Log size: max(64, 4 k) entries per query row, at least 2^20 -- a sizing choice (the radius sweep's, scaled with k), not a tuned number.
-constexpr long long KZ_R1_LOG_MIN = 1ll << 20;
+// (log size: max(KZ_CERT_LOG_PER_ROW, 4 k) entries per query row -- the radius sweep's sizing choice, scaled with k)
 #define KZ_R1_RHO 9.5367431640625e-07 /* 2^-20 */
 
 // Query side (P, Q) from (tau, a); index side (U, V) from b.  EUC: the metric is euclidean (d = sqrt v).
@@ -256,9 +256,7 @@ __global__ __launch_bounds__(256) void kz_r1_query_kernel(int64_t n_rows, int64_
     const double hq = h * Q;
     const double E = eps + eps_mult * ((gamma_acc + 1.1920928955078125e-07 /* 2^-23 */) * W + 1.788139343261719e-07 /* 3 x 2^-24 */ * fabs(hq) * umax);
     const double want = (0.5 * qc2 - h * P - E) / scale;
-    float pf = (float)want;
-    if ((double)pf > want) pf = nextafterf(pf, -INFINITY);
-    pf = nextafterf(pf, -INFINITY);
+    const float pf = kz_round_below(want);
     const float qf = (float)(hq / scale);
     ok = ok && fabs(qs) < (double)INFINITY && fabs(E) < (double)INFINITY && fabsf(pf) < INFINITY && fabsf(qf) < INFINITY;
     e_out[r] = E;
@@ -306,9 +304,7 @@ __global__ __launch_bounds__(256) void kz_r1_resolve_kernel(const i32x2e* __rest
             const double w = kz_rank_reduce<T, KIND, METRIC>(v, mp, q_a[q], 0.0, t_a[j], 0.0);
             const double key = 0.5 * (rowq[(int64_t)q * 3] - (metric == KZ_COSINE ? 2.0 * v : v));
             const double lhs = key + vkey[j] + qd[q] * ud[j];
-            const double ratio = fabs((double)log_key[at] * hscale[1] - lhs) / E[q];
-            if (!(ratio <= 1.0)) atomicOr(flag, KZ_R1_F_VIOLATED);
-            if (ratio == ratio) atomicMax(max_ratio_bits, (unsigned long long)__double_as_longlong(ratio));   // (non-negative: ordered as integers)
+            if (!kz_bound_holds((double)log_key[at] * hscale[1], lhs, E[q], max_ratio_bits)) atomicOr(flag, KZ_R1_F_VIOLATED);
             w_out[e] = w;
             key_out[e] = kz_knnr_key(w);
             idx_out[e] = (int)j;
@@ -328,18 +324,7 @@ __global__ __launch_bounds__(256) void kz_r1_select_kernel(const int* __restrict
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= n_rows) return;   // (wave-uniform)
-    auto lower = [&](int key) {   // the first place whose row key is >= key
-        int lo = 0, hi = n;
-        while (lo < hi) {
-            const int mid = lo + (hi - lo) / 2;
-            if (row_key[mid] < key)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        return lo;
-    };
-    const int a = lower(q), b = lower(q + 1);
+    const int a = kz_run_lower(row_key, n, q), b = kz_run_lower(row_key, n, q + 1);
     const unsigned long long tk = kz_knnr_key(tau[q]);
     int under = 0;   // (uniform)
     for (int e0 = a; e0 < b; e0 += 64) {   // (uniform)
@@ -376,10 +361,6 @@ __global__ __launch_bounds__(256) void kz_r1_select_kernel(const int* __restrict
     if (bad) atomicOr(flag, KZ_R1_F_VIOLATED);
 }
 
-static KzCountKernel kz_emit_r1_lookup(int n_slices) {
-    return n_slices <= KZ_CNT_WPS3_MAX ? kz_emit_r1_lookup_lo(n_slices) : kz_emit_r1_lookup_hi(n_slices);
-}
-
 // (kind, metric) -> f(KzRankC<KIND>, bool_constant<EUC>) for the four rank-one kinds
 template <typename F>
 static void kz_r1_dispatch(int kind, int metric, F f) {
@@ -406,69 +387,38 @@ static int kz_knn_reduced_sweep_run(const char* who, kz_ctx* ctx, kz_matrix* que
     const int n_rows = (int)q_count;
     const double mp = index->mink_p;
     KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-    // ---- the query rows' fp16 image: the query's own when the range is whole, else the rows as a matrix of their own -------------
-    KzPoolBuf<void> sub_raw;
-    KzPoolBuf<int> fl;
-    KzMatrixPtr qsub;
-    kz_matrix* qm = query;
-    int rc = KZ_OK;
-    if (q_begin != 0 || q_count != query->n) {
-        const size_t row_bytes = (size_t)d * 4;
-        rc = sub_raw.alloc(ctx, (size_t)n_rows * row_bytes);
-        if (rc == KZ_OK) rc = fl.alloc(ctx, (size_t)n_rows * sizeof(int));
-        if (rc != KZ_OK) return rc;
-        hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, fl.get(), n_rows);
-        hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_rows), dim3(256), 0, ctx->stream, (const char*)query->raw, (const int*)fl.get(), q_begin, n_rows,
-                           (int64_t)row_bytes, (char*)sub_raw.get(), (int64_t*)nullptr, (const int64_t*)nullptr);
-        KZ_HIP(hipGetLastError());
-        kz_matrix* m = nullptr;
-        rc = kz_matrix_create(ctx, sub_raw.get(), 2, n_rows, d, query->dtype, query->metric, &m);
-        qsub.reset(m);
-        if (rc != KZ_OK) return rc;
-        qm = m;
-    }
-    rc = kz_himage_ensure(qm, index);
+    KzSweepQuery qs;
+    int rc = qs.init(ctx, query, q_begin, n_rows, nullptr, index);
     if (rc != KZ_OK) return rc;
-    const int n_qtiles = (int)qm->n_tiles, n_ytiles = (int)index->n_tiles;
-    const int64_t n_pad = (int64_t)n_qtiles * KZ_TILE, y_pad = (int64_t)n_ytiles * KZ_TILE;
+    const int n_ytiles = (int)index->n_tiles;
+    const int64_t n_pad = qs.n_pad, y_pad = (int64_t)n_ytiles * KZ_TILE;
     // ---- buffers --------------------------------------------------------------------------------------------------------------------
-    size_t mem_free = 0, mem_total = 0;
-    KZ_HIP(hipMemGetInfo(&mem_free, &mem_total));
-    const long long per_row = 4ll * k > 64 ? 4ll * k : 64;
-    long long log_cap = per_row * n_rows > KZ_R1_LOG_MIN ? per_row * n_rows : KZ_R1_LOG_MIN;
-    if (log_cap > (long long)(mem_free / 4 / 12)) log_cap = (long long)(mem_free / 4 / 12);   // (12 bytes an entry, a quarter of what is free)
-    if (log_cap > 0x7ffffffeLL) log_cap = 0x7ffffffeLL;                                       // (the sort's entry count is an int)
     const size_t n_seed = (size_t)n_rows * k_seed;
-    KzPoolBuf<int> ibuf;       // 16 ints: [0..1] log entries, [2..3] max ratio bits, [4] flags, [6..7] max |U|, max |bias'| (float bits)
+    KzSweepLog log;            // counters: [4] flags, [6..7] max |U|, max |bias'| (float bits); no extras
     KzPoolBuf<double> dq;      // tau [n_rows] | E [n_rows] | hQ [n_rows] | seed_w [n_seed]
     KzPoolBuf<double> dy;      // V key [y_pad] | U [y_pad]
     KzPoolBuf<unsigned long long> seed_key;
     KzPoolBuf<float> fy;       // bias' [y_pad] | U [y_pad]
     KzPoolBuf<float2> urange, pq;
-    KzPoolBuf<i32x2e> log_meta;
-    KzPoolBuf<float> log_key;
-    KzPoolBuf<int4> d_work;
-    rc = ibuf.alloc(ctx, 16 * sizeof(int));
+    rc = log.alloc(ctx, 4ll * k > KZ_CERT_LOG_PER_ROW ? 4ll * k : KZ_CERT_LOG_PER_ROW, n_rows, true, 0);
     if (rc == KZ_OK) rc = dq.alloc(ctx, (3 * (size_t)n_rows + n_seed) * sizeof(double));
     if (rc == KZ_OK) rc = dy.alloc(ctx, 2 * (size_t)y_pad * sizeof(double));
     if (rc == KZ_OK) rc = seed_key.alloc(ctx, n_seed * 8);
     if (rc == KZ_OK) rc = fy.alloc(ctx, 2 * (size_t)y_pad * sizeof(float));
     if (rc == KZ_OK) rc = urange.alloc(ctx, (size_t)n_ytiles * sizeof(float2));
     if (rc == KZ_OK) rc = pq.alloc(ctx, (size_t)n_pad * sizeof(float2));
-    if (rc == KZ_OK) rc = log_meta.alloc(ctx, (size_t)log_cap * sizeof(i32x2e) + 8);
-    if (rc == KZ_OK) rc = log_key.alloc(ctx, (size_t)log_cap * sizeof(float) + 4);
     if (rc != KZ_OK) return rc;
-    unsigned long long* counters = (unsigned long long*)ibuf.get();
-    int* flag = ibuf.get() + 4;
-    unsigned* gmax = (unsigned*)(ibuf.get() + 6);
+    unsigned long long* counters = log.counters();
+    int* flag = log.words.get() + 4;
+    unsigned* gmax = (unsigned*)(log.words.get() + 6);
     double *tau = dq.get(), *E = tau + n_rows, *qd = E + n_rows, *seed_w = qd + n_rows;
     double *vkey = dy.get(), *ud = vkey + y_pad;
     float *bias2 = fy.get(), *yu = bias2 + y_pad;
     const float* yraw = (const float*)index->raw;
     const float* qraw = (const float*)query->raw;
-    const kz_himage *qi = qm->himg, *ii = index->himg;
+    const kz_himage *qi = qs.m->himg, *ii = index->himg;
     const double* hscale = (const double*)ii->center->d_scale;
-    hipLaunchKernelGGL(kz_radius_clear_kernel, dim3(1), dim3(256), 0, ctx->stream, ibuf.get(), (int64_t)16);
+    hipLaunchKernelGGL(kz_radius_clear_kernel, dim3(1), dim3(256), 0, ctx->stream, log.words.get(), (int64_t)log.n_words);
     // ---- tau from the seeds; the index side, then the query side of the threshold ---------------------------------------------------
     {
         const long long wgs = ((long long)n_seed + 3) / 4;
@@ -497,116 +447,62 @@ static int kz_knn_reduced_sweep_run(const char* who, kz_ctx* ctx, kz_matrix* que
     KZ_HIP(hipStreamSynchronize(ctx->stream));
     st->n_rows = n_rows;
     if (h_flag) return KZ_OK;
-    // ---- the sweep: work items of kz_plan.h unchanged (query tile x index range, rounds in lockstep) -----------------------------
+    // ---- the sweep ------------------------------------------------------------------------------------------------------------------
     const int n_slices = index->kg / 4;
-    const KzCountKernel kern = kz_emit_r1_lookup(n_slices);
-    if (!kern.fn) {
-        kz_set_error("%s: internal: no sweep kernel for %d slices", who, n_slices);
-        return KZ_ERR_UNSUPPORTED;
-    }
-    int per_cu = 1;
-    rc = kz_count_occupancy(ctx, kern, &per_cu);
+    const KzCountKernel kern = kz_cert_lookup(n_slices, kz_emit_r1_lookup_lo, kz_emit_r1_lookup_hi);
+    KzSweepWork work;
+    rc = kz_cert_plan(who, ctx, kern, "sweep", n_slices, qs.n_qtiles, n_ytiles, &work);
     if (rc != KZ_OK) return rc;
-    const int slots = per_cu * ctx->n_cus;
-    KzPlan pl;
-    kz_plan_pass(n_qtiles, n_ytiles, slots, kz_max_pieces(16, 1), 16, 1, 1, 1, ctx->force_splits, 1, &pl);
-    std::vector<KzWorkItem> hw((size_t)pl.W);   // (pageable: alive until the synchronisation behind the sweep)
-    {
-        const int per_xcd = (slots + 7) / 8;
-        kz_plan_fill_work(pl, n_ytiles, 1, hw.data(), 4 * per_xcd > KZ_QGROUP ? 4 * per_xcd : KZ_QGROUP);
-    }
-    rc = d_work.alloc(ctx, (size_t)pl.W * sizeof(int4));
+    KnnEmitR1Params ep;
+    memset(&ep, 0, sizeof(ep));
+    ep.qpack = (const float*)qi->packed;
+    ep.ypack = (const float*)ii->packed;
+    ep.ybias = bias2;
+    ep.yu = yu;
+    ep.urange = urange.get();
+    ep.work = work.d_work.get();
+    ep.n_ytiles = n_ytiles;
+    ep.pq = pq.get();
+    ep.log_cnt = counters;
+    ep.log_cap = log.cap;
+    ep.log_meta = log.meta.get();
+    ep.log_key = log.key.get();
+    rc = kz_cert_launch(ctx, kern, ep, work.pl.W);
     if (rc != KZ_OK) return rc;
-    KZ_HIP(hipMemcpyAsync(d_work.get(), hw.data(), (size_t)pl.W * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
-    {
-        KnnEmitR1Params ep;
-        memset(&ep, 0, sizeof(ep));
-        ep.qpack = (const float*)qi->packed;
-        ep.ypack = (const float*)ii->packed;
-        ep.ybias = bias2;
-        ep.yu = yu;
-        ep.urange = urange.get();
-        ep.work = d_work.get();
-        ep.n_ytiles = n_ytiles;
-        ep.pq = pq.get();
-        ep.log_cnt = counters;
-        ep.log_cap = log_cap;
-        ep.log_meta = log_meta.get();
-        ep.log_key = log_key.get();
-        void* args[] = {&ep};
-        KZ_HIP(hipLaunchKernel(kern.fn, dim3(pl.W), dim3(256), args, (size_t)kern.lds_bytes, ctx->stream));
-    }
-    KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-    struct {
-        unsigned long long n_log, ratio_bits;
-        int flag, pad;
-    } hc;
-    KZ_HIP(hipMemcpyAsync(&hc, counters, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: the sweep failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
-    float ms = 0;
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    st->sweep_ms = ms;
-    st->n_candidates = (int64_t)hc.n_log;
-    if (hc.n_log > (unsigned long long)log_cap) {
-        st->overflowed = 1;
-        return KZ_OK;
-    }
+    KzSweepCounters hc;
+    rc = kz_cert_sweep_done(ctx, who, log, &hc, st);
+    if (rc != KZ_OK || st->overflowed) return rc;
     const int n = (int)hc.n_log;
     if (n < n_rows) return KZ_OK;   // (fewer entries than rows: some row lacks its own seeds -- the row check would say so)
     // ---- order the log by (query row, index row); exact w of every entry; the k smallest of every row ---------------------------
-    KzPoolBuf<int> ka, kb, pa, pb, idx;
+    KzLogOrder ord;
+    KzPoolBuf<int> idx;
     KzPoolBuf<double> wbuf;
     KzPoolBuf<unsigned long long> kbuf;
-    rc = ka.alloc(ctx, (size_t)n * 4);
-    if (rc == KZ_OK) rc = kb.alloc(ctx, (size_t)n * 4);
-    if (rc == KZ_OK) rc = pa.alloc(ctx, (size_t)n * 4);
-    if (rc == KZ_OK) rc = pb.alloc(ctx, (size_t)n * 4);
+    rc = kz_cert_order_log(ctx, log.meta.get(), n, &ord);
     if (rc == KZ_OK) rc = idx.alloc(ctx, (size_t)n * 4);
     if (rc == KZ_OK) rc = wbuf.alloc(ctx, (size_t)n * 8);
     if (rc == KZ_OK) rc = kbuf.alloc(ctx, (size_t)n * 8);
     if (rc != KZ_OK) return rc;
     {
-        const dim3 grid(kz_blocks(n, 4096)), wg(256);
-        // (kz_radius_sweep.h's scheme: by index row, then, stable, by query row -> kb = row keys, pa = places)
-        hipLaunchKernelGGL(kz_radius_index_keys_kernel, grid, wg, 0, ctx->stream, (const i32x2e*)log_meta.get(), n, ka.get(), pa.get());
-        KZ_HIP(hipGetLastError());
-        rc = kz_sort_pairs_f32_i32(ctx, reinterpret_cast<const float*>(ka.get()), reinterpret_cast<float*>(kb.get()), pa.get(), pb.get(), n, 0);
-        if (rc != KZ_OK) return rc;
-        hipLaunchKernelGGL(kz_radius_row_keys_kernel, grid, wg, 0, ctx->stream, (const i32x2e*)log_meta.get(), n, (const int*)pb.get(), ka.get());
-        KZ_HIP(hipGetLastError());
-        rc = kz_sort_pairs_f32_i32(ctx, reinterpret_cast<const float*>(ka.get()), reinterpret_cast<float*>(kb.get()), pb.get(), pa.get(), n, 0);
-        if (rc != KZ_OK) return rc;
-    }
-    {
         const long long wgs = ((long long)n + 3) / 4;
         kz_rank_dispatch(kind, index, [&](auto t, auto kd, auto mt) {
             hipLaunchKernelGGL((kz_r1_resolve_kernel<typename decltype(t)::type, decltype(kd)::value, decltype(mt)::value>),
-                               dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(256), 0, ctx->stream, (const i32x2e*)log_meta.get(), (const float*)log_key.get(),
-                               (const int*)pa.get(), (long long)n, n_rows, q_begin, qraw, yraw, (const double*)query->sqn, (const double*)index->sqn, index->n, d,
+                               dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(256), 0, ctx->stream, (const i32x2e*)log.meta.get(), (const float*)log.key.get(),
+                               ord.pos(), (long long)n, n_rows, q_begin, qraw, yraw, (const double*)query->sqn, (const double*)index->sqn, index->n, d,
                                metric, mp, d_q_a, d_t_a, (const double*)qi->rowq, hscale, (const double*)E, (const double*)qd, (const double*)vkey,
                                (const double*)ud, flag, counters + 1, wbuf.get(), kbuf.get(), idx.get());
         });
     }
-    hipLaunchKernelGGL(kz_r1_select_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream, (const int*)kb.get(), n, n_rows, k, (const double*)tau,
+    hipLaunchKernelGGL(kz_r1_select_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream, ord.row_key(), n, n_rows, k, (const double*)tau,
                        (const double*)wbuf.get(), (const unsigned long long*)kbuf.get(), (const int*)idx.get(), d_seed,
                        (const unsigned long long*)seed_key.get(), k_seed, flag, d_w, d_ind);
     KZ_HIP(hipGetLastError());
     KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-    KZ_HIP(hipMemcpyAsync(&hc, counters, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: resolving the log failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
+    rc = log.read(ctx, who, "resolving the log", &hc);
+    if (rc != KZ_OK) return rc;
     memcpy(&st->max_err_ratio, &hc.ratio_bits, 8);
+    float ms = 0;
     KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
     st->resolve_ms = ms;
     if (hc.flag) return KZ_OK;   // (a violated bound or row check: nothing of the above is trusted)
@@ -647,15 +543,11 @@ extern "C" int kz_knn_reduced_sweep(kz_ctx* ctx, const kz_matrix* query_c, int64
     }
     if (done) {
         st.route_taken = 1;
-    } else {   // the whole call on the exact route (its time, read-backs included, is fallback_ms)
-        KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-        const int rc = kz_knn_reduced(ctx, query, q_begin, q_count, index, k, kind, d_q_a, d_q_b, d_t_a, d_t_b, d_w, d_ind);
+    } else {
+        const int rc = kz_cert_exact_route(ctx, &st.fallback_ms, [&] {
+            return kz_knn_reduced(ctx, query, q_begin, q_count, index, k, kind, d_q_a, d_q_b, d_t_a, d_t_b, d_w, d_ind);
+        });
         if (rc != KZ_OK) return rc;
-        KZ_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-        KZ_HIP(hipEventSynchronize(ctx->ev[6]));
-        float ms = 0;
-        KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
-        st.fallback_ms = ms;
         st.n_rows = q_count;
     }
     if (stats) *stats = st;

@@ -4,9 +4,12 @@
 //   kz_plan_rounds  -- greedy rounds (which query tiles sweep which index ranges)
 //   kz_plan_pass    -- rounds -> candidate-list layout (regions, pieces, element offsets) + the work table, one item per
 //                      workgroup, in the XCD-aware order the kernels are dispatched in
+//   kz_plan_sweep_work, kz_plan_log_capacity -- the work table and the log size of a certified count / emit sweep (kz_cert_sweep.h)
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #ifndef KZ_TILE
 #define KZ_TILE 128
@@ -179,4 +182,24 @@ static inline void kz_plan_fill_work(const KzPlan& pl, int n_ytiles, int tpw, Kz
             }
         }
     }
+}
+
+// The count and emit sweeps (kz_cert_sweep.h) keep no candidate lists: one plan of single-tile units, the contiguous layout at its
+// smallest entry count (max_pieces = kz_max_pieces(16, 1)), and groups of four times what an XCD holds (their query fragments stay
+// in registers, as the fp16 list kernel's).  hw[pl->W] is the table the kernel reads.
+static inline void kz_plan_sweep_work(int n_qtiles, int n_ytiles, int slots, int max_pieces, int force_splits, KzPlan* pl,
+                                      std::vector<KzWorkItem>* hw) {
+    kz_plan_pass(n_qtiles, n_ytiles, slots, max_pieces, 16, 1, 1, 1, force_splits, 1, pl);
+    hw->assign((size_t)pl->W, KzWorkItem{0, 0, 0, 0});
+    const int per_xcd = (slots + 7) / 8;
+    kz_plan_fill_work(*pl, n_ytiles, 1, hw->data(), 4 * per_xcd > KZ_QGROUP ? 4 * per_xcd : KZ_QGROUP);
+}
+
+// Entries of a sweep's candidate log: per_row a row, at least floor_entries -- sizing choices, not tuned figures -- and at most a
+// quarter of the free memory at 12 bytes an entry; fits_int: the log is sorted, and the sort's entry count is an int.
+static inline long long kz_plan_log_capacity(long long per_row, long long n_rows, long long floor_entries, size_t free_bytes, bool fits_int) {
+    long long cap = per_row * n_rows > floor_entries ? per_row * n_rows : floor_entries;
+    if (cap > (long long)(free_bytes / 4 / 12)) cap = (long long)(free_bytes / 4 / 12);
+    if (fits_int && cap > 0x7ffffffeLL) cap = 0x7ffffffeLL;
+    return cap;
 }

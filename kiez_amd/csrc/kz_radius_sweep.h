@@ -6,8 +6,8 @@
 //      (kz_h_key_eps, kz_range.h) cannot order against the radius;
 //   2a. capacity == 0: kz_knn_count_h_kernel (kz_knn_cnt16.h, unchanged) counts the keys above hi into a count vector and logs the
 //      band; kz_radius_resolve_kernel<false> adds the band entries whose exact w is <= radius;
-//   2b. capacity > 0: kz_knn_emit_h_kernel (kz_knn_emit16.h) logs every key >= lo; the log is ordered by (query row, index row) with
-//      two stable passes of kz_sort_pairs_f32_i32 (kz_lists_combine's scheme); kz_radius_resolve_kernel<true> evaluates every entry
+//   2b. capacity > 0: kz_knn_emit_h_kernel (kz_knn_emit16.h) logs every key >= lo; the log is ordered by (query row, index row)
+//      (kz_cert_order_log, kz_cert_sweep.h: two stable passes of kz_sort_pairs_f32_i32); kz_radius_resolve_kernel<true> evaluates every entry
 //      -- kz_exact_value, kz_output_distance<float>: the bits of the exact route -- and the predicate w <= radius;
 //   3. kz_radius_rows_kernel: one wave per query row finds its run of the ordered log (two binary searches), counts the kept entries
 //      and, in its second launch, writes them at d_indptr[row] + ballot prefix: ascending by index row, no atomics on the output;
@@ -19,7 +19,7 @@
 // norm or interval is not finite: rows of a CSR are not independent the way ranks are, so there is no per-row fallback.
 // Rows of 80 .. 128 slices (d = 1025 .. 2048): both sweeps are builds of kz_knn_cntx_h_kernel (kz_knn_cntx16.h), two workgroups an item.
 #pragma once
-#include "kz_knn_cntx16.h"
+#include "kz_cert_sweep.h"
 
 enum { KZ_RSW_F_NONFINITE = 1, KZ_RSW_F_VIOLATED = 2 };
 
@@ -56,11 +56,7 @@ __global__ __launch_bounds__(256) void kz_radius_band_kernel(int64_t n_rows, int
     }
     const double key_hi = 0.5 * (qc2 - (metric == KZ_COSINE ? 2.0 * v_lo : v_lo)), key_lo = 0.5 * (qc2 - (metric == KZ_COSINE ? 2.0 * v_hi : v_hi));
     const double want_lo = (key_lo - eps) / hscale[1], want_hi = (key_hi + eps) / hscale[1];
-    float lo = (float)want_lo, hi = (float)want_hi;
-    if ((double)lo > want_lo) lo = nextafterf(lo, -INFINITY);
-    lo = nextafterf(lo, -INFINITY);
-    if ((double)hi < want_hi) hi = nextafterf(hi, INFINITY);
-    hi = nextafterf(hi, INFINITY);
+    const float lo = kz_round_below(want_lo), hi = kz_round_above(want_hi);
     const bool ok = fabs(qs) < (double)INFINITY && fabs(eps) < (double)INFINITY && fabsf(lo) < INFINITY && fabsf(hi) < INFINITY;
     if (!ok) {
         lohi[r] = make_float2(INFINITY, INFINITY);
@@ -68,20 +64,6 @@ __global__ __launch_bounds__(256) void kz_radius_band_kernel(int64_t n_rows, int
         return;
     }
     lohi[r] = make_float2(lo, hi);
-}
-
-// Keys of the first sort pass: the index row of every log entry, and the entry's place.
-__global__ __launch_bounds__(256) void kz_radius_index_keys_kernel(const i32x2e* __restrict__ log_meta, int n, int* __restrict__ key, int* __restrict__ pos) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-        key[e] = log_meta[e].y;
-        pos[e] = (int)e;
-    }
-}
-// Keys of the second pass: the query row of the entry the first pass put at place e.
-__global__ __launch_bounds__(256) void kz_radius_row_keys_kernel(const i32x2e* __restrict__ log_meta, int n, const int* __restrict__ pos, int* __restrict__ key) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) key[e] = log_meta[pos[e]].x & ~KZ_EMIT_ABOVE;
 }
 
 // One wave per log entry.  EMIT: place e of the ordered log is entry pos[e] = {query row | above bit, index row, key~}; its exact w
@@ -116,9 +98,7 @@ __global__ __launch_bounds__(256) void kz_radius_resolve_kernel(const i32x2e* __
             const double w = kz_output_distance<float>(v, metric);
             const bool in = w <= radius;   // (NaN: false)
             const double key = 0.5 * (rowq[(int64_t)q * 3] - (metric == KZ_COSINE ? 2.0 * v : v));
-            const double ratio = fabs((double)log_key[at] * hscale[1] - key) / eps[q];
-            if (!(ratio <= 1.0) || (above && !in)) atomicOr(flag, KZ_RSW_F_VIOLATED);
-            if (ratio == ratio) atomicMax(max_ratio_bits, (unsigned long long)__double_as_longlong(ratio));   // (non-negative: ordered as integers)
+            if (!kz_bound_holds((double)log_key[at] * hscale[1], key, eps[q], max_ratio_bits) || (above && !in)) atomicOr(flag, KZ_RSW_F_VIOLATED);
             if (EMIT) {
                 keep[e] = in ? 1 : 0;
                 w_out[e] = w;
@@ -147,18 +127,7 @@ __global__ __launch_bounds__(256) void kz_radius_rows_kernel(const int* __restri
         row_end = indptr[q + 1];
         if (row_end > capacity || row_end == out) return;
     }
-    auto lower = [&](int key) {   // the first place whose row key is >= key
-        int lo = 0, hi = n;
-        while (lo < hi) {
-            const int mid = lo + (hi - lo) / 2;
-            if (row_key[mid] < key)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        return lo;
-    };
-    const int a = lower(q), b = lower(q + 1);
+    const int a = kz_run_lower(row_key, n, q), b = kz_run_lower(row_key, n, q + 1);
     int kept = 0;   // (uniform)
     for (int e0 = a; e0 < b; e0 += 64) {   // (uniform)
         const int e = e0 + lane;
@@ -186,18 +155,8 @@ __global__ __launch_bounds__(256) void kz_radius_clear_kernel(int* __restrict__ 
     if (i < n) words[i] = 0;
 }
 
-static KzCountKernel kz_emit_lookup(int n_slices) {   // (kz_count_lookup's rule)
-    if (n_slices > 64) return kz_emit_lookup_x(n_slices);
-    if (n_slices > 24) return kz_emit_lookup_w(n_slices);
-    return n_slices <= KZ_CNT_WPS3_MAX ? kz_emit_lookup_lo(n_slices) : kz_emit_lookup_hi(n_slices);
-}
-static int kz_emit_launch(kz_ctx* ctx, const KzCountKernel& k, const KnnEmitParams& p, int n_items) {
-    const int rc = kz_raise_lds(ctx, k.fn, k.lds_bytes);
-    if (rc != KZ_OK) return rc;
-    KnnEmitParams pc = p;
-    void* args[] = {&pc};
-    KZ_HIP(hipLaunchKernel(k.fn, dim3(k.wg_per_item * n_items), dim3(256), args, (size_t)k.lds_bytes, ctx->stream));
-    return KZ_OK;
+static KzCountKernel kz_emit_lookup(int n_slices) {
+    return kz_cert_lookup(n_slices, kz_emit_lookup_lo, kz_emit_lookup_hi, kz_emit_lookup_w, kz_emit_lookup_x);
 }
 
 // The sweep route.  *done = 0: nothing the caller may keep was decided (overflow, a violated or non-finite bound) -- the exact route
@@ -210,190 +169,109 @@ static int kz_radius_sweep_run(const char* who, kz_ctx* ctx, kz_matrix* query, i
     const int n_rows = (int)q_count;
     const bool emit = capacity > 0;
     KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-    // ---- the query rows' fp16 image: the query's own when the range is whole, else the rows as a matrix of their own -------------
-    KzPoolBuf<void> sub_raw;
-    KzPoolBuf<int> fl;
-    KzMatrixPtr qsub;
-    kz_matrix* qm = query;
-    int rc = KZ_OK;
-    if (q_begin != 0 || q_count != query->n) {
-        const size_t row_bytes = (size_t)d * 4;
-        rc = sub_raw.alloc(ctx, (size_t)n_rows * row_bytes);
-        if (rc == KZ_OK) rc = fl.alloc(ctx, (size_t)n_rows * sizeof(int));
-        if (rc != KZ_OK) return rc;
-        hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, fl.get(), n_rows);
-        hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_rows), dim3(256), 0, ctx->stream, (const char*)query->raw, (const int*)fl.get(), q_begin, n_rows,
-                           (int64_t)row_bytes, (char*)sub_raw.get(), (int64_t*)nullptr, (const int64_t*)nullptr);
-        KZ_HIP(hipGetLastError());
-        kz_matrix* m = nullptr;
-        rc = kz_matrix_create(ctx, sub_raw.get(), 2, n_rows, d, query->dtype, query->metric, &m);
-        qsub.reset(m);
-        if (rc != KZ_OK) return rc;
-        qm = m;
-    }
-    rc = kz_himage_ensure(qm, index);
+    KzSweepQuery qs;
+    int rc = qs.init(ctx, query, q_begin, n_rows, nullptr, index);
     if (rc != KZ_OK) return rc;
-    const int n_qtiles = (int)qm->n_tiles, n_ytiles = (int)index->n_tiles;
-    const int64_t n_pad = (int64_t)n_qtiles * KZ_TILE;
-    // ---- intervals, counters, the log (sized as kz_rank_sweep.h sizes its own) ---------------------------------------------------
-    size_t mem_free = 0, mem_total = 0;
-    KZ_HIP(hipMemGetInfo(&mem_free, &mem_total));
-    long long log_cap = KZ_RANK_LOG_PER_ROW * n_rows > KZ_RANK_LOG_MIN ? KZ_RANK_LOG_PER_ROW * n_rows : KZ_RANK_LOG_MIN;
-    if (log_cap > (long long)(mem_free / 4 / 12)) log_cap = (long long)(mem_free / 4 / 12);   // (12 bytes an entry, a quarter of what is free)
-    if (log_cap > 0x7ffffffeLL) log_cap = 0x7ffffffeLL;                                       // (the sort's entry count is an int)
+    const int n_ytiles = (int)index->n_tiles;
+    const int64_t n_pad = qs.n_pad;
+    // ---- intervals, counters, the log ---------------------------------------------------------------------------------------------
     KzPoolBuf<float2> lohi;
     KzPoolBuf<double> epsb;     // [n_rows]
-    KzPoolBuf<int> ibuf;        // 16 ints: [0..1] log entries, [2..3] max ratio bits, [4] flags, [8..11] the scan's running base and the
-                                // longest row | the count call: count [n_rows] int64 | band_cnt [n_pad]
+    KzSweepLog log;             // counters: [4] flags, [8..11] the scan's running base and the longest row; extras, the count call:
+                                // count [n_rows] int64 | band_cnt [n_pad]
     KzPoolBuf<int> row_n;       // [n_rows]
-    KzPoolBuf<i32x2e> log_meta;
-    KzPoolBuf<float> log_key;
-    KzPoolBuf<int4> d_work;
-    const size_t n_clear = 16 + (emit ? 0 : (size_t)n_pad + 2 * (size_t)n_rows);
     rc = lohi.alloc(ctx, (size_t)n_pad * sizeof(float2));
     if (rc == KZ_OK) rc = epsb.alloc(ctx, (size_t)n_rows * sizeof(double));
-    if (rc == KZ_OK) rc = ibuf.alloc(ctx, n_clear * sizeof(int));
+    if (rc == KZ_OK) rc = log.alloc(ctx, KZ_CERT_LOG_PER_ROW, n_rows, true, emit ? 0 : (size_t)n_pad + 2 * (size_t)n_rows);
     if (rc == KZ_OK) rc = row_n.alloc(ctx, (size_t)n_rows * sizeof(int));
-    if (rc == KZ_OK) rc = log_meta.alloc(ctx, (size_t)log_cap * sizeof(i32x2e) + 8);
-    if (rc == KZ_OK) rc = log_key.alloc(ctx, (size_t)log_cap * sizeof(float) + 4);
     if (rc != KZ_OK) return rc;
-    unsigned long long* counters = (unsigned long long*)ibuf.get();
-    int* flag = ibuf.get() + 4;
-    int64_t* scan_state = (int64_t*)(ibuf.get() + 8);
-    long long* count = (long long*)(ibuf.get() + 16);
-    int* band_cnt = ibuf.get() + 16 + 2 * (size_t)n_rows;   // (the count kernel's per-row band counter: written, not read here)
-    hipLaunchKernelGGL(kz_radius_clear_kernel, dim3((unsigned)((n_clear + 255) / 256)), dim3(256), 0, ctx->stream, ibuf.get(), (int64_t)n_clear);
-    const kz_himage *qi = qm->himg, *ii = index->himg;
+    unsigned long long* counters = log.counters();
+    int* flag = log.words.get() + 4;
+    int64_t* scan_state = (int64_t*)(log.words.get() + 8);
+    long long* count = (long long*)log.extra();
+    int* band_cnt = log.extra() + 2 * (size_t)n_rows;   // (the count kernel's per-row band counter: written, not read here)
+    hipLaunchKernelGGL(kz_radius_clear_kernel, dim3((unsigned)((log.n_words + 255) / 256)), dim3(256), 0, ctx->stream, log.words.get(), (int64_t)log.n_words);
+    const kz_himage *qi = qs.m->himg, *ii = index->himg;
     hipLaunchKernelGGL(kz_radius_band_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, ctx->stream, (int64_t)n_rows, n_pad, q_begin,
                        (const double*)query->sqn, metric, radius, (const double*)qi->rowq, (const double*)ii->d_max,
                        (const double*)ii->center->d_scale, (const double*)index->d_stats, ctx->eps_scale, kz_gamma_acc_h(index->kg), lohi.get(),
                        epsb.get(), flag);
     KZ_HIP(hipGetLastError());
-    // ---- the sweep: work items of kz_plan.h unchanged (query tile x index range, rounds in lockstep) -----------------------------
+    // ---- the sweep ------------------------------------------------------------------------------------------------------------------
     const int n_slices = kz_h_nsr(index->kg);   // (the padded count the images are packed with)
     const KzCountKernel kern = emit ? kz_emit_lookup(n_slices) : kz_count_lookup(n_slices);
-    if (!kern.fn) {
-        kz_set_error("%s: internal: no sweep kernel for %d slices", who, n_slices);
-        return KZ_ERR_UNSUPPORTED;
-    }
-    int per_cu = 1;
-    rc = kz_count_occupancy(ctx, kern, &per_cu);
+    KzSweepWork work;
+    rc = kz_cert_plan(who, ctx, kern, "sweep", n_slices, qs.n_qtiles, n_ytiles, &work);
     if (rc != KZ_OK) return rc;
-    const int slots = per_cu * ctx->n_cus;
-    KzPlan pl;
-    kz_plan_pass(n_qtiles, n_ytiles, slots, kz_max_pieces(16, 1), 16, 1, 1, 1, ctx->force_splits, 1, &pl);
-    std::vector<KzWorkItem> hw((size_t)pl.W);   // (pageable: alive until the synchronisation behind the sweep)
-    {
-        const int per_xcd = (slots + 7) / 8;
-        kz_plan_fill_work(pl, n_ytiles, 1, hw.data(), 4 * per_xcd > KZ_QGROUP ? 4 * per_xcd : KZ_QGROUP);
-    }
-    rc = d_work.alloc(ctx, (size_t)pl.W * sizeof(int4));
-    if (rc != KZ_OK) return rc;
-    KZ_HIP(hipMemcpyAsync(d_work.get(), hw.data(), (size_t)pl.W * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
     if (emit) {
         KnnEmitParams ep;
         memset(&ep, 0, sizeof(ep));
         ep.qpack = (const float*)qi->packed;
         ep.ypack = (const float*)ii->packed;
         ep.ybias = ii->bias;
-        ep.work = d_work.get();
+        ep.work = work.d_work.get();
         ep.n_ytiles = n_ytiles;
         ep.lohi = lohi.get();
         ep.log_cnt = counters;
-        ep.log_cap = log_cap;
-        ep.log_meta = log_meta.get();
-        ep.log_key = log_key.get();
-        rc = kz_emit_launch(ctx, kern, ep, pl.W);
+        ep.log_cap = log.cap;
+        ep.log_meta = log.meta.get();
+        ep.log_key = log.key.get();
+        rc = kz_cert_launch(ctx, kern, ep, work.pl.W);
     } else {
         // the count kernel as it is: the row list is the identity, the count vector stands where the rank vector stood
-        if (!fl.get()) {
-            rc = fl.alloc(ctx, (size_t)n_rows * sizeof(int));
-            if (rc != KZ_OK) return rc;
-            hipLaunchKernelGGL(kz_iota_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, fl.get(), n_rows);
-        }
         KnnCountParams cp;
         memset(&cp, 0, sizeof(cp));
+        rc = qs.identity(&cp.list);
+        if (rc != KZ_OK) return rc;
         cp.qpack = (const float*)qi->packed;
         cp.ypack = (const float*)ii->packed;
         cp.ybias = ii->bias;
-        cp.work = d_work.get();
+        cp.work = work.d_work.get();
         cp.n_ytiles = n_ytiles;
         cp.lohi = lohi.get();
-        cp.list = fl.get();
         cp.n_list = n_rows;
         cp.rank = count;
         cp.band_cnt = band_cnt;
         cp.log_cnt = counters;
-        cp.log_cap = log_cap;
-        cp.log_meta = log_meta.get();
-        cp.log_key = log_key.get();
-        rc = kz_count_launch(ctx, kern, cp, pl.W);
+        cp.log_cap = log.cap;
+        cp.log_meta = log.meta.get();
+        cp.log_key = log.key.get();
+        rc = kz_cert_launch(ctx, kern, cp, work.pl.W);
     }
     if (rc != KZ_OK) return rc;
-    KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-    struct {
-        unsigned long long n_log, ratio_bits;
-        int flag, pad;
-    } h;
-    KZ_HIP(hipMemcpyAsync(&h, counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: the sweep failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
-    float ms = 0;
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    st->sweep_ms = ms;
+    KzSweepCounters h;
+    rc = kz_cert_sweep_done(ctx, who, log, &h, st);
+    if (rc != KZ_OK) return rc;
     st->n_rows = n_rows;
-    st->n_candidates = (int64_t)h.n_log;
-    if (h.n_log > (unsigned long long)log_cap) {
-        st->overflowed = 1;
-        return KZ_OK;
-    }
-    if (h.flag) return KZ_OK;   // (a non-finite interval)
+    if (st->overflowed || h.flag) return KZ_OK;   // (flag: a non-finite interval)
     // ---- from the log to the CSR ---------------------------------------------------------------------------------------------------
     const int n = (int)h.n_log;
-    KzPoolBuf<int> ka, kb, pa, pb, keep;
+    KzLogOrder ord;
+    KzPoolBuf<int> keep;
     KzPoolBuf<double> wbuf;
     const float* yraw = (const float*)index->raw;
     const float* qraw = (const float*)query->raw;
     if (emit) {
         if (n > 0) {
-            rc = ka.alloc(ctx, (size_t)n * 4);
-            if (rc == KZ_OK) rc = kb.alloc(ctx, (size_t)n * 4);
-            if (rc == KZ_OK) rc = pa.alloc(ctx, (size_t)n * 4);
-            if (rc == KZ_OK) rc = pb.alloc(ctx, (size_t)n * 4);
+            rc = kz_cert_order_log(ctx, log.meta.get(), n, &ord);
             if (rc == KZ_OK) rc = keep.alloc(ctx, (size_t)n * 4);
             if (rc == KZ_OK) rc = wbuf.alloc(ctx, (size_t)n * 8);
             if (rc != KZ_OK) return rc;
-            const dim3 grid(kz_blocks(n, 4096)), wg(256);
-            // by index row: ka = keys, pa = places -> kb, pb   (the sort moves the keys as bit patterns: non-negative ints come back as
-            // they went in, ordered as integers); then, stable, by query row: ka = keys of the places pb -> kb = row keys, pa = places
-            hipLaunchKernelGGL(kz_radius_index_keys_kernel, grid, wg, 0, ctx->stream, (const i32x2e*)log_meta.get(), n, ka.get(), pa.get());
-            KZ_HIP(hipGetLastError());
-            rc = kz_sort_pairs_f32_i32(ctx, reinterpret_cast<const float*>(ka.get()), reinterpret_cast<float*>(kb.get()), pa.get(), pb.get(), n, 0);
-            if (rc != KZ_OK) return rc;
-            hipLaunchKernelGGL(kz_radius_row_keys_kernel, grid, wg, 0, ctx->stream, (const i32x2e*)log_meta.get(), n, (const int*)pb.get(), ka.get());
-            KZ_HIP(hipGetLastError());
-            rc = kz_sort_pairs_f32_i32(ctx, reinterpret_cast<const float*>(ka.get()), reinterpret_cast<float*>(kb.get()), pb.get(), pa.get(), n, 0);
-            if (rc != KZ_OK) return rc;
             const long long wgs = ((long long)n + 3) / 4;
             hipLaunchKernelGGL(kz_radius_resolve_kernel<true>, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(256), 0, ctx->stream,
-                               (const i32x2e*)log_meta.get(), (const float*)log_key.get(), (const int*)pa.get(), (long long)n, n_rows, q_begin, qraw, yraw,
+                               (const i32x2e*)log.meta.get(), (const float*)log.key.get(), ord.pos(), (long long)n, n_rows, q_begin, qraw, yraw,
                                (const double*)query->sqn, (const double*)index->sqn, index->n, d, metric, radius, (const double*)qi->rowq,
                                (const double*)ii->center->d_scale, (const double*)epsb.get(), flag, counters + 1, keep.get(), wbuf.get(),
                                (long long*)nullptr);
         }
-        hipLaunchKernelGGL(kz_radius_rows_kernel<false>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream, (const int*)kb.get(),
-                           (const int*)pa.get(), n, n_rows, (const int*)keep.get(), (const double*)wbuf.get(), (const i32x2e*)log_meta.get(), row_n.get(),
+        hipLaunchKernelGGL(kz_radius_rows_kernel<false>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream, ord.row_key(),
+                           ord.pos(), n, n_rows, (const int*)keep.get(), (const double*)wbuf.get(), (const i32x2e*)log.meta.get(), row_n.get(),
                            (const int64_t*)nullptr, capacity, (int64_t*)nullptr, (double*)nullptr);
     } else {
         if (n > 0) {
             const long long wgs = ((long long)n + 3) / 4;
             hipLaunchKernelGGL(kz_radius_resolve_kernel<false>, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(256), 0, ctx->stream,
-                               (const i32x2e*)log_meta.get(), (const float*)log_key.get(), (const int*)nullptr, (long long)n, n_rows, q_begin, qraw, yraw,
+                               (const i32x2e*)log.meta.get(), (const float*)log.key.get(), (const int*)nullptr, (long long)n, n_rows, q_begin, qraw, yraw,
                                (const double*)query->sqn, (const double*)index->sqn, index->n, d, metric, radius, (const double*)qi->rowq,
                                (const double*)ii->center->d_scale, (const double*)epsb.get(), flag, counters + 1, (int*)nullptr, (double*)nullptr,
                                count);
@@ -403,20 +281,14 @@ static int kz_radius_sweep_run(const char* who, kz_ctx* ctx, kz_matrix* query, i
     }
     hipLaunchKernelGGL(kz_radius_scan_batch_kernel, dim3(1), dim3(256), 0, ctx->stream, (const int*)row_n.get(), 0, n_rows, d_indptr, scan_state);
     if (emit)
-        hipLaunchKernelGGL(kz_radius_rows_kernel<true>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream, (const int*)kb.get(),
-                           (const int*)pa.get(), n, n_rows, (const int*)keep.get(), (const double*)wbuf.get(), (const i32x2e*)log_meta.get(), (int*)nullptr,
+        hipLaunchKernelGGL(kz_radius_rows_kernel<true>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream, ord.row_key(),
+                           ord.pos(), n, n_rows, (const int*)keep.get(), (const double*)wbuf.get(), (const i32x2e*)log.meta.get(), (int*)nullptr,
                            (const int64_t*)d_indptr, capacity, d_ind, d_dist);
     KZ_HIP(hipGetLastError());
     int64_t h_state[2] = {0, 0};   // the total, the longest row
-    KZ_HIP(hipMemcpyAsync(&h, counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     KZ_HIP(hipMemcpyAsync(h_state, scan_state, sizeof(h_state), hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: resolving the log failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
+    rc = log.read(ctx, who, "resolving the log", &h);
+    if (rc != KZ_OK) return rc;
     memcpy(&st->max_err_ratio, &h.ratio_bits, 8);
     if (h.flag) return KZ_OK;   // (a violated bound: nothing of the above is trusted)
     if (sorted && emit && h_state[1] >= 2) {
@@ -434,6 +306,7 @@ static int kz_radius_sweep_run(const char* who, kz_ctx* ctx, kz_matrix* query, i
     }
     KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
     KZ_HIP(hipEventSynchronize(ctx->ev[5]));
+    float ms = 0;
     KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
     st->resolve_ms = ms;
     st->n_pairs = h_state[0];
@@ -465,15 +338,11 @@ extern "C" int kz_radius_neighbors_sweep(kz_ctx* ctx, const kz_matrix* query_c, 
     }
     if (done) {
         st.route_taken = 1;
-    } else {   // the whole call on the exact route (its time, read-backs included, is fallback_ms)
-        KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-        const int rc = kz_radius_impl(who, ctx, query, q_begin, q_count, index, radius, sorted, capacity, nullptr, d_indptr, d_ind, d_dist, h_total);
+    } else {
+        const int rc = kz_cert_exact_route(ctx, &st.fallback_ms, [&] {
+            return kz_radius_impl(who, ctx, query, q_begin, q_count, index, radius, sorted, capacity, nullptr, d_indptr, d_ind, d_dist, h_total);
+        });
         if (rc != KZ_OK) return rc;
-        KZ_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-        KZ_HIP(hipEventSynchronize(ctx->ev[6]));
-        float ms = 0;
-        KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
-        st.fallback_ms = ms;
         st.n_rows = q_count;
         st.n_pairs = *h_total;
     }

@@ -52,6 +52,7 @@
 // the gold pair itself among them (KZ_RANK_F_GOLD_SEEN), which is the row's own check that its band was logged.
 #pragma once
 #include "kz_knn_cnt_r1_16.h"
+#include "kz_cert_sweep.h"
 
 // One workgroup: ext[0] = max |V| in key units (vkey) over the real rows.
 __global__ __launch_bounds__(256) void kz_rank_r1_extent_kernel(const double* __restrict__ vkey, int64_t n_i, double* __restrict__ ext) {
@@ -155,19 +156,11 @@ __global__ __launch_bounds__(256) void kz_rank_r1_query_kernel(const int* __rest
     if (!state_ok) atomicOr(gflag, KZ_R1_F_INVALID);
     double u_good, u_far;
     const double p_hi = kz_r1_inward_p<KIND, EUC>(tau, a, P, Q, umax * (1.0 + 1.1920928955078125e-07 /* 2^-23 */), ext[0] / h, &u_good, &u_far);
-    float ug = (float)u_good, uf = (float)u_far;   // (u_good rounded up, u_far down, one float step further each; -inf stays)
-    if ((double)ug < u_good) ug = nextafterf(ug, INFINITY);
-    ug = nextafterf(ug, INFINITY);
-    if ((double)uf > u_far) uf = nextafterf(uf, -INFINITY);
-    uf = nextafterf(uf, -INFINITY);
+    const float ug = kz_round_above(u_good), uf = kz_round_below(u_far);   // (-inf stays)
     const double hq = h * Q;
     const double E = eps + eps_mult * ((gamma_acc + 1.1920928955078125e-07 /* 2^-23 */) * W + 1.788139343261719e-07 /* 3 x 2^-24 */ * fabs(hq) * umax);
     const double want_lo = (0.5 * qc2 - h * P - E) / scale, want_hi = (0.5 * qc2 - h * p_hi + E) / scale;
-    float lo = (float)want_lo, hi = (float)want_hi;
-    if ((double)lo > want_lo) lo = nextafterf(lo, -INFINITY);
-    lo = nextafterf(lo, -INFINITY);
-    if ((double)hi < want_hi) hi = nextafterf(hi, INFINITY);
-    hi = nextafterf(hi, INFINITY);
+    const float lo = kz_round_below(want_lo), hi = kz_round_above(want_hi);
     const float qf = (float)(hq / scale);
     ok = ok && state_ok && fabs(tau) < (double)INFINITY && fabs(qs) < (double)INFINITY && fabs(E) < (double)INFINITY && fabsf(lo) < INFINITY &&
          fabsf(hi) < INFINITY && fabsf(qf) < INFINITY && lo <= hi;
@@ -209,11 +202,9 @@ __global__ __launch_bounds__(256) void kz_rank_r1_resolve_kernel(const i32x2e* _
             const double w = kz_rank_reduce<T, KIND, METRIC>(v, mp, q_a[row], 0.0, t_a[j], 0.0);
             const double key = 0.5 * (rowq[(int64_t)q * 3] - (metric == KZ_COSINE ? 2.0 * v : v));
             const double lhs = key + vkey[j] + qd[q] * ud[j];
-            const double ratio = fabs((double)log_key[e] * hscale[1] - lhs) / E[q];
             int f = j == g ? KZ_RANK_F_GOLD_SEEN : 0;
-            if (!(ratio <= 1.0)) f |= KZ_RANK_F_VIOLATED;
+            if (!kz_bound_holds((double)log_key[e] * hscale[1], lhs, E[q], max_ratio_bits)) f |= KZ_RANK_F_VIOLATED;
             if (f) atomicOr(flag + q, f);
-            if (ratio == ratio) atomicMax(max_ratio_bits, (unsigned long long)__double_as_longlong(ratio));   // (non-negative: ordered as integers)
             double wgq = wg[q];
             wgq = wgq != wgq ? (double)INFINITY : wgq;
             if (kz_rank_before(w, j, wgq, g)) atomicAdd(reinterpret_cast<unsigned long long*>(rank + row), 1ull);
@@ -221,75 +212,45 @@ __global__ __launch_bounds__(256) void kz_rank_r1_resolve_kernel(const i32x2e* _
     }
 }
 
-static KzCountKernel kz_count_r1_lookup(int n_slices) {
-    return n_slices <= KZ_CNT_WPS3_MAX ? kz_count_r1_lookup_lo(n_slices) : kz_count_r1_lookup_hi(n_slices);
-}
-
 // The sweep route over the compacted list fl [n_list].  *done = 0: a state outside a form's domain -- nothing the caller may keep was
 // decided, the exact route rewrites every output.
 static int kz_gold_ranks_r1_run(const char* who, kz_ctx* ctx, kz_matrix* query, int64_t q_begin, kz_matrix* index, const int64_t* d_gold,
                                 const KzRankReduction& red, const int* fl, int n_list, int64_t* d_rank, kz_rank_sweep_stats* st, int* done) {
     *done = 0;
-    const int d = (int)index->d, metric = index->metric, kind = red.kind;
+    const int d = (int)index->d, metric = index->metric, kind = red.kind, n_ytiles = (int)index->n_tiles;
     const double mp = index->mink_p;
     KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-    // ---- the listed rows as a matrix of their own, its fp16 image beside the index's ------------------------------------------
-    const size_t row_bytes = (size_t)d * 4;
-    KzPoolBuf<void> sub_raw;
-    KzMatrixPtr qsub;
-    int rc = sub_raw.alloc(ctx, (size_t)n_list * row_bytes);
+    KzSweepQuery qs;
+    int rc = qs.init(ctx, query, q_begin, n_list, fl, index);
     if (rc != KZ_OK) return rc;
-    hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_list), dim3(256), 0, ctx->stream, (const char*)query->raw, fl, q_begin, n_list, (int64_t)row_bytes,
-                       (char*)sub_raw.get(), (int64_t*)nullptr, (const int64_t*)nullptr);
-    KZ_HIP(hipGetLastError());
-    {
-        kz_matrix* m = nullptr;
-        rc = kz_matrix_create(ctx, sub_raw.get(), 2, n_list, d, query->dtype, query->metric, &m);
-        qsub.reset(m);
-        if (rc == KZ_OK) rc = kz_himage_ensure(qsub.get(), index);
-        if (rc != KZ_OK) return rc;
-    }
-    const int n_qtiles = (int)qsub->n_tiles, n_ytiles = (int)index->n_tiles;
-    const int64_t n_pad = (int64_t)n_qtiles * KZ_TILE, y_pad = (int64_t)n_ytiles * KZ_TILE;
+    const int64_t n_pad = qs.n_pad, y_pad = (int64_t)n_ytiles * KZ_TILE;
     // ---- buffers --------------------------------------------------------------------------------------------------------------
-    size_t mem_free = 0, mem_total = 0;
-    KZ_HIP(hipMemGetInfo(&mem_free, &mem_total));
-    long long log_cap = KZ_RANK_LOG_PER_ROW * n_list > KZ_RANK_LOG_MIN ? KZ_RANK_LOG_PER_ROW * n_list : KZ_RANK_LOG_MIN;
-    if (log_cap > (long long)(mem_free / 4 / 12)) log_cap = (long long)(mem_free / 4 / 12);   // (12 bytes an entry, a quarter of what is free)
-    KzPoolBuf<int> ibuf;      // 16 ints ([0..1] log entries, [2..3] max ratio bits, [4] state flag, [6..7] max |U|, max |bias'|) | flag [n_pad] | band_cnt [n_pad]
+    KzSweepLog log;           // counters: [4] state flag, [6..7] max |U|, max |bias'|; extras: flag [n_pad] | band_cnt [n_pad]
     KzPoolBuf<double> dq;     // wg [n_list] | E [n_list] | hQ [n_list] | extent [1]
     KzPoolBuf<double> dy;     // V key [y_pad] | U [y_pad]
     KzPoolBuf<float> fy;      // bias' [y_pad] | U [y_pad]
     KzPoolBuf<float2> urange;
     KzPoolBuf<float4> plq;
-    KzPoolBuf<int> fb;        // [n_list + 1]
-    KzPoolBuf<i32x2e> log_meta;
-    KzPoolBuf<float> log_key;
-    KzPoolBuf<int4> d_work;
     KzPoolBuf<KnnCountR1Out> d_out;
-    rc = ibuf.alloc(ctx, (16 + 2 * (size_t)n_pad) * sizeof(int));
+    rc = log.alloc(ctx, KZ_CERT_LOG_PER_ROW, n_list, false, 2 * (size_t)n_pad);
     if (rc == KZ_OK) rc = dq.alloc(ctx, (3 * (size_t)n_list + 1) * sizeof(double));
     if (rc == KZ_OK) rc = dy.alloc(ctx, 2 * (size_t)y_pad * sizeof(double));
     if (rc == KZ_OK) rc = fy.alloc(ctx, 2 * (size_t)y_pad * sizeof(float));
     if (rc == KZ_OK) rc = urange.alloc(ctx, (size_t)n_ytiles * sizeof(float2));
     if (rc == KZ_OK) rc = plq.alloc(ctx, 2 * (size_t)n_pad * sizeof(float4));
-    if (rc == KZ_OK) rc = fb.alloc(ctx, ((size_t)n_list + 1) * sizeof(int));
-    if (rc == KZ_OK) rc = log_meta.alloc(ctx, (size_t)log_cap * sizeof(i32x2e) + 8);
-    if (rc == KZ_OK) rc = log_key.alloc(ctx, (size_t)log_cap * sizeof(float) + 4);
     if (rc == KZ_OK) rc = d_out.alloc(ctx, sizeof(KnnCountR1Out));
     if (rc != KZ_OK) return rc;
-    unsigned long long* counters = (unsigned long long*)ibuf.get();
-    int* gflag = ibuf.get() + 4;
-    unsigned* gmax = (unsigned*)(ibuf.get() + 6);
-    int *flag = ibuf.get() + 16, *band_cnt = flag + n_pad;
+    int* gflag = log.words.get() + 4;
+    unsigned* gmax = (unsigned*)(log.words.get() + 6);
+    int *flag = log.extra(), *band_cnt = flag + n_pad;
     double *wg = dq.get(), *E = wg + n_list, *qd = E + n_list, *ext = qd + n_list;
     double *vkey = dy.get(), *ud = vkey + y_pad;
     float *bias2 = fy.get(), *yu = bias2 + y_pad;
     const float* yraw = (const float*)index->raw;
     const float* qraw = (const float*)query->raw;
-    const kz_himage *qi = qsub->himg, *ii = index->himg;
+    const kz_himage *qi = qs.m->himg, *ii = index->himg;
     const double* hscale = (const double*)ii->center->d_scale;
-    KZ_HIP(hipMemsetAsync(ibuf.get(), 0, (16 + 2 * (size_t)n_pad) * sizeof(int), ctx->stream));
+    KZ_HIP(hipMemsetAsync(log.words.get(), 0, log.n_words * sizeof(int), ctx->stream));
     // ---- the index side, then tau and the two edges of every listed row ---------------------------------------------------------
     kz_r1_dispatch(kind, metric, [&](auto kd, auto euc) {
         hipLaunchKernelGGL((kz_r1_index_kernel<decltype(kd)::value, decltype(euc)::value>), dim3((unsigned)n_ytiles), dim3(128), 0, ctx->stream,
@@ -308,106 +269,47 @@ static int kz_gold_ranks_r1_run(const char* who, kz_ctx* ctx, kz_matrix* query, 
     KZ_HIP(hipMemcpyAsync(&h_flag, gflag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     KZ_HIP(hipStreamSynchronize(ctx->stream));
     if (h_flag) return KZ_OK;
-    // ---- the sweep: work items of kz_plan.h unchanged (query tile x index range, rounds in lockstep) ---------------------------
-    const KzCountKernel kern = kz_count_r1_lookup(index->kg / 4);
-    if (!kern.fn) {
-        kz_set_error("%s: internal: no count kernel for %d slices", who, index->kg / 4);
-        return KZ_ERR_UNSUPPORTED;
-    }
-    int per_cu = 1;
-    rc = kz_count_occupancy(ctx, kern, &per_cu);
+    // ---- the sweep ------------------------------------------------------------------------------------------------------------
+    const int n_slices = index->kg / 4;
+    const KzCountKernel kern = kz_cert_lookup(n_slices, kz_count_r1_lookup_lo, kz_count_r1_lookup_hi);
+    KzSweepWork work;
+    rc = kz_cert_plan(who, ctx, kern, "count", n_slices, qs.n_qtiles, n_ytiles, &work);
     if (rc != KZ_OK) return rc;
-    const int slots = per_cu * ctx->n_cus;
-    KzPlan pl;
-    kz_plan_pass(n_qtiles, n_ytiles, slots, kz_max_pieces(16, 1), 16, 1, 1, 1, ctx->force_splits, 1, &pl);
-    std::vector<KzWorkItem> hw((size_t)pl.W);   // (pageable: alive until the synchronisation behind the sweep)
-    {
-        const int per_xcd = (slots + 7) / 8;
-        kz_plan_fill_work(pl, n_ytiles, 1, hw.data(), 4 * per_xcd > KZ_QGROUP ? 4 * per_xcd : KZ_QGROUP);
-    }
-    rc = d_work.alloc(ctx, (size_t)pl.W * sizeof(int4));
-    if (rc != KZ_OK) return rc;
-    KZ_HIP(hipMemcpyAsync(d_work.get(), hw.data(), (size_t)pl.W * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
     KnnCountR1Out ho;   // (pageable: alive until the synchronisation behind the sweep)
     memset(&ho, 0, sizeof(ho));
     ho.list = fl;
     ho.rank = (long long*)d_rank;
     ho.band_cnt = band_cnt;
-    ho.log_cnt = counters;
-    ho.log_cap = log_cap;
-    ho.log_meta = log_meta.get();
-    ho.log_key = log_key.get();
+    ho.log_cnt = log.counters();
+    ho.log_cap = log.cap;
+    ho.log_meta = log.meta.get();
+    ho.log_key = log.key.get();
     ho.n_list = n_list;
     KZ_HIP(hipMemcpyAsync(d_out.get(), &ho, sizeof(ho), hipMemcpyHostToDevice, ctx->stream));
-    {
-        KnnCountR1Params cp;
-        memset(&cp, 0, sizeof(cp));
-        cp.qpack = (const float*)qi->packed;
-        cp.ypack = (const float*)ii->packed;
-        cp.ybias = bias2;
-        cp.yu = yu;
-        cp.urange = urange.get();
-        cp.work = d_work.get();
-        cp.n_ytiles = n_ytiles;
-        cp.plq = plq.get();
-        cp.out = d_out.get();
-        void* args[] = {&cp};
-        KZ_HIP(hipLaunchKernel(kern.fn, dim3(pl.W), dim3(256), args, (size_t)kern.lds_bytes, ctx->stream));
-    }
-    KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-    unsigned long long n_band = 0;
-    KZ_HIP(hipMemcpyAsync(&n_band, counters, 8, hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: the count sweep failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
+    KnnCountR1Params cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.qpack = (const float*)qi->packed;
+    cp.ypack = (const float*)ii->packed;
+    cp.ybias = bias2;
+    cp.yu = yu;
+    cp.urange = urange.get();
+    cp.work = work.d_work.get();
+    cp.n_ytiles = n_ytiles;
+    cp.plq = plq.get();
+    cp.out = d_out.get();
+    rc = kz_cert_launch(ctx, kern, cp, work.pl.W);
+    if (rc != KZ_OK) return rc;
     // ---- the band, the rows that are not trusted --------------------------------------------------------------------------------
-    const bool over = n_band > (unsigned long long)log_cap;
-    if (!over && n_band > 0) {
-        const long long wgs = ((long long)n_band + 3) / 4;
+    rc = kz_rank_sweep_finish(who, ctx, query, q_begin, index, d_gold, &red, fl, n_list, n_pad, log, d_rank, st, [&](long long n_band, dim3 grid) {
         kz_rank_dispatch(kind, index, [&](auto t, auto kd, auto mt) {
-            hipLaunchKernelGGL((kz_rank_r1_resolve_kernel<typename decltype(t)::type, decltype(kd)::value, decltype(mt)::value>),
-                               dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(256), 0, ctx->stream, (const i32x2e*)log_meta.get(), (const float*)log_key.get(),
-                               (long long)n_band, fl, q_begin, d_gold, qraw, yraw, (const double*)query->sqn, (const double*)index->sqn, index->n, d, metric, mp,
-                               red.q_a, red.t_a, (const double*)qi->rowq, hscale, (const double*)wg, (const double*)E, (const double*)qd, (const double*)vkey,
-                               (const double*)ud, (const int*)band_cnt, flag, counters + 1, d_rank);
+            hipLaunchKernelGGL((kz_rank_r1_resolve_kernel<typename decltype(t)::type, decltype(kd)::value, decltype(mt)::value>), grid, dim3(256), 0, ctx->stream,
+                               (const i32x2e*)log.meta.get(), (const float*)log.key.get(), n_band, fl, q_begin, d_gold, qraw, yraw, (const double*)query->sqn,
+                               (const double*)index->sqn, index->n, d, metric, mp, red.q_a, red.t_a, (const double*)qi->rowq, hscale, (const double*)wg,
+                               (const double*)E, (const double*)qd, (const double*)vkey, (const double*)ud, (const int*)band_cnt, flag, log.counters() + 1,
+                               d_rank);
         });
-    }
-    hipLaunchKernelGGL(kz_rank_fallback_kernel, dim3(1), dim3(256), 0, ctx->stream, fl, n_list, (const int*)flag, (const int*)band_cnt, over ? 1 : 0, fb.get(),
-                       d_rank);
-    KZ_HIP(hipGetLastError());
-    KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-    int n_fb = 0;
-    unsigned long long ratio_bits = 0;
-    KZ_HIP(hipMemcpyAsync(&n_fb, fb.get() + n_list, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(&ratio_bits, counters + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: resolving the band failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
-    if (n_fb > 0) {
-        rc = kz_gold_ranks_walk(who, ctx, query, q_begin, index, d_gold, &red, fb.get(), n_fb, d_rank);
-        if (rc != KZ_OK) return rc;
-    }
-    KZ_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-    KZ_HIP(hipEventSynchronize(ctx->ev[6]));
-    st->n_fallback_rows = n_fb;
-    st->n_sweep_rows = n_list - n_fb;
-    st->n_band_pairs = (int64_t)n_band;
-    memcpy(&st->max_err_ratio, &ratio_bits, 8);
-    float ms = 0;
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    st->sweep_ms = ms;
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
-    st->band_ms = ms;
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
-    st->fallback_ms = ms;
+    });
+    if (rc != KZ_OK) return rc;
     *done = 1;
     return KZ_OK;
 }
@@ -418,47 +320,8 @@ extern "C" int kz_gold_ranks_reduced_sweep(kz_ctx* ctx, const kz_matrix* query_c
     const char* who = "kz_gold_ranks_reduced_sweep";
     kz_matrix* query = const_cast<kz_matrix*>(query_c);
     kz_matrix* index = const_cast<kz_matrix*>(index_c);
-    const int rcp = kz_require_pair(who, ctx, query, q_begin, q_count, index, d_gold, d_rank);
-    if (rcp != KZ_OK) return rcp;
-    const int rcr = kz_rank_require_reduction(who, kind, d_q_a, d_q_b, d_t_a, d_t_b);
-    if (rcr != KZ_OK) return rcr;
-    kz_rank_sweep_stats st;
-    memset(&st, 0, sizeof(st));
-    if (stats) *stats = st;
-    KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "%s: more than 2^31 - 1 rows", who);
-    if (q_count == 0) return KZ_OK;
-    KZ_HIP(hipSetDevice(ctx->device));
     const KzRankReduction red{kind, d_q_a, d_q_b, d_t_a, d_t_b};
-    int done = 0;
-    if (kind != KZ_RANK_MP_NORMAL && kz_rank_sweep_shapes_ok(ctx, query, index)) {
-        // (every buffer is released when the call returns, stream-ordered, behind its last synchronisation)
-        KzPoolBuf<int> fl;
-        int n_list = 0;
-        int rc = kz_rank_compact(ctx, q_count, index, d_gold, d_rank, fl, &n_list);
-        if (rc != KZ_OK) return rc;
-        st.n_rows = n_list;
-        if (n_list == 0) {
-            st.route_taken = 1;
-            if (stats) *stats = st;
-            return KZ_OK;
-        }
-        rc = kz_gold_ranks_r1_run(who, ctx, query, q_begin, index, d_gold, red, fl.get(), n_list, d_rank, &st, &done);
-        if (rc != KZ_OK) return rc;
-    }
-    if (done) {
-        st.route_taken = 1;
-    } else {   // the whole call on the exact route (its time is fallback_ms; no sweep rows, hence no fallback rows)
-        KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-        int n_listed = 0;
-        const int rc = kz_gold_ranks_impl(who, ctx, query, q_begin, q_count, index, d_gold, &red, d_rank, &n_listed);
-        if (rc != KZ_OK) return rc;
-        KZ_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-        KZ_HIP(hipEventSynchronize(ctx->ev[6]));
-        float ms = 0;
-        KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
-        st.fallback_ms = ms;
-        st.n_rows = n_listed;
-    }
-    if (stats) *stats = st;
-    return KZ_OK;
+    return kz_rank_sweep_call(who, ctx, query, q_begin, q_count, index, d_gold, &red, d_rank, stats, [&](const int* fl, int n_list, kz_rank_sweep_stats* st, int* done) {
+        return kz_gold_ranks_r1_run(who, ctx, query, q_begin, index, d_gold, red, fl, n_list, d_rank, st, done);
+    });
 }

@@ -13,13 +13,11 @@
 // Element types: float32 rows run the sweep; float64, float16 and bfloat16 rows take the exact route (the band's values are read by
 // the float32 kernels' rule only, as kz_exact_pairs_kernel's are).
 #pragma once
-#include "kz_knn_cntx16.h"
+#include "kz_cert_sweep.h"
 
-// Sizing choices, not tuned figures: a row whose band holds more entries than this is cheaper on the exact walk than worth arguing
-// about (ties by the thousand, a gold row deep inside a tight cluster); the log holds 64 entries per listed row, at least 2^20.
+// A sizing choice, not a tuned figure: a row whose band holds more entries than this is cheaper on the exact walk than worth arguing
+// about (ties by the thousand, a gold row deep inside a tight cluster).  (The log: KzSweepLog, KZ_CERT_LOG_PER_ROW entries a row.)
 constexpr int KZ_RANK_BAND_ROW_CAP = 1024;
-constexpr long long KZ_RANK_LOG_PER_ROW = 64;
-constexpr long long KZ_RANK_LOG_MIN = 1ll << 20;
 enum { KZ_RANK_F_NONFINITE = 1, KZ_RANK_F_VIOLATED = 2, KZ_RANK_F_GOLD_SEEN = 4 };
 
 // One wave per listed row r (row list[r] of the call): vg [r] the exact value of its gold pair, eps [r] the bound, lohi [r] the
@@ -48,11 +46,7 @@ __global__ __launch_bounds__(256) void kz_rank_band_kernel(const int* __restrict
     const double eps = kz_h_key_eps(rowq + r * 3, y_hmax, ystats, metric == KZ_COSINE ? 0.0 : qsqn[qrow], metric, eps_mult, gamma_acc);
     const double key = 0.5 * (qc2 - (metric == KZ_COSINE ? 2.0 * v : v));
     const double want_lo = (key - eps) / hscale[1], want_hi = (key + eps) / hscale[1];
-    float lo = (float)want_lo, hi = (float)want_hi;
-    if ((double)lo > want_lo) lo = nextafterf(lo, -INFINITY);
-    lo = nextafterf(lo, -INFINITY);
-    if ((double)hi < want_hi) hi = nextafterf(hi, INFINITY);
-    hi = nextafterf(hi, INFINITY);
+    const float lo = kz_round_below(want_lo), hi = kz_round_above(want_hi);
     const bool ok = fabs(v) < (double)INFINITY && fabs(eps) < (double)INFINITY && fabsf(lo) < INFINITY && fabsf(hi) < INFINITY;
     lohi[r] = ok ? make_float2(lo, hi) : make_float2(INFINITY, INFINITY);
     vg[r] = v;
@@ -83,11 +77,9 @@ __global__ __launch_bounds__(256) void kz_rank_resolve_kernel(const i32x2e* __re
         const double v = kz_exact_value<float>(qraw + qrow * (int64_t)d, yraw + j * (int64_t)d, qsqn[qrow], ysqn[j], d, metric, lane);
         if (lane == 0) {   // (every lane holds v; the wave meets again at the next entry's butterfly)
             const double key = 0.5 * (rowq[(int64_t)q * 3] - (metric == KZ_COSINE ? 2.0 * v : v));
-            const double ratio = fabs((double)log_key[e] * hscale[1] - key) / eps[q];
             int f = j == g ? KZ_RANK_F_GOLD_SEEN : 0;
-            if (!(ratio <= 1.0)) f |= KZ_RANK_F_VIOLATED;
+            if (!kz_bound_holds((double)log_key[e] * hscale[1], key, eps[q], max_ratio_bits)) f |= KZ_RANK_F_VIOLATED;
             if (f) atomicOr(flag + q, f);
-            if (ratio == ratio) atomicMax(max_ratio_bits, (unsigned long long)__double_as_longlong(ratio));   // (non-negative: ordered as integers)
             if (kz_rank_before(v, j, vg[q], g)) atomicAdd(reinterpret_cast<unsigned long long*>(rank + row), 1ull);
         }
     }
@@ -121,47 +113,164 @@ __global__ __launch_bounds__(256) void kz_rank_fallback_kernel(const int* __rest
     if (tid == 0) fb[n_list] = base;
 }
 
-// By slice count (kz_h_nsr): lo / hi (2 .. 24), the wide rows (32 .. 64), the parity-split builds (80 .. 128).  A count without a
-// build gets the empty descriptor of the unit that would hold it.
 static KzCountKernel kz_count_lookup(int n_slices) {
-    if (n_slices > 64) return kz_count_lookup_x(n_slices);
-    if (n_slices > 24) return kz_count_lookup_w(n_slices);
-    return n_slices <= KZ_CNT_WPS3_MAX ? kz_count_lookup_lo(n_slices) : kz_count_lookup_hi(n_slices);
+    return kz_cert_lookup(n_slices, kz_count_lookup_lo, kz_count_lookup_hi, kz_count_lookup_w, kz_count_lookup_x);
 }
-// The count kernel's own occupancy query and launcher (beside kz_sweep_occupancy / kz_sweep_launch: it is no entry of kz_sweep_kernel's
-// table, whose contract is "lists of K'").  The builds of 2 .. 24 slices stay below 64 KiB of LDS; the parity-split builds take
-// 97.5 KiB, and BOTH the query and the launch raise the function's limit first (kz_raise_lds: neither depends on the other).
-static int kz_count_occupancy(kz_ctx* ctx, const KzCountKernel& k, int* blocks_per_cu) {
-    const int rc = kz_raise_lds(ctx, k.fn, k.lds_bytes);
+
+// Both rank sweeps behind the launch of their count kernel (words of the log: counters | flag [n_pad] | band_cnt [n_pad]): the band's
+// size, resolve(n_band, workgroups) -- the call's resolve kernel -- unless the log overflowed, the rows that are not trusted through
+// the exact walk (red: the reduction, or null), the statistics.  ev[3] was recorded where the call began.
+template <class Resolve>
+static int kz_rank_sweep_finish(const char* who, kz_ctx* ctx, kz_matrix* query, int64_t q_begin, kz_matrix* index, const int64_t* d_gold,
+                                const KzRankReduction* red, const int* fl, int n_list, int64_t n_pad, const KzSweepLog& log, int64_t* d_rank,
+                                kz_rank_sweep_stats* st, Resolve resolve) {
+    unsigned long long* counters = log.counters();
+    const int *flag = log.extra(), *band_cnt = flag + n_pad;
+    KzPoolBuf<int> fb;   // [n_list + 1]
+    int rc = fb.alloc(ctx, ((size_t)n_list + 1) * sizeof(int));
     if (rc != KZ_OK) return rc;
-    int nb = 0;
-    KZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, 256, k.lds_bytes));
-    *blocks_per_cu = nb < 1 ? 1 : nb;
-    return KZ_OK;
-}
-// n_items work items of the plan: wg_per_item workgroups each
-static int kz_count_launch(kz_ctx* ctx, const KzCountKernel& k, const KnnCountParams& p, int n_items) {
-    const int rc = kz_raise_lds(ctx, k.fn, k.lds_bytes);
+    KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
+    unsigned long long n_band = 0;
+    KZ_HIP(hipMemcpyAsync(&n_band, counters, 8, hipMemcpyDeviceToHost, ctx->stream));
+    rc = kz_cert_sync(ctx, who, "the count sweep");
     if (rc != KZ_OK) return rc;
-    KnnCountParams pc = p;
-    void* args[] = {&pc};
-    KZ_HIP(hipLaunchKernel(k.fn, dim3(k.wg_per_item * n_items), dim3(256), args, (size_t)k.lds_bytes, ctx->stream));
+    const bool over = n_band > (unsigned long long)log.cap;
+    if (!over && n_band > 0) {
+        const long long wgs = ((long long)n_band + 3) / 4;
+        resolve((long long)n_band, dim3((unsigned)(wgs < 65536 ? wgs : 65536)));
+    }
+    hipLaunchKernelGGL(kz_rank_fallback_kernel, dim3(1), dim3(256), 0, ctx->stream, fl, n_list, flag, band_cnt, over ? 1 : 0, fb.get(), d_rank);
+    KZ_HIP(hipGetLastError());
+    KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
+    int n_fb = 0;
+    unsigned long long ratio_bits = 0;
+    KZ_HIP(hipMemcpyAsync(&n_fb, fb.get() + n_list, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(&ratio_bits, counters + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+    rc = kz_cert_sync(ctx, who, "resolving the band");
+    if (rc != KZ_OK) return rc;
+    if (n_fb > 0) {
+        rc = kz_gold_ranks_walk(who, ctx, query, q_begin, index, d_gold, red, fb.get(), n_fb, d_rank);
+        if (rc != KZ_OK) return rc;
+    }
+    KZ_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
+    KZ_HIP(hipEventSynchronize(ctx->ev[6]));
+    st->n_fallback_rows = n_fb;
+    st->n_sweep_rows = n_list - n_fb;
+    st->n_band_pairs = (int64_t)n_band;
+    memcpy(&st->max_err_ratio, &ratio_bits, 8);
+    float ms = 0;
+    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
+    st->sweep_ms = ms;
+    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+    st->band_ms = ms;
+    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
+    st->fallback_ms = ms;
     return KZ_OK;
 }
 
-// Where the sweeps exist.  The rank-one sweeps (kz_rank_r1_sweep.h, kz_knn_reduced_sweep.h) have builds of 2 .. 24 slices; the plain
-// count and emit sweeps (here, kz_radius_sweep.h) of every slice count of the fp16 tier (kz_h_slices_ok: 2 .. 24 and 32 .. 128,
-// d = 17 .. 384 and 497 .. 2048).
-static bool kz_sweep_operands_ok(const kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index) {
-    return !query->pre && !index->pre && ctx->precision != 1 && index->dtype == KZ_F32 && query->dtype == KZ_F32 && index->metric <= KZ_COSINE &&
-           query->kg == index->kg && index->n >= KZ_TILE;
+// The sweep route over the compacted list fl [n_list] (every buffer is released when the call returns, stream-ordered, behind its
+// last synchronisation).  *done = 1: every listed row has its rank.
+static int kz_gold_ranks_sweep_run(const char* who, kz_ctx* ctx, kz_matrix* query, int64_t q_begin, kz_matrix* index, const int64_t* d_gold,
+                                   const int* fl, int n_list, int64_t* d_rank, kz_rank_sweep_stats* st, int* done) {
+    *done = 0;
+    const int d = (int)index->d, metric = index->metric, n_ytiles = (int)index->n_tiles;
+    KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    KzSweepQuery qs;
+    int rc = qs.init(ctx, query, q_begin, n_list, fl, index);
+    if (rc != KZ_OK) return rc;
+    const int64_t n_pad = qs.n_pad;
+    // ---- thresholds, counters, the log ----------------------------------------------------------------------------------------
+    KzPoolBuf<float2> lohi;
+    KzPoolBuf<double> dbuf;   // vg [n_list] | eps [n_list]
+    KzSweepLog log;           // extras: flag [n_pad] | band_cnt [n_pad]
+    rc = lohi.alloc(ctx, (size_t)n_pad * sizeof(float2));
+    if (rc == KZ_OK) rc = dbuf.alloc(ctx, (size_t)n_list * 2 * sizeof(double));
+    if (rc == KZ_OK) rc = log.alloc(ctx, KZ_CERT_LOG_PER_ROW, n_list, false, 2 * (size_t)n_pad);
+    if (rc != KZ_OK) return rc;
+    double *vg = dbuf.get(), *eps = dbuf.get() + n_list;
+    int *flag = log.extra(), *band_cnt = flag + n_pad;
+    KZ_HIP(hipMemsetAsync(log.words.get(), 0, log.n_words * sizeof(int), ctx->stream));
+    const kz_himage *qi = qs.m->himg, *ii = index->himg;
+    hipLaunchKernelGGL(kz_rank_band_kernel, dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, ctx->stream, fl, n_list, n_pad, q_begin, d_gold,
+                       (const float*)query->raw, (const float*)index->raw, (const double*)query->sqn, (const double*)index->sqn, d, metric,
+                       (const double*)qi->rowq, (const double*)ii->d_max, (const double*)ii->center->d_scale, (const double*)index->d_stats,
+                       ctx->eps_scale, kz_gamma_acc_h(index->kg), lohi.get(), vg, eps, flag);
+    KZ_HIP(hipGetLastError());
+    // ---- the sweep ------------------------------------------------------------------------------------------------------------
+    const int n_slices = kz_h_nsr(index->kg);   // (the padded count the images are packed with)
+    const KzCountKernel kern = kz_count_lookup(n_slices);
+    KzSweepWork work;
+    rc = kz_cert_plan(who, ctx, kern, "count", n_slices, qs.n_qtiles, n_ytiles, &work);
+    if (rc != KZ_OK) return rc;
+    KnnCountParams cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.qpack = (const float*)qi->packed;
+    cp.ypack = (const float*)ii->packed;
+    cp.ybias = ii->bias;
+    cp.work = work.d_work.get();
+    cp.n_ytiles = n_ytiles;
+    cp.lohi = lohi.get();
+    cp.list = fl;
+    cp.n_list = n_list;
+    cp.rank = (long long*)d_rank;
+    cp.band_cnt = band_cnt;
+    cp.log_cnt = log.counters();
+    cp.log_cap = log.cap;
+    cp.log_meta = log.meta.get();
+    cp.log_key = log.key.get();
+    rc = kz_cert_launch(ctx, kern, cp, work.pl.W);
+    if (rc != KZ_OK) return rc;
+    // ---- the band, the rows that are not trusted --------------------------------------------------------------------------------
+    rc = kz_rank_sweep_finish(who, ctx, query, q_begin, index, d_gold, nullptr, fl, n_list, n_pad, log, d_rank, st, [&](long long n_band, dim3 grid) {
+        hipLaunchKernelGGL(kz_rank_resolve_kernel, grid, dim3(256), 0, ctx->stream, (const i32x2e*)log.meta.get(), (const float*)log.key.get(), n_band, fl,
+                           q_begin, d_gold, (const float*)query->raw, (const float*)index->raw, (const double*)query->sqn, (const double*)index->sqn,
+                           index->n, d, metric, (const double*)qi->rowq, (const double*)ii->center->d_scale, (const double*)vg, (const double*)eps,
+                           (const int*)band_cnt, flag, log.counters() + 1, d_rank);
+    });
+    if (rc != KZ_OK) return rc;
+    *done = 1;
+    return KZ_OK;
 }
-static bool kz_rank_sweep_shapes_ok(const kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index) {
-    const int n_slices = index->kg / 4;
-    return kz_sweep_operands_ok(ctx, query, index) && n_slices >= 2 && n_slices <= 24;
-}
-static bool kz_plain_sweep_shapes_ok(const kz_ctx* ctx, const kz_matrix* query, const kz_matrix* index) {
-    return kz_sweep_operands_ok(ctx, query, index) && kz_h_slices_ok(index->kg);
+
+// Both rank entry points: the argument checks, the listed rows (kz_rank_compact) through run(fl, n_list, &st, &done) where the sweep
+// serves the call, else -- or with done = 0 -- the whole call on the exact route (its time is fallback_ms; no sweep rows, hence no
+// fallback rows).  red: the reduction of kz_gold_ranks_reduced_sweep, or null.
+template <class Run>
+static int kz_rank_sweep_call(const char* who, kz_ctx* ctx, kz_matrix* query, int64_t q_begin, int64_t q_count, kz_matrix* index,
+                              const int64_t* d_gold, const KzRankReduction* red, int64_t* d_rank, kz_rank_sweep_stats* stats, Run run) {
+    const int rcp = kz_require_pair(who, ctx, query, q_begin, q_count, index, d_gold, d_rank);
+    if (rcp != KZ_OK) return rcp;
+    const int rcr = red ? kz_rank_require_reduction(who, red->kind, red->q_a, red->q_b, red->t_a, red->t_b) : KZ_OK;
+    if (rcr != KZ_OK) return rcr;
+    kz_rank_sweep_stats st;
+    memset(&st, 0, sizeof(st));
+    if (stats) *stats = st;
+    KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "%s: more than 2^31 - 1 rows", who);
+    if (q_count == 0) return KZ_OK;
+    KZ_HIP(hipSetDevice(ctx->device));
+    int done = 0;
+    if (red ? red->kind != KZ_RANK_MP_NORMAL && kz_rank_sweep_shapes_ok(ctx, query, index) : kz_plain_sweep_shapes_ok(ctx, query, index)) {
+        KzPoolBuf<int> fl;
+        int n_list = 0;
+        int rc = kz_rank_compact(ctx, q_count, index, d_gold, d_rank, fl, &n_list);
+        if (rc != KZ_OK) return rc;
+        st.n_rows = n_list;
+        done = n_list == 0;
+        if (!done) rc = run((const int*)fl.get(), n_list, &st, &done);
+        if (rc != KZ_OK) return rc;
+    }
+    if (done) {
+        st.route_taken = 1;
+    } else {
+        int n_listed = 0;
+        const int rc = kz_cert_exact_route(ctx, &st.fallback_ms, [&] {
+            return kz_gold_ranks_impl(who, ctx, query, q_begin, q_count, index, d_gold, red, d_rank, &n_listed);
+        });
+        if (rc != KZ_OK) return rc;
+        st.n_rows = n_listed;
+    }
+    if (stats) *stats = st;
+    return KZ_OK;
 }
 
 extern "C" int kz_gold_ranks_sweep(kz_ctx* ctx, const kz_matrix* query_c, int64_t q_begin, int64_t q_count, const kz_matrix* index_c,
@@ -169,177 +278,7 @@ extern "C" int kz_gold_ranks_sweep(kz_ctx* ctx, const kz_matrix* query_c, int64_
     const char* who = "kz_gold_ranks_sweep";
     kz_matrix* query = const_cast<kz_matrix*>(query_c);
     kz_matrix* index = const_cast<kz_matrix*>(index_c);
-    const int rcp = kz_require_pair(who, ctx, query, q_begin, q_count, index, d_gold, d_rank);
-    if (rcp != KZ_OK) return rcp;
-    kz_rank_sweep_stats st;
-    memset(&st, 0, sizeof(st));
-    if (stats) *stats = st;
-    KZ_REQUIRE(q_count < 0x7fffffff && index->n < 0x7fffffff, "%s: more than 2^31 - 1 rows", who);
-    if (q_count == 0) return KZ_OK;
-    KZ_HIP(hipSetDevice(ctx->device));
-    float ms = 0;
-    if (!kz_plain_sweep_shapes_ok(ctx, query, index)) {   // the whole call on the exact route
-        KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-        int n_listed = 0;
-        const int rc = kz_gold_ranks_impl(who, ctx, query, q_begin, q_count, index, d_gold, nullptr, d_rank, &n_listed);
-        if (rc != KZ_OK) return rc;
-        KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-        KZ_HIP(hipEventSynchronize(ctx->ev[4]));
-        KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-        st.n_rows = n_listed;   // (no sweep rows, hence no fallback rows: the time of the exact route is fallback_ms)
-        st.fallback_ms = ms;
-        if (stats) *stats = st;
-        return KZ_OK;
-    }
-    // (every buffer below is released when the call returns, stream-ordered, behind its last synchronisation)
-    KzPoolBuf<int> fl;
-    int n_list = 0;
-    int rc = kz_rank_compact(ctx, q_count, index, d_gold, d_rank, fl, &n_list);
-    if (rc != KZ_OK) return rc;
-    st.route_taken = 1;
-    st.n_rows = n_list;
-    if (n_list == 0) {
-        if (stats) *stats = st;
-        return KZ_OK;
-    }
-    KZ_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-    // ---- the listed rows as a matrix of their own, its fp16 image beside the index's ------------------------------------------
-    const int d = (int)index->d, metric = index->metric;
-    const size_t row_bytes = (size_t)d * 4;
-    KzPoolBuf<void> sub_raw;
-    KzMatrixPtr qsub;
-    rc = sub_raw.alloc(ctx, (size_t)n_list * row_bytes);
-    if (rc != KZ_OK) return rc;
-    hipLaunchKernelGGL(kz_gather_rows_kernel, dim3(n_list), dim3(256), 0, ctx->stream, (const char*)query->raw, fl.get(), q_begin, n_list, (int64_t)row_bytes,
-                       (char*)sub_raw.get(), (int64_t*)nullptr, (const int64_t*)nullptr);
-    KZ_HIP(hipGetLastError());
-    {
-        kz_matrix* m = nullptr;
-        rc = kz_matrix_create(ctx, sub_raw.get(), 2, n_list, d, query->dtype, query->metric, &m);
-        qsub.reset(m);
-        if (rc == KZ_OK) rc = kz_himage_ensure(qsub.get(), index);
-        if (rc != KZ_OK) return rc;
-    }
-    const int n_qtiles = (int)qsub->n_tiles, n_ytiles = (int)index->n_tiles;
-    const int64_t n_pad = (int64_t)n_qtiles * KZ_TILE;
-    // ---- thresholds, counters, the log ----------------------------------------------------------------------------------------
-    size_t mem_free = 0, mem_total = 0;
-    KZ_HIP(hipMemGetInfo(&mem_free, &mem_total));
-    long long log_cap = KZ_RANK_LOG_PER_ROW * n_list > KZ_RANK_LOG_MIN ? KZ_RANK_LOG_PER_ROW * n_list : KZ_RANK_LOG_MIN;
-    if (log_cap > (long long)(mem_free / 4 / 12)) log_cap = (long long)(mem_free / 4 / 12);   // (12 bytes an entry, a quarter of what is free)
-    KzPoolBuf<float2> lohi;
-    KzPoolBuf<double> dbuf;   // vg [n_list] | eps [n_list]
-    KzPoolBuf<int> ibuf;      // counters (16 ints: [0..1] log entries, [2..3] max ratio bits) | flag [n_pad] | band_cnt [n_pad]
-    KzPoolBuf<int> fb;        // [n_list + 1]
-    KzPoolBuf<i32x2e> log_meta;
-    KzPoolBuf<float> log_key;
-    KzPoolBuf<int4> d_work;
-    rc = lohi.alloc(ctx, (size_t)n_pad * sizeof(float2));
-    if (rc == KZ_OK) rc = dbuf.alloc(ctx, (size_t)n_list * 2 * sizeof(double));
-    if (rc == KZ_OK) rc = ibuf.alloc(ctx, (16 + 2 * (size_t)n_pad) * sizeof(int));
-    if (rc == KZ_OK) rc = fb.alloc(ctx, ((size_t)n_list + 1) * sizeof(int));
-    if (rc == KZ_OK) rc = log_meta.alloc(ctx, (size_t)log_cap * sizeof(i32x2e) + 8);
-    if (rc == KZ_OK) rc = log_key.alloc(ctx, (size_t)log_cap * sizeof(float) + 4);
-    if (rc != KZ_OK) return rc;
-    double *vg = dbuf.get(), *eps = dbuf.get() + n_list;
-    unsigned long long* counters = (unsigned long long*)ibuf.get();
-    int *flag = ibuf.get() + 16, *band_cnt = flag + n_pad;
-    KZ_HIP(hipMemsetAsync(ibuf.get(), 0, (16 + 2 * (size_t)n_pad) * sizeof(int), ctx->stream));
-    const kz_himage *qi = qsub->himg, *ii = index->himg;
-    hipLaunchKernelGGL(kz_rank_band_kernel, dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, ctx->stream, (const int*)fl.get(), n_list, n_pad, q_begin, d_gold,
-                       (const float*)query->raw, (const float*)index->raw, (const double*)query->sqn, (const double*)index->sqn, d, metric,
-                       (const double*)qi->rowq, (const double*)ii->d_max, (const double*)ii->center->d_scale, (const double*)index->d_stats,
-                       ctx->eps_scale, kz_gamma_acc_h(index->kg), lohi.get(), vg, eps, flag);
-    KZ_HIP(hipGetLastError());
-    // ---- the sweep: work items of kz_plan.h unchanged (query tile x index range, rounds in lockstep) ---------------------------
-    const int n_slices = kz_h_nsr(index->kg);   // (the padded count the images are packed with)
-    const KzCountKernel kern = kz_count_lookup(n_slices);
-    if (!kern.fn) {
-        kz_set_error("%s: internal: no count kernel for %d slices", who, n_slices);
-        return KZ_ERR_UNSUPPORTED;
-    }
-    int per_cu = 1;
-    rc = kz_count_occupancy(ctx, kern, &per_cu);
-    if (rc != KZ_OK) return rc;
-    const int slots = per_cu * ctx->n_cus;
-    KzPlan pl;
-    kz_plan_pass(n_qtiles, n_ytiles, slots, kz_max_pieces(16, 1), 16, 1, 1, 1, ctx->force_splits, 1, &pl);
-    std::vector<KzWorkItem> hw((size_t)pl.W);   // (pageable: alive until the synchronisation behind the sweep)
-    {
-        const int per_xcd = (slots + 7) / 8;
-        kz_plan_fill_work(pl, n_ytiles, 1, hw.data(), 4 * per_xcd > KZ_QGROUP ? 4 * per_xcd : KZ_QGROUP);
-    }
-    rc = d_work.alloc(ctx, (size_t)pl.W * sizeof(int4));
-    if (rc != KZ_OK) return rc;
-    KZ_HIP(hipMemcpyAsync(d_work.get(), hw.data(), (size_t)pl.W * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
-    KnnCountParams cp;
-    memset(&cp, 0, sizeof(cp));
-    cp.qpack = (const float*)qi->packed;
-    cp.ypack = (const float*)ii->packed;
-    cp.ybias = ii->bias;
-    cp.work = d_work.get();
-    cp.n_ytiles = n_ytiles;
-    cp.lohi = lohi.get();
-    cp.list = fl.get();
-    cp.n_list = n_list;
-    cp.rank = (long long*)d_rank;
-    cp.band_cnt = band_cnt;
-    cp.log_cnt = counters;
-    cp.log_cap = log_cap;
-    cp.log_meta = log_meta.get();
-    cp.log_key = log_key.get();
-    rc = kz_count_launch(ctx, kern, cp, pl.W);
-    if (rc != KZ_OK) return rc;
-    KZ_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
-    unsigned long long n_band = 0;
-    KZ_HIP(hipMemcpyAsync(&n_band, counters, 8, hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: the count sweep failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
-    // ---- the band, the rows that are not trusted --------------------------------------------------------------------------------
-    const bool over = n_band > (unsigned long long)log_cap;
-    if (!over && n_band > 0) {
-        const long long wgs = ((long long)n_band + 3) / 4;
-        hipLaunchKernelGGL(kz_rank_resolve_kernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(256), 0, ctx->stream, (const i32x2e*)log_meta.get(),
-                           (const float*)log_key.get(), (long long)n_band, (const int*)fl.get(), q_begin, d_gold, (const float*)query->raw,
-                           (const float*)index->raw, (const double*)query->sqn, (const double*)index->sqn, index->n, d, metric, (const double*)qi->rowq,
-                           (const double*)ii->center->d_scale, (const double*)vg, (const double*)eps, (const int*)band_cnt, flag, counters + 1, d_rank);
-    }
-    hipLaunchKernelGGL(kz_rank_fallback_kernel, dim3(1), dim3(256), 0, ctx->stream, (const int*)fl.get(), n_list, (const int*)flag, (const int*)band_cnt,
-                       over ? 1 : 0, fb.get(), d_rank);
-    KZ_HIP(hipGetLastError());
-    KZ_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
-    int n_fb = 0;
-    unsigned long long ratio_bits = 0;
-    KZ_HIP(hipMemcpyAsync(&n_fb, fb.get() + n_list, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(&ratio_bits, counters + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            kz_set_error("%s: resolving the band failed: %s", who, hipGetErrorString(e));
-            return KZ_ERR_HIP;
-        }
-    }
-    if (n_fb > 0) {
-        rc = kz_gold_ranks_walk(who, ctx, query, q_begin, index, d_gold, nullptr, fb.get(), n_fb, d_rank);
-        if (rc != KZ_OK) return rc;
-    }
-    KZ_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-    KZ_HIP(hipEventSynchronize(ctx->ev[6]));
-    st.n_fallback_rows = n_fb;
-    st.n_sweep_rows = n_list - n_fb;
-    st.n_band_pairs = (int64_t)n_band;
-    memcpy(&st.max_err_ratio, &ratio_bits, 8);
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    st.sweep_ms = ms;
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
-    st.band_ms = ms;
-    KZ_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
-    st.fallback_ms = ms;
-    if (stats) *stats = st;
-    return KZ_OK;
+    return kz_rank_sweep_call(who, ctx, query, q_begin, q_count, index, d_gold, nullptr, d_rank, stats, [&](const int* fl, int n_list, kz_rank_sweep_stats* st, int* done) {
+        return kz_gold_ranks_sweep_run(who, ctx, query, q_begin, index, d_gold, fl, n_list, d_rank, st, done);
+    });
 }

@@ -7,6 +7,8 @@
 //   * regions partition the query tiles, end on unit boundaries (wide workgroups), pieces tile the index exactly;
 //   * list offsets of distinct (query row, piece) pairs never overlap and stay inside the element count of the plan;
 //   * items of one XCD label (block id % 8) are consecutive in the logical order.
+// The certified sweeps' work table (kz_plan_sweep_work) gets the coverage check on its own shapes, and their log size
+// (kz_plan_log_capacity) its three bounds.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -75,6 +77,56 @@ static void check(int n_qtiles, int n_ytiles, int slots, int KP, int tpw, int fo
     delete hw;
 }
 
+// The work table of the certified count / emit sweeps (kz_plan_sweep_work): every (query tile, index tile) pair in exactly one
+// item, every item non-empty and inside the shape.
+static void check_sweep_work(int n_qtiles, int n_ytiles, int slots, int force_splits) {
+    const int max_pieces = 128;   // (kz_max_pieces(16, 1))
+    KzPlan pl;
+    std::vector<KzWorkItem>* hw = new std::vector<KzWorkItem>();   // (on the heap, exactly W items: ASan guards both ends)
+    kz_plan_sweep_work(n_qtiles, n_ytiles, slots, max_pieces, force_splits, &pl, hw);
+    CHECK((int)hw->size() == pl.W && pl.W >= 1, "sweep work: %zu items, plan says %d", hw->size(), pl.W);
+    std::vector<unsigned char> cover((size_t)n_qtiles * n_ytiles, 0);
+    for (int i = 0; i < (int)hw->size(); ++i) {
+        const KzWorkItem w = (*hw)[i];
+        const bool ok = w.x >= 0 && w.x < n_qtiles && w.y >= 0 && w.y < w.z && w.z <= n_ytiles;
+        CHECK(ok, "sweep work %d x %d, %d slots, force %d: item %d = {%d, %d, %d}", n_qtiles, n_ytiles, slots, force_splits, i, w.x, w.y, w.z);
+        if (!ok) continue;
+        for (int t = w.y; t < w.z; ++t) ++cover[(size_t)w.x * n_ytiles + t];
+    }
+    for (size_t e = 0; e < cover.size(); ++e)
+        if (cover[e] != 1) {
+            CHECK(false, "sweep work %d x %d, %d slots, force %d: pair (%zu, %zu) covered %d times", n_qtiles, n_ytiles, slots, force_splits,
+                  e / n_ytiles, e % n_ytiles, (int)cover[e]);
+            break;
+        }
+    delete hw;
+}
+
+// The log's capacity (kz_plan_log_capacity): at least the floor unless memory limits it, never above a quarter of the free memory at
+// 12 bytes an entry (free / 48), never above 2^31 - 2 where the count must fit an int.
+static int check_log_capacity() {
+    const long long floor_entries = 1ll << 20, int_max = 0x7ffffffeLL;
+    const size_t gib = (size_t)1 << 30;
+    int n = 0;
+    for (long long per_row : {64ll, 512ll})
+        for (long long n_rows : {1ll, 150ll, 16384ll, 100000ll, 2147483646ll})
+            for (size_t free_bytes : {(size_t)0, (size_t)47, (size_t)48, (size_t)(48 << 20) - 1, gib, 100 * gib, 288 * gib})
+                for (bool fits_int : {false, true}) {
+                    const long long cap = kz_plan_log_capacity(per_row, n_rows, floor_entries, free_bytes, fits_int);
+                    const long long by_mem = (long long)(free_bytes / 48);
+                    const long long want = per_row * n_rows > floor_entries ? per_row * n_rows : floor_entries;
+                    CHECK(cap >= 0 && cap <= by_mem, "log capacity %lld above free / 48 = %lld", cap, by_mem);
+                    CHECK(!fits_int || cap <= int_max, "log capacity %lld does not fit an int", cap);
+                    CHECK(cap <= want, "log capacity %lld above what was asked for, %lld", cap, want);
+                    // below what was asked for only where memory or the int limits it -- then it IS that limit
+                    const long long limit = fits_int && int_max < by_mem ? int_max : by_mem;
+                    CHECK(cap == (want < limit ? want : limit), "log capacity %lld, expected min(%lld, %lld)", cap, want, limit);
+                    CHECK(cap >= floor_entries || cap == by_mem, "log capacity %lld below the floor with %lld entries of memory", cap, by_mem);
+                    ++n;
+                }
+    return n;
+}
+
 int main() {
     unsigned s = 12345;
     auto rnd = [&](int lo, int hi) {
@@ -98,6 +150,14 @@ int main() {
         check(nq, ny, rnd(1, 1024), KPs[rnd(0, 3)], rnd(1, 3), i % 7 == 0 ? rnd(1, 80) : 0, rnd(1, 12));
         ++n;
     }
+    for (int nq : {1, 2, 3, 24, 25, 100})
+        for (int ny : {1, 2, 33, 157, 7813})
+            for (int slots : {256, 512, 768})
+                for (int force : {0, 2, 5}) {
+                    check_sweep_work(nq, ny, slots, force);
+                    ++n;
+                }
+    n += check_log_capacity();
     std::printf("%d plans checked, %d failures\n", n, fails);
     return fails ? 1 : 0;
 }

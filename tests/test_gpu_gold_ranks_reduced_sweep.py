@@ -72,6 +72,32 @@ def test_several_index_ranges_per_query_tile():
     check("csls", "sqeuclidean", 32, n_q=300, n_i=20001)
 
 
+@pytest.mark.parametrize("q_begin,q_count", [(37, 150), (299, 1)])
+def test_row_ranges(q_begin, q_count):
+    """A row range (two query tiles, the second partial; the last row alone): the bytes of the exact route on the same range, the
+    slice of the whole-range result, and the sweep's own route on every row of the range -- a fallback cannot hide a broken range."""
+    from kiez_amd import _native as N
+    ctx = N.Context.get()
+    q, y, gold = make_case(300, 4097, 32, 0)
+    q, y = q.astype(np.float32), y.astype(np.float32)
+    rng = np.random.default_rng(1)
+    mean = numpy_distances(q, y, "euclidean").mean()
+    q_a, t_a = rng.uniform(0.8, 1.2, 300) * mean, rng.uniform(0.5, 2.0, 4097) * mean
+    qm, im = N.DeviceMatrix(ctx, q, "euclidean"), N.DeviceMatrix(ctx, y, "euclidean")
+    dev_gold = lambda g: ctx.to_device(np.where(g < 0, np.iinfo(np.int64).min, g))   # noqa: E731
+    t_state = (ctx.to_device(t_a),)
+    rows = slice(q_begin, q_begin + q_count)
+    assert (gold[rows] >= 0).all()
+    whole = N.gold_ranks_reduced_sweep(ctx, qm, im, dev_gold(gold), KINDS["csls"], (ctx.to_device(q_a),), t_state).numpy()
+    args = (ctx, qm, im, dev_gold(gold[rows]), KINDS["csls"], (ctx.to_device(np.ascontiguousarray(q_a[rows])),), t_state, q_begin, q_count)
+    stats = {}
+    got = N.gold_ranks_reduced_sweep(*args, stats=stats).numpy()
+    print(f"rows [{q_begin}, {q_begin + q_count}): {stats}")
+    assert got.tobytes() == N.gold_ranks_reduced(*args).numpy().tobytes()
+    np.testing.assert_array_equal(got, whole[rows])
+    assert stats["route_taken"] == 1 and stats["n_rows"] == q_count
+
+
 @pytest.mark.parametrize("metric", ["euclidean", "sqeuclidean", "cosine"])
 @pytest.mark.parametrize("kind", ["csls", "ls", "nicdm", "dual"])
 def test_kinds_and_metrics(kind, metric):

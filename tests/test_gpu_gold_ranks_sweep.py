@@ -87,6 +87,26 @@ def test_several_index_ranges_per_query_tile():
     check(300, 20001, 32, "sqeuclidean")
 
 
+@pytest.mark.parametrize("q_begin,q_count", [(37, 150), (299, 1)])
+def test_row_ranges(q_begin, q_count):
+    """A row range (two query tiles, the second partial; the last row alone): the bytes of route="exact" on the same range, the slice
+    of the whole-range result, and the sweep's own route on every row of the range -- a fallback cannot hide a broken range."""
+    from kiez_amd import _native as N
+    ctx = N.Context.get()
+    q, y, gold = make_case(300, 4097, 32, 0)
+    qm, im = N.DeviceMatrix(ctx, q.astype(np.float32), "euclidean"), N.DeviceMatrix(ctx, y.astype(np.float32), "euclidean")
+    dev = lambda g: ctx.to_device(np.where(g < 0, np.iinfo(np.int64).min, g))   # noqa: E731
+    rows = slice(q_begin, q_begin + q_count)
+    assert (gold[rows] >= 0).all()
+    whole = N.gold_ranks(ctx, qm, im, dev(gold), route="sweep").numpy()
+    stats = {}
+    got = N.gold_ranks(ctx, qm, im, dev(gold[rows]), q_begin, q_count, route="sweep", stats=stats).numpy()
+    print(f"rows [{q_begin}, {q_begin + q_count}): {stats}")
+    assert got.tobytes() == N.gold_ranks(ctx, qm, im, dev(gold[rows]), q_begin, q_count).numpy().tobytes()
+    np.testing.assert_array_equal(got, whole[rows])
+    assert stats["route_taken"] == 1 and stats["n_rows"] == q_count
+
+
 @pytest.mark.parametrize("d,metric", [(8, "cosine"), (32, "euclidean"), (100, "sqeuclidean"), (208, "cosine"), (384, "euclidean")])
 def test_widths_and_metrics(d, metric):
     check(256, 4097, d, metric, seed=d)

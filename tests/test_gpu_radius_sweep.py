@@ -120,6 +120,35 @@ def test_query_sizes(n_q):
     check(n_q, 4097, 32, "sqeuclidean", seed=n_q)
 
 
+@pytest.mark.parametrize("q_begin,q_count", [(37, 150), (299, 1)])
+def test_row_ranges(q_begin, q_count):
+    """A row range (two query tiles, the second partial; the last row alone), neighbours for both sort_results and the count-only
+    call: the bytes of route="exact" on the same range, the slice of the whole-range result, and the sweep's own route on every row
+    of the range -- a fallback cannot hide a broken range."""
+    from kiez_amd import _native as N
+    ctx = N.Context.get()
+    q, y = make_case(300, 4097, 32, 0)
+    radius = pick_radius(numpy_distances(q, y, "euclidean"), 8)
+    qm, im = N.DeviceMatrix(ctx, q, "euclidean"), N.DeviceMatrix(ctx, y, "euclidean")
+    for sort_results in (True, False):
+        whole = call(qm, im, radius, "sweep", sort_results=sort_results)
+        lo, hi = whole[0][q_begin], whole[0][q_begin + q_count]
+        stats = {}
+        got = call(qm, im, radius, "sweep", stats, sort_results=sort_results, q_begin=q_begin, q_count=q_count)
+        print(f"rows [{q_begin}, {q_begin + q_count}) sorted={sort_results}: {[{k: c[k] for k in STAT_KEYS} for c in stats['calls']]}")
+        assert_same_bytes(got, call(qm, im, radius, "exact", sort_results=sort_results, q_begin=q_begin, q_count=q_count))
+        np.testing.assert_array_equal(got[0], whole[0][q_begin:q_begin + q_count + 1] - lo)
+        np.testing.assert_array_equal(got[1], whole[1][lo:hi])
+        assert got[2].tobytes() == whole[2][lo:hi].tobytes() and got[3] == hi - lo
+        assert all(c["route_taken"] == 1 and c["n_rows"] == q_count for c in stats["calls"])
+    cstats = {}
+    indptr, n = N.radius_counts(ctx, qm, im, radius, q_begin=q_begin, q_count=q_count, route="sweep", stats=cstats)
+    exact_indptr, exact_n = N.radius_counts(ctx, qm, im, radius, q_begin=q_begin, q_count=q_count)
+    assert indptr.numpy().tobytes() == exact_indptr.numpy().tobytes() and n == exact_n
+    np.testing.assert_array_equal(indptr.numpy(), got[0])
+    assert cstats["route_taken"] == 1 and cstats["n_rows"] == q_count
+
+
 def test_several_index_ranges_per_query_tile():
     from kiez_amd import _native as N
     n, qt, pc, ln = C.c_int(0), (C.c_int * 8)(), (C.c_int * 8)(), (C.c_int * 8)()
